@@ -26,6 +26,13 @@ Extra objects on the JSON line:
   cpu_baseline  the oracle (CPU restatement, "port") timed on the host cores on
                 a bounded sample of the same workload, extrapolated linearly in
                 layers (stated in "sample").
+
+--dump-outputs DIR writes what the last timed step returned to its caller (rank 0),
+for output-by-output comparison of two builds on identical seeded inputs:
+  tokens.npy         (B, prefill + gen) float64: the token ids generate() returned
+  prefix_embeds.npy  (B, P + prompt, 4096) float32: model.embed()'s image prefix + prompt embeddings
+                     (beyond 64 MB in all: prefix_embeds_sample.npy, a fixed seeded sample of it)
+  train_loss.npy     (1,) float64, --train-only: the loss of the last timed training step
 """
 import argparse
 import datetime
@@ -78,6 +85,8 @@ def parse():
     ap.add_argument("--variants", action=argparse.BooleanOptionalAction, default=True,
                     help="N = 1 only: also time BASELINE config[3] (MAGMA_v2: attention + MLP adapters) and the model-native 384^2 "
                          "images as extra objects ('magma_v2', 'generate_res384'); never in 'value'")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64; see the module docstring)")
     args = ap.parse_args()
     if args.fp8 == "off":
         args.fp8 = None
@@ -764,9 +773,11 @@ def main():
     prompt = torch.randint(0, 50256, (B, args.prompt), device=dev, generator=g)
 
     value = ms_step = roof = gen_s = gen_h = gen8 = gen_per_rank = toks = None
+    last = {}                          # what the last step handed back, for --dump-outputs
     if not args.train_only:
         def one_step():
             emb = model.embed([images, prompt])
+            last["prefix_embeds"] = emb
             return model.generate(emb, max_steps=gen, temperature=0.0, decode=False, stop_on_eos=False)
 
         def sync():
@@ -791,6 +802,8 @@ def main():
             dt = float(t)
         ms_step = dt / args.steps * 1e3
         value = world * B * gen / (dt / args.steps)
+        if args.dump_outputs and rank == 0:
+            dumped = dump_outputs(args.dump_outputs, {"tokens": toks.double(), "prefix_embeds": last["prefix_embeds"].float()})
 
         # ---- roofline of the dominant kernel (decode weight streaming), measured live ----
         roof = None
@@ -974,6 +987,10 @@ def main():
         line.update(flat_training_keys(train, world, args))
         if args.train_only:
             line["value"], line["ms_per_step"] = full.get("images_per_s"), full.get("ms_per_step")
+            if args.dump_outputs:
+                if "loss" not in full:
+                    raise SystemExit(f"--dump-outputs: the training step produced no loss: {train}")
+                dumped = dump_outputs(args.dump_outputs, {"train_loss": torch.tensor([full["loss"]], dtype=torch.float64)})
             mf = (line.get("roofline") or {}).get("train")
             if isinstance(mf, dict) and "achieved" in mf:      # the dominant kernel of THIS workload in the contract's own keys
                 line["roofline"].update({"bound": "mfma", "kernel": mf["kernel"], "achieved": mf["achieved"], "peak": mf["peak"],
@@ -983,6 +1000,8 @@ def main():
                 line["config1"] = config1_leg(model, dev)
             except Exception as e:  # noqa: BLE001
                 line["config1"] = {"pass": False, "error": repr(e)[:300]}
+        if args.dump_outputs:
+            line["dumped_outputs"] = dumped
         if not args.no_cpu_baseline:
             # rank 0 only, AFTER the last timed region; at N > 1 the other ranks are parked at the final barrier meanwhile (the
             # process group's timeout is 30 min), so the first multi-GPU record carries its CPU baseline too
@@ -1020,6 +1039,32 @@ def main():
     print(json.dumps(line), flush=True)
     sys.stderr.flush()
     os._exit(0)
+
+
+DUMP_CAP_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Each tensor -> out_dir/<name>.npy (the caller picks float32 / float64); returns {name: shape} for the result line.  When
+    the whole would pass 64 MB, the largest tensor is stored as <name>_sample.npy instead: the elements of its flattened form at a
+    fixed seeded set of positions (sorted), so that two runs with the same arguments store the same positions."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: t.detach().cpu() for k, t in arrays.items()}
+    total = sum(t.numel() * t.element_size() for t in arrays.values())
+    if total + 4096 * len(arrays) > DUMP_CAP_BYTES:
+        name = max(arrays, key=lambda k: arrays[k].numel() * arrays[k].element_size())
+        t = arrays.pop(name)
+        room = DUMP_CAP_BYTES - (total - t.numel() * t.element_size()) - 4096 * (len(arrays) + 1)    # .npy headers
+        n = room // t.element_size()
+        idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:n].sort().values
+        arrays[f"{name}_sample"] = t.reshape(-1)[idx]
+    shapes = {}
+    for name, t in arrays.items():
+        assert t.dtype in (torch.float32, torch.float64), (name, t.dtype)
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.numpy())
+        shapes[name] = list(t.shape)
+    return shapes
 
 
 def _flush_c_stdio():

@@ -12,7 +12,7 @@ imports ``oracle`` and fails loudly when its HIP library is missing.
 
 PARITY PIN STATUS (see DESIGN.md "Oracle"):
   * adapters / sampling filters / build_labels: pinned against the reference's
-    own modules imported from /root/reference (tests/golden/make_golden.py).
+    own modules imported in place (tests/golden/make_golden.py).
   * GPT-J block arithmetic: the reference's implementation lives in the
     un-vendored fork ``finetuneanon/transformers@gpt-neo-localattention3-rp-b``
     (reference setup.py:4).  It is pinned against the independent statement of

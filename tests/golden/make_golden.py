@@ -1,5 +1,5 @@
 """Generates tests/golden/reference_pins.pt by RUNNING the reference's own code
-from /root/reference (read-only) in this container -- nothing is copied:
+from a checkout of the reference MAGMA repository (read-only) -- nothing is copied:
 
   * magma/adapters.py and magma/sampling.py are imported as-is (a 6-line
     annotation-only ``torchtyping`` shim is put in sys.modules first);
@@ -7,7 +7,8 @@ from /root/reference (read-only) in this container -- nothing is copied:
     ``build_labels`` FunctionDef is extracted with ``ast`` and executed in place.
 
 The fixtures pin the oracle (oracle/model.py) and the host-side sampling logic
-(magma_amd/sampling.py) to the reference.  Re-run:  python tests/golden/make_golden.py
+(magma_amd/sampling.py) to the reference.  Re-run:
+    python tests/golden/make_golden.py <path to a checkout of the reference MAGMA repository>
 """
 import ast
 import importlib.util
@@ -17,7 +18,7 @@ import types
 
 import torch
 
-REF = "/root/reference"
+REF = None                  # the reference checkout, from the command line
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "reference_pins.pt")
 
 
@@ -195,4 +196,7 @@ def main():
 
 
 if __name__ == "__main__":
+    if len(sys.argv) != 2 or not os.path.isdir(os.path.join(sys.argv[1], "magma")):
+        sys.exit(__doc__)
+    REF = os.path.abspath(sys.argv[1])
     main()

@@ -3,11 +3,20 @@ GPU, encoder bookkeeping, label oracle edge cases, synthetic data contract."""
 import ctypes
 import os
 import re
+import sys
 
 import pytest
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import reference_cases as RC  # noqa: E402
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+# what the reference's own host-side code returned on the inputs of tests/reference_cases.py, run in place by
+# tests/golden/make_host_golden.py; the published YAMLs it ran on are kept next to it in golden/reference_configs/
+REF_PINS = torch.load(os.path.join(GOLDEN, "reference_host_pins.pt"), weights_only=False)
+REF_CONFIGS = os.path.join(GOLDEN, "reference_configs")
 
 
 def test_configs_parse_like_the_reference():
@@ -19,15 +28,13 @@ def test_configs_parse_like_the_reference():
     v2 = MultimodalConfig.from_yml(os.path.join(ROOT, "configs", "MAGMA_v2.yml"))
     assert set(v2.adapter_config) == {"mlp", "attention"} and v2.adapter_config["attention"]["downsample_factor"] == 8
     assert v2.extra.get("dataset_type") == "new"          # unknown keys are kept, not fatal
-    ref = "/root/reference/configs"
-    if os.path.isdir(ref):                                  # the published YAMLs parse unchanged
-        r1 = MultimodalConfig.from_yml(os.path.join(ref, "MAGMA_v1.yml"))
-        r2 = MultimodalConfig.from_yml(os.path.join(ref, "MAGMA_v2.yml"))
-        for f in ("encoder_name", "adapter_config", "lr", "image_enc_lr", "batch_size", "gradient_accumulation_steps",
-                  "use_image_embed_layernorm", "image_embed_dropout_prob", "image_size", "gradient_clipping"):
-            assert getattr(r1, f) == getattr(v1, f), f
-            assert getattr(r2, f) == getattr(v2, f), f
-        assert set(r2.extra) == {"dataset_type", "vqa_dir", "gqa_dir"}
+    # the published YAMLs (kept as data in tests/golden/reference_configs/) parse unchanged
+    r1 = MultimodalConfig.from_yml(os.path.join(REF_CONFIGS, "MAGMA_v1.yml"))
+    r2 = MultimodalConfig.from_yml(os.path.join(REF_CONFIGS, "MAGMA_v2.yml"))
+    for f in RC.CONFIG_FIELDS:
+        assert getattr(r1, f) == getattr(v1, f), f
+        assert getattr(r2, f) == getattr(v2, f), f
+    assert set(r2.extra) == set(RC.V2_EXTRA_KEYS)
 
 
 def test_library_exports_every_declared_symbol():
@@ -351,272 +358,98 @@ def test_workspace_query_is_consistent_with_the_split_policy():
     assert f(0, 1, 1) == 0
 
 
-def _reference_module(name, rel, stubs=None):
-    """Execute one reference source file IN PLACE (read-only, nothing copied) as module refmagma.<name>: an annotation-only torchtyping
-    shim and, for files with relative imports, stub siblings (reference magma/utils.py itself needs deepspeed / wandb / gdown)."""
-    import importlib.util
-    import sys
-    import types
-    tt = types.ModuleType("torchtyping")
-
-    class TensorType:
-        def __class_getitem__(cls, item):
-            return cls
-    tt.TensorType, tt.patch_typeguard = TensorType, (lambda: None)
-    sys.modules.setdefault("torchtyping", tt)
-    pkg = sys.modules.setdefault("refmagma", types.ModuleType("refmagma"))
-    pkg.__path__ = []
-    for sname, attrs in (stubs or {}).items():
-        m = types.ModuleType(f"refmagma.{sname}")
-        m.__dict__.update(attrs)
-        sys.modules[f"refmagma.{sname}"] = m
-    spec = importlib.util.spec_from_file_location(f"refmagma.{name}", os.path.join("/root/reference", rel))
-    mod = importlib.util.module_from_spec(spec)
-    mod.__package__ = "refmagma"
-    sys.modules[f"refmagma.{name}"] = mod
-    spec.loader.exec_module(mod)
-    return mod
-
-
-needs_reference = pytest.mark.skipif(not os.path.isdir("/root/reference/magma"), reason="the reference tree is only present in the build container")
-
-
-@needs_reference
 def test_config_equals_the_reference_class_run_in_place():
     """reference magma/config.py:20-144 (MultimodalConfig + the derived DeepSpeed dictionary: optimizer, WarmupDecayLR parameters, ZeRO
-    stage, clipping, micro-batch arithmetic) executed in place on the published YAMLs: every dataclass field and the whole derived
-    dictionary equal this repo's MultimodalConfig.  The reference class REJECTS its own MAGMA_v2.yml (three keys that are not fields,
-    SURVEY Q11) -- pinned as well; with those keys dropped the two classes agree on v2 too."""
-    import dataclasses
-    import yaml
+    stage, clipping, micro-batch arithmetic), run in place on the published YAMLs (tests/golden/make_host_golden.py): every dataclass
+    field and the whole derived dictionary equal this repo's MultimodalConfig on the same files.  The reference class REJECTS its own
+    MAGMA_v2.yml (three keys that are not fields) -- pinned as well; with those keys dropped the two classes agree on v2 too."""
     from magma_amd.config import MultimodalConfig
-    ref = _reference_module("config", "magma/config.py", stubs={"utils": {"is_main": lambda: False}})
-    v1 = "/root/reference/configs/MAGMA_v1.yml"
-    r1, m1 = ref.MultimodalConfig.from_yml(v1), MultimodalConfig.from_yml(v1)
-    fields = dataclasses.asdict(r1)
-    assert len(fields) >= 40
-    for k, v in fields.items():
+    pins = REF_PINS["config"]
+    m1 = MultimodalConfig.from_yml(os.path.join(REF_CONFIGS, "MAGMA_v1.yml"))
+    assert len(pins["v1"]) >= 40
+    for k, v in pins["v1"].items():
         if k == "name":                       # a random uuid4 prefix on both sides when the YAML gives none (reference config.py)
             assert isinstance(m1.name, str) and len(m1.name) == len(v)
             continue
         assert getattr(m1, k) == v, k
-    assert r1.deepspeed_config_params == m1.deepspeed_config_params
-    v2 = "/root/reference/configs/MAGMA_v2.yml"
-    with pytest.raises(TypeError):
-        ref.MultimodalConfig.from_yml(v2)
-    raw = yaml.safe_load(open(v2))
-    extra = {k: raw.pop(k) for k in ("dataset_type", "vqa_dir", "gqa_dir")}
-    r2, m2 = ref.MultimodalConfig(**raw), MultimodalConfig.from_yml(v2)
-    for k, v in dataclasses.asdict(r2).items():
+    assert pins["v1_deepspeed"] == m1.deepspeed_config_params
+    assert pins["v2_from_yml_raises"] == "TypeError"
+    m2 = MultimodalConfig.from_yml(os.path.join(REF_CONFIGS, "MAGMA_v2.yml"))
+    for k, v in pins["v2"].items():
         assert k == "name" or getattr(m2, k) == v, k
-    assert r2.deepspeed_config_params == m2.deepspeed_config_params and m2.extra == extra
+    assert pins["v2_deepspeed"] == m2.deepspeed_config_params and m2.extra == pins["v2_extra"]
+    assert set(pins["v2_extra"]) == set(RC.V2_EXTRA_KEYS)
 
 
-@needs_reference
 def test_dataset_equals_the_reference_class_run_in_place(tmp_path):
-    """reference magma/datasets/dataset.py:92-160 (ImgCptDataset over the LazyLoader, collate_fn) executed in place on an on-disk dataset in
-    the reference's layout -- two shards, a record without image_path (path inferred from the record's name), greyscale and RGB
-    images -- with the same tokenizer and transform objects as this repo's reader: same length, same order, identical tensors per
-    item, identical batches from collate_fn (single-caption records: the reference draws the caption with random.choice)."""
-    import json
-    import numpy as np
-    import PIL.Image as I
+    """reference magma/datasets/dataset.py:92-160 (ImgCptDataset over the LazyLoader, collate_fn), run in place by
+    tests/golden/make_host_golden.py on an on-disk dataset in the reference's layout -- two shards, a record without image_path (path
+    inferred from the record's name), greyscale and RGB images -- with the same tokenizer and transform objects as this repo's reader:
+    same length, same order, identical tensors per item, identical batches from collate_fn (single-caption records: the reference
+    draws the caption with random.choice)."""
     from magma_amd.datasets import ImgCptDataset, collate_fn
-    from magma_amd.tokenizer import ByteTokenizer
-    from magma_amd.transforms import clip_preprocess
-    ref = _reference_module("dataset", "magma/datasets/dataset.py")
-    rng = np.random.RandomState(1)
-    n = 0
-    for shard in ("00000", "00001"):
-        (tmp_path / "image_data" / shard).mkdir(parents=True)
-        (tmp_path / "images" / shard).mkdir(parents=True)
-        for i in range(4):
-            grey = (i == 2)
-            arr = (rng.rand(37 + i, 61) * 255).astype("uint8") if grey else (rng.rand(37 + i, 61, 3) * 255).astype("uint8")
-            I.fromarray(arr).save(tmp_path / "images" / shard / f"{i}.jpg")
-            rec = {"captions": [f"a caption for image {shard}/{i}, long enough to be cut"], "metadata": {"n": n}}
-            if i != 1:
-                rec["image_path"] = f"images/{shard}/{i}.jpg"
-            (tmp_path / "image_data" / shard / f"{i}.json").write_text(json.dumps(rec))
-            n += 1
-    tok, tf = ByteTokenizer(40), clip_preprocess(32)
-    theirs = ref.ImgCptDataset(tmp_path, tok, tf, seq_len=40)
-    mine = ImgCptDataset(tmp_path, tok, tf, seq_len=40)
-    assert len(theirs) == len(mine) == 8
-    items_t, items_m = [theirs[i] for i in range(8)], [mine[i] for i in range(8)]
-    for (it, ct), (im, cm) in zip(items_t, items_m):
+    pins = REF_PINS["dataset"]
+    RC.write_dataset(tmp_path)
+    tok, tf = RC.dataset_tokenizer_and_transform()
+    mine = ImgCptDataset(tmp_path, tok, tf, seq_len=RC.DATASET_SEQ_LEN)
+    assert len(pins["items"]) == len(mine) == 8
+    items_m = [mine[i] for i in range(8)]
+    for (it, ct), (im, cm) in zip(pins["items"], items_m):
         assert it.shape == im.shape and torch.equal(it, im)
         assert ct.dtype == cm.dtype and torch.equal(ct, cm)
-    bt, bm = ref.collate_fn(items_t, seq_len=24), collate_fn(items_m, seq_len=24)
-    assert torch.equal(bt[0], bm[0]) and torch.equal(bt[1], bm[1]) and bm[1].shape == (8, 24)
+    bt, bm = pins["collate"], collate_fn(items_m, seq_len=RC.COLLATE_SEQ_LEN)
+    assert torch.equal(bt[0], bm[0]) and torch.equal(bt[1], bm[1]) and bm[1].shape == (8, RC.COLLATE_SEQ_LEN)
 
 
-@needs_reference
 @pytest.mark.parametrize("weight_decay,image_enc_lr,use_ln", [(0.0, 2e-6, True), (0.05, 2e-6, True), (0.05, None, False), (0.0, 2e-6, False)])
 def test_param_groups_equal_the_reference_functions_run_in_place(weight_decay, image_enc_lr, use_ln):
     """reference magma/utils.py:120-238 (get_params_for_weight_decay_optimization + configure_param_groups; utils.py itself needs
-    deepspeed / wandb / gdown, so the two FunctionDefs are extracted with ast and executed in place) on a model with the reference's
-    attribute structure (image_prefix.enc / .proj / .ln, lm with Embedding / LayerNorm / Linear + frozen tensors): the same groups in the
-    same order -- per group the same (lr, weight_decay) and the SAME parameter objects in the same order -- and the same
-    warmup_min_lr / warmup_max_lr lists written into the scheduler parameters."""
-    import ast
-    import copy
-    from collections import defaultdict
-    from types import SimpleNamespace
+    deepspeed / wandb / gdown, so tests/golden/make_host_golden.py extracts the two FunctionDefs with ast and runs them in place) on a
+    model with the reference's attribute structure (image_prefix.enc / .proj / .ln, lm with Embedding / LayerNorm / Linear + frozen
+    tensors): the same groups in the same order -- per group the same (lr, weight_decay) and the same parameters in the same order --
+    and the same warmup_min_lr / warmup_max_lr lists written into the scheduler parameters."""
     from magma_amd.utils import configure_param_groups
-    src = open("/root/reference/magma/utils.py").read()
-    ns = {"torch": torch, "defaultdict": defaultdict}
-    for node in ast.parse(src).body:
-        if isinstance(node, ast.FunctionDef) and node.name in ("get_params_for_weight_decay_optimization", "configure_param_groups"):
-            exec(compile(ast.Module(body=[node], type_ignores=[]), "/root/reference/magma/utils.py", "exec"), ns)
-    nn = torch.nn
-    torch.manual_seed(0)
-    model = nn.Module()
-    model.image_prefix = nn.Module()
-    model.image_prefix.enc = nn.Sequential(nn.Conv2d(3, 4, 3, bias=False), nn.BatchNorm2d(4), nn.Conv2d(4, 4, 1))
-    model.image_prefix.proj = nn.Linear(4, 8)
-    if use_ln:
-        model.image_prefix.ln = nn.LayerNorm(8)
-    model.lm = nn.Sequential(nn.Embedding(11, 8), nn.LayerNorm(8), nn.Linear(8, 8), nn.Sequential(nn.Linear(8, 2), nn.ReLU(), nn.Linear(2, 8)),
-                             nn.Linear(8, 11))
-    for p in list(model.lm[0].parameters()) + list(model.lm[2].parameters()) + list(model.lm[4].parameters()):
-        p.requires_grad_(False)                       # frozen LM, trainable adapters + LayerNorm
-    sched = {"scheduler": {"type": "WarmupDecayLR", "params": {"warmup_min_lr": 0, "warmup_max_lr": 8e-4}}}
-    def cfg():
-        return SimpleNamespace(weight_decay=weight_decay, image_enc_lr=image_enc_lr, use_image_embed_layernorm=use_ln, lr=8e-4, min_lr=1e-7,
-                               deepspeed_config_params=copy.deepcopy(sched))
-    c_ref, c_mine = cfg(), cfg()
-    theirs = ns["configure_param_groups"](model, c_ref)
-    mine = configure_param_groups(model, c_mine)
-    assert len(theirs) == len(mine)
-    for gt, gm in zip(theirs, mine):
-        assert gt.get("lr") == gm.get("lr") and gt.get("weight_decay") == gm.get("weight_decay")
-        assert len(gt["params"]) == len(gm["params"]) and all(a is b for a, b in zip(gt["params"], gm["params"]))
-    assert c_ref.deepspeed_config_params == c_mine.deepspeed_config_params
+    pins = REF_PINS["param_groups"][(weight_decay, image_enc_lr, use_ln)]
+    model = RC.param_group_model(use_ln)
+    cfg = RC.param_group_config(weight_decay, image_enc_lr, use_ln)
+    mine = configure_param_groups(model, cfg)
+    assert all(isinstance(p, torch.nn.Parameter) for g in mine for p in g["params"])
+    assert RC.describe_param_groups(model, mine) == pins["groups"]
+    assert cfg.deepspeed_config_params == pins["deepspeed"]
 
 
-@needs_reference
 @pytest.mark.parametrize("run_blind", [False, True])
-def test_train_and_eval_step_equal_the_reference_functions_run_in_place(monkeypatch, run_blind):
-    """reference magma/train_loop.py:7-21,48-60 (train_step / eval_step) and utils.py:26-34 (reduce_losses) executed in place against a
-    recording engine, next to this repo's train_loop on the same engine and the same loader: the same sequence of engine calls
-    (gradient_accumulation_steps x {forward, backward, step}; eval_steps x forward), the same captions, images zeroed under
-    run_blind, the same returned mean loss.  (The reference moves its batch with .half().cuda(): patched to stay on the host here;
-    this repo's loop moves it to engine.device in bf16 -- the dtype is the documented difference.)"""
-    import ast
-    import sys
-    import types
-    from types import SimpleNamespace
-    import torch.distributed as dist
+def test_train_and_eval_step_equal_the_reference_functions_run_in_place(run_blind):
+    """reference magma/train_loop.py:7-21,48-60 (train_step / eval_step) and utils.py:26-34 (reduce_losses), run in place by
+    tests/golden/make_host_golden.py against a recording engine; this repo's train_loop on the same engine and the same loader: the
+    same sequence of engine calls (gradient_accumulation_steps x {forward, backward, step}; eval_steps x forward), the same captions,
+    images zeroed under run_blind, the same returned mean loss.  (The reference moves its batch with .half().cuda(), kept on the host
+    for the pins; this repo's loop moves it to engine.device in bf16 -- the dtype is the documented difference.)"""
     from magma_amd import train_loop as mine
-    ns = {"torch": torch, "dist": dist}
-    for node in ast.parse(open("/root/reference/magma/utils.py").read()).body:
-        if isinstance(node, ast.FunctionDef) and node.name == "reduce_losses":
-            exec(compile(ast.Module(body=[node], type_ignores=[]), "/root/reference/magma/utils.py", "exec"), ns)
-    tv, tvu = types.ModuleType("torchvision"), types.ModuleType("torchvision.utils")
-    tvu.make_grid = lambda *a, **k: None
-    tv.utils = tvu
-    monkeypatch.setitem(sys.modules, "torchvision", tv)
-    monkeypatch.setitem(sys.modules, "torchvision.utils", tvu)
-    ref = _reference_module("train_loop", "magma/train_loop.py",
-                            stubs={"utils": {"reduce_losses": ns["reduce_losses"], "to_cuda_half": lambda *a: a}})
-    monkeypatch.setattr(torch.Tensor, "cuda", lambda self, *a, **k: self)
-
-    class Engine:
-        device = torch.device("cpu")
-
-        def __init__(self):
-            self.events, self.n = [], 0
-
-        def __call__(self, images, captions, **kw):
-            self.n += 1
-            self.events.append(("forward", tuple(images.shape), float(images.float().abs().sum()) == 0.0, captions.clone()))
-            return SimpleNamespace(loss=torch.tensor(float(self.n) * 0.5))
-
-        def backward(self, loss):
-            self.events.append(("backward", float(loss)))
-
-        def step(self):
-            self.events.append(("step",))
-
-    def loader():
-        g = torch.Generator().manual_seed(3)
-        while True:
-            yield torch.rand(2, 3, 8, 8, generator=g) + 0.1, torch.randint(0, 50, (2, 16), generator=g)
-
-    config = SimpleNamespace(gradient_accumulation_steps=3, eval_steps=2, run_blind=run_blind)
-    for fn_ref, fn_mine, n_calls in ((ref.train_step, mine.train_step, 3), (ref.eval_step, mine.eval_step, 2)):
-        e_ref, e_mine = Engine(), Engine()
-        l_ref = fn_ref(config, loader(), e_ref)
-        l_mine = fn_mine(config, loader(), e_mine)
-        assert float(l_mine) == pytest.approx(float(l_ref)) == pytest.approx(sum(0.5 * (i + 1) for i in range(n_calls)) / n_calls)
-        assert [ev[0] for ev in e_ref.events] == [ev[0] for ev in e_mine.events]
-        for a, b in zip(e_ref.events, e_mine.events):
+    for fn_mine, name, n_calls in ((mine.train_step, "train_step", 3), (mine.eval_step, "eval_step", 2)):
+        pin = REF_PINS["steps"][(run_blind, name)]
+        e_mine = RC.RecordingEngine()
+        l_mine = fn_mine(RC.step_config(run_blind), RC.step_loader(), e_mine)
+        assert float(l_mine) == pytest.approx(pin["loss"]) == pytest.approx(sum(0.5 * (i + 1) for i in range(n_calls)) / n_calls)
+        assert [ev[0] for ev in pin["events"]] == [ev[0] for ev in e_mine.events]
+        for a, b in zip(pin["events"], e_mine.events):
             if a[0] == "forward":
                 assert a[1] == b[1] and a[2] == b[2] == run_blind and torch.equal(a[3], b[3])
             else:
                 assert a == b
 
 
-@needs_reference
 def test_checkpoint_helpers_equal_the_reference_functions_run_in_place(tmp_path):
     """reference magma/utils.py:89-117 (save_model / load_model) and :285-308 (infer_checkpoint_path_from_config), extracted with ast and
-    executed in place, next to this repo's functions on a recording engine and the same directory trees: the same client state and
-    config.yml written, the same resume step returned (0 when the engine reports a failed load), the same path found through the
-    `latest` tag and the same ValueErrors for a missing folder / tag / file."""
-    import ast
-    from pathlib import Path
-    from types import SimpleNamespace
-    import yaml
+    run in place by tests/golden/make_host_golden.py; this repo's functions on the same recording engine and the same directory trees:
+    the same client state and config.yml written, the same resume step returned (0 when the engine reports a failed load), the same
+    path found through the `latest` tag and the same ValueErrors for a missing folder / tag / file."""
     from magma_amd import utils as mine
-    ns = {"os": os, "Path": Path, "yaml": yaml}
-    for node in ast.parse(open("/root/reference/magma/utils.py").read()).body:
-        if isinstance(node, ast.FunctionDef) and node.name in ("save_model", "load_model", "infer_checkpoint_path_from_config"):
-            exec(compile(ast.Module(body=[node], type_ignores=[]), "/root/reference/magma/utils.py", "exec"), ns)
-
-    class Engine:
-        def __init__(self, ok=True):
-            self.saved, self.ok = [], ok
-
-        def save_checkpoint(self, save_dir, client_state=None, tag=None):
-            self.saved.append((str(save_dir), client_state))
-
-        def load_checkpoint(self, load_dir, load_optimizer_states=True, load_lr_scheduler_states=True, tag=None):
-            if not self.ok:
-                raise AssertionError("no checkpoint here")
-            return str(load_dir), {"global_step": 1234}
-
-    cfg = SimpleNamespace(to_dict=lambda: {"lr": 8e-4, "encoder_name": "clip_resnet_large", "nested": {"a": [1, 2]}})
-    out = {}
-    for who, mod in (("ref", ns), ("mine", mine.__dict__)):
-        d = tmp_path / who
-        e = Engine()
-        mod["save_model"](e, str(d), 77, cfg)
-        out[who] = (e.saved[0][1], (d / "config.yml").read_text())
-        assert mod["load_model"](Engine(ok=True), str(d)) == 1234
-        assert mod["load_model"](Engine(ok=False), str(d)) == 0
-        assert mod["load_model"](Engine(ok=True), str(d), load_optimizer_states=False, load_lr_scheduler_states=False) == 1234
-    assert out["ref"] == out["mine"]
-    save = tmp_path / "ckpts"
-    for who, mod in (("ref", ns), ("mine", mine.__dict__)):
-        f = mod["infer_checkpoint_path_from_config"]
-        with pytest.raises(ValueError):
-            f(SimpleNamespace(save=None))
-    for stage in range(3):
-        results = []
-        for mod in (ns, mine.__dict__):
-            try:
-                results.append(("ok", mod["infer_checkpoint_path_from_config"](SimpleNamespace(save=str(save)))))
-            except ValueError as e:
-                results.append(("ValueError", str(e)))
-        assert results[0] == results[1], (stage, results)
-        assert results[0][0] == ("ok" if stage == 2 else "ValueError")
-        if stage == 0:
-            save.mkdir()
-            (save / "latest").write_text("global_step500\n")
-        elif stage == 1:
-            (save / "global_step500").mkdir()
-            (save / "global_step500" / "mp_rank_00_model_states.pt").write_bytes(b"x")
+    got = RC.checkpoint_helpers_run(mine.save_model, mine.load_model, mine.infer_checkpoint_path_from_config, tmp_path)
+    pin = REF_PINS["checkpoint"]
+    assert pin["load"] == [1234, 0, 1234] and pin["save_none"] == "ValueError"
+    assert [r[0] for r in pin["infer"]] == ["ValueError", "ValueError", "ok"]
+    assert got == pin
 
 
 def test_from_checkpoint_signature_and_safe_unpickle(tmp_path, monkeypatch):

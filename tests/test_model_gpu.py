@@ -60,7 +60,7 @@ def test_encoder_and_prefix(setup):
     assert got2.shape == (2, 4, cfg.d_model)
 
 
-def test_embed_matches_reference_layout(setup):
+def test_embed_matches_reference_layout(setup, tmp_path):
     from oracle.model import embed
     cfg, p, model, images, ids = setup
     got = model.embed([images, ids])
@@ -71,7 +71,7 @@ def test_embed_matches_reference_layout(setup):
     import numpy as np
     import PIL.Image as I
     from magma_amd import ImageInput
-    path = "/tmp/_magma_test_img.png"
+    path = str(tmp_path / "img.png")
     I.fromarray((np.random.RandomState(0).rand(90, 70, 3) * 255).astype("uint8")).save(path)
     lst = [ImageInput(path), "hi"]
     out = model.preprocess_inputs(lst, embed=False)
