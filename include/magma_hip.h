@@ -81,8 +81,11 @@ const char* mg_version(void);
  *      epilogue changed size.  Added mg_conv_weight_relayout_batch / mg_bn_fold_batch (one launch per step for all
  *      convolutions of the image encoder) and mg_transpose_bn_param_grad_bf16; mg_rotary_split_fp8 gained `inplace` (before the stream):
  *      the rotated q / k also written back into the fused qkv activation, replacing a mg_rotary_qk_inplace_bf16 pass; mg_attn_bwd_rows_bf16
- *      gained `first_rows` (before the stream): only the gradients of the first positions (the bottom block of a frozen LM).                                                                                            */
-#define MG_ABI_VERSION 6
+ *      gained `first_rows` (before the stream): only the gradients of the first positions (the bottom block of a frozen LM).
+ *   7  ragged batches (right-padded prompts of different lengths): mg_attn_decode_bf16, mg_attn_decode_fused_bf16,
+ *      mg_decode_attn_gemv_bf16 and mg_sample_finish gained `pos_stride` (before the stream; 0 = one KV write position for the
+ *      batch as before, 1 = row b at d_pos[b]); mg_advance_pos gained `B` and `pos_stride` (before the stream).                 */
+#define MG_ABI_VERSION 7
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -247,7 +250,7 @@ int mg_decode_attn_gemv_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_bf16* vcach
                                                   * GEMV [W_out | W_up] */,
                              int32_t B, int32_t H, int32_t Smax, const int32_t* d_pos, int32_t rot_dim,
                              const float* sin_t, const float* cos_t, const mg_skinny_desc* gemv,
-                             void* stream);
+                             int32_t pos_stride /* ABI 7: see mg_attn_decode_fused_bf16 */, void* stream);
 
 /* K8/K17 + ImagePrefix LN: y = (x-mean)/sqrt(var+eps)*gamma+beta, fp32 stats.  Replaces nn.LayerNorm at reference
  * magma/image_prefix.py:58-60,106-107 and ln_1 / ln_f of the GPT-J blocks built at magma/language_model.py:12-45
@@ -289,22 +292,26 @@ int mg_attn_prefill_bf16(const mg_bf16* q, const mg_bf16* kcache, const mg_bf16*
                          void* stream);
 
 /* K10 decode (reference magma/sampling.py:86-90, past_key_values path): one query row per (b,h) against
- * ctx = *d_pos + 1 cached keys.                                                                            */
+ * ctx = pos_b + 1 cached keys, pos_b = d_pos[b * pos_stride].
+ * pos_stride (ABI 7): 0 = one position for the whole batch (d_pos[0]); 1 = d_pos holds B positions, one per row (a ragged,
+ * right-padded batch: row b's prompt has its own length, its cache slots >= pos_b are never read before a step writes them). */
 int mg_attn_decode_bf16(const mg_bf16* q, const mg_bf16* kcache, const mg_bf16* vcache,
                         mg_bf16* out, int32_t B, int32_t H, int32_t Smax, const int32_t* d_pos,
-                        void* stream);
+                        int32_t pos_stride, void* stream);
 
 /* K9 epilogue + K10 decode in ONE launch: takes the fused qkv row of the new token
- * [B, 3*H*256], rotates q,k, appends k,v at *d_pos, attends over [0, *d_pos].      */
+ * [B, 3*H*256], rotates q,k at angle row pos_b, appends k,v at pos_b, attends over [0, pos_b];
+ * pos_b = d_pos[b * pos_stride] as in mg_attn_decode_bf16.                                 */
 int mg_attn_decode_fused_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_bf16* vcache, mg_bf16* out, int32_t B,
                               int32_t H, int32_t Smax, const int32_t* d_pos, int32_t rot_dim,
-                              const float* sin_t, const float* cos_t, void* stream);
+                              const float* sin_t, const float* cos_t, int32_t pos_stride, void* stream);
 
 /* K24 greedy (reference magma/sampling.py:96-97, temperature == 0.0): token[b] = argmax_v logits[b, v] (first maximum), int64 out;
  * optionally appends to out_tokens[b*out_ld + *d_pos_out] and bumps *d_pos.  */
 int mg_argmax_f32(const float* logits, int64_t ld, int32_t B, int32_t V, int64_t* token,
                   void* stream);
-int mg_advance_pos(int32_t* d_pos, int32_t delta, void* stream);
+/* d_pos[0] += delta (pos_stride 0), or d_pos[b] += delta for b < B (pos_stride 1, ABI 7). */
+int mg_advance_pos(int32_t* d_pos, int32_t delta, int32_t B, int32_t pos_stride, void* stream);
 
 /* K24 sampled (reference magma/sampling.py:99-107: top_k_filter :22-30, top_p_filter :7-19 -- the reference's own rule, SURVEY Q6 --
  * softmax(logits / temperature), multinomial) as one launch per token step, graph-capturable (csrc/sampling.hip).
@@ -316,7 +323,8 @@ int mg_advance_pos(int32_t* d_pos, int32_t delta, void* stream);
  *   reference's filters put -inf).
  * mg_sample_finish is the loop bookkeeping of a token step in one small launch: records the first step with
  * (token == eos).all() (reference sampling.py:109, read by the host every few steps instead of a sync per token), advances
- * the step counter, bumps the KV-cache write position *d_pos by delta (NULL: untouched) and appends the tokens to
+ * the step counter, bumps the KV-cache write position by delta (d_pos NULL: untouched; pos_stride 0: d_pos[0]; 1: all B
+ * entries d_pos[b], ABI 7) and appends the tokens to
  * history[b * ld_history + step] (NULL: off; the host copies the history once when generate() ends); `clear` (NULL: off) =
  * n_clear int32 at clear[i * clear_stride] set to zero for the next step (device-side counters a caller wants re-armed
  * inside the captured step).                                                                                             */
@@ -325,7 +333,7 @@ int mg_sample_f32(const float* logits, int64_t ld, int32_t B, int32_t V, float t
                   void* stream);
 int mg_sample_finish(const int64_t* token, int32_t B, int64_t eos, int32_t* state, int32_t* d_pos, int32_t delta,
                      int64_t* history, int64_t ld_history, int32_t history_cols, int32_t* clear, int32_t n_clear,
-                     int32_t clear_stride, void* stream);
+                     int32_t clear_stride, int32_t pos_stride, void* stream);
 
 /* CLIP VisionTransformer front end and attention (encoder_name "clip" = ViT-B/32; reference magma/image_encoders.py:56-63):
  *   patchify   img [B,3,H,W] bf16 NCHW -> rows [B*(H/P)*(W/P), 3*P*P] in (c, py, px) order = the im2col of the stride-P patch

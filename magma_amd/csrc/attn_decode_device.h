@@ -5,11 +5,13 @@
 #include "gemm_device.h"
 
 // ---------------------------------------------------------------------------
-// decode attention: one query per (b,h); ctx = *d_pos + 1 keys.  grid B*H, 256 thr.
+// decode attention: one query per (b,h); ctx = pos + 1 keys, pos = d_pos[b * pos_stride]
+// (pos_stride 0: one position for the batch; 1: one per row -- right-padded prompts of
+// different lengths).  grid B*H, 256 thr.
 //   FUSED = false: q [B,H,256] already rotated, K/V already appended.
 //   FUSED = true : reads the fused qkv row [B, 3*H*256] of the new token, applies
-//                  the rotary to q and k, appends k,v to the cache at *d_pos and
-//                  attends over [0, *d_pos] -- one launch instead of two.
+//                  the rotary to q and k at angle row pos, appends k,v to the cache
+//                  at pos and attends over [0, pos] -- one launch instead of two.
 // Scores: S^T[key][.] = K . q^T on the MFMA (16 keys per wave step, all 8 K
 // fragment loads of a step in flight at once, no cross-lane reductions); the 16
 // "query columns" of the B operand all carry the same q.  PV: VALU, lane = 4
@@ -23,6 +25,7 @@ struct AttnDecodeParams {
   const mg_bf16* qin; mg_bf16* kcache; mg_bf16* vcache; mg_bf16* out;
   int H, Smax; const int* d_pos; int rot_dim; const float* sin_t; const float* cos_t;
   int64_t ld_out = 0;      // row stride of `out` in elements (0 = H * 256)
+  int pos_stride = 0;      // position of row b = d_pos[b * pos_stride]
 };
 
 // Device body: `bh` = (batch, head) index, `lds` = ATTN_DEC_LDS bytes of scratch (16-byte aligned).
@@ -48,7 +51,7 @@ MG_DEV void attn_decode_body(const AttnDecodeParams& P, int bh, char* lds) {
   const int li = lane & 15, lq = lane >> 4;
   const int b = bh / H, h = bh - b * H;
   const int64_t out_off = P.ld_out ? (int64_t)b * P.ld_out + (int64_t)h * DH : (int64_t)bh * DH;
-  const int pos = *d_pos;
+  const int pos = d_pos[b * P.pos_stride];
   const int ctx = min(pos + 1, min(Smax, DEC_MAX_CTX));
   mg_bf16* kb = kcache + (int64_t)bh * Smax * DH;
   mg_bf16* vb = vcache + (int64_t)bh * Smax * DH;

@@ -283,8 +283,9 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ 
   }
 }
 
-__global__ void advance_pos_kernel(int* d_pos, int delta) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) *d_pos += delta;
+// n positions (1, or one per row of a ragged batch) advance by delta
+__global__ void advance_pos_kernel(int* d_pos, int delta, int n) {
+  for (int i = threadIdx.x; i < n; i += blockDim.x) d_pos[i] += delta;
 }
 
 // ---------------------------------------------------------------------------
@@ -585,9 +586,11 @@ extern "C" int mg_argmax_f32(const float* logits, int64_t ld, int32_t B, int32_t
   return MG_OK;
 }
 
-extern "C" int mg_advance_pos(int32_t* d_pos, int32_t delta, void* stream) {
+extern "C" int mg_advance_pos(int32_t* d_pos, int32_t delta, int32_t B, int32_t pos_stride, void* stream) {
   if (!d_pos) MG_FAIL(MG_ERR_SHAPE, "mg_advance_pos: null pointer");
-  hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d_pos, delta);
+  if (pos_stride != 0 && pos_stride != 1) MG_FAIL(MG_ERR_SHAPE, "mg_advance_pos: pos_stride must be 0 or 1");
+  if (pos_stride == 1 && B <= 0) MG_FAIL(MG_ERR_SHAPE, "mg_advance_pos: pos_stride 1 needs B > 0 positions");
+  hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d_pos, delta, pos_stride ? B : 1);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }

@@ -1301,15 +1301,16 @@ extern "C" int mg_gemm_skinny2_bf16(const mg_skinny_desc* a, const mg_skinny_des
 extern "C" int mg_decode_attn_gemv_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_bf16* vcache, mg_bf16* attn_out, int64_t ld_attn_out,
                                         int32_t B, int32_t H, int32_t Smax, const int32_t* d_pos, int32_t rot_dim,
                                         const float* sin_t, const float* cos_t, const mg_skinny_desc* gemv,
-                                        void* stream) {
+                                        int32_t pos_stride, void* stream) {
   if (B <= 0 || H <= 0 || Smax <= 0 || Smax > DEC_MAX_CTX) MG_FAIL(MG_ERR_SHAPE, "mg_decode_attn_gemv_bf16: need 0 < Smax <= %d", DEC_MAX_CTX);
+  if (pos_stride != 0 && pos_stride != 1) MG_FAIL(MG_ERR_SHAPE, "mg_decode_attn_gemv_bf16: pos_stride must be 0 or 1");
   if (rot_dim < 0 || rot_dim > 256 || (rot_dim & 7)) MG_FAIL(MG_ERR_SHAPE, "mg_decode_attn_gemv_bf16: rot_dim must be a multiple of 8 in [0,256]");
   if (!qkv || !kcache || !vcache || !attn_out || !d_pos || (rot_dim && (!sin_t || !cos_t))) MG_FAIL(MG_ERR_SHAPE, "mg_decode_attn_gemv_bf16: null pointer");
   if (!MG_ALIGNED16(qkv) || !MG_ALIGNED16(kcache) || !MG_ALIGNED16(vcache) || !MG_ALIGNED16(attn_out)) MG_FAIL(MG_ERR_ALIGN, "mg_decode_attn_gemv_bf16: pointers must be 16-byte aligned");
   SkinnyParams sp;
   if (int rc = fill_skinny(gemv, sp, "mg_decode_attn_gemv_bf16(gemv)")) return rc;
   if (ld_attn_out != 0 && (ld_attn_out < (int64_t)H * 256 || (ld_attn_out & 7))) MG_FAIL(MG_ERR_SHAPE, "mg_decode_attn_gemv_bf16: ld_attn_out must be 0 or a multiple of 8 >= H*256");
-  AttnDecodeParams ap{qkv, kcache, vcache, attn_out, H, Smax, d_pos, rot_dim, sin_t, cos_t, ld_attn_out};
+  AttnDecodeParams ap{qkv, kcache, vcache, attn_out, H, Smax, d_pos, rot_dim, sin_t, cos_t, ld_attn_out, pos_stride};
   hipStream_t s = (hipStream_t)stream;
   const int n_attn = B * H, grid = n_attn + sp.ntiles;
   if (sp.w_scale && sp.ksteps % 64 != 0) MG_FAIL(MG_ERR_UNSUPPORTED, "mg_decode_attn_gemv_bf16: fp8 weights need K %% 2048 == 0 here");

@@ -320,10 +320,11 @@ __global__ __launch_bounds__(ST) void sample_kernel(const SampleParams p) {
 
 // Loop bookkeeping of one token step in ONE small launch: (next_token == eos).all() of reference sampling.py:109 recorded as
 // the FIRST step at which it held, the step counter of the random stream, the KV-cache write position, and the token
-// history the host reads once at the end of generate() (instead of one small copy per step).
+// history the host reads once at the end of generate() (instead of one small copy per step).  n_pos = 1 (one position for
+// the batch) or B (one per row of a ragged batch): every entry advances by delta.
 // state = {step, first_all_eos_step (-1 = not yet)}
 __global__ void sample_finish_kernel(const int64_t* __restrict__ tok, int B, int64_t eos, int32_t* __restrict__ state,
-                                     int32_t* __restrict__ d_pos, int delta, int64_t* __restrict__ history, int64_t ld_hist,
+                                     int32_t* __restrict__ d_pos, int delta, int n_pos, int64_t* __restrict__ history, int64_t ld_hist,
                                      int hist_cols, int32_t* __restrict__ clear, int n_clear, int clear_stride) {
   // every thread needs the step BEFORE thread 0 bumps it: one read, broadcast through LDS (rows beyond the first wave would
   // otherwise race with the increment below)
@@ -334,12 +335,13 @@ __global__ void sample_finish_kernel(const int64_t* __restrict__ tok, int B, int
   for (int i = threadIdx.x; i < n_clear; i += blockDim.x) clear[(int64_t)i * clear_stride] = 0;
   if (history && step < hist_cols)
     for (int b = threadIdx.x; b < B; b += blockDim.x) history[(int64_t)b * ld_hist + step] = tok[b];
+  if (d_pos)
+    for (int b = threadIdx.x; b < n_pos; b += blockDim.x) d_pos[b] += delta;
   if (threadIdx.x != 0) return;
   bool all = true;
   for (int b = 0; b < B; ++b) all = all && (tok[b] == eos);
   if (all && state[1] < 0) state[1] = step;
   state[0] = step + 1;
-  if (d_pos) *d_pos += delta;
 }
 
 }  // namespace
@@ -360,10 +362,12 @@ extern "C" int mg_sample_f32(const float* logits, int64_t ld, int32_t B, int32_t
 
 extern "C" int mg_sample_finish(const int64_t* token, int32_t B, int64_t eos, int32_t* state, int32_t* d_pos, int32_t delta,
                                 int64_t* history, int64_t ld_history, int32_t history_cols, int32_t* clear, int32_t n_clear,
-                                int32_t clear_stride, void* stream) {
+                                int32_t clear_stride, int32_t pos_stride, void* stream) {
   if (!token || !state || B <= 0) MG_FAIL(MG_ERR_SHAPE, "mg_sample_finish: bad arguments");
+  if (pos_stride != 0 && pos_stride != 1) MG_FAIL(MG_ERR_SHAPE, "mg_sample_finish: pos_stride must be 0 or 1");
   if (history && (ld_history < history_cols || history_cols <= 0)) MG_FAIL(MG_ERR_SHAPE, "mg_sample_finish: bad history geometry");
   hipLaunchKernelGGL(sample_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, token, B, eos, state, d_pos, delta,
+                     pos_stride ? B : 1,
                      history, ld_history, history_cols, clear, clear ? n_clear : 0, clear_stride > 0 ? clear_stride : 1);
   MG_CHECK_LAUNCH();
   return MG_OK;

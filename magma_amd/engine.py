@@ -41,11 +41,14 @@ def rotary_tables(rotary_dim: int, n_pos: int, device):
 class KVCache:
     """Opaque ``past_key_values`` (reference sampling.py:81-93 only hands it back)."""
 
-    def __init__(self, n_layer: int, B: int, H: int, Smax: int, device):
+    def __init__(self, n_layer: int, B: int, H: int, Smax: int, device, ragged: bool = False):
         self.k = torch.empty(n_layer, B, H, Smax, 256, dtype=BF16, device=device)
         self.v = torch.empty(n_layer, B, H, Smax, 256, dtype=BF16, device=device)
-        self.d_pos = torch.zeros(1, dtype=torch.int32, device=device)   # next write position
-        self.pos = 0                                                     # host mirror
+        # next write position: one for the batch, or -- ragged (right-padded prompts of different lengths) -- one per row
+        self.ragged = bool(ragged)
+        self.pos_stride = 1 if self.ragged else 0                         # launch argument of every decode kernel
+        self.d_pos = torch.zeros(B if self.ragged else 1, dtype=torch.int32, device=device)
+        self.pos = 0                                                     # host mirror (ragged: of the largest position)
         # token-selection state of the generate() loop (device side): {step, first step at which every row emitted eos},
         # the seed of the sampling stream, the eos id the bookkeeping launch compares against
         self.sample_state = torch.tensor([0, -1], dtype=torch.int32, device=device)
@@ -371,7 +374,13 @@ class LMEngine:
     def forward(self, input_ids=None, inputs_embeds=None, labels=None, use_cache=False, past_key_values=None,
                 output_hidden_states=False, cache_hint: Optional[int] = None, reuse_cache: bool = False,
                 return_logits: bool = False, sampling=None, eos_token: Optional[int] = None,
-                seed: Optional[int] = None, feed_back: bool = False) -> LMOutput:
+                seed: Optional[int] = None, feed_back: bool = False, lengths=None) -> LMOutput:
+        """``lengths`` (int [B], 1 <= len_b <= S; prefill with use_cache=True only): the rows of ``inputs_embeds`` are prompts
+        of different lengths, right-padded to S.  Row b's logits are those of its position len_b - 1, and the cache keeps one
+        write position per row (len_b, then + 1 per step) -- see DESIGN.md, "Ragged batches"."""
+        if lengths is not None and (labels is not None or past_key_values is not None or not use_cache):
+            raise ValueError("lengths= applies to the prefill call (use_cache=True, no past_key_values, no labels); "
+                             "a ragged cache keeps its per-row positions for the steps that follow")
         if labels is not None:
             if inputs_embeds is None:
                 inputs_embeds = self.embed_ids(input_ids)
@@ -398,7 +407,7 @@ class LMEngine:
         if inputs_embeds is None:
             inputs_embeds = self.embed_ids(input_ids)
         if use_cache:
-            logits, cache, hs = self.prefill(inputs_embeds, cache_hint, output_hidden_states, reuse_cache)
+            logits, cache, hs = self.prefill(inputs_embeds, cache_hint, output_hidden_states, reuse_cache, lengths=lengths)
             # generate() only reads the last position, so only that row is computed
             out = LMOutput(logits=logits.unsqueeze(1), past_key_values=cache, hidden_states=hs, loss=None)
             if eos_token is not None:     # generate(): first token of the loop selected here, device-side bookkeeping armed
@@ -503,27 +512,53 @@ class LMEngine:
                 hs.append(x.view(B, S, d))
         return x, hs
 
+    @staticmethod
+    def check_lengths(lengths, B: int, S: int) -> torch.Tensor:
+        """Prompt lengths of a right-padded batch as a host int64 [B] tensor; 1 <= len_b <= S."""
+        lens = torch.as_tensor(lengths).detach().to("cpu")
+        if lens.is_floating_point() or lens.is_complex() or lens.dtype == torch.bool:
+            raise TypeError(f"lengths must be integers, got {lens.dtype}")
+        lens = lens.to(torch.int64)
+        if lens.ndim != 1 or lens.shape[0] != B:
+            raise ValueError(f"lengths must have shape ({B},) (one length per row), got {tuple(lens.shape)}")
+        if int(lens.min()) < 1 or int(lens.max()) > S:
+            raise ValueError(f"every length must lie in [1, {S}] (the padded sequence length), got {lens.tolist()}")
+        return lens
+
     def prefill(self, embeds: torch.Tensor, cache_hint: Optional[int] = None, want_hidden=False,
-                reuse_cache: bool = False):
+                reuse_cache: bool = False, lengths=None):
         B, S, _ = embeds.shape
+        ragged = lengths is not None
+        if ragged:
+            lens = self.check_lengths(lengths, B, S)
         n_pos = self.cfg.max_position_embeddings
         Smax = min(n_pos, ops.ceil_to(S + (cache_hint if cache_hint else 256), 64))
         if reuse_cache:
             # generate() owns the cache for the duration of one call: keep one KV cache (and the
             # hipGraph of the token step captured on it) per shape instead of re-allocating and
-            # re-capturing for every call
-            cache = self._cache_pool.pop((B, Smax), None)
+            # re-capturing for every call.  Ragged and uniform caches never share an entry: the
+            # position layout (and with it the captured launches) differ
+            key = (B, Smax, ragged)
+            cache = self._cache_pool.pop(key, None)
             if cache is None:
                 while len(self._cache_pool) >= self._cache_pool_max:      # least recently used shape goes first
                     self._cache_pool.pop(next(iter(self._cache_pool)))
-                cache = KVCache(self.L, B, self.H, Smax, self.device)
-            self._cache_pool[(B, Smax)] = cache                          # (re-)insert as most recently used
+                cache = KVCache(self.L, B, self.H, Smax, self.device, ragged=ragged)
+            self._cache_pool[key] = cache                                # (re-)insert as most recently used
         else:
-            cache = KVCache(self.L, B, self.H, Smax, self.device)
+            cache = KVCache(self.L, B, self.H, Smax, self.device, ragged=ragged)
+        # right padding: the prefill is unchanged -- under the causal mask a valid row attends to valid keys only, and the
+        # K / V the padded rows leave in slots >= len_b are overwritten by decode steps before any row reads them
         x, hs = self._blocks_prefill(embeds, cache, want_hidden)
-        cache.pos = S
-        cache.d_pos.fill_(S)
-        last = x.view(B, S, self.d)[:, S - 1, :]                 # strided rows, no copy
+        if ragged:
+            cache.pos = int(lens.max())
+            cache.d_pos.copy_(lens.to(torch.int32), non_blocking=True)       # no stream sync (as sample_state in forward)
+            rows = (torch.arange(B, dtype=torch.int64) * S + lens - 1).to(self.device, non_blocking=True)
+            last = x.index_select(0, rows)                       # row len_b - 1 of every sequence
+        else:
+            cache.pos = S
+            cache.d_pos.fill_(S)
+            last = x.view(B, S, self.d)[:, S - 1, :]             # strided rows, no copy
         xl = ops.layernorm(last, self.lnf_g, self.lnf_b, self.eps)
         logits = self._head(xl)
         return logits, cache, hs
@@ -578,7 +613,7 @@ class LMEngine:
         else:
             tok = ops.sample(logits, mode[0], mode[1], mode[2], cache.seed, cache.sample_state, out=out)
         ops.sample_finish(tok, cache.eos, cache.sample_state, d_pos=cache.d_pos if advance else None, history=cache.history,
-                          clear=clear, clear_stride=16 if clear is not None else 1)
+                          clear=clear, clear_stride=16 if clear is not None else 1, pos_stride=cache.pos_stride)
         return tok
 
     def check_decode(self, cache: KVCache):
@@ -591,6 +626,7 @@ class LMEngine:
         ``feed_back``: the input ids are the tokens the previous step selected (st.token, still on the device) -- the
         reference's loop feeds exactly those back (sampling.py:88-90) -- instead of ids copied in from the caller."""
         B = cache.B
+        ps = cache.pos_stride            # 1 on a ragged cache: every attention launch reads row b's position d_pos[b]
         ops.embedding(st.token.view(B, 1) if feed_back else st.ids, self.wte, st.xa.view(B, 1, self.d))
         x, xn = st.xa, st.xb
         d3 = 3 * self.d
@@ -625,7 +661,7 @@ class LMEngine:
                 r = ly.mlp_adapter[0].N
                 ctx, t = st.ctx_t[:, : self.d], st.ctx_t[:, self.d: self.d + r]
                 ops.decode_attn_gemv(st.qkv, cache.k[li], cache.v[li], ctx, B, self.H, cache.d_pos, self.rot, self.sin_t, self.cos_t,
-                                     (st.h, ly.fc_out, st.m, {}))
+                                     (st.h, ly.fc_out, st.m, {}), pos_stride=ps)
                 ops.gemm_skinny(st.m, ly.mlp_adapter[0], out=t, act=ops.MG_ACT_RELU, variant=self._dec_dn_variant)
                 ops.gemm_skinny(st.ctx_t[:, : self.d + r], ly.out_up, out=xn, residuals=(st.m, x), variant=self._dec_cat_variant)
                 x, xn = xn, x
@@ -636,7 +672,7 @@ class LMEngine:
                 r = ly.mlp_adapter[0].N
                 ctx, t = st.ctx_t[:, : self.d], st.ctx_t[:, self.d: self.d + r]
                 ops.decode_attn_gemv(st.qkv, cache.k[li], cache.v[li], ctx, B, self.H, cache.d_pos, self.rot, self.sin_t, self.cos_t,
-                                     (st.h, ly.fc_dn, st.m, {"split": (self.d, t, ops.MG_ACT_RELU, ly.fc_dn.bias_b)}))
+                                     (st.h, ly.fc_dn, st.m, {"split": (self.d, t, ops.MG_ACT_RELU, ly.fc_dn.bias_b)}), pos_stride=ps)
                 # launch 3: x' = [W_out | W_up] [ctx ; t] + b_up + m + x
                 ops.gemm_skinny(st.ctx_t[:, : self.d + r], ly.out_up, out=xn, residuals=(st.m, x))
                 x, xn = xn, x
@@ -648,7 +684,7 @@ class LMEngine:
                 # launch 2: attention workgroups + fc_out GEMV workgroups in one grid (they are independent
                 # branches of the parallel block; the latency-bound attention hides under the weight stream)
                 ops.decode_attn_gemv(st.qkv, cache.k[li], cache.v[li], st.ctx, B, self.H, cache.d_pos, self.rot,
-                                     self.sin_t, self.cos_t, (st.h, src.fc_out, st.m, {}))
+                                     self.sin_t, self.cos_t, (st.h, src.fc_out, st.m, {}), pos_stride=ps)
                 # launch 3: out_proj || adapter-down
                 t = st.t[:, : ly.mlp_adapter[0].N]
                 ops.gemm_skinny2((st.ctx, src.out, st.a, {}), (st.m, src.mlp_adapter[0], t, {"act": ly.mlp_act}))
@@ -667,7 +703,7 @@ class LMEngine:
                 if w8_on:
                     up_cat = src.up_cat
                 ops.decode_attn_gemv(st.qkv, cache.k[li], cache.v[li], st.ctx, B, self.H, cache.d_pos, self.rot,
-                                     self.sin_t, self.cos_t, (st.h, src.fc_out, st.m, {}))
+                                     self.sin_t, self.cos_t, (st.h, src.fc_out, st.m, {}), pos_stride=ps)
                 ops.gemm_skinny2((st.ctx, src.out, st.a, {}), (st.m, src.mlp_adapter[0], t, {"act": ly.mlp_act}))
                 ops.gemm_skinny(st.a, src.attn_adapter[0], out=ta, act=ly.attn_act)
                 ops.gemm_skinny(st.tcat[:, : up_cat.Kp], up_cat, out=xn, residuals=(st.m, st.a, x))
@@ -677,7 +713,7 @@ class LMEngine:
                 side.wait_stream(main)
                 torch.cuda.set_stream(side)
             ops.attn_decode_fused(st.qkv, cache.k[li], cache.v[li], st.ctx, B, self.H, cache.d_pos, self.rot,
-                                  self.sin_t, self.cos_t)
+                                  self.sin_t, self.cos_t, pos_stride=ps)
             a = G(st.ctx, ly.out, out=st.a)
             if par and not wide:      # parallel adapters read ln_1(x): the one decode configuration that needs the LayerNorm as a tensor
                 ops.layernorm(x, ly.ln_g, ly.ln_b, self.eps, out=st.ln)
@@ -716,7 +752,7 @@ class LMEngine:
             head = self.head_w8 if w8_on else self.head_dec
             ops.gemm_skinny(x, head, out=st.logits, ln_fold=(head.colsum, self.d, self.eps))
         if mode == "noselect":
-            ops.advance_pos(cache.d_pos)          # teacher-forced position: nothing selected, nothing recorded
+            ops.advance_pos(cache.d_pos, pos_stride=ps)   # teacher-forced position: nothing selected, nothing recorded
         else:
             self.select_token(st.logits[:, : self.V], cache, mode, out=st.token, advance=True)
 

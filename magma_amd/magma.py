@@ -15,7 +15,7 @@ from copy import deepcopy
 from os.path import exists
 from pathlib import Path
 import os
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -220,13 +220,68 @@ class Magma(nn.Module):
         return out
 
     @torch.no_grad()
+    def embed_batch(self, batch: List[list]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """A batch of requests with prompts of different lengths: ``batch`` is a list of per-sample input lists, each
+        element a str, an ImageInput or an already preprocessed tensor (batch dimension 1) as ``preprocess_inputs`` /
+        ``embed`` take them.  Returns (embeddings (B, S_max, d), right-padded with zeros; lengths int64 [B]) -- the
+        arguments of ``generate(embeddings, lengths=lengths)``.  The caller's lists are left as they are; every image of
+        the batch goes through ONE image_prefix call."""
+        from . import ops
+        torch.cuda.set_device(self.device)
+        if not batch:
+            raise ValueError("embed_batch: empty batch")
+        samples = []
+        for sample in batch:
+            items = []
+            for inp in sample:
+                if isinstance(inp, str):
+                    inp = self.tokenizer.encode(inp, return_tensors="pt")
+                elif isinstance(inp, ImageInput):
+                    inp = inp.get_transformed_image(transform_fn=self.transforms)
+                elif not isinstance(inp, torch.Tensor):
+                    raise Exception(f"Invalid input type:{type(inp)}")
+                if inp.ndim not in (2, 4):
+                    raise ValueError(f"Expected 2d or 4d tensor, got {inp.ndim}d")
+                if inp.shape[0] != 1:
+                    raise ValueError(f"embed_batch takes one sample per list: batch dimension 1, got {tuple(inp.shape)}")
+                items.append(inp)
+            if not items:
+                raise ValueError("embed_batch: a sample without inputs")
+            samples.append(items)
+        images = [x for items in samples for x in items if x.ndim == 4]
+        prefix = None
+        if images:
+            if any(x.shape != images[0].shape for x in images):
+                raise ValueError("embed_batch: all images of a batch must share one shape (the transforms give a fixed size)")
+            prefix = self.image_prefix(torch.cat([x.to(self.device) for x in images]))     # ONE call for the whole batch
+        P = 0 if prefix is None else prefix.shape[1]
+        lengths = torch.tensor([sum(P if x.ndim == 4 else x.shape[1] for x in items) for items in samples], dtype=torch.int64)
+        d = self.lm.config.hidden_size
+        out = torch.zeros(len(samples), int(lengths.max()), d, dtype=self.dtype, device=self.device)
+        k = 0
+        for b, items in enumerate(samples):
+            off = 0
+            for x in items:
+                if x.ndim == 4:
+                    out[b, off:off + P] = prefix[k]
+                    k += 1
+                    off += P
+                else:
+                    ops.embedding(x.to(self.device).contiguous(), self.lm.engine.wte, out[b:b + 1], row_off=off)
+                    off += x.shape[1]
+        return out, lengths
+
+    @torch.no_grad()
     def generate(self, embeddings, max_steps: int = 100, temperature: float = 0.7, top_k: int = 0,
                  top_p: float = 0.9, decode: bool = True, stop_on_eos: bool = True, seed: int = None,
-                 eos_check_every: int = None):
-        """reference magma.py:214-236 (+ stop_on_eos / seed / eos_check_every, see sampling.generate)."""
+                 eos_check_every: int = None, lengths=None):
+        """reference magma.py:214-236 (+ stop_on_eos / seed / eos_check_every / lengths, see sampling.generate).
+        ``lengths``: prompts of different lengths, right-padded (embed_batch); ``embeddings`` may also be a list of
+        per-sample (1, s_i, d) tensors."""
         torch.cuda.set_device(self.device)
         return generate(self, embeddings=embeddings, max_steps=max_steps, temperature=temperature, top_k=top_k,
-                        top_p=top_p, decode=decode, stop_on_eos=stop_on_eos, seed=seed, eos_check_every=eos_check_every)
+                        top_p=top_p, decode=decode, stop_on_eos=stop_on_eos, seed=seed, eos_check_every=eos_check_every,
+                        lengths=lengths)
 
     # ------------------------------------------------------------- forward
     def forward(self, images=None, captions=None, output_hidden_states: bool = False, input_embeddings=None,

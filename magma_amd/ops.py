@@ -312,15 +312,26 @@ def gemm_skinny2(a: tuple, b: tuple):
     return oa, ob
 
 
-def decode_attn_gemv(qkv, kcache, vcache, attn_out, B, H, d_pos, rot_dim, sin_t, cos_t, gemv: tuple):
+def _pos_stride(d_pos: torch.Tensor, B: int, pos_stride: int) -> int:
+    """pos_stride 0: one write position shared by the batch (d_pos[0]); 1: row b at d_pos[b] (ragged batches)."""
+    assert d_pos.dtype == torch.int32 and d_pos.is_contiguous()
+    if pos_stride not in (0, 1):
+        raise ValueError("pos_stride must be 0 (one shared position) or 1 (one position per row)")
+    if pos_stride == 1 and d_pos.numel() < B:
+        raise ValueError(f"pos_stride=1 needs one position per row: d_pos has {d_pos.numel()} entries for B = {B}")
+    return pos_stride
+
+
+def decode_attn_gemv(qkv, kcache, vcache, attn_out, B, H, d_pos, rot_dim, sin_t, cos_t, gemv: tuple, *, pos_stride: int = 0):
     """Decode attention (rotary + append + attend) co-launched with one independent GEMV
-    gemv = (x, w, out, kwargs)."""
+    gemv = (x, w, out, kwargs).  ``pos_stride=1``: row b writes / attends at its own position d_pos[b]."""
     _need_gpu(qkv)
+    ps = _pos_stride(d_pos, B, pos_stride)
     d, og = skinny_desc(gemv[0], gemv[1], gemv[2], **gemv[3])
     assert attn_out.ndim == 2 and attn_out.stride(1) == 1 and attn_out.shape[1] == H * 256   # a column range of a wider row is fine
     check(L.load().mg_decode_attn_gemv_bf16(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), attn_out.data_ptr(),
                                             attn_out.stride(0), B, H, kcache.shape[2], d_pos.data_ptr(), rot_dim, sin_t.data_ptr(),
-                                            cos_t.data_ptr(), C.byref(d), _stream()), "mg_decode_attn_gemv_bf16")
+                                            cos_t.data_ptr(), C.byref(d), ps, _stream()), "mg_decode_attn_gemv_bf16")
     return attn_out, og
 
 
@@ -458,19 +469,22 @@ def attn_prefill(q, kcache, vt, out, B, H, S, lse: Optional[torch.Tensor] = None
     return out
 
 
-def attn_decode(q, kcache, vcache, out, B, H, d_pos):
+def attn_decode(q, kcache, vcache, out, B, H, d_pos, *, pos_stride: int = 0):
+    """Attention of one (already rotated) query per (b, h) over [0, pos_b]; pos_b = d_pos[b * pos_stride]."""
     _need_gpu(q)
+    ps = _pos_stride(d_pos, B, pos_stride)
     check(L.load().mg_attn_decode_bf16(q.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), B, H,
-                                       kcache.shape[2], d_pos.data_ptr(), _stream()), "mg_attn_decode_bf16")
+                                       kcache.shape[2], d_pos.data_ptr(), ps, _stream()), "mg_attn_decode_bf16")
     return out
 
 
-def attn_decode_fused(qkv, kcache, vcache, out, B, H, d_pos, rot_dim, sin_t, cos_t):
-    """rotary(q,k) + KV append at *d_pos + attention over [0, *d_pos], one launch."""
+def attn_decode_fused(qkv, kcache, vcache, out, B, H, d_pos, rot_dim, sin_t, cos_t, *, pos_stride: int = 0):
+    """rotary(q,k) + KV append at pos_b + attention over [0, pos_b], one launch; pos_b = d_pos[b * pos_stride]."""
     _need_gpu(qkv)
+    ps = _pos_stride(d_pos, B, pos_stride)
     check(L.load().mg_attn_decode_fused_bf16(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), B, H,
                                              kcache.shape[2], d_pos.data_ptr(), rot_dim, sin_t.data_ptr(),
-                                             cos_t.data_ptr(), _stream()), "mg_attn_decode_fused_bf16")
+                                             cos_t.data_ptr(), ps, _stream()), "mg_attn_decode_fused_bf16")
     return out
 
 
@@ -504,10 +518,12 @@ def sample(logits: torch.Tensor, temperature: float, top_k: int, top_p: float, s
 
 
 def sample_finish(token: torch.Tensor, eos: int, state: torch.Tensor, d_pos: Optional[torch.Tensor] = None, delta: int = 1,
-                  history: Optional[torch.Tensor] = None, clear: Optional[torch.Tensor] = None, clear_stride: int = 1):
+                  history: Optional[torch.Tensor] = None, clear: Optional[torch.Tensor] = None, clear_stride: int = 1, *,
+                  pos_stride: int = 0):
     """Bookkeeping of one token step: first all-eos step, step counter, (optionally) KV write position += delta and the
-    token history [B, n_steps] int64."""
+    token history [B, n_steps] int64.  ``pos_stride=1``: d_pos holds one position per row and every one advances."""
     _need_gpu(token, state, d_pos, history)
+    ps = 0 if d_pos is None else _pos_stride(d_pos, token.numel(), pos_stride)
     assert token.dtype == torch.int64 and state.dtype == torch.int32 and state.numel() >= 2
     if history is not None:
         assert history.dtype == torch.int64 and history.ndim == 2 and history.stride(1) == 1 and history.shape[0] == token.numel()
@@ -515,12 +531,14 @@ def sample_finish(token: torch.Tensor, eos: int, state: torch.Tensor, d_pos: Opt
         assert clear.dtype == torch.int32 and clear.is_contiguous()
     check(L.load().mg_sample_finish(token.data_ptr(), token.numel(), int(eos), state.data_ptr(), _p(d_pos), delta, _p(history),
                                     0 if history is None else history.stride(0), 0 if history is None else history.shape[1],
-                                    _p(clear), 0 if clear is None else clear.numel() // clear_stride, clear_stride, _stream()),
+                                    _p(clear), 0 if clear is None else clear.numel() // clear_stride, clear_stride, ps, _stream()),
           "mg_sample_finish")
 
 
-def advance_pos(d_pos: torch.Tensor, delta: int = 1):
-    check(L.load().mg_advance_pos(d_pos.data_ptr(), delta, _stream()), "mg_advance_pos")
+def advance_pos(d_pos: torch.Tensor, delta: int = 1, *, pos_stride: int = 0):
+    """d_pos[0] += delta; with ``pos_stride=1`` every entry of d_pos (one position per row) += delta."""
+    ps = _pos_stride(d_pos, d_pos.numel(), pos_stride)
+    check(L.load().mg_advance_pos(d_pos.data_ptr(), delta, d_pos.numel(), ps, _stream()), "mg_advance_pos")
 
 
 def patchify(img: torch.Tensor, P: int) -> torch.Tensor:
