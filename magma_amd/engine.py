@@ -693,8 +693,8 @@ class LMEngine:
                 x, xn = xn, x
                 continue
             up_cat = self._adapter_up_cat(ly) if self.group_launches and not par and not wide else None
-            if w8_on and (up_cat is None or src.up_cat is None or src.mlp_adapter[0] is None):
-                raise NotImplementedError("W8A16 decode covers the grouped MAGMA_v1 and MAGMA_v2 steps ('normal' adapters, K % 1024 == 0) only")
+            if w8_on and up_cat is not None and (src.up_cat is None or src.mlp_adapter[0] is None):
+                raise NotImplementedError("W8A16 decode of the MAGMA_v2 step needs adapter projections with K % 1024 == 0")
             if up_cat is not None:
                 # MAGMA_v2 (attention AND mlp adapters): 5 launches.  x' = up_m(t) + up_a(ta) + m + a + x is ONE GEMV over
                 # the concatenated bottlenecks [t | ta] against [W_up_m | W_up_a] (the adapter outputs only ever appear summed).
@@ -714,7 +714,9 @@ class LMEngine:
                 torch.cuda.set_stream(side)
             ops.attn_decode_fused(st.qkv, cache.k[li], cache.v[li], st.ctx, B, self.H, cache.d_pos, self.rot,
                                   self.sin_t, self.cos_t, pos_stride=ps)
-            a = G(st.ctx, ly.out, out=st.a)
+            # every other block (no MLP adapter, parallel adapters, adapters with a LayerNorm): out_proj and fc_out from src --
+            # e4m3 under W8A16 --, the small adapter projections in bf16
+            a = G(st.ctx, src.out, out=st.a)
             if par and not wide:      # parallel adapters read ln_1(x): the one decode configuration that needs the LayerNorm as a tensor
                 ops.layernorm(x, ly.ln_g, ly.ln_b, self.eps, out=st.ln)
             if ly.attn_adapter is not None:
@@ -729,7 +731,7 @@ class LMEngine:
             if side is not None:
                 torch.cuda.set_stream(main)
             if ly.mlp_adapter is not None:
-                G(st.h, ly.fc_out, out=st.m)
+                G(st.h, src.fc_out, out=st.m)
                 t = st.t[:, : ly.mlp_adapter[0].N]
                 if side is not None:
                     main.wait_stream(side)
@@ -743,7 +745,7 @@ class LMEngine:
             else:
                 if side is not None:
                     main.wait_stream(side)
-                G(st.h, ly.fc_out, out=xn, residuals=(a, x))
+                G(st.h, src.fc_out, out=xn, residuals=(a, x))
             x, xn = xn, x
         if wide:
             ops.layernorm(x, self.lnf_g, self.lnf_b, self.eps, out=st.lnf)

@@ -518,10 +518,12 @@ class MagmaEngine:
         sc = sval.reshape(1).to(F32).expand(up.weight.shape[0]).contiguous()
         return dnw, RawWeight(up.weight.data, bias=(self.master_of(up.bias) * sc).contiguous()), sc
 
-    def _ad8_ok(self, ly, mod) -> bool:
-        """fp8 adapter chain: plain ReLU MLP adapter (no LayerNorm, not parallel), shapes the 256x256 fp8 kernel's MX output covers."""
+    def _ad8_ok(self, ly, blk) -> bool:
+        """fp8 adapter chain: plain ReLU MLP adapter (no LayerNorm, not parallel), shapes the 256x256 fp8 kernel's MX output covers.
+        Takes the block: ``blk.mlp`` is Sequential(mlp, Adapter) only when the block has an MLP adapter (the bare MLP otherwise)."""
         if not (self.fp8 and self.fp8_mx and self.fp8_adapters) or ly.mlp_adapter is None or ly.mlp_par is not None:
             return False
+        mod = blk.mlp[1]
         if not getattr(mod, "plain", False):
             return False
         r, d = mod.down.weight.shape
@@ -709,7 +711,7 @@ class MagmaEngine:
                 m = self._fgemm((li, "fc_out"), h, ly.fc_out)
                 t = self._adapter_down(blk.mlp, ln, dn, sv, "t")
                 x = ops.gemm(t, up, scale=sc, residuals=(m, a, x), layout="rm")
-            elif self._ad8_ok(ly, blk.mlp[1]):
+            elif self._ad8_ok(ly, blk):
                 # config[4]: the adapter GEMMs on the fp8 MFMA, operands from the producing epilogues (see __init__)
                 p8 = self._ad8(li, blk.mlp[1])
                 m_mx = ops.mx_empty(M, ly.fc_out.N, dev)
@@ -899,7 +901,7 @@ class MagmaEngine:
                 dt, dn_t = self._par_adapter_backward(blk.mlp, g, ln, sv["t"], sv.get("t_pre"))
                 extra.append(self._adapter_dx(blk.mlp, dt, dn_t, ln))
                 dm = g
-            elif self._ad8_ok(ly, blk.mlp[1]) and not bottom:
+            elif self._ad8_ok(ly, blk) and not bottom:
                 mod, p8 = blk.mlp[1], self._ad8(li, blk.mlp[1])
                 gq = ops.quantize_rows_fp8(g)          # also the operand of the out_proj dgrad below (no attention adapter: da = g)
                 self._acc_wgrad(mod.up.weight, RawWeight(ops.transpose_colsum(g, self.grad_of(mod.up.bias))), _t(sv["t"]))

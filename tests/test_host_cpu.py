@@ -37,6 +37,20 @@ def test_configs_parse_like_the_reference():
     assert set(r2.extra) == set(RC.V2_EXTRA_KEYS)
 
 
+def test_reduced_config_helper_adapter_sets():
+    """magma_amd.testing.tiny_multimodal_config: the adapter sets the tests build (reference magma.py:111-120 adds each adapter
+    only when adapter_config names it)."""
+    from magma_amd.testing import tiny_multimodal_config as tiny
+    assert tiny().adapter_config == {"mlp": {"adapter_type": "normal", "downsample_factor": 4}}
+    assert set(tiny(8, 8).adapter_config) == {"mlp", "attention"}
+    assert tiny(mlp_factor=None).adapter_config == {}
+    assert tiny(mlp_factor=None, attn_factor=8, attn_type="scaled_parallel").adapter_config == {
+        "attention": {"adapter_type": "scaled_parallel", "downsample_factor": 8}}
+    assert not tiny(adapter_config=None).adapter_config
+    assert tiny(mlp_factor=None, adapter_config={"attention": {"adapter_type": "parallel"}}).adapter_config == {
+        "attention": {"adapter_type": "parallel"}}
+
+
 def test_library_exports_every_declared_symbol():
     """include/magma_hip.h is the contract: every function it declares must be
     exported by the built library and bound by magma_amd.lib (no compute calls here)."""
