@@ -84,8 +84,9 @@ const char* mg_version(void);
  *      gained `first_rows` (before the stream): only the gradients of the first positions (the bottom block of a frozen LM).
  *   7  ragged batches (right-padded prompts of different lengths): mg_attn_decode_bf16, mg_attn_decode_fused_bf16,
  *      mg_decode_attn_gemv_bf16 and mg_sample_finish gained `pos_stride` (before the stream; 0 = one KV write position for the
- *      batch as before, 1 = row b at d_pos[b]); mg_advance_pos gained `B` and `pos_stride` (before the stream).                 */
-#define MG_ABI_VERSION 7
+ *      batch as before, 1 = row b at d_pos[b]); mg_advance_pos gained `B` and `pos_stride` (before the stream).
+ *   8  beam search: added mg_beam_state, mg_beam_topk_f32, mg_beam_finish and mg_kv_reorder_bf16 (nothing moved).            */
+#define MG_ABI_VERSION 8
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -334,6 +335,43 @@ int mg_sample_f32(const float* logits, int64_t ld, int32_t B, int32_t V, float t
 int mg_sample_finish(const int64_t* token, int32_t B, int64_t eos, int32_t* state, int32_t* d_pos, int32_t delta,
                      int64_t* history, int64_t ld_history, int32_t history_cols, int32_t* clear, int32_t n_clear,
                      int32_t clear_stride, int32_t pos_stride, void* stream);
+
+/* Beam search (transformers' GenerationMixin._beam_search, do_sample=False, one eos id; DESIGN.md "Beam search"): three
+ * enqueue-only, graph-capturable launches per token step over R = B * k rows (k = num_beams <= 16, rows sample-major).
+ * mg_beam_topk_f32: per row, the top K2 = 2k candidate scores run[row] + log_softmax(logits[row]) in the order (score
+ *   descending, lower token first) -> cand_score [R, K2] fp32, cand_tok [R, K2] int32.  Needs 2 <= K2 <= min(32, V).
+ * mg_beam_finish: per sample, the top 2k of the k*V candidates (merge of its rows' lists by score descending, then lower flat
+ *   index beam*V + token), then the finish / next-beam / early-stop rules: candidates among the first k that end in eos (or
+ *   reach max_steps) finish with score sum / gen_len^length_penalty and merge into the k finished slots; the best k that do not
+ *   become the running beams (parent[row], token[row] = the fed-back token, run[row]); histories gathered by parent; d_pos
+ *   advanced (pos_stride 0: d_pos[0]; 1: all R entries); state = {step, first step at which generation stops} as in
+ *   mg_sample_finish.  early_stopping: 0 = False (heuristic on the current length), 1 = True, 2 = "never".
+ * mg_kv_reorder_bf16: for every row b with p = parent[b] != b, K / V positions [0, d_pos[p * pos_stride]) of row p (its
+ *   positions before this call) copied into row b, every layer and head; positions of b past that are left alone (caches
+ *   [L, R, H, Smax, 256]; kstage / vstage of the same shape hold the rows that are read by another row and are themselves
+ *   overwritten).  Two launches; any parent map within [0, R), on uniform and per-row positions.
+ *   mg_beam_finish writes identity parents at every step after the recorded stop (the finished slots are final then).        */
+typedef struct mg_beam_state {
+  float* run;           /* [R] running-beam scores (in/out)                                                     */
+  float* fin_score;     /* [R] finished-slot scores, sample-major (k slots per sample)                          */
+  int32_t* fin_flag;    /* [R] 1 = the slot holds a finished hypothesis                                         */
+  int32_t* fin_len;     /* [R] generated length of the slot's hypothesis (eos included)                         */
+  int64_t* fin_tok;     /* [R, ld] tokens of the finished hypotheses (eos after fin_len)                        */
+  int64_t* fin_stage;   /* [R, ld] staging copy                                                                 */
+  int64_t* hist;        /* [R, ld] token history of the running beams                                           */
+  int64_t* hist_stage;  /* [R, ld] staging copy                                                                 */
+  int64_t ld;           /* columns of the four token buffers                                                    */
+  int32_t* unsat;       /* [B] the early-stop heuristic still allows an improvement (latched)                   */
+  int32_t* parent;      /* [R] out: the row each new running row continues                                      */
+  int64_t* token;       /* [R] out: the new last token of each running row                                      */
+} mg_beam_state;
+int mg_beam_topk_f32(const float* logits, int64_t ld, int32_t R, int32_t V, const float* run, int32_t K2, float* cand_score,
+                     int32_t* cand_tok, void* stream);
+int mg_beam_finish(const float* cand_score, const int32_t* cand_tok, int32_t B, int32_t k, int32_t V, int64_t eos,
+                   double length_penalty, int32_t early_stopping, int32_t max_steps, int32_t* state, int32_t* d_pos,
+                   int32_t pos_stride, const mg_beam_state* bs, void* stream);
+int mg_kv_reorder_bf16(mg_bf16* kcache, mg_bf16* vcache, mg_bf16* kstage, mg_bf16* vstage, int32_t L, int32_t R, int32_t H,
+                       int32_t Smax, const int32_t* parent, const int32_t* d_pos, int32_t pos_stride, void* stream);
 
 /* CLIP VisionTransformer front end and attention (encoder_name "clip" = ViT-B/32; reference magma/image_encoders.py:56-63):
  *   patchify   img [B,3,H,W] bf16 NCHW -> rows [B*(H/P)*(W/P), 3*P*P] in (c, py, px) order = the im2col of the stride-P patch

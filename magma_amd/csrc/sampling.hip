@@ -372,3 +372,338 @@ extern "C" int mg_sample_finish(const int64_t* token, int32_t B, int64_t eos, in
   MG_CHECK_LAUNCH();
   return MG_OK;
 }
+
+// ================================================================================================================================
+// Beam search (DESIGN.md "Beam search"): the rule of transformers' vectorised GenerationMixin._beam_search with do_sample=False
+// and one eos id, restated on the host in magma_amd/sampling.py (beam_search), as three enqueue-only launches per token step:
+//   beam_topk_kernel    one workgroup per row (B*k rows): max and logsumexp of the row, then the top 2k of that row's candidate
+//                       scores  run[row] + ((x - max) - lse)  in the order (score descending, lower token first) -- the radix
+//                       descent of sample_kernel's top-k on the order-preserving keys of the SCORES (so that equal fp32 scores
+//                       are ordered by index exactly as the per-sample merge orders them), ties at the threshold cut by index
+//                       with one wave and ballots.  A sample's top 2k over k*V candidates lie in the union of its rows' top 2k.
+//   beam_finish_kernel  one workgroup: per sample, the merge of the k lists by (score desc, flat index beam*V + token asc), the
+//                       finish / next-beam / early-stop rules, the parent map, the token histories gathered by parent, the
+//                       finished hypotheses, the fed-back token, d_pos and the "first step at which generation stops" record.
+//   kv_reorder_kernel   K / V positions [0, d_pos_b) of row parent[b] into row b, every layer, in two launches: rows that are
+//                       read by another row AND are themselves overwritten are staged first; identity rows are skipped.
+namespace {
+
+constexpr int BK_MAX = 16;              // largest num_beams
+constexpr int BK2_MAX = 2 * BK_MAX;
+
+__global__ __launch_bounds__(ST) void beam_topk_kernel(const float* __restrict__ logits, int64_t ld, int V,
+                                                       const float* __restrict__ run, int K2, float* __restrict__ cand_score,
+                                                       int32_t* __restrict__ cand_tok) {
+  __shared__ uint32_t hist32[256];
+  __shared__ float shf[ST / 64];
+  __shared__ uint32_t bc[4];
+  __shared__ int s_cut, s_n;
+  __shared__ uint32_t s_key[BK2_MAX];
+  __shared__ int s_idx[BK2_MAX];
+  __shared__ float s_sc[BK2_MAX];
+  const int tid = threadIdx.x, row = blockIdx.x;
+  const float* x = logits + (int64_t)row * ld;
+  const float r = run[row];
+
+  float mx = -INFINITY;
+  for (int i = tid; i < V; i += ST) mx = fmaxf(mx, x[i]);
+  mx = blk_max(mx, shf);
+  float z = 0.f;
+  for (int i = tid; i < V; i += ST) z += expf(x[i] - mx);
+  z = blk_sum(z, shf);
+  const float lse = logf(z);
+  auto score = [&](int i) -> float { return r + ((x[i] - mx) - lse); };   // log_softmax, then the running score
+
+  // key of the K2-th largest score (MSB-first radix descent, 8 bits per level)
+  uint32_t prefix = 0, mask = 0, remaining = (uint32_t)K2, in_bucket = 0;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    if (tid < 256) hist32[tid] = 0;
+    __syncthreads();
+    for (int i = tid; i < V; i += ST) {
+      const uint32_t k = fkey(score(i));
+      if ((k & mask) == prefix) atomicAdd(&hist32[(k >> shift) & 255], 1u);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      uint32_t rem = remaining; int d = 0;
+      for (int b = 255; b >= 0; --b) {
+        if (hist32[b] >= rem) { d = b; break; }
+        rem -= hist32[b];
+      }
+      bc[0] = (uint32_t)d; bc[1] = rem; bc[2] = hist32[d];
+    }
+    __syncthreads();
+    prefix |= bc[0] << shift; mask |= 255u << shift; remaining = bc[1]; in_bucket = bc[2];
+    __syncthreads();
+  }
+  const uint32_t tk = prefix;
+  // the candidates: every key above tk, and the first `remaining` keys equal to it by index (cut = index of the first tie left out)
+  if (tid == 0) { s_cut = 0x7fffffff; s_n = 0; }
+  __syncthreads();
+  if (in_bucket > remaining && tid < 64) {
+    uint32_t seen = 0;
+    for (int base = 0; base < V; base += 64) {
+      const int i = base + tid;
+      const bool eq = i < V && fkey(score(i)) == tk;
+      const unsigned long long m = __ballot(eq);
+      const uint32_t c = (uint32_t)__popcll(m);
+      if (seen + c > remaining) {
+        if (eq && (uint32_t)__popcll(m & ((1ull << tid) - 1ull)) == remaining - seen) s_cut = i;
+        break;
+      }
+      seen += c;
+    }
+  }
+  __syncthreads();
+  const int cut = s_cut;
+  for (int i = tid; i < V; i += ST) {
+    const float s = score(i);
+    const uint32_t k = fkey(s);
+    if (k > tk || (k == tk && i < cut)) {
+      const int slot = atomicAdd(&s_n, 1);
+      if (slot < BK2_MAX) { s_key[slot] = k; s_idx[slot] = i; s_sc[slot] = s; }
+    }
+  }
+  __syncthreads();
+  const int n = min(s_n, K2);
+  if (tid < n) {      // rank by (score desc, index asc): a fixed order whatever order the atomics handed out the slots in
+    const uint32_t k = s_key[tid]; const int i = s_idx[tid];
+    int rank = 0;
+    for (int j = 0; j < n; ++j) rank += (s_key[j] > k || (s_key[j] == k && s_idx[j] < i)) ? 1 : 0;
+    cand_score[(int64_t)row * K2 + rank] = s_sc[tid];
+    cand_tok[(int64_t)row * K2 + rank] = i;
+  }
+}
+
+struct BeamArgs {
+  const float* cand_score; const int32_t* cand_tok;
+  int B, k, K2, V; int64_t eos; double length_penalty; int early_stopping; int max_steps;
+  int32_t* state; int32_t* d_pos; int n_pos;
+  mg_beam_state s;
+};
+
+MG_DEV bool key_before(uint32_t ka, int ia, uint32_t kb, int ib) { return ka > kb || (ka == kb && ia < ib); }
+
+__global__ __launch_bounds__(512) void beam_finish_kernel(const BeamArgs a) {
+  __shared__ int s_step, s_stopped;
+  __shared__ float t_score[BK2_MAX];
+  __shared__ int t_beam[BK2_MAX], t_tok[BK2_MAX];
+  __shared__ int r_sel[BK_MAX];           // running row q of this sample continues top candidate r_sel[q]
+  __shared__ int f_src[BK_MAX];           // finished slot q: old slot f_src[q] (>= 0) or top candidate -(f_src[q] + 1)
+  __shared__ int g_unsat, g_allfin, g_allhit;
+  // thread 0's working set (LDS, not private arrays: dynamically indexed private arrays would live in scratch)
+  __shared__ bool hit[BK2_MAX], fl[BK_MAX + BK2_MAX];
+  __shared__ float mod[BK2_MAX], val[BK_MAX + BK2_MAX];
+  __shared__ int pick[BK_MAX], olen[BK_MAX];
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int k = a.k, K2 = a.K2, R = a.B * a.k;
+  const int64_t ld = a.s.ld;
+  if (tid == 0) { s_step = a.state[0]; s_stopped = a.state[1] >= 0; g_unsat = 0; g_allfin = 1; g_allhit = 1; }
+  __syncthreads();
+  const int step = s_step;
+  if (s_stopped) {
+    // generation stopped at an earlier step (the host reads the record only every few steps): the finished slots are final,
+    // so nothing is selected or merged any more; identity parents make the reorder launches copy nothing
+    for (int r = tid; r < R; r += nt) a.s.parent[r] = r;
+    if (a.d_pos)
+      for (int b = tid; b < a.n_pos; b += nt) a.d_pos[b] += 1;
+    if (tid == 0) a.state[0] = step + 1;
+    return;
+  }
+  const int cols = min(step, (int)ld);      // columns [0, step) hold the tokens of the steps so far
+  for (int64_t e = tid; e < (int64_t)R * cols; e += nt) {
+    const int64_t rr = e / cols, c = e % cols;
+    a.s.hist_stage[rr * ld + c] = a.s.hist[rr * ld + c];
+    a.s.fin_stage[rr * ld + c] = a.s.fin_tok[rr * ld + c];
+  }
+  __syncthreads();
+  const int gen_len = step + 1;
+  const float den = (float)pow((double)gen_len, a.length_penalty);
+  for (int smp = 0; smp < a.B; ++smp) {
+    const int r0 = smp * k;
+    // ---- top 2k of the sample's k*V candidates: merge of the per-row lists ----
+    if (tid < k * K2) {
+      const int bm = tid / K2;
+      const float sc = a.cand_score[(int64_t)r0 * K2 + tid];
+      const int tok = a.cand_tok[(int64_t)r0 * K2 + tid];
+      const uint32_t kk = fkey(sc);
+      const int flat = bm * a.V + tok;
+      int rank = 0;
+      for (int u = 0; u < k * K2; ++u) {
+        const int bu = u / K2;
+        rank += key_before(fkey(a.cand_score[(int64_t)r0 * K2 + u]), bu * a.V + a.cand_tok[(int64_t)r0 * K2 + u], kk, flat) ? 1 : 0;
+      }
+      if (rank < K2) { t_score[rank] = sc; t_beam[rank] = bm; t_tok[rank] = tok; }
+    }
+    __syncthreads();
+    if (tid == 0) {
+      bool allhit = true;
+      for (int j = 0; j < K2; ++j) { hit[j] = t_tok[j] == a.eos || gen_len >= a.max_steps; allhit = allhit && hit[j]; }
+      // next running beams: the best k after every candidate that hit a stopping criterion lost 1e9
+      for (int j = 0; j < K2; ++j) mod[j] = hit[j] ? t_score[j] + -1.0e9f : t_score[j];
+      for (int j = 0; j < K2; ++j) {
+        int rank = 0;
+        for (int u = 0; u < K2; ++u) rank += key_before(fkey(mod[u]), u, fkey(mod[j]), j) ? 1 : 0;
+        if (rank < k) r_sel[rank] = j;
+      }
+      for (int q = 0; q < k; ++q) {
+        const int j = r_sel[q];
+        a.s.run[r0 + q] = mod[j];
+        a.s.parent[r0 + q] = r0 + t_beam[j];
+        a.s.token[r0 + q] = t_tok[j];
+      }
+      // finished slots: merge the old k with the first k candidates that just finished
+      bool full = true;
+      for (int q = 0; q < k; ++q) {
+        val[q] = a.s.fin_score[r0 + q]; fl[q] = a.s.fin_flag[r0 + q] != 0; olen[q] = a.s.fin_len[r0 + q];
+        full = full && fl[q];
+      }
+      full = full && a.early_stopping == 1;
+      const bool unsat = a.s.unsat[smp] != 0;
+      for (int j = 0; j < K2; ++j) {
+        const bool just = hit[j] && j < k;
+        float v = t_score[j] / den;
+        if (full) v = v + -1.0e9f;
+        if (!unsat) v = v + -1.0e9f;
+        if (!just) v = v + -1.0e9f;
+        val[k + j] = v; fl[k + j] = just;
+      }
+      const int nm = k + K2;
+      for (int e = 0; e < nm; ++e) {
+        int rank = 0;
+        for (int u = 0; u < nm; ++u) rank += key_before(fkey(val[u]), u, fkey(val[e]), e) ? 1 : 0;
+        if (rank < k) pick[rank] = e;
+      }
+      bool allfin = true;
+      float minf = INFINITY;
+      for (int q = 0; q < k; ++q) {
+        const int e = pick[q];
+        a.s.fin_score[r0 + q] = val[e];
+        a.s.fin_flag[r0 + q] = fl[e] ? 1 : 0;
+        a.s.fin_len[r0 + q] = e < k ? olen[e] : gen_len;
+        f_src[q] = e < k ? e : -(e - k + 1);
+        allfin = allfin && fl[e];
+        minf = fminf(minf, val[e]);
+      }
+      // early-stop heuristic on the new state (latched)
+      const int hyp = (a.early_stopping == 2 && a.length_penalty > 0.0) ? a.max_steps : gen_len;
+      const float best = a.s.run[r0] / (float)pow((double)hyp, a.length_penalty);
+      bool any = false;
+      for (int q = 0; q < k; ++q) any = any || best > (fl[pick[q]] ? minf : -1.0e9f);
+      const bool unsat_new = unsat && any;
+      a.s.unsat[smp] = unsat_new ? 1 : 0;
+      if (unsat_new) g_unsat = 1;
+      if (!allfin) g_allfin = 0;
+      if (!allhit) g_allhit = 0;
+    }
+    __syncthreads();
+    // ---- token rows: running histories gathered by parent, finished rows from the old slots or the new candidates ----
+    const int w = cols + 1;
+    for (int e = tid; e < 2 * k * w; e += nt) {
+      const int which = e / (k * w), q = (e / w) % k, c = e % w;
+      if (c >= ld) continue;
+      int64_t v;
+      if (which == 0) {
+        const int j = r_sel[q];
+        v = c < cols ? a.s.hist_stage[(int64_t)(r0 + t_beam[j]) * ld + c] : (int64_t)t_tok[j];
+        a.s.hist[(int64_t)(r0 + q) * ld + c] = v;
+      } else {
+        const int src = f_src[q];
+        if (src >= 0) v = c < cols ? a.s.fin_stage[(int64_t)(r0 + src) * ld + c] : a.eos;
+        else {
+          const int j = -src - 1;
+          v = c < cols ? a.s.hist_stage[(int64_t)(r0 + t_beam[j]) * ld + c] : (int64_t)t_tok[j];
+        }
+        a.s.fin_tok[(int64_t)(r0 + q) * ld + c] = v;
+      }
+    }
+    __syncthreads();
+  }
+  if (a.d_pos)
+    for (int b = tid; b < a.n_pos; b += nt) a.d_pos[b] += 1;
+  if (tid == 0) {
+    const bool go_on = g_unsat && !(g_allfin && a.early_stopping == 1) && !g_allhit;
+    if (!go_on && a.state[1] < 0) a.state[1] = step;
+    a.state[0] = step + 1;
+  }
+}
+
+// grid (H, R, L); phase 0 stages the rows that must be (their own d_pos positions), phase 1 copies every non-identity row b
+// from its parent p: positions [0, d_pos_p) -- what was staged of p, and in beam search d_pos_p == d_pos_b (same sample)
+__global__ __launch_bounds__(256) void kv_reorder_kernel(uint4* __restrict__ kc, uint4* __restrict__ vc, uint4* __restrict__ ks,
+                                                         uint4* __restrict__ vs, int R, int H, int Smax,
+                                                         const int32_t* __restrict__ parent, const int32_t* __restrict__ d_pos,
+                                                         int pos_stride, int phase) {
+  const int h = blockIdx.x, b = blockIdx.y, l = blockIdx.z;
+  auto staged = [&](int row) -> bool {           // row is overwritten and some other row reads it
+    if (parent[row] == row) return false;
+    for (int c = 0; c < R; ++c) if (c != row && parent[c] == row) return true;
+    return false;
+  };
+  const int p = parent[b];
+  if (p < 0 || p >= R) return;                   // written by the bookkeeping launch; never trusted here
+  int n = d_pos[(phase == 0 ? b : p) * pos_stride];
+  n = max(0, min(n, Smax));
+  const int64_t per = (int64_t)256 * 2 / 16;     // uint4 per position (256 bf16)
+  const int64_t cnt = (int64_t)n * per;
+  if (phase == 0) {
+    if (!staged(b)) return;
+    const int64_t off = (((int64_t)l * R + b) * H + h) * Smax * per;
+    for (int64_t i = threadIdx.x; i < cnt; i += blockDim.x) { ks[off + i] = kc[off + i]; vs[off + i] = vc[off + i]; }
+  } else {
+    if (p == b) return;
+    const bool from_stage = staged(p);
+    const int64_t dst = (((int64_t)l * R + b) * H + h) * Smax * per;
+    const int64_t src = (((int64_t)l * R + p) * H + h) * Smax * per;
+    const uint4* sk = from_stage ? ks : kc;
+    const uint4* sv = from_stage ? vs : vc;
+    for (int64_t i = threadIdx.x; i < cnt; i += blockDim.x) { kc[dst + i] = sk[src + i]; vc[dst + i] = sv[src + i]; }
+  }
+}
+
+}  // namespace
+
+extern "C" int mg_beam_topk_f32(const float* logits, int64_t ld, int32_t R, int32_t V, const float* run, int32_t K2,
+                                float* cand_score, int32_t* cand_tok, void* stream) {
+  if (!logits || !run || !cand_score || !cand_tok || R <= 0 || V <= 0 || ld < V)
+    MG_FAIL(MG_ERR_SHAPE, "mg_beam_topk_f32: bad logits / R / V / ld");
+  if (K2 < 2 || K2 > BK2_MAX || K2 > V) MG_FAIL(MG_ERR_SHAPE, "mg_beam_topk_f32: need 2 <= K2 <= min(%d, V), got %d", BK2_MAX, K2);
+  hipLaunchKernelGGL(beam_topk_kernel, dim3(R), dim3(ST), 0, (hipStream_t)stream, logits, ld, V, run, K2, cand_score, cand_tok);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_beam_finish(const float* cand_score, const int32_t* cand_tok, int32_t B, int32_t k, int32_t V, int64_t eos,
+                              double length_penalty, int32_t early_stopping, int32_t max_steps, int32_t* state, int32_t* d_pos,
+                              int32_t pos_stride, const mg_beam_state* bs, void* stream) {
+  if (!cand_score || !cand_tok || !state || !bs || B <= 0 || k < 1 || k > BK_MAX || V < 2 * k || max_steps < 1)
+    MG_FAIL(MG_ERR_SHAPE, "mg_beam_finish: bad arguments (B %d, k %d, V %d, max_steps %d)", B, k, V, max_steps);
+  if (early_stopping < 0 || early_stopping > 2) MG_FAIL(MG_ERR_SHAPE, "mg_beam_finish: early_stopping must be 0, 1 or 2");
+  if (pos_stride != 0 && pos_stride != 1) MG_FAIL(MG_ERR_SHAPE, "mg_beam_finish: pos_stride must be 0 or 1");
+  const mg_beam_state& s = *bs;
+  if (!s.run || !s.fin_score || !s.fin_flag || !s.fin_len || !s.fin_tok || !s.fin_stage || !s.hist || !s.hist_stage ||
+      !s.unsat || !s.parent || !s.token || s.ld < 1)
+    MG_FAIL(MG_ERR_SHAPE, "mg_beam_finish: a beam-state buffer is missing");
+  BeamArgs a{cand_score, cand_tok, B, k, 2 * k, V, eos, length_penalty, early_stopping, max_steps, state, d_pos,
+             pos_stride ? B * k : 1, s};
+  hipLaunchKernelGGL(beam_finish_kernel, dim3(1), dim3(512), 0, (hipStream_t)stream, a);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_kv_reorder_bf16(mg_bf16* kcache, mg_bf16* vcache, mg_bf16* kstage, mg_bf16* vstage, int32_t L, int32_t R,
+                                  int32_t H, int32_t Smax, const int32_t* parent, const int32_t* d_pos, int32_t pos_stride,
+                                  void* stream) {
+  if (!kcache || !vcache || !kstage || !vstage || !parent || !d_pos || L <= 0 || R <= 0 || H <= 0 || Smax <= 0)
+    MG_FAIL(MG_ERR_SHAPE, "mg_kv_reorder_bf16: bad arguments");
+  if (pos_stride != 0 && pos_stride != 1) MG_FAIL(MG_ERR_SHAPE, "mg_kv_reorder_bf16: pos_stride must be 0 or 1");
+  if (!MG_ALIGNED16(kcache) || !MG_ALIGNED16(vcache) || !MG_ALIGNED16(kstage) || !MG_ALIGNED16(vstage))
+    MG_FAIL(MG_ERR_SHAPE, "mg_kv_reorder_bf16: buffers must be 16-byte aligned");
+  if (H > 65535 || L > 65535) MG_FAIL(MG_ERR_SHAPE, "mg_kv_reorder_bf16: grid too large");
+  for (int phase = 0; phase < 2; ++phase) {
+    hipLaunchKernelGGL(kv_reorder_kernel, dim3(H, R, L), dim3(256), 0, (hipStream_t)stream, (uint4*)kcache, (uint4*)vcache,
+                       (uint4*)kstage, (uint4*)vstage, R, H, Smax, parent, d_pos, pos_stride, phase);
+    MG_CHECK_LAUNCH();
+  }
+  return MG_OK;
+}

@@ -57,9 +57,46 @@ class KVCache:
         self.history = torch.zeros(B, Smax, dtype=torch.int64, device=device)   # token selected at step s of the current loop
         self.B, self.Smax = B, Smax
         self.decode_state = None
+        self.beam = None          # BeamBuffers of a beam-search loop (B = samples x num_beams rows), allocated on first use
 
     def __len__(self):
         return self.k.shape[0]
+
+
+class BeamBuffers:
+    """Device state of beam search over a KV cache of R = B * k rows (DESIGN.md "Beam search"): running scores, the k finished
+    slots per sample (scores, flags, lengths, tokens), the early-stop latch per sample, the parent map and the per-row top-2k
+    candidates of a step, staging copies of the token rows, and K / V staging buffers for the cache reorder."""
+
+    def __init__(self, cache: KVCache, k: int, token: torch.Tensor):
+        R, dev = cache.B, cache.k.device
+        assert R % k == 0
+        self.k, self.B = k, R // k
+        f32, i32, i64 = torch.float32, torch.int32, torch.int64
+        self.run = torch.zeros(R, dtype=f32, device=dev)
+        self.fin_score = torch.zeros(R, dtype=f32, device=dev)
+        self.fin_flag = torch.zeros(R, dtype=i32, device=dev)
+        self.fin_len = torch.zeros(R, dtype=i32, device=dev)
+        self.fin_tok = torch.zeros(R, cache.Smax, dtype=i64, device=dev)
+        self.fin_stage = torch.zeros(R, cache.Smax, dtype=i64, device=dev)
+        self.hist_stage = torch.zeros(R, cache.Smax, dtype=i64, device=dev)
+        self.unsat = torch.ones(self.B, dtype=i32, device=dev)
+        self.parent = torch.arange(R, dtype=i32, device=dev)
+        self.cand_score = torch.zeros(R, 2 * k, dtype=f32, device=dev)
+        self.cand_tok = torch.zeros(R, 2 * k, dtype=i32, device=dev)
+        self.kstage, self.vstage = torch.empty_like(cache.k), torch.empty_like(cache.v)
+        self.bufs = dict(run=self.run, fin_score=self.fin_score, fin_flag=self.fin_flag, fin_len=self.fin_len,
+                         fin_tok=self.fin_tok, fin_stage=self.fin_stage, hist=cache.history, hist_stage=self.hist_stage,
+                         unsat=self.unsat, parent=self.parent, token=token)
+
+    def reset(self, eos: int):
+        """State at the start of a generate() call (enqueued, no sync)."""
+        self.run.view(self.B, self.k).fill_(-1e9)[:, 0] = 0.0
+        self.fin_score.fill_(-1e9)
+        self.fin_flag.zero_()
+        self.fin_len.zero_()
+        self.fin_tok.fill_(eos)
+        self.unsat.fill_(1)
 
 
 class _Layer:
@@ -374,8 +411,10 @@ class LMEngine:
     def forward(self, input_ids=None, inputs_embeds=None, labels=None, use_cache=False, past_key_values=None,
                 output_hidden_states=False, cache_hint: Optional[int] = None, reuse_cache: bool = False,
                 return_logits: bool = False, sampling=None, eos_token: Optional[int] = None,
-                seed: Optional[int] = None, feed_back: bool = False, lengths=None) -> LMOutput:
-        """``lengths`` (int [B], 1 <= len_b <= S; prefill with use_cache=True only): the rows of ``inputs_embeds`` are prompts
+                seed: Optional[int] = None, feed_back: bool = False, lengths=None, beam=None) -> LMOutput:
+        """``beam`` = (num_beams, length_penalty, early_stopping, max_steps): beam-search token selection (the rows are
+        samples x num_beams, sample-major; DESIGN.md "Beam search") instead of ``sampling``.
+        ``lengths`` (int [B], 1 <= len_b <= S; prefill with use_cache=True only): the rows of ``inputs_embeds`` are prompts
         of different lengths, right-padded to S.  Row b's logits are those of its position len_b - 1, and the cache keeps one
         write position per row (len_b, then + 1 per step) -- see DESIGN.md, "Ragged batches"."""
         if lengths is not None and (labels is not None or past_key_values is not None or not use_cache):
@@ -397,11 +436,12 @@ class LMEngine:
                     raise ValueError("cached decoding needs at least one new token")
                 rows = []
                 for i in range(T):      # only the LAST position selects a token (history / RNG step / eos latch untouched before)
-                    lg, tok = self.decode(input_ids[:, i:i + 1], past_key_values, sampling=sampling, select=i == T - 1)
+                    lg, tok = self.decode(input_ids[:, i:i + 1], past_key_values, sampling=sampling, select=i == T - 1,
+                                          beam=beam)
                     rows.append(lg.clone())
                 return LMOutput(logits=torch.stack(rows, 1), past_key_values=past_key_values, next_token=tok, loss=None,
                                 eos_state=past_key_values.sample_state)
-            logits, tok = self.decode(None if feed_back else input_ids, past_key_values, sampling=sampling)
+            logits, tok = self.decode(None if feed_back else input_ids, past_key_values, sampling=sampling, beam=beam)
             return LMOutput(logits=logits.unsqueeze(1), past_key_values=past_key_values, next_token=tok, loss=None,
                             eos_state=past_key_values.sample_state)
         if inputs_embeds is None:
@@ -419,7 +459,10 @@ class LMEngine:
                 if seed is not None:
                     cache.seed.fill_(int(seed) & 0x7fffffffffffffff)
                 st = self._ensure_decode_state(cache)      # the first token lands where the decode steps read it back
-                out["next_token"] = self.select_token(logits, cache, sampling, out=st.token)
+                mode = sampling
+                if beam is not None:
+                    mode = self._arm_beam(cache, st, beam)
+                out["next_token"] = self.select_token(logits, cache, mode, out=st.token)
                 out["eos_state"] = cache.sample_state
             return out
         x, hs = self._blocks_prefill(inputs_embeds, None, output_hidden_states)
@@ -602,12 +645,57 @@ class LMEngine:
         st.steps = 0
         return st
 
+    @staticmethod
+    def beam_mode(beam):
+        """("beam", num_beams, length_penalty, early_stopping, max_steps): the token-selection mode (and graph key) of beam search."""
+        from .sampling import check_beam_args
+        k, lp, es, n = beam
+        es = check_beam_args(int(k), 1, es)
+        return ("beam", int(k), float(lp), es, int(n))
+
+    def _arm_beam(self, cache: KVCache, st, beam):
+        """Beam buffers of this cache for num_beams = k (re-allocated -- and the captured steps dropped -- when k changes),
+        reset for a new generate() call.  Returns the selection mode."""
+        mode = self.beam_mode(beam)
+        k = mode[1]
+        if cache.B % k:
+            raise ValueError(f"beam search over {cache.B} cache rows with num_beams = {k}: rows must be samples x num_beams")
+        if 2 * k > self.V:
+            raise ValueError(f"num_beams = {k} needs a vocabulary of at least {2 * k} tokens")
+        if cache.beam is None or cache.beam.k != k:
+            cache.beam = BeamBuffers(cache, k, st.token)
+            st.graphs.clear()
+        cache.beam.reset(cache.eos)
+        return mode
+
+    def _select_beam(self, logits: torch.Tensor, cache: KVCache, mode, advance: bool):
+        """The beam step's three launches: per-row top 2k, the bookkeeping of every sample, the K / V reorder by parent."""
+        bm = cache.beam
+        _, k, lp, es, max_steps = mode
+        ops.beam_topk(logits, bm.run, bm.cand_score, bm.cand_tok)
+        ops.beam_finish(bm.cand_score, bm.cand_tok, bm.B, k, logits.shape[1], cache.eos, lp, es, max_steps, cache.sample_state,
+                        bm.bufs, d_pos=cache.d_pos if advance else None, pos_stride=cache.pos_stride)
+        ops.kv_reorder(cache.k, cache.v, bm.kstage, bm.vstage, bm.parent, cache.d_pos, pos_stride=cache.pos_stride)
+        return bm.bufs["token"]
+
+    def beam_results(self, cache: KVCache, n_ret: int):
+        """(tokens (B*n_ret, n) int64 eos-padded, scores (B*n_ret,) fp32, lengths (B*n_ret,) int64) of the best n_ret finished
+        hypotheses per sample (slots are kept in score order); n = the longest of them.  One host sync."""
+        bm = cache.beam
+        lens = bm.fin_len.view(bm.B, bm.k)[:, :n_ret].reshape(-1).to(torch.int64)
+        n = max(1, int(lens.max()))
+        toks = bm.fin_tok.view(bm.B, bm.k, -1)[:, :n_ret, :n].reshape(bm.B * n_ret, n)
+        return toks.clone(), bm.fin_score.view(bm.B, bm.k)[:, :n_ret].reshape(-1).clone(), lens
+
     def select_token(self, logits: torch.Tensor, cache: KVCache, mode, out: Optional[torch.Tensor] = None,
                      advance: bool = False, clear: Optional[torch.Tensor] = None) -> torch.Tensor:
         """next token of every row from fp32 logits (B, V): greedy argmax (mode None; reference sampling.py:96-97) or the
         sampled branch (mode = (temperature, top_k, top_p); :99-107), then the loop bookkeeping in one small launch
         (all-eos step, step counter, token history, and -- inside a decode step -- the KV write position).  Enqueue-only:
-        used inside the captured token step and, eagerly, on the prefill logits."""
+        used inside the captured token step and, eagerly, on the prefill logits.  A beam mode (beam_mode) runs the beam step
+        instead: the selected token of every row lands in cache.beam's token buffer (the decode state's st.token)."""
+        if isinstance(mode, tuple) and mode and mode[0] == "beam":
+            return self._select_beam(logits, cache, mode, advance)
         if mode is None:
             tok = ops.argmax(logits, out=out)
         else:
@@ -768,7 +856,8 @@ class LMEngine:
             st = cache.decode_state = self._alloc_decode_state(cache)
         return st
 
-    def decode(self, input_ids: Optional[torch.Tensor], cache: KVCache, use_graph: bool = True, sampling=None, select: bool = True):
+    def decode(self, input_ids: Optional[torch.Tensor], cache: KVCache, use_graph: bool = True, sampling=None, select: bool = True,
+               beam=None):
         """One cached step.  Returns (fp32 logits (B,V) view, selected token (B,) view: greedy, or sampled when
         ``sampling = (temperature, top_k, top_p)``); both are overwritten by the next step.  ``input_ids=None`` feeds the
         previously selected tokens back without leaving the device.  ``select=False`` (teacher-forced positions of a
@@ -790,6 +879,10 @@ class LMEngine:
         if not feed_back:
             st.ids.copy_(input_ids.reshape(cache.B, 1))
         mode = None if sampling is None else (float(sampling[0]), int(sampling[1]), float(sampling[2]))
+        if beam is not None:
+            mode = self.beam_mode(beam)
+            if cache.beam is None or cache.beam.k != mode[1]:
+                raise ValueError("beam decoding needs a cache armed for this num_beams (prefill with eos_token= and beam=)")
         if not select:
             if feed_back:
                 raise ValueError("decode(select=False) needs input_ids: there is no selected token to feed back")

@@ -19,7 +19,7 @@ MG_A_DENSE, MG_A_CONV3X3 = 0, 1
 MG_AUX_NONE, MG_AUX_RELU_GATE, MG_AUX_GELU_GRAD, MG_AUX_MUL, MG_AUX_QUICK_GELU_GRAD = 0, 1, 2, 3, 4
 
 
-ABI_VERSION = 7      # include/magma_hip.h MG_ABI_VERSION
+ABI_VERSION = 8      # include/magma_hip.h MG_ABI_VERSION
 
 
 class MagmaHipError(RuntimeError):
@@ -50,6 +50,12 @@ class RelayoutJob(C.Structure):          # mg_relayout_job
 class BnFoldJob(C.Structure):            # mg_bn_fold_job
     _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p), ("mean", C.c_void_p), ("var", C.c_void_p),
                 ("scale", C.c_void_p), ("shift", C.c_void_p), ("eps", C.c_float), ("C", C.c_int32), ("first_block", C.c_int64)]
+
+
+class BeamState(C.Structure):            # mg_beam_state
+    _fields_ = [("run", C.c_void_p), ("fin_score", C.c_void_p), ("fin_flag", C.c_void_p), ("fin_len", C.c_void_p),
+                ("fin_tok", C.c_void_p), ("fin_stage", C.c_void_p), ("hist", C.c_void_p), ("hist_stage", C.c_void_p),
+                ("ld", C.c_int64), ("unsat", C.c_void_p), ("parent", C.c_void_p), ("token", C.c_void_p)]
 
 
 class GemmDesc(C.Structure):
@@ -112,6 +118,9 @@ SYMBOLS = {
     "mg_advance_pos": (C.c_int, [_vp, _i32, _i32, _i32, _vp]),
     "mg_sample_f32": (C.c_int, [_vp, _i64, _i32, _i32, _f32, _i32, C.c_double, _vp, _vp, _vp, _vp, _i64, _vp]),
     "mg_sample_finish": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "mg_beam_topk_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "mg_beam_finish": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, C.c_double, _i32, _i32, _vp, _vp, _i32, C.POINTER(BeamState), _vp]),
+    "mg_kv_reorder_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "mg_patchify_bf16": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "mg_vit_embed_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "mg_attn_small_bf16": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),

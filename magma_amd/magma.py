@@ -274,14 +274,17 @@ class Magma(nn.Module):
     @torch.no_grad()
     def generate(self, embeddings, max_steps: int = 100, temperature: float = 0.7, top_k: int = 0,
                  top_p: float = 0.9, decode: bool = True, stop_on_eos: bool = True, seed: int = None,
-                 eos_check_every: int = None, lengths=None):
+                 eos_check_every: int = None, lengths=None, num_beams: int = 1, length_penalty: float = 1.0,
+                 early_stopping=False, num_return_sequences: int = 1, return_scores: bool = False):
         """reference magma.py:214-236 (+ stop_on_eos / seed / eos_check_every / lengths, see sampling.generate).
         ``lengths``: prompts of different lengths, right-padded (embed_batch); ``embeddings`` may also be a list of
-        per-sample (1, s_i, d) tensors."""
+        per-sample (1, s_i, d) tensors.  ``num_beams`` > 1: beam search (length_penalty, early_stopping,
+        num_return_sequences, return_scores: see sampling.generate)."""
         torch.cuda.set_device(self.device)
         return generate(self, embeddings=embeddings, max_steps=max_steps, temperature=temperature, top_k=top_k,
                         top_p=top_p, decode=decode, stop_on_eos=stop_on_eos, seed=seed, eos_check_every=eos_check_every,
-                        lengths=lengths)
+                        lengths=lengths, num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping,
+                        num_return_sequences=num_return_sequences, return_scores=return_scores)
 
     # ------------------------------------------------------------- forward
     def forward(self, images=None, captions=None, output_hidden_states: bool = False, input_embeddings=None,

@@ -541,6 +541,61 @@ def advance_pos(d_pos: torch.Tensor, delta: int = 1, *, pos_stride: int = 0):
     check(L.load().mg_advance_pos(d_pos.data_ptr(), delta, d_pos.numel(), ps, _stream()), "mg_advance_pos")
 
 
+def beam_topk(logits: torch.Tensor, run: torch.Tensor, cand_score: torch.Tensor, cand_tok: torch.Tensor):
+    """Per row: the top K2 = cand_score.shape[1] scores run[row] + log_softmax(logits[row]) (score desc, lower token first)."""
+    _need_gpu(logits, run, cand_score, cand_tok)
+    assert logits.dtype == torch.float32 and logits.ndim == 2 and logits.stride(1) == 1
+    R, V = logits.shape
+    assert run.dtype == torch.float32 and run.is_contiguous() and run.numel() == R
+    assert cand_score.dtype == torch.float32 and cand_tok.dtype == torch.int32 and cand_score.is_contiguous() and cand_tok.is_contiguous()
+    assert cand_score.shape == cand_tok.shape and cand_score.ndim == 2 and cand_score.shape[0] == R
+    check(L.load().mg_beam_topk_f32(logits.data_ptr(), logits.stride(0), R, V, run.data_ptr(), cand_score.shape[1],
+                                    cand_score.data_ptr(), cand_tok.data_ptr(), _stream()), "mg_beam_topk_f32")
+
+
+EARLY_STOPPING_CODES = {False: 0, True: 1, "never": 2}
+
+
+def beam_finish(cand_score: torch.Tensor, cand_tok: torch.Tensor, B: int, k: int, V: int, eos: int, length_penalty: float,
+                early_stopping, max_steps: int, state: torch.Tensor, bufs: dict, d_pos: Optional[torch.Tensor] = None,
+                pos_stride: int = 0):
+    """Beam bookkeeping of one token step (mg_beam_finish).  ``bufs``: run, fin_score, fin_flag, fin_len, fin_tok, fin_stage,
+    hist, hist_stage, unsat, parent, token (BeamBuffers.as_dict())."""
+    R = B * k
+    _need_gpu(cand_score, cand_tok, state, d_pos, *bufs.values())
+    assert cand_score.shape == (R, 2 * k) and cand_tok.shape == (R, 2 * k)
+    es = EARLY_STOPPING_CODES[early_stopping]
+    ps = 0 if d_pos is None else _pos_stride(d_pos, R, pos_stride)
+    f32, i32, i64 = torch.float32, torch.int32, torch.int64
+    for name, dt, n in (("run", f32, R), ("fin_score", f32, R), ("fin_flag", i32, R), ("fin_len", i32, R), ("unsat", i32, B),
+                        ("parent", i32, R), ("token", i64, R)):
+        t = bufs[name]
+        assert t.dtype == dt and t.is_contiguous() and t.numel() == n, name
+    ld = bufs["hist"].shape[1]
+    for name in ("fin_tok", "fin_stage", "hist", "hist_stage"):
+        t = bufs[name]
+        assert t.dtype == i64 and t.is_contiguous() and t.shape == (R, ld), name
+    assert state.dtype == i32 and state.numel() >= 2
+    bs = L.BeamState(*(bufs[n].data_ptr() for n in ("run", "fin_score", "fin_flag", "fin_len", "fin_tok", "fin_stage", "hist",
+                                                    "hist_stage")), ld, bufs["unsat"].data_ptr(), bufs["parent"].data_ptr(),
+                     bufs["token"].data_ptr())
+    check(L.load().mg_beam_finish(cand_score.data_ptr(), cand_tok.data_ptr(), B, k, V, int(eos), float(length_penalty), es,
+                                  int(max_steps), state.data_ptr(), _p(d_pos), ps, C.byref(bs), _stream()), "mg_beam_finish")
+
+
+def kv_reorder(kcache: torch.Tensor, vcache: torch.Tensor, kstage: torch.Tensor, vstage: torch.Tensor, parent: torch.Tensor,
+               d_pos: torch.Tensor, *, pos_stride: int = 0):
+    """Row b of every layer's K / V cache [L, R, H, Smax, 256] gets positions [0, d_pos_b) of row parent[b] (parent[b] != b)."""
+    _need_gpu(kcache, vcache, kstage, vstage, parent, d_pos)
+    Lr, R, H, Smax, hd = kcache.shape
+    assert hd == 256 and kcache.dtype == BF16 and all(t.shape == kcache.shape and t.dtype == BF16 and t.is_contiguous()
+                                                      for t in (kcache, vcache, kstage, vstage))
+    assert parent.dtype == torch.int32 and parent.is_contiguous() and parent.numel() == R
+    ps = _pos_stride(d_pos, R, pos_stride)
+    check(L.load().mg_kv_reorder_bf16(kcache.data_ptr(), vcache.data_ptr(), kstage.data_ptr(), vstage.data_ptr(), Lr, R, H, Smax,
+                                      parent.data_ptr(), d_pos.data_ptr(), ps, _stream()), "mg_kv_reorder_bf16")
+
+
 def patchify(img: torch.Tensor, P: int) -> torch.Tensor:
     """img [B,3,H,W] bf16 -> [B*(H/P)*(W/P), 3*P*P] rows in (c, py, px) order (im2col of the stride-P patch conv)."""
     _need_gpu(img)

@@ -10,7 +10,7 @@ a device-side record read every few steps.  ``top_k_filter`` / ``top_p_filter``
 below are the host statements of the same rules (pinned to the reference's own
 functions, tests/test_oracle_pins.py) and serve LM objects other than the engine."""
 import os
-from typing import List, Tuple, Union
+from typing import Callable, List, Tuple, Union
 
 import torch
 import torch.nn.functional as F
@@ -69,11 +69,150 @@ def pad_ragged(embeddings) -> Tuple[torch.Tensor, torch.Tensor]:
     return out, lengths
 
 
+MAX_BEAMS = 16
+
+
+def check_beam_args(num_beams: int, num_return_sequences: int, early_stopping):
+    """ValueError for arguments beam search does not take; returns early_stopping normalised to True / False / "never"."""
+    if not isinstance(num_beams, int) or num_beams < 1:
+        raise ValueError(f"num_beams must be an integer >= 1, got {num_beams!r}")
+    if num_beams > MAX_BEAMS:
+        raise ValueError(f"num_beams must be at most {MAX_BEAMS}, got {num_beams}")
+    if not isinstance(num_return_sequences, int) or num_return_sequences < 1 or num_return_sequences > num_beams:
+        raise ValueError(f"num_return_sequences must lie in [1, num_beams = {num_beams}], got {num_return_sequences!r}")
+    if isinstance(early_stopping, str):
+        if early_stopping != "never":
+            raise ValueError(f"early_stopping must be True, False or 'never', got {early_stopping!r}")
+        return early_stopping
+    if early_stopping not in (True, False):
+        raise ValueError(f"early_stopping must be True, False or 'never', got {early_stopping!r}")
+    return bool(early_stopping)
+
+
+def reorder_past(past, rows: torch.Tensor):
+    """A KV cache whose batch rows are rearranged by ``rows`` (row b <- old row rows[b]): transformers Cache objects
+    (reorder_cache), or nested lists / tuples of (batch, ...) tensors."""
+    if hasattr(past, "reorder_cache"):
+        past.reorder_cache(rows)
+        return past
+    if isinstance(past, (list, tuple)):
+        return type(past)(reorder_past(p, rows) for p in past)
+    if torch.is_tensor(past):
+        return past.index_select(0, rows.to(past.device))
+    raise TypeError(f"cannot reorder a cache of type {type(past).__name__} for beam search")
+
+
+@torch.no_grad()
+def beam_search(step: Callable, batch_size: int, num_beams: int, max_steps: int, eos_token: int, length_penalty: float = 1.0,
+                early_stopping=False, num_return_sequences: int = 1, record: list = None):
+    """Beam search, the rule of transformers' vectorised ``GenerationMixin._beam_search`` called with do_sample=False, one eos
+    id and the prompt passed as embeddings (prompt length 0: lengths count generated tokens only), in the same fp32 torch
+    arithmetic.  This is the host statement the device kernels (csrc/sampling.hip, beam_*) are tested against.
+
+    ``step(parents, tokens)`` returns the fp32 logits (B*k, V) of the running rows (sample-major, k = num_beams): first
+    ``step(None, None)`` (the prompts, each repeated k times), then ``parents`` (B*k,) int64 -- the row each new row
+    continues, its cache must be reordered so -- and ``tokens`` (B*k,), the last token of each row.
+
+    Per step and sample: the top 2k of the k*V candidates running_score[beam] + log_softmax(logits[beam]) (running scores
+    start at [0, -1e9, ...]: the first step expands beam 0 only); a candidate among the first k that ends in eos (or reaches
+    max_steps) finishes with score sum_logprobs / gen_len ** length_penalty and merges into the k finished slots; the best k
+    that do not end in eos run on.  early_stopping True: a sample stops taking hypotheses once its k slots are full; False:
+    once the best running beam, scored at the current length, cannot beat the worst finished one; "never": the same at
+    max_steps when length_penalty > 0.
+
+    Returns (sequences (B*n_ret, n) int64, eos-padded, n = the longest returned hypothesis; scores (B*n_ret,) fp32;
+    lengths (B*n_ret,) int64), the best n_ret = num_return_sequences hypotheses per sample in score order.
+
+    ``record`` (a list): one dict per step is appended with the values every decision of that step compared -- the top 2k + 1
+    candidate scores per sample, the merged finished-slot scores, the early-stop comparison and whether a candidate finished
+    or hit eos outside the first k -- for beam_margin() and for tests that must show which rules a run exercised."""
+    early_stopping = check_beam_args(num_beams, num_return_sequences, early_stopping)
+    B, k = batch_size, num_beams
+    K2 = 2 * k
+    top_mask = torch.arange(K2) < k
+    run = torch.zeros(B, k)
+    run[:, 1:] = -1e9
+    fin_score = torch.full((B, k), -1e9)
+    fin_flag = torch.zeros(B, k, dtype=torch.bool)
+    fin_len = torch.zeros(B, k, dtype=torch.int64)
+    seq = torch.full((B, k, max_steps), eos_token, dtype=torch.int64)
+    fin_seq = seq.clone()
+    unsat = torch.ones(B, 1, dtype=torch.bool)
+    logits = step(None, None)
+    for t in range(max_steps):
+        V = logits.shape[-1]
+        lp = F.log_softmax(logits.float().cpu(), dim=-1).view(B, k, V) + run[:, :, None]
+        flat = lp.reshape(B, k * V)
+        top_s, top_i = torch.topk(flat, K2)
+        beam, tok = top_i // V, top_i % V
+        cand_seq = torch.take_along_dim(seq, beam[:, :, None], dim=1)
+        cand_seq[:, :, t] = tok
+        hits = (tok == eos_token) | (t + 1 >= max_steps)
+        # running beams: the best k that did not finish
+        mod = top_s + hits.to(torch.float32) * -1.0e9
+        nxt = torch.topk(mod, k)[1]
+        seq = torch.take_along_dim(cand_seq, nxt[:, :, None], dim=1)
+        run = torch.take_along_dim(mod, nxt, dim=1)
+        parent = torch.take_along_dim(beam, nxt, dim=1)
+        # finished slots
+        just = hits & top_mask[None, :]
+        v = top_s / ((t + 1) ** length_penalty)
+        v += (torch.all(fin_flag, dim=-1, keepdim=True) & (early_stopping is True)).to(torch.float32) * -1.0e9
+        v += (~unsat).to(torch.float32) * -1.0e9
+        v += (~just) * -1.0e9
+        m_score = torch.cat((fin_score, v), dim=1)
+        pick = torch.topk(m_score, k)[1]
+        fin_seq = torch.take_along_dim(torch.cat((fin_seq, cand_seq), dim=1), pick[:, :, None], dim=1)
+        fin_score = torch.take_along_dim(m_score, pick, dim=1)
+        fin_flag = torch.take_along_dim(torch.cat((fin_flag, just), dim=1), pick, dim=1)
+        fin_len = torch.take_along_dim(torch.cat((fin_len, torch.full((B, K2), t + 1)), dim=1), pick, dim=1)
+        # early-stop heuristic (latched), then the stop rule of the whole batch
+        hyp = max_steps if (early_stopping == "never" and length_penalty > 0.0) else t + 1
+        best = run[:, :1] / (hyp ** length_penalty)
+        worst = torch.where(fin_flag, torch.min(fin_score, dim=1, keepdim=True)[0], -1.0e9)
+        if record is not None:
+            record.append(dict(top=torch.topk(flat, min(K2 + 1, k * V)).values, merged=m_score, best=best.clone(),
+                               worst=worst.clone(), unsat=unsat.clone(), finished=just.clone(),
+                               eos_outside=(tok[:, k:] == eos_token).clone(), step=t))
+        unsat = unsat & torch.any(best > worst, dim=-1, keepdim=True)
+        go_on = bool(torch.any(unsat)) and not (bool(torch.all(fin_flag)) and early_stopping is True) and not bool(torch.all(hits))
+        if not go_on:
+            break
+        rows = (parent + torch.arange(B)[:, None] * k).reshape(-1)
+        logits = step(rows, seq[:, :, t].reshape(-1))
+    n_ret = num_return_sequences
+    lens = fin_len[:, :n_ret].reshape(-1)
+    n = int(lens.max())
+    return fin_seq[:, :n_ret, :n].reshape(B * n_ret, n), fin_score[:, :n_ret].reshape(-1).clone(), lens
+
+
+def beam_margin(record: list) -> float:
+    """Smallest gap between two values that a decision of a recorded beam_search run compared: consecutive top-2k+1 candidate
+    scores of a sample, consecutive real finished-slot scores, and the early-stop comparison (values at -1e9 are placeholders
+    and are left out).  A run on other arithmetic (bf16 logits) makes the same decisions while its scores stay within half of
+    this of the recorded ones."""
+    gaps = [float("inf")]
+    for r in record:
+        for row in r["top"]:
+            v = row[row > -1e8]
+            if v.numel() > 1:
+                gaps.append(float((v[:-1] - v[1:]).min()))
+        for row in r["merged"]:
+            v = torch.sort(row[row > -1e8], descending=True).values
+            if v.numel() > 1:
+                gaps.append(float((v[:-1] - v[1:]).min()))
+        live = r["unsat"][:, 0] & (r["worst"] > -1e8).all(-1)
+        if bool(live.any()):
+            gaps.append(float((r["best"][live] - r["worst"][live].min(-1, keepdim=True).values).abs().min()))
+    return min(gaps)
+
+
 @torch.no_grad()
 def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, top_k: int = 0,
              top_p: float = 0.9, eos_token: int = None, decode: bool = True,
              stop_on_eos: bool = True, seed: int = None, eos_check_every: int = None,
-             lengths=None) -> Union[List[str], torch.Tensor]:
+             lengths=None, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False,
+             num_return_sequences: int = 1, return_scores: bool = False) -> Union[List[str], torch.Tensor]:
     """reference sampling.py:43-121.  Token selection (argmax, or top-k / the reference's top-p rule / softmax /
     multinomial) and the ``(next_token == eos).all()`` test run on the device inside the captured token step; the host
     reads the recorded "first all-eos step" every ``eos_check_every`` steps (default 8, MAGMA_EOS_CHECK_EVERY) instead of
@@ -83,8 +222,19 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     Ragged batches (prompts of different lengths): ``lengths`` (int [B]) gives the prompt length of every row of the
     right-padded ``embeddings`` (B, S_max, d); ``embeddings`` may also be a list of (1, s_i, d) / (s_i, d) tensors, padded
     here.  Row b of the output is then image_token x len_b, the generated tokens, eos up to the width S_max + n (n = steps
-    run).  Needs the HIP engine (an LM object without device token selection raises)."""
+    run).  Needs the HIP engine (an LM object without device token selection raises).
+
+    Beam search (``num_beams`` > 1, at most 16; DESIGN.md "Beam search"): the rule of transformers' ``_beam_search`` with
+    do_sample=False (``beam_search`` above), ``length_penalty`` / ``early_stopping`` (True, False, "never") as there.
+    temperature, top_k, top_p and seed do not apply.  Returns the best ``num_return_sequences`` hypotheses of every sample,
+    sample-major: B * n_ret strings, or (B * n_ret, s + n) ids laid out as above (n = the longest returned hypothesis);
+    ``return_scores=True`` returns (output, fp32 scores (B * n_ret,)) -- with num_beams=1 that runs the beam rule with one
+    beam.  The HIP engine runs the whole beam step on the device; any other LM object runs the host statement."""
     eos_token = eos_token or model.eos_token
+    early_stopping = check_beam_args(num_beams, num_return_sequences, early_stopping)
+    if num_beams > 1 or return_scores:
+        return _generate_beam(model, embeddings, max_steps, eos_token, decode, eos_check_every, lengths, num_beams,
+                              float(length_penalty), early_stopping, num_return_sequences, return_scores)
     was_training = model.training
     if isinstance(embeddings, (list, tuple)):
         embeddings, derived = pad_ragged(embeddings)
@@ -162,3 +312,65 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
         out = [model.tokenizer.decode(remove_tokens_after_eos(row, eos_token, model.image_token)) for row in out]
     model.train(was_training)
     return out
+
+
+@torch.no_grad()
+def _generate_beam(model, embeddings, max_steps, eos_token, decode, eos_check_every, lengths, k, length_penalty,
+                   early_stopping, n_ret, return_scores):
+    was_training = model.training
+    if isinstance(embeddings, (list, tuple)):
+        embeddings, derived = pad_ragged(embeddings)
+        if lengths is not None and not torch.equal(torch.as_tensor(lengths).cpu().to(torch.int64).view(-1), derived):
+            raise ValueError(f"lengths {list(lengths)} do not match the per-sample embeddings ({derived.tolist()})")
+        lengths = derived
+    b, s, _ = embeddings.shape
+    dev = embeddings.device
+    on_device = getattr(model.lm, "device_token_selection", False)
+    if lengths is not None:
+        if not on_device:
+            raise ValueError("generate(lengths=...) needs the HIP engine's LM (per-row KV positions)")
+        from .engine import LMEngine
+        lengths = LMEngine.check_lengths(lengths, b, s)
+    model.eval()
+    emb = embeddings.repeat_interleave(k, dim=0)           # B prompts -> B*k rows, sample-major
+    if on_device:
+        mode = (k, length_penalty, early_stopping, int(max_steps))
+        every = eos_check_every or int(os.environ.get("MAGMA_EOS_CHECK_EVERY", "8"))
+        kw = {} if lengths is None else {"lengths": lengths.repeat_interleave(k)}
+        for i in range(max_steps):
+            if i == 0:
+                o = model.lm(inputs_embeds=emb, use_cache=True, past_key_values=None, cache_hint=max_steps, reuse_cache=True,
+                             eos_token=eos_token, beam=mode, **kw)
+            else:
+                o = model.lm(input_ids=None, use_cache=True, past_key_values=past, feed_back=True, beam=mode)
+            past = o.past_key_values
+            if ((i + 1) % every == 0 or i + 1 == max_steps) and int(o.eos_state[1]) >= 0:     # one host sync per `every` steps
+                break
+        toks, scores, lens = model.lm.engine.beam_results(past, n_ret)
+    else:
+        cache = {}
+
+        def step(rows, tokens):
+            if rows is None:
+                o = model.lm(inputs_embeds=emb, use_cache=True, past_key_values=None)
+            else:
+                o = model.lm(input_ids=tokens[:, None].to(dev), use_cache=True,
+                             past_key_values=reorder_past(cache["past"], rows.to(dev)))
+            cache["past"] = o.past_key_values
+            return o.logits[:, -1, :].float()
+
+        toks, scores, lens = beam_search(step, b, k, max_steps, eos_token, length_penalty, early_stopping, n_ret)
+    toks, lens = toks.to(dev), lens.to(dev)
+    n = toks.shape[1]
+    out = torch.full((b * n_ret, s + n), eos_token, dtype=torch.long, device=dev)
+    if lengths is None:
+        out[:, :s] = model.image_token
+        out[:, s:] = toks
+    else:                                                    # ragged: row j of sample b starts after len_b image tokens
+        lens_r = lengths.to(dev).repeat_interleave(n_ret)[:, None]
+        out.masked_fill_(torch.arange(s + n, device=dev)[None, :] < lens_r, model.image_token)
+        out.scatter_(1, lens_r + torch.arange(n, device=dev)[None, :], toks)
+    if decode:
+        out = [model.tokenizer.decode(remove_tokens_after_eos(row, eos_token, model.image_token)) for row in out]
+    model.train(was_training)
+    return (out, scores.float().cpu()) if return_scores else out
