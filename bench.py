@@ -12,7 +12,13 @@ Inputs and weights are resident in HBM before the timed region.  Multi-GPU =
 independent replicas (the inference path has no exchange step): value is the
 sum over ranks / max-over-ranks time, scaling "weak".
 
-Extra objects on the JSON line:
+A plain run does only what the headline needs: set up, warm up, time the steps, write --dump-outputs, print the
+line (metric, value, unit, ms_per_step, per_rank_ms, config).  With --train-only the headline is the training step
+(train.full_S2048 and its data-parallel fields).  Everything else -- the roofline objects, the sampled / host-input /
+fp8 generate legs, the training leg with its forward-only, fp8 and truncated variants, config1, cpu_baseline, the
+384^2 and MAGMA_v2 variants -- runs only with --full, as selected by the options below.
+
+Extra objects on the JSON line (--full):
   roofline      dominant kernel = the decode weight-streaming GEMM (HBM-bound):
                 algorithmic bytes = every LM + adapter + head weight byte once
                 per token step (12.16 GB at full size) / time of the CAPTURED
@@ -59,16 +65,20 @@ def parse():
     ap.add_argument("--res", type=int, default=224, help="image resolution (224 per BASELINE.json; 384 = model native)")
     ap.add_argument("--config", default="MAGMA_v1")
     ap.add_argument("--layers", type=int, default=None, help="debug: fewer LM layers (result is then NOT the metric)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline objects, the sampled / host-input / fp8 generate "
+                         "legs, the training leg (and its variants), config1, cpu_baseline, the 384^2 and MAGMA_v2 variants; "
+                         "the options below select among them.  Without it a run times the headline alone")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--train-steps", type=int, default=5, help="timed training steps for the extra 'train' object (0 = skip)")
+    ap.add_argument("--train-steps", type=int, default=5, help="--full: timed training steps for the extra 'train' object (0 = skip)")
     ap.add_argument("--train-warmup", type=int, default=2, help="untimed training steps in front of the timed ones")
     ap.add_argument("--train-batch", type=int, default=16, help="per-GPU micro-batch of the training step (BASELINE config[2])")
     ap.add_argument("--train-truncate", action=argparse.BooleanOptionalAction, default=True,
-                    help="also time the exact-truncation variant (SURVEY Q3: identical loss and gradients, the sequence is cut "
+                    help="--full: also time the exact-truncation variant (SURVEY Q3: identical loss and gradients, the sequence is cut "
                          "after the longest caption); reported as train.truncated, never as the headline")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--fp8", choices=["attn", "all", "off"], default="all",
-                    help="also time BASELINE config[4]: fp8 (e4m3) MFMA for QKV/out_proj/adapter GEMMs ('attn') or every "
+                    help="--full: also time BASELINE config[4]: fp8 (e4m3) MFMA for QKV/out_proj/adapter GEMMs ('attn') or every "
                          "block GEMM ('all'), W8A16 decode and the fp8 training step; reported in extra objects "
                          "('generate_fp8', 'train.forward_only_fp8', 'train.full_S2048_fp8'), never in 'value'")
     ap.add_argument("--rendezvous-only", action="store_true",
@@ -76,14 +86,14 @@ def parse():
                          "the process group, run the bench's barrier / MAX-over-ranks collectives and rank 0 prints a line with "
                          "n_gpus = N and value = null; no model, no GPU needed with MAGMA_BENCH_BACKEND=gloo")
     ap.add_argument("--with-cpu-baseline", action="store_true",
-                    help="--rendezvous-only: rank 0 also measures cpu_baseline where a real run does (after the last collective, the "
+                    help="--rendezvous-only: rank 0 also measures cpu_baseline where a --full run does (after the last collective, the "
                          "other ranks waiting at the final barrier) -- the N > 1 control flow of that leg without a GPU")
     ap.add_argument("--train-only", action="store_true",
                     help="only the training leg (BASELINE's 'train images/sec, whole node'): metric / value / ms_per_step / roofline "
                          "of the line are the training step's; the generate legs, variants and config1 are skipped -- a multi-GPU "
-                         "record that fits a short lease")
+                         "record that fits a short lease (its forward-only, fp8 and truncated legs, roofline and cpu_baseline: --full)")
     ap.add_argument("--variants", action=argparse.BooleanOptionalAction, default=True,
-                    help="N = 1 only: also time BASELINE config[3] (MAGMA_v2: attention + MLP adapters) and the model-native 384^2 "
+                    help="--full, N = 1 only: also time BASELINE config[3] (MAGMA_v2: attention + MLP adapters) and the model-native 384^2 "
                          "images as extra objects ('magma_v2', 'generate_res384'); never in 'value'")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64; see the module docstring)")
@@ -348,30 +358,31 @@ def bench_train(model, args, rank, world, dev):
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    # forward only (eval mode, same batch): the north-star's "GPT-J + adapter forward" MFMA fraction
-    eng.eval()
-    with torch.no_grad():
-        model(images, caps)
-        sync()
-        t0 = time.perf_counter()
-        for _ in range(2):
+    if args.full:
+        # forward only (eval mode, same batch): the north-star's "GPT-J + adapter forward" MFMA fraction
+        eng.eval()
+        with torch.no_grad():
             model(images, caps)
-        sync()
-    dtf = (time.perf_counter() - t0) / 2
-    L, d, ff = model.lm.config.num_layers, model.lm.config.hidden_size, model.lm.config.intermediate_size
-    r = sum(ad.N for ad in (model.lm.engine.layers[0].mlp_adapter or ())[:1]) + sum(ad.N for ad in (model.lm.engine.layers[0].attn_adapter or ())[:1])
-    f_fwd = B * (S * L * (8 * d * d + 4 * d * ff + 4 * d * r) + 4 * L * d * S * S + 47.72e9 * (args.res / 224.0) ** 2)
-    f_fwd_exec = f_fwd - B * 2 * L * d * S * S          # causal tiles only (c = 1/2): what the kernels execute
-    out["forward_only"] = {"ms": dtf * 1e3, "algorithmic_tflops": f_fwd / dtf / 1e12, "mfma_frac_of_2.5PF": f_fwd / dtf / 2.5e15,
-                           "executed_tflops": f_fwd_exec / dtf / 1e12, "mfma_frac_executed": f_fwd_exec / dtf / 2.5e15,
-                           "note": "image prefix + 28 blocks at S=2048 + loss on target rows; 'algorithmic' counts full-S^2 attention "
-                                   "FLOPs as the reference computes them (c = 1), 'executed' the causal tiles the kernel runs (c = 1/2)"}
-    if args.fp8:
-        out["forward_only_fp8"] = _forward_fp8(model, images, caps, args.fp8, sync, dtf, f_fwd)
-        out["forward_only_fp8_mx"] = _forward_fp8(model, images, caps, args.fp8, sync, dtf, f_fwd, scaling="mx")
+            sync()
+            t0 = time.perf_counter()
+            for _ in range(2):
+                model(images, caps)
+            sync()
+        dtf = (time.perf_counter() - t0) / 2
+        L, d, ff = model.lm.config.num_layers, model.lm.config.hidden_size, model.lm.config.intermediate_size
+        r = sum(ad.N for ad in (model.lm.engine.layers[0].mlp_adapter or ())[:1]) + sum(ad.N for ad in (model.lm.engine.layers[0].attn_adapter or ())[:1])
+        f_fwd = B * (S * L * (8 * d * d + 4 * d * ff + 4 * d * r) + 4 * L * d * S * S + 47.72e9 * (args.res / 224.0) ** 2)
+        f_fwd_exec = f_fwd - B * 2 * L * d * S * S          # causal tiles only (c = 1/2): what the kernels execute
+        out["forward_only"] = {"ms": dtf * 1e3, "algorithmic_tflops": f_fwd / dtf / 1e12, "mfma_frac_of_2.5PF": f_fwd / dtf / 2.5e15,
+                               "executed_tflops": f_fwd_exec / dtf / 1e12, "mfma_frac_executed": f_fwd_exec / dtf / 2.5e15,
+                               "note": "image prefix + 28 blocks at S=2048 + loss on target rows; 'algorithmic' counts full-S^2 attention "
+                                       "FLOPs as the reference computes them (c = 1), 'executed' the causal tiles the kernel runs (c = 1/2)"}
+        if args.fp8:
+            out["forward_only_fp8"] = _forward_fp8(model, images, caps, args.fp8, sync, dtf, f_fwd)
+            out["forward_only_fp8_mx"] = _forward_fp8(model, images, caps, args.fp8, sync, dtf, f_fwd, scaling="mx")
     eng.train()
     exposed_comm_ms = overlapped = comm_busy_ms = train_per_rank = None
-    for trunc in ([False, True] if args.train_truncate else [False]):
+    for trunc in ([False, True] if args.train_truncate and args.full else [False]):
         eng.truncate = trunc
         for _ in range(args.train_warmup):
             step()
@@ -403,7 +414,7 @@ def bench_train(model, args, rank, world, dev):
                                 "to bf16 summation order: tests/test_train_gpu.py::test_truncation_is_exact, loss within 2e-3, gradients "
                                 "within 2e-2 rel-L2) but skips the padded positions the reference computes")
     eng.truncate = False
-    if args.fp8:   # BASELINE config[4], training side: frozen-weight block GEMMs (forward + dgrad) on the fp8 MFMA
+    if args.fp8 and args.full:   # BASELINE config[4], training side: frozen-weight block GEMMs (forward + dgrad) on the fp8 MFMA
         eng.fp8, eng.truncate = True, False
         try:
             dt8, spread8, loss8 = timed_steps(step, args.train_steps, args.train_warmup, sync)
@@ -773,6 +784,7 @@ def main():
     prompt = torch.randint(0, 50256, (B, args.prompt), device=dev, generator=g)
 
     value = ms_step = roof = gen_s = gen_h = gen8 = gen_per_rank = toks = None
+    train_leg = args.full or args.train_only           # the training step is the headline of --train-only, an extra leg otherwise
     last = {}                          # what the last step handed back, for --dump-outputs
     if not args.train_only:
         def one_step():
@@ -805,125 +817,126 @@ def main():
         if args.dump_outputs and rank == 0:
             dumped = dump_outputs(args.dump_outputs, {"tokens": toks.double(), "prefix_embeds": last["prefix_embeds"].float()})
 
-        # ---- roofline of the dominant kernel (decode weight streaming), measured live ----
-        roof = None
-        if rank == 0:
-            emb = model.embed([images, prompt])
-            out = model.lm(inputs_embeds=emb, use_cache=True, cache_hint=gen + 40)
-            cache = out.past_key_values
-            tok = out.logits[:, -1].argmax(-1, keepdim=True)
-            for _ in range(3):                                       # eager, capture, first replay
-                eng.decode(tok, cache)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            n_rep = 20
-            torch.cuda.synchronize()
-            e0.record()
-            for _ in range(n_rep):
-                eng.decode(tok, cache)
-            e1.record()
-            torch.cuda.synchronize()
-            ms_tok = e0.elapsed_time(e1) / n_rep
-            # dominant kernel in isolation: every decode GEMV of the model (all layers + head) launched
-            # back to back on the real weights (12.16 GB, far beyond the 256 MiB Infinity Cache), HIP events
-            # on the launch stream.  achieved = algorithmic bytes per launch / average launch duration.
-            st = cache.decode_state
-            jobs, wbytes, shapes = decode_gemv_jobs(eng, st)
-
-            def sweep():
-                for fn in jobs:
-                    fn()
-
-            gk = torch.cuda.CUDAGraph()
-            sweep()
-            torch.cuda.synchronize()
-            with torch.cuda.graph(gk):
-                sweep()
-            gk.replay()
-            torch.cuda.synchronize()
-            e0.record()
-            for _ in range(10):
-                gk.replay()
-            e1.record()
-            torch.cuda.synchronize()
-            ms_sweep = e0.elapsed_time(e1) / 10
-            sweep_achieved = wbytes / (ms_sweep * 1e-3) / 1e9
-            achieved = wbytes / (ms_tok * 1e-3) / 1e9      # the launches the captured token step RUNS (attention co-launches, argmax, bookkeeping included)
-            traffic, traffic_src = pmc_traffic_per_launch(shapes)
-            roof = {"bound": "hbm", "kernel": "skinny_kernel (decode weight-streaming GEMM, M=8): the captured token step",
-                    "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0,
-                    # the same weight streams as bare GEMVs back to back (fc_out as a plain GEMV instead of the attention co-launch)
-                    "sweep_achieved": sweep_achieved, "sweep_frac": sweep_achieved / 8000.0,
-                    # HBM bytes per launch from the PMC pass over this sweep (per GEMV shape), not measured in this run
-                    "traffic": traffic, "traffic_source": traffic_src,
-                    "bytes_per_launch": wbytes / len(jobs), "launches": len(jobs),
-                    "streamed_bytes": sum(n * k * 2 for n, k in shapes), "algorithmic_bytes": wbytes,
-                    "block": {0: "4 launches", 1: "3 launches (adapter-down folded through fc_out)", 2: "4 launches, [W_out | W_up] K-concatenated"}.get(eng.fold_dn, "?"),
-                    "avg_launch_us": ms_sweep * 1e3 / len(jobs),
-                    "token_step": {"ms": ms_tok, "decode_tokens_per_s": B / (ms_tok * 1e-3),
-                                   "hbm_frac_whole_step": wbytes / (ms_tok * 1e-3) / 8e12}}
-
-        # the reference's DEFAULT generate() settings (temperature 0.7, top_p 0.9, magma.py:214-221): the sampled branch -- top-p
-        # rule, softmax, multinomial -- runs inside the same captured token step (csrc/sampling.hip); never the headline
-        gen_s = None
-        try:
-            def sampled_step():
+        if args.full:
+            # ---- roofline of the dominant kernel (decode weight streaming), measured live ----
+            roof = None
+            if rank == 0:
                 emb = model.embed([images, prompt])
-                return model.generate(emb, max_steps=gen, temperature=0.7, top_k=0, top_p=0.9, decode=False, stop_on_eos=False, seed=1)
-            sampled_step()
-            sync()
-            t0 = time.perf_counter()
-            for _ in range(args.steps):
-                sampled_step()
-            sync()
-            dts = (time.perf_counter() - t0) / args.steps
-            gen_s = {"mode": "temperature 0.7, top_p 0.9 (reference defaults), device-side sampling in the decode graph",
-                     "tokens_per_s": world * B * gen / dts, "ms_per_call": dts * 1e3, "vs_greedy": (dt / args.steps) / dts}
-        except Exception as e:  # noqa: BLE001
-            gen_s = {"error": repr(e)[:300]}
+                out = model.lm(inputs_embeds=emb, use_cache=True, cache_hint=gen + 40)
+                cache = out.past_key_values
+                tok = out.logits[:, -1].argmax(-1, keepdim=True)
+                for _ in range(3):                                       # eager, capture, first replay
+                    eng.decode(tok, cache)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                n_rep = 20
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(n_rep):
+                    eng.decode(tok, cache)
+                e1.record()
+                torch.cuda.synchronize()
+                ms_tok = e0.elapsed_time(e1) / n_rep
+                # dominant kernel in isolation: every decode GEMV of the model (all layers + head) launched
+                # back to back on the real weights (12.16 GB, far beyond the 256 MiB Infinity Cache), HIP events
+                # on the launch stream.  achieved = algorithmic bytes per launch / average launch duration.
+                st = cache.decode_state
+                jobs, wbytes, shapes = decode_gemv_jobs(eng, st)
 
-        # the reference's callers hand over HOST tensors (preprocess_inputs -> CPU float images); `value` above starts with the
-        # inputs resident in HBM, this leg adds the H2D copy + cast of the batch (pinned fp32 images, int64 prompt) to every call
-        gen_h = None
-        try:
-            images_h, prompt_h = images.float().cpu().pin_memory(), prompt.cpu().pin_memory()
+                def sweep():
+                    for fn in jobs:
+                        fn()
 
-            def host_step():
-                emb = model.embed([images_h.to(dev, non_blocking=True).to(torch.bfloat16), prompt_h.to(dev, non_blocking=True)])
-                return model.generate(emb, max_steps=gen, temperature=0.0, decode=False, stop_on_eos=False)
-            host_step()
-            sync()
-            t0 = time.perf_counter()
-            for _ in range(args.steps):
-                host_step()
-            sync()
-            dth = (time.perf_counter() - t0) / args.steps
-            gen_h = {"mode": "inputs start in pinned host memory (fp32 images, int64 prompt): PCIe copy + cast inside the timed region",
-                     "tokens_per_s": world * B * gen / dth, "ms_per_call": dth * 1e3, "h2d_bytes_per_call": int(images_h.numel() * 4 + prompt_h.numel() * 8)}
-        except Exception as e:  # noqa: BLE001
-            gen_h = {"error": repr(e)[:300]}
+                gk = torch.cuda.CUDAGraph()
+                sweep()
+                torch.cuda.synchronize()
+                with torch.cuda.graph(gk):
+                    sweep()
+                gk.replay()
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(10):
+                    gk.replay()
+                e1.record()
+                torch.cuda.synchronize()
+                ms_sweep = e0.elapsed_time(e1) / 10
+                sweep_achieved = wbytes / (ms_sweep * 1e-3) / 1e9
+                achieved = wbytes / (ms_tok * 1e-3) / 1e9      # the launches the captured token step RUNS (attention co-launches, argmax, bookkeeping included)
+                traffic, traffic_src = pmc_traffic_per_launch(shapes)
+                roof = {"bound": "hbm", "kernel": "skinny_kernel (decode weight-streaming GEMM, M=8): the captured token step",
+                        "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0,
+                        # the same weight streams as bare GEMVs back to back (fc_out as a plain GEMV instead of the attention co-launch)
+                        "sweep_achieved": sweep_achieved, "sweep_frac": sweep_achieved / 8000.0,
+                        # HBM bytes per launch from the PMC pass over this sweep (per GEMV shape), not measured in this run
+                        "traffic": traffic, "traffic_source": traffic_src,
+                        "bytes_per_launch": wbytes / len(jobs), "launches": len(jobs),
+                        "streamed_bytes": sum(n * k * 2 for n, k in shapes), "algorithmic_bytes": wbytes,
+                        "block": {0: "4 launches", 1: "3 launches (adapter-down folded through fc_out)", 2: "4 launches, [W_out | W_up] K-concatenated"}.get(eng.fold_dn, "?"),
+                        "avg_launch_us": ms_sweep * 1e3 / len(jobs),
+                        "token_step": {"ms": ms_tok, "decode_tokens_per_s": B / (ms_tok * 1e-3),
+                                       "hbm_frac_whole_step": wbytes / (ms_tok * 1e-3) / 8e12}}
 
-        gen8 = None
-        if args.fp8:
-            # BASELINE config[4] on the inference side: e4m3 weights in every decode GEMV (W8A16: bf16 activations, weights
-            # widened in registers -> half the bytes per token step) + fp8 MFMA projections in the prefill.  Different
-            # numerics (weight quantisation), so this is a separate object and never the headline `value`.
-            eng.decode_w8, eng.fp8_mode = True, args.fp8
-            eng._cache_pool.clear()
+            # the reference's DEFAULT generate() settings (temperature 0.7, top_p 0.9, magma.py:214-221): the sampled branch -- top-p
+            # rule, softmax, multinomial -- runs inside the same captured token step (csrc/sampling.hip); never the headline
+            gen_s = None
             try:
-                one_step()
+                def sampled_step():
+                    emb = model.embed([images, prompt])
+                    return model.generate(emb, max_steps=gen, temperature=0.7, top_k=0, top_p=0.9, decode=False, stop_on_eos=False, seed=1)
+                sampled_step()
                 sync()
                 t0 = time.perf_counter()
                 for _ in range(args.steps):
-                    one_step()
+                    sampled_step()
                 sync()
-                dt8 = (time.perf_counter() - t0) / args.steps
-                gen8 = {"mode": f"decode W8A16 + prefill fp8 '{args.fp8}'", "tokens_per_s": world * B * gen / dt8, "ms_per_call": dt8 * 1e3,
-                        "speedup_vs_bf16": (dt / args.steps) / dt8}
-            except Exception as e:  # noqa: BLE001  (the bf16 line must survive a failure of the extra leg)
-                gen8 = {"error": repr(e)[:300]}
-            finally:
-                eng.decode_w8, eng.fp8_mode = False, None
+                dts = (time.perf_counter() - t0) / args.steps
+                gen_s = {"mode": "temperature 0.7, top_p 0.9 (reference defaults), device-side sampling in the decode graph",
+                         "tokens_per_s": world * B * gen / dts, "ms_per_call": dts * 1e3, "vs_greedy": (dt / args.steps) / dts}
+            except Exception as e:  # noqa: BLE001
+                gen_s = {"error": repr(e)[:300]}
+
+            # the reference's callers hand over HOST tensors (preprocess_inputs -> CPU float images); `value` above starts with the
+            # inputs resident in HBM, this leg adds the H2D copy + cast of the batch (pinned fp32 images, int64 prompt) to every call
+            gen_h = None
+            try:
+                images_h, prompt_h = images.float().cpu().pin_memory(), prompt.cpu().pin_memory()
+
+                def host_step():
+                    emb = model.embed([images_h.to(dev, non_blocking=True).to(torch.bfloat16), prompt_h.to(dev, non_blocking=True)])
+                    return model.generate(emb, max_steps=gen, temperature=0.0, decode=False, stop_on_eos=False)
+                host_step()
+                sync()
+                t0 = time.perf_counter()
+                for _ in range(args.steps):
+                    host_step()
+                sync()
+                dth = (time.perf_counter() - t0) / args.steps
+                gen_h = {"mode": "inputs start in pinned host memory (fp32 images, int64 prompt): PCIe copy + cast inside the timed region",
+                         "tokens_per_s": world * B * gen / dth, "ms_per_call": dth * 1e3, "h2d_bytes_per_call": int(images_h.numel() * 4 + prompt_h.numel() * 8)}
+            except Exception as e:  # noqa: BLE001
+                gen_h = {"error": repr(e)[:300]}
+
+            gen8 = None
+            if args.fp8:
+                # BASELINE config[4] on the inference side: e4m3 weights in every decode GEMV (W8A16: bf16 activations, weights
+                # widened in registers -> half the bytes per token step) + fp8 MFMA projections in the prefill.  Different
+                # numerics (weight quantisation), so this is a separate object and never the headline `value`.
+                eng.decode_w8, eng.fp8_mode = True, args.fp8
                 eng._cache_pool.clear()
+                try:
+                    one_step()
+                    sync()
+                    t0 = time.perf_counter()
+                    for _ in range(args.steps):
+                        one_step()
+                    sync()
+                    dt8 = (time.perf_counter() - t0) / args.steps
+                    gen8 = {"mode": f"decode W8A16 + prefill fp8 '{args.fp8}'", "tokens_per_s": world * B * gen / dt8, "ms_per_call": dt8 * 1e3,
+                            "speedup_vs_bf16": (dt / args.steps) / dt8}
+                except Exception as e:  # noqa: BLE001  (the bf16 line must survive a failure of the extra leg)
+                    gen8 = {"error": repr(e)[:300]}
+                finally:
+                    eng.decode_w8, eng.fp8_mode = False, None
+                    eng._cache_pool.clear()
     if rank == 0:
         cname = os.path.splitext(os.path.basename(str(args.config)))[0]
         adapters = "MLP adapters" if cname == "MAGMA_v1" else ("attention + MLP adapters" if cname == "MAGMA_v2" else "adapters per config")
@@ -950,22 +963,24 @@ def main():
                                "prefill_len": int(toks.shape[1] - gen)},
                     "per_rank_ms": gen_per_rank,          # each rank's own time per step (the headline divides by the MAX)
                     "roofline": roof}
-            line["generate_sampled"] = gen_s
-            line["generate_from_host"] = gen_h
+            if args.full:
+                line["generate_sampled"] = gen_s
+                line["generate_from_host"] = gen_h
             if gen8 is not None:
                 line["generate_fp8"] = gen8
-        line["train"] = None
+        if train_leg:
+            line["train"] = None
     train = None
-    if args.train_steps > 0:
+    if args.train_steps > 0 and train_leg:
         try:
             train = bench_train(model, args, rank, world, dev)
         except Exception as e:  # noqa: BLE001
             train = {"error": repr(e)[:300]}
-    if rank == 0:
+    if rank == 0 and train_leg:
         line["train"] = train
         # second half of the metric in the SAME roofline object the driver parses: the training step is MFMA-bound, its
         # dominant kernel is the tile GEMM (measured live here, like the decode kernel above); flat copies for flat parsers
-        if args.train_steps > 0 and line.get("roofline") is not None:
+        if args.full and args.train_steps > 0 and line.get("roofline") is not None:
             try:
                 mf = gemm_roofline(model, args, dev)
                 line["roofline"]["train"] = mf
@@ -985,6 +1000,7 @@ def main():
         # exchange's exposed time and the exchange stream's busy time per step
         full = (train or {}).get("full_S2048") or {}
         line.update(flat_training_keys(train, world, args))
+    if rank == 0:
         if args.train_only:
             line["value"], line["ms_per_step"] = full.get("images_per_s"), full.get("ms_per_step")
             if args.dump_outputs:
@@ -995,21 +1011,21 @@ def main():
             if isinstance(mf, dict) and "achieved" in mf:      # the dominant kernel of THIS workload in the contract's own keys
                 line["roofline"].update({"bound": "mfma", "kernel": mf["kernel"], "achieved": mf["achieved"], "peak": mf["peak"],
                                          "unit": mf["unit"], "frac": mf["frac"], "traffic": None})
-        elif world == 1 and args.layers is None:
+        elif args.full and world == 1 and args.layers is None:
             try:
                 line["config1"] = config1_leg(model, dev)
             except Exception as e:  # noqa: BLE001
                 line["config1"] = {"pass": False, "error": repr(e)[:300]}
         if args.dump_outputs:
             line["dumped_outputs"] = dumped
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0 only, AFTER the last timed region; at N > 1 the other ranks are parked at the final barrier meanwhile (the
             # process group's timeout is 30 min), so the first multi-GPU record carries its CPU baseline too
             try:
                 line["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
             except Exception as e:  # noqa: BLE001
                 line["cpu_baseline"] = {"error": str(e)[:200]}
-        if args.variants and world == 1 and args.layers is None:
+        if args.full and args.variants and world == 1 and args.layers is None:
             # BASELINE config[3] and the model-native resolution, driver-visible: each in its own try (the headline line must
             # survive), after the headline model has been released (the training step peaks at ~176 GB)
             cname = os.path.splitext(os.path.basename(str(args.config)))[0]

@@ -142,7 +142,7 @@ def test_bench_two_ranks_self_launched(dev):
     env = dict(os.environ, MAGMA_BENCH_BACKEND="gloo", MAGMA_BENCH_DEVICE="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--layers", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "1", "--layers", "1",
                         "--train-steps", "1", "--train-warmup", "1", "--train-batch", "2", "--no-cpu-baseline", "--fp8", "off",
                         "--no-train-truncate"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
