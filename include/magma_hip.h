@@ -85,8 +85,10 @@ const char* mg_version(void);
  *   7  ragged batches (right-padded prompts of different lengths): mg_attn_decode_bf16, mg_attn_decode_fused_bf16,
  *      mg_decode_attn_gemv_bf16 and mg_sample_finish gained `pos_stride` (before the stream; 0 = one KV write position for the
  *      batch as before, 1 = row b at d_pos[b]); mg_advance_pos gained `B` and `pos_stride` (before the stream).
- *   8  beam search: added mg_beam_state, mg_beam_topk_f32, mg_beam_finish and mg_kv_reorder_bf16 (nothing moved).            */
-#define MG_ABI_VERSION 8
+ *   8  beam search: added mg_beam_state, mg_beam_topk_f32, mg_beam_finish and mg_kv_reorder_bf16 (nothing moved).
+ *   9  continuing from a cache: mg_rotary_split_bf16 gained `pos_stride` (before the stream; 0 = as before, 1 = row b's chunk starts
+ *      at d_pos[b]); added mg_attn_prefill_cached_bf16 (a chunk of new queries per row against the KV cache).                   */
+#define MG_ABI_VERSION 9
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -274,7 +276,9 @@ int mg_embedding_bf16(const int64_t* ids, int32_t B, int32_t T, const mg_bf16* w
 int mg_rotary_split_bf16(const mg_bf16* qkv, int64_t ld_qkv /* row stride in elements, 0 = 3*H*256 */, int32_t B, int32_t S, int32_t H, int32_t rot_dim,
                          const float* sin_t, const float* cos_t, int32_t pos0_host,
                          const int32_t* d_pos, mg_bf16* q_out, mg_bf16* kcache, mg_bf16* vcache,
-                         int32_t Smax, mg_bf16* vt, int32_t vt_ld, void* stream);
+                         int32_t Smax, mg_bf16* vt, int32_t vt_ld,
+                         int32_t pos_stride /* ABI 9: 0 = positions from pos0 as above; 1 = row b's row s at d_pos[b] + s (d_pos
+                                             * required, vt NULL; slots at or past Smax are skipped) */, void* stream);
 
 /* Training form of K9 (positions 0..S-1): q, k, v [B,H,S,256] plus ALL THREE column-tiled transposes vt, qt, kt
  * [B,H,ld_t/32,256,32] in one pass over qkv -- vt feeds mg_attn_prefill_bf16, qt / kt are the s-contraction operands
@@ -291,6 +295,17 @@ int mg_attn_prefill_bf16(const mg_bf16* q, const mg_bf16* kcache, const mg_bf16*
                          int64_t ld_out /* row stride of out in elements; 0 = H*256 (ABI 2: see mg_decode_attn_gemv_bf16) */,
                          float* lse, int32_t B, int32_t H, int32_t S, int32_t Smax, int32_t vt_ld,
                          void* stream);
+
+/* K10 over a cache (ABI 9): causal flash attention of a chunk of T new queries per sequence against the KV cache, the arithmetic of
+ * mg_attn_prefill_bf16 (fp32 online softmax, scale 1/16).  Row b's chunk starts at p_b = d_pos[b * pos_stride] (pos_stride as in
+ * mg_attn_decode_bf16); query t sits at position p_b + t and attends to cache keys [0, p_b + t] -- the chunk's own K / V must already be
+ * written at [p_b, p_b + T) (mg_rotary_split_bf16 with pos_stride).  q: rotated queries, row t of head (b, h) at
+ * q + b q_stride_b + h q_stride_h + t q_ld_row (elements, multiples of 8; [B,H,T,256]: 256, H T 256, T 256); kcache / vcache
+ * [B,H,Smax,256] read as rows (no V^T); out [B*T, >= H*256] at row stride ld_out (0 = H*256).  Key loads stay below
+ * min(p_b + T, Smax); rows t >= T_b of a right-padded chunk compute values nobody reads.                                              */
+int mg_attn_prefill_cached_bf16(const mg_bf16* q, int64_t q_ld_row, int64_t q_stride_b, int64_t q_stride_h,
+                                const mg_bf16* kcache, const mg_bf16* vcache, mg_bf16* out, int64_t ld_out, int32_t B, int32_t H,
+                                int32_t T, int32_t Smax, const int32_t* d_pos, int32_t pos_stride, void* stream);
 
 /* K10 decode (reference magma/sampling.py:86-90, past_key_values path): one query row per (b,h) against
  * ctx = pos_b + 1 cached keys, pos_b = d_pos[b * pos_stride].

@@ -23,7 +23,8 @@ namespace {
 // ---------------------------------------------------------------------------
 // QKT: also write the rotated q and k transposed (qt, kt, same column-tiled layout as vt) -- the s-contraction
 // operands of the backward kernels, which otherwise cost two more passes (mg_head_transpose_bf16) over q and k.
-template <bool QKT>
+// PER_ROW (ABI 9): row b's positions start at d_pos[b] (a ragged cache extended by a chunk); slots at or past Smax are not written.
+template <bool QKT, bool PER_ROW = false>
 __global__ __launch_bounds__(256) void rotary_split_kernel(
     const mg_bf16* __restrict__ qkv, int64_t ld_qkv, int B, int S, int H, int rot_dim,
     const float* __restrict__ sin_t, const float* __restrict__ cos_t, int pos0_host,
@@ -34,7 +35,7 @@ __global__ __launch_bounds__(256) void rotary_split_kernel(
   const int tid = threadIdx.x;
   const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
   const int s0 = blockIdx.x * 32;
-  const int pos0 = d_pos ? *d_pos : pos0_host;
+  const int pos0 = PER_ROW ? d_pos[b] : d_pos ? *d_pos : pos0_host;
   const int dmodel = H * DH;
   const int half_rot = rot_dim >> 1;
 
@@ -45,7 +46,7 @@ __global__ __launch_bounds__(256) void rotary_split_kernel(
     const int s = s0 + row;
     const int d0 = c * 8;
     u32x4 vv = (u32x4){0u, 0u, 0u, 0u}, qz = vv, kz = vv;
-    if (s < S) {
+    if (s < S && (!PER_ROW || (unsigned)(pos0 + s) < (unsigned)Smax)) {
       const mg_bf16* base = qkv + (int64_t)(b * S + s) * ld_qkv + h * DH + d0;
       u32x4 qv = *(const u32x4*)base;
       u32x4 kv = *(const u32x4*)(base + dmodel);
@@ -464,8 +465,10 @@ extern "C" int mg_rotary_split_bf16(const mg_bf16* qkv, int64_t ld_qkv, int32_t 
                                     const float* sin_t, const float* cos_t, int32_t pos0_host,
                                     const int32_t* d_pos, mg_bf16* q_out, mg_bf16* kcache,
                                     mg_bf16* vcache, int32_t Smax, mg_bf16* vt, int32_t vt_ld,
-                                    void* stream) {
+                                    int32_t pos_stride, void* stream) {
   if (B <= 0 || S <= 0 || H <= 0) MG_FAIL(MG_ERR_SHAPE, "mg_rotary_split_bf16: B,S,H must be positive");
+  if (pos_stride != 0 && pos_stride != 1) MG_FAIL(MG_ERR_SHAPE, "mg_rotary_split_bf16: pos_stride must be 0 or 1");
+  if (pos_stride && (!d_pos || vt)) MG_FAIL(MG_ERR_SHAPE, "mg_rotary_split_bf16: per-row positions (pos_stride 1) need d_pos and no V^T");
   if (ld_qkv == 0) ld_qkv = (int64_t)3 * H * DH;
   if (ld_qkv < (int64_t)3 * H * DH || (ld_qkv & 7)) MG_FAIL(MG_ERR_SHAPE, "mg_rotary_split_bf16: ld_qkv must be a multiple of 8 and >= 3*H*256");
   if (rot_dim < 0 || rot_dim > DH || (rot_dim & 7)) MG_FAIL(MG_ERR_SHAPE, "mg_rotary_split_bf16: rot_dim must be a multiple of 8 in [0,256]");
@@ -478,8 +481,12 @@ extern "C" int mg_rotary_split_bf16(const mg_bf16* qkv, int64_t ld_qkv, int32_t 
   }
   if (!d_pos && pos0_host + S > Smax) MG_FAIL(MG_ERR_SHAPE, "mg_rotary_split_bf16: pos0+S exceeds Smax");
   dim3 grid((S + 31) / 32, B * H);
-  hipLaunchKernelGGL(rotary_split_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, qkv, ld_qkv, B, S, H, rot_dim, sin_t,
-                     cos_t, pos0_host, d_pos, q_out, kcache, vcache, Smax, vt, vt_ld, nullptr, nullptr);
+  if (pos_stride)
+    hipLaunchKernelGGL((rotary_split_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, qkv, ld_qkv, B, S, H, rot_dim, sin_t,
+                       cos_t, 0, d_pos, q_out, kcache, vcache, Smax, nullptr, 0, nullptr, nullptr);
+  else
+    hipLaunchKernelGGL(rotary_split_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, qkv, ld_qkv, B, S, H, rot_dim, sin_t,
+                       cos_t, pos0_host, d_pos, q_out, kcache, vcache, Smax, vt, vt_ld, nullptr, nullptr);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }

@@ -58,9 +58,65 @@ class KVCache:
         self.B, self.Smax = B, Smax
         self.decode_state = None
         self.beam = None          # BeamBuffers of a beam-search loop (B = samples x num_beams rows), allocated on first use
+        # continuing from this cache (DESIGN.md "Continuing from a cache"): host copy of the per-row write positions as of host
+        # position _rows_at (None: every row at self.pos), and per row the generated token not yet fed back (-1: none)
+        self._rows, self._rows_at = None, 0
+        self.pending = None
 
     def __len__(self):
         return self.k.shape[0]
+
+    def rows_pos(self) -> torch.Tensor:
+        """Host int64 [B]: the next write position of every row (no device sync: every step since the last set advanced all rows)."""
+        if self._rows is None:
+            return torch.full((self.B,), self.pos, dtype=torch.int64)
+        return self._rows + (self.pos - self._rows_at)
+
+    def _drop_graphs(self):
+        if self.decode_state is not None:
+            self.decode_state.graphs.clear()
+
+    def set_rows(self, pos, pending=None):
+        """Row b's next write position becomes pos[b] (host ints; the cache turns ragged), its not-yet-fed token pending[b] (-1 none)."""
+        pos = torch.as_tensor(pos, dtype=torch.int64).cpu().view(-1)
+        assert pos.numel() == self.B
+        if not self.ragged:           # pos_stride and the d_pos buffer are launch arguments of the captured token step
+            self.ragged, self.pos_stride = True, 1
+            self.d_pos = torch.zeros(self.B, dtype=torch.int32, device=self.k.device)
+            self._drop_graphs()
+        self.d_pos.copy_(pos.to(torch.int32), non_blocking=True)
+        self._rows, self.pos = pos.clone(), int(pos.max())
+        self._rows_at = self.pos
+        self.pending = None if pending is None else torch.as_tensor(pending, dtype=torch.int64).cpu().view(-1).clone()
+
+    def grow(self, Smax: int):
+        """Re-allocate for Smax positions, keeping the written ones; graphs captured on the old buffers are dropped."""
+        if Smax <= self.Smax:
+            return
+        used = min(self.Smax, int(self.rows_pos().max()))
+        for name in ("k", "v"):
+            old = getattr(self, name)
+            new = torch.empty(*old.shape[:3], Smax, old.shape[4], dtype=old.dtype, device=old.device)
+            new[:, :, :, :used].copy_(old[:, :, :, :used])
+            setattr(self, name, new)
+        self.history = torch.zeros(self.B, Smax, dtype=torch.int64, device=self.k.device)
+        self.Smax = Smax
+        self.beam = None
+        self._drop_graphs()
+
+    def expand(self, n: int) -> "KVCache":
+        """A new cache in which every row appears n times in a row (sample-major, row b -> rows b n .. b n + n - 1): one prompt
+        cached once, continued by n different inputs.  Only the written positions are copied."""
+        if not isinstance(n, int) or n < 1:
+            raise ValueError(f"expand(n) takes an integer n >= 1, got {n!r}")
+        rows = self.rows_pos()
+        used = min(self.Smax, int(rows.max()))
+        out = KVCache(len(self), self.B * n, self.k.shape[2], self.Smax, self.k.device, ragged=True)
+        out.k[:, :, :, :used].copy_(self.k[:, :, :, :used].repeat_interleave(n, dim=1))
+        out.v[:, :, :, :used].copy_(self.v[:, :, :, :used].repeat_interleave(n, dim=1))
+        out.eos = self.eos
+        out.set_rows(rows.repeat_interleave(n), None if self.pending is None else self.pending.repeat_interleave(n))
+        return out
 
 
 class BeamBuffers:
@@ -417,13 +473,25 @@ class LMEngine:
         ``lengths`` (int [B], 1 <= len_b <= S; prefill with use_cache=True only): the rows of ``inputs_embeds`` are prompts
         of different lengths, right-padded to S.  Row b's logits are those of its position len_b - 1, and the cache keeps one
         write position per row (len_b, then + 1 per step) -- see DESIGN.md, "Ragged batches"."""
-        if lengths is not None and (labels is not None or past_key_values is not None or not use_cache):
-            raise ValueError("lengths= applies to the prefill call (use_cache=True, no past_key_values, no labels); "
-                             "a ragged cache keeps its per-row positions for the steps that follow")
+        extending = past_key_values is not None and inputs_embeds is not None
+        if lengths is not None and (labels is not None or (past_key_values is not None and not extending) or not use_cache):
+            raise ValueError("lengths= applies to the prefill call and to inputs_embeds appended to a cache (use_cache=True, no "
+                             "labels); a ragged cache keeps its per-row positions for the steps that follow")
         if labels is not None:
             if inputs_embeds is None:
                 inputs_embeds = self.embed_ids(input_ids)
             return self.forward_loss(inputs_embeds, labels, output_hidden_states, return_logits)
+        if extending:
+            # inputs_embeds appended to a cache (the HF GPT-Neo forward takes this pair; positions follow the past): one chunk pass
+            if input_ids is not None:
+                raise ValueError("pass input_ids or inputs_embeds, not both")
+            if beam is not None:
+                raise NotImplementedError("beam search does not continue from a KV cache")
+            logits, cache, full = self.extend(past_key_values, inputs_embeds, lengths=lengths, cache_hint=cache_hint)
+            out = LMOutput(logits=logits.unsqueeze(1), past_key_values=cache, hidden_states=None, loss=None, full_logits=full)
+            if eos_token is not None:
+                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, None)
+            return out
         if past_key_values is not None:
             if not feed_back and input_ids is None:
                 raise ValueError("cached decoding takes input_ids (reference sampling.py:88-90)")
@@ -450,25 +518,28 @@ class LMEngine:
             logits, cache, hs = self.prefill(inputs_embeds, cache_hint, output_hidden_states, reuse_cache, lengths=lengths)
             # generate() only reads the last position, so only that row is computed
             out = LMOutput(logits=logits.unsqueeze(1), past_key_values=cache, hidden_states=hs, loss=None)
-            if eos_token is not None:     # generate(): first token of the loop selected here, device-side bookkeeping armed
-                if cache.eos != int(eos_token):        # the eos id is a launch argument of the captured bookkeeping kernel
-                    cache.eos = int(eos_token)
-                    if cache.decode_state is not None:
-                        cache.decode_state.graphs.clear()
-                cache.sample_state.copy_(torch.tensor([0, -1], dtype=torch.int32), non_blocking=True)
-                if seed is not None:
-                    cache.seed.fill_(int(seed) & 0x7fffffffffffffff)
-                st = self._ensure_decode_state(cache)      # the first token lands where the decode steps read it back
-                mode = sampling
-                if beam is not None:
-                    mode = self._arm_beam(cache, st, beam)
-                out["next_token"] = self.select_token(logits, cache, mode, out=st.token)
-                out["eos_state"] = cache.sample_state
+            if eos_token is not None:
+                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, beam)
             return out
         x, hs = self._blocks_prefill(inputs_embeds, None, output_hidden_states)
         B, S, _ = inputs_embeds.shape
         logits = self._full_logits(x, B * S).view(B, S, self.V)
         return LMOutput(logits=logits, past_key_values=None, hidden_states=hs, loss=None)
+
+    def _arm_first_token(self, out: LMOutput, logits, cache: KVCache, eos_token, seed, sampling, beam):
+        """generate(): the first token of the loop selected from the prefill / extend logits, device-side bookkeeping armed."""
+        if cache.eos != int(eos_token):        # the eos id is a launch argument of the captured bookkeeping kernel
+            cache.eos = int(eos_token)
+            cache._drop_graphs()
+        cache.sample_state.copy_(torch.tensor([0, -1], dtype=torch.int32), non_blocking=True)
+        if seed is not None:
+            cache.seed.fill_(int(seed) & 0x7fffffffffffffff)
+        st = self._ensure_decode_state(cache)      # the first token lands where the decode steps read it back
+        mode = sampling
+        if beam is not None:
+            mode = self._arm_beam(cache, st, beam)
+        out["next_token"] = self.select_token(logits, cache, mode, out=st.token)
+        out["eos_state"] = cache.sample_state
 
     def embed_ids(self, ids: torch.Tensor) -> torch.Tensor:
         ids = ids.to(self.device).contiguous()
@@ -476,7 +547,10 @@ class LMEngine:
         return ops.embedding(ids, self.wte, out)
 
     # -------------------------------------------------------------- prefill
-    def _blocks_prefill(self, embeds: torch.Tensor, cache: Optional[KVCache], want_hidden=False, lse_out=None):
+    def _blocks_prefill(self, embeds: torch.Tensor, cache: Optional[KVCache], want_hidden=False, lse_out=None, chunk=False):
+        """The blocks over B x S new rows.  ``chunk``: the rows continue ``cache`` -- row b's S rows sit at cache.d_pos[b * pos_stride]
+        + s, their K / V are appended there and they attend over the cached keys (mg_attn_prefill_cached_bf16); every GEMM, adapter and
+        epilogue launch is the prefill's."""
         B, S, d = embeds.shape
         assert d == self.d
         if S > self.cfg.max_position_embeddings:
@@ -486,7 +560,7 @@ class LMEngine:
         M = B * S
         vt_ld = ops.ceil_to(S, 32)
         q = torch.empty(B, self.H, S, 256, dtype=BF16, device=dev)
-        vt = torch.empty(B, self.H, vt_ld // 32, 256, 32, dtype=BF16, device=dev)   # V^T in 32-key tiles
+        vt = None if chunk else torch.empty(B, self.H, vt_ld // 32, 256, 32, dtype=BF16, device=dev)   # V^T in 32-key tiles
         if cache is None:   # no cache requested: one scratch K/V shared by all layers
             kscr = torch.empty(B, self.H, S, 256, dtype=BF16, device=dev)
             vscr = torch.empty(B, self.H, S, 256, dtype=BF16, device=dev)
@@ -516,7 +590,11 @@ class LMEngine:
             else:
                 qkv = self._linear(ly, "qkv", ly.qkv, ln, lnq)
             kc, vc = (cache.k[li], cache.v[li]) if cache is not None else (kscr, vscr)
-            if self.fp8_mode and self.fp8_attn and cache is None and qkv.is_contiguous():
+            if chunk:
+                ops.rotary_split(qkv, B, S, self.H, self.rot, self.sin_t, self.cos_t, q, kc, vc, d_pos=cache.d_pos,
+                                 pos_stride=cache.pos_stride)
+                ops.attn_prefill_cached(q, kc, vc, ctx, B, self.H, S, cache.d_pos, pos_stride=cache.pos_stride)
+            elif self.fp8_mode and self.fp8_attn and cache is None and qkv.is_contiguous():
                 # BASELINE config[4]: the attention core on the fp8 MFMA as well (no KV cache to fill: cached decoding reads bf16)
                 a8 = ops.rotary_split_fp8(qkv, B, S, self.H, self.rot, self.sin_t, self.cos_t)
                 ops.attn_prefill_fp8(a8, ctx, lse=None if lse_out is None else lse_out[li])
@@ -593,8 +671,10 @@ class LMEngine:
         # right padding: the prefill is unchanged -- under the causal mask a valid row attends to valid keys only, and the
         # K / V the padded rows leave in slots >= len_b are overwritten by decode steps before any row reads them
         x, hs = self._blocks_prefill(embeds, cache, want_hidden)
+        cache._rows, cache.pending = (lens.clone() if ragged else None), None
         if ragged:
             cache.pos = int(lens.max())
+            cache._rows_at = cache.pos
             cache.d_pos.copy_(lens.to(torch.int32), non_blocking=True)       # no stream sync (as sample_state in forward)
             rows = (torch.arange(B, dtype=torch.int64) * S + lens - 1).to(self.device, non_blocking=True)
             last = x.index_select(0, rows)                       # row len_b - 1 of every sequence
@@ -605,6 +685,74 @@ class LMEngine:
         xl = ops.layernorm(last, self.lnf_g, self.lnf_b, self.eps)
         logits = self._head(xl)
         return logits, cache, hs
+
+    def detach_cache(self, cache: KVCache) -> KVCache:
+        """Take ``cache`` out of the reuse pool: no later generate() call overwrites it."""
+        for key, c in list(self._cache_pool.items()):
+            if c is cache:
+                del self._cache_pool[key]
+        return cache
+
+    def extend(self, cache: KVCache, embeds: torch.Tensor, lengths=None, cache_hint: Optional[int] = None):
+        """Append B x T new rows (``lengths``: T_b >= 1 of them per row, right-padded) to ``cache`` and run the blocks over them
+        only: row b's rows take positions p_b .. p_b + T_b - 1 (p_b = its write position; a token a generate() call left
+        pending -- selected, not fed back -- goes first).  Grows the cache when p_b + T_b + cache_hint exceeds Smax.  Returns
+        (fp32 logits (B, V) of every row's last new position, the cache -- positions advanced by T_b --, the (B, T', V) logits
+        of the caller's T rows as a lazy value -- a pending token's own logits are not among them)."""
+        if not isinstance(cache, KVCache):
+            raise TypeError(f"past_key_values must be this engine's KVCache, got {type(cache).__name__}")
+        if cache.beam is not None and cache.beam.k > 1:
+            raise NotImplementedError("a beam-search cache cannot be continued")
+        if embeds.ndim != 3 or embeds.shape[0] != cache.B or embeds.shape[2] != self.d:
+            raise ValueError(f"inputs_embeds must be ({cache.B}, T, {self.d}) for this cache, got {tuple(embeds.shape)}")
+        B, T, _ = embeds.shape
+        if T < 1:
+            raise ValueError("continuing a cache needs at least one new position per row")
+        lens = self.check_lengths(lengths, B, T) if lengths is not None else None
+        T_in, shift = T, None
+        if cache.pending is not None and bool((cache.pending >= 0).any()):
+            has = cache.pending >= 0
+            if lens is None:
+                lens = torch.full((B,), T, dtype=torch.int64)
+            idx = has.nonzero().squeeze(1).to(self.device)
+            e = torch.zeros(B, T + 1, self.d, dtype=BF16, device=self.device)
+            e[:, :T] = embeds
+            e[idx, 1:] = embeds.to(BF16).index_select(0, idx)
+            e[idx, :1] = self.embed_ids(cache.pending.clamp(min=0).view(B, 1).to(self.device)).index_select(0, idx)
+            embeds, lens, T = e, lens + has.to(torch.int64), T + 1
+            shift = has.to(torch.int64)
+        rows = cache.rows_pos()
+        add = lens if lens is not None else torch.full((B,), T, dtype=torch.int64)
+        n_pos = self.cfg.max_position_embeddings
+        end = rows + add
+        if int(end.max()) > n_pos:
+            raise ValueError(f"continuing the cache reaches position {int(end.max())}, beyond max_position_embeddings = {n_pos}")
+        cache.pending = None
+        need = max(int(end.max()), int(rows.max()) + T) + (cache_hint or 0)
+        self.detach_cache(cache)
+        if need > cache.Smax:
+            cache.grow(min(n_pos, ops.ceil_to(need, 64)))
+        if lens is not None and not cache.ragged:
+            cache.set_rows(rows)
+        x, _ = self._blocks_prefill(embeds, cache, chunk=True)
+        if cache.ragged:
+            cache.d_pos.add_(add.to(torch.int32).to(self.device, non_blocking=True))
+            cache._rows, cache.pos = end, int(end.max())
+            cache._rows_at = cache.pos
+        else:
+            cache.d_pos.add_(T)
+            cache.pos += T
+        if lens is not None:
+            last = x.index_select(0, (torch.arange(B, dtype=torch.int64) * T + lens - 1).to(self.device, non_blocking=True))
+        else:
+            last = x.view(B, T, self.d)[:, T - 1, :]
+        logits = self._head(ops.layernorm(last, self.lnf_g, self.lnf_b, self.eps))
+        if shift is None:
+            full = LMOutput.lazy(lambda: self._full_logits(x, B * T).view(B, T, self.V))
+        else:       # the caller's rows only: row b's input t sits at combined row t + 1 when a pending token went first
+            rows = (torch.arange(B)[:, None] * T + torch.arange(T_in)[None, :] + shift[:, None]).reshape(-1).to(self.device)
+            full = LMOutput.lazy(lambda: self._full_logits(x.index_select(0, rows), B * T_in).view(B, T_in, self.V))
+        return logits, cache, full
 
     def _head(self, xl: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         M = xl.shape[0]

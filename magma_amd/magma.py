@@ -275,16 +275,38 @@ class Magma(nn.Module):
     def generate(self, embeddings, max_steps: int = 100, temperature: float = 0.7, top_k: int = 0,
                  top_p: float = 0.9, decode: bool = True, stop_on_eos: bool = True, seed: int = None,
                  eos_check_every: int = None, lengths=None, num_beams: int = 1, length_penalty: float = 1.0,
-                 early_stopping=False, num_return_sequences: int = 1, return_scores: bool = False):
+                 early_stopping=False, num_return_sequences: int = 1, return_scores: bool = False, past_key_values=None,
+                 return_past_key_values: bool = False):
         """reference magma.py:214-236 (+ stop_on_eos / seed / eos_check_every / lengths, see sampling.generate).
         ``lengths``: prompts of different lengths, right-padded (embed_batch); ``embeddings`` may also be a list of
         per-sample (1, s_i, d) tensors.  ``num_beams`` > 1: beam search (length_penalty, early_stopping,
-        num_return_sequences, return_scores: see sampling.generate)."""
+        num_return_sequences, return_scores: see sampling.generate).  ``return_past_key_values=True`` returns (output, past);
+        ``past_key_values=past`` continues that conversation with ``embeddings`` as the next turn (see sampling.generate)."""
         torch.cuda.set_device(self.device)
         return generate(self, embeddings=embeddings, max_steps=max_steps, temperature=temperature, top_k=top_k,
                         top_p=top_p, decode=decode, stop_on_eos=stop_on_eos, seed=seed, eos_check_every=eos_check_every,
                         lengths=lengths, num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping,
-                        num_return_sequences=num_return_sequences, return_scores=return_scores)
+                        num_return_sequences=num_return_sequences, return_scores=return_scores,
+                        past_key_values=past_key_values, return_past_key_values=return_past_key_values)
+
+    @torch.no_grad()
+    def cache_prompt(self, embeddings, lengths=None, cache_hint: int = 256):
+        """A KV cache holding only the prompts ``embeddings`` ((B, S, d) with optional ``lengths``, a list of per-sample tensors,
+        or embed_batch's (embeddings, lengths)), for ``generate(question, past_key_values=cache)``.  Shared prefix: cache one
+        image and instruction once, then ``cache.expand(n)`` and ask n questions.  The cache belongs to the caller."""
+        from .sampling import pad_ragged
+        from .engine import LMEngine
+        torch.cuda.set_device(self.device)
+        from .sampling import is_embed_batch
+        if is_embed_batch(embeddings):
+            embeddings, lengths = embeddings
+        if isinstance(embeddings, (list, tuple)):
+            embeddings, lengths = pad_ragged(embeddings)
+        B, S, _ = embeddings.shape
+        lens = LMEngine.check_lengths(lengths, B, S) if lengths is not None else torch.full((B,), S, dtype=torch.int64)
+        _, cache, _ = self.lm.engine.prefill(embeddings, cache_hint, lengths=lens)
+        cache.set_rows(lens)
+        return cache
 
     # ------------------------------------------------------------- forward
     def forward(self, images=None, captions=None, output_hidden_states: bool = False, input_embeddings=None,

@@ -373,13 +373,20 @@ def embedding(ids: torch.Tensor, wte: torch.Tensor, out: torch.Tensor, row_off: 
 
 
 def rotary_split(qkv, B, S, H, rot_dim, sin_t, cos_t, q_out, kcache, vcache, *, pos0: int = 0,
-                 d_pos: Optional[torch.Tensor] = None, vt: Optional[torch.Tensor] = None):
+                 d_pos: Optional[torch.Tensor] = None, vt: Optional[torch.Tensor] = None, pos_stride: int = 0):
+    """``pos_stride=1`` (with ``d_pos`` of B positions, no ``vt``): row b's S rows land at d_pos[b] + s -- a chunk appended to a
+    ragged cache (slots at or past Smax are skipped)."""
     _need_gpu(qkv)
     assert qkv.ndim == 2 and qkv.stride(1) == 1          # [B*S, >= 3*H*256]: a column range of a wider GEMM output is fine
     Smax = kcache.shape[2]
+    ps = 0
+    if pos_stride:
+        if d_pos is None or vt is not None:
+            raise ValueError("rotary_split(pos_stride=1) needs d_pos and no vt")
+        ps = _pos_stride(d_pos, B, pos_stride)
     check(L.load().mg_rotary_split_bf16(qkv.data_ptr(), qkv.stride(0), B, S, H, rot_dim, sin_t.data_ptr(), cos_t.data_ptr(), pos0,
                                         _p(d_pos), q_out.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), Smax,
-                                        _p(vt), 0 if vt is None else vt.shape[2] * 32, _stream()),
+                                        _p(vt), 0 if vt is None else vt.shape[2] * 32, ps, _stream()),
           "mg_rotary_split_bf16")
 
 
@@ -466,6 +473,30 @@ def attn_prefill(q, kcache, vt, out, B, H, S, lse: Optional[torch.Tensor] = None
     assert out.ndim == 2 and out.stride(1) == 1 and out.shape[1] == H * 256      # a column range of a wider row is fine
     check(L.load().mg_attn_prefill_bf16(q.data_ptr(), kcache.data_ptr(), vt.data_ptr(), out.data_ptr(), out.stride(0), _p(lse),
                                         B, H, S, kcache.shape[2], vt.shape[2] * 32, _stream()), "mg_attn_prefill_bf16")
+    return out
+
+
+def attn_prefill_cached(q, kcache, vcache, out, B, H, T, d_pos, *, pos_stride: int = 0):
+    """Causal attention of a chunk of T new (already rotated) queries per row against the KV cache: query t of row b sits at
+    p_b + t (p_b = d_pos[b * pos_stride]) and sees cache keys [0, p_b + t]; the chunk's K / V must already be in the cache
+    (rotary_split with pos_stride).  q [B,H,T,256] (any row / head / batch strides that are multiples of 8, rows contiguous);
+    out [B*T, H*256] (a column range of a wider row is fine)."""
+    _need_gpu(q)
+    if q.ndim != 4 or tuple(q.shape) != (B, H, T, 256) or q.stride(3) != 1 or q.dtype != torch.bfloat16:
+        raise ValueError(f"q must be bf16 ({B}, {H}, {T}, 256) with contiguous rows, got {q.dtype} {tuple(q.shape)}")
+    for name, c in (("kcache", kcache), ("vcache", vcache)):
+        if c.ndim != 4 or c.shape[0] != B or c.shape[1] != H or c.shape[3] != 256 or not c.is_contiguous() or c.dtype != torch.bfloat16:
+            raise ValueError(f"{name} must be a contiguous bf16 ({B}, {H}, Smax, 256) cache, got {c.dtype} {tuple(c.shape)}")
+    if kcache.shape != vcache.shape:
+        raise ValueError("kcache and vcache must have the same shape")
+    if out.ndim != 2 or out.stride(1) != 1 or out.shape[0] != B * T or out.shape[1] != H * 256 or out.dtype != torch.bfloat16:
+        raise ValueError(f"out must be bf16 ({B * T}, {H * 256}) with unit column stride, got {out.dtype} {tuple(out.shape)}")
+    if T > kcache.shape[2]:
+        raise ValueError(f"a chunk of {T} rows does not fit a cache of Smax = {kcache.shape[2]}")
+    ps = _pos_stride(d_pos, B, pos_stride)
+    check(L.load().mg_attn_prefill_cached_bf16(q.data_ptr(), q.stride(2), q.stride(0), q.stride(1), kcache.data_ptr(),
+                                               vcache.data_ptr(), out.data_ptr(), out.stride(0), B, H, T, kcache.shape[2],
+                                               d_pos.data_ptr(), ps, _stream()), "mg_attn_prefill_cached_bf16")
     return out
 
 

@@ -69,6 +69,14 @@ def pad_ragged(embeddings) -> Tuple[torch.Tensor, torch.Tensor]:
     return out, lengths
 
 
+def is_embed_batch(x) -> bool:
+    """embed_batch's (embeddings (B, S, d), lengths [B] integers) -- as opposed to a tuple of per-sample embeddings."""
+    if not (isinstance(x, tuple) and len(x) == 2 and torch.is_tensor(x[0]) and x[0].ndim == 3):
+        return False
+    lens = torch.as_tensor(x[1]) if not torch.is_tensor(x[1]) else x[1]
+    return lens.ndim == 1 and not lens.is_floating_point() and not lens.is_complex() and lens.dtype != torch.bool
+
+
 MAX_BEAMS = 16
 
 
@@ -212,7 +220,8 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
              top_p: float = 0.9, eos_token: int = None, decode: bool = True,
              stop_on_eos: bool = True, seed: int = None, eos_check_every: int = None,
              lengths=None, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False,
-             num_return_sequences: int = 1, return_scores: bool = False) -> Union[List[str], torch.Tensor]:
+             num_return_sequences: int = 1, return_scores: bool = False, past_key_values=None,
+             return_past_key_values: bool = False) -> Union[List[str], torch.Tensor]:
     """reference sampling.py:43-121.  Token selection (argmax, or top-k / the reference's top-p rule / softmax /
     multinomial) and the ``(next_token == eos).all()`` test run on the device inside the captured token step; the host
     reads the recorded "first all-eos step" every ``eos_check_every`` steps (default 8, MAGMA_EOS_CHECK_EVERY) instead of
@@ -229,9 +238,24 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     temperature, top_k, top_p and seed do not apply.  Returns the best ``num_return_sequences`` hypotheses of every sample,
     sample-major: B * n_ret strings, or (B * n_ret, s + n) ids laid out as above (n = the longest returned hypothesis);
     ``return_scores=True`` returns (output, fp32 scores (B * n_ret,)) -- with num_beams=1 that runs the beam rule with one
-    beam.  The HIP engine runs the whole beam step on the device; any other LM object runs the host statement."""
+    beam.  The HIP engine runs the whole beam step on the device; any other LM object runs the host statement.
+
+    Multi-turn (DESIGN.md "Continuing from a cache"; HIP engine only, greedy or sampled): ``return_past_key_values=True`` returns
+    (output, past).  ``past`` belongs to the caller (no later call reuses its buffers) and holds every row's conversation: its
+    prompt and its generated tokens before its first eos.  ``generate(new, past_key_values=past)`` continues it with the new
+    inputs -- a (B, T, d) tensor, a list of per-row tensors or embed_batch's (embeddings, lengths) -- and gives what a fresh call
+    over [prompt_b ; kept tokens_b ; new_b] gives; only the new rows go through the blocks.  The output is laid out as for a call
+    on the new inputs alone.  ``past`` is advanced in place; KVCache.expand(n) gives each row n copies (one cached prompt, n
+    questions).  A continued call leaves ``past`` holding the whole conversation so far (the same state it returns with
+    ``return_past_key_values=True``), so it can be continued again."""
     eos_token = eos_token or model.eos_token
     early_stopping = check_beam_args(num_beams, num_return_sequences, early_stopping)
+    continuing = past_key_values is not None or return_past_key_values
+    if continuing and (num_beams > 1 or return_scores):
+        raise NotImplementedError("beam search neither continues from nor returns a KV cache (past_key_values / "
+                                  "return_past_key_values need num_beams=1 and return_scores=False)")
+    if is_embed_batch(embeddings):
+        embeddings, lengths = embeddings                      # embed_batch's (embeddings, lengths)
     if num_beams > 1 or return_scores:
         return _generate_beam(model, embeddings, max_steps, eos_token, decode, eos_check_every, lengths, num_beams,
                               float(length_penalty), early_stopping, num_return_sequences, return_scores)
@@ -245,6 +269,12 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     dev = embeddings.device
     # the HIP engine selects the token itself; any other LM object gets the reference's call (sampling.py:81-93)
     on_device = getattr(model.lm, "device_token_selection", False)
+    if continuing and not on_device:
+        raise ValueError("past_key_values / return_past_key_values need the HIP engine's LM")
+    if continuing and max_steps < 1:
+        raise ValueError("continuing a conversation needs max_steps >= 1")
+    if past_key_values is not None and past_key_values.B != b:
+        raise ValueError(f"the cache holds {past_key_values.B} rows, the new inputs {b}")
     if lengths is not None:
         if not on_device:
             raise ValueError("generate(lengths=...) needs the HIP engine's LM (per-row KV positions): this LM object has no "
@@ -265,8 +295,15 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     if lengths is not None:
         first_kw["lengths"] = lengths
     step_kw = dict(sampling=mode) if on_device else {}
+    if past_key_values is not None:
+        start = past_key_values.rows_pos() + (past_key_values.pending >= 0).to(torch.int64) \
+            if past_key_values.pending is not None else past_key_values.rows_pos()
+        ext_kw = dict(first_kw, lengths=lengths if lengths is not None else torch.full((b,), s, dtype=torch.int64))
     for i in range(max_steps):
-        if i == 0:
+        if i == 0 and past_key_values is not None:      # the new rows appended to the caller's cache (LMEngine.extend)
+            outputs = model.lm(inputs_embeds=embeddings, use_cache=True, past_key_values=past_key_values, cache_hint=max_steps,
+                               **ext_kw)
+        elif i == 0:
             outputs = model.lm(inputs_embeds=embeddings, use_cache=True, past_key_values=None, cache_hint=max_steps,
                                reuse_cache=True, **first_kw)
         elif on_device:      # the token selected by the previous step is fed back on the device: nothing crosses the host
@@ -308,10 +345,33 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
         out[:, s:n] = past.history[:, : n - s]
         model.lm.engine.check_decode(past)
     out = out[:, :n]
+    if continuing:      # the cache keeps the conversation (a continued one too: it was advanced in place and stays continuable)
+        if past_key_values is None:
+            start = lengths if lengths is not None else torch.full((b,), s, dtype=torch.int64)
+        else:
+            start = start + (lengths if lengths is not None else s)
+        keep_conversation(past, start, n - s, eos_token)
+        model.lm.engine.detach_cache(past)
     if decode:
         out = [model.tokenizer.decode(remove_tokens_after_eos(row, eos_token, model.image_token)) for row in out]
     model.train(was_training)
-    return out
+    return (out, past) if return_past_key_values else out
+
+
+def keep_conversation(cache, start: torch.Tensor, n_gen: int, eos_token):
+    """After a generate() call of n_gen kept steps whose first token sits at position start[b] of row b: every row keeps its
+    generated tokens before its first eos.  A row that emitted eos is cut back to just before it (its later slots are
+    overwritten by what comes next); a row that did not keeps its last token pending, to be fed first by the next call."""
+    hist = cache.history[:, :n_gen].cpu()                  # one host sync
+    pos, pend = start.clone().to(torch.int64), torch.full((cache.B,), -1, dtype=torch.int64)
+    for r in range(cache.B):
+        hits = (hist[r] == eos_token).nonzero() if eos_token is not None else torch.empty(0)
+        if hits.numel():
+            pos[r] += int(hits[0])
+        else:
+            pos[r] += n_gen - 1
+            pend[r] = int(hist[r, n_gen - 1])
+    cache.set_rows(pos, pend)
 
 
 @torch.no_grad()
