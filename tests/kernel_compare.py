@@ -1,0 +1,656 @@
+"""Per-element comparison of a kernel's output with an fp64 reference, against a bound DERIVED from the arithmetic the kernel does.
+
+Why: the whole-tensor number of the suite (rel = ||got - ref||_F / ||ref||_F) averages.  A dropped 16-byte store at a tile corner,
+a last row that reads the row above, a tail element without its bias all stay under its thresholds on a large tensor
+(tests/test_kernel_compare_cpu.py keeps the figures).  Here every element has its own bound, and one element over it fails.
+
+Conventions
+    * inputs of the kernels are bf16 (or fp32) values, which fp64 holds exactly: references are formed in fp64 from them,
+      on the device of the inputs (``f64``), so that a reference product is two extra matmuls and not a host round trip;
+    * ``u`` is a unit roundoff: 2^-8 for bf16 (8 significand bits; ``f2bf`` / ``pack2bf`` in csrc/common.h round to nearest even),
+      2^-24 for fp32.  ``gamma(n) = n u32 / (1 - n u32)`` is the standard bound on the relative error of n chained fp32 roundings
+      (Higham, Accuracy and Stability of Numerical Algorithms, lemma 3.1).  A sum of K products accumulated in fp32 IN ANY ORDER has
+      |computed - exact| <= gamma(K) * sum_k |a_k b_k|  (ibid. section 3.1: every term passes through at most K roundings whatever
+      the tree), which is why one constructor covers split-K, both MFMA shapes, the GEMV bursts and wave reductions alike;
+    * a value rounded once to the output type adds ``u_out |exact|``, and applies to the already perturbed value: the fp32 terms
+      carry a factor (1 + u_out);
+    * denormals: the MFMA and the packed conversions may flush them; an element then moves by less than 2^-126.  ``FLOOR`` (2^-120)
+      covers a few dozen of those and is far below anything a test looks at.
+
+None of the constants is fitted to what a kernel gives.  A ratio above 1 on the hardware is a finding: either a kernel fault (the
+failure message shows where) or an error source missing here, which is then added as a NAMED term with its reason.
+
+Plain module, imported by the tests the way fullwidth_common.py is: no fixtures, no pytest settings."""
+import math
+
+import torch
+
+U_BF16 = 2.0 ** -8
+U_F32 = 2.0 ** -24
+FLOOR = 2.0 ** -120
+# hardware v_exp_f32 / v_log_f32 / v_rcp_f32 / v_rsq_f32: 1 ulp (CDNA ISA guide, "VOP1 transcendental precision") = 2 u32
+U_TRANS = 2.0 * U_F32
+# sup |d/dx gelu_new(x)| = 1.1290 (at x = 1.46): how far the tanh-form GELU stretches an error of its argument
+GELU_LIPSCHITZ = 1.13
+
+
+def unit_roundoff(dtype) -> float:
+    if dtype == torch.bfloat16:
+        return U_BF16
+    if dtype == torch.float32:
+        return U_F32
+    if dtype == torch.float64:
+        return 2.0 ** -53
+    raise ValueError(f"no unit roundoff for {dtype}")
+
+
+def gamma(n: float) -> float:
+    """n chained fp32 roundings: relative error <= n u / (1 - n u)."""
+    nu = float(n) * U_F32
+    assert nu < 0.5, "gamma(n) is meaningless for n u >= 1/2"
+    return nu / (1.0 - nu)
+
+
+def f64(t: torch.Tensor) -> torch.Tensor:
+    return t.detach().to(torch.float64)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the comparator
+# ---------------------------------------------------------------------------------------------------------------------------
+def ratios(got: torch.Tensor, ref: torch.Tensor, bound: torch.Tensor) -> torch.Tensor:
+    """|got - ref| / bound per element (fp64); +inf where got is not finite although ref is."""
+    assert got.shape == ref.shape == bound.shape, (got.shape, ref.shape, bound.shape)
+    assert ref.dtype == torch.float64 and bound.dtype == torch.float64, "reference and bound are formed in fp64"
+    g = f64(got)
+    r = (g - ref).abs() / bound
+    bad = ~torch.isfinite(g) & torch.isfinite(ref)
+    return torch.where(bad | torch.isnan(r), torch.full_like(r, float("inf")), r)
+
+
+def worst_ratio(got, ref, bound) -> float:
+    return float(ratios(got, ref, bound).max()) if got.numel() else 0.0
+
+
+def rel_l2(got, ref) -> float:
+    """The whole-tensor number of the suite: kept in messages and as the second, coarser check of every test."""
+    d = f64(got) - f64(ref)
+    return float(d.norm() / (f64(ref).norm() + 1e-300))
+
+
+def describe_failure(got, ref, bound, r=None) -> str:
+    """Worst ratio and where, how many elements are over, and the bounding box of their indices -- a tile corner, one row,
+    one 8-wide run look very different there."""
+    r = ratios(got, ref, bound) if r is None else r
+    over = r > 1.0
+    n_over = int(over.sum())
+    flat = int(torch.argmax(r))
+    idx = tuple(int(i) for i in torch.unravel_index(torch.tensor(flat), r.shape)) if r.ndim else ()
+    msg = (f"worst |err|/bound {float(r.reshape(-1)[flat]):.3g} at index {idx} "
+           f"(got {float(f64(got).reshape(-1)[flat]):.9g}, ref {float(ref.reshape(-1)[flat]):.9g}, "
+           f"bound {float(bound.reshape(-1)[flat]):.3g}); {n_over} of {r.numel()} elements over the bound")
+    if n_over:
+        nz = over.nonzero()
+        lo, hi = nz.min(0).values.tolist(), nz.max(0).values.tolist()
+        box = " x ".join(f"[{a}..{b}]" for a, b in zip(lo, hi))
+        vol = 1
+        for a, b in zip(lo, hi):
+            vol *= b - a + 1
+        msg += f"; bounding box of the offenders {box} ({n_over} of its {vol} elements)"
+        nf = int((~torch.isfinite(f64(got)) & torch.isfinite(ref)).sum())
+        if nf:
+            msg += f"; {nf} not finite"
+    return msg + f"; whole-tensor rel-L2 {rel_l2(got, ref):.3e}"
+
+
+def assert_elementwise(got: torch.Tensor, ref: torch.Tensor, bound: torch.Tensor, what: str = "") -> float:
+    """Fails if any element has |got - ref| > bound or is not finite where ref is.  ref, bound: fp64, of got's shape.
+    Prints (pytest -s / a log shows it) and returns the worst ratio of a passing comparison."""
+    r = ratios(got, ref, bound)
+    worst = float(r.max()) if r.numel() else 0.0
+    print(f"[elementwise] {what}: worst err/bound {worst:.3g}, rel-L2 {rel_l2(got, ref):.3e}, {r.numel()} elements")
+    assert worst <= 1.0, f"{what}: {describe_failure(got, ref, bound, r)}"
+    return worst
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# bound constructors
+# ---------------------------------------------------------------------------------------------------------------------------
+def rounded(ref: torch.Tensor, fp32_err: torch.Tensor, out_dtype) -> torch.Tensor:
+    """A value computed in fp32 with absolute error <= fp32_err, then rounded ONCE to out_dtype:
+    |fl(x + e) - x| <= u_out |x + e| + |e| <= u_out |x| + (1 + u_out) |e|."""
+    u = unit_roundoff(out_dtype)
+    return u * ref.abs() + (1.0 + u) * fp32_err + FLOOR
+
+
+def product_terms(a: torch.Tensor, w: torch.Tensor):
+    """(ref, mag) = (A W^T, |A| |W|^T) in fp64 on the operands' device -- the two extra products of a GEMM case."""
+    a64, w64 = f64(a), f64(w)
+    return a64 @ w64.t(), a64.abs() @ w64.abs().t()
+
+
+def conv2d_terms(x: torch.Tensor, w: torch.Tensor, stride: int = 1, padding: int = 1):
+    """(ref, mag, K) of a convolution as the GEMM it is run as: x [B, Cin, H, W], w [Cout, Cin, k, k] -> rows [B*Ho*Wo, Cout] in
+    NHWC order; fp64 through unfold + matmul (no dependence on a vendor convolution in fp64)."""
+    Cout, Cin, k, _ = w.shape
+    cols = torch.nn.functional.unfold(f64(x), k, padding=padding, stride=stride)          # [B, Cin k k, Ho Wo]
+    w2 = f64(w).reshape(Cout, Cin * k * k)
+    to_rows = lambda t: t.permute(0, 2, 1).reshape(-1, Cout)
+    return to_rows(w2 @ cols), to_rows(w2.abs() @ cols.abs()), Cin * k * k
+
+
+# v_mfma_scale_f32_16x16x128_f8f6f4 (the fp8 GEMMs) does not add its products the way an fp32 chain would.  Products are summed in
+# groups of F8_MFMA_GROUP consecutive k; inside a group each product is aligned to the group's largest product and the bits below
+# 2^-F8_MFMA_KEEP_BITS of that product's leading bit are DROPPED (truncated, not rounded).  A product in ANOTHER group survives
+# down to 2^-23 of the large one: the group sums are added with fp32 width.  Not in the ISA guide: measured with single products
+# next to a large one, accumulator zero (tests/test_fp8_gpu.py::test_mx_mfma_sums_groups_of_8_and_truncates pins it).  How the
+# running accumulator C enters the alignment is NOT probed (mg_debug_mx_mfma has no C operand): the bounds take its addition as
+# one fp32 rounding per instruction, inside gamma(K).  The 32x32x64 form the fp8 attention uses has no single-instruction entry
+# point at all and is not bounded here.
+F8_MFMA_GROUP = 8
+F8_MFMA_KEEP_BITS = 13
+
+
+def f8_mfma_truncation(a: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """Named term of the fp8 paths: |error| of A W^T from the truncation inside the f8f6f4 MFMA.  In a group of 8 products the 7
+    that are not the largest lose less than 2^-13 of the largest each, and |a_k w_k| <= max_g |a| max_g |w|:
+        7 * 2^-13 * sum over groups g of  max_{k in g} |a_mk| * max_{k in g} |w_nk|        (one small matmul of group maxima).
+    a, w: the DEQUANTISED operands [M, K], [N, K] (a group lies inside one 32-element scale block)."""
+    def gmax(t):
+        t = f64(t).abs()
+        pad = -t.shape[1] % F8_MFMA_GROUP
+        if pad:
+            t = torch.nn.functional.pad(t, (0, pad))
+        return t.view(t.shape[0], -1, F8_MFMA_GROUP).amax(-1)
+    return (F8_MFMA_GROUP - 1) * 2.0 ** -F8_MFMA_KEEP_BITS * (gmax(a) @ gmax(w).t())
+
+
+def gemm_bound(ref, mag, K: int, out_dtype, *, n_epilogue: int = 0, bf16_partials: int = 0, act: str = "none",
+               pre: torch.Tensor = None, extra_err: torch.Tensor = None) -> torch.Tensor:
+    """out = round_out( act( sum_k a_k w_k [* scale] [+ bias] [+ residuals] ) ).
+
+    ref          the exact OUTPUT (after the activation)
+    mag          magnitude sum of every term that is added before the activation: |A| |W|^T [* |scale|] + |bias| + |res_0| + ...
+    K            contraction length; n_epilogue = number of further fp32 operations of the epilogue (one per scale / bias / residual)
+                 -> accumulation term gamma(K + n_epilogue) * mag, valid for any summation order (split-K slabs are fp32)
+    bf16_partials  how many times a partial result is rounded to bf16 before it is combined (0 for every kernel of the library
+                 today: split-K slabs and GEMV partials are fp32); each adds u_bf16 * mag
+    act / pre    "none" | "relu" (1-Lipschitz: the bound passes through) | "gelu" (gelu_new_f of csrc/common.h:
+                 x * rcp(1 + exp(-2u)), u = sqrt(2/pi) (x + 0.044715 x^3); ``pre`` = exact pre-activation).  The argument error is
+                 stretched by at most GELU_LIPSCHITZ; the evaluation itself adds, relative to |gelu(x)|: the polynomial (4 roundings,
+                 all terms of one sign) and the product with log2(e) move the exponent by (4 + 2) u32 |2u|, v_exp_f32 and
+                 v_rcp_f32 are 1 ulp each, the add and the two multiplies one rounding each.
+    extra_err    a further absolute error of the value before the activation (f8_mfma_truncation, scaled like the product)"""
+    err = gamma(K + n_epilogue) * mag + bf16_partials * U_BF16 * mag
+    if extra_err is not None:
+        err = err + extra_err
+    return rounded(ref, through_activation(err, act, pre, ref), out_dtype)
+
+
+def through_activation(err, act: str, pre=None, ref=None):
+    """The fp32 error of act(x) given the error ``err`` of x (see gemm_bound)."""
+    if act == "gelu":
+        assert pre is not None and ref is not None
+        two_u = 2.0 * math.sqrt(2.0 / math.pi) * (pre + 0.044715 * pre ** 3)
+        eval_rel = 6.0 * U_F32 * two_u.abs() + 2.0 * U_TRANS + 3.0 * U_F32
+        return GELU_LIPSCHITZ * err + eval_rel * ref.abs()
+    if act not in ("none", "relu"):
+        raise ValueError(act)
+    return err
+
+
+def exp_rel_err(qk_mag_max: torch.Tensor, K: int) -> torch.Tensor:
+    """Relative error of one softmax weight exp(t_j - m) as the kernels form it, t_j = (q . k_j) / 16:
+       * the score is a K-term fp32 dot product: |dt| <= gamma(K) * (|q| . |k_j|) / 16;
+       * scale, subtraction of the running maximum and the conversion to a base-2 exponent (an fma with 1/16 * log2(e), or a
+         subtraction and __expf's multiply) round the exponent at most 4 times, each relative to a magnitude <= 2 max_j |t_j|;
+         an absolute error d of the exponent is a relative error d of the exponential;
+       * every later update of the running maximum multiplies the weight by exp(m_old - m_new): the exponents of those factors
+         telescope to at most 2 max_j |t_j| in all, 4 more roundings at that magnitude (their hardware error: n_rescale below);
+       * v_exp_f32 itself: 1 ulp.
+    The SAME rounded maximum enters numerator and denominator of the softmax, so its own error cancels.
+    qk_mag_max = max over the visible keys of (|q| . |k_j|) / 16, per query (broadcastable to the output)."""
+    # K roundings at magnitude A = max (|q| . |k_j|) / 16, and 4 + 4 at magnitude 2 A = 16 at magnitude A
+    return gamma(K + 16) * qk_mag_max + U_TRANS
+
+
+def attention_terms(q, k, v, mask=None, scale: float = 1.0 / 16.0):
+    """fp64 softmax(q k^T * scale) v with the magnitude products the bound needs.  q [..., Sq, D], k, v [..., Sk, D];
+    mask (bool, broadcastable to [..., Sq, Sk]): True = visible.  -> dict(ref, pv_mag = P |V|, qk_mag_max [..., Sq, 1], lse, p)."""
+    q64, k64, v64 = f64(q), f64(k), f64(v)
+    t = q64 @ k64.transpose(-1, -2) * scale
+    a = q64.abs() @ k64.abs().transpose(-1, -2) * scale
+    if mask is not None:
+        t = t.masked_fill(~mask, float("-inf"))
+        a = a.masked_fill(~mask, 0.0)
+    p = torch.softmax(t, -1)
+    return dict(ref=p @ v64, pv_mag=p @ v64.abs(), qk_mag_max=a.max(-1, keepdim=True).values, lse=torch.logsumexp(t, -1), p=p)
+
+
+def attention_bound(terms: dict, n_keys: int, out_dtype=torch.bfloat16, *, K: int = 256, p_dtype=torch.bfloat16,
+                    n_rescale: int = None, n_fp32: float = None) -> torch.Tensor:
+    """o = round_out( (sum_j p~_j v_j) / (sum_j p_j) ),  p_j = exp(t_j - m).
+
+    * p rounded to p_dtype before the PV product (bf16 on the MFMA in prefill / cached prefill / attn_fwd_rows; fp32, i.e. no
+      such term, in decode attention and attn_small): u_p * (P |V|);
+    * the exponential (exp_rel_err = e): numerator and denominator both move by a relative e: e * (P |V| + |ref|) <= 2 e P |V|;
+      each of the n_rescale updates of the running maximum (default: one per 32-key tile; the kernels without tiles, decode
+      attention with its single maximum and attn_small with one update per key at most, say so) is one more hardware
+      exponential on every earlier weight: + n_rescale * U_TRANS;
+    * fp32 accumulation of numerator (magnitude P |V|) and denominator (|ref| relative): n_fp32 roundings on the way of a term
+      (default n_keys + n_keys / 16 + 16: the additions over n_keys keys, one multiply per tile for the rescale, cross-wave
+      merges, reciprocal and final multiply): 2 * gamma(n_fp32) * P |V|;
+    * output rounding: u_out |ref|."""
+    if n_rescale is None:
+        n_rescale = -(-n_keys // 32)
+    if n_fp32 is None:
+        n_fp32 = n_keys + n_keys / 16 + 16
+    e = exp_rel_err(terms["qk_mag_max"], K) + n_rescale * U_TRANS
+    u_p = unit_roundoff(p_dtype) if p_dtype != torch.float32 else 0.0
+    pv = terms["pv_mag"]
+    err = u_p * pv + 2.0 * e * pv + 2.0 * gamma(n_fp32) * pv
+    return rounded(terms["ref"], err, out_dtype)
+
+
+def lse_bound(terms: dict, n_keys: int, K: int = 256) -> torch.Tensor:
+    """lse = m + log(sum_j exp(t_j - m)) in fp32: a relative error e of the sum is an absolute error e of its logarithm
+    (exponential + accumulation); m, the logarithm (v_log_f32, 1 ulp, times ln 2) and the final add round relative to
+    magnitudes <= 2 max |t| + |lse|."""
+    e = exp_rel_err(terms["qk_mag_max"], K).squeeze(-1) + -(-n_keys // 32) * U_TRANS + gamma(n_keys + n_keys / 16 + 16)
+    mag = 2.0 * terms["qk_mag_max"].squeeze(-1) + terms["lse"].abs()
+    return e + (4.0 * U_F32 + U_TRANS) * (mag + 1.0) + FLOOR
+
+
+def layernorm_terms(x, g, b, eps: float):
+    x64, g64, b64 = f64(x), f64(g), f64(b)
+    mean = x64.mean(-1, keepdim=True)
+    xc = x64 - mean
+    var = (xc * xc).mean(-1, keepdim=True)
+    rstd = (var + eps).rsqrt()
+    return dict(ref=xc * rstd * g64 + b64, mean=mean, var=var, rstd=rstd, xc=xc, x=x64, g=g64, b=b64, eps=eps)
+
+
+def layernorm_bound(t: dict, d: int, out_dtype=torch.bfloat16, *, one_pass_variance: bool = False) -> torch.Tensor:
+    """y = round_out( (x - mean) * rstd * g + b ), statistics by fp32 row reductions over d terms.
+
+    * mean: |d mean| <= gamma(d + 1) * mean|x|;
+    * variance, two-pass form sum (x - mean)^2 / d: relative gamma(d + 4), plus 2 |d mean| mean|x - mean| / var ... bounded below
+      through the Cauchy-Schwarz step mean|x - mean| <= sqrt(var);  one-pass form E[x^2] - mean^2 (one_pass_variance): the
+      cancellation costs gamma(d + 4) * (E[x^2] + mean^2) / var instead;
+    * rstd = rsq(var + eps): half the relative error of var, + 1 ulp;
+    * the element: (x - mean) carries |d mean| + u32 |x - mean|; three more roundings for * rstd, * g, + b."""
+    x, xc, var, rstd, g, b = t["x"], t["xc"], t["var"], t["rstd"], t["g"], t["b"]
+    mean_abs = x.abs().mean(-1, keepdim=True)
+    d_mean = gamma(d + 1) * mean_abs
+    ve = var + t["eps"]
+    if one_pass_variance:
+        ex2 = (x * x).mean(-1, keepdim=True)
+        d_var = gamma(d + 4) * (ex2 + t["mean"] ** 2) + 2.0 * t["mean"].abs() * d_mean
+    else:
+        d_var = gamma(d + 4) * var + 2.0 * d_mean * var.sqrt() + d_mean ** 2
+    rel_rstd = 0.5 * d_var / ve + U_TRANS + U_F32
+    scale = (rstd * g).abs()
+    err = scale * (d_mean + U_F32 * xc.abs()) + (xc * rstd * g).abs() * (rel_rstd + 3.0 * U_F32) + U_F32 * (t["ref"].abs() + b.abs())
+    return rounded(t["ref"], err, out_dtype)
+
+
+def map_bound(ref: torch.Tensor, mag: torch.Tensor, n_ops: int, out_dtype) -> torch.Tensor:
+    """An element-wise map of n_ops fp32 operations on terms whose magnitudes add up to ``mag`` (no reduction)."""
+    return rounded(ref, gamma(n_ops) * mag, out_dtype)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# inputs that make the boundaries count
+# ---------------------------------------------------------------------------------------------------------------------------
+def self_dominant_qkv(shape, c: float, seed: int, device="cpu"):
+    """q of scale 0.5, k_i = bf16(c q_i + 0.25 noise), v of scale 1 (bf16 tensors of ``shape`` = [..., S, D]): each query's own
+    key dominates its softmax row (t_ii ~ c |q_i|^2 / 16 = 4 c at D = 256 against a spread of ~1 for the others), so a causal
+    boundary that is off by one -- the diagonal key left out, a row that reads the row above -- changes the output by far more
+    than the bound.  With i.i.d. q / k / v a long row averages ~S values and one missing key is invisible to any comparator."""
+    g = torch.Generator().manual_seed(seed)
+    q = (torch.randn(*shape, generator=g) * 0.5).to(torch.bfloat16)
+    k = (c * q.float() + 0.25 * torch.randn(*shape, generator=g)).to(torch.bfloat16)
+    v = torch.randn(*shape, generator=g).to(torch.bfloat16)
+    return q.to(device), k.to(device), v.to(device)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# one-call forms for the GEMM / GEMV tests
+# ---------------------------------------------------------------------------------------------------------------------------
+def gelu_new64(x: torch.Tensor) -> torch.Tensor:
+    return 0.5 * x * (1.0 + torch.tanh(math.sqrt(2.0 / math.pi) * (x + 0.044715 * x ** 3)))
+
+
+def linear_reference(a=None, w=None, *, prod=None, bias=None, scale=None, row_scale=None, residuals=(), base=None, act: str = "none",
+                     act_n0: int = 0, post_residuals=(), out_dtype=torch.bfloat16, bf16_partials: int = 0):
+    """(ref, bound) of  out = [base +] act( (A W^T) [* scale[n]] [* row_scale[m]] [+ bias[n]] [+ residuals] ) [+ post_residuals],
+    the activation on the columns >= act_n0, everything in fp64 on the operands' device.  ``prod`` = (exact product, magnitude
+    product, K [, a further absolute error of the product]) replaces A, W for operands that are not plain matrices (the
+    implicit-im2col convolution) or whose product carries a named term of its own (the fp8 MFMA)."""
+    extra = None
+    if prod is None:
+        p, m = product_terms(a, w)
+        K = a.shape[1]
+    elif len(prod) == 4:
+        p, m, K, extra = prod
+    else:
+        p, m, K = prod
+    n = 0
+    if scale is not None:
+        p, m, n = p * f64(scale), m * f64(scale).abs(), n + 1
+        extra = None if extra is None else extra * f64(scale).abs()
+    if row_scale is not None:
+        p, m, n = p * f64(row_scale)[:, None], m * f64(row_scale).abs()[:, None], n + 1
+        extra = None if extra is None else extra * f64(row_scale).abs()[:, None]
+    if bias is not None:
+        p, m, n = p + f64(bias), m + f64(bias).abs(), n + 1
+    for r in residuals:
+        p, m, n = p + f64(r), m + f64(r).abs(), n + 1
+    if base is not None:
+        assert act == "none"
+        p, m, n = p + f64(base), m + f64(base).abs(), n + 1
+    pre = p
+    if act == "relu":
+        ref = torch.relu(pre)
+    elif act == "gelu":
+        ref = gelu_new64(pre)
+    else:
+        ref = pre
+    if act_n0:
+        col = torch.arange(pre.shape[1], device=pre.device) >= act_n0
+        ref = torch.where(col, ref, pre)
+    if not post_residuals:
+        bound = gemm_bound(ref, m, K, out_dtype, n_epilogue=n, bf16_partials=bf16_partials, act=act, pre=pre, extra_err=extra)
+        if act_n0 and act == "gelu":
+            bound = torch.where(col, bound, gemm_bound(pre, m, K, out_dtype, n_epilogue=n, bf16_partials=bf16_partials, extra_err=extra))
+        return ref, bound
+    # terms added after the activation: the activation's fp32 error (the bound of an fp32 output less its own rounding)
+    # passes through, each addition rounds once relative to the magnitudes added so far
+    act_err = gemm_bound(ref, m, K, torch.float64, n_epilogue=n, bf16_partials=bf16_partials, act=act, pre=pre, extra_err=extra)
+    if act_n0 and act == "gelu":
+        act_err = torch.where(col, act_err, gemm_bound(pre, m, K, torch.float64, n_epilogue=n, bf16_partials=bf16_partials, extra_err=extra))
+    out, mag = ref, ref.abs()
+    for r in post_residuals:
+        out, mag = out + f64(r), mag + f64(r).abs()
+    return out, rounded(out, act_err + gamma(len(post_residuals)) * mag, out_dtype)
+
+
+def assert_linear(out: torch.Tensor, what: str, a=None, w=None, **kw) -> float:
+    """Per-element check of a GEMM / GEMV output against linear_reference(...) of the same operands (out_dtype = out's)."""
+    ref, bound = linear_reference(a, w, out_dtype=out.dtype, **kw)
+    return assert_elementwise(out, ref, bound, what)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# one-call forms for the attention tests
+# ---------------------------------------------------------------------------------------------------------------------------
+def causal_mask(Sq: int, Sk: int, p0, device) -> torch.Tensor:
+    """[.., Sq, Sk] bool: query t (at position p0 + t) sees keys 0 .. p0 + t.  p0: int, or a tensor [B] of per-row positions
+    (-> [B, 1, Sq, Sk])."""
+    key = torch.arange(Sk, device=device)[None, :]
+    qpos = torch.arange(Sq, device=device)[:, None]
+    if torch.is_tensor(p0):
+        return key[None, None] <= (qpos[None, None] + p0.to(device).view(-1, 1, 1, 1))
+    return key <= qpos + p0
+
+
+def rows_of(t: torch.Tensor) -> torch.Tensor:
+    """[B, H, S, D] -> the [B*S, H*D] activation layout the attention kernels write."""
+    B, H, S, D = t.shape
+    return t.permute(0, 2, 1, 3).reshape(B * S, H * D)
+
+
+def assert_causal_attention(out_rows, q, k, v, what: str, *, p0=0, p_dtype=torch.bfloat16, lse=None, n_rescale: int = None) -> float:
+    """out_rows [B*Sq, H*D] (any row stride) = softmax(q k^T / 16 under the causal mask at offset p0) v, per element against
+    attention_bound; q [B, H, Sq, D], k / v [B, H, Sk, D] with Sk >= p0 + Sq.  lse [B, H, Sq] fp32 is checked too when given.
+    n_rescale: see attention_bound (0 for the decode kernels, which take one maximum before any exponential)."""
+    Sq, Sk = q.shape[2], k.shape[2]
+    T = attention_terms(q, k, v, causal_mask(Sq, Sk, p0, q.device))
+    n_keys = int(p0.max()) + Sq if torch.is_tensor(p0) else p0 + Sq
+    bound = attention_bound(T, n_keys, out_rows.dtype, K=q.shape[-1], p_dtype=p_dtype, n_rescale=n_rescale)
+    worst = assert_elementwise(out_rows, rows_of(T["ref"]), rows_of(bound), what)
+    if lse is not None:
+        assert_elementwise(lse, T["lse"], lse_bound(T, n_keys, K=q.shape[-1]), what + " (lse)")
+    return worst
+
+
+def dominant_edge_keys(q: torch.Tensor, k: torch.Tensor, gain: float = 4.0, tile: int = 32) -> torch.Tensor:
+    """k with the keys at the edges of the kernels' 32-key tiles (first and last key of every tile, and the very last key, which
+    ends a PARTIAL tile when S % 32 != 0) replaced by bf16(gain * q) of the same position: each of those keys dominates the row of
+    its own query, the only one that sees it as its newest key -- a causal limit or a tile tail that is off by one there shows."""
+    S = k.shape[-2]
+    idx = sorted({j for j in range(S) if j % tile in (0, tile - 1)} | {S - 1})
+    k = k.clone()
+    k[..., idx, :] = (q[..., idx, :].float() * gain).to(torch.bfloat16)
+    return k
+
+
+def attention_backward_reference(q, k, v, dO_rows, out_rows, lse, *, p0: int = 0, scale: float = 1.0 / 16.0) -> dict:
+    """What the flash-attention backward kernels compute FROM THEIR INPUTS -- q, k, v, the output gradient dO_rows [B*S, H*D] and the
+    two tensors the forward kernel saved, out_rows (bf16 O, [B*S, H*D]) and lse (fp32, [B, H, S]) -- in fp64, with per-element
+    bounds -> {"dq" | "dk" | "dv": (ref, bound)}, each [B, H, S, D] for bf16 outputs:
+
+        P_ij = exp(q_i . k_j scale - lse_i),  D_i = sum_d dO_id O_id,  dS = P o (dO V^T - D),
+        dV = P^T dO,  dQ = scale dS K,  dK = scale dS^T Q.
+
+    The reference takes O and lse exactly as the backward kernel reads them.  The forward's own errors (a bf16 O, an lse that is
+    a few ulp off) are the forward tests' business; taking D from the exact softmax instead would put sum_d |dO| bound(O) into
+    every element of dQ and dK -- a worst case over 256 signed errors that is ~16 x what they add up to and hides a dropped store.
+
+    What each step of the kernels (csrc/attention_bwd*.hip, attention_tr.hip) may add:
+      P_ij  = exp2(s_ij sc2 - lse_i log2 e): the relative error e_p of a weight is that of the exponential (exp_rel_err) and the
+              roundings of lse log2(e) and of the subtraction, relative to |lse|;
+      dV_j  = sum_i bf16(P_ij) dO_i : (u_bf16 + e_p) per weight, fp32 accumulation over the queries;
+      D_i   : an fp32 dot product over D terms;
+      dS_ij = bf16( P_ij (dP_ij - D_i) ), dP = dO V^T an fp32 dot product over D; some variants multiply with the already rounded
+              bf16(P) (two bf16 roundings), others with the fp32 weight: 2 u_bf16 covers both;
+      dQ_i  = scale sum_j dS_ij k_j,  dK_j = scale sum_i dS_ij q_i : the error of dS passes through |K| / |Q|, + fp32 accumulation
+              and the output rounding."""
+    B, H, S, D = q.shape
+    n_keys = p0 + S
+    mask = causal_mask(S, k.shape[2], p0, q.device)
+    q64, k64, v64 = f64(q), f64(k), f64(v)
+    dO = f64(dO_rows).reshape(B, S, H, D).permute(0, 2, 1, 3)
+    O = f64(out_rows).reshape(B, S, H, D).permute(0, 2, 1, 3)
+    lse64 = f64(lse)[..., None]
+    t = (q64 @ k64.transpose(-1, -2) * scale).masked_fill(~mask, float("-inf"))
+    P = torch.exp(t - lse64)
+    a_max = (q64.abs() @ k64.abs().transpose(-1, -2) * scale).masked_fill(~mask, 0.0).max(-1, keepdim=True).values
+    u = U_BF16
+    e_p = exp_rel_err(a_max, D) + 4.0 * U_F32 * (lse64.abs() + 1.0)                 # [B,H,S,1]
+    dP, dP_mag = dO @ v64.transpose(-1, -2), dO.abs() @ v64.abs().transpose(-1, -2)
+    Dv = (dO * O).sum(-1, keepdim=True)
+    D_err = gamma(D + 8) * (dO.abs() * O.abs()).sum(-1, keepdim=True)
+    dS = P * (dP - Dv)
+    E = P * (gamma(D + 8) * dP_mag + D_err + gamma(2) * (dP.abs() + Dv.abs())) + (2.0 * u + e_p) * dS.abs()
+    acc = gamma(n_keys + n_keys / 16 + 16)
+    dV = P.transpose(-1, -2) @ dO
+    dV_err = ((u + e_p) * P).transpose(-1, -2) @ dO.abs() + acc * (P.transpose(-1, -2) @ dO.abs())
+    dQ = dS @ k64 * scale
+    dQ_err = (E @ k64.abs() + acc * (dS.abs() @ k64.abs())) * scale
+    dK = dS.transpose(-1, -2) @ q64 * scale
+    dK_err = (E.transpose(-1, -2) @ q64.abs() + acc * (dS.abs().transpose(-1, -2) @ q64.abs())) * scale
+    bf = torch.bfloat16
+    return {"dq": (dQ, rounded(dQ, dQ_err, bf)), "dk": (dK, rounded(dK, dK_err, bf)), "dv": (dV, rounded(dV, dV_err, bf))}
+
+
+def assert_attention_backward(dq, dk, dv, q, k, v, dO_rows, out_rows, lse, what: str) -> dict:
+    ref = attention_backward_reference(q, k, v, dO_rows, out_rows, lse)
+    for name, got in (("dq", dq), ("dk", dk), ("dv", dv)):
+        assert_elementwise(got, ref[name][0], ref[name][1], f"{what} {name}")
+    return ref
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# LayerNorm backward, rotary, column sums
+# ---------------------------------------------------------------------------------------------------------------------------
+def layernorm_bwd_reference(dy, x, g, eps: float, res=None):
+    """dx = rstd (gy - mean(gy) - xhat mean(gy xhat)) [+ res], gy = dy * g, and xhat, in fp64, with per-element bounds for bf16
+    outputs -> {"dx": (ref, bound), "xhat": (ref, bound)}.
+
+    The statistics are those of layernorm_bound (two-pass variance); xhat carries |rstd| (d_mean + u32 |x - mean|) and the
+    relative error of rstd; the two row means are fp32 reductions over d terms (gamma(d + 3) of their magnitude sums), the second
+    one also sees the error of xhat; the element combines three terms (gamma(4) of the magnitudes) and is scaled by rstd."""
+    d = x.shape[-1]
+    T = layernorm_terms(x, torch.ones(d, device=x.device), torch.zeros(d, device=x.device), eps)
+    xc, var, rstd = T["xc"], T["var"], T["rstd"]
+    xh = xc * rstd
+    d_mean = gamma(d + 1) * T["x"].abs().mean(-1, keepdim=True)
+    d_var = gamma(d + 4) * var + 2.0 * d_mean * var.sqrt() + d_mean ** 2
+    rel_rstd = 0.5 * d_var / (var + eps) + U_TRANS + U_F32
+    d_xh = rstd * (d_mean + U_F32 * xc.abs()) + xh.abs() * (rel_rstd + 2.0 * U_F32)
+    gy = f64(dy) * f64(g)
+    c1, c2 = gy.mean(-1, keepdim=True), (gy * xh).mean(-1, keepdim=True)
+    d_c1 = gamma(d + 3) * gy.abs().mean(-1, keepdim=True)
+    d_c2 = gamma(d + 4) * (gy * xh).abs().mean(-1, keepdim=True) + (gy.abs() * d_xh).mean(-1, keepdim=True)
+    inner = gy - c1 - xh * c2
+    inner_mag = gy.abs() + c1.abs() + (xh * c2).abs()
+    d_inner = d_c1 + xh.abs() * d_c2 + c2.abs() * d_xh + gamma(4) * inner_mag
+    dx = rstd * inner
+    d_dx = rstd * d_inner + dx.abs() * (rel_rstd + U_F32)
+    if res is not None:
+        dx = dx + f64(res)
+        d_dx = d_dx + U_F32 * (dx.abs() + f64(res).abs())
+    bf = torch.bfloat16
+    return {"dx": (dx, rounded(dx, d_dx, bf)), "xhat": (xh, rounded(xh, d_xh, bf))}
+
+
+def rotary_reference(x: torch.Tensor, sin_rows: torch.Tensor, cos_rows: torch.Tensor, rot_dim: int):
+    """GPT-J rotary on the first rot_dim of the last axis, pairs (2 i, 2 i + 1) turned by angle i of the row's position:
+    y_2i = x_2i c_i - x_2i+1 s_i,  y_2i+1 = x_2i+1 c_i + x_2i s_i.  x [..., D]; sin_rows / cos_rows [..., rot_dim / 2] (the fp32 table
+    rows the kernel reads, broadcastable) -> (ref, bound): two products and one addition in fp32, one rounding to bf16."""
+    x64 = f64(x)
+    s, c = f64(sin_rows), f64(cos_rows)
+    xe, xo = x64[..., 0:rot_dim:2], x64[..., 1:rot_dim:2]
+    ref, mag = x64.clone(), x64.abs().clone()
+    ref[..., 0:rot_dim:2], ref[..., 1:rot_dim:2] = xe * c - xo * s, xo * c + xe * s
+    mag[..., 0:rot_dim:2] = mag[..., 1:rot_dim:2] = (xe * c).abs() + (xo * s).abs() + (xo * c).abs() + (xe * s).abs()
+    err = gamma(2) * mag
+    err[..., rot_dim:] = 0.0                 # copied, not computed
+    return ref, rounded(ref, err, torch.bfloat16)
+
+
+def ln_fold_reference(x, w2, b2, colsum, eps: float, act: str = "none", out_dtype=torch.bfloat16):
+    """The decode GEMV with LayerNorm folded in (ops.fold_layernorm): y = act( rstd (x W'^T - mean colsum) + b' ) on the PRE-FOLDED
+    operands (W' bf16, colsum and b' fp32 as given), mean / rstd of the row of x taken inside the kernel with the ONE-PASS variance
+    E[x^2] - mean^2 -> (ref, bound).  The product: gamma(K) |x| |W'|^T; the mean: gamma(K + 2) mean|x|, multiplied by |colsum|;
+    the variance cancels: gamma(K + 4) (E[x^2] + mean^2) + 2 |mean| d_mean, rstd inherits half of it relative to var + eps (+ v_rsq_f32);
+    subtraction, two products and the bias: one rounding each relative to the magnitudes at hand."""
+    K = x.shape[1]
+    x64 = f64(x)
+    P, Pmag = product_terms(x, w2)
+    cs, b = f64(colsum), f64(b2)
+    mean = x64.mean(-1, keepdim=True)
+    ex2 = (x64 * x64).mean(-1, keepdim=True)
+    var = (ex2 - mean ** 2).clamp_min(0)
+    rstd = (var + eps).rsqrt()
+    d_mean = gamma(K + 2) * x64.abs().mean(-1, keepdim=True)
+    d_var = gamma(K + 4) * (ex2 + mean ** 2) + 2.0 * mean.abs() * d_mean
+    rel_rstd = 0.5 * d_var / (var + eps) + U_TRANS + 2.0 * U_F32
+    inner = P - mean * cs
+    d_inner = gamma(K) * Pmag + cs.abs() * d_mean + gamma(2) * (P.abs() + (mean * cs).abs())
+    pre = rstd * inner + b
+    err = rstd * d_inner + (rstd * inner).abs() * (rel_rstd + U_F32) + U_F32 * (pre.abs() + b.abs())
+    ref = gelu_new64(pre) if act == "gelu" else (torch.relu(pre) if act == "relu" else pre)
+    return ref, rounded(ref, through_activation(err, act, pre, ref), out_dtype)
+
+
+def cross_entropy_reference(logits: torch.Tensor, targets: torch.Tensor, ignore_index: int = -100) -> dict:
+    """Row losses lse_r - logit_r[target] (0 on ignored rows) and d mean-loss / d logits = (softmax - onehot) / n_valid (bf16), fp64,
+    with bounds -> {"rows": (ref, bound), "dlogits": (ref, bound)}.
+
+    A row reduction over V terms on 256 threads: the maximum is exact; every exponent logit - max is one rounding relative to at
+    most 2 max|logit| and the libm exponential is good to 2 u32: e = 2 u32 (max|logit| + 1); the sum passes a term through at
+    most V / 256 + 9 additions; reciprocal / logarithm (2 u32), the multiplications and the final additions one rounding each."""
+    lg = f64(logits)
+    R, V = lg.shape
+    valid = targets != ignore_index
+    n = max(int(valid.sum()), 1)
+    lmax = lg.abs().amax(-1, keepdim=True)
+    e = 2.0 * U_F32 * (lmax + 1.0) + gamma(V / 256 + 16)
+    lse = torch.logsumexp(lg, -1, keepdim=True)
+    p = torch.exp(lg - lse)
+    tg = targets.clamp_min(0).to(lg.device)
+    onehot = torch.zeros_like(lg).scatter_(1, tg[:, None], 1.0)
+    v = valid.to(lg.device)[:, None]
+    picked = lg.gather(1, tg[:, None])
+    rows = torch.where(v, lse - picked, torch.zeros_like(lse)).squeeze(1)
+    rows_err = (e + 4.0 * U_F32 * (lmax + lse.abs() + picked.abs() + 1.0)).squeeze(1)
+    dl = torch.where(v, (p - onehot) / n, torch.zeros_like(p))
+    dl_err = (2.0 * e * p + 3.0 * U_F32 * (p + onehot)) / n
+    return {"rows": (rows, rounded(rows, rows_err, torch.float32)), "dlogits": (dl, rounded(dl, dl_err, torch.bfloat16)), "n": n}
+
+
+def gelu_new_grad_terms(x: torch.Tensor):
+    """d/dx gelu_new(x) as gelu_new_grad_f of csrc/common.h forms it -> (ref, fp32 error), fp64:
+        sg = rcp(1 + exp(-2u)),  t = 2 sg - 1,  grad = sg + 0.5 x (1 - t^2) k0 (1 + 3 k1 x^2).
+    sg has the relative error of gelu_new_f's sigmoid (through_activation); 1 - t^2 CANCELS for large |x|: its error is absolute,
+    2 |t| d_t + 2 u32 with d_t = 2 d_sg + u32, and is multiplied by C = 0.5 |x| k0 (1 + 3 k1 x^2); the other factors and the final
+    addition round once each relative to their magnitudes."""
+    x = f64(x)
+    k0, k1 = math.sqrt(2.0 / math.pi), 0.044715
+    two_u = 2.0 * k0 * (x + k1 * x ** 3)
+    sg = torch.sigmoid(two_u)
+    t = 2.0 * sg - 1.0
+    C = 0.5 * x.abs() * k0 * (1.0 + 3.0 * k1 * x * x)
+    ref = sg + 0.5 * x * (1.0 - t * t) * k0 * (1.0 + 3.0 * k1 * x * x)
+    d_sg = sg * (6.0 * U_F32 * two_u.abs() + 2.0 * U_TRANS + 2.0 * U_F32)
+    d_t = 2.0 * d_sg + U_F32
+    d_one_minus = 2.0 * t.abs() * d_t + 2.0 * U_F32
+    err = d_sg + C * d_one_minus + gamma(8) * C * (1.0 - t * t) + U_F32 * (ref.abs() + sg)
+    return ref, err
+
+
+# libm erff (OCML) has no accuracy statement in the HIP headers; OCML is built to the OpenCL full-profile table, which allows erf
+# 16 ulp.  Named term of the two gelu_erf passes: 16 ulp = 32 u32 relative to |erf|.
+ERFF_ULPS = 16
+
+
+def gelu_erf_terms(x: torch.Tensor):
+    """torch.nn.GELU() as gelu_erf_f / gelu_erf_grad_f of csrc/backward.hip form it -> (gelu, its fp32 error, gelu', its fp32 error):
+        gelu = 0.5 x (1 + erf(z)), z = x / sqrt 2;      gelu' = 0.5 (1 + erf(z)) + x phi(x), phi = 0.39894 exp(-x^2 / 2) (__expf).
+    1 + erf CANCELS for negative x: its error is absolute -- erff's ERFF_ULPS relative to |erf|, the rounding of z stretched by
+    erf' = 2 / sqrt(pi) exp(-z^2), one addition; the exponential moves by (2 |y| + 4) u32 for the exponent y = x^2 / 2
+    (two products, log2(e), v_exp_f32); every further product or addition rounds once."""
+    x = f64(x)
+    z = x / math.sqrt(2.0)
+    erf = torch.erf(z)
+    d_one_plus = (2.0 * ERFF_ULPS * U_F32 * erf.abs() + U_F32 * z.abs() * (2.0 / math.sqrt(math.pi)) * torch.exp(-z * z) * 2.0
+                  + U_F32 * (1.0 + erf.abs()))
+    gelu = 0.5 * x * (1.0 + erf)
+    gelu_err = 0.5 * x.abs() * d_one_plus + 2.0 * U_F32 * gelu.abs()
+    y = 0.5 * x * x
+    xphi = x * 0.3989422804014327 * torch.exp(-y)
+    grad = 0.5 * (1.0 + erf) + xphi
+    grad_err = 0.5 * d_one_plus + xphi.abs() * ((2.0 * y + 4.0) * U_F32 + gamma(4)) + U_F32 * (grad.abs() + xphi.abs())
+    return gelu, gelu_err, grad, grad_err
+
+
+def adamw_reference(p0, m0, v0, g, norm_sq, lr, b1, b2, eps, wd, step: int, max_norm: float, grad_scale: float = 1.0) -> dict:
+    """ONE step of the fused clip + AdamW kernel (csrc/backward.hip: adamw_kernel) from the state (p0, m0, v0), in fp64 on the same
+    fp32 inputs and fp32-rounded hyper-parameters -> {"p" | "m" | "v": (ref, fp32 bound), "p_bf16": (ref, bf16 bound)}.
+    The bias corrections 1 - beta^step cancel: their relative error is 3 u32 beta^step / (1 - beta^step) (powf to 2 ulp, one
+    subtraction); the clip factor takes a square root, two products, an addition, a division and a minimum: gamma(8)."""
+    f32c = lambda x: float(torch.tensor(x, dtype=torch.float32))
+    lr, b1, b2, eps, wd, max_norm, gs = map(f32c, (lr, b1, b2, eps, wd, max_norm, grad_scale))
+    d = f64
+    clip = gs
+    if norm_sq is not None and max_norm > 0:
+        clip = gs * min(1.0, max_norm / (float(d(norm_sq).sqrt()) * gs + f32c(1e-6)))
+    c_rel = gamma(8)
+    gi = d(g) * clip
+    m_r = b1 * d(m0) + (1 - b1) * gi
+    d_m = gamma(4) * ((b1 * d(m0)).abs() + ((1 - b1) * gi).abs()) + (1 - b1) * gi.abs() * c_rel
+    v_r = b2 * d(v0) + (1 - b2) * gi * gi
+    d_v = gamma(5) * v_r + (1 - b2) * gi * gi * 2 * c_rel
+    bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
+    rel_bc1, rel_bc2 = 3 * U_F32 * b1 ** step / bc1 + U_F32, 3 * U_F32 * b2 ** step / bc2 + U_F32
+    p1 = d(p0) - lr * wd * d(p0)
+    den = (v_r / bc2).sqrt() + eps
+    upd = lr * (m_r / bc1) / den
+    d_upd = lr / bc1 / den * d_m + upd.abs() * (rel_bc1 + 0.5 * (d_v / v_r.clamp_min(1e-300) + rel_bc2) + gamma(8))
+    p_r = p1 - upd
+    d_p = gamma(3) * (d(p0).abs() * (1 + lr * wd)) + d_upd + U_F32 * (p1.abs() + upd.abs())
+    f32 = torch.float32
+    return {"m": (m_r, rounded(m_r, d_m, f32)), "v": (v_r, rounded(v_r, d_v, f32)), "p": (p_r, rounded(p_r, d_p, f32)),
+            "p_bf16": (p_r, rounded(p_r, d_p + U_F32 * p_r.abs(), torch.bfloat16))}

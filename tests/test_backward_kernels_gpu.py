@@ -5,6 +5,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import kernel_compare as kcmp
+
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
 
@@ -46,8 +48,13 @@ def test_colsum(dev):
     out = torch.zeros(520, device=dev)
     ops.colsum(x, out)
     assert rel(out, x.float().sum(0)) < 1e-5
+    s1, m1 = x.double().sum(0), x.double().abs().sum(0)
+    kcmp.assert_elementwise(out, s1, kcmp.rounded(s1, kcmp.gamma(1000 + 8) * m1, torch.float32), "colsum")
+    first = out.clone()
     ops.colsum(x, out, y)                                         # accumulates
     assert rel(out, x.float().sum(0) + (x.float() * y.float()).sum(0)) < 1e-5
+    s2, m2 = first.double() + (x.double() * y.double()).sum(0), first.double().abs() + (x.double() * y.double()).abs().sum(0)
+    kcmp.assert_elementwise(out, s2, kcmp.rounded(s2, kcmp.gamma(1000 + 9) * m2, torch.float32), "colsum of x * y, accumulated")
 
 
 @pytest.mark.parametrize("rows,d", [(9, 4096), (33, 512)])
@@ -63,6 +70,9 @@ def test_layernorm_bwd(dev, rows, d):
     dx, xh = ops.layernorm_bwd(dy, x, g, 1e-5, res=res, want_xhat=True)
     assert rel(dx, xf.grad + res.float()) < 4e-3
     assert rel(xh, F.layer_norm(x.float(), (d,))) < 4e-3
+    R = kcmp.layernorm_bwd_reference(dy, x, g, 1e-5, res=res)
+    kcmp.assert_elementwise(dx, *R["dx"], f"layernorm_bwd dx {rows}x{d}")
+    kcmp.assert_elementwise(xh, *R["xhat"], f"layernorm_bwd xhat {rows}x{d}")
 
 
 def test_ce_fwd_bwd(dev):
@@ -77,6 +87,7 @@ def test_ce_fwd_bwd(dev):
     loss, dl = ops.cross_entropy_fwd_bwd(lg, tg.to(dev), 1056)
     assert abs(float(loss) - float(ref)) < 1e-4
     assert rel(dl[:, :V], lgr.grad) < 4e-3 and bool((dl[:, V:] == 0).all())
+    kcmp.assert_elementwise(dl[:, :V], *kcmp.cross_entropy_reference(lg, tg)["dlogits"], "cross-entropy d logits")
 
 
 def test_epilogue_aux_modes(dev):
@@ -88,20 +99,39 @@ def test_epilogue_aux_modes(dev):
     r0 = rnd(M, N, dev=dev, seed=14).to(BF16)
     lin = ops.PackedLinear(w, bias=rnd(N, dev=dev, seed=15))
     acc = a.float() @ w.float().t() + lin.bias
+    # per element: the accumulator A W^T + bias in fp64 with its fp32 error (a bound without an output rounding), then what
+    # each aux mode does to it -- a product with a factor f multiplies the error by |f| and rounds once more
+    acc64, acc_err = kcmp.linear_reference(a, w, bias=lin.bias, out_dtype=torch.float64)
+    gate = (aux.double() > 0).double()
+    U = kcmp.U_F32
+
+    def bound(ref, err):
+        return kcmp.rounded(ref, err, BF16)
     out = ops.gemm(a, lin, aux=aux, aux_mode=ops.MG_AUX_RELU_GATE, residuals=(r0,))
     assert rel(out, acc * (aux.float() > 0) + r0.float()) < 4e-3
+    ref = acc64 * gate + r0.double()
+    kcmp.assert_elementwise(out, ref, bound(ref, acc_err * gate + U * ((acc64 * gate).abs() + r0.double().abs())), "aux relu gate, then residual")
     out = ops.gemm(a, lin, aux=aux, aux_mode=ops.MG_AUX_RELU_GATE, residuals=(r0,), aux_after=True)
     assert rel(out, (acc + r0.float()) * (aux.float() > 0)) < 4e-3
+    ref = (acc64 + r0.double()) * gate
+    kcmp.assert_elementwise(out, ref, bound(ref, (acc_err + U * (acc64.abs() + r0.double().abs())) * gate), "residual, then aux relu gate")
     xa = aux.float().requires_grad_(True)
     gl = 0.5 * xa * (1 + torch.tanh(math.sqrt(2 / math.pi) * (xa + 0.044715 * xa ** 3)))
     gl.sum().backward()
     out = ops.gemm(a, lin, aux=aux, aux_mode=ops.MG_AUX_GELU_GRAD)
     assert rel(out, acc * xa.grad) < 4e-3
+    gg, gg_err = kcmp.gelu_new_grad_terms(aux)
+    ref = acc64 * gg
+    kcmp.assert_elementwise(out, ref, bound(ref, acc_err * gg.abs() + acc64.abs() * gg_err + U * ref.abs()), "aux gelu gradient")
     out = ops.gemm(a, lin, aux=aux, aux_mode=ops.MG_AUX_MUL)
     assert rel(out, acc * aux.float()) < 4e-3
+    ref = acc64 * aux.double()
+    kcmp.assert_elementwise(out, ref, bound(ref, acc_err * aux.double().abs() + U * ref.abs()), "aux multiply")
     pre = torch.empty(M, N, dtype=BF16, device=dev)
     out = ops.gemm(a, lin, act=ops.MG_ACT_GELU_NEW, out2=pre)
     assert rel(pre, acc) < 4e-3 and rel(out, F.gelu(acc, approximate="tanh")) < 4e-3
+    kcmp.assert_linear(pre, "pre-activation copy (out2)", a, w, bias=lin.bias)
+    kcmp.assert_linear(out, "gelu beside the pre-activation copy", a, w, bias=lin.bias, act="gelu")
 
 
 @pytest.mark.parametrize("B,H,S", [(1, 1, 64), (2, 2, 57), (1, 2, 152), (1, 1, 1), (1, 2, 300), (2, 1, 385), (1, 1, 1024)])
@@ -130,6 +160,40 @@ def test_attention_backward(dev, B, H, S):
             assert float(got.float().abs().max()) < 1e-6, name
         else:
             assert rel(got, ref) < 1.5e-2, (name, rel(got, ref))
+    kcmp.assert_causal_attention(out, q, k, v, f"prefill attention (forward of the backward test) B={B} H={H} S={S}", lse=lse)
+    kcmp.assert_attention_backward(dq, dk, dv, q, k, v, dO, out, lse, f"attn_bwd B={B} H={H} S={S}")
+
+
+@pytest.mark.parametrize("inputs", ["self c=1", "self c=2", "tile edges"])
+@pytest.mark.parametrize("S", [57, 300, 385, 1024, 2048])
+def test_attention_backward_boundary_inputs(dev, S, inputs):
+    """dQ / dK / dV of attn_bwd and attn_bwd_rows (and the forward of attn_fwd_rows) on inputs where the causal boundary counts:
+    each query's own key dominates its row, or the keys at the edges of the 32-key tiles and the last key do
+    (kernel_compare.self_dominant_qkv / dominant_edge_keys); partial (57 / 300 / 385) and full (1024 / 2048) last tiles.  dV_j is
+    sum_i P_ij dO_i: a diagonal weight that is left out, or taken from the row above, moves dV_j by about |dO_j|."""
+    from magma_amd import ops
+    B, H = 1, 2
+    d = H * 256
+    if inputs == "tile edges":
+        q = rnd(B, H, S, 256, dev=dev, seed=24, scale=0.5).to(BF16)
+        k = kcmp.dominant_edge_keys(q, rnd(B, H, S, 256, dev=dev, seed=25, scale=0.5).to(BF16))
+        v = rnd(B, H, S, 256, dev=dev, seed=26).to(BF16)
+    else:
+        q, k, v = kcmp.self_dominant_qkv((B, H, S, 256), float(inputs[-1]), seed=27, device=dev)
+    dO = rnd(B * S, d, dev=dev, seed=28).to(BF16)
+    x = ops.AttnRows.of_bhsd(q, k, v)
+    out = torch.empty(B * S, d, dtype=BF16, device=dev)
+    lse = torch.empty(B, H, S, dtype=torch.float32, device=dev)
+    ops.attn_fwd_rows(x, out, lse=lse)
+    kcmp.assert_causal_attention(out, q, k, v, f"attn_fwd_rows, {inputs}, S={S}", lse=lse)
+    kcmp.assert_attention_backward(*ops.attn_bwd_rows(x, dO, out, lse), q, k, v, dO, out, lse, f"attn_bwd_rows, {inputs}, S={S}")
+    hs = H * S * 256
+    vt, qt, kt = (ops.head_transpose(t, B, H, S, sb=hs, ss=256, sh=S * 256) for t in (v, q, k))
+    dOt = ops.head_transpose(dO, B, H, S, sb=S * d, ss=d, sh=256)
+    out2, lse2 = torch.empty_like(out), torch.empty_like(lse)
+    ops.attn_prefill(q, k, vt, out2, B, H, S, lse=lse2)
+    kcmp.assert_attention_backward(*ops.attn_bwd(q, k, v, qt, kt, dO, dOt, out2, lse2, B, H, S), q, k, v, dO, out2, lse2,
+                                   f"attn_bwd, {inputs}, S={S}")
 
 
 @pytest.mark.parametrize("variant", [0, 1, 2, 3, 4, 5, 6, 7, 8])
@@ -163,6 +227,7 @@ def test_attention_backward_kernel_variants(dev, monkeypatch, variant, B, H, S):
             assert float(got.float().abs().max()) < 1e-6, name
         else:
             assert rel(got, ref) < 1.5e-2, (variant, name, rel(got, ref))
+    kcmp.assert_attention_backward(dq, dk, dv, q, k, v, dO, out, lse, f"attn_bwd variant {variant} B={B} H={H} S={S}")
     rot = 64
     inv = 1.0 / (10000 ** (torch.arange(0, rot, 2, dtype=torch.float32, device=dev) / rot))
     ang = torch.arange(S + 3, dtype=torch.float32, device=dev)[:, None] * inv[None, :]
@@ -292,6 +357,7 @@ def test_attention_without_transposed_images(dev, B, H, S):
     sc = sc.masked_fill(~torch.ones(S, S, dtype=torch.bool, device=dev).tril(), float("-inf"))
     o = (torch.softmax(sc, -1) @ vf).permute(0, 2, 1, 3).reshape(B * S, d)
     assert rel(out, o.detach()) < 1e-2
+    kcmp.assert_causal_attention(out, q, k, v, f"attn_fwd_rows B={B} H={H} S={S}", lse=lse)
     o.backward(dO.float())
     dq, dk, dv = ops.attn_bwd_rows(x, dO, out, lse)
     for got, ref, name in ((dq, qf.grad, "dq"), (dk, kf.grad, "dk"), (dv, vf.grad, "dv")):
@@ -299,6 +365,7 @@ def test_attention_without_transposed_images(dev, B, H, S):
             assert float(got.float().abs().max()) < 1e-6, name
         else:
             assert rel(got, ref) < 1.5e-2, (name, rel(got, ref))
+    kcmp.assert_attention_backward(dq, dk, dv, q, k, v, dO, out, lse, f"attn_bwd_rows B={B} H={H} S={S}")
     for a, b_ in zip(ops.attn_bwd_rows(xf, dO, out_f[:, :d], lse), (dq, dk, dv)):
         assert torch.equal(a, b_)
     rot = 64
@@ -345,6 +412,12 @@ def test_rotary_merge_bwd(dev):
     got = out.view(B, S, 3, H, 256).float().cpu()
     assert rel(got[:, :, 0], x.grad) < 4e-3
     assert torch.equal(got[:, :, 2], dv.float().cpu().permute(0, 2, 1, 3))
+    # per element: the inverse rotation R(-theta) of dq and dk = the rotary with -sin
+    sd, cd = sin_t[:S].to(dev)[:, None, :], cos_t[:S].to(dev)[:, None, :]
+    gd = out.view(B, S, 3, H, 256)
+    for i, (src, name) in enumerate(((dq, "dq"), (dk, "dk"))):
+        rref, rbound = kcmp.rotary_reference(src.permute(0, 2, 1, 3), -sd, cd, 64)
+        kcmp.assert_elementwise(gd[:, :, i], rref, rbound, f"rotary_merge_bwd {name}")
 
 
 def test_conv_backward_helpers(dev):
@@ -355,8 +428,13 @@ def test_conv_backward_helpers(dev):
     xr = torch.zeros(B, C, H, W, device=dev, requires_grad=True)
     F.avg_pool2d(xr, 2).backward(dy.float().permute(0, 3, 1, 2))
     assert rel(dx, xr.grad.permute(0, 2, 3, 1)) < 4e-3
+    dx_ref = (dy.double() / 4).repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)      # each input pixel gets dy / 4
+    kcmp.assert_elementwise(dx, dx_ref, kcmp.map_bound(dx_ref, dx_ref.abs(), 1, BF16), "avgpool2_bwd")
     a, b, gt = (rnd(64, 24, dev=dev, seed=41 + i).to(BF16) for i in range(3))
     assert rel(ops.add_gate(a, b, gt), (a.float() + b.float()) * (gt.float() > 0)) < 4e-3
+    ag_ref = (a.double() + b.double()) * (gt.double() > 0)
+    kcmp.assert_elementwise(ops.add_gate(a, b, gt), ag_ref, kcmp.map_bound(ag_ref, (a.double().abs() + b.double().abs()) * (gt.double() > 0), 1, BF16),
+                            "add_gate")
     assert torch.equal(ops.add_gate(a), a)
     # im2col^T x dY^T == conv weight gradient
     x = rnd(B, H, W, C, dev=dev, seed=44).to(BF16)
@@ -374,6 +452,11 @@ def test_conv_backward_helpers(dev):
     ops.bn_param_grad(g, y, sub, gamma, beta, dg, db)
     assert rel(db, g.float().sum(0)) < 1e-4
     assert rel(dg, (g.float() * (y.float() - sub.float() - beta) / gamma).sum(0)) < 1e-4
+    g64, y64, s64 = g.double(), y.double(), sub.double()
+    db_r, dg_r = g64.sum(0), (g64 * (y64 - s64 - beta.double()) / gamma.double()).sum(0)
+    dg_m = (g64.abs() * (y64.abs() + s64.abs() + beta.double().abs()) / gamma.double().abs()).sum(0)
+    kcmp.assert_elementwise(db, db_r, kcmp.rounded(db_r, kcmp.gamma(M + 8) * g64.abs().sum(0), torch.float32), f"bn_param_grad dbeta {M}x{C}")
+    kcmp.assert_elementwise(dg, dg_r, kcmp.rounded(dg_r, kcmp.gamma(M + 12) * dg_m, torch.float32), f"bn_param_grad dgamma {M}x{C}")
     # ragged row counts around the kernel's 16-row groups / 256-row blocks, with and without the residual operand, C > 512
     for M2, C2, with_sub in ((1, 8, True), (267, 520, False), (513 + 7, 40, True)):
         g2, y2 = rnd(M2, C2, dev=dev, seed=52).to(BF16), rnd(M2, C2, dev=dev, seed=53).to(BF16)
@@ -383,6 +466,13 @@ def test_conv_backward_helpers(dev):
         ops.bn_param_grad(g2, y2, s2, gm, bt, dg2, db2)
         yy = y2.float() - (s2.float() if with_sub else 0)
         assert rel(db2, g2.float().sum(0)) < 1e-4 and rel(dg2, (g2.float() * (yy - bt) / gm).sum(0)) < 1e-4, (M2, C2)
+        # per element: column sums over M2 rows in fp32 (any order: threads, LDS, atomics), four operations per term of dgamma
+        y64 = y2.double() - (s2.double() if with_sub else 0.0)
+        db_r, db_m = g2.double().sum(0), g2.double().abs().sum(0)
+        dg_r = (g2.double() * (y64 - bt.double()) / gm.double()).sum(0)
+        dg_m = (g2.double().abs() * (y2.double().abs() + (s2.double().abs() if with_sub else 0.0) + bt.double().abs()) / gm.double().abs()).sum(0)
+        kcmp.assert_elementwise(db2, db_r, kcmp.rounded(db_r, kcmp.gamma(M2 + 8) * db_m, torch.float32), f"bn_param_grad dbeta {M2}x{C2}")
+        kcmp.assert_elementwise(dg2, dg_r, kcmp.rounded(dg_r, kcmp.gamma(M2 + 12) * dg_m, torch.float32), f"bn_param_grad dgamma {M2}x{C2}")
         # the same sums taken while g is transposed for the weight-gradient GEMM (one pass over g): the transpose bit for bit, the
         # sums accumulated ON TOP of what the buffers hold
         dg3, db3 = torch.full((C2,), 3.0, device=dev), torch.full((C2,), -2.0, device=dev)
@@ -406,7 +496,12 @@ def test_adamw_and_clip(dev):
         opt.step()
         nsq = torch.zeros(1, device=dev)
         ops.sumsq(g, nsq)
+        before = (p.clone(), m.clone(), v.clone())
         ops.adamw(p, m, v, g, pb, 1e-2, 0.9, 0.95, 1e-8, 0.1, step, max_norm=1.0, norm_sq=nsq)
+        # per element, each step from the state the kernel itself left (errors of earlier steps are not re-counted)
+        R = kcmp.adamw_reference(*before, g, nsq, 1e-2, 0.9, 0.95, 1e-8, 0.1, step, 1.0)
+        for name, got in (("m", m), ("v", v), ("p", p), ("p_bf16", pb)):
+            kcmp.assert_elementwise(got, *R[name], f"adamw + clip, step {step}, {name}")
     assert rel(p, ref_p.detach()) < 1e-5
     assert torch.equal(pb, p.to(BF16))
 
@@ -468,3 +563,168 @@ def test_transpose_colsum(dev, R, C):
     assert bool((xt[:, R:] == 0).all())
     ref = 0.5 + x.float().sum(0)
     assert float((acc - ref).abs().max()) <= 1e-3 * float(ref.abs().max()) + 1e-3
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# entry points that only whole-model tests reached: each against an fp64 statement of the same operation, per element
+# (tests/kernel_compare.py), at one aligned and one ragged shape
+# ---------------------------------------------------------------------------------------------------------------------------
+U32 = kcmp.U_F32
+
+
+@pytest.mark.parametrize("n", [8 * 4096, 8 * 37, 8])
+def test_mul(dev, n):
+    """mg_mul_bf16 (dropout backward): one fp32 product rounded to bf16."""
+    from magma_amd import ops
+    a, b = rnd(n, dev=dev, seed=801).to(BF16), rnd(n, dev=dev, seed=802).to(BF16)
+    ref = a.double() * b.double()
+    kcmp.assert_elementwise(ops.mul(a, b), ref, kcmp.map_bound(ref, ref.abs(), 1, BF16), f"mul n={n}")
+
+
+@pytest.mark.parametrize("rows,cols,ld", [(64, 256, 256), (37, 203, 208), (1, 5, 9)])
+@pytest.mark.parametrize("with_scale", [False, True])
+def test_scale_rows_acc(dev, rows, cols, ld, with_scale):
+    """mg_scale_rows_acc_f32: dst[r, c] += src[r, c] * row_scale[r] in fp32, src at a row stride wider than cols; the columns of src
+    past cols never reach dst."""
+    from magma_amd import ops
+    dst0 = rnd(rows, cols, dev=dev, seed=811)
+    wide = rnd(rows, ld, dev=dev, seed=812)
+    rs = rnd(rows, dev=dev, seed=813) if with_scale else None
+    dst = dst0.clone()
+    ops.scale_rows_acc(dst, wide[:, :cols], rs)
+    term = wide[:, :cols].double() * (rs.double()[:, None] if with_scale else 1.0)
+    ref = dst0.double() + term
+    kcmp.assert_elementwise(dst, ref, kcmp.map_bound(ref, dst0.double().abs() + term.abs(), 2, torch.float32),
+                            f"scale_rows_acc {rows}x{cols} ld {ld} row_scale={with_scale}")
+
+
+@pytest.mark.parametrize("n", [4 * 65536, 4 * 1001, 4])
+def test_cast_f32_bf16(dev, n):
+    """mg_cast_f32_bf16: round to nearest even, bit for bit what torch's cast gives -- ties to either side and a value just above
+    a tie among the inputs."""
+    from magma_amd import ops
+    src = rnd(n, dev=dev, seed=821) * 3
+    special = torch.tensor([1 + 2.0 ** -8, 1 + 3 * 2.0 ** -8, 1 + 2.0 ** -8 + 2.0 ** -23, -(1 + 2.0 ** -8)], device=dev)
+    src[:4] = special
+    dst = torch.full((n,), float("nan"), dtype=BF16, device=dev)
+    ops.cast_f32_bf16(src, dst)
+    assert torch.equal(dst, src.to(BF16))
+
+
+@pytest.mark.parametrize("C", [256, 300, 8])
+@pytest.mark.parametrize("M", [1568, 37])
+def test_bn_batch_fold(dev, C, M):
+    """mg_bn_batch_fold_f32: per-channel sums -> (scale, shift, mean, rstd) and the in-place running-statistics update of
+    nn.BatchNorm2d (momentum, unbiased variance), against fp64 on the same sums.  var = E[x^2] - mean^2 cancels: its bound
+    is relative to E[x^2] + mean^2, and rstd inherits half of it relative to var + eps."""
+    from magma_amd import ops
+    eps, mom = 1e-5, 0.1
+    x = rnd(M, C, dev=dev, seed=831) * (rnd(C, dev=dev, seed=832).abs() + 0.5) + rnd(C, dev=dev, seed=833) * 0.5
+    s1, s2 = x.sum(0).contiguous(), (x * x).sum(0).contiguous()
+    g, b = rnd(C, dev=dev, seed=834) * 0.2 + 1, rnd(C, dev=dev, seed=835) * 0.2
+    rm0, rv0 = rnd(C, dev=dev, seed=836), rnd(C, dev=dev, seed=837).abs() + 0.3
+    rm, rv = rm0.clone(), rv0.clone()
+    scale, shift, mean, rstd = ops.bn_batch_fold(s1, s2, g, b, M, eps, mom, rm, rv)
+    inv_m = 1.0 / M
+    mom32, eps32 = float(torch.tensor(mom, dtype=torch.float32)), float(torch.tensor(eps, dtype=torch.float32))
+    mean_r = s1.double() * inv_m
+    ex2 = s2.double() * inv_m
+    var_r = (ex2 - mean_r ** 2).clamp_min(0)
+    rstd_r = (var_r + eps32).rsqrt()
+    scale_r = g.double() * rstd_r
+    shift_r = b.double() - mean_r * scale_r
+    unb = M / (M - 1)
+    rm_r = (1 - mom32) * rm0.double() + mom32 * mean_r
+    rv_r = (1 - mom32) * rv0.double() + mom32 * var_r * unb
+    d_mean = kcmp.gamma(2) * mean_r.abs()                                   # 1 / M rounded, one product
+    d_var = kcmp.gamma(4) * (ex2 + mean_r ** 2) + 2 * mean_r.abs() * d_mean
+    rel_rstd = 0.5 * d_var / (var_r + eps32) + kcmp.U_TRANS + 2 * U32      # v_rsq_f32 (1 ulp), the addition of eps
+    f32 = torch.float32
+    tag = f"bn_batch_fold C={C} M={M}"
+    kcmp.assert_elementwise(mean, mean_r, kcmp.rounded(mean_r, d_mean, f32), tag + " mean")
+    kcmp.assert_elementwise(rstd, rstd_r, kcmp.rounded(rstd_r, rel_rstd * rstd_r, f32), tag + " rstd")
+    kcmp.assert_elementwise(scale, scale_r, kcmp.rounded(scale_r, (rel_rstd + U32) * scale_r.abs(), f32), tag + " scale")
+    d_ms = (mean_r * scale_r).abs() * (kcmp.gamma(2) + rel_rstd + 2 * U32)
+    kcmp.assert_elementwise(shift, shift_r, kcmp.rounded(shift_r, d_ms + U32 * (b.double().abs() + (mean_r * scale_r).abs()), f32), tag + " shift")
+    run_mag = ((1 - mom32) * rm0.double()).abs() + (mom32 * mean_r).abs()
+    kcmp.assert_elementwise(rm, rm_r, kcmp.rounded(rm_r, kcmp.gamma(4) * run_mag + mom32 * d_mean, f32), tag + " running mean (in place)")
+    run_mag = ((1 - mom32) * rv0.double()).abs() + (mom32 * var_r * unb).abs()
+    kcmp.assert_elementwise(rv, rv_r, kcmp.rounded(rv_r, kcmp.gamma(5) * run_mag + mom32 * unb * d_var, f32), tag + " running variance (in place)")
+    # without running statistics nothing else changes
+    out2 = ops.bn_batch_fold(s1, s2, g, b, M, eps, mom)
+    assert all(torch.equal(a_, b_) for a_, b_ in zip(out2, (scale, shift, mean, rstd)))
+
+
+@pytest.mark.parametrize("M,C", [(64, 64), (37, 40), (1, 8), (4099, 264)])
+@pytest.mark.parametrize("relu", [False, True])
+@pytest.mark.parametrize("with_res", [False, True])
+def test_bn_apply(dev, M, C, relu, with_res):
+    """mg_bn_apply_bf16: y = [relu](z * scale[c] + shift[c] [+ res]), three fp32 operations, one rounding to bf16."""
+    from magma_amd import ops
+    z = rnd(M, C, dev=dev, seed=841).to(BF16)
+    res = rnd(M, C, dev=dev, seed=842).to(BF16) if with_res else None
+    scale, shift = rnd(C, dev=dev, seed=843) * 0.3 + 1, rnd(C, dev=dev, seed=844)
+    y = ops.bn_apply(z, scale, shift, res, relu)
+    pre = z.double() * scale.double() + shift.double() + (res.double() if with_res else 0.0)
+    mag = (z.double() * scale.double()).abs() + shift.double().abs() + (res.double().abs() if with_res else 0.0)
+    ref = pre.clamp_min(0) if relu else pre
+    kcmp.assert_elementwise(y, ref, kcmp.map_bound(ref, mag, 3, BF16), f"bn_apply {M}x{C} relu={relu} res={with_res}")
+
+
+@pytest.mark.parametrize("M,C", [(64, 64), (37, 40), (1, 8), (4099, 264)])
+def test_bn_bwd_dz(dev, M, C):
+    """mg_bn_bwd_dz_bf16: dz = gamma rstd (g - dbeta / M - xhat dgamma / M), xhat = (z - mean) rstd; ten fp32 operations at most on
+    the way of a term (1 / M is itself rounded), magnitudes summed without cancellation, one rounding to bf16."""
+    from magma_amd import ops
+    g = rnd(M, C, dev=dev, seed=851).to(BF16)
+    z = (rnd(M, C, dev=dev, seed=852) * 2 + 0.3).to(BF16)
+    mean, rstd = rnd(C, dev=dev, seed=853) * 0.3, rnd(C, dev=dev, seed=854).abs() * 0.3 + 0.4
+    gamma_, dgamma, dbeta = rnd(C, dev=dev, seed=855) * 0.2 + 1, rnd(C, dev=dev, seed=856) * M ** 0.5, rnd(C, dev=dev, seed=857) * M ** 0.5
+    dz = ops.bn_bwd_dz(g, z, mean, rstd, gamma_, dgamma, dbeta)
+    d64 = lambda t: t.double()
+    xh = (d64(z) - d64(mean)) * d64(rstd)
+    xh_mag = (d64(z).abs() + d64(mean).abs()) * d64(rstd)
+    t2, t3, t3_mag = d64(dbeta) / M, xh * d64(dgamma) / M, xh_mag * d64(dgamma).abs() / M
+    k = (d64(gamma_) * d64(rstd)).abs()
+    ref = d64(gamma_) * d64(rstd) * (d64(g) - t2 - t3)
+    kcmp.assert_elementwise(dz, ref, kcmp.map_bound(ref, k * (d64(g).abs() + t2.abs() + t3_mag), 10, BF16), f"bn_bwd_dz {M}x{C}")
+
+
+@pytest.mark.parametrize("n", [8 * 4096 + 3, 1000, 1 << 20])
+def test_sumsq_bf16_gradients(dev, n):
+    """mg_sumsq_bf16 (the bf16 buckets of the data-parallel step; ops.sumsq dispatches on the dtype): out[0] += sum g^2.  A term
+    passes through at most n / 256 additions in its thread, 9 in the workgroup and one atomic per workgroup (<= 2048)."""
+    from magma_amd import ops
+    g = (rnd(n, dev=dev, seed=861) * 3).to(BF16)
+    out = torch.full((1,), 2.5, device=dev)
+    ops.sumsq(g, out)
+    ref = 2.5 + (g.double() ** 2).sum().reshape(1)
+    kcmp.assert_elementwise(out, ref, kcmp.rounded(ref, kcmp.gamma(n // 256 + 2048 + 16) * ref, torch.float32), f"sumsq bf16 n={n}")
+    out32 = torch.full((1,), 2.5, device=dev)
+    ops.sumsq(g.float(), out32)                         # the fp32 form on the same values
+    kcmp.assert_elementwise(out32, ref, kcmp.rounded(ref, kcmp.gamma(n // 256 + 2048 + 16) * ref, torch.float32), f"sumsq f32 n={n}")
+
+
+@pytest.mark.parametrize("gdtype", [BF16, torch.float32])
+@pytest.mark.parametrize("n", [10007, 1 << 16, 515])
+def test_adamw_one_step_per_element(dev, n, gdtype):
+    """mg_adamw_gbf16_f32 / mg_adamw_f32 (ops.adamw dispatches on the gradient's dtype): ONE step from a given state (p, m, v all
+    non-trivial, step 3) with clipping and a gradient scale, p / m / v / the bf16 model copy per element against fp64 on the same
+    fp32 inputs and hyper-parameters.  The bias corrections 1 - beta^step cancel: their relative error is
+    3 u32 beta^step / (1 - beta^step) (powf to 2 ulp, one subtraction)."""
+    from magma_amd import ops
+    lr, b1, b2, eps, wd, step, max_norm, gs = 1e-2, 0.9, 0.95, 1e-8, 0.1, 3, 1.0, 0.25
+    p0 = rnd(n, dev=dev, seed=871)
+    m0 = rnd(n, dev=dev, seed=872) * 0.1
+    v0 = rnd(n, dev=dev, seed=873).abs() * 0.01
+    g = (rnd(n, dev=dev, seed=874) * 3).to(gdtype)
+    nsq = torch.zeros(1, device=dev)
+    ops.sumsq(g, nsq)
+    p, m, v = p0.clone(), m0.clone(), v0.clone()
+    pb = torch.full((n,), float("nan"), dtype=BF16, device=dev)
+    ops.adamw(p, m, v, g, pb, lr, b1, b2, eps, wd, step, max_norm=max_norm, norm_sq=nsq, grad_scale=gs)
+    R = kcmp.adamw_reference(p0, m0, v0, g, nsq, lr, b1, b2, eps, wd, step, max_norm, gs)
+    tag = f"adamw n={n} gradients {gdtype}"
+    for name, got in (("m", m), ("v", v), ("p", p), ("p_bf16", pb)):
+        kcmp.assert_elementwise(got, *R[name], f"{tag} {name}")
+    assert torch.equal(pb, p.to(BF16))

@@ -8,6 +8,8 @@ import math
 import pytest
 import torch
 
+import kernel_compare as kcmp
+
 pytestmark = pytest.mark.gpu
 
 BF16 = torch.bfloat16
@@ -47,12 +49,44 @@ def test_chunk_attention_per_row_positions(dev, T):
     for b, p in enumerate(pos):
         e = rel(out[b * T:(b + 1) * T], ref_chunk(q[b], kc[b], vc[b], p, T))
         assert math.isfinite(e) and e <= 3e-3, f"row {b} (p = {p}, T = {T}): rel-L2 {e:.3e}"
+    kcmp.assert_causal_attention(out, q, kc, vc, f"chunk attention T={T}, positions {pos}", p0=d_pos)
     # one shared position (pos_stride 0) reads d_pos[0] for every row
     out0 = torch.empty_like(out)
     ops.attn_prefill_cached(q, kc, vc, out0, B, H, T, d_pos[1:2].contiguous(), pos_stride=0)
     for b in range(B):
         e = rel(out0[b * T:(b + 1) * T], ref_chunk(q[b], kc[b], vc[b], 37, T))
         assert e <= 3e-3, f"shared position, row {b}: rel-L2 {e:.3e}"
+    kcmp.assert_causal_attention(out0, q, kc, vc, f"chunk attention T={T}, shared position 37", p0=37)
+
+
+@pytest.mark.parametrize("inputs", ["self c=1", "self c=2", "tile edges"])
+@pytest.mark.parametrize("T", [1, 5, 32, 33, 130])
+@pytest.mark.parametrize("Smax,ends", [(384, None), (2048, (1024, 1991, 2048))])
+def test_chunk_attention_boundary_inputs(dev, T, inputs, Smax, ends):
+    """Keys that make the causal limit of every row count: the key a query appended itself (position p_b + t) dominates its row
+    ("self": k = bf16(c q + 0.25 noise)), or only the keys at the edges of the 32-key tiles and the chunk's last key do ("tile
+    edges": k = 4 q there).  A limit that is off by one in either direction moves those rows far outside the per-element bound.
+    Short contexts (positions 0 / 37 / 190) and long ones whose chunk ENDS at key 1024 (a full tile), 1991 (a partial one) and
+    2048 (the end of the cache)."""
+    from magma_amd import ops
+    B, H = 3, 2
+    pos = [0, 37, 190] if ends is None else [e - T for e in ends]
+    kc = rnd(B, H, Smax, 256, dev=dev, seed=21, scale=0.5).to(BF16)
+    vc = rnd(B, H, Smax, 256, dev=dev, seed=22).to(BF16)
+    q = rnd(B, H, T, 256, dev=dev, seed=23, scale=0.5).to(BF16)
+    noise = rnd(B, H, T, 256, dev=dev, seed=24, scale=0.25)
+    for b, p in enumerate(pos):
+        if inputs == "tile edges":
+            ts = [t for t in range(T) if (p + t) % 32 in (0, 31) or t == T - 1]
+            kc[b, :, [p + t for t in ts]] = (q[b, :, ts].float() * 4).to(BF16)
+        else:
+            kc[b, :, p:p + T] = (float(inputs[-1]) * q[b].float() + noise[b]).to(BF16)
+    d_pos = torch.tensor(pos, dtype=torch.int32, device=dev)
+    out = torch.full((B * T, H * 256), float("nan"), dtype=BF16, device=dev)
+    ops.attn_prefill_cached(q, kc, vc, out, B, H, T, d_pos, pos_stride=1)
+    kcmp.assert_causal_attention(out, q, kc, vc, f"chunk attention T={T}, positions {pos}, {inputs}", p0=d_pos)
+    for b, p in enumerate(pos):
+        assert rel(out[b * T:(b + 1) * T], ref_chunk(q[b], kc[b], vc[b], p, T)) <= 3e-3
 
 
 def test_chunk_attention_strided_queries_and_wide_output(dev):
@@ -68,6 +102,7 @@ def test_chunk_attention_strided_queries_and_wide_output(dev):
     ops.attn_prefill_cached(q, kc, vc, wide[:, : H * 256], B, H, T, torch.tensor(pos, dtype=torch.int32, device=dev), pos_stride=1)
     for b, p in enumerate(pos):
         assert rel(wide[b * T:(b + 1) * T, : H * 256], ref_chunk(q[b], kc[b], vc[b], p, T)) <= 3e-3
+    kcmp.assert_causal_attention(wide[:, : H * 256], q, kc, vc, "chunk attention, strided q, wide output", p0=torch.tensor(pos))
     assert torch.equal(wide[:, H * 256:], torch.zeros_like(wide[:, H * 256:]))
 
 
@@ -85,6 +120,8 @@ def test_chunk_attention_agrees_with_prefill_and_decode(dev):
     ref = torch.empty_like(out)
     ops.attn_fwd_rows(ops.AttnRows.of_bhsd(q.contiguous(), k, v), ref)
     assert rel(out, ref) <= 3e-3
+    kcmp.assert_causal_attention(out, q, k, v, "chunk attention at p = 0")
+    kcmp.assert_causal_attention(ref, q, k, v, "attn_fwd_rows on the same operands")
     # T = 1: one query per row at its own position, as attn_decode computes it
     pos = [5, 200]
     d_pos = torch.tensor(pos, dtype=torch.int32, device=dev)
@@ -95,6 +132,8 @@ def test_chunk_attention_agrees_with_prefill_and_decode(dev):
     ops.attn_decode(q1, kc, vc, r1, B, H, d_pos, pos_stride=1)
     for b in range(B):
         assert rel(o1[b], r1[b]) <= 3e-3, f"row {b}"
+    kcmp.assert_causal_attention(o1, q1, kc, vc, "chunk attention, T = 1", p0=d_pos)
+    kcmp.assert_causal_attention(r1, q1, kc, vc, "attn_decode on the same operands", p0=d_pos, p_dtype=torch.float32, n_rescale=0)
 
 
 def test_chunk_attention_argument_checks(dev):

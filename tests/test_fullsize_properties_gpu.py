@@ -12,6 +12,8 @@ run d = 4096 / S = 2048 in seconds, so at these sizes parity is argued from inva
 import pytest
 import torch
 
+import kernel_compare as kcmp
+
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
 
@@ -104,6 +106,15 @@ def test_flash_attention_properties_s2048(dev):
     sc = sc.masked_fill(~torch.ones(S, S, dtype=torch.bool, device=dev).tril(), float("-inf"))
     ref = (torch.softmax(sc, -1) @ v.float()).permute(0, 2, 1, 3).reshape(B * S, d)
     assert rel(out, ref) < 1e-2, rel(out, ref)
+    kcmp.assert_causal_attention(out, q, k, v, "flash attention S=2048, i.i.d.", lse=lse)
+    # with i.i.d. inputs a last row without its own key is invisible (a row of 2048 keys averages): each query's own key dominates
+    for c in (1.0, 2.0):
+        qs, ks, vs = kcmp.self_dominant_qkv((B, H, S, 256), c, seed=19, device=dev)
+        outs, lses = fwd(qs, ks, vs)
+        kcmp.assert_causal_attention(outs, qs, ks, vs, f"flash attention S=2048, self-dominant c={c}", lse=lses)
+    ke = kcmp.dominant_edge_keys(q, k)
+    oute, lsee = fwd(q, ke, v)
+    kcmp.assert_causal_attention(oute, q, ke, v, "flash attention S=2048, dominant tile-edge keys", lse=lsee)
     # backward: scaling identity per head, and dv against autograd
     dO = torch.randn(B * S, d, device=dev, generator=g).to(BF16)
     qt = ops.head_transpose(q, B, H, S, sb=hs, ss=256, sh=S * 256)
@@ -119,6 +130,7 @@ def test_flash_attention_properties_s2048(dev):
     sc = sc.masked_fill(~torch.ones(S, S, dtype=torch.bool, device=dev).tril(), float("-inf"))
     (torch.softmax(sc, -1) @ vf).permute(0, 2, 1, 3).reshape(B * S, d).backward(dO.float())
     assert rel(dq, qf.grad) < 1.5e-2 and rel(dk, kf.grad) < 1.5e-2 and rel(dv, vf.grad) < 1.5e-2
+    kcmp.assert_attention_backward(dq, dk, dv, q, k, v, dO, out, lse, "attn_bwd S=2048")
 
 
 @pytest.mark.parametrize("M,N,K,why", [(4096, 4096, 16384, "fc_out slice, 256x256 kernel"),
@@ -136,5 +148,6 @@ def test_tile_gemm_training_shapes(dev, M, N, K, why):
     ref = a.float() @ w.float().t() + bias + res.float()
     out = ops.gemm(a, lin, residuals=(res,))
     assert rel(out, ref) < 4e-3, (why, rel(out, ref))
+    kcmp.assert_linear(out, f"tile GEMM {M}x{N}x{K} ({why})", a, w, bias=bias, residuals=(res,))
     again = ops.gemm(a, lin, residuals=(res,))
     assert torch.equal(out, again), f"{why}: not deterministic"

@@ -1,0 +1,314 @@
+"""tests/kernel_compare.py checked on the CPU: no kernel is called, modified or made to misbehave here.
+
+For a GEMM, a causal attention and a LayerNorm an HONEST STAND-IN plays the kernel: the same operation in fp32 with a permuted
+summation order, rounded once to the output type (and P rounded to bf16 before PV, as the prefill kernels do).  Faults of the
+kinds hand-written kernels have are then written into that result tensor on the host.  Conditions on the helper:
+
+  1. every honest stand-in passes, worst |err| / bound < 1;
+  2. every seeded fault fails, and its worst ratio is at least 8 x the bound;
+  3. the faults of the table in DESIGN.md ("Test comparators") are ACCEPTED by the whole-tensor criterion
+     ||got - ref|| / ||ref|| at the threshold the GPU suite uses for that case.  That is the gap the per-element bound closes;
+     the assertion stops anyone from simplifying the helper back to a norm.
+
+Seeds, scales and shapes are those of the GPU tests the cases mirror."""
+import math
+
+import pytest
+import torch
+
+import kernel_compare as kc
+
+BF16 = torch.bfloat16
+FAULT_FACTOR = 8.0
+
+
+def rnd(*shape, scale=1.0, seed=0):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    return torch.randn(*shape, generator=g) * scale
+
+
+def old_rel(got, ref):
+    """The criterion of the suite before the per-element bound (assert_close / rel_err of tests/test_kernels_gpu.py)."""
+    a, b = got.float(), ref.float()
+    return float((a - b).norm() / (b.norm() + 1e-12))
+
+
+def check_fault(name, bad, ref, bound, old_tol=None):
+    """Condition 2 (and 3 where old_tol is given) for one faulty tensor; returns the figures for the printed table."""
+    w = kc.worst_ratio(bad, ref, bound)
+    with pytest.raises(AssertionError, match="bounding box"):
+        kc.assert_elementwise(bad, ref, bound, name)
+    assert w >= FAULT_FACTOR, f"{name}: worst ratio {w:.2f} < {FAULT_FACTOR}"
+    old = old_rel(bad, ref)
+    print(f"    fault {name:<46s} err/bound {w:9.1f}   rel-L2 {old:.2e}" + (f" < {old_tol} (accepted before)" if old_tol else ""))
+    if old_tol is not None:
+        assert old < old_tol, f"{name}: the whole-tensor criterion was expected to accept this fault ({old:.3e} >= {old_tol})"
+    return w, old
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# GEMM
+# ---------------------------------------------------------------------------------------------------------------------------
+def gemm_stand_in(a, w, bias, seed):
+    """fp32 accumulation over K in a permuted order (64-wide chunks of a random permutation), bias, one rounding to bf16."""
+    K = a.shape[1]
+    perm = torch.randperm(K, generator=torch.Generator().manual_seed(seed))
+    acc = torch.zeros(a.shape[0], w.shape[0], dtype=torch.float32)
+    af, wf = a.float(), w.float()
+    for c in perm.split(64):
+        acc += af[:, c] @ wf[:, c].t()
+    if bias is not None:
+        acc += bias
+    return acc.to(BF16)
+
+
+# (M, N, K, threshold of the mirrored test, faults the old criterion is asserted to accept)
+GEMM_CASES = [
+    (1216, 512, 4096, 4e-3, {"one element zeroed", "8-wide store dropped at the last tile corner", "8 tail elements x1.5"}),
+    (300, 200, 192, 4e-3, {"one element zeroed"}),
+    (2048, 4096, 4096, 4e-3, {"8-wide store dropped at the last tile corner"}),
+]
+
+
+@pytest.mark.parametrize("M,N,K,tol,accepted", GEMM_CASES, ids=lambda v: str(v) if isinstance(v, int) else None)
+def test_gemm_stand_in_and_faults(M, N, K, tol, accepted):
+    a = rnd(M, K, seed=1).to(BF16)
+    w = rnd(N, K, seed=2, scale=0.05).to(BF16)
+    bias = rnd(N, seed=5)
+    prod, pmag = kc.product_terms(a, w)
+    ref = prod + bias.double()
+    bound = kc.gemm_bound(ref, pmag + bias.double().abs(), K, BF16, n_epilogue=1)
+    good = gemm_stand_in(a, w, bias, seed=9)
+    worst = kc.assert_elementwise(good, ref, bound, f"honest GEMM {M}x{N}x{K}")
+    assert worst < 1.0
+    assert old_rel(good, ref) < tol
+    print(f"  GEMM {M}x{N}x{K}: honest err/bound {worst:.2f}, rel-L2 {old_rel(good, ref):.2e}")
+
+    def tol_of(name):
+        return tol if name in accepted else None
+    # one element: the one of median magnitude in the last row (a typical element, not a large one)
+    j = int(ref[M - 1].abs().argsort()[N // 2])
+    bad = good.clone(); bad[M - 1, j] = 0
+    check_fault("one element zeroed", bad, ref, bound, tol_of("one element zeroed"))
+    bad = good.clone(); bad[M - 1, N - 8:] = 0
+    check_fault("8-wide store dropped at the last tile corner", bad, ref, bound, tol_of("8-wide store dropped at the last tile corner"))
+    bad = good.clone(); bad[M - 1, N - 8:] = (bad[M - 1, N - 8:].float() * 1.5).to(BF16)
+    check_fault("8 tail elements x1.5", bad, ref, bound, tol_of("8 tail elements x1.5"))
+    bad = good.clone(); bad[M - 1] = bad[M - 2]
+    check_fault("last row equal to the row above", bad, ref, bound)
+    bad = good.clone(); bad[M - 16:, N - 16:] = bad[M - 16:, N - 16:].t().clone()
+    check_fault("last 16x16 sub-tile transposed", bad, ref, bound)
+    # the tail element that misses its bias: the last column whose bias is not small (|bias| > 0.5; N(0,1) entries)
+    jb = int((bias.abs() > 0.5).nonzero().max())
+    bad = good.clone(); bad[M - 1, jb] = (bad[M - 1, jb].float() - bias[jb]).to(BF16)
+    check_fault("tail element without its bias", bad, ref, bound)
+
+
+def test_gemm_bound_is_tight_not_generous():
+    """At K = 192 the honest stand-in comes close to the bound (the output rounding alone reaches u |x| just above a power of
+    two): the bound has no slack to hide a fault in.  0.9: some of 60 000 elements lies within 10 % of such a tie."""
+    M, N, K = 300, 200, 192
+    a = rnd(M, K, seed=1).to(BF16)
+    w = rnd(N, K, seed=2, scale=0.05).to(BF16)
+    ref, mag = kc.product_terms(a, w)
+    bound = kc.gemm_bound(ref, mag, K, BF16)
+    worst = kc.worst_ratio(gemm_stand_in(a, w, None, seed=3), ref, bound)
+    assert 0.9 < worst < 1.0, worst
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# causal attention
+# ---------------------------------------------------------------------------------------------------------------------------
+def attention_stand_in(q, k, v, seed, drop_diagonal_of_last_row=False):
+    """fp32 scores, exp(t - m) in fp32, row sum of the UNROUNDED weights, weights rounded to bf16 before PV, PV accumulated in
+    fp32 over 32-key tiles taken in a permuted order, one rounding of the output to bf16: what the prefill kernels do."""
+    S = q.shape[-2]
+    t = (q.float() @ k.float().transpose(-1, -2)) * 0.0625
+    mask = torch.ones(S, S, dtype=torch.bool).tril()
+    if drop_diagonal_of_last_row:
+        mask = mask.clone(); mask[S - 1, S - 1] = False
+    t = t.masked_fill(~mask, float("-inf"))
+    p = torch.exp(t - t.max(-1, keepdim=True).values)
+    l = p.sum(-1, keepdim=True)
+    pb = p.to(BF16).float()
+    vf = v.float()
+    tiles = list(range(0, S, 32))
+    order = torch.randperm(len(tiles), generator=torch.Generator().manual_seed(seed)).tolist()
+    acc = torch.zeros_like(q, dtype=torch.float32)
+    for i in order:
+        s0 = tiles[i]
+        acc += pb[..., s0:s0 + 32] @ vf[..., s0:s0 + 32, :]
+    return (acc / l).to(BF16)
+
+
+def causal_terms(q, k, v):
+    S = q.shape[-2]
+    return kc.attention_terms(q, k, v, torch.ones(S, S, dtype=torch.bool).tril())
+
+
+def iid_qkv(S, seed0=81):
+    return (rnd(1, 1, S, 256, seed=seed0, scale=0.5).to(BF16), rnd(1, 1, S, 256, seed=seed0 + 1, scale=0.5).to(BF16),
+            rnd(1, 1, S, 256, seed=seed0 + 2).to(BF16))
+
+
+def test_attention_iid_inputs():
+    """i.i.d. Gaussian q / k / v (what the GPU tests used alone): the whole-tensor criterion accepts a wrong last row, the
+    per-element bound does not -- and NEITHER sees a last row without its diagonal key at S = 2048, because a long softmax row
+    averages ~S values.  That is why the structured inputs below exist."""
+    # S = 1024, test_attention_forward_kernel_variants (threshold 8e-3)
+    q, k, v = iid_qkv(1024)
+    T = causal_terms(q, k, v)
+    ref, bound = T["ref"], kc.attention_bound(T, 1024)
+    good = attention_stand_in(q, k, v, seed=4)
+    worst = kc.assert_elementwise(good, ref, bound, "honest attention, i.i.d., S=1024")
+    assert worst < 1.0 and old_rel(good, ref) < 8e-3
+    bad = good.clone(); bad[0, 0, -1] = bad[0, 0, -2]
+    check_fault("S=1024 last query row = the row above it", bad, ref, bound, 8e-3)
+    bad = good.clone(); bad[0, 0, -1, -8:] = 0
+    check_fault("S=1024 8-wide store dropped in the last row", bad, ref, bound, 8e-3)
+    # S = 2048, test_flash_attention_properties_s2048 (threshold 1e-2)
+    q, k, v = iid_qkv(2048)
+    T = causal_terms(q, k, v)
+    ref, bound = T["ref"], kc.attention_bound(T, 2048)
+    good = attention_stand_in(q, k, v, seed=5)
+    assert kc.assert_elementwise(good, ref, bound, "honest attention, i.i.d., S=2048") < 1.0
+    bad = good.clone(); bad[0, 0, -1] = bad[0, 0, -2]
+    w = kc.worst_ratio(bad, ref, bound)
+    assert w > 1.0 and old_rel(bad, ref) < 1e-2, (w, old_rel(bad, ref))
+    print(f"    fault S=2048 i.i.d. last row = the row above: err/bound {w:.1f}, rel-L2 {old_rel(bad, ref):.2e} < 1e-2 (accepted before)")
+    nodiag = attention_stand_in(q, k, v, seed=5, drop_diagonal_of_last_row=True)
+    w = kc.worst_ratio(nodiag, ref, bound)
+    print(f"    fault S=2048 i.i.d. last row without its diagonal key: err/bound {w:.2f}, rel-L2 {old_rel(nodiag, ref):.2e}: "
+          f"invisible to any comparator with these inputs")
+    assert old_rel(nodiag, ref) < 1e-2
+
+
+@pytest.mark.parametrize("c", [1.0, 2.0, "tile edges"])
+@pytest.mark.parametrize("S", [57, 300, 1024, 2048])
+def test_attention_self_dominant_inputs(S, c):
+    """k_i = bf16(c q_i + 0.25 noise): each query's own key dominates its row; or ("tile edges", kernel_compare.dominant_edge_keys)
+    i.i.d. keys whose tile-edge positions and last key -- the end of a partial tile at S = 57 / 300 -- are 4 q.  The honest
+    stand-in stays inside the bound and both causal-boundary faults of the last row are far outside it, at full (1024, 2048)
+    and partial (57, 300) last tiles."""
+    if c == "tile edges":
+        q, k, v = iid_qkv(S, seed0=94)
+        k = kc.dominant_edge_keys(q, k)
+    else:
+        q, k, v = kc.self_dominant_qkv((1, 1, S, 256), c, seed=91)
+    T = causal_terms(q, k, v)
+    ref, bound = T["ref"], kc.attention_bound(T, S)
+    good = attention_stand_in(q, k, v, seed=6)
+    worst = kc.assert_elementwise(good, ref, bound, f"honest attention, self-dominant c={c}, S={S}")
+    assert worst < 1.0
+    nodiag = attention_stand_in(q, k, v, seed=6, drop_diagonal_of_last_row=True)
+    # at S = 2048, c = 1 the whole-tensor criterion of test_flash_attention_properties_s2048 still accepts the missing diagonal
+    check_fault(f"S={S} c={c} last row without its diagonal key", nodiag, ref, bound, 1e-2 if (S == 2048 and c == 1.0) else None)
+    bad = good.clone(); bad[0, 0, -1] = bad[0, 0, -2]
+    check_fault(f"S={S} c={c} last query row = the row above it", bad, ref, bound)
+    bad = good.clone(); bad[0, 0, -1, -8:] = 0
+    check_fault(f"S={S} c={c} 8-wide store dropped in the last row", bad, ref, bound)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# causal attention, backward
+# ---------------------------------------------------------------------------------------------------------------------------
+def attention_backward_stand_in(q, k, v, dO_rows, out_rows, lse):
+    """What the backward kernels do, in fp32: P from the saved lse, rounded to bf16 for dV and dS; D from the saved bf16 O;
+    dS rounded to bf16 before dQ / dK; one rounding of each output to bf16."""
+    B, H, S, D = q.shape
+    dO = dO_rows.float().reshape(B, S, H, D).permute(0, 2, 1, 3)
+    O = out_rows.float().reshape(B, S, H, D).permute(0, 2, 1, 3)
+    t = (q.float() @ k.float().transpose(-1, -2)) * 0.0625
+    t = t.masked_fill(~torch.ones(S, S, dtype=torch.bool).tril(), float("-inf"))
+    pb = torch.exp(t - lse[..., None]).to(BF16).float()
+    dV = pb.transpose(-1, -2) @ dO
+    dS = (pb * (dO @ v.float().transpose(-1, -2) - (dO * O).sum(-1, keepdim=True))).to(BF16).float()
+    return {"dq": (dS @ k.float() * 0.0625).to(BF16), "dk": (dS.transpose(-1, -2) @ q.float() * 0.0625).to(BF16), "dv": dV.to(BF16)}
+
+
+@pytest.mark.parametrize("inputs", ["i.i.d.", "self c=1"])
+@pytest.mark.parametrize("S", [300, 1024])
+def test_attention_backward_stand_in_and_faults(S, inputs):
+    """dQ / dK / dV against kernel_compare.attention_backward_reference, which takes O and lse as the backward kernel reads them
+    (the forward stand-in's bf16 O, an fp32 lse): the honest stand-in is below 1, and a dropped 8-wide store or a row copied from
+    the row above -- in the last row and in a middle row of each gradient -- is at least 8 x the bound.  (With D taken from the
+    exact softmax instead, sum_d |dO| bound(O) enters every element of dQ / dK and the same drops reach 0.9 .. 3.8 only.)
+    The tile-edge inputs are left out here: a row whose softmax is one-hot has dQ = 0 exactly, so a dropped store is no fault."""
+    if inputs == "i.i.d.":
+        q, k, v = iid_qkv(S, seed0=20)
+    else:
+        q, k, v = kc.self_dominant_qkv((1, 1, S, 256), 1.0, seed=27)
+    dO = rnd(S, 256, seed=23).to(BF16)
+    out = kc.rows_of(attention_stand_in(q, k, v, seed=4))
+    lse = causal_terms(q, k, v)["lse"].float()
+    R = kc.attention_backward_reference(q, k, v, dO, out, lse)
+    good = attention_backward_stand_in(q, k, v, dO, out, lse)
+    for name in ("dq", "dk", "dv"):
+        ref, bound = R[name]
+        assert kc.assert_elementwise(good[name], ref, bound, f"honest attention backward {name}, {inputs}, S={S}") < 1.0
+        for row in (S - 1, S // 2):
+            bad = good[name].clone(); bad[0, 0, row, -8:] = 0
+            check_fault(f"S={S} {inputs} {name}: 8-wide store dropped in row {row}", bad, ref, bound)
+            bad = good[name].clone(); bad[0, 0, row] = bad[0, 0, row - 1]
+            check_fault(f"S={S} {inputs} {name}: row {row} = the row above it", bad, ref, bound)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# LayerNorm
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("rows,d", [(37, 512), (8, 4096)])
+def test_layernorm_stand_in_and_faults(rows, d):
+    x = (rnd(rows, d, seed=41) * 2 + 0.3).to(BF16)
+    g = rnd(d, seed=42) * 0.1 + 1
+    b = rnd(d, seed=43) * 0.1
+    T = kc.layernorm_terms(x, g, b, 1e-5)
+    ref, bound = T["ref"], kc.layernorm_bound(T, d)
+    perm = torch.randperm(d, generator=torch.Generator().manual_seed(7))
+    xf = x.float()
+    mean = xf[:, perm].sum(-1, keepdim=True) / d
+    var = ((xf - mean)[:, perm] ** 2).sum(-1, keepdim=True) / d
+    good = ((xf - mean) * torch.rsqrt(var + 1e-5) * g + b).to(BF16)
+    worst = kc.assert_elementwise(good, ref, bound, f"honest LayerNorm {rows}x{d}")
+    assert worst < 1.0
+    j = int(ref[rows - 1].abs().argsort()[d // 2])
+    bad = good.clone(); bad[rows - 1, j] = 0
+    check_fault("one element zeroed", bad, ref, bound)
+    bad = good.clone(); bad[rows - 1, d - 8:] = 0
+    check_fault("8-wide store dropped at the end of the last row", bad, ref, bound)
+    bad = good.clone(); bad[rows - 1] = bad[rows - 2]
+    check_fault("last row equal to the row above", bad, ref, bound)
+    jb = int((b.abs() > 0.05).nonzero().max())
+    bad = good.clone(); bad[rows - 1, jb] = (bad[rows - 1, jb].float() - b[jb]).to(BF16)
+    check_fault("tail element without its beta", bad, ref, bound)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the comparator itself
+# ---------------------------------------------------------------------------------------------------------------------------
+def test_failure_message_locates_the_fault():
+    ref = torch.arange(64 * 48, dtype=torch.float64).reshape(64, 48) / 7 + 1
+    bound = kc.rounded(ref, torch.zeros_like(ref), BF16)
+    got = ref.to(BF16)
+    assert kc.assert_elementwise(got, ref, bound, "exact rounding") <= 1.0      # half an ulp just above a power of two = u |x|
+    bad = got.clone(); bad[48:64, 40:48] = 0
+    with pytest.raises(AssertionError) as e:
+        kc.assert_elementwise(bad, ref, bound, "corner")
+    m = str(e.value)
+    assert "[48..63] x [40..47]" in m and "128 of 3072 elements over" in m and "worst |err|/bound" in m and "at index (" in m
+    nan = got.clone(); nan[3, 5] = float("nan")
+    with pytest.raises(AssertionError, match=r"\[3\.\.3\] x \[5\.\.5\].*1 not finite"):
+        kc.assert_elementwise(nan, ref, bound, "nan")
+    with pytest.raises(AssertionError):
+        kc.assert_elementwise(got, ref.float(), bound, "fp32 reference refused")
+
+
+def test_constants():
+    assert kc.U_BF16 == 2.0 ** -8 and kc.U_F32 == 2.0 ** -24
+    # bf16 rounds to nearest even: 1 + 2^-8 is a tie and goes to 1, the half-ulp error equals u |x| / (1 + u)
+    assert float(torch.tensor(1 + 2.0 ** -8).to(BF16)) == 1.0
+    assert float(torch.tensor(1 + 3 * 2.0 ** -8).to(BF16)) == 1 + 2.0 ** -6
+    assert math.isclose(kc.gamma(4096), 4096 * 2.0 ** -24 / (1 - 4096 * 2.0 ** -24))
+    x = torch.linspace(-6, 6, 24001, dtype=torch.float64, requires_grad=True)
+    y = 0.5 * x * (1 + torch.tanh(math.sqrt(2 / math.pi) * (x + 0.044715 * x ** 3)))
+    (gr,) = torch.autograd.grad(y.sum(), x)
+    assert 1.12 < float(gr.abs().max()) <= kc.GELU_LIPSCHITZ

@@ -1,11 +1,16 @@
 """Kernel-level parity: every C-ABI entry point against a plain PyTorch fp32
 reference of the same op, on seeded random (never zero-filled, never symmetric)
-inputs.  Tolerances are stated per test.  All calls go through libmagma_hip.so."""
+inputs.  Tolerances are stated per test.  All calls go through libmagma_hip.so.
+
+Next to every whole-tensor number (assert_close: one rel-L2 per tensor, which averages a wrong tile corner away) stands a
+per-element check against an fp64 reference with a derived bound (tests/kernel_compare.py; DESIGN.md "Test comparators")."""
 import math
 
 import pytest
 import torch
 import torch.nn.functional as F
+
+import kernel_compare as kcmp
 
 pytestmark = pytest.mark.gpu
 
@@ -42,6 +47,7 @@ def test_gemm_dense(dev, layout, M, N, K):
     out = ops.gemm(a, lin, layout=layout)
     ref = a.float() @ w.float().t()
     assert_close(out, ref, GEMM_TOL, f"gemm {layout} {M}x{N}x{K}")
+    kcmp.assert_linear(out, f"gemm {layout} {M}x{N}x{K}", a, w)
 
 
 def test_gemm_transpose_detecting(dev):
@@ -71,22 +77,27 @@ def test_gemm_epilogue(dev):
     x = acc + bias
     ref = 0.5 * x * (1 + torch.tanh(math.sqrt(2 / math.pi) * (x + 0.044715 * x ** 3)))
     assert_close(out, ref, GEMM_TOL, "bias+gelu")
+    kcmp.assert_linear(out, "gemm bias+gelu", a, w, bias=bias, act="gelu")
     # scale + bias + relu  (folded BatchNorm)
     out = ops.gemm(a, lin, act=ops.MG_ACT_RELU, scale=scale)
     assert_close(out, F.relu(acc * scale + bias), GEMM_TOL, "scale+bias+relu")
+    kcmp.assert_linear(out, "gemm scale+bias+relu", a, w, scale=scale, bias=bias, act="relu")
     # bias + 3 residuals (GPT-J block sum), fp32 out
     out = ops.gemm(a, lin, residuals=(r0, r1, r2), out_dtype=torch.float32)
     assert out.dtype == torch.float32
     assert_close(out, acc + bias + r0.float() + r1.float() + r2.float(), 1e-4, "bias+3res f32")
+    kcmp.assert_linear(out, "gemm bias+3res f32", a, w, bias=bias, residuals=(r0, r1, r2))
     # scale+bias, residual, relu after (bottleneck tail)
     out = ops.gemm(a, lin, scale=scale, residuals=(r0,), act_after=ops.MG_ACT_RELU)
     assert_close(out, F.relu(acc * scale + bias + r0.float()), GEMM_TOL, "bn+identity+relu")
+    kcmp.assert_linear(out, "gemm bn+identity+relu", a, w, scale=scale, bias=bias, residuals=(r0,), act="relu")
     # N not a multiple of 4 (vocab 50258 style), fp32 logits into a padded buffer
     N2 = 203
     lin2 = ops.PackedLinear(w[:N2], bias=bias[:N2])
     buf = torch.full((M, 208), 7.0, dtype=torch.float32, device=dev)
     ops.gemm(a, lin2, out=buf)
     assert_close(buf[:, :N2], acc[:, :N2] + bias[:N2], 1e-4, "odd N")
+    kcmp.assert_linear(buf[:, :N2], "gemm odd N f32", a, w[:N2], bias=bias[:N2])
     assert bool((buf[:, N2:] == 7.0).all()), "wrote past N"
     # row stride that is a multiple of 4 but not of 8: the epilogue must fall back from 16-byte to 8-byte accesses
     for Mx, tile in ((M, 128), (1100, 256)):
@@ -95,6 +106,7 @@ def test_gemm_epilogue(dev):
         bufx = torch.zeros(Mx, 332, dtype=BF16, device=dev)
         ops.gemm(ax, lin, out=bufx[:, :N], residuals=(rx,), tile=tile)
         assert_close(bufx[:, :N], ax.float() @ w.float().t() + bias + rx[:, :N].float(), GEMM_TOL, f"ldc%8!=0 tile{tile}")
+        kcmp.assert_linear(bufx[:, :N], f"gemm ldc%8!=0 tile{tile}", ax, w, bias=bias, residuals=(rx[:, :N],))
         assert bool((bufx[:, N:] == 0).all())
 
 
@@ -109,6 +121,7 @@ def test_conv3x3(dev, layout, B, H, W, Cin, Cout):
     out = ops.gemm(x_nhwc.view(B * H * W, Cin), lin, conv=(H, W, Cin), layout=layout)
     ref = F.conv2d(x.float(), w.float(), padding=1).permute(0, 2, 3, 1).reshape(B * H * W, Cout)
     assert_close(out, ref, GEMM_TOL, f"conv3x3 {layout}")
+    kcmp.assert_linear(out, f"conv3x3 {layout} {B}x{H}x{W} {Cin}->{Cout}", prod=kcmp.conv2d_terms(x, w))
 
 
 @pytest.mark.parametrize("M", [1, 8, 16])
@@ -128,8 +141,10 @@ def test_gemm_skinny(dev, M, N, K, variant):
     out = ops.gemm_skinny(x, lin, residuals=(res,), variant=variant)
     ref = x.float() @ w.float().t() + bias + res.float()
     assert_close(out, ref, GEMM_TOL, f"skinny M={M} {N}x{K} v={variant}")
+    kcmp.assert_linear(out, f"skinny M={M} {N}x{K} v={variant}", x, w, bias=bias, residuals=(res,))
     out32 = ops.gemm_skinny(x, lin, act=ops.MG_ACT_RELU, out_dtype=torch.float32, variant=variant)
     assert_close(out32, F.relu(x.float() @ w.float().t() + bias), 1e-4, "skinny relu f32")
+    kcmp.assert_linear(out32, f"skinny relu f32 M={M} {N}x{K} v={variant}", x, w, bias=bias, act="relu")
 
 
 @pytest.mark.parametrize("N,K,base", [(4096, 16384, 1 | 4 << 4 | 16 << 8), (4096, 8192, 1 | 4 << 4 | 16 << 8), (4096, 4096, 1 | 8 << 4 | 8 << 8),
@@ -146,11 +161,13 @@ def test_gemm_skinny_pipelined_bursts_are_bit_identical(dev, N, K, base):
     b = ops.gemm_skinny(x, lin, out_dtype=torch.float32, variant=base | 1 << 16)
     assert torch.equal(a, b)
     assert_close(a, x.float() @ w.float().t() + lin.bias, 1e-4 * (K / 1024) ** 0.5 + 1e-4, "skinny f32")
+    kcmp.assert_linear(a, f"skinny f32 {N}x{K} v={base}", x, w, bias=lin.bias)
     colsum = w.float().sum(1).contiguous()
     fold = (colsum, K, 1e-5)
     a = ops.gemm_skinny(x, lin, out_dtype=torch.float32, variant=base, ln_fold=fold)
     b = ops.gemm_skinny(x, lin, out_dtype=torch.float32, variant=base | 1 << 16, ln_fold=fold)
     assert torch.equal(a, b)
+    kcmp.assert_elementwise(a, *kcmp.ln_fold_reference(x, w, lin.bias, colsum, 1e-5, out_dtype=torch.float32), f"skinny ln-fold f32 {N}x{K}")
 
 
 def test_tile_roundtrip(dev):
@@ -168,6 +185,8 @@ def test_layernorm(dev, rows, d):
     out = ops.layernorm(x, g, b, 1e-5)
     ref = F.layer_norm(x.float(), (d,), g, b, 1e-5)
     assert_close(out, ref, 3e-3, "layernorm")
+    T = kcmp.layernorm_terms(x, g, b, 1e-5)
+    kcmp.assert_elementwise(out, T["ref"], kcmp.layernorm_bound(T, d), f"layernorm {rows}x{d}")
 
 
 @pytest.mark.parametrize("rows,d", [(8195, 4096), (8192, 2048), (9001, 264), (8194, 2056)])
@@ -184,6 +203,8 @@ def test_layernorm_rows_per_workgroup_form(dev, rows, d):
     out = ops.layernorm(x, g, b, 1e-5)
     ref = F.layer_norm(x.float(), (d,), g, b, 1e-5)
     assert_close(out, ref, 3e-3, "layernorm, rows per workgroup")
+    T = kcmp.layernorm_terms(x, g, b, 1e-5)
+    kcmp.assert_elementwise(out, T["ref"], kcmp.layernorm_bound(T, d), f"layernorm, rows per workgroup {rows}x{d}")
     pieces = torch.cat([ops.layernorm(x[i:i + 4096], g, b, 1e-5) for i in range(0, rows, 4096)])
     assert torch.equal(out, pieces)
 
@@ -227,6 +248,10 @@ def test_rotary_split_and_prefill_attention(dev, B, S, H):
     v_ref = x[:, :, 2].permute(0, 2, 1, 3)
     assert_close(q.cpu(), q_ref, 3e-3, "q rotary")
     assert_close(kc[:, :, :S].cpu(), k_ref, 3e-3, "k rotary")
+    xd = qkv.view(B, S, 3, H, 256).permute(2, 0, 3, 1, 4)                       # [3, B, H, S, 256] on the device
+    for got, src, name in ((q, xd[0], "q"), (kc[:, :, :S], xd[1], "k")):
+        rref, rbound = kcmp.rotary_reference(src, sin_t[:S], cos_t[:S], 64)
+        kcmp.assert_elementwise(got, rref, rbound, f"rotary_split {name} B={B} S={S} H={H}")
     assert torch.equal(vc[:, :, :S].float().cpu(), v_ref)
     vt_flat = vt.permute(0, 1, 3, 2, 4).reshape(B, H, 256, vt_ld)       # [b,h,tile,d,i] -> [b,h,d,32*tile+i]
     assert torch.equal(vt_flat[:, :, :, :S].float().cpu(), v_ref.transpose(2, 3))
@@ -242,6 +267,7 @@ def test_rotary_split_and_prefill_attention(dev, B, S, H):
     ref = (torch.softmax(sc, -1) @ vf).permute(0, 2, 1, 3).reshape(B * S, d)
     assert_close(out, ref, 8e-3, "flash attention")   # P is rounded to bf16 like the reference's cast
     assert_close(lse, torch.logsumexp(sc, -1), 1e-4, "lse")
+    kcmp.assert_causal_attention(out, q, kc[:, :, :S], vc[:, :, :S], f"prefill attention B={B} H={H} S={S}", lse=lse)
 
 
 @pytest.mark.parametrize("variant", [4, 5])
@@ -267,6 +293,7 @@ def test_attention_forward_kernel_variants(dev, monkeypatch, variant, B, H, S):
     ref = (torch.softmax(sc, -1) @ v.float()).permute(0, 2, 1, 3).reshape(B * S, d)
     assert_close(out, ref, 8e-3, "flash attention")
     assert_close(lse, torch.logsumexp(sc, -1), 1e-4, "lse")
+    kcmp.assert_causal_attention(out, q, k, v, f"prefill attention variant {variant} B={B} H={H} S={S}", lse=lse)
     wide = torch.full((B * S, d + 136), float("nan"), dtype=BF16, device=dev)
     ops.attn_prefill(q, k, vt, wide[:, :d], B, H, S, lse=lse)
     assert torch.equal(wide[:, :d], out)
@@ -287,6 +314,105 @@ def test_attention_online_softmax_rescale(dev):
     sc = sc.masked_fill(~torch.ones(S, S, dtype=torch.bool, device=dev).tril(), float("-inf"))
     ref = (torch.softmax(sc, -1) @ v.float()).reshape(S, 256)
     assert_close(out, ref, 8e-3, "rescale branch")
+    kcmp.assert_causal_attention(out, q, k, v, "prefill attention, rescale branch")
+
+
+@pytest.mark.parametrize("variant", [4, 5])
+@pytest.mark.parametrize("inputs", ["self c=1", "self c=2", "tile edges"])
+@pytest.mark.parametrize("S", [57, 300, 385, 1024, 2048])
+def test_attention_forward_boundary_inputs(dev, monkeypatch, variant, inputs, S):
+    """Inputs that make the causal boundary count (kernel_compare.self_dominant_qkv / dominant_edge_keys): with i.i.d. q / k / v a long
+    softmax row averages ~S values and a last row that leaves out its own key, or reads the row above, is invisible to any
+    comparator.  Here each query's own key dominates its row (c = 1: t_ii ~ 4 against a spread of ~1; c = 2: ~8), or the keys at
+    the edges of the 32-key tiles and the very last key (the end of a partial tile at S = 57 / 300 / 385) dominate theirs."""
+    from magma_amd import ops
+    monkeypatch.setenv("MAGMA_ATTN_FWD", str(variant))
+    B, H = 1, 2
+    if inputs == "tile edges":
+        q = rnd(B, H, S, 256, dev=dev, seed=84, scale=0.5).to(BF16)
+        k = kcmp.dominant_edge_keys(q, rnd(B, H, S, 256, dev=dev, seed=85, scale=0.5).to(BF16))
+        v = rnd(B, H, S, 256, dev=dev, seed=86).to(BF16)
+    else:
+        q, k, v = kcmp.self_dominant_qkv((B, H, S, 256), float(inputs[-1]), seed=87, device=dev)
+    vt = ops.head_transpose(v, B, H, S, sb=H * S * 256, ss=256, sh=S * 256)
+    out = torch.empty(B * S, H * 256, dtype=BF16, device=dev)
+    lse = torch.empty(B, H, S, dtype=torch.float32, device=dev)
+    ops.attn_prefill(q, k, vt, out, B, H, S, lse=lse)
+    kcmp.assert_causal_attention(out, q, k, v, f"prefill attention variant {variant}, {inputs}, S={S}", lse=lse)
+    assert_close(out, kcmp.rows_of(kcmp.attention_terms(q, k, v, kcmp.causal_mask(S, S, 0, dev))["ref"]), 8e-3, "flash attention")
+
+
+def assert_decode_attention(q, kcache, vcache, ctx_rows, what, out):
+    """out [B, H*256] of single-query attention over the first ctx_rows[b] keys of row b, per element (P stays fp32 in the decode
+    kernels: no bf16 term for it)."""
+    B, H = q.shape[0], q.shape[1]
+    worst = 0.0
+    for b in range(B):
+        c = int(ctx_rows[b])
+        T = kcmp.attention_terms(q[b], kcache[b, :, :c], vcache[b, :, :c])
+        bound = kcmp.attention_bound(T, c, out.dtype, p_dtype=torch.float32, n_rescale=0)      # one maximum, taken before the exponentials
+        worst = max(worst, kcmp.assert_elementwise(out[b].view(H, 1, 256), T["ref"], bound, f"{what}, row {b} (ctx {c})"))
+    return worst
+
+
+@pytest.mark.parametrize("dominant", ["none", "newest", "first"])
+@pytest.mark.parametrize("ctx", [1, 16, 17, 63, 64, 65, 255, 256, 257, 2047, 2048, 4096])
+def test_decode_attention_strides_and_dominant_keys(dev, ctx, dominant):
+    """attn_decode, attn_decode_fused and decode_attn_gemv at contexts that cross the kernel's own strides (16 keys per wave step,
+    64 per pass, 256 in the statistics loop, 32 in the PV loop) up to the 4096 keys it accepts, Smax to match; the newest key
+    (position pos, appended by the fused kernels in the same launch) or key 0 dominating the row, so that a context that is one
+    key short (or starts one key late) is far outside the bound; the cache slot AFTER the newest key, which no honest kernel reads,
+    holds 3 q, so that a context one key long is far outside it too; one position for the batch and one per row (pos_stride 1)."""
+    from magma_amd import ops
+    from oracle.model import rotary_tables
+    B, H = 2, 2
+    Smax = max(64, (ctx + 63) // 64 * 64)
+    d = H * 256
+    kc0 = rnd(B, H, Smax, 256, dev=dev, seed=81, scale=0.5).to(BF16)
+    vc0 = rnd(B, H, Smax, 256, dev=dev, seed=82).to(BF16)
+    qkv = rnd(B, 3 * d, dev=dev, seed=83, scale=0.5).to(BF16)
+    if dominant == "newest":            # k of the new token = 2 q (the rotary turns both by the same angle: k_rot = 2 q_rot)
+        qkv[:, d:2 * d] = (qkv[:, :d].float() * 2).to(BF16)
+    sin_t, cos_t = rotary_tables(64, Smax)
+    sin_t, cos_t = sin_t.to(dev).contiguous(), cos_t.to(dev).contiguous()
+    x = rnd(B, 512, dev=dev, seed=84).to(BF16)
+    w = rnd(264, 512, dev=dev, seed=85, scale=0.05).to(BF16)
+    lin = ops.PackedLinear(w, bias=rnd(264, dev=dev, seed=86))
+    for pos_rows in ([ctx - 1, ctx - 1], [ctx - 1, (ctx - 1) // 2]):
+        per_row = pos_rows[0] != pos_rows[1]
+        d_pos = torch.tensor(pos_rows if per_row else pos_rows[:1], dtype=torch.int32, device=dev)
+        ps = 1 if per_row else 0
+        ctx_rows = [p + 1 for p in pos_rows]
+        kcache, vcache = kc0.clone(), vc0.clone()
+        q = torch.empty(B, H, 1, 256, dtype=BF16, device=dev)
+        ops.rotary_split(qkv, B, 1, H, 64, sin_t, cos_t, q, kcache, vcache, d_pos=d_pos, pos_stride=ps)
+        if dominant == "first":         # key 0 = 2 q of the row (where key 0 is not the key just appended)
+            for b in range(B):
+                if ctx_rows[b] > 1:
+                    kcache[b, :, 0] = (q[b, :, 0].float() * 2).to(BF16)
+        for b in range(B):              # a trap behind the context: key pos + 1 would dominate any row that read it
+            if pos_rows[b] + 1 < Smax:
+                kcache[b, :, pos_rows[b] + 1] = (q[b, :, 0].float() * 3).to(BF16)
+        kin, vin = kcache.clone(), vcache.clone()
+        for b in range(B):              # the slot of the new token is written by the fused kernels themselves
+            kin[b, :, pos_rows[b]] = kc0[b, :, pos_rows[b]]
+            vin[b, :, pos_rows[b]] = vc0[b, :, pos_rows[b]]
+        tag = f"ctx {ctx_rows} Smax {Smax} dominant {dominant}"
+        out = torch.full((B, d), float("nan"), dtype=BF16, device=dev)
+        ops.attn_decode(q, kcache, vcache, out, B, H, d_pos, pos_stride=ps)
+        assert_decode_attention(q, kcache, vcache, ctx_rows, f"attn_decode {tag}", out)
+        k2, v2 = kin.clone(), vin.clone()
+        out2 = torch.full((B, d), float("nan"), dtype=BF16, device=dev)
+        ops.attn_decode_fused(qkv, k2, v2, out2, B, H, d_pos, 64, sin_t, cos_t, pos_stride=ps)
+        assert torch.equal(k2, kcache) and torch.equal(v2, vcache), "fused append must write the same cache rows, and only those"
+        assert_decode_attention(q, kcache, vcache, ctx_rows, f"attn_decode_fused {tag}", out2)
+        k3, v3 = kin.clone(), vin.clone()
+        out3 = torch.full((B, d), float("nan"), dtype=BF16, device=dev)
+        y = torch.empty(B, 264, dtype=torch.float32, device=dev)
+        ops.decode_attn_gemv(qkv, k3, v3, out3, B, H, d_pos, 64, sin_t, cos_t, (x, lin, y, {"out_dtype": torch.float32}), pos_stride=ps)
+        assert torch.equal(k3, kcache) and torch.equal(v3, vcache)
+        assert_decode_attention(q, kcache, vcache, ctx_rows, f"decode_attn_gemv {tag}", out3)
+        kcmp.assert_linear(y, f"decode_attn_gemv, the co-launched GEMV ({tag})", x, w, bias=lin.bias)
 
 
 @pytest.mark.parametrize("ctx", [1, 57, 152, 184])
@@ -308,6 +434,10 @@ def test_decode_attention(dev, ctx):
     pos = torch.tensor([ctx - 1])
     k_new = _rotary_ref(x[:, :, 1], pos, 64).permute(0, 2, 1, 3)
     assert_close(kc[:, :, ctx - 1:ctx].cpu(), k_new, 3e-3, "appended k")
+    xd = qkv.view(B, 3, H, 1, 256)
+    for got, src, name in ((q, xd[:, 0], "q"), (kc[:, :, ctx - 1:ctx], xd[:, 1], "appended k")):
+        rref, rbound = kcmp.rotary_reference(src, sin_t[ctx - 1], cos_t[ctx - 1], 64)
+        kcmp.assert_elementwise(got, rref, rbound, f"rotary_split (decode) {name} ctx={ctx}")
     assert torch.equal(vc[:, :, ctx - 1].float().cpu(), x[:, 0, 2])
     if ctx > 1:
         assert torch.equal(kc[:, :, :ctx - 1], kc0[:, :, :ctx - 1]) and torch.equal(vc[:, :, ctx:], vc0[:, :, ctx:])
@@ -316,12 +446,14 @@ def test_decode_attention(dev, ctx):
     sc = (q.float() @ kc[:, :, :ctx].float().transpose(-1, -2)) / 16.0
     ref = (torch.softmax(sc, -1) @ vc[:, :, :ctx].float()).reshape(B, d)
     assert_close(out, ref, 3e-3, "decode attention")
+    assert_decode_attention(q, kc, vc, [ctx] * B, f"attn_decode ctx {ctx}", out)
     # fused variant: rotary + append + attention in one launch, from the same qkv row
     kc2, vc2 = kc0.clone(), vc0.clone()
     out2 = torch.empty(B, d, dtype=BF16, device=dev)
     ops.attn_decode_fused(qkv, kc2, vc2, out2, B, H, d_pos, 64, sin_t, cos_t)
     assert torch.equal(kc2, kc) and torch.equal(vc2, vc), "fused append must write the same cache rows"
     assert_close(out2, ref, 3e-3, "fused decode attention")
+    assert_decode_attention(q, kc, vc, [ctx] * B, f"attn_decode_fused ctx {ctx}", out2)
 
 
 def test_decode_colaunch_burst_variants_are_bit_identical(dev, monkeypatch):
@@ -353,6 +485,7 @@ def test_decode_colaunch_burst_variants_are_bit_identical(dev, monkeypatch):
         return att, y, kc, vc
     ref = co(0)
     assert_close(ref[1], x.float() @ w.float().t() + lin.bias, 1e-3, "fc_out")
+    kcmp.assert_linear(ref[1], "co-launched fc_out f32", x, w, bias=lin.bias)
     for pipe in (16, 8):
         got = co(pipe)
         assert all(torch.equal(a, b) for a, b in zip(ref, got)), pipe
@@ -377,6 +510,8 @@ def test_avgpool_and_stem(dev):
     y = ops.avgpool2(x.permute(0, 2, 3, 1).contiguous())
     ref = F.avg_pool2d(x.float(), 2).permute(0, 2, 3, 1)
     assert_close(y, ref, 3e-3, "avgpool")
+    pref = F.avg_pool2d(x.double(), 2).permute(0, 2, 3, 1)
+    kcmp.assert_elementwise(y, pref, kcmp.map_bound(pref, F.avg_pool2d(x.double().abs(), 2).permute(0, 2, 3, 1), 4, BF16), "avgpool2")
     img = rnd(2, 3, 20, 16, dev=dev, seed=102).to(BF16)
     w = rnd(8, 3, 3, 3, dev=dev, seed=103, scale=0.2).to(BF16)
     cols = ops.stem_im2col(img)
@@ -385,6 +520,7 @@ def test_avgpool_and_stem(dev):
     out = ops.gemm(cols, ops.PackedLinear(wk))
     ref = F.conv2d(img.float(), w.float(), stride=2, padding=1).permute(0, 2, 3, 1).reshape(-1, 8)
     assert_close(out, ref, GEMM_TOL, "stem conv via im2col")
+    kcmp.assert_linear(out, "stem conv via im2col", prod=kcmp.conv2d_terms(img, w, stride=2))
 
 
 def test_build_labels_exact(dev):
@@ -416,6 +552,11 @@ def test_cross_entropy(dev):
     loss, rows = ops.cross_entropy(lg, tg.to(dev))
     ref = F.cross_entropy(lg.cpu(), tg, ignore_index=-100)
     assert abs(float(loss) - float(ref)) < 1e-4 * max(1.0, abs(float(ref)))
+    C = kcmp.cross_entropy_reference(lg, tg)
+    kcmp.assert_elementwise(rows, *C["rows"], "cross-entropy row losses")
+    mean = (C["rows"][0].sum() / C["n"]).reshape(1)
+    kcmp.assert_elementwise(loss.reshape(1), mean, kcmp.rounded(mean, C["rows"][1].sum() / C["n"] + kcmp.gamma(R + 2) * mean.abs(), torch.float32),
+                            "cross-entropy mean loss")
 
 
 def test_errors_are_loud(dev):
@@ -446,10 +587,14 @@ def test_skinny_layernorm_fold_and_split(dev):
     ref = ln @ w.float().t() + b
     assert_close(out_a, ref[:, :N1], 1e-2, "ln-fold segment a")
     assert_close(out_b, F.gelu(ref[:, N1:], approximate="tanh"), 1e-2, "ln-fold segment b (gelu)")
+    # per element, on the folded operands the kernel multiplies (the whole-tensor numbers above also carry the rounding of W gamma)
+    kcmp.assert_elementwise(out_a, *kcmp.ln_fold_reference(x, w2[:N1], b2[:N1], cs[:N1], 1e-5), "ln-fold segment a")
+    kcmp.assert_elementwise(out_b, *kcmp.ln_fold_reference(x, w2[N1:], b2[N1:], cs[N1:], 1e-5, act="gelu"), "ln-fold segment b (gelu)")
     # single segment, fp32 out (lm_head with ln_f folded)
     lin2 = ops.PackedLinear(w2, bias=b2)
     o32 = ops.gemm_skinny(x, lin2, out_dtype=torch.float32, ln_fold=(cs, K, 1e-5))
     assert_close(o32, ref, 1e-2, "ln-fold fp32")
+    kcmp.assert_elementwise(o32, *kcmp.ln_fold_reference(x, w2, b2, cs, 1e-5, out_dtype=torch.float32), "ln-fold fp32")
 
 
 @pytest.mark.parametrize("tile", [256])
@@ -469,7 +614,10 @@ def test_gemm256_deep_pipeline(dev, layout, M, N, K, tile):
         out = ops.gemm(a, lin, layout=layout, residuals=(res,), tile=tile)
         ref = a.float() @ w.float().t() + bias + res.float()
         assert_close(out, ref, GEMM_TOL, f"gemm256 {layout} {M}x{N}x{K} rep{rep}")
+        lref, lbound = kcmp.linear_reference(a, w, bias=bias, residuals=(res,))
+        kcmp.assert_elementwise(out, lref, lbound, f"gemm256 {layout} {M}x{N}x{K} rep{rep}")
         out128 = ops.gemm(a, lin, layout=layout, residuals=(res,), tile=128)
+        kcmp.assert_elementwise(out128, lref, lbound, f"gemm128 {layout} {M}x{N}x{K} rep{rep}")
         assert float((out.float() - out128.float()).abs().max()) <= 2e-2 * float(ref.abs().max())
 
 
@@ -488,6 +636,9 @@ def test_gemm256_tile_walk_group_sizes(dev, monkeypatch, group_m):
     ref_plain = ops.gemm(a, lin, tile=256, out_dtype=torch.float32)
     ref_res = ops.gemm(a, lin, tile=256, act=ops.MG_ACT_GELU_NEW, residuals=(res,))
     assert_close(ref_plain, a.float() @ w.float().t() + lin.bias, GEMM_TOL, "default walk")
+    if group_m == 1:         # the references of every group size are the same two launches: bound them once
+        kcmp.assert_linear(ref_plain, "gemm256 default walk f32", a, w, bias=lin.bias)
+        kcmp.assert_linear(ref_res, "gemm256 default walk gelu + residual", a, w, bias=lin.bias, act="gelu", post_residuals=(res,))
     monkeypatch.setenv("MAGMA_G256_GROUP_M", str(group_m))
     assert torch.equal(ops.gemm(a, lin, tile=256, out_dtype=torch.float32), ref_plain)
     assert torch.equal(ops.gemm(a, lin, tile=256, act=ops.MG_ACT_GELU_NEW, residuals=(res,)), ref_res)
@@ -507,9 +658,13 @@ def test_gemm_activation_from_column(dev, tile, M):
     ref = a.float() @ w.float().t() + bias
     ref[:, n0:] = F.gelu(ref[:, n0:], approximate="tanh")
     assert_close(out, ref, GEMM_TOL, f"act_n0 tile={tile} M={M}")
+    lref, lbound = kcmp.linear_reference(a, w, bias=bias, act="gelu", act_n0=n0)
+    kcmp.assert_elementwise(out, lref, lbound, f"act_n0 tile={tile} M={M}")
     # the two column ranges as separate GEMMs on row views of the same packed weight: same values
     qkv = ops.gemm(a, lin.rows(0, n0, bias=bias[:n0].contiguous()))
     h = ops.gemm(a, lin.rows(n0, N, bias=bias[n0:].contiguous()), act=ops.MG_ACT_GELU_NEW)
+    kcmp.assert_elementwise(qkv, lref[:, :n0], lbound[:, :n0], f"act_n0 row view [0, n0) M={M}")
+    kcmp.assert_elementwise(h, lref[:, n0:], lbound[:, n0:], f"act_n0 row view [n0, N) M={M}")
     assert float((out[:, :n0].float() - qkv.float()).abs().max()) <= 2e-2 * float(ref.abs().max())
     assert float((out[:, n0:].float() - h.float()).abs().max()) <= 2e-2 * float(ref.abs().max())
 
@@ -528,10 +683,13 @@ def test_gemm_split_k(dev, layout):
     ref = F.gelu(a.float() @ w.float().t() + bias, approximate="tanh") + r0[:, :N].float()
     base = ops.gemm(a, lin, layout=layout, act=ops.MG_ACT_GELU_NEW, residuals=(r0,), out_dtype=torch.float32, split_k=1)
     assert_close(base, ref, 1e-4, "split_k=1")
+    lref, lbound = kcmp.linear_reference(a, w, bias=bias, act="gelu", post_residuals=(r0[:, :N],), out_dtype=torch.float32)
+    kcmp.assert_elementwise(base, lref, lbound, f"split_k=1 {layout}")
     for sk in (0, 2, 3, 7, 16):
         buf = torch.full((M, 208), 7.0, dtype=torch.float32, device=dev)
         ops.gemm(a, lin, out=buf, layout=layout, act=ops.MG_ACT_GELU_NEW, residuals=(r0,), split_k=sk)
         assert_close(buf[:, :N], ref, 1e-4, f"split_k={sk}")
+        kcmp.assert_elementwise(buf[:, :N], lref, lbound, f"split_k={sk} {layout}")
         assert bool((buf[:, N:] == 7.0).all()), "wrote past N"
         again = ops.gemm(a, lin, layout=layout, act=ops.MG_ACT_GELU_NEW, residuals=(r0,), out_dtype=torch.float32, split_k=sk)
         assert torch.equal(again, buf[:, :N]), f"split_k={sk} is not deterministic"
@@ -542,8 +700,11 @@ def test_gemm_split_k(dev, layout):
     linc = ops.PackedLinear(wc.permute(0, 2, 3, 1).reshape(Cout, 9 * Cin).contiguous(), tiled=True, rowmajor=True)
     xn = x.permute(0, 2, 3, 1).contiguous().view(B * H * W, Cin)
     refc = F.conv2d(x.float(), wc.float(), padding=1).permute(0, 2, 3, 1).reshape(B * H * W, Cout)
+    cref, cbound = kcmp.linear_reference(prod=kcmp.conv2d_terms(x, wc))
     for sk in (1, 2, 5):
-        assert_close(ops.gemm(xn, linc, conv=(H, W, Cin), layout=layout, split_k=sk), refc, GEMM_TOL, f"conv split_k={sk}")
+        outc = ops.gemm(xn, linc, conv=(H, W, Cin), layout=layout, split_k=sk)
+        assert_close(outc, refc, GEMM_TOL, f"conv split_k={sk}")
+        kcmp.assert_elementwise(outc, cref, cbound, f"conv split_k={sk} {layout}")
     with pytest.raises(Exception, match="split_k"):
         ops.gemm(a, lin, split_k=65)
 
@@ -562,13 +723,16 @@ def test_gemm256_split_k(dev, M, N, K, split):
     res = rnd(M, ops.ceil_to(N, 8), dev=dev, seed=503).to(BF16)[:, :N]
     lin = ops.PackedLinear(w, bias=bias, tiled=True, rowmajor=True)
     ref = a.float() @ w.float().t() + bias + res.float()
+    lref, lbound = kcmp.linear_reference(a, w, bias=bias, residuals=(res,), out_dtype=torch.float32)
     for layout in ("rm", "ft"):
         kw = dict(layout=layout, residuals=(res,), out_dtype=torch.float32)
         out = ops.gemm(a, lin, tile=256 if split else 0, split_k=split, **kw)
         assert_close(out, ref, GEMM_TOL, f"gemm256 split-K {layout} {M}x{N}x{K} split {split}")
+        kcmp.assert_elementwise(out, lref, lbound, f"gemm256 split-K {layout} {M}x{N}x{K} split {split}")
         out2 = ops.gemm(a, lin, tile=256 if split else 0, split_k=split, **kw)
         assert torch.equal(out, out2)
         o128 = ops.gemm(a, lin, tile=128, **kw)
+        kcmp.assert_elementwise(o128, lref, lbound, f"gemm128 {layout} {M}x{N}x{K}")
         assert float((out - o128).abs().max()) <= 2e-3 * float(ref.abs().max())
 
 
@@ -598,11 +762,16 @@ def test_gemm_accumulates_into_fp32_output_with_row_scale(dev, M, N, K, tile, sp
                      row_scale=rs if use_rs else None)
             ref = before[:, :N] + (prod * rs[:, None] if use_rs else prod)
             assert_close(buf[:, :N], ref, 2e-5, f"accumulate {layout} row_scale={use_rs}")
+            kcmp.assert_linear(buf[:, :N], f"accumulate {layout} row_scale={use_rs} {M}x{N}x{K}", a, w, row_scale=rs if use_rs else None,
+                             base=before[:, :N])
+            once = buf[:, :N].clone()                 # the second pass adds to what the first one left
             assert torch.equal(buf[:, N:], before[:, N:]), "wrote past N"
             # twice = the product added twice (no hidden state in the workspace)
             ops.gemm(a, lin, out=buf[:, :N], layout=layout, use_bias=False, tile=tile, split_k=split, accumulate=True,
                      row_scale=rs if use_rs else None)
             assert_close(buf[:, :N], before[:, :N] + 2 * (prod * rs[:, None] if use_rs else prod), 2e-5, "second accumulation")
+            kcmp.assert_linear(buf[:, :N], f"second accumulation {layout} row_scale={use_rs} {M}x{N}x{K}", a, w,
+                               row_scale=rs if use_rs else None, base=once)
     with pytest.raises(Exception, match="accumulate"):
         d_out = torch.zeros(M, ops.ceil_to(N, 8), dtype=BF16, device=dev)
         ops.gemm(a, lin, out=d_out[:, :N], use_bias=False, accumulate=True)
@@ -616,9 +785,63 @@ def test_gelu_erf_passes(dev, M, N, ld):
     x = (rnd(M, ld, dev=dev, seed=600) * 2).to(BF16)[:, :N]
     g = rnd(M, ld, dev=dev, seed=601).to(BF16)[:, :N]
     assert_close(ops.gelu_erf(x), F.gelu(x.float()), 3e-3, "gelu (erf)")
+    ge, ge_err, gd, gd_err = kcmp.gelu_erf_terms(x)
+    kcmp.assert_elementwise(ops.gelu_erf(x), ge, kcmp.rounded(ge, ge_err, BF16), f"gelu_erf {M}x{N}")
     xr = x.float().clone().requires_grad_(True)
     F.gelu(xr).backward(torch.ones_like(xr))
     assert_close(ops.gelu_erf_grad_mul(g, x), g.float() * xr.grad, 3e-3, "gelu (erf) gradient")
+    gref = g.double() * gd
+    kcmp.assert_elementwise(ops.gelu_erf_grad_mul(g, x), gref, kcmp.rounded(gref, g.double().abs() * gd_err + kcmp.U_F32 * gref.abs(), BF16),
+                            f"gelu_erf_grad_mul {M}x{N}")
     y = x.clone()
     ops.gelu_erf(y, out=y)
     assert torch.equal(y, ops.gelu_erf(x))
+
+
+@pytest.mark.parametrize("B,H,W,P", [(2, 64, 64, 32), (3, 42, 70, 14), (1, 96, 192, 96)])
+def test_patchify(dev, B, H, W, P):
+    """mg_patchify_bf16: the im2col of the stride-P patch convolution, rows in (c, py, px) order -- a copy, bit for bit; a patch
+    size that is no multiple of the vector width (14) and one with more (c, py) rows than the workgroup has threads (96)."""
+    from magma_amd import ops
+    img = rnd(B, 3, H, W, dev=dev, seed=701).to(BF16)
+    out = ops.patchify(img, P)
+    ref = img.view(B, 3, H // P, P, W // P, P).permute(0, 2, 4, 1, 3, 5).reshape(B * (H // P) * (W // P), 3 * P * P)
+    assert out.shape == ref.shape and torch.equal(out, ref)
+
+
+@pytest.mark.parametrize("B,G,width", [(2, 49, 768), (3, 5, 300), (1, 1, 8)])
+def test_vit_embed(dev, B, G, width):
+    """mg_vit_embed_bf16: [class | patches] + positional embedding, one fp32 addition rounded to bf16; a width that is no multiple of
+    the 256 threads that walk it."""
+    from magma_amd import ops
+    patches = rnd(B * G, width, dev=dev, seed=711).to(BF16)
+    cls = rnd(width, dev=dev, seed=712).to(BF16)
+    pos = rnd(G + 1, width, dev=dev, seed=713, scale=0.3).to(BF16)
+    out = ops.vit_embed(patches, cls, pos, B)
+    tok = torch.cat([cls.double().expand(B, 1, width), patches.double().view(B, G, width)], 1)
+    ref = tok + pos.double()
+    assert out.shape == (B, G + 1, width)
+    kcmp.assert_elementwise(out, ref, kcmp.map_bound(ref, tok.abs() + pos.double().abs(), 1, BF16), f"vit_embed B={B} G={G} width={width}")
+
+
+@pytest.mark.parametrize("inputs", ["i.i.d.", "one key dominates"])
+@pytest.mark.parametrize("B,S,H", [(2, 64, 2), (3, 50, 12), (1, 256, 1), (2, 1, 3), (1, 197, 2)])
+def test_attn_small_forward(dev, B, S, H, inputs):
+    """mg_attn_small_bf16 (CLIP ViT: non-causal, head dim 64, S <= 256, everything in fp32 with an online softmax that may update its
+    maximum at every key) against fp64 softmax(q k^T / 8) v per element; S = 50 / 197 (ViT-B/32, ViT-B/16), the LDS limit 256, one
+    token; and with the LAST key dominating every row (a key loop that ends one short shows in every element)."""
+    from magma_amd import ops
+    w = H * 64
+    qkv = rnd(B * S, 3 * w, dev=dev, seed=721).to(BF16)
+    x = qkv.view(B, S, 3, H, 64).permute(2, 0, 3, 1, 4)         # [3, B, H, S, 64]
+    if inputs == "one key dominates" and S > 1:      # every query gets the component u, the last key is 3 u: t ~ 3 |u|^2 / 8 = 24
+        u = rnd(1, H, 1, 64, dev=dev, seed=722)
+        x[0][:] = (x[0].float() + u).to(BF16)          # (x is a view of qkv: the kernel reads these values)
+        x[1][:, :, S - 1] = (3 * u[:, :, 0]).to(BF16)
+    out = ops.attn_small(qkv, B, S, H)
+    q, k, v = x[0], x[1], x[2]
+    T = kcmp.attention_terms(q, k, v, scale=0.125)
+    # per key: multiply by the rescale factor, multiply p v, add -> 3 roundings on a term's way, + reciprocal and final multiply
+    bound = kcmp.attention_bound(T, S, BF16, K=64, p_dtype=torch.float32, n_rescale=S, n_fp32=3 * S + 4)
+    kcmp.assert_elementwise(out, kcmp.rows_of(T["ref"]), kcmp.rows_of(bound), f"attn_small B={B} S={S} H={H}, {inputs}")
+    assert_close(out, kcmp.rows_of(T["ref"]), 3e-3, "attn_small")

@@ -11,6 +11,8 @@ import math
 import pytest
 import torch
 
+import kernel_compare as kcmp
+
 pytestmark = pytest.mark.gpu
 
 BF16 = torch.bfloat16
@@ -58,6 +60,12 @@ def test_decode_kernels_per_row_positions(dev):
         sc = (q_rot[-1][:, None, :] @ kc[b, :, : p + 1].float().cpu().transpose(-1, -2)) / 16.0
         ref = (torch.softmax(sc, -1) @ vc[b, :, : p + 1].float().cpu()).reshape(d)
         assert_close(out[b], ref, 3e-3, f"fused decode attention, row {b}")
+    # per element, on the bf16 q the kernel itself attends with (the stand-alone rotary pass writes the same q, k, v bits)
+    qk = torch.empty(B, H, 1, 256, dtype=BF16, device=dev)
+    kcx, vcx = kc0.clone(), vc0.clone()
+    ops.rotary_split(qkv, B, 1, H, rot, sin_t, cos_t, qk, kcx, vcx, d_pos=d_pos, pos_stride=1)
+    assert torch.equal(kcx, kc) and torch.equal(vcx, vc)
+    kcmp.assert_causal_attention(out, qk, kc, vc, f"fused decode attention, positions {pos}", p0=d_pos, p_dtype=torch.float32, n_rescale=0)
 
     # stand-alone attention on an already rotated q, over the cache the fused launch wrote
     q = torch.stack(q_rot).to(BF16).to(dev).view(B, H, 1, 256).contiguous()
@@ -67,6 +75,7 @@ def test_decode_kernels_per_row_positions(dev):
         sc = (q[b].float().cpu() @ kc[b, :, : p + 1].float().cpu().transpose(-1, -2)) / 16.0
         ref = (torch.softmax(sc, -1) @ vc[b, :, : p + 1].float().cpu()).reshape(d)
         assert_close(out2[b], ref, 3e-3, f"decode attention, row {b}")
+    kcmp.assert_causal_attention(out2, q, kc, vc, f"decode attention, positions {pos}", p0=d_pos, p_dtype=torch.float32, n_rescale=0)
 
     # the co-launch with a GEMV: the same attention body, so the same cache writes and the same context rows
     kc3, vc3 = kc0.clone(), vc0.clone()
@@ -80,6 +89,7 @@ def test_decode_kernels_per_row_positions(dev):
     assert torch.equal(kc3, kc) and torch.equal(vc3, vc)
     assert torch.equal(out3, out)
     assert_close(y, xg.float() @ w.float().t(), 1e-3, "co-launched GEMV")
+    kcmp.assert_linear(y, "co-launched GEMV (per-row positions)", xg, w)
     assert d_pos.tolist() == pos, "the decode kernels must not move the positions"
 
     # pos_stride 0 on the same buffer: every row appends at d_pos[0], as before
