@@ -242,9 +242,11 @@ def pad_k_rowmajor(w: torch.Tensor) -> torch.Tensor:
 def skinny_desc(x: torch.Tensor, w: PackedLinear, out: Optional[torch.Tensor] = None, *, act: int = MG_ACT_NONE,
                 residuals: Sequence[torch.Tensor] = (), act_after: int = MG_ACT_NONE, scale=None,
                 use_bias: bool = True, out_dtype=BF16, variant: int = 0, ln_fold: Optional[tuple] = None,
-                split: Optional[tuple] = None):
+                split: Optional[tuple] = None, aux=None, aux_mode: int = MG_AUX_NONE, aux_after: bool = False,
+                out2: Optional[torch.Tensor] = None):
     """Build the C descriptor of one decode-shape (M <= 16) weight-streaming GEMM.  Returns
-    (desc, out, keepalive)."""
+    (desc, out, keepalive).  ``aux`` / ``aux_mode`` / ``aux_after`` / ``out2`` as for ``gemm`` (mg_epilogue.aux / .C2: the GEMV
+    then runs the general epilogue instead of its four-column fast path); with ``split`` they belong to the first segment."""
     _need_gpu(x)
     assert x.dtype == BF16 and x.ndim == 2 and x.stride(1) == 1 and w.ft is not None
     assert x.shape[1] == w.Kp, "decode activations must span the padded K"
@@ -258,7 +260,7 @@ def skinny_desc(x: torch.Tensor, w: PackedLinear, out: Optional[torch.Tensor] = 
     if w8:
         d.w_scale = w.scale.data_ptr()
     n_a = w.N if split is None else split[0]
-    d.ep = _epilogue(out, n_a, w.bias if use_bias else None, scale, act, residuals, act_after)
+    d.ep = _epilogue(out, n_a, w.bias if use_bias else None, scale, act, residuals, act_after, aux, aux_mode, aux_after, out2)
     if ln_fold is not None:
         cs, dd, eps = ln_fold
         d.ln_colsum, d.ln_inv_d, d.ln_eps = cs.data_ptr(), 1.0 / dd, eps

@@ -32,6 +32,13 @@ FLOOR = 2.0 ** -120
 U_TRANS = 2.0 * U_F32
 # sup |d/dx gelu_new(x)| = 1.1290 (at x = 1.46): how far the tanh-form GELU stretches an error of its argument
 GELU_LIPSCHITZ = 1.13
+# CLIP's QuickGELU x sigmoid(1.702 x): the constant as the kernels hold it (1.702f, the fp32 value nearest to 1.702), and
+# sup |d/dx| = 1.0998 (at 1.702 x = 2.40)
+QUICK_GELU_K = 1.7020000219345093
+QUICK_GELU_LIPSCHITZ = 1.10
+# a plain fp32 division in device code: correctly rounded with hipcc's defaults; 2.5 ulp is what HIP / OpenCL state for the
+# form a compiler may choose instead (-fno-hip-fp32-correctly-rounded-divide-sqrt).  2.5 ulp = 5 u32.
+U_DIV = 5.0 * U_F32
 
 
 def unit_roundoff(dtype) -> float:
@@ -194,6 +201,14 @@ def through_activation(err, act: str, pre=None, ref=None):
         two_u = 2.0 * math.sqrt(2.0 / math.pi) * (pre + 0.044715 * pre ** 3)
         eval_rel = 6.0 * U_F32 * two_u.abs() + 2.0 * U_TRANS + 3.0 * U_F32
         return GELU_LIPSCHITZ * err + eval_rel * ref.abs()
+    if act == "quick_gelu":
+        # apply_act of csrc/common.h: v * __frcp_rn(1 + __expf(-1.702f v)).  The exponent t = 1.702 v is rounded as a product and
+        # once more inside __expf (times log2 e): an absolute error 2 u32 |t| of the exponent is that relative error of the
+        # exponential, which v_exp_f32 forms to 1 ulp; 1 + e inherits at most that relative error and rounds once, the reciprocal
+        # is good to 1 ulp, the final product rounds once.
+        assert pre is not None and ref is not None
+        eval_rel = 2.0 * U_F32 * (QUICK_GELU_K * pre).abs() + 2.0 * U_TRANS + 2.0 * U_F32
+        return QUICK_GELU_LIPSCHITZ * err + eval_rel * ref.abs()
     if act not in ("none", "relu"):
         raise ValueError(act)
     return err
@@ -373,6 +388,107 @@ def linear_reference(a=None, w=None, *, prod=None, bias=None, scale=None, row_sc
     for r in post_residuals:
         out, mag = out + f64(r), mag + f64(r).abs()
     return out, rounded(out, act_err + gamma(len(post_residuals)) * mag, out_dtype)
+
+
+ACTS = ("none", "relu", "gelu", "quick_gelu")
+AUX_MODES = ("none", "relu_gate", "gelu_grad", "mul", "quick_gelu_grad")
+
+
+def aux_factor_terms(aux: torch.Tensor, aux_mode: str):
+    """(f, d_f): the factor an aux mode makes of the bf16 aux operand (exact in fp64) and the fp32 error of forming it.
+    relu_gate is ``aux > 0`` exactly as the kernels write it: 0.0 and -0.0 close the gate."""
+    a = f64(aux)
+    if aux_mode == "relu_gate":
+        return (a > 0).to(torch.float64), torch.zeros_like(a)
+    if aux_mode == "mul":
+        return a, torch.zeros_like(a)
+    if aux_mode == "gelu_grad":
+        return gelu_new_grad_terms(a)
+    if aux_mode == "quick_gelu_grad":
+        return quick_gelu_grad_terms(a)
+    raise ValueError(aux_mode)
+
+
+def epilogue_reference(prod_terms, *, scale=None, row_scale=None, bias=None, act: str = "none", act_n0: int = 0, aux=None,
+                       aux_mode: str = "none", aux_after: bool = False, residuals=(), act_after: str = "none", base=None,
+                       out_dtype=torch.bfloat16) -> dict:
+    """The contract of mg_epilogue (include/magma_hip.h), literally and in its order, in fp64 with per-element bounds:
+
+        v = (acc * row_scale[m]) * scale[n] + bias[n];   C2 = bf16(v);   v = act(v) on the columns >= act_n0;
+        v *= f(aux) unless aux_after;   v += res0;  v += res1;  v += res2;   v *= f(aux) if aux_after;
+        v = relu(v) if act_after;   C = out_dtype(v), or C = base + v (fp32, ``accumulate``)
+        -> {"C": (ref, bound), "C2": (ref, bound)}
+
+    prod_terms = (exact product, magnitude product, K [, a further absolute error of the product]) as product_terms /
+    conv2d_terms / the fp8 tests' dequantised_product give it.  act: one of ACTS; aux_mode: one of AUX_MODES.
+
+    The bound carries the pair (exact value x, fp32 error e) through the same steps.  One fp32 operation on a value with error
+    e gives |fl(x~) - x| <= e + u32 (|x| + e) (``once``); a product with an exact factor s multiplies e by |s| first.
+      accumulator   e = gamma(K) * mag [+ the product's own term]: K products summed in fp32 in any order
+      row_scale, scale, bias, each residual, base: one operation each (the kernels may contract scale and bias into one fma:
+                    fewer roundings, never more)
+      C2            one rounding of (x, e) to bf16
+      act           through_activation: relu 1-Lipschitz; gelu / quick_gelu stretch e by their Lipschitz constant and add the
+                    evaluation error; columns < act_n0 keep (x, e)
+      aux product   x f with |f~ - f| <= d_f (aux_factor_terms; 0 for the gate and the plain product): e |f| + (|x| + e) d_f, one
+                    more rounding.  With aux_after the pair that is multiplied already holds the residual sum, so the factor
+                    applies to the residuals' roundings too -- and a closed gate makes the output exactly 0
+      act_after     ReLU is 1-Lipschitz: x = relu(x), e unchanged
+      store         ``rounded``: u_out |x| + (1 + u_out) e"""
+    if len(prod_terms) == 4:
+        x, mag, K, extra = prod_terms
+    else:
+        (x, mag, K), extra = prod_terms, None
+    assert act in ACTS and aux_mode in AUX_MODES and act_after in ("none", "relu")
+    e = gamma(K) * mag
+    if extra is not None:
+        e = e + extra
+
+    def once(x, e):
+        return e + U_F32 * (x.abs() + e)
+
+    if row_scale is not None:
+        s = f64(row_scale)[:, None]
+        x, e = x * s, e * s.abs()
+        e = once(x, e)
+    if scale is not None:
+        s = f64(scale)
+        x, e = x * s, e * s.abs()
+        e = once(x, e)
+    if bias is not None:
+        x = x + f64(bias)
+        e = once(x, e)
+    out = {"C2": (x, rounded(x, e, torch.bfloat16))}
+    if act != "none":
+        y = torch.relu(x) if act == "relu" else (gelu_new64(x) if act == "gelu" else quick_gelu64(x))
+        ye = through_activation(e, act, x, y)
+        if act_n0:
+            col = torch.arange(x.shape[1], device=x.device) >= act_n0
+            y, ye = torch.where(col, y, x), torch.where(col, ye, e)
+        x, e = y, ye
+    if aux_mode != "none":
+        f, d_f = aux_factor_terms(aux, aux_mode)
+
+    def times_aux(x, e):
+        xe = e * f.abs() + (x.abs() + e) * d_f
+        x = x * f
+        return x, once(x, xe)
+
+    if aux_mode != "none" and not aux_after:
+        x, e = times_aux(x, e)
+    for r in residuals:
+        x = x + f64(r)
+        e = once(x, e)
+    if aux_mode != "none" and aux_after:
+        x, e = times_aux(x, e)
+    if act_after == "relu":
+        x = torch.relu(x)
+    if base is not None:
+        assert out_dtype == torch.float32, "accumulate adds into an fp32 output"
+        x = x + f64(base)
+        e = once(x, e)
+    out["C"] = (x, rounded(x, e, out_dtype))
+    return out
 
 
 def assert_linear(out: torch.Tensor, what: str, a=None, w=None, **kw) -> float:
@@ -598,6 +714,33 @@ def gelu_new_grad_terms(x: torch.Tensor):
     d_t = 2.0 * d_sg + U_F32
     d_one_minus = 2.0 * t.abs() * d_t + 2.0 * U_F32
     err = d_sg + C * d_one_minus + gamma(8) * C * (1.0 - t * t) + U_F32 * (ref.abs() + sg)
+    return ref, err
+
+
+def quick_gelu64(x: torch.Tensor) -> torch.Tensor:
+    return x * torch.sigmoid(QUICK_GELU_K * x)
+
+
+def quick_gelu_grad_terms(x: torch.Tensor):
+    """d/dx [x sigmoid(1.702 x)] as quick_gelu_grad_f of csrc/common.h forms it -> (ref, fp32 error), fp64:
+        sg = 1 / (1 + exp(-t)), t = 1.702f x;      grad = sg * (1 + t (1 - sg)).
+    sg = 1 / (1 + E): the exponent is rounded twice (the product, and __expf's own product with log2 e) -> 2 u32 |t| relative to the
+    exponential E, v_exp_f32 1 ulp; a relative error d of E moves sg by sg (E / (1 + E)) d = sg (1 - sg) d; the addition rounds
+    once, the division is good to U_DIV.  1 - sg CANCELS for large positive x (sg -> 1): its error is
+    ABSOLUTE, d_sg + u32 (1 - sg), and is multiplied by |t|; t itself and the product t (1 - sg) round once each; 1 + (.) and the
+    final product with sg round once each."""
+    x = f64(x)
+    t = QUICK_GELU_K * x
+    sg = torch.sigmoid(t)
+    om = torch.sigmoid(-t)                                  # 1 - sg without the cancellation
+    d_sg = sg * (om * (2.0 * U_F32 * t.abs() + U_TRANS) + U_F32 + U_DIV)
+    d_om = d_sg + U_F32 * om
+    b = t * om
+    d_b = t.abs() * d_om + 2.0 * U_F32 * b.abs()
+    c = 1.0 + b
+    d_c = d_b + U_F32 * c.abs()
+    ref = sg * c
+    err = c.abs() * d_sg + sg * d_c + U_F32 * ref.abs()
     return ref, err
 
 

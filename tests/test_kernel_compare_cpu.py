@@ -16,6 +16,7 @@ import math
 import pytest
 import torch
 
+import epilogue_cases as ec
 import kernel_compare as kc
 
 BF16 = torch.bfloat16
@@ -114,6 +115,147 @@ def test_gemm_bound_is_tight_not_generous():
     bound = kc.gemm_bound(ref, mag, K, BF16)
     worst = kc.worst_ratio(gemm_stand_in(a, w, None, seed=3), ref, bound)
     assert 0.9 < worst < 1.0, worst
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the epilogue contract (kernel_compare.epilogue_reference, epilogue_cases.py)
+# ---------------------------------------------------------------------------------------------------------------------------
+# 130 x 203 x 128: the shape of the per-element tail path of the GPU matrix (N % 8 = 3, so "the last N % 8 columns" exist)
+EPI_SHAPE = (130, 203, 128)
+_epi_case = {}
+
+
+def epi_case():
+    if not _epi_case:
+        _epi_case["case"] = ec.make_case(*EPI_SHAPE, seed=0)
+    return _epi_case["case"]
+
+
+def test_epilogue_configurations_cover_every_pair():
+    """Every pair of 'on' values of {scale, row_scale, bias, act (3), act_n0, aux_mode (4), aux_after, residuals, act_after, C2,
+    fp32 output, accumulate} occurs in one configuration at least -- except two activations or two aux modes at once, which no
+    descriptor can say -- and each activation / aux mode / residual count also occurs with the other fields OFF (the engine
+    entries).  Every entry obeys check_epilogue (cfg asserts accumulate -> fp32)."""
+    feats = [ec.features(c) for c in ec.CONFIGS]
+    names = sorted(set().union(*feats))
+    missing = []
+    for i, a in enumerate(names):
+        for b in names[i + 1:]:
+            if a.split("=")[0] == b.split("=")[0] and "=" in a:
+                continue
+            if not any(a in f and b in f for f in feats):
+                missing.append((a, b))
+    assert not missing, missing
+    assert {c["act"] for c in ec.CONFIGS} == set(kc.ACTS) and {c["aux_mode"] for c in ec.CONFIGS} == set(kc.AUX_MODES)
+    assert {c["n_res"] for c in ec.CONFIGS} == {0, 1, 2, 3}
+    assert any(c["act"] == "quick_gelu" and c["c2"] for c in ec.CONFIGS) and any(c["aux_mode"] == "quick_gelu_grad" for c in ec.CONFIGS)
+
+
+def test_epilogue_inputs_hold_the_special_values():
+    M, N, _ = EPI_SHAPE
+    aux = epi_case()["aux"].float()
+    zero = aux == 0
+    neg = zero & torch.signbit(aux)
+    assert 0.1 < float(zero.float().mean()) < 0.3 and int(neg.sum()) > 1000 and int((zero & ~neg).sum()) > 1000
+    rows, cols = ec.corner_index(M, N)
+    assert rows == [0, 63, 64, 127, 128, 129] and cols == [0, 7, 8, 202]
+    assert bool(zero[rows][:, cols].all())
+    (rp, cp), (rn, cn) = ec.big_index(M, N)
+    assert float(aux[rp, cp]) == 30.0 and float(aux[rn, cn]) == -30.0
+    assert bool((aux > 0).any()) and bool((aux < 0).any())
+    # the two GELU derivatives at +-30: exactly 1 and 0 in fp32, and 1 / 0 within the stated error in fp64
+    for mode in ("gelu_grad", "quick_gelu_grad"):
+        f32 = ec._aux32(torch.tensor([30.0, -30.0]), mode)
+        assert float(f32[0]) == 1.0 and abs(float(f32[1])) < 1e-18, (mode, f32)
+        f, d_f = kc.aux_factor_terms(torch.tensor([30.0, -30.0]).to(BF16), mode)
+        assert abs(float(f[0]) - 1.0) <= float(d_f[0]) + 1e-12 and abs(float(f[1])) <= float(d_f[1]) + 1e-12
+
+
+@pytest.mark.parametrize("name", [c["name"] for c in ec.CONFIGS])
+def test_epilogue_stand_in_passes_every_configuration(name):
+    """The honest float32 stand-in of the contract is inside the bound of epilogue_reference for C and for C2, under every
+    configuration; where the gate is closed it stores exactly what closed_gate_expectation says."""
+    c, case = ec.BY_NAME[name], epi_case()
+    R = ec.reference(case, c)
+    C, C2 = ec.stand_in(case, c)
+    assert kc.assert_elementwise(C, *R["C"], f"stand-in {name} C") < 1.0
+    if c["c2"]:
+        assert kc.assert_elementwise(C2, *R["C2"], f"stand-in {name} C2") < 1.0
+    if c["aux_mode"] == "relu_gate":
+        closed = case["aux"] == 0
+        assert torch.equal(C[closed], ec.closed_gate_expectation(case, c)[closed])
+
+
+@pytest.mark.parametrize("fault", ec.FAULTS)
+def test_epilogue_seeded_faults_exceed_the_bound(fault):
+    """Each slip a hand-written copy of the epilogue can have, written into the stand-in, is at least 8 x outside the bound in
+    EVERY configuration it can occur in.  Printed per configuration: the margin.  Faults that only special elements show:
+      * "gate with >=" differs where aux is exactly 0.0 or -0.0 and nowhere else (1 / 7 + 1 / 11 of the elements here);
+      * "res2 dropped ..." differs in the last N % 8 = 3 columns only;
+      * "activation left of act_n0" differs in the columns < act_n0 only, "C2 taken after the activation" in C2 only."""
+    case = epi_case()
+    M, N, _ = EPI_SHAPE
+    hit = 0
+    for c in ec.CONFIGS:
+        if not ec.fault_applies(fault, c, N):
+            continue
+        hit += 1
+        R = ec.reference(case, c)
+        C, C2 = ec.stand_in(case, c, fault)
+        which = "C2" if fault == "C2 taken after the activation" else "C"
+        bad = C2 if which == "C2" else C
+        w, _ = check_fault(f"{fault} [{c['name']}]", bad, *R[which])
+        other = C if which == "C2" else C2
+        if (which == "C2" or c["c2"]) and fault != "row_scale after the bias":      # the output the fault does not touch stays inside its bound
+            assert kc.worst_ratio(other, *R["C" if which == "C2" else "C2"]) < 1.0
+        if fault == "gate with >=":
+            r = kc.ratios(C, *R["C"])
+            assert float(r[case["aux"] != 0].max()) < 1.0, "the fault must be invisible where aux != 0"
+        if fault == "res2 dropped in the last N % 8 columns":
+            assert float(kc.ratios(C, *R["C"])[:, : N - N % 8].max()) < 1.0
+    assert hit >= 2, f"{fault}: only {hit} configurations can show it"
+
+
+def test_epilogue_reference_agrees_with_linear_reference():
+    """Where both can state a case, the two constructors give the same reference, and epilogue_reference is never the looser one:
+    both count the same roundings, but a rounding of an epilogue step is relative to the VALUE at hand, which epilogue_reference
+    carries, where linear_reference charges it to the magnitude sum -- the bounds part where the product cancels, and stay
+    within a factor of two (the accumulation term gamma(K) |A| |W|^T and the output rounding are common to both)."""
+    case = epi_case()
+    a, w = case["a"], case["w"]
+    for name, kw in (("bias", dict(bias=case["bias"])),
+                     ("scale_bias_relu", dict(scale=case["scale"], bias=case["bias"], act="relu")),
+                     ("bias_gelu", dict(bias=case["bias"], act="gelu")),
+                     ("bias_gelu_n0", dict(bias=case["bias"], act="gelu", act_n0=ec.act_n0_of(EPI_SHAPE[1]))),
+                     ("bias_res3", dict(bias=case["bias"], residuals=case["res"]))):
+        lref, lbound = kc.linear_reference(a, w, **kw)
+        eref, ebound = ec.reference(case, ec.BY_NAME[name])["C"]
+        assert torch.allclose(lref, eref, rtol=1e-14, atol=1e-14), name
+        assert float((ebound / lbound).max()) <= 1.0 + 1e-9 and float((ebound / lbound).min()) > 0.5, (name, float((ebound / lbound).min()))
+
+
+def test_quick_gelu_terms():
+    """quick_gelu through through_activation and quick_gelu_grad_terms against float32 evaluations of the kernels' formulas on a
+    dense grid (honest: inside the bound), against autograd in fp64 (the references are the derivative they claim to be), and the
+    cancellation of 1 - sg at large positive x stays bounded in ABSOLUTE terms."""
+    x32 = torch.linspace(-40, 40, 160001)
+    x = x32.double()
+    ref = kc.quick_gelu64(x)
+    err = kc.through_activation(torch.zeros_like(x), "quick_gelu", x, ref)
+    got = ec._act32(x32, "quick_gelu").double()
+    assert float(((got - ref).abs() / (err + kc.FLOOR)).max()) < 1.0
+    gref, gerr = kc.quick_gelu_grad_terms(x32)
+    ggot = ec._aux32(x32, "quick_gelu_grad").double()
+    assert float(((ggot - gref).abs() / (gerr + kc.FLOOR)).max()) < 1.0
+    xa = x.clone().requires_grad_(True)
+    (auto,) = torch.autograd.grad(kc.quick_gelu64(xa).sum(), xa)
+    assert float((auto - gref).abs().max()) < 1e-12
+    assert 1.09 < float(gref.abs().max()) <= kc.QUICK_GELU_LIPSCHITZ
+    # where 1 - sg cancels (large positive x) the error stays ABSOLUTE and of the size |t| u32: no relative blow-up
+    assert bool((gerr <= (8.0 * (kc.QUICK_GELU_K * x).abs() + 16.0) * kc.U_F32).all()), float(gerr.max())
+    assert kc.QUICK_GELU_K == float(torch.tensor(1.702, dtype=torch.float32))
+    # a derivative that is 0.1 % off is far outside
+    assert float(((gref - 0.999 * ggot).abs() / (gerr + kc.FLOOR))[x32.abs() < 4].max()) > FAULT_FACTOR
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
