@@ -219,6 +219,11 @@ class LMEngine:
             ly.fc_out = ops.PackedLinear(mlp.c_proj.weight, mlp.c_proj.bias)
             ly.ln_g, ly.ln_b = f32(blk.ln_1.weight), f32(blk.ln_1.bias)
             ly.dec_in = None      # decode-only fused [qkv | fc_in] operand with ln_1 folded in (built lazily)
+            # lazily built operands, None until built (whether a block HAS one is _block_kind's answer, not the field's):
+            # [W_out | W_up] (_ensure_out_up), [W_up_mlp | W_up_attn] (_adapter_up_cat), [W_fc_out ; W_dn W_fc_out]
+            # (_fold_adapter_down), the e4m3 prefill copies by projection name (_fp8_weight), the W8A16 decode operands
+            ly.out_up = ly.up_cat = ly.fc_dn = ly.w8 = None
+            ly.fp8 = {}
             ly._src = (a, mlp)
             self.layers.append(ly)
         self.lnf_g, self.lnf_b = f32(lm.transformer.ln_f.weight), f32(lm.transformer.ln_f.bias)
@@ -226,7 +231,7 @@ class LMEngine:
         self.Vp = ops.ceil_to(self.V, 8)
         self.sin_t, self.cos_t = rotary_tables(cfg.rotary_dim, cfg.max_position_embeddings, dev)
         self.rot = cfg.rotary_dim
-        self.head_dec = None
+        self.head_dec = self.head_w8 = None
         self._lm_head = lm.lm_head
         self._cache_pool = {}                        # (B, Smax) -> KVCache + captured decode graph, LRU-bounded
         self._cache_pool_max = int(os.environ.get("MAGMA_CACHE_POOL", "4"))
@@ -245,7 +250,6 @@ class LMEngine:
         self._dec_in_variant = int(os.environ.get("MAGMA_DEC_IN_VARIANT", "0"))   # tuning knob: nt | waves<<4 | kc<<8
         self._dec_dn_variant = int(os.environ.get("MAGMA_DEC_DN_VARIANT", "0"))   # the same for the adapter-down and the
         self._dec_cat_variant = int(os.environ.get("MAGMA_DEC_CAT_VARIANT", "0"))  # [W_out | W_up] launches of the v1 block
-        self._side_stream = torch.cuda.Stream(device=dev)
         self.group_launches = os.environ.get("MAGMA_DECODE_GROUPED", "1") == "1"
         # MAGMA_DECODE_FOLD -- how the adapter of a MAGMA_v1 block is laid over the block's launches (round 4):
         #   0  four launches as in rounds 1-3: [ln_1+qkv+fc_in] -> [attention || fc_out] -> [out_proj || adapter-down] -> [adapter-up]
@@ -262,7 +266,6 @@ class LMEngine:
         self.fold_dn = int(os.environ.get("MAGMA_DECODE_FOLD", "2"))
         self.fuse_in = os.environ.get("MAGMA_PREFILL_FUSE_IN", "1") == "1"      # [qkv | fc_in] as one prefill GEMM
         self.cat_up = os.environ.get("MAGMA_PREFILL_CAT", "1") == "1"           # out_proj + adapter-up as one GEMM over [ctx | t]
-        self.two_streams = os.environ.get("MAGMA_DECODE_STREAMS", "1") == "2"   # measured slower (3.07 vs 2.94 ms/step): off
 
     @staticmethod
     def _pack_adapter(mod):
@@ -289,6 +292,43 @@ class LMEngine:
         """Input of an adapter's down-projection: x, or LayerNorm(x) for an adapter built with add_layernorm."""
         return x if ln is None else ops.layernorm(x, ln[0], ln[1], ln[2], out=out)
 
+    def _adapter(self, G_dn, G_up, pair, act, ln, x_in, par, residuals, t=None, ln_out=None, out=None):
+        """Bottleneck adapter after or beside a projection:  out = up(act(down([LayerNorm] x_in))) [* par] + residuals.
+        ``pair`` = (down, up) packed; ``act`` the activation code (erf-GELU runs as its own pass over t); ``ln`` the adapter's
+        (gamma, beta, eps) or None; ``x_in`` the wrapped projection's output, or -- parallel adapters, ``par`` = their scale vector
+        -- the block's ln_1 output.  ``G_dn`` / ``G_up`` (x, w, **epilogue) launch the two GEMMs: the decode step passes its GEMV
+        (or tile GEMM) twice and its scratch buffers ``t`` / ``ln_out`` / ``out``; the prefill passes _linear under the
+        projections' fp8 names (a parallel up-projection stays on ops.gemm) and lets the GEMMs allocate."""
+        dn, up = pair
+        kw = {}
+        if par is not None:
+            kw["scale"], up = self._par_up(up, par)
+        t = self._act_fix(G_dn(self._ad_in(ln, x_in, out=ln_out), dn, out=t, act=self._epi_act(act)), act)
+        return G_up(t, up, out=out, residuals=residuals, **kw)
+
+    def _fold_pack(self, cls, w, b, gamma, beta, split=None):
+        """LayerNorm(gamma, beta) folded into [w; b] (ops.fold_layernorm), packed as ``cls`` (PackedLinear | PackedLinearW8).
+        ``split``: the bias of the output columns >= split goes to .bias_b (second segment of a split launch).  The e4m3 pack
+        takes the fold's column sums from its DEQUANTISED weights, so that  rstd*(acc*scale - mean*colsum)  stays exact for what
+        the kernel multiplies."""
+        w2, b2, cs = ops.fold_layernorm(w, b, gamma, beta)
+        lin = cls(w2, bias=b2 if split is None else b2[:split])
+        if split is not None:
+            lin.bias_b = b2[split:].contiguous()
+        lin.colsum = cs if cls is ops.PackedLinear else lin.dequant().sum(1).contiguous()
+        return lin
+
+    def _fold_dec_in(self, cls, ly):
+        """[q | k | v | fc_in] with ln_1 folded in: [3d+ff, d], bias zeros | b_fc (.bias over the qkv columns, .bias_b over fc_in)."""
+        a, mlp = ly._src
+        d3 = 3 * self.d
+        w = torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, mlp.c_fc.weight], dim=0)
+        b = torch.cat([torch.zeros(d3, device=self.device), mlp.c_fc.bias.detach().float()])
+        return self._fold_pack(cls, w, b, ly.ln_g, ly.ln_b, split=d3)
+
+    def _fold_head(self, cls):
+        return self._fold_pack(cls, self._lm_head.weight, self._lm_head.bias, self.lnf_g, self.lnf_b)
+
     def _ensure_decode_packs(self):
         """Decode operands with the LayerNorms folded in (frozen gamma/beta): per layer one
         fused [3d+ff, d] matrix W' = [Wqkv;Wfc]*gamma whose single weight-streaming launch
@@ -296,46 +336,57 @@ class LMEngine:
         GEMV instead of two); ln_f is folded into lm_head the same way."""
         if self.head_dec is not None:
             return
-        d3 = 3 * self.d
         for ly in self.layers:
-            a, mlp = ly._src
-            w = torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, mlp.c_fc.weight], dim=0)
-            b = torch.cat([torch.zeros(d3, device=self.device), mlp.c_fc.bias.detach().float()])
-            w2, b2, cs = ops.fold_layernorm(w, b, ly.ln_g, ly.ln_b)
-            lin = ops.PackedLinear(w2, bias=b2[:d3])
-            lin.bias_b, lin.colsum = b2[d3:].contiguous(), cs
-            ly.dec_in = lin
-            del w, w2
+            ly.dec_in = self._fold_dec_in(ops.PackedLinear, ly)
             self._fold_adapter_down(ly)
             if self.fold_dn in (1, 2):
                 self._ensure_out_up(ly)          # built HERE, never inside a token step (no allocation under hipGraph capture)
-        w2, b2, cs = ops.fold_layernorm(self._lm_head.weight, self._lm_head.bias, self.lnf_g, self.lnf_b)
-        self.head_dec = ops.PackedLinear(w2, bias=b2)
-        self.head_dec.colsum = cs
+        self.head_dec = self._fold_head(ops.PackedLinear)
+
+    def _block_kind(self, ly, wide=False, w8=False, fold_dn=0, group=True) -> str:
+        """Which launch sequence (_block_<kind>) the token step runs for this layer: "wide" | "fold2" | "fold1" | "grouped" | "v2" |
+        "generic" -- the ONE place that tells the block shapes apart (table: DESIGN.md, "The six block kinds").  A MAGMA_v1 block
+        (v1 below) is the 'normal' MLP adapter with a plain ReLU bottleneck -- what the folds are written for -- and every K a
+        multiple of 128; a fold that does not apply, and W8A16 always, falls to the four-launch "grouped" block."""
+        if wide:
+            return "wide"
+        if (not group or ly.mlp_adapter is None or ly.mlp_par is not None or ly.attn_par is not None or ly.mlp_ad_ln is not None
+                or ly.mlp_act == ops.MG_ACT_GELU_ERF):
+            return "generic"
+        dn, up = ly.mlp_adapter
+        k128 = all(p.Kp % 128 == 0 for p in (ly.fc_out, ly.out, dn))
+        if ly.attn_adapter is None:
+            if not k128:
+                return "generic"
+            v1 = ly.mlp_act == ops.MG_ACT_RELU and not (dn.N % 16 or (self.d + dn.N) % 128 or dn.K != self.d or up.K != dn.N
+                                                        or up.Kp != up.K)
+            if v1 and not w8 and fold_dn == 2:
+                return "fold2"
+            if v1 and not w8 and fold_dn == 1 and ly.fc_dn is not None:
+                return "fold1"
+            return "grouped"
+        dn_a, up_a = ly.attn_adapter
+        if ly.attn_ad_ln is not None or ly.attn_act == ops.MG_ACT_GELU_ERF:       # a pass of its own after the down-projection
+            return "generic"
+        cat = dn.N == up.K == up.Kp and dn_a.N == up_a.K == up_a.Kp and (up.K + up_a.K) % 128 == 0
+        return "v2" if cat and k128 and dn_a.Kp % 128 == 0 else "generic"
 
     def _v1_block(self, ly) -> bool:
-        """MAGMA_v1 block shape: mlp adapter of the 'normal' type only, every K a multiple of 128."""
-        if ly.mlp_adapter is None or ly.attn_adapter is not None or ly.mlp_par is not None:
-            return False
-        if ly.mlp_ad_ln is not None or ly.mlp_act != ops.MG_ACT_RELU:      # the folds are written for the plain ReLU bottleneck
-            return False
-        dn, up = ly.mlp_adapter
-        return not (dn.N % 16 or (self.d + dn.N) % 128 or ly.fc_out.Kp % 128 or dn.K != self.d or up.K != dn.N or up.Kp != up.K)
+        """MAGMA_v1 block shape (_block_kind): the blocks that have a [W_out | W_up] operand."""
+        return self._block_kind(ly, fold_dn=2) == "fold2"
 
     def _ensure_out_up(self, ly):
         """[W_out | W_up] (d rows over K = d + r, bias b_up) of a MAGMA_v1 block -- the operand of the ONE GEMM / GEMV that
         replaces out_proj and the adapter's up-projection (prefill / forward blocks and the decode step) -- or None where a
-        block does not have that shape.  Built with the decode operands (_ensure_decode_packs / repack_adapters) or on the first
-        prefill that wants it; dropped by repack_adapters (it contains W_up).  It is a SECOND copy of W_out (42 MB per block,
-        1.2 GB at 28 blocks): ly.out stays for the paths that still read it (fp8 modes, MAGMA_PREFILL_CAT=0 / MAGMA_DECODE_FOLD=0,
-        attention adapters)."""
-        if "out_up" not in ly.__dict__:
-            ly.out_up = None
-            if self._v1_block(ly):
-                a, _ = ly._src
-                up = ly.mlp_adapter[1]
-                w_up = ops.PackedLinear.untile(up.ft)[: up.N, : up.K]
-                ly.out_up = ops.PackedLinear(torch.cat([a.out_proj.weight.detach().to(BF16), w_up], dim=1), bias=up.bias)
+        block does not have that shape.  Built with the decode operands (_ensure_decode_packs / repack_adapters), when a token
+        step is planned (_ensure_decode_state) or on the first prefill that wants it; dropped by repack_adapters (it contains
+        W_up).  It is a SECOND copy of W_out (42 MB per block, 1.2 GB at 28 blocks): ly.out stays for the paths that still read
+        it (fp8 modes, MAGMA_PREFILL_CAT=0 / MAGMA_DECODE_FOLD=0, attention adapters)."""
+        if ly.out_up is None and self._v1_block(ly):
+            a, _ = ly._src
+            up = ly.mlp_adapter[1]
+            w_up = ops.PackedLinear.untile(up.ft)[: up.N, : up.K]
+            ly.out_up = ops.PackedLinear(torch.cat([a.out_proj.weight.detach().to(BF16), w_up], dim=1), bias=up.bias)
         return ly.out_up
 
     def _fold_adapter_down(self, ly):
@@ -352,39 +403,28 @@ class LMEngine:
         ly.fc_dn.bias_b = (w_dn @ b_fc + dn.bias).contiguous()
 
     def _ensure_decode_packs_w8(self):
-        """e4m3 copies of every decode operand (same LayerNorm folds; the fold's column sums are taken from the
-        DEQUANTISED weights so that  rstd*(acc*scale - mean*colsum)  stays exact for what the kernel multiplies)."""
-        if getattr(self, "head_w8", None) is not None:
+        """e4m3 copies of every decode operand (same LayerNorm folds, _fold_pack)."""
+        if self.head_w8 is not None:
             return
-        d3 = 3 * self.d
+        unpacked = lambda p: ops.PackedLinear.untile(p.ft)[: p.N, : p.K]  # noqa: E731
         for ly in self.layers:
             a, mlp = ly._src
-            w = torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, mlp.c_fc.weight], dim=0)
-            b = torch.cat([torch.zeros(d3, device=self.device), mlp.c_fc.bias.detach().float()])
-            w2, b2, _ = ops.fold_layernorm(w, b, ly.ln_g, ly.ln_b)
-            lin = ops.PackedLinearW8(w2, bias=b2[:d3])
-            lin.bias_b, lin.colsum = b2[d3:].contiguous(), lin.dequant().sum(1).contiguous()
             w8 = _Layer()
-            w8.dec_in = lin
+            w8.dec_in = self._fold_dec_in(ops.PackedLinearW8, ly)
             w8.out = ops.PackedLinearW8(a.out_proj.weight)
             w8.fc_out = ops.PackedLinearW8(mlp.c_proj.weight, mlp.c_proj.bias)
             w8.mlp_adapter = None
             if ly.mlp_adapter is not None:
                 # (the up-projection alone is only used by the MAGMA_v1 step; in MAGMA_v2 -- K = 512 -- it lives in up_cat below)
-                w8.mlp_adapter = tuple(ops.PackedLinearW8(ops.PackedLinear.untile(p.ft)[: p.N, : p.K], p.bias) if p.K % 1024 == 0 else None
-                                       for p in ly.mlp_adapter)
+                w8.mlp_adapter = tuple(ops.PackedLinearW8(unpacked(p), p.bias) if p.K % 1024 == 0 else None for p in ly.mlp_adapter)
             # MAGMA_v2 (attention AND mlp adapters): the attention adapter's down-projection and the concatenated up-projection
             w8.attn_adapter = w8.up_cat = None
             cat = self._adapter_up_cat(ly)
-            if cat is not None and ly.attn_par is None and ly.mlp_par is None and cat.K % 1024 == 0:
-                w8.attn_adapter = (ops.PackedLinearW8(ops.PackedLinear.untile(ly.attn_adapter[0].ft)[: ly.attn_adapter[0].N, : ly.attn_adapter[0].K],
-                                                      ly.attn_adapter[0].bias),)
-                w8.up_cat = ops.PackedLinearW8(ops.PackedLinear.untile(cat.ft)[: cat.N, : cat.K], cat.bias)
+            if cat is not None and cat.K % 1024 == 0:
+                w8.attn_adapter = (ops.PackedLinearW8(unpacked(ly.attn_adapter[0]), ly.attn_adapter[0].bias),)
+                w8.up_cat = ops.PackedLinearW8(unpacked(cat), cat.bias)
             ly.w8 = w8
-            del w, w2
-        w2, b2, _ = ops.fold_layernorm(self._lm_head.weight, self._lm_head.bias, self.lnf_g, self.lnf_b)
-        self.head_w8 = ops.PackedLinearW8(w2, bias=b2)
-        self.head_w8.colsum = self.head_w8.dequant().sum(1).contiguous()
+        self.head_w8 = self._fold_head(ops.PackedLinearW8)
 
     def repack_adapters(self, lm):
         """Refresh only the (trainable) adapter operands after optimizer steps; the
@@ -400,13 +440,16 @@ class LMEngine:
                 if par:
                     ly.mlp_par = torch.full((self.d,), blk.mlp.scale_value(), dtype=torch.float32, device=ly.mlp_par.device)
             ly.fp8 = {}
-            ly.__dict__.pop("up_cat", None)
-            ly.__dict__.pop("out_up", None)        # [W_out | W_up] contains the adapter weights: rebuilt on next use
-            ly.__dict__.pop("fc_dn", None)
-            if self.head_dec is not None:          # decode operands exist: rebuild the folded ones now, not inside the next token step
+            # [W_out | W_up], [W_up_mlp | W_up_attn] and the folded down-projection contain the adapter weights: what was built
+            # is rebuilt now, not inside the next token step (a planned step reads the fields, it does not build them)
+            had_out_up, had_up_cat = ly.out_up is not None, ly.up_cat is not None
+            ly.up_cat = ly.out_up = ly.fc_dn = None
+            if self.head_dec is not None:
                 self._fold_adapter_down(ly)
-                if self.fold_dn in (1, 2):
-                    self._ensure_out_up(ly)
+            if had_out_up or (self.head_dec is not None and self.fold_dn in (1, 2)):
+                self._ensure_out_up(ly)
+            if had_up_cat:
+                self._adapter_up_cat(ly)
 
     @staticmethod
     def _par_up(up, par):
@@ -421,32 +464,22 @@ class LMEngine:
         return par, sc
 
     def _adapter_up_cat(self, ly):
-        """[W_up_mlp | W_up_attn] along K (bias = sum) for blocks that carry both adapters, or None."""
-        if ly.mlp_adapter is None or ly.attn_adapter is None or ly.mlp_ad_ln is not None or ly.attn_ad_ln is not None:
-            return None
-        if ops.MG_ACT_GELU_ERF in (ly.mlp_act, ly.attn_act):       # its own pass after the down-projection: generic block
-            return None
-        cat = ly.__dict__.get("up_cat")
-        if cat is None:
-            (dn_m, up_m), (dn_a, up_a) = ly.mlp_adapter, ly.attn_adapter
-            ok = (dn_m.N == up_m.K == up_m.Kp and dn_a.N == up_a.K == up_a.Kp and (up_m.K + up_a.K) % 128 == 0
-                  and ly.fc_out.Kp % 128 == 0 and ly.out.Kp % 128 == 0 and dn_m.Kp % 128 == 0 and dn_a.Kp % 128 == 0)
-            if not ok:
-                ly.up_cat = False
-                return None
+        """[W_up_mlp | W_up_attn] along K (bias = sum) for blocks that carry both adapters (_block_kind "v2"), or None.  Built when
+        a token step is planned or with the W8A16 operands, never inside a step."""
+        if ly.up_cat is None and self._block_kind(ly) == "v2":
+            up_m, up_a = ly.mlp_adapter[1], ly.attn_adapter[1]
             w = torch.cat([ops.PackedLinear.untile(up_m.ft)[: up_m.N, : up_m.K], ops.PackedLinear.untile(up_a.ft)[: up_a.N, : up_a.K]], dim=1)
-            cat = ly.up_cat = ops.PackedLinear(w, bias=up_m.bias + up_a.bias)
-        return cat or None
+            ly.up_cat = ops.PackedLinear(w, bias=up_m.bias + up_a.bias)
+        return ly.up_cat
 
     # ---- fp8 operand path (config 5) ----------------------------------------------------------------
     def _fp8_weight(self, ly, name: str, lin):
         """e4m3 copy (per-output-channel scales) of a packed bf16 weight, made on first use."""
-        packs = ly.__dict__.setdefault("fp8", {})
         mx = self.fp8_scaling == "mx"
-        w8 = packs.get(name)
+        w8 = ly.fp8.get(name)
         if w8 is None or isinstance(w8, ops.PackedLinearMX) != mx:
             w = ops.PackedLinear.untile(lin.ft)[: lin.N, : lin.K] if lin.ft is not None else lin.rm[: lin.N, : lin.K]
-            w8 = packs[name] = (ops.PackedLinearMX if mx else ops.PackedLinearFP8)(w, lin.bias)
+            w8 = ly.fp8[name] = (ops.PackedLinearMX if mx else ops.PackedLinearFP8)(w, lin.bias)
         return w8
 
     def _quantize(self, x):
@@ -570,8 +603,7 @@ class LMEngine:
         # round trip (the attention output `a`) less per block; at M = 456 also one split-K fix-up less.  MAGMA_PREFILL_CAT=0: off.
         r_cat = 0
         if self.cat_up and not self.fp8_mode:
-            r_cat = max([ly.mlp_adapter[0].N for ly in self.layers if ly.mlp_adapter is not None and ly.attn_adapter is None
-                         and ly.mlp_par is None and self._ensure_out_up(ly) is not None] + [0])
+            r_cat = max([ly.mlp_adapter[0].N for ly in self.layers if self._ensure_out_up(ly) is not None] + [0])
         ctx_t = torch.empty(M, d + r_cat, dtype=BF16, device=dev)
         ctx = ctx_t[:, :d]
         hs = [x.view(B, S, d)] if want_hidden else None
@@ -601,7 +633,7 @@ class LMEngine:
             else:
                 ops.rotary_split(qkv, B, S, self.H, self.rot, self.sin_t, self.cos_t, q, kc, vc, pos0=0, vt=vt)
                 ops.attn_prefill(q, kc, vt, ctx, B, self.H, S, lse=None if lse_out is None else lse_out[li])
-            if r_cat and ly.__dict__.get("out_up") is not None and ly.mlp_adapter[0].N == r_cat:
+            if r_cat and ly.out_up is not None and ly.mlp_adapter[0].N == r_cat:
                 h = h_fused if h_fused is not None else self._linear(ly, "fc_in", ly.fc_in, ln, lnq, act=ops.MG_ACT_GELU_NEW)
                 m = ops.gemm(h, ly.fc_out)
                 ops.gemm(m, ly.mlp_adapter[0], out=ctx_t[:, d:], act=ops.MG_ACT_RELU)
@@ -609,24 +641,19 @@ class LMEngine:
                 if want_hidden:
                     hs.append(x.view(B, S, d))
                 continue
+            # x @ w^T under the projection's fp8 name; a parallel adapter reads ln_1's output, its up-projection stays on ops.gemm
+            L = lambda name: lambda t, w, **kw: self._linear(ly, name, w, t, **kw)  # noqa: E731
             a = self._linear(ly, "out", ly.out, ctx)
-            if ly.attn_adapter is not None and ly.attn_par is not None:      # parallel: adapter reads the attention INPUT
-                sc, up = self._par_up(ly.attn_adapter[1], ly.attn_par)
-                t = self._act_fix(self._linear(ly, "attn_dn", ly.attn_adapter[0], self._ad_in(ly.attn_ad_ln, ln), act=self._epi_act(ly.attn_act)), ly.attn_act)
-                a = ops.gemm(t, up, scale=sc, residuals=(a,))
-            elif ly.attn_adapter is not None:
-                t = self._act_fix(self._linear(ly, "attn_dn", ly.attn_adapter[0], self._ad_in(ly.attn_ad_ln, a), act=self._epi_act(ly.attn_act)), ly.attn_act)
-                a = self._linear(ly, "attn_up", ly.attn_adapter[1], t, residuals=(a,))
+            if ly.attn_adapter is not None:
+                par = ly.attn_par
+                a = self._adapter(L("attn_dn"), ops.gemm if par is not None else L("attn_up"), ly.attn_adapter, ly.attn_act,
+                                  ly.attn_ad_ln, ln if par is not None else a, par, (a,))
             h = h_fused if h_fused is not None else self._linear(ly, "fc_in", ly.fc_in, ln, lnq, act=ops.MG_ACT_GELU_NEW)
-            if ly.mlp_adapter is not None and ly.mlp_par is not None:        # parallel: adapter reads the MLP INPUT
-                sc, up = self._par_up(ly.mlp_adapter[1], ly.mlp_par)
+            if ly.mlp_adapter is not None:
+                par = ly.mlp_par
                 m = self._linear(ly, "fc_out", ly.fc_out, h)
-                t = self._act_fix(self._linear(ly, "mlp_dn", ly.mlp_adapter[0], self._ad_in(ly.mlp_ad_ln, ln), act=self._epi_act(ly.mlp_act)), ly.mlp_act)
-                x = ops.gemm(t, up, scale=sc, residuals=(m, a, x))
-            elif ly.mlp_adapter is not None:
-                m = self._linear(ly, "fc_out", ly.fc_out, h)
-                t = self._act_fix(self._linear(ly, "mlp_dn", ly.mlp_adapter[0], self._ad_in(ly.mlp_ad_ln, m), act=self._epi_act(ly.mlp_act)), ly.mlp_act)
-                x = self._linear(ly, "mlp_up", ly.mlp_adapter[1], t, residuals=(m, a, x))
+                x = self._adapter(L("mlp_dn"), ops.gemm if par is not None else L("mlp_up"), ly.mlp_adapter, ly.mlp_act,
+                                  ly.mlp_ad_ln, ln if par is not None else m, par, (m, a, x))
             else:
                 x = self._linear(ly, "fc_out", ly.fc_out, h, residuals=(a, x))
             if want_hidden:
@@ -778,7 +805,7 @@ class LMEngine:
         e = lambda *s, dt=BF16: torch.empty(*s, dtype=dt, device=dev)  # noqa: E731
         st.ids = torch.zeros(B, 1, dtype=torch.int64, device=dev)
         st.xa, st.xb = e(B, d), e(B, d)
-        st.ln, st.qkv, st.q = e(B, d), e(B, 3 * d), e(B, self.H, 1, 256)
+        st.ln, st.qkv = e(B, d), e(B, 3 * d)
         st.ctx, st.a, st.a2, st.h, st.m = e(B, d), e(B, d), e(B, d), e(B, ff), e(B, d)
         r_mlp = max([ly.mlp_adapter[0].N for ly in self.layers if ly.mlp_adapter] + [8])
         r_att = max([ly.attn_adapter[0].N for ly in self.layers if ly.attn_adapter] + [8])
@@ -852,156 +879,146 @@ class LMEngine:
                           clear=clear, clear_stride=16 if clear is not None else 1, pos_stride=cache.pos_stride)
         return tok
 
-    def check_decode(self, cache: KVCache):
-        """Kept for callers of earlier revisions (the in-launch hand-off experiments had a time-out flag to read here)."""
-        return None
-
     def _decode_step(self, cache: KVCache, st, mode=None, feed_back: bool = False):
         """Enqueue one token step for all B sequences (graph-capturable: no
-        allocation, no sync, position read from cache.d_pos on the device).
+        allocation, no sync, position read from cache.d_pos on the device): embedding, per layer the launch sequence of the
+        kind planned for it (st.kinds, _ensure_decode_state), the head, token selection.
         ``feed_back``: the input ids are the tokens the previous step selected (st.token, still on the device) -- the
         reference's loop feeds exactly those back (sampling.py:88-90) -- instead of ids copied in from the caller."""
         B = cache.B
-        ps = cache.pos_stride            # 1 on a ragged cache: every attention launch reads row b's position d_pos[b]
         ops.embedding(st.token.view(B, 1) if feed_back else st.ids, self.wte, st.xa.view(B, 1, self.d))
         x, xn = st.xa, st.xb
-        d3 = 3 * self.d
-        main = torch.cuda.current_stream()
-        side = self._side_stream if self.two_streams else None
-        w8_on = self.decode_w8
-        # B > 16 (the weight-streaming GEMV kernels take M <= 16): the same block, every projection through the tile GEMM
-        # on the prefill operands -- weights are still read once per step for the whole batch (reference sampling.py:43-121
-        # has no batch limit).  LayerNorm is a launch of its own there (the fold lives in the GEMV kernel).
-        wide = B > 16
-        G = ops.gemm if wide else ops.gemm_skinny
-        if wide and w8_on:
-            raise NotImplementedError("W8A16 decode covers batches of at most 16 sequences")
-        for li, ly in enumerate(self.layers):
-            src = ly.w8 if w8_on else ly                 # e4m3 or bf16 operands (same launches)
-            if wide:
-                ops.layernorm(x, ly.ln_g, ly.ln_b, self.eps, out=st.ln)
-                ops.gemm(st.ln, ly.qkv, out=st.qkv)
-                ops.gemm(st.ln, ly.fc_in, out=st.h, act=ops.MG_ACT_GELU_NEW)
-            else:
-                # ln_1 + qkv + fc_in(+gelu) in ONE weight-streaming launch
-                ops.gemm_skinny(x, src.dec_in, out=st.qkv, ln_fold=(src.dec_in.colsum, self.d, self.eps),
-                                split=(d3, st.h, ops.MG_ACT_GELU_NEW, src.dec_in.bias_b), variant=self._dec_in_variant)
-            # attention branch (latency-bound, 128 workgroups) runs on a second HIP stream
-            # underneath the MLP branch's weight streaming; both join at the adapter-up GEMV
-            par = ly.mlp_par is not None or ly.attn_par is not None
-            grouped = (not wide and self.group_launches and not par and ly.mlp_adapter is not None and ly.attn_adapter is None
-                       and ly.mlp_ad_ln is None and ly.mlp_act != ops.MG_ACT_GELU_ERF and ly.fc_out.Kp % 128 == 0 and ly.out.Kp % 128 == 0 and ly.mlp_adapter[0].Kp % 128 == 0)
-            out_up = self._ensure_out_up(ly) if (grouped and not w8_on and self.fold_dn in (1, 2)) else None
-            if out_up is not None and self.fold_dn == 2:
-                # MAGMA_DECODE_FOLD=2: attention || fc_out (context row lands in st.ctx_t), adapter-down alone, [W_out | W_up] GEMV
-                r = ly.mlp_adapter[0].N
-                ctx, t = st.ctx_t[:, : self.d], st.ctx_t[:, self.d: self.d + r]
-                ops.decode_attn_gemv(st.qkv, cache.k[li], cache.v[li], ctx, B, self.H, cache.d_pos, self.rot, self.sin_t, self.cos_t,
-                                     (st.h, ly.fc_out, st.m, {}), pos_stride=ps)
-                ops.gemm_skinny(st.m, ly.mlp_adapter[0], out=t, act=ops.MG_ACT_RELU, variant=self._dec_dn_variant)
-                ops.gemm_skinny(st.ctx_t[:, : self.d + r], ly.out_up, out=xn, residuals=(st.m, x), variant=self._dec_cat_variant)
-                x, xn = xn, x
-                continue
-            if out_up is not None and self.fold_dn == 1 and getattr(ly, "fc_dn", None) is not None:
-                # three launches (fold_dn).  launch 2: attention || [fc_out ; W_dn W_fc_out]: m and the adapter bottleneck t
-                # from ONE pass over h; the context row lands beside t in st.ctx_t
-                r = ly.mlp_adapter[0].N
-                ctx, t = st.ctx_t[:, : self.d], st.ctx_t[:, self.d: self.d + r]
-                ops.decode_attn_gemv(st.qkv, cache.k[li], cache.v[li], ctx, B, self.H, cache.d_pos, self.rot, self.sin_t, self.cos_t,
-                                     (st.h, ly.fc_dn, st.m, {"split": (self.d, t, ops.MG_ACT_RELU, ly.fc_dn.bias_b)}), pos_stride=ps)
-                # launch 3: x' = [W_out | W_up] [ctx ; t] + b_up + m + x
-                ops.gemm_skinny(st.ctx_t[:, : self.d + r], ly.out_up, out=xn, residuals=(st.m, x))
-                x, xn = xn, x
-                continue
-            if grouped and w8_on and (src.mlp_adapter is None or src.mlp_adapter[0] is None or src.mlp_adapter[1] is None):
-                # an adapter projection whose K is not a multiple of 1024 has no e4m3 operand (_ensure_decode_packs_w8)
-                raise NotImplementedError("W8A16 decode needs adapter projections with K % 1024 == 0 (downsample_factor 4 at d = 4096)")
-            if grouped:
-                # launch 2: attention workgroups + fc_out GEMV workgroups in one grid (they are independent
-                # branches of the parallel block; the latency-bound attention hides under the weight stream)
-                ops.decode_attn_gemv(st.qkv, cache.k[li], cache.v[li], st.ctx, B, self.H, cache.d_pos, self.rot,
-                                     self.sin_t, self.cos_t, (st.h, src.fc_out, st.m, {}), pos_stride=ps)
-                # launch 3: out_proj || adapter-down
-                t = st.t[:, : ly.mlp_adapter[0].N]
-                ops.gemm_skinny2((st.ctx, src.out, st.a, {}), (st.m, src.mlp_adapter[0], t, {"act": ly.mlp_act}))
-                # launch 4: adapter-up + the block's three residuals
-                ops.gemm_skinny(t, src.mlp_adapter[1], out=xn, residuals=(st.m, st.a, x))
-                x, xn = xn, x
-                continue
-            up_cat = self._adapter_up_cat(ly) if self.group_launches and not par and not wide else None
-            if w8_on and up_cat is not None and (src.up_cat is None or src.mlp_adapter[0] is None):
-                raise NotImplementedError("W8A16 decode of the MAGMA_v2 step needs adapter projections with K % 1024 == 0")
-            if up_cat is not None:
-                # MAGMA_v2 (attention AND mlp adapters): 5 launches.  x' = up_m(t) + up_a(ta) + m + a + x is ONE GEMV over
-                # the concatenated bottlenecks [t | ta] against [W_up_m | W_up_a] (the adapter outputs only ever appear summed).
-                r1 = ly.mlp_adapter[0].N
-                t, ta = st.tcat[:, :r1], st.tcat[:, r1: r1 + ly.attn_adapter[0].N]
-                if w8_on:
-                    up_cat = src.up_cat
-                ops.decode_attn_gemv(st.qkv, cache.k[li], cache.v[li], st.ctx, B, self.H, cache.d_pos, self.rot,
-                                     self.sin_t, self.cos_t, (st.h, src.fc_out, st.m, {}), pos_stride=ps)
-                ops.gemm_skinny2((st.ctx, src.out, st.a, {}), (st.m, src.mlp_adapter[0], t, {"act": ly.mlp_act}))
-                ops.gemm_skinny(st.a, src.attn_adapter[0], out=ta, act=ly.attn_act)
-                ops.gemm_skinny(st.tcat[:, : up_cat.Kp], up_cat, out=xn, residuals=(st.m, st.a, x))
-                x, xn = xn, x
-                continue
-            if side is not None:
-                side.wait_stream(main)
-                torch.cuda.set_stream(side)
-            ops.attn_decode_fused(st.qkv, cache.k[li], cache.v[li], st.ctx, B, self.H, cache.d_pos, self.rot,
-                                  self.sin_t, self.cos_t, pos_stride=ps)
-            # every other block (no MLP adapter, parallel adapters, adapters with a LayerNorm): out_proj and fc_out from src --
-            # e4m3 under W8A16 --, the small adapter projections in bf16
-            a = G(st.ctx, src.out, out=st.a)
-            if par and not wide:      # parallel adapters read ln_1(x): the one decode configuration that needs the LayerNorm as a tensor
-                ops.layernorm(x, ly.ln_g, ly.ln_b, self.eps, out=st.ln)
-            if ly.attn_adapter is not None:
-                ta = st.ta[:, : ly.attn_adapter[0].N]
-                if ly.attn_par is not None:
-                    sc, up = self._par_up(ly.attn_adapter[1], ly.attn_par)
-                    self._act_fix(G(self._ad_in(ly.attn_ad_ln, st.ln, out=st.ad_ln), ly.attn_adapter[0], out=ta, act=self._epi_act(ly.attn_act)), ly.attn_act)
-                    a = G(ta, up, out=st.a2, scale=sc, residuals=(a,))
-                else:
-                    self._act_fix(G(self._ad_in(ly.attn_ad_ln, a, out=st.ad_ln), ly.attn_adapter[0], out=ta, act=self._epi_act(ly.attn_act)), ly.attn_act)
-                    a = G(ta, ly.attn_adapter[1], out=st.a2, residuals=(a,))
-            if side is not None:
-                torch.cuda.set_stream(main)
-            if ly.mlp_adapter is not None:
-                G(st.h, src.fc_out, out=st.m)
-                t = st.t[:, : ly.mlp_adapter[0].N]
-                if side is not None:
-                    main.wait_stream(side)
-                if ly.mlp_par is not None:
-                    sc, up = self._par_up(ly.mlp_adapter[1], ly.mlp_par)
-                    self._act_fix(G(self._ad_in(ly.mlp_ad_ln, st.ln, out=st.ad_ln), ly.mlp_adapter[0], out=t, act=self._epi_act(ly.mlp_act)), ly.mlp_act)
-                    G(t, up, out=xn, scale=sc, residuals=(st.m, a, x))
-                else:
-                    self._act_fix(G(self._ad_in(ly.mlp_ad_ln, st.m, out=st.ad_ln), ly.mlp_adapter[0], out=t, act=self._epi_act(ly.mlp_act)), ly.mlp_act)
-                    G(t, ly.mlp_adapter[1], out=xn, residuals=(st.m, a, x))
-            else:
-                if side is not None:
-                    main.wait_stream(side)
-                G(st.h, src.fc_out, out=xn, residuals=(a, x))
+        for li, (ly, kind) in enumerate(zip(self.layers, st.kinds)):
+            getattr(self, "_block_" + kind)(cache, st, li, ly, ly.w8 if st.w8 else ly, x, xn)
             x, xn = xn, x
-        if wide:
+        if B > 16:
             ops.layernorm(x, self.lnf_g, self.lnf_b, self.eps, out=st.lnf)
             ops.gemm(st.lnf, self.head, out=st.logits)
         else:
-            head = self.head_w8 if w8_on else self.head_dec
+            head = self.head_w8 if st.w8 else self.head_dec
             ops.gemm_skinny(x, head, out=st.logits, ln_fold=(head.colsum, self.d, self.eps))
         if mode == "noselect":
-            ops.advance_pos(cache.d_pos, pos_stride=ps)   # teacher-forced position: nothing selected, nothing recorded
+            ops.advance_pos(cache.d_pos, pos_stride=cache.pos_stride)   # teacher-forced position: nothing selected, nothing recorded
         else:
             self.select_token(st.logits[:, : self.V], cache, mode, out=st.token, advance=True)
 
+    # One method per block kind (_block_kind): x -> xn for layer li.  ``src`` holds the block's weight-streaming operands: the
+    # layer itself, or its e4m3 copies (ly.w8) under W8A16 -- the same launches.  On a ragged cache (pos_stride 1) every
+    # attention launch reads row b's position d_pos[b].
+    def _dec_in(self, st, src, x):
+        # ln_1 + qkv + fc_in(+gelu) in ONE weight-streaming launch
+        ops.gemm_skinny(x, src.dec_in, out=st.qkv, ln_fold=(src.dec_in.colsum, self.d, self.eps),
+                        split=(3 * self.d, st.h, ops.MG_ACT_GELU_NEW, src.dec_in.bias_b), variant=self._dec_in_variant)
+
+    def _attn_gemv(self, cache, st, li, ctx, gemv):
+        # attention workgroups + one GEMV's workgroups in one grid (they are independent branches of the parallel block; the
+        # latency-bound attention hides under the weight stream)
+        ops.decode_attn_gemv(st.qkv, cache.k[li], cache.v[li], ctx, cache.B, self.H, cache.d_pos, self.rot, self.sin_t, self.cos_t,
+                             gemv, pos_stride=cache.pos_stride)
+
+    def _block_fold2(self, cache, st, li, ly, src, x, xn):
+        # MAGMA_DECODE_FOLD=2: attention || fc_out (context row lands in st.ctx_t), adapter-down alone, [W_out | W_up] GEMV
+        r = ly.mlp_adapter[0].N
+        ctx, t = st.ctx_t[:, : self.d], st.ctx_t[:, self.d: self.d + r]
+        self._dec_in(st, ly, x)
+        self._attn_gemv(cache, st, li, ctx, (st.h, ly.fc_out, st.m, {}))
+        ops.gemm_skinny(st.m, ly.mlp_adapter[0], out=t, act=ops.MG_ACT_RELU, variant=self._dec_dn_variant)
+        ops.gemm_skinny(st.ctx_t[:, : self.d + r], ly.out_up, out=xn, residuals=(st.m, x), variant=self._dec_cat_variant)
+
+    def _block_fold1(self, cache, st, li, ly, src, x, xn):
+        # three launches (fold_dn).  launch 2: attention || [fc_out ; W_dn W_fc_out]: m and the adapter bottleneck t
+        # from ONE pass over h; the context row lands beside t in st.ctx_t.  launch 3: x' = [W_out | W_up] [ctx ; t] + b_up + m + x
+        r = ly.mlp_adapter[0].N
+        ctx, t = st.ctx_t[:, : self.d], st.ctx_t[:, self.d: self.d + r]
+        self._dec_in(st, ly, x)
+        self._attn_gemv(cache, st, li, ctx, (st.h, ly.fc_dn, st.m, {"split": (self.d, t, ops.MG_ACT_RELU, ly.fc_dn.bias_b)}))
+        ops.gemm_skinny(st.ctx_t[:, : self.d + r], ly.out_up, out=xn, residuals=(st.m, x))
+
+    def _block_grouped(self, cache, st, li, ly, src, x, xn):
+        # four launches: [ln_1+qkv+fc_in] -> [attention || fc_out] -> [out_proj || adapter-down] -> [adapter-up + the block's
+        # three residuals]
+        t = st.t[:, : ly.mlp_adapter[0].N]
+        self._dec_in(st, src, x)
+        self._attn_gemv(cache, st, li, st.ctx, (st.h, src.fc_out, st.m, {}))
+        ops.gemm_skinny2((st.ctx, src.out, st.a, {}), (st.m, src.mlp_adapter[0], t, {"act": ly.mlp_act}))
+        ops.gemm_skinny(t, src.mlp_adapter[1], out=xn, residuals=(st.m, st.a, x))
+
+    def _block_v2(self, cache, st, li, ly, src, x, xn):
+        # MAGMA_v2 (attention AND mlp adapters): 5 launches.  x' = up_m(t) + up_a(ta) + m + a + x is ONE GEMV over
+        # the concatenated bottlenecks [t | ta] against [W_up_m | W_up_a] (the adapter outputs only ever appear summed)
+        r1 = ly.mlp_adapter[0].N
+        t, ta = st.tcat[:, :r1], st.tcat[:, r1: r1 + ly.attn_adapter[0].N]
+        self._dec_in(st, src, x)
+        self._attn_gemv(cache, st, li, st.ctx, (st.h, src.fc_out, st.m, {}))
+        ops.gemm_skinny2((st.ctx, src.out, st.a, {}), (st.m, src.mlp_adapter[0], t, {"act": ly.mlp_act}))
+        ops.gemm_skinny(st.a, src.attn_adapter[0], out=ta, act=ly.attn_act)
+        ops.gemm_skinny(st.tcat[:, : src.up_cat.Kp], src.up_cat, out=xn, residuals=(st.m, st.a, x))
+
+    def _block_generic(self, cache, st, li, ly, src, x, xn, wide=False):
+        # every other block (no MLP adapter, parallel adapters, adapters with a LayerNorm or erf-GELU): attention alone, then
+        # out_proj and fc_out from src -- e4m3 under W8A16 --, the small adapter projections in bf16 (_adapter).  ``wide``:
+        # called from _block_wide, which has made ln_1, qkv and h
+        G = ops.gemm if wide else ops.gemm_skinny
+        if not wide:
+            self._dec_in(st, src, x)
+        ops.attn_decode_fused(st.qkv, cache.k[li], cache.v[li], st.ctx, cache.B, self.H, cache.d_pos, self.rot,
+                              self.sin_t, self.cos_t, pos_stride=cache.pos_stride)
+        a = G(st.ctx, src.out, out=st.a)
+        par = ly.mlp_par is not None or ly.attn_par is not None
+        if par and not wide:      # parallel adapters read ln_1(x): the one GEMV-step configuration that needs the LayerNorm as a tensor
+            ops.layernorm(x, ly.ln_g, ly.ln_b, self.eps, out=st.ln)
+        if ly.attn_adapter is not None:
+            a = self._adapter(G, G, ly.attn_adapter, ly.attn_act, ly.attn_ad_ln, st.ln if ly.attn_par is not None else a, ly.attn_par,
+                              (a,), t=st.ta[:, : ly.attn_adapter[0].N], ln_out=st.ad_ln, out=st.a2)
+        if ly.mlp_adapter is not None:
+            G(st.h, src.fc_out, out=st.m)
+            self._adapter(G, G, ly.mlp_adapter, ly.mlp_act, ly.mlp_ad_ln, st.ln if ly.mlp_par is not None else st.m, ly.mlp_par,
+                          (st.m, a, x), t=st.t[:, : ly.mlp_adapter[0].N], ln_out=st.ad_ln, out=xn)
+        else:
+            G(st.h, src.fc_out, out=xn, residuals=(a, x))
+
+    def _block_wide(self, cache, st, li, ly, src, x, xn):
+        # B > 16 (the weight-streaming GEMV kernels take M <= 16): the generic block, every projection through the tile GEMM
+        # on the prefill operands -- weights are still read once per step for the whole batch (reference sampling.py:43-121
+        # has no batch limit).  LayerNorm is a launch of its own there (the fold lives in the GEMV kernel)
+        ops.layernorm(x, ly.ln_g, ly.ln_b, self.eps, out=st.ln)
+        ops.gemm(st.ln, ly.qkv, out=st.qkv)
+        ops.gemm(st.ln, ly.fc_in, out=st.h, act=ops.MG_ACT_GELU_NEW)
+        self._block_generic(cache, st, li, ly, ly, x, xn, wide=True)
+
+    def _plan_decode(self, B: int):
+        """(kind of every layer's block, what decode() refuses this plan with | None) for a cache of B rows under the engine's
+        current switches; builds the operands the kinds read, so that no token step allocates."""
+        w8 = self.decode_w8
+        kinds = [self._block_kind(ly, B > 16, w8, self.fold_dn, self.group_launches) for ly in self.layers]
+        if w8 and B > 16:
+            return kinds, "W8A16 decode covers batches of at most 16 sequences"
+        for ly, kind in zip(self.layers, kinds):
+            if kind in ("fold1", "fold2"):
+                self._ensure_out_up(ly)
+            if kind == "v2":
+                self._adapter_up_cat(ly)
+            # an adapter projection whose K is not a multiple of 1024 has no e4m3 operand (_ensure_decode_packs_w8)
+            if w8 and kind == "grouped" and any(p is None for p in ly.w8.mlp_adapter):
+                return kinds, "W8A16 decode needs adapter projections with K % 1024 == 0 (downsample_factor 4 at d = 4096)"
+            if w8 and kind == "v2" and (ly.w8.up_cat is None or ly.w8.mlp_adapter[0] is None):
+                return kinds, "W8A16 decode of the MAGMA_v2 step needs adapter projections with K % 1024 == 0"
+        return kinds, None
+
     def _ensure_decode_state(self, cache: KVCache):
+        """The cache's decode state: scratch buffers, captured graphs and the plan of the token step (st.w8, st.kinds, st.refusal),
+        fixed when the state is created -- the eager step and every graph captured on this cache run the same launches, whatever
+        is written to the engine's switches afterwards."""
         st = cache.decode_state
         if st is None:
             if cache.B <= 16:           # larger batches run the tile GEMM on the prefill operands (no LayerNorm-folded packs)
                 self._ensure_decode_packs()
             if self.decode_w8:
                 self._ensure_decode_packs_w8()
-            st = cache.decode_state = self._alloc_decode_state(cache)
+            st = self._alloc_decode_state(cache)
+            st.w8 = self.decode_w8
+            st.kinds, st.refusal = self._plan_decode(cache.B)
+            cache.decode_state = st
         return st
 
     def decode(self, input_ids: Optional[torch.Tensor], cache: KVCache, use_graph: bool = True, sampling=None, select: bool = True,
@@ -1023,6 +1040,8 @@ class LMEngine:
                               "launches and the captured hipGraph of the B <= 16 step do not apply, and W8A16 decode is refused",
                               RuntimeWarning, stacklevel=2)
         st = self._ensure_decode_state(cache)
+        if st.refusal is not None:      # before anything of the step is enqueued
+            raise NotImplementedError(st.refusal)
         feed_back = input_ids is None
         if not feed_back:
             st.ids.copy_(input_ids.reshape(cache.B, 1))

@@ -340,10 +340,8 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
         out.fill_(eos_token)
         out.masked_fill_(torch.arange(s + max_steps, device=dev)[None, :] < lens, model.image_token)
         out.scatter_(1, lens + torch.arange(n_gen, device=dev)[None, :], past.history[:, :n_gen])
-        model.lm.engine.check_decode(past)
     elif on_device:          # one copy of the token history the bookkeeping kernel kept
         out[:, s:n] = past.history[:, : n - s]
-        model.lm.engine.check_decode(past)
     out = out[:, :n]
     if continuing:      # the cache keeps the conversation (a continued one too: it was advanced in place and stays continuable)
         if past_key_values is None:
