@@ -503,6 +503,13 @@ int mg_head_transpose_bf16(const mg_bf16* src, int64_t sb, int64_t ss, int64_t s
 int mg_colsum_f32(const mg_bf16* x, int64_t ldx, const mg_bf16* y, int64_t ldy, float* out, int32_t M,
                   int32_t N, void* stream);
 
+/* The same sums without atomics: one partial per 256 rows goes to `parts` (fp32 [mg_colsum_det_parts(M), N], contents
+ * ignored on entry) and a second launch adds the partials to out in row order, so the result is the same bits in every run.
+ * For sums that feed a rounding decision (the batch-statistics BatchNorm). */
+int64_t mg_colsum_det_parts(int32_t M);
+int mg_colsum_det_f32(const mg_bf16* x, int64_t ldx, const mg_bf16* y, int64_t ldy, float* out, float* parts, int32_t M,
+                      int32_t N, void* stream);
+
 /* LayerNorm input gradient (+ optional residual add, optional xhat output).         */
 int mg_layernorm_bwd_bf16(const mg_bf16* dy, int64_t lddy, const mg_bf16* x, int64_t ldx, const float* gamma,
                           const mg_bf16* res, int64_t ldr, mg_bf16* dx, int64_t lddx, mg_bf16* xhat,
@@ -621,7 +628,7 @@ int mg_im2col_t_bf16(const mg_bf16* x, mg_bf16* out, int64_t ldo, int32_t B, int
 
 /* batch-statistics BatchNorm of the CLIP trunk in training (the reference's tower runs in train mode after its
  * first eval phase, reference train.py:164,182).  z = raw conv output [M, C] bf16 (M = B*H*W); sum / sumsq = per-channel sums
- * of z and z*z (mg_colsum_f32).  fold: scale = gamma * rstd, shift = beta - mean * scale, and running_mean / running_var
+ * of z and z*z (mg_colsum_det_f32: reproducible, they feed bf16 roundings).  fold: scale = gamma * rstd, shift = beta - mean * scale, and running_mean / running_var
  * (may be NULL) updated like nn.BatchNorm2d (momentum, unbiased variance).  apply: y = [relu](z*scale + shift [+ res]).
  * bwd_dz: dz = gamma * rstd * (g - dbeta/M - xhat * dgamma/M) with xhat = (z - mean) * rstd, dgamma / dbeta = this call's
  * per-channel sums of g * xhat and g.                                                                                    */

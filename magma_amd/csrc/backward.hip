@@ -161,7 +161,11 @@ __global__ __launch_bounds__(256) void head_transpose_kernel(const mg_bf16* __re
 // ---------------------------------------------------------------------------
 // column sums: out[n] += sum_m x[m][n] * (y ? y[m][n] : 1)   (fp32 atomics)
 // grid (ceil(N/512), ceil(M/rows_per_block))
+// PARTIAL: no atomics -- workgroup (., by) stores its sums to out[by * N + n] (a [gridDim.y, N] workspace) and
+// colsum_finish_kernel adds them up in row order, so the result does not depend on the order the workgroups retire in
+// (the batch-statistics BatchNorm: its statistics feed a bf16 rounding, and more than two atomic partials do not commute).
 // ---------------------------------------------------------------------------
+template <bool PARTIAL>
 __global__ __launch_bounds__(256) void colsum_kernel(const mg_bf16* __restrict__ x, int64_t ldx,
                                                      const mg_bf16* __restrict__ y, int64_t ldy,
                                                      float* __restrict__ out, int M, int N, int rows_per_block) {
@@ -189,8 +193,21 @@ __global__ __launch_bounds__(256) void colsum_kernel(const mg_bf16* __restrict__
   if (rl == 0 && n < N) {
 #pragma unroll
     for (int j = 0; j < 8; ++j)
-      if (n + j < N) atomicAdd(out + n + j, red[0][cl][j] + red[1][cl][j] + red[2][cl][j] + red[3][cl][j]);
+      if (n + j < N) {
+        const float s = red[0][cl][j] + red[1][cl][j] + red[2][cl][j] + red[3][cl][j];
+        if (PARTIAL) out[(int64_t)blockIdx.y * N + n + j] = s;
+        else atomicAdd(out + n + j, s);
+      }
   }
+}
+
+// out[n] += part[0][n] + part[1][n] + ... in that order; grid ceil(N/256)
+__global__ __launch_bounds__(256) void colsum_finish_kernel(const float* __restrict__ part, int nparts, float* __restrict__ out, int N) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  float s = 0.f;
+  for (int b = 0; b < nparts; ++b) s += part[(int64_t)b * N + n];
+  out[n] += s;
 }
 
 // ---------------------------------------------------------------------------
@@ -783,7 +800,21 @@ extern "C" int mg_colsum_f32(const mg_bf16* x, int64_t ldx, const mg_bf16* y, in
   if (M <= 0 || N <= 0 || (N & 7)) MG_FAIL(MG_ERR_SHAPE, "mg_colsum_f32: N must be a positive multiple of 8");
   if (!x || !out || !MG_ALIGNED16(x) || !MG_ALIGNED16(y) || (ldx & 7) || (y && (ldy & 7))) MG_FAIL(MG_ERR_ALIGN, "mg_colsum_f32: 16-byte alignment required");
   const int rpb = 256;
-  hipLaunchKernelGGL(colsum_kernel, dim3((N + 511) / 512, (M + rpb - 1) / rpb), dim3(256), 0, (hipStream_t)stream, x, ldx, y, ldy, out, M, N, rpb);
+  hipLaunchKernelGGL(colsum_kernel<false>, dim3((N + 511) / 512, (M + rpb - 1) / rpb), dim3(256), 0, (hipStream_t)stream, x, ldx, y, ldy, out, M, N, rpb);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int64_t mg_colsum_det_parts(int32_t M) { return M > 0 ? (M + 255) / 256 : 0; }
+
+extern "C" int mg_colsum_det_f32(const mg_bf16* x, int64_t ldx, const mg_bf16* y, int64_t ldy, float* out, float* parts,
+                                 int32_t M, int32_t N, void* stream) {
+  if (M <= 0 || N <= 0 || (N & 7)) MG_FAIL(MG_ERR_SHAPE, "mg_colsum_det_f32: N must be a positive multiple of 8");
+  if (!x || !out || !parts || !MG_ALIGNED16(x) || !MG_ALIGNED16(y) || (ldx & 7) || (y && (ldy & 7))) MG_FAIL(MG_ERR_ALIGN, "mg_colsum_det_f32: 16-byte alignment required");
+  const int rpb = 256, nparts = (M + rpb - 1) / rpb;     // == mg_colsum_det_parts(M)
+  hipLaunchKernelGGL(colsum_kernel<true>, dim3((N + 511) / 512, nparts), dim3(256), 0, (hipStream_t)stream, x, ldx, y, ldy, parts, M, N, rpb);
+  MG_CHECK_LAUNCH();
+  hipLaunchKernelGGL(colsum_finish_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, parts, nparts, out, N);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }

@@ -145,6 +145,8 @@ SYMBOLS = {
     "mg_transpose_colsum_bf16": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp]),
     "mg_head_transpose_bf16": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp]),
     "mg_colsum_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp]),
+    "mg_colsum_det_parts": (C.c_int64, [_i32]),
+    "mg_colsum_det_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _vp]),
     "mg_layernorm_bwd_bf16": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _f32, _vp]),
     "mg_ce_bwd_bf16": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "mg_rotary_merge_bwd_bf16": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

@@ -847,10 +847,16 @@ def head_transpose(src: torch.Tensor, B: int, H: int, S: int, sb: int, ss: int, 
     return out
 
 
-def colsum(x: torch.Tensor, out: torch.Tensor, y: Optional[torch.Tensor] = None):
-    """out[n] += sum_m x[m,n] * (y[m,n] if y else 1); out fp32 [N]."""
+def colsum(x: torch.Tensor, out: torch.Tensor, y: Optional[torch.Tensor] = None, deterministic: bool = False):
+    """out[n] += sum_m x[m,n] * (y[m,n] if y else 1); out fp32 [N].  deterministic: partials per 256 rows added in row order by a
+    second launch instead of fp32 atomics -- the same bits in every run (for sums that feed a rounding decision)."""
     _need_gpu(x, out)
     assert x.dtype == BF16 and x.ndim == 2 and x.stride(1) == 1 and out.dtype == torch.float32
+    if deterministic:
+        parts = torch.empty(L.load().mg_colsum_det_parts(x.shape[0]), x.shape[1], dtype=torch.float32, device=x.device)
+        check(L.load().mg_colsum_det_f32(x.data_ptr(), x.stride(0), _p(y), 0 if y is None else y.stride(0), out.data_ptr(),
+                                         parts.data_ptr(), x.shape[0], x.shape[1], _stream()), "mg_colsum_det_f32")
+        return out
     check(L.load().mg_colsum_f32(x.data_ptr(), x.stride(0), _p(y), 0 if y is None else y.stride(0), out.data_ptr(),
                                  x.shape[0], x.shape[1], _stream()), "mg_colsum_f32")
     return out

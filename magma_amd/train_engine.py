@@ -1346,8 +1346,8 @@ class MagmaEngine:
             z = ops.gemm(a, wop, conv=convarg, layout="rm", use_bias=False)
             M, C = z.shape
             sums = torch.zeros(2, C, dtype=F32, device=z.device)
-            ops.colsum(z, sums[0])
-            ops.colsum(z, sums[1], z)
+            ops.colsum(z, sums[0], deterministic=True)
+            ops.colsum(z, sums[1], z, deterministic=True)
             st = self._bn_stats[id(bn)]
             mom = 0.1 if bn.momentum is None else float(bn.momentum)
             scale, shift, mean, rstd = ops.bn_batch_fold(sums[0], sums[1], gamma, beta, M, bn.eps, mom, st[0], st[1])
@@ -1425,8 +1425,8 @@ class MagmaEngine:
             # dbeta = sum g, dgamma = sum g * xhat = rstd * (sum g*z - mean * sum g); then the gradient wrt the raw conv output
             C = g.shape[1]
             sums = torch.zeros(2, C, dtype=F32, device=g.device)
-            ops.colsum(g, sums[0])
-            ops.colsum(g, sums[1], rec["z"])
+            ops.colsum(g, sums[0], deterministic=True)
+            ops.colsum(g, sums[1], rec["z"], deterministic=True)
             dbeta = sums[0]
             dgamma = rec["rstd"] * (sums[1] - rec["mean"] * dbeta)
             self.grad_of(bn.weight).add_(dgamma)

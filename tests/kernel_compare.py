@@ -797,3 +797,80 @@ def adamw_reference(p0, m0, v0, g, norm_sq, lr, b1, b2, eps, wd, step: int, max_
     f32 = torch.float32
     return {"m": (m_r, rounded(m_r, d_m, f32)), "v": (v_r, rounded(v_r, d_v, f32)), "p": (p_r, rounded(p_r, d_p, f32)),
             "p_bf16": (p_r, rounded(p_r, d_p + U_F32 * p_r.abs(), torch.bfloat16))}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# gradient accumulation: a window against the sum of its micro-steps
+# ---------------------------------------------------------------------------------------------------------------------------
+ACC_ASSOC_ROUNDINGS = 8.0        # first term: 8 u32 of the magnitude sum
+ACC_NOISE_FACTOR = 4.0           # second term: one repeat is ONE sample of the run-to-run noise
+ACC_NOISE_FLOOR = 1e-5           # third term: the suite's figure for atomic noise (test_per_block_recompute_is_exact, test_dp_nccl_gpu.py)
+ACC_VISIBLE = 100.0              # every part must be at least this many bounds large somewhere
+
+
+def accumulation_reference(parts) -> torch.Tensor:
+    """sum_i g_i in fp64: what a gradient buffer holds after a window whose micro-batches give g_1 .. g_N taken alone."""
+    ref = f64(parts[0]).clone()
+    for p in parts[1:]:
+        ref += f64(p)
+    return ref
+
+
+def accumulation_bound(parts, repeats) -> torch.Tensor:
+    """Per-element bound on |G - sum_i g_i| for ONE trainable tensor whose window gradient G accumulated N micro-steps.
+    parts = [g_1 .. g_N]: the fp32 gradients of the micro-batches taken alone (each into a zeroed buffer); repeats: a second run
+    of the same, [g_1' .. g_N'].
+
+        8 u32 sum_i |g_i|  +  4 sum_i |g_i - g_i'|  +  1e-5 rms(sum_i g_i)
+
+      * fp32 addition in another association (N - 1 additions of values the parts already rounded; every producer adds its
+        K-term dot product to what the buffer holds instead of to zero), plus the one extra rounding an fma-style
+        ``dst += s * src`` can have;
+      * the run-to-run noise of the fp32 atomics behind the column sums, MEASURED reference against reference, never against the
+        window; one repeat is a single sample of it, hence the factor;
+      * a floor for the elements whose two samples happened to agree: the suite's own figure for that noise, as a fraction of the
+        tensor's rms.
+    FLOOR keeps the bound of a tensor that is exactly zero in every part positive (0 / 0 would read as a failure)."""
+    assert len(parts) >= 1 and len(repeats) == len(parts)
+    mag = torch.zeros_like(f64(parts[0]))
+    noise = torch.zeros_like(mag)
+    for p, r in zip(parts, repeats):
+        mag += f64(p).abs()
+        noise += (f64(p) - f64(r)).abs()
+    ref = accumulation_reference(parts)
+    rms = float(ref.pow(2).mean().sqrt()) if ref.numel() else 0.0
+    return ACC_ASSOC_ROUNDINGS * U_F32 * mag + ACC_NOISE_FACTOR * noise + ACC_NOISE_FLOOR * rms + FLOOR
+
+
+def accumulation_conditions(parts, repeats, what: str = ""):
+    """The two conditions that hold BEFORE a window is looked at -> (ref, bound, self_ratio, invisible):
+
+      1. reference within the bound: sum_i g_i' passes against sum_i g_i (asserted here; a failure says the bound is too tight
+         for this tensor's noise, it does not blame the engine);
+      2. every part is visible: max over the elements of |g_i| / bound >= ACC_VISIBLE for every i -- leaving part i out, or adding
+         it twice, is then at least 100 bounds somewhere.  ``invisible`` lists (i, ratio, identically_zero) of the parts that
+         are not; the caller decides (only an identically zero part may be excused)."""
+    ref, bound = accumulation_reference(parts), accumulation_bound(parts, repeats)
+    again = accumulation_reference(repeats)
+    r = ratios(again, ref, bound)
+    self_ratio = float(r.max()) if r.numel() else 0.0
+    assert self_ratio <= 1.0, (f"{what}: the REFERENCE does not meet its own bound (a repeat of the parts against the first run): the "
+                               f"bound is too tight for this tensor's run-to-run noise; {describe_failure(again, ref, bound, r)}")
+    invisible = []
+    for i, p in enumerate(parts):
+        vis = float((f64(p).abs() / bound).max()) if ref.numel() else 0.0
+        if vis < ACC_VISIBLE:
+            invisible.append((i, vis, not bool(f64(p).any()) and not bool(f64(repeats[i]).any())))
+    return ref, bound, self_ratio, invisible
+
+
+def assert_accumulation(got, parts, repeats, what: str = "") -> dict:
+    """One tensor of a window: both conditions, then got against sum_i g_i per element (assert_elementwise's report: worst
+    ratio, index, count, bounding box).  A part that is not visible fails unless it is identically zero in both runs.
+    -> {"worst", "self", "zero_parts"}."""
+    ref, bound, self_ratio, invisible = accumulation_conditions(parts, repeats, what)
+    bad = [(i, f"{v:.3g}") for i, v, zero in invisible if not zero]
+    assert not bad, (f"{what}: part(s) {bad} (index, max |g_i| / bound) are below {ACC_VISIBLE:g}: a window that dropped them would "
+                     f"pass.  Choose inputs under which every micro-batch moves this tensor; do not relax the condition")
+    worst = assert_elementwise(got, ref, bound, what)
+    return {"worst": worst, "self": self_ratio, "zero_parts": [i for i, _, zero in invisible if zero]}

@@ -57,6 +57,31 @@ def test_colsum(dev):
     kcmp.assert_elementwise(out, s2, kcmp.rounded(s2, kcmp.gamma(1000 + 9) * m2, torch.float32), "colsum of x * y, accumulated")
 
 
+@pytest.mark.parametrize("M,N", [(8, 64), (300, 40), (2085, 520)])
+def test_colsum_deterministic(dev, M, N):
+    """The two-stage form the batch-statistics BatchNorm uses: 1, 2 and 9 partials of 256 rows (the last one short), one and two
+    column stripes of 512.  Same fp64 reference and the same bound as test_colsum (M terms in some order, the accumulation, the
+    partials' extra additions); it accumulates into what ``out`` holds, and -- its point -- repeated calls give the same bits
+    whatever order the workgroups retire in (the atomic form does not from three partials on)."""
+    from magma_amd import ops
+    x = rnd(M, N, dev=dev, seed=40).to(BF16)
+    y = rnd(M, N, dev=dev, seed=41).to(BF16)
+    start = rnd(N, dev=dev, seed=42)
+    s1, m1 = x.double().sum(0), x.double().abs().sum(0)
+    out = torch.zeros(N, device=dev)
+    ops.colsum(x, out, deterministic=True)
+    kcmp.assert_elementwise(out, s1, kcmp.rounded(s1, kcmp.gamma(M + 9) * m1, torch.float32), f"deterministic colsum {M}x{N}")
+    xy = x.double() * y.double()
+    s2, m2 = start.double() + xy.sum(0), start.double().abs() + xy.abs().sum(0)
+    runs = []
+    for _ in range(8):
+        out = start.clone()
+        ops.colsum(x, out, y, deterministic=True)
+        runs.append(out)
+    kcmp.assert_elementwise(runs[0], s2, kcmp.rounded(s2, kcmp.gamma(M + 9) * m2, torch.float32), f"deterministic colsum of x * y {M}x{N}, accumulated")
+    assert all(torch.equal(r, runs[0]) for r in runs[1:])
+
+
 @pytest.mark.parametrize("rows,d", [(9, 4096), (33, 512)])
 def test_layernorm_bwd(dev, rows, d):
     from magma_amd import ops

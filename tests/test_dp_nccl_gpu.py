@@ -6,6 +6,8 @@ import pytest
 import torch
 import torch.distributed as dist
 
+import accumulation_common as acc
+
 pytestmark = pytest.mark.gpu
 
 
@@ -56,6 +58,60 @@ def test_overlapped_allreduce_single_rank(dev, backend, monkeypatch):
         assert float((a - b).norm() / (a.norm() + 1e-20)) < 1e-5
     for a, b in zip(m0, m1):
         assert float((a - b).norm() / (a.norm() + 1e-20)) < 1e-5
+
+
+def _window_engine(dev, with_group):
+    from magma_amd.testing import build_reduced_magma
+    from magma_amd.train_engine import MagmaEngine
+    torch.manual_seed(0)
+    model = build_reduced_magma(dev, n_positions=128)
+    model.config.gradient_accumulation_steps = 3
+    eng = MagmaEngine(model, truncate=True)
+    assert eng._dist == with_group and eng.gas == 3
+    eng.train()
+    # the micro-batches of tests/test_grad_accumulation_gpu.py: truncated lengths 64, 128, 64
+    return eng, acc.micro_batches(5, model.eos_token, model.seq_len, 4, 512)
+
+
+@pytest.mark.parametrize("backend", ["torch", "rccl"])
+def test_overlapped_allreduce_waits_for_the_window_single_rank(dev, backend, monkeypatch):
+    """gradient_accumulation_steps = 3 under a 1-rank group: no bucket leaves before the window's last backward (_is_boundary);
+    what the exchange returns is bf16 of the COMPLETE window's gradient, element for element (SUM over one rank is the identity, so
+    a bucket cast before a later micro-step or a later kernel of the same backward added to it would differ); and that gradient is
+    the sum of the micro-batches' gradients taken alone without a group (kernel_compare.accumulation_bound)."""
+    import kernel_compare as kc
+    eng, batches = _window_engine(dev, False)
+    runs = [acc.take_parts(eng, batches) for _ in range(2)]         # parts and their repeat, without a group
+    names = {id(p): n for n, p in eng.module.named_parameters()}
+    order = [[names[id(p)] for p in grp.params] for grp in eng.groups]
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    os.environ.setdefault("MASTER_PORT", "29541")
+    monkeypatch.setenv("MAGMA_DP_BACKEND", backend)
+    dist.init_process_group("nccl", rank=0, world_size=1)
+    try:
+        eng, batches = _window_engine(dev, True)
+        assert eng._exchange.name.startswith("mg_comm") == (backend == "rccl") and eng.exchange_bf16
+        for i in range(3):
+            acc.forward_backward(eng, batches, i)
+            if i < 2:
+                assert not any(eng._reduced) and not eng._works, f"a bucket left during backward {i + 1} of 3"
+                before = [grp.grad.clone() for grp in eng.groups]
+                eng.step()
+                assert all(torch.equal(a, grp.grad) for a, grp in zip(before, eng.groups)) and eng.global_steps == 0
+        assert any(eng._reduced), "no bucket was handed to RCCL during the last backward"
+        G = [grp.grad.clone() for grp in eng.groups]
+        eng.step()
+        torch.cuda.synchronize()
+        assert eng.global_steps == 1 and not any(eng._reduced) and not eng._works
+        for gi, (grp, g) in enumerate(zip(eng.groups, G)):
+            assert torch.equal(grp.comm, g.to(torch.bfloat16)), f"group {gi}: the exchanged bucket is not bf16 of the window's gradient"
+        assert [[{id(p): n for n, p in eng.module.named_parameters()}[id(p)] for p in grp.params] for grp in eng.groups] == order
+        for gi, grp in enumerate(eng.groups):
+            for p, name in zip(grp.params, order[gi]):
+                kc.assert_accumulation(grp.view(G[gi], p), [grp.view(r[gi], p) for r in runs[0]], [grp.view(r[gi], p) for r in runs[1]],
+                                       f"1-rank window {name} {tuple(p.shape)}")
+    finally:
+        dist.destroy_process_group()
 
 
 def test_compute_stream_with_reserved_cus(dev, monkeypatch):

@@ -454,3 +454,90 @@ def test_constants():
     y = 0.5 * x * (1 + torch.tanh(math.sqrt(2 / math.pi) * (x + 0.044715 * x ** 3)))
     (gr,) = torch.autograd.grad(y.sum(), x)
     assert 1.12 < float(gr.abs().max()) <= kc.GELU_LIPSCHITZ
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# gradient accumulation: a window of N micro-steps against the sum of its parts
+# ---------------------------------------------------------------------------------------------------------------------------
+ACC_NOISE = 1e-6          # injected, relative, on top of the re-ordered fp32 sums: the level of the column sums' atomics
+
+
+def _micro_gradient(src, seed):
+    """One micro-step's gradient of a bias-like / weight-like tensor the way a column-sum kernel forms it: the rows of ``src``
+    added in fp32 in an order that differs from run to run (32-row chunks of a permutation), with atomic-like noise on top."""
+    g = torch.Generator().manual_seed(seed)
+    acc = torch.zeros(src.shape[1:], dtype=torch.float32)
+    for c in torch.randperm(src.shape[0], generator=g).split(32):
+        acc += src[c].sum(0)
+    return acc * (1.0 + ACC_NOISE * torch.randn(acc.shape, generator=g))
+
+
+def _window(srcs, seed, start=None):
+    """N parts accumulated into ONE fp32 buffer, ``buf += g_i``, in yet another order."""
+    buf = torch.zeros(srcs[0].shape[1:], dtype=torch.float32) if start is None else start.clone()
+    for i, s in enumerate(srcs):
+        buf += _micro_gradient(s, seed + i)
+    return buf
+
+
+@pytest.mark.parametrize("shape", [(1056,), (64, 136)], ids=["bias", "weight"])
+def test_accumulation_stand_in_and_faults(shape):
+    """kernel_compare.accumulation_bound on the host: a float32 stand-in of 'three micro-steps into one buffer' passes; the five
+    ways a gradient sink or the engine around it can break the window are each far over the bound.  Rows per micro-step differ
+    (64 / 128 / 96) as the truncated sequence lengths of the GPU test do."""
+    N = 3
+    srcs = [rnd(r, *shape, seed=50 + i, scale=0.02) for i, r in enumerate((64, 128, 96))]
+    parts = [_micro_gradient(s, 100 + i) for i, s in enumerate(srcs)]
+    repeats = [_micro_gradient(s, 200 + i) for i, s in enumerate(srcs)]
+    ref, bound, self_ratio, invisible = kc.accumulation_conditions(parts, repeats, f"stand-in {shape}")
+    assert self_ratio <= 1.0 and not invisible
+    good = _window(srcs, 300)
+    out = kc.assert_accumulation(good, parts, repeats, f"honest window {shape}")
+    assert out["worst"] < 1.0 and out["zero_parts"] == []
+    print(f"  accumulation {shape}: honest err/bound {out['worst']:.3f}, reference against reference {out['self']:.3f}")
+    # the five faults, each written the way the engine would commit it
+    check_fault("the last part overwrites (only g_N remains)", _micro_gradient(srcs[-1], 302), ref, bound)
+    bad = good.clone()
+    bad.reshape(-1)[-3:] -= parts[0].reshape(-1)[-3:]
+    check_fault("first part missing from the last 3 elements (a cs[:V]-style slice)", bad, ref, bound)
+    assert "3 of" in kc.describe_failure(bad, ref, bound)
+    check_fault("one part added twice", good + _micro_gradient(srcs[1], 310), ref, bound)
+    check_fault("buffer starts from the previous window's contents", _window(srcs, 300, start=_window(srcs, 400)), ref, bound)
+    check_fault("result scaled by 1/N (scale applied in backward instead of at the step)", good / N, ref, bound)
+
+
+def test_accumulation_conditions_refuse_weak_inputs():
+    """The two conditions are checked before a window is looked at: a reference noisier than its own bound is reported as such,
+    and a part too small to be missed is listed (an identically zero one flagged as excusable, any other not)."""
+    srcs = [rnd(64, 256, seed=60 + i, scale=0.02) for i in range(3)]
+    parts = [_micro_gradient(s, 100 + i) for i, s in enumerate(srcs)]
+    repeats = [_micro_gradient(s, 200 + i) for i, s in enumerate(srcs)]
+    # run-to-run noise that the repeat sampled (one element moved by 1e-3 of the largest) is covered by 4 x the sample itself
+    rep_b = [p.clone() for p in parts]
+    rep_b[1][7] += 1e-3 * parts[1].abs().max()
+    _, _, self_ratio, _ = kc.accumulation_conditions(parts, rep_b, "noise seen by the sample")
+    assert 0.2 < self_ratio <= 0.25
+    # noise in rare discrete jumps is NOT covered: a repeat that happened to agree measures nothing, and a window that jumped fails
+    got = _window(srcs, 300)
+    got[11] += 7e-5 * parts[2][11]
+    quiet = [p.clone() for p in parts]
+    with pytest.raises(AssertionError, match="bounding box"):
+        kc.assert_accumulation(got, parts, quiet, "one quiet sample")
+    faint = [parts[0], parts[1] * 1e-7, parts[2]]
+    faint_r = [repeats[0], repeats[1] * 1e-7, repeats[2]]
+    _, _, _, invisible = kc.accumulation_conditions(faint, faint_r, "faint part")
+    assert [(i, z) for i, _, z in invisible] == [(1, False)]
+    with pytest.raises(AssertionError, match="below 100"):
+        kc.assert_accumulation(_window(srcs, 300), faint, faint_r, "faint part")
+    zero = [parts[0], torch.zeros_like(parts[1]), parts[2]]
+    zero_r = [repeats[0], torch.zeros_like(parts[1]), repeats[2]]
+    got = parts[0] + parts[2]
+    assert kc.assert_accumulation(got, zero, zero_r, "zero part")["zero_parts"] == [1]
+    # parts that cancel: the first term follows sum |g_i|, the floor the rms of the (small) sum -- the bound stays far below the parts
+    cancel = [parts[0], -parts[0] + 1e-3 * parts[2], parts[2]]
+    cancel_r = [repeats[0], -repeats[0] + 1e-3 * repeats[2], repeats[2]]
+    ref, bound, self_ratio, _ = kc.accumulation_conditions(cancel, cancel_r, "cancelling parts")
+    assert self_ratio <= 1.0 and float((bound / kc.f64(parts[0]).abs().clamp_min(1e-30)).median()) < 1e-4
+    # an all-zero tensor is compared, not divided by zero
+    z = [torch.zeros(8)] * 3
+    assert kc.assert_accumulation(torch.zeros(8), z, z, "all zero")["worst"] == 0.0

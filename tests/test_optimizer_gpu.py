@@ -20,8 +20,12 @@ def warmup_decay_lr(step, lr_max, lr_min, warmup, total):
     return lr_max * max(0.0, (total - step) / max(1.0, total - warmup))
 
 
+@pytest.mark.parametrize("gas", [1, 3])
 @pytest.mark.parametrize("wd", [0.0, 0.05])
-def test_five_step_trajectory_matches_torch_adamw(dev, wd):
+def test_five_step_trajectory_matches_torch_adamw(dev, wd, gas):
+    """gas = 3: the flat gradient holds the SUM of a window (3 x the gradient torch sees), step() is called after every
+    micro-step as train_loop.train_step does; the two early calls change nothing, the third applies 1 / gas -- in the update and
+    in grad_norm() -- and the trajectory is the one of gas = 1 under the same assertions."""
     from magma_amd.testing import tiny_multimodal_config
     from magma_amd.train_engine import MagmaEngine
     from magma_amd.magma import Magma
@@ -34,8 +38,9 @@ def test_five_step_trajectory_matches_torch_adamw(dev, wd):
                         max_position_embeddings=128)
     enc = ModifiedResNetTrunk((1, 1, 2, 1), 16, 64, device=dev, dtype=torch.bfloat16)
     model = Magma(cfg, device=dev, lm_config=lm_cfg, enc=enc)
-    model.config.gradient_accumulation_steps = 1
+    model.config.gradient_accumulation_steps = gas
     eng = MagmaEngine(model)
+    assert eng.gas == gas
     sched = cfg.deepspeed_config_params["scheduler"]["params"]
     warmup, total = eng.lr_scheduler.warmup, eng.lr_scheduler.total
     assert warmup == 4 and total == sched["total_num_steps"]
@@ -50,7 +55,7 @@ def test_five_step_trajectory_matches_torch_adamw(dev, wd):
         scale = 10.0 if step % 2 == 0 else 1e-3          # norm far above / far below the clip threshold
         for g, tp in zip(eng.groups, tparams):
             gr = torch.randn(g.n, device=dev, generator=gen) * scale / math.sqrt(n_train)
-            g.grad.copy_(gr)
+            g.grad.copy_(gr * gas)
             tp.grad = gr.clone()
         lrs = [warmup_decay_lr(step, g.lr_max, cfg.min_lr, warmup, total) for g in eng.groups]
         assert eng.lr_scheduler.get_lr() == pytest.approx(lrs, rel=1e-12)
@@ -58,8 +63,16 @@ def test_five_step_trajectory_matches_torch_adamw(dev, wd):
             pg["lr"] = lr
         norm = torch.nn.utils.clip_grad_norm_(tparams, 1.0)
         opt.step()
+        for micro in range(gas - 1):            # inside the window: step() must not touch anything
+            eng.micro_steps += 1
+            before = [t.clone() for g in eng.groups for t in (g.master, g.m, g.v, g.grad, g.model)]
+            eng.step()
+            after = [t for g in eng.groups for t in (g.master, g.m, g.v, g.grad, g.model)]
+            assert all(torch.equal(a, b) for a, b in zip(before, after)), (step, micro)
+            assert eng.global_steps == step and eng.lr_scheduler.get_lr() == pytest.approx(lrs, rel=1e-12)
         eng.micro_steps += 1
         eng.step()
+        assert eng.global_steps == step + 1 and eng.micro_steps == (step + 1) * gas
         assert eng.grad_norm() == pytest.approx(float(norm), rel=1e-4)
         for g, tp in zip(eng.groups, tparams):
             err = float((g.master - tp.detach()).abs().max() / tp.detach().abs().max())
