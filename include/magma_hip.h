@@ -87,8 +87,9 @@ const char* mg_version(void);
  *      batch as before, 1 = row b at d_pos[b]); mg_advance_pos gained `B` and `pos_stride` (before the stream).
  *   8  beam search: added mg_beam_state, mg_beam_topk_f32, mg_beam_finish and mg_kv_reorder_bf16 (nothing moved).
  *   9  continuing from a cache: mg_rotary_split_bf16 gained `pos_stride` (before the stream; 0 = as before, 1 = row b's chunk starts
- *      at d_pos[b]); added mg_attn_prefill_cached_bf16 (a chunk of new queries per row against the KV cache).                   */
-#define MG_ABI_VERSION 9
+ *      at d_pos[b]); added mg_attn_prefill_cached_bf16 (a chunk of new queries per row against the KV cache).
+ *  10  logits processors: added mg_logits_process_f32 and mg_beam_topk_scores_f32 (nothing moved).                              */
+#define MG_ABI_VERSION 10
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -387,6 +388,28 @@ int mg_beam_finish(const float* cand_score, const int32_t* cand_tok, int32_t B, 
                    int32_t pos_stride, const mg_beam_state* bs, void* stream);
 int mg_kv_reorder_bf16(mg_bf16* kcache, mg_bf16* vcache, mg_bf16* kstage, mg_bf16* vstage, int32_t L, int32_t R, int32_t H,
                        int32_t Smax, const int32_t* parent, const int32_t* d_pos, int32_t pos_stride, void* stream);
+
+/* Logits processors (ABI 10; DESIGN.md "Logits processors"): transformers' RepetitionPenaltyLogitsProcessor,
+ * NoRepeatNGramLogitsProcessor, MinNewTokensLengthLogitsProcessor and SuppressTokensLogitsProcessor, applied in that order, in
+ * place, to the fp32 rows logits [R, ld] (columns >= V untouched) in ONE enqueue-only launch of one workgroup per row; no
+ * allocation, no scratch.  step = state[0] (device) tokens have been generated; row r's are history[r * ld_history + 0 .. len),
+ * len = min(step, history_cols).
+ *   repetition_penalty p > 0 (1 = off): every DISTINCT token t of the row's history, once: x[t] = x[t] < 0 ? x[t] * p : x[t] / p
+ *     (fp32 multiply / correctly rounded divide);
+ *   no_repeat_ngram n in [0, 16] (0 = off): if len >= n, every window start w in [0, len - n] whose n - 1 tokens equal the last
+ *     n - 1 tokens sets x[history[w + n - 1]] = -inf (n = 1: every generated token);
+ *   min_new_tokens: step < min_new_tokens sets x[eos] = -inf;   suppress [n_suppress <= 1024] int32 (device): x[t] = -inf.
+ * Token ids outside [0, V) -- in the history, eos, the suppress list -- are skipped.  history may be NULL when neither the
+ * penalty nor the n-gram rule is on.  V is bounded by the LDS token map of the penalty (491 520).
+ * normalize = 1 (beam search): first x <- (x - max) - logsumexp over the V columns, with the arithmetic mg_beam_topk_f32 uses
+ * internally (the same bits), then the rules -- not renormalised afterwards, as in transformers' _beam_search.
+ * mg_beam_topk_scores_f32 is mg_beam_topk_f32 for rows that already hold such scores: candidates run[row] + scores[row][t].  */
+int mg_logits_process_f32(float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* state, const int64_t* history,
+                          int64_t ld_history, int32_t history_cols, float repetition_penalty, int32_t no_repeat_ngram,
+                          int32_t min_new_tokens, int64_t eos, const int32_t* suppress, int32_t n_suppress, int32_t normalize,
+                          void* stream);
+int mg_beam_topk_scores_f32(const float* scores, int64_t ld, int32_t R, int32_t V, const float* run, int32_t K2,
+                            float* cand_score, int32_t* cand_tok, void* stream);
 
 /* CLIP VisionTransformer front end and attention (encoder_name "clip" = ViT-B/32; reference magma/image_encoders.py:56-63):
  *   patchify   img [B,3,H,W] bf16 NCHW -> rows [B*(H/P)*(W/P), 3*P*P] in (c, py, px) order = the im2col of the stride-P patch

@@ -391,9 +391,12 @@ namespace {
 constexpr int BK_MAX = 16;              // largest num_beams
 constexpr int BK2_MAX = 2 * BK_MAX;
 
-__global__ __launch_bounds__(ST) void beam_topk_kernel(const float* __restrict__ logits, int64_t ld, int V,
-                                                       const float* __restrict__ run, int K2, float* __restrict__ cand_score,
-                                                       int32_t* __restrict__ cand_tok) {
+// PRE: the rows already hold log_softmax (and the logits processors' -inf) -- logits_process_kernel with normalize = 1 wrote
+// (x - max) - lse with the arithmetic below -- so a candidate's score is run + x.  A compile-time branch of one body: the
+// instance without PRE is the kernel as it was.
+template <bool PRE>
+MG_DEV void beam_topk_body(const float* __restrict__ logits, int64_t ld, int V, const float* __restrict__ run, int K2,
+                           float* __restrict__ cand_score, int32_t* __restrict__ cand_tok) {
   __shared__ uint32_t hist32[256];
   __shared__ float shf[ST / 64];
   __shared__ uint32_t bc[4];
@@ -405,14 +408,19 @@ __global__ __launch_bounds__(ST) void beam_topk_kernel(const float* __restrict__
   const float* x = logits + (int64_t)row * ld;
   const float r = run[row];
 
-  float mx = -INFINITY;
-  for (int i = tid; i < V; i += ST) mx = fmaxf(mx, x[i]);
-  mx = blk_max(mx, shf);
-  float z = 0.f;
-  for (int i = tid; i < V; i += ST) z += expf(x[i] - mx);
-  z = blk_sum(z, shf);
-  const float lse = logf(z);
-  auto score = [&](int i) -> float { return r + ((x[i] - mx) - lse); };   // log_softmax, then the running score
+  float mx = -INFINITY, lse = 0.f;
+  if constexpr (!PRE) {
+    for (int i = tid; i < V; i += ST) mx = fmaxf(mx, x[i]);
+    mx = blk_max(mx, shf);
+    float z = 0.f;
+    for (int i = tid; i < V; i += ST) z += expf(x[i] - mx);
+    z = blk_sum(z, shf);
+    lse = logf(z);
+  }
+  auto score = [&](int i) -> float {       // log_softmax, then the running score
+    if constexpr (PRE) return r + x[i];
+    else return r + ((x[i] - mx) - lse);
+  };
 
   // key of the K2-th largest score (MSB-first radix descent, 8 bits per level)
   uint32_t prefix = 0, mask = 0, remaining = (uint32_t)K2, in_bucket = 0;
@@ -472,6 +480,86 @@ __global__ __launch_bounds__(ST) void beam_topk_kernel(const float* __restrict__
     for (int j = 0; j < n; ++j) rank += (s_key[j] > k || (s_key[j] == k && s_idx[j] < i)) ? 1 : 0;
     cand_score[(int64_t)row * K2 + rank] = s_sc[tid];
     cand_tok[(int64_t)row * K2 + rank] = i;
+  }
+}
+
+__global__ __launch_bounds__(ST) void beam_topk_kernel(const float* __restrict__ logits, int64_t ld, int V,
+                                                       const float* __restrict__ run, int K2, float* __restrict__ cand_score,
+                                                       int32_t* __restrict__ cand_tok) {
+  beam_topk_body<false>(logits, ld, V, run, K2, cand_score, cand_tok);
+}
+__global__ __launch_bounds__(ST) void beam_topk_pre_kernel(const float* __restrict__ logits, int64_t ld, int V,
+                                                           const float* __restrict__ run, int K2, float* __restrict__ cand_score,
+                                                           int32_t* __restrict__ cand_tok) {
+  beam_topk_body<true>(logits, ld, V, run, K2, cand_score, cand_tok);
+}
+
+// Logits processors (DESIGN.md "Logits processors"): the rules of transformers' RepetitionPenaltyLogitsProcessor,
+// NoRepeatNGramLogitsProcessor, MinNewTokensLengthLogitsProcessor and SuppressTokensLogitsProcessor, in that order, restated on the
+// host in magma_amd/sampling.py (process_logits), as ONE enqueue-only launch in front of the selection launch: one workgroup per
+// row, in place on the row's fp32 logits, reading the step from state[0] and the row's tokens so far from the history the
+// bookkeeping launches keep (beam search: gathered by parent every step).  Work per row is O(step) -- history tokens, windows,
+// suppress ids -- plus, for the penalty, clearing a V-bit map in LDS; only normalize = 1 (beam search: the rules apply to
+// log_softmax, not renormalised) sweeps the row, with beam_topk_body's own max / logsumexp arithmetic.
+struct ProcessParams {
+  float* x; int64_t ld; int V;
+  const int32_t* state;                     // device: [0] = step = tokens generated so far
+  const int64_t* history; int64_t ld_hist; int hist_cols;
+  float penalty; int ngram; int min_new; int64_t eos;
+  const int32_t* suppress; int n_suppress;
+  int normalize;
+};
+
+__global__ __launch_bounds__(ST) void logits_process_kernel(const ProcessParams p) {
+  extern __shared__ uint32_t seen[];        // V bits (only when the penalty applies): token already penalised
+  __shared__ float shf[ST / 64];
+  const int tid = threadIdx.x, V = p.V;
+  float* x = p.x + (int64_t)blockIdx.x * p.ld;
+  const int step = p.state[0];
+  const int len = max(0, min(step, p.hist_cols));
+  const int64_t* h = p.history + (int64_t)blockIdx.x * p.ld_hist;
+
+  if (p.normalize) {
+    float mx = -INFINITY;
+    for (int i = tid; i < V; i += ST) mx = fmaxf(mx, x[i]);
+    mx = blk_max(mx, shf);
+    float z = 0.f;
+    for (int i = tid; i < V; i += ST) z += expf(x[i] - mx);
+    z = blk_sum(z, shf);
+    const float lse = logf(z);
+    for (int i = tid; i < V; i += ST) x[i] = (x[i] - mx) - lse;
+    __syncthreads();
+  }
+  // repetition penalty, once per distinct token: the thread whose atomicOr found the token's bit clear applies it, so no
+  // element is read after it was penalised, however often the token occurs
+  if (p.penalty != 1.0f && len > 0) {
+    for (int i = tid; i < (V + 31) / 32; i += ST) seen[i] = 0u;
+    __syncthreads();
+    for (int i = tid; i < len; i += ST) {
+      const int64_t t = h[i];
+      if (t < 0 || t >= V) continue;
+      const uint32_t bit = 1u << ((int)t & 31);
+      if (atomicOr(&seen[(int)t >> 5], bit) & bit) continue;
+      const float v = x[t];
+      x[t] = v < 0.f ? v * p.penalty : v / p.penalty;
+    }
+    __syncthreads();
+  }
+  // from here on every write is -inf and nothing is read back: no ordering between the three rules is needed
+  const int n = p.ngram;
+  if (n > 0 && len >= n) {
+    const int64_t* pre = h + (len - n + 1);              // the last n - 1 tokens
+    for (int w = tid; w <= len - n; w += ST) {           // one window per thread
+      bool eq = true;
+      for (int j = 0; j < n - 1; ++j) eq = eq && h[w + j] == pre[j];
+      const int64_t t = h[w + n - 1];
+      if (eq && t >= 0 && t < V) x[t] = -INFINITY;
+    }
+  }
+  if (tid == 0 && step < p.min_new && p.eos >= 0 && p.eos < V) x[p.eos] = -INFINITY;
+  for (int i = tid; i < p.n_suppress; i += ST) {
+    const int t = p.suppress[i];
+    if (t >= 0 && t < V) x[t] = -INFINITY;
   }
 }
 
@@ -669,6 +757,38 @@ extern "C" int mg_beam_topk_f32(const float* logits, int64_t ld, int32_t R, int3
     MG_FAIL(MG_ERR_SHAPE, "mg_beam_topk_f32: bad logits / R / V / ld");
   if (K2 < 2 || K2 > BK2_MAX || K2 > V) MG_FAIL(MG_ERR_SHAPE, "mg_beam_topk_f32: need 2 <= K2 <= min(%d, V), got %d", BK2_MAX, K2);
   hipLaunchKernelGGL(beam_topk_kernel, dim3(R), dim3(ST), 0, (hipStream_t)stream, logits, ld, V, run, K2, cand_score, cand_tok);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_beam_topk_scores_f32(const float* scores, int64_t ld, int32_t R, int32_t V, const float* run, int32_t K2,
+                                       float* cand_score, int32_t* cand_tok, void* stream) {
+  if (!scores || !run || !cand_score || !cand_tok || R <= 0 || V <= 0 || ld < V)
+    MG_FAIL(MG_ERR_SHAPE, "mg_beam_topk_scores_f32: bad scores / R / V / ld");
+  if (K2 < 2 || K2 > BK2_MAX || K2 > V) MG_FAIL(MG_ERR_SHAPE, "mg_beam_topk_scores_f32: need 2 <= K2 <= min(%d, V), got %d", BK2_MAX, K2);
+  hipLaunchKernelGGL(beam_topk_pre_kernel, dim3(R), dim3(ST), 0, (hipStream_t)stream, scores, ld, V, run, K2, cand_score, cand_tok);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_logits_process_f32(float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* state, const int64_t* history,
+                                     int64_t ld_history, int32_t history_cols, float repetition_penalty, int32_t no_repeat_ngram,
+                                     int32_t min_new_tokens, int64_t eos, const int32_t* suppress, int32_t n_suppress,
+                                     int32_t normalize, void* stream) {
+  if (!logits || !state || R <= 0 || V <= 0 || ld < V) MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_f32: bad logits / state / R / V / ld");
+  if (!(repetition_penalty > 0.f)) MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_f32: repetition_penalty must be > 0");
+  if (no_repeat_ngram < 0 || no_repeat_ngram > 16 || min_new_tokens < 0)
+    MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_f32: need 0 <= no_repeat_ngram <= 16 and min_new_tokens >= 0");
+  if (n_suppress < 0 || n_suppress > 1024 || (n_suppress > 0 && !suppress))
+    MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_f32: need 0 <= n_suppress <= 1024 and a suppress array");
+  const bool reads_history = repetition_penalty != 1.0f || no_repeat_ngram > 0;
+  if (reads_history && (!history || history_cols <= 0 || ld_history < history_cols))
+    MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_f32: the penalty and the n-gram rule need a history [R, ld_history >= history_cols > 0]");
+  const size_t lds = repetition_penalty != 1.0f ? (size_t)((V + 31) / 32) * 4 : 0;
+  if (lds > 60 * 1024) MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_f32: V = %d exceeds the LDS token map (491 520 tokens)", V);
+  ProcessParams p{logits, ld, V, state, history, ld_history, history ? history_cols : 0, repetition_penalty, no_repeat_ngram,
+                  min_new_tokens, eos, suppress, n_suppress, normalize ? 1 : 0};
+  hipLaunchKernelGGL(logits_process_kernel, dim3(R), dim3(ST), lds, (hipStream_t)stream, p);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }

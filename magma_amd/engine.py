@@ -58,6 +58,9 @@ class KVCache:
         self.B, self.Smax = B, Smax
         self.decode_state = None
         self.beam = None          # BeamBuffers of a beam-search loop (B = samples x num_beams rows), allocated on first use
+        # logits processors: the suppress ids on the device (int32 [1024], allocated on first use; its address and the NUMBER of
+        # ids are launch arguments of the captured step, the ids themselves are not) and the host copy of what it holds
+        self.suppress, self.suppress_ids = None, ()
         # continuing from this cache (DESIGN.md "Continuing from a cache"): host copy of the per-row write positions as of host
         # position _rows_at (None: every row at self.pos), and per row the generated token not yet fed back (-1: none)
         self._rows, self._rows_at = None, 0
@@ -157,6 +160,11 @@ class BeamBuffers:
 
 class _Layer:
     pass
+
+
+class ProcMode(tuple):
+    """LMEngine.proc_mode's checked (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress ids): passed again as
+    ``processors=`` it is taken as it is (generate() checks once, not once per token)."""
 
 
 class LMEngine:
@@ -500,9 +508,12 @@ class LMEngine:
     def forward(self, input_ids=None, inputs_embeds=None, labels=None, use_cache=False, past_key_values=None,
                 output_hidden_states=False, cache_hint: Optional[int] = None, reuse_cache: bool = False,
                 return_logits: bool = False, sampling=None, eos_token: Optional[int] = None,
-                seed: Optional[int] = None, feed_back: bool = False, lengths=None, beam=None) -> LMOutput:
+                seed: Optional[int] = None, feed_back: bool = False, lengths=None, beam=None, processors=None) -> LMOutput:
         """``beam`` = (num_beams, length_penalty, early_stopping, max_steps): beam-search token selection (the rows are
         samples x num_beams, sample-major; DESIGN.md "Beam search") instead of ``sampling``.
+        ``processors`` (sampling.check_processor_args' dict, or None): the logits processors in front of whichever selection
+        runs (DESIGN.md "Logits processors").  The first token is selected from a processed COPY of the prefill / extend
+        logits (``.logits`` stays raw); a cached step processes its logits in place (see decode).
         ``lengths`` (int [B], 1 <= len_b <= S; prefill with use_cache=True only): the rows of ``inputs_embeds`` are prompts
         of different lengths, right-padded to S.  Row b's logits are those of its position len_b - 1, and the cache keeps one
         write position per row (len_b, then + 1 per step) -- see DESIGN.md, "Ragged batches"."""
@@ -523,7 +534,7 @@ class LMEngine:
             logits, cache, full = self.extend(past_key_values, inputs_embeds, lengths=lengths, cache_hint=cache_hint)
             out = LMOutput(logits=logits.unsqueeze(1), past_key_values=cache, hidden_states=None, loss=None, full_logits=full)
             if eos_token is not None:
-                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, None)
+                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, None, processors)
             return out
         if past_key_values is not None:
             if not feed_back and input_ids is None:
@@ -538,11 +549,12 @@ class LMEngine:
                 rows = []
                 for i in range(T):      # only the LAST position selects a token (history / RNG step / eos latch untouched before)
                     lg, tok = self.decode(input_ids[:, i:i + 1], past_key_values, sampling=sampling, select=i == T - 1,
-                                          beam=beam)
+                                          beam=beam, processors=processors)
                     rows.append(lg.clone())
                 return LMOutput(logits=torch.stack(rows, 1), past_key_values=past_key_values, next_token=tok, loss=None,
                                 eos_state=past_key_values.sample_state)
-            logits, tok = self.decode(None if feed_back else input_ids, past_key_values, sampling=sampling, beam=beam)
+            logits, tok = self.decode(None if feed_back else input_ids, past_key_values, sampling=sampling, beam=beam,
+                                      processors=processors)
             return LMOutput(logits=logits.unsqueeze(1), past_key_values=past_key_values, next_token=tok, loss=None,
                             eos_state=past_key_values.sample_state)
         if inputs_embeds is None:
@@ -552,14 +564,39 @@ class LMEngine:
             # generate() only reads the last position, so only that row is computed
             out = LMOutput(logits=logits.unsqueeze(1), past_key_values=cache, hidden_states=hs, loss=None)
             if eos_token is not None:
-                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, beam)
+                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, beam, processors)
             return out
         x, hs = self._blocks_prefill(inputs_embeds, None, output_hidden_states)
         B, S, _ = inputs_embeds.shape
         logits = self._full_logits(x, B * S).view(B, S, self.V)
         return LMOutput(logits=logits, past_key_values=None, hidden_states=hs, loss=None)
 
-    def _arm_first_token(self, out: LMOutput, logits, cache: KVCache, eos_token, seed, sampling, beam):
+    @staticmethod
+    def proc_mode(processors):
+        """None (nothing is enqueued) or (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress ids): the processor
+        mode that travels beside the selection mode."""
+        if processors is None or isinstance(processors, ProcMode):
+            return processors
+        from .sampling import check_processor_args
+        d = check_processor_args(**processors)
+        return None if d is None else ProcMode((d["repetition_penalty"], d["no_repeat_ngram_size"], d["min_new_tokens"],
+                                                d["suppress_tokens"]))
+
+    def _arm_processors(self, cache: KVCache, proc):
+        """The suppress ids of ``proc`` in the cache's device buffer (written only when they differ from what it holds; never
+        inside a captured step: decode() calls this before it captures or replays)."""
+        if proc is None:
+            return
+        ids = proc[3]
+        if any(t >= self.V for t in ids):
+            raise ValueError(f"suppress_tokens must be token ids in [0, {self.V}), got {[t for t in ids if t >= self.V]}")
+        if cache.suppress is None:
+            cache.suppress = torch.zeros(1024, dtype=torch.int32, device=self.device)
+        if ids and ids != cache.suppress_ids:
+            cache.suppress[: len(ids)].copy_(torch.tensor(ids, dtype=torch.int32), non_blocking=True)
+            cache.suppress_ids = ids
+
+    def _arm_first_token(self, out: LMOutput, logits, cache: KVCache, eos_token, seed, sampling, beam, processors=None):
         """generate(): the first token of the loop selected from the prefill / extend logits, device-side bookkeeping armed."""
         if cache.eos != int(eos_token):        # the eos id is a launch argument of the captured bookkeeping kernel
             cache.eos = int(eos_token)
@@ -571,7 +608,11 @@ class LMEngine:
         mode = sampling
         if beam is not None:
             mode = self._arm_beam(cache, st, beam)
-        out["next_token"] = self.select_token(logits, cache, mode, out=st.token)
+        proc = self.proc_mode(processors)
+        if proc is not None:       # step 0 of the rules on a copy: the caller's .logits stay raw
+            self._arm_processors(cache, proc)
+            logits = logits.clone()
+        out["next_token"] = self.select_token(logits, cache, mode, out=st.token, proc=proc)
         out["eos_state"] = cache.sample_state
 
     def embed_ids(self, ids: torch.Tensor) -> torch.Tensor:
@@ -816,7 +857,7 @@ class LMEngine:
         st.ad_ln = e(B, d)                 # LayerNorm output in front of an adapter built with add_layernorm
         st.logits = e(B, self.Vp, dt=torch.float32)
         st.token = torch.zeros(B, dtype=torch.int64, device=dev)
-        st.graphs = {}             # token-selection mode (None = greedy | (temperature, top_k, top_p)) -> captured hipGraph
+        st.graphs = {}             # (token-selection mode, feed_back[, processor values]) -> captured hipGraph
         st.steps = 0
         return st
 
@@ -843,11 +884,12 @@ class LMEngine:
         cache.beam.reset(cache.eos)
         return mode
 
-    def _select_beam(self, logits: torch.Tensor, cache: KVCache, mode, advance: bool):
-        """The beam step's three launches: per-row top 2k, the bookkeeping of every sample, the K / V reorder by parent."""
+    def _select_beam(self, logits: torch.Tensor, cache: KVCache, mode, advance: bool, normalized: bool = False):
+        """The beam step's three launches: per-row top 2k, the bookkeeping of every sample, the K / V reorder by parent.
+        ``normalized``: the logits processors' launch has already turned the rows into (processed) log_softmax scores."""
         bm = cache.beam
         _, k, lp, es, max_steps = mode
-        ops.beam_topk(logits, bm.run, bm.cand_score, bm.cand_tok)
+        ops.beam_topk(logits, bm.run, bm.cand_score, bm.cand_tok, normalized=normalized)
         ops.beam_finish(bm.cand_score, bm.cand_tok, bm.B, k, logits.shape[1], cache.eos, lp, es, max_steps, cache.sample_state,
                         bm.bufs, d_pos=cache.d_pos if advance else None, pos_stride=cache.pos_stride)
         ops.kv_reorder(cache.k, cache.v, bm.kstage, bm.vstage, bm.parent, cache.d_pos, pos_stride=cache.pos_stride)
@@ -863,14 +905,21 @@ class LMEngine:
         return toks.clone(), bm.fin_score.view(bm.B, bm.k)[:, :n_ret].reshape(-1).clone(), lens
 
     def select_token(self, logits: torch.Tensor, cache: KVCache, mode, out: Optional[torch.Tensor] = None,
-                     advance: bool = False, clear: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     advance: bool = False, clear: Optional[torch.Tensor] = None, proc=None) -> torch.Tensor:
         """next token of every row from fp32 logits (B, V): greedy argmax (mode None; reference sampling.py:96-97) or the
         sampled branch (mode = (temperature, top_k, top_p); :99-107), then the loop bookkeeping in one small launch
         (all-eos step, step counter, token history, and -- inside a decode step -- the KV write position).  Enqueue-only:
         used inside the captured token step and, eagerly, on the prefill logits.  A beam mode (beam_mode) runs the beam step
-        instead: the selected token of every row lands in cache.beam's token buffer (the decode state's st.token)."""
-        if isinstance(mode, tuple) and mode and mode[0] == "beam":
-            return self._select_beam(logits, cache, mode, advance)
+        instead: the selected token of every row lands in cache.beam's token buffer (the decode state's st.token).
+        ``proc`` (proc_mode; the ids already in cache.suppress, _arm_processors): the logits processors, one launch IN PLACE on
+        ``logits`` immediately before the selection -- on the raw logits, or as log_softmax + rules in front of the beam step."""
+        is_beam = isinstance(mode, tuple) and bool(mode) and mode[0] == "beam"
+        if proc is not None:
+            ops.logits_process(logits, cache.sample_state, cache.history, repetition_penalty=proc[0], no_repeat_ngram_size=proc[1],
+                               min_new_tokens=proc[2], eos=cache.eos, suppress=cache.suppress, n_suppress=len(proc[3]),
+                               normalize=is_beam)
+        if is_beam:
+            return self._select_beam(logits, cache, mode, advance, normalized=proc is not None)
         if mode is None:
             tok = ops.argmax(logits, out=out)
         else:
@@ -879,7 +928,7 @@ class LMEngine:
                           clear=clear, clear_stride=16 if clear is not None else 1, pos_stride=cache.pos_stride)
         return tok
 
-    def _decode_step(self, cache: KVCache, st, mode=None, feed_back: bool = False):
+    def _decode_step(self, cache: KVCache, st, mode=None, feed_back: bool = False, proc=None):
         """Enqueue one token step for all B sequences (graph-capturable: no
         allocation, no sync, position read from cache.d_pos on the device): embedding, per layer the launch sequence of the
         kind planned for it (st.kinds, _ensure_decode_state), the head, token selection.
@@ -900,7 +949,7 @@ class LMEngine:
         if mode == "noselect":
             ops.advance_pos(cache.d_pos, pos_stride=cache.pos_stride)   # teacher-forced position: nothing selected, nothing recorded
         else:
-            self.select_token(st.logits[:, : self.V], cache, mode, out=st.token, advance=True)
+            self.select_token(st.logits[:, : self.V], cache, mode, out=st.token, advance=True, proc=proc)
 
     # One method per block kind (_block_kind): x -> xn for layer li.  ``src`` holds the block's weight-streaming operands: the
     # layer itself, or its e4m3 copies (ly.w8) under W8A16 -- the same launches.  On a ragged cache (pos_stride 1) every
@@ -1022,12 +1071,14 @@ class LMEngine:
         return st
 
     def decode(self, input_ids: Optional[torch.Tensor], cache: KVCache, use_graph: bool = True, sampling=None, select: bool = True,
-               beam=None):
+               beam=None, processors=None):
         """One cached step.  Returns (fp32 logits (B,V) view, selected token (B,) view: greedy, or sampled when
         ``sampling = (temperature, top_k, top_p)``); both are overwritten by the next step.  ``input_ids=None`` feeds the
         previously selected tokens back without leaving the device.  ``select=False`` (teacher-forced positions of a
         multi-token call): no token is selected -- the history, the RNG step counter and the all-eos latch are left alone,
-        only the KV write position advances; the returned token view is stale."""
+        only the KV write position advances; the returned token view is stale.
+        ``processors`` (forward): the logits processors run in place on the step's logits before the selection, so the
+        returned logits are then the PROCESSED ones (beam search: the processed log_softmax scores)."""
         if cache.pos >= cache.Smax:
             raise ValueError(f"KV cache full (Smax={cache.Smax}); pass a larger cache_hint / max_steps")
         if cache.B > 16:
@@ -1054,17 +1105,21 @@ class LMEngine:
             if feed_back:
                 raise ValueError("decode(select=False) needs input_ids: there is no selected token to feed back")
             mode = "noselect"
+        proc = self.proc_mode(processors) if select else None
+        self._arm_processors(cache, proc)
         key = (mode, feed_back)
+        if proc is not None:        # the values are launch arguments of the captured step (the suppress ids are not: their count is)
+            key += (tuple(proc[:3]) + (len(proc[3]),),)
         if not use_graph:
-            self._decode_step(cache, st, mode, feed_back)
+            self._decode_step(cache, st, mode, feed_back, proc)
         elif key in st.graphs:
             st.graphs[key].replay()
         elif st.steps == 0:
-            self._decode_step(cache, st, mode, feed_back)    # first step eager (loads code objects)
+            self._decode_step(cache, st, mode, feed_back, proc)    # first step eager (loads code objects)
         else:
             g = torch.cuda.CUDAGraph()            # hipGraph on ROCm
             with torch.cuda.graph(g):
-                self._decode_step(cache, st, mode, feed_back)
+                self._decode_step(cache, st, mode, feed_back, proc)
             st.graphs[key] = g
             g.replay()
         st.steps += 1

@@ -242,13 +242,16 @@ class GPTJForCausalLM(nn.Module):
                 labels: Optional[torch.Tensor] = None, use_cache: bool = False, past_key_values: Any = None,
                 output_hidden_states: bool = False, cache_hint: Optional[int] = None, reuse_cache: bool = False,
                 return_logits: bool = False, sampling=None, eos_token: Optional[int] = None,
-                seed: Optional[int] = None, feed_back: bool = False, lengths=None, beam=None, **unused) -> LMOutput:
-        """``lengths``: prompt lengths of a right-padded batch; ``beam``: beam-search token selection (LMEngine.forward)."""
+                seed: Optional[int] = None, feed_back: bool = False, lengths=None, beam=None, processors=None,
+                **unused) -> LMOutput:
+        """``lengths``: prompt lengths of a right-padded batch; ``beam``: beam-search token selection; ``processors``: the logits
+        processors in front of the selection (LMEngine.forward)."""
         return self.engine.forward(input_ids=input_ids, inputs_embeds=inputs_embeds, labels=labels,
                                    use_cache=use_cache, past_key_values=past_key_values,
                                    output_hidden_states=output_hidden_states, cache_hint=cache_hint,
                                    reuse_cache=reuse_cache, return_logits=return_logits, sampling=sampling,
-                                   eos_token=eos_token, seed=seed, feed_back=feed_back, lengths=lengths, beam=beam)
+                                   eos_token=eos_token, seed=seed, feed_back=feed_back, lengths=lengths, beam=beam,
+                                   processors=processors)
 
 
 def get_gptj(gradient_checkpointing: bool = False, from_pretrained: bool = False, device=None,

@@ -574,16 +574,43 @@ def advance_pos(d_pos: torch.Tensor, delta: int = 1, *, pos_stride: int = 0):
     check(L.load().mg_advance_pos(d_pos.data_ptr(), delta, d_pos.numel(), ps, _stream()), "mg_advance_pos")
 
 
-def beam_topk(logits: torch.Tensor, run: torch.Tensor, cand_score: torch.Tensor, cand_tok: torch.Tensor):
-    """Per row: the top K2 = cand_score.shape[1] scores run[row] + log_softmax(logits[row]) (score desc, lower token first)."""
+def logits_process(logits: torch.Tensor, state: torch.Tensor, history: Optional[torch.Tensor], *, repetition_penalty: float = 1.0,
+                   no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, eos: int = -1,
+                   suppress: Optional[torch.Tensor] = None, n_suppress: Optional[int] = None, normalize: bool = False):
+    """The logits processors (mg_logits_process_f32; host statement: sampling.process_logits) in place on the fp32 rows
+    ``logits`` (R, V): repetition penalty, no-repeat n-gram, min-new-tokens, suppress, in transformers' order.  ``state[0]`` is
+    the step (tokens generated so far, read on the device), ``history`` (R, >= step) int64 the rows' tokens, ``suppress`` a
+    device int32 array of which the first ``n_suppress`` (default: all) ids count.  ``normalize``: log_softmax first (the beam
+    form, for beam_topk(normalized=True)).  Enqueue-only."""
+    _need_gpu(logits, state, history, suppress)
+    assert logits.dtype == torch.float32 and logits.ndim == 2 and logits.stride(1) == 1
+    assert state.dtype == torch.int32 and state.numel() >= 1
+    R, V = logits.shape
+    if history is not None:
+        assert history.dtype == torch.int64 and history.ndim == 2 and history.stride(1) == 1 and history.shape[0] == R
+    if suppress is not None:
+        assert suppress.dtype == torch.int32 and suppress.is_contiguous()
+    ns = (0 if suppress is None else suppress.numel()) if n_suppress is None else int(n_suppress)
+    assert ns == 0 or (suppress is not None and ns <= suppress.numel())
+    check(L.load().mg_logits_process_f32(logits.data_ptr(), logits.stride(0), R, V, state.data_ptr(), _p(history),
+                                         0 if history is None else history.stride(0), 0 if history is None else history.shape[1],
+                                         float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens), int(eos),
+                                         _p(suppress), ns, 1 if normalize else 0, _stream()), "mg_logits_process_f32")
+    return logits
+
+
+def beam_topk(logits: torch.Tensor, run: torch.Tensor, cand_score: torch.Tensor, cand_tok: torch.Tensor, normalized: bool = False):
+    """Per row: the top K2 = cand_score.shape[1] scores run[row] + log_softmax(logits[row]) (score desc, lower token first).
+    ``normalized``: the rows already hold log_softmax scores (logits_process(normalize=True)): candidates run[row] + logits[row]."""
     _need_gpu(logits, run, cand_score, cand_tok)
     assert logits.dtype == torch.float32 and logits.ndim == 2 and logits.stride(1) == 1
     R, V = logits.shape
     assert run.dtype == torch.float32 and run.is_contiguous() and run.numel() == R
     assert cand_score.dtype == torch.float32 and cand_tok.dtype == torch.int32 and cand_score.is_contiguous() and cand_tok.is_contiguous()
     assert cand_score.shape == cand_tok.shape and cand_score.ndim == 2 and cand_score.shape[0] == R
-    check(L.load().mg_beam_topk_f32(logits.data_ptr(), logits.stride(0), R, V, run.data_ptr(), cand_score.shape[1],
-                                    cand_score.data_ptr(), cand_tok.data_ptr(), _stream()), "mg_beam_topk_f32")
+    name = "mg_beam_topk_scores_f32" if normalized else "mg_beam_topk_f32"
+    check(getattr(L.load(), name)(logits.data_ptr(), logits.stride(0), R, V, run.data_ptr(), cand_score.shape[1],
+                                  cand_score.data_ptr(), cand_tok.data_ptr(), _stream()), name)
 
 
 EARLY_STOPPING_CODES = {False: 0, True: 1, "never": 2}

@@ -77,6 +77,73 @@ def is_embed_batch(x) -> bool:
     return lens.ndim == 1 and not lens.is_floating_point() and not lens.is_complex() and lens.dtype != torch.bool
 
 
+MAX_NGRAM, MAX_SUPPRESS = 16, 1024
+
+
+def check_processor_args(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, vocab: int = None):
+    """ValueError for values the logits processors do not take.  Returns None when all four are neutral (nothing is applied,
+    nothing is launched), else dict(repetition_penalty float, no_repeat_ngram_size int, min_new_tokens int, suppress_tokens
+    tuple of ints).  ``vocab``: the number of logits V, when known -- suppress ids must lie in [0, V)."""
+    p = repetition_penalty
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not p > 0 or p == float("inf"):
+        raise ValueError(f"repetition_penalty must be a number > 0, got {p!r}")
+    n = no_repeat_ngram_size
+    if isinstance(n, bool) or not isinstance(n, int) or n < 0 or n > MAX_NGRAM:
+        raise ValueError(f"no_repeat_ngram_size must be an integer in [0, {MAX_NGRAM}], got {n!r}")
+    m = min_new_tokens
+    if isinstance(m, bool) or not isinstance(m, int) or m < 0:
+        raise ValueError(f"min_new_tokens must be an integer >= 0, got {m!r}")
+    if torch.is_tensor(suppress_tokens):
+        suppress_tokens = suppress_tokens.tolist()
+    ids = tuple(suppress_tokens) if suppress_tokens is not None else ()
+    if len(ids) > MAX_SUPPRESS:
+        raise ValueError(f"suppress_tokens takes at most {MAX_SUPPRESS} ids, got {len(ids)}")
+    for t in ids:
+        if isinstance(t, bool) or not isinstance(t, int) or t < 0 or (vocab is not None and t >= vocab):
+            raise ValueError(f"suppress_tokens must be token ids in [0, {'V' if vocab is None else vocab}), got {t!r}")
+    if float(p) == 1.0 and n == 0 and m == 0 and not ids:
+        return None
+    return dict(repetition_penalty=float(p), no_repeat_ngram_size=n, min_new_tokens=m, suppress_tokens=ids)
+
+
+def process_logits(scores, history, step: int, *, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
+                   min_new_tokens: int = 0, eos_token: int = None, suppress_tokens=()):
+    """The logits processors, host statement (the device kernel is csrc/sampling.hip, logits_process_kernel): the rules of
+    transformers' RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor, MinNewTokensLengthLogitsProcessor and
+    SuppressTokensLogitsProcessor in the order GenerationMixin._get_logits_processor chains them, with the prompt passed as
+    embeddings: the processors' ``input_ids`` are the generated tokens only.
+
+    ``scores`` (R, V) fp32; row r has generated ``history[r, :step]`` (``history`` (R, >= step) int64).  Returns a new tensor.
+      repetition penalty p   every distinct token t of the row's history, once: x[t] = x[t] * p if x[t] < 0 else x[t] / p
+      no-repeat n-gram n     if step >= n: every window start w in [0, step - n] whose n - 1 tokens equal the last n - 1 tokens
+                             bans history[w + n - 1] (-inf); n = 1 bans every generated token
+      min new tokens         step < min_new_tokens: x[eos] = -inf
+      suppress               x[t] = -inf for every listed t
+    Greedy and sampled selection apply this to the raw logits (before temperature / top-k / top-p), beam search to
+    log_softmax(logits) without renormalising, as transformers does."""
+    x = scores.clone()
+    R, V = x.shape
+    hist = history[:, :step].to(torch.int64)
+    p = float(repetition_penalty)
+    if p != 1.0 and step > 0:
+        got = torch.gather(x, 1, hist)
+        x = x.scatter(1, hist, torch.where(got < 0, got * p, got / p))
+    n = int(no_repeat_ngram_size)
+    if n > 0 and step >= n:
+        prefix = hist[:, step + 1 - n:]
+        windows = hist.unfold(1, n, 1)                                          # (R, step - n + 1, n)
+        match = (windows[..., :-1] == prefix[:, None, :]).all(-1)
+        banned = torch.zeros(R, V + 1, dtype=torch.bool)
+        banned.scatter_(1, torch.where(match, windows[..., -1], V), True)       # non-matching windows land in a spare column
+        x = x.masked_fill(banned[:, :V], float("-inf"))
+    if step < int(min_new_tokens) and eos_token is not None:
+        x[:, int(eos_token)] = float("-inf")
+    ids = list(suppress_tokens) if suppress_tokens is not None else []
+    if ids:
+        x[:, torch.tensor(ids, dtype=torch.int64)] = float("-inf")
+    return x
+
+
 MAX_BEAMS = 16
 
 
@@ -112,7 +179,7 @@ def reorder_past(past, rows: torch.Tensor):
 
 @torch.no_grad()
 def beam_search(step: Callable, batch_size: int, num_beams: int, max_steps: int, eos_token: int, length_penalty: float = 1.0,
-                early_stopping=False, num_return_sequences: int = 1, record: list = None):
+                early_stopping=False, num_return_sequences: int = 1, record: list = None, processors: dict = None):
     """Beam search, the rule of transformers' vectorised ``GenerationMixin._beam_search`` called with do_sample=False, one eos
     id and the prompt passed as embeddings (prompt length 0: lengths count generated tokens only), in the same fp32 torch
     arithmetic.  This is the host statement the device kernels (csrc/sampling.hip, beam_*) are tested against.
@@ -133,7 +200,11 @@ def beam_search(step: Callable, batch_size: int, num_beams: int, max_steps: int,
 
     ``record`` (a list): one dict per step is appended with the values every decision of that step compared -- the top 2k + 1
     candidate scores per sample, the merged finished-slot scores, the early-stop comparison and whether a candidate finished
-    or hit eos outside the first k -- for beam_margin() and for tests that must show which rules a run exercised."""
+    or hit eos outside the first k -- for beam_margin() and for tests that must show which rules a run exercised.
+
+    ``processors`` (check_processor_args' dict, or None): the logits processors, applied as transformers' _beam_search applies
+    them -- to log_softmax(logits) of every row, with the row's tokens so far, before the running score is added and without
+    renormalising."""
     early_stopping = check_beam_args(num_beams, num_return_sequences, early_stopping)
     B, k = batch_size, num_beams
     K2 = 2 * k
@@ -149,7 +220,10 @@ def beam_search(step: Callable, batch_size: int, num_beams: int, max_steps: int,
     logits = step(None, None)
     for t in range(max_steps):
         V = logits.shape[-1]
-        lp = F.log_softmax(logits.float().cpu(), dim=-1).view(B, k, V) + run[:, :, None]
+        lp = F.log_softmax(logits.float().cpu(), dim=-1)
+        if processors:
+            lp = process_logits(lp, seq.reshape(B * k, max_steps), t, eos_token=eos_token, **processors)
+        lp = lp.view(B, k, V) + run[:, :, None]
         flat = lp.reshape(B, k * V)
         top_s, top_i = torch.topk(flat, K2)
         beam, tok = top_i // V, top_i % V
@@ -215,13 +289,21 @@ def beam_margin(record: list) -> float:
     return min(gaps)
 
 
+def _logit_count(model):
+    """V, the number of logits of the model's LM (rows of lm_head), or None when the LM object does not say."""
+    cfg = getattr(getattr(model, "lm", None), "config", None)
+    v = getattr(cfg, "head_rows", None) or getattr(cfg, "vocab_size", None)
+    return int(v) if isinstance(v, int) else None
+
+
 @torch.no_grad()
 def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, top_k: int = 0,
              top_p: float = 0.9, eos_token: int = None, decode: bool = True,
              stop_on_eos: bool = True, seed: int = None, eos_check_every: int = None,
              lengths=None, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False,
              num_return_sequences: int = 1, return_scores: bool = False, past_key_values=None,
-             return_past_key_values: bool = False) -> Union[List[str], torch.Tensor]:
+             return_past_key_values: bool = False, *, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
+             min_new_tokens: int = 0, suppress_tokens=None) -> Union[List[str], torch.Tensor]:
     """reference sampling.py:43-121.  Token selection (argmax, or top-k / the reference's top-p rule / softmax /
     multinomial) and the ``(next_token == eos).all()`` test run on the device inside the captured token step; the host
     reads the recorded "first all-eos step" every ``eos_check_every`` steps (default 8, MAGMA_EOS_CHECK_EVERY) instead of
@@ -247,9 +329,19 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     over [prompt_b ; kept tokens_b ; new_b] gives; only the new rows go through the blocks.  The output is laid out as for a call
     on the new inputs alone.  ``past`` is advanced in place; KVCache.expand(n) gives each row n copies (one cached prompt, n
     questions).  A continued call leaves ``past`` holding the whole conversation so far (the same state it returns with
-    ``return_past_key_values=True``), so it can be continued again."""
+    ``return_past_key_values=True``), so it can be continued again.
+
+    Logits processors (DESIGN.md "Logits processors"; all three selection modes): ``repetition_penalty`` (> 0, 1.0 = off),
+    ``no_repeat_ngram_size`` (0 = off, at most 16), ``min_new_tokens`` (eos is banned for that many steps) and
+    ``suppress_tokens`` (at most 1024 ids that are never selected) are the rules of transformers' processors of those names
+    (``process_logits`` above), applied in transformers' order to the raw logits before temperature / top-k / top-p, and in
+    beam search to log_softmax(logits) before the running score is added.  The prompt is embeddings, so the rules see the
+    tokens generated by THIS call only: a continued conversation (``past_key_values``) starts with an empty history again.
+    The HIP engine applies them inside the captured token step (one small launch in front of the selection); at the
+    defaults nothing is launched and the output is bit for bit what it was."""
     eos_token = eos_token or model.eos_token
     early_stopping = check_beam_args(num_beams, num_return_sequences, early_stopping)
+    proc = check_processor_args(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, _logit_count(model))
     continuing = past_key_values is not None or return_past_key_values
     if continuing and (num_beams > 1 or return_scores):
         raise NotImplementedError("beam search neither continues from nor returns a KV cache (past_key_values / "
@@ -258,7 +350,7 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
         embeddings, lengths = embeddings                      # embed_batch's (embeddings, lengths)
     if num_beams > 1 or return_scores:
         return _generate_beam(model, embeddings, max_steps, eos_token, decode, eos_check_every, lengths, num_beams,
-                              float(length_penalty), early_stopping, num_return_sequences, return_scores)
+                              float(length_penalty), early_stopping, num_return_sequences, return_scores, proc)
     was_training = model.training
     if isinstance(embeddings, (list, tuple)):
         embeddings, derived = pad_ragged(embeddings)
@@ -295,6 +387,9 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     if lengths is not None:
         first_kw["lengths"] = lengths
     step_kw = dict(sampling=mode) if on_device else {}
+    if on_device and proc is not None:      # only then: an LM object written before the processors keeps its signature
+        from .engine import LMEngine
+        first_kw["processors"] = step_kw["processors"] = LMEngine.proc_mode(proc)      # checked once, not once per token
     if past_key_values is not None:
         start = past_key_values.rows_pos() + (past_key_values.pending >= 0).to(torch.int64) \
             if past_key_values.pending is not None else past_key_values.rows_pos()
@@ -320,8 +415,10 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
                     break
             continue
         logits = outputs.logits[:, -1, :].float()            # any other LM object: the reference's host-side arithmetic
+        if proc is not None:
+            logits = process_logits(logits.cpu(), out[:, s:n].cpu(), n - s, eos_token=eos_token, **proc).to(logits.device)
         if greedy:
-            next_token = outputs.next_token.unsqueeze(1) if outputs.get("next_token") is not None else \
+            next_token = outputs.next_token.unsqueeze(1) if outputs.get("next_token") is not None and proc is None else \
                 torch.argmax(logits, dim=-1, keepdim=True)
         else:
             if top_k > 0:
@@ -374,7 +471,7 @@ def keep_conversation(cache, start: torch.Tensor, n_gen: int, eos_token):
 
 @torch.no_grad()
 def _generate_beam(model, embeddings, max_steps, eos_token, decode, eos_check_every, lengths, k, length_penalty,
-                   early_stopping, n_ret, return_scores):
+                   early_stopping, n_ret, return_scores, proc=None):
     was_training = model.training
     if isinstance(embeddings, (list, tuple)):
         embeddings, derived = pad_ragged(embeddings)
@@ -395,12 +492,14 @@ def _generate_beam(model, embeddings, max_steps, eos_token, decode, eos_check_ev
         mode = (k, length_penalty, early_stopping, int(max_steps))
         every = eos_check_every or int(os.environ.get("MAGMA_EOS_CHECK_EVERY", "8"))
         kw = {} if lengths is None else {"lengths": lengths.repeat_interleave(k)}
+        from .engine import LMEngine
+        pkw = {} if proc is None else {"processors": LMEngine.proc_mode(proc)}
         for i in range(max_steps):
             if i == 0:
                 o = model.lm(inputs_embeds=emb, use_cache=True, past_key_values=None, cache_hint=max_steps, reuse_cache=True,
-                             eos_token=eos_token, beam=mode, **kw)
+                             eos_token=eos_token, beam=mode, **kw, **pkw)
             else:
-                o = model.lm(input_ids=None, use_cache=True, past_key_values=past, feed_back=True, beam=mode)
+                o = model.lm(input_ids=None, use_cache=True, past_key_values=past, feed_back=True, beam=mode, **pkw)
             past = o.past_key_values
             if ((i + 1) % every == 0 or i + 1 == max_steps) and int(o.eos_state[1]) >= 0:     # one host sync per `every` steps
                 break
@@ -417,7 +516,7 @@ def _generate_beam(model, embeddings, max_steps, eos_token, decode, eos_check_ev
             cache["past"] = o.past_key_values
             return o.logits[:, -1, :].float()
 
-        toks, scores, lens = beam_search(step, b, k, max_steps, eos_token, length_penalty, early_stopping, n_ret)
+        toks, scores, lens = beam_search(step, b, k, max_steps, eos_token, length_penalty, early_stopping, n_ret, processors=proc)
     toks, lens = toks.to(dev), lens.to(dev)
     n = toks.shape[1]
     out = torch.full((b * n_ret, s + n), eos_token, dtype=torch.long, device=dev)
