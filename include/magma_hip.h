@@ -88,8 +88,9 @@ const char* mg_version(void);
  *   8  beam search: added mg_beam_state, mg_beam_topk_f32, mg_beam_finish and mg_kv_reorder_bf16 (nothing moved).
  *   9  continuing from a cache: mg_rotary_split_bf16 gained `pos_stride` (before the stream; 0 = as before, 1 = row b's chunk starts
  *      at d_pos[b]); added mg_attn_prefill_cached_bf16 (a chunk of new queries per row against the KV cache).
- *  10  logits processors: added mg_logits_process_f32 and mg_beam_topk_scores_f32 (nothing moved).                              */
-#define MG_ABI_VERSION 10
+ *  10  logits processors: added mg_logits_process_f32 and mg_beam_topk_scores_f32 (nothing moved).
+ *  11  MXFP4 decode weights (W4A16): mg_skinny_desc grew by `w_mx4_scale` at its end (NULL = as before; nothing else moved). */
+#define MG_ABI_VERSION 11
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -238,6 +239,15 @@ typedef struct mg_skinny_desc {
    * (W ~= q * w_scale[n]); the kernel widens the bytes to bf16 in registers (exact) and multiplies the
    * accumulators by w_scale before the LayerNorm fold / epilogue.  Needs Kp % 1024 == 0.                     */
   const float* w_scale;
+  /* OCP MXFP4 weights, bf16 activations (W4A16; 4.25 bits per weight).  NULL = not MXFP4.  Otherwise W holds e2m1 codes (two per
+   * byte, element 2i in the low nibble of byte i) tiled as [ceil(N/16)][Kp/128][64 lanes][16 B] (lane = kq*16 + n; bytes
+   * 4s..4s+3 = W[n][128j + 32s + 8kq ..+7], s = 0..3: one 16-byte lane load covers FOUR k-steps) and w_mx4_scale the E8M0
+   * block scales, one per 32 K-elements of a row, tiled as [ceil(N/16)][Kp/128][16 n] 32-bit words (byte s of word n = the
+   * scale of W[n][128j + 32s .. +31]; value = 2^(byte - 127), bytes in [2, 251]).  One MX block of a row is exactly what one
+   * 16x16x32 MFMA step consumes for it: the kernel widens two codes at a time with v_cvt_scalef32_pk_bf16_fp4, the block scale
+   * as the scale operand (exact: every e2m1 value times such a power of two is a bf16 value), so nothing is applied after the
+   * accumulation.  Rows beyond N are zero.  Needs Kp % 512 == 0, a 16-byte aligned w_mx4_scale, and w_scale == NULL.  ABI 11.   */
+  const uint8_t* w_mx4_scale;
 } mg_skinny_desc;
 
 int mg_gemm_skinny_bf16(const mg_skinny_desc* d, void* stream);

@@ -870,19 +870,19 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
 #undef MG_STAMP
 }
 
-template <int WAVES, int KC, int NT, bool W8 = false, bool PIPE = false>
+template <int WAVES, int KC, int NT, int WT = WT_BF16, bool PIPE = false>
 __global__ __launch_bounds__(WAVES * 64) void skinny_kernel(const SkinnyParams p) {
   __shared__ __attribute__((aligned(16))) char lds[skinny_lds_bytes<WAVES, NT>()];
-  skinny_body<WAVES, KC, NT, W8, false, NoWait, PIPE>(p, blockIdx.x, lds);
+  skinny_body<WAVES, KC, NT, WT, false, NoWait, PIPE>(p, blockIdx.x, lds);
 }
 
 // two independent GEMVs (same variant) in ONE launch: blocks [0, g0) work on p0, the rest on p1.
 // Decode uses it for out_proj || adapter-down: the 64-workgroup adapter GEMV hides under the other.
-template <int WAVES, int KC, int NT, bool W8 = false, bool PIPE = false>
+template <int WAVES, int KC, int NT, int WT = WT_BF16, bool PIPE = false>
 __global__ __launch_bounds__(WAVES * 64) void skinny2_kernel(const SkinnyParams p0, const SkinnyParams p1, int g0) {
   __shared__ __attribute__((aligned(16))) char lds[skinny_lds_bytes<WAVES, NT>()];
-  if ((int)blockIdx.x < g0) skinny_body<WAVES, KC, NT, W8, false, NoWait, PIPE>(p0, blockIdx.x, lds);
-  else skinny_body<WAVES, KC, NT, W8, false, NoWait, PIPE>(p1, blockIdx.x - g0, lds);
+  if ((int)blockIdx.x < g0) skinny_body<WAVES, KC, NT, WT, false, NoWait, PIPE>(p0, blockIdx.x, lds);
+  else skinny_body<WAVES, KC, NT, WT, false, NoWait, PIPE>(p1, blockIdx.x - g0, lds);
 }
 
 int check_epilogue(const mg_epilogue& ep, const char* who, bool tile_gemm = false, int N = 0) {
@@ -965,10 +965,10 @@ int launch_gemm256(GemmParams gp, hipStream_t s) {
   return MG_OK;
 }
 
-template <int WAVES, int KC, int NT, bool W8 = false, bool PIPE = false>
+template <int WAVES, int KC, int NT, int WT = WT_BF16, bool PIPE = false>
 int launch_skinny(const SkinnyParams& sp, hipStream_t s) {
   const int grid = (sp.ntiles + NT - 1) / NT;
-  hipLaunchKernelGGL((skinny_kernel<WAVES, KC, NT, W8, PIPE>), dim3(grid), dim3(WAVES * 64), 0, s, sp);
+  hipLaunchKernelGGL((skinny_kernel<WAVES, KC, NT, WT, PIPE>), dim3(grid), dim3(WAVES * 64), 0, s, sp);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }
@@ -1187,11 +1187,14 @@ int fill_skinny(const mg_skinny_desc* d, SkinnyParams& sp, const char* who) {
   sp.ln_colsum = d->ln_colsum; sp.ln_inv_d = d->ln_inv_d; sp.ln_eps = d->ln_eps;
   sp.split_n = d->split_n; sp.ep_b = d->ep_b;
   sp.w_scale = d->w_scale;
+  sp.w_mx4 = (const uint32_t*)d->w_mx4_scale;
 #ifdef MG_GEMM_ABLATIONS
   static const int dbg = [] { const char* e = getenv("MAGMA_SKINNY_DBG"); return e ? atoi(e) : 0; }();
   sp.dbg = dbg;
 #endif
   if (d->w_scale && (!MG_ALIGNED16(d->w_scale) || (d->Kp & 1023))) MG_FAIL(MG_ERR_SHAPE, "%s: fp8 weights need a 16-byte aligned w_scale and Kp %% 1024 == 0", who);
+  if (d->w_mx4_scale && d->w_scale) MG_FAIL(MG_ERR_UNSUPPORTED, "%s: w_scale (e4m3 weights) and w_mx4_scale (MXFP4 weights) are both set", who);
+  if (d->w_mx4_scale && (!MG_ALIGNED16(d->w_mx4_scale) || (d->Kp & 511))) MG_FAIL(MG_ERR_SHAPE, "%s: MXFP4 weights need a 16-byte aligned w_mx4_scale and Kp %% 512 == 0", who);
   if (d->split_n != 0) {
     if (d->split_n < 0 || d->split_n >= d->N || (d->split_n & 15)) MG_FAIL(MG_ERR_SHAPE, "%s: split_n must be a multiple of 16 inside (0, N)", who);
     if (int rc = check_epilogue(d->ep_b, who)) return rc;
@@ -1203,12 +1206,12 @@ int fill_skinny(const mg_skinny_desc* d, SkinnyParams& sp, const char* who) {
 // decode attention workgroups and the workgroups of one weight-streaming GEMV in ONE launch: the
 // attention part (B*H workgroups, latency-bound, a few hundred KB of KV) runs underneath the GEMV's
 // HBM stream instead of leaving most of the chip idle for ~10 us per layer.
-template <int KC, bool W8 = false, bool PIPE = false>
+template <int KC, int WT = WT_BF16, bool PIPE = false>
 __global__ __launch_bounds__(256) void decode_attn_gemv_kernel(const AttnDecodeParams ap, int n_attn, const SkinnyParams sp) {
   constexpr int LDS = ATTN_DEC_LDS > skinny_lds_bytes<4, 1>() ? ATTN_DEC_LDS : skinny_lds_bytes<4, 1>();
   __shared__ __attribute__((aligned(16))) char lds[LDS];
   if ((int)blockIdx.x < n_attn) attn_decode_body<true>(ap, blockIdx.x, lds);
-  else skinny_body<4, KC, 1, W8, false, NoWait, PIPE>(sp, blockIdx.x - n_attn, lds);
+  else skinny_body<4, KC, 1, WT, false, NoWait, PIPE>(sp, blockIdx.x - n_attn, lds);
 }
 
 constexpr int MG_DECODE_PIPE_DEFAULT = 0;
@@ -1231,11 +1234,34 @@ extern "C" int mg_gemm_skinny_bf16(const mg_skinny_desc* d, void* stream) {
   if ((d->nt_hint >> 17) & 1) MG_FAIL(MG_ERR_UNSUPPORTED, "mg_gemm_skinny_bf16: the LDS-DMA GEMV exists only in the ablation library (make ABL=1)");
 #endif
   if (pipe) {
-    if (sp.w_scale || nt != 1 || sp.ksteps % (waves * kc) != 0) MG_FAIL(MG_ERR_UNSUPPORTED, "mg_gemm_skinny_bf16: pipelined variants are bf16, one n-tile");
-#define MG_SKP(W_, K_) if (waves == W_ && kc == K_) return launch_skinny<W_, K_, 1, false, true>(sp, s)
+    if (sp.w_scale || sp.w_mx4 || nt != 1 || sp.ksteps % (waves * kc) != 0) MG_FAIL(MG_ERR_UNSUPPORTED, "mg_gemm_skinny_bf16: pipelined variants are bf16, one n-tile");
+#define MG_SKP(W_, K_) if (waves == W_ && kc == K_) return launch_skinny<W_, K_, 1, WT_BF16, true>(sp, s)
     MG_SKP(4, 16); MG_SKP(4, 8); MG_SKP(8, 8); MG_SKP(8, 4); MG_SKP(4, 4);
 #undef MG_SKP
     MG_FAIL(MG_ERR_UNSUPPORTED, "mg_gemm_skinny_bf16: pipelined variant (waves=%d,kc=%d) not instantiated", waves, kc);
+  }
+  if (sp.w_mx4) {
+    // MXFP4 weights: a 16-byte load covers FOUR k-steps, so a burst of KC k-steps holds a quarter of the bf16 burst's bytes
+    // while the x fragments cost the same registers and the same L2 traffic.  The variants therefore stream several n-tiles
+    // per workgroup (NT x the weight bytes in flight per x fragment, 1 / NT of the x re-reads) -- but only while that leaves a
+    // workgroup for every CU; always 4 waves, which divide every Kp % 512 == 0.  nt_hint picks (kc, nt) as for bf16 (its wave
+    // field must be 0 or 4).  Measured per shape with tools/decode_w4_bench.py --sweep (M = 8, time per launch of a captured graph
+    // over 28 operands): [28672 x 4096] 15.0 us at (kc 8, nt 4), 17.2 at (8, 2), 21.9 at (8, 1); [4096 x 16384] 13.4 us at
+    // (16, 1) and (32, 1), 15.8 at (16, 2), 22.4 at (16, 4).  Every Kp % 512 == 0 gets an instantiated pair: (4, 4) where a
+    // wave's share of K is an odd number of k-step quads.
+    const int per_wave = sp.ksteps / 4;
+    if (d->nt_hint == 0) {
+      nt = sp.ntiles >= 1024 ? 4 : sp.ntiles >= 512 ? 2 : 1;
+      kc = nt == 4 && per_wave % 8 == 0 ? 8 : per_wave % 16 == 0 ? 16 : per_wave % 8 == 0 ? 8 : 4;
+    } else if ((waves != 0 && waves != 4) || kc <= 0 || per_wave % kc != 0) {
+      MG_FAIL(MG_ERR_SHAPE, "mg_gemm_skinny_bf16: MXFP4 variant (waves=%d,kc=%d,nt=%d) does not divide ksteps=%d with 4 waves", waves, kc, nt, sp.ksteps);
+    }
+#define MG_SK4(K_, N_) if (kc == K_ && nt == N_) return launch_skinny<4, K_, N_, WT_MX4>(sp, s)
+    MG_SK4(4, 1); MG_SK4(8, 1); MG_SK4(16, 1); MG_SK4(32, 1);
+    MG_SK4(4, 2); MG_SK4(8, 2); MG_SK4(16, 2); MG_SK4(32, 2);
+    MG_SK4(4, 4); MG_SK4(8, 4); MG_SK4(16, 4);
+#undef MG_SK4
+    MG_FAIL(MG_ERR_UNSUPPORTED, "mg_gemm_skinny_bf16: MXFP4 variant (kc=%d,nt=%d) not instantiated", kc, nt);
   }
   if (d->nt_hint == 0) {
     // measured on MI355X (tools/kbench.py, profiles/r01_kbench_*.jsonl): many
@@ -1250,15 +1276,15 @@ extern "C" int mg_gemm_skinny_bf16(const mg_skinny_desc* d, void* stream) {
   if (sp.w_scale) {   // fp8 weights: a 16-byte load covers TWO k-steps, so the bursts are twice as deep as for bf16 to keep
                       // the same bytes in flight (Kp % 1024 == 0 guarantees that every variant below divides)
     if (d->nt_hint != 0) {
-      if (waves == 8 && kc == 4) return launch_skinny<8, 4, 1, true>(sp, s);
-      if (waves == 8 && kc == 8 && sp.ksteps % 64 == 0) return launch_skinny<8, 8, 1, true>(sp, s);
-      if (waves == 4 && kc == 16 && sp.ksteps % 64 == 0) return launch_skinny<4, 16, 1, true>(sp, s);
-      if (waves == 4 && kc == 8) return launch_skinny<4, 8, 1, true>(sp, s);
+      if (waves == 8 && kc == 4) return launch_skinny<8, 4, 1, WT_FP8>(sp, s);
+      if (waves == 8 && kc == 8 && sp.ksteps % 64 == 0) return launch_skinny<8, 8, 1, WT_FP8>(sp, s);
+      if (waves == 4 && kc == 16 && sp.ksteps % 64 == 0) return launch_skinny<4, 16, 1, WT_FP8>(sp, s);
+      if (waves == 4 && kc == 8) return launch_skinny<4, 8, 1, WT_FP8>(sp, s);
       MG_FAIL(MG_ERR_UNSUPPORTED, "mg_gemm_skinny_bf16: fp8-weight variant (waves=%d,kc=%d) not instantiated", waves, kc);
     }
-    if (sp.ksteps >= 512) return launch_skinny<4, 16, 1, true>(sp, s);
-    if (sp.ksteps % 64 == 0) return launch_skinny<8, 8, 1, true>(sp, s);
-    return launch_skinny<4, 8, 1, true>(sp, s);
+    if (sp.ksteps >= 512) return launch_skinny<4, 16, 1, WT_FP8>(sp, s);
+    if (sp.ksteps % 64 == 0) return launch_skinny<8, 8, 1, WT_FP8>(sp, s);
+    return launch_skinny<4, 8, 1, WT_FP8>(sp, s);
   }
 #define MG_SK(W_, K_, N_) if (waves == W_ && kc == K_ && nt == N_) return launch_skinny<W_, K_, N_>(sp, s)
   MG_SK(8, 16, 1); MG_SK(8, 16, 2); MG_SK(4, 16, 1); MG_SK(4, 16, 2);
@@ -1280,11 +1306,20 @@ extern "C" int mg_gemm_skinny2_bf16(const mg_skinny_desc* a, const mg_skinny_des
   const int grid = pa.ntiles + pb.ntiles;
   // (burst shapes other than 8 waves x 4 k-steps -- one burst of 16, two of 8 issued up front, double-buffered 4 x 16 and
   //  8 x 4 -- were measured inside the decode graph in rounds 2 and 3: all slower, 2.55-2.60 ms per token against 2.54)
-  if ((pa.w_scale != nullptr) != (pb.w_scale != nullptr)) MG_FAIL(MG_ERR_UNSUPPORTED, "mg_gemm_skinny2_bf16: both problems must use the same weight type");
+  if ((pa.w_scale != nullptr) != (pb.w_scale != nullptr) || (pa.w_mx4 != nullptr) != (pb.w_mx4 != nullptr))
+    MG_FAIL(MG_ERR_UNSUPPORTED, "mg_gemm_skinny2_bf16: both problems must use the same weight type");
+  if (pa.w_mx4) {   // MXFP4: one variant for both problems (4 waves divide every Kp % 512 == 0), one n-tile per workgroup (the pair
+                    // of a decode block has 256 + 64 tiles: fewer workgroups than that leave CUs idle, see mg_gemm_skinny_bf16)
+    if (pa.ksteps % 64 == 0 && pb.ksteps % 64 == 0) hipLaunchKernelGGL((skinny2_kernel<4, 16, 1, WT_MX4>), dim3(grid), dim3(256), 0, s, pa, pb, pa.ntiles);
+    else if (pa.ksteps % 32 == 0 && pb.ksteps % 32 == 0) hipLaunchKernelGGL((skinny2_kernel<4, 8, 1, WT_MX4>), dim3(grid), dim3(256), 0, s, pa, pb, pa.ntiles);
+    else hipLaunchKernelGGL((skinny2_kernel<4, 4, 1, WT_MX4>), dim3(grid), dim3(256), 0, s, pa, pb, pa.ntiles);
+    MG_CHECK_LAUNCH();
+    return MG_OK;
+  }
   if (pa.w_scale && pa.ksteps % 64 == 0 && pb.ksteps % 64 == 0) {
-    hipLaunchKernelGGL((skinny2_kernel<8, 8, 1, true>), dim3(grid), dim3(512), 0, s, pa, pb, pa.ntiles);
+    hipLaunchKernelGGL((skinny2_kernel<8, 8, 1, WT_FP8>), dim3(grid), dim3(512), 0, s, pa, pb, pa.ntiles);
   } else if (pa.w_scale) {
-    hipLaunchKernelGGL((skinny2_kernel<8, 4, 1, true>), dim3(grid), dim3(512), 0, s, pa, pb, pa.ntiles);
+    hipLaunchKernelGGL((skinny2_kernel<8, 4, 1, WT_FP8>), dim3(grid), dim3(512), 0, s, pa, pb, pa.ntiles);
   } else if (pa.ksteps % 32 == 0 && pb.ksteps % 32 == 0) {
     hipLaunchKernelGGL((skinny2_kernel<8, 4, 1>), dim3(grid), dim3(512), 0, s, pa, pb, pa.ntiles);
   } else if (pa.ksteps % 4 == 0 && pb.ksteps % 4 == 0) {
@@ -1316,9 +1351,13 @@ extern "C" int mg_decode_attn_gemv_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_
   if (sp.w_scale && sp.ksteps % 64 != 0) MG_FAIL(MG_ERR_UNSUPPORTED, "mg_decode_attn_gemv_bf16: fp8 weights need K %% 2048 == 0 here");
   // MAGMA_DECODE_PIPE: 0 = burst-and-drain, 16 / 8 = double-buffered bursts of that many k-steps (bf16 weights)
   const int pipe = [] { const char* e = getenv("MAGMA_DECODE_PIPE"); return e ? atoi(e) : MG_DECODE_PIPE_DEFAULT; }();   // read per call (graph capture)
-  if (sp.w_scale) hipLaunchKernelGGL((decode_attn_gemv_kernel<16, true>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
-  else if (pipe == 16 && sp.ksteps % 64 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<16, false, true>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
-  else if (pipe == 8 && sp.ksteps % 32 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<8, false, true>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
+  if (sp.w_mx4) {   // MXFP4: one n-tile per workgroup (fc_out has 256 tiles: see the measured table in mg_gemm_skinny_bf16)
+    if (sp.ksteps % 64 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<16, WT_MX4>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
+    else if (sp.ksteps % 32 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<8, WT_MX4>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
+    else hipLaunchKernelGGL((decode_attn_gemv_kernel<4, WT_MX4>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
+  } else if (sp.w_scale) hipLaunchKernelGGL((decode_attn_gemv_kernel<16, WT_FP8>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
+  else if (pipe == 16 && sp.ksteps % 64 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<16, WT_BF16, true>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
+  else if (pipe == 8 && sp.ksteps % 32 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<8, WT_BF16, true>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
   else if (sp.ksteps % 64 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<16>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
   else if (sp.ksteps % 16 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<4>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
   else if (sp.ksteps % 4 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<1>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);

@@ -597,6 +597,11 @@ struct SkinnyParams {
   // (lane = kq*16 + n: bytes 0-7 = W[n][32*(2j) + 8kq ..], bytes 8-15 = the same columns of k-step 2j+1) and
   // w_scale[n] the per-output-channel scale; the weights are widened to bf16 in registers, so the stream is half as long.
   const float* w_scale;
+  // OCP MXFP4 weights (W4A16): W holds e2m1 codes in the layout [n-tile][k-step quad j][64 lanes][16 B] (lane = kq*16 + n: bytes
+  // 4s..4s+3 = the eight codes of W[n][32*(4j+s) + 8kq ..], element 2i in the low nibble of byte i) and w_mx4 the E8M0 block
+  // scales as [n-tile][k-step quad j][16 n] words, byte s = the scale of row n's k-step 4j+s -- one MX block IS one row of one
+  // MFMA k-step.  The codes are widened to bf16 with the scale applied (exact), nothing happens after the accumulation.
+  const uint32_t* w_mx4;
 #ifdef MG_GEMM_ABLATIONS
   int dbg;   // ablation library only (`make ABL=1`, MAGMA_SKINNY_DBG): bit 0 = skip the LayerNorm-fold row statistics (WRONG results)
 #endif
@@ -617,6 +622,21 @@ MG_DEV bf16x8 fp8x8_to_bf16(uint32_t w0, uint32_t w1) {
   return __builtin_bit_cast(bf16x8, o);
 }
 
+// weight types of the skinny kernels (skinny_body's WT)
+constexpr int WT_BF16 = 0, WT_FP8 = 1, WT_MX4 = 2;
+
+// 8 e2m1 codes (one 32-bit word, element 2i in the low nibble of byte i) x 2^(e8m0 - 127) -> 8 bf16 (exact for e8m0 in [2, 251]:
+// v_cvt_scalef32_pk_bf16_fp4 widens two codes per instruction, op_sel picks the byte, the block scale is its scale operand)
+MG_DEV bf16x8 mx4x8_to_bf16(uint32_t codes, float scale) {
+  const u32x4 o = {__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 0)),
+                   __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 1)),
+                   __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 2)),
+                   __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 3))};
+  return __builtin_bit_cast(bf16x8, o);
+}
+// byte s of a word of four E8M0 scales -> the fp32 power of two (the byte is the exponent field)
+MG_DEV float e8m0_byte(uint32_t word, int s) { return __builtin_bit_cast(float, ((word >> (8 * s)) & 0xffu) << 23); }
+
 // gemv_dma.hip: the same GEMV with an LDS-DMA loader wave and one persistent workgroup per CU (nt_hint bit 17)
 int skinny_dma_launch(const SkinnyParams& sp, int variant, hipStream_t s);
 
@@ -629,9 +649,13 @@ struct NoWait { MG_DEV void operator()() const {} };
 // always has KC..2*KC weight loads in flight instead of draining its queue at every burst boundary.  That matters where
 // occupancy cannot hide the drain: fc_out (N = 4096 -> 256 workgroups of 4 waves, ONE wave per SIMD, 8 bursts of 16 loads
 // each).  Same MFMA order per accumulator, hence bit-identical results.
-template <int WAVES, int KC, int NT, bool W8 = false, bool COH = false, class Wait = NoWait, bool PIPE = false>
+// WT: WT_BF16 | WT_FP8 (e4m3 bytes, two k-steps per 16-byte load) | WT_MX4 (e2m1 codes + E8M0 block scales, four k-steps per load; the
+// burst also loads one word of scales per n-tile and k-step quad, issued with the weights).
+template <int WAVES, int KC, int NT, int WT = WT_BF16, bool COH = false, class Wait = NoWait, bool PIPE = false>
 MG_DEV void skinny_body(const SkinnyParams& p, int block, char* lds, Wait wait = Wait()) {
+  constexpr bool W8 = WT == WT_FP8, W4 = WT == WT_MX4;
   static_assert(!W8 || KC % 2 == 0, "fp8 weights are stored in k-step pairs");
+  static_assert(!W4 || (KC % 4 == 0 && !PIPE && !COH), "MXFP4 weights are stored in k-step quads; burst-and-drain stream only");
   static_assert(!PIPE || (!COH && __is_same(Wait, NoWait)), "the pipelined stream has no dependency wait / coherent loads");
   float* red = (float*)lds;
   const int lane = threadIdx.x & 63;
@@ -648,16 +672,23 @@ MG_DEV void skinny_body(const SkinnyParams& p, int block, char* lds, Wait wait =
   for (int t = 0; t < NT; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
   float xs = 0.f, xss = 0.f;   // row statistics of x (LayerNorm fold)
 
-  constexpr int WL = W8 ? KC / 2 : KC;      // 16-byte loads per n-tile and chunk
+  constexpr int WL = W4 ? KC / 4 : W8 ? KC / 2 : KC;      // 16-byte loads per n-tile and chunk
   u32x4 wf[NT][WL];
+  uint32_t wsc[NT][W4 ? WL : 1];                          // MXFP4: the four block scales of every load (row li)
   auto load_w = [&](int kc) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       const int nt = min(nt0 + t, p.ntiles - 1);
-      const u32x4* wp = W8 ? (const u32x4*)p.W + ((int64_t)nt * (p.ksteps >> 1) + ((ks0 + kc) >> 1)) * 64 + lane
+      const u32x4* wp = W4 ? (const u32x4*)p.W + ((int64_t)nt * (p.ksteps >> 2) + ((ks0 + kc) >> 2)) * 64 + lane
+                      : W8 ? (const u32x4*)p.W + ((int64_t)nt * (p.ksteps >> 1) + ((ks0 + kc) >> 1)) * 64 + lane
                            : (const u32x4*)p.W + ((int64_t)nt * p.ksteps + ks0 + kc) * 64 + lane;
 #pragma unroll
       for (int i = 0; i < WL; ++i) wf[t][i] = __builtin_nontemporal_load(wp + i * 64);
+      if constexpr (W4) {
+        const uint32_t* sp = p.w_mx4 + ((int64_t)nt * (p.ksteps >> 2) + ((ks0 + kc) >> 2)) * 16 + li;
+#pragma unroll
+        for (int i = 0; i < WL; ++i) wsc[t][i] = __builtin_nontemporal_load(sp + i * 16);
+      }
     }
   };
   constexpr bool AHEAD = !__is_same(Wait, NoWait);     // persistent step: first weight burst before the dependency wait
@@ -760,7 +791,8 @@ MG_DEV void skinny_body(const SkinnyParams& p, int block, char* lds, Wait wait =
 #pragma unroll
       for (int i = 0; i < KC; ++i) {
         bf16x8 w;
-        if constexpr (W8) w = fp8x8_to_bf16(wf[t][i >> 1][(i & 1) * 2], wf[t][i >> 1][(i & 1) * 2 + 1]);
+        if constexpr (W4) w = mx4x8_to_bf16(wf[t][i >> 2][i & 3], e8m0_byte(wsc[t][i >> 2], i & 3));
+        else if constexpr (W8) w = fp8x8_to_bf16(wf[t][i >> 1][(i & 1) * 2], wf[t][i >> 1][(i & 1) * 2 + 1]);
         else w = __builtin_bit_cast(bf16x8, wf[t][i]);
         acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, xf[i], acc[t], 0, 0, 0);
       }

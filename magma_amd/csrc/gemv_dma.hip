@@ -202,7 +202,7 @@ void launch_dma(const SkinnyParams& sp, int grid, hipStream_t s) {
 
 // variant bit 0: non-temporal DMA; bits 1..3: form; bits 4..12: workgroups (0 = 256)
 int skinny_dma_launch(const SkinnyParams& sp, int variant, hipStream_t s) {
-  if (sp.w_scale) MG_FAIL(MG_ERR_UNSUPPORTED, "mg_gemm_skinny_bf16: the LDS-DMA GEMV streams bf16 weights");
+  if (sp.w_scale || sp.w_mx4) MG_FAIL(MG_ERR_UNSUPPORTED, "mg_gemm_skinny_bf16: the LDS-DMA GEMV streams bf16 weights");
   if (sp.M > 8 || (sp.ksteps & 15) || sp.ksteps > 128) MG_FAIL(MG_ERR_UNSUPPORTED, "mg_gemm_skinny_bf16: the LDS-DMA GEMV needs M <= 8 and K %% 512 == 0, K <= 4096 (M=%d K=%d)", sp.M, sp.ksteps * 32);
   int grid = (variant >> 4) & 0x1FF;
   if (grid == 0) grid = 256;

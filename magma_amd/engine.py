@@ -229,8 +229,8 @@ class LMEngine:
             ly.dec_in = None      # decode-only fused [qkv | fc_in] operand with ln_1 folded in (built lazily)
             # lazily built operands, None until built (whether a block HAS one is _block_kind's answer, not the field's):
             # [W_out | W_up] (_ensure_out_up), [W_up_mlp | W_up_attn] (_adapter_up_cat), [W_fc_out ; W_dn W_fc_out]
-            # (_fold_adapter_down), the e4m3 prefill copies by projection name (_fp8_weight), the W8A16 decode operands
-            ly.out_up = ly.up_cat = ly.fc_dn = ly.w8 = None
+            # (_fold_adapter_down), the e4m3 prefill copies by projection name (_fp8_weight), the W8A16 / W4A16 decode operands
+            ly.out_up = ly.up_cat = ly.fc_dn = ly.w8 = ly.w4 = None
             ly.fp8 = {}
             ly._src = (a, mlp)
             self.layers.append(ly)
@@ -239,7 +239,7 @@ class LMEngine:
         self.Vp = ops.ceil_to(self.V, 8)
         self.sin_t, self.cos_t = rotary_tables(cfg.rotary_dim, cfg.max_position_embeddings, dev)
         self.rot = cfg.rotary_dim
-        self.head_dec = self.head_w8 = None
+        self.head_dec = self.head_w8 = self.head_w4 = None
         self._lm_head = lm.lm_head
         self._cache_pool = {}                        # (B, Smax) -> KVCache + captured decode graph, LRU-bounded
         self._cache_pool_max = int(os.environ.get("MAGMA_CACHE_POOL", "4"))
@@ -255,6 +255,10 @@ class LMEngine:
         # W8A16 decode: e4m3 weights (per-output-channel scales) widened to bf16 in registers by the weight-streaming
         # GEMVs -> half the bytes per token step.  Changes the numerics (weight quantisation), so it is opt-in.
         self.decode_w8 = os.environ.get("MAGMA_DECODE_W8", "0") == "1"
+        # W4A16 decode: OCP MXFP4 weights (e2m1 codes, one E8M0 scale per 32 K-elements), widened the same way -> 4.25 bits per
+        # weight.  Opt-in for the same reason, and exclusive with W8A16 (_quantised_decode: both set is an error).
+        self.decode_w4 = os.environ.get("MAGMA_DECODE_W4", "0") == "1"
+        self._quantised_decode()
         self._dec_in_variant = int(os.environ.get("MAGMA_DEC_IN_VARIANT", "0"))   # tuning knob: nt | waves<<4 | kc<<8
         self._dec_dn_variant = int(os.environ.get("MAGMA_DEC_DN_VARIANT", "0"))   # the same for the adapter-down and the
         self._dec_cat_variant = int(os.environ.get("MAGMA_DEC_CAT_VARIANT", "0"))  # [W_out | W_up] launches of the v1 block
@@ -315,10 +319,10 @@ class LMEngine:
         return G_up(t, up, out=out, residuals=residuals, **kw)
 
     def _fold_pack(self, cls, w, b, gamma, beta, split=None):
-        """LayerNorm(gamma, beta) folded into [w; b] (ops.fold_layernorm), packed as ``cls`` (PackedLinear | PackedLinearW8).
+        """LayerNorm(gamma, beta) folded into [w; b] (ops.fold_layernorm), packed as ``cls`` (PackedLinear | PackedLinearW8 | PackedLinearW4).
         ``split``: the bias of the output columns >= split goes to .bias_b (second segment of a split launch).  The e4m3 pack
         takes the fold's column sums from its DEQUANTISED weights, so that  rstd*(acc*scale - mean*colsum)  stays exact for what
-        the kernel multiplies."""
+        the kernel multiplies; the MXFP4 pack does the same (fold first, then quantise)."""
         w2, b2, cs = ops.fold_layernorm(w, b, gamma, beta)
         lin = cls(w2, bias=b2 if split is None else b2[:split])
         if split is not None:
@@ -410,29 +414,66 @@ class LMEngine:
         ly.fc_dn = ops.PackedLinear(torch.cat([mlp.c_proj.weight.detach().to(BF16), (w_dn @ w_fc).to(BF16)], dim=0), bias=b_fc)
         ly.fc_dn.bias_b = (w_dn @ b_fc + dn.bias).contiguous()
 
-    def _ensure_decode_packs_w8(self):
-        """e4m3 copies of every decode operand (same LayerNorm folds, _fold_pack)."""
-        if self.head_w8 is not None:
+    # the quantised decode modes: engine switch -> (name, weight class, K every operand must be a multiple of, layer / head field)
+    _QUANT_DECODE = {"decode_w8": ("W8A16", "PackedLinearW8", 1024, "w8", "head_w8"),
+                     "decode_w4": ("W4A16", "PackedLinearW4", 512, "w4", "head_w4")}
+
+    def _quantised_decode(self):
+        """The active quantised decode mode as its _QUANT_DECODE row, or None (bf16 weights)."""
+        if self.decode_w8 and self.decode_w4:
+            raise ValueError("decode_w8 (MAGMA_DECODE_W8) and decode_w4 (MAGMA_DECODE_W4) are both set: one weight format per token step")
+        for switch, row in self._QUANT_DECODE.items():
+            if getattr(self, switch):
+                return row
+        return None
+
+    def _ensure_decode_packs_q(self, mode):
+        """Quantised copies (``mode``: a _QUANT_DECODE row) of every decode operand (same LayerNorm folds, _fold_pack).  An operand
+        whose K the format's kernel does not take has no copy (None): _plan_decode refuses the step that would need it."""
+        _, cls, kmod, field, head = mode
+        cls = getattr(ops, cls)
+        if getattr(self, head) is not None or self._quant_misfit(mode) is not None:
             return
-        unpacked = lambda p: ops.PackedLinear.untile(p.ft)[: p.N, : p.K]  # noqa: E731
         for ly in self.layers:
             a, mlp = ly._src
-            w8 = _Layer()
-            w8.dec_in = self._fold_dec_in(ops.PackedLinearW8, ly)
-            w8.out = ops.PackedLinearW8(a.out_proj.weight)
-            w8.fc_out = ops.PackedLinearW8(mlp.c_proj.weight, mlp.c_proj.bias)
-            w8.mlp_adapter = None
-            if ly.mlp_adapter is not None:
-                # (the up-projection alone is only used by the MAGMA_v1 step; in MAGMA_v2 -- K = 512 -- it lives in up_cat below)
-                w8.mlp_adapter = tuple(ops.PackedLinearW8(unpacked(p), p.bias) if p.K % 1024 == 0 else None for p in ly.mlp_adapter)
-            # MAGMA_v2 (attention AND mlp adapters): the attention adapter's down-projection and the concatenated up-projection
-            w8.attn_adapter = w8.up_cat = None
-            cat = self._adapter_up_cat(ly)
-            if cat is not None and cat.K % 1024 == 0:
-                w8.attn_adapter = (ops.PackedLinearW8(unpacked(ly.attn_adapter[0]), ly.attn_adapter[0].bias),)
-                w8.up_cat = ops.PackedLinearW8(unpacked(cat), cat.bias)
-            ly.w8 = w8
-        self.head_w8 = self._fold_head(ops.PackedLinearW8)
+            q = _Layer()
+            q.dec_in = self._fold_dec_in(cls, ly)
+            q.out = cls(a.out_proj.weight)
+            q.fc_out = cls(mlp.c_proj.weight, mlp.c_proj.bias)
+            self._quantised_adapters(q, ly, cls, kmod)
+            setattr(ly, field, q)
+        setattr(self, head, self._fold_head(cls))
+
+    def _quant_misfit(self, mode):
+        """Why the FROZEN projections have no operand in this quantised format (their K is d or d_ff), or None.  Nothing is
+        packed then; _plan_decode hands the reason to st.refusal."""
+        name, _, kmod = mode[:3]
+        bad = sorted({k for ly in self.layers for k in (self.d, ly.fc_out.K) if k % kmod})
+        if bad:
+            return f"{name} decode needs every projection's K to be a multiple of {kmod} (this model has K = {', '.join(map(str, bad))})"
+        return None
+
+    def _quantised_adapters(self, q, ly, cls, kmod):
+        """The adapter projections of ``ly`` as ``cls`` into the layer's quantised operand set ``q``."""
+        unpacked = lambda p: ops.PackedLinear.untile(p.ft)[: p.N, : p.K]  # noqa: E731
+        q.mlp_adapter = None
+        if ly.mlp_adapter is not None:
+            # (the up-projection alone is only used by the MAGMA_v1 step; in MAGMA_v2 -- K = 512 -- it lives in up_cat below)
+            q.mlp_adapter = tuple(cls(unpacked(p), p.bias) if p.K % kmod == 0 else None for p in ly.mlp_adapter)
+        # MAGMA_v2 (attention AND mlp adapters): the attention adapter's down-projection and the concatenated up-projection
+        q.attn_adapter = q.up_cat = None
+        cat = self._adapter_up_cat(ly)
+        if cat is not None and cat.K % kmod == 0:
+            q.attn_adapter = (cls(unpacked(ly.attn_adapter[0]), ly.attn_adapter[0].bias),)
+            q.up_cat = cls(unpacked(cat), cat.bias)
+
+    def _ensure_decode_packs_w8(self):
+        """e4m3 copies of every decode operand."""
+        self._ensure_decode_packs_q(self._QUANT_DECODE["decode_w8"])
+
+    def _ensure_decode_packs_w4(self):
+        """MXFP4 copies of every decode operand."""
+        self._ensure_decode_packs_q(self._QUANT_DECODE["decode_w4"])
 
     def repack_adapters(self, lm):
         """Refresh only the (trainable) adapter operands after optimizer steps; the
@@ -458,6 +499,9 @@ class LMEngine:
                 self._ensure_out_up(ly)
             if had_up_cat:
                 self._adapter_up_cat(ly)
+            for _, cls, kmod, field, _ in self._QUANT_DECODE.values():
+                if getattr(ly, field) is not None:     # the quantised decode operands hold copies of the adapter projections
+                    self._quantised_adapters(getattr(ly, field), ly, getattr(ops, cls), kmod)
 
     @staticmethod
     def _par_up(up, par):
@@ -938,13 +982,13 @@ class LMEngine:
         ops.embedding(st.token.view(B, 1) if feed_back else st.ids, self.wte, st.xa.view(B, 1, self.d))
         x, xn = st.xa, st.xb
         for li, (ly, kind) in enumerate(zip(self.layers, st.kinds)):
-            getattr(self, "_block_" + kind)(cache, st, li, ly, ly.w8 if st.w8 else ly, x, xn)
+            getattr(self, "_block_" + kind)(cache, st, li, ly, ly.w8 if st.w8 else ly.w4 if st.w4 else ly, x, xn)
             x, xn = xn, x
         if B > 16:
             ops.layernorm(x, self.lnf_g, self.lnf_b, self.eps, out=st.lnf)
             ops.gemm(st.lnf, self.head, out=st.logits)
         else:
-            head = self.head_w8 if st.w8 else self.head_dec
+            head = self.head_w8 if st.w8 else self.head_w4 if st.w4 else self.head_dec
             ops.gemm_skinny(x, head, out=st.logits, ln_fold=(head.colsum, self.d, self.eps))
         if mode == "noselect":
             ops.advance_pos(cache.d_pos, pos_stride=cache.pos_stride)   # teacher-forced position: nothing selected, nothing recorded
@@ -952,7 +996,7 @@ class LMEngine:
             self.select_token(st.logits[:, : self.V], cache, mode, out=st.token, advance=True, proc=proc)
 
     # One method per block kind (_block_kind): x -> xn for layer li.  ``src`` holds the block's weight-streaming operands: the
-    # layer itself, or its e4m3 copies (ly.w8) under W8A16 -- the same launches.  On a ragged cache (pos_stride 1) every
+    # layer itself, or its e4m3 / MXFP4 copies (ly.w8 / ly.w4) under W8A16 / W4A16 -- the same launches.  On a ragged cache (pos_stride 1) every
     # attention launch reads row b's position d_pos[b].
     def _dec_in(self, st, src, x):
         # ln_1 + qkv + fc_in(+gelu) in ONE weight-streaming launch
@@ -1038,34 +1082,41 @@ class LMEngine:
     def _plan_decode(self, B: int):
         """(kind of every layer's block, what decode() refuses this plan with | None) for a cache of B rows under the engine's
         current switches; builds the operands the kinds read, so that no token step allocates."""
-        w8 = self.decode_w8
+        mode = self._quantised_decode()
+        w8 = mode is not None           # either quantised format: the blocks take the kinds W8A16 takes
+        name, _, kmod, field, _ = mode or ("", "", 0, "", "")
         kinds = [self._block_kind(ly, B > 16, w8, self.fold_dn, self.group_launches) for ly in self.layers]
         if w8 and B > 16:
-            return kinds, "W8A16 decode covers batches of at most 16 sequences"
+            return kinds, f"{name} decode covers batches of at most 16 sequences"
+        if w8 and self._quant_misfit(mode) is not None:
+            return kinds, self._quant_misfit(mode)
         for ly, kind in zip(self.layers, kinds):
             if kind in ("fold1", "fold2"):
                 self._ensure_out_up(ly)
             if kind == "v2":
                 self._adapter_up_cat(ly)
-            # an adapter projection whose K is not a multiple of 1024 has no e4m3 operand (_ensure_decode_packs_w8)
-            if w8 and kind == "grouped" and any(p is None for p in ly.w8.mlp_adapter):
-                return kinds, "W8A16 decode needs adapter projections with K % 1024 == 0 (downsample_factor 4 at d = 4096)"
-            if w8 and kind == "v2" and (ly.w8.up_cat is None or ly.w8.mlp_adapter[0] is None):
-                return kinds, "W8A16 decode of the MAGMA_v2 step needs adapter projections with K % 1024 == 0"
+            # an adapter projection whose K is not a multiple of 1024 (W4A16: 512) has no quantised operand (_ensure_decode_packs_q)
+            q = getattr(ly, field) if w8 else None
+            if w8 and kind == "grouped" and any(p is None for p in q.mlp_adapter):
+                return kinds, (f"{name} decode needs adapter projections with K % {kmod} == 0" +
+                               (" (downsample_factor 4 at d = 4096)" if kmod == 1024 else ""))
+            if w8 and kind == "v2" and (q.up_cat is None or q.mlp_adapter[0] is None):
+                return kinds, f"{name} decode of the MAGMA_v2 step needs adapter projections with K % {kmod} == 0"
         return kinds, None
 
     def _ensure_decode_state(self, cache: KVCache):
-        """The cache's decode state: scratch buffers, captured graphs and the plan of the token step (st.w8, st.kinds, st.refusal),
+        """The cache's decode state: scratch buffers, captured graphs and the plan of the token step (st.w8 / st.w4, st.kinds, st.refusal),
         fixed when the state is created -- the eager step and every graph captured on this cache run the same launches, whatever
         is written to the engine's switches afterwards."""
         st = cache.decode_state
         if st is None:
             if cache.B <= 16:           # larger batches run the tile GEMM on the prefill operands (no LayerNorm-folded packs)
                 self._ensure_decode_packs()
-            if self.decode_w8:
-                self._ensure_decode_packs_w8()
+            mode = self._quantised_decode()
+            if mode is not None:
+                self._ensure_decode_packs_q(mode)
             st = self._alloc_decode_state(cache)
-            st.w8 = self.decode_w8
+            st.w8, st.w4 = self.decode_w8, self.decode_w4
             st.kinds, st.refusal = self._plan_decode(cache.B)
             cache.decode_state = st
         return st
@@ -1088,7 +1139,7 @@ class LMEngine:
                 import warnings
                 warnings.warn(f"decode batch {cache.B} > 16: the token step runs every projection through the tile GEMM, launched "
                               "eagerly with a separate LayerNorm (correct, tested) -- the weight-streaming GEMVs, the fused "
-                              "launches and the captured hipGraph of the B <= 16 step do not apply, and W8A16 decode is refused",
+                              "launches and the captured hipGraph of the B <= 16 step do not apply, and W8A16 / W4A16 decode is refused",
                               RuntimeWarning, stacklevel=2)
         st = self._ensure_decode_state(cache)
         if st.refusal is not None:      # before anything of the step is enqueued

@@ -19,7 +19,7 @@ MG_A_DENSE, MG_A_CONV3X3 = 0, 1
 MG_AUX_NONE, MG_AUX_RELU_GATE, MG_AUX_GELU_GRAD, MG_AUX_MUL, MG_AUX_QUICK_GELU_GRAD = 0, 1, 2, 3, 4
 
 
-ABI_VERSION = 10     # include/magma_hip.h MG_ABI_VERSION
+ABI_VERSION = 11     # include/magma_hip.h MG_ABI_VERSION
 
 
 class MagmaHipError(RuntimeError):
@@ -82,6 +82,7 @@ class SkinnyDesc(C.Structure):
         ("split_n", C.c_int32), ("_pad", C.c_int32),
         ("ep_b", Epilogue),
         ("w_scale", C.c_void_p),
+        ("w_mx4_scale", C.c_void_p),
     ]
 
 

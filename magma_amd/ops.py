@@ -259,6 +259,8 @@ def skinny_desc(x: torch.Tensor, w: PackedLinear, out: Optional[torch.Tensor] = 
     d.M, d.N, d.Kp, d.nt_hint = M, w.N, w.Kp, variant
     if w8:
         d.w_scale = w.scale.data_ptr()
+    elif isinstance(w, PackedLinearW4):
+        d.w_mx4_scale = w.scales.data_ptr()
     n_a = w.N if split is None else split[0]
     d.ep = _epilogue(out, n_a, w.bias if use_bias else None, scale, act, residuals, act_after, aux, aux_mode, aux_after, out2)
     if ln_fold is not None:
@@ -294,6 +296,86 @@ class PackedLinearW8:
         n16 = self.ft.shape[0] * 16
         q = self.ft.permute(0, 3, 1, 4, 2, 5).reshape(n16, self.K)
         return (q.view(torch.float8_e4m3fn).float() * self.scale[:, None])[: self.N]
+
+
+_E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+_E2M1_MIDPOINTS = (0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)
+
+
+def quantize_mx_fp4(w: torch.Tensor):
+    """[N, K] (K % 32 == 0) -> (codes uint8 [N, K/2], scales uint8 [N, K/32]): OCP MX v1.0 MXFP4.  Per 32 consecutive K-elements
+    of a row the shared exponent is e = floor(log2 amax) - 2 (2 = the exponent of e2m1's largest value, 6), clamped to
+    [-125, 124] so that every non-zero dequantised value is a NORMAL bf16 and ``scale_byte << 23`` is the fp32 scale; the
+    elements are w * 2^-e rounded to nearest, ties to the even code, onto +-{0, .5, 1, 1.5, 2, 3, 4, 6}, saturating at +-6.  An
+    all-zero block has all-zero codes (scale byte 127); a value that rounds to zero is stored as +0.  Element 2i sits in the
+    low nibble of byte i.  Plain torch on any device."""
+    assert w.ndim == 2 and w.shape[1] % 32 == 0, "MXFP4 blocks are 32 K-elements"
+    N, K = w.shape
+    blk = w.detach().to(torch.float32).reshape(N, K // 32, 32)
+    amax = blk.abs().amax(-1)
+    _, ex = torch.frexp(amax)                                   # amax = m * 2^ex, m in [0.5, 1): floor(log2 amax) = ex - 1
+    e = torch.where(amax > 0, ex - 3, torch.zeros_like(ex)).clamp(-125, 124)
+    a = torch.ldexp(blk, -e[..., None]).abs()                   # exact: a power-of-two factor
+    mag = torch.zeros(a.shape, dtype=torch.uint8, device=w.device)
+    for j, m in enumerate(_E2M1_MIDPOINTS):                     # code j | j+1 meet at m: the tie goes to the even one
+        mag += (a >= m) if j & 1 else (a > m)
+    code = mag | (((blk < 0) & (mag > 0)).to(torch.uint8) << 3)
+    code = code.reshape(N, K // 2, 2)
+    return (code[..., 0] | (code[..., 1] << 4)).contiguous(), (e + 127).to(torch.uint8).contiguous()
+
+
+def dequantize_mx_fp4(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """(codes [N, K/2], scales [N, K/32]) -> the exact fp32 values [N, K] (each one is also a bf16 value)."""
+    N, K = codes.shape[0], codes.shape[1] * 2
+    c = torch.stack([codes & 15, codes >> 4], dim=-1).reshape(N, K).long()
+    v = torch.tensor(_E2M1_VALUES, dtype=torch.float32, device=codes.device)[c & 7]
+    v = torch.where((c & 8) != 0, -v, v)
+    e = (scales.to(torch.int32) - 127).repeat_interleave(32, dim=1)
+    return torch.ldexp(v, e)
+
+
+def tile_mx_fp4(codes: torch.Tensor, scales: torch.Tensor):
+    """Row-major MXFP4 (quantize_mx_fp4; K % 128 == 0) -> the W4A16 GEMV's operands, rows zero-padded to a multiple of 16:
+    codes  [ceil(N/16)][K/128][64 lanes][16 B], lane = kq*16 + n, bytes 4s..4s+3 = the codes of W[n][128j + 32s + 8kq .. +7];
+    scales [ceil(N/16)][K/128][16 n][4 B], byte s = the E8M0 scale of W[n][128j + 32s .. +31] (padding rows: 127)."""
+    N, K = codes.shape[0], codes.shape[1] * 2
+    assert K % 128 == 0 and scales.shape == (N, K // 32)
+    n16 = ceil_to(N, 16)
+    c = torch.zeros(n16, K // 2, dtype=torch.uint8, device=codes.device)
+    c[:N] = codes
+    sc = torch.full((n16, K // 32), 127, dtype=torch.uint8, device=codes.device)
+    sc[:N] = scales
+    # [n16, K/2] -> [nt, n(16), quad j, step s(4), kq(4), 4 B] -> [nt, j, kq, n, s, 4 B]
+    ft = c.view(n16 // 16, 16, K // 128, 4, 4, 4).permute(0, 2, 4, 1, 3, 5).contiguous()
+    st = sc.view(n16 // 16, 16, K // 128, 4).permute(0, 2, 1, 3).contiguous()
+    return ft, st
+
+
+def untile_mx_fp4(ft: torch.Tensor, st: torch.Tensor, N: int):
+    """Inverse of tile_mx_fp4: row-major (codes [N, K/2], scales [N, K/32])."""
+    nt, kq4 = ft.shape[0], ft.shape[1]
+    codes = ft.permute(0, 3, 1, 4, 2, 5).reshape(nt * 16, kq4 * 64)
+    scales = st.permute(0, 2, 1, 3).reshape(nt * 16, kq4 * 4)
+    return codes[:N].contiguous(), scales[:N].contiguous()
+
+
+class PackedLinearW4:
+    """Decode weight as OCP MXFP4 (e2m1 codes + one E8M0 scale per 32 K-elements, 4.25 bits per weight) for the W4A16
+    weight-streaming GEMV (bf16 activations; the kernel widens the codes in registers with the block scale applied, exactly).
+    ``ft`` / ``scales``: the tiled codes and scale bytes (tile_mx_fp4; include/magma_hip.h mg_skinny_desc.w_mx4_scale).  K must
+    be a multiple of 512: four waves split K, each in whole k-step quads (one 16-byte lane load = 4 k-steps = 128 K-elements).
+    Packing is plain torch: it runs on the weight's device, the CPU included."""
+
+    def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor] = None):
+        self.N, self.K = weight.shape
+        assert self.K % 512 == 0, "W4A16 decode weights need K % 512 == 0"
+        self.Kp = self.K
+        self.ft, self.scales = tile_mx_fp4(*quantize_mx_fp4(weight))
+        self.bias = None if bias is None else bias.detach().to(torch.float32).contiguous()
+
+    def dequant(self) -> torch.Tensor:
+        """The exact fp32 values [N, K] the kernel multiplies (every one a bf16 value)."""
+        return dequantize_mx_fp4(*untile_mx_fp4(self.ft, self.scales, self.N))
 
 
 def gemm_skinny(x: torch.Tensor, w: PackedLinear, out: Optional[torch.Tensor] = None, **kw) -> torch.Tensor:
