@@ -89,8 +89,10 @@ const char* mg_version(void);
  *   9  continuing from a cache: mg_rotary_split_bf16 gained `pos_stride` (before the stream; 0 = as before, 1 = row b's chunk starts
  *      at d_pos[b]); added mg_attn_prefill_cached_bf16 (a chunk of new queries per row against the KV cache).
  *  10  logits processors: added mg_logits_process_f32 and mg_beam_topk_scores_f32 (nothing moved).
- *  11  MXFP4 decode weights (W4A16): mg_skinny_desc grew by `w_mx4_scale` at its end (NULL = as before; nothing else moved). */
-#define MG_ABI_VERSION 11
+ *  11  MXFP4 decode weights (W4A16): mg_skinny_desc grew by `w_mx4_scale` at its end (NULL = as before; nothing else moved).
+ *  12  per-row stopping: added mg_sample_finish_rows; mg_logits_process_f32 gained `eos_more` / `n_eos_more` (before the stream;
+ *      NULL / 0 = as before): further eos ids the min_new_tokens rule bans. */
+#define MG_ABI_VERSION 12
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -362,6 +364,31 @@ int mg_sample_finish(const int64_t* token, int32_t B, int64_t eos, int32_t* stat
                      int64_t* history, int64_t ld_history, int32_t history_cols, int32_t* clear, int32_t n_clear,
                      int32_t clear_stride, int32_t pos_stride, void* stream);
 
+/* Per-row stopping (ABI 12; DESIGN.md "Per-row stopping"): mg_sample_finish's bookkeeping with the stopping rule of transformers'
+ * GenerationMixin._sample -- a row that finished stays finished and is padded, the loop ends when no row is unfinished -- several
+ * eos ids and stop sequences, in ONE enqueue-only, graph-capturable launch of one workgroup (host statement:
+ * magma_amd/sampling.py, stop_update).  token, B, state, d_pos, delta, history, clear and pos_stride as in mg_sample_finish.
+ *   table   device int32[MG_STOP_TABLE_INTS] = eos ids [8] | sequence lengths [16] | sequence tokens [16][16]; read at run time
+ *           (other ids of the same counts need no re-capture); n_eos in [1, 8] and n_seq in [0, 16] are launch arguments.
+ *   finish  device int32 [B][2] = {step at which the row finished (-1: unfinished), reason}; reason = MG_STOP_EOS | i (token ==
+ *           eos id i) or MG_STOP_SEQ | j (the row's tokens history[b][0 .. step] end with sequence j, the lowest such j); eos is
+ *           tested first.  The caller resets it to {-1, 0} when a loop starts.
+ * Per row, with step = state[0]: a finished row gets `pad` written into token[b] (the next step feeds it back) and into
+ * history[b][step]; an unfinished row's token goes into the history and is tested.  Then state[1] = step if no row is unfinished
+ * and state[1] < 0; state[0] = step + 1; d_pos advanced.  Any B (rows are strided over the workgroup).  A sequence only matches
+ * while step < history_cols, and a length outside [1, 16] or above step + 1 never matches: nothing outside the history is read.
+ * n_seq > 0 without a history is refused.                                                                                    */
+#define MG_STOP_MAX_EOS 8
+#define MG_STOP_MAX_SEQ 16
+#define MG_STOP_MAX_LEN 16
+#define MG_STOP_TABLE_INTS (MG_STOP_MAX_EOS + MG_STOP_MAX_SEQ + MG_STOP_MAX_SEQ * MG_STOP_MAX_LEN)
+#define MG_STOP_EOS 0x100
+#define MG_STOP_SEQ 0x200
+int mg_sample_finish_rows(int64_t* token, int32_t B, int32_t* state, int32_t* d_pos, int32_t delta, int64_t* history,
+                          int64_t ld_history, int32_t history_cols, int32_t* clear, int32_t n_clear, int32_t clear_stride,
+                          int32_t pos_stride, const int32_t* table, int32_t n_eos, int32_t n_seq, int64_t pad, int32_t* finish,
+                          void* stream);
+
 /* Beam search (transformers' GenerationMixin._beam_search, do_sample=False, one eos id; DESIGN.md "Beam search"): three
  * enqueue-only, graph-capturable launches per token step over R = B * k rows (k = num_beams <= 16, rows sample-major).
  * mg_beam_topk_f32: per row, the top K2 = 2k candidate scores run[row] + log_softmax(logits[row]) in the order (score
@@ -408,7 +435,8 @@ int mg_kv_reorder_bf16(mg_bf16* kcache, mg_bf16* vcache, mg_bf16* kstage, mg_bf1
  *     (fp32 multiply / correctly rounded divide);
  *   no_repeat_ngram n in [0, 16] (0 = off): if len >= n, every window start w in [0, len - n] whose n - 1 tokens equal the last
  *     n - 1 tokens sets x[history[w + n - 1]] = -inf (n = 1: every generated token);
- *   min_new_tokens: step < min_new_tokens sets x[eos] = -inf;   suppress [n_suppress <= 1024] int32 (device): x[t] = -inf.
+ *   min_new_tokens: step < min_new_tokens sets x[eos] = -inf, and x[eos_more[i]] = -inf for i < n_eos_more <= 8 (ABI 12; device
+ *     int32, NULL / 0 = one eos id as before);   suppress [n_suppress <= 1024] int32 (device): x[t] = -inf.
  * Token ids outside [0, V) -- in the history, eos, the suppress list -- are skipped.  history may be NULL when neither the
  * penalty nor the n-gram rule is on.  V is bounded by the LDS token map of the penalty (491 520).
  * normalize = 1 (beam search): first x <- (x - max) - logsumexp over the V columns, with the arithmetic mg_beam_topk_f32 uses
@@ -417,7 +445,7 @@ int mg_kv_reorder_bf16(mg_bf16* kcache, mg_bf16* vcache, mg_bf16* kstage, mg_bf1
 int mg_logits_process_f32(float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* state, const int64_t* history,
                           int64_t ld_history, int32_t history_cols, float repetition_penalty, int32_t no_repeat_ngram,
                           int32_t min_new_tokens, int64_t eos, const int32_t* suppress, int32_t n_suppress, int32_t normalize,
-                          void* stream);
+                          const int32_t* eos_more, int32_t n_eos_more, void* stream);
 int mg_beam_topk_scores_f32(const float* scores, int64_t ld, int32_t R, int32_t V, const float* run, int32_t K2,
                             float* cand_score, int32_t* cand_tok, void* stream);
 

@@ -344,6 +344,62 @@ __global__ void sample_finish_kernel(const int64_t* __restrict__ tok, int B, int
   state[0] = step + 1;
 }
 
+// Per-row stopping (DESIGN.md "Per-row stopping"; host statement: sampling.py stop_update): the bookkeeping above with the rule of
+// transformers' _sample -- a finished row is padded and stays finished, the loop ends when no row is unfinished -- for up to 8 eos
+// ids and 16 stop sequences of up to 16 tokens, read from a device table (its contents may change between graph replays, the
+// counts are launch arguments).  Still one workgroup: rows are strided over it, every row is handled by one thread (its history
+// write and its tail reads are that thread's own), and the "some row is unfinished" flag goes through LDS with a barrier
+// between the row loop and thread 0's read, so B may exceed the workgroup.
+// finish[b] = {step at which row b finished or -1, reason}
+__global__ void sample_finish_rows_kernel(int64_t* __restrict__ tok, int B, int32_t* __restrict__ state, int32_t* __restrict__ d_pos,
+                                          int delta, int n_pos, int64_t* __restrict__ history, int64_t ld_hist, int hist_cols,
+                                          int32_t* __restrict__ clear, int n_clear, int clear_stride,
+                                          const int32_t* __restrict__ table, int n_eos, int n_seq, int64_t pad,
+                                          int32_t* __restrict__ finish) {
+  // as in sample_finish_kernel: the step is read once, BEFORE thread 0 bumps it, and broadcast through LDS
+  __shared__ int s_step, s_open;
+  if (threadIdx.x == 0) { s_step = state[0]; s_open = 0; }
+  __syncthreads();
+  const int step = s_step;
+  for (int i = threadIdx.x; i < n_clear; i += blockDim.x) clear[(int64_t)i * clear_stride] = 0;
+  if (d_pos)
+    for (int b = threadIdx.x; b < n_pos; b += blockDim.x) d_pos[b] += delta;
+  const int32_t* seq_len = table + MG_STOP_MAX_EOS;
+  const int32_t* seq_tok = seq_len + MG_STOP_MAX_SEQ;
+  const bool in_hist = history && step >= 0 && step < hist_cols;
+  bool open = false;
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    int64_t* h = history ? history + (int64_t)b * ld_hist : nullptr;
+    int32_t* f = finish + 2 * (int64_t)b;
+    if (f[0] >= 0) {                      // finished at an earlier step: padded, never looked at again
+      tok[b] = pad;
+      if (in_hist) h[step] = pad;
+      continue;
+    }
+    const int64_t t = tok[b];
+    if (in_hist) h[step] = t;
+    int code = 0;
+    for (int e = 0; e < n_eos && !code; ++e)
+      if (t == (int64_t)table[e]) code = MG_STOP_EOS | e;
+    if (!code && in_hist) {
+      for (int s = 0; s < n_seq && !code; ++s) {
+        const int L = seq_len[s];
+        if (L < 1 || L > MG_STOP_MAX_LEN || L > step + 1) continue;
+        bool eq = true;
+        for (int j = 0; j < L; ++j) eq = eq && h[step - L + 1 + j] == (int64_t)seq_tok[s * MG_STOP_MAX_LEN + j];
+        if (eq) code = MG_STOP_SEQ | s;
+      }
+    }
+    if (code) { f[0] = step; f[1] = code; }
+    else open = true;
+  }
+  if (open) atomicOr(&s_open, 1);
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  if (!s_open && state[1] < 0) state[1] = step;
+  state[0] = step + 1;
+}
+
 }  // namespace
 
 extern "C" int mg_sample_f32(const float* logits, int64_t ld, int32_t B, int32_t V, float temperature, int32_t top_k,
@@ -369,6 +425,24 @@ extern "C" int mg_sample_finish(const int64_t* token, int32_t B, int64_t eos, in
   hipLaunchKernelGGL(sample_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, token, B, eos, state, d_pos, delta,
                      pos_stride ? B : 1,
                      history, ld_history, history_cols, clear, clear ? n_clear : 0, clear_stride > 0 ? clear_stride : 1);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_sample_finish_rows(int64_t* token, int32_t B, int32_t* state, int32_t* d_pos, int32_t delta, int64_t* history,
+                                     int64_t ld_history, int32_t history_cols, int32_t* clear, int32_t n_clear, int32_t clear_stride,
+                                     int32_t pos_stride, const int32_t* table, int32_t n_eos, int32_t n_seq, int64_t pad,
+                                     int32_t* finish, void* stream) {
+  if (!token || !state || !table || !finish || B <= 0) MG_FAIL(MG_ERR_SHAPE, "mg_sample_finish_rows: bad arguments");
+  if (pos_stride != 0 && pos_stride != 1) MG_FAIL(MG_ERR_SHAPE, "mg_sample_finish_rows: pos_stride must be 0 or 1");
+  if (history && (ld_history < history_cols || history_cols <= 0)) MG_FAIL(MG_ERR_SHAPE, "mg_sample_finish_rows: bad history geometry");
+  if (n_eos < 1 || n_eos > MG_STOP_MAX_EOS || n_seq < 0 || n_seq > MG_STOP_MAX_SEQ)
+    MG_FAIL(MG_ERR_SHAPE, "mg_sample_finish_rows: need 1 <= n_eos <= %d and 0 <= n_seq <= %d, got %d / %d", MG_STOP_MAX_EOS,
+            MG_STOP_MAX_SEQ, n_eos, n_seq);
+  if (n_seq > 0 && !history) MG_FAIL(MG_ERR_SHAPE, "mg_sample_finish_rows: stop sequences are matched against the token history: it is missing");
+  hipLaunchKernelGGL(sample_finish_rows_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, token, B, state, d_pos, delta,
+                     pos_stride ? B : 1, history, ld_history, history ? history_cols : 0, clear, clear ? n_clear : 0,
+                     clear_stride > 0 ? clear_stride : 1, table, n_eos, n_seq, pad, finish);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }
@@ -508,6 +582,7 @@ struct ProcessParams {
   float penalty; int ngram; int min_new; int64_t eos;
   const int32_t* suppress; int n_suppress;
   int normalize;
+  const int32_t* eos_more; int n_eos_more;   // further eos ids of the min-new-tokens rule (per-row stopping with an eos list)
 };
 
 __global__ __launch_bounds__(ST) void logits_process_kernel(const ProcessParams p) {
@@ -557,6 +632,10 @@ __global__ __launch_bounds__(ST) void logits_process_kernel(const ProcessParams 
     }
   }
   if (tid == 0 && step < p.min_new && p.eos >= 0 && p.eos < V) x[p.eos] = -INFINITY;
+  if (tid < p.n_eos_more && step < p.min_new) {
+    const int t = p.eos_more[tid];
+    if (t >= 0 && t < V) x[t] = -INFINITY;
+  }
   for (int i = tid; i < p.n_suppress; i += ST) {
     const int t = p.suppress[i];
     if (t >= 0 && t < V) x[t] = -INFINITY;
@@ -774,20 +853,22 @@ extern "C" int mg_beam_topk_scores_f32(const float* scores, int64_t ld, int32_t 
 extern "C" int mg_logits_process_f32(float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* state, const int64_t* history,
                                      int64_t ld_history, int32_t history_cols, float repetition_penalty, int32_t no_repeat_ngram,
                                      int32_t min_new_tokens, int64_t eos, const int32_t* suppress, int32_t n_suppress,
-                                     int32_t normalize, void* stream) {
+                                     int32_t normalize, const int32_t* eos_more, int32_t n_eos_more, void* stream) {
   if (!logits || !state || R <= 0 || V <= 0 || ld < V) MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_f32: bad logits / state / R / V / ld");
   if (!(repetition_penalty > 0.f)) MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_f32: repetition_penalty must be > 0");
   if (no_repeat_ngram < 0 || no_repeat_ngram > 16 || min_new_tokens < 0)
     MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_f32: need 0 <= no_repeat_ngram <= 16 and min_new_tokens >= 0");
   if (n_suppress < 0 || n_suppress > 1024 || (n_suppress > 0 && !suppress))
     MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_f32: need 0 <= n_suppress <= 1024 and a suppress array");
+  if (n_eos_more < 0 || n_eos_more > MG_STOP_MAX_EOS || (n_eos_more > 0 && !eos_more))
+    MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_f32: need 0 <= n_eos_more <= %d and an eos_more array", MG_STOP_MAX_EOS);
   const bool reads_history = repetition_penalty != 1.0f || no_repeat_ngram > 0;
   if (reads_history && (!history || history_cols <= 0 || ld_history < history_cols))
     MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_f32: the penalty and the n-gram rule need a history [R, ld_history >= history_cols > 0]");
   const size_t lds = repetition_penalty != 1.0f ? (size_t)((V + 31) / 32) * 4 : 0;
   if (lds > 60 * 1024) MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_f32: V = %d exceeds the LDS token map (491 520 tokens)", V);
   ProcessParams p{logits, ld, V, state, history, ld_history, history ? history_cols : 0, repetition_penalty, no_repeat_ngram,
-                  min_new_tokens, eos, suppress, n_suppress, normalize ? 1 : 0};
+                  min_new_tokens, eos, suppress, n_suppress, normalize ? 1 : 0, eos_more, eos_more ? n_eos_more : 0};
   hipLaunchKernelGGL(logits_process_kernel, dim3(R), dim3(ST), lds, (hipStream_t)stream, p);
   MG_CHECK_LAUNCH();
   return MG_OK;

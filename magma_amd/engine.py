@@ -61,6 +61,10 @@ class KVCache:
         # logits processors: the suppress ids on the device (int32 [1024], allocated on first use; its address and the NUMBER of
         # ids are launch arguments of the captured step, the ids themselves are not) and the host copy of what it holds
         self.suppress, self.suppress_ids = None, ()
+        # per-row stopping: the stop table on the device (int32 [ops.STOP_TABLE_INTS]: eos ids, sequence lengths, sequence
+        # tokens; allocated on first use; its address and the COUNTS are launch arguments of the captured step, its contents are
+        # not), the host copy of what it holds, and the finish record int32 [B, 2] = {step the row finished at or -1, reason}
+        self.stop_table, self.stop_held, self.finish = None, None, None
         # continuing from this cache (DESIGN.md "Continuing from a cache"): host copy of the per-row write positions as of host
         # position _rows_at (None: every row at self.pos), and per row the generated token not yet fed back (-1: none)
         self._rows, self._rows_at = None, 0
@@ -165,6 +169,10 @@ class _Layer:
 class ProcMode(tuple):
     """LMEngine.proc_mode's checked (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress ids): passed again as
     ``processors=`` it is taken as it is (generate() checks once, not once per token)."""
+
+
+class StopMode(tuple):
+    """LMEngine.stop_mode's checked (eos ids, stop sequences): passed again as ``stop=`` it is taken as it is."""
 
 
 class LMEngine:
@@ -552,16 +560,22 @@ class LMEngine:
     def forward(self, input_ids=None, inputs_embeds=None, labels=None, use_cache=False, past_key_values=None,
                 output_hidden_states=False, cache_hint: Optional[int] = None, reuse_cache: bool = False,
                 return_logits: bool = False, sampling=None, eos_token: Optional[int] = None,
-                seed: Optional[int] = None, feed_back: bool = False, lengths=None, beam=None, processors=None) -> LMOutput:
+                seed: Optional[int] = None, feed_back: bool = False, lengths=None, beam=None, processors=None,
+                stop=None) -> LMOutput:
         """``beam`` = (num_beams, length_penalty, early_stopping, max_steps): beam-search token selection (the rows are
         samples x num_beams, sample-major; DESIGN.md "Beam search") instead of ``sampling``.
         ``processors`` (sampling.check_processor_args' dict, or None): the logits processors in front of whichever selection
         runs (DESIGN.md "Logits processors").  The first token is selected from a processed COPY of the prefill / extend
         logits (``.logits`` stays raw); a cached step processes its logits in place (see decode).
+        ``stop`` (sampling.check_stop_args' dict, or None): per-row stopping in the bookkeeping launch of the selection (DESIGN.md
+        "Per-row stopping"); armed with ``eos_token`` (the pad id, the first eos id) on the prefill / extend call and passed
+        again to every cached step; not with ``beam``.
         ``lengths`` (int [B], 1 <= len_b <= S; prefill with use_cache=True only): the rows of ``inputs_embeds`` are prompts
         of different lengths, right-padded to S.  Row b's logits are those of its position len_b - 1, and the cache keeps one
         write position per row (len_b, then + 1 per step) -- see DESIGN.md, "Ragged batches"."""
         extending = past_key_values is not None and inputs_embeds is not None
+        if stop is not None and beam is not None:
+            raise NotImplementedError("per-row stopping is not combined with beam search")
         if lengths is not None and (labels is not None or (past_key_values is not None and not extending) or not use_cache):
             raise ValueError("lengths= applies to the prefill call and to inputs_embeds appended to a cache (use_cache=True, no "
                              "labels); a ragged cache keeps its per-row positions for the steps that follow")
@@ -578,7 +592,7 @@ class LMEngine:
             logits, cache, full = self.extend(past_key_values, inputs_embeds, lengths=lengths, cache_hint=cache_hint)
             out = LMOutput(logits=logits.unsqueeze(1), past_key_values=cache, hidden_states=None, loss=None, full_logits=full)
             if eos_token is not None:
-                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, None, processors)
+                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, None, processors, stop)
             return out
         if past_key_values is not None:
             if not feed_back and input_ids is None:
@@ -593,12 +607,12 @@ class LMEngine:
                 rows = []
                 for i in range(T):      # only the LAST position selects a token (history / RNG step / eos latch untouched before)
                     lg, tok = self.decode(input_ids[:, i:i + 1], past_key_values, sampling=sampling, select=i == T - 1,
-                                          beam=beam, processors=processors)
+                                          beam=beam, processors=processors, stop=stop)
                     rows.append(lg.clone())
                 return LMOutput(logits=torch.stack(rows, 1), past_key_values=past_key_values, next_token=tok, loss=None,
                                 eos_state=past_key_values.sample_state)
             logits, tok = self.decode(None if feed_back else input_ids, past_key_values, sampling=sampling, beam=beam,
-                                      processors=processors)
+                                      processors=processors, stop=stop)
             return LMOutput(logits=logits.unsqueeze(1), past_key_values=past_key_values, next_token=tok, loss=None,
                             eos_state=past_key_values.sample_state)
         if inputs_embeds is None:
@@ -608,7 +622,7 @@ class LMEngine:
             # generate() only reads the last position, so only that row is computed
             out = LMOutput(logits=logits.unsqueeze(1), past_key_values=cache, hidden_states=hs, loss=None)
             if eos_token is not None:
-                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, beam, processors)
+                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, beam, processors, stop)
             return out
         x, hs = self._blocks_prefill(inputs_embeds, None, output_hidden_states)
         B, S, _ = inputs_embeds.shape
@@ -640,7 +654,32 @@ class LMEngine:
             cache.suppress[: len(ids)].copy_(torch.tensor(ids, dtype=torch.int32), non_blocking=True)
             cache.suppress_ids = ids
 
-    def _arm_first_token(self, out: LMOutput, logits, cache: KVCache, eos_token, seed, sampling, beam, processors=None):
+    @staticmethod
+    def stop_mode(stop):
+        """None (the reference's rule: mg_sample_finish) or (eos ids, stop sequences): the stop mode that travels beside the
+        selection mode.  The pad id is the first eos id."""
+        if stop is None or isinstance(stop, StopMode):
+            return stop
+        from .sampling import check_stop_args
+        d = check_stop_args(list(stop["eos_ids"]), list(stop.get("stop_seqs", ())), True)
+        return StopMode((d["eos_ids"], d["stop_seqs"]))
+
+    def _arm_stop(self, cache: KVCache, stop):
+        """The stop table of ``stop`` in the cache's device buffer (written only when it differs from what the buffer holds;
+        never inside a captured step: decode() calls this before it captures or replays), and the finish record allocated."""
+        if stop is None:
+            return
+        ids = list(stop[0]) + [t for q in stop[1] for t in q]
+        if any(t >= self.V for t in ids):
+            raise ValueError(f"eos ids and stop sequences must be token ids in [0, {self.V}), got {[t for t in ids if t >= self.V]}")
+        if cache.stop_table is None:
+            cache.stop_table = torch.zeros(ops.STOP_TABLE_INTS, dtype=torch.int32, device=self.device)
+            cache.finish = torch.zeros(cache.B, 2, dtype=torch.int32, device=self.device)
+        if tuple(stop) != cache.stop_held:
+            cache.stop_table.copy_(ops.stop_table(stop[0], stop[1]), non_blocking=True)
+            cache.stop_held = tuple(stop)
+
+    def _arm_first_token(self, out: LMOutput, logits, cache: KVCache, eos_token, seed, sampling, beam, processors=None, stop=None):
         """generate(): the first token of the loop selected from the prefill / extend logits, device-side bookkeeping armed."""
         if cache.eos != int(eos_token):        # the eos id is a launch argument of the captured bookkeeping kernel
             cache.eos = int(eos_token)
@@ -656,7 +695,13 @@ class LMEngine:
         if proc is not None:       # step 0 of the rules on a copy: the caller's .logits stay raw
             self._arm_processors(cache, proc)
             logits = logits.clone()
-        out["next_token"] = self.select_token(logits, cache, mode, out=st.token, proc=proc)
+        stop = self.stop_mode(stop)
+        if stop is not None:       # every row unfinished again
+            if int(eos_token) != stop[0][0]:
+                raise ValueError(f"per-row stopping pads with the first eos id: eos_token must be {stop[0][0]}, got {eos_token}")
+            self._arm_stop(cache, stop)
+            cache.finish.copy_(torch.tensor([[-1, 0]] * cache.B, dtype=torch.int32), non_blocking=True)
+        out["next_token"] = self.select_token(logits, cache, mode, out=st.token, proc=proc, stop=stop)
         out["eos_state"] = cache.sample_state
 
     def embed_ids(self, ids: torch.Tensor) -> torch.Tensor:
@@ -949,30 +994,39 @@ class LMEngine:
         return toks.clone(), bm.fin_score.view(bm.B, bm.k)[:, :n_ret].reshape(-1).clone(), lens
 
     def select_token(self, logits: torch.Tensor, cache: KVCache, mode, out: Optional[torch.Tensor] = None,
-                     advance: bool = False, clear: Optional[torch.Tensor] = None, proc=None) -> torch.Tensor:
+                     advance: bool = False, clear: Optional[torch.Tensor] = None, proc=None, stop=None) -> torch.Tensor:
         """next token of every row from fp32 logits (B, V): greedy argmax (mode None; reference sampling.py:96-97) or the
         sampled branch (mode = (temperature, top_k, top_p); :99-107), then the loop bookkeeping in one small launch
         (all-eos step, step counter, token history, and -- inside a decode step -- the KV write position).  Enqueue-only:
         used inside the captured token step and, eagerly, on the prefill logits.  A beam mode (beam_mode) runs the beam step
         instead: the selected token of every row lands in cache.beam's token buffer (the decode state's st.token).
         ``proc`` (proc_mode; the ids already in cache.suppress, _arm_processors): the logits processors, one launch IN PLACE on
-        ``logits`` immediately before the selection -- on the raw logits, or as log_softmax + rules in front of the beam step."""
+        ``logits`` immediately before the selection -- on the raw logits, or as log_softmax + rules in front of the beam step.
+        ``stop`` (stop_mode; the table already in cache.stop_table, _arm_stop): the bookkeeping launch is the per-row one
+        (ops.sample_finish_rows) -- a finished row's token becomes the pad id in place --, and min_new_tokens bans every eos id."""
         is_beam = isinstance(mode, tuple) and bool(mode) and mode[0] == "beam"
         if proc is not None:
+            more = {} if stop is None or len(stop[0]) < 2 else dict(eos_more=cache.stop_table[1:ops.STOP_MAX_EOS],
+                                                                    n_eos_more=len(stop[0]) - 1)
             ops.logits_process(logits, cache.sample_state, cache.history, repetition_penalty=proc[0], no_repeat_ngram_size=proc[1],
                                min_new_tokens=proc[2], eos=cache.eos, suppress=cache.suppress, n_suppress=len(proc[3]),
-                               normalize=is_beam)
+                               normalize=is_beam, **more)
         if is_beam:
             return self._select_beam(logits, cache, mode, advance, normalized=proc is not None)
         if mode is None:
             tok = ops.argmax(logits, out=out)
         else:
             tok = ops.sample(logits, mode[0], mode[1], mode[2], cache.seed, cache.sample_state, out=out)
+        if stop is not None:
+            ops.sample_finish_rows(tok, cache.sample_state, cache.stop_table, len(stop[0]), len(stop[1]), stop[0][0], cache.finish,
+                                   d_pos=cache.d_pos if advance else None, history=cache.history, clear=clear,
+                                   clear_stride=16 if clear is not None else 1, pos_stride=cache.pos_stride)
+            return tok
         ops.sample_finish(tok, cache.eos, cache.sample_state, d_pos=cache.d_pos if advance else None, history=cache.history,
                           clear=clear, clear_stride=16 if clear is not None else 1, pos_stride=cache.pos_stride)
         return tok
 
-    def _decode_step(self, cache: KVCache, st, mode=None, feed_back: bool = False, proc=None):
+    def _decode_step(self, cache: KVCache, st, mode=None, feed_back: bool = False, proc=None, stop=None):
         """Enqueue one token step for all B sequences (graph-capturable: no
         allocation, no sync, position read from cache.d_pos on the device): embedding, per layer the launch sequence of the
         kind planned for it (st.kinds, _ensure_decode_state), the head, token selection.
@@ -993,7 +1047,7 @@ class LMEngine:
         if mode == "noselect":
             ops.advance_pos(cache.d_pos, pos_stride=cache.pos_stride)   # teacher-forced position: nothing selected, nothing recorded
         else:
-            self.select_token(st.logits[:, : self.V], cache, mode, out=st.token, advance=True, proc=proc)
+            self.select_token(st.logits[:, : self.V], cache, mode, out=st.token, advance=True, proc=proc, stop=stop)
 
     # One method per block kind (_block_kind): x -> xn for layer li.  ``src`` holds the block's weight-streaming operands: the
     # layer itself, or its e4m3 / MXFP4 copies (ly.w8 / ly.w4) under W8A16 / W4A16 -- the same launches.  On a ragged cache (pos_stride 1) every
@@ -1122,14 +1176,16 @@ class LMEngine:
         return st
 
     def decode(self, input_ids: Optional[torch.Tensor], cache: KVCache, use_graph: bool = True, sampling=None, select: bool = True,
-               beam=None, processors=None):
+               beam=None, processors=None, stop=None):
         """One cached step.  Returns (fp32 logits (B,V) view, selected token (B,) view: greedy, or sampled when
         ``sampling = (temperature, top_k, top_p)``); both are overwritten by the next step.  ``input_ids=None`` feeds the
         previously selected tokens back without leaving the device.  ``select=False`` (teacher-forced positions of a
         multi-token call): no token is selected -- the history, the RNG step counter and the all-eos latch are left alone,
         only the KV write position advances; the returned token view is stale.
         ``processors`` (forward): the logits processors run in place on the step's logits before the selection, so the
-        returned logits are then the PROCESSED ones (beam search: the processed log_softmax scores)."""
+        returned logits are then the PROCESSED ones (beam search: the processed log_softmax scores).
+        ``stop`` (forward): per-row stopping -- the cache must have been armed with it (its finish record reset) by the prefill /
+        extend call; the returned token view holds the pad id for rows that had finished."""
         if cache.pos >= cache.Smax:
             raise ValueError(f"KV cache full (Smax={cache.Smax}); pass a larger cache_hint / max_steps")
         if cache.B > 16:
@@ -1158,19 +1214,28 @@ class LMEngine:
             mode = "noselect"
         proc = self.proc_mode(processors) if select else None
         self._arm_processors(cache, proc)
+        stop = self.stop_mode(stop) if select else None
+        if stop is not None:
+            if beam is not None:
+                raise NotImplementedError("per-row stopping is not combined with beam search")
+            if cache.finish is None:
+                raise ValueError("per-row stopping needs a cache armed for it (prefill with eos_token= and stop=)")
+            self._arm_stop(cache, stop)
         key = (mode, feed_back)
         if proc is not None:        # the values are launch arguments of the captured step (the suppress ids are not: their count is)
             key += (tuple(proc[:3]) + (len(proc[3]),),)
+        if stop is not None:        # the counts and the pad id are launch arguments, the table's contents are not
+            key += (("stop", len(stop[0]), len(stop[1]), stop[0][0]),)
         if not use_graph:
-            self._decode_step(cache, st, mode, feed_back, proc)
+            self._decode_step(cache, st, mode, feed_back, proc, stop)
         elif key in st.graphs:
             st.graphs[key].replay()
         elif st.steps == 0:
-            self._decode_step(cache, st, mode, feed_back, proc)    # first step eager (loads code objects)
+            self._decode_step(cache, st, mode, feed_back, proc, stop)    # first step eager (loads code objects)
         else:
             g = torch.cuda.CUDAGraph()            # hipGraph on ROCm
             with torch.cuda.graph(g):
-                self._decode_step(cache, st, mode, feed_back, proc)
+                self._decode_step(cache, st, mode, feed_back, proc, stop)
             st.graphs[key] = g
             g.replay()
         st.steps += 1

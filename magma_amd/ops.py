@@ -650,6 +650,51 @@ def sample_finish(token: torch.Tensor, eos: int, state: torch.Tensor, d_pos: Opt
           "mg_sample_finish")
 
 
+STOP_MAX_EOS, STOP_MAX_SEQ, STOP_MAX_LEN = 8, 16, 16                   # include/magma_hip.h MG_STOP_*
+STOP_TABLE_INTS = STOP_MAX_EOS + STOP_MAX_SEQ + STOP_MAX_SEQ * STOP_MAX_LEN
+STOP_EOS, STOP_SEQ = 0x100, 0x200                                       # finish[b][1] = reason | index
+
+
+def stop_table(eos_ids, stop_seqs=()) -> torch.Tensor:
+    """The host image of mg_sample_finish_rows' table (int32 [STOP_TABLE_INTS]): eos ids | sequence lengths | sequence tokens."""
+    eos_ids, stop_seqs = [int(t) for t in eos_ids], [[int(t) for t in q] for q in stop_seqs]
+    assert 1 <= len(eos_ids) <= STOP_MAX_EOS and len(stop_seqs) <= STOP_MAX_SEQ
+    assert all(1 <= len(q) <= STOP_MAX_LEN for q in stop_seqs)
+    t = torch.zeros(STOP_TABLE_INTS, dtype=torch.int32)
+    t[: len(eos_ids)] = torch.tensor(eos_ids, dtype=torch.int32)
+    for j, q in enumerate(stop_seqs):
+        t[STOP_MAX_EOS + j] = len(q)
+        off = STOP_MAX_EOS + STOP_MAX_SEQ + j * STOP_MAX_LEN
+        t[off: off + len(q)] = torch.tensor(q, dtype=torch.int32)
+    return t
+
+
+def sample_finish_rows(token: torch.Tensor, state: torch.Tensor, table: torch.Tensor, n_eos: int, n_seq: int, pad: int,
+                       finish: torch.Tensor, d_pos: Optional[torch.Tensor] = None, delta: int = 1,
+                       history: Optional[torch.Tensor] = None, clear: Optional[torch.Tensor] = None, clear_stride: int = 1, *,
+                       pos_stride: int = 0):
+    """sample_finish with per-row stopping (mg_sample_finish_rows; host statement: sampling.stop_update): a row whose
+    ``finish[b, 0]`` >= 0 gets ``pad`` into ``token[b]`` (in place) and its history; any other row's token is recorded and tested
+    against the first ``n_eos`` eos ids and ``n_seq`` stop sequences of the device ``table`` (stop_table), and
+    ``finish[b] = (step, STOP_EOS | i or STOP_SEQ | j)`` when it finishes.  ``state[1]`` records the first step at which no row
+    is unfinished.  Enqueue-only."""
+    _need_gpu(token, state, table, finish, d_pos, history)
+    B = token.numel()
+    ps = 0 if d_pos is None else _pos_stride(d_pos, B, pos_stride)
+    assert token.dtype == torch.int64 and token.is_contiguous() and state.dtype == torch.int32 and state.numel() >= 2
+    assert table.dtype == torch.int32 and table.is_contiguous() and table.numel() >= STOP_TABLE_INTS
+    assert finish.dtype == torch.int32 and finish.is_contiguous() and finish.shape == (B, 2)
+    if history is not None:
+        assert history.dtype == torch.int64 and history.ndim == 2 and history.stride(1) == 1 and history.shape[0] == B
+    if clear is not None:
+        assert clear.dtype == torch.int32 and clear.is_contiguous()
+    check(L.load().mg_sample_finish_rows(token.data_ptr(), B, state.data_ptr(), _p(d_pos), delta, _p(history),
+                                         0 if history is None else history.stride(0), 0 if history is None else history.shape[1],
+                                         _p(clear), 0 if clear is None else clear.numel() // clear_stride, clear_stride, ps,
+                                         table.data_ptr(), int(n_eos), int(n_seq), int(pad), finish.data_ptr(), _stream()),
+          "mg_sample_finish_rows")
+
+
 def advance_pos(d_pos: torch.Tensor, delta: int = 1, *, pos_stride: int = 0):
     """d_pos[0] += delta; with ``pos_stride=1`` every entry of d_pos (one position per row) += delta."""
     ps = _pos_stride(d_pos, d_pos.numel(), pos_stride)
@@ -658,13 +703,15 @@ def advance_pos(d_pos: torch.Tensor, delta: int = 1, *, pos_stride: int = 0):
 
 def logits_process(logits: torch.Tensor, state: torch.Tensor, history: Optional[torch.Tensor], *, repetition_penalty: float = 1.0,
                    no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, eos: int = -1,
-                   suppress: Optional[torch.Tensor] = None, n_suppress: Optional[int] = None, normalize: bool = False):
+                   suppress: Optional[torch.Tensor] = None, n_suppress: Optional[int] = None, normalize: bool = False,
+                   eos_more: Optional[torch.Tensor] = None, n_eos_more: Optional[int] = None):
     """The logits processors (mg_logits_process_f32; host statement: sampling.process_logits) in place on the fp32 rows
     ``logits`` (R, V): repetition penalty, no-repeat n-gram, min-new-tokens, suppress, in transformers' order.  ``state[0]`` is
     the step (tokens generated so far, read on the device), ``history`` (R, >= step) int64 the rows' tokens, ``suppress`` a
     device int32 array of which the first ``n_suppress`` (default: all) ids count.  ``normalize``: log_softmax first (the beam
-    form, for beam_topk(normalized=True)).  Enqueue-only."""
-    _need_gpu(logits, state, history, suppress)
+    form, for beam_topk(normalized=True)).  ``eos_more``: a device int32 array of which the first ``n_eos_more`` (default: all,
+    at most 8) are further eos ids the min-new-tokens rule bans (None: ``eos`` alone).  Enqueue-only."""
+    _need_gpu(logits, state, history, suppress, eos_more)
     assert logits.dtype == torch.float32 and logits.ndim == 2 and logits.stride(1) == 1
     assert state.dtype == torch.int32 and state.numel() >= 1
     R, V = logits.shape
@@ -674,10 +721,15 @@ def logits_process(logits: torch.Tensor, state: torch.Tensor, history: Optional[
         assert suppress.dtype == torch.int32 and suppress.is_contiguous()
     ns = (0 if suppress is None else suppress.numel()) if n_suppress is None else int(n_suppress)
     assert ns == 0 or (suppress is not None and ns <= suppress.numel())
+    if eos_more is not None:
+        assert eos_more.dtype == torch.int32 and eos_more.is_contiguous()
+    nm = (0 if eos_more is None else eos_more.numel()) if n_eos_more is None else int(n_eos_more)
+    assert nm == 0 or (eos_more is not None and nm <= eos_more.numel())
     check(L.load().mg_logits_process_f32(logits.data_ptr(), logits.stride(0), R, V, state.data_ptr(), _p(history),
                                          0 if history is None else history.stride(0), 0 if history is None else history.shape[1],
                                          float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens), int(eos),
-                                         _p(suppress), ns, 1 if normalize else 0, _stream()), "mg_logits_process_f32")
+                                         _p(suppress), ns, 1 if normalize else 0, _p(eos_more) if nm else None, nm, _stream()),
+          "mg_logits_process_f32")
     return logits
 
 

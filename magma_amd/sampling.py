@@ -10,7 +10,7 @@ a device-side record read every few steps.  ``top_k_filter`` / ``top_p_filter``
 below are the host statements of the same rules (pinned to the reference's own
 functions, tests/test_oracle_pins.py) and serve LM objects other than the engine."""
 import os
-from typing import Callable, List, Tuple, Union
+from typing import Callable, List, NamedTuple, Tuple, Union
 
 import torch
 import torch.nn.functional as F
@@ -117,7 +117,7 @@ def process_logits(scores, history, step: int, *, repetition_penalty: float = 1.
       repetition penalty p   every distinct token t of the row's history, once: x[t] = x[t] * p if x[t] < 0 else x[t] / p
       no-repeat n-gram n     if step >= n: every window start w in [0, step - n] whose n - 1 tokens equal the last n - 1 tokens
                              bans history[w + n - 1] (-inf); n = 1 bans every generated token
-      min new tokens         step < min_new_tokens: x[eos] = -inf
+      min new tokens         step < min_new_tokens: x[eos] = -inf (``eos_token``: one id, or a sequence of ids -- every one)
       suppress               x[t] = -inf for every listed t
     Greedy and sampled selection apply this to the raw logits (before temperature / top-k / top-p), beam search to
     log_softmax(logits) without renormalising, as transformers does."""
@@ -137,11 +137,119 @@ def process_logits(scores, history, step: int, *, repetition_penalty: float = 1.
         banned.scatter_(1, torch.where(match, windows[..., -1], V), True)       # non-matching windows land in a spare column
         x = x.masked_fill(banned[:, :V], float("-inf"))
     if step < int(min_new_tokens) and eos_token is not None:
-        x[:, int(eos_token)] = float("-inf")
+        if isinstance(eos_token, (list, tuple)):
+            x[:, torch.tensor([int(t) for t in eos_token], dtype=torch.int64)] = float("-inf")
+        else:
+            x[:, int(eos_token)] = float("-inf")
     ids = list(suppress_tokens) if suppress_tokens is not None else []
     if ids:
         x[:, torch.tensor(ids, dtype=torch.int64)] = float("-inf")
     return x
+
+
+MAX_EOS_IDS, MAX_STOP_SEQS, MAX_STOP_LEN = 8, 16, 16
+REASON_NONE, REASON_EOS, REASON_STOP = 0, 1, 2
+
+
+class Finish(NamedTuple):
+    """How every row of a per-row generate() call ended (``return_finish=True``)."""
+    kept: torch.Tensor          # int64 [B]: the generated tokens of the row that count, the finishing token included
+    reason: List[str]           # "eos" | "stop" | "length" (the row ran to the end of the call)
+    index: List[int]            # which eos id / which stop sequence (-1 for "length")
+
+
+def check_stop_args(eos_token, stop_sequences=None, stop_per_row=None, vocab: int = None, encode: Callable = None):
+    """ValueError for stopping arguments generate() does not take.  Returns None when the call keeps the reference's rule (one
+    eos id, the batch ends at the first step at which every row selects it), else dict(eos_ids tuple of 1 to 8 ints,
+    stop_seqs tuple of at most 16 tuples of 1 to 16 ints): the per-row rule of ``stop_update``.  ``stop_per_row`` None means
+    per-row exactly when ``eos_token`` is a sequence or ``stop_sequences`` is given.  ``vocab``: the number of logits V, when
+    known -- every id must lie in [0, V).  ``encode``: turns a ``str`` entry of ``stop_sequences`` into token ids."""
+    def ident(t, what):
+        if isinstance(t, bool) or not isinstance(t, int) or t < 0 or (vocab is not None and t >= vocab):
+            raise ValueError(f"{what} must be token ids in [0, {'V' if vocab is None else vocab}), got {t!r}")
+        return t
+
+    if torch.is_tensor(eos_token):
+        eos_token = eos_token.tolist()
+    listed = isinstance(eos_token, (list, tuple))
+    eos_ids = tuple(eos_token) if listed else (eos_token,)
+    if not 1 <= len(eos_ids) <= MAX_EOS_IDS:
+        raise ValueError(f"eos_token takes 1 to {MAX_EOS_IDS} ids, got {len(eos_ids)}")
+    wanted = listed or stop_sequences is not None
+    if stop_per_row is not None and not isinstance(stop_per_row, bool):
+        raise ValueError(f"stop_per_row must be None, True or False, got {stop_per_row!r}")
+    if stop_per_row is False and wanted:
+        raise ValueError("stop_per_row=False keeps the reference's rule of one eos id for the whole batch: it takes neither a "
+                         "list of eos ids nor stop_sequences")
+    if not (wanted or stop_per_row):
+        return None                       # today's call: its eos id is taken as it always was
+    eos_ids = tuple(ident(t, "eos_token") for t in eos_ids)
+    seqs = []
+    if stop_sequences is not None:
+        if isinstance(stop_sequences, str) or not isinstance(stop_sequences, (list, tuple)):
+            raise ValueError("stop_sequences must be a list of token-id sequences or strings")
+        if len(stop_sequences) > MAX_STOP_SEQS:
+            raise ValueError(f"stop_sequences takes at most {MAX_STOP_SEQS} entries, got {len(stop_sequences)}")
+        for q in stop_sequences:
+            if isinstance(q, str):
+                if encode is None:
+                    raise ValueError(f"the stop sequence {q!r} is text and this model has no tokenizer to encode it")
+                q = encode(q)
+            if torch.is_tensor(q):
+                q = q.tolist()
+            if not isinstance(q, (list, tuple)) or not 1 <= len(q) <= MAX_STOP_LEN:
+                raise ValueError(f"a stop sequence is 1 to {MAX_STOP_LEN} token ids, got {q!r}")
+            seqs.append(tuple(ident(t, "stop_sequences") for t in q))
+    return dict(eos_ids=eos_ids, stop_seqs=tuple(seqs))
+
+
+def stop_update(history, step: int, done, eos_ids, stop_seqs=()):
+    """The per-row stopping rule, host statement (the device kernel is csrc/sampling.hip, sample_finish_rows_kernel): the row
+    test of transformers' ``GenerationMixin._sample`` -- EosTokenCriteria with a list of ids, plus stop sequences over token ids
+    -- with the prompt passed as embeddings: only the tokens generated by this call take part.
+
+    ``history`` (R, > step) int64 holds every row's tokens of steps 0 .. step (finished rows: the pad id from the step after
+    they finished), ``done`` (R,) bool the rows that finished at an earlier step.  A row that is not done finishes at this step
+      eos    if history[r, step] is one of ``eos_ids`` (1 to 8): reason (REASON_EOS, index of the id), tested first;
+      stop   if history[r, :step + 1] ends with one of ``stop_seqs`` (at most 16 of 1 to 16 ids; one longer than step + 1
+             cannot match): reason (REASON_STOP, lowest matching index).
+    Returns (done (R,) bool including this step's rows, reason (R, 2) int64 -- (REASON_NONE, -1) for every row that did not
+    finish AT this step).  The caller keeps the finishing token, writes ``eos_ids[0]`` (the pad id) for a done row from the next
+    step on, and ends the loop after the first step at which every row is done."""
+    hist = torch.as_tensor(history).to(torch.int64).cpu()
+    done = torch.as_tensor(done).to(torch.bool).cpu().clone()
+    R = hist.shape[0]
+    reason = torch.tensor([[REASON_NONE, -1]] * R, dtype=torch.int64).view(R, 2)
+    for r in range(R):
+        if bool(done[r]):
+            continue
+        t = int(hist[r, step])
+        hit = None
+        for i, e in enumerate(eos_ids):
+            if t == int(e):
+                hit = (REASON_EOS, i)
+                break
+        if hit is None:
+            for j, q in enumerate(stop_seqs):
+                n = len(q)
+                if 1 <= n <= step + 1 and hist[r, step + 1 - n: step + 1].tolist() == [int(x) for x in q]:
+                    hit = (REASON_STOP, j)
+                    break
+        if hit is not None:
+            done[r] = True
+            reason[r, 0], reason[r, 1] = hit
+    return done, reason
+
+
+def finish_from_record(record, n_gen: int) -> Finish:
+    """``record`` (B, 2) integers = (step at which the row finished or -1, reason * 256 + index) -- the device's finish record,
+    or the host loop's in the same form -- of a call that kept n_gen steps."""
+    rec = torch.as_tensor(record).to(torch.int64).cpu()
+    kept = torch.where(rec[:, 0] >= 0, rec[:, 0] + 1, torch.full_like(rec[:, 0], n_gen)).clamp(max=n_gen)
+    names = {REASON_NONE: "length", REASON_EOS: "eos", REASON_STOP: "stop"}
+    reason = [names[int(c) >> 8] if int(f) >= 0 else "length" for f, c in rec.tolist()]
+    index = [int(c) & 255 if int(f) >= 0 else -1 for f, c in rec.tolist()]
+    return Finish(kept, reason, index)
 
 
 MAX_BEAMS = 16
@@ -303,7 +411,8 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
              lengths=None, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False,
              num_return_sequences: int = 1, return_scores: bool = False, past_key_values=None,
              return_past_key_values: bool = False, *, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
-             min_new_tokens: int = 0, suppress_tokens=None) -> Union[List[str], torch.Tensor]:
+             min_new_tokens: int = 0, suppress_tokens=None, stop_sequences=None, stop_per_row: bool = None,
+             return_finish: bool = False) -> Union[List[str], torch.Tensor]:
     """reference sampling.py:43-121.  Token selection (argmax, or top-k / the reference's top-p rule / softmax /
     multinomial) and the ``(next_token == eos).all()`` test run on the device inside the captured token step; the host
     reads the recorded "first all-eos step" every ``eos_check_every`` steps (default 8, MAGMA_EOS_CHECK_EVERY) instead of
@@ -338,10 +447,34 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     beam search to log_softmax(logits) before the running score is added.  The prompt is embeddings, so the rules see the
     tokens generated by THIS call only: a continued conversation (``past_key_values``) starts with an empty history again.
     The HIP engine applies them inside the captured token step (one small launch in front of the selection); at the
-    defaults nothing is launched and the output is bit for bit what it was."""
-    eos_token = eos_token or model.eos_token
+    defaults nothing is launched and the output is bit for bit what it was.
+
+    Per-row stopping (DESIGN.md "Per-row stopping"; greedy and sampled): the rule of transformers' ``_sample`` (``stop_update``
+    above) instead of the reference's -- a row that finished stays finished and is padded with ``eos_token[0]``, the call ends
+    after the first step at which every row is finished, the output is s + that step + 1 wide.  ``eos_token`` may be a sequence
+    of 1 to 8 ids (a row finishes on any of them; ``min_new_tokens`` bans every one).  ``stop_sequences``: at most 16 entries,
+    each 1 to 16 token ids or a ``str`` that ``model.tokenizer.encode`` turns into ids; a row finishes when the tokens it
+    generated IN THIS CALL end with one of them, and keeps them.  The match is over token ids: text that the model spells with
+    other tokens is not found (unlike transformers' ``stop_strings``); ``min_new_tokens`` does not hold a stop sequence back.
+    ``stop_per_row``: None = per-row exactly when ``eos_token`` is a sequence or ``stop_sequences`` is given; True with one eos
+    id gives a plain batch the per-row rule (it ends when every row HAS emitted eos); False with either raises ValueError.
+    ``stop_on_eos=False`` still runs all ``max_steps``: finished rows are padded, the output has a fixed width.
+    ``return_finish=True`` returns (output, finish) -- (output, past, finish) with a cache --, ``finish`` a ``Finish``: ``kept``
+    int64 [B] (the row's generated tokens that count, the finishing token included), ``reason`` ("eos" | "stop" | "length" per
+    row) and ``index`` (which eos id / sequence).  ``decode=True`` then cuts every row at its own ``kept``.  The HIP engine runs
+    the rule in the bookkeeping launch of the captured token step (no further launch, no host round trip); any other LM object
+    runs the host statement.  Not combined with beam search (NotImplementedError)."""
+    if eos_token is None or (isinstance(eos_token, int) and not eos_token):
+        eos_token = model.eos_token
     early_stopping = check_beam_args(num_beams, num_return_sequences, early_stopping)
     proc = check_processor_args(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, _logit_count(model))
+    stop = check_stop_args(eos_token, stop_sequences, stop_per_row, _logit_count(model),
+                           getattr(getattr(model, "tokenizer", None), "encode", None))
+    if (stop is not None or return_finish) and (num_beams > 1 or return_scores):
+        raise NotImplementedError("per-row stopping (a list of eos ids, stop_sequences, stop_per_row, return_finish) is not "
+                                  "combined with beam search (num_beams > 1 / return_scores=True)")
+    eos_ids = stop["eos_ids"] if stop is not None else (eos_token,)
+    eos_token = eos_ids[0]              # the pad id
     continuing = past_key_values is not None or return_past_key_values
     if continuing and (num_beams > 1 or return_scores):
         raise NotImplementedError("beam search neither continues from nor returns a KV cache (past_key_values / "
@@ -390,6 +523,11 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     if on_device and proc is not None:      # only then: an LM object written before the processors keeps its signature
         from .engine import LMEngine
         first_kw["processors"] = step_kw["processors"] = LMEngine.proc_mode(proc)      # checked once, not once per token
+    if on_device and stop is not None:      # only then, as above
+        from .engine import LMEngine
+        first_kw["stop"] = step_kw["stop"] = LMEngine.stop_mode(stop)
+    if not on_device and stop is not None:
+        done, record = torch.zeros(b, dtype=torch.bool), torch.tensor([[-1, 0]] * b, dtype=torch.int64).view(b, 2)
     if past_key_values is not None:
         start = past_key_values.rows_pos() + (past_key_values.pending >= 0).to(torch.int64) \
             if past_key_values.pending is not None else past_key_values.rows_pos()
@@ -416,7 +554,8 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
             continue
         logits = outputs.logits[:, -1, :].float()            # any other LM object: the reference's host-side arithmetic
         if proc is not None:
-            logits = process_logits(logits.cpu(), out[:, s:n].cpu(), n - s, eos_token=eos_token, **proc).to(logits.device)
+            logits = process_logits(logits.cpu(), out[:, s:n].cpu(), n - s, eos_token=eos_ids if stop is not None else eos_token,
+                                    **proc).to(logits.device)
         if greedy:
             next_token = outputs.next_token.unsqueeze(1) if outputs.get("next_token") is not None and proc is None else \
                 torch.argmax(logits, dim=-1, keepdim=True)
@@ -427,6 +566,17 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
                 logits = top_p_filter(logits, threshold=top_p)
             probs = F.softmax(logits / temperature, dim=-1)
             next_token = torch.multinomial(probs, num_samples=1)
+        if stop is not None:        # the per-row rule (stop_update): finished rows are padded, the others tested
+            next_token = torch.where(done.to(next_token.device)[:, None], torch.full_like(next_token, eos_token), next_token)
+            out[:, n:n + 1] = next_token
+            n += 1
+            was = done
+            done, why = stop_update(out[:, s:n], n - s - 1, done, eos_ids, stop["stop_seqs"])
+            now = done & ~was
+            record[now, 0], record[now, 1] = n - s - 1, why[now, 0] * 256 + why[now, 1]
+            if stop_on_eos and bool(done.all()):
+                break
+            continue
         out[:, n:n + 1] = next_token
         n += 1
         if stop_on_eos and eos_token is not None and bool((next_token == eos_token).all()):
@@ -440,25 +590,54 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     elif on_device:          # one copy of the token history the bookkeeping kernel kept
         out[:, s:n] = past.history[:, : n - s]
     out = out[:, :n]
+    finish = None
+    if stop is not None and (return_finish or continuing or decode):
+        record = past.finish.cpu() if on_device else record           # one host copy
+        finish = finish_from_record(record, n - s)
+    elif return_finish:                                               # the reference's rule: every row ran the whole call
+        finish = finish_from_record(torch.tensor([[-1, 0]] * b).view(b, 2), n - s)
     if continuing:      # the cache keeps the conversation (a continued one too: it was advanced in place and stays continuable)
         if past_key_values is None:
             start = lengths if lengths is not None else torch.full((b,), s, dtype=torch.int64)
         else:
             start = start + (lengths if lengths is not None else s)
-        keep_conversation(past, start, n - s, eos_token)
+        keep_conversation(past, start, n - s, eos_token, finish if stop is not None else None)
         model.lm.engine.detach_cache(past)
-    if decode:
+    if decode and stop is not None:      # every row up to its own kept count; the eos that finished it is dropped as below
+        first = lengths.tolist() if lengths is not None else [s] * b
+        rows = []
+        for r in range(b):
+            ids = out[r, first[r]: first[r] + int(finish.kept[r])].tolist()
+            if finish.reason[r] == "eos":
+                ids = ids[:-1]
+            rows.append(model.tokenizer.decode([t for t in ids if t != model.image_token]))
+        out = rows
+    elif decode:
         out = [model.tokenizer.decode(remove_tokens_after_eos(row, eos_token, model.image_token)) for row in out]
     model.train(was_training)
-    return (out, past) if return_past_key_values else out
+    ret = (out, past) if return_past_key_values else (out,)
+    if return_finish:
+        ret += (finish,)
+    return ret if len(ret) > 1 else ret[0]
 
 
-def keep_conversation(cache, start: torch.Tensor, n_gen: int, eos_token):
+def keep_conversation(cache, start: torch.Tensor, n_gen: int, eos_token, finish: Finish = None):
     """After a generate() call of n_gen kept steps whose first token sits at position start[b] of row b: every row keeps its
     generated tokens before its first eos.  A row that emitted eos is cut back to just before it (its later slots are
-    overwritten by what comes next); a row that did not keeps its last token pending, to be fed first by the next call."""
+    overwritten by what comes next); a row that did not keeps its last token pending, to be fed first by the next call.
+    ``finish`` (a per-row call's Finish): a row finished by an eos id at step f is cut back to just before it; a row finished by
+    a stop sequence at step f keeps tokens 0 .. f, token f pending (the stop text is part of the conversation); the pad tokens
+    fed after either wrote K / V past the row's position, which set_rows cuts off like the tokens after an eos."""
     hist = cache.history[:, :n_gen].cpu()                  # one host sync
     pos, pend = start.clone().to(torch.int64), torch.full((cache.B,), -1, dtype=torch.int64)
+    if finish is not None:
+        for r in range(cache.B):
+            last = int(finish.kept[r]) - 1                 # the finishing step, or n_gen - 1 for an unfinished row
+            pos[r] += last
+            if finish.reason[r] != "eos":
+                pend[r] = int(hist[r, last])
+        cache.set_rows(pos, pend)
+        return
     for r in range(cache.B):
         hits = (hist[r] == eos_token).nonzero() if eos_token is not None else torch.empty(0)
         if hits.numel():
