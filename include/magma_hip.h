@@ -91,8 +91,9 @@ const char* mg_version(void);
  *  10  logits processors: added mg_logits_process_f32 and mg_beam_topk_scores_f32 (nothing moved).
  *  11  MXFP4 decode weights (W4A16): mg_skinny_desc grew by `w_mx4_scale` at its end (NULL = as before; nothing else moved).
  *  12  per-row stopping: added mg_sample_finish_rows; mg_logits_process_f32 gained `eos_more` / `n_eos_more` (before the stream;
- *      NULL / 0 = as before): further eos ids the min_new_tokens rule bans. */
-#define MG_ABI_VERSION 12
+ *      NULL / 0 = as before): further eos ids the min_new_tokens rule bans.
+ *  13  transformers' sampler: added mg_sample_warp_f32 (nothing moved). */
+#define MG_ABI_VERSION 13
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -360,6 +361,20 @@ int mg_advance_pos(int32_t* d_pos, int32_t delta, int32_t B, int32_t pos_stride,
 int mg_sample_f32(const float* logits, int64_t ld, int32_t B, int32_t V, float temperature, int32_t top_k, double top_p,
                   const uint64_t* seed, const int32_t* state, int64_t* token, float* filtered, int64_t ld_filtered,
                   void* stream);
+/* transformers' sampler (ABI 13; DESIGN.md "transformers' sampler"): mg_sample_f32's launch with the rules of transformers'
+ * TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper -> MinPLogitsWarper (min_tokens_to_keep = 1) in place of the
+ * reference's filters, then the same draw on the same Philox stream (host statements: magma_amd/sampling.py top_k_filter_ties,
+ * nucleus_filter, min_p_filter).  Arguments as mg_sample_f32, plus min_p; the temperature must be > 0 also for a filter-only call,
+ * because the nucleus is cut from the probabilities at that temperature.
+ *   top_k   every logit below the k-th largest goes; every tie AT the k-th value stays (0 or >= V: off);
+ *   top_p   with q the 2^-40 fixed-point probabilities of the top-k survivors at the temperature, total their sum and
+ *           c = (uint64)((double)(float)(1 - top_p) * 2^40): a token stays iff the mass ranked before it (descending) is below
+ *           max(total - c, 1); of equal logits at the boundary the first ones by index stay (0 or 1: off);
+ *   min_p   a token stays iff x >= max + temperature * log(min_p), i.e. p >= min_p * p_max (0: off);
+ *   the first maximum always stays; -inf entries carry no mass and are never selected.                                        */
+int mg_sample_warp_f32(const float* logits, int64_t ld, int32_t B, int32_t V, float temperature, int32_t top_k, double top_p,
+                       double min_p, const uint64_t* seed, const int32_t* state, int64_t* token, float* filtered,
+                       int64_t ld_filtered, void* stream);
 int mg_sample_finish(const int64_t* token, int32_t B, int64_t eos, int32_t* state, int32_t* d_pos, int32_t delta,
                      int64_t* history, int64_t ld_history, int32_t history_cols, int32_t* clear, int32_t n_clear,
                      int32_t clear_stride, int32_t pos_stride, void* stream);

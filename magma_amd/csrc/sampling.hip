@@ -27,7 +27,19 @@
 //   multinomial  inverse-CDF draw in index order over the same fixed-point weights exp((x - max) / temperature):
 //                target = floor(r * total / 2^64) with r = 64 Philox4x32-10 bits keyed by (seed, step, row); prefix sums
 //                are integer, hence exact and reproducible (tests restate the draw in Python integers / float64).
+//
+// transformers' sampler (mg_sample_warp_f32; DESIGN.md "transformers' sampler"; host statements: sampling.py top_k_filter_ties,
+// nucleus_filter, min_p_filter) is the same body compiled with WARP = true -- the rules of TemperatureLogitsWarper, TopKLogitsWarper,
+// TopPLogitsWarper and MinPLogitsWarper with min_tokens_to_keep = 1, then the same draw:
+//   top-k        every tie at the k-th value stays (no index cut).
+//   top-p        masses at temperature T over the top-k survivors; a token stays iff the mass ranked before it is below
+//                total - (1 - top_p): the same descent with limit = total - c instead of c (total = the sum of the level-0
+//                histogram), the kept set is {key >= t*} instead of "dropped = {key >= t*} minus the maximum", the first ties at t*
+//                by index stay.  The level-0 bins span [max(min, max - 32 T), max].
+//   min-p        a token stays iff x >= max + T log(min_p): one more comparison in `kept`, no sweep.
+// The instance with WARP = false is the kernel as it was.
 #include "common.h"
+#include <type_traits>
 
 namespace {
 
@@ -92,9 +104,15 @@ struct SampleParams {
   float* filtered; int64_t ldf;   // optional [B, V] filtered logits (tests / callers that want the reference's tensor)
 };
 
+struct WarpParams : SampleParams {
+  double log_min_p;           // log(min_p), -inf when min-p is off
+};
+
 constexpr double FIX = 1099511627776.0;   // 2^40
 
-__global__ __launch_bounds__(ST) void sample_kernel(const SampleParams p) {
+template <class P>
+__global__ __launch_bounds__(ST) void sample_kernel(const P p) {
+  constexpr bool WARP = std::is_same<P, WarpParams>::value;
   __shared__ unsigned long long hist64[256];
   __shared__ uint32_t hist32[256];
   __shared__ float shf[ST / 64];
@@ -158,7 +176,7 @@ __global__ __launch_bounds__(ST) void sample_kernel(const SampleParams p) {
       prefix |= bc[0] << shift; mask |= 255u << shift; remaining = bc[1];
       const uint32_t in_bucket = bc[2];
       __syncthreads();
-      if (shift == 0 && in_bucket > remaining) {     // more ties at the threshold than places left: the first ones by index stay
+      if (shift == 0 && in_bucket > remaining && !WARP) {     // more ties at the threshold than places left: the first ones by index stay
         if (tid == 0) {
           uint32_t seen = 0; int cut = 0x7fffffff;
           for (int i = 0; i < V; ++i) if (fkey(x[i]) == prefix) { if (seen == remaining) { cut = i; break; } ++seen; }
@@ -171,7 +189,7 @@ __global__ __launch_bounds__(ST) void sample_kernel(const SampleParams p) {
     }
     tk = prefix;
   }
-  auto alive = [&](int i, uint32_t k) -> bool { return k > tk || (k == tk && i < k_cut); };
+  auto alive = [&](int i, uint32_t k) -> bool { return k > tk || (k == tk && i < k_cut); };      // WARP: k >= tk, every tie stays
 
   // ---------------- first maximum (rank 0 of the reference's sort; never dropped) ----------------
   float mx = -INFINITY, mn = INFINITY;      // mn: smallest finite logit (only spans the top-p level-0 bins)
@@ -183,23 +201,28 @@ __global__ __launch_bounds__(ST) void sample_kernel(const SampleParams p) {
   imax = blk_min_i(imax, shi);
 
   // ---------------- the reference's top-p rule ----------------
-  uint32_t tstar = 0xffffffffu;    // dropped(i) = alive && i != imax && (key > tstar || (key == tstar && i < tie_cut))
-  int tie_cut = 0;
+  uint32_t tstar = WARP ? 0u : 0xffffffffu;    // dropped(i) = alive && i != imax && (key > tstar || (key == tstar && i < tie_cut))
+  int tie_cut = WARP ? 0x7fffffff : 0;         // WARP: kept(i) = alive && (key > tstar || (key == tstar && i < tie_cut)) && x >= min-p bound
   // the reference compares an fp32 tensor with the PYTHON scalar (1 - threshold): the scalar is evaluated in double, then cast
   // to fp32 for the comparison -- top_p arrives as a double so that exactly that value is formed (0.1f for 0.9, not 0.10000002f)
   const double bound = (double)(float)(1.0 - p.top_p);
   if (p.top_p > 0.0 && bound > 0.0) {
+    const float rtp = 1.0f / p.temperature;
+    auto mass = [&](float v) -> float {      // WARP: the probabilities the nucleus is cut from are those at temperature T
+      if constexpr (WARP) return __expf((v - mx) * rtp);
+      else return __expf(v - mx);
+    };
     float z = 0.f;
-    for (int i = tid; i < V; i += ST) if (alive(i, fkey(x[i]))) z += __expf(x[i] - mx);
+    for (int i = tid; i < V; i += ST) if (alive(i, fkey(x[i]))) z += mass(x[i]);
     z = blk_sum(z, shf);
     const float rz = 1.0f / z;
-    const unsigned long long cfix = (unsigned long long)(bound * FIX);
+    unsigned long long cfix = (unsigned long long)(bound * FIX);      // WARP: becomes total - c once level 0 is summed
     // Level 0: 256 LINEAR value bins over [max(min, max - 32), max] (below max - 32 the fixed-point mass is 0), then the four 8-bit levels of
     // the order-preserving key inside the chosen bin.  Any monotone partition keeps the descent's invariant (`above` = mass
     // strictly above the current range), so t* is what four key levels alone would find -- but the key's top byte (sign + high
     // exponent bits) puts nearly all of the 50 000 logits into two or three buckets, i.e. one LDS atomic queue; linear bins
     // spread them.
-    const float lo = fmaxf(mn, mx - 32.0f);
+    const float lo = fmaxf(mn, WARP ? mx - 32.0f * p.temperature : mx - 32.0f);
     const float bscale = mx > lo ? 255.99f / (mx - lo) : 0.f;
     auto bin0 = [&](float v) -> int { const int b = (int)((v - lo) * bscale); return v > lo ? min(b, 255) : 0; };
     uint32_t prefix = 0, mask = 0;
@@ -217,13 +240,27 @@ __global__ __launch_bounds__(ST) void sample_kernel(const SampleParams p) {
           const int vb = bin0(v);
           if (level == 0 || (vb == b0 && (k & mask) == prefix)) {
             const int bucket = level == 0 ? vb : (int)((k >> shift) & 255);
-            const unsigned long long q = (unsigned long long)((double)(__expf(v - mx) * rz) * FIX + 0.5);
+            const unsigned long long q = (unsigned long long)((double)(mass(v) * rz) * FIX + 0.5);
             atomicAdd(&hist64[bucket], q);
             atomicAdd(&hist32[bucket], 1u);
           }
         }
       }
       __syncthreads();
+      if constexpr (WARP) {
+        if (level == 0) {      // limit = total - c, at least 1 so that the first maximum (preceding mass 0) always stays
+          if (tid < 64) {
+            unsigned long long t = hist64[4 * tid] + hist64[4 * tid + 1] + hist64[4 * tid + 2] + hist64[4 * tid + 3];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+            if (tid == 0) bc64[0] = t;
+          }
+          __syncthreads();
+          const unsigned long long total = bc64[0];
+          cfix = total > cfix ? total - cfix : 1ull;
+          __syncthreads();
+        }
+      }
       scan_mass(above, cfix);
       __syncthreads();
       if (level == 0) b0 = (int)bc[0];
@@ -240,7 +277,7 @@ __global__ __launch_bounds__(ST) void sample_kernel(const SampleParams p) {
       while (m < (int)n_eq && s < cfix) { ++m; s += q_eq; }
     }
     tie_cut = 0x7fffffff;
-    if (m < (int)n_eq) {           // rare: only the first m ties (by index) go -- one thread finds the (m+1)-th tie's index
+    if (m < (int)n_eq) {           // rare: only the first m ties (by index) go (WARP: stay) -- one thread finds the (m+1)-th tie's index
       if (tid == 0) {
         int seen = 0, cut = 0x7fffffff;
         for (int i = 0; i < V; ++i) if (fkey(x[i]) == tstar && alive(i, tstar)) { if (seen == m) { cut = i; break; } ++seen; }
@@ -250,11 +287,20 @@ __global__ __launch_bounds__(ST) void sample_kernel(const SampleParams p) {
       tie_cut = (int)bc[2];
     }
   }
+  float minp_bound = -INFINITY;      // WARP: the smallest fp32 that is >= max + T log(min_p)
+  if constexpr (WARP) {
+    if (p.log_min_p > -INFINITY) {
+      const double t = (double)mx + (double)p.temperature * p.log_min_p;
+      minp_bound = (float)t;
+      if ((double)minp_bound < t) minp_bound = nextafterf(minp_bound, INFINITY);
+    }
+  }
   auto kept = [&](int i, float v) -> bool {
     const uint32_t k = fkey(v);
     if (!alive(i, k)) return false;
     if (i == imax) return true;
-    return !(k > tstar || (k == tstar && i < tie_cut));
+    if constexpr (WARP) return (k > tstar || (k == tstar && i < tie_cut)) && v >= minp_bound;
+    else return !(k > tstar || (k == tstar && i < tie_cut));
   };
 
   if (p.filtered) {
@@ -411,7 +457,24 @@ extern "C" int mg_sample_f32(const float* logits, int64_t ld, int32_t B, int32_t
   if (top_k < 0 || top_p < 0.0 || top_p > 1.0) MG_FAIL(MG_ERR_SHAPE, "mg_sample_f32: need top_k >= 0 and 0 <= top_p <= 1");
   if (filtered && ld_filtered < V) MG_FAIL(MG_ERR_SHAPE, "mg_sample_f32: ld_filtered < V");
   SampleParams p{logits, ld, V, temperature, top_k, top_p, seed, state, token, filtered, ld_filtered};
-  hipLaunchKernelGGL(sample_kernel, dim3(B), dim3(ST), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(sample_kernel<SampleParams>, dim3(B), dim3(ST), 0, (hipStream_t)stream, p);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_sample_warp_f32(const float* logits, int64_t ld, int32_t B, int32_t V, float temperature, int32_t top_k,
+                                  double top_p, double min_p, const uint64_t* seed, const int32_t* state, int64_t* token,
+                                  float* filtered, int64_t ld_filtered, void* stream) {
+  if (B <= 0 || V <= 0 || !logits || ld < V) MG_FAIL(MG_ERR_SHAPE, "mg_sample_warp_f32: bad logits / B / V / ld");
+  if (!token && !filtered) MG_FAIL(MG_ERR_SHAPE, "mg_sample_warp_f32: nothing to produce (token and filtered are both null)");
+  if (!(temperature > 0.f) || temperature == INFINITY) MG_FAIL(MG_ERR_SHAPE, "mg_sample_warp_f32: need a finite temperature > 0 (the filters depend on it)");
+  if (token && !state) MG_FAIL(MG_ERR_SHAPE, "mg_sample_warp_f32: sampling needs a state buffer");
+  if (top_k < 0 || !(top_p >= 0.0 && top_p <= 1.0) || !(min_p >= 0.0 && min_p <= 1.0))
+    MG_FAIL(MG_ERR_SHAPE, "mg_sample_warp_f32: need top_k >= 0, 0 <= top_p <= 1 and 0 <= min_p <= 1");
+  if (filtered && ld_filtered < V) MG_FAIL(MG_ERR_SHAPE, "mg_sample_warp_f32: ld_filtered < V");
+  WarpParams p{{logits, ld, V, temperature, top_k, top_p, seed, state, token, filtered, ld_filtered},
+               min_p > 0.0 ? log(min_p) : -(double)INFINITY};
+  hipLaunchKernelGGL(sample_kernel<WarpParams>, dim3(B), dim3(ST), 0, (hipStream_t)stream, p);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }

@@ -630,6 +630,19 @@ class LMEngine:
         return LMOutput(logits=logits, past_key_values=None, hidden_states=hs, loss=None)
 
     @staticmethod
+    def sample_mode(sampling):
+        """None (greedy), (temperature, top_k, top_p) -- the reference's filters, ops.sample -- or ("warp", temperature, top_k,
+        top_p, min_p) -- transformers' sampler, ops.sample_warp (DESIGN.md "transformers' sampler"): the selection mode, with its
+        values normalised so that it can key a captured step."""
+        if sampling is None:
+            return None
+        if sampling[0] == "warp":
+            if len(sampling) != 5:
+                raise ValueError(f'the warp selection mode is ("warp", temperature, top_k, top_p, min_p), got {sampling!r}')
+            return ("warp", float(sampling[1]), int(sampling[2]), float(sampling[3]), float(sampling[4]))
+        return (float(sampling[0]), int(sampling[1]), float(sampling[2]))
+
+    @staticmethod
     def proc_mode(processors):
         """None (nothing is enqueued) or (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress ids): the processor
         mode that travels beside the selection mode."""
@@ -688,7 +701,7 @@ class LMEngine:
         if seed is not None:
             cache.seed.fill_(int(seed) & 0x7fffffffffffffff)
         st = self._ensure_decode_state(cache)      # the first token lands where the decode steps read it back
-        mode = sampling
+        mode = self.sample_mode(sampling)
         if beam is not None:
             mode = self._arm_beam(cache, st, beam)
         proc = self.proc_mode(processors)
@@ -996,7 +1009,8 @@ class LMEngine:
     def select_token(self, logits: torch.Tensor, cache: KVCache, mode, out: Optional[torch.Tensor] = None,
                      advance: bool = False, clear: Optional[torch.Tensor] = None, proc=None, stop=None) -> torch.Tensor:
         """next token of every row from fp32 logits (B, V): greedy argmax (mode None; reference sampling.py:96-97) or the
-        sampled branch (mode = (temperature, top_k, top_p); :99-107), then the loop bookkeeping in one small launch
+        sampled branch (mode = (temperature, top_k, top_p); :99-107 -- or ("warp", temperature, top_k, top_p, min_p):
+        transformers' sampler, sample_mode), then the loop bookkeeping in one small launch
         (all-eos step, step counter, token history, and -- inside a decode step -- the KV write position).  Enqueue-only:
         used inside the captured token step and, eagerly, on the prefill logits.  A beam mode (beam_mode) runs the beam step
         instead: the selected token of every row lands in cache.beam's token buffer (the decode state's st.token).
@@ -1015,6 +1029,8 @@ class LMEngine:
             return self._select_beam(logits, cache, mode, advance, normalized=proc is not None)
         if mode is None:
             tok = ops.argmax(logits, out=out)
+        elif mode[0] == "warp":
+            tok = ops.sample_warp(logits, mode[1], mode[2], mode[3], mode[4], cache.seed, cache.sample_state, out=out)
         else:
             tok = ops.sample(logits, mode[0], mode[1], mode[2], cache.seed, cache.sample_state, out=out)
         if stop is not None:
@@ -1178,7 +1194,8 @@ class LMEngine:
     def decode(self, input_ids: Optional[torch.Tensor], cache: KVCache, use_graph: bool = True, sampling=None, select: bool = True,
                beam=None, processors=None, stop=None):
         """One cached step.  Returns (fp32 logits (B,V) view, selected token (B,) view: greedy, or sampled when
-        ``sampling = (temperature, top_k, top_p)``); both are overwritten by the next step.  ``input_ids=None`` feeds the
+        ``sampling = (temperature, top_k, top_p)`` or ``("warp", temperature, top_k, top_p, min_p)``, sample_mode); both are
+        overwritten by the next step.  ``input_ids=None`` feeds the
         previously selected tokens back without leaving the device.  ``select=False`` (teacher-forced positions of a
         multi-token call): no token is selected -- the history, the RNG step counter and the all-eos latch are left alone,
         only the KV write position advances; the returned token view is stale.
@@ -1203,7 +1220,7 @@ class LMEngine:
         feed_back = input_ids is None
         if not feed_back:
             st.ids.copy_(input_ids.reshape(cache.B, 1))
-        mode = None if sampling is None else (float(sampling[0]), int(sampling[1]), float(sampling[2]))
+        mode = self.sample_mode(sampling)
         if beam is not None:
             mode = self.beam_mode(beam)
             if cache.beam is None or cache.beam.k != mode[1]:

@@ -278,7 +278,7 @@ class Magma(nn.Module):
                  early_stopping=False, num_return_sequences: int = 1, return_scores: bool = False, past_key_values=None,
                  return_past_key_values: bool = False, *, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
                  min_new_tokens: int = 0, suppress_tokens=None, eos_token=None, stop_sequences=None, stop_per_row: bool = None,
-                 return_finish: bool = False):
+                 return_finish: bool = False, sampler: str = "reference", min_p: float = 0.0):
         """reference magma.py:214-236 (+ stop_on_eos / seed / eos_check_every / lengths, see sampling.generate).
         ``lengths``: prompts of different lengths, right-padded (embed_batch); ``embeddings`` may also be a list of
         per-sample (1, s_i, d) tensors.  ``num_beams`` > 1: beam search (length_penalty, early_stopping,
@@ -288,7 +288,9 @@ class Magma(nn.Module):
         processors of those names over the tokens this call generates, inside the token step (see sampling.generate).
         ``eos_token`` (None: the model's eos; an id or 1 to 8 ids) / ``stop_sequences`` (at most 16 token-id sequences or strings,
         matched over token ids) / ``stop_per_row`` / ``return_finish``: per-row stopping as in transformers -- a finished row is
-        padded and stays finished, the call ends when every row is finished (see sampling.generate)."""
+        padded and stays finished, the call ends when every row is finished (see sampling.generate).
+        ``sampler="transformers"``: temperature, top-k, nucleus top-p and ``min_p`` as transformers' warpers apply them, instead of
+        the reference's filters (see sampling.generate)."""
         torch.cuda.set_device(self.device)
         return generate(self, embeddings=embeddings, max_steps=max_steps, temperature=temperature, top_k=top_k,
                         top_p=top_p, decode=decode, stop_on_eos=stop_on_eos, seed=seed, eos_check_every=eos_check_every,
@@ -297,7 +299,8 @@ class Magma(nn.Module):
                         past_key_values=past_key_values, return_past_key_values=return_past_key_values,
                         repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
                         min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens, eos_token=eos_token,
-                        stop_sequences=stop_sequences, stop_per_row=stop_per_row, return_finish=return_finish)
+                        stop_sequences=stop_sequences, stop_per_row=stop_per_row, return_finish=return_finish, sampler=sampler,
+                        min_p=min_p)
 
     @torch.no_grad()
     def cache_prompt(self, embeddings, lengths=None, cache_hint: int = 256):

@@ -632,6 +632,25 @@ def sample(logits: torch.Tensor, temperature: float, top_k: int, top_p: float, s
     return out
 
 
+def sample_warp(logits: torch.Tensor, temperature: float, top_k: int, top_p: float, min_p: float, seed: Optional[torch.Tensor],
+                state: Optional[torch.Tensor], out: Optional[torch.Tensor] = None, filtered: Optional[torch.Tensor] = None,
+                want_token: bool = True):
+    """transformers' sampler on the device (DESIGN.md "transformers' sampler"): temperature, top-k with every tie kept, nucleus
+    top-p, min-p (sampling.py top_k_filter_ties / nucleus_filter / min_p_filter), softmax and one multinomial draw per row on the
+    stream of ``sample``.  ``filtered`` receives the logits with -inf where a rule dropped the token."""
+    _need_gpu(logits, seed, state, out, filtered)
+    assert logits.dtype == torch.float32 and logits.ndim == 2 and logits.stride(1) == 1
+    B, V = logits.shape
+    if want_token and out is None:
+        out = torch.empty(B, dtype=torch.int64, device=logits.device)
+    if filtered is not None:
+        assert filtered.dtype == torch.float32 and filtered.shape == logits.shape and filtered.stride(1) == 1
+    check(L.load().mg_sample_warp_f32(logits.data_ptr(), logits.stride(0), B, V, float(temperature), int(top_k), float(top_p),
+                                      float(min_p), _p(seed), _p(state), _p(out) if want_token else None, _p(filtered),
+                                      0 if filtered is None else filtered.stride(0), _stream()), "mg_sample_warp_f32")
+    return out
+
+
 def sample_finish(token: torch.Tensor, eos: int, state: torch.Tensor, d_pos: Optional[torch.Tensor] = None, delta: int = 1,
                   history: Optional[torch.Tensor] = None, clear: Optional[torch.Tensor] = None, clear_stride: int = 1, *,
                   pos_stride: int = 0):

@@ -35,6 +35,91 @@ def top_k_filter(logits, k):
     return torch.full_like(logits, float("-inf")).scatter_(1, kept_idx, kept_val)
 
 
+SAMPLERS = ("reference", "transformers")
+_FIX = float(2 ** 40)
+
+
+def check_sampler_args(sampler="reference", min_p=0.0, top_p=0.9):
+    """ValueError for sampler arguments generate() does not take.  Returns None for the reference's sampler (the default: its
+    top-k keeps exactly k, its top-p is ``top_p_filter``), else dict(min_p float): transformers' sampler -- ``top_k_filter_ties``,
+    ``nucleus_filter``, ``min_p_filter`` at the temperature, in that order."""
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
+    if isinstance(min_p, bool) or not isinstance(min_p, (int, float)) or not 0.0 <= min_p <= 1.0:
+        raise ValueError(f"min_p must be a number in [0, 1], got {min_p!r}")
+    if sampler == "reference":
+        if min_p > 0:
+            raise ValueError('min_p needs sampler="transformers": the reference\'s sampler has no min-p rule')
+        return None
+    if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not 0.0 <= top_p <= 1.0:
+        raise ValueError(f'sampler="transformers" takes top_p in [0, 1] (0 and 1: off), got {top_p!r}')
+    return dict(min_p=float(min_p))
+
+
+def top_k_filter_ties(logits, k):
+    """transformers' TopKLogitsWarper: every logit below the k-th largest of its row becomes -inf -- every tie AT the k-th value
+    stays (``top_k_filter`` keeps exactly k).  k == 0 and k >= V: off."""
+    if k <= 0 or k >= logits.shape[-1]:
+        return logits.clone()
+    kth = torch.topk(logits, k).values[..., -1:]
+    return logits.masked_fill(logits < kth, float("-inf"))
+
+
+def nucleus_filter(logits, top_p, temperature: float = 1.0):
+    """transformers' TopPLogitsWarper (min_tokens_to_keep = 1) without a sort, the statement csrc/sampling.hip shares (DESIGN.md
+    "transformers' sampler").  ``logits`` (R, V) are the RAW logits of the survivors so far (-inf: gone); the probabilities are
+    those at ``temperature``.  With q_i = floor(exp((x_i - max) / T) / Z * 2^40 + 0.5) (float64), total = sum q_i and
+    c = (uint64)((double)(float)(1 - top_p) * 2^40), token i stays iff the mass ranked before it in descending order is below
+    max(total - c, 1); of equal logits at the boundary the j-th by index has preceding mass above + j * q and the first ones stay.
+    Applies for 0 < top_p < 1 (0 keeps this project's meaning "off").  Returns a new tensor."""
+    bound = float(torch.tensor(1.0 - float(top_p), dtype=torch.float64).to(torch.float32))
+    if not (float(top_p) > 0.0 and bound > 0.0):
+        return logits.clone()
+    c = int(bound * _FIX)
+    x = logits.double()
+    T = float(torch.tensor(float(temperature), dtype=torch.float32))          # the launch argument is fp32
+    w = torch.exp((x - x.max(-1, keepdim=True).values) / T)
+    q = torch.floor(w / w.sum(-1, keepdim=True) * _FIX + 0.5).to(torch.int64)
+    out = logits.clone()
+    for r in range(x.shape[0]):
+        limit = max(int(q[r].sum()) - c, 1)
+        vals, inv = torch.unique(x[r], sorted=True, return_inverse=True)      # ascending distinct values
+        n = torch.bincount(inv, minlength=vals.numel())
+        mass = torch.zeros(vals.numel(), dtype=torch.int64).scatter_add_(0, inv, q[r])
+        above = mass.flip(0).cumsum(0).flip(0) - mass                       # mass of the strictly larger values
+        q_eq = mass // n.clamp(min=1)
+        # ties of one value: j stays iff above + j * q_eq < limit  ->  m = ceil((limit - above) / q_eq) of them, at most n
+        room = limit - above
+        m = torch.where(room <= 0, torch.zeros_like(n),
+                        torch.where(q_eq > 0, torch.minimum(n, (room + q_eq - 1) // q_eq.clamp(min=1)), n))
+        order = torch.argsort(inv, stable=True)                              # by value, then by index
+        rank = torch.empty_like(order)
+        start = torch.cumsum(n, 0) - n
+        rank[order] = torch.arange(order.numel()) - start[inv[order]]        # index rank among the ties of the value
+        out[r] = out[r].masked_fill(rank >= m[inv], float("-inf"))
+    return out
+
+
+def min_p_filter(logits, min_p, temperature: float = 1.0):
+    """transformers' MinPLogitsWarper (min_tokens_to_keep = 1): a token goes iff p_i < min_p * p_max at ``temperature``, i.e.
+    exp((x_i - max) / T) < min_p in float64 -- a ratio that renormalising the survivors of top-k / top-p does not change.
+    ``logits`` (R, V) raw.  min_p == 0: off.  A maximum is never dropped.  Returns a new tensor."""
+    if not float(min_p) > 0.0:
+        return logits.clone()
+    x = logits.double()
+    T = float(torch.tensor(float(temperature), dtype=torch.float32))
+    d = x - x.max(-1, keepdim=True).values
+    return logits.masked_fill((torch.exp(d / T) < float(min_p)) & (d < 0), float("-inf"))
+
+
+def warp_filter(logits, temperature, top_k=0, top_p=0.0, min_p=0.0):
+    """The chain of transformers' sampler on RAW logits (R, V): top-k with ties, nucleus top-p and min-p at ``temperature``.
+    Returns the raw logits with -inf where a rule dropped the token; the draw is softmax(that / temperature)."""
+    x = top_k_filter_ties(logits, int(top_k))
+    x = nucleus_filter(x, top_p, temperature)
+    return min_p_filter(x, min_p, temperature)
+
+
 def remove_tokens_after_eos(tensor, eos_token, image_token):
     """Everything from the first EOS on becomes EOS; image placeholders and EOS are then dropped."""
     hits = (tensor == eos_token).nonzero()
@@ -412,7 +497,7 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
              num_return_sequences: int = 1, return_scores: bool = False, past_key_values=None,
              return_past_key_values: bool = False, *, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
              min_new_tokens: int = 0, suppress_tokens=None, stop_sequences=None, stop_per_row: bool = None,
-             return_finish: bool = False) -> Union[List[str], torch.Tensor]:
+             return_finish: bool = False, sampler: str = "reference", min_p: float = 0.0) -> Union[List[str], torch.Tensor]:
     """reference sampling.py:43-121.  Token selection (argmax, or top-k / the reference's top-p rule / softmax /
     multinomial) and the ``(next_token == eos).all()`` test run on the device inside the captured token step; the host
     reads the recorded "first all-eos step" every ``eos_check_every`` steps (default 8, MAGMA_EOS_CHECK_EVERY) instead of
@@ -463,13 +548,26 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     int64 [B] (the row's generated tokens that count, the finishing token included), ``reason`` ("eos" | "stop" | "length" per
     row) and ``index`` (which eos id / sequence).  ``decode=True`` then cuts every row at its own ``kept``.  The HIP engine runs
     the rule in the bookkeeping launch of the captured token step (no further launch, no host round trip); any other LM object
-    runs the host statement.  Not combined with beam search (NotImplementedError)."""
+    runs the host statement.  Not combined with beam search (NotImplementedError).
+
+    transformers' sampler (DESIGN.md "transformers' sampler"; sampled selection only): ``sampler="transformers"`` replaces the
+    reference's filters -- whose top-p is not nucleus sampling and is usually a no-op (``top_p_filter``) -- by the rules of
+    transformers' ``_sample`` with do_sample=True, applied after the logits processors in transformers' order: temperature,
+    ``top_k`` (every tie at the k-th value stays; ``top_k_filter_ties``), nucleus ``top_p`` (the smallest set of most probable
+    tokens whose mass reaches top_p at that temperature; 0 and 1 are off; ``nucleus_filter``) and ``min_p`` (tokens less
+    probable than min_p times the most probable one go; 0 is off; ``min_p_filter``), then the same draw on the same stream.
+    The HIP engine runs them in the selection launch of the captured token step (no further launch); any other LM object runs
+    the host statements.  ``sampler="reference"`` (the default) is bit for bit what it was and takes no ``min_p``.  Greedy
+    decoding and beam search ignore the sampler, and raise ValueError for ``min_p`` > 0."""
     if eos_token is None or (isinstance(eos_token, int) and not eos_token):
         eos_token = model.eos_token
     early_stopping = check_beam_args(num_beams, num_return_sequences, early_stopping)
     proc = check_processor_args(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, _logit_count(model))
     stop = check_stop_args(eos_token, stop_sequences, stop_per_row, _logit_count(model),
                            getattr(getattr(model, "tokenizer", None), "encode", None))
+    warp = check_sampler_args(sampler, min_p, top_p)
+    if min_p > 0 and (num_beams > 1 or return_scores or temperature == 0.0):
+        raise ValueError("min_p applies to sampled selection: greedy decoding (temperature=0) and beam search would drop it")
     if (stop is not None or return_finish) and (num_beams > 1 or return_scores):
         raise NotImplementedError("per-row stopping (a list of eos ids, stop_sequences, stop_per_row, return_finish) is not "
                                   "combined with beam search (num_beams > 1 / return_scores=True)")
@@ -513,6 +611,8 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     past = None
     greedy = temperature == 0.0
     mode = None if greedy else (float(temperature), int(top_k), float(top_p))
+    if warp is not None and not greedy:
+        mode = ("warp",) + mode + (warp["min_p"],)
     if seed is None and not greedy:
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     every = eos_check_every or int(os.environ.get("MAGMA_EOS_CHECK_EVERY", "8"))
@@ -560,9 +660,11 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
             next_token = outputs.next_token.unsqueeze(1) if outputs.get("next_token") is not None and proc is None else \
                 torch.argmax(logits, dim=-1, keepdim=True)
         else:
-            if top_k > 0:
+            if warp is not None:
+                logits = warp_filter(logits.cpu(), temperature, top_k, top_p, warp["min_p"]).to(logits.device)
+            if warp is None and top_k > 0:
                 logits = top_k_filter(logits, k=top_k)
-            if top_p > 0:
+            if warp is None and top_p > 0:
                 logits = top_p_filter(logits, threshold=top_p)
             probs = F.softmax(logits / temperature, dim=-1)
             next_token = torch.multinomial(probs, num_samples=1)
