@@ -107,7 +107,11 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const mg_bf16* __rest
         if (xx < 0 || xx >= W) continue;
         const u32x4 a = *(const u32x4*)(x + (((int64_t)b * H + yy) * W + xx) * C + c * 8);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { m[2 * j] = fmaxf(m[2 * j], bflo(a[j])); m[2 * j + 1] = fmaxf(m[2 * j + 1], bfhi(a[j])); }
+        for (int j = 0; j < 4; ++j) {       // PyTorch's rule, not fmaxf: a NaN in the window is the window's result
+          const float lo = bflo(a[j]), hi = bfhi(a[j]);
+          if (lo > m[2 * j] || lo != lo) m[2 * j] = lo;
+          if (hi > m[2 * j + 1] || hi != hi) m[2 * j + 1] = hi;
+        }
       }
     }
     u32x4 o;
@@ -200,7 +204,9 @@ __global__ __launch_bounds__(256) void weight_standardize_bwd_kernel(const mg_bf
 }
 
 // MaxPool2d(3, stride 2, padding 1) backward as a gather (deterministic, no atomics): an input pixel receives dy of every
-// window whose FIRST maximum (row-major scan of the window, as PyTorch's max_pool2d picks it) it is.
+// window whose FIRST maximum (row-major scan of the window, as PyTorch's max_pool2d picks it) it is: the scan starts at the
+// first valid entry and moves on where (v > best) || isnan(v), so a window of -inf gives its gradient to its first valid
+// entry and a NaN takes it from whatever came before.
 __global__ __launch_bounds__(256) void maxpool3x3s2_bwd_kernel(const mg_bf16* __restrict__ x, const mg_bf16* __restrict__ dy,
                                                                mg_bf16* __restrict__ dx, int B, int H, int W, int C, int Ho, int Wo) {
   const int64_t total = (int64_t)B * H * W * C;
@@ -212,7 +218,7 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_bwd_kernel(const mg_bf16* __
     float acc = 0.f;
     for (int yo = max(0, yi / 2); yo <= min(Ho - 1, (yi + 1) / 2); ++yo)
       for (int xo = max(0, xi / 2); xo <= min(Wo - 1, (xi + 1) / 2); ++xo) {
-        float best = -INFINITY; int by = -1, bx = -1;
+        float best = -INFINITY; int by = max(0, 2 * yo - 1), bx = max(0, 2 * xo - 1);
         for (int ky = 0; ky < 3; ++ky) {
           const int yy = 2 * yo + ky - 1;
           if (yy < 0 || yy >= H) continue;
@@ -220,7 +226,7 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_bwd_kernel(const mg_bf16* __
             const int xx = 2 * xo + kx - 1;
             if (xx < 0 || xx >= W) continue;
             const float v = bf2f(x[(((int64_t)b * H + yy) * W + xx) * C + c]);
-            if (v > best) { best = v; by = yy; bx = xx; }
+            if (v > best || v != v) { best = v; by = yy; bx = xx; }
           }
         }
         if (by == yi && bx == xi) acc += bf2f(dy[(((int64_t)b * Ho + yo) * Wo + xo) * C + c]);

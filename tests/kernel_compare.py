@@ -874,3 +874,178 @@ def assert_accumulation(got, parts, repeats, what: str = "") -> dict:
                      f"pass.  Choose inputs under which every micro-batch moves this tensor; do not relax the condition")
     worst = assert_elementwise(got, ref, bound, what)
     return {"worst": worst, "self": self_ratio, "zero_parts": [i for i, _, zero in invisible if zero]}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the NF-ResNet kernels (csrc/nfnet.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+def f32_const(x: float) -> float:
+    """A host double as the kernel receives it through a ``float`` argument."""
+    return float(torch.tensor(x, dtype=torch.float32))
+
+
+def _rsqrt_rel(d_ve, ve):
+    """Relative error of rsqrtf(ve~) when |ve~ - ve| <= d_ve: (1 - x)^-1/2 - 1 <= x / (2 (1 - x)) for x = d_ve / ve in [0, 1)
+    (the difference of the two sides is 0 at 0 and grows), then the hardware v_rsq_f32."""
+    x = d_ve / ve
+    assert float(x.max()) < 0.5, "the variance is not resolved in fp32: no bound to state"
+    return 0.5 * x / (1.0 - x) + U_TRANS
+
+
+def weight_standardize_stats(w: torch.Tensor, eps: float) -> dict:
+    """Row statistics of w [cout, fan_in] in fp64 with the fp32 errors of the way weight_standardize_kernel and
+    weight_standardize_bwd_kernel form them (n = fan_in, sums in any order over 256 threads):
+
+      * mean = (sum w) / n: n additions and a division, |d_mean| <= gamma(n + 1) mean|w|;
+      * c_i = w_i - mean, one subtraction of the perturbed mean: d_c = d_mean + u32 (|c| + d_mean).  This is the CANCELLATION
+        term: for a row 8 + small it is gamma(n) * 8 however small the spread is;
+      * var = (sum c_i^2) / n (two-pass): the squares of perturbed c_i move by 2 |c| d_c + d_c^2 each, then one rounding per
+        square, n additions, a division: d_var = gamma(n + 4) (var + t) + t, t = mean(2 |c| d_c + d_c^2);
+      * r = rsqrtf(var + eps): one rounding of the sum, then _rsqrt_rel."""
+    w64 = f64(w)
+    n = w64.shape[1]
+    eps = f32_const(eps)
+    mean = w64.mean(1, keepdim=True)
+    c = w64 - mean
+    var = (c * c).mean(1, keepdim=True)
+    d_mean = gamma(n + 1) * w64.abs().mean(1, keepdim=True)
+    d_c = d_mean + U_F32 * (c.abs() + d_mean)
+    t = (2.0 * c.abs() * d_c + d_c * d_c).mean(1, keepdim=True)
+    d_var = gamma(n + 4) * (var + t) + t
+    ve = var + eps
+    rel_r = _rsqrt_rel(d_var + U_F32 * ve, ve)
+    return dict(w=w64, n=n, mean=mean, c=c, var=var, r=ve.rsqrt(), d_c=d_c, rel_r=rel_r)
+
+
+def weight_standardize_reference(w: torch.Tensor, gain: torch.Tensor, scale: float, eps: float, to_khwc: bool = False):
+    """timm ScaledStdConv2d's weight transform as mg_weight_standardize_bf16 states it, w [cout, cin, kh, kw] bf16, gain [cout]
+    bf16 -> (ref, bound) [cout, fan_in] in the column order of the output ((cin, ky, kx), or (ky, kx, cin) with to_khwc):
+
+        out = bf16( (w - mean) * g ),   g = gain * scale * rsqrt(var + eps),  biased variance over the fan-in.
+
+    Statistics: weight_standardize_stats.  g takes two more products (rel_g = rel_r + 2 u32), the element one: its fp32 error is
+    |g| d_c + |c g| (rel_g + u32), the first term being the cancellation in w - mean (all that is left for a constant row, whose
+    reference is 0), and ``rounded`` adds the bf16 store."""
+    cout, cin, kh, kw = w.shape
+    T = weight_standardize_stats(w.reshape(cout, -1), eps)
+    g = f64(gain).reshape(cout, 1) * f32_const(scale) * T["r"]
+    rel_g = T["rel_r"] + 2.0 * U_F32
+    ref = T["c"] * g
+    err = (g.abs() * T["d_c"] + ref.abs() * (rel_g + U_F32)) * (1.0 + rel_g + U_F32)
+    if to_khwc:
+        ref, err = (t.reshape(cout, cin, kh * kw).transpose(1, 2).reshape(cout, -1) for t in (ref, err))
+    return ref, rounded(ref, err, torch.bfloat16)
+
+
+def weight_standardize_bwd_reference(w: torch.Tensor, gain: torch.Tensor, dwhat: torch.Tensor, scale: float, eps: float,
+                                     dmult: float = 1.0, dw0=None, dgain0=None) -> dict:
+    """The closed form in the header of weight_standardize_bwd_kernel, in fp64: with n = (w - mean) r, r = rsqrt(var + eps),
+    dh = dwhat * dmult and dn = dh * gain * scale
+
+        dgain = scale * sum(dh n),      dw = r (dn - mean(dn) - n mean(dn n))
+
+    w [cout, fan_in] bf16, gain [cout] bf16, dwhat [cout, fan_in] fp32 (the caller slices the padding off)
+    -> {"dw": (ref, bound), "dgain": (ref, bound)} for what the kernel ADDED to fp32 buffers that held dw0 / dgain0.
+
+      * n: r d_c + |n| (rel_r + u32)                                            (statistics: weight_standardize_stats)
+      * dh, gain * scale and dn are one product each: d_dn = gamma(3) |dn|, dh n for dgain: gamma(2) relative;
+      * m1 = mean(dn): gamma(N + 1) mean|dn| + mean(d_dn);   m2 = mean(dn n): gamma(N + 2) mean|dn n| + mean(|dn| d_n + d_dn |n|);
+      * the element: d_inner = d_dn + d_m1 + |n| d_m2 + |m2| d_n + gamma(4) (|dn| + |m1| + |n m2|), times r (rel_r, one rounding);
+      * dgain: gamma(N + 3) sum|dh n| + sum(|dh| d_n), times scale;
+      * ``+=``: one rounding relative to |buffer + value|, charged to |dw0| + |dw| (the caller subtracts dw0 again in fp64)."""
+    T = weight_standardize_stats(w, eps)
+    N, r = T["n"], T["r"]
+    sc = f32_const(scale)
+    n = T["c"] * r
+    d_n = (r * T["d_c"] + n.abs() * (T["rel_r"] + U_F32)) * (1.0 + T["rel_r"])
+    dh = f64(dwhat) * f32_const(dmult)
+    gs = f64(gain).reshape(-1, 1) * sc
+    dn = dh * gs
+    d_dn = gamma(3) * dn.abs()
+    m1, m2 = dn.mean(1, keepdim=True), (dn * n).mean(1, keepdim=True)
+    d_m1 = gamma(N + 1) * dn.abs().mean(1, keepdim=True) + d_dn.mean(1, keepdim=True)
+    d_m2 = gamma(N + 2) * (dn * n).abs().mean(1, keepdim=True) + (dn.abs() * d_n + d_dn * n.abs()).mean(1, keepdim=True)
+    inner = dn - m1 - n * m2
+    d_inner = d_dn + d_m1 + n.abs() * d_m2 + m2.abs() * d_n + gamma(4) * (dn.abs() + m1.abs() + (n * m2).abs())
+    dw = r * inner
+    d_dw = (r * d_inner + dw.abs() * (T["rel_r"] + U_F32)) * (1.0 + T["rel_r"])
+    dg = sc * (dh * n).sum(1)
+    d_dg = sc * (gamma(N + 3) * (dh * n).abs().sum(1) + (dh.abs() * d_n).sum(1)) + U_F32 * dg.abs()
+    if dw0 is not None:
+        d_dw = d_dw + U_F32 * (f64(dw0).abs() + dw.abs())
+    if dgain0 is not None:
+        d_dg = d_dg + U_F32 * (f64(dgain0).abs() + dg.abs())
+    return {"dw": (dw, rounded(dw, d_dw, torch.float32)), "dgain": (dg, rounded(dg, d_dg, torch.float32))}
+
+
+def relu_mean_rows_reference(x: torch.Tensor):
+    """x [B, HW, C] bf16 -> (ref, bound) [B, C] of bf16( (sum_p relu(x_p)) / HW ): an fp32 sum of HW non-negative terms in any
+    order (the kernel's 32 partial sums and their reduction add zeros exactly) and a division: gamma(HW + 1) of the sum, which
+    is its own magnitude sum; one rounding to bf16."""
+    HW = x.shape[1]
+    ref = torch.relu(f64(x)).mean(1)
+    return ref, rounded(ref, gamma(HW + 1) * ref, torch.bfloat16)
+
+
+def relu_mean_rows_bwd_reference(x: torch.Tensor, g: torch.Tensor):
+    """x [B, HW, C], g [B, C] bf16 -> (ref, bound) [B, HW, C] of dx = x > 0 ? bf16( g * (1 / HW) ) : 0.  The gate is exact and is
+    the caller's to assert (the bound at a closed gate is FLOOR); an open gate passes g through a rounded reciprocal and a
+    rounded product: gamma(2) |g / HW|."""
+    HW = x.shape[1]
+    ref = torch.where(f64(x) > 0, f64(g)[:, None, :] / HW, torch.zeros((), dtype=torch.float64, device=x.device))
+    return ref, map_bound(ref, ref.abs(), 2, torch.bfloat16)
+
+
+def maxpool3x3s2_bwd_reference(x: torch.Tensor, dy: torch.Tensor):
+    """Backward of F.max_pool2d(x, 3, 2, 1), x [B, C, H, W], dy [B, C, Ho, Wo] (bf16 values) -> (ref, bound, count): the window
+    maxima are the indices max_pool2d itself returns on the fp32 copy of x (what autograd scatters through: the first maximum
+    of a row-major scan, a NaN in place of any maximum, the first valid entry of a window of -inf); the up to four window
+    gradients that meet in one element are added in fp64.  The kernel adds them in fp32 and rounds to bf16: gamma(4) sum|dy|.
+    count = how many windows feed the element; where it is 1 the kernel's output must be dy's bits."""
+    import torch.nn.functional as F
+    B, C, H, W = x.shape
+    _, idx = F.max_pool2d(x.detach().float().cpu(), 3, stride=2, padding=1, return_indices=True)
+    idx = idx.reshape(B, C, -1)
+    d = f64(dy).cpu().reshape(B, C, -1)
+    ref = torch.zeros(B, C, H * W, dtype=torch.float64).scatter_add_(2, idx, d)
+    mag = torch.zeros(B, C, H * W, dtype=torch.float64).scatter_add_(2, idx, d.abs())
+    cnt = torch.zeros(B, C, H * W, dtype=torch.float64).scatter_add_(2, idx, torch.ones_like(d))
+    ref, mag, cnt = (t.reshape(B, C, H, W) for t in (ref, mag, cnt))
+    return ref, rounded(ref, gamma(4) * mag, torch.bfloat16), cnt.to(torch.int64)
+
+
+WS_ROW_KINDS = ("normal", "large mean", "constant")
+
+
+def standardize_rows(kind: str, cout: int, cin: int, k: int, seed: int):
+    """(w [cout, cin, k, k], gain [cout]) bf16 for the weight-standardisation tests.
+      normal      N(0.5, 1): the mean subtraction is visible;
+      large mean  8 + 0.01 N(0, 1): in bf16 (spacing 2^-4 above 8, 2^-5 below) most entries ARE 8 and a few sit one step away:
+                  mean >> spread, the output is what survives the cancellation in w - mean;
+      constant    rows of one repeated value (var = 0, a zero-initialised conv is one); the last row, and row 0, all zero."""
+    g = torch.Generator().manual_seed(seed)
+    z = torch.randn(cout, cin, k, k, generator=g)
+    if kind == "normal":
+        w = z + 0.5
+    elif kind == "large mean":
+        w = 8.0 + 0.01 * z
+    elif kind == "constant":
+        w = (torch.randn(cout, 1, 1, 1, generator=g) * 0.3).expand(cout, cin, k, k).clone()
+        w[0] = 0.0
+        w[-1] = 0.0
+    else:
+        raise ValueError(kind)
+    gain = 1.0 + 0.2 * torch.randn(cout, generator=g)
+    return w.to(torch.bfloat16).contiguous(), gain.to(torch.bfloat16)
+
+
+def relu_rows_input(B: int, HW: int, C: int, seed: int):
+    """x [B, HW, C] bf16 with +0, -0 and the smallest positive bf16 (2^-133, a subnormal) among normal values -- an eighth of
+    the elements each -- and g [B, C] bf16: the gate of relu_mean_rows_bwd is x > 0, which the first two close and the third opens."""
+    gen = torch.Generator().manual_seed(seed)
+    x = torch.randn(B, HW, C, generator=gen).to(torch.bfloat16)
+    pick = torch.randint(0, 8, (B, HW, C), generator=gen)
+    x[pick == 0] = 0.0
+    x[pick == 1] = -0.0
+    x[pick == 2] = 2.0 ** -133
+    return x, torch.randn(B, C, generator=gen).to(torch.bfloat16)

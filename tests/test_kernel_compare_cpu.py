@@ -541,3 +541,172 @@ def test_accumulation_conditions_refuse_weak_inputs():
     # an all-zero tensor is compared, not divided by zero
     z = [torch.zeros(8)] * 3
     assert kc.assert_accumulation(torch.zeros(8), z, z, "all zero")["worst"] == 0.0
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the NF-ResNet kernels: weight standardisation (forward, backward), ReLU + mean over positions (forward, backward)
+# ---------------------------------------------------------------------------------------------------------------------------
+WS_SCALE, WS_EPS = 1.7139588594436646, 1e-5        # gamma of ReLU (times fan_in^-1/2 below), ScaledStdConv2d's eps
+
+
+def check_exceeds(name, bad, ref, bound):
+    """A seeded fault whose size is fixed by the shape (1 / (2 fan_in), 1 / HW ...) and need not reach FAULT_FACTOR bounds: it
+    must be over the bound, and the figure is printed."""
+    w = kc.worst_ratio(bad, ref, bound)
+    with pytest.raises(AssertionError, match="bounding box"):
+        kc.assert_elementwise(bad, ref, bound, name)
+    print(f"    fault {name:<58s} err/bound {w:9.1f}   rel-L2 {old_rel(bad, ref):.2e}")
+    return w
+
+
+def ws_stats32(wf, eps, fault=None, ldo=None):
+    """mean, r of weight_standardize_kernel in float32 (sums in a permuted order), with the seeded slips."""
+    N = wf.shape[1]
+    perm = torch.randperm(N, generator=torch.Generator().manual_seed(3))
+    mean = wf[:, perm].sum(1, keepdim=True) / (ldo if fault == "mean over ldo" else N)
+    var = ((wf - mean)[:, perm] ** 2).sum(1, keepdim=True) / (N - 1 if fault == "unbiased variance" else N)
+    r = 1.0 / (var.sqrt() + eps) if fault == "eps outside the root" else torch.rsqrt(var + eps)
+    return mean, r
+
+
+def ws_stand_in(w, gain, scale, eps, to_khwc=False, fault=None, ldo=None):
+    cout, cin, kh, kw = w.shape
+    wf = w.float().reshape(cout, -1)
+    mean, r = ws_stats32(wf, eps, fault, ldo)
+    g = gain.float().reshape(cout, 1) * torch.tensor(scale, dtype=torch.float32) * r
+    out = (wf - mean) * g
+    if to_khwc:
+        out = out.reshape(cout, cin, kh * kw).transpose(1, 2).reshape(cout, -1)
+    return out.to(BF16)
+
+
+def ws_bwd_stand_in(w, gain, dwhat, scale, eps, dmult, dw0, dgain0, fault=None, drop=-1):
+    """weight_standardize_bwd_kernel in float32: returns what it ADDED to the buffers (the difference formed in fp64)."""
+    wf = w.float().reshape(w.shape[0], -1)
+    N = wf.shape[1]
+    mean, r = ws_stats32(wf, eps, fault)
+    sc = torch.tensor(scale, dtype=torch.float32)
+    gs = gain.float().reshape(-1, 1) * sc
+    n = (wf - mean) * r
+    dh = dwhat * torch.tensor(dmult, dtype=torch.float32)
+    dn = dh * gs
+    m1, m2 = dn.sum(1, keepdim=True) / N, (dn * n).sum(1, keepdim=True) / N
+    dw = dw0 + r * (dn - m1 - n * m2)
+    dg = dgain0 + sc * (dh * n).sum(1)
+    if fault == "one gradient element dropped":
+        dw[-1, drop] = dw0[-1, drop]
+    return dw.double() - dw0.double(), dg.double() - dgain0.double()
+
+
+@pytest.mark.parametrize("kind", kc.WS_ROW_KINDS)
+@pytest.mark.parametrize("cout,cin,k", [(16, 3, 3), (40, 24, 3), (8, 2048, 1)])
+def test_weight_standardize_stand_in_and_faults(cout, cin, k, kind):
+    """kernel_compare.weight_standardize_reference / weight_standardize_bwd_reference: the float32 restatement of the two kernels
+    is inside the bound for every row kind; the slips are outside it wherever the arithmetic lets them show:
+      * forward, bf16 output: a biased / unbiased mix-up is 1 / (2 fan_in) of the value -- above u_bf16 at fan-in 27 only; eps
+        outside the root shows where var is not >> eps (the 'large mean' rows); the mean over ldo shows wherever the mean is not 0;
+      * backward, fp32 output: everything shows, at every fan-in."""
+    fan_in = cin * k * k
+    scale = WS_SCALE * fan_in ** -0.5
+    w, gain = kc.standardize_rows(kind, cout, cin, k, seed=70)
+    for khwc in (False, True):
+        ref, bound = kc.weight_standardize_reference(w, gain, scale, WS_EPS, to_khwc=khwc)
+        good = ws_stand_in(w, gain, scale, WS_EPS, to_khwc=khwc)
+        worst = kc.assert_elementwise(good, ref, bound, f"honest weight_standardize {kind} {(cout, cin, k)} khwc={khwc}")
+        assert worst < 1.0
+    if kind == "constant":
+        assert float(ref.abs().max()) == 0.0 and bool((good[0] == 0).all()) and bool((good[-1] == 0).all())
+    else:
+        check_fault("mean over ldo instead of the fan-in", ws_stand_in(w, gain, scale, WS_EPS, True, "mean over ldo", fan_in + 8), ref, bound)
+    small = fan_in <= 216      # at fan-in 2048 the cancellation term gamma(n) |mean| of the bound is itself a few % of a 'large mean' row
+    if kind == "large mean" and small:
+        var = w.double().reshape(cout, -1).var(1, unbiased=False)
+        assert float(var.max()) < 100 * WS_EPS          # var is of eps's size: where the place of eps matters
+        check_fault("eps outside the root", ws_stand_in(w, gain, scale, WS_EPS, True, "eps outside the root"), ref, bound)
+    if kind != "constant" and fan_in == 27:
+        check_exceeds("unbiased variance (fan-in 27: 1.9 % of the value)", ws_stand_in(w, gain, scale, WS_EPS, True, "unbiased variance"), ref, bound)
+    # backward
+    g = torch.Generator().manual_seed(71)
+    dwhat = torch.randn(cout, fan_in, generator=g)
+    dw0, dg0 = torch.randn(cout, fan_in, generator=g), torch.randn(cout, generator=g)
+    R = kc.weight_standardize_bwd_reference(w.reshape(cout, -1), gain, dwhat, scale, WS_EPS, 0.7, dw0, dg0)
+    dw, dg = ws_bwd_stand_in(w, gain, dwhat, scale, WS_EPS, 0.7, dw0, dg0)
+    assert kc.assert_elementwise(dw, *R["dw"], f"honest weight_standardize_bwd dw {kind} {(cout, cin, k)}") < 1.0
+    assert kc.assert_elementwise(dg, *R["dgain"], f"honest weight_standardize_bwd dgain {kind} {(cout, cin, k)}") < 1.0
+    j = int(R["dw"][0][-1].abs().argmax())          # in the last row, the element whose gradient is largest
+    bad, _ = ws_bwd_stand_in(w, gain, dwhat, scale, WS_EPS, 0.7, dw0, dg0, "one gradient element dropped", drop=j)
+    # 'large mean' at fan-in 2048: d_mean = gamma(2049) * 8 is 1.6 % of the one bf16 step that is the whole spread, and n inherits it
+    (check_fault if small or kind != "large mean" else check_exceeds)("one element's gradient dropped", bad, *R["dw"])
+    if kind == "normal" and small:  # 1 / (2 fan_in) of the value: at fan-in 2048 that is the size of the accumulation terms; a
+        bad, badg = ws_bwd_stand_in(w, gain, dwhat, scale, WS_EPS, 0.7, dw0, dg0, "unbiased variance")   # constant row has var = 0 either way
+        check_fault("unbiased variance (dw)", bad, *R["dw"])
+        check_fault("unbiased variance (dgain)", badg, *R["dgain"])
+    if kind == "large mean" and small:
+        bad, _ = ws_bwd_stand_in(w, gain, dwhat, scale, WS_EPS, 0.7, dw0, dg0, "eps outside the root")
+        check_fault("eps outside the root (dw)", bad, *R["dw"])
+
+
+def test_weight_standardize_bwd_reference_is_the_gradient():
+    """The closed form of the kernel's header against autograd through oracle.nfnet.standardized_weight, both in float64."""
+    from oracle.nfnet import standardized_weight
+    cout, cin, k = 12, 5, 3
+    fan_in = cin * k * k
+    w, gain = kc.standardize_rows("normal", cout, cin, k, seed=72)
+    dwhat = rnd(cout, fan_in, seed=73)
+    wd, gd = w.double().requires_grad_(True), gain.double().requires_grad_(True)
+    flat = wd.reshape(cout, -1)                      # standardized_weight computes in float32: restate its lines in float64
+    n = (flat - flat.mean(1, keepdim=True)) * torch.rsqrt(flat.var(1, unbiased=False, keepdim=True) + kc.f32_const(WS_EPS))
+    sc = kc.f32_const(WS_SCALE * fan_in ** -0.5)
+    what = n * gd.reshape(cout, 1) * sc
+    assert torch.allclose(what.float(), standardized_weight(w.float(), gain.float(), WS_EPS).reshape(cout, -1) * (sc / (WS_SCALE * fan_in ** -0.5)), rtol=1e-5, atol=1e-6)
+    (what * dwhat.double() * kc.f32_const(0.7)).sum().backward()
+    R = kc.weight_standardize_bwd_reference(w.reshape(cout, -1), gain, dwhat, WS_SCALE * fan_in ** -0.5, WS_EPS, 0.7)
+    assert torch.allclose(R["dw"][0], wd.grad.reshape(cout, -1), rtol=1e-11, atol=1e-13)
+    assert torch.allclose(R["dgain"][0], gd.grad, rtol=1e-11, atol=1e-13)
+
+
+@pytest.mark.parametrize("HW", [1, 9, 33, 140])
+def test_relu_mean_rows_stand_in_and_faults(HW):
+    B, C = 3, 66
+    x, g = kc.relu_rows_input(B, HW, C, seed=80 + HW)
+    assert float(x[x > 0].min()) == 2.0 ** -133 and bool(torch.signbit(x[x == 0]).any()) and bool((~torch.signbit(x[x == 0])).any())
+    ref, bound = kc.relu_mean_rows_reference(x)
+    perm = torch.randperm(HW, generator=torch.Generator().manual_seed(5))
+    s = torch.relu(x.float())[:, perm].sum(1)
+    assert kc.assert_elementwise((s / HW).to(BF16), ref, bound, f"honest relu_mean_rows HW={HW}") < 1.0
+    check_exceeds(f"relu_mean_rows: 1/(HW+1), HW={HW}", (s / (HW + 1)).to(BF16), ref, bound)
+    rb, bb = kc.relu_mean_rows_bwd_reference(x, g)
+    inv = torch.tensor(1.0, dtype=torch.float32) / HW
+    good = torch.where(x.float() > 0, g.float()[:, None, :] * inv, torch.zeros(())).to(BF16)
+    assert kc.assert_elementwise(good, rb, bb, f"honest relu_mean_rows_bwd HW={HW}") < 1.0
+    assert bool((good[x <= 0] == 0).all()) and bool((good[x > 0] != 0).any())
+    inv1 = torch.tensor(1.0, dtype=torch.float32) / (HW + 1)
+    check_exceeds(f"relu_mean_rows_bwd: 1/(HW+1), HW={HW}", torch.where(x.float() > 0, g.float()[:, None, :] * inv1, torch.zeros(())).to(BF16), rb, bb)
+    check_fault("relu_mean_rows_bwd: gate >= instead of >", torch.where(x.float() >= 0, g.float()[:, None, :] * inv, torch.zeros(())).to(BF16), rb, bb)
+    bad = good.clone(); bad[-1, -1, -1] = 0 if float(good[-1, -1, -1]) != 0 else 1
+    j = (x[-1, -1] > 0).nonzero().max()
+    bad = good.clone(); bad[-1, -1, j] = 0
+    check_fault("relu_mean_rows_bwd: one element's gradient dropped", bad, rb, bb)
+
+
+def test_maxpool_bwd_reference_is_autograd():
+    """kernel_compare.maxpool3x3s2_bwd_reference: its fp64 scatter through max_pool2d's own indices is autograd's backward (fp32)
+    on a map with ties, and on a constant 5 x 7 map with dy = 1 it is the pattern of first valid window entries."""
+    import torch.nn.functional as F
+    x = torch.randint(-1, 2, (2, 8, 7, 9), generator=torch.Generator().manual_seed(1)).to(BF16)
+    dy = rnd(2, 8, 4, 5, seed=2).to(BF16)
+    xf = x.float().requires_grad_(True)
+    F.max_pool2d(xf, 3, 2, 1).backward(dy.float())
+    ref, bound, cnt = kc.maxpool3x3s2_bwd_reference(x, dy)
+    assert torch.allclose(ref, xf.grad.double(), rtol=1e-6, atol=1e-7) and int(cnt.max()) >= 2
+    ref, _, cnt = kc.maxpool3x3s2_bwd_reference(torch.full((1, 1, 5, 7), 0.5), torch.ones(1, 1, 3, 4))
+    row = torch.tensor([1, 1, 0, 1, 0, 1, 0], dtype=torch.float64)
+    want = torch.zeros(5, 7, dtype=torch.float64)
+    want[0] = want[1] = want[3] = row
+    assert torch.equal(ref[0, 0], want) and torch.equal(cnt[0, 0].double(), want)
+    # a window of -inf gives its gradient to its first valid entry; a NaN takes it
+    xi = torch.full((1, 1, 5, 7), float("-inf"))
+    assert torch.equal(kc.maxpool3x3s2_bwd_reference(xi, torch.ones(1, 1, 3, 4))[0][0, 0], want)
+    xi[0, 0, 2, 2] = float("nan")
+    ref = kc.maxpool3x3s2_bwd_reference(xi, torch.ones(1, 1, 3, 4))[0][0, 0]
+    assert float(ref[2, 2]) == 1.0 and float(ref[1, 1]) == 0.0 and float(ref.sum()) == 12.0

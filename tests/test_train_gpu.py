@@ -28,8 +28,9 @@ def oracle_grads(cfg, params, images, caps, mask, dtype, bn_train=False, want_pa
     return float(out["loss"]), {k: p[k].grad.float() for k in names}
 
 
-@pytest.mark.parametrize("variant", ["v1", "v2"])
-def test_gradients_and_step(dev, variant):
+def gradients_and_step(dev, variant, image_hw=(64, 64)):
+    """Body of test_gradients_and_step at an image of image_hw = (H, W) with (H / 32) * (W / 32) = 4 prefix tokens
+    (tests/test_nonsquare_images_gpu.py runs it at 32 x 128)."""
     from magma_amd.testing import build_reduced_magma
     from magma_amd.train_engine import MagmaEngine
     from oracle.model import OracleConfig, init_params, magma_forward
@@ -46,11 +47,12 @@ def test_gradients_and_step(dev, variant):
     eng.train()
     g = torch.Generator().manual_seed(3)
     B, S = 2, model.seq_len
-    images = torch.randn(B, 3, 64, 64, generator=g)
+    images = torch.randn(B, 3, *image_hw, generator=g)
     caps = torch.full((B, S), cfg.eos_token, dtype=torch.int64)
     caps[0, :23] = torch.randint(0, 1000, (23,), generator=g)
     caps[1, :11] = torch.randint(0, 1000, (11,), generator=g)
     P = 4
+    assert (image_hw[0] // 32) * (image_hw[1] // 32) == P
     mask = (torch.rand(B, P, cfg.d_model, generator=g) < 0.9).float() / 0.9
     loss_ref, g_ref = oracle_grads(cfg, params, images, caps, mask, torch.float32)
     loss_bf, g_bf = oracle_grads(cfg, params, images, caps, mask, torch.bfloat16)
@@ -108,6 +110,11 @@ def test_gradients_and_step(dev, variant):
     eng.eval()
     out2 = eng(images.to(dev), caps.to(dev))
     assert torch.isfinite(out2.loss)
+
+
+@pytest.mark.parametrize("variant", ["v1", "v2"])
+def test_gradients_and_step(dev, variant):
+    gradients_and_step(dev, variant)
 
 
 def test_freeze_lm_false_trains_every_gptj_tensor(dev):
