@@ -249,8 +249,12 @@ class LMEngine:
         self.rot = cfg.rotary_dim
         self.head_dec = self.head_w8 = self.head_w4 = None
         self._lm_head = lm.lm_head
-        self._cache_pool = {}                        # (B, Smax) -> KVCache + captured decode graph, LRU-bounded
+        # (B, Smax, ragged) -> KVCache + the decode graphs captured on it, least recently used first; at most _cache_pool_max
+        # entries (MAGMA_CACHE_POOL, default 4; 0 = no pooling: every generate() call allocates its cache and keeps nothing)
+        self._cache_pool = {}
         self._cache_pool_max = int(os.environ.get("MAGMA_CACHE_POOL", "4"))
+        if self._cache_pool_max < 0:
+            raise ValueError(f"MAGMA_CACHE_POOL must be an integer >= 0 (0 = no pooling), got {self._cache_pool_max}")
         # fp8 operands for the prefill / forward GEMMs (BASELINE config 5): None | "attn" (QKV, out_proj, adapters)
         # | "all" (+ fc_in, fc_out).  bf16 stays the default: it is what the parity tests and the headline use.
         self.fp8_mode = os.environ.get("MAGMA_FP8") or None
@@ -704,6 +708,13 @@ class LMEngine:
         mode = self.sample_mode(sampling)
         if beam is not None:
             mode = self._arm_beam(cache, st, beam)
+        elif cache.beam is not None:
+            # a pooled cache that last served beam search starts a greedy / sampled call: without its beam buffers (the K / V
+            # staging copies are as large as the cache) and the steps captured on them -- it may be handed to the caller and
+            # continued (extend refuses a cache that is mid-beam)
+            cache.beam = None
+            for key in [k for k in st.graphs if isinstance(k[0], tuple) and k[0][:1] == ("beam",)]:
+                del st.graphs[key]
         proc = self.proc_mode(processors)
         if proc is not None:       # step 0 of the rules on a copy: the caller's .logits stay raw
             self._arm_processors(cache, proc)
@@ -831,11 +842,13 @@ class LMEngine:
             # position layout (and with it the captured launches) differ
             key = (B, Smax, ragged)
             cache = self._cache_pool.pop(key, None)
+            pooled = self._cache_pool_max > 0                            # a bound of 0: nothing is kept
+            while pooled and len(self._cache_pool) >= self._cache_pool_max:      # least recently used shape goes first
+                self._cache_pool.pop(next(iter(self._cache_pool)))
             if cache is None:
-                while len(self._cache_pool) >= self._cache_pool_max:      # least recently used shape goes first
-                    self._cache_pool.pop(next(iter(self._cache_pool)))
                 cache = KVCache(self.L, B, self.H, Smax, self.device, ragged=ragged)
-            self._cache_pool[key] = cache                                # (re-)insert as most recently used
+            if pooled:
+                self._cache_pool[key] = cache                            # (re-)insert as most recently used
         else:
             cache = KVCache(self.L, B, self.H, Smax, self.device, ragged=ragged)
         # right padding: the prefill is unchanged -- under the causal mask a valid row attends to valid keys only, and the
