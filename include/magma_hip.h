@@ -92,8 +92,9 @@ const char* mg_version(void);
  *  11  MXFP4 decode weights (W4A16): mg_skinny_desc grew by `w_mx4_scale` at its end (NULL = as before; nothing else moved).
  *  12  per-row stopping: added mg_sample_finish_rows; mg_logits_process_f32 gained `eos_more` / `n_eos_more` (before the stream;
  *      NULL / 0 = as before): further eos ids the min_new_tokens rule bans.
- *  13  transformers' sampler: added mg_sample_warp_f32 (nothing moved). */
-#define MG_ABI_VERSION 13
+ *  13  transformers' sampler: added mg_sample_warp_f32 (nothing moved).
+ *  14  added the test probe mg_debug_mx_mfma_acc (nothing moved). */
+#define MG_ABI_VERSION 14
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -204,11 +205,18 @@ int mg_gemm_fp8(const mg_gemm_desc* d, const float* row_scale, void* stream);
  *                       kernel (scales in registers a K-tile ahead; split-K as for bf16) or the 256x256 one (scales staged
  *                       through LDS with their K-tile; bit-identical un-split); the usual epilogue.
  *   mg_debug_mx_mfma    test probe: ONE wave-level MFMA on caller-supplied operand registers (a, b: [64 lanes][8] dwords) and
- *                       per-lane scale dwords -> out [64][4]; pins the instruction's lane / block / scale-byte semantics.            */
+ *                       per-lane scale dwords -> out [64][4]; pins the instruction's lane / block / scale-byte semantics.
+ *   mg_debug_mx_mfma_acc  test probe (revision 14): the same with the accumulator C as an input and for either shape of the
+ *                       instruction: form 16 = v_mfma_scale_f32_16x16x128_f8f6f4 (c_in, out [64][4] floats), form 32 =
+ *                       v_mfma_scale_f32_32x32x64_f8f6f4 (c_in, out [64][16] floats: the lane's accumulator registers in order);
+ *                       out = A B + c_in by ONE instruction of one wave.  Pins how the products of the instruction are aligned,
+ *                       truncated and added to C (tests/kernel_compare.py).                                                      */
 int64_t mg_mx_scale_bytes(int32_t rows, int32_t K);
 int mg_quantize_mx_fp8(const mg_bf16* x, int64_t ldx, int32_t M, int32_t K, uint8_t* q, int64_t ldq, uint8_t* scales, void* stream);
 int mg_gemm_mx_fp8(const mg_gemm_desc* d, const uint8_t* a_scales, const uint8_t* w_scales, void* stream);
 int mg_debug_mx_mfma(const uint32_t* a, const uint32_t* scale_a, const uint32_t* b, const uint32_t* scale_b, float* out, void* stream);
+int mg_debug_mx_mfma_acc(int32_t form, const uint32_t* a, const uint32_t* scale_a, const uint32_t* b, const uint32_t* scale_b,
+                         const float* c_in, float* out, void* stream);
 /* bf16 rows -> e4m3 rows + one fp32 scale per row (x ~= q * scale[m], scale = rowmax|x| / 448, round to
  * nearest even, saturating); q columns [K, ldq) are zero-filled.  K, ldx, ldq multiples of 8.                */
 int mg_quantize_rows_fp8(const mg_bf16* x, int64_t ldx, int32_t M, int32_t K, uint8_t* q, int64_t ldq,

@@ -709,6 +709,35 @@ __global__ __launch_bounds__(64) void mx_mfma_probe_kernel(const uint32_t* __res
 #pragma unroll
   for (int r = 0; r < 4; ++r) out[l * 4 + r] = c[r];
 }
+
+// the same with the accumulator as an input, for both shapes of the instruction: FORM32 = v_mfma_scale_f32_32x32x64_f8f6f4
+// (c_in / out [64][16]), otherwise the 16x16x128 form ([64][4]).  One wave, one instruction.
+template <bool FORM32>
+__global__ __launch_bounds__(64) void mx_mfma_acc_probe_kernel(const uint32_t* __restrict__ a, const uint32_t* __restrict__ sa,
+                                                               const uint32_t* __restrict__ b, const uint32_t* __restrict__ sb,
+                                                               const float* __restrict__ c_in, float* __restrict__ out) {
+  typedef __attribute__((ext_vector_type(8))) int i32x8_;
+  typedef __attribute__((ext_vector_type(16))) float f32x16_;
+  const int l = threadIdx.x;
+  i32x8_ av, bv;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { av[i] = (int)a[l * 8 + i]; bv[i] = (int)b[l * 8 + i]; }
+  if constexpr (FORM32) {
+    f32x16_ c;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) c[r] = c_in[l * 16 + r];
+    c = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, c, 0, 0, 0, (int)sa[l], 0, (int)sb[l]);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) out[l * 16 + r] = c[r];
+  } else {
+    f32x4 c;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) c[r] = c_in[l * 4 + r];
+    c = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, bv, c, 0, 0, 0, (int)sa[l], 0, (int)sb[l]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) out[l * 4 + r] = c[r];
+  }
+}
 }  // namespace
 
 extern "C" int64_t mg_mx_scale_bytes(int32_t rows, int32_t K) {
@@ -731,6 +760,19 @@ extern "C" int mg_debug_mx_mfma(const uint32_t* a, const uint32_t* scale_a, cons
                                 void* stream) {
   if (!a || !scale_a || !b || !scale_b || !out) MG_FAIL(MG_ERR_SHAPE, "mg_debug_mx_mfma: null pointer");
   hipLaunchKernelGGL(mx_mfma_probe_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a, scale_a, b, scale_b, out);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_debug_mx_mfma_acc(int32_t form, const uint32_t* a, const uint32_t* scale_a, const uint32_t* b, const uint32_t* scale_b,
+                                    const float* c_in, float* out, void* stream) {
+  if (!a || !scale_a || !b || !scale_b || !c_in || !out) MG_FAIL(MG_ERR_SHAPE, "mg_debug_mx_mfma_acc: null pointer");
+  if (form == 32)
+    hipLaunchKernelGGL(mx_mfma_acc_probe_kernel<true>, dim3(1), dim3(64), 0, (hipStream_t)stream, a, scale_a, b, scale_b, c_in, out);
+  else if (form == 16)
+    hipLaunchKernelGGL(mx_mfma_acc_probe_kernel<false>, dim3(1), dim3(64), 0, (hipStream_t)stream, a, scale_a, b, scale_b, c_in, out);
+  else
+    MG_FAIL(MG_ERR_SHAPE, "mg_debug_mx_mfma_acc: form must be 16 (16x16x128) or 32 (32x32x64)");
   MG_CHECK_LAUNCH();
   return MG_OK;
 }

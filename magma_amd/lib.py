@@ -19,7 +19,7 @@ MG_A_DENSE, MG_A_CONV3X3 = 0, 1
 MG_AUX_NONE, MG_AUX_RELU_GATE, MG_AUX_GELU_GRAD, MG_AUX_MUL, MG_AUX_QUICK_GELU_GRAD = 0, 1, 2, 3, 4
 
 
-ABI_VERSION = 13     # include/magma_hip.h MG_ABI_VERSION
+ABI_VERSION = 14     # include/magma_hip.h MG_ABI_VERSION
 
 
 class MagmaHipError(RuntimeError):
@@ -185,6 +185,7 @@ SYMBOLS = {
     "mg_quantize_mx_fp8": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp]),
     "mg_gemm_mx_fp8": (C.c_int, [C.POINTER(GemmDesc), _vp, _vp, _vp]),
     "mg_debug_mx_mfma": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "mg_debug_mx_mfma_acc": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mg_conv_weight_relayout_bf16": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "mg_bn_fold_f32": (C.c_int, [_vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _vp]),
     "mg_conv_weight_relayout_batch": (C.c_int, [_vp, _i32, _i64, _vp]),

@@ -1645,3 +1645,17 @@ def debug_mx_mfma(a: torch.Tensor, sa: torch.Tensor, b: torch.Tensor, sb: torch.
     out = torch.empty(64, 4, dtype=torch.float32, device=a.device)
     check(L.load().mg_debug_mx_mfma(a.data_ptr(), sa.data_ptr(), b.data_ptr(), sb.data_ptr(), out.data_ptr(), _stream()), "mg_debug_mx_mfma")
     return out
+
+
+def debug_mx_mfma_acc(form: int, a: torch.Tensor, sa: torch.Tensor, b: torch.Tensor, sb: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    """One scaled f8f6f4 MFMA with its accumulator: form 16 = 16x16x128 (c and the result fp32 [64, 4]), form 32 = 32x32x64
+    ([64, 16]); a, b int32 [64, 8]; sa, sb int32 [64] -> A B + c as the instruction forms it."""
+    _need_gpu(a, sa, b, sb, c)
+    n = {16: 4, 32: 16}[form]
+    assert a.shape == (64, 8) and b.shape == (64, 8) and sa.shape == (64,) and sb.shape == (64,) and c.shape == (64, n)
+    assert a.dtype == b.dtype == sa.dtype == sb.dtype == torch.int32 and c.dtype == torch.float32
+    assert all(t.is_contiguous() for t in (a, sa, b, sb, c))
+    out = torch.empty(64, n, dtype=torch.float32, device=a.device)
+    check(L.load().mg_debug_mx_mfma_acc(form, a.data_ptr(), sa.data_ptr(), b.data_ptr(), sb.data_ptr(), c.data_ptr(), out.data_ptr(),
+                                        _stream()), "mg_debug_mx_mfma_acc")
+    return out

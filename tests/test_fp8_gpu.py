@@ -358,6 +358,225 @@ def test_mx_mfma_sums_groups_of_8_and_truncates(dev):
             kcmp.assert_elementwise(_mx_mfma(ops, Ak, Bk, sa, sb, dev), ref, bound, f"one scaled fp8 MFMA, block exponents +-{spread}")
 
 
+# ------------------------------------------------------------------------ the scaled MFMA with its accumulator, both forms
+def _mx_dims(form):
+    return (32, 64) if form == 32 else (16, 128)
+
+
+def _mx_c_index(form, r, lane):
+    """(row, column) of accumulator register r of each lane."""
+    if form == 32:
+        return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), lane & 31
+    return (lane >> 4) * 4 + r, lane & 15
+
+
+def _mx_pack(form, Mk, dev):
+    """Logical operand [R, K] e4m3 bytes -> the 32 bytes of each lane.  32x32x64: lane l holds row l & 31; its bytes 0-15 are
+    k = 16 hi .. + 15 and its bytes 16-31 k = 32 + 16 hi .. + 15 (hi = l >> 5) -- block b is bytes 16 b .. 16 b + 15 of both
+    half-wave lanes.  16x16x128: as _mx_mfma."""
+    out = torch.zeros(64, 32, dtype=torch.uint8, device=dev)
+    n, R = (2, 32) if form == 32 else (4, 16)
+    for q in range(n):
+        out[R * q:R * q + R, :16] = Mk[:, 16 * q:16 * q + 16]
+        out[R * q:R * q + R, 16:] = Mk[:, 16 * n + 16 * q:16 * n + 16 * q + 16]
+    return out.view(torch.int32).contiguous()
+
+
+def _mx_mfma_acc(ops, form, Ak, Bk, sa, sb, Cm, dev):
+    """One scaled MFMA D = A B^T + C on logical operands: Ak, Bk [R, K] e4m3 bytes, block exponents sa, sb [R, K / 32] (the scale
+    of (row, block b) goes to lane row + R b), C [R, R] fp32 -> D [R, R] fp64.  R, K = 32, 64 or 16, 128."""
+    R, K = _mx_dims(form)
+    n = R * R // 64
+    lane = torch.arange(64, device=dev)
+    ea = torch.cat([sa[:, b] for b in range(K // 32)]).to(torch.int32).contiguous()
+    eb = torch.cat([sb[:, b] for b in range(K // 32)]).to(torch.int32).contiguous()
+    c = torch.empty(64, n, dtype=torch.float32, device=dev)
+    for r in range(n):
+        i, j = _mx_c_index(form, r, lane)
+        c[:, r] = Cm[i, j]
+    out = ops.debug_mx_mfma_acc(form, _mx_pack(form, Ak, dev), ea, _mx_pack(form, Bk, dev), eb, c)
+    D = torch.empty(R, R, device=dev)
+    for r in range(n):
+        i, j = _mx_c_index(form, r, lane)
+        D[i, j] = out[:, r]
+    return D.double()
+
+
+def _pow2_byte(e):          # e4m3 byte of 2^e, -9 <= e <= 8 (subnormals below 2^-6)
+    return (e + 7) << 3 if e >= -6 else 1 << (e + 9)
+
+
+def _pow2_bytes(es, dev):
+    return torch.tensor([_pow2_byte(-int(e)) for e in es], dtype=torch.uint8, device=dev)
+
+
+def _pgrid(R, dev):
+    """Row i carries 2^-(i % 10) in A, column c carries 2^-(c % 10) in B: element (i, c) of D sees the product 2^-p, p = 0 .. 18."""
+    a = torch.arange(R, device=dev) % 10
+    return a, a[:, None] + a[None, :]
+
+
+def test_mx_mfma32_lane_and_scale_semantics(dev):
+    """Pins what csrc/attention_fwd32_fp8.hip relies on (measured on gfx950): in v_mfma_scale_f32_32x32x64_f8f6f4 lane l supplies
+    row / column l & 31; MX block b (32 k) is bytes 16 b .. 16 b + 15 of both half-wave lanes; the scale of (row, block b) is byte
+    0 of the scale dword of lane row + 32 b, whatever the upper bytes hold; D[row][col] sits in lane col + 32 (row >> 2 & 1),
+    register (row & 3) + 4 (row >> 3); the accumulator C is added in the same layout.  The 16x16x128 form through the same entry
+    point gives what mg_debug_mx_mfma gives."""
+    from magma_amd import ops
+    g = torch.Generator(device=dev).manual_seed(1)
+    f8 = torch.float8_e4m3fn
+    for form in (32, 16):
+        R, K = _mx_dims(form)
+
+        def rbytes():                                      # random e4m3 bytes without the NaN encodings
+            b = torch.randint(0, 256, (R, K), generator=g, device=dev, dtype=torch.int64)
+            return torch.where((b & 0x7f) == 0x7f, b & 0x80, b).to(torch.uint8)
+        Ak, Bk = rbytes(), rbytes()
+        sa = torch.randint(118, 136, (R, K // 32), generator=g, device=dev)
+        sb = torch.randint(118, 136, (R, K // 32), generator=g, device=dev)
+        garbage = torch.randint(0, 1 << 23, (R, K // 32), generator=g, device=dev) << 8
+        A = Ak.view(f8).double() * torch.exp2(sa.double() - 127).repeat_interleave(32, dim=1)
+        B = Bk.view(f8).double() * torch.exp2(sb.double() - 127).repeat_interleave(32, dim=1)
+        mag = A.abs() @ B.abs().t()
+        Cm = torch.randn(R, R, generator=g, device=dev) * float(mag.mean())
+        got = _mx_mfma_acc(ops, form, Ak, Bk, sa | garbage, sb | garbage, Cm, dev)
+        ref = A @ B.t() + Cm.double()
+        assert rel(got.float(), ref.float()) < 1e-4, (form, rel(got.float(), ref.float()))
+        # per element: a wrong lane, block or register moves single elements by whole products
+        bound = kcmp.f8_mfma_truncation(A, B) + kcmp.gamma(2 * (K // 8 + 1) + 2) * (mag + Cm.double().abs()) + kcmp.FLOOR
+        kcmp.assert_elementwise(got, ref, bound, f"one scaled fp8 MFMA with C, form {form}, random layout probe")
+        if form == 16:
+            zero = torch.zeros(R, R, device=dev)
+            assert torch.equal(_mx_mfma_acc(ops, 16, Ak, Bk, sa, sb, zero, dev), _mx_mfma(ops, Ak, Bk, sa, sb, dev))
+
+
+def test_mx_mfma32_groups_and_truncation(dev):
+    """Pins kernel_compare.F8_MFMA32_GROUP / F8_MFMA32_KEEP_BITS (measured on gfx950, not in the ISA guide): in
+    v_mfma_scale_f32_32x32x64_f8f6f4, with k = 32 b + 16 hi + r for byte 16 b + r of a lane in half-wave hi, the products are summed
+    in groups of 8 consecutive k.  One product 2^-p beside 2^8 (C = 0), the large one in every group and the small one at every other
+    k: in the same group it survives exactly down to 2^-13 of the large one and is gone below (truncation); anywhere else -- the
+    other half of the 16-byte chunk, the lane's other chunk (the other 32-block), the other half-wave -- down to 2^-23.  A
+    multi-bit product is cut, not rounded, and a negative one is cut towards zero.  Exact results, no tolerance."""
+    from magma_amd import ops
+    G, KB = kcmp.F8_MFMA32_GROUP, kcmp.F8_MFMA32_KEEP_BITS
+    assert (G, KB) == (8, 13)
+    one = torch.full((32, 2), 127, dtype=torch.int32, device=dev)
+    zero = torch.zeros(32, 32, device=dev)
+    a, p = _pgrid(32, dev)
+    small = _pow2_bytes(a, dev)
+    for j0 in (0, 3, 7, 8, 15, 16, 21, 31, 32, 40, 47, 48, 55, 63):          # every group, first / inner / last byte of a group
+        for j in range(64):
+            if j == j0:
+                continue
+            Ak = torch.zeros(32, 64, dtype=torch.uint8, device=dev)
+            Bk = torch.zeros(32, 64, dtype=torch.uint8, device=dev)
+            Ak[:, j0], Bk[:, j0] = 0x78, 0x38                              # 2^8 * 1
+            Ak[:, j], Bk[:, j] = small, small                              # row i, column c: 2^-(i % 10) * 2^-(c % 10)
+            d = _mx_mfma_acc(ops, 32, Ak, Bk, one, one, zero, dev) - 256.0
+            keep = KB if j // G == j0 // G else 23
+            want = torch.where(8 + p <= keep, torch.exp2(-p.double()), torch.zeros_like(d))
+            assert torch.equal(d, want), (j0, j, keep, (d != want).nonzero()[:4].tolist())
+    # 1.75 * 1.25 = 2.1875 = 10.0011b (times 2^-p) and -1 (times 2^-p) in the group of the large product: cut below 2^(8 - 13)
+    a7 = torch.arange(32, device=dev) % 7
+    p7 = (a7[:, None] + a7[None, :]).double()
+    for neg in (False, True):
+        Ak = torch.zeros(32, 64, dtype=torch.uint8, device=dev)
+        Bk = torch.zeros(32, 64, dtype=torch.uint8, device=dev)
+        Ak[:, 0], Bk[:, 0] = 0x78, 0x38
+        Ak[:, 5] = (((7 - a7) << 3) | (0x80 if neg else 6)).to(torch.uint8)    # -2^-a  or  1.75 * 2^-a
+        Bk[:, 5] = (((7 - a7) << 3) | (0 if neg else 2)).to(torch.uint8)       #  2^-b  or  1.25 * 2^-b
+        d = _mx_mfma_acc(ops, 32, Ak, Bk, one, one, zero, dev) - 256.0
+        exact = (-1.0 if neg else 2.1875) * torch.exp2(-p7)
+        step = 2.0 ** (8 - KB)
+        assert torch.equal(d, torch.trunc(exact / step) * step), neg
+    g = torch.Generator(device=dev).manual_seed(3)
+    f8 = torch.float8_e4m3fn
+    for spread in (0, 4, 9):
+        for _ in range(20):
+            b = torch.randint(0, 256, (2, 32, 64), generator=g, device=dev, dtype=torch.int64)
+            b = torch.where((b & 0x7f) == 0x7f, b & 0x80, b).to(torch.uint8)
+            Ak, Bk = b[0].contiguous(), b[1].contiguous()
+            sa = 127 + torch.randint(-spread, spread + 1, (32, 2), generator=g, device=dev)
+            sb = 127 + torch.randint(-spread, spread + 1, (32, 2), generator=g, device=dev)
+            A = Ak.view(f8).double() * torch.exp2(sa.double() - 127).repeat_interleave(32, dim=1)
+            B = Bk.view(f8).double() * torch.exp2(sb.double() - 127).repeat_interleave(32, dim=1)
+            mag = A.abs() @ B.abs().t()
+            Cm = torch.randn(32, 32, generator=g, device=dev) * float(mag.mean())
+            ref = A @ B.t() + Cm.double()
+            # 8 group sums and C: 9 terms aligned with truncation (counted as 2 u32 each, as for the 16x16x128 form) and one rounding
+            bound = kcmp.f8_mfma_truncation(A, B, G, KB) + kcmp.gamma(2 * 9 + 2) * (mag + Cm.double().abs()) + kcmp.FLOOR
+            kcmp.assert_elementwise(_mx_mfma_acc(ops, 32, Ak, Bk, sa, sb, Cm, dev), ref, bound,
+                                    f"one scaled fp8 MFMA 32x32x64 with C, block exponents +-{spread}")
+
+
+@pytest.mark.parametrize("form", [32, 16])
+def test_mx_mfma_accumulator_rule(dev, form):
+    """Pins how the accumulator C enters the scaled f8f6f4 MFMA, both forms (kernel_compare.F8_MFMA_SUM_BITS; measured): C does NOT
+    take part in the in-group alignment -- it is added like one more group sum.  The group sums and C are aligned to the largest
+    of them, a term loses what lies more than 24 bits below that one's leading bit, and the sum is rounded to nearest fp32:
+      (1) C = 2^c beside ONE product 2^-p at any k: the product arrives exactly while it is a multiple of ulp(C) = 2^(c - 23);
+      (2) a product 2^8 beside C = 2^-p: C arrives down to 2^-15 = ulp(2^8); C = 1.5 * 2^-15 rounds up to 2^-14 (nearest even),
+          C = 1.5 * 2^-16 is first cut to 2^-16, then the tie rounds to even: gone;
+      (3) C = 2^8 beside a FULL group of 8 products 2^-p each: the group is summed first (2^(3 - p), exact) -- it arrives while
+          8 * 2^-p >= 2^-15, although no single product reaches an ulp of C;
+      (4) C = 2^8 beside two groups of sum 2^-16 each: one ulp together (the alignment keeps a 24th bit); of sum 2^-17 each, with
+          four groups: 2^-15 together in exact arithmetic, but each is cut first: gone;
+      (5) a multi-bit product 2.1875 * 2^-p in ANOTHER group than a product 2^8 is rounded to nearest at ulp(2^8), not cut."""
+    from magma_amd import ops
+    R, K = _mx_dims(form)
+    assert kcmp.F8_MFMA_SUM_BITS == 24
+    one = torch.full((R, K // 32), 127, dtype=torch.int32, device=dev)
+    a, p = _pgrid(R, dev)
+    small = _pow2_bytes(a, dev)
+    zeros = lambda: torch.zeros(R, K, dtype=torch.uint8, device=dev)
+    ulp = lambda c: 2.0 ** (c - 23)
+    # (1): the block scale 2^-12 pushes the product down to 2^-12 .. 2^-30
+    for c in (0, 8, 20):
+        for j in (0, 1, 7, 8, 17, 33, K - 1):
+            for shift in (0, 12):
+                Ak, Bk = zeros(), zeros()
+                Ak[:, j], Bk[:, j] = small, small
+                Cm = torch.full((R, R), 2.0 ** c, device=dev)
+                d = _mx_mfma_acc(ops, form, Ak, Bk, one - shift, one, Cm, dev) - 2.0 ** c
+                v = torch.exp2(-(p + shift).double())
+                assert torch.equal(d, torch.where(v >= ulp(c), v, torch.zeros_like(v))), (c, j, shift)
+    # (2)
+    ii = torch.arange(R, device=dev)
+    pc = (ii[:, None] + (ii[None, :] % 2) * R).clamp(max=40).double()
+    for j0 in (0, 40):
+        for mult in (1.0, 1.5):
+            Ak, Bk = zeros(), zeros()
+            Ak[:, j0], Bk[:, j0] = 0x78, 0x38
+            Cm = (mult * torch.exp2(-pc)).float()
+            d = _mx_mfma_acc(ops, form, Ak, Bk, one, one, Cm, dev) - 256.0
+            if mult == 1.0:
+                want = torch.where(pc <= 15, torch.exp2(-pc), torch.zeros_like(pc))
+            else:
+                want = torch.where(pc < 15, 1.5 * torch.exp2(-pc), torch.where(pc == 15, torch.full_like(pc, 2.0 ** -14), torch.zeros_like(pc)))
+            assert torch.equal(d, want), (j0, mult)
+    # (3), (4): n products 2^-p each in k = 0 .. n - 1, i.e. n / 8 full groups
+    for n, last_p in ((8, 18), (16, 19), (32, 19)):
+        Ak, Bk = zeros(), zeros()
+        for j in range(n):
+            Ak[:, j], Bk[:, j] = small, small
+        for shift in (0, 12):
+            Cm = torch.full((R, R), 256.0, device=dev)
+            d = _mx_mfma_acc(ops, form, Ak, Bk, one - shift, one, Cm, dev) - 256.0
+            pp = (p + shift).double()
+            assert torch.equal(d, torch.where(pp <= last_p, n * torch.exp2(-pp), torch.zeros_like(pp))), (n, shift)
+    # (5)
+    a7 = torch.arange(R, device=dev) % 7
+    p7 = (a7[:, None] + a7[None, :]).double() + 8
+    Ak, Bk = zeros(), zeros()
+    Ak[:, 0], Bk[:, 0] = 0x78, 0x38
+    Ak[:, 32] = (((7 - a7) << 3) | 6).to(torch.uint8)
+    Bk[:, 32] = (((7 - a7) << 3) | 2).to(torch.uint8)
+    sa = one.clone()
+    sa[:, 1] = 127 - 8
+    d = _mx_mfma_acc(ops, form, Ak, Bk, sa, one, torch.zeros(R, R, device=dev), dev) - 256.0
+    assert torch.equal(d, ((256.0 + 2.1875 * torch.exp2(-p7)).float().double() - 256.0))
+
+
 @pytest.mark.parametrize("M,K", [(5, 64), (37, 1000), (8, 4096), (3, 16384)])
 def test_quantize_mx(dev, M, K):
     from magma_amd import ops
@@ -448,7 +667,8 @@ def test_fp8_attention_forward(dev, B, H, S):
     (2) The attention kernel against fp32 softmax(QK^T/16)V evaluated on the DEQUANTISED operands (what the kernel multiplies):
         what is left is the rounding of P to e4m3 (3 mantissa bits), 2^-4 relative per probability -- stated bound 3e-2 rel-L2
         on the output (measured 1.3-1.9e-2), lse to 2e-3 absolute (no P rounding in it).  A late dominant key forces the
-        deferred-maximum rescale."""
+        deferred-maximum rescale.  The small shapes are also checked per element against kernel_compare.fp8_attention_bound
+        (tests/test_fp8_attention_gpu.py drives the kernel with inputs where each causal boundary decides the output)."""
     from magma_amd import ops
     d = H * 256
     rot = 64
@@ -494,12 +714,8 @@ def test_fp8_attention_forward(dev, B, H, S):
     ref = (torch.softmax(sc, -1) @ vd).permute(0, 2, 1, 3).reshape(B * S, d)
     e = rel(out, ref)
     assert e < 3e-2, e
-    # NO per-element check here, and why: two terms of its bound are known -- u = 2^-4 for P rounded to e4m3 (with an absolute
-    # 2^-14 below e4m3's normal range, 16 p < 2^-6), taken against this reference on the dequantised operands -- but the third is
-    # not: the truncation inside v_mfma_scale_f32_32x32x64_f8f6f4, which forms both QK^T and PV here.  The 16x16x128 form drops
-    # bits below 2^-13 of the largest product of a group of 8 (kernel_compare.f8_mfma_truncation, pinned by a one-instruction
-    # test through mg_debug_mx_mfma); group size and kept width of the 32x32x64 form can only be measured the same way, and the
-    # library has no one-instruction entry point for it.  Assuming the 16x16x128 figures would be a fitted term, not a derived one.
+    if B * H * S <= 1024:            # per element, output and lse (kernel_compare.fp8_attention_bound); the large case keeps the norm alone
+        kcmp.assert_causal_attention_fp8(out, op, f"attn_prefill_fp8 B={B} H={H} S={S}", lse=lse)
     assert float((lse - torch.logsumexp(sc, -1)).abs().max()) < 2e-3
     # against the bf16 path on the unquantised operands: the whole cost of e4m3 operands + e4m3 P (reported, loosely bounded)
     out16 = torch.empty(B * S, d, dtype=BF16, device=dev)

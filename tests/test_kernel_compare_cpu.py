@@ -352,6 +352,144 @@ def test_attention_self_dominant_inputs(S, c):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# causal attention on the fp8 MFMA (csrc/attention_fwd32_fp8.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+F8 = torch.float8_e4m3fn
+FP8_FAULT_FACTOR = 10.0
+FP8_FAULTS = ("limit -1", "limit +1", "V scale of the neighbouring block", "two keys swapped", "missing rescale")
+
+
+def pow2_scale(amax):
+    """The producer's rule: the smallest power of two 2^e with amax / 2^e <= 448 (1 for an all-zero block)."""
+    e = torch.ceil(torch.log2(amax.clamp_min(1e-30) / 448.0))
+    return torch.where(amax > 0, torch.exp2(e), torch.ones_like(amax))
+
+
+class Fp8StandIn:
+    """mg_rotary_split_fp8's operands (without the rotary) and mg_attn_prefill_fp8's arithmetic in torch, one head: q / k e4m3 with
+    one power-of-two scale per token, V e4m3 with one per (d, 32 keys), keys padded to whole 64-key tiles the way the kernel sees
+    them (K rows beyond S: the bytes of row S - 1 with a unit scale; V: zero bytes, unit scales); fp32 scores; the deferred maximum
+    with threshold ``defer`` (log2 units: 4 as in the kernel, 0 = the plain running maximum); P = e4m3(16 p) / 16, row sum of the
+    unrounded p; O accumulated in fp32 tile by tile; one rounding to bf16.  The MFMA's in-group truncation is not imitated."""
+
+    def __init__(self, q, k, v):
+        S = q.shape[0]
+        self.S, self.Sp = S, -(-S // 64) * 64
+        qf, kf, vf = q.float(), k.float(), v.float()
+        sq, sk = pow2_scale(qf.abs().amax(-1, keepdim=True)), pow2_scale(kf.abs().amax(-1, keepdim=True))
+        self.qd = (qf / sq).to(F8).float() * sq
+        kb = (kf / sk).to(F8).float()
+        self.kd = kb * sk
+        self.k_all = torch.cat([self.kd, kb[S - 1:S].expand(self.Sp - S, -1)])            # what the kernel multiplies, padding included
+        vp = torch.cat([vf, torch.zeros(self.Sp - S, 256)]).view(self.Sp // 32, 32, 256)
+        self.sv = pow2_scale(vp.abs().amax(1))                                               # [blocks, 256]
+        self.vb = (vp / self.sv[:, None, :]).to(F8).float()                                  # [blocks, 32, 256] e4m3 values
+        self.vd = (self.vb * self.sv[:, None, :]).view(self.Sp, 256)[:S]
+
+    def run(self, defer=4.0, rows=None, fault=None):
+        """out bf16 [len(rows), 256], lse fp32 [len(rows)] of the query rows ``rows`` (default: all), ``fault`` seeded into them."""
+        S, Sp = self.S, self.Sp
+        rows = torch.arange(S) if rows is None else torch.as_tensor(rows)
+        lim = rows.clone()
+        if fault == "limit -1":
+            lim -= 1
+        elif fault == "limit +1":
+            lim += 1
+        t2 = (self.qd[rows] @ self.k_all.t()) * (0.0625 * 1.4426950408889634)               # fp32, log2 units
+        n = len(rows)
+        m2 = torch.full((n,), -1e30)
+        lsum, O = torch.zeros(n), torch.zeros(n, 256)
+        for kv0 in range(0, Sp, 64):
+            act = lim >= kv0                                                                 # rows that see a key of this tile
+            if not bool(act.any()):
+                break
+            vis = torch.arange(kv0, kv0 + 64)[None, :] <= lim[:, None]
+            sn = t2[:, kv0:kv0 + 64].masked_fill(~vis, -1e30)
+            cand = sn.amax(-1)
+            mnew = torch.where(cand > m2 + defer, cand, m2)
+            alpha = torch.exp2(m2 - mnew)
+            m2 = mnew
+            p = torch.exp2(sn - m2[:, None])
+            lsum = lsum * alpha + p.sum(-1)
+            if fault != "missing rescale":
+                O = O * alpha[:, None]
+            p8 = (p * 16.0).to(F8).float() * 0.0625
+            for b in range(2):
+                blk = kv0 // 32 + b
+                vb, sv = self.vb[blk], self.sv[blk]
+                c = (p8[:, 32 * b:32 * b + 32] @ vb) * sv
+                own = (rows // 32 == blk)                                                    # the block of the row's own (newest) key
+                if fault == "V scale of the neighbouring block" and bool(own.any()):
+                    c[own] = (p8[own, 32 * b:32 * b + 32] @ vb) * self.sv[blk ^ 1]
+                if fault == "two keys swapped" and bool(own.any()):                          # keys r and r ^ 1 exchange their V bytes
+                    for i in own.nonzero().flatten().tolist():
+                        r = int(rows[i]) % 32
+                        vs = vb.clone()
+                        vs[[r, r ^ 1]] = vb[[r ^ 1, r]]
+                        c[i] = (p8[i, 32 * b:32 * b + 32] @ vs) * sv
+                O = O + c
+        return (O / lsum[:, None]).to(BF16), (m2 + torch.log2(lsum)) * 0.6931471805599453
+
+
+def fp8_fault_rows(S):
+    """Single tile-edge rows: the last r < S - 1 with r % 64 == 63, the last with r % 64 == 0, the last row (of a partial 128-block
+    unless S % 128 == 0), the row before it."""
+    return {"r % 64 == 63": ((S - 1) // 64) * 64 - 1, "r % 64 == 0": ((S - 1) // 64) * 64, "last": S - 1, "last - 1": S - 2}
+
+
+_FP8_CASES = {}
+
+
+def fp8_case(kind, S):
+    if (kind, S) not in _FP8_CASES:
+        q, k, v = kc.fp8_attention_inputs(kind, (S, 256), seed=91)
+        st = Fp8StandIn(q, k, v)
+        T = kc.fp8_attention_terms(st.qd, st.kd, st.vd, torch.ones(S, S, dtype=torch.bool).tril())
+        _FP8_CASES[(kind, S)] = (st, T, kc.fp8_attention_bound(T, S), kc.fp8_lse_bound(T, S))
+    return _FP8_CASES[(kind, S)]
+
+
+@pytest.mark.parametrize("S", [193, 300, 1024])
+@pytest.mark.parametrize("kind", kc.FP8_ATTN_INPUTS + ("i.i.d.",))
+def test_fp8_attention_stand_in_is_inside_the_bound(kind, S):
+    """The honest stand-in, with the kernel's deferral threshold and with the plain running maximum, stays inside
+    fp8_attention_bound / fp8_lse_bound for every input kind (and for i.i.d. inputs of the GPU test's scale)."""
+    if kind == "i.i.d.":
+        st = Fp8StandIn(rnd(S, 256, seed=91, scale=0.7).to(BF16), rnd(S, 256, seed=92, scale=0.7).to(BF16), rnd(S, 256, seed=93, scale=0.7).to(BF16))
+        T = kc.fp8_attention_terms(st.qd, st.kd, st.vd, torch.ones(S, S, dtype=torch.bool).tril())
+        bound, lb = kc.fp8_attention_bound(T, S), kc.fp8_lse_bound(T, S)
+    else:
+        st, T, bound, lb = fp8_case(kind, S)
+    for defer in (4.0, 0.0):
+        out, lse = st.run(defer=defer)
+        assert kc.assert_elementwise(out, T["ref"], bound, f"fp8 stand-in, {kind}, S={S}, deferral {defer}") < 1.0
+        kc.assert_elementwise(lse, T["lse"], lb, f"fp8 stand-in lse, {kind}, S={S}, deferral {defer}")
+
+
+@pytest.mark.parametrize("S", [193, 300, 1024])
+def test_fp8_attention_seeded_faults_exceed_the_bound(S):
+    """Each fault, seeded into ONE tile-edge row, leaves fp8_attention_bound by at least 10 x on at least one input kind (the
+    table names it, with the whole-tensor rel-L2 of the output that holds the faulty row: the GPU test's criterion is < 3e-2)."""
+    print()
+    for where, r in fp8_fault_rows(S).items():
+        for fault in FP8_FAULTS:
+            if fault == "limit +1" and r == S - 1 and S % 64 == 0:
+                continue        # key S would open a tile of its own, which the tile loop (ceil(S / 64) tiles) never reaches: no such fault
+            best, best_kind, line = 0.0, None, []
+            for kind in kc.FP8_ATTN_INPUTS:
+                st, T, bound, _ = fp8_case(kind, S)
+                good, _ = st.run()
+                bad_row, _ = st.run(rows=[r], fault=fault)
+                w = kc.worst_ratio(bad_row, T["ref"][r:r + 1], bound[r:r + 1])
+                bad = good.clone(); bad[r] = bad_row[0]
+                line.append(f"{kind} {w:.3g} (rel-L2 {old_rel(bad, T['ref']):.3f})")
+                if w > best:
+                    best, best_kind = w, kind
+            print(f"    S={S} row {r} ({where}) {fault:<36s} caught by {best_kind!r} at {best:.3g} x the bound   [" + ", ".join(line) + "]")
+            assert best >= FP8_FAULT_FACTOR, f"S={S} row {r} ({where}): {fault}: no input kind reaches {FP8_FAULT_FACTOR} x the bound (best {best:.3g}, {best_kind})"
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # causal attention, backward
 # ---------------------------------------------------------------------------------------------------------------------------
 def attention_backward_stand_in(q, k, v, dO_rows, out_rows, lse):
