@@ -1182,6 +1182,8 @@ def attn_bwd_rows(x: AttnRows, dO, O, lse, merged_rot=None, mx_out=None, no_out:
     wanted (rounded up to whole 128-position blocks; the other rows of the outputs stay unwritten)."""
     _need_gpu(dO)
     assert O.ndim == 2 and O.stride(1) == 1 and dO.is_contiguous()
+    # the rows first_rows leaves unwritten would keep 0xFF scale bytes (NaN in E8M0) in an MX copy read in whole 64-row groups
+    assert not (first_rows and mx_out is not None), "first_rows and mx_out exclude each other"
     B, H, S, dev = x.B, x.H, x.S, dO.device
     D = torch.empty(B, H, S, 2, dtype=torch.float32, device=dev)
     if merged_rot is None:

@@ -20,7 +20,7 @@ import contextlib
 import math
 import os
 from pathlib import Path
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 import torch.distributed as dist
@@ -131,6 +131,14 @@ _WGRAD_INPLACE = os.environ.get("MAGMA_WGRAD_INPLACE", "1") != "0"     # A/B swi
 def _t(x: torch.Tensor) -> RawWeight:
     """Transposed copy of a [R, C] activation/weight as a GEMM B operand [C, R]."""
     return RawWeight(ops.transpose(x))       # [C, round_up(R,8)], zero padded
+
+
+class BlockKind(NamedTuple):
+    """What one GPT-J block is for the training step (MagmaEngine._train_block_kind)."""
+    mlp: str          # "none" | "cat" | "parallel" | "fp8" | "serial": the MLP adapter's launches
+    attn: str         # "none" | "parallel" | "serial": the attention adapter's
+    attention: str    # "fp8" | "rows": the attention forward
+
 
 
 class MagmaEngine:
@@ -475,26 +483,41 @@ class MagmaEngine:
             self._lm_train_packs = (packs, PackedLinear(wt))
         return self._lm_train_packs
 
-    def _cat_out_up(self, li, ly, blk):
-        """[W_out | W_up] of block li as a row-major GEMM operand [d, d + r] (bias b_up), or None where the block does not have
-        the shape (plain ReLU MLP adapter without LayerNorm, no attention adapter, out_proj without a bias, bf16, frozen LM).
-        The W_out columns are written once; the W_up columns are refreshed from the live parameter on every forward."""
-        if not self.cat_up or self.fp8 or self.lm_trainable:
-            return None
-        if ly.mlp_adapter is None or ly.mlp_par is not None or ly.attn_adapter is not None:
-            return None
-        mod = blk.mlp[1]
-        a_mod, _ = ly._src
-        if not getattr(mod, "plain", False) or a_mod.out_proj.bias is not None:
-            return None
-        up = mod.up
-        d, r = up.weight.shape
-        if r % 8 or d % 8:            # 16-byte aligned [:, d:] view
-            return None
+    def _layer(self, li):     # (the LMEngine's packed layer, the GPT-J block module) of block li
+        return self.module.lm.engine.layers[li], self.module.lm.transformer.h[li]
+
+    def _train_block_kind(self, li) -> BlockKind:
+        """What block li is for the training step, from its adapters and the switches as they are NOW: the ONE place that tells the
+        shapes apart (table: DESIGN.md, "The training block kinds").  Pure host logic; _block_forward asks once per forward and the
+        answer travels in the tape (sv["kind"]), where the backward reads it.  mlp: the first that applies of "cat" ([W_out | W_up]
+        as one GEMM), "parallel", "fp8" (the MX adapter chain), "serial"; a plain adapter is a ReLU one without LayerNorm."""
+        ly, blk = self._layer(li)
+        attn = "none" if ly.attn_adapter is None else "serial" if ly.attn_par is None else "parallel"
+        mlp = "none"
+        if ly.mlp_adapter is not None:
+            mod = blk.mlp[1] if ly.mlp_par is None else None      # Sequential(mlp, Adapter); a parallel adapter wraps the MLP instead
+            plain = mod is not None and getattr(mod, "plain", False)
+            r, d = mod.down.weight.shape if plain else (1, 1)     # down [r, d], up [d, r]
+            if (plain and self.cat_up and not self.fp8 and not self.lm_trainable and attn == "none"
+                    and ly._src[0].out_proj.bias is None and r % 8 == 0 and d % 8 == 0):
+                mlp = "cat"
+            elif mod is None:
+                mlp = "parallel"
+            elif plain and self.fp8 and self.fp8_mx and self.fp8_adapters and r % 256 == 0 and d % 256 == 0:
+                mlp = "fp8"
+            else:
+                mlp = "serial"
+        return BlockKind(mlp, attn, "fp8" if self.fp8 and self.fp8_attn else "rows")
+
+    def _cat_out_up(self, li):
+        """[W_out | W_up] of a "cat" block as a row-major GEMM operand [d, d + r] (bias b_up).  The W_out columns are written once;
+        the W_up columns are refreshed from the live parameter on every forward."""
+        ly, blk = self._layer(li)
+        up, (d, r) = blk.mlp[1].up, blk.mlp[1].up.weight.shape
         buf = self._out_up.get(li)
         if buf is None or buf.shape != (d, d + r):
             buf = self._out_up[li] = torch.empty(d, d + r, dtype=BF16, device=self.device)
-            buf[:, :d].copy_(a_mod.out_proj.weight.detach())
+            buf[:, :d].copy_(ly._src[0].out_proj.weight.detach())
         buf[:, d:].copy_(up.weight.data)
         return RawWeight(buf, bias=self.master_of(up.bias))
 
@@ -504,30 +527,25 @@ class MagmaEngine:
         return (RawWeight(dn.weight.data, bias=self.master_of(dn.bias)),
                 RawWeight(up.weight.data, bias=self.master_of(up.bias)))
 
+    def _par_scale(self, wrapper):
+        """adapter_scale of a parallel adapter as the fp32 vector the GEMM epilogue's ``scale`` takes; None for the unscaled form."""
+        sp = wrapper.adapter_scale
+        if not torch.is_tensor(sp):
+            assert float(sp) == 1.0
+            return None
+        sval = self.master_of(sp) if self.is_trainable(sp) else sp.detach().float()
+        return sval.reshape(1).to(F32).expand(wrapper.up.weight.shape[0]).contiguous()
+
     def _par_adapter_ops(self, wrapper):
         """(down, up, scale vector or None) of a ParallelAdapter / ParallelAdapterWrapper on the live parameters.  The GEMM
         epilogue computes acc * scale[n] + bias[n]; the reference (acc + b_up) * adapter_scale, so the up bias handed to the
         epilogue is pre-multiplied by the (device-resident, trainable) scale."""
         dn, up = wrapper.down, wrapper.up
         dnw = RawWeight(dn.weight.data, bias=self.master_of(dn.bias))
-        sp = wrapper.adapter_scale
-        if not torch.is_tensor(sp):
-            assert float(sp) == 1.0
+        sc = self._par_scale(wrapper)
+        if sc is None:
             return dnw, RawWeight(up.weight.data, bias=self.master_of(up.bias)), None
-        sval = self.master_of(sp) if self.is_trainable(sp) else sp.detach().float()
-        sc = sval.reshape(1).to(F32).expand(up.weight.shape[0]).contiguous()
         return dnw, RawWeight(up.weight.data, bias=(self.master_of(up.bias) * sc).contiguous()), sc
-
-    def _ad8_ok(self, ly, blk) -> bool:
-        """fp8 adapter chain: plain ReLU MLP adapter (no LayerNorm, not parallel), shapes the 256x256 fp8 kernel's MX output covers.
-        Takes the block: ``blk.mlp`` is Sequential(mlp, Adapter) only when the block has an MLP adapter (the bare MLP otherwise)."""
-        if not (self.fp8 and self.fp8_mx and self.fp8_adapters) or ly.mlp_adapter is None or ly.mlp_par is not None:
-            return False
-        mod = blk.mlp[1]
-        if not getattr(mod, "plain", False):
-            return False
-        r, d = mod.down.weight.shape
-        return r % 256 == 0 and d % 256 == 0
 
     def _ad8(self, li, mod):
         """e4m3 operands of the adapter's four activation-side GEMMs, rebuilt when the weights epoch moved (every optimizer step)."""
@@ -630,117 +648,108 @@ class MagmaEngine:
                         logits_seq_len=S,
                         logits=LMOutput.lazy(lambda: eng._full_logits(xf, xf.shape[0]).view(B, S, eng.V)))
 
-    def _lm_forward(self, emb, labels, tape):
-        eng = self.module.lm.engine
-        dev = self.device
-        B, S, d = emb.shape
-        M, H = B * S, eng.H
-        x = emb.view(M, d)
-        def block(li, ly, blk, x):
-            """One GPT-J block forward: (x', what its backward needs).  Called by the loop below and -- under per-block
-            recompute (self.recompute) -- once more per block from _lm_backward, on the saved block input."""
-            sv = {"x": x}
-            ln = ops.layernorm(x, ly.ln_g, ly.ln_b, eng.eps)
-            lnq = ops.quantize_rows_fp8(ln) if self.fp8 else None     # shared by qkv and fc_in
-            qkv = self._fgemm((li, "qkv"), ln, ly.qkv, lnq)
-            a8 = rows = None
-            if self.fp8 and self.fp8_attn:
-                # e4m3 copies of q, k, v^T for the fp8 forward; the same pass writes the rotated q / k back into the qkv buffer (the
-                # arithmetic of rotary_qk_inplace): the bf16 backward reads q, k, v as rows of that buffer -- no bf16 copies
-                a8 = ops.rotary_split_fp8(qkv, B, S, H, eng.rot, eng.sin_t, eng.cos_t, inplace=True)
-                rows = ops.AttnRows.of_qkv(qkv, B, S, H)
-            elif os.environ.get("MAGMA_ATTN_TR", "1") == "0":
-                # A/B switch only (tools/gpu_r06_step_ab.sh): the round-5 path -- split pass with three transposes, kernels with
-                # transposed operand images
-                vt_ld = ops.ceil_to(S, 32)
-                q, k, v = (torch.empty(B, H, S, 256, dtype=BF16, device=dev) for _ in range(3))
-                vt, qt, kt = (torch.empty(B, H, vt_ld // 32, 256, 32, dtype=BF16, device=dev) for _ in range(3))
-                ops.rotary_split_train(qkv, B, S, H, eng.rot, eng.sin_t, eng.cos_t, q, k, v, vt, qt, kt)
-                sv.update(old=(q, k, v, qt, kt))
-            else:
-                # round 6: no split pass and no transposed copies.  The rotary is applied in place to the q / k sections of the GEMM
-                # output, and the attention kernels (csrc/attention_tr.hip) take q, k, v as strided rows of that buffer -- forward
-                # and backward; the s-contraction fragments (V^T; Q^T, dO^T, K^T) come from the row images by ds_read_b64_tr_b16.
-                ops.rotary_qk_inplace(qkv, B, S, H, eng.rot, eng.sin_t, eng.cos_t)
-                rows = ops.AttnRows.of_qkv(qkv, B, S, H)
-            out_up = self._cat_out_up(li, ly, blk)
-            if out_up is not None:
-                ctx_t = torch.empty(M, out_up.K, dtype=BF16, device=dev)        # [ctx | t]: one saved buffer, one GEMM operand
-                ctx = ctx_t[:, :d]
-            else:
-                ctx = torch.empty(M, d, dtype=BF16, device=dev)
-            lse = torch.empty(B, H, S, dtype=F32, device=dev)
-            ctx_mx = None
-            if a8 is not None:
-                # fp8_mx: the attention epilogue also emits the OCP MX e4m3 copy of ctx (it holds whole rows): out_proj then runs as an
-                # MX GEMM without a quantisation pass over ctx
-                if self.fp8_mx and out_up is None and (H * 256) % 256 == 0:
-                    ctx_mx = ops.mx_empty(M, H * 256, dev)
-                ops.attn_prefill_fp8(a8, ctx, lse=lse, mx_out=ctx_mx)
-            elif rows is None:
-                ops.attn_prefill(q, k, vt, ctx, B, H, S, lse=lse)
-            else:
-                ops.attn_fwd_rows(rows, ctx, lse=lse)
-            sv.update(rows=rows, ctx=ctx, lse=lse)
-            a = None if out_up is not None else self._fgemm((li, "out"), ctx if ctx_mx is None else ("mx", *ctx_mx), ly.out)
-            if ly.attn_adapter is not None and ly.attn_par is not None:
-                # parallel / scaled_parallel (reference adapters.py:42-92): the adapter reads the attention INPUT (ln_1 output)
-                dn, up, sc = self._par_adapter_ops(blk.attn)
-                ta = self._adapter_down(blk.attn, ln, dn, sv, "ta")
-                a = ops.gemm(ta, up, scale=sc, residuals=(a,), layout="rm")
-            elif ly.attn_adapter is not None:
-                dn, up = self._adapter_ops(blk.attn)
-                ta = self._adapter_down(blk.attn, a, dn, sv, "ta")
-                a2 = ops.gemm(ta, up, residuals=(a,), layout="rm")
-                sv.update(a=a)
-                a = a2
-            hpre = torch.empty(M, ly.fc_in.N, dtype=BF16, device=dev)
-            h = self._fgemm((li, "fc_in"), ln, ly.fc_in, lnq, act=ops.MG_ACT_GELU_NEW, out2=hpre, mx_out=self.fp8 and self.fp8_mx)
-            sv["hpre"] = hpre
-            if self.lm_trainable:
-                sv["h"] = h                    # operand of the fc_out weight gradient
-            if out_up is not None:
-                # x' = [ctx | t] [W_out | W_up]^T + b_up + m + x   (reference adapters.py:38-39 on the MLP output + GPT-J's residual sum)
-                dn, _ = self._adapter_ops(blk.mlp[1])
-                m = self._fgemm((li, "fc_out"), h, ly.fc_out)
-                sv["t"] = ops.gemm(m, dn, act=ops.MG_ACT_RELU, layout="rm", out=ctx_t[:, d:])
-                x = ops.gemm(ctx_t, out_up, residuals=(m, x), layout="rm")
-                sv.update(m=m)
-            elif ly.mlp_adapter is not None and ly.mlp_par is not None:
-                dn, up, sc = self._par_adapter_ops(blk.mlp)
-                m = self._fgemm((li, "fc_out"), h, ly.fc_out)
-                t = self._adapter_down(blk.mlp, ln, dn, sv, "t")
-                x = ops.gemm(t, up, scale=sc, residuals=(m, a, x), layout="rm")
-            elif self._ad8_ok(ly, blk):
-                # config[4]: the adapter GEMMs on the fp8 MFMA, operands from the producing epilogues (see __init__)
-                p8 = self._ad8(li, blk.mlp[1])
-                m_mx = ops.mx_empty(M, ly.fc_out.N, dev)
-                m = self._fgemm((li, "fc_out"), h, ly.fc_out, mx_out=m_mx)
-                t_mx = ops.mx_empty(M, p8["dn"].N, dev)
-                t = ops.gemm_mx_fp8(m_mx[0], m_mx[1], p8["dn"], act=ops.MG_ACT_RELU, mx_out=t_mx, tile=256)
-                x = ops.gemm_mx_fp8(t_mx[0], t_mx[1], p8["up"], residuals=(m, a, x))
-                sv.update(m=m, t=t)
-            elif ly.mlp_adapter is not None:
-                dn, up = self._adapter_ops(blk.mlp[1])
-                m = self._fgemm((li, "fc_out"), h, ly.fc_out)
-                t = self._adapter_down(blk.mlp[1], m, dn, sv, "t")
-                x = ops.gemm(t, up, residuals=(m, a, x), layout="rm")
-                sv.update(m=m)
-            else:
-                x = self._fgemm((li, "fc_out"), h, ly.fc_out, residuals=(a, x))
-            return x, sv
+    def _block_forward(self, li, x, dims):
+        """One GPT-J block forward on x [B*S, d], dims = (B, S): (x', sv = what its backward needs, sv["kind"] = its shape, decided
+        here).  Called by _lm_forward and -- under per-block recompute -- once more from _lm_backward, on the saved block input."""
+        eng, dev = self.module.lm.engine, self.device
+        ly, (B, S), H, d = eng.layers[li], dims, eng.H, eng.d
+        M, kind = B * S, self._train_block_kind(li)
+        sv = {"x": x, "kind": kind}
+        ln = ops.layernorm(x, ly.ln_g, ly.ln_b, eng.eps)
+        lnq = ops.quantize_rows_fp8(ln) if self.fp8 else None     # shared by qkv and fc_in
+        qkv = self._fgemm((li, "qkv"), ln, ly.qkv, lnq)
+        # No split pass, no transposed copies: the rotary runs in place on the q / k sections of the GEMM output and the attention
+        # kernels (csrc/attention_tr.hip), forward and backward, take q, k, v as strided rows of that buffer.  "fp8": the same pass
+        # also writes the e4m3 copies of q, k, v^T the fp8 forward reads.
+        if kind.attention == "fp8":
+            a8 = ops.rotary_split_fp8(qkv, B, S, H, eng.rot, eng.sin_t, eng.cos_t, inplace=True)
+        else:
+            ops.rotary_qk_inplace(qkv, B, S, H, eng.rot, eng.sin_t, eng.cos_t)
+        rows = ops.AttnRows.of_qkv(qkv, B, S, H)
+        out_up = self._cat_out_up(li) if kind.mlp == "cat" else None
+        ctx_t = torch.empty(M, d if out_up is None else out_up.K, dtype=BF16, device=dev)   # "cat": [ctx | t], one saved buffer, one GEMM operand
+        ctx = ctx_t[:, :d]
+        lse = torch.empty(B, H, S, dtype=F32, device=dev)
+        # fp8_mx: the fp8 attention's epilogue also emits the OCP MX e4m3 copy of ctx: out_proj runs on it, no quantisation pass
+        ctx_mx = ops.mx_empty(M, H * 256, dev) if kind.attention == "fp8" and self.fp8_mx else None
+        if kind.attention == "fp8":
+            ops.attn_prefill_fp8(a8, ctx, lse=lse, mx_out=ctx_mx)
+        else:
+            ops.attn_fwd_rows(rows, ctx, lse=lse)
+        sv.update(rows=rows, ctx=ctx, lse=lse)
+        a = None if out_up is not None else self._fgemm((li, "out"), ctx if ctx_mx is None else ("mx", *ctx_mx), ly.out)
+        if kind.attn != "none":
+            a = getattr(self, "_attn_fwd_" + kind.attn)(li, sv, ln, a)
+        hpre = torch.empty(M, ly.fc_in.N, dtype=BF16, device=dev)
+        h = self._fgemm((li, "fc_in"), ln, ly.fc_in, lnq, act=ops.MG_ACT_GELU_NEW, out2=hpre, mx_out=self.fp8 and self.fp8_mx)
+        sv["hpre"] = hpre
+        if self.lm_trainable:
+            sv["h"] = h                    # operand of the fc_out weight gradient
+        return getattr(self, "_mlp_fwd_" + kind.mlp)(li, sv, ln, h, a, x, (ctx_t, out_up)), sv
 
-        # Per-block recompute (reference language_model.py:23-37: gradient checkpointing is ON by default there): only each
-        # block's input is kept, its activations are rebuilt in the backward pass right before they are used (deterministic
-        # kernels, no dropout inside the blocks: the same bits).  Off by default -- 288 GB hold the 176 GB of a B = 16 step,
-        # and every reported number is taken without it (SURVEY H6); MAGMA_TRAIN_RECOMPUTE=1 / engine.recompute for larger
-        # per-GPU batches or 384-pixel prefixes.
+    # The forward of each attention-side kind: (li, sv, ln, a = out_proj's output) -> a + the adapter's output
+    def _attn_fwd_parallel(self, li, sv, ln, a):
+        """parallel / scaled_parallel (reference adapters.py:42-92): the adapter reads the attention INPUT (ln_1 output)."""
+        mod = self._layer(li)[1].attn
+        dn, up, sc = self._par_adapter_ops(mod)
+        ta = self._adapter_down(mod, ln, dn, sv, "ta")
+        return ops.gemm(ta, up, scale=sc, residuals=(a,), layout="rm")
+
+    def _attn_fwd_serial(self, li, sv, ln, a):
+        mod = self._layer(li)[1].attn
+        dn, up = self._adapter_ops(mod)
+        ta = self._adapter_down(mod, a, dn, sv, "ta")
+        sv["a"] = a
+        return ops.gemm(ta, up, residuals=(a,), layout="rm")
+
+    # The forward of each MLP-side kind: (li, sv, ln, h = gelu(fc_in), a, x, cat = (the [ctx | t] buffer, [W_out | W_up])) -> x'
+    def _mlp_fwd_none(self, li, sv, ln, h, a, x, cat):
+        return self._fgemm((li, "fc_out"), h, self._layer(li)[0].fc_out, residuals=(a, x))
+
+    def _mlp_fwd_cat(self, li, sv, ln, h, a, x, cat):
+        """x' = [ctx | t] [W_out | W_up]^T + b_up + m + x   (reference adapters.py:38-39 on the MLP output + GPT-J's residual sum)"""
+        ly, blk = self._layer(li)
+        ctx_t, out_up = cat
+        dn, _ = self._adapter_ops(blk.mlp[1])
+        sv["m"] = m = self._fgemm((li, "fc_out"), h, ly.fc_out)
+        sv["t"] = ops.gemm(m, dn, act=ops.MG_ACT_RELU, layout="rm", out=ctx_t[:, dn.K:])
+        return ops.gemm(ctx_t, out_up, residuals=(m, x), layout="rm")
+
+    def _mlp_fwd_parallel(self, li, sv, ln, h, a, x, cat):
+        ly, blk = self._layer(li)
+        dn, up, sc = self._par_adapter_ops(blk.mlp)
+        m = self._fgemm((li, "fc_out"), h, ly.fc_out)
+        t = self._adapter_down(blk.mlp, ln, dn, sv, "t")
+        return ops.gemm(t, up, scale=sc, residuals=(m, a, x), layout="rm")
+
+    def _mlp_fwd_fp8(self, li, sv, ln, h, a, x, cat):
+        """config[4]: the adapter GEMMs on the fp8 MFMA, operands from the producing epilogues (see __init__)."""
+        ly, blk = self._layer(li)
+        p8, M, dev = self._ad8(li, blk.mlp[1]), x.shape[0], self.device
+        m_mx = ops.mx_empty(M, ly.fc_out.N, dev)
+        sv["m"] = m = self._fgemm((li, "fc_out"), h, ly.fc_out, mx_out=m_mx)
+        t_mx = ops.mx_empty(M, p8["dn"].N, dev)
+        sv["t"] = ops.gemm_mx_fp8(m_mx[0], m_mx[1], p8["dn"], act=ops.MG_ACT_RELU, mx_out=t_mx, tile=256)
+        return ops.gemm_mx_fp8(t_mx[0], t_mx[1], p8["up"], residuals=(m, a, x))
+
+    def _mlp_fwd_serial(self, li, sv, ln, h, a, x, cat):
+        ly, blk = self._layer(li)
+        dn, up = self._adapter_ops(blk.mlp[1])
+        sv["m"] = m = self._fgemm((li, "fc_out"), h, ly.fc_out)
+        t = self._adapter_down(blk.mlp[1], m, dn, sv, "t")
+        return ops.gemm(t, up, residuals=(m, a, x), layout="rm")
+
+    def _lm_forward(self, emb, labels, tape):
+        eng, dev = self.module.lm.engine, self.device
+        B, S, d = emb.shape
+        x = emb.view(B * S, d)
+        # Per-block recompute (self.recompute / MAGMA_TRAIN_RECOMPUTE=1, off by default; DESIGN.md section 6): only each block's input is
+        # kept, its activations are rebuilt in the backward pass right before they are used (deterministic kernels: the same bits).
         saved = []
-        for li, (ly, blk) in enumerate(zip(eng.layers, self.module.lm.transformer.h)):
-            xin = x
-            x, sv = block(li, ly, blk, x)
-            saved.append({"x": xin} if self.recompute else sv)
-        tape["block_fn"] = block if self.recompute else None
+        for li in range(len(eng.layers)):
+            x, sv = self._block_forward(li, x, (B, S))
+            saved.append({"x": sv["x"]} if self.recompute else sv)
+        tape["block_fn"] = self.recompute      # flag: _lm_backward calls _block_forward again on each saved block input
         tape["layers"] = saved
         # ---- head + loss on rows that carry a target ----
         rows, tgt = tape["rows"], tape["tgt"]             # built on the host (target_index): no device sync here
@@ -752,7 +761,7 @@ class MagmaEngine:
         ops.gemm(xl, eng.head, out=logits)
         _, head_t = self._lm_packs()
         loss, dlogits = ops.cross_entropy_fwd_bwd(logits[:, : eng.V], tgt, head_t.K)
-        tape.update(xr=xr, dlogits=dlogits, M=M)
+        tape.update(xr=xr, dlogits=dlogits, M=B * S)
         tape["target_logits"] = logits[:, : eng.V]         # fp32, rows that carry a target (reference magma.py:270-276 .logits, those rows)
         tape["x_final"] = x                                # [B*S, d]: .logits over every position is computed from it on first access
         if self.lm_trainable:
@@ -763,8 +772,6 @@ class MagmaEngine:
     def _backward_impl(self, loss=None):
         tape = self._tape
         assert tape is not None, "backward() without a training forward"
-        scale_note = 1.0 / self.gas     # applied at step() through grad_scale (DeepSpeed divides the loss by gas)
-        del scale_note
         d_emb = self._lm_backward(tape)
         B, S, P = tape["B"], tape["S"], tape["P"]
         if isinstance(d_emb, tuple):      # the bottom block formed the gradient of the prefix rows only
@@ -826,13 +833,8 @@ class MagmaEngine:
         from .adapters import activation_codes
         dn, up = wrapper.down, wrapper.up
         _, gmode, needs_pre = activation_codes(wrapper.act)
-        sp = wrapper.adapter_scale
-        scaled = torch.is_tensor(sp)
-        N = up.weight.shape[0]
-        sc = None
-        if scaled:
-            sval = self.master_of(sp) if self.is_trainable(sp) else sp.detach().float()
-            sc = sval.reshape(1).to(F32).expand(N).contiguous()
+        sp, sc, N = wrapper.adapter_scale, self._par_scale(wrapper), up.weight.shape[0]
+        scaled = sc is not None
         gb = torch.zeros(N, dtype=F32, device=g.device)
         ops.colsum(g, gb)                                                  # unscaled d b_up
         gw = ops.gemm(_t(g).rm, _t(t), out_dtype=F32, layout="rm", use_bias=False)     # unscaled d W_up [N, K]
@@ -855,14 +857,9 @@ class MagmaEngine:
         return dt, _t(dn.weight.data)
 
     def _lm_backward(self, tape):
-        eng = self.module.lm.engine
-        dev = self.device
-        packs, head_t = self._lm_packs()
-        B, S, M = tape["B"], tape["S"], tape["M"]
-        H, d = eng.H, eng.d
+        eng, dev, lm = self.module.lm.engine, self.device, self.module.lm
         # loss head: dlogits -> dxl -> ln_f backward -> scatter to the target rows
-        lm = self.module.lm
-        dxl = ops.gemm(tape["dlogits"], head_t)
+        dxl = ops.gemm(tape["dlogits"], self._lm_packs()[1])
         if self.lm_trainable:
             V = lm.lm_head.weight.shape[0]
             dlT = ops.transpose(tape["dlogits"])                       # [Vp, R]
@@ -874,105 +871,108 @@ class MagmaEngine:
             dxr = self._ln_bwd(lm.transformer.ln_f, dxl, tape["xr"])
         else:
             dxr = ops.layernorm_bwd(dxl, tape["xr"], eng.lnf_g, eng.eps)
-        g = torch.zeros(M, d, dtype=BF16, device=dev)
+        g = torch.zeros(tape["M"], eng.d, dtype=BF16, device=dev)
         g.index_copy_(0, tape["rows"], dxr)
         for li in range(len(eng.layers) - 1, -1, -1):
-            ly, blk, pk, sv = eng.layers[li], self.module.lm.transformer.h[li], packs[li], tape["layers"][li]
-            if tape.get("block_fn") is not None:       # per-block recompute: rebuild this block's activations from its input
-                _, sv = tape["block_fn"](li, ly, blk, sv["x"])
-                tape["layers"][li] = None
-            # The BOTTOM block of a frozen LM: below it only the image prefix (positions < P of every sequence) receives a gradient
-            # -- the word embeddings are frozen (reference magma.py:98-100 trains adapters + image prefix) --, so the three dgrads
-            # into ln_1 (fc_out^T, fc_in^T, qkv^T), dQ and the LayerNorm backward are needed for B*P of the B*S rows only, and dK / dV
-            # for the first P keys.  Every parameter gradient is what it was (the adapter branch runs on all rows).
-            bottom = (_BOTTOM_PREFIX_ONLY and li == 0 and not self.lm_trainable and 0 < tape["P"] < S and sv.get("rows") is not None
-                      and ly.mlp_par is None and ly.attn_par is None)
-            P = tape["P"]
-            take = (lambda t_: t_.view(B, S, -1)[:, :P].reshape(B * P, -1)) if bottom else (lambda t_: t_)
-            if li == 0:
-                self.bottom_prefix_rows = P if bottom else 0      # (bench.py: executed-FLOP accounting)
-            # ---- MLP branch ----
-            par = ly.mlp_par is not None or ly.attn_par is not None
-            ln = ops.layernorm(sv["x"], ly.ln_g, ly.ln_b, eng.eps) if par else None   # the parallel adapters' input, recomputed
-            extra = []                                                                 # dL/d ln through the parallel adapters
-            gq = None                                                                  # row-quantised g, shared by its consumers
-            dm_taken = False                                                           # bottom block: dm already holds the prefix rows only
-            if ly.mlp_adapter is not None and ly.mlp_par is not None:
-                dt, dn_t = self._par_adapter_backward(blk.mlp, g, ln, sv["t"], sv.get("t_pre"))
-                extra.append(self._adapter_dx(blk.mlp, dt, dn_t, ln))
-                dm = g
-            elif self._ad8_ok(ly, blk) and not bottom:
-                mod, p8 = blk.mlp[1], self._ad8(li, blk.mlp[1])
-                gq = ops.quantize_rows_fp8(g)          # also the operand of the out_proj dgrad below (no attention adapter: da = g)
-                self._acc_wgrad(mod.up.weight, RawWeight(ops.transpose_colsum(g, self.grad_of(mod.up.bias))), _t(sv["t"]))
-                dt_mx = ops.mx_empty(M, p8["up_t"].N, dev)
-                dt = ops.gemm_fp8(gq[0], gq[1], p8["up_t"], aux=sv["t"], aux_mode=ops.MG_AUX_RELU_GATE, use_bias=False,
-                                  mx_out=dt_mx, tile=256)
-                self._acc_wgrad(mod.down.weight, RawWeight(ops.transpose_colsum(dt, self.grad_of(mod.down.bias))), _t(sv["m"]))
-                dm_mx = ops.mx_empty(M, p8["dn_t"].N, dev)
-                ops.gemm_mx_fp8(dt_mx[0], dt_mx[1], p8["dn_t"], residuals=(g,), use_bias=False, mx_out=dm_mx, no_out=True, tile=256)
-                dm = ("mx", *dm_mx)                    # dL/dm exists only as the MX operand of the fc_out dgrad
-            elif ly.mlp_adapter is not None:
-                dt, dn_t = self._adapter_backward(blk.mlp[1], g, sv["m"], sv["t"], sv.get("t_pre"))
-                if bottom and blk.mlp[1].ln is None:
-                    # dL/dm feeds nothing but the (prefix-rows-only) fc_out dgrad: the same rows suffice here
-                    dm = self._adapter_dx(blk.mlp[1], take(dt), dn_t, None, res=take(g))
-                    dm_taken = True
-                else:
-                    dm = self._adapter_dx(blk.mlp[1], dt, dn_t, sv["m"], res=g)
-            else:
-                dm = g
-            dhpre = self._fgemm((li, "fc_out_t"), dm if dm_taken else take(dm), pk["fc_out_t"], aux=take(sv["hpre"]), aux_mode=ops.MG_AUX_GELU_GRAD,
-                                mx_out=self.fp8 and self.fp8_mx and not bottom)
-            dln_mlp = self._fgemm((li, "fc_in_t"), dhpre, pk["fc_in_t"])
-            if self.lm_trainable:
-                a_mod, mlp_mod = ly._src
-                if ln is None:
-                    ln = ops.layernorm(sv["x"], ly.ln_g, ly.ln_b, eng.eps)
-                ops.colsum(dm, self.grad_of(mlp_mod.c_proj.bias))
-                self._acc_wgrad(mlp_mod.c_proj.weight, _t(dm), _t(sv["h"]))
-                ops.colsum(dhpre, self.grad_of(mlp_mod.c_fc.bias))
-                self._acc_wgrad(mlp_mod.c_fc.weight, _t(dhpre), _t(ln))
-            del dhpre, dm
-            # ---- attention branch ----
-            if ly.attn_adapter is not None and ly.attn_par is not None:
-                dta, dn_t = self._par_adapter_backward(blk.attn, g, ln, sv["ta"], sv.get("ta_pre"))
-                extra.append(self._adapter_dx(blk.attn, dta, dn_t, ln))
-                da = g
-            elif ly.attn_adapter is not None:
-                dta, dn_t = self._adapter_backward(blk.attn, g, sv["a"], sv["ta"], sv.get("ta_pre"))
-                da = self._adapter_dx(blk.attn, dta, dn_t, sv["a"], res=g)
-            else:
-                da = g
-            dctx = self._fgemm((li, "out_t"), da, pk["out_t"], xq=gq if da is g else None)
-            if sv["rows"] is None:      # MAGMA_ATTN_TR=0 (A/B only)
-                q, k, v, qt, kt = sv["old"]
-                dqkv = ops.attn_bwd_merged(q, k, v, qt, kt, dctx, sv["ctx"], sv["lse"], B, H, S, eng.rot, eng.sin_t, eng.cos_t)
-            elif bottom:
-                # dQ of the first ceil(P / 128) query blocks, dK / dV of the first key blocks (mg_attn_bwd_rows_bf16 first_rows)
-                dqkv = take(ops.attn_bwd_rows(sv["rows"], dctx, sv["ctx"], sv["lse"], merged_rot=(eng.rot, eng.sin_t, eng.cos_t), first_rows=P))
-            elif self.fp8 and self.fp8_mx and (3 * H * 256) % 256 == 0:
-                # fp8_mx: the gradient of the fused qkv projection leaves the attention backward's epilogues ONLY as the OCP MX e4m3
-                # operand of the qkv dgrad (the LM is frozen in fp8 mode: nothing else reads dqkv) -- no bf16 dqkv, no quantisation pass
-                dq_mx = ops.mx_empty(M, 3 * H * 256, dev)
-                ops.attn_bwd_rows(sv["rows"], dctx, sv["ctx"], sv["lse"], merged_rot=(eng.rot, eng.sin_t, eng.cos_t), mx_out=dq_mx, no_out=True)
-                dqkv = ("mx", *dq_mx)
-            else:
-                dqkv = ops.attn_bwd_rows(sv["rows"], dctx, sv["ctx"], sv["lse"], merged_rot=(eng.rot, eng.sin_t, eng.cos_t))
-            dln = self._fgemm((li, "qkv_t"), dqkv, pk["qkv_t"], residuals=(dln_mlp, *extra))
-            if self.lm_trainable:
-                self._acc_wgrad(a_mod.out_proj.weight, _t(da), _t(sv["ctx"]))
-                dqkvT, lnT, dd = ops.transpose(dqkv), _t(ln), d
-                for i3, prj in enumerate((a_mod.q_proj, a_mod.k_proj, a_mod.v_proj)):
-                    self._acc_wgrad(prj.weight, RawWeight(dqkvT[i3 * dd:(i3 + 1) * dd]), lnT)
-                g = self._ln_bwd(blk.ln_1, dln, sv["x"], res=g)
-            else:
-                g = ops.layernorm_bwd(dln, take(sv["x"]), ly.ln_g, eng.eps, res=take(g))
-                if bottom:
-                    g = ("prefix", g)     # [B * P, d]: the gradient of the image prefix; the other rows were never formed
+            sv = tape["layers"][li]
+            if tape["block_fn"]:       # per-block recompute: rebuild this block's activations (and its kind) from its input
+                _, sv = self._block_forward(li, sv["x"], (tape["B"], tape["S"]))
+            g = self._block_backward(li, g, sv, tape)
             tape["layers"][li] = None     # free this layer's activations
-            self._reduce_params_async([p for p in blk.parameters() if p.requires_grad])
+            self._reduce_params_async([p for p in self.module.lm.transformer.h[li].parameters() if p.requires_grad])
         return g
+
+    def _block_backward(self, li, g, sv, tape):
+        """g = dL/d(block output) -> dL/d(block input).  The block's shape is sv["kind"], what the forward that wrote sv decided."""
+        eng, (ly, blk) = self.module.lm.engine, self._layer(li)
+        pk, kind = self._lm_packs()[0][li], sv["kind"]
+        B, S, P, M = tape["B"], tape["S"], tape["P"], tape["M"]
+        par = "parallel" in (kind.mlp, kind.attn)
+        # The BOTTOM block of a frozen LM: below it only the image prefix (positions < P of every sequence) receives a gradient
+        # (the word embeddings are frozen, reference magma.py:98-100), so the three dgrads into ln_1 (fc_out^T, fc_in^T, qkv^T), dQ
+        # and the LayerNorm backward are needed for B*P of the B*S rows only, and dK / dV for the first P keys; every parameter
+        # gradient is what it was (the adapter branch runs on all rows).  A backward decision -- P and S are the step's -- and the
+        # alternative of the MX-only gradients (mx): those are written for whole rows of every sequence.
+        bottom = _BOTTOM_PREFIX_ONLY and li == 0 and not self.lm_trainable and 0 < P < S and not par
+        mx = self.fp8 and self.fp8_mx and not bottom
+        take = (lambda t_: t_.view(B, S, -1)[:, :P].reshape(B * P, -1)) if bottom else (lambda t_: t_)
+        if li == 0:
+            self.bottom_prefix_rows = P if bottom else 0      # (bench.py: executed-FLOP accounting)
+        ln = ops.layernorm(sv["x"], ly.ln_g, ly.ln_b, eng.eps) if par else None   # the parallel adapters' input, recomputed
+        # ---- MLP branch: dm on the rows the dgrads need, dL/d ln through a parallel adapter, the row-quantised g if one was made
+        mlp_bwd = "serial" if kind.mlp == "cat" or (kind.mlp == "fp8" and bottom) else kind.mlp
+        dm, extra, gq = (take(g), [], None) if mlp_bwd == "none" else getattr(self, "_mlp_bwd_" + mlp_bwd)(li, g, sv, ln, take if bottom else None)
+        dhpre = self._fgemm((li, "fc_out_t"), dm, pk["fc_out_t"], aux=take(sv["hpre"]), aux_mode=ops.MG_AUX_GELU_GRAD, mx_out=mx)
+        dln_mlp = self._fgemm((li, "fc_in_t"), dhpre, pk["fc_in_t"])
+        if self.lm_trainable:
+            a_mod, mlp_mod = ly._src
+            if ln is None:
+                ln = ops.layernorm(sv["x"], ly.ln_g, ly.ln_b, eng.eps)
+            ops.colsum(dm, self.grad_of(mlp_mod.c_proj.bias))
+            self._acc_wgrad(mlp_mod.c_proj.weight, _t(dm), _t(sv["h"]))
+            ops.colsum(dhpre, self.grad_of(mlp_mod.c_fc.bias))
+            self._acc_wgrad(mlp_mod.c_fc.weight, _t(dhpre), _t(ln))
+        del dhpre, dm
+        # ---- attention branch ----
+        da, extra_a = (g, []) if kind.attn == "none" else getattr(self, "_attn_bwd_" + kind.attn)(li, g, sv, ln)
+        dctx = self._fgemm((li, "out_t"), da, pk["out_t"], xq=gq if da is g else None)
+        rot = (eng.rot, eng.sin_t, eng.cos_t)
+        if mx:
+            # fp8_mx: dqkv leaves the attention backward's epilogues ONLY as the OCP MX e4m3 operand of the qkv dgrad (the LM is
+            # frozen in fp8 mode: nothing else reads it) -- no bf16 dqkv, no quantisation pass
+            dq_mx = ops.mx_empty(M, 3 * eng.H * 256, self.device)
+            ops.attn_bwd_rows(sv["rows"], dctx, sv["ctx"], sv["lse"], merged_rot=rot, mx_out=dq_mx, no_out=True)
+            dqkv = ("mx", *dq_mx)
+        else:
+            # bottom: dQ of the first ceil(P / 128) query blocks, dK / dV of the first key blocks (mg_attn_bwd_rows_bf16 first_rows)
+            dqkv = take(ops.attn_bwd_rows(sv["rows"], dctx, sv["ctx"], sv["lse"], merged_rot=rot, first_rows=P if bottom else 0))
+        dln = self._fgemm((li, "qkv_t"), dqkv, pk["qkv_t"], residuals=(dln_mlp, *extra, *extra_a))
+        if self.lm_trainable:
+            self._acc_wgrad(a_mod.out_proj.weight, _t(da), _t(sv["ctx"]))
+            dqkvT, lnT, dd = ops.transpose(dqkv), _t(ln), eng.d
+            for i3, prj in enumerate((a_mod.q_proj, a_mod.k_proj, a_mod.v_proj)):
+                self._acc_wgrad(prj.weight, RawWeight(dqkvT[i3 * dd:(i3 + 1) * dd]), lnT)
+            return self._ln_bwd(blk.ln_1, dln, sv["x"], res=g)
+        g = ops.layernorm_bwd(dln, take(sv["x"]), ly.ln_g, eng.eps, res=take(g))
+        return ("prefix", g) if bottom else g     # bottom: [B * P, d], the image prefix's gradient; the other rows were never formed
+
+    # The backward of each MLP-side kind: (li, g, sv, ln, take = the bottom block's row selection | None) -> (dm on those rows, [dL/d ln], gq)
+    def _mlp_bwd_parallel(self, li, g, sv, ln, take):
+        mod = self._layer(li)[1].mlp
+        dt, dn_t = self._par_adapter_backward(mod, g, ln, sv["t"], sv.get("t_pre"))
+        return g, [self._adapter_dx(mod, dt, dn_t, ln)], None
+
+    def _mlp_bwd_fp8(self, li, g, sv, ln, take):
+        mod = self._layer(li)[1].mlp[1]
+        p8, M = self._ad8(li, mod), g.shape[0]
+        gq = ops.quantize_rows_fp8(g)          # also the operand of the out_proj dgrad (no attention adapter: da = g)
+        self._acc_wgrad(mod.up.weight, RawWeight(ops.transpose_colsum(g, self.grad_of(mod.up.bias))), _t(sv["t"]))
+        dt_mx = ops.mx_empty(M, p8["up_t"].N, self.device)
+        dt = ops.gemm_fp8(gq[0], gq[1], p8["up_t"], aux=sv["t"], aux_mode=ops.MG_AUX_RELU_GATE, use_bias=False, mx_out=dt_mx, tile=256)
+        self._acc_wgrad(mod.down.weight, RawWeight(ops.transpose_colsum(dt, self.grad_of(mod.down.bias))), _t(sv["m"]))
+        dm_mx = ops.mx_empty(M, p8["dn_t"].N, self.device)
+        ops.gemm_mx_fp8(dt_mx[0], dt_mx[1], p8["dn_t"], residuals=(g,), use_bias=False, mx_out=dm_mx, no_out=True, tile=256)
+        return ("mx", *dm_mx), [], gq          # dL/dm exists only as the MX operand of the fc_out dgrad
+
+    def _mlp_bwd_serial(self, li, g, sv, ln, take):     # also of "cat" (sv["t"]: a view into [ctx | t]) and of "fp8" in the bottom block
+        mod = self._layer(li)[1].mlp[1]
+        dt, dn_t = self._adapter_backward(mod, g, sv["m"], sv["t"], sv.get("t_pre"))
+        if take is not None and mod.ln is None:
+            # dL/dm feeds nothing but the (prefix-rows-only) fc_out dgrad: the same rows suffice here
+            return self._adapter_dx(mod, take(dt), dn_t, None, res=take(g)), [], None
+        dm = self._adapter_dx(mod, dt, dn_t, sv["m"], res=g)
+        return (dm if take is None else take(dm)), [], None
+
+    # The backward of each attention-side kind: (li, g, sv, ln) -> (da = dL/d(out_proj output), [dL/d ln])
+    def _attn_bwd_parallel(self, li, g, sv, ln):
+        mod = self._layer(li)[1].attn
+        dta, dn_t = self._par_adapter_backward(mod, g, ln, sv["ta"], sv.get("ta_pre"))
+        return g, [self._adapter_dx(mod, dta, dn_t, ln)]
+
+    def _attn_bwd_serial(self, li, g, sv, ln):
+        mod = self._layer(li)[1].attn
+        dta, dn_t = self._adapter_backward(mod, g, sv["a"], sv["ta"], sv.get("ta_pre"))
+        return self._adapter_dx(mod, dta, dn_t, sv["a"], res=g), []
 
     # ---- image prefix + CLIP trunk -------------------------------------------------
     def _prefix_forward(self, images, dropout_mask):

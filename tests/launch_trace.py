@@ -15,7 +15,11 @@ Exchanging two buffers, two weights or two launches changes the record; values n
 alive until the trace ends, so that the allocator cannot hand a freed address to an unrelated tensor.
 
 Run as a script it prints the traces of ``CASES`` as JSON: that output, made on the commit before a change to the token step or
-the prefill, is the golden file; tests/test_launch_trace_gpu.py compares the same cases against it."""
+the prefill, is the golden file; tests/test_launch_trace_gpu.py compares the same cases against it.
+
+The second half records a ``MagmaEngine``: what ``_lm_forward`` and ``_lm_backward`` launch in one training step (TrainTrace,
+``TRAIN_CASES``, ``run_train_case``), with the bits of the loss and a digest of every gradient.  ``python tests/launch_trace.py train``
+prints tests/golden/train_launch_trace.json, which tests/test_train_launch_trace_gpu.py compares against."""
 import inspect
 import json
 import os
@@ -55,6 +59,9 @@ class Trace:
         self._written = []        # (start, end, name, row stride of the written tensor), in write order
         self._objects = {}        # id(returned non-tensor object) -> name
         self._keep = []
+        self.on = True
+        self.writes = WRITES
+        self.rename = {}          # argument name -> key in the record
 
     # ---- names -------------------------------------------------------------------------------------------------------------
     def _walk(self, name, o, tensors, weights, depth=0):
@@ -187,11 +194,11 @@ class Trace:
                 rec[k] = {"x": self._describe(v[0], names), "w": self._describe(v[1], names), "out": self._describe(v[2], names),
                           **{kk: self._describe(vv, names) for kk, vv in v[3].items() if kk not in ("x", "w", "out")}}
             else:
-                rec[k] = self._describe(v, names)
+                rec[self.rename.get(k, k)] = self._describe(v, names)
         self.records.append(rec)
         ret = fn(*args, **kwargs)
         written = set()
-        for path in WRITES.get(name, ()):
+        for path in self.writes.get(name, ()):
             t = self._at(bound, path)
             if torch.is_tensor(t):
                 self._written.append((t.data_ptr(), t.data_ptr() + _span(t), f"@{idx}.{path}", t.stride(0) if t.ndim >= 2 else 0))
@@ -209,14 +216,15 @@ class Trace:
         return ret
 
 
-def record(eng, fn, cache=None, inputs=None):
-    """Run fn() with the engine's ops recorded.  Returns (records, fn's result or the exception it raised)."""
+def record(eng, fn, cache=None, inputs=None, trace=None, op_names=OPS):
+    """Run fn() with the engine's ops recorded.  Returns (records, fn's result or the exception it raised).  ``trace``: a Trace
+    to record into instead of a new one (a TrainTrace records only while its ``on`` is set); ``op_names``: the ops replaced."""
     from magma_amd import ops
-    tr = Trace(eng, cache, inputs)
-    saved = {n: getattr(ops, n) for n in OPS}
+    tr = Trace(eng, cache, inputs) if trace is None else trace
+    saved = {n: getattr(ops, n) for n in op_names}
 
     def wrap(n, f):
-        return lambda *a, **k: tr.call(n, f, a, k)
+        return lambda *a, **k: tr.call(n, f, a, k) if tr.on else f(*a, **k)
     for n, f in saved.items():
         setattr(ops, n, wrap(n, f))
     try:
@@ -299,8 +307,192 @@ def run_case(dev, case):
     return out, res
 
 
+# ---- the training step: what MagmaEngine._lm_forward / _lm_backward launch -----------------------------------------------------------
+TRAIN_OPS = OPS + ("rotary_qk_inplace", "attn_fwd_rows", "attn_bwd_rows", "transpose", "transpose_colsum", "colsum", "layernorm_bwd",
+                   "cross_entropy_fwd_bwd", "gelu_erf_grad_mul", "scale_rows_acc", "mx_empty")
+TRAIN_WRITES = {**WRITES, "rotary_qk_inplace": ["qkv"], "rotary_split_fp8": ["qkv"], "attn_fwd_rows": ["out", "lse"],
+                "attn_prefill_fp8": ["out", "lse", "mx_out.0", "mx_out.1"], "attn_bwd_rows": ["mx_out.0", "mx_out.1"],
+                "transpose": ["out"], "transpose_colsum": ["colsum_out"], "colsum": ["out"], "gelu_erf_grad_mul": ["out"],
+                "scale_rows_acc": ["dst"], "gemm_fp8": ["out", "out2", "mx_out.0", "mx_out.1"],
+                "gemm_mx_fp8": ["out", "out2", "mx_out.0", "mx_out.1"]}
+
+
+class TrainTrace(Trace):
+    """Trace of a MagmaEngine: records while ``on`` (set inside _lm_forward / _lm_backward, so the image prefix and the trunk
+    stay out).  Names: a parameter by its named_parameters() name; the flat optimizer buffers ``g<i>.master`` / ``.grad`` /
+    ``.model`` with an element range; the engine's operands (``_out_up[li]``, ``_lm_train_packs``, ``_fp8_packs[key]``,
+    ``_ad8_cache[li]``); the LMEngine's layers as the decode traces name them; a RawWeight built for one call by the tensor it
+    wraps; an AttnRows by the buffer its rows lie in; everything else by the record that wrote it."""
+
+    def __init__(self, teng, inputs=None):
+        super().__init__(teng.module.lm.engine, None, inputs)
+        self.teng, self.on, self.writes = teng, False, TRAIN_WRITES
+        self.rename = {"op": "operands"}       # attn_prefill_fp8(op=...) must not take the record's "op"
+        self._anon = 0
+
+    def _names(self):
+        tensors, weights = [], []
+        te = self.teng
+        for n, p in te.module.named_parameters():
+            tensors.append((n, p.data))
+        for gi, g in enumerate(te.groups):
+            for k in ("master", "grad", "model"):
+                tensors.append((f"g{gi}.{k}", getattr(g, k)))
+        for k in ("_out_up", "_lm_train_packs", "_fp8_packs", "_ad8_cache"):
+            self._walk(k, getattr(te, k), tensors, weights)
+        for k, v in sorted(vars(self.eng).items()):
+            if k == "layers":
+                for i, ly in enumerate(v):
+                    self._walk(f"L{i}", ly, tensors, weights)
+            elif torch.is_tensor(v) or _is_weight(v):
+                self._walk(k, v, tensors, weights)
+        tensors += list(self.inputs.items())
+        return tensors, weights
+
+    def _describe(self, v, names):
+        from magma_amd import ops
+        if torch.is_tensor(v) and self._tensor(v, names[0]).startswith("?"):
+            # made by torch (an index_select, a zeros, an empty handed over as ``out``): numbered by first appearance
+            self._written.append((v.data_ptr(), v.data_ptr() + _span(v), f"?{self._anon}", v.stride(0) if v.ndim >= 2 else 0))
+            self._anon += 1
+        if isinstance(v, ops.AttnRows):
+            return {"rows": [self._describe(t, names) for t in v.keep], "k": (v.k - v.q) // 2, "v": (v.v - v.q) // 2,
+                    "ld_row": v.ld_row, "stride_b": v.stride_b, "stride_h": v.stride_h, "B": v.B, "H": v.H, "S": v.S}
+        if _is_weight(v) and not any(w is v for _, w in names[1]):
+            st = v.ft if getattr(v, "ft", None) is not None else v.rm
+            bias = getattr(v, "bias", None)
+            return {"w": self._describe(st, names), "cls": type(v).__name__, "N": v.N, "K": v.K, "Kp": v.Kp,
+                    "bias": self._describe(bias, names)}
+        return super()._describe(v, names)
+
+
+def _par(mlp_type, attn_type):
+    return {"mlp": dict(adapter_type=mlp_type, downsample_factor=4), "attention": dict(adapter_type=attn_type, downsample_factor=8)}
+
+
+_FP8 = dict(fp8=True, fp8_attn=True, fp8_mx=True, fp8_adapters=True)
+# id -> (build_reduced_magma arguments, engine switches (the rest at TRAIN_SWITCHES), "allrows" | "lm_trainable" | None)
+TRAIN_CASES = {
+    "v1": (dict(mlp_factor=4), {}, None),
+    "v1_nocat": (dict(mlp_factor=4), dict(cat_up=False), None),
+    "v1_allrows": (dict(mlp_factor=4), {}, "allrows"),
+    "v1_recompute": (dict(mlp_factor=4), dict(recompute=True), None),
+    "v2": (dict(mlp_factor=8, attn_factor=8), {}, None),
+    "attn_only": (dict(mlp_factor=None, attn_factor=8), {}, None),
+    "no_adapters": (dict(mlp_factor=None, adapter_config=None), {}, None),
+    "parallel": (dict(adapter_config=_par("parallel", "scaled_parallel")), {}, None),
+    "ln_gelu_erf": (dict(adapter_config={"mlp": _ad(add_layernorm=True, activation=torch.nn.GELU)}), {}, None),
+    "lm_trainable": (dict(mlp_factor=4), {}, "lm_trainable"),
+    "fp8_row": (dict(mlp_factor=4), dict(fp8=True, fp8_attn=False, fp8_mx=False), None),
+    "fp8_mx": (dict(mlp_factor=4), dict(_FP8, fp8_adapters=False), None),
+    "fp8_all": (dict(mlp_factor=2), _FP8, None),
+}
+TRAIN_SWITCHES = dict(fp8=False, fp8_attn=True, fp8_mx=True, fp8_adapters=True, cat_up=True, recompute=False, truncate=False)
+
+
+def build_train_case(dev, case):
+    """(MagmaEngine in training mode, images, captions, dropout mask) of one case: the reduced two-block model (d = 512,
+    d_ff = 2048), B = 2, 64 x 64 images (P = 4), captions of 23 and 11 tokens, data seeds of tests/test_train_gpu.py."""
+    from magma_amd.testing import build_reduced_magma
+    from magma_amd.train_engine import MagmaEngine
+    build, switches, extra = case
+    torch.manual_seed(7)
+    model = build_reduced_magma(dev, n_layer=2, n_positions=128, **build)
+    if extra == "lm_trainable":
+        model.config.freeze_lm = False
+        for p in model.lm.parameters():
+            p.requires_grad = True
+    model.config.gradient_accumulation_steps = 1
+    eng = MagmaEngine(model)
+    eng.train()
+    for k, v in {**TRAIN_SWITCHES, **switches}.items():
+        setattr(eng, k, v)
+    g = torch.Generator().manual_seed(3)
+    B, S, P = 2, model.seq_len, 4
+    images = torch.randn(B, 3, 64, 64, generator=g)
+    caps = torch.full((B, S), model.eos_token, dtype=torch.int64)
+    caps[0, :23] = torch.randint(0, 1000, (23,), generator=g)
+    caps[1, :11] = torch.randint(0, 1000, (11,), generator=g)
+    mask = (torch.rand(B, P, model.lm.engine.d, generator=g) < 0.9).float() / 0.9
+    return eng, images.to(dev), caps.to(dev), mask.to(dev)
+
+
+def run_train_case(dev, case):
+    """One forward and one backward of a case.  {"records": the launches inside _lm_forward and _lm_backward, "loss": hex of
+    the loss's fp32 bits, "grads": {parameter name: SHA-256 of its fp32 gradient}, "kinds": per block the ``sv["kind"]`` the
+    backward read (as lists; None for an engine without _block_backward)} and the engine."""
+    import hashlib
+    import struct
+    from magma_amd import train_engine
+    eng, images, caps, mask = build_train_case(dev, case)
+    tr = TrainTrace(eng)
+    kinds = {}
+
+    def scoped(fn):
+        def inner(*a, **k):
+            if len(a) == 3:       # _lm_forward(emb, labels, tape)
+                tr.inputs.update(emb=a[0], labels=a[1], rows=a[2]["rows"], tgt=a[2]["tgt"])
+            tr.on = True
+            try:
+                return fn(*a, **k)
+            finally:
+                tr.on = False
+        return inner
+    eng._lm_forward, eng._lm_backward = scoped(eng._lm_forward), scoped(eng._lm_backward)
+    if hasattr(eng, "_block_backward"):
+        inner_bb = eng._block_backward
+
+        def block_backward(li, g, sv, tape):
+            kinds[li] = list(sv["kind"])
+            return inner_bb(li, g, sv, tape)
+        eng._block_backward = block_backward
+    saved_bottom = train_engine._BOTTOM_PREFIX_ONLY
+    train_engine._BOTTOM_PREFIX_ONLY = case[2] != "allrows"
+    try:
+        def step():
+            out = eng(images, caps, dropout_mask=mask)
+            eng.backward(out.loss)
+            return out.loss
+        recs, res = record(eng.module.lm.engine, step, trace=tr, op_names=TRAIN_OPS)
+    finally:
+        train_engine._BOTTOM_PREFIX_ONLY = saved_bottom
+    if isinstance(res, Exception):
+        raise res
+    name_of = {id(p): n for n, p in eng.module.named_parameters()}
+    grads = {name_of[id(p)]: hashlib.sha256(eng.grad_of(p).float().cpu().contiguous().numpy().tobytes()).hexdigest()
+             for grp in eng.groups for p in grp.params}
+    loss = struct.pack(">f", float(res.float())).hex()
+    return {"records": json.loads(json.dumps(recs)), "loss": loss, "grads": grads,
+            "kinds": [kinds[li] for li in sorted(kinds)] or None}, eng
+
+
+def main_train(dev, runs=6):
+    """The golden of tests/test_train_launch_trace_gpu.py, one record per line.  Every case runs ``runs`` times: the records and
+    the loss must repeat.  A gradient digest is kept only for the tensors whose digest repeated in every run of every case;
+    the header's ``unstable`` lists the others (sums formed with fp32 atomics)."""
+    w = sys.stdout.write
+    results, unstable = {}, set()
+    for name, case in TRAIN_CASES.items():
+        outs = [run_train_case(dev, case)[0] for _ in range(runs)]
+        results[name] = first = outs[0]
+        for o in outs[1:]:
+            assert o["records"] == first["records"] and o["loss"] == first["loss"], f"{name}: the trace does not repeat"
+        unstable |= {n for n, h in first["grads"].items() if any(o["grads"][n] != h for o in outs)}
+    w(f'{{"header": {{"runs": {runs}, "unstable": {json.dumps(sorted(unstable))}}},\n "cases": {{\n')
+    for ci, (name, first) in enumerate(results.items()):
+        stable = {n: h for n, h in first["grads"].items() if n not in unstable}
+        w(f' {json.dumps(name)}: {{"loss": {json.dumps(first["loss"])},\n')
+        w(f'  "grads": {json.dumps(stable, sort_keys=True)},\n  "records": [\n')
+        w(",\n".join("   " + json.dumps(r, sort_keys=True, separators=(",", ":")) for r in first["records"]))
+        w("\n  ]}" + ("," if ci + 1 < len(TRAIN_CASES) else "") + "\n")
+    torch.cuda.synchronize()
+    w("}}\n")
+
+
 def main():
     dev = torch.device("cuda:0")
+    if sys.argv[1:] == ["train"]:
+        return main_train(dev)
     traces = {}
     for name, case in CASES.items():
         out, res = run_case(dev, case)
