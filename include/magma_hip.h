@@ -93,8 +93,10 @@ const char* mg_version(void);
  *  12  per-row stopping: added mg_sample_finish_rows; mg_logits_process_f32 gained `eos_more` / `n_eos_more` (before the stream;
  *      NULL / 0 = as before): further eos ids the min_new_tokens rule bans.
  *  13  transformers' sampler: added mg_sample_warp_f32 (nothing moved).
- *  14  added the test probe mg_debug_mx_mfma_acc (nothing moved). */
-#define MG_ABI_VERSION 14
+ *  14  added the test probe mg_debug_mx_mfma_acc (nothing moved).
+ *  15  mg_ce_reduce_f32 gained `V` (after R): a target outside [0, V) is ignored by all three cross-entropy kernels alike; before,
+ *      the reduction counted every target >= 0 although mg_ce_rows_f32 / mg_ce_bwd_bf16 gave such a row loss 0 and gradient 0. */
+#define MG_ABI_VERSION 15
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -557,12 +559,12 @@ int mg_build_labels_i64(const int64_t* captions, int64_t* labels, int32_t B, int
 
 /* K19: shifted cross-entropy of the LM call with labels (reference magma/magma.py:270-274; loss computed inside
  * the fork's GPTNeoForCausalLM.forward in fp32).  For each row r of `logits` [R, V] fp32 with target
- * tgt[r] (int64, -100 = ignore): loss_row[r] = logsumexp - logit[tgt] (0 if
+ * tgt[r] (int64; -100, or any other value outside [0, V) = ignore): loss_row[r] = logsumexp - logit[tgt] (0 if
  * ignored).  The caller passes already-shifted rows.  mg_ce_reduce produces
- * mean over valid rows into out[0] and the valid count into out[1].          */
+ * mean over valid rows (targets in [0, V)) into out[0] and the valid count into out[1].          */
 int mg_ce_rows_f32(const float* logits, int64_t ld, const int64_t* tgt, float* loss_row,
                    int32_t R, int32_t V, void* stream);
-int mg_ce_reduce_f32(const float* loss_row, const int64_t* tgt, int32_t R, float* out,
+int mg_ce_reduce_f32(const float* loss_row, const int64_t* tgt, int32_t R, int32_t V, float* out,
                      void* stream);
 
 /* ===================== training path (backward + optimizer) =====================

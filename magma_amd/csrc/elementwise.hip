@@ -345,14 +345,16 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
   if (tid == 0) loss_row[r] = logf(red[4] + red[5] + red[6] + red[7]) + mx - row[tg];
 }
 
+// mean over the rows that carry a target in [0, V): the same rows ce_rows_kernel / ce_bwd_kernel compute (every other target, -100
+// or out of range, is ignored: loss 0, gradient 0, not counted)
 __global__ __launch_bounds__(256) void ce_reduce_kernel(const float* __restrict__ loss_row,
-                                                        const int64_t* __restrict__ tgt, int R,
+                                                        const int64_t* __restrict__ tgt, int R, int V,
                                                         float* __restrict__ out) {
   __shared__ float rs[4], rc[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float s = 0.f, c = 0.f;
   for (int i = tid; i < R; i += 256)
-    if (tgt[i] >= 0) { s += loss_row[i]; c += 1.f; }
+    if (tgt[i] >= 0 && tgt[i] < V) { s += loss_row[i]; c += 1.f; }
   s = wave_sum(s); c = wave_sum(c);
   if (lane == 0) { rs[wave] = s; rc[wave] = c; }
   __syncthreads();
@@ -612,9 +614,9 @@ extern "C" int mg_ce_rows_f32(const float* logits, int64_t ld, const int64_t* tg
   return MG_OK;
 }
 
-extern "C" int mg_ce_reduce_f32(const float* loss_row, const int64_t* tgt, int32_t R, float* out, void* stream) {
-  if (R <= 0 || !loss_row || !tgt || !out) MG_FAIL(MG_ERR_SHAPE, "mg_ce_reduce_f32: bad arguments");
-  hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss_row, tgt, R, out);
+extern "C" int mg_ce_reduce_f32(const float* loss_row, const int64_t* tgt, int32_t R, int32_t V, float* out, void* stream) {
+  if (R <= 0 || V <= 0 || !loss_row || !tgt || !out) MG_FAIL(MG_ERR_SHAPE, "mg_ce_reduce_f32: bad arguments");
+  hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss_row, tgt, R, V, out);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }

@@ -1287,11 +1287,13 @@ class LMEngine:
         if keep.numel() == 0:
             return LMOutput(loss=torch.full((), float("nan"), device=self.device), logits=None, hidden_states=hs,
                             past_key_values=None)
+        kept = tgt[keep].contiguous()
+        ops.refuse_targets_outside(kept, self.V)            # one more two-element device-to-host copy, next to the sync ``keep`` paid
         xr = x.index_select(0, rows[keep])
         xl = ops.layernorm(xr, self.lnf_g, self.lnf_b, self.eps)
         logits = torch.empty(xl.shape[0], self.Vp, dtype=torch.float32, device=self.device)
         ops.gemm(xl, self.head, out=logits)
-        loss, _ = ops.cross_entropy(logits[:, : self.V], tgt[keep].contiguous())
+        loss, _ = ops.cross_entropy(logits[:, : self.V], kept)
         # reference magma.py:270-276 .logits: (B, S, V) over every position -- on request now, otherwise on first access
         full = (self._full_logits(x, B * S).view(B, S, self.V) if want_logits
                 else LMOutput.lazy(lambda: self._full_logits(x, B * S).view(B, S, self.V)))

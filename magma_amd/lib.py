@@ -19,7 +19,7 @@ MG_A_DENSE, MG_A_CONV3X3 = 0, 1
 MG_AUX_NONE, MG_AUX_RELU_GATE, MG_AUX_GELU_GRAD, MG_AUX_MUL, MG_AUX_QUICK_GELU_GRAD = 0, 1, 2, 3, 4
 
 
-ABI_VERSION = 14     # include/magma_hip.h MG_ABI_VERSION
+ABI_VERSION = 15     # include/magma_hip.h MG_ABI_VERSION
 
 
 class MagmaHipError(RuntimeError):
@@ -146,7 +146,7 @@ SYMBOLS = {
     "mg_relu_mean_rows_bwd_bf16": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "mg_build_labels_i64": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _vp]),
     "mg_ce_rows_f32": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _vp]),
-    "mg_ce_reduce_f32": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
+    "mg_ce_reduce_f32": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
     # training path
     "mg_transpose_bf16": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "mg_transpose_colsum_bf16": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp]),

@@ -26,6 +26,7 @@ from .image_input import ImageInput
 from .image_prefix import ImagePrefix
 from .language_model import GPTJConfig, LMOutput, get_gptj
 from .sampling import generate
+from .tokenizer import HeadSizedTokenizer
 from .transforms import get_transforms
 from .utils import build_labels, get_tokenizer, print_main
 
@@ -96,6 +97,8 @@ class Magma(nn.Module):
             # reduced test vocabularies: keep the special ids in range of BOTH tables (eos = V-2, image = V-1)
             v = min(self.lm.config.vocab_size, self.lm.config.head_rows)
             self.eos_token, self.image_token = v - 2, v - 1
+            # ... and what the tokenizer emits: its padding (GPT-2's eos, 50256) would otherwise be a label outside the head
+            self.tokenizer = HeadSizedTokenizer(self.tokenizer, self.eos_token)
         self.lm.config.pad_token_id = self.tokenizer.eos_token_id
         self.word_embedding = self.lm.transformer.wte
         self.transformer = self.lm.transformer.h
@@ -366,7 +369,7 @@ class Magma(nn.Module):
             raise FileNotFoundError(f"checkpoint {checkpoint_path} does not exist (no network download in this build)")
         model = cls(config=config_path, device=device, **model_kwargs)     # model_kwargs: reduced lm_config / enc (tests)
         from .tokenizer import ByteTokenizer
-        if isinstance(model.tokenizer, ByteTokenizer) and os.environ.get("MAGMA_ALLOW_BYTE_TOKENIZER") != "1":
+        if isinstance(getattr(model.tokenizer, "tok", model.tokenizer), ByteTokenizer) and os.environ.get("MAGMA_ALLOW_BYTE_TOKENIZER") != "1":
             raise RuntimeError("from_checkpoint needs the real GPT-2 tokenizer (set MAGMA_TOKENIZER_DIR to its files): the "
                                "byte-level stand-in would feed the wrong token ids to trained weights.  "
                                "MAGMA_ALLOW_BYTE_TOKENIZER=1 overrides (synthetic checkpoints / tests).")

@@ -445,7 +445,11 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: flo
 
 
 def embedding(ids: torch.Tensor, wte: torch.Tensor, out: torch.Tensor, row_off: int = 0) -> torch.Tensor:
-    """out[b, row_off + t, :] = wte[ids[b, t]]; out is (B, S_total, d) contiguous."""
+    """out[b, row_off + t, :] = wte[ids[b, t]]; out is (B, S_total, d) contiguous.
+
+    An id outside [0, vocab) is CLAMPED, silently and without a device sync: a negative id reads row 0, an id >= vocab reads row
+    vocab - 1; nothing outside ``wte`` is ever read (tests/test_row_kernels_gpu.py pins it).  The loss path does not share that
+    leniency: cross_entropy ignores such a target, and the engines refuse it where the labels are on the host."""
     _need_gpu(ids, wte, out)
     assert ids.dtype == torch.int64 and ids.ndim == 2 and ids.is_contiguous()
     assert wte.dtype == BF16 and wte.is_contiguous() and out.dtype == BF16 and out.ndim == 3
@@ -974,17 +978,33 @@ def build_labels(captions: torch.Tensor, prefix_len: int, eos: int) -> torch.Ten
     return labels
 
 
+def refuse_targets_outside(targets: torch.Tensor, V: int) -> None:
+    """Host-side guard of the loss paths: free where the labels are on the host (the training step), one two-element
+    device-to-host copy where they are on the device (the evaluation loss, which synchronises for its row index anyway).  A label
+    outside [0, V) -- a tokenizer wider than the head -- raises ValueError naming the id and V.  The kernels ignore such a target
+    (cross_entropy), and the embedding gather clamps the same id (embedding), so without this it would only show as a smaller loss."""
+    if targets.numel() == 0:
+        return
+    lo, hi = torch.stack(targets.aminmax()).tolist()          # one copy where the labels are on the device
+    if hi >= V:
+        raise ValueError(f"label id {hi} is outside the head's vocabulary: V = {V} (valid ids 0 .. {V - 1})")
+    if lo < 0:
+        raise ValueError(f"label id {lo} is negative: V = {V} (valid ids 0 .. {V - 1}; ignored positions are dropped before the loss)")
+
+
 def cross_entropy(logits: torch.Tensor, targets: torch.Tensor):
-    """logits [R,V] fp32 (rows already shifted), targets [R] int64 (-100 = ignore).
-    Returns (mean loss scalar tensor, per-row loss)."""
+    """logits [R,V] fp32 (rows already shifted), targets [R] int64.  A target of -100, or any other value outside [0, V), is
+    ignored: its row loss is 0 and it is not counted in the mean (F.cross_entropy raises for such a value; no device sync here).
+    Returns (mean loss scalar tensor, per-row loss); the mean is element 0 of the kernel's [mean, valid count] pair."""
     _need_gpu(logits, targets)
-    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and targets.dtype == torch.int64
+    assert logits.dtype == torch.float32 and logits.ndim == 2 and logits.stride(1) == 1
+    assert targets.dtype == torch.int64 and targets.shape == (logits.shape[0],) and targets.is_contiguous()
     R, V = logits.shape
     rows = torch.empty(R, dtype=torch.float32, device=logits.device)
     out = torch.empty(2, dtype=torch.float32, device=logits.device)
     check(L.load().mg_ce_rows_f32(logits.data_ptr(), logits.stride(0), targets.data_ptr(), rows.data_ptr(), R, V,
                                   _stream()), "mg_ce_rows_f32")
-    check(L.load().mg_ce_reduce_f32(rows.data_ptr(), targets.data_ptr(), R, out.data_ptr(), _stream()),
+    check(L.load().mg_ce_reduce_f32(rows.data_ptr(), targets.data_ptr(), R, V, out.data_ptr(), _stream()),
           "mg_ce_reduce_f32")
     return out[0], rows
 
@@ -1044,7 +1064,10 @@ def colsum(x: torch.Tensor, out: torch.Tensor, y: Optional[torch.Tensor] = None,
 
 def layernorm_bwd(dy, x, gamma, eps=1e-5, res=None, want_xhat=False):
     _need_gpu(dy, x)
-    assert dy.dtype == BF16 and x.dtype == BF16 and dy.shape == x.shape and dy.stride(1) == 1 and x.stride(1) == 1
+    assert dy.dtype == BF16 and x.dtype == BF16 and x.ndim == 2 and dy.shape == x.shape and dy.stride(1) == 1 and x.stride(1) == 1
+    _need_gpu(gamma, res)
+    assert gamma.dtype == torch.float32 and gamma.shape == (x.shape[1],) and gamma.is_contiguous(), "gamma: fp32 [d]"
+    assert res is None or (res.dtype == BF16 and res.shape == x.shape and res.stride(1) == 1), "res: bf16, x's shape, unit inner stride"
     dx = torch.empty(x.shape, dtype=BF16, device=x.device)
     xhat = torch.empty(x.shape, dtype=BF16, device=x.device) if want_xhat else None
     check(L.load().mg_layernorm_bwd_bf16(dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), gamma.data_ptr(),
@@ -1055,14 +1078,18 @@ def layernorm_bwd(dy, x, gamma, eps=1e-5, res=None, want_xhat=False):
 
 
 def cross_entropy_fwd_bwd(logits: torch.Tensor, targets: torch.Tensor, ld_out: int):
-    """loss + dlogits (bf16 [R, ld_out], zero padded) for rows already shifted."""
+    """loss + dlogits (bf16 [R, ld_out], columns [V, ld_out) zero) for rows already shifted; targets as in cross_entropy: a row
+    whose target is -100 or outside [0, V) has gradient 0 and is not counted in the 1 / n of the others."""
     _need_gpu(logits, targets)
+    assert logits.dtype == torch.float32 and logits.ndim == 2 and logits.stride(1) == 1
+    assert targets.dtype == torch.int64 and targets.shape == (logits.shape[0],) and targets.is_contiguous()
+    assert ld_out >= logits.shape[1], "ld_out < V"
     R, V = logits.shape
     rows = torch.empty(R, dtype=torch.float32, device=logits.device)
     stats = torch.empty(2, dtype=torch.float32, device=logits.device)
     lib = L.load()
     check(lib.mg_ce_rows_f32(logits.data_ptr(), logits.stride(0), targets.data_ptr(), rows.data_ptr(), R, V, _stream()), "mg_ce_rows_f32")
-    check(lib.mg_ce_reduce_f32(rows.data_ptr(), targets.data_ptr(), R, stats.data_ptr(), _stream()), "mg_ce_reduce_f32")
+    check(lib.mg_ce_reduce_f32(rows.data_ptr(), targets.data_ptr(), R, V, stats.data_ptr(), _stream()), "mg_ce_reduce_f32")
     dl = torch.empty(R, ld_out, dtype=BF16, device=logits.device)
     check(lib.mg_ce_bwd_bf16(logits.data_ptr(), logits.stride(0), targets.data_ptr(), stats.data_ptr(), dl.data_ptr(),
                              ld_out, R, V, _stream()), "mg_ce_bwd_bf16")

@@ -52,6 +52,31 @@ class ByteTokenizer:
         return bytes(i for i in ids if 0 <= i < 256).decode("utf-8", errors="replace")
 
 
+class HeadSizedTokenizer:
+    """A tokenizer whose ids fit a REDUCED head (the test-size models: eos = V - 2, image = V - 1, see Magma.__init__): ``encode``
+    turns the wrapped tokenizer's eos / padding id (GPT-2's 50256) into ``eos`` and folds every other id below it; everything
+    else (decode, the special-token attributes, len) is the wrapped tokenizer's.  Without it every padding position of a
+    tokenized caption is a label >= V, which the loss head ignores and the engines refuse (ops.refuse_targets_outside).
+    Module level and free of closures: the spawned loader workers unpickle datasets that hold one."""
+
+    def __init__(self, tok, eos: int):
+        self.tok, self.eos = tok, int(eos)
+
+    def __getattr__(self, name):          # only called for what this object does not have itself
+        if name in ("tok", "eos"):        # unpickling asks before __init__ ran
+            raise AttributeError(name)
+        return getattr(self.tok, name)
+
+    def __len__(self):
+        return len(self.tok)
+
+    def encode(self, *a, **kw):
+        ids = self.tok.encode(*a, **kw)
+        if torch.is_tensor(ids):
+            return torch.where(ids == self.tok.eos_token_id, torch.full_like(ids, self.eos), ids % self.eos)
+        return [self.eos if i == self.tok.eos_token_id else i % self.eos for i in ids]
+
+
 def get_tokenizer(name: str = "gpt2", sequence_length: int = 2048):
     if name != "gpt2":
         raise ValueError(f"Tokenizer {name} not recognized")

@@ -626,6 +626,7 @@ class MagmaEngine:
         labels = ops.build_labels(captions, P, model.eos_token)
         S = S_full
         rows, tgt, first = self.target_index(captions_host, P, model.eos_token, S_full)
+        ops.refuse_targets_outside(tgt, eng.V)            # host tensors: no device sync
         if self.truncate:     # causal attention + masked loss => identical loss/grads
             S = min(S_full, ops.ceil_to(int(first.max()) + 1 + P + 1, 64))
             rows = (rows // S_full) * S + rows % S_full

@@ -837,29 +837,124 @@ def ln_fold_reference(x, w2, b2, colsum, eps: float, act: str = "none", out_dtyp
 
 
 def cross_entropy_reference(logits: torch.Tensor, targets: torch.Tensor, ignore_index: int = -100) -> dict:
-    """Row losses lse_r - logit_r[target] (0 on ignored rows) and d mean-loss / d logits = (softmax - onehot) / n_valid (bf16), fp64,
-    with bounds -> {"rows": (ref, bound), "dlogits": (ref, bound)}.
+    """Row losses lse_r - logit_r[target] (0 on ignored rows), their mean over the valid rows and d mean-loss / d logits =
+    (softmax - onehot) / n_valid (bf16), fp64, with bounds -> {"rows" | "mean" | "dlogits": (ref, bound), "n_valid", "n"}.
+
+    The contract of the three kernels: a row is IGNORED when its target is ``ignore_index`` or lies outside [0, V) -- loss 0,
+    gradient 0, not counted in n_valid (F.cross_entropy raises for such a target; the kernels cannot).  n = max(n_valid, 1);
+    with n_valid = 0 the mean is NaN, as F.cross_entropy gives.
 
     A row reduction over V terms on 256 threads: the maximum is exact; every exponent logit - max is one rounding relative to at
     most 2 max|logit| and the libm exponential is good to 2 u32: e = 2 u32 (max|logit| + 1); the sum passes a term through at
-    most V / 256 + 9 additions; reciprocal / logarithm (2 u32), the multiplications and the final additions one rounding each."""
+    most V / 256 + 9 additions; reciprocal / logarithm (2 u32), the multiplications and the final additions one rounding each.
+    The mean adds the R row losses in fp32 (all >= 0: gamma(R + 2) of the mean itself) and inherits the rows' own bounds."""
     lg = f64(logits)
     R, V = lg.shape
-    valid = targets != ignore_index
-    n = max(int(valid.sum()), 1)
+    tgl = targets.to(lg.device)
+    valid = (tgl != ignore_index) & (tgl >= 0) & (tgl < V)
+    n_valid = int(valid.sum())
+    n = max(n_valid, 1)
     lmax = lg.abs().amax(-1, keepdim=True)
     e = 2.0 * U_F32 * (lmax + 1.0) + gamma(V / 256 + 16)
     lse = torch.logsumexp(lg, -1, keepdim=True)
     p = torch.exp(lg - lse)
-    tg = targets.clamp_min(0).to(lg.device)
+    tg = torch.where(valid, tgl, torch.zeros_like(tgl))
     onehot = torch.zeros_like(lg).scatter_(1, tg[:, None], 1.0)
-    v = valid.to(lg.device)[:, None]
+    v = valid[:, None]
     picked = lg.gather(1, tg[:, None])
     rows = torch.where(v, lse - picked, torch.zeros_like(lse)).squeeze(1)
-    rows_err = (e + 4.0 * U_F32 * (lmax + lse.abs() + picked.abs() + 1.0)).squeeze(1)
+    rows_err = torch.where(v, e + 4.0 * U_F32 * (lmax + lse.abs() + picked.abs() + 1.0), torch.zeros_like(lse)).squeeze(1)
+    rows_bound = rounded(rows, rows_err, torch.float32)
     dl = torch.where(v, (p - onehot) / n, torch.zeros_like(p))
-    dl_err = (2.0 * e * p + 3.0 * U_F32 * (p + onehot)) / n
-    return {"rows": (rows, rounded(rows, rows_err, torch.float32)), "dlogits": (dl, rounded(dl, dl_err, torch.bfloat16)), "n": n}
+    dl_err = torch.where(v, (2.0 * e * p + 3.0 * U_F32 * (p + onehot)) / n, torch.zeros_like(p))
+    mean = (rows.sum() / n_valid if n_valid else torch.full((), float("nan"), dtype=torch.float64, device=lg.device)).reshape(1)
+    mean_bound = rounded(mean, (torch.where(valid, rows_bound, torch.zeros_like(rows_bound)).sum() / n).reshape(1)
+                         + gamma(R + 2) * mean.abs(), torch.float32)
+    return {"rows": (rows, rows_bound), "dlogits": (dl, rounded(dl, dl_err, torch.bfloat16)), "mean": (mean, mean_bound),
+            "n": n, "n_valid": n_valid}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# inputs of the row kernels (LayerNorm, cross-entropy): the value families of tests/test_row_kernels_gpu.py, shared with the
+# CPU checks of the bounds (tests/test_kernel_compare_cpu.py) so that both sides judge the same numbers
+# ---------------------------------------------------------------------------------------------------------------------------
+LN_FAMILIES = ("offset", "constant", "spike", "zero")
+
+
+def layernorm_family_rows(kind: str, rows: int, d: int, seed: int) -> torch.Tensor:
+    """bf16 [rows, d] on the CPU:
+      "offset"    8 + 0.0625 N(0, 1): the mean is 128 standard deviations away, x - mean cancels 7 bits;
+      "constant"  every element of row r the same bf16 value c_r (another one per row, both signs): variance 0,
+                  rstd = eps^-1/2 multiplies whatever error the mean carries;
+      "spike"     0.01 N(0, 1) with one element 200: at column 0 on even rows, at column d - 1 on odd rows;
+      "zero"      all zero;
+      "mixed"     row r of family r % 4 (spike rows alternate their column): neighbouring rows never share their statistics."""
+    g = torch.Generator().manual_seed(seed)
+    if kind == "offset":
+        x = 8.0 + 0.0625 * torch.randn(rows, d, generator=g)
+    elif kind == "constant":
+        r = torch.arange(rows)
+        c = (0.75 * (r % 5 + 1).float() + 0.0625 * (r % 3).float()) * (1.0 - 2.0 * (r % 2).float())
+        x = c[:, None].expand(rows, d).clone()
+    elif kind == "spike":
+        x = 0.01 * torch.randn(rows, d, generator=g)
+        r = torch.arange(rows)
+        x[r, torch.where(r % 2 == 0, 0, d - 1)] = 200.0
+    elif kind == "zero":
+        x = torch.zeros(rows, d)
+    elif kind == "mixed":
+        x = torch.empty(rows, d)
+        for i, fam in enumerate(LN_FAMILIES):
+            n = len(range(i, rows, 4))
+            if n:
+                x[i::4] = layernorm_family_rows(fam, n, d, seed + 1 + i).float()
+    else:
+        raise ValueError(kind)
+    return x.to(torch.bfloat16)
+
+
+CE_FAMILIES = ("gauss", "peaked", "peaked off", "flat", "ignored", "underflow")
+
+
+def cross_entropy_family(kind: str, R: int, V: int, seed: int):
+    """(logits fp32 [R, V], targets int64 [R]) on the CPU:
+      "gauss"       3 N(0, 1); targets of rows 0 .. 3 (as far as R goes): column 0, column V - 1, the row's arg-max column, and a
+                    column whose logit is set to -200 (its probability underflows fp32); the other rows' targets are random;
+      "peaked"      one logit +3e4 per row (column (7 r + 3) % V), the rest -3e4, target on the peak: loss and gradient exactly 0;
+      "peaked off"  the same logits, target one column past the peak (mod V): loss 6e4, gradient +1/n at the peak and -1/n at
+                    the target (V = 1 has no other column: target on the peak);
+      "flat"        all logits 1e4: loss log V;
+      "ignored"     "gauss" with every target -100;
+      "underflow"   3 N(0, 1) with EVERY row's target logit set to -200 (its probability underflows fp32: the loss is ~200 + lse, the
+                    gradient -1/n there); targets at column 0, at column V - 1 -- the last element of the tail pass of the
+                    256-thread loops -- and, from row 2 on, random."""
+    g = torch.Generator().manual_seed(seed)
+    r = torch.arange(R)
+    if kind in ("gauss", "ignored"):
+        lg = 3.0 * torch.randn(R, V, generator=g)
+        tg = torch.randint(0, V, (R,), generator=g)
+        if R > 3:
+            lg[3, V // 2] = -200.0
+        k = min(R, 4)
+        tg[:k] = torch.tensor([0, V - 1, int(lg[min(2, R - 1)].argmax()), V // 2])[:k]
+        if kind == "ignored":
+            tg[:] = -100
+    elif kind == "underflow":
+        lg = 3.0 * torch.randn(R, V, generator=g)
+        tg = torch.randint(0, V, (R,), generator=g)
+        tg[:min(R, 2)] = torch.tensor([0, V - 1])[:min(R, 2)]
+        lg[r, tg] = -200.0
+    elif kind in ("peaked", "peaked off"):
+        peak = (7 * r + 3) % V
+        lg = torch.full((R, V), -3e4)
+        lg[r, peak] = 3e4
+        tg = peak if kind == "peaked" else (peak + 1) % V
+    elif kind == "flat":
+        lg = torch.full((R, V), 1e4)
+        tg = torch.randint(0, V, (R,), generator=g)
+    else:
+        raise ValueError(kind)
+    return lg, tg.to(torch.int64)
 
 
 def gelu_new_grad_terms(x: torch.Tensor):

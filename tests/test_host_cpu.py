@@ -558,3 +558,33 @@ def test_ctypes_structs_have_the_layout_of_the_header(tmp_path):
     stub = text[text.index("class mg_epilogue(C.Structure)"):text.index("class mg_gemm_desc(C.Structure)")]
     import re
     assert re.findall(r'\("(\w+)",', stub) == [f for f, _ in L.Epilogue._fields_]
+
+
+def test_labels_outside_the_head_vocabulary_are_refused_on_the_host():
+    """A caption id >= V (a tokenizer wider than the head) reaches the loss head through MagmaEngine.target_index unchanged; the
+    kernels would ignore such a target and the embedding gather clamps the id, so the engines refuse it where the labels are on
+    the host: ValueError naming the id and V."""
+    from magma_amd import ops
+    from magma_amd.train_engine import MagmaEngine
+    V, eos, P = 50, 7, 4
+    S = 24 + P
+    caps = torch.randint(8, V, (3, S), generator=torch.Generator().manual_seed(1))
+    caps[:, 20] = eos
+    rows, tgt, _ = MagmaEngine.target_index(caps, P, eos, S)
+    assert int(tgt.max()) < V and int(tgt.min()) >= 0 and tgt.numel() == 3 * 21
+    ops.refuse_targets_outside(tgt, V)                       # in range: silent
+    ops.refuse_targets_outside(tgt[:0], V)                   # nothing to check
+    caps[1, 5] = V                                           # the first id past the head
+    rows, tgt, _ = MagmaEngine.target_index(caps, P, eos, S)
+    assert int(tgt.max()) == V                               # target_index passes it on as it is
+    with pytest.raises(ValueError, match=rf"\b{V}\b.*V = {V}\b"):
+        ops.refuse_targets_outside(tgt, V)
+    caps[1, 5] = 10 ** 6
+    with pytest.raises(ValueError, match=rf"1000000.*V = {V}\b"):
+        ops.refuse_targets_outside(MagmaEngine.target_index(caps, P, eos, S)[1], V)
+    caps[1, 5] = -3
+    with pytest.raises(ValueError, match=rf"-3.*V = {V}\b"):
+        ops.refuse_targets_outside(MagmaEngine.target_index(caps, P, eos, S)[1], V)
+    caps[1, 21] = 10 ** 6                                    # behind the first eos: masked, never a label
+    caps[1, 5] = 9
+    ops.refuse_targets_outside(MagmaEngine.target_index(caps, P, eos, S)[1], V)

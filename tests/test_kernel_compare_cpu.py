@@ -848,3 +848,228 @@ def test_maxpool_bwd_reference_is_autograd():
     xi[0, 0, 2, 2] = float("nan")
     ref = kc.maxpool3x3s2_bwd_reference(xi, torch.ones(1, 1, 3, 4))[0][0, 0]
     assert float(ref[2, 2]) == 1.0 and float(ref[1, 1]) == 0.0 and float(ref.sum()) == 12.0
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the row kernels at their edges (tests/test_row_kernels_gpu.py): LayerNorm forward / backward and the cross-entropy head on the
+# value families of kernel_compare.layernorm_family_rows / cross_entropy_family
+# ---------------------------------------------------------------------------------------------------------------------------
+LN_EPS = 1e-5
+
+
+def ln_stats32(xf, fault=None):
+    """mean, rstd of a row in float32, sums in a permuted order, with the seeded slips (all on the stand-in, never on a kernel)."""
+    d = xf.shape[1]
+    perm = torch.randperm(d, generator=torch.Generator().manual_seed(7))
+    cols = perm[perm < d - 8] if fault == "mean over d - 8 elements" else perm     # the sum misses the last vector, the divisor is d
+    mean = xf[:, cols].sum(-1, keepdim=True) / d
+    var = ((xf - mean)[:, perm] ** 2).sum(-1, keepdim=True) / d
+    rstd = torch.rsqrt(var) if fault == "eps dropped" else torch.rsqrt(var + LN_EPS)
+    if fault == "statistics of the next row":
+        mean, rstd = mean.roll(-1, 0), rstd.roll(-1, 0)
+    return mean, rstd, perm
+
+
+def ln_fwd_stand_in(x, g, b, fault=None):
+    xf = x.float()
+    mean, rstd, _ = ln_stats32(xf, fault)
+    y = ((xf - mean) * rstd * g + b).to(BF16)
+    if fault == "last 8-wide store dropped":
+        y[-1, -8:] = float("nan")          # the GPU tests pre-fill every output with NaN: that is what a dropped store leaves
+    return y
+
+
+def ln_bwd_stand_in(dy, x, g, res, fault=None):
+    xf = x.float()
+    d = xf.shape[1]
+    mean, rstd, perm = ln_stats32(xf, fault)
+    xh = (xf - mean) * rstd
+    gy = dy.float() * g
+    c1 = gy[:, perm].sum(-1, keepdim=True) / d
+    c2 = (gy * xh)[:, perm].sum(-1, keepdim=True) / d
+    dx = rstd * (gy - c1 - xh * c2)
+    if res is not None and fault != "res not added":
+        dx = dx + res.float()
+    dx, xh = dx.to(BF16), xh.to(BF16)
+    if fault == "last 8-wide store dropped":
+        dx[-1, -8:] = float("nan")
+        xh[-1, -8:] = float("nan")
+    return dx, xh
+
+
+def ln_family_case(kind, rows, d):
+    x = kc.layernorm_family_rows(kind, rows, d, seed=60)
+    g = rnd(d, seed=61) * 0.1 + 1
+    b = rnd(d, seed=62) * 0.1 + 0.25          # no beta near 0: an element that lost its store or its statistics shows
+    dy = rnd(rows, d, seed=63).to(BF16)
+    res = rnd(rows, d, seed=64).to(BF16)
+    return x, g, b, dy, res
+
+
+# What each seeded statistics fault must do to each family: the outputs ("fwd", "dx", "xhat") on which it must EXCEED the bound at
+# both shapes, "no-op" where it cannot change a bit of any output, or a dict per d where the shape decides.  Every (family, fault)
+# pair has an entry, and every output that is not listed to exceed is asserted to stay within the bound, so the table states
+# the whole outcome and a change of either the bounds or the stand-in shows.
+#   * rows of one family still differ (offset: the sample mean by 0.0625 / sqrt(d); constant: another c_r per row; spike: the
+#     spike's column and the noise), so a row normalised with the NEXT row's statistics is outside the forward bound on every
+#     family but the all-zero one.  On spike rows mean (200 / d) and variance of neighbours agree to ~1e-4: the shift of the
+#     mean shows in the forward output (its small elements are ~ -mean * rstd, bound u_bf16 of that), while dx -- rstd times
+#     terms that do not contain the mean -- moves by 1e-4 relative, inside the bf16 rounding;
+#   * an all-zero row has mean 0 and variance 0 over any subset of any (all-zero) row: only the dropped eps can show (0 * inf);
+#   * eps = 1e-5 against the variance: constant and zero rows (variance 0) divide by zero; spike rows (variance ~ 4e4 / d) move rstd
+#     by a few fp32 ulps, nothing a bf16 output shows; offset rows (variance 0.0039): rstd moves by eps / (2 var) = 1.3e-3 relative, a third of u_bf16, within
+#     the bound at d = 2056 -- and outside it at d = 8, where the three rows' sample variances are 2 to 4 times smaller.
+NEXT_ROW, SHORT_MEAN, NO_EPS = "statistics of the next row", "mean over d - 8 elements", "eps dropped"
+ALL3 = ("fwd", "dx", "xhat")
+LN_STAT_FAULTS = {
+    ("offset", NEXT_ROW): ALL3, ("offset", SHORT_MEAN): ALL3, ("offset", NO_EPS): {2056: (), 8: ALL3},
+    ("constant", NEXT_ROW): ALL3, ("constant", SHORT_MEAN): ALL3, ("constant", NO_EPS): ALL3,
+    ("spike", NEXT_ROW): {2056: ("fwd", "xhat"), 8: ("fwd",)}, ("spike", SHORT_MEAN): ALL3, ("spike", NO_EPS): (),
+    ("zero", NEXT_ROW): "no-op", ("zero", SHORT_MEAN): "no-op", ("zero", NO_EPS): ALL3,
+    ("mixed", NEXT_ROW): ALL3, ("mixed", SHORT_MEAN): ALL3, ("mixed", NO_EPS): ALL3,
+}
+
+
+@pytest.mark.parametrize("rows,d", [(5, 2056), (3, 8)])
+@pytest.mark.parametrize("kind", kc.LN_FAMILIES + ("mixed",))
+def test_layernorm_families_stand_in_and_faults(kind, rows, d):
+    """Forward and backward bounds on the value families: the honest fp32 stand-in is inside (ratio printed), every seeded fault
+    outside.  LN_STAT_FAULTS states, for every (family, statistics fault) pair, on which outputs the fault must exceed the bound,
+    and where it cannot: there it is asserted to change nothing, or to stay within the bound."""
+    x, g, b, dy, res = ln_family_case(kind, rows, d)
+    T = kc.layernorm_terms(x, g, b, LN_EPS)
+    ref, bound = T["ref"], kc.layernorm_bound(T, d)
+    w = kc.assert_elementwise(ln_fwd_stand_in(x, g, b), ref, bound, f"honest LayerNorm, {kind} rows {rows}x{d}")
+    assert w <= 1.0
+    Rb = {r is not None: kc.layernorm_bwd_reference(dy, x, g, LN_EPS, res=r) for r in (res, None)}
+    for with_res, r in ((True, res), (False, None)):
+        dx, xh = ln_bwd_stand_in(dy, x, g, r)
+        assert kc.assert_elementwise(dx, *Rb[with_res]["dx"], f"honest LayerNorm backward dx, {kind} rows {rows}x{d}, res {with_res}") <= 1.0
+        assert kc.assert_elementwise(xh, *Rb[with_res]["xhat"], f"honest LayerNorm backward xhat, {kind} rows {rows}x{d}") <= 1.0
+    honest = {"fwd": ln_fwd_stand_in(x, g, b)}
+    honest["dx"], honest["xhat"] = ln_bwd_stand_in(dy, x, g, res)
+    refs = {"fwd": (ref, bound), "dx": Rb[True]["dx"], "xhat": Rb[True]["xhat"]}
+    for fault in (NEXT_ROW, SHORT_MEAN, NO_EPS):
+        bad = {"fwd": ln_fwd_stand_in(x, g, b, fault)}
+        bad["dx"], bad["xhat"] = ln_bwd_stand_in(dy, x, g, res, fault)
+        want = LN_STAT_FAULTS[(kind, fault)]
+        want = want[d] if isinstance(want, dict) else want
+        for name in ALL3:
+            what = f"{kind} {rows}x{d} {name}: {fault}"
+            if want == "no-op":
+                assert torch.equal(bad[name], honest[name]), f"{what}: expected to change nothing"
+            elif name in want:
+                check_exceeds(what, bad[name], *refs[name])
+            else:
+                w = kc.worst_ratio(bad[name], *refs[name])
+                print(f"    fault {what:<58s} err/bound {w:9.3g}   (stated to stay within the bound)")
+                assert w <= 1.0, f"{what}: {w:.3g}, LN_STAT_FAULTS states that this fault stays within the bound here"
+    check_exceeds(f"{kind} {rows}x{d} forward: last 8-wide store dropped", ln_fwd_stand_in(x, g, b, "last 8-wide store dropped"), ref, bound)
+    bad = ln_fwd_stand_in(x, g, b); bad[-1, -8:] = 0
+    check_exceeds(f"{kind} {rows}x{d} forward: last 8 elements zero", bad, ref, bound)
+    bdx, bxh = ln_bwd_stand_in(dy, x, g, res, "last 8-wide store dropped")
+    check_exceeds(f"{kind} {rows}x{d} backward dx: last 8-wide store dropped", bdx, *Rb[True]["dx"])
+    check_exceeds(f"{kind} {rows}x{d} backward xhat: last 8-wide store dropped", bxh, *Rb[True]["xhat"])
+    bdx, _ = ln_bwd_stand_in(dy, x, g, res, "res not added")
+    check_exceeds(f"{kind} {rows}x{d} backward dx: res not added", bdx, *Rb[True]["dx"])
+    bdx, _ = ln_bwd_stand_in(dy, x, g, res)
+    check_exceeds(f"{kind} {rows}x{d} backward dx: res added although none was given", bdx, *Rb[False]["dx"])
+
+
+def ce_stand_in(lg, tg, fault=None, Vp=None, pad=1e30):
+    """The three kernels in float32: maximum, exponentials, 256 strided partial sums, logarithm; the mean and the count over the
+    rows whose target lies in [0, V); d logits rounded to bf16.  -> (rows, [mean, count], dlogits).  Seeded slips:
+    "no max", "count includes out-of-range", "sum over V - 1", "sum over Vp" (pad columns hold ``pad``), "onehot at target + 1" / "- 1"."""
+    x = lg.float()
+    R, V = x.shape
+    cols = x
+    if fault == "sum over V - 1":
+        cols = x[:, : V - 1]
+    if fault == "sum over Vp":
+        cols = torch.cat([x, torch.full((R, Vp - V), pad)], 1)
+    mx = torch.zeros(R, 1) if fault == "no max" else cols.amax(1, keepdim=True)
+    e = torch.exp(cols - mx)
+    n = e.shape[1]
+    part = torch.zeros(R, 256)
+    for i in range(0, n, 256):                       # thread t adds columns t, t + 256, ... in order
+        part[:, : min(256, n - i)] += e[:, i:i + 256]
+    s = part.view(R, 4, 64).sum(-1).sum(-1, keepdim=True)
+    valid = (tg >= 0) & (tg < V)
+    t = torch.where(valid, tg, torch.zeros_like(tg))
+    rows = torch.where(valid, (torch.log(s) + mx - x.gather(1, t[:, None])).squeeze(1), torch.zeros(R))
+    counted = (tg >= 0) if fault == "count includes out-of-range" else valid
+    cnt = counted.float().sum()
+    mean = torch.where(counted, rows, torch.zeros(R)).sum() / cnt
+    hot = t + (1 if fault == "onehot at target + 1" else -1 if fault == "onehot at target - 1" else 0)
+    onehot = torch.zeros(R, V).scatter_(1, (hot % V)[:, None], 1.0)
+    dl = (torch.exp(x - mx) * (1.0 / s) - onehot) * (1.0 / cnt)
+    dl = torch.where(valid[:, None], dl, torch.zeros(R, V)).to(BF16)
+    return rows, torch.stack([mean, cnt]), dl
+
+
+def assert_ce(got, C, what):
+    rows, stats, dl = got
+    w = [kc.assert_elementwise(rows, *C["rows"], what + " row losses"), kc.assert_elementwise(dl, *C["dlogits"], what + " d logits")]
+    if C["n_valid"]:
+        w.append(kc.assert_elementwise(stats[:1], *C["mean"], what + " mean"))
+    else:
+        assert bool(torch.isnan(stats[0]))
+    assert float(stats[1]) == C["n_valid"], f"{what}: count {float(stats[1])} != {C['n_valid']}"
+    return max(w)
+
+
+@pytest.mark.parametrize("V", [257, 50258])
+@pytest.mark.parametrize("kind", kc.CE_FAMILIES)
+def test_cross_entropy_families_stand_in(kind, V):
+    lg, tg = kc.cross_entropy_family(kind, 5, V, seed=70)
+    C = kc.cross_entropy_reference(lg, tg)
+    assert assert_ce(ce_stand_in(lg, tg), C, f"honest cross-entropy, {kind} V={V}") <= 1.0
+    if kind == "peaked":
+        assert bool((C["rows"][0] == 0).all()) and bool((C["dlogits"][0] == 0).all())
+    if kind == "peaked off":
+        assert torch.allclose(C["rows"][0], torch.full((5,), 6e4, dtype=torch.float64))
+    if kind == "flat":
+        assert torch.allclose(C["rows"][0], torch.full((5,), math.log(V), dtype=torch.float64))
+
+
+def test_cross_entropy_reference_ignores_targets_outside_the_vocabulary():
+    """The contract the kernels are held to: -100 and every target outside [0, V) are ignored alike, and not counted."""
+    V = 257
+    lg, _ = kc.cross_entropy_family("gauss", 6, V, seed=71)
+    tg = torch.tensor([3, 256, 257, 10 ** 6, -1, -100])
+    C = kc.cross_entropy_reference(lg, tg)
+    assert C["n_valid"] == 2 and C["n"] == 2
+    two = torch.nn.functional.cross_entropy(lg[:2].double(), tg[:2], reduction="none")
+    assert torch.allclose(C["rows"][0][:2], two, rtol=1e-12) and bool((C["rows"][0][2:] == 0).all())
+    assert torch.allclose(C["mean"][0], two.mean().reshape(1), rtol=1e-12)
+    lgr = lg[:2].double().requires_grad_(True)
+    torch.nn.functional.cross_entropy(lgr, tg[:2]).backward()
+    assert torch.allclose(C["dlogits"][0][:2], lgr.grad, rtol=1e-9, atol=1e-300) and bool((C["dlogits"][0][2:] == 0).all())
+    assert bool((C["dlogits"][1][2:] <= kc.FLOOR).all()), "an ignored row has no allowance: exactly 0"
+    assert assert_ce(ce_stand_in(lg, tg), C, "honest cross-entropy, targets outside [0, V)") <= 1.0
+    rows, stats, dl = ce_stand_in(lg, tg, "count includes out-of-range")        # the kernel before the fix
+    assert float(stats[1]) == 4
+    check_exceeds("count includes the out-of-range rows: mean", stats[:1], *C["mean"])
+    check_exceeds("count includes the out-of-range rows: d logits", dl, *C["dlogits"])
+
+
+def test_cross_entropy_seeded_faults_exceed_the_bound():
+    V, Vp = 257, 264
+    lg, tg = kc.cross_entropy_family("peaked off", 5, V, seed=72)
+    C = kc.cross_entropy_reference(lg, tg)
+    rows, stats, dl = ce_stand_in(lg, tg, "no max")
+    check_exceeds("peaked: no max subtraction, row losses", rows, *C["rows"])
+    check_exceeds("peaked: no max subtraction, d logits", dl, *C["dlogits"])
+    lg, tg = kc.cross_entropy_family("gauss", 5, V, seed=72)          # row 1: target V - 1; row 2: target at the arg-max
+    lg[1, V - 1] = lg[1].max() + 1.0                                  # the last column carries most of row 1's sum
+    C = kc.cross_entropy_reference(lg, tg)
+    assert assert_ce(ce_stand_in(lg, tg), C, "honest cross-entropy, last column the largest") <= 1.0
+    for fault in ("sum over V - 1", "sum over Vp"):
+        rows, stats, dl = ce_stand_in(lg, tg, fault, Vp=Vp)
+        check_exceeds(f"gauss: {fault}, row losses", rows, *C["rows"])
+        check_exceeds(f"gauss: {fault}, d logits", dl, *C["dlogits"])
+    for fault in ("onehot at target + 1", "onehot at target - 1"):
+        for kind in kc.CE_FAMILIES[:4]:
+            lg, tg = kc.cross_entropy_family(kind, 5, V, seed=72)
+            rows, stats, dl = ce_stand_in(lg, tg, fault)
+            check_exceeds(f"{kind}: {fault}", dl, *kc.cross_entropy_reference(lg, tg)["dlogits"])
