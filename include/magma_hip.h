@@ -572,7 +572,9 @@ int mg_ce_reduce_f32(const float* loss_row, const int64_t* tgt, int32_t R, int32
  * the DeepSpeed engine configured at magma/config.py:113-134).                                                  */
 
 /* out[C,R] = in[R,C]^T (batched).  Feeds the wgrad GEMMs, which contract over the
- * row index M of activations: dW[N,K] = dY^T[N,M] * (X^T[K,M])^T.                 */
+ * row index M of activations: dW[N,K] = dY^T[N,M] * (X^T[K,M])^T.
+ * C % 8 == 0; R is any positive count with ld_out >= round_up(R, 8): the columns [R, round_up(R, 8)) of out are written as zeros
+ * (the K padding of that GEMM), nothing beyond them is touched.                     */
 int mg_transpose_bf16(const mg_bf16* in, int64_t ld_in, int64_t bs_in, mg_bf16* out, int64_t ld_out,
                       int64_t bs_out, int32_t R, int32_t C, int32_t batch, void* stream);
 /* The same transpose of ONE matrix that also accumulates colsum[c] += sum_r in[r][c] (fp32): the bias gradient and the weight-gradient

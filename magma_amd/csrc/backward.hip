@@ -8,7 +8,9 @@ namespace {
 
 // ---------------------------------------------------------------------------
 // transpose: in [R, C] (ld_in) -> out [C, R] (ld_out); 64x64 tiles through LDS.
-// R, C multiples of 8.  batched through blockIdx.z.
+// C a multiple of 8 (16-byte loads along a row of in); R is any positive count: a row of out is written in 8-element runs, so
+// its columns [R, round_up(R, 8)) are written too, as zeros (ld_out >= round_up(R, 8)) -- the wgrad GEMM contracts over them --
+// and nothing at or past round_up(R, 8) is touched.  batched through blockIdx.z.
 // ---------------------------------------------------------------------------
 // COLSUM: also colsum[c] += sum_r in[r][c] (fp32 atomics, 64 per workgroup) from the tile already in LDS -- the bias gradient of a
 // Linear whose weight gradient needs this very transpose (adapters: one pass over g instead of colsum_kernel + transpose_kernel).

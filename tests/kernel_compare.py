@@ -1309,3 +1309,173 @@ def relu_rows_input(B: int, HW: int, C: int, seed: int):
     x[pick == 1] = -0.0
     x[pick == 2] = 2.0 ** -133
     return x, torch.randn(B, C, generator=gen).to(torch.bfloat16)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the 3x3 convolutions of the CLIP trunk: forward, input gradient (dgrad), weight gradient (wgrad)
+# ---------------------------------------------------------------------------------------------------------------------------
+# (B, H, W, Cin, Cout): the smallest shapes that reach each mechanism of the implicit-im2col loader of gemm128_kernel and of
+# im2col_t_kernel (cpt = Cin / 8 16-byte chunks per tap, 8 chunks per K-tile, 128-row M-tiles, 64-row tiles of im2col_t)
+CONV_SHAPES = [
+    (1, 1, 1, 8, 8),             # one pixel: eight of nine taps are padding; cpt = 1: a K-tile spans eight taps
+    (2, 1, 5, 24, 16),           # image one pixel high
+    (2, 5, 1, 24, 16),           # image one pixel wide
+    (3, 5, 7, 40, 24),           # M = 105: a partial M-tile, M % 8 = 1; cpt = 5: taps end inside a K-tile; images end at rows 35, 70
+    (2, 9, 15, 72, 40),          # M = 270 = 2 M-tiles + 14 rows, cut inside an image row; batch boundary (135) inside a tile; cpt = 9,
+                                 # K = 648: 11 K-tiles, the last one with one chunk
+    (1, 12, 12, 192, 136),       # Cin > 64 and a multiple of 64: taps align with K-tiles; two N-tiles, the second with 8 columns
+    (2, 12, 12, 768, 768),       # layer 4 of the trunk at batch 2: K = 6912
+]
+CONV_FAMILIES = ("integers", "gaussian")
+EXACT_F32 = 2.0 ** 24            # integers of magnitude <= 2^24 are fp32 values
+
+
+def conv_shape_id(shape) -> str:
+    return "x".join(str(v) for v in shape[:3]) + f",{shape[3]}->{shape[4]}"
+
+
+def gemm128_splits(M: int, N: int, K: int, split_k: int) -> int:
+    """How many split-K slabs gemm_dispatch (csrc/gemm.hip) gives the 128x128 kernel for a bf16 problem that does not go to the
+    256x256 kernel (every convolution: its A is not dense), with the default 64 MiB workspace: split_k 1 never splits, n > 1 asks
+    for n, 0 asks for min(16, K-tiles / 4, ceil(512 / tiles)) while fewer than 192 tiles exist; the request is clamped to the
+    number of K-tiles, each split takes ceil(K-tiles / request) K-tiles and only the splits that start before the end exist."""
+    nkt = -(-K // 64)
+    tiles = -(-M // 128) * -(-N // 128)
+    want = split_k
+    if want == 0:
+        want = (2 if (tiles < 512 and nkt >= 128) else 1) if tiles >= 192 else min(16, nkt // 4, -(-512 // tiles))
+    want = max(1, min(want, nkt))
+    assert want * M * -(-N // 128) * 128 * 4 <= 64 << 20, "the default workspace would clamp this request"
+    kt_per = -(-nkt // want)
+    return -(-nkt // kt_per)
+
+
+def split_starts_inside_a_tap(K: int, channels: int, splits: int) -> list:
+    """The first 16-byte chunk of every split after the first, where it does not fall on a tap boundary (chunk % cpt != 0)."""
+    nkt = -(-K // 64)
+    kt_per = -(-nkt // splits)
+    return [s * kt_per * 8 for s in range(1, splits) if (s * kt_per * 8) % (channels // 8)]
+
+
+def conv_case(family: str, shape, seed: int = 0, device="cpu") -> dict:
+    """Every operand of the three passes of one 3x3 convolution (stride 1, padding 1) with a folded BatchNorm behind it.
+
+      x [B, Cin, H, W] bf16, x_rows [M, Cin] (NHWC rows)      the activation          w [Cout, Cin, 3, 3] bf16   the weight
+      g [B, Cout, H, W] bf16, g_rows [M, Cout]                the upstream gradient   scale, bias [Cout] fp32    the folded BatchNorm
+      res_out [M, Cout], res_in [M, Cin] bf16                 residuals of the forward / of the dgrad epilogue
+      gate_in [M, Cin] bf16                                   the ReLU gate of the dgrad epilogue (open where > 0)
+      base [Cout, 9 Cin] fp32                                 what the gradient buffer holds before the wgrad GEMM adds to it
+
+    "integers": values in [-4, 4], scale in {0.5, 1, 2}, gate in {-1, 0, 1}: every product and partial sum of the three passes is
+    a multiple of 1/2 below 2^23 (assert_exact_in_fp32 checks it per use), exact in fp32 in ANY order -- MFMA order, split-K
+    slabs, an accumulate onto the integer base -- so a kernel's output EQUALS the fp64 reference cast once to the output type.
+    "gaussian": the suite's usual operands -- N(0, 1) activations and gradients, weights of scale (9 Cin)^-1/2, scale = |N| + 0.5,
+    gates of either sign with +0 / -0 on the corners -- for the per-element bounds."""
+    B, H, W, Cin, Cout = shape
+    M = B * H * W
+    gen = torch.Generator().manual_seed(1000 * seed + 7 * M + Cin + 3 * Cout)
+    if family == "integers":
+        ints = lambda *s: torch.randint(-4, 5, s, generator=gen).float()
+        x, w, g = ints(B, Cin, H, W), ints(Cout, Cin, 3, 3), ints(B, Cout, H, W)
+        scale = torch.tensor([0.5, 1.0, 2.0])[torch.randint(0, 3, (Cout,), generator=gen)]
+        bias, res_out, res_in, base = ints(Cout), ints(M, Cout), ints(M, Cin), ints(Cout, 9 * Cin)
+        gate_in = torch.randint(-1, 2, (M, Cin), generator=gen).float()
+    elif family == "gaussian":
+        n = lambda *s: torch.randn(*s, generator=gen)
+        x, w, g = n(B, Cin, H, W), n(Cout, Cin, 3, 3) * (9 * Cin) ** -0.5, n(B, Cout, H, W)
+        scale = n(Cout).abs() + 0.5
+        bias, res_out, res_in, base = n(Cout), n(M, Cout), n(M, Cin), n(Cout, 9 * Cin)
+        gate_in = n(M, Cin)
+        gate_in[0, 0], gate_in[-1, -1] = 0.0, -0.0
+    else:
+        raise ValueError(family)
+    bf = lambda t: t.to(torch.bfloat16).to(device)
+    x, w, g = bf(x), bf(w), bf(g)
+    rows = lambda t: t.permute(0, 2, 3, 1).reshape(M, t.shape[1]).contiguous()
+    return dict(family=family, shape=tuple(shape), M=M, x=x, w=w, g=g, x_rows=rows(x), g_rows=rows(g), scale=scale.to(device), bias=bias.to(device),
+                res_out=bf(res_out), res_in=bf(res_in), gate_in=bf(gate_in), base=base.to(device))
+
+
+def conv_weight_rows(w: torch.Tensor) -> torch.Tensor:
+    """[Cout, Cin, 3, 3] -> the forward GEMM operand [Cout, 9 Cin] in (ky, kx, ci) order (conv_weight_relayout mode 0 without its padding)."""
+    return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
+
+
+def conv_dgrad_weight_rows(w: torch.Tensor, scale: torch.Tensor, flip: bool = True) -> torch.Tensor:
+    """The dgrad operand conv_weight_relayout(w, 1, scale) writes, without its padding: [Cin, 9 Cout] bf16,
+    W'[ci][(ky, kx), co] = bf16(W[co][ci][2 - ky][2 - kx] * scale[co]) (tests/test_backward_kernels_gpu.py pins it bit for bit).
+    flip=False is the seeded fault of the CPU tests."""
+    ws = w.float() * scale.float().view(-1, 1, 1, 1)
+    if flip:
+        ws = ws.flip(2, 3)
+    return ws.permute(1, 2, 3, 0).reshape(w.shape[1], -1).to(torch.bfloat16)
+
+
+def conv2d_dgrad_terms(g: torch.Tensor, w: torch.Tensor = None, scale: torch.Tensor = None, *, wd: torch.Tensor = None):
+    """(ref, mag, K) of the input gradient of y = conv2d(x, w * scale[co], padding = 1) as the GEMM it is run as: a 3x3 convolution of
+    the upstream gradient g [B, Cout, H, W] with the taps FLIPPED and the channel roles swapped (a transposed convolution),
+    rows [B*H*W, Cin] in NHWC order, K = 9 Cout.  Either w [Cout, Cin, 3, 3] and scale [Cout] (the exact w * scale in fp64), or
+    wd = the operand the kernel multiplies with, [Cin, >= 9 Cout] in the layout of conv_dgrad_weight_rows (its own bf16
+    rounding of w * scale is then the re-layout kernel's business and not charged to the GEMM)."""
+    Cout = g.shape[1]
+    if wd is None:
+        w64 = f64(w) * (1.0 if scale is None else f64(scale).view(-1, 1, 1, 1))
+        wt = w64.flip(2, 3).permute(1, 0, 2, 3)                                      # [Cin, Cout, ky, kx]
+    else:
+        wt = f64(wd)[:, : 9 * Cout].reshape(wd.shape[0], 3, 3, Cout).permute(0, 3, 1, 2)
+    return conv2d_terms(g, wt)
+
+
+def conv2d_wgrad_terms(g_rows: torch.Tensor, x: torch.Tensor):
+    """(ref, mag, K) of the weight gradient of y = conv2d(x, w, padding = 1): dW[co][(ci, ky, kx)] = sum over the B*H*W output
+    pixels m of g[m][co] * x[pixel m moved by (ky - 1, kx - 1)][ci] (zero outside the image) -- g_rows [B*H*W, Cout] in NHWC order,
+    x [B, Cin, H, W]; rows of the result in the weight's own [Cin, 3, 3] flattening, K = B*H*W."""
+    M = g_rows.shape[0]
+    cols = torch.nn.functional.unfold(f64(x), 3, padding=1).permute(1, 0, 2).reshape(-1, M)        # [Cin 9, M]
+    g64 = f64(g_rows)
+    return g64.t() @ cols.t(), g64.abs().t() @ cols.abs().t(), M
+
+
+def im2col_t_reference(x: torch.Tensor) -> torch.Tensor:
+    """What mg_im2col_t_bf16 writes for x [B, Cin, H, W] bf16: [9 Cin, round_up(M, 8)], row ci * 9 + ky * 3 + kx, column m = the
+    pixel of m moved by (ky - 1, kx - 1) or 0 outside the image; columns [M, round_up(M, 8)) are zero."""
+    B, Cin, H, W = x.shape
+    M = B * H * W
+    out = torch.zeros(9 * Cin, -(-M // 8) * 8, dtype=x.dtype, device=x.device)
+    out[:, :M] = torch.nn.functional.unfold(x.float(), 3, padding=1).permute(1, 0, 2).reshape(9 * Cin, M).to(x.dtype)
+    return out
+
+
+def assert_exact_in_fp32(mag: torch.Tensor, lsb: float = 0.5, what: str = "") -> float:
+    """The premise of the "integers" family, checked instead of assumed: every partial sum is a multiple of ``lsb`` and at most
+    max(mag) in magnitude; such values are fp32 numbers while max(mag) < 2^24 * lsb."""
+    top = float(mag.max()) if mag.numel() else 0.0
+    assert top < EXACT_F32 * lsb, f"{what}: magnitude sum {top:.6g} is not below 2^24 * {lsb}: fp32 sums are no longer exact"
+    return top
+
+
+def assert_bit_exact(got: torch.Tensor, ref: torch.Tensor, what: str = "") -> None:
+    """got == the fp64 reference cast ONCE to got's type, every element (no tolerance; +0 and -0 compare equal)."""
+    assert ref.dtype == torch.float64 and got.shape == ref.shape, (got.shape, ref.shape, ref.dtype)
+    want = ref.to(got.dtype)
+    ok = torch.equal(got, want)
+    print(f"[bit-exact] {what}: {'equal' if ok else 'DIFFERENT'}, {got.numel()} elements")
+    if not ok:
+        bad = (got != want) | torch.isnan(got)
+        nz = bad.nonzero()
+        lo, hi = nz.min(0).values.tolist(), nz.max(0).values.tolist()
+        i = tuple(nz[0].tolist())
+        raise AssertionError(f"{what}: {int(bad.sum())} of {got.numel()} elements differ from the exact result; first at {i} (got {float(got[i]):.9g}, "
+                             f"exact {float(want[i]):.9g}); bounding box of the offenders " + " x ".join(f"[{a}..{b}]" for a, b in zip(lo, hi)))
+
+
+def assert_conv_output(family: str, got: torch.Tensor, ref_bound, what: str, mag: torch.Tensor = None) -> None:
+    """One output of a convolution pass in its family: "integers" -> assert_bit_exact against ref (and the exactness premise on the
+    magnitude sum ``mag``), "gaussian" -> assert_elementwise against (ref, bound)."""
+    ref, bound = ref_bound
+    if family == "integers":
+        assert mag is not None
+        assert_exact_in_fp32(mag, 0.5, what)
+        assert_bit_exact(got, ref, what)
+    else:
+        assert_elementwise(got, ref, bound, what)

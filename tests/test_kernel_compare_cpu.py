@@ -1073,3 +1073,299 @@ def test_cross_entropy_seeded_faults_exceed_the_bound():
             lg, tg = kc.cross_entropy_family(kind, 5, V, seed=72)
             rows, stats, dl = ce_stand_in(lg, tg, fault)
             check_exceeds(f"{kind}: {fault}", dl, *kc.cross_entropy_reference(lg, tg)["dlogits"])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the 3x3 convolutions of the CLIP trunk (tests/test_conv_trunk_kernels_gpu.py): the new term builders against autograd, honest
+# stand-ins that walk the operands the way the kernels do, and the seeded faults, in both input families at every table shape
+# ---------------------------------------------------------------------------------------------------------------------------
+CONV_IDS = [kc.conv_shape_id(s) for s in kc.CONV_SHAPES]
+_conv_cases = {}
+
+
+def conv_case(family, shape):
+    """One set of operands and fp64 products per (family, shape), shared by the tests below and left unchanged."""
+    key = (family, tuple(shape))
+    if key not in _conv_cases:
+        c = kc.conv_case(family, shape)
+        c["fwd"] = kc.conv2d_terms(c["x"], c["w"])
+        c["wd"] = kc.conv_dgrad_weight_rows(c["w"], c["scale"])
+        c["dgrad"] = kc.conv2d_dgrad_terms(c["g"], wd=c["wd"])
+        c["wgrad"] = kc.conv2d_wgrad_terms(c["g_rows"], c["x"])
+        _conv_cases[key] = c
+    return _conv_cases[key]
+
+
+def conv_rows_stand_in(a_rows, wk, B, H, W, *, splits=1, fault=None):
+    """The implicit-im2col GEMM as gemm128_kernel walks it, in fp32: a_rows [M, C] NHWC rows (bf16), wk [N, 9 C] (bf16) in
+    (ky, kx, c) order.  K is walked in 16-byte chunks of 8 channels, 8 chunks per K-tile, ceil(K-tiles / splits) K-tiles per
+    split; chunk q is tap q / cpt, channels 8 (q % cpt) ..; the A chunk of row m comes from row m + (ky - 1) W + (kx - 1) when
+    that pixel is inside the image of m, and is zero for the halo and for tap >= 9.  Each split sums its own fp32 slab, the slabs
+    are added in order.  -> fp32 [M, N].
+
+    Seeded faults (one at a time):
+      "halo_x"           the test on the column is left out: the neighbouring image row (or image) leaks in
+      "halo_batch"       the test on the row is made on the row index of the whole batch: only the first and the last image
+                         have a border above / below, every other border reads the neighbouring IMAGE
+      "drop_last_ktile"  the last K-tile (the partial one where K % 64 != 0) is never staged
+      "split_tap_floor"  a split's tap / channel counters start at the BEGINNING of the tap its first chunk lies in"""
+    M, C = a_rows.shape
+    N, K = wk.shape
+    cpt, nkt = C // 8, -(-K // 64)
+    kt_per = -(-nkt // splits)
+    af = torch.cat([a_rows.float(), torch.zeros(1, C)])                      # row M: the zero page
+    wp = torch.zeros(N, nkt * 64)
+    wp[:, :K] = wk.float()
+    m = torch.arange(M)
+    xx, yy, row = m % W, (m // W) % H, m // W
+    out = torch.zeros(M, N)
+    for kt0 in range(0, nkt, kt_per):
+        kt1 = min(nkt, kt0 + kt_per)
+        if fault == "drop_last_ktile":
+            kt1 = min(kt1, nkt - 1)
+        if kt1 <= kt0:
+            continue
+        q = torch.arange(kt0 * 8, kt1 * 8)
+        qa = q if fault != "split_tap_floor" else (kt0 * 8 // cpt) * cpt + (q - kt0 * 8)      # the chunk the A loader believes it is at
+        tap, cc = qa // cpt, qa % cpt
+        ky, kx = tap // 3, tap % 3
+        y2, x2 = yy[:, None] + ky[None, :] - 1, xx[:, None] + kx[None, :] - 1
+        ok = (tap < 9)[None, :] & (y2 >= 0) & (y2 < H) & (x2 >= 0) & (x2 < W)
+        if fault == "halo_x":
+            ok = (tap < 9)[None, :] & (y2 >= 0) & (y2 < H)
+        if fault == "halo_batch":
+            r2 = row[:, None] + ky[None, :] - 1
+            ok = (tap < 9)[None, :] & (r2 >= 0) & (r2 < B * H) & (x2 >= 0) & (x2 < W)
+        src = m[:, None] + (ky[None, :] - 1) * W + (kx[None, :] - 1)
+        src = torch.where(ok & (src >= 0) & (src < M), src, torch.full_like(src, M))           # outside the tensor: nothing to leak
+        a = af[src[:, :, None], (cc[None, :, None] * 8 + torch.arange(8)[None, None, :])]       # [M, chunks, 8]
+        out += a.reshape(M, -1) @ wp[:, kt0 * 64: kt1 * 64].t()
+    return out
+
+
+def im2col_t_stand_in(x_rows, B, H, W, fault=None):
+    """im2col_t_kernel tap by tap over the NHWC rows: out[ci * 9 + tap][m] = x_rows[m + (ky - 1) W + (kx - 1)][ci] inside the image,
+    0 outside; the columns [M, round_up(M, 8)) are zero.  Fault "tail_copy": they hold a copy of column M - 1."""
+    M, C = x_rows.shape
+    Mp = -(-M // 8) * 8
+    out = torch.zeros(C, 9, Mp, dtype=x_rows.dtype)
+    m = torch.arange(M)
+    xx, yy = m % W, (m // W) % H
+    for tap in range(9):
+        ky, kx = tap // 3, tap % 3
+        ok = (yy + ky - 1 >= 0) & (yy + ky - 1 < H) & (xx + kx - 1 >= 0) & (xx + kx - 1 < W)
+        src = (m + (ky - 1) * W + (kx - 1)).clamp(0, M - 1)
+        out[:, tap, :M] = torch.where(ok[:, None], x_rows[src], torch.zeros_like(x_rows)).t()
+    out = out.reshape(9 * C, Mp)
+    if fault == "tail_copy":
+        out[:, M:] = out[:, M - 1: M]
+    return out
+
+
+def transpose_stand_in(g_rows):
+    M, C = g_rows.shape
+    out = torch.zeros(C, -(-M // 8) * 8, dtype=g_rows.dtype)
+    out[:, :M] = g_rows.t()
+    return out
+
+
+def wgrad_stand_in(gT, xT, base, scale, fault=None):
+    """The accumulating fp32 GEMM of _acc_wgrad over round_up(M, 8) columns of both operands, in 64-column K-tiles:
+    base + scale[co] * (gT xT^T).  Fault "row_scale_on_base": the factor is applied after the base was added."""
+    acc = torch.zeros(gT.shape[0], xT.shape[0])
+    for k0 in range(0, gT.shape[1], 64):
+        acc += gT[:, k0:k0 + 64].float() @ xT[:, k0:k0 + 64].float().t()
+    if fault == "row_scale_on_base":
+        return (base + acc) * scale[:, None]
+    return base + acc * scale[:, None]
+
+
+def accepted(family, got, ref_bound) -> bool:
+    """The verdict of the family's comparison: torch.equal with the reference cast once ("integers"), every element inside its
+    bound ("gaussian")."""
+    ref, bound = ref_bound
+    if family == "integers":
+        return torch.equal(got, ref.to(got.dtype))
+    return kc.worst_ratio(got, ref, bound) <= 1.0
+
+
+# the forward epilogue of the bottleneck with everything in it, and the dgrad epilogue of _unit_bwd's last call
+def fwd_reference(c, full):
+    if not full:
+        return kc.epilogue_reference(c["fwd"])["C"]
+    return kc.epilogue_reference(c["fwd"], scale=c["scale"], bias=c["bias"], act="relu", residuals=(c["res_out"],), act_after="relu")["C"]
+
+
+def fwd_epilogue32(acc, c, full):
+    if not full:
+        return acc.to(BF16)
+    v = torch.relu(acc * c["scale"] + c["bias"]) + c["res_out"].float()
+    return torch.relu(v).to(BF16)
+
+
+def dgrad_reference(c):
+    return kc.epilogue_reference(c["dgrad"], aux=c["gate_in"], aux_mode="relu_gate", aux_after=True, residuals=(c["res_in"],))["C"]
+
+
+def dgrad_epilogue32(acc, c):
+    return ((acc + c["res_in"].float()) * (c["gate_in"].float() > 0)).to(BF16)
+
+
+def wgrad_reference(c):
+    return kc.epilogue_reference(c["wgrad"], row_scale=c["scale"], base=c["base"], out_dtype=torch.float32)["C"]
+
+
+@pytest.mark.parametrize("shape", kc.CONV_SHAPES[:6], ids=CONV_IDS[:6])
+def test_conv_term_builders_are_the_autograd_gradients(shape):
+    """conv2d_dgrad_terms / conv2d_wgrad_terms (unfold + matmul in fp64) == fp64 autograd of F.conv2d(x, w * scale, padding = 1), and
+    the dgrad terms taken from the re-laid-out operand == those taken from w and scale where w * scale is exact in bf16."""
+    c = conv_case("integers", shape)
+    B, H, W, Cin, Cout = shape
+    x = c["x"].double().requires_grad_(True)
+    w = c["w"].double().requires_grad_(True)
+    ws = w * c["scale"].double().view(-1, 1, 1, 1)
+    torch.nn.functional.conv2d(x, ws, padding=1).backward(c["g"].double())
+    dx = x.grad.permute(0, 2, 3, 1).reshape(c["M"], Cin)
+    ref, mag, K = kc.conv2d_dgrad_terms(c["g"], c["w"], c["scale"])
+    assert K == 9 * Cout and torch.equal(ref, dx) and bool((mag >= ref.abs()).all())
+    ref2, mag2, _ = c["dgrad"]
+    assert torch.equal(ref2, dx) and torch.equal(mag2, mag)
+    # dW of the SCALED weight is scale[co] * dW of the plain convolution: the row_scale of the wgrad GEMM
+    dw, wmag, Kw = c["wgrad"]
+    assert Kw == c["M"] and torch.equal(dw * c["scale"].double()[:, None], w.grad.reshape(Cout, 9 * Cin)) and bool((wmag >= dw.abs()).all())
+    # gaussian operands: the same identities to fp64 rounding
+    c = conv_case("gaussian", shape)
+    x = c["x"].double().requires_grad_(True)
+    w = c["w"].double().requires_grad_(True)
+    torch.nn.functional.conv2d(x, w * c["scale"].double().view(-1, 1, 1, 1), padding=1).backward(c["g"].double())
+    ref, mag, _ = kc.conv2d_dgrad_terms(c["g"], c["w"], c["scale"])
+    assert float((ref - x.grad.permute(0, 2, 3, 1).reshape(c["M"], Cin)).abs().max()) <= 1e-12 * float(mag.max())
+    dw, wmag, _ = c["wgrad"]
+    assert float((dw * c["scale"].double()[:, None] - w.grad.reshape(Cout, 9 * Cin)).abs().max()) <= 1e-12 * float(wmag.max()) * 2.0
+
+
+def test_integer_family_is_exact_in_fp32():
+    """The premise of the "integers" family on the CPU: an fp32 convolution of such operands equals the fp64 one exactly, in two
+    summation orders (a vendor convolution, and the tap-by-tap walk cut into three splits), and the magnitude sums stay below 2^23."""
+    for shape in kc.CONV_SHAPES[:6]:
+        c = conv_case("integers", shape)
+        B, H, W, Cin, Cout = shape
+        ref, mag, K = c["fwd"]
+        assert kc.assert_exact_in_fp32(2.0 * mag + 16.0) <= 2.0 * 16 * 9 * Cin + 16
+        f32 = torch.nn.functional.conv2d(c["x"].float(), c["w"].float(), padding=1).permute(0, 2, 3, 1).reshape(c["M"], Cout)
+        assert torch.equal(f32.double(), ref)
+        walked = conv_rows_stand_in(c["x_rows"], kc.conv_weight_rows(c["w"]), B, H, W, splits=3)
+        assert torch.equal(walked.double(), ref) and torch.equal(walked.to(BF16), ref.to(BF16))
+    with pytest.raises(AssertionError, match="no longer exact"):
+        kc.assert_exact_in_fp32(torch.tensor([2.0 ** 23]))
+
+
+def test_gemm128_splits_follows_the_dispatch_rules():
+    """The split counts the GPU test asserts per case, spelled out: (M, N, K, split_k) -> slabs."""
+    for (M, N, K, sk), want in {
+        (1, 8, 72, 0): 1, (10, 16, 216, 0): 1, (105, 24, 360, 0): 1,                  # fewer than 8 K-tiles: no automatic split
+        (270, 40, 648, 0): 2, (270, 40, 648, 2): 2, (270, 40, 648, 5): 4,             # 11 K-tiles: 6 + 5, and 3 + 3 + 3 + 2
+        (144, 136, 1728, 0): 6, (144, 136, 1728, 2): 2, (144, 136, 1728, 5): 5,       # 27 K-tiles: 5 x 5 + 2, 14 + 13, 6 x 4 + 3
+        (288, 768, 6912, 0): 16, (288, 768, 6912, 1): 1,                              # 108 K-tiles, 18 tiles: 15 x 7 + 3
+        (270, 72, 360, 2): 2, (270, 72, 360, 5): 3, (144, 192, 1224, 0): 5,           # the dgrad calls (channels swapped)
+    }.items():
+        assert kc.gemm128_splits(M, N, K, sk) == want, (M, N, K, sk)
+    # at cpt = 9 the splits of the forced 5-way request start at chunks 24, 48 and 72: two of them inside a tap
+    assert kc.split_starts_inside_a_tap(648, 72, 4) == [24, 48]
+    assert kc.split_starts_inside_a_tap(648, 72, 2) == [48]
+    assert kc.split_starts_inside_a_tap(72, 8, 2) == []
+
+
+# which seeded faults change nothing at a shape, and why -- asserted below instead of claimed
+def vacuous(fault, shape):
+    B, H, W, Cin, Cout = shape
+    M = B * H * W
+    if fault == "halo_x":
+        return H * W == 1 and B == 1                 # no other pixel exists
+    if fault == "halo_batch":
+        return B == 1                                # no second image
+    if fault == "no_flip":
+        return H * W == 1                            # only the centre tap reaches a pixel, and the flip leaves it in place
+    if fault == "drop_last_ktile":                   # every tap of the last K-tile is padding for every pixel: taps of the rows above /
+        cpt, nkt = Cin // 8, -(-9 * Cin // 64)       # below in an image one pixel high, of the columns beside in one a pixel wide
+        return all((H == 1 and t // 3 != 1) or (W == 1 and t % 3 != 1) for t in range((nkt - 1) * 8 // cpt, 9))
+    if fault == "split_tap_floor":
+        return not kc.split_starts_inside_a_tap(9 * Cin, Cin, 2)      # cpt = 1 or 2 (8 or 16 channels) divides the 8 chunks of a
+                                                                      # K-tile: every split starts on a tap boundary
+    if fault == "tail_copy":
+        return M % 8 == 0                            # no tail columns
+    return False
+
+
+FWD_FAULTS = ("halo_x", "halo_batch", "drop_last_ktile", "split_tap_floor")
+
+
+@pytest.mark.parametrize("family", kc.CONV_FAMILIES)
+@pytest.mark.parametrize("shape", kc.CONV_SHAPES, ids=CONV_IDS)
+def test_conv_forward_stand_in_and_faults(shape, family):
+    c = conv_case(family, shape)
+    B, H, W, Cin, Cout = shape
+    wk = kc.conv_weight_rows(c["w"])
+    for full in (False, True):
+        ref = fwd_reference(c, full)
+        for splits in (1, 2, 5):
+            assert accepted(family, fwd_epilogue32(conv_rows_stand_in(c["x_rows"], wk, B, H, W, splits=splits), c, full), ref), (full, splits)
+        honest = fwd_epilogue32(conv_rows_stand_in(c["x_rows"], wk, B, H, W, splits=2), c, full)
+        for fault in FWD_FAULTS:
+            bad = fwd_epilogue32(conv_rows_stand_in(c["x_rows"], wk, B, H, W, splits=2, fault=fault), c, full)
+            if vacuous(fault, shape):
+                assert torch.equal(bad, honest), f"{fault} was expected to change nothing at {shape}"
+            else:
+                assert not accepted(family, bad, ref), f"{fault} accepted at {shape}, {family}, full epilogue {full}"
+    if family == "integers" and shape == (2, 9, 15, 72, 40):
+        bad = conv_rows_stand_in(c["x_rows"], wk, B, H, W, fault="halo_x")
+        frac = float((bad.double() != c["fwd"][0]).double().mean())
+        print(f"    halo_x at {shape}: {100 * frac:.1f} % of the outputs change")
+        assert frac > 0.05
+
+
+@pytest.mark.parametrize("family", kc.CONV_FAMILIES)
+@pytest.mark.parametrize("shape", kc.CONV_SHAPES, ids=CONV_IDS)
+def test_conv_dgrad_stand_in_and_faults(shape, family):
+    """The dgrad call: the same loader over the upstream gradient (Cout channels) against W' = the re-laid-out weight, gate and
+    identity-path residual in the epilogue.  The loader's faults again, and the taps not flipped."""
+    c = conv_case(family, shape)
+    B, H, W, Cin, Cout = shape
+    ref = dgrad_reference(c)
+    for splits in (1, 2):
+        assert accepted(family, dgrad_epilogue32(conv_rows_stand_in(c["g_rows"], c["wd"], B, H, W, splits=splits), c), ref), splits
+    honest = dgrad_epilogue32(conv_rows_stand_in(c["g_rows"], c["wd"], B, H, W, splits=2), c)
+    swapped = (B, H, W, Cout, Cin)                                      # the loader sees Cout channels here
+    for fault in FWD_FAULTS + ("no_flip",):
+        if fault == "no_flip":
+            bad = conv_rows_stand_in(c["g_rows"], kc.conv_dgrad_weight_rows(c["w"], c["scale"], flip=False), B, H, W, splits=2)
+        else:
+            bad = conv_rows_stand_in(c["g_rows"], c["wd"], B, H, W, splits=2, fault=fault)
+        bad = dgrad_epilogue32(bad, c)
+        if vacuous(fault, swapped):
+            assert torch.equal(bad, honest), f"{fault} was expected to change nothing at {shape}"
+        else:
+            assert not accepted(family, bad, ref), f"{fault} accepted at {shape}, {family}"
+
+
+@pytest.mark.parametrize("family", kc.CONV_FAMILIES)
+@pytest.mark.parametrize("shape", kc.CONV_SHAPES, ids=CONV_IDS)
+def test_conv_wgrad_stand_in_and_faults(shape, family):
+    c = conv_case(family, shape)
+    B, H, W, Cin, Cout = shape
+    M = c["M"]
+    xT, gT = im2col_t_stand_in(c["x_rows"], B, H, W), transpose_stand_in(c["g_rows"])
+    assert torch.equal(xT, kc.im2col_t_reference(c["x"]))
+    ref = wgrad_reference(c)
+    assert accepted(family, wgrad_stand_in(gT, xT, c["base"], c["scale"]), ref)
+    assert not accepted(family, wgrad_stand_in(gT, xT, c["base"], c["scale"], fault="row_scale_on_base"), ref)
+    # the tail columns: the layout check is what rejects a stale tail (the other operand's zeros hide it from the GEMM) ...
+    bad = im2col_t_stand_in(c["x_rows"], B, H, W, fault="tail_copy")
+    if vacuous("tail_copy", shape):
+        assert torch.equal(bad, xT)
+    else:
+        assert not torch.equal(bad, kc.im2col_t_reference(c["x"])) and bool((bad[:, M:] != 0).any())
+        # ... unless BOTH operands keep a stale tail: then the weight gradient itself is wrong
+        gbad = gT.clone()
+        gbad[:, M:] = gbad[:, M - 1: M]
+        assert not accepted(family, wgrad_stand_in(gbad, bad, c["base"], c["scale"]), ref)
