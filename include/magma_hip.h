@@ -95,8 +95,9 @@ const char* mg_version(void);
  *  13  transformers' sampler: added mg_sample_warp_f32 (nothing moved).
  *  14  added the test probe mg_debug_mx_mfma_acc (nothing moved).
  *  15  mg_ce_reduce_f32 gained `V` (after R): a target outside [0, V) is ignored by all three cross-entropy kernels alike; before,
- *      the reduction counted every target >= 0 although mg_ce_rows_f32 / mg_ce_bwd_bf16 gave such a row loss 0 and gradient 0. */
-#define MG_ABI_VERSION 15
+ *      the reduction counted every target >= 0 although mg_ce_rows_f32 / mg_ce_bwd_bf16 gave such a row loss 0 and gradient 0.
+ *  16  token log-probabilities: added mg_token_logprobs_f32 (nothing moved). */
+#define MG_ABI_VERSION 16
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -473,6 +474,22 @@ int mg_logits_process_f32(float* logits, int64_t ld, int32_t R, int32_t V, const
                           const int32_t* eos_more, int32_t n_eos_more, void* stream);
 int mg_beam_topk_scores_f32(const float* scores, int64_t ld, int32_t R, int32_t V, const float* run, int32_t K2,
                             float* cand_score, int32_t* cand_tok, void* stream);
+
+/* Token log-probabilities (ABI 16; DESIGN.md "Token log-probabilities"; host statement: magma_amd/sampling.py, token_logprobs):
+ * how probable the model found a token, and the n_top most probable tokens beside it, in ONE enqueue-only, graph-capturable
+ * launch of one workgroup per row; no allocation, no scratch.  logits [R, ld] fp32 (columns >= V are not read), token [R] int64.
+ * Per row r, with column c = state[0] (device int32, read at run time: the step of a generate() loop) or c = 0 when state is NULL:
+ *   lp[r * ld_lp + c] = (x[t] - m) - log sum_v exp(x[v] - m), t = token[r], m the row maximum -- the arithmetic and the reduction
+ *     tree of mg_beam_topk_f32 (the same device code);
+ *   top_id / top_lp [(r * cols + c) * n_top + j], j < n_top: the n_top most probable tokens of the row, ranked by RAW LOGIT
+ *     descending, lower token id first -- reproducible from the logits alone, monotone in the log-probability, and entry 0 is what
+ *     mg_argmax_f32 selects -- each value formed by the expression of lp.
+ * n_top in [0, 20] and <= V (anything else is refused before the launch); n_top = 0 takes NULL top pointers and runs no selection
+ * pass.  c outside [0, cols) writes nothing; a token outside [0, V) gives lp = -inf and reads nothing, the lists are still written.
+ * Needs 1 <= cols <= ld_lp.                                                                                                   */
+#define MG_LOGPROBS_MAX_TOP 20
+int mg_token_logprobs_f32(const float* logits, int64_t ld, int32_t R, int32_t V, const int64_t* token, const int32_t* state,
+                          float* lp, int64_t ld_lp, int32_t cols, int32_t n_top, int32_t* top_id, float* top_lp, void* stream);
 
 /* CLIP VisionTransformer front end and attention (encoder_name "clip" = ViT-B/32; reference magma/image_encoders.py:56-63):
  *   patchify   img [B,3,H,W] bf16 NCHW -> rows [B*(H/P)*(W/P), 3*P*P] in (c, py, px) order = the im2col of the stride-P patch

@@ -528,12 +528,19 @@ namespace {
 constexpr int BK_MAX = 16;              // largest num_beams
 constexpr int BK2_MAX = 2 * BK_MAX;
 
-// PRE: the rows already hold log_softmax (and the logits processors' -inf) -- logits_process_kernel with normalize = 1 wrote
-// (x - max) - lse with the arithmetic below -- so a candidate's score is run + x.  A compile-time branch of one body: the
-// instance without PRE is the kernel as it was.
-template <bool PRE>
-MG_DEV void beam_topk_body(const float* __restrict__ logits, int64_t ld, int V, const float* __restrict__ run, int K2,
-                           float* __restrict__ cand_score, int32_t* __restrict__ cand_tok) {
+// The max / logsumexp of a vocabulary row and, from them, the top K2 entries of the row -- ONE body for the beam step's candidate
+// lists and for the token log-probabilities (mg_token_logprobs_f32), so that both form (x - max) - lse with the same arithmetic
+// and the same reduction tree.  x = the row, out_score / out_tok = the row's K2 output slots.
+// PRE: the row already holds log_softmax (and the logits processors' -inf) -- logits_process_kernel with normalize = 1 wrote
+// (x - max) - lse with the arithmetic below -- so a candidate's score is run + x.
+// RAW: the entries are ranked by the raw logit (descending, lower token first) instead of by the score, and the value written is
+// (x - max) - lse itself (no running score): the order is then a function of the logits alone.  K2 = 0: no selection pass.
+// Compile-time branches of one body: the instances without RAW are the beam kernels as they were.
+struct RowLse { float mx, lse; };
+
+template <bool PRE, bool RAW>
+MG_DEV RowLse row_topk_body(const float* __restrict__ x, int V, float r, int K2, float* __restrict__ out_score,
+                            int32_t* __restrict__ out_tok) {
   __shared__ uint32_t hist32[256];
   __shared__ float shf[ST / 64];
   __shared__ uint32_t bc[4];
@@ -541,9 +548,7 @@ MG_DEV void beam_topk_body(const float* __restrict__ logits, int64_t ld, int V, 
   __shared__ uint32_t s_key[BK2_MAX];
   __shared__ int s_idx[BK2_MAX];
   __shared__ float s_sc[BK2_MAX];
-  const int tid = threadIdx.x, row = blockIdx.x;
-  const float* x = logits + (int64_t)row * ld;
-  const float r = run[row];
+  const int tid = threadIdx.x;
 
   float mx = -INFINITY, lse = 0.f;
   if constexpr (!PRE) {
@@ -554,9 +559,16 @@ MG_DEV void beam_topk_body(const float* __restrict__ logits, int64_t ld, int V, 
     z = blk_sum(z, shf);
     lse = logf(z);
   }
+  const RowLse stat{mx, lse};
+  if (K2 <= 0) return stat;                // (uniform over the workgroup)
   auto score = [&](int i) -> float {       // log_softmax, then the running score
     if constexpr (PRE) return r + x[i];
+    else if constexpr (RAW) return (x[i] - mx) - lse;
     else return r + ((x[i] - mx) - lse);
+  };
+  auto key = [&](int i) -> uint32_t {      // what the entries are ranked by
+    if constexpr (RAW) return fkey(x[i]);
+    else return fkey(score(i));
   };
 
   // key of the K2-th largest score (MSB-first radix descent, 8 bits per level)
@@ -565,7 +577,7 @@ MG_DEV void beam_topk_body(const float* __restrict__ logits, int64_t ld, int V, 
     if (tid < 256) hist32[tid] = 0;
     __syncthreads();
     for (int i = tid; i < V; i += ST) {
-      const uint32_t k = fkey(score(i));
+      const uint32_t k = key(i);
       if ((k & mask) == prefix) atomicAdd(&hist32[(k >> shift) & 255], 1u);
     }
     __syncthreads();
@@ -589,7 +601,7 @@ MG_DEV void beam_topk_body(const float* __restrict__ logits, int64_t ld, int V, 
     uint32_t seen = 0;
     for (int base = 0; base < V; base += 64) {
       const int i = base + tid;
-      const bool eq = i < V && fkey(score(i)) == tk;
+      const bool eq = i < V && key(i) == tk;
       const unsigned long long m = __ballot(eq);
       const uint32_t c = (uint32_t)__popcll(m);
       if (seen + c > remaining) {
@@ -602,22 +614,29 @@ MG_DEV void beam_topk_body(const float* __restrict__ logits, int64_t ld, int V, 
   __syncthreads();
   const int cut = s_cut;
   for (int i = tid; i < V; i += ST) {
-    const float s = score(i);
-    const uint32_t k = fkey(s);
+    const uint32_t k = key(i);
     if (k > tk || (k == tk && i < cut)) {
       const int slot = atomicAdd(&s_n, 1);
-      if (slot < BK2_MAX) { s_key[slot] = k; s_idx[slot] = i; s_sc[slot] = s; }
+      if (slot < BK2_MAX) { s_key[slot] = k; s_idx[slot] = i; s_sc[slot] = score(i); }
     }
   }
   __syncthreads();
   const int n = min(s_n, K2);
-  if (tid < n) {      // rank by (score desc, index asc): a fixed order whatever order the atomics handed out the slots in
+  if (tid < n) {      // rank by (key desc, index asc): a fixed order whatever order the atomics handed out the slots in
     const uint32_t k = s_key[tid]; const int i = s_idx[tid];
     int rank = 0;
     for (int j = 0; j < n; ++j) rank += (s_key[j] > k || (s_key[j] == k && s_idx[j] < i)) ? 1 : 0;
-    cand_score[(int64_t)row * K2 + rank] = s_sc[tid];
-    cand_tok[(int64_t)row * K2 + rank] = i;
+    out_score[rank] = s_sc[tid];
+    out_tok[rank] = i;
   }
+  return stat;
+}
+
+template <bool PRE>
+MG_DEV void beam_topk_body(const float* __restrict__ logits, int64_t ld, int V, const float* __restrict__ run, int K2,
+                           float* __restrict__ cand_score, int32_t* __restrict__ cand_tok) {
+  const int row = blockIdx.x;
+  row_topk_body<PRE, false>(logits + (int64_t)row * ld, V, run[row], K2, cand_score + (int64_t)row * K2, cand_tok + (int64_t)row * K2);
 }
 
 __global__ __launch_bounds__(ST) void beam_topk_kernel(const float* __restrict__ logits, int64_t ld, int V,
@@ -629,6 +648,25 @@ __global__ __launch_bounds__(ST) void beam_topk_pre_kernel(const float* __restri
                                                            const float* __restrict__ run, int K2, float* __restrict__ cand_score,
                                                            int32_t* __restrict__ cand_tok) {
   beam_topk_body<true>(logits, ld, V, run, K2, cand_score, cand_tok);
+}
+
+// Token log-probabilities (DESIGN.md "Token log-probabilities"; host statement: sampling.py token_logprobs): per row the
+// log-probability of the row's token and the n_top most probable tokens, from row_topk_body's max / logsumexp -- the arithmetic
+// of the beam step -- ranked by the raw logit.  One workgroup per row; column c = state[0] of the per-step buffers (0 without a
+// state); c outside [0, cols) writes nothing; a token outside [0, V) reads nothing and gives -inf.
+__global__ __launch_bounds__(ST) void token_logprobs_kernel(const float* __restrict__ logits, int64_t ld, int V,
+                                                            const int64_t* __restrict__ token, const int32_t* __restrict__ state,
+                                                            float* __restrict__ lp, int64_t ld_lp, int cols, int n_top,
+                                                            int32_t* __restrict__ top_id, float* __restrict__ top_lp) {
+  const int row = blockIdx.x, c = state ? state[0] : 0;
+  if (c < 0 || c >= cols) return;            // (uniform over the workgroup)
+  const float* x = logits + (int64_t)row * ld;
+  const int64_t slot = ((int64_t)row * cols + c) * n_top;
+  const RowLse s = row_topk_body<false, true>(x, V, 0.f, n_top, top_lp + slot, top_id + slot);
+  if (threadIdx.x == 0) {
+    const int64_t t = token[row];
+    lp[(int64_t)row * ld_lp + c] = t >= 0 && t < V ? (x[t] - s.mx) - s.lse : -INFINITY;
+  }
 }
 
 // Logits processors (DESIGN.md "Logits processors"): the rules of transformers' RepetitionPenaltyLogitsProcessor,
@@ -909,6 +947,21 @@ extern "C" int mg_beam_topk_scores_f32(const float* scores, int64_t ld, int32_t 
     MG_FAIL(MG_ERR_SHAPE, "mg_beam_topk_scores_f32: bad scores / R / V / ld");
   if (K2 < 2 || K2 > BK2_MAX || K2 > V) MG_FAIL(MG_ERR_SHAPE, "mg_beam_topk_scores_f32: need 2 <= K2 <= min(%d, V), got %d", BK2_MAX, K2);
   hipLaunchKernelGGL(beam_topk_pre_kernel, dim3(R), dim3(ST), 0, (hipStream_t)stream, scores, ld, V, run, K2, cand_score, cand_tok);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_token_logprobs_f32(const float* logits, int64_t ld, int32_t R, int32_t V, const int64_t* token,
+                                     const int32_t* state, float* lp, int64_t ld_lp, int32_t cols, int32_t n_top, int32_t* top_id,
+                                     float* top_lp, void* stream) {
+  if (!logits || !token || !lp || R <= 0 || V <= 0 || ld < V) MG_FAIL(MG_ERR_SHAPE, "mg_token_logprobs_f32: bad logits / token / lp / R / V / ld");
+  if (cols < 1 || ld_lp < cols) MG_FAIL(MG_ERR_SHAPE, "mg_token_logprobs_f32: need 1 <= cols <= ld_lp, got %d / %lld", cols, (long long)ld_lp);
+  if (n_top < 0 || n_top > MG_LOGPROBS_MAX_TOP || n_top > V)
+    MG_FAIL(MG_ERR_SHAPE, "mg_token_logprobs_f32: need 0 <= n_top <= min(%d, V), got %d (V = %d)", MG_LOGPROBS_MAX_TOP, n_top, V);
+  if (n_top > 0 && (!top_id || !top_lp)) MG_FAIL(MG_ERR_SHAPE, "mg_token_logprobs_f32: n_top > 0 needs top_id and top_lp");
+  static_assert(MG_LOGPROBS_MAX_TOP <= BK2_MAX, "the top lists are collected in row_topk_body's slots");
+  hipLaunchKernelGGL(token_logprobs_kernel, dim3(R), dim3(ST), 0, (hipStream_t)stream, logits, ld, V, token, state, lp, ld_lp, cols,
+                     n_top, n_top > 0 ? top_id : nullptr, n_top > 0 ? top_lp : nullptr);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }

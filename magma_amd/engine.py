@@ -69,6 +69,23 @@ class KVCache:
         # position _rows_at (None: every row at self.pos), and per row the generated token not yet fed back (-1: none)
         self._rows, self._rows_at = None, 0
         self.pending = None
+        # token log-probabilities (DESIGN.md "Token log-probabilities"), beside the history: fp32 [B, Smax] log-probability of the
+        # token selected at step s, and the n_top most probable tokens of that step (int32 / fp32 [B, Smax, n_top]); allocated on
+        # first request (LMEngine._arm_logprobs), addresses and n_top are launch arguments of the captured step
+        self.lp = self.top_id = self.top_lp = None
+
+    def alloc_logprobs(self, n_top: int):
+        """The per-step log-probability buffers for ``n_top`` alternatives per token (kept when they already have that shape);
+        steps captured on other buffers are dropped."""
+        if self.lp is not None and self.lp.shape[1] == self.Smax and self.top_id.shape[2] == n_top:
+            return
+        dev = self.k.device
+        self.lp = torch.zeros(self.B, self.Smax, dtype=torch.float32, device=dev)
+        self.top_id = torch.zeros(self.B, self.Smax, n_top, dtype=torch.int32, device=dev)
+        self.top_lp = torch.zeros(self.B, self.Smax, n_top, dtype=torch.float32, device=dev)
+        if self.decode_state is not None:
+            for key in [k for k in self.decode_state.graphs if any(isinstance(e, tuple) and e[:1] == ("logprobs",) for e in k)]:
+                del self.decode_state.graphs[key]
 
     def __len__(self):
         return self.k.shape[0]
@@ -110,6 +127,8 @@ class KVCache:
         self.Smax = Smax
         self.beam = None
         self._drop_graphs()
+        if self.lp is not None:           # one column per history column
+            self.alloc_logprobs(self.top_id.shape[2])
 
     def expand(self, n: int) -> "KVCache":
         """A new cache in which every row appears n times in a row (sample-major, row b -> rows b n .. b n + n - 1): one prompt
@@ -565,7 +584,7 @@ class LMEngine:
                 output_hidden_states=False, cache_hint: Optional[int] = None, reuse_cache: bool = False,
                 return_logits: bool = False, sampling=None, eos_token: Optional[int] = None,
                 seed: Optional[int] = None, feed_back: bool = False, lengths=None, beam=None, processors=None,
-                stop=None) -> LMOutput:
+                stop=None, logprobs=None) -> LMOutput:
         """``beam`` = (num_beams, length_penalty, early_stopping, max_steps): beam-search token selection (the rows are
         samples x num_beams, sample-major; DESIGN.md "Beam search") instead of ``sampling``.
         ``processors`` (sampling.check_processor_args' dict, or None): the logits processors in front of whichever selection
@@ -574,12 +593,18 @@ class LMEngine:
         ``stop`` (sampling.check_stop_args' dict, or None): per-row stopping in the bookkeeping launch of the selection (DESIGN.md
         "Per-row stopping"); armed with ``eos_token`` (the pad id, the first eos id) on the prefill / extend call and passed
         again to every cached step; not with ``beam``.
+        ``logprobs`` (None = off, or n_top in [0, 20]): one launch between the selection and its bookkeeping writes the selected
+        token's log-probability under the RAW distribution of the step, and the n_top most probable tokens, into column
+        step of the cache's lp / top_id / top_lp buffers (DESIGN.md "Token log-probabilities"); passed like ``stop``; not with
+        ``beam``.
         ``lengths`` (int [B], 1 <= len_b <= S; prefill with use_cache=True only): the rows of ``inputs_embeds`` are prompts
         of different lengths, right-padded to S.  Row b's logits are those of its position len_b - 1, and the cache keeps one
         write position per row (len_b, then + 1 per step) -- see DESIGN.md, "Ragged batches"."""
         extending = past_key_values is not None and inputs_embeds is not None
         if stop is not None and beam is not None:
             raise NotImplementedError("per-row stopping is not combined with beam search")
+        if logprobs is not None and beam is not None:
+            raise NotImplementedError("token log-probabilities are not combined with beam search (it has its own scores)")
         if lengths is not None and (labels is not None or (past_key_values is not None and not extending) or not use_cache):
             raise ValueError("lengths= applies to the prefill call and to inputs_embeds appended to a cache (use_cache=True, no "
                              "labels); a ragged cache keeps its per-row positions for the steps that follow")
@@ -596,7 +621,7 @@ class LMEngine:
             logits, cache, full = self.extend(past_key_values, inputs_embeds, lengths=lengths, cache_hint=cache_hint)
             out = LMOutput(logits=logits.unsqueeze(1), past_key_values=cache, hidden_states=None, loss=None, full_logits=full)
             if eos_token is not None:
-                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, None, processors, stop)
+                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, None, processors, stop, logprobs)
             return out
         if past_key_values is not None:
             if not feed_back and input_ids is None:
@@ -611,12 +636,12 @@ class LMEngine:
                 rows = []
                 for i in range(T):      # only the LAST position selects a token (history / RNG step / eos latch untouched before)
                     lg, tok = self.decode(input_ids[:, i:i + 1], past_key_values, sampling=sampling, select=i == T - 1,
-                                          beam=beam, processors=processors, stop=stop)
+                                          beam=beam, processors=processors, stop=stop, logprobs=logprobs)
                     rows.append(lg.clone())
                 return LMOutput(logits=torch.stack(rows, 1), past_key_values=past_key_values, next_token=tok, loss=None,
                                 eos_state=past_key_values.sample_state)
             logits, tok = self.decode(None if feed_back else input_ids, past_key_values, sampling=sampling, beam=beam,
-                                      processors=processors, stop=stop)
+                                      processors=processors, stop=stop, logprobs=logprobs)
             return LMOutput(logits=logits.unsqueeze(1), past_key_values=past_key_values, next_token=tok, loss=None,
                             eos_state=past_key_values.sample_state)
         if inputs_embeds is None:
@@ -626,7 +651,7 @@ class LMEngine:
             # generate() only reads the last position, so only that row is computed
             out = LMOutput(logits=logits.unsqueeze(1), past_key_values=cache, hidden_states=hs, loss=None)
             if eos_token is not None:
-                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, beam, processors, stop)
+                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, beam, processors, stop, logprobs)
             return out
         x, hs = self._blocks_prefill(inputs_embeds, None, output_hidden_states)
         B, S, _ = inputs_embeds.shape
@@ -696,7 +721,28 @@ class LMEngine:
             cache.stop_table.copy_(ops.stop_table(stop[0], stop[1]), non_blocking=True)
             cache.stop_held = tuple(stop)
 
-    def _arm_first_token(self, out: LMOutput, logits, cache: KVCache, eos_token, seed, sampling, beam, processors=None, stop=None):
+    def logprob_mode(self, logprobs):
+        """None (nothing is launched or allocated) or n_top, the number of alternatives per token: the log-probability mode that
+        travels beside the selection mode."""
+        if logprobs is None:
+            return None
+        n = logprobs
+        if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= ops.LOGPROBS_MAX_TOP or n > self.V:
+            raise ValueError(f"logprobs must be None or an integer in [0, min({ops.LOGPROBS_MAX_TOP}, V = {self.V})], got {n!r}")
+        return n
+
+    def _arm_logprobs(self, cache: KVCache, st, n_top, proc):
+        """The buffers of the log-probability mode (never allocated inside a captured step: decode() calls this before it captures
+        or replays): the cache's per-step outputs and, when the logits processors run too, the decode state's second logits
+        buffer -- the processors and the selection work on a copy, the log-probabilities read the raw row."""
+        if n_top is None:
+            return
+        cache.alloc_logprobs(n_top)
+        if proc is not None and st.logits_proc is None:
+            st.logits_proc = torch.empty_like(st.logits)
+
+    def _arm_first_token(self, out: LMOutput, logits, cache: KVCache, eos_token, seed, sampling, beam, processors=None, stop=None,
+                         logprobs=None):
         """generate(): the first token of the loop selected from the prefill / extend logits, device-side bookkeeping armed."""
         if cache.eos != int(eos_token):        # the eos id is a launch argument of the captured bookkeeping kernel
             cache.eos = int(eos_token)
@@ -716,16 +762,19 @@ class LMEngine:
             for key in [k for k in st.graphs if isinstance(k[0], tuple) and k[0][:1] == ("beam",)]:
                 del st.graphs[key]
         proc = self.proc_mode(processors)
+        raw = logits
         if proc is not None:       # step 0 of the rules on a copy: the caller's .logits stay raw
             self._arm_processors(cache, proc)
             logits = logits.clone()
+        n_top = self.logprob_mode(logprobs)       # (forward has refused the combination with beam)
+        self._arm_logprobs(cache, st, n_top, proc)
         stop = self.stop_mode(stop)
         if stop is not None:       # every row unfinished again
             if int(eos_token) != stop[0][0]:
                 raise ValueError(f"per-row stopping pads with the first eos id: eos_token must be {stop[0][0]}, got {eos_token}")
             self._arm_stop(cache, stop)
             cache.finish.copy_(torch.tensor([[-1, 0]] * cache.B, dtype=torch.int32), non_blocking=True)
-        out["next_token"] = self.select_token(logits, cache, mode, out=st.token, proc=proc, stop=stop)
+        out["next_token"] = self.select_token(logits, cache, mode, out=st.token, proc=proc, stop=stop, logprobs=n_top, raw=raw)
         out["eos_state"] = cache.sample_state
 
     def embed_ids(self, ids: torch.Tensor) -> torch.Tensor:
@@ -971,6 +1020,7 @@ class LMEngine:
         st.lnf = e(B, d)
         st.ad_ln = e(B, d)                 # LayerNorm output in front of an adapter built with add_layernorm
         st.logits = e(B, self.Vp, dt=torch.float32)
+        st.logits_proc = None      # with logprobs AND processors: the copy the processors and the selection work on (_arm_logprobs)
         st.token = torch.zeros(B, dtype=torch.int64, device=dev)
         st.graphs = {}             # (token-selection mode, feed_back[, processor values]) -> captured hipGraph
         st.steps = 0
@@ -1020,7 +1070,8 @@ class LMEngine:
         return toks.clone(), bm.fin_score.view(bm.B, bm.k)[:, :n_ret].reshape(-1).clone(), lens
 
     def select_token(self, logits: torch.Tensor, cache: KVCache, mode, out: Optional[torch.Tensor] = None,
-                     advance: bool = False, clear: Optional[torch.Tensor] = None, proc=None, stop=None) -> torch.Tensor:
+                     advance: bool = False, clear: Optional[torch.Tensor] = None, proc=None, stop=None, logprobs=None,
+                     raw: Optional[torch.Tensor] = None) -> torch.Tensor:
         """next token of every row from fp32 logits (B, V): greedy argmax (mode None; reference sampling.py:96-97) or the
         sampled branch (mode = (temperature, top_k, top_p); :99-107 -- or ("warp", temperature, top_k, top_p, min_p):
         transformers' sampler, sample_mode), then the loop bookkeeping in one small launch
@@ -1030,7 +1081,10 @@ class LMEngine:
         ``proc`` (proc_mode; the ids already in cache.suppress, _arm_processors): the logits processors, one launch IN PLACE on
         ``logits`` immediately before the selection -- on the raw logits, or as log_softmax + rules in front of the beam step.
         ``stop`` (stop_mode; the table already in cache.stop_table, _arm_stop): the bookkeeping launch is the per-row one
-        (ops.sample_finish_rows) -- a finished row's token becomes the pad id in place --, and min_new_tokens bans every eos id."""
+        (ops.sample_finish_rows) -- a finished row's token becomes the pad id in place --, and min_new_tokens bans every eos id.
+        ``logprobs`` (logprob_mode; the buffers already allocated, _arm_logprobs): one launch AFTER the selection and BEFORE the
+        bookkeeping -- which advances the step the launch reads its column from and overwrites a finished row's token -- writes the
+        token's log-probability and the n_top alternatives of ``raw`` (default ``logits``): the rows as they were before ``proc``."""
         is_beam = isinstance(mode, tuple) and bool(mode) and mode[0] == "beam"
         if proc is not None:
             more = {} if stop is None or len(stop[0]) < 2 else dict(eos_more=cache.stop_table[1:ops.STOP_MAX_EOS],
@@ -1046,6 +1100,9 @@ class LMEngine:
             tok = ops.sample_warp(logits, mode[1], mode[2], mode[3], mode[4], cache.seed, cache.sample_state, out=out)
         else:
             tok = ops.sample(logits, mode[0], mode[1], mode[2], cache.seed, cache.sample_state, out=out)
+        if logprobs is not None:
+            ops.token_logprobs(logits if raw is None else raw, tok, cache.lp, cache.top_id if logprobs else None,
+                               cache.top_lp if logprobs else None, state=cache.sample_state)
         if stop is not None:
             ops.sample_finish_rows(tok, cache.sample_state, cache.stop_table, len(stop[0]), len(stop[1]), stop[0][0], cache.finish,
                                    d_pos=cache.d_pos if advance else None, history=cache.history, clear=clear,
@@ -1055,7 +1112,7 @@ class LMEngine:
                           clear=clear, clear_stride=16 if clear is not None else 1, pos_stride=cache.pos_stride)
         return tok
 
-    def _decode_step(self, cache: KVCache, st, mode=None, feed_back: bool = False, proc=None, stop=None):
+    def _decode_step(self, cache: KVCache, st, mode=None, feed_back: bool = False, proc=None, stop=None, logprobs=None):
         """Enqueue one token step for all B sequences (graph-capturable: no
         allocation, no sync, position read from cache.d_pos on the device): embedding, per layer the launch sequence of the
         kind planned for it (st.kinds, _ensure_decode_state), the head, token selection.
@@ -1075,8 +1132,15 @@ class LMEngine:
             ops.gemm_skinny(x, head, out=st.logits, ln_fold=(head.colsum, self.d, self.eps))
         if mode == "noselect":
             ops.advance_pos(cache.d_pos, pos_stride=cache.pos_stride)   # teacher-forced position: nothing selected, nothing recorded
+        elif logprobs is not None and proc is not None:
+            # the processors run in place: they and the selection get a copy (one device copy inside the step), the
+            # log-probabilities read the untouched st.logits
+            st.logits_proc.copy_(st.logits)
+            self.select_token(st.logits_proc[:, : self.V], cache, mode, out=st.token, advance=True, proc=proc, stop=stop,
+                              logprobs=logprobs, raw=st.logits[:, : self.V])
         else:
-            self.select_token(st.logits[:, : self.V], cache, mode, out=st.token, advance=True, proc=proc, stop=stop)
+            self.select_token(st.logits[:, : self.V], cache, mode, out=st.token, advance=True, proc=proc, stop=stop,
+                              logprobs=logprobs)
 
     # One method per block kind (_block_kind): x -> xn for layer li.  ``src`` holds the block's weight-streaming operands: the
     # layer itself, or its e4m3 / MXFP4 copies (ly.w8 / ly.w4) under W8A16 / W4A16 -- the same launches.  On a ragged cache (pos_stride 1) every
@@ -1205,7 +1269,7 @@ class LMEngine:
         return st
 
     def decode(self, input_ids: Optional[torch.Tensor], cache: KVCache, use_graph: bool = True, sampling=None, select: bool = True,
-               beam=None, processors=None, stop=None):
+               beam=None, processors=None, stop=None, logprobs=None):
         """One cached step.  Returns (fp32 logits (B,V) view, selected token (B,) view: greedy, or sampled when
         ``sampling = (temperature, top_k, top_p)`` or ``("warp", temperature, top_k, top_p, min_p)``, sample_mode); both are
         overwritten by the next step.  ``input_ids=None`` feeds the
@@ -1215,7 +1279,9 @@ class LMEngine:
         ``processors`` (forward): the logits processors run in place on the step's logits before the selection, so the
         returned logits are then the PROCESSED ones (beam search: the processed log_softmax scores).
         ``stop`` (forward): per-row stopping -- the cache must have been armed with it (its finish record reset) by the prefill /
-        extend call; the returned token view holds the pad id for rows that had finished."""
+        extend call; the returned token view holds the pad id for rows that had finished.
+        ``logprobs`` (forward): the step also writes column step of the cache's log-probability buffers, from the RAW logits; with
+        ``processors`` too, those and the selection run on a second buffer, whose rows are what is returned."""
         if cache.pos >= cache.Smax:
             raise ValueError(f"KV cache full (Smax={cache.Smax}); pass a larger cache_hint / max_steps")
         if cache.B > 16:
@@ -1251,26 +1317,32 @@ class LMEngine:
             if cache.finish is None:
                 raise ValueError("per-row stopping needs a cache armed for it (prefill with eos_token= and stop=)")
             self._arm_stop(cache, stop)
+        n_top = self.logprob_mode(logprobs) if select else None
+        if n_top is not None and beam is not None:
+            raise NotImplementedError("token log-probabilities are not combined with beam search")
+        self._arm_logprobs(cache, st, n_top, proc)
         key = (mode, feed_back)
         if proc is not None:        # the values are launch arguments of the captured step (the suppress ids are not: their count is)
             key += (tuple(proc[:3]) + (len(proc[3]),),)
         if stop is not None:        # the counts and the pad id are launch arguments, the table's contents are not
             key += (("stop", len(stop[0]), len(stop[1]), stop[0][0]),)
+        if n_top is not None:       # n_top and the buffers' addresses are launch arguments
+            key += (("logprobs", n_top),)
         if not use_graph:
-            self._decode_step(cache, st, mode, feed_back, proc, stop)
+            self._decode_step(cache, st, mode, feed_back, proc, stop, n_top)
         elif key in st.graphs:
             st.graphs[key].replay()
         elif st.steps == 0:
-            self._decode_step(cache, st, mode, feed_back, proc, stop)    # first step eager (loads code objects)
+            self._decode_step(cache, st, mode, feed_back, proc, stop, n_top)    # first step eager (loads code objects)
         else:
             g = torch.cuda.CUDAGraph()            # hipGraph on ROCm
             with torch.cuda.graph(g):
-                self._decode_step(cache, st, mode, feed_back, proc, stop)
+                self._decode_step(cache, st, mode, feed_back, proc, stop, n_top)
             st.graphs[key] = g
             g.replay()
         st.steps += 1
         cache.pos += 1
-        return st.logits[:, : self.V], st.token
+        return (st.logits_proc if n_top is not None and proc is not None else st.logits)[:, : self.V], st.token
 
     # ------------------------------------------------- loss (eval) forward
     def forward_loss(self, embeds: torch.Tensor, labels: torch.Tensor, want_hidden=False, want_logits=False) -> LMOutput:
@@ -1281,21 +1353,53 @@ class LMEngine:
         B, S, _ = embeds.shape
         x, hs = self._blocks_prefill(embeds, None, want_hidden)
         labels = labels.to(self.device)
-        tgt = labels[:, 1:].reshape(-1)
-        rows = (torch.arange(B, device=self.device)[:, None] * S + torch.arange(S - 1, device=self.device)[None, :]).reshape(-1)
-        keep = (tgt != -100).nonzero().squeeze(1)           # host sync: index plumbing only
-        if keep.numel() == 0:
+        head = self._target_logits(x, S, labels[:, 1:])
+        if head is None:
             return LMOutput(loss=torch.full((), float("nan"), device=self.device), logits=None, hidden_states=hs,
                             past_key_values=None)
-        kept = tgt[keep].contiguous()
+        target_rows, kept, target_logits = head
+        loss, _ = ops.cross_entropy(target_logits, kept)
+        # reference magma.py:270-276 .logits: (B, S, V) over every position -- on request now, otherwise on first access
+        full = (self._full_logits(x, B * S).view(B, S, self.V) if want_logits
+                else LMOutput.lazy(lambda: self._full_logits(x, B * S).view(B, S, self.V)))
+        return LMOutput(loss=loss, logits=full, hidden_states=hs, past_key_values=None,
+                        target_rows=target_rows, target_logits=target_logits)
+
+    def _target_logits(self, x: torch.Tensor, S: int, tgt: torch.Tensor):
+        """ln_f and the fp32 head on the rows that predict a target, the ONE row selection of forward_loss and score.  ``x``
+        (B * S, d) the blocks' output; ``tgt`` (B, n <= S) int64 on the device: the token position s of row b predicts, -100 for
+        none.  Returns (rows of x [n_kept] in (b, s) order, their targets [n_kept], logits (n_kept, V) fp32 view), or None when no
+        position carries a target.  Targets outside [0, V) raise (ops.refuse_targets_outside)."""
+        B, n = tgt.shape
+        flat = tgt.reshape(-1)
+        rows = (torch.arange(B, device=self.device)[:, None] * S + torch.arange(n, device=self.device)[None, :]).reshape(-1)
+        keep = (flat != -100).nonzero().squeeze(1)           # host sync: index plumbing only
+        if keep.numel() == 0:
+            return None
+        kept = flat[keep].contiguous()
         ops.refuse_targets_outside(kept, self.V)            # one more two-element device-to-host copy, next to the sync ``keep`` paid
         xr = x.index_select(0, rows[keep])
         xl = ops.layernorm(xr, self.lnf_g, self.lnf_b, self.eps)
         logits = torch.empty(xl.shape[0], self.Vp, dtype=torch.float32, device=self.device)
         ops.gemm(xl, self.head, out=logits)
-        loss, _ = ops.cross_entropy(logits[:, : self.V], kept)
-        # reference magma.py:270-276 .logits: (B, S, V) over every position -- on request now, otherwise on first access
-        full = (self._full_logits(x, B * S).view(B, S, self.V) if want_logits
-                else LMOutput.lazy(lambda: self._full_logits(x, B * S).view(B, S, self.V)))
-        return LMOutput(loss=loss, logits=full, hidden_states=hs, past_key_values=None,
-                        target_rows=rows[keep], target_logits=logits[:, : self.V])
+        return rows[keep], kept, logits[:, : self.V]
+
+    def score(self, embeds: torch.Tensor, tgt: torch.Tensor, n_top: int = 0):
+        """Log-probabilities of given tokens (Magma.score; DESIGN.md "Token log-probabilities"): one cache-less forward over
+        ``embeds`` (B, S, d), the fp32 head on the rows that predict a target (``tgt`` (B, S) int64: the token position s of row
+        b predicts, -100 for none; _target_logits), then the kernel of the generate() loop without a step counter.  Returns device
+        tensors in (b, s) order of the targets: (log-probabilities [n], top ids [n, n_top] int32, their log-probabilities
+        [n, n_top])."""
+        n_top = self.logprob_mode(n_top)
+        B, S, _ = embeds.shape
+        x, _ = self._blocks_prefill(embeds, None)
+        head = self._target_logits(x, S, tgt.to(self.device))
+        if head is None:
+            raise ValueError("score: no position carries a target")
+        _, kept, logits = head
+        n = kept.numel()
+        lp = torch.empty(n, 1, dtype=torch.float32, device=self.device)
+        top_id = torch.empty(n, 1, n_top, dtype=torch.int32, device=self.device)
+        top_lp = torch.empty(n, 1, n_top, dtype=torch.float32, device=self.device)
+        ops.token_logprobs(logits, kept, lp, top_id if n_top else None, top_lp if n_top else None)
+        return lp[:, 0], top_id[:, 0], top_lp[:, 0]

@@ -281,7 +281,8 @@ class Magma(nn.Module):
                  early_stopping=False, num_return_sequences: int = 1, return_scores: bool = False, past_key_values=None,
                  return_past_key_values: bool = False, *, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
                  min_new_tokens: int = 0, suppress_tokens=None, eos_token=None, stop_sequences=None, stop_per_row: bool = None,
-                 return_finish: bool = False, sampler: str = "reference", min_p: float = 0.0):
+                 return_finish: bool = False, sampler: str = "reference", min_p: float = 0.0, return_logprobs: bool = False,
+                 top_logprobs: int = 0):
         """reference magma.py:214-236 (+ stop_on_eos / seed / eos_check_every / lengths, see sampling.generate).
         ``lengths``: prompts of different lengths, right-padded (embed_batch); ``embeddings`` may also be a list of
         per-sample (1, s_i, d) tensors.  ``num_beams`` > 1: beam search (length_penalty, early_stopping,
@@ -293,7 +294,9 @@ class Magma(nn.Module):
         matched over token ids) / ``stop_per_row`` / ``return_finish``: per-row stopping as in transformers -- a finished row is
         padded and stays finished, the call ends when every row is finished (see sampling.generate).
         ``sampler="transformers"``: temperature, top-k, nucleus top-p and ``min_p`` as transformers' warpers apply them, instead of
-        the reference's filters (see sampling.generate)."""
+        the reference's filters (see sampling.generate).
+        ``return_logprobs`` / ``top_logprobs`` (0 to 20 alternatives per token): a ``TokenLogprobs`` appended to the result -- every
+        generated token's log-probability under the raw model distribution, as ``score`` gives it (see sampling.generate)."""
         torch.cuda.set_device(self.device)
         return generate(self, embeddings=embeddings, max_steps=max_steps, temperature=temperature, top_k=top_k,
                         top_p=top_p, decode=decode, stop_on_eos=stop_on_eos, seed=seed, eos_check_every=eos_check_every,
@@ -303,7 +306,69 @@ class Magma(nn.Module):
                         repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
                         min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens, eos_token=eos_token,
                         stop_sequences=stop_sequences, stop_per_row=stop_per_row, return_finish=return_finish, sampler=sampler,
-                        min_p=min_p)
+                        min_p=min_p, return_logprobs=return_logprobs, top_logprobs=top_logprobs)
+
+    @torch.no_grad()
+    def score(self, embeddings, targets, lengths=None, *, top_logprobs: int = 0):
+        """How probable the model finds GIVEN tokens after a prompt (DESIGN.md "Token log-probabilities"): ranking candidate
+        answers, per-caption perplexity (``exp(-logprobs.sum(1) / count)``).  ``embeddings`` is what ``generate`` takes as a
+        prompt: (B, S, d) with optional ``lengths``, a list of per-sample tensors, or embed_batch's pair.  ``targets``: int64
+        (B, T) right-padded with -100, or a list of id lists; at least one id per row, every id in [0, V).  One cache-less
+        forward over [prompt_b ; wte(targets_b[:-1])], right-padded; the fp32 head runs only on the rows that predict a target.
+        Returns a ``TokenLogprobs`` over the T columns: ``logprobs[b, j]`` = log p(targets_b[j] | prompt_b, targets_b[:j]) under
+        the raw model distribution -- what ``generate(return_logprobs=True)`` reports for a token it selected --, the
+        ``top_logprobs`` most probable tokens at every position, ``count[b]`` = the row's number of targets; positions past it
+        hold 0.0 / -1 / -inf.  Scoring against a KV cache is not supported."""
+        from . import ops
+        from .engine import LMEngine
+        from .sampling import check_logprob_args, is_embed_batch, mask_logprobs, pad_ragged
+        torch.cuda.set_device(self.device)
+        eng = self.lm.engine
+        n_top = check_logprob_args(True, top_logprobs, eng.V)
+        if is_embed_batch(embeddings):
+            embeddings, lengths = embeddings
+        if isinstance(embeddings, (list, tuple)):
+            embeddings, lengths = pad_ragged(embeddings)
+        B, S, d = embeddings.shape
+        lens = LMEngine.check_lengths(lengths, B, S) if lengths is not None else torch.full((B,), S, dtype=torch.int64)
+        if torch.is_tensor(targets):
+            t = targets.detach().to("cpu")
+            if t.ndim != 2 or t.shape[0] != B or t.is_floating_point() or t.dtype == torch.bool:
+                raise ValueError(f"targets must be integers of shape ({B}, T), got {t.dtype} {tuple(t.shape)}")
+            rows = []
+            for r in t.to(torch.int64).tolist():
+                n = sum(1 for v in r if v != -100)
+                if any(v == -100 for v in r[:n]):
+                    raise ValueError("targets must be right-padded with -100 (an ignored position in front of a target)")
+                rows.append(r[:n])
+        else:
+            if len(targets) != B:
+                raise ValueError(f"{len(targets)} target rows for {B} prompts")
+            rows = [[int(v) for v in (r.tolist() if torch.is_tensor(r) else r)] for r in targets]
+        if any(len(r) < 1 for r in rows):
+            raise ValueError("every row needs at least one target id")
+        ops.refuse_targets_outside(torch.tensor([v for r in rows for v in r], dtype=torch.int64), eng.V)
+        count = torch.tensor([len(r) for r in rows], dtype=torch.int64)
+        total = lens + count - 1
+        n_pos = self.lm.config.max_position_embeddings
+        if int(total.max()) > n_pos:
+            raise ValueError(f"prompt plus targets reach {int(total.max())} positions, beyond max_position_embeddings = {n_pos}")
+        W, T = int(total.max()), int(count.max())
+        emb = torch.zeros(B, W, d, dtype=self.dtype, device=self.device)
+        tgt = torch.full((B, W), -100, dtype=torch.int64)
+        tokens = torch.full((B, T), -100, dtype=torch.int64)
+        for b, r in enumerate(rows):
+            L = int(lens[b])
+            emb[b, :L] = embeddings[b, :L]
+            if len(r) > 1:
+                ops.embedding(torch.tensor([r[:-1]], dtype=torch.int64, device=self.device), eng.wte, emb[b:b + 1], row_off=L)
+            tgt[b, L - 1: L - 1 + len(r)] = torch.tensor(r, dtype=torch.int64)
+            tokens[b, : len(r)] = torch.tensor(r, dtype=torch.int64)
+        lp, top_id, top_lp = (v.cpu() for v in eng.score(emb, tgt, n_top))
+        at = torch.arange(T)[None, :] < count[:, None]            # (b, j) order = the order of the kept rows
+        out_lp, out_id, out_tl = torch.zeros(B, T), torch.zeros(B, T, n_top, dtype=torch.int64), torch.zeros(B, T, n_top)
+        out_lp[at], out_id[at], out_tl[at] = lp, top_id.to(torch.int64), top_lp
+        return mask_logprobs(tokens, out_lp, out_id, out_tl, count)
 
     @torch.no_grad()
     def cache_prompt(self, embeddings, lengths=None, cache_hint: int = 256):

@@ -770,6 +770,38 @@ def beam_topk(logits: torch.Tensor, run: torch.Tensor, cand_score: torch.Tensor,
                                   cand_score.data_ptr(), cand_tok.data_ptr(), _stream()), name)
 
 
+LOGPROBS_MAX_TOP = 20                                                   # include/magma_hip.h MG_LOGPROBS_MAX_TOP
+
+
+def token_logprobs(logits: torch.Tensor, token: torch.Tensor, lp: torch.Tensor, top_id: Optional[torch.Tensor] = None,
+                   top_lp: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None):
+    """Per row of the fp32 ``logits`` (R, V): log_softmax(logits[r])[token[r]] into column c of ``lp`` (R, cols) fp32 -- c =
+    ``state[0]`` (device int32, read at run time) or 0 without a state -- and, when ``top_id`` (R, cols, n_top) int32 /
+    ``top_lp`` (R, cols, n_top) fp32 are given, the row's n_top most probable tokens into [r, c, :], ranked by raw logit descending,
+    lower id first (mg_token_logprobs_f32; host statement: sampling.token_logprobs).  c >= cols writes nothing; a token outside
+    [0, V) gives -inf.  n_top must lie in [0, 20] and not exceed V.  Enqueue-only."""
+    _need_gpu(logits, token, lp, top_id, top_lp, state)
+    assert logits.dtype == torch.float32 and logits.ndim == 2 and logits.stride(1) == 1
+    R, V = logits.shape
+    assert token.dtype == torch.int64 and token.is_contiguous() and token.numel() == R
+    assert lp.dtype == torch.float32 and lp.ndim == 2 and lp.shape[0] == R and lp.shape[1] >= 1
+    assert lp.stride(1) == 1 and (R == 1 or lp.stride(0) >= lp.shape[1])
+    cols = lp.shape[1]
+    assert (top_id is None) == (top_lp is None), "top_id and top_lp come together"
+    n_top = 0
+    if top_id is not None:
+        assert top_id.dtype == torch.int32 and top_lp.dtype == torch.float32 and top_id.is_contiguous() and top_lp.is_contiguous()
+        assert top_id.ndim == 3 and top_id.shape[:2] == (R, cols) and top_lp.shape == top_id.shape
+        n_top = top_id.shape[2]
+    if state is not None:
+        assert state.dtype == torch.int32 and state.numel() >= 1
+    check(L.load().mg_token_logprobs_f32(logits.data_ptr(), logits.stride(0), R, V, token.data_ptr(), _p(state), lp.data_ptr(),
+                                         lp.stride(0) if R > 1 else max(lp.stride(0), cols), cols, n_top,
+                                         _p(top_id) if n_top else None, _p(top_lp) if n_top else None, _stream()),
+          "mg_token_logprobs_f32")
+    return lp
+
+
 EARLY_STOPPING_CODES = {False: 0, True: 1, "never": 2}
 
 

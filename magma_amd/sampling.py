@@ -337,6 +337,60 @@ def finish_from_record(record, n_gen: int) -> Finish:
     return Finish(kept, reason, index)
 
 
+MAX_TOP_LOGPROBS = 20
+
+
+class TokenLogprobs(NamedTuple):
+    """Per-token log-probabilities of a generate() call (``return_logprobs=True``) or of Magma.score(): CPU tensors over the n
+    generated (scored) columns.  Positions at or past ``count[b]`` hold 0.0 / -1 / -inf."""
+    tokens: torch.Tensor        # int64 [B, n]
+    logprobs: torch.Tensor      # fp32 [B, n]: log p(tokens[b, i]) under the raw model distribution of that step
+    top_ids: torch.Tensor       # int64 [B, n, k]: the k most probable tokens of the step (raw logit descending, lower id first)
+    top_logprobs: torch.Tensor  # fp32 [B, n, k]
+    count: torch.Tensor         # int64 [B]: the positions of the row that count
+
+
+def check_logprob_args(return_logprobs=False, top_logprobs=0, vocab: int = None):
+    """ValueError for log-probability arguments generate() / score() do not take.  Returns None (off: nothing is launched or
+    allocated) or n_top, the number of alternatives per token (0: the token's own log-probability only)."""
+    k = top_logprobs
+    if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= MAX_TOP_LOGPROBS:
+        raise ValueError(f"top_logprobs must be an integer in [0, {MAX_TOP_LOGPROBS}], got {k!r}")
+    if vocab is not None and k > vocab:
+        raise ValueError(f"top_logprobs = {k} exceeds the vocabulary (V = {vocab})")
+    if not isinstance(return_logprobs, bool):
+        raise ValueError(f"return_logprobs must be True or False, got {return_logprobs!r}")
+    return k if (return_logprobs or k > 0) else None
+
+
+def token_logprobs(logits, tokens, n_top: int = 0):
+    """Token log-probabilities, host statement (the device kernel is csrc/sampling.hip, token_logprobs_kernel) in float64:
+    ``logits`` (R, V), ``tokens`` (R,) -> (log_softmax(logits)[r, tokens[r]] (R,) -- -inf for a token outside [0, V) --,
+    top ids (R, n_top) int64 -- a STABLE descending sort of the logits: raw logit descending, lower id first --, their
+    log-probabilities (R, n_top)), both values float64."""
+    x = torch.as_tensor(logits).detach().cpu().to(torch.float64)
+    t = torch.as_tensor(tokens).detach().cpu().to(torch.int64).view(-1)
+    R, V = x.shape
+    if not 0 <= int(n_top) <= min(MAX_TOP_LOGPROBS, V):
+        raise ValueError(f"n_top must lie in [0, min({MAX_TOP_LOGPROBS}, V = {V})], got {n_top!r}")
+    ls = F.log_softmax(x, dim=-1)
+    ok = (t >= 0) & (t < V)
+    lp = torch.where(ok, ls.gather(1, t.clamp(0, V - 1)[:, None])[:, 0], torch.full((R,), float("-inf"), dtype=torch.float64))
+    ids = torch.sort(x, dim=-1, descending=True, stable=True)[1][:, : int(n_top)]
+    return lp, ids, ls.gather(1, ids)
+
+
+def mask_logprobs(tokens, lp, top_ids, top_lp, count) -> TokenLogprobs:
+    """The result type from per-step values: positions at or past count[b] become 0.0 / -1 / -inf."""
+    count = torch.as_tensor(count).to(torch.int64).cpu().view(-1)
+    lp, top_ids, top_lp = lp.cpu().float().clone(), top_ids.cpu().to(torch.int64).clone(), top_lp.cpu().float().clone()
+    gone = torch.arange(lp.shape[1])[None, :] >= count[:, None]
+    lp[gone] = 0.0
+    top_ids[gone] = -1
+    top_lp[gone] = float("-inf")
+    return TokenLogprobs(tokens.cpu().to(torch.int64).clone(), lp, top_ids, top_lp, count)
+
+
 MAX_BEAMS = 16
 
 
@@ -497,7 +551,8 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
              num_return_sequences: int = 1, return_scores: bool = False, past_key_values=None,
              return_past_key_values: bool = False, *, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
              min_new_tokens: int = 0, suppress_tokens=None, stop_sequences=None, stop_per_row: bool = None,
-             return_finish: bool = False, sampler: str = "reference", min_p: float = 0.0) -> Union[List[str], torch.Tensor]:
+             return_finish: bool = False, sampler: str = "reference", min_p: float = 0.0, return_logprobs: bool = False,
+             top_logprobs: int = 0) -> Union[List[str], torch.Tensor]:
     """reference sampling.py:43-121.  Token selection (argmax, or top-k / the reference's top-p rule / softmax /
     multinomial) and the ``(next_token == eos).all()`` test run on the device inside the captured token step; the host
     reads the recorded "first all-eos step" every ``eos_check_every`` steps (default 8, MAGMA_EOS_CHECK_EVERY) instead of
@@ -571,6 +626,10 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     if (stop is not None or return_finish) and (num_beams > 1 or return_scores):
         raise NotImplementedError("per-row stopping (a list of eos ids, stop_sequences, stop_per_row, return_finish) is not "
                                   "combined with beam search (num_beams > 1 / return_scores=True)")
+    n_top = check_logprob_args(return_logprobs, top_logprobs, _logit_count(model))
+    if n_top is not None and (num_beams > 1 or return_scores):
+        raise NotImplementedError("token log-probabilities (return_logprobs / top_logprobs) are not combined with beam search "
+                                  "(num_beams > 1 / return_scores=True): it has its own scores")
     eos_ids = stop["eos_ids"] if stop is not None else (eos_token,)
     eos_token = eos_ids[0]              # the pad id
     continuing = past_key_values is not None or return_past_key_values
@@ -626,6 +685,9 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     if on_device and stop is not None:      # only then, as above
         from .engine import LMEngine
         first_kw["stop"] = step_kw["stop"] = LMEngine.stop_mode(stop)
+    if on_device and n_top is not None:     # only then, as above
+        first_kw["logprobs"] = step_kw["logprobs"] = n_top
+    host_lp = [] if n_top is not None and not on_device else None      # per step (lp, top ids, top lp) of the host statement
     if not on_device and stop is not None:
         done, record = torch.zeros(b, dtype=torch.bool), torch.tensor([[-1, 0]] * b, dtype=torch.int64).view(b, 2)
     if past_key_values is not None:
@@ -653,6 +715,7 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
                     break
             continue
         logits = outputs.logits[:, -1, :].float()            # any other LM object: the reference's host-side arithmetic
+        raw = logits
         if proc is not None:
             logits = process_logits(logits.cpu(), out[:, s:n].cpu(), n - s, eos_token=eos_ids if stop is not None else eos_token,
                                     **proc).to(logits.device)
@@ -668,6 +731,8 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
                 logits = top_p_filter(logits, threshold=top_p)
             probs = F.softmax(logits / temperature, dim=-1)
             next_token = torch.multinomial(probs, num_samples=1)
+        if host_lp is not None:     # of the raw distribution, for the token as selected (a finished row's is masked at the end)
+            host_lp.append(token_logprobs(raw, next_token.view(-1), n_top))
         if stop is not None:        # the per-row rule (stop_update): finished rows are padded, the others tested
             next_token = torch.where(done.to(next_token.device)[:, None], torch.full_like(next_token, eos_token), next_token)
             out[:, n:n + 1] = next_token
@@ -691,13 +756,24 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
         out.scatter_(1, lens + torch.arange(n_gen, device=dev)[None, :], past.history[:, :n_gen])
     elif on_device:          # one copy of the token history the bookkeeping kernel kept
         out[:, s:n] = past.history[:, : n - s]
+    gen_tokens = past.history[:, : n - s] if on_device and past is not None else out[:, s:n]      # the generated columns
     out = out[:, :n]
     finish = None
-    if stop is not None and (return_finish or continuing or decode):
+    if stop is not None and (return_finish or continuing or decode or (n_top is not None and n > s)):
         record = past.finish.cpu() if on_device else record           # one host copy
         finish = finish_from_record(record, n - s)
     elif return_finish:                                               # the reference's rule: every row ran the whole call
         finish = finish_from_record(torch.tensor([[-1, 0]] * b).view(b, 2), n - s)
+    logprobs = None
+    if n_top is not None:       # one copy of what the steps wrote (or the host statement's values), masked past every row's count
+        n_gen = n - s
+        if n_gen == 0:
+            vals = (torch.zeros(b, 0), torch.zeros(b, 0, n_top, dtype=torch.int64), torch.zeros(b, 0, n_top))
+        elif on_device:
+            vals = (past.lp[:, :n_gen], past.top_id[:, :n_gen], past.top_lp[:, :n_gen])
+        else:
+            vals = tuple(torch.stack([h[j] for h in host_lp[:n_gen]], 1) for j in range(3))
+        logprobs = mask_logprobs(gen_tokens, *vals, finish.kept if finish is not None else torch.full((b,), n_gen))
     if continuing:      # the cache keeps the conversation (a continued one too: it was advanced in place and stays continuable)
         if past_key_values is None:
             start = lengths if lengths is not None else torch.full((b,), s, dtype=torch.int64)
@@ -720,6 +796,8 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     ret = (out, past) if return_past_key_values else (out,)
     if return_finish:
         ret += (finish,)
+    if n_top is not None:
+        ret += (logprobs,)
     return ret if len(ret) > 1 else ret[0]
 
 
