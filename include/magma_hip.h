@@ -96,8 +96,9 @@ const char* mg_version(void);
  *  14  added the test probe mg_debug_mx_mfma_acc (nothing moved).
  *  15  mg_ce_reduce_f32 gained `V` (after R): a target outside [0, V) is ignored by all three cross-entropy kernels alike; before,
  *      the reduction counted every target >= 0 although mg_ce_rows_f32 / mg_ce_bwd_bf16 gave such a row loss 0 and gradient 0.
- *  16  token log-probabilities: added mg_token_logprobs_f32 (nothing moved). */
-#define MG_ABI_VERSION 16
+ *  16  token log-probabilities: added mg_token_logprobs_f32 (nothing moved).
+ *  17  constrained decoding: added mg_logits_process_constrained_f32 (nothing moved). */
+#define MG_ABI_VERSION 17
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -474,6 +475,36 @@ int mg_logits_process_f32(float* logits, int64_t ld, int32_t R, int32_t V, const
                           const int32_t* eos_more, int32_t n_eos_more, void* stream);
 int mg_beam_topk_scores_f32(const float* scores, int64_t ld, int32_t R, int32_t V, const float* run, int32_t K2,
                             float* cand_score, int32_t* cand_tok, void* stream);
+
+/* Constrained decoding (ABI 17; DESIGN.md "Constrained decoding"; host statement: magma_amd/sampling.py, constrain_logits):
+ * mg_logits_process_f32's launch -- its rules first, with its arguments; there is no beam form -- after which row r keeps only the
+ * tokens that continue the walk of its history through a token trie; every other column in [0, V) becomes -inf, a kept column
+ * keeps its value.  Still ONE enqueue-only launch of one workgroup per row: no allocation, no scratch, no host round trip.
+ * table (device int32 [table_ints], read at run time -- the counts too, so a captured launch follows whatever the buffer holds) is
+ * a forest of tries over token ids; node ids are indices into its arrays, which follow each other without gaps:
+ *   [0] n_nodes >= 1   [1] n_edges
+ *   first[n_nodes + 1]    node i's edges are e in [first[i], first[i + 1]);  first[0] = 0, first[n_nodes] = n_edges
+ *   terminal[n_nodes]     != 0: a listed sequence ends at the node (every leaf is terminal)
+ *   parent[n_nodes]       the node the edge into i leaves, -1 for a root
+ *   in_token[n_nodes]     the token of the edge into i (-1 for a root)
+ *   edge_token[n_edges]   ascending within a node, distinct within a node
+ *   edge_child[n_edges]
+ * so table_ints >= 3 + 4 n_nodes + 2 n_edges.  roots [R] (device int32): the root of row r's trie.  With len = min(state[0],
+ * history_cols), the row walks history[r * ld_history + 0 .. len) from roots[r], following the edge of each token:
+ *   the walk ends at node i   kept: the tokens of i's edges, and -- if terminal[i] -- eos and eos_more[0 .. n_eos_more);
+ *   the walk leaves the trie  (a token that is no edge of the node it is at; it never returns): kept: the eos ids alone.
+ * Token ids outside [0, V) are skipped everywhere; nothing beyond history_cols is read; history may not be NULL.  A header or a root
+ * that does not fit (counts < 0, 3 + 4 n + 2 e > table_ints, root outside [0, n_nodes)) counts as off the trie, and every index
+ * an entry supplies is bounded by the header before it is used.
+ * path (device int32 [R, MG_TRIE_MAX_LEN], any contents; rows belong to the launch while it runs): a cache of the nodes the walk
+ * passed, path[r][i] = the node after i + 1 tokens.  An entry is used only after parent / in_token have shown it to be that node
+ * for THIS table and history, so stale or foreign contents never change a result; the launch rewrites the entries it walks.  */
+#define MG_TRIE_MAX_LEN 64
+int mg_logits_process_constrained_f32(float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* state, const int64_t* history,
+                                      int64_t ld_history, int32_t history_cols, float repetition_penalty, int32_t no_repeat_ngram,
+                                      int32_t min_new_tokens, int64_t eos, const int32_t* suppress, int32_t n_suppress,
+                                      const int32_t* eos_more, int32_t n_eos_more, const int32_t* table, int64_t table_ints,
+                                      const int32_t* roots, int32_t* path, void* stream);
 
 /* Token log-probabilities (ABI 16; DESIGN.md "Token log-probabilities"; host statement: magma_amd/sampling.py, token_logprobs):
  * how probable the model found a token, and the n_top most probable tokens beside it, in ONE enqueue-only, graph-capturable

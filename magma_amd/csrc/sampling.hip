@@ -686,9 +686,8 @@ struct ProcessParams {
   const int32_t* eos_more; int n_eos_more;   // further eos ids of the min-new-tokens rule (per-row stopping with an eos list)
 };
 
-__global__ __launch_bounds__(ST) void logits_process_kernel(const ProcessParams p) {
-  extern __shared__ uint32_t seen[];        // V bits (only when the penalty applies): token already penalised
-  __shared__ float shf[ST / 64];
+// the rules of one row; ``seen``: V bits of LDS (only when the penalty applies): token already penalised
+MG_DEV void process_rules(const ProcessParams p, uint32_t* seen, float* shf) {
   const int tid = threadIdx.x, V = p.V;
   float* x = p.x + (int64_t)blockIdx.x * p.ld;
   const int step = p.state[0];
@@ -741,6 +740,100 @@ __global__ __launch_bounds__(ST) void logits_process_kernel(const ProcessParams 
     const int t = p.suppress[i];
     if (t >= 0 && t < V) x[t] = -INFINITY;
   }
+}
+
+__global__ __launch_bounds__(ST) void logits_process_kernel(const ProcessParams p) {
+  extern __shared__ uint32_t seen[];
+  __shared__ float shf[ST / 64];
+  process_rules(p, seen, shf);
+}
+
+// Constrained decoding (DESIGN.md "Constrained decoding"; host statement: sampling.py constrain_logits; the table's layout:
+// include/magma_hip.h): the same launch -- the rules above first -- then the row keeps only the tokens that continue its walk
+// through a token trie.  Three phases, every loop uniform over the workgroup:
+//   1. lookup    path[row][i] caches the node reached after the row's first i + 1 tokens.  It is trusted only as far as it proves
+//                itself against THIS table and THIS history: thread i checks parent[path[i]] == path[i - 1] (the root for i = 0)
+//                and in_token[path[i]] == history[i]; the longest prefix whose checks all pass is, by induction, the walk of that
+//                prefix.  One load round trip for all 64 levels; inside a generate() loop it covers every token but the last.
+//   2. walk      the tokens the prefix does not cover, one level each: the workgroup scans the node's edges for the token (one
+//                round trip per 1024 edges) and records the child in path.  Inside a loop that is one level; after anything
+//                else -- another call, another trie, an eager step -- as many as the cache got wrong.  Off the trie it stops.
+//   3. mask      the node's edge tokens (and the eos ids, at a terminal node or off the trie) set bits in a V-bit map in LDS -- the
+//                penalty's map, free again by then --, then one sweep writes -inf to every column whose bit is clear.  The sweep
+//                reads no logit, so it needs no ordering against the -inf writes of the rules above.
+// Every index a table entry supplies is checked against the header's counts, and the header against table_ints: a table that is
+// not one leaves the eos ids only and reads nothing outside the buffer.
+struct TrieParams {
+  const int32_t* table; int64_t table_ints;
+  const int32_t* roots;                     // [R] the root node of every row
+  int32_t* path;                            // [R, MG_TRIE_MAX_LEN]
+};
+
+__global__ __launch_bounds__(ST) void logits_process_constrained_kernel(const ProcessParams p, const TrieParams c) {
+  extern __shared__ uint32_t bits[];
+  __shared__ float shf[ST / 64];
+  __shared__ int s_good, s_child[2];
+  process_rules(p, bits, shf);
+  const int tid = threadIdx.x, V = p.V, row = blockIdx.x;
+  float* x = p.x + (int64_t)row * p.ld;
+  const int len = max(0, min(p.state[0], p.hist_cols));
+  const int64_t* h = p.history + (int64_t)row * p.ld_hist;
+  const int n = c.table[0], e = c.table[1];
+  const bool sane = n >= 1 && e >= 0 && 3 + 4 * (int64_t)n + 2 * (int64_t)e <= c.table_ints;
+  const int32_t* first = c.table + 2;
+  const int32_t* terminal = first + (sane ? n + 1 : 0);
+  const int32_t* parent = terminal + (sane ? n : 0);
+  const int32_t* in_tok = parent + (sane ? n : 0);
+  const int32_t* etok = in_tok + (sane ? n : 0);
+  const int32_t* echild = etok + (sane ? e : 0);
+  int32_t* path = c.path + (int64_t)row * MG_TRIE_MAX_LEN;
+  const int root = c.roots[row];
+  int cur = sane && root >= 0 && root < n ? root : -1;        // -1: off the trie
+  // 1. lookup
+  const int nv = cur < 0 ? 0 : min(len, MG_TRIE_MAX_LEN);
+  if (tid == 0) s_good = nv;
+  for (int i = tid; i < (V + 31) / 32; i += ST) bits[i] = 0u;
+  __syncthreads();
+  if (tid < nv) {
+    const int ch = path[tid], pa = tid == 0 ? root : path[tid - 1];
+    if (!(ch >= 0 && ch < n && parent[ch] == pa && (int64_t)in_tok[ch] == h[tid])) atomicMin(&s_good, tid);
+  }
+  __syncthreads();
+  int i = s_good;
+  if (i > 0) cur = path[i - 1];
+  // 2. walk (s_child alternates between two slots: a slot is reset two barriers after its last reader)
+  for (int it = 0; cur >= 0 && i < len; ++it) {
+    const int lo = max(first[cur], 0), hi = min(first[cur + 1], e);
+    if (tid == 0) s_child[it & 1] = -1;
+    __syncthreads();
+    const int64_t t = h[i];
+    for (int j = lo + tid; j < hi; j += ST)
+      if ((int64_t)etok[j] == t) s_child[it & 1] = echild[j];
+    __syncthreads();
+    const int ch = s_child[it & 1];
+    if (ch < 0 || ch >= n || i >= MG_TRIE_MAX_LEN) { cur = -1; break; }
+    if (tid == 0) path[i] = ch;
+    cur = ch;
+    ++i;
+  }
+  // 3. mask
+  if (cur >= 0) {
+    const int lo = max(first[cur], 0), hi = min(first[cur + 1], e);
+    for (int j = lo + tid; j < hi; j += ST) {
+      const int t = etok[j];
+      if (t >= 0 && t < V) atomicOr(&bits[t >> 5], 1u << (t & 31));
+    }
+  }
+  if (cur < 0 || terminal[cur] != 0) {
+    if (tid == 0 && p.eos >= 0 && p.eos < V) atomicOr(&bits[(int)p.eos >> 5], 1u << ((int)p.eos & 31));
+    if (tid >= 1 && tid <= p.n_eos_more) {
+      const int t = p.eos_more[tid - 1];
+      if (t >= 0 && t < V) atomicOr(&bits[t >> 5], 1u << (t & 31));
+    }
+  }
+  __syncthreads();
+  for (int v = tid; v < V; v += ST)
+    if (!((bits[v >> 5] >> (v & 31)) & 1u)) x[v] = -INFINITY;
 }
 
 struct BeamArgs {
@@ -966,26 +1059,58 @@ extern "C" int mg_token_logprobs_f32(const float* logits, int64_t ld, int32_t R,
   return MG_OK;
 }
 
+// the checks mg_logits_process_f32 and mg_logits_process_constrained_f32 share
+static int process_args_check(const char* fn, const float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* state,
+                              const int64_t* history, int64_t ld_history, int32_t history_cols, float repetition_penalty,
+                              int32_t no_repeat_ngram, int32_t min_new_tokens, const int32_t* suppress, int32_t n_suppress,
+                              const int32_t* eos_more, int32_t n_eos_more, bool reads_history, bool uses_map) {
+  if (!logits || !state || R <= 0 || V <= 0 || ld < V) MG_FAIL(MG_ERR_SHAPE, "%s: bad logits / state / R / V / ld", fn);
+  if (!(repetition_penalty > 0.f)) MG_FAIL(MG_ERR_SHAPE, "%s: repetition_penalty must be > 0", fn);
+  if (no_repeat_ngram < 0 || no_repeat_ngram > 16 || min_new_tokens < 0)
+    MG_FAIL(MG_ERR_SHAPE, "%s: need 0 <= no_repeat_ngram <= 16 and min_new_tokens >= 0", fn);
+  if (n_suppress < 0 || n_suppress > 1024 || (n_suppress > 0 && !suppress))
+    MG_FAIL(MG_ERR_SHAPE, "%s: need 0 <= n_suppress <= 1024 and a suppress array", fn);
+  if (n_eos_more < 0 || n_eos_more > MG_STOP_MAX_EOS || (n_eos_more > 0 && !eos_more))
+    MG_FAIL(MG_ERR_SHAPE, "%s: need 0 <= n_eos_more <= %d and an eos_more array", fn, MG_STOP_MAX_EOS);
+  if (reads_history && (!history || history_cols <= 0 || ld_history < history_cols))
+    MG_FAIL(MG_ERR_SHAPE, "%s: the penalty, the n-gram rule and the constraint need a history [R, ld_history >= history_cols > 0]", fn);
+  if (uses_map && (size_t)((V + 31) / 32) * 4 > 60 * 1024)
+    MG_FAIL(MG_ERR_SHAPE, "%s: V = %d exceeds the LDS token map (491 520 tokens)", fn, V);
+  return MG_OK;
+}
+
 extern "C" int mg_logits_process_f32(float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* state, const int64_t* history,
                                      int64_t ld_history, int32_t history_cols, float repetition_penalty, int32_t no_repeat_ngram,
                                      int32_t min_new_tokens, int64_t eos, const int32_t* suppress, int32_t n_suppress,
                                      int32_t normalize, const int32_t* eos_more, int32_t n_eos_more, void* stream) {
-  if (!logits || !state || R <= 0 || V <= 0 || ld < V) MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_f32: bad logits / state / R / V / ld");
-  if (!(repetition_penalty > 0.f)) MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_f32: repetition_penalty must be > 0");
-  if (no_repeat_ngram < 0 || no_repeat_ngram > 16 || min_new_tokens < 0)
-    MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_f32: need 0 <= no_repeat_ngram <= 16 and min_new_tokens >= 0");
-  if (n_suppress < 0 || n_suppress > 1024 || (n_suppress > 0 && !suppress))
-    MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_f32: need 0 <= n_suppress <= 1024 and a suppress array");
-  if (n_eos_more < 0 || n_eos_more > MG_STOP_MAX_EOS || (n_eos_more > 0 && !eos_more))
-    MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_f32: need 0 <= n_eos_more <= %d and an eos_more array", MG_STOP_MAX_EOS);
-  const bool reads_history = repetition_penalty != 1.0f || no_repeat_ngram > 0;
-  if (reads_history && (!history || history_cols <= 0 || ld_history < history_cols))
-    MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_f32: the penalty and the n-gram rule need a history [R, ld_history >= history_cols > 0]");
+  const int rc = process_args_check("mg_logits_process_f32", logits, ld, R, V, state, history, ld_history, history_cols,
+                                    repetition_penalty, no_repeat_ngram, min_new_tokens, suppress, n_suppress, eos_more, n_eos_more,
+                                    repetition_penalty != 1.0f || no_repeat_ngram > 0, repetition_penalty != 1.0f);
+  if (rc != MG_OK) return rc;
   const size_t lds = repetition_penalty != 1.0f ? (size_t)((V + 31) / 32) * 4 : 0;
-  if (lds > 60 * 1024) MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_f32: V = %d exceeds the LDS token map (491 520 tokens)", V);
   ProcessParams p{logits, ld, V, state, history, ld_history, history ? history_cols : 0, repetition_penalty, no_repeat_ngram,
                   min_new_tokens, eos, suppress, n_suppress, normalize ? 1 : 0, eos_more, eos_more ? n_eos_more : 0};
   hipLaunchKernelGGL(logits_process_kernel, dim3(R), dim3(ST), lds, (hipStream_t)stream, p);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_logits_process_constrained_f32(float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* state,
+                                                 const int64_t* history, int64_t ld_history, int32_t history_cols,
+                                                 float repetition_penalty, int32_t no_repeat_ngram, int32_t min_new_tokens,
+                                                 int64_t eos, const int32_t* suppress, int32_t n_suppress, const int32_t* eos_more,
+                                                 int32_t n_eos_more, const int32_t* table, int64_t table_ints, const int32_t* roots,
+                                                 int32_t* path, void* stream) {
+  const int rc = process_args_check("mg_logits_process_constrained_f32", logits, ld, R, V, state, history, ld_history, history_cols,
+                                    repetition_penalty, no_repeat_ngram, min_new_tokens, suppress, n_suppress, eos_more, n_eos_more,
+                                    true, true);
+  if (rc != MG_OK) return rc;
+  if (!table || table_ints < 2 || !roots || !path)
+    MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_constrained_f32: need a table of at least 2 ints, roots [R] and path [R, %d]", MG_TRIE_MAX_LEN);
+  ProcessParams p{logits, ld, V, state, history, ld_history, history_cols, repetition_penalty, no_repeat_ngram,
+                  min_new_tokens, eos, suppress, n_suppress, 0, eos_more, eos_more ? n_eos_more : 0};
+  TrieParams c{table, table_ints, roots, path};
+  hipLaunchKernelGGL(logits_process_constrained_kernel, dim3(R), dim3(ST), (size_t)((V + 31) / 32) * 4, (hipStream_t)stream, p, c);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }

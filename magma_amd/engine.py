@@ -73,6 +73,25 @@ class KVCache:
         # token selected at step s, and the n_top most probable tokens of that step (int32 / fp32 [B, Smax, n_top]); allocated on
         # first request (LMEngine._arm_logprobs), addresses and n_top are launch arguments of the captured step
         self.lp = self.top_id = self.top_lp = None
+        # constrained decoding (DESIGN.md "Constrained decoding"): the trie table (int32, grown when a table outgrows it), the
+        # per-row roots int32 [B] and the kernel's path cache int32 [B, 64]; allocated on first use (LMEngine._arm_constraint).
+        # Addresses and the table's capacity are launch arguments of the captured step, the contents are not; trie_held is the
+        # ConstraintMode whose table and roots the buffers hold
+        self.trie_table = self.trie_roots = self.trie_path = self.trie_held = None
+
+    def alloc_trie(self, n_ints: int):
+        """The constraint's buffers for a table of ``n_ints`` (kept when it fits); steps captured on other buffers are dropped."""
+        if self.trie_table is not None and self.trie_table.numel() >= n_ints:
+            return
+        dev = self.k.device
+        self.trie_table = torch.zeros(max(4096, 2 * n_ints), dtype=torch.int32, device=dev)
+        self.trie_held = None
+        if self.trie_roots is None:
+            self.trie_roots = torch.zeros(self.B, dtype=torch.int32, device=dev)
+            self.trie_path = ops.trie_path(self.B, dev)
+        if self.decode_state is not None:
+            for key in [k for k in self.decode_state.graphs if ("constraint",) in k]:
+                del self.decode_state.graphs[key]
 
     def alloc_logprobs(self, n_top: int):
         """The per-step log-probability buffers for ``n_top`` alternatives per token (kept when they already have that shape);
@@ -192,6 +211,16 @@ class ProcMode(tuple):
 
 class StopMode(tuple):
     """LMEngine.stop_mode's checked (eos ids, stop sequences): passed again as ``stop=`` it is taken as it is."""
+
+
+class ConstraintMode:
+    """LMEngine.constraint_mode's checked constraint: the host copies of the table and the per-row roots (sampling.trie_forest)
+    and the largest token id; passed again as ``constraint=`` it is taken as it is (generate() builds it once, not once per token)."""
+
+    def __init__(self, tries):
+        from .sampling import trie_forest
+        self.table, self.roots = trie_forest(tries)
+        self.max_token = max(max(t.tokens()) for t in {id(t): t for t in tries}.values())
 
 
 class LMEngine:
@@ -584,7 +613,7 @@ class LMEngine:
                 output_hidden_states=False, cache_hint: Optional[int] = None, reuse_cache: bool = False,
                 return_logits: bool = False, sampling=None, eos_token: Optional[int] = None,
                 seed: Optional[int] = None, feed_back: bool = False, lengths=None, beam=None, processors=None,
-                stop=None, logprobs=None) -> LMOutput:
+                stop=None, logprobs=None, constraint=None) -> LMOutput:
         """``beam`` = (num_beams, length_penalty, early_stopping, max_steps): beam-search token selection (the rows are
         samples x num_beams, sample-major; DESIGN.md "Beam search") instead of ``sampling``.
         ``processors`` (sampling.check_processor_args' dict, or None): the logits processors in front of whichever selection
@@ -597,6 +626,9 @@ class LMEngine:
         token's log-probability under the RAW distribution of the step, and the n_top most probable tokens, into column
         step of the cache's lp / top_id / top_lp buffers (DESIGN.md "Token log-probabilities"); passed like ``stop``; not with
         ``beam``.
+        ``constraint`` (a list of one sampling.TokenTrie per row, constraint_mode's object, or None): the trie constraint in the
+        processors' launch (DESIGN.md "Constrained decoding") -- it counts as a processor: the first token comes from a processed
+        copy, with ``logprobs`` the step works on the second buffer; passed like ``processors``; not with ``beam``.
         ``lengths`` (int [B], 1 <= len_b <= S; prefill with use_cache=True only): the rows of ``inputs_embeds`` are prompts
         of different lengths, right-padded to S.  Row b's logits are those of its position len_b - 1, and the cache keeps one
         write position per row (len_b, then + 1 per step) -- see DESIGN.md, "Ragged batches"."""
@@ -605,6 +637,8 @@ class LMEngine:
             raise NotImplementedError("per-row stopping is not combined with beam search")
         if logprobs is not None and beam is not None:
             raise NotImplementedError("token log-probabilities are not combined with beam search (it has its own scores)")
+        if constraint is not None and beam is not None:
+            raise NotImplementedError("a constraint is not combined with beam search")
         if lengths is not None and (labels is not None or (past_key_values is not None and not extending) or not use_cache):
             raise ValueError("lengths= applies to the prefill call and to inputs_embeds appended to a cache (use_cache=True, no "
                              "labels); a ragged cache keeps its per-row positions for the steps that follow")
@@ -621,7 +655,7 @@ class LMEngine:
             logits, cache, full = self.extend(past_key_values, inputs_embeds, lengths=lengths, cache_hint=cache_hint)
             out = LMOutput(logits=logits.unsqueeze(1), past_key_values=cache, hidden_states=None, loss=None, full_logits=full)
             if eos_token is not None:
-                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, None, processors, stop, logprobs)
+                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, None, processors, stop, logprobs, constraint)
             return out
         if past_key_values is not None:
             if not feed_back and input_ids is None:
@@ -636,12 +670,12 @@ class LMEngine:
                 rows = []
                 for i in range(T):      # only the LAST position selects a token (history / RNG step / eos latch untouched before)
                     lg, tok = self.decode(input_ids[:, i:i + 1], past_key_values, sampling=sampling, select=i == T - 1,
-                                          beam=beam, processors=processors, stop=stop, logprobs=logprobs)
+                                          beam=beam, processors=processors, stop=stop, logprobs=logprobs, constraint=constraint)
                     rows.append(lg.clone())
                 return LMOutput(logits=torch.stack(rows, 1), past_key_values=past_key_values, next_token=tok, loss=None,
                                 eos_state=past_key_values.sample_state)
             logits, tok = self.decode(None if feed_back else input_ids, past_key_values, sampling=sampling, beam=beam,
-                                      processors=processors, stop=stop, logprobs=logprobs)
+                                      processors=processors, stop=stop, logprobs=logprobs, constraint=constraint)
             return LMOutput(logits=logits.unsqueeze(1), past_key_values=past_key_values, next_token=tok, loss=None,
                             eos_state=past_key_values.sample_state)
         if inputs_embeds is None:
@@ -651,7 +685,7 @@ class LMEngine:
             # generate() only reads the last position, so only that row is computed
             out = LMOutput(logits=logits.unsqueeze(1), past_key_values=cache, hidden_states=hs, loss=None)
             if eos_token is not None:
-                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, beam, processors, stop, logprobs)
+                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, beam, processors, stop, logprobs, constraint)
             return out
         x, hs = self._blocks_prefill(inputs_embeds, None, output_hidden_states)
         B, S, _ = inputs_embeds.shape
@@ -695,6 +729,31 @@ class LMEngine:
         if ids and ids != cache.suppress_ids:
             cache.suppress[: len(ids)].copy_(torch.tensor(ids, dtype=torch.int32), non_blocking=True)
             cache.suppress_ids = ids
+
+    @staticmethod
+    def constraint_mode(constraint):
+        """None (today's launches) or a ConstraintMode: the constraint mode that travels beside the processor mode."""
+        if constraint is None or isinstance(constraint, ConstraintMode):
+            return constraint
+        return ConstraintMode(list(constraint))
+
+    def _arm_constraint(self, cache: KVCache, cons):
+        """The table and the roots of ``cons`` in the cache's device buffers (written only when they differ from what the buffers
+        hold; never inside a captured step: decode() calls this before it captures or replays).  A table that outgrows the
+        buffer re-allocates it, which drops the steps captured on it (KVCache.alloc_trie)."""
+        if cons is None:
+            return
+        if cons.max_token >= self.V:
+            raise ValueError(f"the constraint holds token ids outside [0, {self.V})")
+        if cons.roots.numel() != cache.B:
+            raise ValueError(f"the constraint has {cons.roots.numel()} rows, the cache {cache.B}")
+        cache.alloc_trie(cons.table.numel())
+        held = cache.trie_held
+        if held is cons or (held is not None and torch.equal(held.table, cons.table) and torch.equal(held.roots, cons.roots)):
+            return
+        cache.trie_table[: cons.table.numel()].copy_(cons.table, non_blocking=True)
+        cache.trie_roots.copy_(cons.roots, non_blocking=True)
+        cache.trie_held = cons
 
     @staticmethod
     def stop_mode(stop):
@@ -742,7 +801,7 @@ class LMEngine:
             st.logits_proc = torch.empty_like(st.logits)
 
     def _arm_first_token(self, out: LMOutput, logits, cache: KVCache, eos_token, seed, sampling, beam, processors=None, stop=None,
-                         logprobs=None):
+                         logprobs=None, constraint=None):
         """generate(): the first token of the loop selected from the prefill / extend logits, device-side bookkeeping armed."""
         if cache.eos != int(eos_token):        # the eos id is a launch argument of the captured bookkeeping kernel
             cache.eos = int(eos_token)
@@ -762,19 +821,22 @@ class LMEngine:
             for key in [k for k in st.graphs if isinstance(k[0], tuple) and k[0][:1] == ("beam",)]:
                 del st.graphs[key]
         proc = self.proc_mode(processors)
+        cons = self.constraint_mode(constraint)   # (forward has refused the combination with beam)
         raw = logits
-        if proc is not None:       # step 0 of the rules on a copy: the caller's .logits stay raw
+        if proc is not None or cons is not None:       # step 0 of the rules on a copy: the caller's .logits stay raw
             self._arm_processors(cache, proc)
+            self._arm_constraint(cache, cons)
             logits = logits.clone()
         n_top = self.logprob_mode(logprobs)       # (forward has refused the combination with beam)
-        self._arm_logprobs(cache, st, n_top, proc)
+        self._arm_logprobs(cache, st, n_top, proc if proc is not None else cons)
         stop = self.stop_mode(stop)
         if stop is not None:       # every row unfinished again
             if int(eos_token) != stop[0][0]:
                 raise ValueError(f"per-row stopping pads with the first eos id: eos_token must be {stop[0][0]}, got {eos_token}")
             self._arm_stop(cache, stop)
             cache.finish.copy_(torch.tensor([[-1, 0]] * cache.B, dtype=torch.int32), non_blocking=True)
-        out["next_token"] = self.select_token(logits, cache, mode, out=st.token, proc=proc, stop=stop, logprobs=n_top, raw=raw)
+        out["next_token"] = self.select_token(logits, cache, mode, out=st.token, proc=proc, stop=stop, logprobs=n_top, raw=raw,
+                                                cons=cons)
         out["eos_state"] = cache.sample_state
 
     def embed_ids(self, ids: torch.Tensor) -> torch.Tensor:
@@ -1071,7 +1133,7 @@ class LMEngine:
 
     def select_token(self, logits: torch.Tensor, cache: KVCache, mode, out: Optional[torch.Tensor] = None,
                      advance: bool = False, clear: Optional[torch.Tensor] = None, proc=None, stop=None, logprobs=None,
-                     raw: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     raw: Optional[torch.Tensor] = None, cons=None) -> torch.Tensor:
         """next token of every row from fp32 logits (B, V): greedy argmax (mode None; reference sampling.py:96-97) or the
         sampled branch (mode = (temperature, top_k, top_p); :99-107 -- or ("warp", temperature, top_k, top_p, min_p):
         transformers' sampler, sample_mode), then the loop bookkeeping in one small launch
@@ -1084,11 +1146,21 @@ class LMEngine:
         (ops.sample_finish_rows) -- a finished row's token becomes the pad id in place --, and min_new_tokens bans every eos id.
         ``logprobs`` (logprob_mode; the buffers already allocated, _arm_logprobs): one launch AFTER the selection and BEFORE the
         bookkeeping -- which advances the step the launch reads its column from and overwrites a finished row's token -- writes the
-        token's log-probability and the n_top alternatives of ``raw`` (default ``logits``): the rows as they were before ``proc``."""
+        token's log-probability and the n_top alternatives of ``raw`` (default ``logits``): the rows as they were before ``proc``.
+        ``cons`` (constraint_mode; table and roots already in the cache's buffers, _arm_constraint): the processors' launch is the
+        constrained one (ops.logits_process_constrained) -- ``proc``'s rules, or neutral values, then the trie constraint with
+        every eos id --: with ``proc`` as many launches as without ``cons``, without ``proc`` one more."""
         is_beam = isinstance(mode, tuple) and bool(mode) and mode[0] == "beam"
-        if proc is not None:
+        if proc is not None or cons is not None:
             more = {} if stop is None or len(stop[0]) < 2 else dict(eos_more=cache.stop_table[1:ops.STOP_MAX_EOS],
                                                                     n_eos_more=len(stop[0]) - 1)
+        if cons is not None:
+            rules = proc if proc is not None else (1.0, 0, 0, ())
+            ops.logits_process_constrained(logits, cache.sample_state, cache.history, cache.trie_table, cache.trie_roots,
+                                           cache.trie_path, repetition_penalty=rules[0], no_repeat_ngram_size=rules[1],
+                                           min_new_tokens=rules[2], eos=cache.eos, suppress=cache.suppress,
+                                           n_suppress=len(rules[3]), **more)
+        elif proc is not None:
             ops.logits_process(logits, cache.sample_state, cache.history, repetition_penalty=proc[0], no_repeat_ngram_size=proc[1],
                                min_new_tokens=proc[2], eos=cache.eos, suppress=cache.suppress, n_suppress=len(proc[3]),
                                normalize=is_beam, **more)
@@ -1112,7 +1184,7 @@ class LMEngine:
                           clear=clear, clear_stride=16 if clear is not None else 1, pos_stride=cache.pos_stride)
         return tok
 
-    def _decode_step(self, cache: KVCache, st, mode=None, feed_back: bool = False, proc=None, stop=None, logprobs=None):
+    def _decode_step(self, cache: KVCache, st, mode=None, feed_back: bool = False, proc=None, stop=None, logprobs=None, cons=None):
         """Enqueue one token step for all B sequences (graph-capturable: no
         allocation, no sync, position read from cache.d_pos on the device): embedding, per layer the launch sequence of the
         kind planned for it (st.kinds, _ensure_decode_state), the head, token selection.
@@ -1132,15 +1204,15 @@ class LMEngine:
             ops.gemm_skinny(x, head, out=st.logits, ln_fold=(head.colsum, self.d, self.eps))
         if mode == "noselect":
             ops.advance_pos(cache.d_pos, pos_stride=cache.pos_stride)   # teacher-forced position: nothing selected, nothing recorded
-        elif logprobs is not None and proc is not None:
+        elif logprobs is not None and (proc is not None or cons is not None):
             # the processors run in place: they and the selection get a copy (one device copy inside the step), the
             # log-probabilities read the untouched st.logits
             st.logits_proc.copy_(st.logits)
             self.select_token(st.logits_proc[:, : self.V], cache, mode, out=st.token, advance=True, proc=proc, stop=stop,
-                              logprobs=logprobs, raw=st.logits[:, : self.V])
+                              logprobs=logprobs, raw=st.logits[:, : self.V], cons=cons)
         else:
             self.select_token(st.logits[:, : self.V], cache, mode, out=st.token, advance=True, proc=proc, stop=stop,
-                              logprobs=logprobs)
+                              logprobs=logprobs, cons=cons)
 
     # One method per block kind (_block_kind): x -> xn for layer li.  ``src`` holds the block's weight-streaming operands: the
     # layer itself, or its e4m3 / MXFP4 copies (ly.w8 / ly.w4) under W8A16 / W4A16 -- the same launches.  On a ragged cache (pos_stride 1) every
@@ -1269,7 +1341,7 @@ class LMEngine:
         return st
 
     def decode(self, input_ids: Optional[torch.Tensor], cache: KVCache, use_graph: bool = True, sampling=None, select: bool = True,
-               beam=None, processors=None, stop=None, logprobs=None):
+               beam=None, processors=None, stop=None, logprobs=None, constraint=None):
         """One cached step.  Returns (fp32 logits (B,V) view, selected token (B,) view: greedy, or sampled when
         ``sampling = (temperature, top_k, top_p)`` or ``("warp", temperature, top_k, top_p, min_p)``, sample_mode); both are
         overwritten by the next step.  ``input_ids=None`` feeds the
@@ -1281,7 +1353,8 @@ class LMEngine:
         ``stop`` (forward): per-row stopping -- the cache must have been armed with it (its finish record reset) by the prefill /
         extend call; the returned token view holds the pad id for rows that had finished.
         ``logprobs`` (forward): the step also writes column step of the cache's log-probability buffers, from the RAW logits; with
-        ``processors`` too, those and the selection run on a second buffer, whose rows are what is returned."""
+        ``processors`` too, those and the selection run on a second buffer, whose rows are what is returned.
+        ``constraint`` (forward): the trie constraint in the processors' launch; it counts as one of them in all of the above."""
         if cache.pos >= cache.Smax:
             raise ValueError(f"KV cache full (Smax={cache.Smax}); pass a larger cache_hint / max_steps")
         if cache.B > 16:
@@ -1320,7 +1393,11 @@ class LMEngine:
         n_top = self.logprob_mode(logprobs) if select else None
         if n_top is not None and beam is not None:
             raise NotImplementedError("token log-probabilities are not combined with beam search")
-        self._arm_logprobs(cache, st, n_top, proc)
+        cons = self.constraint_mode(constraint) if select else None
+        if cons is not None and beam is not None:
+            raise NotImplementedError("a constraint is not combined with beam search")
+        self._arm_constraint(cache, cons)
+        self._arm_logprobs(cache, st, n_top, proc if proc is not None else cons)
         key = (mode, feed_back)
         if proc is not None:        # the values are launch arguments of the captured step (the suppress ids are not: their count is)
             key += (tuple(proc[:3]) + (len(proc[3]),),)
@@ -1328,21 +1405,23 @@ class LMEngine:
             key += (("stop", len(stop[0]), len(stop[1]), stop[0][0]),)
         if n_top is not None:       # n_top and the buffers' addresses are launch arguments
             key += (("logprobs", n_top),)
+        if cons is not None:        # the buffers' addresses and the table's capacity are launch arguments, their contents are not
+            key += (("constraint",),)
         if not use_graph:
-            self._decode_step(cache, st, mode, feed_back, proc, stop, n_top)
+            self._decode_step(cache, st, mode, feed_back, proc, stop, n_top, cons)
         elif key in st.graphs:
             st.graphs[key].replay()
         elif st.steps == 0:
-            self._decode_step(cache, st, mode, feed_back, proc, stop, n_top)    # first step eager (loads code objects)
+            self._decode_step(cache, st, mode, feed_back, proc, stop, n_top, cons)    # first step eager (loads code objects)
         else:
             g = torch.cuda.CUDAGraph()            # hipGraph on ROCm
             with torch.cuda.graph(g):
-                self._decode_step(cache, st, mode, feed_back, proc, stop, n_top)
+                self._decode_step(cache, st, mode, feed_back, proc, stop, n_top, cons)
             st.graphs[key] = g
             g.replay()
         st.steps += 1
         cache.pos += 1
-        return (st.logits_proc if n_top is not None and proc is not None else st.logits)[:, : self.V], st.token
+        return (st.logits_proc if n_top is not None and (proc is not None or cons is not None) else st.logits)[:, : self.V], st.token
 
     # ------------------------------------------------- loss (eval) forward
     def forward_loss(self, embeds: torch.Tensor, labels: torch.Tensor, want_hidden=False, want_logits=False) -> LMOutput:

@@ -282,7 +282,7 @@ class Magma(nn.Module):
                  return_past_key_values: bool = False, *, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
                  min_new_tokens: int = 0, suppress_tokens=None, eos_token=None, stop_sequences=None, stop_per_row: bool = None,
                  return_finish: bool = False, sampler: str = "reference", min_p: float = 0.0, return_logprobs: bool = False,
-                 top_logprobs: int = 0):
+                 top_logprobs: int = 0, constraint=None):
         """reference magma.py:214-236 (+ stop_on_eos / seed / eos_check_every / lengths, see sampling.generate).
         ``lengths``: prompts of different lengths, right-padded (embed_batch); ``embeddings`` may also be a list of
         per-sample (1, s_i, d) tensors.  ``num_beams`` > 1: beam search (length_penalty, early_stopping,
@@ -296,7 +296,9 @@ class Magma(nn.Module):
         ``sampler="transformers"``: temperature, top-k, nucleus top-p and ``min_p`` as transformers' warpers apply them, instead of
         the reference's filters (see sampling.generate).
         ``return_logprobs`` / ``top_logprobs`` (0 to 20 alternatives per token): a ``TokenLogprobs`` appended to the result -- every
-        generated token's log-probability under the raw model distribution, as ``score`` gives it (see sampling.generate)."""
+        generated token's log-probability under the raw model distribution, as ``score`` gives it (see sampling.generate).
+        ``constraint`` (a ``sampling.TokenTrie``, a list of token-id sequences or strings, or one of either per row): every row's
+        output stays inside that closed set of answers, followed by eos (see sampling.generate; ``choose`` maps it back)."""
         torch.cuda.set_device(self.device)
         return generate(self, embeddings=embeddings, max_steps=max_steps, temperature=temperature, top_k=top_k,
                         top_p=top_p, decode=decode, stop_on_eos=stop_on_eos, seed=seed, eos_check_every=eos_check_every,
@@ -306,7 +308,18 @@ class Magma(nn.Module):
                         repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
                         min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens, eos_token=eos_token,
                         stop_sequences=stop_sequences, stop_per_row=stop_per_row, return_finish=return_finish, sampler=sampler,
-                        min_p=min_p, return_logprobs=return_logprobs, top_logprobs=top_logprobs)
+                        min_p=min_p, return_logprobs=return_logprobs, top_logprobs=top_logprobs, constraint=constraint)
+
+    @torch.no_grad()
+    def choose(self, embeddings, choices, lengths=None, **generate_kwargs):
+        """Which of ``choices`` (a ``sampling.TokenTrie``, a list of token-id sequences or strings, or one of either per row) the
+        model answers with: constrained GREEDY decoding (``generate(constraint=choices, temperature=0, return_logprobs=True)``,
+        ``max_steps`` = the longest choice + 1).  Returns (index int64 [B]: the position of row b's answer in its choices,
+        ``TokenLogprobs`` of the path under the raw distribution).  It follows the locally most probable allowed token; it is NOT
+        the arg-max of the total sequence probability -- ``score`` every candidate for that (see sampling.choose)."""
+        from .sampling import choose
+        torch.cuda.set_device(self.device)
+        return choose(self, embeddings, choices, lengths=lengths, **generate_kwargs)
 
     @torch.no_grad()
     def score(self, embeddings, targets, lengths=None, *, top_logprobs: int = 0):

@@ -756,6 +756,50 @@ def logits_process(logits: torch.Tensor, state: torch.Tensor, history: Optional[
     return logits
 
 
+TRIE_MAX_LEN = 64           # include/magma_hip.h MG_TRIE_MAX_LEN: the longest sequence of a token trie, columns of the path cache
+
+
+def trie_path(R: int, device) -> torch.Tensor:
+    """The per-row path cache of logits_process_constrained (int32 [R, TRIE_MAX_LEN]; any contents do)."""
+    return torch.zeros(R, TRIE_MAX_LEN, dtype=torch.int32, device=device)
+
+
+def logits_process_constrained(logits: torch.Tensor, state: torch.Tensor, history: torch.Tensor, table: torch.Tensor,
+                               roots: torch.Tensor, path: torch.Tensor, *, repetition_penalty: float = 1.0,
+                               no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, eos: int = -1,
+                               suppress: Optional[torch.Tensor] = None, n_suppress: Optional[int] = None,
+                               eos_more: Optional[torch.Tensor] = None, n_eos_more: Optional[int] = None):
+    """logits_process (its rules, its arguments; no beam form) followed in the same launch by the trie constraint
+    (mg_logits_process_constrained_f32; host statement: sampling.constrain_logits): row r keeps the tokens that continue the walk
+    of ``history[r, :state[0]]`` from node ``roots[r]`` (device int32 [R]) through ``table`` (device int32: sampling.TokenTrie.flat()
+    / trie_forest(), read at run time) and -- at a terminal node or off the trie -- ``eos`` and the ``eos_more`` ids; every other
+    column becomes -inf.  ``path`` (trie_path): the launch's per-row cache, checked before use -- any contents give the same
+    result.  Enqueue-only."""
+    _need_gpu(logits, state, history, suppress, eos_more, table, roots, path)
+    assert logits.dtype == torch.float32 and logits.ndim == 2 and logits.stride(1) == 1
+    assert state.dtype == torch.int32 and state.numel() >= 1
+    R, V = logits.shape
+    assert history.dtype == torch.int64 and history.ndim == 2 and history.stride(1) == 1 and history.shape[0] == R
+    assert table.dtype == torch.int32 and table.is_contiguous() and table.ndim == 1 and table.numel() >= 2
+    assert roots.dtype == torch.int32 and roots.is_contiguous() and roots.numel() >= R
+    assert path.dtype == torch.int32 and path.is_contiguous() and path.ndim == 2 and path.shape[0] >= R and path.shape[1] == TRIE_MAX_LEN
+    if suppress is not None:
+        assert suppress.dtype == torch.int32 and suppress.is_contiguous()
+    ns = (0 if suppress is None else suppress.numel()) if n_suppress is None else int(n_suppress)
+    assert ns == 0 or (suppress is not None and ns <= suppress.numel())
+    if eos_more is not None:
+        assert eos_more.dtype == torch.int32 and eos_more.is_contiguous()
+    nm = (0 if eos_more is None else eos_more.numel()) if n_eos_more is None else int(n_eos_more)
+    assert nm == 0 or (eos_more is not None and nm <= eos_more.numel())
+    check(L.load().mg_logits_process_constrained_f32(logits.data_ptr(), logits.stride(0), R, V, state.data_ptr(), history.data_ptr(),
+                                                     history.stride(0), history.shape[1], float(repetition_penalty),
+                                                     int(no_repeat_ngram_size), int(min_new_tokens), int(eos), _p(suppress), ns,
+                                                     _p(eos_more) if nm else None, nm, table.data_ptr(), table.numel(),
+                                                     roots.data_ptr(), path.data_ptr(), _stream()),
+          "mg_logits_process_constrained_f32")
+    return logits
+
+
 def beam_topk(logits: torch.Tensor, run: torch.Tensor, cand_score: torch.Tensor, cand_tok: torch.Tensor, normalized: bool = False):
     """Per row: the top K2 = cand_score.shape[1] scores run[row] + log_softmax(logits[row]) (score desc, lower token first).
     ``normalized``: the rows already hold log_softmax scores (logits_process(normalize=True)): candidates run[row] + logits[row]."""

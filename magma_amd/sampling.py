@@ -232,6 +232,245 @@ def process_logits(scores, history, step: int, *, repetition_penalty: float = 1.
     return x
 
 
+MAX_TRIE_LEN, MAX_TRIE_SEQS, MAX_TRIE_NODES = 64, 65536, 2 ** 20
+
+
+class TokenTrie:
+    """An immutable trie over token-id sequences: the closed set of answers ``generate(constraint=...)`` keeps a row inside
+    (DESIGN.md "Constrained decoding").  ``sequences``: at most 65 536 entries, each 1 to 64 ids >= 0 (a list, a tuple, a tensor)
+    or a ``str`` that ``encode`` turns into ids (no ``encode``: a ``str`` raises); at most 2^20 nodes.  Duplicates collapse; one
+    sequence may be a prefix of another (its node is terminal AND has edges).  Nodes are numbered breadth first from the root 0,
+    so a node's edges are consecutive; within a node they ascend by token."""
+    __slots__ = ("sequences", "_index", "_kids", "first", "terminal", "parent", "in_token", "edge_token", "edge_child", "_tokens",
+                 "_flat")
+
+    def __init__(self, sequences, encode: Callable = None):
+        if isinstance(sequences, str) or not isinstance(sequences, (list, tuple)):
+            raise ValueError("a TokenTrie takes a list of token-id sequences or strings")
+        if not 1 <= len(sequences) <= MAX_TRIE_SEQS:
+            raise ValueError(f"a TokenTrie takes 1 to {MAX_TRIE_SEQS} sequences, got {len(sequences)}")
+        seqs = []
+        for q in sequences:
+            if isinstance(q, str):
+                if encode is None:
+                    raise ValueError(f"the sequence {q!r} is text and there is no tokenizer to encode it")
+                q = encode(q)
+            if torch.is_tensor(q):
+                q = q.tolist()
+            if not isinstance(q, (list, tuple)) or not 1 <= len(q) <= MAX_TRIE_LEN:
+                raise ValueError(f"a sequence is 1 to {MAX_TRIE_LEN} token ids, got {q!r}")
+            for t in q:
+                if isinstance(t, bool) or not isinstance(t, int) or t < 0 or t >= 2 ** 31:
+                    raise ValueError(f"a sequence holds token ids >= 0, got {t!r}")
+            seqs.append(tuple(q))
+        kids, term = [{}], [False]
+        for q in seqs:
+            n = 0
+            for t in q:
+                c = kids[n].get(t)
+                if c is None:
+                    c = kids[n][t] = len(kids)
+                    kids.append({})
+                    term.append(False)
+                n = c
+            term[n] = True
+        if len(kids) > MAX_TRIE_NODES:
+            raise ValueError(f"a TokenTrie holds at most {MAX_TRIE_NODES} nodes, these sequences need {len(kids)}")
+        order, new = [0], {0: 0}
+        for n in order:                     # breadth first, edges ascending
+            for t in sorted(kids[n]):
+                new[kids[n][t]] = len(order)
+                order.append(kids[n][t])
+        N = len(order)
+        first, parent, in_token, etok, echild = [0], [-1] * N, [-1] * N, [], []
+        for i, n in enumerate(order):
+            for t in sorted(kids[n]):
+                c = new[kids[n][t]]
+                etok.append(t)
+                echild.append(c)
+                parent[c], in_token[c] = i, t
+            first.append(len(etok))
+        index = {}
+        for i, q in enumerate(seqs):
+            index.setdefault(q, i)
+        set_ = object.__setattr__
+        set_(self, "sequences", tuple(seqs))
+        set_(self, "_index", index)
+        set_(self, "_kids", tuple({t: new[c] for t, c in kids[n].items()} for n in order))
+        set_(self, "first", tuple(first))
+        set_(self, "terminal", tuple(int(term[n]) for n in order))
+        set_(self, "parent", tuple(parent))
+        set_(self, "in_token", tuple(in_token))
+        set_(self, "edge_token", tuple(etok))
+        set_(self, "edge_child", tuple(echild))
+        set_(self, "_tokens", frozenset(etok))
+        set_(self, "_flat", torch.tensor([N, len(etok)] + first + list(self.terminal) + parent + in_token + etok + echild,
+                                         dtype=torch.int32))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a TokenTrie is immutable")
+
+    @property
+    def n_nodes(self) -> int:
+        return len(self.terminal)
+
+    @property
+    def n_edges(self) -> int:
+        return len(self.edge_token)
+
+    def tokens(self) -> frozenset:
+        """Every token id of every sequence."""
+        return self._tokens
+
+    def min_len(self) -> int:
+        return min(len(q) for q in self.sequences)
+
+    def max_len(self) -> int:
+        return max(len(q) for q in self.sequences)
+
+    def index(self, tokens) -> int:
+        """The position of the sequence ``tokens`` in the constructor's list (of duplicates: the first), or -1."""
+        if torch.is_tensor(tokens):
+            tokens = tokens.tolist()
+        return self._index.get(tuple(int(t) for t in tokens), -1)
+
+    def node(self, prefix):
+        """The node the walk of ``prefix`` from the root ends at, or None when it leaves the trie."""
+        n = 0
+        for t in prefix:
+            n = self._kids[n].get(int(t))
+            if n is None:
+                return None
+        return n
+
+    def allowed(self, prefix, eos_ids) -> List[int]:
+        """The host rule: after the generated tokens ``prefix`` -- at node n: the tokens of n's edges, plus every eos id if n is
+        terminal; off the trie (a token that is no edge, an eos taken at a terminal node and the padding behind it included):
+        the eos ids alone.  Never empty: a leaf is terminal.  Usable as transformers' ``prefix_allowed_tokens_fn`` body."""
+        if torch.is_tensor(prefix):
+            prefix = prefix.tolist()
+        eos = [int(t) for t in eos_ids]
+        n = self.node(prefix)
+        if n is None:
+            return eos
+        return list(self.edge_token[self.first[n]: self.first[n + 1]]) + (eos if self.terminal[n] else [])
+
+    def flat(self) -> torch.Tensor:
+        """The int32 table the device reads (layout: include/magma_hip.h, mg_logits_process_constrained_f32): {n_nodes, n_edges},
+        first[n_nodes + 1], terminal[n_nodes], parent[n_nodes], in_token[n_nodes], edge_token[n_edges], edge_child[n_edges]."""
+        return self._flat.clone()
+
+    @staticmethod
+    def from_flat(table) -> List[tuple]:
+        """The sequences a one-trie table holds, in breadth-first order of their last node (flat()'s inverse up to order)."""
+        t = torch.as_tensor(table).tolist()
+        n, e = t[0], t[1]
+        terminal, parent, in_token = t[3 + n: 3 + 2 * n], t[3 + 2 * n: 3 + 3 * n], t[3 + 3 * n: 3 + 4 * n]
+        assert len(t) == 3 + 4 * n + 2 * e
+        out = []
+        for i in range(n):
+            if terminal[i]:
+                q, j = [], i
+                while parent[j] >= 0:
+                    q.append(in_token[j])
+                    j = parent[j]
+                out.append(tuple(reversed(q)))
+        return out
+
+
+def trie_forest(tries) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(table int32, roots int32 [len(tries)]): the distinct tries of ``tries`` side by side in one table of TokenTrie.flat()'s
+    layout -- node and edge numbers shifted by what stands before them -- and, per entry, the node that is its root."""
+    distinct, at = [], {}
+    for t in tries:
+        if id(t) not in at:
+            at[id(t)] = len(distinct)
+            distinct.append(t)
+    if len(distinct) == 1:      # the table made once, when the trie was built
+        return distinct[0]._flat, torch.zeros(len(tries), dtype=torch.int32)
+    first, terminal, parent, in_token, etok, echild, root_of = [], [], [], [], [], [], []
+    n_off = e_off = 0
+    for t in distinct:
+        root_of.append(n_off)
+        first += [f + e_off for f in t.first[:-1]]
+        terminal += t.terminal
+        parent += [p + n_off if p >= 0 else -1 for p in t.parent]
+        in_token += t.in_token
+        etok += t.edge_token
+        echild += [c + n_off for c in t.edge_child]
+        n_off, e_off = n_off + t.n_nodes, e_off + t.n_edges
+    table = torch.tensor([n_off, e_off] + first + [e_off] + terminal + parent + in_token + etok + echild, dtype=torch.int32)
+    return table, torch.tensor([root_of[at[id(t)]] for t in tries], dtype=torch.int32)
+
+
+def check_constraint_args(constraint, batch: int = None, encode: Callable = None, vocab: int = None, eos_ids=(), proc: dict = None):
+    """ValueError for a ``constraint`` generate() does not take.  Returns None (``constraint`` None: today's call) or a list of
+    TokenTrie, one per row (one object repeated when the rows share it; a list of length 1 when ``batch`` is None).  Forms: a
+    TokenTrie; a list of sequences (id lists / tensors / ``str`` for ``encode``); a list of ``batch`` of either, one per row.
+    Refused, because they could leave a row without any token: ``no_repeat_ngram_size`` > 0, ``min_new_tokens`` above the
+    shortest sequence, ``suppress_tokens`` that meet the trie's tokens or the eos ids (``proc``: check_processor_args' dict),
+    and a trie id >= ``vocab``."""
+    if constraint is None:
+        return None
+
+    def is_seq(q):
+        return isinstance(q, str) or torch.is_tensor(q) or (isinstance(q, (list, tuple)) and len(q) > 0 and
+                                                            all(isinstance(t, int) and not isinstance(t, bool) for t in q))
+
+    def one(c):
+        return c if isinstance(c, TokenTrie) else TokenTrie(c, encode)
+
+    if isinstance(constraint, TokenTrie):
+        tries = [constraint] * (batch or 1)
+    elif isinstance(constraint, (list, tuple)) and len(constraint) > 0 and all(is_seq(q) for q in constraint):
+        tries = [TokenTrie(constraint, encode)] * (batch or 1)
+    elif isinstance(constraint, (list, tuple)) and len(constraint) > 0:
+        if batch is not None and len(constraint) != batch:
+            raise ValueError(f"a per-row constraint needs one entry per row: {len(constraint)} entries for {batch} rows")
+        tries = [one(c) for c in constraint]
+    else:
+        raise ValueError("constraint must be a TokenTrie, a list of sequences, or a list of one of either per row")
+    distinct = list({id(t): t for t in tries}.values())
+    toks = frozenset().union(*(t.tokens() for t in distinct))
+    if vocab is not None and max(toks) >= vocab:
+        raise ValueError(f"the constraint holds token ids outside [0, {vocab}): {sorted(t for t in toks if t >= vocab)[:8]}")
+    if proc is not None:
+        if proc["no_repeat_ngram_size"] > 0:
+            raise ValueError("no_repeat_ngram_size is not combined with a constraint: it could ban every token the trie allows")
+        shortest = min(t.min_len() for t in distinct)
+        if proc["min_new_tokens"] > shortest:
+            raise ValueError(f"min_new_tokens = {proc['min_new_tokens']} exceeds the constraint's shortest sequence ({shortest} "
+                             "tokens): at its end only eos is allowed, and eos would be banned")
+        hit = sorted(set(proc["suppress_tokens"]) & (toks | {int(t) for t in eos_ids}))
+        if hit:
+            raise ValueError(f"suppress_tokens meets the constraint's tokens or the eos ids ({hit[:8]}): a row could be left "
+                             "without any token")
+    return tries
+
+
+def constrain_logits(scores, history, step: int, tries, eos_ids):
+    """The trie constraint, host statement (the device kernel is csrc/sampling.hip, logits_process_constrained_kernel): the rule
+    of transformers' ``PrefixConstrainedLogitsProcessor(lambda b, ids: tries[b].allowed(ids.tolist(), eos_ids), 1)`` with the
+    prompt passed as embeddings -- ``input_ids`` are the generated tokens only.
+
+    ``scores`` (R, V) fp32; row r has generated ``history[r, :step]``; ``tries``: one TokenTrie for every row, or a list of R.
+    Row r keeps the columns ``tries[r].allowed(history[r, :step], eos_ids)`` (ids outside [0, V) are skipped); every other
+    column becomes -inf.  Returns a new tensor.  It follows the repetition penalty in the chain; the other rules only write
+    -inf, so their order among themselves and with this one does not matter."""
+    R, V = scores.shape
+    if isinstance(tries, TokenTrie):
+        tries = [tries] * R
+    if len(tries) != R:
+        raise ValueError(f"{len(tries)} tries for {R} rows")
+    hist = torch.as_tensor(history)[:, :step].to(torch.int64).cpu().tolist()
+    keep = torch.zeros(R, V, dtype=torch.bool)
+    for r in range(R):
+        ids = [t for t in tries[r].allowed(hist[r], eos_ids) if 0 <= t < V]
+        if ids:
+            keep[r, torch.tensor(ids, dtype=torch.int64)] = True
+    return scores.masked_fill(~keep.to(scores.device), float("-inf"))
+
+
 MAX_EOS_IDS, MAX_STOP_SEQS, MAX_STOP_LEN = 8, 16, 16
 REASON_NONE, REASON_EOS, REASON_STOP = 0, 1, 2
 
@@ -552,7 +791,7 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
              return_past_key_values: bool = False, *, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
              min_new_tokens: int = 0, suppress_tokens=None, stop_sequences=None, stop_per_row: bool = None,
              return_finish: bool = False, sampler: str = "reference", min_p: float = 0.0, return_logprobs: bool = False,
-             top_logprobs: int = 0) -> Union[List[str], torch.Tensor]:
+             top_logprobs: int = 0, constraint=None) -> Union[List[str], torch.Tensor]:
     """reference sampling.py:43-121.  Token selection (argmax, or top-k / the reference's top-p rule / softmax /
     multinomial) and the ``(next_token == eos).all()`` test run on the device inside the captured token step; the host
     reads the recorded "first all-eos step" every ``eos_check_every`` steps (default 8, MAGMA_EOS_CHECK_EVERY) instead of
@@ -613,7 +852,20 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     probable than min_p times the most probable one go; 0 is off; ``min_p_filter``), then the same draw on the same stream.
     The HIP engine runs them in the selection launch of the captured token step (no further launch); any other LM object runs
     the host statements.  ``sampler="reference"`` (the default) is bit for bit what it was and takes no ``min_p``.  Greedy
-    decoding and beam search ignore the sampler, and raise ValueError for ``min_p`` > 0."""
+    decoding and beam search ignore the sampler, and raise ValueError for ``min_p`` > 0.
+
+    Constrained decoding (DESIGN.md "Constrained decoding"; greedy and sampled): ``constraint`` keeps every row's output inside
+    a closed set of answers -- a ``TokenTrie``, a list of token-id sequences or strings (``model.tokenizer.encode`` turns a string
+    into ids), or a list of B of either, one per row (multiple choice: other options for every question).  At every step a row may
+    select only a token that continues one of its sequences, an eos id only where a sequence ends, and after that (or once it has
+    left the trie) the eos ids alone: the rule of transformers' ``PrefixConstrainedLogitsProcessor`` over a trie
+    (``constrain_logits`` above), applied with the logits processors -- after the repetition penalty, before temperature / top-k /
+    top-p -- to the tokens generated by THIS call: a continued conversation starts at the root again.  The HIP engine applies it
+    in the processor launch of the captured token step (with a constraint alone: one small launch more per token); any other LM
+    object runs the host statement.  ``return_logprobs`` still reports the raw distribution.  Refused with ValueError, because a
+    row could be left without a token: ``no_repeat_ngram_size`` > 0, ``min_new_tokens`` above the shortest sequence,
+    ``suppress_tokens`` that meet the trie's tokens or the eos ids, a trie id >= V.  Not combined with beam search
+    (NotImplementedError).  ``constraint=None`` is the call as it was."""
     if eos_token is None or (isinstance(eos_token, int) and not eos_token):
         eos_token = model.eos_token
     early_stopping = check_beam_args(num_beams, num_return_sequences, early_stopping)
@@ -632,6 +884,9 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
                                   "(num_beams > 1 / return_scores=True): it has its own scores")
     eos_ids = stop["eos_ids"] if stop is not None else (eos_token,)
     eos_token = eos_ids[0]              # the pad id
+    if constraint is not None and (num_beams > 1 or return_scores):
+        raise NotImplementedError("a constraint is not combined with beam search (num_beams > 1 / return_scores=True): its "
+                                  "candidate lists would fill with -inf entries")
     continuing = past_key_values is not None or return_past_key_values
     if continuing and (num_beams > 1 or return_scores):
         raise NotImplementedError("beam search neither continues from nor returns a KV cache (past_key_values / "
@@ -649,6 +904,8 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
         lengths = derived
     b, s, _ = embeddings.shape
     dev = embeddings.device
+    cons = check_constraint_args(constraint, b, getattr(getattr(model, "tokenizer", None), "encode", None), _logit_count(model),
+                                 eos_ids, proc)
     # the HIP engine selects the token itself; any other LM object gets the reference's call (sampling.py:81-93)
     on_device = getattr(model.lm, "device_token_selection", False)
     if continuing and not on_device:
@@ -682,6 +939,9 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     if on_device and proc is not None:      # only then: an LM object written before the processors keeps its signature
         from .engine import LMEngine
         first_kw["processors"] = step_kw["processors"] = LMEngine.proc_mode(proc)      # checked once, not once per token
+    if on_device and cons is not None:      # only then, as above
+        from .engine import LMEngine
+        first_kw["constraint"] = step_kw["constraint"] = LMEngine.constraint_mode(cons)      # one table for the whole call
     if on_device and stop is not None:      # only then, as above
         from .engine import LMEngine
         first_kw["stop"] = step_kw["stop"] = LMEngine.stop_mode(stop)
@@ -719,8 +979,11 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
         if proc is not None:
             logits = process_logits(logits.cpu(), out[:, s:n].cpu(), n - s, eos_token=eos_ids if stop is not None else eos_token,
                                     **proc).to(logits.device)
+        if cons is not None:
+            logits = constrain_logits(logits.cpu(), out[:, s:n].cpu(), n - s, cons, eos_ids).to(logits.device)
         if greedy:
-            next_token = outputs.next_token.unsqueeze(1) if outputs.get("next_token") is not None and proc is None else \
+            next_token = outputs.next_token.unsqueeze(1) if outputs.get("next_token") is not None and proc is None \
+                and cons is None else \
                 torch.argmax(logits, dim=-1, keepdim=True)
         else:
             if warp is not None:
@@ -799,6 +1062,40 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     if n_top is not None:
         ret += (logprobs,)
     return ret if len(ret) > 1 else ret[0]
+
+
+def choose(model, embeddings, choices, lengths=None, **generate_kwargs):
+    """Which of ``choices`` the model answers with (Magma.choose): constrained greedy decoding with ``return_logprobs=True`` and
+    ``max_steps`` = the longest choice + 1, every row's tokens mapped back with ``TokenTrie.index``.  ``choices``: what
+    ``generate(constraint=...)`` takes.  Returns (index int64 [B] -- the position of the row's answer in its list of choices --,
+    TokenLogprobs of the path under the raw distribution; ``count[b]`` = the answer's tokens + the eos that ended it).
+    Rows stop on their own (``stop_per_row=True`` unless given).  It follows the GREEDY path through the trie: the most probable
+    next token among those allowed, step by step.  It is NOT the arg-max of the total sequence probability -- a choice whose
+    first token is unlikely loses even if the rest of it is certain; ``Magma.score`` gives every candidate's total."""
+    fixed = {"max_steps", "temperature", "decode", "constraint", "return_logprobs", "return_finish", "return_past_key_values",
+             "num_beams", "return_scores"} & set(generate_kwargs)
+    if fixed:
+        raise ValueError(f"choose() sets {sorted(fixed)} itself")
+    if is_embed_batch(embeddings):
+        embeddings, lengths = embeddings
+    b = len(embeddings) if isinstance(embeddings, (list, tuple)) else embeddings.shape[0]
+    tries = check_constraint_args(choices, b, getattr(getattr(model, "tokenizer", None), "encode", None), _logit_count(model))
+    if tries is None:
+        raise ValueError("choose() needs choices")
+    generate_kwargs.setdefault("stop_per_row", True)
+    _, lp = generate(model, embeddings, max_steps=max(t.max_len() for t in tries) + 1, temperature=0.0, decode=False,
+                     lengths=lengths, constraint=tries, return_logprobs=True, **generate_kwargs)
+    eos = generate_kwargs.get("eos_token")
+    if eos is None or (isinstance(eos, int) and not eos):
+        eos = model.eos_token
+    eos = set(eos.tolist() if torch.is_tensor(eos) else eos if isinstance(eos, (list, tuple)) else [eos])
+    index = torch.full((b,), -1, dtype=torch.int64)
+    for r in range(b):
+        ids = lp.tokens[r, : int(lp.count[r])].tolist()
+        while ids and ids[-1] in eos:
+            ids.pop()
+        index[r] = tries[r].index(ids)
+    return index, lp
 
 
 def keep_conversation(cache, start: torch.Tensor, n_gen: int, eos_token, finish: Finish = None):
