@@ -97,8 +97,9 @@ const char* mg_version(void);
  *  15  mg_ce_reduce_f32 gained `V` (after R): a target outside [0, V) is ignored by all three cross-entropy kernels alike; before,
  *      the reduction counted every target >= 0 although mg_ce_rows_f32 / mg_ce_bwd_bf16 gave such a row loss 0 and gradient 0.
  *  16  token log-probabilities: added mg_token_logprobs_f32 (nothing moved).
- *  17  constrained decoding: added mg_logits_process_constrained_f32 (nothing moved). */
-#define MG_ABI_VERSION 17
+ *  17  constrained decoding: added mg_logits_process_constrained_f32 (nothing moved).
+ *  18  classifier-free guidance: added mg_logits_guidance_f32 and mg_guidance_follow (nothing moved). */
+#define MG_ABI_VERSION 18
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -505,6 +506,24 @@ int mg_logits_process_constrained_f32(float* logits, int64_t ld, int32_t R, int3
                                       int32_t min_new_tokens, int64_t eos, const int32_t* suppress, int32_t n_suppress,
                                       const int32_t* eos_more, int32_t n_eos_more, const int32_t* table, int64_t table_ints,
                                       const int32_t* roots, int32_t* path, void* stream);
+
+/* Classifier-free guidance (ABI 18; DESIGN.md "Classifier-free guidance"; host statement: magma_amd/sampling.py, guide_logits):
+ * the rule of transformers' UnbatchedClassifierFreeGuidanceLogitsProcessor with the plausibility cut of contrastive decoding, in
+ * ONE enqueue-only, graph-capturable launch of one workgroup per pair of rows; no allocation, no scratch.  cond [R, ld_cond] and
+ * uncond [R, ld_uncond] fp32; columns >= V of either are neither read nor written, uncond is only read.  Per pair, in place on the
+ * conditional row, with c = log_softmax(cond row), u = log_softmax(uncond row) -- each (x - m) - log sum_v exp(x[v] - m), m the row
+ * maximum, maximum and sum of BOTH rows from one sweep over the pair (online form) --:
+ *   cond[i] = u[i] + scale * (c[i] - u[i])
+ *   cond[i] = -inf   where the old cond[i] is -inf, or (old cond[i] - m_cond) < log_min_p   (fp32 comparison on the RAW logits;
+ *                    log_min_p = -inf: no cut; the row maximum always stays, ties at the bound stay)
+ * scale finite and >= 0 (1: the conditional log_softmax), log_min_p <= 0; the unconditional rows must be finite.  Neither row
+ * start nor ld needs any alignment beyond 4 bytes (16-byte accesses are used where a row allows them), and the values do not
+ * depend on it: the order of every sum is a function of the element index alone, so equal rows give equal bits wherever they lie.
+ * mg_guidance_follow: the negative half of a guided batch follows the guided half after the bookkeeping launch:
+ *   token[R + r] = token[r];  d_pos[R + r] += delta  (pos_stride 1; d_pos NULL or pos_stride 0: positions left alone), r < R.  */
+int mg_logits_guidance_f32(float* cond, int64_t ld_cond, const float* uncond, int64_t ld_uncond, int32_t R, int32_t V, float scale,
+                           float log_min_p, void* stream);
+int mg_guidance_follow(int64_t* token, int32_t* d_pos, int32_t R, int32_t delta, int32_t pos_stride, void* stream);
 
 /* Token log-probabilities (ABI 16; DESIGN.md "Token log-probabilities"; host statement: magma_amd/sampling.py, token_logprobs):
  * how probable the model found a token, and the n_top most probable tokens beside it, in ONE enqueue-only, graph-capturable

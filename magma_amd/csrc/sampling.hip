@@ -669,6 +669,88 @@ __global__ __launch_bounds__(ST) void token_logprobs_kernel(const float* __restr
   }
 }
 
+// Classifier-free guidance (DESIGN.md "Classifier-free guidance"; host statement: sampling.py guide_logits): the rule of transformers'
+// UnbatchedClassifierFreeGuidanceLogitsProcessor -- out = u + scale * (c - u) over the log_softmax c of the conditional row and u of
+// the unconditional one -- and the plausibility cut of contrastive decoding on the RAW conditional logits, in place on the
+// conditional row.  One workgroup per pair of rows.  row_topk_body's max / logsumexp takes two sweeps per row; over a pair that
+// would be four sweeps and the output pass a fifth, so the two sweeps are folded into ONE: every thread keeps a running (maximum,
+// sum of exp(x - maximum)) per row, rescaling its sum when its maximum grows; the workgroup's maximum comes from blk_max, every
+// thread's sum is rescaled to it once and added by blk_sum -- the same fixed trees.  The output is formed by row_topk_body's
+// expression (x - max) - lse.  Which thread adds which elements, and in which order, depends on the element INDEX alone -- groups of
+// four from index 0, the last V % 4 elements one per thread -- never on where the row lies: equal rows give equal bits (and c - u = 0
+// exactly) wherever they sit, and a row gives the same values in the prefill's buffer as in the step's.  A row start is only 4-byte
+// aligned in general; a group is loaded (and stored) as one 16-byte access where the row allows it, as two 8-byte ones where it
+// allows those, else as four dwords -- the step's own logits rows (ld a multiple of 8) take the first form.
+MG_DEV void online_acc(float v, float& m, float& z) {
+  if (v > m) { z *= expf(m - v); m = v; }             // (m = -inf: z is 0 and stays 0)
+  if (v > -INFINITY) z += expf(v - m);
+}
+MG_DEV void online_acc4(const float4 q, float& m, float& z) {
+  const float vm = fmaxf(fmaxf(q.x, q.y), fmaxf(q.z, q.w));
+  if (vm > m) { z *= expf(m - vm); m = vm; }
+  if (vm > -INFINITY) z += (expf(q.x - m) + expf(q.y - m)) + (expf(q.z - m) + expf(q.w - m));
+}
+MG_DEV int row_align(const float* x) {                // 2: 16-byte aligned, 1: 8-byte, 0: 4-byte (the same for every group of the row)
+  const uint32_t a = (uint32_t)(uintptr_t)x & 15u;
+  return a == 0u ? 2 : a == 8u ? 1 : 0;
+}
+MG_DEV float4 load4(const float* p, int al) {
+  if (al == 2) return *reinterpret_cast<const float4*>(p);
+  if (al == 1) {
+    const float2 a = *reinterpret_cast<const float2*>(p), b = *reinterpret_cast<const float2*>(p + 2);
+    return make_float4(a.x, a.y, b.x, b.y);
+  }
+  return make_float4(p[0], p[1], p[2], p[3]);
+}
+MG_DEV void store4(float* p, int al, const float4 v) {
+  if (al == 2) *reinterpret_cast<float4*>(p) = v;
+  else if (al == 1) { *reinterpret_cast<float2*>(p) = make_float2(v.x, v.y); *reinterpret_cast<float2*>(p + 2) = make_float2(v.z, v.w); }
+  else { p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w; }
+}
+MG_DEV void row_online(const float* x, int V, float& m, float& z) {
+  const int tid = threadIdx.x, nvec = V >> 2, al = row_align(x);
+  for (int i = tid; i < nvec; i += ST) online_acc4(load4(x + 4 * i, al), m, z);
+  if (tid < V - 4 * nvec) online_acc(x[4 * nvec + tid], m, z);
+}
+
+__global__ __launch_bounds__(ST) void logits_guidance_kernel(float* cond, int64_t ld_cond, const float* uncond, int64_t ld_uncond,
+                                                             int V, float scale, float log_min_p) {
+  __shared__ float shf[ST / 64];
+  const int tid = threadIdx.x;
+  float* xc = cond + (int64_t)blockIdx.x * ld_cond;
+  const float* xu = uncond + (int64_t)blockIdx.x * ld_uncond;
+  float mc = -INFINITY, zc = 0.f, mu = -INFINITY, zu = 0.f;
+  row_online(xc, V, mc, zc);
+  row_online(xu, V, mu, zu);
+  const float Mc = blk_max(mc, shf), Mu = blk_max(mu, shf);
+  const float lc = logf(blk_sum(mc > -INFINITY ? zc * expf(mc - Mc) : 0.f, shf));
+  const float lu = logf(blk_sum(mu > -INFINITY ? zu * expf(mu - Mu) : 0.f, shf));
+  // (the barriers of the reductions stand between every read above and every write below)
+  auto guide = [&](float c, float u) -> float {
+    const float d = c - Mc;
+    if (c == -INFINITY || d < log_min_p) return -INFINITY;       // a conditional -inf stays; the cut is on the raw logits
+    const float lpc = d - lc, lpu = (u - Mu) - lu;
+    return lpu + scale * (lpc - lpu);
+  };
+  const int nvec = V >> 2, alc = row_align(xc), alu = row_align(xu);
+  for (int i = tid; i < nvec; i += ST) {
+    float4 c = load4(xc + 4 * i, alc);
+    const float4 u = load4(xu + 4 * i, alu);
+    c.x = guide(c.x, u.x); c.y = guide(c.y, u.y); c.z = guide(c.z, u.z); c.w = guide(c.w, u.w);
+    store4(xc + 4 * i, alc, c);
+  }
+  if (tid < V - 4 * nvec) xc[4 * nvec + tid] = guide(xc[4 * nvec + tid], xu[4 * nvec + tid]);
+}
+
+// The negative half of a guided batch follows the guided half: after the bookkeeping launch (a finished row's pad id included)
+// token[R + r] = token[r], and row R + r's KV write position advances as row r's did.
+__global__ void guidance_follow_kernel(int64_t* __restrict__ token, int32_t* __restrict__ d_pos, int R, int delta) {
+  for (int r = threadIdx.x; r < R; r += blockDim.x) {
+    token[R + r] = token[r];
+    if (d_pos) d_pos[R + r] += delta;
+  }
+}
+
 // Logits processors (DESIGN.md "Logits processors"): the rules of transformers' RepetitionPenaltyLogitsProcessor,
 // NoRepeatNGramLogitsProcessor, MinNewTokensLengthLogitsProcessor and SuppressTokensLogitsProcessor, in that order, restated on the
 // host in magma_amd/sampling.py (process_logits), as ONE enqueue-only launch in front of the selection launch: one workgroup per
@@ -1055,6 +1137,26 @@ extern "C" int mg_token_logprobs_f32(const float* logits, int64_t ld, int32_t R,
   static_assert(MG_LOGPROBS_MAX_TOP <= BK2_MAX, "the top lists are collected in row_topk_body's slots");
   hipLaunchKernelGGL(token_logprobs_kernel, dim3(R), dim3(ST), 0, (hipStream_t)stream, logits, ld, V, token, state, lp, ld_lp, cols,
                      n_top, n_top > 0 ? top_id : nullptr, n_top > 0 ? top_lp : nullptr);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_logits_guidance_f32(float* cond, int64_t ld_cond, const float* uncond, int64_t ld_uncond, int32_t R, int32_t V,
+                                      float scale, float log_min_p, void* stream) {
+  if (!cond || !uncond || R <= 0 || V <= 0 || ld_cond < V || ld_uncond < V)
+    MG_FAIL(MG_ERR_SHAPE, "mg_logits_guidance_f32: bad cond / uncond / R / V / ld");
+  if (!(scale >= 0.f) || scale == INFINITY) MG_FAIL(MG_ERR_SHAPE, "mg_logits_guidance_f32: scale must be finite and >= 0");
+  if (!(log_min_p <= 0.f)) MG_FAIL(MG_ERR_SHAPE, "mg_logits_guidance_f32: log_min_p must be <= 0 (-inf: no cut)");
+  hipLaunchKernelGGL(logits_guidance_kernel, dim3(R), dim3(ST), 0, (hipStream_t)stream, cond, ld_cond, uncond, ld_uncond, V, scale,
+                     log_min_p);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_guidance_follow(int64_t* token, int32_t* d_pos, int32_t R, int32_t delta, int32_t pos_stride, void* stream) {
+  if (!token || R <= 0) MG_FAIL(MG_ERR_SHAPE, "mg_guidance_follow: bad arguments");
+  if (pos_stride != 0 && pos_stride != 1) MG_FAIL(MG_ERR_SHAPE, "mg_guidance_follow: pos_stride must be 0 or 1");
+  hipLaunchKernelGGL(guidance_follow_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, token, pos_stride ? d_pos : nullptr, R, delta);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }

@@ -223,6 +223,10 @@ class ConstraintMode:
         self.max_token = max(max(t.tokens()) for t in {id(t): t for t in tries}.values())
 
 
+class GuidanceMode(tuple):
+    """LMEngine.guidance_mode's checked (guidance_scale, guidance_min_p): passed again as ``guidance=`` it is taken as it is."""
+
+
 class LMEngine:
     def __init__(self, lm):
         cfg = lm.config
@@ -613,7 +617,7 @@ class LMEngine:
                 output_hidden_states=False, cache_hint: Optional[int] = None, reuse_cache: bool = False,
                 return_logits: bool = False, sampling=None, eos_token: Optional[int] = None,
                 seed: Optional[int] = None, feed_back: bool = False, lengths=None, beam=None, processors=None,
-                stop=None, logprobs=None, constraint=None) -> LMOutput:
+                stop=None, logprobs=None, constraint=None, guidance=None) -> LMOutput:
         """``beam`` = (num_beams, length_penalty, early_stopping, max_steps): beam-search token selection (the rows are
         samples x num_beams, sample-major; DESIGN.md "Beam search") instead of ``sampling``.
         ``processors`` (sampling.check_processor_args' dict, or None): the logits processors in front of whichever selection
@@ -629,6 +633,12 @@ class LMEngine:
         ``constraint`` (a list of one sampling.TokenTrie per row, constraint_mode's object, or None): the trie constraint in the
         processors' launch (DESIGN.md "Constrained decoding") -- it counts as a processor: the first token comes from a processed
         copy, with ``logprobs`` the step works on the second buffer; passed like ``processors``; not with ``beam``.
+        ``guidance`` ((guidance_scale, guidance_min_p), guidance_mode's object, or None): classifier-free guidance (DESIGN.md
+        "Classifier-free guidance").  The batch is 2R ragged rows: rows [0, R) the prompts, rows [R, 2R) the negative prompts.  One
+        launch combines row r with row R + r in front of the processors, everything from there to the bookkeeping runs over the
+        first R rows (and the first R rows of the per-row buffers), one launch copies the token to row R + r and advances its
+        position.  It counts as a processor (first token from a copy; with ``logprobs`` the second buffer, the log-probabilities
+        are those of the raw conditional rows); passed like ``processors``; not with ``beam``, not when continuing a cache.
         ``lengths`` (int [B], 1 <= len_b <= S; prefill with use_cache=True only): the rows of ``inputs_embeds`` are prompts
         of different lengths, right-padded to S.  Row b's logits are those of its position len_b - 1, and the cache keeps one
         write position per row (len_b, then + 1 per step) -- see DESIGN.md, "Ragged batches"."""
@@ -639,6 +649,10 @@ class LMEngine:
             raise NotImplementedError("token log-probabilities are not combined with beam search (it has its own scores)")
         if constraint is not None and beam is not None:
             raise NotImplementedError("a constraint is not combined with beam search")
+        if guidance is not None and beam is not None:
+            raise NotImplementedError("guidance is not combined with beam search")
+        if guidance is not None and extending:
+            raise NotImplementedError("guidance does not continue from a KV cache")
         if lengths is not None and (labels is not None or (past_key_values is not None and not extending) or not use_cache):
             raise ValueError("lengths= applies to the prefill call and to inputs_embeds appended to a cache (use_cache=True, no "
                              "labels); a ragged cache keeps its per-row positions for the steps that follow")
@@ -670,12 +684,14 @@ class LMEngine:
                 rows = []
                 for i in range(T):      # only the LAST position selects a token (history / RNG step / eos latch untouched before)
                     lg, tok = self.decode(input_ids[:, i:i + 1], past_key_values, sampling=sampling, select=i == T - 1,
-                                          beam=beam, processors=processors, stop=stop, logprobs=logprobs, constraint=constraint)
+                                          beam=beam, processors=processors, stop=stop, logprobs=logprobs, constraint=constraint,
+                                          guidance=guidance)
                     rows.append(lg.clone())
                 return LMOutput(logits=torch.stack(rows, 1), past_key_values=past_key_values, next_token=tok, loss=None,
                                 eos_state=past_key_values.sample_state)
             logits, tok = self.decode(None if feed_back else input_ids, past_key_values, sampling=sampling, beam=beam,
-                                      processors=processors, stop=stop, logprobs=logprobs, constraint=constraint)
+                                      processors=processors, stop=stop, logprobs=logprobs, constraint=constraint,
+                                      guidance=guidance)
             return LMOutput(logits=logits.unsqueeze(1), past_key_values=past_key_values, next_token=tok, loss=None,
                             eos_state=past_key_values.sample_state)
         if inputs_embeds is None:
@@ -685,7 +701,8 @@ class LMEngine:
             # generate() only reads the last position, so only that row is computed
             out = LMOutput(logits=logits.unsqueeze(1), past_key_values=cache, hidden_states=hs, loss=None)
             if eos_token is not None:
-                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, beam, processors, stop, logprobs, constraint)
+                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, beam, processors, stop, logprobs, constraint,
+                                      guidance)
             return out
         x, hs = self._blocks_prefill(inputs_embeds, None, output_hidden_states)
         B, S, _ = inputs_embeds.shape
@@ -737,7 +754,28 @@ class LMEngine:
             return constraint
         return ConstraintMode(list(constraint))
 
-    def _arm_constraint(self, cache: KVCache, cons):
+    @staticmethod
+    def guidance_mode(guidance):
+        """None (today's launches) or a GuidanceMode (guidance_scale, guidance_min_p): the guidance mode that travels beside the
+        processor mode; its values are launch arguments of the captured step, so it is part of the step's key."""
+        if guidance is None or isinstance(guidance, GuidanceMode):
+            return guidance
+        from .sampling import check_guidance_values
+        scale, min_p = guidance
+        check_guidance_values(scale, min_p)
+        return GuidanceMode((float(scale), float(min_p)))
+
+    @staticmethod
+    def _guided_rows(cache: KVCache, gd) -> int:
+        """The rows the selection runs over: all of the cache's, or -- guided -- its first half."""
+        if gd is None:
+            return cache.B
+        if cache.B % 2 or cache.pos_stride != 1:
+            raise ValueError(f"guidance needs a ragged cache of 2R rows (prompts, then negative prompts), got {cache.B} rows"
+                             f"{'' if cache.pos_stride == 1 else ' with one shared position'}")
+        return cache.B // 2
+
+    def _arm_constraint(self, cache: KVCache, cons, rows: Optional[int] = None):
         """The table and the roots of ``cons`` in the cache's device buffers (written only when they differ from what the buffers
         hold; never inside a captured step: decode() calls this before it captures or replays).  A table that outgrows the
         buffer re-allocates it, which drops the steps captured on it (KVCache.alloc_trie)."""
@@ -745,14 +783,15 @@ class LMEngine:
             return
         if cons.max_token >= self.V:
             raise ValueError(f"the constraint holds token ids outside [0, {self.V})")
-        if cons.roots.numel() != cache.B:
-            raise ValueError(f"the constraint has {cons.roots.numel()} rows, the cache {cache.B}")
+        rows = cache.B if rows is None else rows      # (guided: the first half of the cache's rows)
+        if cons.roots.numel() != rows:
+            raise ValueError(f"the constraint has {cons.roots.numel()} rows, the cache {rows}")
         cache.alloc_trie(cons.table.numel())
         held = cache.trie_held
         if held is cons or (held is not None and torch.equal(held.table, cons.table) and torch.equal(held.roots, cons.roots)):
             return
         cache.trie_table[: cons.table.numel()].copy_(cons.table, non_blocking=True)
-        cache.trie_roots.copy_(cons.roots, non_blocking=True)
+        cache.trie_roots[:rows].copy_(cons.roots, non_blocking=True)
         cache.trie_held = cons
 
     @staticmethod
@@ -801,7 +840,7 @@ class LMEngine:
             st.logits_proc = torch.empty_like(st.logits)
 
     def _arm_first_token(self, out: LMOutput, logits, cache: KVCache, eos_token, seed, sampling, beam, processors=None, stop=None,
-                         logprobs=None, constraint=None):
+                         logprobs=None, constraint=None, guidance=None):
         """generate(): the first token of the loop selected from the prefill / extend logits, device-side bookkeeping armed."""
         if cache.eos != int(eos_token):        # the eos id is a launch argument of the captured bookkeeping kernel
             cache.eos = int(eos_token)
@@ -822,13 +861,14 @@ class LMEngine:
                 del st.graphs[key]
         proc = self.proc_mode(processors)
         cons = self.constraint_mode(constraint)   # (forward has refused the combination with beam)
+        gd = self.guidance_mode(guidance)         # (the same)
         raw = logits
-        if proc is not None or cons is not None:       # step 0 of the rules on a copy: the caller's .logits stay raw
+        if proc is not None or cons is not None or gd is not None:       # step 0 of the rules on a copy: the caller's .logits stay raw
             self._arm_processors(cache, proc)
-            self._arm_constraint(cache, cons)
+            self._arm_constraint(cache, cons, self._guided_rows(cache, gd))
             logits = logits.clone()
         n_top = self.logprob_mode(logprobs)       # (forward has refused the combination with beam)
-        self._arm_logprobs(cache, st, n_top, proc if proc is not None else cons)
+        self._arm_logprobs(cache, st, n_top, proc if proc is not None else cons if cons is not None else gd)
         stop = self.stop_mode(stop)
         if stop is not None:       # every row unfinished again
             if int(eos_token) != stop[0][0]:
@@ -836,7 +876,7 @@ class LMEngine:
             self._arm_stop(cache, stop)
             cache.finish.copy_(torch.tensor([[-1, 0]] * cache.B, dtype=torch.int32), non_blocking=True)
         out["next_token"] = self.select_token(logits, cache, mode, out=st.token, proc=proc, stop=stop, logprobs=n_top, raw=raw,
-                                                cons=cons)
+                                                cons=cons, guidance=gd)
         out["eos_state"] = cache.sample_state
 
     def embed_ids(self, ids: torch.Tensor) -> torch.Tensor:
@@ -1133,7 +1173,7 @@ class LMEngine:
 
     def select_token(self, logits: torch.Tensor, cache: KVCache, mode, out: Optional[torch.Tensor] = None,
                      advance: bool = False, clear: Optional[torch.Tensor] = None, proc=None, stop=None, logprobs=None,
-                     raw: Optional[torch.Tensor] = None, cons=None) -> torch.Tensor:
+                     raw: Optional[torch.Tensor] = None, cons=None, guidance=None) -> torch.Tensor:
         """next token of every row from fp32 logits (B, V): greedy argmax (mode None; reference sampling.py:96-97) or the
         sampled branch (mode = (temperature, top_k, top_p); :99-107 -- or ("warp", temperature, top_k, top_p, min_p):
         transformers' sampler, sample_mode), then the loop bookkeeping in one small launch
@@ -1149,19 +1189,29 @@ class LMEngine:
         token's log-probability and the n_top alternatives of ``raw`` (default ``logits``): the rows as they were before ``proc``.
         ``cons`` (constraint_mode; table and roots already in the cache's buffers, _arm_constraint): the processors' launch is the
         constrained one (ops.logits_process_constrained) -- ``proc``'s rules, or neutral values, then the trie constraint with
-        every eos id --: with ``proc`` as many launches as without ``cons``, without ``proc`` one more."""
+        every eos id --: with ``proc`` as many launches as without ``cons``, without ``proc`` one more.
+        ``guidance`` (guidance_mode): ``logits`` / ``raw`` / ``out`` hold 2R rows.  First ops.logits_guidance in place on rows
+        [0, R) against rows [R, 2R); then all of the above over the first R rows of everything; last ops.guidance_follow mirrors
+        the tokens into ``out[R:]`` and advances the positions of rows [R, 2R).  Two launches more.  Returns the R tokens."""
+        half = None
+        if guidance is not None:
+            R = self._guided_rows(cache, guidance)
+            assert out is not None and logits.shape[0] == 2 * R and not (isinstance(mode, tuple) and mode[:1] == ("beam",))
+            ops.logits_guidance(logits[:R], logits[R:], guidance[0], guidance[1])
+            half, logits, raw, out = out, logits[:R], None if raw is None else raw[:R], out[:R]
+        rows = (lambda t: t) if guidance is None else (lambda t: None if t is None else t[:R])   # the per-row buffers' share
         is_beam = isinstance(mode, tuple) and bool(mode) and mode[0] == "beam"
         if proc is not None or cons is not None:
             more = {} if stop is None or len(stop[0]) < 2 else dict(eos_more=cache.stop_table[1:ops.STOP_MAX_EOS],
                                                                     n_eos_more=len(stop[0]) - 1)
         if cons is not None:
             rules = proc if proc is not None else (1.0, 0, 0, ())
-            ops.logits_process_constrained(logits, cache.sample_state, cache.history, cache.trie_table, cache.trie_roots,
+            ops.logits_process_constrained(logits, cache.sample_state, rows(cache.history), cache.trie_table, cache.trie_roots,
                                            cache.trie_path, repetition_penalty=rules[0], no_repeat_ngram_size=rules[1],
                                            min_new_tokens=rules[2], eos=cache.eos, suppress=cache.suppress,
                                            n_suppress=len(rules[3]), **more)
         elif proc is not None:
-            ops.logits_process(logits, cache.sample_state, cache.history, repetition_penalty=proc[0], no_repeat_ngram_size=proc[1],
+            ops.logits_process(logits, cache.sample_state, rows(cache.history), repetition_penalty=proc[0], no_repeat_ngram_size=proc[1],
                                min_new_tokens=proc[2], eos=cache.eos, suppress=cache.suppress, n_suppress=len(proc[3]),
                                normalize=is_beam, **more)
         if is_beam:
@@ -1173,18 +1223,22 @@ class LMEngine:
         else:
             tok = ops.sample(logits, mode[0], mode[1], mode[2], cache.seed, cache.sample_state, out=out)
         if logprobs is not None:
-            ops.token_logprobs(logits if raw is None else raw, tok, cache.lp, cache.top_id if logprobs else None,
-                               cache.top_lp if logprobs else None, state=cache.sample_state)
+            ops.token_logprobs(logits if raw is None else raw, tok, rows(cache.lp), rows(cache.top_id) if logprobs else None,
+                               rows(cache.top_lp) if logprobs else None, state=cache.sample_state)
         if stop is not None:
-            ops.sample_finish_rows(tok, cache.sample_state, cache.stop_table, len(stop[0]), len(stop[1]), stop[0][0], cache.finish,
-                                   d_pos=cache.d_pos if advance else None, history=cache.history, clear=clear,
-                                   clear_stride=16 if clear is not None else 1, pos_stride=cache.pos_stride)
-            return tok
-        ops.sample_finish(tok, cache.eos, cache.sample_state, d_pos=cache.d_pos if advance else None, history=cache.history,
-                          clear=clear, clear_stride=16 if clear is not None else 1, pos_stride=cache.pos_stride)
+            ops.sample_finish_rows(tok, cache.sample_state, cache.stop_table, len(stop[0]), len(stop[1]), stop[0][0],
+                                   rows(cache.finish), d_pos=cache.d_pos if advance else None, history=rows(cache.history),
+                                   clear=clear, clear_stride=16 if clear is not None else 1, pos_stride=cache.pos_stride)
+        else:
+            ops.sample_finish(tok, cache.eos, cache.sample_state, d_pos=cache.d_pos if advance else None,
+                              history=rows(cache.history), clear=clear, clear_stride=16 if clear is not None else 1,
+                              pos_stride=cache.pos_stride)
+        if half is not None:        # after the bookkeeping: a finished row's pad id is mirrored too
+            ops.guidance_follow(half, cache.d_pos if advance else None, R, pos_stride=cache.pos_stride)
         return tok
 
-    def _decode_step(self, cache: KVCache, st, mode=None, feed_back: bool = False, proc=None, stop=None, logprobs=None, cons=None):
+    def _decode_step(self, cache: KVCache, st, mode=None, feed_back: bool = False, proc=None, stop=None, logprobs=None, cons=None,
+                     guidance=None):
         """Enqueue one token step for all B sequences (graph-capturable: no
         allocation, no sync, position read from cache.d_pos on the device): embedding, per layer the launch sequence of the
         kind planned for it (st.kinds, _ensure_decode_state), the head, token selection.
@@ -1204,15 +1258,15 @@ class LMEngine:
             ops.gemm_skinny(x, head, out=st.logits, ln_fold=(head.colsum, self.d, self.eps))
         if mode == "noselect":
             ops.advance_pos(cache.d_pos, pos_stride=cache.pos_stride)   # teacher-forced position: nothing selected, nothing recorded
-        elif logprobs is not None and (proc is not None or cons is not None):
+        elif logprobs is not None and (proc is not None or cons is not None or guidance is not None):
             # the processors run in place: they and the selection get a copy (one device copy inside the step), the
             # log-probabilities read the untouched st.logits
             st.logits_proc.copy_(st.logits)
             self.select_token(st.logits_proc[:, : self.V], cache, mode, out=st.token, advance=True, proc=proc, stop=stop,
-                              logprobs=logprobs, raw=st.logits[:, : self.V], cons=cons)
+                              logprobs=logprobs, raw=st.logits[:, : self.V], cons=cons, guidance=guidance)
         else:
             self.select_token(st.logits[:, : self.V], cache, mode, out=st.token, advance=True, proc=proc, stop=stop,
-                              logprobs=logprobs, cons=cons)
+                              logprobs=logprobs, cons=cons, guidance=guidance)
 
     # One method per block kind (_block_kind): x -> xn for layer li.  ``src`` holds the block's weight-streaming operands: the
     # layer itself, or its e4m3 / MXFP4 copies (ly.w8 / ly.w4) under W8A16 / W4A16 -- the same launches.  On a ragged cache (pos_stride 1) every
@@ -1341,7 +1395,7 @@ class LMEngine:
         return st
 
     def decode(self, input_ids: Optional[torch.Tensor], cache: KVCache, use_graph: bool = True, sampling=None, select: bool = True,
-               beam=None, processors=None, stop=None, logprobs=None, constraint=None):
+               beam=None, processors=None, stop=None, logprobs=None, constraint=None, guidance=None):
         """One cached step.  Returns (fp32 logits (B,V) view, selected token (B,) view: greedy, or sampled when
         ``sampling = (temperature, top_k, top_p)`` or ``("warp", temperature, top_k, top_p, min_p)``, sample_mode); both are
         overwritten by the next step.  ``input_ids=None`` feeds the
@@ -1354,7 +1408,9 @@ class LMEngine:
         extend call; the returned token view holds the pad id for rows that had finished.
         ``logprobs`` (forward): the step also writes column step of the cache's log-probability buffers, from the RAW logits; with
         ``processors`` too, those and the selection run on a second buffer, whose rows are what is returned.
-        ``constraint`` (forward): the trie constraint in the processors' launch; it counts as one of them in all of the above."""
+        ``constraint`` (forward): the trie constraint in the processors' launch; it counts as one of them in all of the above.
+        ``guidance`` (forward): the cache's 2R rows are R pairs; the returned token view holds the R selected tokens twice, the
+        returned logits hold the guided rows [0, R) in place of the conditional ones."""
         if cache.pos >= cache.Smax:
             raise ValueError(f"KV cache full (Smax={cache.Smax}); pass a larger cache_hint / max_steps")
         if cache.B > 16:
@@ -1396,8 +1452,11 @@ class LMEngine:
         cons = self.constraint_mode(constraint) if select else None
         if cons is not None and beam is not None:
             raise NotImplementedError("a constraint is not combined with beam search")
-        self._arm_constraint(cache, cons)
-        self._arm_logprobs(cache, st, n_top, proc if proc is not None else cons)
+        gd = self.guidance_mode(guidance) if select else None
+        if gd is not None and beam is not None:
+            raise NotImplementedError("guidance is not combined with beam search")
+        self._arm_constraint(cache, cons, self._guided_rows(cache, gd))
+        self._arm_logprobs(cache, st, n_top, proc if proc is not None else cons if cons is not None else gd)
         key = (mode, feed_back)
         if proc is not None:        # the values are launch arguments of the captured step (the suppress ids are not: their count is)
             key += (tuple(proc[:3]) + (len(proc[3]),),)
@@ -1407,21 +1466,24 @@ class LMEngine:
             key += (("logprobs", n_top),)
         if cons is not None:        # the buffers' addresses and the table's capacity are launch arguments, their contents are not
             key += (("constraint",),)
+        if gd is not None:          # scale and cut are launch arguments
+            key += (("guidance",) + tuple(gd),)
         if not use_graph:
-            self._decode_step(cache, st, mode, feed_back, proc, stop, n_top, cons)
+            self._decode_step(cache, st, mode, feed_back, proc, stop, n_top, cons, gd)
         elif key in st.graphs:
             st.graphs[key].replay()
         elif st.steps == 0:
-            self._decode_step(cache, st, mode, feed_back, proc, stop, n_top, cons)    # first step eager (loads code objects)
+            self._decode_step(cache, st, mode, feed_back, proc, stop, n_top, cons, gd)    # first step eager (loads code objects)
         else:
             g = torch.cuda.CUDAGraph()            # hipGraph on ROCm
             with torch.cuda.graph(g):
-                self._decode_step(cache, st, mode, feed_back, proc, stop, n_top, cons)
+                self._decode_step(cache, st, mode, feed_back, proc, stop, n_top, cons, gd)
             st.graphs[key] = g
             g.replay()
         st.steps += 1
         cache.pos += 1
-        return (st.logits_proc if n_top is not None and (proc is not None or cons is not None) else st.logits)[:, : self.V], st.token
+        second = n_top is not None and (proc is not None or cons is not None or gd is not None)
+        return (st.logits_proc if second else st.logits)[:, : self.V], st.token
 
     # ------------------------------------------------- loss (eval) forward
     def forward_loss(self, embeds: torch.Tensor, labels: torch.Tensor, want_hidden=False, want_logits=False) -> LMOutput:

@@ -19,7 +19,7 @@ MG_A_DENSE, MG_A_CONV3X3 = 0, 1
 MG_AUX_NONE, MG_AUX_RELU_GATE, MG_AUX_GELU_GRAD, MG_AUX_MUL, MG_AUX_QUICK_GELU_GRAD = 0, 1, 2, 3, 4
 
 
-ABI_VERSION = 17     # include/magma_hip.h MG_ABI_VERSION
+ABI_VERSION = 18     # include/magma_hip.h MG_ABI_VERSION
 
 
 class MagmaHipError(RuntimeError):
@@ -130,6 +130,8 @@ SYMBOLS = {
                                         _vp]),
     "mg_logits_process_constrained_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _f32, _i32, _i32, _i64, _vp, _i32, _vp,
                                                     _i32, _vp, _i64, _vp, _vp, _vp]),
+    "mg_logits_guidance_f32": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _f32, _f32, _vp]),
+    "mg_guidance_follow": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "mg_beam_finish": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, C.c_double, _i32, _i32, _vp, _vp, _i32, C.POINTER(BeamState), _vp]),
     "mg_kv_reorder_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "mg_patchify_bf16": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),

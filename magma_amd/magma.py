@@ -223,12 +223,15 @@ class Magma(nn.Module):
         return out
 
     @torch.no_grad()
-    def embed_batch(self, batch: List[list]) -> Tuple[torch.Tensor, torch.Tensor]:
+    def embed_batch(self, batch: List[list], drop_images: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
         """A batch of requests with prompts of different lengths: ``batch`` is a list of per-sample input lists, each
         element a str, an ImageInput or an already preprocessed tensor (batch dimension 1) as ``preprocess_inputs`` /
         ``embed`` take them.  Returns (embeddings (B, S_max, d), right-padded with zeros; lengths int64 [B]) -- the
         arguments of ``generate(embeddings, lengths=lengths)``.  The caller's lists are left as they are; every image of
-        the batch goes through ONE image_prefix call."""
+        the batch goes through ONE image_prefix call.
+        ``drop_images=True``: the same samples with every ImageInput / 4-D item left out (no image is transformed or encoded)
+        -- the text-only negative prompt of ``generate(..., guidance_scale=, negative_embeddings=)``; a sample that is left
+        without inputs raises ValueError."""
         from . import ops
         torch.cuda.set_device(self.device)
         if not batch:
@@ -237,6 +240,8 @@ class Magma(nn.Module):
         for sample in batch:
             items = []
             for inp in sample:
+                if drop_images and (isinstance(inp, ImageInput) or (isinstance(inp, torch.Tensor) and inp.ndim == 4)):
+                    continue
                 if isinstance(inp, str):
                     inp = self.tokenizer.encode(inp, return_tensors="pt")
                 elif isinstance(inp, ImageInput):
@@ -249,7 +254,7 @@ class Magma(nn.Module):
                     raise ValueError(f"embed_batch takes one sample per list: batch dimension 1, got {tuple(inp.shape)}")
                 items.append(inp)
             if not items:
-                raise ValueError("embed_batch: a sample without inputs")
+                raise ValueError("embed_batch: a sample without inputs" + (" once its images are dropped" if drop_images and sample else ""))
             samples.append(items)
         images = [x for items in samples for x in items if x.ndim == 4]
         prefix = None
@@ -282,7 +287,8 @@ class Magma(nn.Module):
                  return_past_key_values: bool = False, *, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
                  min_new_tokens: int = 0, suppress_tokens=None, eos_token=None, stop_sequences=None, stop_per_row: bool = None,
                  return_finish: bool = False, sampler: str = "reference", min_p: float = 0.0, return_logprobs: bool = False,
-                 top_logprobs: int = 0, constraint=None):
+                 top_logprobs: int = 0, constraint=None, guidance_scale: float = 1.0, negative_embeddings=None,
+                 negative_lengths=None, guidance_min_p: float = 0.0):
         """reference magma.py:214-236 (+ stop_on_eos / seed / eos_check_every / lengths, see sampling.generate).
         ``lengths``: prompts of different lengths, right-padded (embed_batch); ``embeddings`` may also be a list of
         per-sample (1, s_i, d) tensors.  ``num_beams`` > 1: beam search (length_penalty, early_stopping,
@@ -298,7 +304,11 @@ class Magma(nn.Module):
         ``return_logprobs`` / ``top_logprobs`` (0 to 20 alternatives per token): a ``TokenLogprobs`` appended to the result -- every
         generated token's log-probability under the raw model distribution, as ``score`` gives it (see sampling.generate).
         ``constraint`` (a ``sampling.TokenTrie``, a list of token-id sequences or strings, or one of either per row): every row's
-        output stays inside that closed set of answers, followed by eos (see sampling.generate; ``choose`` maps it back)."""
+        output stays inside that closed set of answers, followed by eos (see sampling.generate; ``choose`` maps it back).
+        ``guidance_scale`` (1.0 = off) / ``negative_embeddings`` (what ``embeddings`` takes; ``embed_batch(batch, drop_images=True)``
+        gives the text-only prompt) / ``negative_lengths`` / ``guidance_min_p``: classifier-free guidance against a negative prompt
+        -- transformers' ``guidance_scale`` / ``negative_prompt_ids`` rule with the plausibility cut of contrastive decoding, inside
+        the token step; the output is laid out as for ``embeddings`` alone (see sampling.generate)."""
         torch.cuda.set_device(self.device)
         return generate(self, embeddings=embeddings, max_steps=max_steps, temperature=temperature, top_k=top_k,
                         top_p=top_p, decode=decode, stop_on_eos=stop_on_eos, seed=seed, eos_check_every=eos_check_every,
@@ -308,7 +318,9 @@ class Magma(nn.Module):
                         repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
                         min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens, eos_token=eos_token,
                         stop_sequences=stop_sequences, stop_per_row=stop_per_row, return_finish=return_finish, sampler=sampler,
-                        min_p=min_p, return_logprobs=return_logprobs, top_logprobs=top_logprobs, constraint=constraint)
+                        min_p=min_p, return_logprobs=return_logprobs, top_logprobs=top_logprobs, constraint=constraint,
+                        guidance_scale=guidance_scale, negative_embeddings=negative_embeddings, negative_lengths=negative_lengths,
+                        guidance_min_p=guidance_min_p)
 
     @torch.no_grad()
     def choose(self, embeddings, choices, lengths=None, **generate_kwargs):

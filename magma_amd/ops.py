@@ -800,6 +800,36 @@ def logits_process_constrained(logits: torch.Tensor, state: torch.Tensor, histor
     return logits
 
 
+def logits_guidance(cond: torch.Tensor, uncond: torch.Tensor, scale: float, min_p: float = 0.0):
+    """Classifier-free guidance in place on the fp32 rows ``cond`` (R, V) against ``uncond`` (R, V), one launch of one workgroup
+    per pair (mg_logits_guidance_f32; host statement: sampling.guide_logits): with c / u the log_softmax of the two rows,
+    cond = u + scale * (c - u); a conditional -inf stays -inf; ``min_p`` > 0 also writes -inf where cond - max(cond) <
+    log(min_p) (fp32 comparison against the fp32 rounding of the float64 log, on the raw conditional logits).  ``uncond`` is
+    only read and must be finite; both are views of any row stride.  Enqueue-only."""
+    _need_gpu(cond, uncond)
+    assert cond.dtype == torch.float32 and cond.ndim == 2 and cond.stride(1) == 1
+    assert uncond.dtype == torch.float32 and uncond.shape == cond.shape and uncond.stride(1) == 1
+    R, V = cond.shape
+    if not 0.0 <= float(min_p) <= 1.0:
+        raise ValueError(f"min_p must lie in [0, 1], got {min_p!r}")
+    log_min_p = float(torch.tensor(float(min_p), dtype=torch.float64).log().to(torch.float32)) if float(min_p) > 0.0 else float("-inf")
+    check(L.load().mg_logits_guidance_f32(cond.data_ptr(), cond.stride(0) if R > 1 else max(cond.stride(0), V), uncond.data_ptr(),
+                                          uncond.stride(0) if R > 1 else max(uncond.stride(0), V), R, V, float(scale), log_min_p,
+                                          _stream()), "mg_logits_guidance_f32")
+    return cond
+
+
+def guidance_follow(token: torch.Tensor, d_pos: Optional[torch.Tensor], R: int, delta: int = 1, *, pos_stride: int = 1):
+    """The negative half of a guided batch follows the guided half (mg_guidance_follow): token[R + r] = token[r] and, with
+    ``d_pos`` and ``pos_stride=1``, d_pos[R + r] += delta, for r < R.  Runs after the bookkeeping launch.  Enqueue-only."""
+    _need_gpu(token, d_pos)
+    R = int(R)
+    assert token.dtype == torch.int64 and token.is_contiguous() and R >= 1 and token.numel() >= 2 * R
+    ps = 0 if d_pos is None else _pos_stride(d_pos, 2 * R, pos_stride)
+    check(L.load().mg_guidance_follow(token.data_ptr(), _p(d_pos), R, int(delta), ps, _stream()), "mg_guidance_follow")
+    return token
+
+
 def beam_topk(logits: torch.Tensor, run: torch.Tensor, cand_score: torch.Tensor, cand_tok: torch.Tensor, normalized: bool = False):
     """Per row: the top K2 = cand_score.shape[1] scores run[row] + log_softmax(logits[row]) (score desc, lower token first).
     ``normalized``: the rows already hold log_softmax scores (logits_process(normalize=True)): candidates run[row] + logits[row]."""

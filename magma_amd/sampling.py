@@ -471,6 +471,93 @@ def constrain_logits(scores, history, step: int, tries, eos_ids):
     return scores.masked_fill(~keep.to(scores.device), float("-inf"))
 
 
+def check_guidance_values(guidance_scale=1.0, guidance_min_p=0.0):
+    """ValueError for a guidance scale that is not a finite number >= 0, or a guidance_min_p outside [0, 1]."""
+    g = guidance_scale
+    if isinstance(g, bool) or not isinstance(g, (int, float)) or not 0.0 <= g < float("inf"):
+        raise ValueError(f"guidance_scale must be a finite number >= 0 (1.0 = off), got {g!r}")
+    m = guidance_min_p
+    if isinstance(m, bool) or not isinstance(m, (int, float)) or not 0.0 <= m <= 1.0:
+        raise ValueError(f"guidance_min_p must be a number in [0, 1] (0 = off), got {m!r}")
+
+
+def check_guidance_args(guidance_scale=1.0, negative_embeddings=None, negative_lengths=None, guidance_min_p=0.0, batch: int = None,
+                        hidden: int = None):
+    """ValueError for guidance arguments generate() does not take.  Returns None at the defaults (the call as it was) or
+    dict(scale float, min_p float, embeddings (B, S', d) tensor, lengths int64 [B] on the host or None).
+    ``negative_embeddings`` takes what ``embeddings`` takes: a (B, S', d) tensor, a (1, S', d) tensor (broadcast to every row), a
+    list of per-row tensors, or embed_batch's (embeddings, lengths); ``negative_lengths`` belongs to the tensor forms.  Refused: a
+    scale != 1 without a negative prompt, a negative prompt or ``guidance_min_p`` > 0 with scale == 1, and -- ``batch`` / ``hidden``
+    given -- a row count other than 1 or ``batch`` or another hidden size."""
+    check_guidance_values(guidance_scale, guidance_min_p)
+    scale, min_p = float(guidance_scale), float(guidance_min_p)
+    if scale == 1.0:
+        if negative_embeddings is not None or negative_lengths is not None:
+            raise ValueError("a negative prompt has no effect at guidance_scale = 1.0: pass a scale != 1 or leave it out")
+        if min_p > 0.0:
+            raise ValueError("guidance_min_p has no effect at guidance_scale = 1.0: it is the cut of the guidance rule")
+        return None
+    if negative_embeddings is None:
+        raise ValueError(f"guidance_scale = {scale} needs negative_embeddings (the negative / unconditional prompt)")
+    neg, lens = negative_embeddings, negative_lengths
+    if is_embed_batch(neg):
+        if lens is not None:
+            raise ValueError("negative_embeddings already carries its lengths")
+        neg, lens = neg
+    elif isinstance(neg, (list, tuple)):
+        neg, derived = pad_ragged(neg)
+        if lens is not None and not torch.equal(torch.as_tensor(lens).cpu().to(torch.int64).view(-1), derived):
+            raise ValueError(f"negative_lengths {list(lens)} do not match the per-sample embeddings ({derived.tolist()})")
+        lens = derived
+    if not torch.is_tensor(neg) or neg.ndim != 3 or neg.shape[1] < 1:
+        raise ValueError("negative_embeddings must be a (B, S', d) or (1, S', d) tensor, a list of per-row tensors or "
+                         "embed_batch's (embeddings, lengths)")
+    if lens is not None:
+        lens = torch.as_tensor(lens).detach().cpu()
+        if lens.is_floating_point() or lens.is_complex() or lens.dtype == torch.bool or lens.ndim != 1 or \
+                lens.shape[0] != neg.shape[0] or int(lens.min()) < 1 or int(lens.max()) > neg.shape[1]:
+            raise ValueError(f"negative_lengths must be {neg.shape[0]} integers in [1, {neg.shape[1]}], got {lens.tolist()}")
+        lens = lens.to(torch.int64)
+    if hidden is not None and neg.shape[2] != hidden:
+        raise ValueError(f"negative_embeddings has hidden size {neg.shape[2]}, the prompt {hidden}")
+    if batch is not None:
+        if neg.shape[0] not in (1, batch):
+            raise ValueError(f"negative_embeddings has {neg.shape[0]} rows, the prompt {batch} (1 row is broadcast)")
+        if neg.shape[0] != batch:
+            neg = neg.expand(batch, -1, -1)
+            lens = None if lens is None else lens.expand(batch).clone()
+    return dict(scale=scale, min_p=min_p, embeddings=neg, lengths=lens)
+
+
+def guide_logits(cond, uncond, guidance_scale, guidance_min_p=0.0):
+    """Classifier-free guidance, host statement (the device kernel is csrc/sampling.hip, logits_guidance_kernel) in float64 from
+    fp32 inputs: ``cond`` / ``uncond`` (R, V), the logits of the same step under the prompt and under the negative prompt.
+        c = log_softmax(cond), u = log_softmax(uncond)
+        out = u + guidance_scale * (c - u)
+        out[i] = -inf  where  cond[i] - max(cond) < log(guidance_min_p)        (guidance_min_p > 0 only)
+    The first two lines are transformers' ``UnbatchedClassifierFreeGuidanceLogitsProcessor.__call__``; the third is the
+    plausibility cut of contrastive decoding (Li et al. 2023): without it a large scale promotes tokens that are impossible under
+    the conditional model merely because the negative model finds them even less likely.  The cut compares the fp32 difference
+    of the RAW conditional logits with the fp32 rounding of the float64 log -- no logsumexp takes part, so host and device keep
+    exactly the same set; the row maximum always stays, ties at the bound stay.  ``guidance_scale`` finite and >= 0 (1: c
+    itself), ``guidance_min_p`` in [0, 1] (0: off).  A conditional -inf stays -inf (whatever the scale, 0 included).  The
+    unconditional logits must be finite (ValueError): u = -inf under c > -inf would give +inf.  Returns float64 (R, V)."""
+    check_guidance_values(guidance_scale, guidance_min_p)
+    c32 = torch.as_tensor(cond).detach().cpu().to(torch.float32)
+    u32 = torch.as_tensor(uncond).detach().cpu().to(torch.float32)
+    if c32.ndim != 2 or c32.shape != u32.shape:
+        raise ValueError(f"cond and uncond must be (R, V) alike, got {tuple(c32.shape)} / {tuple(u32.shape)}")
+    if not bool(torch.isfinite(u32).all()):
+        raise ValueError("the unconditional logits must be finite")
+    c, u = F.log_softmax(c32.double(), dim=-1), F.log_softmax(u32.double(), dim=-1)
+    out = u + float(guidance_scale) * (c - u)
+    out = out.masked_fill(c32 == float("-inf"), float("-inf"))
+    if float(guidance_min_p) > 0.0:
+        bound = torch.tensor(float(guidance_min_p), dtype=torch.float64).log().to(torch.float32)
+        out = out.masked_fill((c32 - c32.max(-1, keepdim=True).values) < bound, float("-inf"))
+    return out
+
+
 MAX_EOS_IDS, MAX_STOP_SEQS, MAX_STOP_LEN = 8, 16, 16
 REASON_NONE, REASON_EOS, REASON_STOP = 0, 1, 2
 
@@ -791,7 +878,8 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
              return_past_key_values: bool = False, *, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
              min_new_tokens: int = 0, suppress_tokens=None, stop_sequences=None, stop_per_row: bool = None,
              return_finish: bool = False, sampler: str = "reference", min_p: float = 0.0, return_logprobs: bool = False,
-             top_logprobs: int = 0, constraint=None) -> Union[List[str], torch.Tensor]:
+             top_logprobs: int = 0, constraint=None, guidance_scale: float = 1.0, negative_embeddings=None,
+             negative_lengths=None, guidance_min_p: float = 0.0) -> Union[List[str], torch.Tensor]:
     """reference sampling.py:43-121.  Token selection (argmax, or top-k / the reference's top-p rule / softmax /
     multinomial) and the ``(next_token == eos).all()`` test run on the device inside the captured token step; the host
     reads the recorded "first all-eos step" every ``eos_check_every`` steps (default 8, MAGMA_EOS_CHECK_EVERY) instead of
@@ -865,7 +953,26 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     object runs the host statement.  ``return_logprobs`` still reports the raw distribution.  Refused with ValueError, because a
     row could be left without a token: ``no_repeat_ngram_size`` > 0, ``min_new_tokens`` above the shortest sequence,
     ``suppress_tokens`` that meet the trie's tokens or the eos ids, a trie id >= V.  Not combined with beam search
-    (NotImplementedError).  ``constraint=None`` is the call as it was."""
+    (NotImplementedError).  ``constraint=None`` is the call as it was.
+
+    Classifier-free guidance (DESIGN.md "Classifier-free guidance"; greedy and sampled): ``guidance_scale`` != 1 with
+    ``negative_embeddings`` asks every question twice -- under the prompt and under a negative prompt, e.g. the same text without
+    its image (``Magma.embed_batch(batch, drop_images=True)``) -- and selects from u + guidance_scale * (c - u) over the two
+    log_softmax distributions: the rule of transformers' ``guidance_scale`` / ``negative_prompt_ids``
+    (``UnbatchedClassifierFreeGuidanceLogitsProcessor``; ``guide_logits`` above), the first processor of the chain, in front of the
+    repetition penalty.  ``negative_embeddings`` takes what ``embeddings`` takes -- a (B, S', d) tensor, a (1, S', d) tensor that
+    every row shares, a list of per-row tensors, embed_batch's (embeddings, lengths) -- with ``negative_lengths`` for the tensor
+    forms; its length is independent of the prompt's.  ``guidance_min_p`` > 0 adds the plausibility cut of contrastive decoding:
+    tokens less probable than guidance_min_p times the most probable one UNDER THE PROMPT are never selected.  The output is laid
+    out as for the call on ``embeddings`` alone.  The HIP engine runs one cache of 2B ragged rows (the prompts, then the negative
+    prompts), one prefill, and the token step over 2B rows with two small launches more (the combination in front of the
+    processors, the token mirrored to the negative rows behind the bookkeeping); everything between them runs over B rows, so a
+    guided row draws from the random stream of the same row unguided.  Any other LM object runs two model calls per step and the
+    host statement.  ``return_logprobs`` still reports the raw conditional distribution.  ValueError: a scale that is negative or
+    not finite, ``guidance_min_p`` outside [0, 1], a scale != 1 without a negative prompt, a negative prompt or ``guidance_min_p``
+    at scale 1, row counts or hidden sizes that do not match.  Not combined with beam search, ``past_key_values`` or
+    ``return_past_key_values`` (NotImplementedError): a guided cache holds two conversations per sample.  At the defaults the
+    call is bit for bit what it was, and nothing is launched or allocated."""
     if eos_token is None or (isinstance(eos_token, int) and not eos_token):
         eos_token = model.eos_token
     early_stopping = check_beam_args(num_beams, num_return_sequences, early_stopping)
@@ -887,6 +994,13 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     if constraint is not None and (num_beams > 1 or return_scores):
         raise NotImplementedError("a constraint is not combined with beam search (num_beams > 1 / return_scores=True): its "
                                   "candidate lists would fill with -inf entries")
+    guide = check_guidance_args(guidance_scale, negative_embeddings, negative_lengths, guidance_min_p)
+    if guide is not None and (num_beams > 1 or return_scores):
+        raise NotImplementedError("guidance (guidance_scale / negative_embeddings) is not combined with beam search (num_beams > 1 "
+                                  "/ return_scores=True): its running scores would mix two distributions")
+    if guide is not None and (past_key_values is not None or return_past_key_values):
+        raise NotImplementedError("guidance neither continues from nor returns a KV cache (past_key_values / "
+                                  "return_past_key_values): a guided cache holds two conversations per row")
     continuing = past_key_values is not None or return_past_key_values
     if continuing and (num_beams > 1 or return_scores):
         raise NotImplementedError("beam search neither continues from nor returns a KV cache (past_key_values / "
@@ -904,6 +1018,8 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
         lengths = derived
     b, s, _ = embeddings.shape
     dev = embeddings.device
+    if guide is not None:       # the negative prompt as (b, s', d) rows, row counts and hidden size checked
+        guide = check_guidance_args(guidance_scale, negative_embeddings, negative_lengths, guidance_min_p, b, embeddings.shape[2])
     cons = check_constraint_args(constraint, b, getattr(getattr(model, "tokenizer", None), "encode", None), _logit_count(model),
                                  eos_ids, proc)
     # the HIP engine selects the token itself; any other LM object gets the reference's call (sampling.py:81-93)
@@ -920,6 +1036,8 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
                              "device token selection and would attend over the padding")
         from .engine import LMEngine
         lengths = LMEngine.check_lengths(lengths, b, s)
+    if guide is not None and guide["lengths"] is not None and not on_device:
+        raise ValueError("negative prompts of different lengths need the HIP engine's LM (per-row KV positions)")
     model.eval()
     out = torch.full((b, s + max_steps), eos_token, dtype=torch.long, device=dev)
     out[:, :s] = model.image_token
@@ -936,6 +1054,17 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     if lengths is not None:
         first_kw["lengths"] = lengths
     step_kw = dict(sampling=mode) if on_device else {}
+    prompts = embeddings
+    if on_device and guide is not None:     # ONE ragged batch of 2b rows: the prompts, then the negative prompts
+        from .engine import LMEngine
+        neg = guide["embeddings"].to(device=dev, dtype=embeddings.dtype)
+        s_neg = neg.shape[1]
+        prompts = torch.zeros(2 * b, max(s, s_neg), embeddings.shape[2], dtype=embeddings.dtype, device=dev)
+        prompts[:b, :s], prompts[b:, :s_neg] = embeddings, neg
+        first_kw["lengths"] = torch.cat([lengths if lengths is not None else torch.full((b,), s, dtype=torch.int64),
+                                         guide["lengths"] if guide["lengths"] is not None
+                                         else torch.full((b,), s_neg, dtype=torch.int64)])
+        first_kw["guidance"] = step_kw["guidance"] = LMEngine.guidance_mode((guide["scale"], guide["min_p"]))
     if on_device and proc is not None:      # only then: an LM object written before the processors keeps its signature
         from .engine import LMEngine
         first_kw["processors"] = step_kw["processors"] = LMEngine.proc_mode(proc)      # checked once, not once per token
@@ -959,7 +1088,7 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
             outputs = model.lm(inputs_embeds=embeddings, use_cache=True, past_key_values=past_key_values, cache_hint=max_steps,
                                **ext_kw)
         elif i == 0:
-            outputs = model.lm(inputs_embeds=embeddings, use_cache=True, past_key_values=None, cache_hint=max_steps,
+            outputs = model.lm(inputs_embeds=prompts, use_cache=True, past_key_values=None, cache_hint=max_steps,
                                reuse_cache=True, **first_kw)
         elif on_device:      # the token selected by the previous step is fed back on the device: nothing crosses the host
             outputs = model.lm(input_ids=None, use_cache=True, past_key_values=past, feed_back=True, **step_kw)
@@ -976,6 +1105,15 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
             continue
         logits = outputs.logits[:, -1, :].float()            # any other LM object: the reference's host-side arithmetic
         raw = logits
+        if guide is not None:       # the negative stream: a second model call with its own past, then the host statement
+            if i == 0:
+                neg_out = model.lm(inputs_embeds=guide["embeddings"].to(dev), use_cache=True, past_key_values=None,
+                                   cache_hint=max_steps)
+            else:
+                neg_out = model.lm(input_ids=out[:, n - 1:n], use_cache=True, past_key_values=neg_past)
+            neg_past = neg_out.past_key_values
+            logits = guide_logits(logits, neg_out.logits[:, -1, :].float(), guide["scale"], guide["min_p"]) \
+                .to(torch.float32).to(logits.device)
         if proc is not None:
             logits = process_logits(logits.cpu(), out[:, s:n].cpu(), n - s, eos_token=eos_ids if stop is not None else eos_token,
                                     **proc).to(logits.device)
@@ -983,7 +1121,7 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
             logits = constrain_logits(logits.cpu(), out[:, s:n].cpu(), n - s, cons, eos_ids).to(logits.device)
         if greedy:
             next_token = outputs.next_token.unsqueeze(1) if outputs.get("next_token") is not None and proc is None \
-                and cons is None else \
+                and cons is None and guide is None else \
                 torch.argmax(logits, dim=-1, keepdim=True)
         else:
             if warp is not None:
@@ -1016,14 +1154,15 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
         lens = lengths.to(dev, non_blocking=True)[:, None]
         out.fill_(eos_token)
         out.masked_fill_(torch.arange(s + max_steps, device=dev)[None, :] < lens, model.image_token)
-        out.scatter_(1, lens + torch.arange(n_gen, device=dev)[None, :], past.history[:, :n_gen])
+        out.scatter_(1, lens + torch.arange(n_gen, device=dev)[None, :], past.history[:b, :n_gen])
     elif on_device:          # one copy of the token history the bookkeeping kernel kept
-        out[:, s:n] = past.history[:, : n - s]
-    gen_tokens = past.history[:, : n - s] if on_device and past is not None else out[:, s:n]      # the generated columns
+        out[:, s:n] = past.history[:b, : n - s]
+    # (``[:b]``: a guided cache holds 2b rows and keeps the per-row records of the b guided ones in its first b rows)
+    gen_tokens = past.history[:b, : n - s] if on_device and past is not None else out[:, s:n]      # the generated columns
     out = out[:, :n]
     finish = None
     if stop is not None and (return_finish or continuing or decode or (n_top is not None and n > s)):
-        record = past.finish.cpu() if on_device else record           # one host copy
+        record = past.finish[:b].cpu() if on_device else record       # one host copy
         finish = finish_from_record(record, n - s)
     elif return_finish:                                               # the reference's rule: every row ran the whole call
         finish = finish_from_record(torch.tensor([[-1, 0]] * b).view(b, 2), n - s)
@@ -1033,7 +1172,7 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
         if n_gen == 0:
             vals = (torch.zeros(b, 0), torch.zeros(b, 0, n_top, dtype=torch.int64), torch.zeros(b, 0, n_top))
         elif on_device:
-            vals = (past.lp[:, :n_gen], past.top_id[:, :n_gen], past.top_lp[:, :n_gen])
+            vals = (past.lp[:b, :n_gen], past.top_id[:b, :n_gen], past.top_lp[:b, :n_gen])
         else:
             vals = tuple(torch.stack([h[j] for h in host_lp[:n_gen]], 1) for j in range(3))
         logprobs = mask_logprobs(gen_tokens, *vals, finish.kept if finish is not None else torch.full((b,), n_gen))
