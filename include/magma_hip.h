@@ -98,8 +98,9 @@ const char* mg_version(void);
  *      the reduction counted every target >= 0 although mg_ce_rows_f32 / mg_ce_bwd_bf16 gave such a row loss 0 and gradient 0.
  *  16  token log-probabilities: added mg_token_logprobs_f32 (nothing moved).
  *  17  constrained decoding: added mg_logits_process_constrained_f32 (nothing moved).
- *  18  classifier-free guidance: added mg_logits_guidance_f32 and mg_guidance_follow (nothing moved). */
-#define MG_ABI_VERSION 18
+ *  18  classifier-free guidance: added mg_logits_guidance_f32 and mg_guidance_follow (nothing moved).
+ *  19  ranking choices: added mg_attn_prefill_tree_bf16, mg_rotary_split_at_bf16 and mg_token_logprobs_rows_f32 (nothing moved). */
+#define MG_ABI_VERSION 19
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -334,6 +335,30 @@ int mg_attn_prefill_cached_bf16(const mg_bf16* q, int64_t q_ld_row, int64_t q_st
                                 const mg_bf16* kcache, const mg_bf16* vcache, mg_bf16* out, int64_t ld_out, int32_t B, int32_t H,
                                 int32_t T, int32_t Smax, const int32_t* d_pos, int32_t pos_stride, void* stream);
 
+/* K10 over a cache, the chunk a TREE (ABI 19; DESIGN.md "Ranking choices"): mg_attn_prefill_cached_bf16 with another mask.  The
+ * chunk's T rows are the non-root nodes of a trie in depth-first preorder; sub [B, T] int32 (row stride T), sub[b][j] = one past
+ * the last row of node j's subtree, so "j is t or an ancestor of t" is j <= t < sub[b][j].  Query t of row b sees the cache keys
+ * [0, p_b) and chunk key j (cache slot p_b + j) iff j <= t && t < sub[b][j]; the chunk's K / V must already be written at
+ * [p_b, p_b + T) (mg_rotary_split_at_bf16).  sub[b][j] == T for every j is a chain: the causal mask, and the bytes of
+ * mg_attn_prefill_cached_bf16.  Padding rows of a ragged batch carry sub[b][t] = t + 1 (they see the prompt and themselves).
+ * Every other operand is mg_attn_prefill_cached_bf16's, laid out as there.  p_min: the caller's HOST copy of the smallest p_b
+ * (d_pos lives on the device and the call only enqueues): every query must see at least one cached key, so p_min < 1 is
+ * refused with MG_ERR_SHAPE before the launch, as are a NULL sub and strides that are no multiples of 8.  Key loads stay below
+ * min(p_b + T, Smax).                                                                                                          */
+int mg_attn_prefill_tree_bf16(const mg_bf16* q, int64_t q_ld_row, int64_t q_stride_b, int64_t q_stride_h,
+                              const mg_bf16* kcache, const mg_bf16* vcache, mg_bf16* out, int64_t ld_out, int32_t B, int32_t H,
+                              int32_t T, int32_t Smax, const int32_t* d_pos, int32_t pos_stride, const int32_t* sub, int32_t p_min,
+                              void* stream);
+
+/* K9 for such a chunk (ABI 19): mg_rotary_split_bf16 with pos_stride = 1 and the slot and the angle apart.  d_pos [B] and
+ * off [B, S] int32 (row stride S): row s of sequence b is written to cache slot d_pos[b] + s and rotated with the angles of
+ * position d_pos[b] + off[b][s] (a trie node: off = depth - 1).  qkv [B*S, >= 3*H*256] at row stride ld_qkv (0 = 3*H*256);
+ * q_out [B,H,S,256]; kcache / vcache [B,H,Smax,256]; sin / cos tables [>= Smax, rot_dim/2] f32.  A row whose slot or position lies
+ * outside [0, Smax) is skipped.  off[b][s] == s gives the bytes of mg_rotary_split_bf16 with pos_stride = 1.                       */
+int mg_rotary_split_at_bf16(const mg_bf16* qkv, int64_t ld_qkv, int32_t B, int32_t S, int32_t H, int32_t rot_dim,
+                            const float* sin_t, const float* cos_t, const int32_t* d_pos, const int32_t* off, mg_bf16* q_out,
+                            mg_bf16* kcache, mg_bf16* vcache, int32_t Smax, void* stream);
+
 /* K10 decode (reference magma/sampling.py:86-90, past_key_values path): one query row per (b,h) against
  * ctx = pos_b + 1 cached keys, pos_b = d_pos[b * pos_stride].
  * pos_stride (ABI 7): 0 = one position for the whole batch (d_pos[0]); 1 = d_pos holds B positions, one per row (a ragged,
@@ -540,6 +565,14 @@ int mg_guidance_follow(int64_t* token, int32_t* d_pos, int32_t R, int32_t delta,
 #define MG_LOGPROBS_MAX_TOP 20
 int mg_token_logprobs_f32(const float* logits, int64_t ld, int32_t R, int32_t V, const int64_t* token, const int32_t* state,
                           float* lp, int64_t ld_lp, int32_t cols, int32_t n_top, int32_t* top_id, float* top_lp, void* stream);
+
+/* The same with a row indirection (ABI 19; DESIGN.md "Ranking choices"): N entries, one workgroup each; entry i gives
+ *   lp[i] = (x[t] - m) - log sum_v exp(x[v] - m), x = logits row row_of[i] (logits [n_rows, ld] fp32), t = token[i],
+ * by mg_token_logprobs_f32's device body in its n_top = 0 form -- the same bits for the same row and token -- so the edges out of
+ * one trie node share their parent's row without a copy.  row_of / token [N] int32.  A row outside [0, n_rows) or a token outside
+ * [0, V) reads nothing and gives -inf.                                                                                       */
+int mg_token_logprobs_rows_f32(const float* logits, int64_t ld, int32_t n_rows, int32_t V, const int32_t* row_of,
+                               const int32_t* token, int32_t N, float* lp, void* stream);
 
 /* CLIP VisionTransformer front end and attention (encoder_name "clip" = ViT-B/32; reference magma/image_encoders.py:56-63):
  *   patchify   img [B,3,H,W] bf16 NCHW -> rows [B*(H/P)*(W/P), 3*P*P] in (c, py, px) order = the im2col of the stride-P patch

@@ -1251,3 +1251,38 @@ extern "C" int mg_kv_reorder_bf16(mg_bf16* kcache, mg_bf16* vcache, mg_bf16* kst
   }
   return MG_OK;
 }
+
+// ---------------------------------------------------------------------------
+// Token log-probabilities by row index (behind everything else: the kernels of the token step keep their place in the code object)
+namespace {
+// mg_token_logprobs_f32 with a row indirection (mg_token_logprobs_rows_f32, ABI 19; DESIGN.md "Ranking choices"): entry i reads logits row
+// row_of[i] and token[i], so the children of one trie node share their parent's logits row without a copy.  token_logprobs_kernel's
+// body in its n_top = 0 form -- the same max / logsumexp, the same expression -- hence the same bits for the same row and token.
+// A row outside [0, n_rows) or a token outside [0, V) reads nothing and gives -inf.
+__global__ __launch_bounds__(ST) void token_logprobs_rows_kernel(const float* __restrict__ logits, int64_t ld, int n_rows, int V,
+                                                                 const int32_t* __restrict__ row_of,
+                                                                 const int32_t* __restrict__ token, float* __restrict__ lp) {
+  const int i = blockIdx.x, row = row_of[i];
+  if (row < 0 || row >= n_rows) {            // (uniform over the workgroup)
+    if (threadIdx.x == 0) lp[i] = -INFINITY;
+    return;
+  }
+  const float* x = logits + (int64_t)row * ld;
+  const RowLse s = row_topk_body<false, true>(x, V, 0.f, 0, nullptr, nullptr);
+  if (threadIdx.x == 0) {
+    const int t = token[i];
+    lp[i] = t >= 0 && t < V ? (x[t] - s.mx) - s.lse : -INFINITY;
+  }
+}
+}  // namespace
+
+extern "C" int mg_token_logprobs_rows_f32(const float* logits, int64_t ld, int32_t n_rows, int32_t V, const int32_t* row_of,
+                                          const int32_t* token, int32_t N, float* lp, void* stream) {
+  const char* who = "mg_token_logprobs_rows_f32";
+  if (!logits || !row_of || !token || !lp) MG_FAIL(MG_ERR_SHAPE, "%s: null pointer", who);
+  if (n_rows <= 0 || V <= 0 || N <= 0 || ld < V) MG_FAIL(MG_ERR_SHAPE, "%s: need n_rows, V, N > 0 and ld >= V", who);
+  if (((uintptr_t)logits | (uintptr_t)row_of | (uintptr_t)token | (uintptr_t)lp) & 3) MG_FAIL(MG_ERR_ALIGN, "%s: pointers must be 4-byte aligned", who);
+  hipLaunchKernelGGL(token_logprobs_rows_kernel, dim3(N), dim3(ST), 0, (hipStream_t)stream, logits, ld, n_rows, V, row_of, token, lp);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}

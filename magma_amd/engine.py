@@ -885,10 +885,13 @@ class LMEngine:
         return ops.embedding(ids, self.wte, out)
 
     # -------------------------------------------------------------- prefill
-    def _blocks_prefill(self, embeds: torch.Tensor, cache: Optional[KVCache], want_hidden=False, lse_out=None, chunk=False):
+    def _blocks_prefill(self, embeds: torch.Tensor, cache: Optional[KVCache], want_hidden=False, lse_out=None, chunk=False,
+                        tree=None):
         """The blocks over B x S new rows.  ``chunk``: the rows continue ``cache`` -- row b's S rows sit at cache.d_pos[b * pos_stride]
         + s, their K / V are appended there and they attend over the cached keys (mg_attn_prefill_cached_bf16); every GEMM, adapter and
-        epilogue launch is the prefill's."""
+        epilogue launch is the prefill's.  ``tree`` (with ``chunk``; tree_forward): the rows are trie nodes -- (d_pos int32 [B], off,
+        sub int32 [B, S], p_min) -- row s goes to slot d_pos[b] + s at position d_pos[b] + off[b, s] and sees the cache below d_pos[b]
+        and the chunk rows j <= s < sub[b, j] (mg_rotary_split_at_bf16 / mg_attn_prefill_tree_bf16 in place of the chunk's two)."""
         B, S, d = embeds.shape
         assert d == self.d
         if S > self.cfg.max_position_embeddings:
@@ -927,7 +930,11 @@ class LMEngine:
             else:
                 qkv = self._linear(ly, "qkv", ly.qkv, ln, lnq)
             kc, vc = (cache.k[li], cache.v[li]) if cache is not None else (kscr, vscr)
-            if chunk:
+            if tree is not None:
+                t_pos, t_off, t_sub, t_pmin = tree
+                ops.rotary_split_at(qkv, B, S, self.H, self.rot, self.sin_t, self.cos_t, q, kc, vc, t_pos, t_off)
+                ops.attn_prefill_tree(q, kc, vc, ctx, B, self.H, S, t_pos, t_sub, p_min=t_pmin, pos_stride=1)
+            elif chunk:
                 ops.rotary_split(qkv, B, S, self.H, self.rot, self.sin_t, self.cos_t, q, kc, vc, d_pos=cache.d_pos,
                                  pos_stride=cache.pos_stride)
                 ops.attn_prefill_cached(q, kc, vc, ctx, B, self.H, S, cache.d_pos, pos_stride=cache.pos_stride)
@@ -1087,6 +1094,65 @@ class LMEngine:
             rows = (torch.arange(B)[:, None] * T + torch.arange(T_in)[None, :] + shift[:, None]).reshape(-1).to(self.device)
             full = LMOutput.lazy(lambda: self._full_logits(x.index_select(0, rows), B * T_in).view(B, T_in, self.V))
         return logits, cache, full
+
+    def tree_forward(self, cache: KVCache, rows) -> torch.Tensor:
+        """The blocks over a TREE of new rows against ``cache`` (Magma.rank; DESIGN.md "Ranking choices"): ``rows`` = (token, off, sub)
+        int32 (B, T) host or device tensors as sampling.pad_trie_rows lays them out -- the trie's non-root nodes in depth-first
+        preorder, right-padded.  Node t of row b is fed wte[token[b, t]] at position p_b + off[b, t] (p_b = the row's write
+        position), its K / V go to the scratch slot p_b + t, and it attends to the cached keys below p_b and to the nodes
+        j <= t < sub[b, j] (itself and its ancestors).  _blocks_prefill in its third chunk mode: every GEMM, adapter and epilogue
+        launch is the prefill's.  The cache's positions are NOT advanced and nothing below p_b is written: the cache stays what
+        it was (slots >= p_b are scratch, as for any cache), so one prompt cache serves any number of trees.  Returns the
+        final hidden rows (B * T, d); the caller runs ln_f and the head on the rows it needs."""
+        if not isinstance(cache, KVCache):
+            raise TypeError(f"tree_forward needs this engine's KVCache, got {type(cache).__name__}")
+        token, off, sub = (torch.as_tensor(t) for t in rows)
+        if token.ndim != 2 or token.shape[0] != cache.B or off.shape != token.shape or sub.shape != token.shape:
+            raise ValueError(f"rows must be three ({cache.B}, T) tensors, got {tuple(token.shape)}, {tuple(off.shape)}, {tuple(sub.shape)}")
+        B, T = token.shape
+        pos = cache.rows_pos()
+        if cache.pending is not None and bool((cache.pending >= 0).any()):
+            raise ValueError("tree_forward: the cache holds a token that has not been fed back; continue it first")
+        if int(pos.min()) < 1:
+            raise ValueError("tree_forward needs at least one cached position in front of every tree")
+        n_pos = self.cfg.max_position_embeddings
+        if int(pos.max()) + T > n_pos:
+            raise ValueError(f"the tree's {T} rows behind position {int(pos.max())} exceed max_position_embeddings = {n_pos}")
+        if int(pos.max()) + T > cache.Smax:
+            self.detach_cache(cache)
+            cache.grow(min(n_pos, ops.ceil_to(int(pos.max()) + T, 64)))
+        dev = self.device
+        d_pos = cache.d_pos if cache.ragged else cache.d_pos[:1].expand(B).contiguous()
+        to32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()  # noqa: E731
+        embeds = self.embed_ids(token.to(torch.int64))
+        x, _ = self._blocks_prefill(embeds, cache, chunk=True, tree=(d_pos, to32(off), to32(sub), int(pos.min())))
+        return x
+
+    HEAD_SLAB = 1024          # rows of fp32 logits alive at once in head_token_logprobs (x Vp x 4 bytes: 0.2 GB at V = 50400)
+
+    def head_token_logprobs(self, x: torch.Tensor, rows: torch.Tensor, row_of: torch.Tensor, token: torch.Tensor) -> torch.Tensor:
+        """ln_f and the fp32 head on the hidden rows ``x[rows]`` (``rows`` int64 [R], host), HEAD_SLAB rows at a time, and per entry
+        i the log-probability of ``token[i]`` under logits row ``row_of[i]`` of those R (both int32 [N], host, ``row_of``
+        ascending): mg_token_logprobs_rows_f32, no logits row is copied for a node's fan-out.  Returns fp32 [N] on the device."""
+        N, R = row_of.numel(), rows.numel()
+        lp = torch.empty(N, dtype=torch.float32, device=self.device)
+        if N == 0:
+            return lp
+        assert bool((row_of[1:] >= row_of[:-1]).all()) and int(row_of[0]) >= 0 and int(row_of[-1]) < R
+        rows_d, tok_d = rows.to(self.device), token.to(self.device)
+        edge = torch.searchsorted(row_of, torch.arange(0, R + self.HEAD_SLAB, self.HEAD_SLAB, dtype=row_of.dtype)).tolist()
+        logits = torch.empty(min(R, self.HEAD_SLAB), self.Vp, dtype=torch.float32, device=self.device)
+        for k, r0 in enumerate(range(0, R, self.HEAD_SLAB)):
+            e0, e1 = edge[k], edge[k + 1]
+            if e1 == e0:
+                continue
+            n = min(self.HEAD_SLAB, R - r0)
+            xl = ops.layernorm(x.index_select(0, rows_d[r0:r0 + n]), self.lnf_g, self.lnf_b, self.eps)
+            # score's head (_target_logits): the tile GEMM whatever n is -- a row's logits do not depend on how many rows share the
+            # launch (_head would switch to the weight-streaming kernel at n <= 16), so a choice keeps its bits from group to group
+            ops.gemm(xl, self.head, out=logits[:n])
+            ops.token_logprobs_rows(logits[:n, : self.V], (row_of[e0:e1] - r0).to(self.device), tok_d[e0:e1], lp[e0:e1])
+        return lp
 
     def _head(self, xl: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         M = xl.shape[0]

@@ -328,10 +328,26 @@ class Magma(nn.Module):
         model answers with: constrained GREEDY decoding (``generate(constraint=choices, temperature=0, return_logprobs=True)``,
         ``max_steps`` = the longest choice + 1).  Returns (index int64 [B]: the position of row b's answer in its choices,
         ``TokenLogprobs`` of the path under the raw distribution).  It follows the locally most probable allowed token; it is NOT
-        the arg-max of the total sequence probability -- ``score`` every candidate for that (see sampling.choose)."""
+        the arg-max of the total sequence probability -- ``rank`` gives that, for all choices in one forward (see sampling.choose)."""
         from .sampling import choose
         torch.cuda.set_device(self.device)
         return choose(self, embeddings, choices, lengths=lengths, **generate_kwargs)
+
+    @torch.no_grad()
+    def rank(self, embeddings, choices, lengths=None, *, eos: bool = True, length_penalty: float = 0.0, max_nodes: int = None,
+             return_terms: bool = False):
+        """Rank ``choices`` (what ``choose`` takes) by their probability as whole sequences after the prompt ``embeddings`` /
+        ``lengths`` (what ``generate`` takes): the closed-vocabulary evaluation of a captioning / VQA model (DESIGN.md "Ranking
+        choices").  Returns ``sampling.Ranking(index int64 [B], scores fp32 [B, C], logprobs fp32 [B, C], count int64 [B, C])``,
+        columns in the caller's order: ``logprobs[b, c]`` = sum_j log p(choice_c[j] | prompt_b, choice_c[:j]) + (``eos``)
+        log p(eos | prompt_b, choice_c) under the raw distribution -- ``score``'s numbers --, ``count`` the number of terms,
+        ``scores = logprobs / count ** length_penalty``, ``index`` the arg-max (lowest position on a tie); rows with fewer choices
+        are padded with -inf / 0.  All choices of a row cost ONE forward over prompt + trie nodes (shared prefixes once), not one
+        forward per candidate; ``max_nodes`` caps the nodes per forward (see sampling.rank)."""
+        from .sampling import rank
+        torch.cuda.set_device(self.device)
+        return rank(self, embeddings, choices, lengths=lengths, eos=eos, length_penalty=length_penalty, max_nodes=max_nodes,
+                    return_terms=return_terms)
 
     @torch.no_grad()
     def score(self, embeddings, targets, lengths=None, *, top_logprobs: int = 0):

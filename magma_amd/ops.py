@@ -588,6 +588,49 @@ def attn_prefill_cached(q, kcache, vcache, out, B, H, T, d_pos, *, pos_stride: i
     return out
 
 
+def attn_prefill_tree(q, kcache, vcache, out, B, H, T, d_pos, sub, *, p_min: int, pos_stride: int = 0):
+    """attn_prefill_cached over a chunk whose T rows are the nodes of a trie in depth-first preorder (DESIGN.md "Ranking choices";
+    sampling.trie_rows): ``sub`` int32 (B, T), sub[b, j] = one past the last row of node j's subtree.  Query t of row b sees the
+    cache keys [0, p_b) and chunk key j (slot p_b + j) iff j <= t < sub[b, j].  sub == T everywhere is a chain: the bytes of
+    attn_prefill_cached.  ``p_min``: the caller's host copy of the smallest p_b -- every query needs a cached key, p_min < 1 is
+    refused by the library before the launch.  The other operands are attn_prefill_cached's."""
+    _need_gpu(q, sub)
+    if q.ndim != 4 or tuple(q.shape) != (B, H, T, 256) or q.stride(3) != 1 or q.dtype != torch.bfloat16:
+        raise ValueError(f"q must be bf16 ({B}, {H}, {T}, 256) with contiguous rows, got {q.dtype} {tuple(q.shape)}")
+    for name, c in (("kcache", kcache), ("vcache", vcache)):
+        if c.ndim != 4 or c.shape[0] != B or c.shape[1] != H or c.shape[3] != 256 or not c.is_contiguous() or c.dtype != torch.bfloat16:
+            raise ValueError(f"{name} must be a contiguous bf16 ({B}, {H}, Smax, 256) cache, got {c.dtype} {tuple(c.shape)}")
+    if kcache.shape != vcache.shape:
+        raise ValueError("kcache and vcache must have the same shape")
+    if out.ndim != 2 or out.stride(1) != 1 or out.shape[0] != B * T or out.shape[1] != H * 256 or out.dtype != torch.bfloat16:
+        raise ValueError(f"out must be bf16 ({B * T}, {H * 256}) with unit column stride, got {out.dtype} {tuple(out.shape)}")
+    if T > kcache.shape[2]:
+        raise ValueError(f"a chunk of {T} rows does not fit a cache of Smax = {kcache.shape[2]}")
+    if sub is not None and (sub.dtype != torch.int32 or tuple(sub.shape) != (B, T) or not sub.is_contiguous()):
+        raise ValueError(f"sub must be a contiguous int32 ({B}, {T}) tensor, got {sub.dtype} {tuple(sub.shape)}")
+    ps = _pos_stride(d_pos, B, pos_stride)
+    check(L.load().mg_attn_prefill_tree_bf16(q.data_ptr(), q.stride(2), q.stride(0), q.stride(1), kcache.data_ptr(),
+                                             vcache.data_ptr(), out.data_ptr(), out.stride(0), B, H, T, kcache.shape[2],
+                                             d_pos.data_ptr(), ps, _p(sub), int(p_min), _stream()), "mg_attn_prefill_tree_bf16")
+    return out
+
+
+def rotary_split_at(qkv, B, S, H, rot_dim, sin_t, cos_t, q_out, kcache, vcache, d_pos, off):
+    """rotary_split(pos_stride=1) with the slot and the angle apart: row s of sequence b lands in cache slot d_pos[b] + s, rotated
+    with the angles of position d_pos[b] + off[b, s] (``off`` int32 (B, S): a trie node's depth - 1).  Slots or positions at or
+    past Smax are skipped.  off[b, s] == s gives the bytes of rotary_split(pos_stride=1)."""
+    _need_gpu(qkv, d_pos, off)
+    assert qkv.ndim == 2 and qkv.stride(1) == 1
+    assert d_pos.dtype == torch.int32 and d_pos.is_contiguous() and d_pos.numel() >= B
+    if off.dtype != torch.int32 or tuple(off.shape) != (B, S) or not off.is_contiguous():
+        raise ValueError(f"off must be a contiguous int32 ({B}, {S}) tensor, got {off.dtype} {tuple(off.shape)}")
+    if sin_t.shape[0] < kcache.shape[2]:
+        raise ValueError(f"the rotary tables hold {sin_t.shape[0]} positions, the cache {kcache.shape[2]}")
+    check(L.load().mg_rotary_split_at_bf16(qkv.data_ptr(), qkv.stride(0), B, S, H, rot_dim, sin_t.data_ptr(), cos_t.data_ptr(),
+                                           d_pos.data_ptr(), off.data_ptr(), q_out.data_ptr(), kcache.data_ptr(),
+                                           vcache.data_ptr(), kcache.shape[2], _stream()), "mg_rotary_split_at_bf16")
+
+
 def attn_decode(q, kcache, vcache, out, B, H, d_pos, *, pos_stride: int = 0):
     """Attention of one (already rotated) query per (b, h) over [0, pos_b]; pos_b = d_pos[b * pos_stride]."""
     _need_gpu(q)
@@ -873,6 +916,20 @@ def token_logprobs(logits: torch.Tensor, token: torch.Tensor, lp: torch.Tensor, 
                                          lp.stride(0) if R > 1 else max(lp.stride(0), cols), cols, n_top,
                                          _p(top_id) if n_top else None, _p(top_lp) if n_top else None, _stream()),
           "mg_token_logprobs_f32")
+    return lp
+
+
+def token_logprobs_rows(logits: torch.Tensor, row_of: torch.Tensor, token: torch.Tensor, lp: torch.Tensor):
+    """token_logprobs with a row indirection (mg_token_logprobs_rows_f32): lp[i] = log_softmax(logits[row_of[i]])[token[i]] for N
+    entries -- ``row_of`` / ``token`` int32 (N,), ``lp`` fp32 (N,) -- with the bits token_logprobs gives for that row and token; the
+    edges out of one trie node share their parent's logits row.  A row outside the logits or a token outside [0, V) gives -inf."""
+    _need_gpu(logits, row_of, token, lp)
+    assert logits.dtype == torch.float32 and logits.ndim == 2 and logits.stride(1) == 1
+    N = row_of.numel()
+    assert row_of.dtype == torch.int32 and token.dtype == torch.int32 and row_of.is_contiguous() and token.is_contiguous()
+    assert token.numel() == N and lp.dtype == torch.float32 and lp.is_contiguous() and lp.numel() == N
+    check(L.load().mg_token_logprobs_rows_f32(logits.data_ptr(), logits.stride(0), logits.shape[0], logits.shape[1], row_of.data_ptr(),
+                                              token.data_ptr(), N, lp.data_ptr(), _stream()), "mg_token_logprobs_rows_f32")
     return lp
 
 

@@ -9,6 +9,7 @@ per-step ``(next_token == eos).all()`` host sync of the reference (:109) became
 a device-side record read every few steps.  ``top_k_filter`` / ``top_p_filter``
 below are the host statements of the same rules (pinned to the reference's own
 functions, tests/test_oracle_pins.py) and serve LM objects other than the engine."""
+import math
 import os
 from typing import Callable, List, NamedTuple, Tuple, Union
 
@@ -235,6 +236,29 @@ def process_logits(scores, history, step: int, *, repetition_penalty: float = 1.
 MAX_TRIE_LEN, MAX_TRIE_SEQS, MAX_TRIE_NODES = 64, 65536, 2 ** 20
 
 
+class TrieRows(NamedTuple):
+    """A trie's non-root nodes in depth-first preorder (TokenTrie.rows; DESIGN.md "Ranking choices"): int32 tensors."""
+    token: torch.Tensor         # [N]: the edge into node i
+    parent: torch.Tensor        # [N]: the row of its parent, -1 for a child of the root
+    off: torch.Tensor           # [N]: depth - 1; the token is fed at position p + off[i]
+    sub: torch.Tensor           # [N]: one past the last row of node i's subtree: j is i or an ancestor of i iff j <= i < sub[j]
+    terminal: torch.Tensor      # [N]: a listed sequence ends here
+    leaf_of: torch.Tensor       # [C]: the row of listed sequence c
+
+
+def pad_trie_rows(rows) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(token, off, sub) int32 [B, T] of a batch of TrieRows (None: a row without a tree), right-padded to T = the most nodes
+    of a row: a padding row carries token 0, off 0 and sub[t] = t + 1 -- it sees the prompt and itself, nobody sees it."""
+    T = max([1] + [r.token.numel() for r in rows if r is not None])
+    token, off = torch.zeros(len(rows), T, dtype=torch.int32), torch.zeros(len(rows), T, dtype=torch.int32)
+    sub = (torch.arange(T, dtype=torch.int32) + 1).repeat(len(rows), 1)
+    for b, r in enumerate(rows):
+        if r is not None:
+            n = r.token.numel()
+            token[b, :n], off[b, :n], sub[b, :n] = r.token, r.off, r.sub
+    return token, off, sub
+
+
 class TokenTrie:
     """An immutable trie over token-id sequences: the closed set of answers ``generate(constraint=...)`` keeps a row inside
     (DESIGN.md "Constrained decoding").  ``sequences``: at most 65 536 entries, each 1 to 64 ids >= 0 (a list, a tuple, a tensor)
@@ -359,6 +383,40 @@ class TokenTrie:
         """The int32 table the device reads (layout: include/magma_hip.h, mg_logits_process_constrained_f32): {n_nodes, n_edges},
         first[n_nodes + 1], terminal[n_nodes], parent[n_nodes], in_token[n_nodes], edge_token[n_edges], edge_child[n_edges]."""
         return self._flat.clone()
+
+    def rows(self, select=None) -> "TrieRows":
+        """The non-root nodes in depth-first preorder (edges ascending), the table ``rank`` feeds one forward with (DESIGN.md
+        "Ranking choices"): ``TrieRows`` of int32 tensors -- token[i] the edge into node i, parent[i] the row of its parent (-1: a
+        child of the root), off[i] = depth - 1 (the token is fed at position p + off[i]), sub[i] one past the last row of node
+        i's subtree, terminal[i], and leaf_of[c] the row of listed sequence c (duplicates share a row).  In preorder "j is i or an
+        ancestor of i" is j <= i < sub[j].  ``select``: positions of the constructor's list -- the rows of the trie of those
+        sequences only (leaf_of in that order); preorder keeps a node's row number when later sequences are left out."""
+        seqs = self.sequences if select is None else [self.sequences[c] for c in select]
+        order = sorted(set(seqs))               # lexicographic over the distinct sequences = preorder, edges ascending
+        token, parent, off, terminal, row_at = [], [], [], [], {}
+        path = []                               # rows of the current root-to-node path
+        prev = ()
+        for q in order:
+            keep = 0
+            while keep < min(len(prev), len(q)) and prev[keep] == q[keep]:
+                keep += 1
+            del path[keep:]
+            for d in range(keep, len(q)):
+                parent.append(path[-1] if path else -1)
+                path.append(len(token))
+                token.append(q[d])
+                off.append(d)
+                terminal.append(0)
+            terminal[path[-1]] = 1
+            row_at[q] = path[-1]
+            prev = q
+        n = len(token)
+        sub = [i + 1 for i in range(n)]
+        for i in range(n - 1, -1, -1):          # a parent precedes its children: fold the subtree ends upwards
+            if parent[i] >= 0:
+                sub[parent[i]] = max(sub[parent[i]], sub[i])
+        i32 = lambda v: torch.tensor(v, dtype=torch.int32)  # noqa: E731
+        return TrieRows(i32(token), i32(parent), i32(off), i32(sub), i32(terminal), i32([row_at[q] for q in seqs]))
 
     @staticmethod
     def from_flat(table) -> List[tuple]:
@@ -1210,7 +1268,7 @@ def choose(model, embeddings, choices, lengths=None, **generate_kwargs):
     TokenLogprobs of the path under the raw distribution; ``count[b]`` = the answer's tokens + the eos that ended it).
     Rows stop on their own (``stop_per_row=True`` unless given).  It follows the GREEDY path through the trie: the most probable
     next token among those allowed, step by step.  It is NOT the arg-max of the total sequence probability -- a choice whose
-    first token is unlikely loses even if the rest of it is certain; ``Magma.score`` gives every candidate's total."""
+    first token is unlikely loses even if the rest of it is certain; ``rank`` below gives every choice's total in one forward."""
     fixed = {"max_steps", "temperature", "decode", "constraint", "return_logprobs", "return_finish", "return_past_key_values",
              "num_beams", "return_scores"} & set(generate_kwargs)
     if fixed:
@@ -1235,6 +1293,220 @@ def choose(model, embeddings, choices, lengths=None, **generate_kwargs):
             ids.pop()
         index[r] = tries[r].index(ids)
     return index, lp
+
+
+class Ranking(NamedTuple):
+    """What rank() returns: CPU tensors over the B rows and the C = most choices of a row, in the caller's order; a row with fewer
+    choices is padded with -inf / 0."""
+    index: torch.Tensor         # int64 [B]: the arg-max of scores, the lowest position on an exact tie
+    scores: torch.Tensor        # fp32 [B, C]: logprobs / count ** length_penalty
+    logprobs: torch.Tensor      # fp32 [B, C]: sum_j log p(choice[j] | prompt, choice[:j]) (+ log p(eos | prompt, choice))
+    count: torch.Tensor         # int64 [B, C]: the number of terms
+
+
+def rank_groups(trie: TokenTrie, budget: int) -> List[List[int]]:
+    """The listed sequences of ``trie`` (positions of its list) in groups whose tries hold at most ``budget`` nodes each: whole
+    sequences, consecutive in preorder (lexicographic order), so the first group's nodes keep the rows they have in the whole trie;
+    a duplicate stays with its first copy.  One group when everything fits.  ValueError when one sequence alone does not."""
+    at = {}
+    for c, q in enumerate(trie.sequences):
+        at.setdefault(q, []).append(c)
+    groups, cur, n, prev = [], [], 0, ()
+    for q in sorted(at):
+        if len(q) > budget:
+            raise ValueError(f"a choice of {len(q)} tokens does not fit into {budget} free positions")
+        keep = 0
+        while cur and keep < min(len(prev), len(q)) and prev[keep] == q[keep]:
+            keep += 1
+        if cur and n + len(q) - keep > budget:
+            groups.append(cur)
+            cur, n, keep = [], 0, 0
+        cur = cur + at[q]
+        n += len(q) - keep
+        prev = q
+    groups.append(cur)
+    return groups
+
+
+def _rank_host(model, embeddings, lens, tries, eos_id, width):
+    """The definition: one forward per candidate over [prompt_b ; choice_c], log_softmax in float64 (token_logprobs).  Returns
+    the terms float64 [B, C, width]: choice c's tokens in order, then its eos term when ``eos_id`` is not None; 0 behind them."""
+    B, C = len(tries), max(len(t.sequences) for t in tries)
+    terms = torch.zeros(B, C, width, dtype=torch.float64)
+    for b, trie in enumerate(tries):
+        prompt = embeddings[b:b + 1, : int(lens[b])]
+        for c, q in enumerate(trie.sequences):
+            o = model.lm(inputs_embeds=prompt, use_cache=True, past_key_values=None)
+            logits = [o.logits[:, -1].float()]
+            fed = list(q) if eos_id is not None else list(q[:-1])
+            if fed:
+                o = model.lm(input_ids=torch.tensor([fed], dtype=torch.int64, device=prompt.device), use_cache=True,
+                             past_key_values=o.past_key_values)
+                logits.append(o.logits[0, -len(fed):].float())
+            want = list(q) + ([eos_id] if eos_id is not None else [])
+            lp, _, _ = token_logprobs(torch.cat(logits, 0), torch.tensor(want, dtype=torch.int64))
+            terms[b, c, : len(want)] = lp
+    return terms
+
+
+def _rank_engine(model, embeddings, lens, tries, eos_id, width, max_nodes):
+    """rank() on the HIP engine: one prefill of the B prompts (its logits are the root's edges), then per group of choices one
+    LMEngine.tree_forward over the trie's nodes against the same prompt cache, the fp32 head in slabs on the nodes that predict
+    something (a node with children, a terminal node when eos counts), mg_token_logprobs_rows_f32 per edge.  The sums along the
+    paths are per-level index ops on the device -- a gather of every candidate's terms, root first and the eos term last, and
+    ``width`` adds in that fixed order: C x width floats, not a cost that a kernel of its own would move.  Returns (terms fp32
+    [B, C, width], sums fp32 [B, C]) on the host."""
+    from . import ops
+    eng = model.lm.engine
+    dev = eng.device
+    B, C = len(tries), max(len(t.sequences) for t in tries)
+    n_pos = eng.cfg.max_position_embeddings
+    budget = n_pos - int(lens.max())
+    if max_nodes is not None:
+        budget = min(budget, int(max_nodes))
+    made = {}
+    for t in tries:
+        if id(t) not in made:
+            groups = rank_groups(t, budget)
+            made[id(t)] = [t.rows(g) for g in groups], groups
+    T_max = max(r.token.numel() for rs, _ in made.values() for r in rs)
+    logits0, cache, _ = eng.prefill(embeddings.to(dev), cache_hint=T_max, reuse_cache=True, lengths=lens)
+    terms, sums = torch.zeros(B, C, width), torch.full((B, C), float("-inf"))
+    for g in range(max(len(rs) for rs, _ in made.values())):
+        rows = [made[id(t)][0][g] if g < len(made[id(t)][0]) else None for t in tries]
+        token, off, sub = pad_trie_rows(rows)
+        T = token.shape[1]
+        x = eng.tree_forward(cache, (token, off, sub))
+        root_row, root_tok, need, tree_ent = [], [], [], []      # entries under the prompt's logits / under a node's logits
+        per_row = []
+        for b, r in enumerate(rows):
+            if r is None:
+                per_row.append(None)
+                continue
+            parent, term, tok = r.parent.tolist(), r.terminal.tolist(), r.token.tolist()
+            feeds = set(parent) | ({i for i, v in enumerate(term) if v} if eos_id is not None else set())
+            feeds.discard(-1)
+            slot = {i: len(need) + k for k, i in enumerate(sorted(feeds))}       # node -> its row among the head's rows
+            need += [b * T + i for i in sorted(feeds)]
+            ent = {}                                                             # node -> ("r" | "t", index in that list)
+            for i, pa in enumerate(parent):
+                if pa < 0:
+                    ent[i] = ("r", len(root_row))
+                    root_row.append(b)
+                    root_tok.append(tok[i])
+                else:
+                    ent[i] = ("t", len(tree_ent))
+                    tree_ent.append((slot[pa], tok[i]))
+            eos_ent = {}
+            if eos_id is not None:
+                for i, v in enumerate(term):
+                    if v:
+                        eos_ent[i] = ("t", len(tree_ent))
+                        tree_ent.append((slot[i], eos_id))
+            per_row.append((parent, ent, eos_ent, r.leaf_of.tolist()))
+        i32 = lambda v: torch.tensor(v, dtype=torch.int32)  # noqa: E731
+        lp_root = torch.empty(len(root_row), dtype=torch.float32, device=dev)
+        ops.token_logprobs_rows(logits0, i32(root_row).to(dev), i32(root_tok).to(dev), lp_root)
+        order = sorted(range(len(tree_ent)), key=lambda e: tree_ent[e][0])
+        where = [0] * len(order)
+        for k, e in enumerate(order):
+            where[e] = k
+        lp_tree = eng.head_token_logprobs(x, torch.tensor(need, dtype=torch.int64), i32([tree_ent[e][0] for e in order]),
+                                          i32([tree_ent[e][1] for e in order]))
+        n_root, pad = len(root_row), len(root_row) + len(tree_ent)
+        at = lambda e: e[1] if e[0] == "r" else n_root + where[e[1]]  # noqa: E731
+        gather, dest = [], []
+        for b, pr in enumerate(per_row):
+            if pr is None:
+                continue
+            parent, ent, eos_ent, leaf_of = pr
+            for c, leaf in zip(made[id(tries[b])][1][g], leaf_of):
+                path, i = [], leaf
+                while i >= 0:
+                    path.append(at(ent[i]))
+                    i = parent[i]
+                path.reverse()                                                   # root first
+                if eos_id is not None:
+                    path.append(at(eos_ent[leaf]))
+                gather.append(path + [pad] * (width - len(path)))
+                dest.append(b * C + c)
+        lp_ext = torch.cat([lp_root, lp_tree, torch.zeros(1, dtype=torch.float32, device=dev)])
+        tv = lp_ext[torch.tensor(gather, dtype=torch.int64).to(dev)]            # [n, width]; + 0.0 behind a path changes nothing
+        acc = tv[:, 0].clone()
+        for d in range(1, width):
+            acc = acc + tv[:, d]
+        dest = torch.tensor(dest, dtype=torch.int64)
+        terms.view(B * C, width)[dest] = tv.cpu()
+        sums.view(B * C)[dest] = acc.cpu()
+    return terms, sums
+
+
+@torch.no_grad()
+def rank(model, embeddings, choices, lengths=None, *, eos=True, length_penalty=0.0, max_nodes: int = None,
+         return_terms: bool = False):
+    """Rank a closed set of answers by their probability as whole sequences (Magma.rank; DESIGN.md "Ranking choices").
+    ``embeddings`` / ``lengths``: what ``generate`` takes as a prompt (a (B, S, d) tensor, a list of per-row tensors, embed_batch's
+    pair).  ``choices``: what ``choose`` takes -- a ``TokenTrie``, a list of token-id sequences or strings, or one of either per
+    row.  Returns a ``Ranking``: ``logprobs[b, c]`` = sum_j log p(choice_c[j] | prompt_b, choice_c[:j]), plus
+    log p(eos | prompt_b, choice_c) when ``eos`` (the model's eos id), all under the raw distribution -- the numbers
+    ``Magma.score`` gives; ``count`` = the number of terms; ``scores = logprobs / count ** length_penalty``; ``index`` = the arg-max
+    of ``scores``, the lowest position on an exact tie.  Columns follow the caller's list (a duplicate gets its score twice); rows
+    with fewer than C choices are padded with -inf / 0.  ``return_terms=True`` returns (Ranking, terms fp32 [B, C, L + 1]): every
+    term of the sums in order, 0 behind them.
+    This function over an LM object without the engine is the definition: one forward per candidate over [prompt ; choice].  The
+    HIP engine computes all choices of a row exactly in ONE forward over prompt + trie nodes: the prompt is prefilled once, the
+    trie's nodes go through the blocks as one chunk in which every node attends to the prompt and to its own ancestors and sits
+    at the position of its depth (LMEngine.tree_forward), so shared prefixes are computed once.  A trie with more nodes than free
+    positions (``max_position_embeddings`` - prompt, or ``max_nodes``) is split into groups of whole choices, each its own tree
+    against the same prompt cache.  ValueError: arguments ``choose`` refuses, ``eos`` that is no bool, a ``length_penalty`` that
+    is not finite, a choice that would pass ``max_position_embeddings``."""
+    if not isinstance(eos, bool):
+        raise ValueError(f"eos must be True or False (the model's eos id counts or not), got {eos!r}")
+    if isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float)) or not math.isfinite(length_penalty):
+        raise ValueError(f"length_penalty must be a finite number, got {length_penalty!r}")
+    if max_nodes is not None and (isinstance(max_nodes, bool) or not isinstance(max_nodes, int) or max_nodes < 1):
+        raise ValueError(f"max_nodes must be a positive integer, got {max_nodes!r}")
+    if is_embed_batch(embeddings):
+        embeddings, lengths = embeddings
+    if isinstance(embeddings, (list, tuple)):
+        embeddings, lengths = pad_ragged(embeddings)
+    if not torch.is_tensor(embeddings) or embeddings.ndim != 3:
+        raise ValueError("embeddings must be a (B, S, d) tensor, a list of per-row tensors or embed_batch's pair")
+    B, S, _ = embeddings.shape
+    tries = check_constraint_args(choices, B, getattr(getattr(model, "tokenizer", None), "encode", None), _logit_count(model))
+    if tries is None:
+        raise ValueError("rank() needs choices")
+    if lengths is None:
+        lens = torch.full((B,), S, dtype=torch.int64)
+    else:
+        lens = torch.as_tensor(lengths).detach().to("cpu")
+        if lens.is_floating_point() or lens.dtype == torch.bool or lens.ndim != 1 or lens.shape[0] != B:
+            raise ValueError(f"lengths must be {B} integers (one prompt length per row), got {lens.dtype} {tuple(lens.shape)}")
+        lens = lens.to(torch.int64)
+        if int(lens.min()) < 1 or int(lens.max()) > S:
+            raise ValueError(f"every length must lie in [1, {S}], got {lens.tolist()}")
+    n_pos = getattr(getattr(model.lm, "config", None), "max_position_embeddings", None)
+    for b, t in enumerate(tries):
+        if n_pos is not None and int(lens[b]) + t.max_len() > n_pos:
+            raise ValueError(f"row {b}: the prompt ({int(lens[b])} positions) plus its longest choice ({t.max_len()} tokens) "
+                             f"passes max_position_embeddings = {n_pos}")
+    eos_id = int(model.eos_token) if eos else None
+    C, width = max(len(t.sequences) for t in tries), max(t.max_len() for t in tries) + 1
+    if getattr(model.lm, "device_token_selection", False):
+        terms, sums = _rank_engine(model, embeddings, lens, tries, eos_id, width, max_nodes)
+    else:
+        t64 = _rank_host(model, embeddings, lens, tries, eos_id, width)
+        terms, sums = t64.float(), t64.sum(-1).float()
+    count = torch.zeros(B, C, dtype=torch.int64)
+    for b, t in enumerate(tries):
+        count[b, : len(t.sequences)] = torch.tensor([len(q) + int(eos) for q in t.sequences], dtype=torch.int64)
+    live = count > 0
+    logprobs = torch.where(live, sums, torch.full_like(sums, float("-inf")))
+    scores = torch.where(live, logprobs / count.clamp(min=1).to(torch.float32) ** float(length_penalty), logprobs)
+    best = scores.max(dim=1, keepdim=True).values
+    index = torch.where(scores == best, torch.arange(C)[None, :], torch.full((1, 1), C)).min(dim=1).values
+    out = Ranking(index.to(torch.int64), scores, logprobs, count)
+    return (out, terms) if return_terms else out
 
 
 def keep_conversation(cache, start: torch.Tensor, n_gen: int, eos_token, finish: Finish = None):
