@@ -19,7 +19,7 @@ Per block (parallel residual, adapters after attention/MLP):
 from __future__ import annotations
 
 import os
-from typing import List, Optional
+from typing import Any, List, NamedTuple, Optional
 
 import torch
 
@@ -71,10 +71,10 @@ class KVCache:
         self.pending = None
         # token log-probabilities (DESIGN.md "Token log-probabilities"), beside the history: fp32 [B, Smax] log-probability of the
         # token selected at step s, and the n_top most probable tokens of that step (int32 / fp32 [B, Smax, n_top]); allocated on
-        # first request (LMEngine._arm_logprobs), addresses and n_top are launch arguments of the captured step
+        # first request (SelectionPlan.arm), addresses and n_top are launch arguments of the captured step
         self.lp = self.top_id = self.top_lp = None
         # constrained decoding (DESIGN.md "Constrained decoding"): the trie table (int32, grown when a table outgrows it), the
-        # per-row roots int32 [B] and the kernel's path cache int32 [B, 64]; allocated on first use (LMEngine._arm_constraint).
+        # per-row roots int32 [B] and the kernel's path cache int32 [B, 64]; allocated on first use (SelectionPlan.arm).
         # Addresses and the table's capacity are launch arguments of the captured step, the contents are not; trie_held is the
         # ConstraintMode whose table and roots the buffers hold
         self.trie_table = self.trie_roots = self.trie_path = self.trie_held = None
@@ -89,9 +89,7 @@ class KVCache:
         if self.trie_roots is None:
             self.trie_roots = torch.zeros(self.B, dtype=torch.int32, device=dev)
             self.trie_path = ops.trie_path(self.B, dev)
-        if self.decode_state is not None:
-            for key in [k for k in self.decode_state.graphs if ("constraint",) in k]:
-                del self.decode_state.graphs[key]
+        self._drop_graphs(lambda key: key.constrained)
 
     def alloc_logprobs(self, n_top: int):
         """The per-step log-probability buffers for ``n_top`` alternatives per token (kept when they already have that shape);
@@ -102,9 +100,7 @@ class KVCache:
         self.lp = torch.zeros(self.B, self.Smax, dtype=torch.float32, device=dev)
         self.top_id = torch.zeros(self.B, self.Smax, n_top, dtype=torch.int32, device=dev)
         self.top_lp = torch.zeros(self.B, self.Smax, n_top, dtype=torch.float32, device=dev)
-        if self.decode_state is not None:
-            for key in [k for k in self.decode_state.graphs if any(isinstance(e, tuple) and e[:1] == ("logprobs",) for e in k)]:
-                del self.decode_state.graphs[key]
+        self._drop_graphs(lambda key: key.n_top is not None)
 
     def __len__(self):
         return self.k.shape[0]
@@ -115,9 +111,11 @@ class KVCache:
             return torch.full((self.B,), self.pos, dtype=torch.int64)
         return self._rows + (self.pos - self._rows_at)
 
-    def _drop_graphs(self):
-        if self.decode_state is not None:
-            self.decode_state.graphs.clear()
+    def _drop_graphs(self, which=lambda key: True):
+        """Forget the captured steps whose StepKey ``which`` selects (by default all of them)."""
+        graphs = self.decode_state.graphs if self.decode_state is not None else {}
+        for key in [k for k in graphs if which(k)]:
+            del graphs[key]
 
     def set_rows(self, pos, pending=None):
         """Row b's next write position becomes pos[b] (host ints; the cache turns ragged), its not-yet-fed token pending[b] (-1 none)."""
@@ -204,18 +202,9 @@ class _Layer:
     pass
 
 
-class ProcMode(tuple):
-    """LMEngine.proc_mode's checked (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress ids): passed again as
-    ``processors=`` it is taken as it is (generate() checks once, not once per token)."""
-
-
-class StopMode(tuple):
-    """LMEngine.stop_mode's checked (eos ids, stop sequences): passed again as ``stop=`` it is taken as it is."""
-
-
 class ConstraintMode:
     """LMEngine.constraint_mode's checked constraint: the host copies of the table and the per-row roots (sampling.trie_forest)
-    and the largest token id; passed again as ``constraint=`` it is taken as it is (generate() builds it once, not once per token)."""
+    and the largest token id."""
 
     def __init__(self, tries):
         from .sampling import trie_forest
@@ -223,8 +212,125 @@ class ConstraintMode:
         self.max_token = max(max(t.tokens()) for t in {id(t): t for t in tries}.values())
 
 
-class GuidanceMode(tuple):
-    """LMEngine.guidance_mode's checked (guidance_scale, guidance_min_p): passed again as ``guidance=`` it is taken as it is."""
+class StepKey(NamedTuple):
+    """What the launches of a token step depend on (SelectionPlan.graph_key): two steps share a captured graph exactly when their
+    keys are equal.  Launch arguments are in it; the contents of the device tables, rewritten between replays, are not."""
+    feed_back: bool
+    mode: Any                   # None (greedy), the sampling tuple, the beam tuple, or "noselect" (a teacher-forced position)
+    proc: Optional[tuple]       # (repetition_penalty, no_repeat_ngram_size, min_new_tokens, NUMBER of suppress ids)
+    stop: Optional[tuple]       # (number of eos ids, number of stop sequences, pad id)
+    n_top: Optional[int]        # the log-probability buffers' addresses are launch arguments too (KVCache.alloc_logprobs)
+    constrained: bool           # the trie buffers' addresses and capacity are launch arguments (KVCache.alloc_trie)
+    guidance: Optional[tuple]   # (scale, cut)
+
+    @property
+    def beam(self) -> bool:
+        return isinstance(self.mode, tuple) and self.mode[:1] == ("beam",)
+
+
+class SelectionPlan(NamedTuple):
+    """The checked modes of one token step (DESIGN.md "The selection plan"), built once per call by LMEngine.selection_plan --
+    the only place that normalises the public keywords and refuses their combinations -- and handed down as it is: forward,
+    decode, _arm_first_token, _decode_step and select_token read it, nothing below re-checks it."""
+    mode: Any = None                        # None (greedy), sample_mode's tuple, or beam_mode's tuple
+    proc: Optional[tuple] = None            # proc_mode: (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress ids)
+    stop: Optional[tuple] = None            # stop_mode: (eos ids, stop sequences)
+    n_top: Optional[int] = None             # logprob_mode
+    cons: Optional[ConstraintMode] = None   # constraint_mode
+    guidance: Optional[tuple] = None        # guidance_mode: (scale, cut)
+    vocab: Optional[int] = None             # V the token ids were checked against (None: arm() cannot check them)
+    select: bool = True                     # False: a teacher-forced position, only the KV write position advances
+    keys: tuple = ()                        # graph_key of feed_back False / True, computed once (keyed)
+
+    @property
+    def is_beam(self) -> bool:
+        return isinstance(self.mode, tuple) and self.mode[:1] == ("beam",)
+
+    @property
+    def rewrites_logits(self) -> bool:
+        """Something runs in place on the logits in front of the selection: the first token is then selected from a copy (the
+        caller's ``.logits`` stay raw), and a step that also reports log-probabilities works on the second logits buffer."""
+        return self.proc is not None or self.cons is not None or self.guidance is not None
+
+    @property
+    def second_buffer(self) -> bool:
+        return self.n_top is not None and self.rewrites_logits
+
+    def without_selection(self) -> "SelectionPlan":
+        """The plan of a teacher-forced position of a multi-token call: nothing selected, nothing processed or recorded (a beam
+        mode stays, for arm() to find the cache armed for it; the step's key does not read it)."""
+        return SelectionPlan(mode=self.mode if self.is_beam else None, vocab=self.vocab, select=False).keyed()
+
+    def keyed(self) -> "SelectionPlan":
+        """The plan with both of its step keys computed: a replayed step looks its graph up without building anything."""
+        p, s = self.proc, self.stop
+        rest = (self.mode if self.select else "noselect", None if p is None else tuple(p[:3]) + (len(p[3]),),
+                None if s is None else (len(s[0]), len(s[1]), s[0][0]), self.n_top, self.cons is not None, self.guidance)
+        return self._replace(keys=(StepKey(False, *rest), StepKey(True, *rest)))
+
+    def graph_key(self, feed_back: bool) -> StepKey:
+        return (self.keys or self.keyed().keys)[bool(feed_back)]
+
+    def rows(self, cache: KVCache) -> int:
+        """The rows the selection runs over: all of the cache's, or -- guided -- its first half."""
+        if self.guidance is None:
+            return cache.B
+        if cache.B % 2 or cache.pos_stride != 1:
+            raise ValueError(f"guidance needs a ragged cache of 2R rows (prompts, then negative prompts), got {cache.B} rows"
+                             f"{'' if cache.pos_stride == 1 else ' with one shared position'}")
+        return cache.B // 2
+
+    def arm(self, cache: KVCache, st, first: bool = False):
+        """What the step's launches read and the step does not write, in the cache's device buffers -- never touched inside a
+        captured step: decode() and _arm_first_token call this before anything is captured or replayed.  Token ids are checked
+        against the vocabulary; the suppress ids, the stop table, the trie's table and roots are copied only when they differ
+        from what the buffers hold (a table that outgrows its buffer re-allocates it: KVCache.alloc_trie); the log-probability
+        buffers and -- when something rewrites the logits too -- the second logits buffer are allocated.  ``first``: the call
+        that starts a loop marks every row unfinished; a later step finds the cache armed or refuses."""
+        dev, V = cache.k.device, self.vocab if self.vocab is not None else float("inf")
+        if self.is_beam and not first and (cache.beam is None or cache.beam.k != self.mode[1]):
+            raise ValueError("beam decoding needs a cache armed for this num_beams (prefill with eos_token= and beam=)")
+        if self.proc is not None:
+            ids = self.proc[3]
+            if any(t >= V for t in ids):
+                raise ValueError(f"suppress_tokens must be token ids in [0, {V}), got {[t for t in ids if t >= V]}")
+            if cache.suppress is None:
+                cache.suppress = torch.zeros(1024, dtype=torch.int32, device=dev)
+            if ids and ids != cache.suppress_ids:
+                cache.suppress[: len(ids)].copy_(torch.tensor(ids, dtype=torch.int32), non_blocking=True)
+                cache.suppress_ids = ids
+        if self.stop is not None:
+            eos_ids, seqs = self.stop
+            if not first and cache.finish is None:
+                raise ValueError("per-row stopping needs a cache armed for it (prefill with eos_token= and stop=)")
+            ids = list(eos_ids) + [t for q in seqs for t in q]
+            if any(t >= V for t in ids):
+                raise ValueError(f"eos ids and stop sequences must be token ids in [0, {V}), got {[t for t in ids if t >= V]}")
+            if cache.stop_table is None:
+                cache.stop_table = torch.zeros(ops.STOP_TABLE_INTS, dtype=torch.int32, device=dev)
+                cache.finish = torch.zeros(cache.B, 2, dtype=torch.int32, device=dev)
+            if tuple(self.stop) != cache.stop_held:
+                cache.stop_table.copy_(ops.stop_table(eos_ids, seqs), non_blocking=True)
+                cache.stop_held = tuple(self.stop)
+            if first:       # every row unfinished again
+                cache.finish.copy_(torch.tensor([[-1, 0]] * cache.B, dtype=torch.int32), non_blocking=True)
+        rows = self.rows(cache)
+        cons = self.cons
+        if cons is not None:
+            if cons.max_token >= V:
+                raise ValueError(f"the constraint holds token ids outside [0, {V})")
+            if cons.roots.numel() != rows:
+                raise ValueError(f"the constraint has {cons.roots.numel()} rows, the cache {rows}")
+            cache.alloc_trie(cons.table.numel())
+            held = cache.trie_held
+            if not (held is cons or (held is not None and torch.equal(held.table, cons.table) and torch.equal(held.roots, cons.roots))):
+                cache.trie_table[: cons.table.numel()].copy_(cons.table, non_blocking=True)
+                cache.trie_roots[:rows].copy_(cons.roots, non_blocking=True)
+                cache.trie_held = cons
+        if self.n_top is not None:
+            cache.alloc_logprobs(self.n_top)
+            if self.rewrites_logits and st.logits_proc is None:
+                st.logits_proc = torch.empty_like(st.logits)
 
 
 class LMEngine:
@@ -617,8 +723,9 @@ class LMEngine:
                 output_hidden_states=False, cache_hint: Optional[int] = None, reuse_cache: bool = False,
                 return_logits: bool = False, sampling=None, eos_token: Optional[int] = None,
                 seed: Optional[int] = None, feed_back: bool = False, lengths=None, beam=None, processors=None,
-                stop=None, logprobs=None, constraint=None, guidance=None) -> LMOutput:
-        """``beam`` = (num_beams, length_penalty, early_stopping, max_steps): beam-search token selection (the rows are
+                stop=None, logprobs=None, constraint=None, guidance=None, plan=None) -> LMOutput:
+        """``plan`` (a SelectionPlan): selection_plan's checked form of the seven selection keywords that follow, INSTEAD of them.
+        ``beam`` = (num_beams, length_penalty, early_stopping, max_steps): beam-search token selection (the rows are
         samples x num_beams, sample-major; DESIGN.md "Beam search") instead of ``sampling``.
         ``processors`` (sampling.check_processor_args' dict, or None): the logits processors in front of whichever selection
         runs (DESIGN.md "Logits processors").  The first token is selected from a processed COPY of the prefill / extend
@@ -630,10 +737,10 @@ class LMEngine:
         token's log-probability under the RAW distribution of the step, and the n_top most probable tokens, into column
         step of the cache's lp / top_id / top_lp buffers (DESIGN.md "Token log-probabilities"); passed like ``stop``; not with
         ``beam``.
-        ``constraint`` (a list of one sampling.TokenTrie per row, constraint_mode's object, or None): the trie constraint in the
+        ``constraint`` (a list of one sampling.TokenTrie per row, or None): the trie constraint in the
         processors' launch (DESIGN.md "Constrained decoding") -- it counts as a processor: the first token comes from a processed
         copy, with ``logprobs`` the step works on the second buffer; passed like ``processors``; not with ``beam``.
-        ``guidance`` ((guidance_scale, guidance_min_p), guidance_mode's object, or None): classifier-free guidance (DESIGN.md
+        ``guidance`` ((guidance_scale, guidance_min_p), or None): classifier-free guidance (DESIGN.md
         "Classifier-free guidance").  The batch is 2R ragged rows: rows [0, R) the prompts, rows [R, 2R) the negative prompts.  One
         launch combines row r with row R + r in front of the processors, everything from there to the bookkeeping runs over the
         first R rows (and the first R rows of the per-row buffers), one launch copies the token to row R + r and advances its
@@ -643,15 +750,10 @@ class LMEngine:
         of different lengths, right-padded to S.  Row b's logits are those of its position len_b - 1, and the cache keeps one
         write position per row (len_b, then + 1 per step) -- see DESIGN.md, "Ragged batches"."""
         extending = past_key_values is not None and inputs_embeds is not None
-        if stop is not None and beam is not None:
-            raise NotImplementedError("per-row stopping is not combined with beam search")
-        if logprobs is not None and beam is not None:
-            raise NotImplementedError("token log-probabilities are not combined with beam search (it has its own scores)")
-        if constraint is not None and beam is not None:
-            raise NotImplementedError("a constraint is not combined with beam search")
-        if guidance is not None and beam is not None:
-            raise NotImplementedError("guidance is not combined with beam search")
-        if guidance is not None and extending:
+        if plan is None:
+            plan = self.selection_plan(sampling=sampling, beam=beam, processors=processors, stop=stop, logprobs=logprobs,
+                                       constraint=constraint, guidance=guidance, vocab=self.V)
+        if plan.guidance is not None and extending:
             raise NotImplementedError("guidance does not continue from a KV cache")
         if lengths is not None and (labels is not None or (past_key_values is not None and not extending) or not use_cache):
             raise ValueError("lengths= applies to the prefill call and to inputs_embeds appended to a cache (use_cache=True, no "
@@ -664,12 +766,12 @@ class LMEngine:
             # inputs_embeds appended to a cache (the HF GPT-Neo forward takes this pair; positions follow the past): one chunk pass
             if input_ids is not None:
                 raise ValueError("pass input_ids or inputs_embeds, not both")
-            if beam is not None:
+            if plan.is_beam:
                 raise NotImplementedError("beam search does not continue from a KV cache")
             logits, cache, full = self.extend(past_key_values, inputs_embeds, lengths=lengths, cache_hint=cache_hint)
             out = LMOutput(logits=logits.unsqueeze(1), past_key_values=cache, hidden_states=None, loss=None, full_logits=full)
             if eos_token is not None:
-                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, None, processors, stop, logprobs, constraint)
+                self._arm_first_token(out, logits, cache, eos_token, seed, plan)
             return out
         if past_key_values is not None:
             if not feed_back and input_ids is None:
@@ -683,15 +785,11 @@ class LMEngine:
                     raise ValueError("cached decoding needs at least one new token")
                 rows = []
                 for i in range(T):      # only the LAST position selects a token (history / RNG step / eos latch untouched before)
-                    lg, tok = self.decode(input_ids[:, i:i + 1], past_key_values, sampling=sampling, select=i == T - 1,
-                                          beam=beam, processors=processors, stop=stop, logprobs=logprobs, constraint=constraint,
-                                          guidance=guidance)
+                    lg, tok = self.decode(input_ids[:, i:i + 1], past_key_values, select=i == T - 1, plan=plan)
                     rows.append(lg.clone())
                 return LMOutput(logits=torch.stack(rows, 1), past_key_values=past_key_values, next_token=tok, loss=None,
                                 eos_state=past_key_values.sample_state)
-            logits, tok = self.decode(None if feed_back else input_ids, past_key_values, sampling=sampling, beam=beam,
-                                      processors=processors, stop=stop, logprobs=logprobs, constraint=constraint,
-                                      guidance=guidance)
+            logits, tok = self.decode(None if feed_back else input_ids, past_key_values, plan=plan)
             return LMOutput(logits=logits.unsqueeze(1), past_key_values=past_key_values, next_token=tok, loss=None,
                             eos_state=past_key_values.sample_state)
         if inputs_embeds is None:
@@ -701,13 +799,32 @@ class LMEngine:
             # generate() only reads the last position, so only that row is computed
             out = LMOutput(logits=logits.unsqueeze(1), past_key_values=cache, hidden_states=hs, loss=None)
             if eos_token is not None:
-                self._arm_first_token(out, logits, cache, eos_token, seed, sampling, beam, processors, stop, logprobs, constraint,
-                                      guidance)
+                self._arm_first_token(out, logits, cache, eos_token, seed, plan)
             return out
         x, hs = self._blocks_prefill(inputs_embeds, None, output_hidden_states)
         B, S, _ = inputs_embeds.shape
         logits = self._full_logits(x, B * S).view(B, S, self.V)
         return LMOutput(logits=logits, past_key_values=None, hidden_states=hs, loss=None)
+
+    @classmethod
+    def selection_plan(cls, plan=None, *, sampling=None, beam=None, processors=None, stop=None, logprobs=None, constraint=None,
+                       guidance=None, vocab: Optional[int] = None) -> SelectionPlan:
+        """The SelectionPlan of the public selection keywords (forward's), checked: the one place that calls the normalisers
+        below and that refuses what beam search is not combined with.  A plan that is already built comes back as it is, so a
+        loop builds one and passes ``plan=`` on every call.  ``vocab``: the number of logits V the token ids must lie in."""
+        if plan is not None:
+            if any(v is not None for v in (sampling, beam, processors, stop, logprobs, constraint, guidance)):
+                raise ValueError("pass plan= or the selection keywords it was built from, not both")
+            return plan
+        for what, given in (("per-row stopping is", stop), ("token log-probabilities are", logprobs),
+                            ("a constraint is", constraint), ("guidance is", guidance)):
+            if beam is not None and given is not None:
+                raise NotImplementedError(f"{what} not combined with beam search")
+        mode = cls.sample_mode(sampling)
+        if beam is not None:
+            mode = cls.beam_mode(beam)
+        return SelectionPlan(mode, cls.proc_mode(processors), cls.stop_mode(stop), cls.logprob_mode(logprobs, vocab),
+                             cls.constraint_mode(constraint), cls.guidance_mode(guidance), vocab).keyed()
 
     @staticmethod
     def sample_mode(sampling):
@@ -724,123 +841,50 @@ class LMEngine:
 
     @staticmethod
     def proc_mode(processors):
-        """None (nothing is enqueued) or (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress ids): the processor
-        mode that travels beside the selection mode."""
-        if processors is None or isinstance(processors, ProcMode):
-            return processors
+        """None (nothing is enqueued) or (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress ids), from
+        sampling.check_processor_args' keywords."""
+        if processors is None:
+            return None
         from .sampling import check_processor_args
         d = check_processor_args(**processors)
-        return None if d is None else ProcMode((d["repetition_penalty"], d["no_repeat_ngram_size"], d["min_new_tokens"],
-                                                d["suppress_tokens"]))
-
-    def _arm_processors(self, cache: KVCache, proc):
-        """The suppress ids of ``proc`` in the cache's device buffer (written only when they differ from what it holds; never
-        inside a captured step: decode() calls this before it captures or replays)."""
-        if proc is None:
-            return
-        ids = proc[3]
-        if any(t >= self.V for t in ids):
-            raise ValueError(f"suppress_tokens must be token ids in [0, {self.V}), got {[t for t in ids if t >= self.V]}")
-        if cache.suppress is None:
-            cache.suppress = torch.zeros(1024, dtype=torch.int32, device=self.device)
-        if ids and ids != cache.suppress_ids:
-            cache.suppress[: len(ids)].copy_(torch.tensor(ids, dtype=torch.int32), non_blocking=True)
-            cache.suppress_ids = ids
+        return None if d is None else (d["repetition_penalty"], d["no_repeat_ngram_size"], d["min_new_tokens"], d["suppress_tokens"])
 
     @staticmethod
     def constraint_mode(constraint):
-        """None (today's launches) or a ConstraintMode: the constraint mode that travels beside the processor mode."""
-        if constraint is None or isinstance(constraint, ConstraintMode):
-            return constraint
-        return ConstraintMode(list(constraint))
+        """None (today's launches) or a ConstraintMode, from one sampling.TokenTrie per row."""
+        return None if constraint is None else ConstraintMode(list(constraint))
 
     @staticmethod
     def guidance_mode(guidance):
-        """None (today's launches) or a GuidanceMode (guidance_scale, guidance_min_p): the guidance mode that travels beside the
-        processor mode; its values are launch arguments of the captured step, so it is part of the step's key."""
-        if guidance is None or isinstance(guidance, GuidanceMode):
-            return guidance
+        """None (today's launches) or (guidance_scale, guidance_min_p) as floats: launch arguments of the captured step."""
+        if guidance is None:
+            return None
         from .sampling import check_guidance_values
         scale, min_p = guidance
         check_guidance_values(scale, min_p)
-        return GuidanceMode((float(scale), float(min_p)))
-
-    @staticmethod
-    def _guided_rows(cache: KVCache, gd) -> int:
-        """The rows the selection runs over: all of the cache's, or -- guided -- its first half."""
-        if gd is None:
-            return cache.B
-        if cache.B % 2 or cache.pos_stride != 1:
-            raise ValueError(f"guidance needs a ragged cache of 2R rows (prompts, then negative prompts), got {cache.B} rows"
-                             f"{'' if cache.pos_stride == 1 else ' with one shared position'}")
-        return cache.B // 2
-
-    def _arm_constraint(self, cache: KVCache, cons, rows: Optional[int] = None):
-        """The table and the roots of ``cons`` in the cache's device buffers (written only when they differ from what the buffers
-        hold; never inside a captured step: decode() calls this before it captures or replays).  A table that outgrows the
-        buffer re-allocates it, which drops the steps captured on it (KVCache.alloc_trie)."""
-        if cons is None:
-            return
-        if cons.max_token >= self.V:
-            raise ValueError(f"the constraint holds token ids outside [0, {self.V})")
-        rows = cache.B if rows is None else rows      # (guided: the first half of the cache's rows)
-        if cons.roots.numel() != rows:
-            raise ValueError(f"the constraint has {cons.roots.numel()} rows, the cache {rows}")
-        cache.alloc_trie(cons.table.numel())
-        held = cache.trie_held
-        if held is cons or (held is not None and torch.equal(held.table, cons.table) and torch.equal(held.roots, cons.roots)):
-            return
-        cache.trie_table[: cons.table.numel()].copy_(cons.table, non_blocking=True)
-        cache.trie_roots[:rows].copy_(cons.roots, non_blocking=True)
-        cache.trie_held = cons
+        return (float(scale), float(min_p))
 
     @staticmethod
     def stop_mode(stop):
-        """None (the reference's rule: mg_sample_finish) or (eos ids, stop sequences): the stop mode that travels beside the
-        selection mode.  The pad id is the first eos id."""
-        if stop is None or isinstance(stop, StopMode):
-            return stop
+        """None (the reference's rule: mg_sample_finish) or (eos ids, stop sequences), from sampling.check_stop_args' dict.  The
+        pad id is the first eos id."""
+        if stop is None:
+            return None
         from .sampling import check_stop_args
         d = check_stop_args(list(stop["eos_ids"]), list(stop.get("stop_seqs", ())), True)
-        return StopMode((d["eos_ids"], d["stop_seqs"]))
+        return (d["eos_ids"], d["stop_seqs"])
 
-    def _arm_stop(self, cache: KVCache, stop):
-        """The stop table of ``stop`` in the cache's device buffer (written only when it differs from what the buffer holds;
-        never inside a captured step: decode() calls this before it captures or replays), and the finish record allocated."""
-        if stop is None:
-            return
-        ids = list(stop[0]) + [t for q in stop[1] for t in q]
-        if any(t >= self.V for t in ids):
-            raise ValueError(f"eos ids and stop sequences must be token ids in [0, {self.V}), got {[t for t in ids if t >= self.V]}")
-        if cache.stop_table is None:
-            cache.stop_table = torch.zeros(ops.STOP_TABLE_INTS, dtype=torch.int32, device=self.device)
-            cache.finish = torch.zeros(cache.B, 2, dtype=torch.int32, device=self.device)
-        if tuple(stop) != cache.stop_held:
-            cache.stop_table.copy_(ops.stop_table(stop[0], stop[1]), non_blocking=True)
-            cache.stop_held = tuple(stop)
-
-    def logprob_mode(self, logprobs):
-        """None (nothing is launched or allocated) or n_top, the number of alternatives per token: the log-probability mode that
-        travels beside the selection mode."""
+    @staticmethod
+    def logprob_mode(logprobs, vocab: Optional[int] = None):
+        """None (nothing is launched or allocated) or n_top, the number of alternatives per token."""
         if logprobs is None:
             return None
         n = logprobs
-        if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= ops.LOGPROBS_MAX_TOP or n > self.V:
-            raise ValueError(f"logprobs must be None or an integer in [0, min({ops.LOGPROBS_MAX_TOP}, V = {self.V})], got {n!r}")
+        if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= ops.LOGPROBS_MAX_TOP or (vocab is not None and n > vocab):
+            raise ValueError(f"logprobs must be None or an integer in [0, min({ops.LOGPROBS_MAX_TOP}, V = {vocab})], got {n!r}")
         return n
 
-    def _arm_logprobs(self, cache: KVCache, st, n_top, proc):
-        """The buffers of the log-probability mode (never allocated inside a captured step: decode() calls this before it captures
-        or replays): the cache's per-step outputs and, when the logits processors run too, the decode state's second logits
-        buffer -- the processors and the selection work on a copy, the log-probabilities read the raw row."""
-        if n_top is None:
-            return
-        cache.alloc_logprobs(n_top)
-        if proc is not None and st.logits_proc is None:
-            st.logits_proc = torch.empty_like(st.logits)
-
-    def _arm_first_token(self, out: LMOutput, logits, cache: KVCache, eos_token, seed, sampling, beam, processors=None, stop=None,
-                         logprobs=None, constraint=None, guidance=None):
+    def _arm_first_token(self, out: LMOutput, logits, cache: KVCache, eos_token, seed, plan: SelectionPlan):
         """generate(): the first token of the loop selected from the prefill / extend logits, device-side bookkeeping armed."""
         if cache.eos != int(eos_token):        # the eos id is a launch argument of the captured bookkeeping kernel
             cache.eos = int(eos_token)
@@ -849,34 +893,19 @@ class LMEngine:
         if seed is not None:
             cache.seed.fill_(int(seed) & 0x7fffffffffffffff)
         st = self._ensure_decode_state(cache)      # the first token lands where the decode steps read it back
-        mode = self.sample_mode(sampling)
-        if beam is not None:
-            mode = self._arm_beam(cache, st, beam)
+        if plan.is_beam:
+            self._arm_beam(cache, st, plan.mode)
         elif cache.beam is not None:
             # a pooled cache that last served beam search starts a greedy / sampled call: without its beam buffers (the K / V
             # staging copies are as large as the cache) and the steps captured on them -- it may be handed to the caller and
             # continued (extend refuses a cache that is mid-beam)
             cache.beam = None
-            for key in [k for k in st.graphs if isinstance(k[0], tuple) and k[0][:1] == ("beam",)]:
-                del st.graphs[key]
-        proc = self.proc_mode(processors)
-        cons = self.constraint_mode(constraint)   # (forward has refused the combination with beam)
-        gd = self.guidance_mode(guidance)         # (the same)
-        raw = logits
-        if proc is not None or cons is not None or gd is not None:       # step 0 of the rules on a copy: the caller's .logits stay raw
-            self._arm_processors(cache, proc)
-            self._arm_constraint(cache, cons, self._guided_rows(cache, gd))
-            logits = logits.clone()
-        n_top = self.logprob_mode(logprobs)       # (forward has refused the combination with beam)
-        self._arm_logprobs(cache, st, n_top, proc if proc is not None else cons if cons is not None else gd)
-        stop = self.stop_mode(stop)
-        if stop is not None:       # every row unfinished again
-            if int(eos_token) != stop[0][0]:
-                raise ValueError(f"per-row stopping pads with the first eos id: eos_token must be {stop[0][0]}, got {eos_token}")
-            self._arm_stop(cache, stop)
-            cache.finish.copy_(torch.tensor([[-1, 0]] * cache.B, dtype=torch.int32), non_blocking=True)
-        out["next_token"] = self.select_token(logits, cache, mode, out=st.token, proc=proc, stop=stop, logprobs=n_top, raw=raw,
-                                                cons=cons, guidance=gd)
+            cache._drop_graphs(lambda key: key.beam)
+        if plan.stop is not None and int(eos_token) != plan.stop[0][0]:
+            raise ValueError(f"per-row stopping pads with the first eos id: eos_token must be {plan.stop[0][0]}, got {eos_token}")
+        plan.arm(cache, st, first=True)
+        # step 0 of the rules runs on a copy: the caller's .logits stay raw
+        out["next_token"] = self.select_token(logits.clone() if plan.rewrites_logits else logits, cache, plan, out=st.token, raw=logits)
         out["eos_state"] = cache.sample_state
 
     def embed_ids(self, ids: torch.Tensor) -> torch.Tensor:
@@ -1188,9 +1217,9 @@ class LMEngine:
         st.lnf = e(B, d)
         st.ad_ln = e(B, d)                 # LayerNorm output in front of an adapter built with add_layernorm
         st.logits = e(B, self.Vp, dt=torch.float32)
-        st.logits_proc = None      # with logprobs AND processors: the copy the processors and the selection work on (_arm_logprobs)
+        st.logits_proc = None      # with logprobs AND processors: the copy the processors and the selection work on (SelectionPlan.arm)
         st.token = torch.zeros(B, dtype=torch.int64, device=dev)
-        st.graphs = {}             # (token-selection mode, feed_back[, processor values]) -> captured hipGraph
+        st.graphs = {}             # StepKey (SelectionPlan.graph_key) -> captured hipGraph
         st.steps = 0
         return st
 
@@ -1202,10 +1231,9 @@ class LMEngine:
         es = check_beam_args(int(k), 1, es)
         return ("beam", int(k), float(lp), es, int(n))
 
-    def _arm_beam(self, cache: KVCache, st, beam):
-        """Beam buffers of this cache for num_beams = k (re-allocated -- and the captured steps dropped -- when k changes),
-        reset for a new generate() call.  Returns the selection mode."""
-        mode = self.beam_mode(beam)
+    def _arm_beam(self, cache: KVCache, st, mode):
+        """Beam buffers of this cache for num_beams = k of the beam ``mode`` (re-allocated -- and the captured steps dropped --
+        when k changes), reset for a new generate() call."""
         k = mode[1]
         if cache.B % k:
             raise ValueError(f"beam search over {cache.B} cache rows with num_beams = {k}: rows must be samples x num_beams")
@@ -1215,14 +1243,13 @@ class LMEngine:
             cache.beam = BeamBuffers(cache, k, st.token)
             st.graphs.clear()
         cache.beam.reset(cache.eos)
-        return mode
 
-    def _select_beam(self, logits: torch.Tensor, cache: KVCache, mode, advance: bool, normalized: bool = False):
-        """The beam step's three launches: per-row top 2k, the bookkeeping of every sample, the K / V reorder by parent.
-        ``normalized``: the logits processors' launch has already turned the rows into (processed) log_softmax scores."""
+    def _select_beam(self, logits: torch.Tensor, cache: KVCache, plan: SelectionPlan, advance: bool):
+        """The beam step's three launches: per-row top 2k, the bookkeeping of every sample, the K / V reorder by parent.  With
+        processors, their launch has already turned the rows into (processed) log_softmax scores."""
         bm = cache.beam
-        _, k, lp, es, max_steps = mode
-        ops.beam_topk(logits, bm.run, bm.cand_score, bm.cand_tok, normalized=normalized)
+        _, k, lp, es, max_steps = plan.mode
+        ops.beam_topk(logits, bm.run, bm.cand_score, bm.cand_tok, normalized=plan.proc is not None)
         ops.beam_finish(bm.cand_score, bm.cand_tok, bm.B, k, logits.shape[1], cache.eos, lp, es, max_steps, cache.sample_state,
                         bm.bufs, d_pos=cache.d_pos if advance else None, pos_stride=cache.pos_stride)
         ops.kv_reorder(cache.k, cache.v, bm.kstage, bm.vstage, bm.parent, cache.d_pos, pos_stride=cache.pos_stride)
@@ -1237,39 +1264,36 @@ class LMEngine:
         toks = bm.fin_tok.view(bm.B, bm.k, -1)[:, :n_ret, :n].reshape(bm.B * n_ret, n)
         return toks.clone(), bm.fin_score.view(bm.B, bm.k)[:, :n_ret].reshape(-1).clone(), lens
 
-    def select_token(self, logits: torch.Tensor, cache: KVCache, mode, out: Optional[torch.Tensor] = None,
-                     advance: bool = False, clear: Optional[torch.Tensor] = None, proc=None, stop=None, logprobs=None,
-                     raw: Optional[torch.Tensor] = None, cons=None, guidance=None) -> torch.Tensor:
-        """next token of every row from fp32 logits (B, V): greedy argmax (mode None; reference sampling.py:96-97) or the
-        sampled branch (mode = (temperature, top_k, top_p); :99-107 -- or ("warp", temperature, top_k, top_p, min_p):
-        transformers' sampler, sample_mode), then the loop bookkeeping in one small launch
+    def select_token(self, logits: torch.Tensor, cache: KVCache, plan: SelectionPlan, out: Optional[torch.Tensor] = None,
+                     advance: bool = False, raw: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """next token of every row from fp32 logits (B, V) under ``plan`` (armed: SelectionPlan.arm): greedy argmax (mode None;
+        reference sampling.py:96-97) or the sampled branch (mode = (temperature, top_k, top_p); :99-107 -- or ("warp",
+        temperature, top_k, top_p, min_p): transformers' sampler, sample_mode), then the loop bookkeeping in one small launch
         (all-eos step, step counter, token history, and -- inside a decode step -- the KV write position).  Enqueue-only:
         used inside the captured token step and, eagerly, on the prefill logits.  A beam mode (beam_mode) runs the beam step
         instead: the selected token of every row lands in cache.beam's token buffer (the decode state's st.token).
-        ``proc`` (proc_mode; the ids already in cache.suppress, _arm_processors): the logits processors, one launch IN PLACE on
-        ``logits`` immediately before the selection -- on the raw logits, or as log_softmax + rules in front of the beam step.
-        ``stop`` (stop_mode; the table already in cache.stop_table, _arm_stop): the bookkeeping launch is the per-row one
+        ``plan.proc`` (the ids already in cache.suppress): the logits processors, one launch IN PLACE on ``logits`` immediately
+        before the selection -- on the raw logits, or as log_softmax + rules in front of the beam step.
+        ``plan.stop`` (the table already in cache.stop_table): the bookkeeping launch is the per-row one
         (ops.sample_finish_rows) -- a finished row's token becomes the pad id in place --, and min_new_tokens bans every eos id.
-        ``logprobs`` (logprob_mode; the buffers already allocated, _arm_logprobs): one launch AFTER the selection and BEFORE the
-        bookkeeping -- which advances the step the launch reads its column from and overwrites a finished row's token -- writes the
-        token's log-probability and the n_top alternatives of ``raw`` (default ``logits``): the rows as they were before ``proc``.
-        ``cons`` (constraint_mode; table and roots already in the cache's buffers, _arm_constraint): the processors' launch is the
-        constrained one (ops.logits_process_constrained) -- ``proc``'s rules, or neutral values, then the trie constraint with
-        every eos id --: with ``proc`` as many launches as without ``cons``, without ``proc`` one more.
-        ``guidance`` (guidance_mode): ``logits`` / ``raw`` / ``out`` hold 2R rows.  First ops.logits_guidance in place on rows
-        [0, R) against rows [R, 2R); then all of the above over the first R rows of everything; last ops.guidance_follow mirrors
-        the tokens into ``out[R:]`` and advances the positions of rows [R, 2R).  Two launches more.  Returns the R tokens."""
+        ``plan.n_top`` (the buffers already allocated): one launch AFTER the selection and BEFORE the bookkeeping -- which
+        advances the step the launch reads its column from and overwrites a finished row's token -- writes the token's
+        log-probability and the n_top alternatives of ``raw`` (default ``logits``): the rows as they were before the processors.
+        ``plan.cons`` (table and roots already in the cache's buffers): the processors' launch is the constrained one
+        (ops.logits_process_constrained) -- the processors' rules, or neutral values, then the trie constraint with every eos
+        id --: with processors as many launches as without a constraint, without them one more.
+        ``plan.guidance``: ``logits`` / ``raw`` / ``out`` hold 2R rows.  First ops.logits_guidance in place on rows [0, R) against
+        rows [R, 2R); then all of the above over the first R rows of everything; last ops.guidance_follow mirrors the tokens
+        into ``out[R:]`` and advances the positions of rows [R, 2R).  Two launches more.  Returns the R tokens."""
+        mode, proc, stop, n_top, cons, guidance = plan[:6]
         half = None
         if guidance is not None:
-            R = self._guided_rows(cache, guidance)
-            assert out is not None and logits.shape[0] == 2 * R and not (isinstance(mode, tuple) and mode[:1] == ("beam",))
+            R = plan.rows(cache)
+            assert out is not None and logits.shape[0] == 2 * R and not plan.is_beam
             ops.logits_guidance(logits[:R], logits[R:], guidance[0], guidance[1])
             half, logits, raw, out = out, logits[:R], None if raw is None else raw[:R], out[:R]
         rows = (lambda t: t) if guidance is None else (lambda t: None if t is None else t[:R])   # the per-row buffers' share
-        is_beam = isinstance(mode, tuple) and bool(mode) and mode[0] == "beam"
-        if proc is not None or cons is not None:
-            more = {} if stop is None or len(stop[0]) < 2 else dict(eos_more=cache.stop_table[1:ops.STOP_MAX_EOS],
-                                                                    n_eos_more=len(stop[0]) - 1)
+        more = {} if stop is None or len(stop[0]) < 2 else dict(eos_more=cache.stop_table[1:ops.STOP_MAX_EOS], n_eos_more=len(stop[0]) - 1)
         if cons is not None:
             rules = proc if proc is not None else (1.0, 0, 0, ())
             ops.logits_process_constrained(logits, cache.sample_state, rows(cache.history), cache.trie_table, cache.trie_roots,
@@ -1279,35 +1303,33 @@ class LMEngine:
         elif proc is not None:
             ops.logits_process(logits, cache.sample_state, rows(cache.history), repetition_penalty=proc[0], no_repeat_ngram_size=proc[1],
                                min_new_tokens=proc[2], eos=cache.eos, suppress=cache.suppress, n_suppress=len(proc[3]),
-                               normalize=is_beam, **more)
-        if is_beam:
-            return self._select_beam(logits, cache, mode, advance, normalized=proc is not None)
+                               normalize=plan.is_beam, **more)
+        if plan.is_beam:
+            return self._select_beam(logits, cache, plan, advance)
         if mode is None:
             tok = ops.argmax(logits, out=out)
         elif mode[0] == "warp":
             tok = ops.sample_warp(logits, mode[1], mode[2], mode[3], mode[4], cache.seed, cache.sample_state, out=out)
         else:
             tok = ops.sample(logits, mode[0], mode[1], mode[2], cache.seed, cache.sample_state, out=out)
-        if logprobs is not None:
-            ops.token_logprobs(logits if raw is None else raw, tok, rows(cache.lp), rows(cache.top_id) if logprobs else None,
-                               rows(cache.top_lp) if logprobs else None, state=cache.sample_state)
+        if n_top is not None:
+            ops.token_logprobs(logits if raw is None else raw, tok, rows(cache.lp), rows(cache.top_id) if n_top else None,
+                               rows(cache.top_lp) if n_top else None, state=cache.sample_state)
         if stop is not None:
             ops.sample_finish_rows(tok, cache.sample_state, cache.stop_table, len(stop[0]), len(stop[1]), stop[0][0],
                                    rows(cache.finish), d_pos=cache.d_pos if advance else None, history=rows(cache.history),
-                                   clear=clear, clear_stride=16 if clear is not None else 1, pos_stride=cache.pos_stride)
+                                   pos_stride=cache.pos_stride)
         else:
             ops.sample_finish(tok, cache.eos, cache.sample_state, d_pos=cache.d_pos if advance else None,
-                              history=rows(cache.history), clear=clear, clear_stride=16 if clear is not None else 1,
-                              pos_stride=cache.pos_stride)
+                              history=rows(cache.history), pos_stride=cache.pos_stride)
         if half is not None:        # after the bookkeeping: a finished row's pad id is mirrored too
             ops.guidance_follow(half, cache.d_pos if advance else None, R, pos_stride=cache.pos_stride)
         return tok
 
-    def _decode_step(self, cache: KVCache, st, mode=None, feed_back: bool = False, proc=None, stop=None, logprobs=None, cons=None,
-                     guidance=None):
+    def _decode_step(self, cache: KVCache, st, plan: SelectionPlan, feed_back: bool = False):
         """Enqueue one token step for all B sequences (graph-capturable: no
         allocation, no sync, position read from cache.d_pos on the device): embedding, per layer the launch sequence of the
-        kind planned for it (st.kinds, _ensure_decode_state), the head, token selection.
+        kind planned for it (st.kinds, _ensure_decode_state), the head, token selection under ``plan``.
         ``feed_back``: the input ids are the tokens the previous step selected (st.token, still on the device) -- the
         reference's loop feeds exactly those back (sampling.py:88-90) -- instead of ids copied in from the caller."""
         B = cache.B
@@ -1322,17 +1344,16 @@ class LMEngine:
         else:
             head = self.head_w8 if st.w8 else self.head_w4 if st.w4 else self.head_dec
             ops.gemm_skinny(x, head, out=st.logits, ln_fold=(head.colsum, self.d, self.eps))
-        if mode == "noselect":
+        if not plan.select:
             ops.advance_pos(cache.d_pos, pos_stride=cache.pos_stride)   # teacher-forced position: nothing selected, nothing recorded
-        elif logprobs is not None and (proc is not None or cons is not None or guidance is not None):
+        elif plan.second_buffer:
             # the processors run in place: they and the selection get a copy (one device copy inside the step), the
             # log-probabilities read the untouched st.logits
             st.logits_proc.copy_(st.logits)
-            self.select_token(st.logits_proc[:, : self.V], cache, mode, out=st.token, advance=True, proc=proc, stop=stop,
-                              logprobs=logprobs, raw=st.logits[:, : self.V], cons=cons, guidance=guidance)
+            self.select_token(st.logits_proc[:, : self.V], cache, plan, out=st.token, advance=True, raw=st.logits[:, : self.V])
         else:
-            self.select_token(st.logits[:, : self.V], cache, mode, out=st.token, advance=True, proc=proc, stop=stop,
-                              logprobs=logprobs, cons=cons, guidance=guidance)
+            self.select_token(st.logits[:, : self.V], cache, plan, out=st.token, advance=True)
+
 
     # One method per block kind (_block_kind): x -> xn for layer li.  ``src`` holds the block's weight-streaming operands: the
     # layer itself, or its e4m3 / MXFP4 copies (ly.w8 / ly.w4) under W8A16 / W4A16 -- the same launches.  On a ragged cache (pos_stride 1) every
@@ -1461,13 +1482,14 @@ class LMEngine:
         return st
 
     def decode(self, input_ids: Optional[torch.Tensor], cache: KVCache, use_graph: bool = True, sampling=None, select: bool = True,
-               beam=None, processors=None, stop=None, logprobs=None, constraint=None, guidance=None):
+               beam=None, processors=None, stop=None, logprobs=None, constraint=None, guidance=None, plan=None):
         """One cached step.  Returns (fp32 logits (B,V) view, selected token (B,) view: greedy, or sampled when
         ``sampling = (temperature, top_k, top_p)`` or ``("warp", temperature, top_k, top_p, min_p)``, sample_mode); both are
         overwritten by the next step.  ``input_ids=None`` feeds the
         previously selected tokens back without leaving the device.  ``select=False`` (teacher-forced positions of a
         multi-token call): no token is selected -- the history, the RNG step counter and the all-eos latch are left alone,
         only the KV write position advances; the returned token view is stale.
+        ``plan`` (forward): the SelectionPlan of the loop, INSTEAD of the selection keywords; a replayed step then checks nothing.
         ``processors`` (forward): the logits processors run in place on the step's logits before the selection, so the
         returned logits are then the PROCESSED ones (beam search: the processed log_softmax scores).
         ``stop`` (forward): per-row stopping -- the cache must have been armed with it (its finish record reset) by the prefill /
@@ -1477,6 +1499,9 @@ class LMEngine:
         ``constraint`` (forward): the trie constraint in the processors' launch; it counts as one of them in all of the above.
         ``guidance`` (forward): the cache's 2R rows are R pairs; the returned token view holds the R selected tokens twice, the
         returned logits hold the guided rows [0, R) in place of the conditional ones."""
+        if plan is None:
+            plan = self.selection_plan(sampling=sampling, beam=beam, processors=processors, stop=stop, logprobs=logprobs,
+                                       constraint=constraint, guidance=guidance, vocab=self.V)
         if cache.pos >= cache.Smax:
             raise ValueError(f"KV cache full (Smax={cache.Smax}); pass a larger cache_hint / max_steps")
         if cache.B > 16:
@@ -1494,62 +1519,27 @@ class LMEngine:
         feed_back = input_ids is None
         if not feed_back:
             st.ids.copy_(input_ids.reshape(cache.B, 1))
-        mode = self.sample_mode(sampling)
-        if beam is not None:
-            mode = self.beam_mode(beam)
-            if cache.beam is None or cache.beam.k != mode[1]:
-                raise ValueError("beam decoding needs a cache armed for this num_beams (prefill with eos_token= and beam=)")
         if not select:
             if feed_back:
                 raise ValueError("decode(select=False) needs input_ids: there is no selected token to feed back")
-            mode = "noselect"
-        proc = self.proc_mode(processors) if select else None
-        self._arm_processors(cache, proc)
-        stop = self.stop_mode(stop) if select else None
-        if stop is not None:
-            if beam is not None:
-                raise NotImplementedError("per-row stopping is not combined with beam search")
-            if cache.finish is None:
-                raise ValueError("per-row stopping needs a cache armed for it (prefill with eos_token= and stop=)")
-            self._arm_stop(cache, stop)
-        n_top = self.logprob_mode(logprobs) if select else None
-        if n_top is not None and beam is not None:
-            raise NotImplementedError("token log-probabilities are not combined with beam search")
-        cons = self.constraint_mode(constraint) if select else None
-        if cons is not None and beam is not None:
-            raise NotImplementedError("a constraint is not combined with beam search")
-        gd = self.guidance_mode(guidance) if select else None
-        if gd is not None and beam is not None:
-            raise NotImplementedError("guidance is not combined with beam search")
-        self._arm_constraint(cache, cons, self._guided_rows(cache, gd))
-        self._arm_logprobs(cache, st, n_top, proc if proc is not None else cons if cons is not None else gd)
-        key = (mode, feed_back)
-        if proc is not None:        # the values are launch arguments of the captured step (the suppress ids are not: their count is)
-            key += (tuple(proc[:3]) + (len(proc[3]),),)
-        if stop is not None:        # the counts and the pad id are launch arguments, the table's contents are not
-            key += (("stop", len(stop[0]), len(stop[1]), stop[0][0]),)
-        if n_top is not None:       # n_top and the buffers' addresses are launch arguments
-            key += (("logprobs", n_top),)
-        if cons is not None:        # the buffers' addresses and the table's capacity are launch arguments, their contents are not
-            key += (("constraint",),)
-        if gd is not None:          # scale and cut are launch arguments
-            key += (("guidance",) + tuple(gd),)
+            plan = plan.without_selection()
+        plan.arm(cache, st)
+        key = plan.graph_key(feed_back)
         if not use_graph:
-            self._decode_step(cache, st, mode, feed_back, proc, stop, n_top, cons, gd)
+            self._decode_step(cache, st, plan, feed_back)
         elif key in st.graphs:
             st.graphs[key].replay()
         elif st.steps == 0:
-            self._decode_step(cache, st, mode, feed_back, proc, stop, n_top, cons, gd)    # first step eager (loads code objects)
+            self._decode_step(cache, st, plan, feed_back)    # first step eager (loads code objects)
         else:
             g = torch.cuda.CUDAGraph()            # hipGraph on ROCm
             with torch.cuda.graph(g):
-                self._decode_step(cache, st, mode, feed_back, proc, stop, n_top, cons, gd)
+                self._decode_step(cache, st, plan, feed_back)
             st.graphs[key] = g
             g.replay()
         st.steps += 1
         cache.pos += 1
-        second = n_top is not None and (proc is not None or cons is not None or gd is not None)
-        return (st.logits_proc if second else st.logits)[:, : self.V], st.token
+        return (st.logits_proc if plan.second_buffer else st.logits)[:, : self.V], st.token
 
     # ------------------------------------------------- loss (eval) forward
     def forward_loss(self, embeds: torch.Tensor, labels: torch.Tensor, want_hidden=False, want_logits=False) -> LMOutput:
@@ -1597,7 +1587,7 @@ class LMEngine:
         b predicts, -100 for none; _target_logits), then the kernel of the generate() loop without a step counter.  Returns device
         tensors in (b, s) order of the targets: (log-probabilities [n], top ids [n, n_top] int32, their log-probabilities
         [n, n_top])."""
-        n_top = self.logprob_mode(n_top)
+        n_top = self.logprob_mode(n_top, self.V)
         B, S, _ = embeds.shape
         x, _ = self._blocks_prefill(embeds, None)
         head = self._target_logits(x, S, tgt.to(self.device))

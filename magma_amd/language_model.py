@@ -243,19 +243,19 @@ class GPTJForCausalLM(nn.Module):
                 output_hidden_states: bool = False, cache_hint: Optional[int] = None, reuse_cache: bool = False,
                 return_logits: bool = False, sampling=None, eos_token: Optional[int] = None,
                 seed: Optional[int] = None, feed_back: bool = False, lengths=None, beam=None, processors=None,
-                stop=None, logprobs=None, constraint=None, guidance=None, **unused) -> LMOutput:
+                stop=None, logprobs=None, constraint=None, guidance=None, plan=None, **unused) -> LMOutput:
         """``lengths``: prompt lengths of a right-padded batch; ``beam``: beam-search token selection; ``processors``: the logits
         processors in front of the selection; ``stop``: per-row stopping in the bookkeeping launch behind it; ``logprobs``: the
         selected token's log-probability and the most probable alternatives, written between the two; ``constraint``: the trie
         constraint in the processors' launch; ``guidance``: classifier-free guidance of rows [0, R) against rows [R, 2R)
-        (LMEngine.forward)."""
+        (LMEngine.forward); ``plan``: LMEngine.selection_plan's checked form of those seven keywords, passed instead of them."""
         return self.engine.forward(input_ids=input_ids, inputs_embeds=inputs_embeds, labels=labels,
                                    use_cache=use_cache, past_key_values=past_key_values,
                                    output_hidden_states=output_hidden_states, cache_hint=cache_hint,
                                    reuse_cache=reuse_cache, return_logits=return_logits, sampling=sampling,
                                    eos_token=eos_token, seed=seed, feed_back=feed_back, lengths=lengths, beam=beam,
                                    processors=processors, stop=stop, logprobs=logprobs, constraint=constraint,
-                                   guidance=guidance)
+                                   guidance=guidance, plan=plan)
 
 
 def get_gptj(gradient_checkpointing: bool = False, from_pretrained: bool = False, device=None,

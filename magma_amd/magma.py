@@ -361,17 +361,14 @@ class Magma(nn.Module):
         ``top_logprobs`` most probable tokens at every position, ``count[b]`` = the row's number of targets; positions past it
         hold 0.0 / -1 / -inf.  Scoring against a KV cache is not supported."""
         from . import ops
-        from .engine import LMEngine
-        from .sampling import check_logprob_args, is_embed_batch, mask_logprobs, pad_ragged
+        from .sampling import check_logprob_args, mask_logprobs, prompt_batch
         torch.cuda.set_device(self.device)
         eng = self.lm.engine
         n_top = check_logprob_args(True, top_logprobs, eng.V)
-        if is_embed_batch(embeddings):
-            embeddings, lengths = embeddings
-        if isinstance(embeddings, (list, tuple)):
-            embeddings, lengths = pad_ragged(embeddings)
+        embeddings, lens = prompt_batch(embeddings, lengths)
         B, S, d = embeddings.shape
-        lens = LMEngine.check_lengths(lengths, B, S) if lengths is not None else torch.full((B,), S, dtype=torch.int64)
+        if lens is None:
+            lens = torch.full((B,), S, dtype=torch.int64)
         if torch.is_tensor(targets):
             t = targets.detach().to("cpu")
             if t.ndim != 2 or t.shape[0] != B or t.is_floating_point() or t.dtype == torch.bool:
@@ -416,16 +413,11 @@ class Magma(nn.Module):
         """A KV cache holding only the prompts ``embeddings`` ((B, S, d) with optional ``lengths``, a list of per-sample tensors,
         or embed_batch's (embeddings, lengths)), for ``generate(question, past_key_values=cache)``.  Shared prefix: cache one
         image and instruction once, then ``cache.expand(n)`` and ask n questions.  The cache belongs to the caller."""
-        from .sampling import pad_ragged
-        from .engine import LMEngine
+        from .sampling import prompt_batch
         torch.cuda.set_device(self.device)
-        from .sampling import is_embed_batch
-        if is_embed_batch(embeddings):
-            embeddings, lengths = embeddings
-        if isinstance(embeddings, (list, tuple)):
-            embeddings, lengths = pad_ragged(embeddings)
-        B, S, _ = embeddings.shape
-        lens = LMEngine.check_lengths(lengths, B, S) if lengths is not None else torch.full((B,), S, dtype=torch.int64)
+        embeddings, lens = prompt_batch(embeddings, lengths)
+        if lens is None:
+            lens = torch.full((embeddings.shape[0],), embeddings.shape[1], dtype=torch.int64)
         _, cache, _ = self.lm.engine.prefill(embeddings, cache_hint, lengths=lens)
         cache.set_rows(lens)
         return cache

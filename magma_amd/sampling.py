@@ -11,7 +11,7 @@ below are the host statements of the same rules (pinned to the reference's own
 functions, tests/test_oracle_pins.py) and serve LM objects other than the engine."""
 import math
 import os
-from typing import Callable, List, NamedTuple, Tuple, Union
+from typing import Callable, List, NamedTuple, Optional, Tuple, Union
 
 import torch
 import torch.nn.functional as F
@@ -161,6 +161,28 @@ def is_embed_batch(x) -> bool:
         return False
     lens = torch.as_tensor(x[1]) if not torch.is_tensor(x[1]) else x[1]
     return lens.ndim == 1 and not lens.is_floating_point() and not lens.is_complex() and lens.dtype != torch.bool
+
+
+def prompt_batch(embeddings, lengths=None, *, check: bool = True, name: str = "lengths", per_row: bool = True):
+    """The prompt forms every entry point takes -- a (B, S, d) tensor with optional ``lengths``, a list of per-sample tensors,
+    embed_batch's (embeddings, lengths) -- as (right-padded (B, S, d) tensor, lengths or None).  A list is padded and gives its
+    own lengths; ``lengths`` passed beside it must agree.  ``check``: the lengths come back as LMEngine.check_lengths' host
+    int64 [B] tensor (1 <= len_b <= S) -- refused when the LM keeps no KV position ``per_row`` (only the HIP engine does).
+    ``name``: what the error calls the lengths."""
+    if is_embed_batch(embeddings):
+        embeddings, lengths = embeddings
+    if isinstance(embeddings, (list, tuple)):
+        embeddings, derived = pad_ragged(embeddings)
+        if lengths is not None and not torch.equal(torch.as_tensor(lengths).cpu().to(torch.int64).view(-1), derived):
+            raise ValueError(f"{name} {list(lengths)} do not match the per-sample embeddings ({derived.tolist()})")
+        lengths = derived
+    if check and lengths is not None:
+        if not per_row:
+            raise ValueError("generate(lengths=...) needs the HIP engine's LM (per-row KV positions): this LM object has no "
+                             "device token selection and would attend over the padding")
+        from .engine import LMEngine
+        lengths = LMEngine.check_lengths(lengths, embeddings.shape[0], embeddings.shape[1])
+    return embeddings, lengths
 
 
 MAX_NGRAM, MAX_SUPPRESS = 16, 1024
@@ -558,15 +580,9 @@ def check_guidance_args(guidance_scale=1.0, negative_embeddings=None, negative_l
     if negative_embeddings is None:
         raise ValueError(f"guidance_scale = {scale} needs negative_embeddings (the negative / unconditional prompt)")
     neg, lens = negative_embeddings, negative_lengths
-    if is_embed_batch(neg):
-        if lens is not None:
-            raise ValueError("negative_embeddings already carries its lengths")
-        neg, lens = neg
-    elif isinstance(neg, (list, tuple)):
-        neg, derived = pad_ragged(neg)
-        if lens is not None and not torch.equal(torch.as_tensor(lens).cpu().to(torch.int64).view(-1), derived):
-            raise ValueError(f"negative_lengths {list(lens)} do not match the per-sample embeddings ({derived.tolist()})")
-        lens = derived
+    if is_embed_batch(neg) and lens is not None:
+        raise ValueError("negative_embeddings already carries its lengths")
+    neg, lens = prompt_batch(neg, lens, check=False, name="negative_lengths")       # (its own range check follows)
     if not torch.is_tensor(neg) or neg.ndim != 3 or neg.shape[1] < 1:
         raise ValueError("negative_embeddings must be a (B, S', d) or (1, S', d) tensor, a list of per-row tensors or "
                          "embed_batch's (embeddings, lengths)")
@@ -1063,44 +1079,28 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     if continuing and (num_beams > 1 or return_scores):
         raise NotImplementedError("beam search neither continues from nor returns a KV cache (past_key_values / "
                                   "return_past_key_values need num_beams=1 and return_scores=False)")
-    if is_embed_batch(embeddings):
-        embeddings, lengths = embeddings                      # embed_batch's (embeddings, lengths)
+    embeddings, lengths = prompt_batch(embeddings, lengths, check=False)
+    # the HIP engine selects the token itself; any other LM object gets the reference's call (sampling.py:81-93)
+    on_device = getattr(model.lm, "device_token_selection", False)
     if num_beams > 1 or return_scores:
         return _generate_beam(model, embeddings, max_steps, eos_token, decode, eos_check_every, lengths, num_beams,
                               float(length_penalty), early_stopping, num_return_sequences, return_scores, proc)
     was_training = model.training
-    if isinstance(embeddings, (list, tuple)):
-        embeddings, derived = pad_ragged(embeddings)
-        if lengths is not None and not torch.equal(torch.as_tensor(lengths).cpu().to(torch.int64).view(-1), derived):
-            raise ValueError(f"lengths {list(lengths)} do not match the per-sample embeddings ({derived.tolist()})")
-        lengths = derived
     b, s, _ = embeddings.shape
-    dev = embeddings.device
     if guide is not None:       # the negative prompt as (b, s', d) rows, row counts and hidden size checked
         guide = check_guidance_args(guidance_scale, negative_embeddings, negative_lengths, guidance_min_p, b, embeddings.shape[2])
     cons = check_constraint_args(constraint, b, getattr(getattr(model, "tokenizer", None), "encode", None), _logit_count(model),
                                  eos_ids, proc)
-    # the HIP engine selects the token itself; any other LM object gets the reference's call (sampling.py:81-93)
-    on_device = getattr(model.lm, "device_token_selection", False)
     if continuing and not on_device:
         raise ValueError("past_key_values / return_past_key_values need the HIP engine's LM")
     if continuing and max_steps < 1:
         raise ValueError("continuing a conversation needs max_steps >= 1")
     if past_key_values is not None and past_key_values.B != b:
         raise ValueError(f"the cache holds {past_key_values.B} rows, the new inputs {b}")
-    if lengths is not None:
-        if not on_device:
-            raise ValueError("generate(lengths=...) needs the HIP engine's LM (per-row KV positions): this LM object has no "
-                             "device token selection and would attend over the padding")
-        from .engine import LMEngine
-        lengths = LMEngine.check_lengths(lengths, b, s)
+    lengths = prompt_batch(embeddings, lengths, per_row=on_device)[1]       # (the batch is normalised: this checks the lengths)
     if guide is not None and guide["lengths"] is not None and not on_device:
         raise ValueError("negative prompts of different lengths need the HIP engine's LM (per-row KV positions)")
     model.eval()
-    out = torch.full((b, s + max_steps), eos_token, dtype=torch.long, device=dev)
-    out[:, :s] = model.image_token
-    n = s
-    past = None
     greedy = temperature == 0.0
     mode = None if greedy else (float(temperature), int(top_k), float(top_p))
     if warp is not None and not greedy:
@@ -1108,138 +1108,21 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     if seed is None and not greedy:
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     every = eos_check_every or int(os.environ.get("MAGMA_EOS_CHECK_EVERY", "8"))
-    first_kw = dict(sampling=mode, eos_token=eos_token, seed=seed) if on_device else {}
-    if lengths is not None:
-        first_kw["lengths"] = lengths
-    step_kw = dict(sampling=mode) if on_device else {}
-    prompts = embeddings
-    if on_device and guide is not None:     # ONE ragged batch of 2b rows: the prompts, then the negative prompts
-        from .engine import LMEngine
-        neg = guide["embeddings"].to(device=dev, dtype=embeddings.dtype)
-        s_neg = neg.shape[1]
-        prompts = torch.zeros(2 * b, max(s, s_neg), embeddings.shape[2], dtype=embeddings.dtype, device=dev)
-        prompts[:b, :s], prompts[b:, :s_neg] = embeddings, neg
-        first_kw["lengths"] = torch.cat([lengths if lengths is not None else torch.full((b,), s, dtype=torch.int64),
-                                         guide["lengths"] if guide["lengths"] is not None
-                                         else torch.full((b,), s_neg, dtype=torch.int64)])
-        first_kw["guidance"] = step_kw["guidance"] = LMEngine.guidance_mode((guide["scale"], guide["min_p"]))
-    if on_device and proc is not None:      # only then: an LM object written before the processors keeps its signature
-        from .engine import LMEngine
-        first_kw["processors"] = step_kw["processors"] = LMEngine.proc_mode(proc)      # checked once, not once per token
-    if on_device and cons is not None:      # only then, as above
-        from .engine import LMEngine
-        first_kw["constraint"] = step_kw["constraint"] = LMEngine.constraint_mode(cons)      # one table for the whole call
-    if on_device and stop is not None:      # only then, as above
-        from .engine import LMEngine
-        first_kw["stop"] = step_kw["stop"] = LMEngine.stop_mode(stop)
-    if on_device and n_top is not None:     # only then, as above
-        first_kw["logprobs"] = step_kw["logprobs"] = n_top
-    host_lp = [] if n_top is not None and not on_device else None      # per step (lp, top ids, top lp) of the host statement
-    if not on_device and stop is not None:
-        done, record = torch.zeros(b, dtype=torch.bool), torch.tensor([[-1, 0]] * b, dtype=torch.int64).view(b, 2)
-    if past_key_values is not None:
-        start = past_key_values.rows_pos() + (past_key_values.pending >= 0).to(torch.int64) \
-            if past_key_values.pending is not None else past_key_values.rows_pos()
-        ext_kw = dict(first_kw, lengths=lengths if lengths is not None else torch.full((b,), s, dtype=torch.int64))
-    for i in range(max_steps):
-        if i == 0 and past_key_values is not None:      # the new rows appended to the caller's cache (LMEngine.extend)
-            outputs = model.lm(inputs_embeds=embeddings, use_cache=True, past_key_values=past_key_values, cache_hint=max_steps,
-                               **ext_kw)
-        elif i == 0:
-            outputs = model.lm(inputs_embeds=prompts, use_cache=True, past_key_values=None, cache_hint=max_steps,
-                               reuse_cache=True, **first_kw)
-        elif on_device:      # the token selected by the previous step is fed back on the device: nothing crosses the host
-            outputs = model.lm(input_ids=None, use_cache=True, past_key_values=past, feed_back=True, **step_kw)
-        else:
-            outputs = model.lm(input_ids=out[:, n - 1:n], use_cache=True, past_key_values=past, **step_kw)
-        past = outputs.past_key_values
-        if on_device:
-            n += 1
-            if stop_on_eos and eos_token is not None and ((i + 1) % every == 0 or i + 1 == max_steps):
-                first = int(outputs.eos_state[1])            # one host sync per `every` steps
-                if first >= 0:
-                    n = s + first + 1                        # tokens after the first all-eos step are dropped again
-                    break
-            continue
-        logits = outputs.logits[:, -1, :].float()            # any other LM object: the reference's host-side arithmetic
-        raw = logits
-        if guide is not None:       # the negative stream: a second model call with its own past, then the host statement
-            if i == 0:
-                neg_out = model.lm(inputs_embeds=guide["embeddings"].to(dev), use_cache=True, past_key_values=None,
-                                   cache_hint=max_steps)
-            else:
-                neg_out = model.lm(input_ids=out[:, n - 1:n], use_cache=True, past_key_values=neg_past)
-            neg_past = neg_out.past_key_values
-            logits = guide_logits(logits, neg_out.logits[:, -1, :].float(), guide["scale"], guide["min_p"]) \
-                .to(torch.float32).to(logits.device)
-        if proc is not None:
-            logits = process_logits(logits.cpu(), out[:, s:n].cpu(), n - s, eos_token=eos_ids if stop is not None else eos_token,
-                                    **proc).to(logits.device)
-        if cons is not None:
-            logits = constrain_logits(logits.cpu(), out[:, s:n].cpu(), n - s, cons, eos_ids).to(logits.device)
-        if greedy:
-            next_token = outputs.next_token.unsqueeze(1) if outputs.get("next_token") is not None and proc is None \
-                and cons is None and guide is None else \
-                torch.argmax(logits, dim=-1, keepdim=True)
-        else:
-            if warp is not None:
-                logits = warp_filter(logits.cpu(), temperature, top_k, top_p, warp["min_p"]).to(logits.device)
-            if warp is None and top_k > 0:
-                logits = top_k_filter(logits, k=top_k)
-            if warp is None and top_p > 0:
-                logits = top_p_filter(logits, threshold=top_p)
-            probs = F.softmax(logits / temperature, dim=-1)
-            next_token = torch.multinomial(probs, num_samples=1)
-        if host_lp is not None:     # of the raw distribution, for the token as selected (a finished row's is masked at the end)
-            host_lp.append(token_logprobs(raw, next_token.view(-1), n_top))
-        if stop is not None:        # the per-row rule (stop_update): finished rows are padded, the others tested
-            next_token = torch.where(done.to(next_token.device)[:, None], torch.full_like(next_token, eos_token), next_token)
-            out[:, n:n + 1] = next_token
-            n += 1
-            was = done
-            done, why = stop_update(out[:, s:n], n - s - 1, done, eos_ids, stop["stop_seqs"])
-            now = done & ~was
-            record[now, 0], record[now, 1] = n - s - 1, why[now, 0] * 256 + why[now, 1]
-            if stop_on_eos and bool(done.all()):
-                break
-            continue
-        out[:, n:n + 1] = next_token
-        n += 1
-        if stop_on_eos and eos_token is not None and bool((next_token == eos_token).all()):
-            break
-    if on_device and lengths is not None:     # ragged: row b's tokens follow its own prompt, eos after them
-        n_gen = n - s                         # (no host sync: the next call's launches queue behind this one)
-        lens = lengths.to(dev, non_blocking=True)[:, None]
-        out.fill_(eos_token)
-        out.masked_fill_(torch.arange(s + max_steps, device=dev)[None, :] < lens, model.image_token)
-        out.scatter_(1, lens + torch.arange(n_gen, device=dev)[None, :], past.history[:b, :n_gen])
-    elif on_device:          # one copy of the token history the bookkeeping kernel kept
-        out[:, s:n] = past.history[:b, : n - s]
-    # (``[:b]``: a guided cache holds 2b rows and keeps the per-row records of the b guided ones in its first b rows)
-    gen_tokens = past.history[:b, : n - s] if on_device and past is not None else out[:, s:n]      # the generated columns
-    out = out[:, :n]
-    finish = None
-    if stop is not None and (return_finish or continuing or decode or (n_top is not None and n > s)):
-        record = past.finish[:b].cpu() if on_device else record       # one host copy
-        finish = finish_from_record(record, n - s)
-    elif return_finish:                                               # the reference's rule: every row ran the whole call
-        finish = finish_from_record(torch.tensor([[-1, 0]] * b).view(b, 2), n - s)
+    modes = dict(mode=mode, proc=proc, stop=stop, n_top=n_top, cons=cons, guide=guide, eos_ids=eos_ids)
+    want_finish = stop is not None and (return_finish or continuing or decode)      # the tail reads the per-row finish record
+    run = (_device_loop if on_device else _host_loop)(
+        model, embeddings, lengths, max_steps, eos_token, seed, every, stop_on_eos, modes, want_finish, past_key_values)
+    out, n_gen, past = run.out, run.out.shape[1] - s, run.past
+    record = run.record
+    if record is None and return_finish:                              # the reference's rule: every row ran the whole call
+        record = torch.tensor([[-1, 0]] * b).view(b, 2)
+    finish = None if record is None else finish_from_record(record, n_gen)
     logprobs = None
-    if n_top is not None:       # one copy of what the steps wrote (or the host statement's values), masked past every row's count
-        n_gen = n - s
-        if n_gen == 0:
-            vals = (torch.zeros(b, 0), torch.zeros(b, 0, n_top, dtype=torch.int64), torch.zeros(b, 0, n_top))
-        elif on_device:
-            vals = (past.lp[:b, :n_gen], past.top_id[:b, :n_gen], past.top_lp[:b, :n_gen])
-        else:
-            vals = tuple(torch.stack([h[j] for h in host_lp[:n_gen]], 1) for j in range(3))
-        logprobs = mask_logprobs(gen_tokens, *vals, finish.kept if finish is not None else torch.full((b,), n_gen))
+    if n_top is not None:       # what the steps wrote (or the host statement's values), masked past every row's count
+        vals = run.logprobs if n_gen else (torch.zeros(b, 0), torch.zeros(b, 0, n_top, dtype=torch.int64), torch.zeros(b, 0, n_top))
+        logprobs = mask_logprobs(run.tokens, *vals, finish.kept if finish is not None else torch.full((b,), n_gen))
     if continuing:      # the cache keeps the conversation (a continued one too: it was advanced in place and stays continuable)
-        if past_key_values is None:
-            start = lengths if lengths is not None else torch.full((b,), s, dtype=torch.int64)
-        else:
-            start = start + (lengths if lengths is not None else s)
-        keep_conversation(past, start, n - s, eos_token, finish if stop is not None else None)
+        keep_conversation(past, run.start, n_gen, eos_token, finish if stop is not None else None)
         model.lm.engine.detach_cache(past)
     if decode and stop is not None:      # every row up to its own kept count; the eos that finished it is dropped as below
         first = lengths.tolist() if lengths is not None else [s] * b
@@ -1261,6 +1144,149 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     return ret if len(ret) > 1 else ret[0]
 
 
+class _Generated(NamedTuple):
+    """What a generate() loop hands to the shared tail: ``out`` (b, s + n) ids laid out for the caller, ``tokens`` (b, n) the
+    generated columns, the LM's ``past``, the finish ``record`` (host [b, 2]; None when the tail does not read it), the per-step
+    ``logprobs`` (lp, top ids, top lp; None without a step), ``start`` (engine: the cache position of every row's first new token)."""
+    out: torch.Tensor
+    tokens: torch.Tensor
+    past: object = None
+    record: Optional[torch.Tensor] = None
+    logprobs: Optional[tuple] = None
+    start: Optional[torch.Tensor] = None
+
+
+def _device_loop(model, embeddings, lengths, max_steps, eos_token, seed, every, stop_on_eos, modes, want_finish,
+                 past_key_values) -> _Generated:
+    """generate()'s loop on the HIP engine: one prefill (or the new inputs appended to the caller's cache), then steps that feed
+    the selected token back on the device -- nothing crosses the host but the all-eos step, read every ``every`` steps -- under ONE
+    SelectionPlan built here; the output is laid out from the token history the bookkeeping launch kept."""
+    from .engine import LMEngine
+    b, s, _ = embeddings.shape
+    dev = embeddings.device
+    stop, n_top, guide = modes["stop"], modes["n_top"], modes["guide"]
+    plan = LMEngine.selection_plan(sampling=modes["mode"], processors=modes["proc"], stop=stop, logprobs=n_top,
+                                   constraint=modes["cons"], guidance=None if guide is None else (guide["scale"], guide["min_p"]),
+                                   vocab=model.lm.engine.V)
+    first_kw = dict(eos_token=eos_token, seed=seed, plan=plan, lengths=lengths)
+    own = lengths if lengths is not None else torch.full((b,), s, dtype=torch.int64)     # the positions every row adds
+    prompts, start = embeddings, own
+    if guide is not None:       # ONE ragged batch of 2b rows: the prompts, then the negative prompts
+        neg = guide["embeddings"].to(device=dev, dtype=embeddings.dtype)
+        s_neg = neg.shape[1]
+        prompts = torch.zeros(2 * b, max(s, s_neg), embeddings.shape[2], dtype=embeddings.dtype, device=dev)
+        prompts[:b, :s], prompts[b:, :s_neg] = embeddings, neg
+        first_kw["lengths"] = torch.cat([own, guide["lengths"] if guide["lengths"] is not None
+                                         else torch.full((b,), s_neg, dtype=torch.int64)])
+    if past_key_values is not None:      # the new rows appended to the caller's cache (LMEngine.extend)
+        before = past_key_values.rows_pos() + (past_key_values.pending >= 0).to(torch.int64) \
+            if past_key_values.pending is not None else past_key_values.rows_pos()
+        start, first_kw["lengths"] = before + own, own
+    n_gen, past = 0, None
+    for i in range(max_steps):
+        if i > 0:        # the token selected by the previous step is fed back on the device
+            outputs = model.lm(input_ids=None, use_cache=True, past_key_values=past, feed_back=True, plan=plan)
+        elif past_key_values is not None:
+            outputs = model.lm(inputs_embeds=embeddings, use_cache=True, past_key_values=past_key_values, cache_hint=max_steps,
+                               **first_kw)
+        else:
+            outputs = model.lm(inputs_embeds=prompts, use_cache=True, past_key_values=None, cache_hint=max_steps,
+                               reuse_cache=True, **first_kw)
+        past = outputs.past_key_values
+        n_gen += 1
+        if stop_on_eos and eos_token is not None and ((i + 1) % every == 0 or i + 1 == max_steps):
+            first = int(outputs.eos_state[1])            # one host sync per `every` steps
+            if first >= 0:
+                n_gen = first + 1                        # tokens after the first all-eos step are dropped again
+                break
+    # (``[:b]``: a guided cache holds 2b rows and keeps the per-row records of the b guided ones in its first b rows)
+    tokens = past.history[:b, :n_gen] if past is not None else torch.zeros(b, 0, dtype=torch.long, device=dev)
+    out = torch.full((b, s + n_gen), eos_token, dtype=torch.long, device=dev)
+    if lengths is not None:     # ragged: row b's tokens follow its own prompt, eos after them
+        lens = lengths.to(dev, non_blocking=True)[:, None]          # (no host sync: the next call's launches queue behind this one)
+        out.masked_fill_(torch.arange(s + n_gen, device=dev)[None, :] < lens, model.image_token)
+        out.scatter_(1, lens + torch.arange(n_gen, device=dev)[None, :], tokens)
+    else:                       # one copy of the token history the bookkeeping kernel kept
+        out[:, :s] = model.image_token
+        out[:, s:] = tokens
+    record = past.finish[:b].cpu() if stop is not None and (want_finish or (n_top is not None and n_gen)) else None
+    vals = (past.lp[:b, :n_gen], past.top_id[:b, :n_gen], past.top_lp[:b, :n_gen]) if n_top is not None and n_gen else None
+    return _Generated(out, tokens, past, record, vals, start)
+
+
+def _host_loop(model, embeddings, lengths, max_steps, eos_token, seed, every, stop_on_eos, modes, want_finish,
+               past_key_values) -> _Generated:
+    """generate()'s loop over any other LM object: the reference's call (sampling.py:81-93) and its host-side arithmetic, with
+    the host statement of every mode in the engine's order -- guide_logits, process_logits, constrain_logits, the selection
+    (warp_filter for transformers' sampler), token_logprobs of the raw row, stop_update.  (``lengths``, ``seed``, ``every`` and a
+    cache belong to the engine's loop; generate() has refused ``lengths`` and a cache here.)"""
+    b, s, _ = embeddings.shape
+    dev = embeddings.device
+    mode, proc, stop, n_top, cons, guide, eos_ids = (modes[k] for k in ("mode", "proc", "stop", "n_top", "cons", "guide", "eos_ids"))
+    warp = mode is not None and mode[0] == "warp"
+    temperature, top_k, top_p = mode[1:4] if warp else mode if mode is not None else (0.0, 0, 0.0)
+    out = torch.full((b, s + max_steps), eos_token, dtype=torch.long, device=dev)
+    out[:, :s] = model.image_token
+    n, past = s, None
+    host_lp = []                # per step (lp, top ids, top lp) of the host statement
+    if stop is not None:
+        done, record = torch.zeros(b, dtype=torch.bool), torch.tensor([[-1, 0]] * b, dtype=torch.int64).view(b, 2)
+    for i in range(max_steps):
+        if i == 0:
+            outputs = model.lm(inputs_embeds=embeddings, use_cache=True, past_key_values=None, cache_hint=max_steps, reuse_cache=True)
+        else:
+            outputs = model.lm(input_ids=out[:, n - 1:n], use_cache=True, past_key_values=past)
+        past = outputs.past_key_values
+        logits = outputs.logits[:, -1, :].float()
+        raw = logits
+        if guide is not None:       # the negative stream: a second model call with its own past, then the host statement
+            if i == 0:
+                neg_out = model.lm(inputs_embeds=guide["embeddings"].to(dev), use_cache=True, past_key_values=None,
+                                   cache_hint=max_steps)
+            else:
+                neg_out = model.lm(input_ids=out[:, n - 1:n], use_cache=True, past_key_values=neg_past)
+            neg_past = neg_out.past_key_values
+            logits = guide_logits(logits, neg_out.logits[:, -1, :].float(), guide["scale"], guide["min_p"]) \
+                .to(torch.float32).to(logits.device)
+        if proc is not None:
+            logits = process_logits(logits.cpu(), out[:, s:n].cpu(), n - s, eos_token=eos_ids if stop is not None else eos_token,
+                                    **proc).to(logits.device)
+        if cons is not None:
+            logits = constrain_logits(logits.cpu(), out[:, s:n].cpu(), n - s, cons, eos_ids).to(logits.device)
+        if mode is None:
+            next_token = outputs.next_token.unsqueeze(1) if outputs.get("next_token") is not None and proc is None \
+                and cons is None and guide is None else \
+                torch.argmax(logits, dim=-1, keepdim=True)
+        else:
+            if warp:
+                logits = warp_filter(logits.cpu(), temperature, top_k, top_p, mode[4]).to(logits.device)
+            if not warp and top_k > 0:
+                logits = top_k_filter(logits, k=top_k)
+            if not warp and top_p > 0:
+                logits = top_p_filter(logits, threshold=top_p)
+            probs = F.softmax(logits / temperature, dim=-1)
+            next_token = torch.multinomial(probs, num_samples=1)
+        if n_top is not None:       # of the raw distribution, for the token as selected (a finished row's is masked at the end)
+            host_lp.append(token_logprobs(raw, next_token.view(-1), n_top))
+        if stop is not None:        # the per-row rule (stop_update): finished rows are padded, the others tested
+            next_token = torch.where(done.to(next_token.device)[:, None], torch.full_like(next_token, eos_token), next_token)
+        out[:, n:n + 1] = next_token
+        n += 1
+        if stop is not None:
+            was = done
+            done, why = stop_update(out[:, s:n], n - s - 1, done, eos_ids, stop["stop_seqs"])
+            now = done & ~was
+            record[now, 0], record[now, 1] = n - s - 1, why[now, 0] * 256 + why[now, 1]
+            if stop_on_eos and bool(done.all()):
+                break
+        elif stop_on_eos and eos_token is not None and bool((next_token == eos_token).all()):
+            break
+    n_gen = n - s
+    vals = tuple(torch.stack([h[j] for h in host_lp[:n_gen]], 1) for j in range(3)) if n_top is not None and n_gen else None
+    keep = stop is not None and (want_finish or (n_top is not None and n_gen))
+    return _Generated(out[:, :n], out[:, s:n], past, record if keep else None, vals)
+
+
 def choose(model, embeddings, choices, lengths=None, **generate_kwargs):
     """Which of ``choices`` the model answers with (Magma.choose): constrained greedy decoding with ``return_logprobs=True`` and
     ``max_steps`` = the longest choice + 1, every row's tokens mapped back with ``TokenTrie.index``.  ``choices``: what
@@ -1273,9 +1299,8 @@ def choose(model, embeddings, choices, lengths=None, **generate_kwargs):
              "num_beams", "return_scores"} & set(generate_kwargs)
     if fixed:
         raise ValueError(f"choose() sets {sorted(fixed)} itself")
-    if is_embed_batch(embeddings):
-        embeddings, lengths = embeddings
-    b = len(embeddings) if isinstance(embeddings, (list, tuple)) else embeddings.shape[0]
+    embeddings, lengths = prompt_batch(embeddings, lengths, check=False)
+    b = embeddings.shape[0]
     tries = check_constraint_args(choices, b, getattr(getattr(model, "tokenizer", None), "encode", None), _logit_count(model))
     if tries is None:
         raise ValueError("choose() needs choices")
@@ -1466,10 +1491,7 @@ def rank(model, embeddings, choices, lengths=None, *, eos=True, length_penalty=0
         raise ValueError(f"length_penalty must be a finite number, got {length_penalty!r}")
     if max_nodes is not None and (isinstance(max_nodes, bool) or not isinstance(max_nodes, int) or max_nodes < 1):
         raise ValueError(f"max_nodes must be a positive integer, got {max_nodes!r}")
-    if is_embed_batch(embeddings):
-        embeddings, lengths = embeddings
-    if isinstance(embeddings, (list, tuple)):
-        embeddings, lengths = pad_ragged(embeddings)
+    embeddings, lengths = prompt_batch(embeddings, lengths, check=False)        # (rank's own wording for the lengths below)
     if not torch.is_tensor(embeddings) or embeddings.ndim != 3:
         raise ValueError("embeddings must be a (B, S, d) tensor, a list of per-row tensors or embed_batch's pair")
     B, S, _ = embeddings.shape
@@ -1539,34 +1561,25 @@ def keep_conversation(cache, start: torch.Tensor, n_gen: int, eos_token, finish:
 @torch.no_grad()
 def _generate_beam(model, embeddings, max_steps, eos_token, decode, eos_check_every, lengths, k, length_penalty,
                    early_stopping, n_ret, return_scores, proc=None):
+    """generate()'s beam search over the prompt batch it has normalised: on the HIP engine's device, or beam_search on the host."""
     was_training = model.training
-    if isinstance(embeddings, (list, tuple)):
-        embeddings, derived = pad_ragged(embeddings)
-        if lengths is not None and not torch.equal(torch.as_tensor(lengths).cpu().to(torch.int64).view(-1), derived):
-            raise ValueError(f"lengths {list(lengths)} do not match the per-sample embeddings ({derived.tolist()})")
-        lengths = derived
+    on_device = getattr(model.lm, "device_token_selection", False)
+    embeddings, lengths = prompt_batch(embeddings, lengths, per_row=on_device)
     b, s, _ = embeddings.shape
     dev = embeddings.device
-    on_device = getattr(model.lm, "device_token_selection", False)
-    if lengths is not None:
-        if not on_device:
-            raise ValueError("generate(lengths=...) needs the HIP engine's LM (per-row KV positions)")
-        from .engine import LMEngine
-        lengths = LMEngine.check_lengths(lengths, b, s)
     model.eval()
     emb = embeddings.repeat_interleave(k, dim=0)           # B prompts -> B*k rows, sample-major
     if on_device:
-        mode = (k, length_penalty, early_stopping, int(max_steps))
-        every = eos_check_every or int(os.environ.get("MAGMA_EOS_CHECK_EVERY", "8"))
-        kw = {} if lengths is None else {"lengths": lengths.repeat_interleave(k)}
         from .engine import LMEngine
-        pkw = {} if proc is None else {"processors": LMEngine.proc_mode(proc)}
+        plan = LMEngine.selection_plan(beam=(k, length_penalty, early_stopping, int(max_steps)), processors=proc,
+                                       vocab=model.lm.engine.V)
+        every = eos_check_every or int(os.environ.get("MAGMA_EOS_CHECK_EVERY", "8"))
         for i in range(max_steps):
             if i == 0:
                 o = model.lm(inputs_embeds=emb, use_cache=True, past_key_values=None, cache_hint=max_steps, reuse_cache=True,
-                             eos_token=eos_token, beam=mode, **kw, **pkw)
+                             eos_token=eos_token, plan=plan, lengths=None if lengths is None else lengths.repeat_interleave(k))
             else:
-                o = model.lm(input_ids=None, use_cache=True, past_key_values=past, feed_back=True, beam=mode, **pkw)
+                o = model.lm(input_ids=None, use_cache=True, past_key_values=past, feed_back=True, plan=plan)
             past = o.past_key_values
             if ((i + 1) % every == 0 or i + 1 == max_steps) and int(o.eos_state[1]) >= 0:     # one host sync per `every` steps
                 break

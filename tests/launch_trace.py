@@ -17,7 +17,11 @@ alive until the trace ends, so that the allocator cannot hand a freed address to
 Run as a script it prints the traces of ``CASES`` as JSON: that output, made on the commit before a change to the token step or
 the prefill, is the golden file; tests/test_launch_trace_gpu.py compares the same cases against it.
 
-The second half records a ``MagmaEngine``: what ``_lm_forward`` and ``_lm_backward`` launch in one training step (TrainTrace,
+``SELECT_CASES`` / ``run_select_case`` record the token-selection ops alone (SELECT_OPS: what runs behind the head, for the first
+token of a call and for one cached step, under every selection mode); ``python tests/launch_trace.py select`` prints
+tests/golden/selection_launch_trace.json, made on the commit before a change to how the modes reach the step.
+
+The last part records a ``MagmaEngine``: what ``_lm_forward`` and ``_lm_backward`` launch in one training step (TrainTrace,
 ``TRAIN_CASES``, ``run_train_case``), with the bits of the loss and a digest of every gradient.  ``python tests/launch_trace.py train``
 prints tests/golden/train_launch_trace.json, which tests/test_train_launch_trace_gpu.py compares against."""
 import inspect
@@ -307,6 +311,125 @@ def run_case(dev, case):
     return out, res
 
 
+# ---- token selection: what the first token of a call and one cached step launch behind the head -------------------------------------
+SELECT_OPS = ("logits_guidance", "logits_process", "logits_process_constrained", "argmax", "sample", "sample_warp", "token_logprobs",
+              "sample_finish", "sample_finish_rows", "guidance_follow", "beam_topk", "beam_finish", "kv_reorder", "advance_pos")
+SELECT_WRITES = {"logits_guidance": ["cond"], "logits_process": ["logits"], "logits_process_constrained": ["logits"],
+                 "argmax": ["out"], "sample": ["out"], "sample_warp": ["out"]}
+# the cache's buffers of the selection modes (allocated on first use) and of beam search
+_CACHE_SELECT = ("suppress", "stop_table", "finish", "lp", "top_id", "top_lp", "trie_table", "trie_roots", "trie_path")
+_BEAM_BUFFERS = ("run", "fin_score", "fin_flag", "fin_len", "fin_tok", "fin_stage", "hist_stage", "unsat", "parent", "cand_score",
+                 "cand_tok", "kstage", "vstage")
+
+
+class SelectTrace(Trace):
+    """Trace of the selection ops alone: the cache's selection and beam buffers are named too, and a tensor that lives in no
+    named buffer (the prefill's logits, the copy the first token's processors work on) is numbered by first appearance."""
+
+    def __init__(self, eng, cache=None, inputs=None):
+        super().__init__(eng, cache, inputs)
+        self.writes = SELECT_WRITES
+        self._anon = 0
+
+    def _names(self):
+        tensors, weights = super()._names()
+        cache = self.cache
+        if cache is None and len(self.eng._cache_pool) == 1:
+            cache = next(iter(self.eng._cache_pool.values()))
+        if cache is not None:
+            tensors += [(f"cache.{k}", getattr(cache, k)) for k in _CACHE_SELECT if getattr(cache, k) is not None]
+            if cache.beam is not None:
+                tensors += [(f"cache.beam.{k}", getattr(cache.beam, k)) for k in _BEAM_BUFFERS]
+        return tensors, weights
+
+    def _describe(self, v, names):
+        if torch.is_tensor(v) and self._tensor(v, names[0])[:2] in ("?+", "?["):      # in no buffer, not numbered yet
+            self._written.append((v.data_ptr(), v.data_ptr() + _span(v), f"?{self._anon}", v.stride(0) if v.ndim >= 2 else 0))
+            self._anon += 1
+        return super()._describe(v, names)
+
+
+_PROC =dict(repetition_penalty=1.3, no_repeat_ngram_size=2, min_new_tokens=1, suppress_tokens=[11, 12])
+_PROC_CONS = dict(_PROC, no_repeat_ngram_size=0)       # (a constraint refuses the n-gram rule)
+_STOP = dict(eos_ids=[0, 7], stop_seqs=[[21, 22]])
+_STOP2 = dict(eos_ids=[0, 7])
+_GUIDE = (1.5, 0.05)
+_BEAM = (2, 1.0, False, 8)
+# id -> (keywords of the first-token call and of the cached step, "guided" | "beam" | "two_tokens" | "extend" | None).
+# ``constraint: True`` stands for one TokenTrie per selecting row.
+SELECT_CASES = {
+    "greedy": ({}, None),
+    "sample": (dict(sampling=(0.7, 5, 0.9)), None),
+    "warp": (dict(sampling=("warp", 0.7, 5, 0.9, 0.05)), None),
+    "processors": (dict(processors=_PROC), None),
+    "stop": (dict(stop=_STOP), None),
+    "logprobs0": (dict(logprobs=0), None),
+    "logprobs3": (dict(logprobs=3), None),
+    "processors_logprobs": (dict(processors=_PROC, logprobs=3), None),
+    "constraint": (dict(constraint=True), None),
+    "constraint_all": (dict(constraint=True, processors=_PROC_CONS, stop=_STOP2, logprobs=3), None),
+    "guidance": (dict(guidance=_GUIDE), "guided"),
+    "guidance_logprobs": (dict(guidance=_GUIDE, logprobs=3), "guided"),
+    "guidance_all": (dict(guidance=_GUIDE, constraint=True, processors=_PROC_CONS, stop=_STOP2, logprobs=3,
+                          sampling=(0.7, 5, 0.9)), "guided"),
+    "beam": (dict(beam=_BEAM), "beam"),
+    "beam_processors": (dict(beam=_BEAM, processors=_PROC), "beam"),
+    "two_tokens": (dict(sampling=(0.7, 5, 0.9), processors=_PROC), "two_tokens"),
+    "extend": (dict(processors=_PROC, stop=_STOP), "extend"),
+}
+
+
+def run_select_case(dev, case):
+    """{"first": the selection launches of the first token (forward(..., eos_token=, seed=) on the prefill logits -- "extend": on
+    the logits of inputs_embeds appended to a cache), "step": those of one cached step, eager, the selected tokens fed back --
+    "two_tokens": of one call with two input ids per row}: the reduced model, 2 selecting rows, 5 prompt positions."""
+    from magma_amd.sampling import TokenTrie
+    from magma_amd.testing import build_reduced_magma
+    kw, kind = case
+    torch.manual_seed(7)
+    model = build_reduced_magma(dev, mlp_factor=4)
+    model.eval()
+    eng = model.lm.engine
+    R = 2
+    B = 2 * R if kind in ("guided", "beam") else R
+    if kw.get("constraint") is True:
+        kw = dict(kw, constraint=[TokenTrie([[31, 32], [31, 33, 34]]), TokenTrie([[41], [42, 43]])])
+    g = torch.Generator().manual_seed(3)
+    emb = torch.randn(B, 5, eng.d, generator=g).to(torch.bfloat16).to(dev)
+    first = dict(kw, eos_token=0, seed=5)
+    if kind == "guided":
+        first["lengths"] = torch.tensor([5, 4, 3, 5])
+    out = {}
+    with torch.no_grad():
+        if kind == "extend":
+            cache = eng.forward(inputs_embeds=emb, use_cache=True, cache_hint=16).past_key_values
+            more = torch.randn(B, 3, eng.d, generator=g).to(torch.bfloat16).to(dev)
+            call = lambda: eng.forward(inputs_embeds=more, use_cache=True, past_key_values=cache, cache_hint=8, **first)  # noqa: E731
+        else:
+            cache = None
+            call = lambda: eng.forward(inputs_embeds=emb, use_cache=True, cache_hint=8, reuse_cache=True, **first)  # noqa: E731
+        tr = SelectTrace(eng, cache)
+        out["first"], res = record(eng, call, trace=tr, op_names=SELECT_OPS)
+        if isinstance(res, Exception):
+            raise res
+        cache = res.past_key_values
+        tr = SelectTrace(eng, cache)
+        if kind == "two_tokens":
+            ids = torch.randint(0, 1000, (B, 2), generator=g).to(dev)
+            eager = eng.decode
+            eng.decode = lambda *a, **k: eager(*a, use_graph=False, **k)        # forward() would capture its second step
+            try:
+                out["step"], res = record(eng, lambda: eng.forward(input_ids=ids, use_cache=True, past_key_values=cache, **kw),
+                                          trace=tr, op_names=SELECT_OPS)
+            finally:
+                del eng.decode
+        else:
+            out["step"], res = record(eng, lambda: eng.decode(None, cache, use_graph=False, **kw), trace=tr, op_names=SELECT_OPS)
+        if isinstance(res, Exception):
+            raise res
+    return out
+
+
 # ---- the training step: what MagmaEngine._lm_forward / _lm_backward launch -----------------------------------------------------------
 TRAIN_OPS = OPS + ("rotary_qk_inplace", "attn_fwd_rows", "attn_bwd_rows", "transpose", "transpose_colsum", "colsum", "layernorm_bwd",
                    "cross_entropy_fwd_bwd", "gelu_erf_grad_mul", "scale_rows_acc", "mx_empty")
@@ -493,6 +616,14 @@ def main():
     dev = torch.device("cuda:0")
     if sys.argv[1:] == ["train"]:
         return main_train(dev)
+    if sys.argv[1:] == ["select"]:
+        traces = {name: run_select_case(dev, case) for name, case in SELECT_CASES.items()}
+        torch.cuda.synchronize()
+        sys.stdout.write("{\n" + ",\n".join(
+            f' {json.dumps(name)}: {{' + ", ".join(
+                f'"{ph}": [\n' + ",\n".join("   " + json.dumps(r, sort_keys=True, separators=(",", ":")) for r in recs) + "\n  ]"
+                for ph, recs in sorted(out.items())) + "}" for name, out in traces.items()) + "\n}\n")
+        return
     traces = {}
     for name, case in CASES.items():
         out, res = run_case(dev, case)

@@ -34,6 +34,27 @@ def test_launches_match_golden(dev, name):
         assert len(got[phase]) == len(want), f"{name} / {phase}: {len(got[phase])} launches, golden has {len(want)}"
 
 
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "selection_launch_trace.json")) as f:
+    SELECT_GOLDEN = json.load(f)
+
+
+def test_selection_golden_covers_the_cases():
+    assert set(SELECT_GOLDEN) == set(LT.SELECT_CASES)
+    for name in LT.SELECT_CASES:
+        assert set(SELECT_GOLDEN[name]) == {"first", "step"} and all(SELECT_GOLDEN[name].values()), name
+
+
+@pytest.mark.parametrize("name", list(LT.SELECT_CASES))
+def test_selection_launches_match_golden(dev, name):
+    """The selection ops of the first token and of one cached step under every selection mode and the combinations that take
+    another path (tests/golden/selection_launch_trace.json: recorded on the commit before the modes became one SelectionPlan)."""
+    got = json.loads(json.dumps(LT.run_select_case(dev, LT.SELECT_CASES[name])))
+    for phase, want in SELECT_GOLDEN[name].items():
+        for i, (g, w) in enumerate(zip(got[phase], want)):
+            assert g == w, f"{name} / {phase}: record {i} differs"
+        assert len(got[phase]) == len(want), f"{name} / {phase}: {len(got[phase])} launches, golden has {len(want)}"
+
+
 def test_w8_refusal_comes_before_the_first_launch(dev):
     """W8A16 on a grouped block whose adapter has no e4m3 operand (r = 256 at d = 1024): decode() refuses while it plans the
     step, with nothing of that step enqueued.  (Planning packs the e4m3 weights first: those quantize_rows_fp8 launches read
