@@ -763,6 +763,98 @@ def assert_attention_backward(dq, dk, dv, q, k, v, dO_rows, out_rows, lse, what:
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# the ViT attention backward (attn_small_bwd_kernel, csrc/elementwise.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+# (B, S, H): one token (dq = dk = 0, dv = dO); two tokens, two batch items, one head; a short odd sequence; ViT-B/32 at 224;
+# one below the LDS limit; the limit with one head and with twelve; more workgroups (23 * 12 = 276) than the 256 CUs
+ATTN_SMALL_BWD_SHAPES = ((1, 1, 3), (2, 2, 1), (1, 7, 2), (2, 50, 12), (2, 63, 2), (3, 64, 1), (1, 64, 12), (23, 50, 12))
+ATTN_SMALL_BWD_FAMILIES = ("i.i.d.", "last key leads", "class rows only", "ViT scale")
+
+
+def attn_small_lead_gain(S: int) -> float:
+    """c of the "last key leads" family: the last key is c u, every query carries u (|u|^2 ~ 64), so that key's score is ~8 c
+    above scores that spread by ~1.4.  0.75 from S = 7 on (a lead of 6: the median largest weight is 0.70 .. 0.91 against 50 .. 64
+    rivals, 0.98 against 6), 0.5 (a lead of 4 over one rival: 0.98) below: peaked, but NOT one-hot -- a one-hot row has dS = 0
+    exactly, and a dropped dq store is no fault there (tests/test_kernel_compare_cpu.py asserts both properties)."""
+    return 0.75 if S >= 7 else 0.5
+
+
+def attn_small_backward_inputs(family: str, B: int, S: int, H: int, seed: int = 731):
+    """(qkv [B*S, 3*H*64], d_out [B*S, H*64]) bf16 on the CPU, from fixed seeds:
+      "i.i.d."           unit Gaussians, as test_attn_small_forward;
+      "last key leads"   that test's construction with the gain of attn_small_lead_gain: every row of P leans on column S - 1,
+                         which an output sum that ends one index short leaves out;
+      "class rows only"  d_out is zero except in row 0 of each image: what the last ViT block's backward is given (only the class
+                         token is read); dP, dS and dq are then zero outside row 0;
+      "ViT scale"        qkv * 0.7, unit d_out: the inputs of test_attn_small_backward."""
+    g = torch.Generator().manual_seed(seed + 8 * S + H)
+    w = H * 64
+    qkv = torch.randn(B * S, 3 * w, generator=g)
+    d_out = torch.randn(B * S, w, generator=g)
+    if family == "ViT scale":
+        qkv = qkv * 0.7
+    elif family == "last key leads":
+        u = torch.randn(1, 1, H, 64, generator=g)
+        x = qkv.view(B, S, 3, H, 64)
+        x[:, :, 0] += u
+        if S > 1:
+            x[:, S - 1, 1] = attn_small_lead_gain(S) * u[:, 0]
+    elif family == "class rows only":
+        d_out.view(B, S, w)[:, 1:] = 0.0
+    elif family != "i.i.d.":
+        raise ValueError(family)
+    return qkv.to(torch.bfloat16), d_out.to(torch.bfloat16)
+
+
+def heads_of(rows: torch.Tensor, B: int, S: int, H: int) -> torch.Tensor:
+    """[B*S, n*H*64] rows (n = 3: the fused q | k | v columns; n = 1: one of them) -> [n, B, H, S, 64] views."""
+    return rows.view(B, S, -1, H, 64).permute(2, 0, 3, 1, 4)
+
+
+def attn_small_backward_reference(qkv, d_out, B: int, S: int, H: int) -> dict:
+    """What mg_attn_small_bwd_bf16 computes from qkv [B*S, 3*H*64] and d_out [B*S, H*64], in fp64, with per-element bounds for its
+    bf16 outputs -> {"dq" | "dk" | "dv": (ref, bound)}, each [B, H, S, 64]:
+
+        t = q k^T / 8,  P = softmax(t),  dP = dO V^T,  D_i = sum_j P_ij dP_ij,  dS = P o (dP - D) / 8,
+        dQ = dS K,  dK = dS^T Q,  dV = P^T dO.
+
+    Unlike the flash kernels of attention_backward_reference this one saves nothing: everything is fp32 in LDS, nothing is masked,
+    P is never rounded to bf16 and D comes from P o dP, not from an O of the forward.  One term per step of the kernel:
+      score, dP   64-term fp32 dot products (the factor 1/8 is exact): gamma(64) (|q| . |k|) / 8 and gamma(64) (|dO| . |v|);
+      P_ij        e = __expf(t_ij - m): exp_rel_err(max_j (|q| . |k_j|) / 8, 64) covers the score, the subtraction, __expf's own
+                  multiply and v_exp_f32; the same rounded m enters numerator and denominator.  l adds S such terms in fp32
+                  (each carries the exponential's error once more, and at most S roundings), inv = 1 / l is a division (U_DIV),
+                  e * inv rounds once:  e_p = 2 exp_rel_err + gamma(S + 2) + U_DIV, relative;
+      D_i         the sum of S products P~_ij dP~_ij in fp32:
+                  sum_j P_ij (e_p |dP_ij| + gamma(64) (|dO| . |v|)_ij) + gamma(S) sum_j P_ij |dP_ij|;
+      dS_ij       P~ (dP~ - D~) / 8, a subtraction and two products (the last by 1/8, exact -- counted all the same):
+                  E_ij = P_ij (gamma(64) (|dO| . |v|)_ij + D_err_i + gamma(3) (|dP_ij| + |D_i|)) / 8 + (e_p + gamma(2)) |dS_ij|;
+      dQ, dK, dV  sums over S terms in fp32: E |K| + gamma(S) |dS| |K|, its transposed form with |Q|, and
+                  (e_p + gamma(S)) P^T |dO| with e_p of the row the weight comes from; then one rounding to bf16."""
+    x = heads_of(f64(qkv), B, S, H)
+    q, k, v = x[0], x[1], x[2]
+    dO = heads_of(f64(d_out), B, S, H)[0]
+    t = q @ k.transpose(-1, -2) * 0.125
+    a_max = (q.abs() @ k.abs().transpose(-1, -2) * 0.125).max(-1, keepdim=True).values
+    P = torch.softmax(t, -1)
+    e_p = 2.0 * exp_rel_err(a_max, 64) + gamma(S + 2) + U_DIV                          # [B, H, S, 1]
+    dP, dP_mag = dO @ v.transpose(-1, -2), dO.abs() @ v.abs().transpose(-1, -2)
+    Dv = (P * dP).sum(-1, keepdim=True)
+    D_err = (P * (e_p * dP.abs() + gamma(64) * dP_mag)).sum(-1, keepdim=True) + gamma(S) * (P * dP.abs()).sum(-1, keepdim=True)
+    dS = P * (dP - Dv) * 0.125
+    E = P * (gamma(64) * dP_mag + D_err + gamma(3) * (dP.abs() + Dv.abs())) * 0.125 + (e_p + gamma(2)) * dS.abs()
+    acc = gamma(S)
+    dQ = dS @ k
+    dQ_err = E @ k.abs() + acc * (dS.abs() @ k.abs())
+    dK = dS.transpose(-1, -2) @ q
+    dK_err = E.transpose(-1, -2) @ q.abs() + acc * (dS.abs().transpose(-1, -2) @ q.abs())
+    dV = P.transpose(-1, -2) @ dO
+    dV_err = ((e_p + acc) * P).transpose(-1, -2) @ dO.abs()
+    bf = torch.bfloat16
+    return {"dq": (dQ, rounded(dQ, dQ_err, bf)), "dk": (dK, rounded(dK, dK_err, bf)), "dv": (dV, rounded(dV, dV_err, bf))}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # LayerNorm backward, rotary, column sums
 # ---------------------------------------------------------------------------------------------------------------------------
 def layernorm_bwd_reference(dy, x, g, eps: float, res=None):

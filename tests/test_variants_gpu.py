@@ -384,6 +384,7 @@ def test_vit_pooled_prefix_train_gradients(dev):
     name_of = {id(p): n for n, p in model.named_parameters()}
     seen, bad = set(), []
     dots = n1 = n2 = bd = b1 = 0.0
+    thirds = 0
     for grp in eng.groups:
         for p in grp.params:
             n = name_of[id(p)]
@@ -395,9 +396,21 @@ def test_vit_pooled_prefix_train_gradients(dev):
             e_hip, e_bf = rel(got, ref), rel(gb, ref)
             if e_hip > 2 * e_bf + 3e-2:
                 bad.append((n, e_hip, e_bf))
+            if n.endswith(("attn.in_proj_weight", "attn.in_proj_bias")):
+                # the q, k and v rows each on their own: in the whole tensor the K rows (the gradient mg_attn_small_bwd_bf16
+                # writes as dk) are diluted by the V rows, and a few per cent of error in them stay under the floor.  (The k third
+                # of the BIAS is zero in exact arithmetic -- a constant added to every key's score leaves the softmax as it is --
+                # so its reference is the fp32 oracle's roundoff, ~1e-9, and the rule compares two such residues there.)
+                for third, (a, r, b) in zip("qkv", zip(got.chunk(3), ref.chunk(3), gb.chunk(3))):
+                    thirds += 1
+                    t_hip, t_bf = rel(a, r), rel(b, r)
+                    print(f"[thirds] {n} {third} rows: rel {t_hip:.3e}, bf16 oracle {t_bf:.3e}, |ref| {float(r.norm()):.3e}")
+                    if t_hip > 2 * t_bf + 3e-2:
+                        bad.append((f"{n}, {third} rows", t_hip, t_bf))
             dots += float((got * ref).sum()); n1 += float((got * got).sum()); n2 += float((ref * ref).sum())
             bd += float((gb * ref).sum()); b1 += float((gb * gb).sum())
     assert len(seen) == len(g_ref) and len(seen) > 150, (len(seen), len(g_ref), sorted(set(g_ref) - seen)[:5])
+    assert thirds == 72, thirds                 # 12 blocks x (weight, bias) x (q, k, v)
     assert not bad, bad[:8]
     cos_hip, cos_bf = dots / (n1 ** 0.5 * n2 ** 0.5), bd / (b1 ** 0.5 * n2 ** 0.5)
     assert 1 - cos_hip <= 2 * (1 - cos_bf) + 1e-3, (cos_hip, cos_bf)
