@@ -99,8 +99,9 @@ const char* mg_version(void);
  *  16  token log-probabilities: added mg_token_logprobs_f32 (nothing moved).
  *  17  constrained decoding: added mg_logits_process_constrained_f32 (nothing moved).
  *  18  classifier-free guidance: added mg_logits_guidance_f32 and mg_guidance_follow (nothing moved).
- *  19  ranking choices: added mg_attn_prefill_tree_bf16, mg_rotary_split_at_bf16 and mg_token_logprobs_rows_f32 (nothing moved). */
-#define MG_ABI_VERSION 19
+ *  19  ranking choices: added mg_attn_prefill_tree_bf16, mg_rotary_split_at_bf16 and mg_token_logprobs_rows_f32 (nothing moved).
+ *  20  explaining answers: added mg_attn_prefill_scaled_bf16 (nothing moved). */
+#define MG_ABI_VERSION 20
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -323,6 +324,19 @@ int mg_attn_prefill_bf16(const mg_bf16* q, const mg_bf16* kcache, const mg_bf16*
                          int64_t ld_out /* row stride of out in elements; 0 = H*256 (ABI 2: see mg_decode_attn_gemv_bf16) */,
                          float* lse, int32_t B, int32_t H, int32_t S, int32_t Smax, int32_t vt_ld,
                          void* stream);
+
+/* K10 with a per-key scale on the score (ABI 20; DESIGN.md "Explaining an answer"): the operands of mg_attn_prefill_bf16 plus
+ * key_scale, fp32, row b's S entries at key_scale + b * ld_scale (ld_scale >= S floats; the heads of a row share it).  For query t and
+ * key j of row b the score is  s[t][j] = (q_t . k_j) / 16 * key_scale[b][j]  in fp32, the causal mask (j > t excluded) is applied
+ * AFTER the scaling, then the fp32 softmax and P V of mg_attn_prefill_bf16.  A scale of 0 therefore leaves the key the weight
+ * exp(0 - max), a masked key stays masked whatever its scale, and the running maximum is taken over the scaled scores.  lse is the
+ * log-sum-exp of the scaled scores.  Entries must be finite and >= 0 (the caller's duty: the kernel does not look); nothing past
+ * key_scale[b][S - 1] is read.  One implementation, the 32-query-wave kernel that mg_attn_prefill_bf16 runs by default (its
+ * MAGMA_ATTN_FWD switch does not apply here): with key_scale == 1 out and lse have that kernel's bits.  ld_out % 8 == 0 (0 = H*256),
+ * S <= 4096 (the row's scales are staged in LDS), key_scale 4-byte aligned.                                                         */
+int mg_attn_prefill_scaled_bf16(const mg_bf16* q, const mg_bf16* kcache, const mg_bf16* vt, mg_bf16* out, int64_t ld_out,
+                                float* lse, int32_t B, int32_t H, int32_t S, int32_t Smax, int32_t vt_ld,
+                                const float* key_scale, int64_t ld_scale, void* stream);
 
 /* K10 over a cache (ABI 9): causal flash attention of a chunk of T new queries per sequence against the KV cache, the arithmetic of
  * mg_attn_prefill_bf16 (fp32 online softmax, scale 1/16).  Row b's chunk starts at p_b = d_pos[b * pos_stride] (pos_stride as in

@@ -13,6 +13,16 @@
 //                 [ rescale of O^T when the running maximum moved (rare) ]
 //                 [ V^T(t) reads | O^T += V^T(t) P^T(t)   : 16 MFMAs  ||  row max / running max / alpha of tile t+1     ]
 // K rows and V^T tiles stream through a 4-stage LDS ring filled by LDS-DMA, counted vmcnt + one barrier per tile.
+//
+// The kernel's text below is compiled TWICE: this file includes itself once.
+//   attn_prefill32_kernel          ATTN32_SCALED 0: the kernel of mg_attn_prefill_bf16, token for token what it was;
+//   attn_prefill32_scaled_kernel   ATTN32_SCALED 1: mg_attn_prefill_scaled_bf16 -- every score multiplied by its key's entry of
+//       key_scale (row b at key_scale + b * ld_scale) BEFORE the causal mask.  The row's scales sit in LDS behind the ring, staged
+//       once beside the Q loads (an ordinary global load inside the pipelined loop would break the hand-counted vmcnt of the DMA
+//       ring), and a lane reads the 16 of its keys of a tile a burst of MFMAs ahead of the part 1 that multiplies them in.
+// Two compilations of one text and not a template flag: as a template instance, or inlined from a shared body, hipcc schedules
+// the unscaled kernel differently (same instructions, other order and registers); like this it keeps its bytes.
+#ifndef ATTN32_KERNEL              // ---- first pass only
 #include "attn32_device.h"
 #include <stdlib.h>
 
@@ -32,9 +42,17 @@ MG_DEV float pair_sum(float x) {
   return __uint_as_float(a[0]) + __uint_as_float(a[1]);
 }
 
-__global__ __launch_bounds__(256) void attn_prefill32_kernel(
+#define ATTN32_KERNEL attn_prefill32_kernel
+#define ATTN32_SCALED 0
+#endif                             // ---- both passes: the kernel
+
+__global__ __launch_bounds__(256) void ATTN32_KERNEL(
     const mg_bf16* __restrict__ q, const mg_bf16* __restrict__ kcache, const mg_bf16* __restrict__ vt,
-    mg_bf16* __restrict__ out, int64_t ld_out, float* __restrict__ lse, int B, int H, int S, int Smax, int vt_ld, float defer) {
+    mg_bf16* __restrict__ out, int64_t ld_out, float* __restrict__ lse, int B, int H, int S, int Smax, int vt_ld, float defer
+#if ATTN32_SCALED
+    , const float* __restrict__ key_scale, int64_t ld_scale
+#endif
+    ) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -74,6 +92,25 @@ __global__ __launch_bounds__(256) void attn_prefill32_kernel(
 #pragma unroll
     for (int ks = 0; ks < 16; ++ks) qf[ks] = *(const bf16x8*)(qp + ks * 16);
   }
+  // scales of keys [0, (ntiles + 1) * 32): part 1 of the tile past the last one (fully masked) reads them too; keys >= S get 1.0
+  // and the global index is clamped, so nothing past key_scale[b][S - 1] is read
+#if ATTN32_SCALED
+  {
+    const float* ksrow = key_scale + (int64_t)b * ld_scale;
+    float* kw = (float*)(smem + F_STAGES * F_STAGE);
+    const int n = (ntiles + 1) * 32;
+    for (int j0 = tid; j0 < n; j0 += 1024) {
+      float v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = ksrow[min(j0 + u * 256, S - 1)];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int j = j0 + u * 256;
+        if (j < n) kw[j] = j < S ? v[u] : 1.0f;
+      }
+    }
+  }
+#endif
   f32x16 o[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
@@ -100,8 +137,24 @@ __global__ __launch_bounds__(256) void attn_prefill32_kernel(
   bf16x8 fa[4], fb[4];
   f32x16 sA, sB;                       // scores of the current / the next tile, swapping roles every iteration (no copies)
   float alpha;
+#if ATTN32_SCALED
+  // the 16 scales of this lane's keys of one tile (key (r >> 3) 16 + (r & 7) + 8 hi of tile kv0), read from LDS a burst
+  // of MFMAs ahead of the part 1 that multiplies them in
+  f32x4 kq[4];
+  auto fetch_scale = [&](int kv0) {
+    const float* sp = (const float*)(smem + F_STAGES * F_STAGE) + kv0 + hi * 8;
+    kq[0] = *(const f32x4*)sp;
+    kq[1] = *(const f32x4*)(sp + 4);
+    kq[2] = *(const f32x4*)(sp + 16);
+    kq[3] = *(const f32x4*)(sp + 20);
+  };
+#endif
   // part 1 of the softmax of the tile whose scores are in sn: (mask,) row maximum, running maximum, rescale factor
   auto part1 = [&](f32x16& sn, int kv0) {
+#if ATTN32_SCALED                       // on the fp32 score, BEFORE the mask: a masked key stays masked whatever its scale
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sn[r] *= kq[r >> 2][r & 3];
+#endif
     // only the tiles that straddle this wave's queries (and the ragged last tile) need the mask
     if (kv0 + 31 > my_first || kv0 + 32 > S) {
       const int lim = lim0 - kv0;
@@ -123,6 +176,9 @@ __global__ __launch_bounds__(256) void attn_prefill32_kernel(
   MG_BARRIER_KEEP_DMA();
   {
     const uint32_t krow = rb;
+#if ATTN32_SCALED
+    fetch_scale(0);
+#endif
     rd_row4x(fa, smem, krow, 0);
     rd_row4x(fb, smem, krow, 1);
     MG_SCHED_FENCE();
@@ -233,6 +289,9 @@ __global__ __launch_bounds__(256) void attn_prefill32_kernel(
     MG_SCHED_FENCE();
     // ---- block B: O^T += V^T(t) P^T(t), 16 MFMAs; part 1 of softmax(t+1) behind the first burst ----
     MG_LGKM4();
+#if ATTN32_SCALED
+    fetch_scale((t + 1) * 32);
+#endif
 #pragma unroll
     for (int i = 0; i < 4; ++i) { const int j = ((i & 1) << 1) | (i >> 1); mfma32a(o[j >> 1], fa[j], (j & 1) ? pf1 : pf0); }
     rd_t4(fa, vtp, 2, tx);
@@ -294,6 +353,13 @@ __global__ __launch_bounds__(256) void attn_prefill32_kernel(
   if (lse && hi == 0 && qrow < S) lse[(int64_t)bh * S + qrow] = (m2 + log2f(lsum)) * 0.6931471805599453f;
 }
 
+#if !ATTN32_SCALED                 // ---- first pass only: the text once more as the scaled kernel, then the launchers
+#undef ATTN32_KERNEL
+#undef ATTN32_SCALED
+#define ATTN32_KERNEL attn_prefill32_scaled_kernel
+#define ATTN32_SCALED 1
+#include "attention_fwd32.hip"
+
 }  // namespace
 
 int attn_prefill32_launch(const mg_bf16* q, const mg_bf16* kcache, const mg_bf16* vt, mg_bf16* out, int64_t ld_out, float* lse,
@@ -306,3 +372,31 @@ int attn_prefill32_launch(const mg_bf16* q, const mg_bf16* kcache, const mg_bf16
   MG_CHECK_LAUNCH();
   return MG_OK;
 }
+
+// The forward with a per-key scale on the fp32 score (magma_hip.h; DESIGN.md "Explaining an answer"): the kernel above with the
+// row's scales staged in LDS behind the ring -- (ceil(S / 32) + 1) * 32 floats.  One implementation: the variant switch of
+// mg_attn_prefill_bf16 does not apply here, and with key_scale == 1 the result has the bits of its default (this file's kernel).
+constexpr float ATTN32_DEFER = 8.0f;          // FA2_DEFER of attention.hip, what mg_attn_prefill_bf16 passes by default
+constexpr int ATTN32_SCALED_MAX_S = 4096;     // 16.1 KiB of scales: 144.1 of the workgroup's 160 KiB of LDS
+
+extern "C" int mg_attn_prefill_scaled_bf16(const mg_bf16* q, const mg_bf16* kcache, const mg_bf16* vt, mg_bf16* out, int64_t ld_out,
+                                           float* lse, int32_t B, int32_t H, int32_t S, int32_t Smax, int32_t vt_ld,
+                                           const float* key_scale, int64_t ld_scale, void* stream) {
+  const char* who = "mg_attn_prefill_scaled_bf16";
+  if (ld_out == 0) ld_out = (int64_t)H * DH;
+  if (ld_out < (int64_t)H * DH || (ld_out & 7)) MG_FAIL(MG_ERR_SHAPE, "%s: ld_out must be 0 or a multiple of 8 >= H*256", who);
+  if (B <= 0 || H <= 0 || S <= 0 || S > Smax) MG_FAIL(MG_ERR_SHAPE, "%s: bad B/H/S/Smax", who);
+  if (S > ATTN32_SCALED_MAX_S) MG_FAIL(MG_ERR_SHAPE, "%s: S <= %d (the row's scales are staged in LDS beside the ring)", who, ATTN32_SCALED_MAX_S);
+  if ((vt_ld & 31) || vt_ld < ((S + 31) & ~31)) MG_FAIL(MG_ERR_SHAPE, "%s: vt_ld must be a multiple of 32 and >= S", who);
+  if (!q || !kcache || !vt || !out || !key_scale) MG_FAIL(MG_ERR_SHAPE, "%s: null pointer", who);
+  if (ld_scale < S) MG_FAIL(MG_ERR_SHAPE, "%s: ld_scale must be >= S", who);
+  if (!MG_ALIGNED16(q) || !MG_ALIGNED16(kcache) || !MG_ALIGNED16(vt) || !MG_ALIGNED16(out)) MG_FAIL(MG_ERR_ALIGN, "%s: pointers must be 16-byte aligned", who);
+  if ((uintptr_t)key_scale & 3) MG_FAIL(MG_ERR_ALIGN, "%s: key_scale must be 4-byte aligned", who);
+  const int lds = F_STAGES * F_STAGE + (((S + 31) >> 5) + 1) * 128;
+  if (int rc = mg_allow_dynamic_lds((const void*)attn_prefill32_scaled_kernel, lds, who)) return rc;
+  hipLaunchKernelGGL(attn_prefill32_scaled_kernel, dim3((unsigned)(((S + 127) / 128) * B * H)), dim3(256), lds,
+                     (hipStream_t)stream, q, kcache, vt, out, ld_out, lse, B, H, S, Smax, vt_ld, ATTN32_DEFER, key_scale, ld_scale);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+#endif

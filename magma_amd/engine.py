@@ -915,14 +915,23 @@ class LMEngine:
 
     # -------------------------------------------------------------- prefill
     def _blocks_prefill(self, embeds: torch.Tensor, cache: Optional[KVCache], want_hidden=False, lse_out=None, chunk=False,
-                        tree=None):
+                        tree=None, key_scale=None):
         """The blocks over B x S new rows.  ``chunk``: the rows continue ``cache`` -- row b's S rows sit at cache.d_pos[b * pos_stride]
         + s, their K / V are appended there and they attend over the cached keys (mg_attn_prefill_cached_bf16); every GEMM, adapter and
         epilogue launch is the prefill's.  ``tree`` (with ``chunk``; tree_forward): the rows are trie nodes -- (d_pos int32 [B], off,
         sub int32 [B, S], p_min) -- row s goes to slot d_pos[b] + s at position d_pos[b] + off[b, s] and sees the cache below d_pos[b]
-        and the chunk rows j <= s < sub[b, j] (mg_rotary_split_at_bf16 / mg_attn_prefill_tree_bf16 in place of the chunk's two)."""
+        and the chunk rows j <= s < sub[b, j] (mg_rotary_split_at_bf16 / mg_attn_prefill_tree_bf16 in place of the chunk's two).  ``key_scale``
+        (check_key_scale; the plain cache-less bf16 branch only): fp32 [B, S], every block and head multiplies the score of key j of
+        row b by key_scale[b, j] before the causal mask (mg_attn_prefill_scaled_bf16 in place of mg_attn_prefill_bf16)."""
         B, S, d = embeds.shape
         assert d == self.d
+        if key_scale is not None:
+            mode = ("a tree forward" if tree is not None else "a chunk that continues a KV cache" if chunk
+                    else "the fp8 attention mode" if self.fp8_mode and self.fp8_attn and cache is None else None)
+            if mode is not None:
+                raise NotImplementedError(f"key_scale is not implemented for {mode}")
+            if key_scale.dtype != torch.float32 or tuple(key_scale.shape) != (B, S) or key_scale.device != embeds.device:
+                raise ValueError(f"key_scale must be fp32 ({B}, {S}) on {embeds.device}, got {key_scale.dtype} {tuple(key_scale.shape)}")
         if S > self.cfg.max_position_embeddings:
             raise ValueError(f"sequence length {S} exceeds max_position_embeddings")
         dev = self.device
@@ -973,7 +982,10 @@ class LMEngine:
                 ops.attn_prefill_fp8(a8, ctx, lse=None if lse_out is None else lse_out[li])
             else:
                 ops.rotary_split(qkv, B, S, self.H, self.rot, self.sin_t, self.cos_t, q, kc, vc, pos0=0, vt=vt)
-                ops.attn_prefill(q, kc, vt, ctx, B, self.H, S, lse=None if lse_out is None else lse_out[li])
+                if key_scale is not None:
+                    ops.attn_prefill_scaled(q, kc, vt, ctx, B, self.H, S, key_scale, lse=None if lse_out is None else lse_out[li])
+                else:
+                    ops.attn_prefill(q, kc, vt, ctx, B, self.H, S, lse=None if lse_out is None else lse_out[li])
             if r_cat and ly.out_up is not None and ly.mlp_adapter[0].N == r_cat:
                 h = h_fused if h_fused is not None else self._linear(ly, "fc_in", ly.fc_in, ln, lnq, act=ops.MG_ACT_GELU_NEW)
                 m = ops.gemm(h, ly.fc_out)
@@ -1581,15 +1593,37 @@ class LMEngine:
         ops.gemm(xl, self.head, out=logits)
         return rows[keep], kept, logits[:, : self.V]
 
-    def score(self, embeds: torch.Tensor, tgt: torch.Tensor, n_top: int = 0):
+    @staticmethod
+    def check_key_scale(key_scale, B: int, S: int) -> torch.Tensor:
+        """The host check of a key scale, before any launch: a (B, S) tensor, finite, >= 0.  Returns it as a contiguous fp32 host
+        tensor (the caller moves it to the device)."""
+        ks = torch.as_tensor(key_scale)
+        if ks.ndim != 2 or tuple(ks.shape) != (B, S):
+            raise ValueError(f"key_scale must have shape ({B}, {S}), got {tuple(ks.shape)}")
+        if not ks.dtype.is_floating_point:
+            raise ValueError(f"key_scale must be a floating-point tensor, got {ks.dtype}")
+        ks = ks.detach().to("cpu", torch.float32).contiguous()       # one small copy when it sat on the device
+        if not bool(torch.isfinite(ks).all()):
+            raise ValueError("key_scale must be finite")
+        if bool((ks < 0).any()):
+            raise ValueError("key_scale must be >= 0")
+        return ks
+
+    def score(self, embeds: torch.Tensor, tgt: torch.Tensor, n_top: int = 0, key_scale=None):
         """Log-probabilities of given tokens (Magma.score; DESIGN.md "Token log-probabilities"): one cache-less forward over
         ``embeds`` (B, S, d), the fp32 head on the rows that predict a target (``tgt`` (B, S) int64: the token position s of row
         b predicts, -100 for none; _target_logits), then the kernel of the generate() loop without a step counter.  Returns device
         tensors in (b, s) order of the targets: (log-probabilities [n], top ids [n, n_top] int32, their log-probabilities
-        [n, n_top])."""
+        [n, n_top]).  ``key_scale`` (B, S), finite and >= 0 (checked on the host before any launch): the attention of every block and
+        head multiplies the score of key j of row b by key_scale[b, j] (DESIGN.md "Explaining an answer"); None launches what it
+        always did."""
         n_top = self.logprob_mode(n_top, self.V)
         B, S, _ = embeds.shape
-        x, _ = self._blocks_prefill(embeds, None)
+        if key_scale is not None:
+            if self.fp8_mode and self.fp8_attn:
+                raise NotImplementedError("key_scale is not implemented for the fp8 attention mode")
+            key_scale = self.check_key_scale(key_scale, B, S).to(self.device)
+        x, _ = self._blocks_prefill(embeds, None, key_scale=key_scale)
         head = self._target_logits(x, S, tgt.to(self.device))
         if head is None:
             raise ValueError("score: no position carries a target")

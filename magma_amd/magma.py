@@ -349,22 +349,14 @@ class Magma(nn.Module):
         return rank(self, embeddings, choices, lengths=lengths, eos=eos, length_penalty=length_penalty, max_nodes=max_nodes,
                     return_terms=return_terms)
 
-    @torch.no_grad()
-    def score(self, embeddings, targets, lengths=None, *, top_logprobs: int = 0):
-        """How probable the model finds GIVEN tokens after a prompt (DESIGN.md "Token log-probabilities"): ranking candidate
-        answers, per-caption perplexity (``exp(-logprobs.sum(1) / count)``).  ``embeddings`` is what ``generate`` takes as a
-        prompt: (B, S, d) with optional ``lengths``, a list of per-sample tensors, or embed_batch's pair.  ``targets``: int64
-        (B, T) right-padded with -100, or a list of id lists; at least one id per row, every id in [0, V).  One cache-less
-        forward over [prompt_b ; wte(targets_b[:-1])], right-padded; the fp32 head runs only on the rows that predict a target.
-        Returns a ``TokenLogprobs`` over the T columns: ``logprobs[b, j]`` = log p(targets_b[j] | prompt_b, targets_b[:j]) under
-        the raw model distribution -- what ``generate(return_logprobs=True)`` reports for a token it selected --, the
-        ``top_logprobs`` most probable tokens at every position, ``count[b]`` = the row's number of targets; positions past it
-        hold 0.0 / -1 / -inf.  Scoring against a KV cache is not supported."""
+    def _score_inputs(self, embeddings, targets, lengths=None, width: int = None, host_check=None):
+        """What score() and explain() feed the engine: the checked prompts and targets as (emb (B, W, d) on the device = [prompt_b ;
+        wte(targets_b[:-1])] right-padded with zeros, tgt (B, W) int64 host: the token position s of row b predicts or -100, tokens
+        (B, T) int64 host right-padded with -100, count int64 [B], lens int64 [B], S = the prompts' padded width).  W = max_b (len_b + count_b - 1), or ``width``
+        when that is larger.  ``host_check(B, W, S)`` runs after every check of the inputs and before the first launch."""
         from . import ops
-        from .sampling import check_logprob_args, mask_logprobs, prompt_batch
-        torch.cuda.set_device(self.device)
+        from .sampling import prompt_batch
         eng = self.lm.engine
-        n_top = check_logprob_args(True, top_logprobs, eng.V)
         embeddings, lens = prompt_batch(embeddings, lengths)
         B, S, d = embeddings.shape
         if lens is None:
@@ -389,9 +381,15 @@ class Magma(nn.Module):
         count = torch.tensor([len(r) for r in rows], dtype=torch.int64)
         total = lens + count - 1
         n_pos = self.lm.config.max_position_embeddings
-        if int(total.max()) > n_pos:
-            raise ValueError(f"prompt plus targets reach {int(total.max())} positions, beyond max_position_embeddings = {n_pos}")
         W, T = int(total.max()), int(count.max())
+        if width is not None:
+            if int(width) < W:
+                raise ValueError(f"width {width} is less than the {W} positions the batch needs")
+            W = int(width)
+        if W > n_pos:
+            raise ValueError(f"prompt plus targets reach {W} positions, beyond max_position_embeddings = {n_pos}")
+        if host_check is not None:
+            host_check(B, W, S)
         emb = torch.zeros(B, W, d, dtype=self.dtype, device=self.device)
         tgt = torch.full((B, W), -100, dtype=torch.int64)
         tokens = torch.full((B, T), -100, dtype=torch.int64)
@@ -402,11 +400,77 @@ class Magma(nn.Module):
                 ops.embedding(torch.tensor([r[:-1]], dtype=torch.int64, device=self.device), eng.wte, emb[b:b + 1], row_off=L)
             tgt[b, L - 1: L - 1 + len(r)] = torch.tensor(r, dtype=torch.int64)
             tokens[b, : len(r)] = torch.tensor(r, dtype=torch.int64)
-        lp, top_id, top_lp = (v.cpu() for v in eng.score(emb, tgt, n_top))
+        return emb, tgt, tokens, count, lens, S
+
+    @torch.no_grad()
+    def score(self, embeddings, targets, lengths=None, *, top_logprobs: int = 0, key_scale=None, width: int = None,
+              past_key_values=None):
+        """How probable the model finds GIVEN tokens after a prompt (DESIGN.md "Token log-probabilities"): ranking candidate
+        answers, per-caption perplexity (``exp(-logprobs.sum(1) / count)``).  ``embeddings`` is what ``generate`` takes as a
+        prompt: (B, S, d) with optional ``lengths``, a list of per-sample tensors, or embed_batch's pair.  ``targets``: int64
+        (B, T) right-padded with -100, or a list of id lists; at least one id per row, every id in [0, V).  One cache-less
+        forward over [prompt_b ; wte(targets_b[:-1])], right-padded; the fp32 head runs only on the rows that predict a target.
+        Returns a ``TokenLogprobs`` over the T columns: ``logprobs[b, j]`` = log p(targets_b[j] | prompt_b, targets_b[:j]) under
+        the raw model distribution -- what ``generate(return_logprobs=True)`` reports for a token it selected --, the
+        ``top_logprobs`` most probable tokens at every position, ``count[b]`` = the row's number of targets; positions past it
+        hold 0.0 / -1 / -inf.  Scoring against a KV cache is not supported (``past_key_values`` raises NotImplementedError).
+
+        ``key_scale`` (DESIGN.md "Explaining an answer"): scores under suppressed attention.  In every block and head the
+        pre-softmax score of key j of row b is multiplied by key_scale[b, j]; 1.0 leaves a key alone, entries are finite and >= 0
+        (checked on the host before any launch).  Shape (B, W) over the W = max_b (len_b + count_b - 1) positions of the forward,
+        or (B, S) over the prompt positions only, which is right-padded with 1.0.  None launches what score always launched.
+        ``width``: run the forward over this many positions (>= W; the extra ones are padding no row sees) -- what gives all
+        forwards of ``explain`` one shape."""
+        from .sampling import check_logprob_args, mask_logprobs
+        torch.cuda.set_device(self.device)
+        eng = self.lm.engine
+        n_top = check_logprob_args(True, top_logprobs, eng.V)
+        if past_key_values is not None:
+            raise NotImplementedError("score runs one cache-less forward: past_key_values"
+                                      + (" and key_scale are" if key_scale is not None else " is") + " not supported")
+        if key_scale is not None and getattr(eng, "fp8_mode", False) and getattr(eng, "fp8_attn", False):
+            raise NotImplementedError("key_scale is not implemented for the fp8 attention mode")
+        scale = []
+
+        def check_scale(B, W, S):           # on the host, before the first launch
+            ks = torch.as_tensor(key_scale)
+            if ks.ndim != 2 or ks.shape[0] != B or ks.shape[1] not in (W, S):
+                raise ValueError(f"key_scale must have shape ({B}, {W}) or, over the prompt positions, ({B}, {S}); got {tuple(ks.shape)}")
+            ks = eng.check_key_scale(ks, B, ks.shape[1])
+            scale.append(ks if ks.shape[1] == W else torch.cat([ks, torch.ones(B, W - ks.shape[1])], 1))
+
+        emb, tgt, tokens, count, lens, _ = self._score_inputs(embeddings, targets, lengths, width,
+                                                              check_scale if key_scale is not None else None)
+        B, T = tokens.shape
+        key_scale = scale[0] if scale else None
+        lp, top_id, top_lp = (v.cpu() for v in eng.score(emb, tgt, n_top, key_scale=key_scale))
         at = torch.arange(T)[None, :] < count[:, None]            # (b, j) order = the order of the kept rows
         out_lp, out_id, out_tl = torch.zeros(B, T), torch.zeros(B, T, n_top, dtype=torch.int64), torch.zeros(B, T, n_top)
         out_lp[at], out_id[at], out_tl[at] = lp, top_id.to(torch.int64), top_lp
         return mask_logprobs(tokens, out_lp, out_id, out_tl, count)
+
+    @torch.no_grad()
+    def explain(self, embeddings, targets, lengths=None, *, suppression: float = 0.9, units=None,
+                similarity_threshold: float = None, batch_size: int = 16, return_terms: bool = False):
+        """Which prompt positions carry an answer (DESIGN.md "Explaining an answer"): perturbation-only relevance by attention
+        suppression (AtMan).  ``embeddings`` / ``lengths`` / ``targets`` are what ``score`` takes.  A unit is a set of prompt
+        positions suppressed together -- by default one unit per prompt position; ``units``: per row a list of position lists (a
+        word of several tokens, a block of patches).  For each unit the targets are scored again with the pre-softmax attention
+        score of the unit's keys multiplied by ``1 - suppression`` in every block and head; the rise of the mean negative
+        log-probability of the targets is the unit's relevance.  ``similarity_threshold`` = kappa: every prompt position whose
+        embedding has cosine c >= kappa with one of the unit's is suppressed along with it, by ``1 - suppression * c``.
+        Returns ``sampling.Explanation(relevance [B, U], loss [B], perturbed_loss [B, U], count [B])`` on the host; columns past
+        count[b] hold 0.0; ``Explanation.grid`` cuts the image-patch map out of a row.  ``return_terms``: also the per-target
+        log-probabilities, fp32 [B, 1 + U, T] (index 0: unperturbed; 0.0 where there is nothing).
+
+        Cost: sum_b (1 + count[b]) rows, scored ``batch_size`` at a time in forwards of ONE shape (batch_size, W), W = max_b (len_b +
+        n_targets_b - 1); the last forward is filled up with unperturbed copies.  A forward holds about 14 bf16 activations of
+        batch_size x W x d elements (fused qkv | fc_in, q, k, v, V^T, the attention output, two residual streams) plus
+        batch_size x n_targets fp32 logit rows of the padded vocabulary: 0.3 GB at batch_size 16, W 172, d 4096.  Whether that
+        fits is the caller's business."""
+        from .sampling import explain
+        return explain(self, embeddings, targets, lengths=lengths, suppression=suppression, units=units,
+                       similarity_threshold=similarity_threshold, batch_size=batch_size, return_terms=return_terms)
 
     @torch.no_grad()
     def cache_prompt(self, embeddings, lengths=None, cache_hint: int = 256):

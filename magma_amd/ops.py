@@ -564,6 +564,34 @@ def attn_prefill(q, kcache, vt, out, B, H, S, lse: Optional[torch.Tensor] = None
     return out
 
 
+def attn_prefill_scaled(q, kcache, vt, out, B, H, S, key_scale, lse: Optional[torch.Tensor] = None):
+    """attn_prefill with every score multiplied by its key's scale before the causal mask (mg_attn_prefill_scaled_bf16; DESIGN.md
+    "Explaining an answer"): s[t, j] = (q_t . k_j) / 16 * key_scale[b, j] in fp32.  ``key_scale`` fp32 (B, >= S) with unit column
+    stride (row stride = its stride(0); the heads of a row share it); entries finite and >= 0 -- the callers' duty (LMEngine.score
+    checks on the host), the kernel does not look.  The other operands are attn_prefill's; S <= 4096."""
+    _need_gpu(q, key_scale)
+    if q.ndim != 4 or tuple(q.shape) != (B, H, S, 256) or not q.is_contiguous() or q.dtype != torch.bfloat16:
+        raise ValueError(f"q must be a contiguous bf16 ({B}, {H}, {S}, 256) tensor, got {q.dtype} {tuple(q.shape)}")
+    if kcache.ndim != 4 or kcache.shape[0] != B or kcache.shape[1] != H or kcache.shape[3] != 256 or not kcache.is_contiguous() \
+            or kcache.dtype != torch.bfloat16 or kcache.shape[2] < S:
+        raise ValueError(f"kcache must be a contiguous bf16 ({B}, {H}, Smax >= {S}, 256) cache, got {kcache.dtype} {tuple(kcache.shape)}")
+    if vt.ndim != 5 or vt.shape[0] != B or vt.shape[1] != H or tuple(vt.shape[3:]) != (256, 32) or not vt.is_contiguous() \
+            or vt.dtype != torch.bfloat16 or vt.shape[2] * 32 < S:
+        raise ValueError(f"vt must be a contiguous bf16 ({B}, {H}, >= {ceil_to(S, 32) // 32}, 256, 32) tensor, got {vt.dtype} {tuple(vt.shape)}")
+    if out.ndim != 2 or out.stride(1) != 1 or out.shape[0] != B * S or out.shape[1] != H * 256 or out.dtype != torch.bfloat16:
+        raise ValueError(f"out must be bf16 ({B * S}, {H * 256}) with unit column stride, got {out.dtype} {tuple(out.shape)}")
+    if key_scale.dtype != torch.float32 or key_scale.ndim != 2 or key_scale.shape[0] != B or key_scale.shape[1] < S \
+            or key_scale.stride(1) != 1 or (B > 1 and key_scale.stride(0) < S):
+        raise ValueError(f"key_scale must be fp32 ({B}, >= {S}) with unit column stride, got {key_scale.dtype} {tuple(key_scale.shape)}")
+    if lse is not None and (lse.dtype != torch.float32 or lse.numel() != B * H * S or not lse.is_contiguous()):
+        raise ValueError(f"lse must be a contiguous fp32 tensor of {B * H * S} elements, got {lse.dtype} {tuple(lse.shape)}")
+    check(L.load().mg_attn_prefill_scaled_bf16(q.data_ptr(), kcache.data_ptr(), vt.data_ptr(), out.data_ptr(), out.stride(0), _p(lse),
+                                               B, H, S, kcache.shape[2], vt.shape[2] * 32, key_scale.data_ptr(),
+                                               key_scale.stride(0) if B > 1 else max(key_scale.stride(0), S), _stream()),
+          "mg_attn_prefill_scaled_bf16")
+    return out
+
+
 def attn_prefill_cached(q, kcache, vcache, out, B, H, T, d_pos, *, pos_stride: int = 0):
     """Causal attention of a chunk of T new (already rotated) queries per row against the KV cache: query t of row b sits at
     p_b + t (p_b = d_pos[b * pos_stride]) and sees cache keys [0, p_b + t]; the chunk's K / V must already be in the cache

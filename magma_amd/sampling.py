@@ -1531,6 +1531,177 @@ def rank(model, embeddings, choices, lengths=None, *, eos=True, length_penalty=0
     return (out, terms) if return_terms else out
 
 
+class Explanation(NamedTuple):
+    """What explain() returns: CPU tensors over the B rows and the U = most units of a row; columns past count[b] hold 0.0."""
+    relevance: torch.Tensor        # fp32 [B, U]: perturbed_loss - loss[:, None]
+    loss: torch.Tensor             # fp32 [B]: mean negative log-probability of the row's targets, unperturbed
+    perturbed_loss: torch.Tensor   # fp32 [B, U]: the same with unit u suppressed
+    count: torch.Tensor            # int64 [B]: the row's number of units
+
+    def grid(self, b: int, start: int, height: int, width: int) -> torch.Tensor:
+        """The relevance of the height * width units from ``start`` on as a (height, width) view -- the image-patch map when the
+        default units are used and the image's tokens start at prompt position ``start`` (image_prefix lays them out row-major:
+        12 x 12 for RN50x16 at 384 x 384)."""
+        n = int(height) * int(width)
+        if height < 1 or width < 1 or start < 0 or start + n > self.relevance.shape[1]:
+            raise ValueError(f"grid of {height} x {width} units from {start} does not fit {self.relevance.shape[1]} units")
+        return self.relevance[b, start: start + n].view(int(height), int(width))
+
+
+def check_explain_args(suppression=0.9, similarity_threshold=None, batch_size=16):
+    """The scalar arguments of explain(): 0 <= suppression <= 1 (the scale 1 - suppression c stays >= 0), a finite threshold or
+    None, batch_size >= 1."""
+    if isinstance(suppression, bool) or not isinstance(suppression, (int, float)) or not 0.0 <= float(suppression) <= 1.0:
+        raise ValueError(f"suppression must be a number in [0, 1], got {suppression!r}")
+    if similarity_threshold is not None and (isinstance(similarity_threshold, bool) or not isinstance(similarity_threshold, (int, float))
+                                             or not math.isfinite(similarity_threshold)):
+        raise ValueError(f"similarity_threshold must be a finite number or None, got {similarity_threshold!r}")
+    if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+        raise ValueError(f"batch_size must be an integer >= 1, got {batch_size!r}")
+
+
+def explain_units(lens, units=None) -> List[List[List[int]]]:
+    """The units of every row as lists of prompt positions.  None: one unit per prompt position.  Otherwise per row a list of
+    non-empty position lists; a position outside [0, len_b) -- a target or a padding position -- raises."""
+    lens = [int(v) for v in lens]
+    if units is None:
+        return [[[p] for p in range(n)] for n in lens]
+    if len(units) != len(lens):
+        raise ValueError(f"{len(units)} unit lists for {len(lens)} rows")
+    out = []
+    for b, (row, n) in enumerate(zip(units, lens)):
+        chk = []
+        for u in row:
+            u = [int(p) for p in (u.tolist() if torch.is_tensor(u) else u)]
+            if not u:
+                raise ValueError(f"row {b}: an empty unit")
+            if any(p < 0 or p >= n for p in u):
+                raise ValueError(f"row {b}: unit {u} names a position outside the prompt [0, {n})")
+            chk.append(u)
+        out.append(chk)
+    return out
+
+
+def unit_scale(prompt, unit, suppression: float, similarity_threshold: float = None) -> torch.Tensor:
+    """The scale vector of one unit over the n prompt positions of its row, fp32 [n] on the host.  Without a threshold: 1 - suppression
+    on the unit's positions, 1.0 elsewhere.  With kappa: position k with c = max_{i in unit} cos(e_i, e_k) >= kappa gets
+    1 - suppression c (the unit's own positions: c = 1); ``prompt`` (n, d) are the row's prompt embeddings, the cosine is taken in
+    fp32 on the host so that the comparison with kappa is the same everywhere."""
+    n = prompt.shape[0]
+    idx = torch.tensor(unit, dtype=torch.int64)
+    c = torch.zeros(n, dtype=torch.float32)
+    if similarity_threshold is not None:
+        e = prompt.detach().to("cpu", torch.float32)
+        e = e / e.norm(dim=1, keepdim=True).clamp_min(1e-30)
+        c = (e[idx] @ e.t()).max(dim=0).values.clamp(max=1.0)
+        c = torch.where(c >= float(similarity_threshold), c, torch.zeros_like(c))
+    c[idx] = 1.0
+    return 1.0 - float(suppression) * c
+
+
+def explain_work_list(n_units, batch_size: int) -> List[Tuple[int, int]]:
+    """The rows explain() scores, as (b, u): per row its unperturbed copy (u = -1) and then its units, filled up with unperturbed
+    copies of row 0 to a multiple of batch_size."""
+    work = [(b, u) for b, n in enumerate(n_units) for u in range(-1, n)]
+    return work + [(0, -1)] * (-len(work) % batch_size)
+
+
+def mean_nll(logprobs: torch.Tensor, count: torch.Tensor) -> torch.Tensor:
+    """-sum_j logprobs[i, j] / count[i] in fp32 (positions past count[i] hold 0.0)."""
+    return -(logprobs.to(torch.float32).sum(dim=1) / count.to(torch.float32))
+
+
+def _explanation(work, losses, terms, n_units, return_terms):
+    B, U = len(n_units), max(n_units)
+    loss = torch.zeros(B, dtype=torch.float32)
+    pert = torch.zeros(B, U, dtype=torch.float32)
+    tm = torch.zeros(B, 1 + U, terms.shape[1], dtype=torch.float32)
+    seen = set()
+    for i, (b, u) in enumerate(work):
+        if (b, u) in seen:          # the fill-up copies
+            continue
+        seen.add((b, u))
+        tm[b, 1 + u] = terms[i]
+        if u < 0:
+            loss[b] = losses[i]
+        else:
+            pert[b, u] = losses[i]
+    live = torch.arange(U)[None, :] < torch.tensor(n_units)[:, None]
+    rel = torch.where(live, pert - loss[:, None], torch.zeros_like(pert))
+    out = Explanation(rel, loss, pert, torch.tensor(n_units, dtype=torch.int64))
+    return (out, tm) if return_terms else out
+
+
+def explain_reference(model, embeddings, targets, lengths=None, *, suppression=0.9, units=None, similarity_threshold=None,
+                      batch_size=16, return_terms=False):
+    """The host statement of Magma.explain (DESIGN.md "Explaining an answer"), the plain loop: for every (row, unit) of the work
+    list build the scale vector, score the row's targets with Magma.score(..., key_scale=) -- batch_size rows per call, every
+    call padded to the same width -- and subtract the row's unperturbed loss."""
+    check_explain_args(suppression, similarity_threshold, batch_size)
+    embeddings, lens = prompt_batch(embeddings, lengths)
+    B = embeddings.shape[0]
+    lens = torch.full((B,), embeddings.shape[1], dtype=torch.int64) if lens is None else lens
+    rows = [[int(v) for v in (r.tolist() if torch.is_tensor(r) else r) if int(v) != -100] for r in targets]
+    W = max(int(n) + len(r) - 1 for n, r in zip(lens, rows))
+    T = max(len(r) for r in rows)
+    unit_rows = explain_units(lens, units)
+    work = explain_work_list([len(u) for u in unit_rows], batch_size)
+    losses, terms = [], []
+    for i0 in range(0, len(work), batch_size):
+        chunk = work[i0: i0 + batch_size]
+        prompts, tgts, scales = [], [], []
+        for b, u in chunk:
+            n = int(lens[b])
+            prompts.append(embeddings[b, :n])
+            tgts.append(rows[b])
+            ks = torch.ones(W, dtype=torch.float32)
+            if u >= 0:
+                ks[:n] = unit_scale(embeddings[b, :n], unit_rows[b][u], suppression, similarity_threshold)
+            scales.append(ks)
+        lp = model.score(prompts, tgts, key_scale=torch.stack(scales), width=W)
+        terms.append(F.pad(lp.logprobs, (0, T - lp.logprobs.shape[1])))       # the chunk's widest row may be narrower than T
+        losses.append(mean_nll(terms[-1], lp.count))
+    return _explanation(work, torch.cat(losses), torch.cat(terms), [len(u) for u in unit_rows], return_terms)
+
+
+def explain(model, embeddings, targets, lengths=None, *, suppression=0.9, units=None, similarity_threshold=None, batch_size=16,
+            return_terms=False):
+    """Magma.explain: the work list of explain_reference through LMEngine.score in forwards of one shape (batch_size, W).  The
+    inputs are prepared once for the B rows ([prompt_b ; wte(targets_b[:-1])], the target positions) and gathered per forward on
+    the device; the scale matrix of a forward is built on the host and copied once."""
+    check_explain_args(suppression, similarity_threshold, batch_size)
+    torch.cuda.set_device(model.device)
+    eng = model.lm.engine
+    if getattr(eng, "fp8_mode", False) and getattr(eng, "fp8_attn", False):
+        raise NotImplementedError("key_scale is not implemented for the fp8 attention mode")
+    prompts, _ = prompt_batch(embeddings, lengths)
+    emb, tgt, tokens, count, lens, _ = model._score_inputs(embeddings, targets, lengths)
+    B, W = tgt.shape
+    T = tokens.shape[1]
+    unit_rows = explain_units(lens, units)
+    n_units = [len(u) for u in unit_rows]
+    if max(n_units) < 1:
+        raise ValueError("no row has a unit")
+    host = [prompts[b, : int(lens[b])].detach().to("cpu", torch.float32) for b in range(B)] if similarity_threshold is not None \
+        else [prompts[b, : int(lens[b])] for b in range(B)]      # one D2H copy per row, only the cosine needs it
+    work = explain_work_list(n_units, batch_size)
+    at = torch.arange(T)[None, :] < count[:, None]
+    losses, terms = [], []
+    for i0 in range(0, len(work), batch_size):
+        chunk = work[i0: i0 + batch_size]
+        idx = torch.tensor([b for b, _ in chunk], dtype=torch.int64)
+        ks = torch.ones(len(chunk), W, dtype=torch.float32)
+        for i, (b, u) in enumerate(chunk):
+            if u >= 0:
+                ks[i, : int(lens[b])] = unit_scale(host[b], unit_rows[b][u], suppression, similarity_threshold)
+        lp, _, _ = eng.score(emb.index_select(0, idx.to(emb.device)), tgt[idx], 0, key_scale=ks)
+        out = torch.zeros(len(chunk), T)
+        out[at[idx]] = lp.cpu()
+        losses.append(mean_nll(out, count[idx]))
+        terms.append(out)
+    return _explanation(work, torch.cat(losses), torch.cat(terms), n_units, return_terms)
+
+
 def keep_conversation(cache, start: torch.Tensor, n_gen: int, eos_token, finish: Finish = None):
     """After a generate() call of n_gen kept steps whose first token sits at position start[b] of row b: every row keeps its
     generated tokens before its first eos.  A row that emitted eos is cut back to just before it (its later slots are
