@@ -1337,15 +1337,15 @@ def attn_bwd(q, k, v, qt, kt, dO, dOt, O, lse, B, H, S):
     return dq, dk, dv
 
 
-def attn_bwd_merged(q, k, v, qt, kt, dO, O, lse, B, H, S, rot_dim, sin_t, cos_t):
+def attn_bwd_merged(q, k, v, qt, kt, dO, O, lse, B, H, S, rot_dim, sin_t, cos_t, out=None):
     """dO transpose + attn_bwd + rotary_merge_bwd in one call: -> dqkv [B*S, 3*H*256] (gradient of the fused qkv
-    projection)."""
+    projection).  ``out``: a contiguous bf16 [B*S, 3*H*256] to write into instead of a new tensor."""
     _need_gpu(q)
     assert O.ndim == 2 and O.stride(1) == 1 and dO.is_contiguous()       # O may be the [:, :d] view of a [ctx | t] buffer
     dev = q.device
     D = torch.empty(B, H, S, 2, dtype=torch.float32, device=dev)
     dOt = torch.empty_like(qt)                                       # workspace, filled by the first launch
-    dqkv = torch.empty(B * S, 3 * H * 256, dtype=BF16, device=dev)
+    dqkv = _grad_out(out, (B * S, 3 * H * 256), dev)
     check(L.load().mg_attn_bwd_merged_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), qt.data_ptr(), kt.data_ptr(),
                                            dO.data_ptr(), dOt.data_ptr(), O.data_ptr(), lse.data_ptr(), D.data_ptr(),
                                            dqkv.data_ptr(), rot_dim, sin_t.data_ptr(), cos_t.data_ptr(), B, H, S,
@@ -1392,12 +1392,22 @@ def attn_fwd_rows(x: AttnRows, out, lse: Optional[torch.Tensor] = None):
     return out
 
 
-def attn_bwd_rows(x: AttnRows, dO, O, lse, merged_rot=None, mx_out=None, no_out: bool = False, first_rows: int = 0):
+def _grad_out(out, shape, dev):
+    """A gradient output of the attention backward: new, or the caller's ``out`` (contiguous bf16 of that shape)."""
+    if out is None:
+        return torch.empty(shape, dtype=BF16, device=dev)
+    _need_gpu(out)
+    assert out.dtype == BF16 and tuple(out.shape) == tuple(shape) and out.is_contiguous(), f"out: contiguous bf16 {tuple(shape)}"
+    return out
+
+
+def attn_bwd_rows(x: AttnRows, dO, O, lse, merged_rot=None, mx_out=None, no_out: bool = False, first_rows: int = 0, out=None):
     """Attention backward without transposed operands.  merged_rot None -> (dq, dk, dv) [B,H,S,256]; merged_rot = (rot_dim, sin_t,
     cos_t) -> dqkv [B*S, 3 H 256], the gradient of the fused qkv projection (inverse rotary applied).  Merged form only:
     ``mx_out`` = (q, scales) from mx_empty(B*S, 3 H 256) -> the epilogue also writes the OCP MX e4m3 copy of dqkv; with ``no_out``
     only that copy (returns None).  ``first_rows`` > 0: only the gradients of the positions < first_rows of every sequence are
-    wanted (rounded up to whole 128-position blocks; the other rows of the outputs stay unwritten)."""
+    wanted (rounded up to whole 128-position blocks; the other rows of the outputs stay unwritten).  ``out``: the tensor(s) to
+    write into instead of new ones -- (dq, dk, dv) for the separate form, dqkv for the merged one."""
     _need_gpu(dO)
     assert O.ndim == 2 and O.stride(1) == 1 and dO.is_contiguous()
     # the rows first_rows leaves unwritten would keep 0xFF scale bytes (NaN in E8M0) in an MX copy read in whole 64-row groups
@@ -1405,7 +1415,7 @@ def attn_bwd_rows(x: AttnRows, dO, O, lse, merged_rot=None, mx_out=None, no_out:
     B, H, S, dev = x.B, x.H, x.S, dO.device
     D = torch.empty(B, H, S, 2, dtype=torch.float32, device=dev)
     if merged_rot is None:
-        dq, dk, dv = (torch.empty(B, H, S, 256, dtype=BF16, device=dev) for _ in range(3))
+        dq, dk, dv = (_grad_out(t, (B, H, S, 256), dev) for t in (out if out is not None else (None, None, None)))
         check(L.load().mg_attn_bwd_rows_bf16(x.q, x.k, x.v, x.ld_row, x.stride_b, x.stride_h, dO.data_ptr(), O.data_ptr(), O.stride(0),
                                              lse.data_ptr(), D.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), None, 0, None, None,
                                              B, H, S, None, None, int(first_rows), _stream()), "mg_attn_bwd_rows_bf16")
@@ -1416,7 +1426,8 @@ def attn_bwd_rows(x: AttnRows, dO, O, lse, merged_rot=None, mx_out=None, no_out:
     if q8 is not None:
         assert q8.dtype == torch.uint8 and q8.shape[0] >= B * S and q8.stride(0) == 3 * H * 256
         assert sc8.numel() == int(L.load().mg_mx_scale_bytes(B * S, 3 * H * 256))
-    dqkv = None if no_out else torch.empty(B * S, 3 * H * 256, dtype=BF16, device=dev)
+    assert not (no_out and out is not None), "no_out and out exclude each other"
+    dqkv = None if no_out else _grad_out(out, (B * S, 3 * H * 256), dev)
     check(L.load().mg_attn_bwd_rows_bf16(x.q, x.k, x.v, x.ld_row, x.stride_b, x.stride_h, dO.data_ptr(), O.data_ptr(), O.stride(0),
                                          lse.data_ptr(), D.data_ptr(), None, None, None, _p(dqkv), rot_dim, sin_t.data_ptr(),
                                          cos_t.data_ptr(), B, H, S, _p(q8), _p(sc8), int(first_rows), _stream()), "mg_attn_bwd_rows_bf16")

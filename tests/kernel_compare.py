@@ -726,7 +726,10 @@ def attention_backward_reference(q, k, v, dO_rows, out_rows, lse, *, p0: int = 0
       dS_ij = bf16( P_ij (dP_ij - D_i) ), dP = dO V^T an fp32 dot product over D; some variants multiply with the already rounded
               bf16(P) (two bf16 roundings), others with the fp32 weight: 2 u_bf16 covers both;
       dQ_i  = scale sum_j dS_ij k_j,  dK_j = scale sum_i dS_ij q_i : the error of dS passes through |K| / |Q|, + fp32 accumulation
-              and the output rounding."""
+              and the output rounding.
+
+    "dq_err" | "dk_err" | "dv_err": the fp32 error terms alone, BEFORE the output rounding -- what an epilogue that does more
+    than round (merged_backward_reference: the inverse rotary, then one rounding) has to carry on."""
     B, H, S, D = q.shape
     n_keys = p0 + S
     mask = causal_mask(S, k.shape[2], p0, q.device)
@@ -752,7 +755,8 @@ def attention_backward_reference(q, k, v, dO_rows, out_rows, lse, *, p0: int = 0
     dK = dS.transpose(-1, -2) @ q64 * scale
     dK_err = (E.transpose(-1, -2) @ q64.abs() + acc * (dS.abs().transpose(-1, -2) @ q64.abs())) * scale
     bf = torch.bfloat16
-    return {"dq": (dQ, rounded(dQ, dQ_err, bf)), "dk": (dK, rounded(dK, dK_err, bf)), "dv": (dV, rounded(dV, dV_err, bf))}
+    return {"dq": (dQ, rounded(dQ, dQ_err, bf)), "dk": (dK, rounded(dK, dK_err, bf)), "dv": (dV, rounded(dV, dV_err, bf)),
+            "dq_err": dQ_err, "dk_err": dK_err, "dv_err": dV_err}
 
 
 def assert_attention_backward(dq, dk, dv, q, k, v, dO_rows, out_rows, lse, what: str) -> dict:
@@ -760,6 +764,84 @@ def assert_attention_backward(dq, dk, dv, q, k, v, dO_rows, out_rows, lse, what:
     for name, got in (("dq", dq), ("dk", dk), ("dv", dv)):
         assert_elementwise(got, ref[name][0], ref[name][1], f"{what} {name}")
     return ref
+
+
+MERGED_BWD_FAMILIES = ("i.i.d.", "self c=2")
+MERGED_BWD_IID_SCALE = 1.5
+
+
+def merged_backward_inputs(kind: str, B: int, H: int, S: int, seed: int = 50):
+    """(q, k, v [B, H, S, 256], dO [B*S, H 256]) bf16 on the CPU for the tests of the merged backward, where ONE wrong row has to
+    show in dq as well.  dq_i = sum_j dS_ij k_j / 16 is a sum of signed terms, and the bound follows their MAGNITUDES: under a flat
+    softmax (i.i.d. q / k of scale 0.5: scores spread by 0.25) a row of n keys has |dq_i| ~ n^-1/2 of its magnitude sum, the bound
+    is ~ 3 u_bf16 n^1/2 |dq_i|, and at n = 2048 no fault of a row's own size reaches 8 bounds.  Both families keep the softmax peaked:
+      "i.i.d."     q, k ~ N(0, 1.5^2): scores spread by 1.5^2 = 2.25, the weights of a row are log-normal and a handful carry it
+                   (n exp(-2.25^2) effective keys at most);
+      "self c=2"   self_dominant_qkv with c = 2: a query's own key leads by ~8 and keeps more than half of the row at S = 2048
+                   (c = 1 leads by 4 and is down to 3 % there).
+    v and dO ~ N(0, 1).  tests/test_kernel_compare_cpu.py checks on the CPU that every seeded fault is >= 8 bounds for them.  That is
+    a property of THESE draws, not of the families: dq stays the weak output (a turn by the neighbouring position's angles reaches
+    9 .. 40 bounds in its last row at S = 2048 depending on the draw, a stronger lead, c = 3, makes rows one-hot and dq ~ 0), so
+    the default seed is the one the CPU test was checked with."""
+    g = torch.Generator().manual_seed(seed + 7 * S + H)
+    if kind == "i.i.d.":
+        q, k = ((torch.randn(B, H, S, 256, generator=g) * MERGED_BWD_IID_SCALE).to(torch.bfloat16) for _ in range(2))
+        v = torch.randn(B, H, S, 256, generator=g).to(torch.bfloat16)
+    elif kind.startswith("self c="):
+        q, k, v = self_dominant_qkv((B, H, S, 256), float(kind[7:]), seed + 7 * S + H)
+    else:
+        raise ValueError(kind)
+    return q, k, v, torch.randn(B * S, H * 256, generator=g).to(torch.bfloat16)
+
+
+def inverse_rotary_with_error(x: torch.Tensor, err: torch.Tensor, sin_rows: torch.Tensor, cos_rows: torch.Tensor, rot_dim: int):
+    """The inverse GPT-J turn R(-theta) of an fp64 value x [..., D] that a kernel holds in fp32 with absolute error <= err:
+    y_2i = x_2i c + x_2i+1 s,  y_2i+1 = x_2i+1 c - x_2i s  on the first rot_dim columns -> (y, error of the fp32 y).
+    Each element takes the error of itself through |c| and that of its pair partner through |s|; the arithmetic -- the 1/16 scale
+    of the accumulator, two products, one addition: gamma(4) -- is relative to the magnitude sum of the two products as the
+    kernel forms them (the perturbed values, hence |x| + err).  Columns >= rot_dim are not touched."""
+    y, e = x.clone(), err.clone()
+    if rot_dim == 0:
+        return y, e
+    s, c = f64(sin_rows).abs(), f64(cos_rows).abs()
+    xe, xo, ee, eo = x[..., 0:rot_dim:2], x[..., 1:rot_dim:2], err[..., 0:rot_dim:2], err[..., 1:rot_dim:2]
+    y[..., 0:rot_dim:2] = xe * f64(cos_rows) + xo * f64(sin_rows)
+    y[..., 1:rot_dim:2] = xo * f64(cos_rows) - xe * f64(sin_rows)
+    e[..., 0:rot_dim:2] = ee * c + eo * s + gamma(4) * ((xe.abs() + ee) * c + (xo.abs() + eo) * s)
+    e[..., 1:rot_dim:2] = eo * c + ee * s + gamma(4) * ((xo.abs() + eo) * c + (xe.abs() + ee) * s)
+    return y, e
+
+
+def merged_backward_reference(ref: dict, sin_t, cos_t, rot_dim: int, B: int, H: int, S: int):
+    """The MERGED output of the attention backward -- dqkv [B*S, 3 H 256] = [dq | dk | dv], the gradient of the fused qkv projection
+    (mg_attn_bwd_merged_bf16, mg_attn_bwd_rows_bf16 with dqkv) -- from ``ref`` = attention_backward_reference(...) of the same
+    operands -> (ref_rows, bound_rows), both [B*S, 3 H 256] fp64.
+
+    The epilogues (store_grad_row, store_grad_tile32, store_grad_tile32_tr) turn the first rot_dim columns of every dq and dk head
+    by R(-theta_s) with row s of the fp32 tables sin_t / cos_t [>= S, rot_dim / 2] (exact in fp64), in fp32, BEFORE the single
+    rounding to bf16: inverse_rotary_with_error carries the un-rounded error terms of ``ref`` through the turn, ``rounded`` adds
+    the one rounding.  Columns >= rot_dim and all of dv: the un-turned reference and error, i.e. the bound of the separate
+    outputs.  Placement as grad_row_ptr (csrc/attn_bwd_device.h) states it: row b S + s, column which H 256 + h 256 + d."""
+    ref_rows, bound_rows = [], []
+    for name in ("dq", "dk", "dv"):
+        x, err = ref[name][0], ref[name + "_err"]
+        assert x.shape[0] == B and x.shape[1] == H and x.shape[2] == S, (x.shape, B, H, S)
+        if name != "dv" and rot_dim:
+            assert sin_t.shape[0] >= S and sin_t.shape[1] == rot_dim // 2 == cos_t.shape[1] and sin_t.dtype == torch.float32
+            x, err = inverse_rotary_with_error(x, err, sin_t[:S].to(x.device), cos_t[:S].to(x.device), rot_dim)
+        ref_rows.append(rows_of(x))
+        bound_rows.append(rows_of(rounded(x, err, torch.bfloat16)))
+    return torch.cat(ref_rows, 1), torch.cat(bound_rows, 1)
+
+
+def assert_merged_attention_backward(dqkv, q, k, v, dO_rows, out_rows, lse, rot_dim: int, sin_t, cos_t, what: str, ref: dict = None) -> float:
+    """dqkv [B*S, 3 H 256] per element against merged_backward_reference; ``ref``: the attention_backward_reference of the same
+    operands where the caller has it already (assert_attention_backward returns it).  Returns the worst |err| / bound."""
+    B, H, S, _ = q.shape
+    if ref is None:
+        ref = attention_backward_reference(q, k, v, dO_rows, out_rows, lse)
+    ref_rows, bound_rows = merged_backward_reference(ref, sin_t, cos_t, rot_dim, B, H, S)
+    return assert_elementwise(dqkv, ref_rows, bound_rows, what)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -888,12 +970,15 @@ def layernorm_bwd_reference(dy, x, g, eps: float, res=None):
     return {"dx": (dx, rounded(dx, d_dx, bf)), "xhat": (xh, rounded(xh, d_xh, bf))}
 
 
-def rotary_reference(x: torch.Tensor, sin_rows: torch.Tensor, cos_rows: torch.Tensor, rot_dim: int):
+def rotary_reference(x: torch.Tensor, sin_rows: torch.Tensor, cos_rows: torch.Tensor, rot_dim: int, inverse: bool = False):
     """GPT-J rotary on the first rot_dim of the last axis, pairs (2 i, 2 i + 1) turned by angle i of the row's position:
     y_2i = x_2i c_i - x_2i+1 s_i,  y_2i+1 = x_2i+1 c_i + x_2i s_i.  x [..., D]; sin_rows / cos_rows [..., rot_dim / 2] (the fp32 table
-    rows the kernel reads, broadcastable) -> (ref, bound): two products and one addition in fp32, one rounding to bf16."""
+    rows the kernel reads, broadcastable) -> (ref, bound): two products and one addition in fp32, one rounding to bf16.
+    inverse: the turn back, y_2i = x_2i c_i + x_2i+1 s_i,  y_2i+1 = x_2i+1 c_i - x_2i s_i (what the backward applies to dq and dk)."""
     x64 = f64(x)
     s, c = f64(sin_rows), f64(cos_rows)
+    if inverse:
+        s = -s
     xe, xo = x64[..., 0:rot_dim:2], x64[..., 1:rot_dim:2]
     ref, mag = x64.clone(), x64.abs().clone()
     ref[..., 0:rot_dim:2], ref[..., 1:rot_dim:2] = xe * c - xo * s, xo * c + xe * s

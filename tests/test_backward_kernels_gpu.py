@@ -21,6 +21,13 @@ def rel(a, b):
     return float((a - b).norm() / (b.norm() + 1e-12))
 
 
+def rot_tables(rows, rot, dev):
+    """fp32 GPT-J tables sin, cos [rows, rot / 2] (rot = 0: empty tables, which the entry points accept)."""
+    inv = 1.0 / (10000 ** (torch.arange(0, rot, 2, dtype=torch.float32, device=dev) / max(rot, 1)))
+    ang = torch.arange(rows, dtype=torch.float32, device=dev)[:, None] * inv[None, :]
+    return ang.sin().contiguous(), ang.cos().contiguous()
+
+
 def test_transposes(dev):
     from magma_amd import ops
     x = rnd(200, 136, dev=dev, seed=1).to(BF16)
@@ -195,7 +202,9 @@ def test_attention_backward_boundary_inputs(dev, S, inputs):
     """dQ / dK / dV of attn_bwd and attn_bwd_rows (and the forward of attn_fwd_rows) on inputs where the causal boundary counts:
     each query's own key dominates its row, or the keys at the edges of the 32-key tiles and the last key do
     (kernel_compare.self_dominant_qkv / dominant_edge_keys); partial (57 / 300 / 385) and full (1024 / 2048) last tiles.  dV_j is
-    sum_i P_ij dO_i: a diagonal weight that is left out, or taken from the row above, moves dV_j by about |dO_j|."""
+    sum_i P_ij dO_i: a diagonal weight that is left out, or taken from the row above, moves dV_j by about |dO_j|.
+    The merged outputs of both entries (rot_dim 64) are held to kernel_compare.merged_backward_reference from the same reference:
+    the only kernel-level check of dqkv at S = 2048, the training length."""
     from magma_amd import ops
     B, H = 1, 2
     d = H * 256
@@ -211,14 +220,22 @@ def test_attention_backward_boundary_inputs(dev, S, inputs):
     lse = torch.empty(B, H, S, dtype=torch.float32, device=dev)
     ops.attn_fwd_rows(x, out, lse=lse)
     kcmp.assert_causal_attention(out, q, k, v, f"attn_fwd_rows, {inputs}, S={S}", lse=lse)
-    kcmp.assert_attention_backward(*ops.attn_bwd_rows(x, dO, out, lse), q, k, v, dO, out, lse, f"attn_bwd_rows, {inputs}, S={S}")
+    ref = kcmp.assert_attention_backward(*ops.attn_bwd_rows(x, dO, out, lse), q, k, v, dO, out, lse, f"attn_bwd_rows, {inputs}, S={S}")
+    # the merged output (dqkv with the inverse rotary in the epilogue: what the training engine consumes), from the same reference
+    rot = 64
+    sin_t, cos_t = rot_tables(S + 3, rot, dev)
+    kcmp.assert_merged_attention_backward(ops.attn_bwd_rows(x, dO, out, lse, merged_rot=(rot, sin_t, cos_t)), q, k, v, dO, out, lse,
+                                          rot, sin_t, cos_t, f"attn_bwd_rows merged, {inputs}, S={S}", ref=ref)
+    del ref
     hs = H * S * 256
     vt, qt, kt = (ops.head_transpose(t, B, H, S, sb=hs, ss=256, sh=S * 256) for t in (v, q, k))
     dOt = ops.head_transpose(dO, B, H, S, sb=S * d, ss=d, sh=256)
     out2, lse2 = torch.empty_like(out), torch.empty_like(lse)
     ops.attn_prefill(q, k, vt, out2, B, H, S, lse=lse2)
-    kcmp.assert_attention_backward(*ops.attn_bwd(q, k, v, qt, kt, dO, dOt, out2, lse2, B, H, S), q, k, v, dO, out2, lse2,
-                                   f"attn_bwd, {inputs}, S={S}")
+    ref = kcmp.assert_attention_backward(*ops.attn_bwd(q, k, v, qt, kt, dO, dOt, out2, lse2, B, H, S), q, k, v, dO, out2, lse2,
+                                         f"attn_bwd, {inputs}, S={S}")
+    kcmp.assert_merged_attention_backward(ops.attn_bwd_merged(q, k, v, qt, kt, dO, out2, lse2, B, H, S, rot, sin_t, cos_t), q, k, v, dO,
+                                          out2, lse2, rot, sin_t, cos_t, f"attn_bwd_merged, {inputs}, S={S}", ref=ref)
 
 
 @pytest.mark.parametrize("variant", [0, 1, 2, 3, 4, 5, 6, 7, 8])
@@ -252,13 +269,17 @@ def test_attention_backward_kernel_variants(dev, monkeypatch, variant, B, H, S):
             assert float(got.float().abs().max()) < 1e-6, name
         else:
             assert rel(got, ref) < 1.5e-2, (variant, name, rel(got, ref))
-    kcmp.assert_attention_backward(dq, dk, dv, q, k, v, dO, out, lse, f"attn_bwd variant {variant} B={B} H={H} S={S}")
+    ref = kcmp.assert_attention_backward(dq, dk, dv, q, k, v, dO, out, lse, f"attn_bwd variant {variant} B={B} H={H} S={S}")
     rot = 64
     inv = 1.0 / (10000 ** (torch.arange(0, rot, 2, dtype=torch.float32, device=dev) / rot))
     ang = torch.arange(S + 3, dtype=torch.float32, device=dev)[:, None] * inv[None, :]
     sin_t, cos_t = ang.sin().contiguous(), ang.cos().contiguous()
     two_pass = ops.rotary_merge_bwd(dq, dk, dv, B, S, H, rot, sin_t, cos_t)
     merged = ops.attn_bwd_merged(q, k, v, qt, kt, dO, out, lse, B, H, S, rot, sin_t, cos_t)
+    # every element of dqkv against the fp64 reference turned by the table row of its position, one rounding; the norms below stay
+    # as the coarser second check
+    kcmp.assert_merged_attention_backward(merged, q, k, v, dO, out, lse, rot, sin_t, cos_t,
+                                          f"attn_bwd_merged variant {variant} B={B} H={H} S={S}", ref=ref)
     assert torch.equal(merged[:, 2 * d:], two_pass[:, 2 * d:])                     # dv: no rotary, same rounding
     if S > 1:
         for sl in (slice(0, d), slice(d, 2 * d)):
@@ -390,7 +411,7 @@ def test_attention_without_transposed_images(dev, B, H, S):
             assert float(got.float().abs().max()) < 1e-6, name
         else:
             assert rel(got, ref) < 1.5e-2, (name, rel(got, ref))
-    kcmp.assert_attention_backward(dq, dk, dv, q, k, v, dO, out, lse, f"attn_bwd_rows B={B} H={H} S={S}")
+    ref = kcmp.assert_attention_backward(dq, dk, dv, q, k, v, dO, out, lse, f"attn_bwd_rows B={B} H={H} S={S}")
     for a, b_ in zip(ops.attn_bwd_rows(xf, dO, out_f[:, :d], lse), (dq, dk, dv)):
         assert torch.equal(a, b_)
     rot = 64
@@ -399,6 +420,11 @@ def test_attention_without_transposed_images(dev, B, H, S):
     sin_t, cos_t = ang.sin().contiguous(), ang.cos().contiguous()
     two_pass = ops.rotary_merge_bwd(dq, dk, dv, B, S, H, rot, sin_t, cos_t)
     merged = ops.attn_bwd_rows(xf, dO, out, lse, merged_rot=(rot, sin_t, cos_t))
+    # dqkv per element, from both operand forms: every bit comparison below (mx_out, no_out, first_rows) rests on this tensor
+    for got, form in ((merged, "fused qkv operand"), (ops.attn_bwd_rows(x, dO, out, lse, merged_rot=(rot, sin_t, cos_t)), "[B,H,S,256] operands")):
+        kcmp.assert_merged_attention_backward(got, q, k, v, dO, out, lse, rot, sin_t, cos_t,
+                                              f"attn_bwd_rows merged, {form}, B={B} H={H} S={S}", ref=ref)
+    del ref
     assert merged.shape == (B * S, 3 * d) and torch.equal(merged[:, 2 * d:], two_pass[:, 2 * d:])
     if S > 1:
         for sl in (slice(0, d), slice(d, 2 * d)):
@@ -422,6 +448,92 @@ def test_attention_without_transposed_images(dev, B, H, S):
             assert torch.equal(a[:, :, :n], b_[:, :, :n]), P
         part = ops.attn_bwd_rows(xf, dO, out, lse, merged_rot=(rot, sin_t, cos_t), first_rows=P)
         assert torch.equal(part.view(B, S, 3 * d)[:, :n], merged.view(B, S, 3 * d)[:, :n]), P
+
+
+def merged_sections(dqkv, B, H, S):
+    """dqkv [B*S, 3 H 256] -> its dq, dk, dv sections as [B, H, S, 256] views (grad_row_ptr, csrc/attn_bwd_device.h)."""
+    x = dqkv.view(B, S, 3, H, 256).permute(2, 0, 3, 1, 4)
+    return x[0], x[1], x[2]
+
+
+MERGED_S_LADDER = (1, 31, 32, 33, 127, 128, 129, 257)        # around the 32-row wave tiles and the 128-row blocks
+MERGED_ROT_LADDER = (0, 8, 32, 256)                          # at S = 129; rot_dim 64 is the S ladder's
+
+
+@pytest.mark.parametrize("inputs", kcmp.MERGED_BWD_FAMILIES)
+@pytest.mark.parametrize("S,rot", [(S, 64) for S in MERGED_S_LADDER] + [(129, r) for r in MERGED_ROT_LADDER])
+def test_merged_backward_sequence_and_rotary_edges(dev, monkeypatch, S, rot, inputs):
+    """dqkv of the rows entry (mg_attn_bwd_rows_bf16) and of mg_attn_bwd_merged_bf16 at one variant per epilogue -- 0: store_grad_row,
+    3: store_grad_tile32, 8: store_grad_tile32_tr -- per element against kernel_compare.merged_backward_reference, B = 2, H = 2:
+    with a ragged S the rows a tile holds past S lie next to the NEXT batch item's rows, and the tables [S + 3, rot / 2] have rows
+    past S that a position off by one would read.  Inputs: kernel_compare.merged_backward_inputs (for which the CPU suite shows
+    every single-row fault of an epilogue at 8 bounds and more).  dqkv is handed over full of NaN: every element must be written.
+    Where the merged and the separate form issue the SAME launches -- the rows entry, and variant 8 (>= 5: attn_bwd_prep_kernel
+    in both) -- the columns the rotary does not touch (all of them at rot_dim 0, all of dv always) agree bit for bit with the
+    separate dq / dk / dv.  Variants 0 and 3 take D = rowsum(dO o O) from attn_bwd_prep_t_kernel in the merged form, another
+    summation order: there dq and dk have the per-element bound only, and dv (which does not depend on D) the bits."""
+    from magma_amd import ops
+    B, H = 2, 2
+    d = H * 256
+    q, k, v, dO = (t.to(dev) for t in kcmp.merged_backward_inputs(inputs, B, H, S))
+    x = ops.AttnRows.of_bhsd(q, k, v)
+    out = torch.empty(B * S, d, dtype=BF16, device=dev)
+    lse = torch.empty(B, H, S, dtype=torch.float32, device=dev)
+    ops.attn_fwd_rows(x, out, lse=lse)
+    sin_t, cos_t = rot_tables(S + 3, rot, dev)
+    ref = kcmp.attention_backward_reference(q, k, v, dO, out, lse)
+    hs = H * S * 256
+    qt, kt = (ops.head_transpose(t, B, H, S, sb=hs, ss=256, sh=S * 256) for t in (q, k))
+    dOt = ops.head_transpose(dO, B, H, S, sb=S * d, ss=d, sh=256)
+
+    def check(dqkv, sep, what, same_launches):
+        assert bool(torch.isfinite(dqkv).all()), f"{what}: {int((~torch.isfinite(dqkv)).sum())} elements of dqkv not written"
+        kcmp.assert_merged_attention_backward(dqkv, q, k, v, dO, out, lse, rot, sin_t, cos_t, f"{what}, {inputs}, S={S} rot={rot}", ref=ref)
+        mq, mk, mv = merged_sections(dqkv, B, H, S)
+        assert torch.equal(mv, sep[2]), f"{what}: dv"
+        if same_launches:
+            assert torch.equal(mq[..., rot:], sep[0][..., rot:]) and torch.equal(mk[..., rot:], sep[1][..., rot:]), f"{what}: columns >= rot_dim"
+
+    nan = lambda: torch.full((B * S, 3 * d), float("nan"), dtype=BF16, device=dev)
+    check(ops.attn_bwd_rows(x, dO, out, lse, merged_rot=(rot, sin_t, cos_t), out=nan()), ops.attn_bwd_rows(x, dO, out, lse), "attn_bwd_rows merged", True)
+    for variant in (0, 3, 8):
+        monkeypatch.setenv("MAGMA_ATTN_BWD", str(variant))
+        sep = ops.attn_bwd(q, k, v, qt, kt, dO, dOt, out, lse, B, H, S)
+        dqkv = ops.attn_bwd_merged(q, k, v, qt, kt, dO, out, lse, B, H, S, rot, sin_t, cos_t, out=nan())
+        check(dqkv, sep, f"attn_bwd_merged variant {variant}", variant >= 5)
+
+
+SENTINEL = -1232.0          # exact in bf16; nothing the kernels compute from these inputs comes near it
+
+
+@pytest.mark.parametrize("P", [1, 127, 128, 129])
+def test_attention_backward_first_rows_leaves_the_rest_unwritten(dev, P):
+    """first_rows = P at S = 300 (B = 2, H = 2): the first ceil(P / 128) blocks of 128 positions carry the bits of the full launch --
+    whose merged output is held to the per-element bound here -- and every row from ceil(P / 128) 128 on still holds what the
+    caller put there, in the merged and in the separate form: a block too many, or a tile that runs past its block, shows."""
+    from magma_amd import ops
+    B, H, S, rot = 2, 2, 300, 64
+    d = H * 256
+    q, k, v, dO = (t.to(dev) for t in kcmp.merged_backward_inputs("i.i.d.", B, H, S))
+    x = ops.AttnRows.of_bhsd(q, k, v)
+    out = torch.empty(B * S, d, dtype=BF16, device=dev)
+    lse = torch.empty(B, H, S, dtype=torch.float32, device=dev)
+    ops.attn_fwd_rows(x, out, lse=lse)
+    sin_t, cos_t = rot_tables(S + 3, rot, dev)
+    full_sep = ops.attn_bwd_rows(x, dO, out, lse)
+    full = ops.attn_bwd_rows(x, dO, out, lse, merged_rot=(rot, sin_t, cos_t))
+    ref = kcmp.assert_attention_backward(*full_sep, q, k, v, dO, out, lse, "attn_bwd_rows (full launch of the first_rows test)")
+    kcmp.assert_merged_attention_backward(full, q, k, v, dO, out, lse, rot, sin_t, cos_t, "attn_bwd_rows merged (full launch)", ref=ref)
+    n = (P + 127) // 128 * 128
+    assert n < S
+    part = ops.attn_bwd_rows(x, dO, out, lse, merged_rot=(rot, sin_t, cos_t), first_rows=P,
+                             out=torch.full((B * S, 3 * d), SENTINEL, dtype=BF16, device=dev)).view(B, S, 3 * d)
+    assert torch.equal(part[:, :n], full.view(B, S, 3 * d)[:, :n]), "merged: the written rows"
+    assert bool((part[:, n:] == SENTINEL).all()), f"merged: {int((part[:, n:] != SENTINEL).sum())} elements written at positions >= {n}"
+    outs = tuple(torch.full((B, H, S, 256), SENTINEL, dtype=BF16, device=dev) for _ in range(3))
+    for got, want, name in zip(ops.attn_bwd_rows(x, dO, out, lse, first_rows=P, out=outs), full_sep, ("dq", "dk", "dv")):
+        assert torch.equal(got[:, :, :n], want[:, :, :n]), f"{name}: the written rows"
+        assert bool((got[:, :, n:] == SENTINEL).all()), f"{name}: {int((got[:, :, n:] != SENTINEL).sum())} elements written at positions >= {n}"
 
 
 def test_rotary_merge_bwd(dev):
@@ -588,6 +700,10 @@ def test_transpose_colsum(dev, R, C):
     assert bool((xt[:, R:] == 0).all())
     ref = 0.5 + x.float().sum(0)
     assert float((acc - ref).abs().max()) <= 1e-3 * float(ref.abs().max()) + 1e-3
+    # per element, the bound of test_colsum: R terms and the start value added in fp32 in any order (tile partials, wave
+    # reductions, the atomic onto what is there), relative to the magnitude sum
+    s, m = 0.5 + x.double().sum(0), 0.5 + x.double().abs().sum(0)
+    kcmp.assert_elementwise(acc, s, kcmp.rounded(s, kcmp.gamma(R + 9) * m, torch.float32), f"transpose_colsum R={R} C={C}")
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
