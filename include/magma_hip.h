@@ -100,8 +100,9 @@ const char* mg_version(void);
  *  17  constrained decoding: added mg_logits_process_constrained_f32 (nothing moved).
  *  18  classifier-free guidance: added mg_logits_guidance_f32 and mg_guidance_follow (nothing moved).
  *  19  ranking choices: added mg_attn_prefill_tree_bf16, mg_rotary_split_at_bf16 and mg_token_logprobs_rows_f32 (nothing moved).
- *  20  explaining answers: added mg_attn_prefill_scaled_bf16 (nothing moved). */
-#define MG_ABI_VERSION 20
+ *  20  explaining answers: added mg_attn_prefill_scaled_bf16 (nothing moved).
+ *  21  diverse beam search: added mg_beam_finish_groups (nothing moved). */
+#define MG_ABI_VERSION 21
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -459,7 +460,8 @@ int mg_sample_finish_rows(int64_t* token, int32_t B, int32_t* state, int32_t* d_
 /* Beam search (transformers' GenerationMixin._beam_search, do_sample=False, one eos id; DESIGN.md "Beam search"): three
  * enqueue-only, graph-capturable launches per token step over R = B * k rows (k = num_beams <= 16, rows sample-major).
  * mg_beam_topk_f32: per row, the top K2 = 2k candidate scores run[row] + log_softmax(logits[row]) in the order (score
- *   descending, lower token first) -> cand_score [R, K2] fp32, cand_tok [R, K2] int32.  Needs 2 <= K2 <= min(32, V).
+ *   descending, lower token first) -> cand_score [R, K2] fp32, cand_tok [R, K2] int32.  Needs 2 <= K2 <= min(32, V)
+ *   (diverse beam search asks for K2 = k + k / G).
  * mg_beam_finish: per sample, the top 2k of the k*V candidates (merge of its rows' lists by score descending, then lower flat
  *   index beam*V + token), then the finish / next-beam / early-stop rules: candidates among the first k that end in eos (or
  *   reach max_steps) finish with score sum / gen_len^length_penalty and merge into the k finished slots; the best k that do not
@@ -481,7 +483,7 @@ typedef struct mg_beam_state {
   int64_t* hist;        /* [R, ld] token history of the running beams                                           */
   int64_t* hist_stage;  /* [R, ld] staging copy                                                                 */
   int64_t ld;           /* columns of the four token buffers                                                    */
-  int32_t* unsat;       /* [B] the early-stop heuristic still allows an improvement (latched)                   */
+  int32_t* unsat;       /* [B] ([B * G] with groups) the early-stop heuristic still allows an improvement (latched) */
   int32_t* parent;      /* [R] out: the row each new running row continues                                      */
   int64_t* token;       /* [R] out: the new last token of each running row                                      */
 } mg_beam_state;
@@ -490,6 +492,21 @@ int mg_beam_topk_f32(const float* logits, int64_t ld, int32_t R, int32_t V, cons
 int mg_beam_finish(const float* cand_score, const int32_t* cand_tok, int32_t B, int32_t k, int32_t V, int64_t eos,
                    double length_penalty, int32_t early_stopping, int32_t max_steps, int32_t* state, int32_t* d_pos,
                    int32_t pos_stride, const mg_beam_state* bs, void* stream);
+/* Diverse beam search (ABI 21; Vijayakumar et al. 2018; DESIGN.md "Diverse beam search"; host statement: magma_amd/sampling.py,
+ * group_beam_search): mg_beam_finish for k beams in G groups of k' = k / G (rows sample-major, then group-major: row
+ * b*k + g*k' + q).  A group is a sample of k' beams in every rule above: its own running scores, k' finished slots and
+ * early-stop latch (unsat has B*G entries, index b*G + g); the stop of the call is mg_beam_finish's over the B*G groups.  Within a
+ * step the groups of a sample are handled in the order g = 0 .. G-1, and group g's candidate scores are
+ * cand_score - diversity_penalty * n_t in fp32 (one rounded product, one rounded subtraction, no fma), n_t = the number of running
+ * beams of groups 0 .. g-1 of that sample whose token selected at this step is t; -inf stays -inf.  cand_score / cand_tok
+ * [R, K2] are mg_beam_topk_f32's (or mg_beam_topk_scores_f32's) lists of length K2 = k + k' -- at most k - k' tokens are
+ * penalised, so no token outside a row's unpenalised top k + k' reaches the group's top 2k' -- or 2k at G = 1, where the call
+ * writes what mg_beam_finish writes, bit for bit.  One workgroup, the device code of mg_beam_finish.
+ * Needs 1 <= G <= k, k % G == 0, K2 as above, k' * K2 <= 512, V >= K2, diversity_penalty finite and >= 0.                  */
+int mg_beam_finish_groups(const float* cand_score, const int32_t* cand_tok, int32_t B, int32_t k, int32_t G, int32_t K2,
+                          float diversity_penalty, int32_t V, int64_t eos, double length_penalty, int32_t early_stopping,
+                          int32_t max_steps, int32_t* state, int32_t* d_pos, int32_t pos_stride, const mg_beam_state* bs,
+                          void* stream);
 int mg_kv_reorder_bf16(mg_bf16* kcache, mg_bf16* vcache, mg_bf16* kstage, mg_bf16* vstage, int32_t L, int32_t R, int32_t H,
                        int32_t Smax, const int32_t* parent, const int32_t* d_pos, int32_t pos_stride, void* stream);
 

@@ -521,6 +521,9 @@ extern "C" int mg_sample_finish_rows(int64_t* token, int32_t B, int32_t* state, 
 //   beam_finish_kernel  one workgroup: per sample, the merge of the k lists by (score desc, flat index beam*V + token asc), the
 //                       finish / next-beam / early-stop rules, the parent map, the token histories gathered by parent, the
 //                       finished hypotheses, the fed-back token, d_pos and the "first step at which generation stops" record.
+//                       beam_finish_groups_kernel (DESIGN.md "Diverse beam search") is the same body walking the G groups of
+//                       every sample as samples of k / G beams, a group's candidates penalised for the tokens that the
+//                       sample's earlier groups selected at this step; its rows' lists are k + k / G long.
 //   kv_reorder_kernel   K / V positions [0, d_pos_b) of row parent[b] into row b, every layer, in two launches: rows that are
 //                       read by another row AND are themselves overwritten are staged first; identity rows are skipped.
 namespace {
@@ -923,23 +926,47 @@ struct BeamArgs {
   int B, k, K2, V; int64_t eos; double length_penalty; int early_stopping; int max_steps;
   int32_t* state; int32_t* d_pos; int n_pos;
   mg_beam_state s;
+  int G; float diversity;     // grouped instance only: num_beam_groups and lambda; K2 is then the per-row list length k + k / G
 };
 
 MG_DEV bool key_before(uint32_t ka, int ia, uint32_t kb, int ib) { return ka > kb || (ka == kb && ia < ib); }
 
-__global__ __launch_bounds__(512) void beam_finish_kernel(const BeamArgs a) {
+// Diverse beam search: a candidate's score less lambda times the number n of running beams of the sample's earlier groups that
+// selected its token at this step -- one rounded product, one rounded subtraction, never contracted into an fma (the host
+// statement, sampling.group_beam_search, rounds twice)
+MG_DEV float diversity_score(float score, float lambda, int n) {
+#pragma clang fp contract(off)
+  const float pen = lambda * (float)n;
+  return score - pen;
+}
+
+// ONE body for beam search and diverse beam search (DESIGN.md "Diverse beam search").  A group is a pseudo-sample of kq = k / G
+// beams: pseudo-sample ps = smp * G + g owns rows [r0, r0 + kq), r0 = smp * k + g * kq, its own finished slots, its own unsat
+// latch.  !GROUPED is G = 1 (kq = k, lists of 2k entries read from global memory as they are): beam_finish_kernel as it was.
+// GROUPED: the kq lists of KL = k + kq entries are first penalised into LDS against the tokens that the sample's groups 0 .. g-1
+// selected at this step (prev_tok), then merged to the top 2kq like any sample's.
+template <bool GROUPED>
+MG_DEV void beam_finish_body(const BeamArgs& a) {
   __shared__ int s_step, s_stopped;
   __shared__ float t_score[BK2_MAX];
   __shared__ int t_beam[BK2_MAX], t_tok[BK2_MAX];
-  __shared__ int r_sel[BK_MAX];           // running row q of this sample continues top candidate r_sel[q]
+  __shared__ int r_sel[BK_MAX];           // running row q of this (pseudo-)sample continues top candidate r_sel[q]
   __shared__ int f_src[BK_MAX];           // finished slot q: old slot f_src[q] (>= 0) or top candidate -(f_src[q] + 1)
   __shared__ int g_unsat, g_allfin, g_allhit;
   // thread 0's working set (LDS, not private arrays: dynamically indexed private arrays would live in scratch)
   __shared__ bool hit[BK2_MAX], fl[BK_MAX + BK2_MAX];
   __shared__ float mod[BK2_MAX], val[BK_MAX + BK2_MAX];
   __shared__ int pick[BK_MAX], olen[BK_MAX];
+  // GROUPED: the group's penalised candidates and the tokens the sample's earlier groups selected at this step
+  __shared__ float p_score[GROUPED ? 512 : 1];
+  __shared__ int p_flat[GROUPED ? 512 : 1], p_tok[GROUPED ? 512 : 1];
+  __shared__ int prev_tok[BK_MAX];
   const int tid = threadIdx.x, nt = blockDim.x;
-  const int k = a.k, K2 = a.K2, R = a.B * a.k;
+  const int R = a.B * a.k;
+  const int G = GROUPED ? a.G : 1;
+  const int k = GROUPED ? a.k / G : a.k;          // beams of a (pseudo-)sample
+  const int K2 = 2 * k;                           // its top list
+  const int KL = GROUPED ? a.K2 : K2;             // entries of a row's candidate list
   const int64_t ld = a.s.ld;
   if (tid == 0) { s_step = a.state[0]; s_stopped = a.state[1] >= 0; g_unsat = 0; g_allfin = 1; g_allhit = 1; }
   __syncthreads();
@@ -962,19 +989,35 @@ __global__ __launch_bounds__(512) void beam_finish_kernel(const BeamArgs a) {
   __syncthreads();
   const int gen_len = step + 1;
   const float den = (float)pow((double)gen_len, a.length_penalty);
-  for (int smp = 0; smp < a.B; ++smp) {
-    const int r0 = smp * k;
-    // ---- top 2k of the sample's k*V candidates: merge of the per-row lists ----
-    if (tid < k * K2) {
-      const int bm = tid / K2;
-      const float sc = a.cand_score[(int64_t)r0 * K2 + tid];
-      const int tok = a.cand_tok[(int64_t)r0 * K2 + tid];
+  for (int smp = 0; smp < a.B * G; ++smp) {
+    const int g = GROUPED ? smp % G : 0;
+    const int r0 = GROUPED ? (smp / G) * a.k + g * k : smp * k;
+    // ---- top 2k of the (pseudo-)sample's k*V candidates: merge of the per-row lists ----
+    if constexpr (GROUPED) {
+      if (tid < k * KL) {
+        const int tok = a.cand_tok[(int64_t)r0 * KL + tid];
+        int n = 0;
+        for (int u = 0; u < g * k; ++u) n += prev_tok[u] == tok ? 1 : 0;
+        p_score[tid] = diversity_score(a.cand_score[(int64_t)r0 * KL + tid], a.diversity, n);
+        p_tok[tid] = tok;
+        p_flat[tid] = (tid / KL) * a.V + tok;
+      }
+      __syncthreads();
+    }
+    if (tid < k * KL) {
+      const int bm = tid / KL;
+      float sc; int tok;
+      if constexpr (GROUPED) { sc = p_score[tid]; tok = p_tok[tid]; }
+      else { sc = a.cand_score[(int64_t)r0 * KL + tid]; tok = a.cand_tok[(int64_t)r0 * KL + tid]; }
       const uint32_t kk = fkey(sc);
       const int flat = bm * a.V + tok;
       int rank = 0;
-      for (int u = 0; u < k * K2; ++u) {
-        const int bu = u / K2;
-        rank += key_before(fkey(a.cand_score[(int64_t)r0 * K2 + u]), bu * a.V + a.cand_tok[(int64_t)r0 * K2 + u], kk, flat) ? 1 : 0;
+      for (int u = 0; u < k * KL; ++u) {
+        if constexpr (GROUPED) rank += key_before(fkey(p_score[u]), p_flat[u], kk, flat) ? 1 : 0;
+        else {
+          const int bu = u / KL;
+          rank += key_before(fkey(a.cand_score[(int64_t)r0 * KL + u]), bu * a.V + a.cand_tok[(int64_t)r0 * KL + u], kk, flat) ? 1 : 0;
+        }
       }
       if (rank < K2) { t_score[rank] = sc; t_beam[rank] = bm; t_tok[rank] = tok; }
     }
@@ -994,6 +1037,7 @@ __global__ __launch_bounds__(512) void beam_finish_kernel(const BeamArgs a) {
         a.s.run[r0 + q] = mod[j];
         a.s.parent[r0 + q] = r0 + t_beam[j];
         a.s.token[r0 + q] = t_tok[j];
+        if constexpr (GROUPED) prev_tok[g * k + q] = t_tok[j];
       }
       // finished slots: merge the old k with the first k candidates that just finished
       bool full = true;
@@ -1070,6 +1114,9 @@ __global__ __launch_bounds__(512) void beam_finish_kernel(const BeamArgs a) {
     a.state[0] = step + 1;
   }
 }
+
+__global__ __launch_bounds__(512) void beam_finish_kernel(const BeamArgs a) { beam_finish_body<false>(a); }
+__global__ __launch_bounds__(512) void beam_finish_groups_kernel(const BeamArgs a) { beam_finish_body<true>(a); }
 
 // grid (H, R, L); phase 0 stages the rows that must be (their own d_pos positions), phase 1 copies every non-identity row b
 // from its parent p: positions [0, d_pos_p) -- what was staged of p, and in beam search d_pos_p == d_pos_b (same sample)
@@ -1229,8 +1276,35 @@ extern "C" int mg_beam_finish(const float* cand_score, const int32_t* cand_tok, 
       !s.unsat || !s.parent || !s.token || s.ld < 1)
     MG_FAIL(MG_ERR_SHAPE, "mg_beam_finish: a beam-state buffer is missing");
   BeamArgs a{cand_score, cand_tok, B, k, 2 * k, V, eos, length_penalty, early_stopping, max_steps, state, d_pos,
-             pos_stride ? B * k : 1, s};
+             pos_stride ? B * k : 1, s, 1, 0.f};
   hipLaunchKernelGGL(beam_finish_kernel, dim3(1), dim3(512), 0, (hipStream_t)stream, a);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_beam_finish_groups(const float* cand_score, const int32_t* cand_tok, int32_t B, int32_t k, int32_t G, int32_t K2,
+                                     float diversity_penalty, int32_t V, int64_t eos, double length_penalty,
+                                     int32_t early_stopping, int32_t max_steps, int32_t* state, int32_t* d_pos, int32_t pos_stride,
+                                     const mg_beam_state* bs, void* stream) {
+  if (!cand_score || !cand_tok || !state || !bs || B <= 0 || k < 1 || k > BK_MAX || max_steps < 1)
+    MG_FAIL(MG_ERR_SHAPE, "mg_beam_finish_groups: bad arguments (B %d, k %d, max_steps %d)", B, k, max_steps);
+  if (G < 1 || G > k || k % G != 0) MG_FAIL(MG_ERR_SHAPE, "mg_beam_finish_groups: G = %d must lie in [1, k] and divide k = %d", G, k);
+  const int kq = k / G;
+  if (G > 1 ? K2 != k + kq : K2 != 2 * k)
+    MG_FAIL(MG_ERR_SHAPE, "mg_beam_finish_groups: K2 must be k + k / G = %d (2k at G = 1), got %d", G > 1 ? k + kq : 2 * k, K2);
+  if (K2 > BK2_MAX || kq * K2 > 512 || V < K2)
+    MG_FAIL(MG_ERR_SHAPE, "mg_beam_finish_groups: need K2 <= min(%d, V) and (k / G) * K2 <= 512 (K2 %d, V %d)", BK2_MAX, K2, V);
+  if (!(diversity_penalty >= 0.f) || diversity_penalty == INFINITY)      // (NaN fails the first test)
+    MG_FAIL(MG_ERR_SHAPE, "mg_beam_finish_groups: diversity_penalty must be finite and >= 0");
+  if (early_stopping < 0 || early_stopping > 2) MG_FAIL(MG_ERR_SHAPE, "mg_beam_finish_groups: early_stopping must be 0, 1 or 2");
+  if (pos_stride != 0 && pos_stride != 1) MG_FAIL(MG_ERR_SHAPE, "mg_beam_finish_groups: pos_stride must be 0 or 1");
+  const mg_beam_state& s = *bs;
+  if (!s.run || !s.fin_score || !s.fin_flag || !s.fin_len || !s.fin_tok || !s.fin_stage || !s.hist || !s.hist_stage ||
+      !s.unsat || !s.parent || !s.token || s.ld < 1)
+    MG_FAIL(MG_ERR_SHAPE, "mg_beam_finish_groups: a beam-state buffer is missing");
+  BeamArgs a{cand_score, cand_tok, B, k, K2, V, eos, length_penalty, early_stopping, max_steps, state, d_pos,
+             pos_stride ? B * k : 1, s, G, diversity_penalty};
+  hipLaunchKernelGGL(beam_finish_groups_kernel, dim3(1), dim3(512), 0, (hipStream_t)stream, a);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }

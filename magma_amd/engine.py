@@ -165,12 +165,15 @@ class KVCache:
 class BeamBuffers:
     """Device state of beam search over a KV cache of R = B * k rows (DESIGN.md "Beam search"): running scores, the k finished
     slots per sample (scores, flags, lengths, tokens), the early-stop latch per sample, the parent map and the per-row top-2k
-    candidates of a step, staging copies of the token rows, and K / V staging buffers for the cache reorder."""
+    candidates of a step, staging copies of the token rows, and K / V staging buffers for the cache reorder.  With G > 1 groups
+    (DESIGN.md "Diverse beam search") every group of k / G rows is a sample of its own: B * G latches, running scores
+    [0, -1e9, ...] per group, and candidate lists of k + k / G entries per row."""
 
-    def __init__(self, cache: KVCache, k: int, token: torch.Tensor):
+    def __init__(self, cache: KVCache, k: int, token: torch.Tensor, G: int = 1):
         R, dev = cache.B, cache.k.device
-        assert R % k == 0
-        self.k, self.B = k, R // k
+        assert R % k == 0 and k % G == 0
+        self.k, self.B, self.G = k, R // k, G
+        K2 = 2 * k if G == 1 else k + k // G
         f32, i32, i64 = torch.float32, torch.int32, torch.int64
         self.run = torch.zeros(R, dtype=f32, device=dev)
         self.fin_score = torch.zeros(R, dtype=f32, device=dev)
@@ -179,10 +182,10 @@ class BeamBuffers:
         self.fin_tok = torch.zeros(R, cache.Smax, dtype=i64, device=dev)
         self.fin_stage = torch.zeros(R, cache.Smax, dtype=i64, device=dev)
         self.hist_stage = torch.zeros(R, cache.Smax, dtype=i64, device=dev)
-        self.unsat = torch.ones(self.B, dtype=i32, device=dev)
+        self.unsat = torch.ones(self.B * G, dtype=i32, device=dev)
         self.parent = torch.arange(R, dtype=i32, device=dev)
-        self.cand_score = torch.zeros(R, 2 * k, dtype=f32, device=dev)
-        self.cand_tok = torch.zeros(R, 2 * k, dtype=i32, device=dev)
+        self.cand_score = torch.zeros(R, K2, dtype=f32, device=dev)
+        self.cand_tok = torch.zeros(R, K2, dtype=i32, device=dev)
         self.kstage, self.vstage = torch.empty_like(cache.k), torch.empty_like(cache.v)
         self.bufs = dict(run=self.run, fin_score=self.fin_score, fin_flag=self.fin_flag, fin_len=self.fin_len,
                          fin_tok=self.fin_tok, fin_stage=self.fin_stage, hist=cache.history, hist_stage=self.hist_stage,
@@ -190,7 +193,7 @@ class BeamBuffers:
 
     def reset(self, eos: int):
         """State at the start of a generate() call (enqueued, no sync)."""
-        self.run.view(self.B, self.k).fill_(-1e9)[:, 0] = 0.0
+        self.run.view(self.B * self.G, self.k // self.G).fill_(-1e9)[:, 0] = 0.0
         self.fin_score.fill_(-1e9)
         self.fin_flag.zero_()
         self.fin_len.zero_()
@@ -247,6 +250,11 @@ class SelectionPlan(NamedTuple):
         return isinstance(self.mode, tuple) and self.mode[:1] == ("beam",)
 
     @property
+    def beam_groups(self) -> tuple:
+        """(num_beam_groups, diversity_penalty) of a beam mode: (1, 0.0) for the five-entry tuple of plain beam search."""
+        return tuple(self.mode[5:7]) if len(self.mode) > 5 else (1, 0.0)
+
+    @property
     def rewrites_logits(self) -> bool:
         """Something runs in place on the logits in front of the selection: the first token is then selected from a copy (the
         caller's ``.logits`` stay raw), and a step that also reports log-probabilities works on the second logits buffer."""
@@ -288,7 +296,8 @@ class SelectionPlan(NamedTuple):
         buffers and -- when something rewrites the logits too -- the second logits buffer are allocated.  ``first``: the call
         that starts a loop marks every row unfinished; a later step finds the cache armed or refuses."""
         dev, V = cache.k.device, self.vocab if self.vocab is not None else float("inf")
-        if self.is_beam and not first and (cache.beam is None or cache.beam.k != self.mode[1]):
+        armed = cache.beam is not None and (cache.beam.k, cache.beam.G) == (self.mode[1], self.beam_groups[0]) if self.is_beam else True
+        if not first and not armed:
             raise ValueError("beam decoding needs a cache armed for this num_beams (prefill with eos_token= and beam=)")
         if self.proc is not None:
             ids = self.proc[3]
@@ -726,7 +735,8 @@ class LMEngine:
                 stop=None, logprobs=None, constraint=None, guidance=None, plan=None) -> LMOutput:
         """``plan`` (a SelectionPlan): selection_plan's checked form of the seven selection keywords that follow, INSTEAD of them.
         ``beam`` = (num_beams, length_penalty, early_stopping, max_steps): beam-search token selection (the rows are
-        samples x num_beams, sample-major; DESIGN.md "Beam search") instead of ``sampling``.
+        samples x num_beams, sample-major; DESIGN.md "Beam search") instead of ``sampling``.  Followed by (num_beam_groups > 1,
+        diversity_penalty): diverse beam search (rows sample-major, then group-major; DESIGN.md "Diverse beam search").
         ``processors`` (sampling.check_processor_args' dict, or None): the logits processors in front of whichever selection
         runs (DESIGN.md "Logits processors").  The first token is selected from a processed COPY of the prefill / extend
         logits (``.logits`` stays raw); a cached step processes its logits in place (see decode).
@@ -1237,44 +1247,63 @@ class LMEngine:
 
     @staticmethod
     def beam_mode(beam):
-        """("beam", num_beams, length_penalty, early_stopping, max_steps): the token-selection mode (and graph key) of beam search."""
+        """("beam", num_beams, length_penalty, early_stopping, max_steps): the token-selection mode (and graph key) of beam search,
+        from those four values -- or, followed by (num_beam_groups, diversity_penalty) with more than one group, the seven-entry
+        mode of diverse beam search: G and the penalty are launch arguments.  One group gives the five-entry tuple as it was."""
         from .sampling import check_beam_args
-        k, lp, es, n = beam
-        es = check_beam_args(int(k), 1, es)
-        return ("beam", int(k), float(lp), es, int(n))
+        k, lp, es, n = beam[:4]
+        G, lam = beam[4:] if len(beam) > 4 else (1, 0.0)
+        es = check_beam_args(int(k), 1, es, G, lam)
+        mode = ("beam", int(k), float(lp), es, int(n))
+        return mode if G == 1 else mode + (int(G), float(lam))
 
     def _arm_beam(self, cache: KVCache, st, mode):
-        """Beam buffers of this cache for num_beams = k of the beam ``mode`` (re-allocated -- and the captured steps dropped --
-        when k changes), reset for a new generate() call."""
-        k = mode[1]
+        """Beam buffers of this cache for num_beams = k (in G groups) of the beam ``mode`` (re-allocated -- and the captured steps
+        dropped -- when (k, G) changes), reset for a new generate() call."""
+        k, G = mode[1], mode[5] if len(mode) > 5 else 1
         if cache.B % k:
             raise ValueError(f"beam search over {cache.B} cache rows with num_beams = {k}: rows must be samples x num_beams")
-        if 2 * k > self.V:
-            raise ValueError(f"num_beams = {k} needs a vocabulary of at least {2 * k} tokens")
-        if cache.beam is None or cache.beam.k != k:
-            cache.beam = BeamBuffers(cache, k, st.token)
+        need = 2 * k if G == 1 else k + k // G            # the length of a row's candidate list
+        if need > self.V:
+            raise ValueError(f"num_beams = {k}{'' if G == 1 else f' in {G} groups'} needs a vocabulary of at least {need} tokens")
+        if cache.beam is None or (cache.beam.k, cache.beam.G) != (k, G):
+            cache.beam = BeamBuffers(cache, k, st.token, G)
             st.graphs.clear()
         cache.beam.reset(cache.eos)
 
     def _select_beam(self, logits: torch.Tensor, cache: KVCache, plan: SelectionPlan, advance: bool):
         """The beam step's three launches: per-row top 2k, the bookkeeping of every sample, the K / V reorder by parent.  With
-        processors, their launch has already turned the rows into (processed) log_softmax scores."""
+        processors, their launch has already turned the rows into (processed) log_softmax scores.  With G > 1 groups the lists
+        are k + k / G long (bm.cand_score's width) and the bookkeeping launch is the grouped one; nothing else differs."""
         bm = cache.beam
-        _, k, lp, es, max_steps = plan.mode
+        _, k, lp, es, max_steps = plan.mode[:5]
+        G, lam = plan.beam_groups
         ops.beam_topk(logits, bm.run, bm.cand_score, bm.cand_tok, normalized=plan.proc is not None)
-        ops.beam_finish(bm.cand_score, bm.cand_tok, bm.B, k, logits.shape[1], cache.eos, lp, es, max_steps, cache.sample_state,
-                        bm.bufs, d_pos=cache.d_pos if advance else None, pos_stride=cache.pos_stride)
+        pos = dict(d_pos=cache.d_pos if advance else None, pos_stride=cache.pos_stride)
+        if G == 1:
+            ops.beam_finish(bm.cand_score, bm.cand_tok, bm.B, k, logits.shape[1], cache.eos, lp, es, max_steps, cache.sample_state,
+                            bm.bufs, **pos)
+        else:
+            ops.beam_finish_groups(bm.cand_score, bm.cand_tok, bm.B, k, G, lam, logits.shape[1], cache.eos, lp, es, max_steps,
+                                   cache.sample_state, bm.bufs, **pos)
         ops.kv_reorder(cache.k, cache.v, bm.kstage, bm.vstage, bm.parent, cache.d_pos, pos_stride=cache.pos_stride)
         return bm.bufs["token"]
 
     def beam_results(self, cache: KVCache, n_ret: int):
         """(tokens (B*n_ret, n) int64 eos-padded, scores (B*n_ret,) fp32, lengths (B*n_ret,) int64) of the best n_ret finished
-        hypotheses per sample (slots are kept in score order); n = the longest of them.  One host sync."""
+        hypotheses per sample (slots are kept in score order); n = the longest of them.  One host sync.  With groups: the
+        first n_ret of the sample's slots taken round-robin over the groups by rank within the group (DESIGN.md "Diverse beam
+        search")."""
         bm = cache.beam
-        lens = bm.fin_len.view(bm.B, bm.k)[:, :n_ret].reshape(-1).to(torch.int64)
+
+        def slots(t):       # (B, k, ...) in the order the hypotheses are returned in
+            t = t.view(bm.B, bm.G, bm.k // bm.G, *t.shape[1:])
+            return (t.transpose(1, 2) if bm.G > 1 else t).reshape(bm.B, bm.k, *t.shape[3:])
+
+        lens = slots(bm.fin_len)[:, :n_ret].reshape(-1).to(torch.int64)
         n = max(1, int(lens.max()))
-        toks = bm.fin_tok.view(bm.B, bm.k, -1)[:, :n_ret, :n].reshape(bm.B * n_ret, n)
-        return toks.clone(), bm.fin_score.view(bm.B, bm.k)[:, :n_ret].reshape(-1).clone(), lens
+        toks = slots(bm.fin_tok)[:, :n_ret, :n].reshape(bm.B * n_ret, n)
+        return toks.clone(), slots(bm.fin_score)[:, :n_ret].reshape(-1).clone(), lens
 
     def select_token(self, logits: torch.Tensor, cache: KVCache, plan: SelectionPlan, out: Optional[torch.Tensor] = None,
                      advance: bool = False, raw: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -964,18 +964,16 @@ def token_logprobs_rows(logits: torch.Tensor, row_of: torch.Tensor, token: torch
 EARLY_STOPPING_CODES = {False: 0, True: 1, "never": 2}
 
 
-def beam_finish(cand_score: torch.Tensor, cand_tok: torch.Tensor, B: int, k: int, V: int, eos: int, length_penalty: float,
-                early_stopping, max_steps: int, state: torch.Tensor, bufs: dict, d_pos: Optional[torch.Tensor] = None,
-                pos_stride: int = 0):
-    """Beam bookkeeping of one token step (mg_beam_finish).  ``bufs``: run, fin_score, fin_flag, fin_len, fin_tok, fin_stage,
-    hist, hist_stage, unsat, parent, token (BeamBuffers.as_dict())."""
+def _beam_state(cand_score, cand_tok, B, k, G, K2, state, bufs, d_pos, pos_stride):
+    """The checked buffers of a beam bookkeeping launch as (mg_beam_state, pos_stride): beam_finish's (G = 1) and
+    beam_finish_groups' share of the work."""
     R = B * k
     _need_gpu(cand_score, cand_tok, state, d_pos, *bufs.values())
-    assert cand_score.shape == (R, 2 * k) and cand_tok.shape == (R, 2 * k)
-    es = EARLY_STOPPING_CODES[early_stopping]
+    assert cand_score.shape == (R, K2) and cand_tok.shape == (R, K2)
+    assert cand_score.dtype == torch.float32 and cand_tok.dtype == torch.int32 and cand_score.is_contiguous() and cand_tok.is_contiguous()
     ps = 0 if d_pos is None else _pos_stride(d_pos, R, pos_stride)
     f32, i32, i64 = torch.float32, torch.int32, torch.int64
-    for name, dt, n in (("run", f32, R), ("fin_score", f32, R), ("fin_flag", i32, R), ("fin_len", i32, R), ("unsat", i32, B),
+    for name, dt, n in (("run", f32, R), ("fin_score", f32, R), ("fin_flag", i32, R), ("fin_len", i32, R), ("unsat", i32, B * G),
                         ("parent", i32, R), ("token", i64, R)):
         t = bufs[name]
         assert t.dtype == dt and t.is_contiguous() and t.numel() == n, name
@@ -987,8 +985,34 @@ def beam_finish(cand_score: torch.Tensor, cand_tok: torch.Tensor, B: int, k: int
     bs = L.BeamState(*(bufs[n].data_ptr() for n in ("run", "fin_score", "fin_flag", "fin_len", "fin_tok", "fin_stage", "hist",
                                                     "hist_stage")), ld, bufs["unsat"].data_ptr(), bufs["parent"].data_ptr(),
                      bufs["token"].data_ptr())
+    return bs, ps
+
+
+def beam_finish(cand_score: torch.Tensor, cand_tok: torch.Tensor, B: int, k: int, V: int, eos: int, length_penalty: float,
+                early_stopping, max_steps: int, state: torch.Tensor, bufs: dict, d_pos: Optional[torch.Tensor] = None,
+                pos_stride: int = 0):
+    """Beam bookkeeping of one token step (mg_beam_finish).  ``bufs``: run, fin_score, fin_flag, fin_len, fin_tok, fin_stage,
+    hist, hist_stage, unsat, parent, token (BeamBuffers.as_dict())."""
+    bs, ps = _beam_state(cand_score, cand_tok, B, k, 1, 2 * k, state, bufs, d_pos, pos_stride)
+    es = EARLY_STOPPING_CODES[early_stopping]
     check(L.load().mg_beam_finish(cand_score.data_ptr(), cand_tok.data_ptr(), B, k, V, int(eos), float(length_penalty), es,
                                   int(max_steps), state.data_ptr(), _p(d_pos), ps, C.byref(bs), _stream()), "mg_beam_finish")
+
+
+def beam_finish_groups(cand_score: torch.Tensor, cand_tok: torch.Tensor, B: int, k: int, G: int, diversity_penalty: float, V: int,
+                       eos: int, length_penalty: float, early_stopping, max_steps: int, state: torch.Tensor, bufs: dict,
+                       d_pos: Optional[torch.Tensor] = None, pos_stride: int = 0):
+    """Bookkeeping of one token step of diverse beam search (mg_beam_finish_groups): beam_finish over k beams in ``G`` groups
+    of k / G, group g's candidates less ``diversity_penalty`` times the number of earlier groups' beams that selected their token
+    at this step.  The candidate lists hold K2 = cand_score.shape[1] entries per row: k + k / G (2k at G = 1, where the call
+    writes what beam_finish writes); ``bufs`` as for beam_finish, with B * G entries in ``unsat``."""
+    if G < 1 or k % G:
+        raise ValueError(f"num_beam_groups = {G} must divide num_beams = {k}")
+    bs, ps = _beam_state(cand_score, cand_tok, B, k, G, cand_score.shape[1], state, bufs, d_pos, pos_stride)
+    es = EARLY_STOPPING_CODES[early_stopping]
+    check(L.load().mg_beam_finish_groups(cand_score.data_ptr(), cand_tok.data_ptr(), B, k, G, cand_score.shape[1],
+                                         float(diversity_penalty), V, int(eos), float(length_penalty), es, int(max_steps),
+                                         state.data_ptr(), _p(d_pos), ps, C.byref(bs), _stream()), "mg_beam_finish_groups")
 
 
 def kv_reorder(kcache: torch.Tensor, vcache: torch.Tensor, kstage: torch.Tensor, vstage: torch.Tensor, parent: torch.Tensor,

@@ -794,7 +794,27 @@ def mask_logprobs(tokens, lp, top_ids, top_lp, count) -> TokenLogprobs:
 MAX_BEAMS = 16
 
 
-def check_beam_args(num_beams: int, num_return_sequences: int, early_stopping):
+def check_group_args(num_beams: int, num_beam_groups=1, diversity_penalty=0.0, vocab: int = None):
+    """ValueError for group arguments diverse beam search does not take (num_beams already checked); returns
+    (num_beam_groups, diversity_penalty as a float)."""
+    G = num_beam_groups
+    if isinstance(G, bool) or not isinstance(G, int) or G < 1:
+        raise ValueError(f"num_beam_groups must be an integer >= 1, got {G!r}")
+    if num_beams % G:
+        raise ValueError(f"num_beam_groups must divide num_beams = {num_beams}, got {G}")
+    lam = diversity_penalty
+    if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not math.isfinite(lam) or lam < 0:
+        raise ValueError(f"diversity_penalty must be a finite number >= 0, got {lam!r}")
+    if G == 1 and lam != 0:
+        raise ValueError(f"diversity_penalty = {lam} needs num_beam_groups > 1: one group is never penalised")
+    if vocab is not None and G > 1 and vocab < num_beams + num_beams // G:
+        raise ValueError(f"num_beams = {num_beams} in {G} groups needs a vocabulary of at least {num_beams + num_beams // G} "
+                         f"tokens, got {vocab}")
+    return G, float(lam)
+
+
+def check_beam_args(num_beams: int, num_return_sequences: int, early_stopping, num_beam_groups=1, diversity_penalty=0.0,
+                    vocab: int = None):
     """ValueError for arguments beam search does not take; returns early_stopping normalised to True / False / "never"."""
     if not isinstance(num_beams, int) or num_beams < 1:
         raise ValueError(f"num_beams must be an integer >= 1, got {num_beams!r}")
@@ -802,6 +822,7 @@ def check_beam_args(num_beams: int, num_return_sequences: int, early_stopping):
         raise ValueError(f"num_beams must be at most {MAX_BEAMS}, got {num_beams}")
     if not isinstance(num_return_sequences, int) or num_return_sequences < 1 or num_return_sequences > num_beams:
         raise ValueError(f"num_return_sequences must lie in [1, num_beams = {num_beams}], got {num_return_sequences!r}")
+    check_group_args(num_beams, num_beam_groups, diversity_penalty, vocab)
     if isinstance(early_stopping, str):
         if early_stopping != "never":
             raise ValueError(f"early_stopping must be True, False or 'never', got {early_stopping!r}")
@@ -822,6 +843,69 @@ def reorder_past(past, rows: torch.Tensor):
     if torch.is_tensor(past):
         return past.index_select(0, rows.to(past.device))
     raise TypeError(f"cannot reorder a cache of type {type(past).__name__} for beam search")
+
+
+class _BeamState:
+    """The state of P (pseudo-)samples of k beams each in beam_search's rule: running scores (starting at [0, -1e9, ...]), the
+    running and the finished token rows, the k finished slots and the early-stop latch."""
+
+    def __init__(self, P: int, k: int, max_steps: int, eos_token: int):
+        self.run = torch.zeros(P, k)
+        self.run[:, 1:] = -1e9
+        self.fin_score = torch.full((P, k), -1e9)
+        self.fin_flag = torch.zeros(P, k, dtype=torch.bool)
+        self.fin_len = torch.zeros(P, k, dtype=torch.int64)
+        self.seq = torch.full((P, k, max_steps), eos_token, dtype=torch.int64)
+        self.fin_seq = self.seq.clone()
+        self.unsat = torch.ones(P, 1, dtype=torch.bool)
+
+
+def _beam_rule(st: _BeamState, flat, t: int, V: int, max_steps: int, eos_token: int, length_penalty: float, early_stopping,
+               record: list = None, extra: Callable = None, ties_by_index: bool = False):
+    """One step of beam search's rule over ``st``'s P (pseudo-)samples of k beams, from their candidate scores ``flat``
+    (P, k*V) fp32: the per-step arithmetic beam_search and group_beam_search share.  Advances ``st`` in place and returns
+    (parent (P, k) -- the beam, within its sample, that each new running beam continues --, hits (P, 2k) -- which of the top
+    candidates met a stopping criterion).  ``extra(top_s, beam, tok, nxt)``: further entries of the step's ``record`` dict.
+    ``ties_by_index``: running beams of equal score are taken in candidate order, as the device takes them -- at the last step
+    every candidate finishes and all of them round to -1e9, so the "running" beams are then the k best candidates.  Nothing
+    reads them in beam search; in diverse beam search the later groups' penalty does."""
+    P, k = st.run.shape
+    K2 = 2 * k
+    top_mask = torch.arange(K2) < k
+    top_s, top_i = torch.topk(flat, K2)
+    beam, tok = top_i // V, top_i % V
+    cand_seq = torch.take_along_dim(st.seq, beam[:, :, None], dim=1)
+    cand_seq[:, :, t] = tok
+    hits = (tok == eos_token) | (t + 1 >= max_steps)
+    # running beams: the best k that did not finish
+    mod = top_s + hits.to(torch.float32) * -1.0e9
+    nxt = torch.sort(mod, dim=1, descending=True, stable=True)[1][:, :k] if ties_by_index else torch.topk(mod, k)[1]
+    st.seq = torch.take_along_dim(cand_seq, nxt[:, :, None], dim=1)
+    st.run = torch.take_along_dim(mod, nxt, dim=1)
+    parent = torch.take_along_dim(beam, nxt, dim=1)
+    # finished slots
+    just = hits & top_mask[None, :]
+    v = top_s / ((t + 1) ** length_penalty)
+    v += (torch.all(st.fin_flag, dim=-1, keepdim=True) & (early_stopping is True)).to(torch.float32) * -1.0e9
+    v += (~st.unsat).to(torch.float32) * -1.0e9
+    v += (~just) * -1.0e9
+    m_score = torch.cat((st.fin_score, v), dim=1)
+    pick = torch.topk(m_score, k)[1]
+    st.fin_seq = torch.take_along_dim(torch.cat((st.fin_seq, cand_seq), dim=1), pick[:, :, None], dim=1)
+    st.fin_score = torch.take_along_dim(m_score, pick, dim=1)
+    st.fin_flag = torch.take_along_dim(torch.cat((st.fin_flag, just), dim=1), pick, dim=1)
+    st.fin_len = torch.take_along_dim(torch.cat((st.fin_len, torch.full((P, K2), t + 1)), dim=1), pick, dim=1)
+    # early-stop heuristic (latched)
+    hyp = max_steps if (early_stopping == "never" and length_penalty > 0.0) else t + 1
+    best = st.run[:, :1] / (hyp ** length_penalty)
+    worst = torch.where(st.fin_flag, torch.min(st.fin_score, dim=1, keepdim=True)[0], -1.0e9)
+    if record is not None:
+        record.append(dict(top=torch.topk(flat, min(K2 + 1, k * V)).values, merged=m_score, best=best.clone(),
+                           worst=worst.clone(), unsat=st.unsat.clone(), finished=just.clone(),
+                           eos_outside=(tok[:, k:] == eos_token).clone(), step=t,
+                           **(extra(top_s, beam, tok, nxt) if extra is not None else {})))
+    st.unsat = st.unsat & torch.any(best > worst, dim=-1, keepdim=True)
+    return parent, hits
 
 
 @torch.no_grad()
@@ -854,65 +938,108 @@ def beam_search(step: Callable, batch_size: int, num_beams: int, max_steps: int,
     renormalising."""
     early_stopping = check_beam_args(num_beams, num_return_sequences, early_stopping)
     B, k = batch_size, num_beams
-    K2 = 2 * k
-    top_mask = torch.arange(K2) < k
-    run = torch.zeros(B, k)
-    run[:, 1:] = -1e9
-    fin_score = torch.full((B, k), -1e9)
-    fin_flag = torch.zeros(B, k, dtype=torch.bool)
-    fin_len = torch.zeros(B, k, dtype=torch.int64)
-    seq = torch.full((B, k, max_steps), eos_token, dtype=torch.int64)
-    fin_seq = seq.clone()
-    unsat = torch.ones(B, 1, dtype=torch.bool)
+    st = _BeamState(B, k, max_steps, eos_token)
     logits = step(None, None)
     for t in range(max_steps):
         V = logits.shape[-1]
         lp = F.log_softmax(logits.float().cpu(), dim=-1)
         if processors:
-            lp = process_logits(lp, seq.reshape(B * k, max_steps), t, eos_token=eos_token, **processors)
-        lp = lp.view(B, k, V) + run[:, :, None]
-        flat = lp.reshape(B, k * V)
-        top_s, top_i = torch.topk(flat, K2)
-        beam, tok = top_i // V, top_i % V
-        cand_seq = torch.take_along_dim(seq, beam[:, :, None], dim=1)
-        cand_seq[:, :, t] = tok
-        hits = (tok == eos_token) | (t + 1 >= max_steps)
-        # running beams: the best k that did not finish
-        mod = top_s + hits.to(torch.float32) * -1.0e9
-        nxt = torch.topk(mod, k)[1]
-        seq = torch.take_along_dim(cand_seq, nxt[:, :, None], dim=1)
-        run = torch.take_along_dim(mod, nxt, dim=1)
-        parent = torch.take_along_dim(beam, nxt, dim=1)
-        # finished slots
-        just = hits & top_mask[None, :]
-        v = top_s / ((t + 1) ** length_penalty)
-        v += (torch.all(fin_flag, dim=-1, keepdim=True) & (early_stopping is True)).to(torch.float32) * -1.0e9
-        v += (~unsat).to(torch.float32) * -1.0e9
-        v += (~just) * -1.0e9
-        m_score = torch.cat((fin_score, v), dim=1)
-        pick = torch.topk(m_score, k)[1]
-        fin_seq = torch.take_along_dim(torch.cat((fin_seq, cand_seq), dim=1), pick[:, :, None], dim=1)
-        fin_score = torch.take_along_dim(m_score, pick, dim=1)
-        fin_flag = torch.take_along_dim(torch.cat((fin_flag, just), dim=1), pick, dim=1)
-        fin_len = torch.take_along_dim(torch.cat((fin_len, torch.full((B, K2), t + 1)), dim=1), pick, dim=1)
-        # early-stop heuristic (latched), then the stop rule of the whole batch
-        hyp = max_steps if (early_stopping == "never" and length_penalty > 0.0) else t + 1
-        best = run[:, :1] / (hyp ** length_penalty)
-        worst = torch.where(fin_flag, torch.min(fin_score, dim=1, keepdim=True)[0], -1.0e9)
-        if record is not None:
-            record.append(dict(top=torch.topk(flat, min(K2 + 1, k * V)).values, merged=m_score, best=best.clone(),
-                               worst=worst.clone(), unsat=unsat.clone(), finished=just.clone(),
-                               eos_outside=(tok[:, k:] == eos_token).clone(), step=t))
-        unsat = unsat & torch.any(best > worst, dim=-1, keepdim=True)
-        go_on = bool(torch.any(unsat)) and not (bool(torch.all(fin_flag)) and early_stopping is True) and not bool(torch.all(hits))
+            lp = process_logits(lp, st.seq.reshape(B * k, max_steps), t, eos_token=eos_token, **processors)
+        lp = lp.view(B, k, V) + st.run[:, :, None]
+        parent, hits = _beam_rule(st, lp.reshape(B, k * V), t, V, max_steps, eos_token, length_penalty, early_stopping, record)
+        # the stop rule of the whole batch
+        go_on = (bool(torch.any(st.unsat)) and not (bool(torch.all(st.fin_flag)) and early_stopping is True)
+                 and not bool(torch.all(hits)))
         if not go_on:
             break
         rows = (parent + torch.arange(B)[:, None] * k).reshape(-1)
-        logits = step(rows, seq[:, :, t].reshape(-1))
+        logits = step(rows, st.seq[:, :, t].reshape(-1))
     n_ret = num_return_sequences
-    lens = fin_len[:, :n_ret].reshape(-1)
+    lens = st.fin_len[:, :n_ret].reshape(-1)
     n = int(lens.max())
-    return fin_seq[:, :n_ret, :n].reshape(B * n_ret, n), fin_score[:, :n_ret].reshape(-1).clone(), lens
+    return st.fin_seq[:, :n_ret, :n].reshape(B * n_ret, n), st.fin_score[:, :n_ret].reshape(-1).clone(), lens
+
+
+@torch.no_grad()
+def group_beam_search(step: Callable, batch_size: int, num_beams: int, num_beam_groups: int, diversity_penalty: float,
+                      max_steps: int, eos_token: int, length_penalty: float = 1.0, early_stopping=False,
+                      num_return_sequences: int = 1, record: list = None, processors: dict = None):
+    """Diverse beam search (Vijayakumar et al., "Diverse Beam Search", 2018), stated from the paper in beam_search's fp32
+    torch arithmetic (``_beam_rule``): the host statement mg_beam_finish_groups is tested against (DESIGN.md "Diverse beam
+    search").  k = num_beams beams in G = num_beam_groups groups of k' = k / G; the rows ``step`` sees are sample-major, then
+    group-major: row b*k + g*k' + q.
+
+    A group is a pseudo-sample: group (b, g) runs beam_search's rule with k' beams over its own rows -- its own running scores
+    (starting at [0, -1e9, ...]), its own k' finished slots, its own early-stop latch, its own top 2k' candidates.  The call
+    stops by beam_search's rule over the B*G groups; a group whose latch has dropped keeps running beams, as samples do.
+
+    Within a step the groups of a sample are handled in the order g = 0 .. G-1, and group g's candidate scores are
+    (run + logp) - lambda * n_t in fp32: run + logp is beam_search's candidate, lambda * n_t one rounded product, the
+    subtraction one rounded subtraction.  n_t counts the running beams of groups 0 .. g-1 of the same sample whose token
+    selected AT THIS STEP is t (whether or not their latch has dropped); group 0 is never penalised; -inf stays -inf.  At the
+    last step, where every candidate finishes and the running scores all round to -1e9, a group's "running" beams are its k'
+    best candidates (ties are taken in candidate order), so the tokens its hypotheses end in are penalised like any other.
+    ``processors`` run first, on log_softmax, as in beam_search; the diversity term comes after them, on the candidate score.
+
+    Returns beam_search's triple; the n_ret = num_return_sequences (in [1, k]) hypotheses of a sample are taken round-robin
+    over the groups by rank within each group -- g0's best, g1's best, ..., g(G-1)'s best, g0's second, ... -- each with its own
+    score: n_ret = G is one hypothesis per group, n_ret = 1 is group 0's best (plain beam search with k' beams).
+
+    ``record``: one dict per step AND group is appended (group-minor), holding what beam_search records per sample -- taken on
+    the penalised scores, so beam_margin reads it as it is -- and ``group``; ``counts`` (B, V), n_t as the group saw it;
+    ``top_beam`` / ``top_tok`` / ``top_n`` (B, 2k'), the group's top candidates and their n_t; ``running`` (B, k'), which of
+    them became its running beams; ``row_rank`` (B, 2k'), the position of each top candidate in its own row's UNPENALISED order
+    (score descending, lower token first): a value >= 2k' is a candidate that lists of 2k' per row would have missed, and
+    k + k' - 1 -- the last entry of the device's lists -- is the largest there can be."""
+    early_stopping = check_beam_args(num_beams, num_return_sequences, early_stopping, num_beam_groups, diversity_penalty)
+    B, k, G = batch_size, num_beams, num_beam_groups
+    kq = k // G
+    lam = torch.tensor(float(diversity_penalty), dtype=torch.float32)
+    groups = [_BeamState(B, kq, max_steps, eos_token) for _ in range(G)]
+    logits = step(None, None)
+    for t in range(max_steps):
+        V = logits.shape[-1]
+        if V < k + kq:
+            raise ValueError(f"num_beams = {k} in {G} groups needs a vocabulary of at least {k + kq} tokens, got {V}")
+        lp = F.log_softmax(logits.float().cpu(), dim=-1)
+        if processors:
+            seq = torch.stack([st.seq for st in groups], dim=1)                      # (B, G, k', max_steps)
+            lp = process_logits(lp, seq.reshape(B * k, max_steps), t, eos_token=eos_token, **processors)
+        lp = lp.view(B, G, kq, V)
+        counts = torch.zeros(B, V, dtype=torch.float32)
+        parents, all_hits = [], []
+        for g, st in enumerate(groups):
+            plain = lp[:, g] + st.run[:, :, None]                                    # beam_search's candidates (B, k', V)
+            cand = plain - (lam * counts)[:, None, :]
+            seen = counts.clone()
+
+            def extra(top_s, beam, tok, nxt, g=g, plain=plain, seen=seen):
+                row = torch.take_along_dim(plain, beam[:, :, None], dim=1)           # (B, 2k', V): the row each one came from
+                mine = torch.take_along_dim(row, tok[:, :, None], dim=2)
+                before = (row > mine) | ((row == mine) & (torch.arange(V)[None, None, :] < tok[:, :, None]))
+                return dict(group=g, counts=seen, top_n=torch.take_along_dim(seen, tok, dim=1), top_beam=beam.clone(),
+                            top_tok=tok.clone(), running=nxt.clone(), row_rank=before.sum(-1))
+
+            parent, hits = _beam_rule(st, cand.reshape(B, kq * V), t, V, max_steps, eos_token, length_penalty, early_stopping,
+                                      record, extra if record is not None else None, ties_by_index=True)
+            counts.scatter_add_(1, st.seq[:, :, t], torch.ones(B, kq))
+            parents.append(parent + g * kq)
+            all_hits.append(hits)
+        # the stop rule of the whole call, over the B*G groups
+        go_on = (any(bool(torch.any(st.unsat)) for st in groups)
+                 and not (all(bool(torch.all(st.fin_flag)) for st in groups) and early_stopping is True)
+                 and not all(bool(torch.all(h)) for h in all_hits))
+        if not go_on:
+            break
+        rows = (torch.cat(parents, dim=1) + torch.arange(B)[:, None] * k).reshape(-1)
+        logits = step(rows, torch.cat([st.seq[:, :, t] for st in groups], dim=1).reshape(-1))
+    n_ret = num_return_sequences
+    # round-robin over the groups by rank within the group: (B, G, k') -> (B, k', G) -> the first n_ret
+    pool = lambda name: torch.stack([getattr(st, name) for st in groups], dim=1).transpose(1, 2)  # noqa: E731
+    lens = pool("fin_len").reshape(B, k)[:, :n_ret].reshape(-1)
+    n = int(lens.max())
+    seqs = pool("fin_seq").reshape(B, k, max_steps)[:, :n_ret, :n].reshape(B * n_ret, n)
+    return seqs, pool("fin_score").reshape(B, k)[:, :n_ret].reshape(-1).clone(), lens
 
 
 def beam_margin(record: list) -> float:
@@ -953,7 +1080,8 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
              min_new_tokens: int = 0, suppress_tokens=None, stop_sequences=None, stop_per_row: bool = None,
              return_finish: bool = False, sampler: str = "reference", min_p: float = 0.0, return_logprobs: bool = False,
              top_logprobs: int = 0, constraint=None, guidance_scale: float = 1.0, negative_embeddings=None,
-             negative_lengths=None, guidance_min_p: float = 0.0) -> Union[List[str], torch.Tensor]:
+             negative_lengths=None, guidance_min_p: float = 0.0, num_beam_groups: int = 1,
+             diversity_penalty: float = 0.0) -> Union[List[str], torch.Tensor]:
     """reference sampling.py:43-121.  Token selection (argmax, or top-k / the reference's top-p rule / softmax /
     multinomial) and the ``(next_token == eos).all()`` test run on the device inside the captured token step; the host
     reads the recorded "first all-eos step" every ``eos_check_every`` steps (default 8, MAGMA_EOS_CHECK_EVERY) instead of
@@ -971,6 +1099,19 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     sample-major: B * n_ret strings, or (B * n_ret, s + n) ids laid out as above (n = the longest returned hypothesis);
     ``return_scores=True`` returns (output, fp32 scores (B * n_ret,)) -- with num_beams=1 that runs the beam rule with one
     beam.  The HIP engine runs the whole beam step on the device; any other LM object runs the host statement.
+
+    Diverse beam search (DESIGN.md "Diverse beam search"; Vijayakumar et al. 2018): ``num_beam_groups`` = G > 1 (a divisor of
+    ``num_beams``) runs the beams in G groups of k' = num_beams / G, each by the beam rule with k' beams -- its own finished
+    slots, its own early-stop latch --, and within a step group g scores a candidate token ``diversity_penalty`` (finite, >= 0,
+    and 0 at G = 1; 0 at G > 1 gives G equal groups) lower for every beam of groups 0 .. g-1 of the same sample that selected
+    that token at this step (``group_beam_search`` above), so the groups drift apart: several DIFFERENT captions of one image.
+    The logits processors run first, on log_softmax; the diversity term comes after them, on the candidate score (transformers
+    4.x put its Hamming processor in front of the repetition penalty).  The ``num_return_sequences`` hypotheses of a sample come
+    back round-robin over the groups by rank within each group -- group 0's best, group 1's best, ..., then the second of
+    each --, every one with its own score (transformers 4.x pooled them by score): n_ret = G is one caption per group, n_ret = 1
+    is group 0's best, i.e. plain beam search with k' beams.  V must be at least num_beams + k'.  The HIP engine runs it in the
+    same three launches per token as beam search (the candidate lists are num_beams + k' long, the bookkeeping launch walks the
+    groups); any other LM object runs the host statement.  At ``num_beam_groups=1`` the call is bit for bit what it was.
 
     Multi-turn (DESIGN.md "Continuing from a cache"; HIP engine only, greedy or sampled): ``return_past_key_values=True`` returns
     (output, past).  ``past`` belongs to the caller (no later call reuses its buffers) and holds every row's conversation: its
@@ -1049,7 +1190,8 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     call is bit for bit what it was, and nothing is launched or allocated."""
     if eos_token is None or (isinstance(eos_token, int) and not eos_token):
         eos_token = model.eos_token
-    early_stopping = check_beam_args(num_beams, num_return_sequences, early_stopping)
+    early_stopping = check_beam_args(num_beams, num_return_sequences, early_stopping, num_beam_groups, diversity_penalty,
+                                     _logit_count(model))
     proc = check_processor_args(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, _logit_count(model))
     stop = check_stop_args(eos_token, stop_sequences, stop_per_row, _logit_count(model),
                            getattr(getattr(model, "tokenizer", None), "encode", None))
@@ -1084,7 +1226,8 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     on_device = getattr(model.lm, "device_token_selection", False)
     if num_beams > 1 or return_scores:
         return _generate_beam(model, embeddings, max_steps, eos_token, decode, eos_check_every, lengths, num_beams,
-                              float(length_penalty), early_stopping, num_return_sequences, return_scores, proc)
+                              float(length_penalty), early_stopping, num_return_sequences, return_scores, proc,
+                              num_beam_groups, float(diversity_penalty))
     was_training = model.training
     b, s, _ = embeddings.shape
     if guide is not None:       # the negative prompt as (b, s', d) rows, row counts and hidden size checked
@@ -1731,7 +1874,7 @@ def keep_conversation(cache, start: torch.Tensor, n_gen: int, eos_token, finish:
 
 @torch.no_grad()
 def _generate_beam(model, embeddings, max_steps, eos_token, decode, eos_check_every, lengths, k, length_penalty,
-                   early_stopping, n_ret, return_scores, proc=None):
+                   early_stopping, n_ret, return_scores, proc=None, groups=1, diversity=0.0):
     """generate()'s beam search over the prompt batch it has normalised: on the HIP engine's device, or beam_search on the host."""
     was_training = model.training
     on_device = getattr(model.lm, "device_token_selection", False)
@@ -1742,7 +1885,8 @@ def _generate_beam(model, embeddings, max_steps, eos_token, decode, eos_check_ev
     emb = embeddings.repeat_interleave(k, dim=0)           # B prompts -> B*k rows, sample-major
     if on_device:
         from .engine import LMEngine
-        plan = LMEngine.selection_plan(beam=(k, length_penalty, early_stopping, int(max_steps)), processors=proc,
+        beam = (k, length_penalty, early_stopping, int(max_steps)) + ((groups, diversity) if groups > 1 else ())
+        plan = LMEngine.selection_plan(beam=beam, processors=proc,
                                        vocab=model.lm.engine.V)
         every = eos_check_every or int(os.environ.get("MAGMA_EOS_CHECK_EVERY", "8"))
         for i in range(max_steps):
@@ -1767,7 +1911,12 @@ def _generate_beam(model, embeddings, max_steps, eos_token, decode, eos_check_ev
             cache["past"] = o.past_key_values
             return o.logits[:, -1, :].float()
 
-        toks, scores, lens = beam_search(step, b, k, max_steps, eos_token, length_penalty, early_stopping, n_ret, processors=proc)
+        if groups > 1:
+            toks, scores, lens = group_beam_search(step, b, k, groups, diversity, max_steps, eos_token, length_penalty,
+                                                   early_stopping, n_ret, processors=proc)
+        else:
+            toks, scores, lens = beam_search(step, b, k, max_steps, eos_token, length_penalty, early_stopping, n_ret,
+                                             processors=proc)
     toks, lens = toks.to(dev), lens.to(dev)
     n = toks.shape[1]
     out = torch.full((b * n_ret, s + n), eos_token, dtype=torch.long, device=dev)
