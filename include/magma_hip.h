@@ -101,8 +101,10 @@ const char* mg_version(void);
  *  18  classifier-free guidance: added mg_logits_guidance_f32 and mg_guidance_follow (nothing moved).
  *  19  ranking choices: added mg_attn_prefill_tree_bf16, mg_rotary_split_at_bf16 and mg_token_logprobs_rows_f32 (nothing moved).
  *  20  explaining answers: added mg_attn_prefill_scaled_bf16 (nothing moved).
- *  21  diverse beam search: added mg_beam_finish_groups (nothing moved). */
-#define MG_ABI_VERSION 21
+ *  21  diverse beam search: added mg_beam_finish_groups (nothing moved).
+ *  22  contrastive search: added mg_contrastive_topk_f32, mg_contrastive_sim_bf16, mg_contrastive_finish and
+ *      mg_kv_broadcast_bf16 (nothing moved). */
+#define MG_ABI_VERSION 22
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -604,6 +606,46 @@ int mg_token_logprobs_f32(const float* logits, int64_t ld, int32_t R, int32_t V,
  * [0, V) reads nothing and gives -inf.                                                                                       */
 int mg_token_logprobs_rows_f32(const float* logits, int64_t ld, int32_t n_rows, int32_t V, const int32_t* row_of,
                                const int32_t* token, int32_t N, float* lp, void* stream);
+
+/* Contrastive search (ABI 22; Su et al. 2022, "A Contrastive Framework for Neural Text Generation"; DESIGN.md "Contrastive
+ * search"; host statement: magma_amd/sampling.py, contrastive_rank / contrastive_search).  A sample owns a group of k <= 16 cache
+ * rows b*k .. b*k + k - 1, one per candidate token; four enqueue-only, graph-capturable launches follow the head of a token step
+ * over those R = B * k rows (no allocation, no scratch, no host round trip, nothing shared between workgroups of a launch):
+ *
+ * mg_contrastive_topk_f32: per sample b the k most probable tokens of logits row src[b] (logits [R, ld] fp32, columns >= V are not
+ *   read; src [B] int32, a value outside the sample's group reads row b*k), ranked by raw logit descending, lower id first -- the
+ *   device body of mg_token_logprobs_f32 -- as int64 into token[b*k + j] (the next step's input ids) and
+ *   cand_p[b*k + j] = exp((x - max) - logsumexp), the fp32 softmax probability.
+ * mg_contrastive_sim_bf16: hidden [R, ld_hidden] bf16 (the candidates' ln_f outputs), the context store ctx [B, Tmax, d] bf16 and
+ *   ctx_len [B] int32 (device; clamped to [0, Tmax]) -> part [B, n_chunk, k] fp32, n_chunk = ceil(Tmax / MG_CONTRASTIVE_CHUNK):
+ *   part[b, c, j] = max over the valid positions t of chunk c of  <h_j, c_t> / (|h_j| |c_t|)  in fp32 from the bf16 values (norms
+ *   from the same values; a zero vector gives 0), or -1e30 for a chunk without a valid position.  Grid (n_chunk, B).  d must be a
+ *   multiple of 256, ld_hidden >= d a multiple of 8, hidden and ctx 16-byte aligned.  len_max: the caller's host-side upper bound of
+ *   ctx_len's entries, refused when it exceeds Tmax.
+ * mg_contrastive_finish: one workgroup.  Per sample: penalty_j = max over the chunks of part (0 without any context position),
+ *   score_j = (1 - alpha) * cand_p[b*k + j] - alpha * penalty_j in fp32, j* = the first largest.  Writes token[b*k + j*] into
+ *   history[(b*k + j) * ld_history + step] for every j < k (step = state[0]; nothing outside [0, history_cols)), src[b] = b*k + j*,
+ *   hidden row b*k + j* into ctx[b, ctx_len[b]] and ctx_len[b] += 1 (both only while ctx_len[b] < Tmax); then mg_sample_finish's
+ *   bookkeeping: state[1] = step if every sample's token is eos and state[1] < 0, state[0] = step + 1, d_pos[i] += delta for the
+ *   R rows (pos_stride 1) or d_pos[0] (pos_stride 0; d_pos NULL: no advance).  alpha in (0, 1]; len_max as above, refused when
+ *   len_max >= Tmax (no room to append).
+ * mg_kv_broadcast_bf16: caches [L, R, H, Smax, 256] bf16.  For every row r of a group whose src[b] != r: the 256-element K and V
+ *   rows of every layer and head at position d_pos[r * pos_stride] + pos_delta are copied from row src[b] (pos_delta = -1 behind
+ *   mg_contrastive_finish, which has advanced the positions).  A src outside the group or a position outside [0, Smax) copies
+ *   nothing; k = 1 launches nothing.  Not mg_kv_reorder_bf16: one position, not whole rows. */
+#define MG_CONTRASTIVE_CHUNK 32
+#define MG_CONTRASTIVE_MAX_K 16
+int mg_contrastive_topk_f32(const float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* src, int32_t B, int32_t k,
+                            int64_t* token, float* cand_p, void* stream);
+int mg_contrastive_sim_bf16(const mg_bf16* hidden, int64_t ld_hidden, const mg_bf16* ctx, int32_t B, int32_t Tmax, int32_t d,
+                            const int32_t* ctx_len, int32_t len_max, int32_t k, float* part, int32_t n_chunk, void* stream);
+int mg_contrastive_finish(const float* part, int32_t n_chunk, const float* cand_p, int32_t B, int32_t k, float alpha,
+                          const mg_bf16* hidden, int64_t ld_hidden, int32_t d, mg_bf16* ctx, int32_t Tmax, int32_t* ctx_len,
+                          int32_t len_max, int32_t* src, const int64_t* token, int64_t* history, int64_t ld_history,
+                          int32_t history_cols, int64_t eos, int32_t* state, int32_t* d_pos, int32_t delta, int32_t pos_stride,
+                          void* stream);
+int mg_kv_broadcast_bf16(mg_bf16* kcache, mg_bf16* vcache, int32_t L, int32_t R, int32_t H, int32_t Smax, int32_t k,
+                         const int32_t* src, const int32_t* d_pos, int32_t pos_stride, int32_t pos_delta, void* stream);
 
 /* CLIP VisionTransformer front end and attention (encoder_name "clip" = ViT-B/32; reference magma/image_encoders.py:56-63):
  *   patchify   img [B,3,H,W] bf16 NCHW -> rows [B*(H/P)*(W/P), 3*P*P] in (c, py, px) order = the im2col of the stride-P patch

@@ -1360,3 +1360,277 @@ extern "C" int mg_token_logprobs_rows_f32(const float* logits, int64_t ld, int32
   MG_CHECK_LAUNCH();
   return MG_OK;
 }
+
+// ================================================================================================================================
+// Contrastive search (ABI 22; Su et al. 2022; DESIGN.md "Contrastive search"; host statement: magma_amd/sampling.py,
+// contrastive_rank / contrastive_search).  A sample owns k cache rows, one per candidate token; per token step, behind the head:
+//   contrastive_sim_kernel     grid (context chunks of 32 positions, samples), 8 waves: cosines of the <= 16 candidate hidden rows
+//                              against the chunk's context rows on the 16x16x32 bf16 MFMA (context rows the 16-row operand, the
+//                              candidates -- zero beyond k -- the 16 columns), wave w taking d / 8 of the hidden size; every lane loads 16
+//                              bytes per operand and K-slice, the squared norms of both sides are summed from the very fragments
+//                              the MFMA reads.  The eight partial tiles meet in LDS; per candidate the maximum over the chunk's
+//                              valid positions goes to part[b, chunk, j].  Nothing is shared between workgroups.
+//   contrastive_finish_kernel  one workgroup: per sample the maximum over the chunks, score_j = (1 - alpha) p_j - alpha penalty_j, the
+//                              first largest j; the selected token to the history, src[b] = the selected row, its hidden row
+//                              appended to the context store; then mg_sample_finish's bookkeeping (one workgroup because the
+//                              all-eos latch and the step counter are the whole batch's).
+//   kv_broadcast_kernel        the K / V of the selected row at the position just written, to the sample's other k - 1 rows.
+//   contrastive_topk_kernel    row_topk_body's max / logsumexp / radix descent on the selected row's logits: the next k candidates
+//                              (raw logit descending, lower id first) into the token rows of the sample, p = exp(log_softmax).
+namespace {
+
+constexpr int CS_CHUNK = 32;            // context positions per workgroup of the similarity kernel (MG_CONTRASTIVE_CHUNK)
+constexpr int CS_WAVES = 8;
+constexpr float CS_EMPTY = -1.0e30f;    // part[] of a chunk without a valid position
+
+MG_DEV float sumsq8(const u32x4 w) {
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { const float a = bflo(w[i]), b = bfhi(w[i]); s = fmaf(a, a, s); s = fmaf(b, b, s); }
+  return s;
+}
+
+__global__ __launch_bounds__(CS_WAVES * 64) void contrastive_sim_kernel(const mg_bf16* __restrict__ hidden, int64_t ld_h,
+                                                                        const mg_bf16* __restrict__ ctx, int Tmax, int d,
+                                                                        const int32_t* __restrict__ ctx_len, int k,
+                                                                        float* __restrict__ part, int n_chunk) {
+  __shared__ float s_acc[CS_WAVES][2][256];
+  __shared__ float s_nx[CS_WAVES][CS_CHUNK];
+  __shared__ float s_nc[CS_WAVES][16];
+  __shared__ float s_cos[CS_CHUNK][16];
+  const int chunk = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int len = max(0, min(ctx_len[b], Tmax));
+  const int p0 = chunk * CS_CHUNK;
+  float* out = part + ((int64_t)b * n_chunk + chunk) * k;
+  if (p0 >= len) {                           // (uniform over the workgroup)
+    if (tid < k) out[tid] = CS_EMPTY;
+    return;
+  }
+  const int lane = tid & 63, wave = tid >> 6, li = lane & 15, lq = lane >> 4;
+  const int dw = d / CS_WAVES, kbeg = wave * dw + lq * 8;
+  // rows past the valid length read the last valid row (inside the store) and are masked below
+  const mg_bf16* base = ctx + (int64_t)b * Tmax * d;
+  const mg_bf16* ra = base + (int64_t)min(p0 + li, len - 1) * d + kbeg;
+  const mg_bf16* rb = base + (int64_t)min(p0 + 16 + li, len - 1) * d + kbeg;
+  const bool cand = li < k;
+  const mg_bf16* rc = hidden + ((int64_t)b * k + min(li, k - 1)) * ld_h + kbeg;
+  f32x4 acc0 = (f32x4){0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
+  float na = 0.f, nb = 0.f, nc = 0.f;
+  auto slice = [&](const u32x4 fa, const u32x4 fb, const u32x4 fc) {
+    const bf16x8 c8 = __builtin_bit_cast(bf16x8, fc);
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa), c8, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fb), c8, acc1, 0, 0, 0);
+    na += sumsq8(fa); nb += sumsq8(fb); nc += sumsq8(fc);
+  };
+  const u32x4 zero = (u32x4){0u, 0u, 0u, 0u};
+  int k0 = 0;
+  for (; k0 + 128 <= dw; k0 += 128) {        // four K-slices in flight: 12 loads of 16 bytes per lane
+    u32x4 fa[4], fb[4], fc[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      fa[u] = *(const u32x4*)(ra + k0 + 32 * u);
+      fb[u] = *(const u32x4*)(rb + k0 + 32 * u);
+      fc[u] = cand ? *(const u32x4*)(rc + k0 + 32 * u) : zero;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) slice(fa[u], fb[u], fc[u]);
+  }
+  for (; k0 < dw; k0 += 32)
+    slice(*(const u32x4*)(ra + k0), *(const u32x4*)(rb + k0), cand ? *(const u32x4*)(rc + k0) : zero);
+  // the four k-groups of a row sit 16 lanes apart
+  na += __shfl_xor(na, 16, 64); na += __shfl_xor(na, 32, 64);
+  nb += __shfl_xor(nb, 16, 64); nb += __shfl_xor(nb, 32, 64);
+  nc += __shfl_xor(nc, 16, 64); nc += __shfl_xor(nc, 32, 64);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {              // acc[r]: context row lq * 4 + r of the tile, candidate li
+    s_acc[wave][0][(lq * 4 + r) * 16 + li] = acc0[r];
+    s_acc[wave][1][(lq * 4 + r) * 16 + li] = acc1[r];
+  }
+  if (lq == 0) { s_nx[wave][li] = na; s_nx[wave][16 + li] = nb; s_nc[wave][li] = nc; }
+  __syncthreads();
+  {
+    const int p = tid >> 4, j = tid & 15;    // 512 threads: 32 positions x 16 candidates
+    float dot = 0.f, nx = 0.f, ncj = 0.f;
+#pragma unroll
+    for (int w = 0; w < CS_WAVES; ++w) {
+      dot += s_acc[w][p >> 4][(p & 15) * 16 + j];
+      nx += s_nx[w][p];
+      ncj += s_nc[w][j];
+    }
+    float c = (nx > 0.f && ncj > 0.f) ? dot / (sqrtf(nx) * sqrtf(ncj)) : 0.f;
+    if (p0 + p >= len) c = CS_EMPTY;
+    s_cos[p][j] = c;
+  }
+  __syncthreads();
+  if (tid < k) {
+    float m = CS_EMPTY;
+#pragma unroll
+    for (int p = 0; p < CS_CHUNK; ++p) m = fmaxf(m, s_cos[p][tid]);
+    out[tid] = m;
+  }
+}
+
+struct ContrastFinishArgs {
+  const float* part; int n_chunk; const float* cand_p; int B, k; float alpha;
+  const mg_bf16* hidden; int64_t ld_h; int d; mg_bf16* ctx; int Tmax; int32_t* ctx_len; int32_t* src;
+  const int64_t* token; int64_t* history; int64_t ld_hist; int hist_cols; int64_t eos; int32_t* state;
+  int32_t* d_pos; int n_pos, delta;
+};
+
+__global__ __launch_bounds__(256) void contrastive_finish_kernel(const ContrastFinishArgs a) {
+  __shared__ int s_step, s_sel, s_all;
+  __shared__ float s_score[BK_MAX];
+  const int tid = threadIdx.x, k = a.k;
+  if (tid == 0) { s_step = a.state[0]; s_all = 1; }      // read once, before thread 0 bumps it (sample_finish_kernel)
+  __syncthreads();
+  const int step = s_step;
+  for (int b = 0; b < a.B; ++b) {
+    if (tid < k) {
+      float pen = CS_EMPTY;
+      for (int c = 0; c < a.n_chunk; ++c) pen = fmaxf(pen, a.part[((int64_t)b * a.n_chunk + c) * k + tid]);
+      if (pen <= CS_EMPTY) pen = 0.f;                    // no context position at all
+      s_score[tid] = (1.f - a.alpha) * a.cand_p[b * k + tid] - a.alpha * pen;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int best = 0;
+      for (int j = 1; j < k; ++j) if (s_score[j] > s_score[best]) best = j;
+      s_sel = best;
+    }
+    __syncthreads();
+    const int row = b * k + s_sel;
+    const int len = a.ctx_len[b];
+    const int64_t tok = a.token[row];
+    if (len >= 0 && len < a.Tmax) {                      // the selected hidden row joins the context
+      const uint4* s = (const uint4*)(a.hidden + (int64_t)row * a.ld_h);
+      uint4* t = (uint4*)(a.ctx + ((int64_t)b * a.Tmax + len) * a.d);
+      for (int i = tid; i < a.d / 8; i += blockDim.x) t[i] = s[i];
+    }
+    if (a.history && tid < k && step >= 0 && step < a.hist_cols) a.history[(int64_t)(b * k + tid) * a.ld_hist + step] = tok;
+    __syncthreads();                                     // every thread has read ctx_len[b] and s_sel
+    if (tid == 0) {
+      a.src[b] = row;
+      if (len >= 0 && len < a.Tmax) a.ctx_len[b] = len + 1;
+      if (tok != a.eos) s_all = 0;
+    }
+  }
+  if (a.d_pos)
+    for (int i = tid; i < a.n_pos; i += blockDim.x) a.d_pos[i] += a.delta;
+  __syncthreads();
+  if (tid != 0) return;
+  if (s_all && a.state[1] < 0) a.state[1] = step;
+  a.state[0] = step + 1;
+}
+
+// grid (H, R, L), 64 threads: lanes 0-31 one 16-byte piece of the K row each, lanes 32-63 of the V row
+__global__ __launch_bounds__(64) void kv_broadcast_kernel(uint4* __restrict__ kc, uint4* __restrict__ vc, int R, int H, int Smax,
+                                                          int k, const int32_t* __restrict__ src,
+                                                          const int32_t* __restrict__ d_pos, int pos_stride, int pos_delta) {
+  const int h = blockIdx.x, r = blockIdx.y, l = blockIdx.z;
+  const int b = r / k, s = src[b];
+  if (s == r || s < b * k || s >= b * k + k) return;     // written by the bookkeeping launch; never trusted here
+  const int pos = d_pos[r * pos_stride] + pos_delta;
+  if (pos < 0 || pos >= Smax) return;
+  const int64_t per = 32;                                // uint4 per position (256 bf16)
+  const int64_t dst = ((((int64_t)l * R + r) * H + h) * Smax + pos) * per;
+  const int64_t from = ((((int64_t)l * R + s) * H + h) * Smax + pos) * per;
+  const int i = threadIdx.x & 31;
+  if (threadIdx.x < 32) kc[dst + i] = kc[from + i];
+  else vc[dst + i] = vc[from + i];
+}
+
+__global__ __launch_bounds__(ST) void contrastive_topk_kernel(const float* __restrict__ logits, int64_t ld, int R, int V,
+                                                              const int32_t* __restrict__ src, int k, int64_t* __restrict__ token,
+                                                              float* __restrict__ cand_p) {
+  __shared__ float s_lp[BK2_MAX];
+  __shared__ int32_t s_tok[BK2_MAX];
+  const int b = blockIdx.x;
+  int row = src[b];
+  if (row < b * k || row >= b * k + k || row >= R) row = b * k;      // (uniform; never trusted)
+  row_topk_body<false, true>(logits + (int64_t)row * ld, V, 0.f, k, s_lp, s_tok);
+  __syncthreads();
+  if (threadIdx.x < k) {
+    token[b * k + threadIdx.x] = (int64_t)s_tok[threadIdx.x];
+    cand_p[b * k + threadIdx.x] = expf(s_lp[threadIdx.x]);
+  }
+}
+
+}  // namespace
+
+extern "C" int mg_contrastive_topk_f32(const float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* src, int32_t B,
+                                       int32_t k, int64_t* token, float* cand_p, void* stream) {
+  const char* who = "mg_contrastive_topk_f32";
+  if (!logits || !src || !token || !cand_p) MG_FAIL(MG_ERR_SHAPE, "%s: null pointer", who);
+  if (B <= 0 || V <= 0 || ld < V) MG_FAIL(MG_ERR_SHAPE, "%s: need B, V > 0 and ld >= V", who);
+  if (k < 1 || k > BK_MAX || k > V) MG_FAIL(MG_ERR_SHAPE, "%s: need 1 <= k <= min(%d, V), got %d (V = %d)", who, BK_MAX, k, V);
+  if (R != B * k) MG_FAIL(MG_ERR_SHAPE, "%s: logits must hold R = B * k = %d rows, got %d", who, B * k, R);
+  if (((uintptr_t)logits | (uintptr_t)src | (uintptr_t)cand_p) & 3) MG_FAIL(MG_ERR_ALIGN, "%s: logits, src and cand_p must be 4-byte aligned", who);
+  if ((uintptr_t)token & 7) MG_FAIL(MG_ERR_ALIGN, "%s: token must be 8-byte aligned", who);
+  hipLaunchKernelGGL(contrastive_topk_kernel, dim3(B), dim3(ST), 0, (hipStream_t)stream, logits, ld, R, V, src, k, token, cand_p);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_contrastive_sim_bf16(const mg_bf16* hidden, int64_t ld_hidden, const mg_bf16* ctx, int32_t B, int32_t Tmax,
+                                       int32_t d, const int32_t* ctx_len, int32_t len_max, int32_t k, float* part, int32_t n_chunk,
+                                       void* stream) {
+  const char* who = "mg_contrastive_sim_bf16";
+  if (!hidden || !ctx || !ctx_len || !part) MG_FAIL(MG_ERR_SHAPE, "%s: null pointer", who);
+  if (B <= 0 || B > 65535 || Tmax <= 0) MG_FAIL(MG_ERR_SHAPE, "%s: need 0 < B <= 65535 and Tmax > 0", who);
+  if (len_max < 0 || len_max > Tmax) MG_FAIL(MG_ERR_SHAPE, "%s: ctx_len reaches %d, the store holds Tmax = %d positions", who, len_max, Tmax);
+  if (k < 1 || k > BK_MAX) MG_FAIL(MG_ERR_SHAPE, "%s: need 1 <= k <= %d, got %d", who, BK_MAX, k);
+  if (d <= 0 || d % 256 != 0) MG_FAIL(MG_ERR_SHAPE, "%s: d must be a multiple of 256, got %d", who, d);
+  if (ld_hidden < d || ld_hidden % 8 != 0) MG_FAIL(MG_ERR_SHAPE, "%s: ld_hidden must be >= d and a multiple of 8", who);
+  if (n_chunk != (Tmax + CS_CHUNK - 1) / CS_CHUNK)
+    MG_FAIL(MG_ERR_SHAPE, "%s: part holds n_chunk = ceil(Tmax / %d) = %d chunks per sample, got %d", who, CS_CHUNK, (Tmax + CS_CHUNK - 1) / CS_CHUNK, n_chunk);
+  if (!MG_ALIGNED16(hidden) || !MG_ALIGNED16(ctx)) MG_FAIL(MG_ERR_ALIGN, "%s: hidden and ctx must be 16-byte aligned", who);
+  if (((uintptr_t)ctx_len | (uintptr_t)part) & 3) MG_FAIL(MG_ERR_ALIGN, "%s: ctx_len and part must be 4-byte aligned", who);
+  hipLaunchKernelGGL(contrastive_sim_kernel, dim3(n_chunk, B), dim3(CS_WAVES * 64), 0, (hipStream_t)stream, hidden, ld_hidden, ctx,
+                     Tmax, d, ctx_len, k, part, n_chunk);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_contrastive_finish(const float* part, int32_t n_chunk, const float* cand_p, int32_t B, int32_t k, float alpha,
+                                     const mg_bf16* hidden, int64_t ld_hidden, int32_t d, mg_bf16* ctx, int32_t Tmax,
+                                     int32_t* ctx_len, int32_t len_max, int32_t* src, const int64_t* token, int64_t* history,
+                                     int64_t ld_history, int32_t history_cols, int64_t eos, int32_t* state, int32_t* d_pos, int32_t delta,
+                                     int32_t pos_stride, void* stream) {
+  const char* who = "mg_contrastive_finish";
+  if (!part || !cand_p || !hidden || !ctx || !ctx_len || !src || !token || !state) MG_FAIL(MG_ERR_SHAPE, "%s: null pointer", who);
+  if (B <= 0 || Tmax <= 0 || n_chunk != (Tmax + CS_CHUNK - 1) / CS_CHUNK)
+    MG_FAIL(MG_ERR_SHAPE, "%s: need B, Tmax > 0 and n_chunk = ceil(Tmax / %d)", who, CS_CHUNK);
+  if (len_max < 0 || len_max >= Tmax)
+    MG_FAIL(MG_ERR_SHAPE, "%s: ctx_len reaches %d, no room to append in a store of Tmax = %d positions", who, len_max, Tmax);
+  if (k < 1 || k > BK_MAX) MG_FAIL(MG_ERR_SHAPE, "%s: need 1 <= k <= %d, got %d", who, BK_MAX, k);
+  if (!(alpha > 0.f && alpha <= 1.f)) MG_FAIL(MG_ERR_SHAPE, "%s: penalty_alpha must lie in (0, 1]", who);      // (NaN fails)
+  if (d <= 0 || d % 256 != 0 || ld_hidden < d || ld_hidden % 8 != 0)
+    MG_FAIL(MG_ERR_SHAPE, "%s: d must be a multiple of 256, ld_hidden >= d and a multiple of 8", who);
+  if (pos_stride != 0 && pos_stride != 1) MG_FAIL(MG_ERR_SHAPE, "%s: pos_stride must be 0 or 1", who);
+  if (history && (ld_history < history_cols || history_cols <= 0)) MG_FAIL(MG_ERR_SHAPE, "%s: bad history geometry", who);
+  if (!MG_ALIGNED16(hidden) || !MG_ALIGNED16(ctx)) MG_FAIL(MG_ERR_ALIGN, "%s: hidden and ctx must be 16-byte aligned", who);
+  if (((uintptr_t)part | (uintptr_t)cand_p | (uintptr_t)ctx_len | (uintptr_t)src | (uintptr_t)state | (uintptr_t)d_pos) & 3)
+    MG_FAIL(MG_ERR_ALIGN, "%s: fp32 / int32 buffers must be 4-byte aligned", who);
+  if (((uintptr_t)token | (uintptr_t)history) & 7) MG_FAIL(MG_ERR_ALIGN, "%s: token and history must be 8-byte aligned", who);
+  ContrastFinishArgs a{part, n_chunk, cand_p, B, k, alpha, hidden, ld_hidden, d, ctx, Tmax, ctx_len, src, token, history,
+                       ld_history, history ? history_cols : 0, eos, state, d_pos, pos_stride ? B * k : 1, delta};
+  hipLaunchKernelGGL(contrastive_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_kv_broadcast_bf16(mg_bf16* kcache, mg_bf16* vcache, int32_t L, int32_t R, int32_t H, int32_t Smax, int32_t k,
+                                    const int32_t* src, const int32_t* d_pos, int32_t pos_stride, int32_t pos_delta, void* stream) {
+  const char* who = "mg_kv_broadcast_bf16";
+  if (!kcache || !vcache || !src || !d_pos || L <= 0 || R <= 0 || H <= 0 || Smax <= 0) MG_FAIL(MG_ERR_SHAPE, "%s: bad arguments", who);
+  if (k < 1 || k > BK_MAX || R % k != 0) MG_FAIL(MG_ERR_SHAPE, "%s: need 1 <= k <= %d dividing R = %d, got %d", who, BK_MAX, R, k);
+  if (pos_stride != 0 && pos_stride != 1) MG_FAIL(MG_ERR_SHAPE, "%s: pos_stride must be 0 or 1", who);
+  if (!MG_ALIGNED16(kcache) || !MG_ALIGNED16(vcache)) MG_FAIL(MG_ERR_ALIGN, "%s: the caches must be 16-byte aligned", who);
+  if (((uintptr_t)src | (uintptr_t)d_pos) & 3) MG_FAIL(MG_ERR_ALIGN, "%s: src and d_pos must be 4-byte aligned", who);
+  if (H > 65535 || L > 65535 || R > 65535) MG_FAIL(MG_ERR_SHAPE, "%s: grid too large", who);
+  if (k == 1) return MG_OK;                   // a group of one row has no sibling
+  hipLaunchKernelGGL(kv_broadcast_kernel, dim3(H, R, L), dim3(64), 0, (hipStream_t)stream, (uint4*)kcache, (uint4*)vcache, R, H, Smax,
+                     k, src, d_pos, pos_stride, pos_delta);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}

@@ -58,6 +58,8 @@ class KVCache:
         self.B, self.Smax = B, Smax
         self.decode_state = None
         self.beam = None          # BeamBuffers of a beam-search loop (B = samples x num_beams rows), allocated on first use
+        self.contrast = None      # ContrastBuffers of a contrastive-search loop (B = samples x top_k rows), allocated on first use
+        self.prefill_x = None     # the prefill's last-block output (B, S, d), kept only for a contrastive plan to arm from
         # logits processors: the suppress ids on the device (int32 [1024], allocated on first use; its address and the NUMBER of
         # ids are launch arguments of the captured step, the ids themselves are not) and the host copy of what it holds
         self.suppress, self.suppress_ids = None, ()
@@ -142,7 +144,7 @@ class KVCache:
             setattr(self, name, new)
         self.history = torch.zeros(self.B, Smax, dtype=torch.int64, device=self.k.device)
         self.Smax = Smax
-        self.beam = None
+        self.beam = self.contrast = None
         self._drop_graphs()
         if self.lp is not None:           # one column per history column
             self.alloc_logprobs(self.top_id.shape[2])
@@ -201,6 +203,23 @@ class BeamBuffers:
         self.unsat.fill_(1)
 
 
+class ContrastBuffers:
+    """Device state of contrastive search over a KV cache of R = B * k rows (DESIGN.md "Contrastive search"): the context store
+    ``ctx`` (B, Smax, d) bf16 of ln_f outputs -- one row per prompt position, then one per generated token --, its valid length per
+    sample, the row of every sample's group that was selected last (``src``), the candidates' probabilities and the per-chunk
+    partial maxima of the similarity launch.  The candidates' ids live in the decode state's token rows."""
+
+    def __init__(self, cache: KVCache, k: int, d: int):
+        R, dev = cache.B, cache.k.device
+        assert R % k == 0
+        self.k, self.B, self.Tmax = k, R // k, cache.Smax
+        self.ctx = torch.zeros(self.B, self.Tmax, d, dtype=BF16, device=dev)
+        self.ctx_len = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.src = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.cand_p = torch.zeros(self.B, k, dtype=torch.float32, device=dev)
+        self.part = torch.zeros(self.B, ops.contrastive_chunks(self.Tmax), k, dtype=torch.float32, device=dev)
+
+
 class _Layer:
     pass
 
@@ -230,12 +249,16 @@ class StepKey(NamedTuple):
     def beam(self) -> bool:
         return isinstance(self.mode, tuple) and self.mode[:1] == ("beam",)
 
+    @property
+    def contrast(self) -> bool:
+        return isinstance(self.mode, tuple) and self.mode[:1] == ("contrast",)
+
 
 class SelectionPlan(NamedTuple):
     """The checked modes of one token step (DESIGN.md "The selection plan"), built once per call by LMEngine.selection_plan --
     the only place that normalises the public keywords and refuses their combinations -- and handed down as it is: forward,
     decode, _arm_first_token, _decode_step and select_token read it, nothing below re-checks it."""
-    mode: Any = None                        # None (greedy), sample_mode's tuple, or beam_mode's tuple
+    mode: Any = None                        # None (greedy), sample_mode's tuple, beam_mode's tuple, or contrast_mode's tuple
     proc: Optional[tuple] = None            # proc_mode: (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress ids)
     stop: Optional[tuple] = None            # stop_mode: (eos ids, stop sequences)
     n_top: Optional[int] = None             # logprob_mode
@@ -248,6 +271,10 @@ class SelectionPlan(NamedTuple):
     @property
     def is_beam(self) -> bool:
         return isinstance(self.mode, tuple) and self.mode[:1] == ("beam",)
+
+    @property
+    def is_contrast(self) -> bool:
+        return isinstance(self.mode, tuple) and self.mode[:1] == ("contrast",)
 
     @property
     def beam_groups(self) -> tuple:
@@ -299,6 +326,10 @@ class SelectionPlan(NamedTuple):
         armed = cache.beam is not None and (cache.beam.k, cache.beam.G) == (self.mode[1], self.beam_groups[0]) if self.is_beam else True
         if not first and not armed:
             raise ValueError("beam decoding needs a cache armed for this num_beams (prefill with eos_token= and beam=)")
+        if self.is_contrast and not first:
+            cb = cache.contrast
+            if cb is None or (cb.k, cb.Tmax) != (self.mode[1], cache.Smax):
+                raise ValueError("contrastive decoding needs a cache armed for this top_k (prefill with eos_token= and a contrastive plan)")
         if self.proc is not None:
             ids = self.proc[3]
             if any(t >= V for t in ids):
@@ -765,6 +796,8 @@ class LMEngine:
                                        constraint=constraint, guidance=guidance, vocab=self.V)
         if plan.guidance is not None and extending:
             raise NotImplementedError("guidance does not continue from a KV cache")
+        if plan.is_contrast and extending:
+            raise NotImplementedError("contrastive search does not continue from a KV cache")
         if lengths is not None and (labels is not None or (past_key_values is not None and not extending) or not use_cache):
             raise ValueError("lengths= applies to the prefill call and to inputs_embeds appended to a cache (use_cache=True, no "
                              "labels); a ragged cache keeps its per-row positions for the steps that follow")
@@ -805,7 +838,8 @@ class LMEngine:
         if inputs_embeds is None:
             inputs_embeds = self.embed_ids(input_ids)
         if use_cache:
-            logits, cache, hs = self.prefill(inputs_embeds, cache_hint, output_hidden_states, reuse_cache, lengths=lengths)
+            logits, cache, hs = self.prefill(inputs_embeds, cache_hint, output_hidden_states, reuse_cache, lengths=lengths,
+                                             keep_x=plan.is_contrast and eos_token is not None)
             # generate() only reads the last position, so only that row is computed
             out = LMOutput(logits=logits.unsqueeze(1), past_key_values=cache, hidden_states=hs, loss=None)
             if eos_token is not None:
@@ -818,21 +852,32 @@ class LMEngine:
 
     @classmethod
     def selection_plan(cls, plan=None, *, sampling=None, beam=None, processors=None, stop=None, logprobs=None, constraint=None,
-                       guidance=None, vocab: Optional[int] = None) -> SelectionPlan:
+                       guidance=None, vocab: Optional[int] = None, contrast=None) -> SelectionPlan:
         """The SelectionPlan of the public selection keywords (forward's), checked: the one place that calls the normalisers
-        below and that refuses what beam search is not combined with.  A plan that is already built comes back as it is, so a
-        loop builds one and passes ``plan=`` on every call.  ``vocab``: the number of logits V the token ids must lie in."""
+        below and that refuses what beam search and contrastive search (``contrast`` = (top_k, penalty_alpha)) are not combined
+        with.  A plan that is already built comes back as it is, so a loop builds one and passes ``plan=`` on every call.
+        ``vocab``: the number of logits V the token ids must lie in."""
         if plan is not None:
-            if any(v is not None for v in (sampling, beam, processors, stop, logprobs, constraint, guidance)):
+            if any(v is not None for v in (sampling, beam, processors, stop, logprobs, constraint, guidance, contrast)):
                 raise ValueError("pass plan= or the selection keywords it was built from, not both")
             return plan
         for what, given in (("per-row stopping is", stop), ("token log-probabilities are", logprobs),
                             ("a constraint is", constraint), ("guidance is", guidance)):
             if beam is not None and given is not None:
                 raise NotImplementedError(f"{what} not combined with beam search")
+        # ``contrast`` = (top_k, penalty_alpha): contrastive search (DESIGN.md "Contrastive search").  What it is not combined with
+        # yet are follow-ups, not design limits: processors would run in front of its top-k, per-row stopping in its finish launch
+        for what, given in (("beam search is", beam), ("logits processors are", processors), ("per-row stopping is", stop),
+                            ("token log-probabilities are", logprobs), ("a constraint is", constraint), ("guidance is", guidance)):
+            if contrast is not None and given is not None:
+                raise NotImplementedError(f"{what} not combined with contrastive search")
         mode = cls.sample_mode(sampling)
         if beam is not None:
             mode = cls.beam_mode(beam)
+        if contrast is not None:
+            if sampling is not None:
+                raise ValueError("contrastive search is deterministic: it takes no sampling mode")
+            mode = cls.contrast_mode(contrast, vocab)
         return SelectionPlan(mode, cls.proc_mode(processors), cls.stop_mode(stop), cls.logprob_mode(logprobs, vocab),
                              cls.constraint_mode(constraint), cls.guidance_mode(guidance), vocab).keyed()
 
@@ -848,6 +893,15 @@ class LMEngine:
                 raise ValueError(f'the warp selection mode is ("warp", temperature, top_k, top_p, min_p), got {sampling!r}')
             return ("warp", float(sampling[1]), int(sampling[2]), float(sampling[3]), float(sampling[4]))
         return (float(sampling[0]), int(sampling[1]), float(sampling[2]))
+
+    @staticmethod
+    def contrast_mode(contrast, vocab: Optional[int] = None):
+        """("contrast", top_k, penalty_alpha): the token-selection mode (and graph key: both are launch arguments) of contrastive
+        search, from (top_k, penalty_alpha) checked by sampling.check_contrastive_args."""
+        from .sampling import check_contrastive_args
+        k, alpha = contrast
+        k, alpha = check_contrastive_args(alpha, k, vocab)
+        return ("contrast", k, alpha)
 
     @staticmethod
     def proc_mode(processors):
@@ -914,6 +968,11 @@ class LMEngine:
         if plan.stop is not None and int(eos_token) != plan.stop[0][0]:
             raise ValueError(f"per-row stopping pads with the first eos id: eos_token must be {plan.stop[0][0]}, got {eos_token}")
         plan.arm(cache, st, first=True)
+        if plan.is_contrast:
+            # no token yet: selecting one needs its candidates' hidden states, so the prefill's logits give the first candidate set
+            self._arm_contrast(cache, st, plan, logits)
+            out["next_token"], out["eos_state"] = None, cache.sample_state
+            return
         # step 0 of the rules runs on a copy: the caller's .logits stay raw
         out["next_token"] = self.select_token(logits.clone() if plan.rewrites_logits else logits, cache, plan, out=st.token, raw=logits)
         out["eos_state"] = cache.sample_state
@@ -1037,7 +1096,9 @@ class LMEngine:
         return lens
 
     def prefill(self, embeds: torch.Tensor, cache_hint: Optional[int] = None, want_hidden=False,
-                reuse_cache: bool = False, lengths=None):
+                reuse_cache: bool = False, lengths=None, keep_x: bool = False):
+        """``keep_x``: the last block's output for every prompt row stays on the cache (cache.prefill_x, (B, S, d)) until
+        _arm_contrast has turned it into the context store."""
         B, S, _ = embeds.shape
         ragged = lengths is not None
         if ragged:
@@ -1063,6 +1124,7 @@ class LMEngine:
         # right padding: the prefill is unchanged -- under the causal mask a valid row attends to valid keys only, and the
         # K / V the padded rows leave in slots >= len_b are overwritten by decode steps before any row reads them
         x, hs = self._blocks_prefill(embeds, cache, want_hidden)
+        cache.prefill_x = x.view(B, S, self.d) if keep_x else None
         cache._rows, cache.pending = (lens.clone() if ragged else None), None
         if ragged:
             cache.pos = int(lens.max())
@@ -1271,6 +1333,45 @@ class LMEngine:
             st.graphs.clear()
         cache.beam.reset(cache.eos)
 
+    def _arm_contrast(self, cache: KVCache, st, plan: SelectionPlan, logits: torch.Tensor):
+        """The once-per-call work of contrastive search, outside any capture: the buffers of this cache for top_k = k (re-allocated
+        -- and the steps captured on them dropped -- when (k, Smax) changes), the prompt's ln_f outputs into the context store (the
+        k rows of a sample hold the same prompt: row b * k is read), ctx_len = the prompt lengths, and the first candidate set from
+        the prefill's logits into the token rows the first step embeds."""
+        _, k, _ = plan.mode
+        R = cache.B
+        x, cache.prefill_x = cache.prefill_x, None
+        if R % k:
+            raise ValueError(f"contrastive search over {R} cache rows with top_k = {k}: rows must be samples x top_k")
+        if k > self.V:
+            raise ValueError(f"top_k = {k} needs a vocabulary of at least {k} tokens")
+        if x is None:
+            raise ValueError("contrastive search is armed by the prefill call (inputs_embeds with eos_token= and the plan)")
+        cb = cache.contrast
+        if cb is None or (cb.k, cb.Tmax) != (k, cache.Smax):
+            cache.contrast = cb = ContrastBuffers(cache, k, self.d)
+            cache._drop_graphs(lambda key: key.contrast)
+        B, S = R // k, x.shape[1]
+        h = ops.layernorm(x[::k].reshape(B * S, self.d), self.lnf_g, self.lnf_b, self.eps)     # the op every later hidden row comes from
+        cb.ctx[:, :S].copy_(h.view(B, S, self.d))
+        cb.ctx_len.copy_(cache.rows_pos()[::k].to(torch.int32), non_blocking=True)
+        cb.src.copy_(torch.arange(0, R, k, dtype=torch.int32), non_blocking=True)
+        ops.contrastive_topk(logits, cb.src, k, st.token, cb.cand_p)
+
+    def _select_contrast(self, x: torch.Tensor, cache: KVCache, st, plan: SelectionPlan):
+        """The contrastive step's launches behind the head (DESIGN.md "Contrastive search"): ln_f of the candidates' rows (the wide
+        step has it in st.lnf already), the similarity against the context store, the selection with greedy decoding's
+        bookkeeping, the selected row's new K / V to its siblings, the next candidate set from the selected row's logits."""
+        cb = cache.contrast
+        _, k, alpha = plan.mode
+        if cache.B <= 16:
+            ops.layernorm(x, self.lnf_g, self.lnf_b, self.eps, out=st.lnf)
+        ops.contrastive_sim(st.lnf, cb.ctx, cb.ctx_len, k, cb.part, len_max=cache.pos)
+        ops.contrastive_finish(cb.part, cb.cand_p, alpha, st.lnf, cb.ctx, cb.ctx_len, cb.src, st.token, cache.eos, cache.sample_state,
+                               cache.pos, d_pos=cache.d_pos, history=cache.history, pos_stride=cache.pos_stride)
+        ops.kv_broadcast(cache.k, cache.v, k, cb.src, cache.d_pos, pos_stride=cache.pos_stride, pos_delta=-1)
+        ops.contrastive_topk(st.logits[:, : self.V], cb.src, k, st.token, cb.cand_p)
+
     def _select_beam(self, logits: torch.Tensor, cache: KVCache, plan: SelectionPlan, advance: bool):
         """The beam step's three launches: per-row top 2k, the bookkeeping of every sample, the K / V reorder by parent.  With
         processors, their launch has already turned the rows into (processed) log_softmax scores.  With G > 1 groups the lists
@@ -1385,7 +1486,9 @@ class LMEngine:
         else:
             head = self.head_w8 if st.w8 else self.head_w4 if st.w4 else self.head_dec
             ops.gemm_skinny(x, head, out=st.logits, ln_fold=(head.colsum, self.d, self.eps))
-        if not plan.select:
+        if plan.is_contrast and plan.select:
+            self._select_contrast(x, cache, st, plan)
+        elif not plan.select:
             ops.advance_pos(cache.d_pos, pos_stride=cache.pos_stride)   # teacher-forced position: nothing selected, nothing recorded
         elif plan.second_buffer:
             # the processors run in place: they and the selection get a copy (one device copy inside the step), the

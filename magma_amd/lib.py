@@ -19,7 +19,7 @@ MG_A_DENSE, MG_A_CONV3X3 = 0, 1
 MG_AUX_NONE, MG_AUX_RELU_GATE, MG_AUX_GELU_GRAD, MG_AUX_MUL, MG_AUX_QUICK_GELU_GRAD = 0, 1, 2, 3, 4
 
 
-ABI_VERSION = 21     # include/magma_hip.h MG_ABI_VERSION
+ABI_VERSION = 22     # include/magma_hip.h MG_ABI_VERSION
 
 
 class MagmaHipError(RuntimeError):
@@ -140,6 +140,11 @@ SYMBOLS = {
     "mg_beam_finish_groups": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _i64, C.c_double, _i32, _i32, _vp, _vp,
                                         _i32, C.POINTER(BeamState), _vp]),
     "mg_kv_reorder_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
+    "mg_contrastive_topk_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "mg_contrastive_sim_bf16": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _vp]),
+    "mg_contrastive_finish": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _f32, _vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i64,
+                                        _i32, _i64, _vp, _vp, _i32, _i32, _vp]),
+    "mg_kv_broadcast_bf16": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp]),
     "mg_patchify_bf16": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "mg_vit_embed_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "mg_attn_small_bf16": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),

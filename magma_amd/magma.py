@@ -288,7 +288,8 @@ class Magma(nn.Module):
                  min_new_tokens: int = 0, suppress_tokens=None, eos_token=None, stop_sequences=None, stop_per_row: bool = None,
                  return_finish: bool = False, sampler: str = "reference", min_p: float = 0.0, return_logprobs: bool = False,
                  top_logprobs: int = 0, constraint=None, guidance_scale: float = 1.0, negative_embeddings=None,
-                 negative_lengths=None, guidance_min_p: float = 0.0, num_beam_groups: int = 1, diversity_penalty: float = 0.0):
+                 negative_lengths=None, guidance_min_p: float = 0.0, num_beam_groups: int = 1, diversity_penalty: float = 0.0,
+                 penalty_alpha: float = 0.0):
         """reference magma.py:214-236 (+ stop_on_eos / seed / eos_check_every / lengths, see sampling.generate).
         ``lengths``: prompts of different lengths, right-padded (embed_batch); ``embeddings`` may also be a list of
         per-sample (1, s_i, d) tensors.  ``num_beams`` > 1: beam search (length_penalty, early_stopping,
@@ -311,7 +312,9 @@ class Magma(nn.Module):
         the token step; the output is laid out as for ``embeddings`` alone (see sampling.generate).
         ``num_beam_groups`` (a divisor of ``num_beams``) / ``diversity_penalty``: diverse beam search -- the beams run in groups
         that are penalised for selecting the tokens earlier groups selected at the same step, and ``num_return_sequences`` takes
-        the groups' hypotheses round-robin: several different captions of one image (see sampling.generate)."""
+        the groups' hypotheses round-robin: several different captions of one image (see sampling.generate).
+        ``penalty_alpha`` in (0, 1] with ``top_k`` in [1, 16]: contrastive search -- among the ``top_k`` most probable tokens the one
+        whose hidden state is least similar to the context's, deterministic (see sampling.generate)."""
         torch.cuda.set_device(self.device)
         return generate(self, embeddings=embeddings, max_steps=max_steps, temperature=temperature, top_k=top_k,
                         top_p=top_p, decode=decode, stop_on_eos=stop_on_eos, seed=seed, eos_check_every=eos_check_every,
@@ -323,7 +326,8 @@ class Magma(nn.Module):
                         stop_sequences=stop_sequences, stop_per_row=stop_per_row, return_finish=return_finish, sampler=sampler,
                         min_p=min_p, return_logprobs=return_logprobs, top_logprobs=top_logprobs, constraint=constraint,
                         guidance_scale=guidance_scale, negative_embeddings=negative_embeddings, negative_lengths=negative_lengths,
-                        guidance_min_p=guidance_min_p, num_beam_groups=num_beam_groups, diversity_penalty=diversity_penalty)
+                        guidance_min_p=guidance_min_p, num_beam_groups=num_beam_groups, diversity_penalty=diversity_penalty,
+                        penalty_alpha=penalty_alpha)
 
     @torch.no_grad()
     def choose(self, embeddings, choices, lengths=None, **generate_kwargs):

@@ -1028,6 +1028,91 @@ def kv_reorder(kcache: torch.Tensor, vcache: torch.Tensor, kstage: torch.Tensor,
                                       parent.data_ptr(), d_pos.data_ptr(), ps, _stream()), "mg_kv_reorder_bf16")
 
 
+CONTRASTIVE_CHUNK, CONTRASTIVE_MAX_K = 32, 16                           # include/magma_hip.h MG_CONTRASTIVE_*
+
+
+def contrastive_chunks(Tmax: int) -> int:
+    """Context chunks per sample of a store of ``Tmax`` positions: the middle extent of contrastive_sim's ``part``."""
+    return (Tmax + CONTRASTIVE_CHUNK - 1) // CONTRASTIVE_CHUNK
+
+
+def contrastive_topk(logits: torch.Tensor, src: torch.Tensor, k: int, token: torch.Tensor, cand_p: torch.Tensor):
+    """Per sample b the ``k`` most probable tokens of logits row ``src[b]`` (fp32 (B * k, V); ``src`` int32 (B,)), raw logit
+    descending, lower id first, into ``token[b * k + j]`` (int64 (B * k,): the next step's input ids) and their fp32 softmax
+    probabilities into ``cand_p`` (B, k) (mg_contrastive_topk_f32).  Enqueue-only."""
+    _need_gpu(logits, src, token, cand_p)
+    assert logits.dtype == torch.float32 and logits.ndim == 2 and logits.stride(1) == 1
+    R, V = logits.shape
+    B = src.numel()
+    assert src.dtype == torch.int32 and src.is_contiguous()
+    assert token.dtype == torch.int64 and token.is_contiguous() and token.numel() == B * k
+    assert cand_p.dtype == torch.float32 and cand_p.is_contiguous() and cand_p.numel() == B * k
+    check(L.load().mg_contrastive_topk_f32(logits.data_ptr(), logits.stride(0), R, V, src.data_ptr(), B, int(k), token.data_ptr(),
+                                           cand_p.data_ptr(), _stream()), "mg_contrastive_topk_f32")
+
+
+def _contrast_store(hidden, ctx, ctx_len, k):
+    """The checked geometry (B, Tmax, d, n_chunk) of a contrastive launch's hidden rows and context store."""
+    assert hidden.dtype == BF16 and hidden.ndim == 2 and hidden.stride(1) == 1
+    assert ctx.dtype == BF16 and ctx.ndim == 3 and ctx.is_contiguous()
+    B, Tmax, d = ctx.shape
+    assert hidden.shape == (B * k, d), f"hidden must be ({B * k}, {d}), got {tuple(hidden.shape)}"
+    assert ctx_len.dtype == torch.int32 and ctx_len.is_contiguous() and ctx_len.numel() == B
+    return B, Tmax, d, contrastive_chunks(Tmax)
+
+
+def contrastive_sim(hidden: torch.Tensor, ctx: torch.Tensor, ctx_len: torch.Tensor, k: int, part: torch.Tensor, len_max: int):
+    """part[b, c, j] (fp32 (B, contrastive_chunks(Tmax), k)) = the largest cosine of candidate row ``hidden[b * k + j]`` (bf16
+    (B * k, d)) with the valid positions (< ``ctx_len[b]``) of chunk c of ``ctx[b]`` (bf16 (B, Tmax, d)); -1e30 for a chunk without
+    one (mg_contrastive_sim_bf16).  ``len_max``: the caller's host bound of ctx_len's entries (checked against Tmax; the device
+    values are clamped).  Enqueue-only."""
+    _need_gpu(hidden, ctx, ctx_len, part)
+    B, Tmax, d, n_chunk = _contrast_store(hidden, ctx, ctx_len, k)
+    assert part.dtype == torch.float32 and part.is_contiguous() and part.numel() == B * n_chunk * k
+    check(L.load().mg_contrastive_sim_bf16(hidden.data_ptr(), hidden.stride(0), ctx.data_ptr(), B, Tmax, d, ctx_len.data_ptr(),
+                                           int(len_max), int(k), part.data_ptr(), n_chunk, _stream()), "mg_contrastive_sim_bf16")
+    return part
+
+
+def contrastive_finish(part: torch.Tensor, cand_p: torch.Tensor, alpha: float, hidden: torch.Tensor, ctx: torch.Tensor,
+                       ctx_len: torch.Tensor, src: torch.Tensor, token: torch.Tensor, eos: int, state: torch.Tensor, len_max: int,
+                       d_pos: Optional[torch.Tensor] = None, delta: int = 1, history: Optional[torch.Tensor] = None, *,
+                       pos_stride: int = 0):
+    """The selection and the bookkeeping of a contrastive step (mg_contrastive_finish; host statement: sampling.contrastive_rank):
+    per sample the first j with the largest (1 - alpha) * cand_p[b, j] - alpha * max_c part[b, c, j]; its token (``token[b * k + j]``)
+    into column ``state[0]`` of the k history rows of the sample, ``src[b] = b * k + j``, its hidden row appended to ``ctx[b]``,
+    ``ctx_len[b] += 1``; then sample_finish's bookkeeping over the B selected tokens, every row's position advanced."""
+    _need_gpu(part, cand_p, hidden, ctx, ctx_len, src, token, state, d_pos, history)
+    k = cand_p.shape[-1] if cand_p.ndim == 2 else 0
+    B, Tmax, d, n_chunk = _contrast_store(hidden, ctx, ctx_len, k)
+    assert cand_p.dtype == torch.float32 and cand_p.is_contiguous() and cand_p.shape == (B, k)
+    assert part.dtype == torch.float32 and part.is_contiguous() and part.numel() == B * n_chunk * k
+    assert src.dtype == torch.int32 and src.is_contiguous() and src.numel() == B
+    assert token.dtype == torch.int64 and token.is_contiguous() and token.numel() == B * k
+    assert state.dtype == torch.int32 and state.numel() >= 2
+    ps = 0 if d_pos is None else _pos_stride(d_pos, B * k, pos_stride)
+    if history is not None:
+        assert history.dtype == torch.int64 and history.ndim == 2 and history.stride(1) == 1 and history.shape[0] == B * k
+    check(L.load().mg_contrastive_finish(part.data_ptr(), n_chunk, cand_p.data_ptr(), B, k, float(alpha), hidden.data_ptr(),
+                                         hidden.stride(0), d, ctx.data_ptr(), Tmax, ctx_len.data_ptr(), int(len_max), src.data_ptr(),
+                                         token.data_ptr(), _p(history), 0 if history is None else history.stride(0),
+                                         0 if history is None else history.shape[1], int(eos), state.data_ptr(), _p(d_pos),
+                                         int(delta), ps, _stream()), "mg_contrastive_finish")
+
+
+def kv_broadcast(kcache: torch.Tensor, vcache: torch.Tensor, k: int, src: torch.Tensor, d_pos: torch.Tensor, *, pos_stride: int = 0,
+                 pos_delta: int = 0):
+    """In every layer and head of the K / V caches [L, R, H, Smax, 256]: position ``d_pos[r] + pos_delta`` of row ``src[r // k]``
+    copied to the other rows r of its group of ``k`` (mg_kv_broadcast_bf16).  One position, not kv_reorder's whole rows."""
+    _need_gpu(kcache, vcache, src, d_pos)
+    Lr, R, H, Smax, hd = kcache.shape
+    assert hd == 256 and all(t.shape == kcache.shape and t.dtype == BF16 and t.is_contiguous() for t in (kcache, vcache))
+    assert src.dtype == torch.int32 and src.is_contiguous() and src.numel() * k == R
+    ps = _pos_stride(d_pos, R, pos_stride)
+    check(L.load().mg_kv_broadcast_bf16(kcache.data_ptr(), vcache.data_ptr(), Lr, R, H, Smax, int(k), src.data_ptr(), d_pos.data_ptr(),
+                                        ps, int(pos_delta), _stream()), "mg_kv_broadcast_bf16")
+
+
 def patchify(img: torch.Tensor, P: int) -> torch.Tensor:
     """img [B,3,H,W] bf16 -> [B*(H/P)*(W/P), 3*P*P] rows in (c, py, px) order (im2col of the stride-P patch conv)."""
     _need_gpu(img)

@@ -1063,6 +1063,106 @@ def beam_margin(record: list) -> float:
     return min(gaps)
 
 
+def check_contrastive_args(penalty_alpha=0.0, top_k=0, vocab: int = None):
+    """ValueError for arguments contrastive search does not take; returns None when it is off (``penalty_alpha`` == 0: ``top_k``
+    is then the sampler's keyword and is not looked at), else (top_k, penalty_alpha as a float)."""
+    a = penalty_alpha
+    if isinstance(a, bool) or not isinstance(a, (int, float)) or not math.isfinite(a) or not 0.0 <= a <= 1.0:
+        raise ValueError(f"penalty_alpha must be a finite number in [0, 1] (0 = contrastive search off), got {a!r}")
+    if a == 0:
+        return None
+    k = top_k
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise ValueError(f"top_k must be an integer in [1, {MAX_BEAMS}] with penalty_alpha > 0, got {k!r}")
+    if k == 0:
+        raise ValueError(f"penalty_alpha = {a} needs top_k candidates: pass top_k in [1, {MAX_BEAMS}] (transformers' examples use 4)")
+    if not 1 <= k <= MAX_BEAMS:
+        raise ValueError(f"top_k must be an integer in [1, {MAX_BEAMS}] with penalty_alpha > 0, got {k!r}")
+    if vocab is not None and k > vocab:
+        raise ValueError(f"top_k = {k} exceeds the vocabulary of {vocab} tokens")
+    return k, float(a)
+
+
+def contrastive_rank(context, ctx_len, cand_hidden, cand_p, penalty_alpha: float):
+    """Steps 3-4 of contrastive search's rule for B samples, in fp64: ``context`` (B, T, d) the context hidden states, of which
+    the first ``ctx_len[b]`` count; ``cand_hidden`` (B, k, d) and ``cand_p`` (B, k) the candidates' hidden states and
+    probabilities.  penalty_j = max over the valid c of cos(h_j, c) (a zero vector gives cosine 0; no valid position gives 0),
+    score_j = (1 - penalty_alpha) * p_j - penalty_alpha * penalty_j.  Returns (selected (B,) int64: the first j with the largest
+    score, score (B, k) fp64, penalty (B, k) fp64).  The host statement mg_contrastive_sim_bf16 / mg_contrastive_finish are
+    tested against."""
+    c, h = context.detach().cpu().double(), cand_hidden.detach().cpu().double()
+    ctx_len = torch.as_tensor(ctx_len).cpu().to(torch.int64)
+    den = h.norm(dim=-1)[:, :, None] * c.norm(dim=-1)[:, None, :]
+    cos = torch.einsum("bkd,btd->bkt", h, c)
+    cos = torch.where(den > 0, cos / den.clamp_min(1e-300), torch.zeros_like(cos))
+    valid = torch.arange(c.shape[1])[None, :] < ctx_len[:, None]
+    cos = cos.masked_fill(~valid[:, None, :], -math.inf)
+    pen = cos.max(dim=-1).values if c.shape[1] else torch.full(h.shape[:2], -math.inf, dtype=torch.float64)
+    pen = torch.where(torch.isinf(pen), torch.zeros_like(pen), pen)
+    score = (1.0 - penalty_alpha) * cand_p.detach().cpu().double() - penalty_alpha * pen
+    return torch.argmax(score, dim=-1), score, pen
+
+
+@torch.no_grad()
+def contrastive_search(step: Callable, prompt_hidden, first_logits, lengths, top_k: int, penalty_alpha: float, max_steps: int,
+                       eos_token: int, stop_on_eos: bool = True):
+    """Contrastive search (Su et al. 2022, "A Contrastive Framework for Neural Text Generation"; ``penalty_alpha`` / ``top_k`` of
+    transformers 4.x's ``generate``), stated from the paper: the host statement the device kernels (csrc/sampling.hip,
+    contrastive_*) are tested against.
+
+    Per sample a list C of context hidden states -- ``prompt_hidden`` (B, S, d), of which the first ``lengths[b]`` count (None: all
+    S), then one per generated token.  Per step: p = softmax(logits) in fp32 of the last context position (``first_logits``
+    (B, V), then the selected candidate's); the candidates are the ``top_k`` most probable tokens, ordered by descending
+    probability, ties by smaller id (taken on the logits, which p is monotone in); ``step`` forwards them; the candidate with the
+    first largest (1 - alpha) * p_j - alpha * max_{c in C} cos(h_j, c) (``contrastive_rank``) is emitted, its hidden state joins C,
+    its logits are the next step's.  Every generated token costs one ``step``, the first included.  With ``stop_on_eos`` the loop
+    ends after the first step at which every sample emitted ``eos_token`` (greedy decoding's rule).
+
+    ``step(tokens, parents)`` returns (fp32 logits (B*k, V), hidden states (B*k, d)) of the candidate ``tokens`` (B*k,) int64,
+    sample-major, each forwarded against the cache as it stands.  ``parents`` is None on the first call and afterwards (B*k,)
+    int64: the row of the PREVIOUS call whose K / V every row now continues (b*k + the selected j, k times per sample) -- the
+    callback owns the cache, as in beam_search.
+
+    Returns (tokens (B, n) int64, record): one dict per step with ``cand`` (B, k) ids, ``p``, ``penalty``, ``score`` (B, k),
+    ``selected`` (B,) and ``gap`` (B,), the best score less the second best (inf at top_k = 1), for contrastive_margin()."""
+    top_k, penalty_alpha = check_contrastive_args(penalty_alpha, top_k, first_logits.shape[-1])
+    B, V = first_logits.shape
+    k = top_k
+    hid = prompt_hidden.detach().cpu()
+    S, d = hid.shape[1], hid.shape[2]
+    ctx = torch.zeros(B, S + max_steps, d, dtype=hid.dtype)
+    ctx[:, :S] = hid
+    ctx_len = torch.full((B,), S, dtype=torch.int64) if lengths is None else torch.as_tensor(lengths).cpu().to(torch.int64).clone()
+    logits = first_logits.detach().float().cpu()
+    rows = torch.arange(B)
+    tokens, record, parents = [], [], None
+    for _ in range(max_steps):
+        p = F.softmax(logits, dim=-1)
+        cand = torch.sort(logits, dim=-1, descending=True, stable=True).indices[:, :k]
+        cand_p = torch.take_along_dim(p, cand, dim=1)
+        lg, h = step(cand.reshape(-1), parents)
+        lg, h = lg.detach().float().cpu().view(B, k, V), h.detach().cpu().view(B, k, d)
+        sel, score, pen = contrastive_rank(ctx, ctx_len, h, cand_p, penalty_alpha)
+        top2 = torch.topk(score, min(2, k), dim=-1).values
+        gap = top2[:, 0] - top2[:, 1] if k > 1 else torch.full((B,), math.inf, dtype=torch.float64)
+        record.append(dict(cand=cand, p=cand_p, penalty=pen, score=score, selected=sel, gap=gap))
+        tok = cand[rows, sel]
+        ctx[rows, ctx_len] = h[rows, sel].to(ctx.dtype)
+        ctx_len += 1
+        logits = lg[rows, sel]
+        parents = (rows * k + sel).repeat_interleave(k)
+        tokens.append(tok)
+        if stop_on_eos and eos_token is not None and bool((tok == eos_token).all()):
+            break
+    return (torch.stack(tokens, 1) if tokens else torch.zeros(B, 0, dtype=torch.int64)), record
+
+
+def contrastive_margin(record: list) -> float:
+    """Smallest gap between the best and the second-best score of any sample at any step of a recorded contrastive_search run.  A
+    run on other arithmetic makes the same selections while its scores stay within half of this of the recorded ones."""
+    return min([float("inf")] + [float(r["gap"].min()) for r in record])
+
+
 def _logit_count(model):
     """V, the number of logits of the model's LM (rows of lm_head), or None when the LM object does not say."""
     cfg = getattr(getattr(model, "lm", None), "config", None)
@@ -1081,7 +1181,7 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
              return_finish: bool = False, sampler: str = "reference", min_p: float = 0.0, return_logprobs: bool = False,
              top_logprobs: int = 0, constraint=None, guidance_scale: float = 1.0, negative_embeddings=None,
              negative_lengths=None, guidance_min_p: float = 0.0, num_beam_groups: int = 1,
-             diversity_penalty: float = 0.0) -> Union[List[str], torch.Tensor]:
+             diversity_penalty: float = 0.0, penalty_alpha: float = 0.0) -> Union[List[str], torch.Tensor]:
     """reference sampling.py:43-121.  Token selection (argmax, or top-k / the reference's top-p rule / softmax /
     multinomial) and the ``(next_token == eos).all()`` test run on the device inside the captured token step; the host
     reads the recorded "first all-eos step" every ``eos_check_every`` steps (default 8, MAGMA_EOS_CHECK_EVERY) instead of
@@ -1187,7 +1287,21 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     not finite, ``guidance_min_p`` outside [0, 1], a scale != 1 without a negative prompt, a negative prompt or ``guidance_min_p``
     at scale 1, row counts or hidden sizes that do not match.  Not combined with beam search, ``past_key_values`` or
     ``return_past_key_values`` (NotImplementedError): a guided cache holds two conversations per sample.  At the defaults the
-    call is bit for bit what it was, and nothing is launched or allocated."""
+    call is bit for bit what it was, and nothing is launched or allocated.
+
+    Contrastive search (DESIGN.md "Contrastive search"; Su et al. 2022; ``penalty_alpha`` / ``top_k`` of transformers 4.x):
+    ``penalty_alpha`` in (0, 1] with ``top_k`` in [1, 16] selects, among the ``top_k`` most probable next tokens, the one with the
+    largest (1 - penalty_alpha) * p - penalty_alpha * (largest cosine of its hidden state -- the output of ln_f -- with the hidden
+    state of any prompt position or earlier generated token): deterministic, and built for open-ended text such as captions,
+    where greedy and beam search repeat themselves (``contrastive_search`` above; 0.6 and 4 are the paper's values).  ``top_k=0``
+    with ``penalty_alpha`` > 0 is a ValueError.  ``temperature``, ``top_p``, ``seed`` and ``sampler`` do not apply, as with beam
+    search.  Ragged prompts, ``decode``, ``stop_on_eos``, ``eos_check_every`` and the one-eos batch-wide stopping rule are greedy
+    decoding's.  The HIP engine runs a cache of B * top_k rows -- every candidate is one row of the captured token step, whose
+    weight stream they share -- with five small launches behind the head in place of the argmax and its bookkeeping; any other LM
+    object runs the host statement on ``output_hidden_states``.  Not yet combined (NotImplementedError) with beam search /
+    ``return_scores``, the logits processors, per-row stopping / several eos ids / ``return_finish``, ``return_logprobs``,
+    ``constraint``, guidance, ``past_key_values`` / ``return_past_key_values``.  ``penalty_alpha=0.0`` (the default) is the call as
+    it was, bit for bit, with the same launches and nothing allocated."""
     if eos_token is None or (isinstance(eos_token, int) and not eos_token):
         eos_token = model.eos_token
     early_stopping = check_beam_args(num_beams, num_return_sequences, early_stopping, num_beam_groups, diversity_penalty,
@@ -1218,6 +1332,22 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
         raise NotImplementedError("guidance neither continues from nor returns a KV cache (past_key_values / "
                                   "return_past_key_values): a guided cache holds two conversations per row")
     continuing = past_key_values is not None or return_past_key_values
+    contrast = check_contrastive_args(penalty_alpha, top_k, _logit_count(model))
+    if contrast is not None:
+        for what, given in (("beam search (num_beams > 1 / return_scores=True) is", num_beams > 1 or return_scores),
+                            ("the logits processors are", proc is not None),
+                            ("per-row stopping (a list of eos ids, stop_sequences, stop_per_row, return_finish) is",
+                             stop is not None or return_finish),
+                            ("token log-probabilities (return_logprobs / top_logprobs) are", n_top is not None),
+                            ("a constraint is", constraint is not None), ("guidance is", guide is not None),
+                            ("a KV cache (past_key_values / return_past_key_values) is", continuing)):
+            if given:
+                raise NotImplementedError(f"{what} not combined with contrastive search (penalty_alpha > 0) yet")
+        if min_p > 0:
+            raise ValueError("min_p applies to sampled selection: contrastive search (penalty_alpha > 0) would drop it")
+        embeddings, lengths = prompt_batch(embeddings, lengths, check=False)
+        return _generate_contrastive(model, embeddings, max_steps, eos_token, decode, eos_check_every, lengths, contrast[0],
+                                     contrast[1], stop_on_eos)
     if continuing and (num_beams > 1 or return_scores):
         raise NotImplementedError("beam search neither continues from nor returns a KV cache (past_key_values / "
                                   "return_past_key_values need num_beams=1 and return_scores=False)")
@@ -1931,3 +2061,65 @@ def _generate_beam(model, embeddings, max_steps, eos_token, decode, eos_check_ev
         out = [model.tokenizer.decode(remove_tokens_after_eos(row, eos_token, model.image_token)) for row in out]
     model.train(was_training)
     return (out, scores.float().cpu()) if return_scores else out
+
+
+@torch.no_grad()
+def _generate_contrastive(model, embeddings, max_steps, eos_token, decode, eos_check_every, lengths, k, alpha, stop_on_eos):
+    """generate()'s contrastive search over the prompt batch it has normalised: on the HIP engine's device -- one prefill over
+    B * k rows (every sample k times, sample-major, as beam search lays them out), then one token step per generated token,
+    the first included --, or contrastive_search on the host."""
+    was_training = model.training
+    on_device = getattr(model.lm, "device_token_selection", False)
+    embeddings, lengths = prompt_batch(embeddings, lengths, per_row=on_device)
+    b, s, _ = embeddings.shape
+    dev = embeddings.device
+    model.eval()
+    emb = embeddings.repeat_interleave(k, dim=0)           # B prompts -> B*k rows, sample-major
+    if on_device:
+        from .engine import LMEngine
+        plan = LMEngine.selection_plan(contrast=(k, alpha), vocab=model.lm.engine.V)
+        every = eos_check_every or int(os.environ.get("MAGMA_EOS_CHECK_EVERY", "8"))
+        o = model.lm(inputs_embeds=emb, use_cache=True, past_key_values=None, cache_hint=max_steps, reuse_cache=True,
+                     eos_token=eos_token, plan=plan, lengths=None if lengths is None else lengths.repeat_interleave(k))
+        past, n_gen = o.past_key_values, 0
+        for i in range(max_steps):
+            o = model.lm(input_ids=None, use_cache=True, past_key_values=past, feed_back=True, plan=plan)
+            n_gen += 1
+            if stop_on_eos and eos_token is not None and ((i + 1) % every == 0 or i + 1 == max_steps):
+                first = int(o.eos_state[1])                 # one host sync per `every` steps
+                if first >= 0:
+                    n_gen = first + 1
+                    break
+        toks = past.history[::k, :n_gen]                    # the k rows of a sample hold the same history
+    else:
+        cache = {}
+        ln_f = getattr(getattr(model.lm, "transformer", None), "ln_f", None)
+
+        def hidden(o):      # hidden_states[-1] of transformers' GPT-J: the output of ln_f
+            h = o.hidden_states[-1]
+            return ln_f(h) if ln_f is not None else h
+
+        def step(tokens, parents):
+            past = cache["past"] if parents is None else reorder_past(cache["past"], parents.to(dev))
+            o = model.lm(input_ids=tokens[:, None].to(dev), use_cache=True, past_key_values=past, output_hidden_states=True)
+            cache["past"] = o.past_key_values
+            return o.logits[:, -1, :].float(), hidden(o)[:, -1, :]
+
+        o = model.lm(inputs_embeds=emb, use_cache=True, past_key_values=None, output_hidden_states=True)
+        cache["past"] = o.past_key_values
+        toks, _ = contrastive_search(step, hidden(o)[::k], o.logits[::k, -1, :].float(), None, k, alpha, max_steps, eos_token,
+                                     stop_on_eos)
+    toks = toks.to(dev)
+    n = toks.shape[1]
+    out = torch.full((b, s + n), eos_token, dtype=torch.long, device=dev)
+    if lengths is None:
+        out[:, :s] = model.image_token
+        out[:, s:] = toks
+    else:                                                    # ragged: row b's tokens follow its own prompt, eos after them
+        lens = lengths.to(dev)[:, None]
+        out.masked_fill_(torch.arange(s + n, device=dev)[None, :] < lens, model.image_token)
+        out.scatter_(1, lens + torch.arange(n, device=dev)[None, :], toks)
+    if decode:
+        out = [model.tokenizer.decode(remove_tokens_after_eos(row, eos_token, model.image_token)) for row in out]
+    model.train(was_training)
+    return out
