@@ -159,7 +159,19 @@ typedef struct mg_epilogue {
  * K6 (ImagePrefix proj), K2/K3 (CLIP 1x1 / 3x3 convs as implicit GEMM).
  * C[M,N] = A[M,K] * W[N,K]^T, bf16 in, fp32 accumulate, MFMA 16x16x32.
  * Replaces F.linear / F.conv2d calls reached from reference
- * magma/image_prefix.py:83,93 and the LM call at magma/magma.py:270-274.    */
+ * magma/image_prefix.py:83,93 and the LM call at magma/magma.py:270-274.
+ *
+ * OPERAND SIZE (every entry point of this header): an operand of any size is either addressed correctly or refused with an
+ * error, never misread.  Leading dimensions and strides are int64_t and the kernels scale row indices in 64 bits; where a
+ * kernel keeps a 32-bit offset, its launcher states the limit and returns MG_ERR_SHAPE past it:
+ *   - 256x256 GEMM (tile_hint 0 on large shapes, or 256 ..): the loaders add a 32-bit per-lane byte offset to the workgroup's
+ *     64-bit row origin, so 256 rows of A, and of a row-major W, must span less than 2^32 bytes (lda, ldw < 2^23 bf16 elements
+ *     / 2^24 fp8 bytes) and a fragment-tiled W less than 2^32 bytes as a whole.  M * lda and N * ldw themselves are not bounded.
+ *     Past the limit tile_hint 0 runs the 128x128 kernel (64-bit addresses); a forced 256 tile, and the MX output copy that only
+ *     that kernel writes, are refused.
+ *   - row attention (mg_attn_fwd_rows_bf16, mg_attn_bwd_rows_bf16): S * ld_row * 2 < 2^31;  cached / tree prefill:
+ *     Smax * 256 * 2 < 2^31;  decode attention: Smax <= its stated maximum context.
+ * DESIGN.md "Operands past 4 GiB" lists every kernel; tests/test_far_operands_gpu.py holds them to it.                        */
 typedef struct mg_gemm_desc {
   const mg_bf16* A;
   int64_t lda;

@@ -416,16 +416,21 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
   const int li = lane & 15, lq = lane >> 4;
 
   // ---- DMA sources: per half-tile this wave moves 2 pieces of 1 KiB ----
-  int a_off[2][2], b_off[2][2];                   // element offsets (< 2^31 on this path)
+  // The workgroup's row origin goes into the uniform 64-bit bases below (scalar arithmetic), so the per-lane element offsets
+  // span at most the tile's 255 rows: gemm_dispatch sends only ld < 2^23 elements here (256 * ld * 2 bytes < 2^32), and A or a
+  // row-major W of any size is addressed correctly.  (Fragment-tiled W: whole-panel offsets, bounded by gemm_dispatch too.)
+  const mg_bf16* const a_base = p.A + (int64_t)m0 * p.lda;
+  const mg_bf16* const w_base = WLAYOUT == MG_W_ROWMAJOR ? p.W + (int64_t)n0 * p.ldw : p.W;
+  int a_off[2][2], b_off[2][2];                   // element offsets from a_base / w_base (< 2^31)
 #pragma unroll
   for (int h = 0; h < 2; ++h)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int r = h * 128 + wave * 16 + j * 8 + (lane >> 3);
       const int gch = (lane & 7) ^ ((r >> 1) & 7);
-      a_off[h][j] = (int)(min(m0 + r, p.M - 1) * p.lda + gch * 8);
+      a_off[h][j] = (min(m0 + r, p.M - 1) - m0) * (int)p.lda + gch * 8;
       if (WLAYOUT == MG_W_ROWMAJOR) {
-        b_off[h][j] = (int)(min(n0 + r, p.N - 1) * p.ldw + gch * 8);
+        b_off[h][j] = (min(n0 + r, p.N - 1) - n0) * (int)p.ldw + gch * 8;
       } else {
         const int ntiles = (p.N + 15) >> 4;
         const int nt = min((n0 >> 4) + h * 8 + wave, ntiles - 1);
@@ -436,7 +441,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
 #define MG_DMA_A(kt, h)                                                                                  \
   {                                                                                                      \
     char* dst_ = smem + ((kt) & 1) * G256_BUF + ((h) * 128 + wave * 16) * 128;                           \
-    const mg_bf16* src_ = p.A + (int64_t)KT_SRC(kt) * p.a_kt;                            \
+    const mg_bf16* src_ = a_base + (int64_t)KT_SRC(kt) * p.a_kt;                          \
     if (ABL != 4 || abl_on) {                                                                            \
       glds16s(src_, (uint32_t)a_off[h][0] * 2u, dst_);                                                   \
       glds16s(src_, (uint32_t)a_off[h][1] * 2u, dst_ + 1024);                                            \
@@ -447,11 +452,11 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
     char* base_ = smem + ((kt) & 1) * G256_BUF + G256_TILE;                                              \
     if (ABL == 4 && !abl_on) {                                                                           \
     } else if (WLAYOUT == MG_W_ROWMAJOR) {                                                               \
-      const mg_bf16* src_ = p.W + (int64_t)KT_SRC(kt) * 64;                          \
+      const mg_bf16* src_ = w_base + (int64_t)KT_SRC(kt) * 64;                        \
       glds16s(src_, (uint32_t)b_off[h][0] * 2u, base_ + ((h) * 128 + wave * 16) * 128);                  \
       glds16s(src_, (uint32_t)b_off[h][1] * 2u, base_ + ((h) * 128 + wave * 16 + 8) * 128);              \
     } else {                                                                                             \
-      const mg_bf16* src_ = p.W + (int64_t)KT_SRC(kt) * 1024;                        \
+      const mg_bf16* src_ = w_base + (int64_t)KT_SRC(kt) * 1024;                      \
       glds16s(src_, (uint32_t)b_off[h][0] * 2u, base_ + (((h) * 8 + wave) * 2) * 1024);                  \
       glds16s(src_, (uint32_t)b_off[h][1] * 2u, base_ + (((h) * 8 + wave) * 2 + 1) * 1024);              \
     }                                                                                                    \
@@ -470,10 +475,10 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int ra = (wave >> 2) * 128 + u * 64 + (wave & 3) * 16 + j * 8 + (lane >> 3);
-        a2_off[u][j] = (int)(min(m0 + ra, p.M - 1) * p.lda + ((lane & 7) ^ ((ra >> 1) & 7)) * 8);
+        a2_off[u][j] = (min(m0 + ra, p.M - 1) - m0) * (int)p.lda + ((lane & 7) ^ ((ra >> 1) & 7)) * 8;
         if (WLAYOUT == MG_W_ROWMAJOR) {
           const int rb = (wave >> 1) * 64 + u * 32 + (wave & 1) * 16 + j * 8 + (lane >> 3);
-          b2_off[u][j] = (int)(min(n0 + rb, p.N - 1) * p.ldw + ((lane & 7) ^ ((rb >> 1) & 7)) * 8);
+          b2_off[u][j] = (min(n0 + rb, p.N - 1) - n0) * (int)p.ldw + ((lane & 7) ^ ((rb >> 1) & 7)) * 8;
         } else {
           const int ntiles = (p.N + 15) >> 4;
           const int nt = min((n0 >> 4) + (wave >> 1) * 4 + u * 2 + (wave & 1), ntiles - 1);
@@ -484,7 +489,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
 #define MG_DMA_A2(kt, u)                                                                                 \
   {                                                                                                      \
     char* dst_ = smem + ((kt) & 1) * G256_BUF + ((wave >> 2) * 128 + (u) * 64 + (wave & 3) * 16) * 128;  \
-    const mg_bf16* src_ = p.A + (int64_t)KT_SRC(kt) * p.a_kt;                                            \
+    const mg_bf16* src_ = a_base + (int64_t)KT_SRC(kt) * p.a_kt;                                          \
     if (ABL != 4 || abl_on) {                                                                            \
       glds16s(src_, (uint32_t)a2_off[u][0] * 2u, dst_);                                                  \
       glds16s(src_, (uint32_t)a2_off[u][1] * 2u, dst_ + 1024);                                           \
@@ -495,12 +500,12 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
     char* base_ = smem + ((kt) & 1) * G256_BUF + G256_TILE;                                              \
     if (ABL == 4 && !abl_on) {                                                                           \
     } else if (WLAYOUT == MG_W_ROWMAJOR) {                                                               \
-      const mg_bf16* src_ = p.W + (int64_t)KT_SRC(kt) * 64;                                              \
+      const mg_bf16* src_ = w_base + (int64_t)KT_SRC(kt) * 64;                                            \
       char* d_ = base_ + ((wave >> 1) * 64 + (u) * 32 + (wave & 1) * 16) * 128;                          \
       glds16s(src_, (uint32_t)b2_off[u][0] * 2u, d_);                                                    \
       glds16s(src_, (uint32_t)b2_off[u][1] * 2u, d_ + 1024);                                             \
     } else {                                                                                             \
-      const mg_bf16* src_ = p.W + (int64_t)KT_SRC(kt) * 1024;                                            \
+      const mg_bf16* src_ = w_base + (int64_t)KT_SRC(kt) * 1024;                                          \
       char* d_ = base_ + (((wave >> 1) * 4 + (u) * 2 + (wave & 1)) * 2) * 1024;                          \
       glds16s(src_, (uint32_t)b2_off[u][0] * 2u, d_);                                                    \
       glds16s(src_, (uint32_t)b2_off[u][1] * 2u, d_ + 1024);                                             \
@@ -1025,7 +1030,15 @@ int gemm_dispatch(const mg_gemm_desc* d, bool fp8, const float* row_scale, hipSt
   const bool rm = d->w_layout == MG_W_ROWMAJOR;
   // large dense shapes go to the deep-pipelined 256x256 kernel (tile_hint: 0 auto, 128 / 256 force)
   const int64_t wgs256 = (int64_t)((d->M + 255) / 256) * ((d->N + 255) / 256);
-  const bool can256 = d->a_mode == MG_A_DENSE && (gp.K % 128) == 0;           // gp.K counts PAIRS of fp8 values on the fp8 path
+  // The loaders of the 256x256 kernel add a 32-bit per-lane byte offset to the workgroup's 64-bit row origin: the 256 rows of a
+  // tile of A, and of a row-major W, must span less than 2^32 bytes (ld < 2^23 kernel elements), a fragment-tiled W less than 2^32
+  // bytes as a whole.  Wider operands go to the 128x128 kernel (64-bit addresses per piece), or are refused where the tile is forced.
+  const bool fits256 = gp.lda < ((int64_t)1 << 23) &&
+                       (rm ? gp.ldw < ((int64_t)1 << 23) : (int64_t)((d->N + 15) >> 4) * (gp.ldw >> 5) * 512 < ((int64_t)1 << 31));
+  if (!fits256 && d->a_mode == MG_A_DENSE && (gp.K % 128) == 0 && ((d->tile_hint >= 256 && d->tile_hint <= 272) || d->ep.C8))
+    MG_FAIL(MG_ERR_SHAPE, "%s: lda=%lld / ldw=%lld exceed the 32-bit byte offsets of the 256x256 tile loaders (256 * ld * 2 bytes < 2^32; packed W < 2^32 bytes)%s",
+            who, (long long)d->lda, (long long)d->ldw, d->ep.C8 ? "; the MX output copy is written by that kernel only" : "");
+  const bool can256 = d->a_mode == MG_A_DENSE && (gp.K % 128) == 0 && fits256;           // gp.K counts PAIRS of fp8 values on the fp8 path
   const bool want256 = (d->tile_hint >= 256 && d->tile_hint <= 272) ||
                        (d->tile_hint == 0 && wgs256 >= 192 && d->M >= 1024 && d->N >= 512);
   // bf16: 32x32x16 MFMA (tile_hint 258) or 16x16x32 (259); 0 / 256 follow MAGMA_GEMM256_MFMA (default below)

@@ -1324,12 +1324,15 @@ def transpose(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tens
     return out
 
 
-def transpose_colsum(x: torch.Tensor, colsum_out: torch.Tensor) -> torch.Tensor:
-    """transpose(x) that also accumulates the column sums of x into colsum_out (fp32 [C]): one pass instead of two."""
-    _need_gpu(x, colsum_out)
+def transpose_colsum(x: torch.Tensor, colsum_out: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """transpose(x) that also accumulates the column sums of x into colsum_out (fp32 [C]): one pass instead of two.
+    ``out`` as for ``transpose``: [C, round_up(R, 8)] bf16, any row stride."""
+    _need_gpu(x, colsum_out, out)
     assert x.dtype == BF16 and x.ndim == 2 and x.stride(1) == 1 and colsum_out.dtype == torch.float32 and colsum_out.numel() >= x.shape[1]
     R, Cc = x.shape
-    out = torch.empty(Cc, ceil_to(R, 8), dtype=BF16, device=x.device)
+    if out is None:
+        out = torch.empty(Cc, ceil_to(R, 8), dtype=BF16, device=x.device)
+    assert out.dtype == BF16 and out.ndim == 2 and out.stride(1) == 1 and tuple(out.shape) == (Cc, ceil_to(R, 8))
     check(L.load().mg_transpose_colsum_bf16(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), R, Cc, colsum_out.data_ptr(), _stream()),
           "mg_transpose_colsum_bf16")
     return out
