@@ -18,15 +18,17 @@ Per block (parallel residual, adapters after attention/MLP):
 """
 from __future__ import annotations
 
+import itertools
 import os
 from typing import Any, List, NamedTuple, Optional
 
 import torch
 
-from . import ops
+from . import adapters, ops
 from .language_model import LMOutput
 
 BF16 = torch.bfloat16
+_PACK_GENS = itertools.count(1)      # LMEngine._packs_gen
 
 
 def rotary_tables(rotary_dim: int, n_pos: int, device):
@@ -447,6 +449,12 @@ class LMEngine:
         self.rot = cfg.rotary_dim
         self.head_dec = self.head_w8 = self.head_w4 = None
         self._lm_head = lm.lm_head
+        # The adapter operands are copies of TRAINED weights.  _packs_epoch: adapters._WEIGHTS_EPOCH (bumped by every writer that goes
+        # round torch: the optimizer step, Magma.invalidate_packed) when they were last packed -- _current_packs repacks when it
+        # moved.  _packs_gen: one number per set of packs, unique across engines; a cache's captured steps hold the raw addresses of
+        # one set and are dropped (decode) when the number differs.
+        self._blocks = lm.transformer.h
+        self._packs_epoch, self._packs_gen = adapters._WEIGHTS_EPOCH, next(_PACK_GENS)
         # (B, Smax, ragged) -> KVCache + the decode graphs captured on it, least recently used first; at most _cache_pool_max
         # entries (MAGMA_CACHE_POOL, default 4; 0 = no pooling: every generate() call allocates its cache and keeps nothing)
         self._cache_pool = {}
@@ -601,9 +609,10 @@ class LMEngine:
         """[W_out | W_up] (d rows over K = d + r, bias b_up) of a MAGMA_v1 block -- the operand of the ONE GEMM / GEMV that
         replaces out_proj and the adapter's up-projection (prefill / forward blocks and the decode step) -- or None where a
         block does not have that shape.  Built with the decode operands (_ensure_decode_packs / repack_adapters), when a token
-        step is planned (_ensure_decode_state) or on the first prefill that wants it; dropped by repack_adapters (it contains
-        W_up).  It is a SECOND copy of W_out (42 MB per block, 1.2 GB at 28 blocks): ly.out stays for the paths that still read
-        it (fp8 modes, MAGMA_PREFILL_CAT=0 / MAGMA_DECODE_FOLD=0, attention adapters)."""
+        step is planned (_ensure_decode_state) or on the first prefill that wants it; dropped AND rebuilt by repack_adapters (it
+        contains W_up), whose new _packs_gen retires every token step captured against the old one.  It is a SECOND copy of
+        W_out (42 MB per block, 1.2 GB at 28 blocks): ly.out stays for the paths that still read it (fp8 modes,
+        MAGMA_PREFILL_CAT=0 / MAGMA_DECODE_FOLD=0, attention adapters)."""
         if ly.out_up is None and self._v1_block(ly):
             a, _ = ly._src
             up = ly.mlp_adapter[1]
@@ -685,10 +694,15 @@ class LMEngine:
         """MXFP4 copies of every decode operand."""
         self._ensure_decode_packs_q(self._QUANT_DECODE["decode_w4"])
 
-    def repack_adapters(self, lm):
+    def repack_adapters(self, lm=None):
         """Refresh only the (trainable) adapter operands after optimizer steps; the
-        12 GB of frozen weights keep their packed copies."""
-        for ly, blk in zip(self.layers, lm.transformer.h):
+        12 GB of frozen weights keep their packed copies.  Every operand that contains an adapter weight is a NEW tensor
+        afterwards and the old ones go back to the allocator: a token step captured before (on a pooled cache or on one the
+        caller holds) points at freed memory.  No cache is visited here: the new _packs_gen makes _ensure_decode_state drop a
+        cache's captured steps before decode() would replay one.  Called by MagmaEngine.eval() and, for every other writer
+        that bumps the weights epoch, by _current_packs; ``lm`` defaults to the model this engine was built from."""
+        self._packs_epoch, self._packs_gen = adapters._WEIGHTS_EPOCH, next(_PACK_GENS)
+        for ly, blk in zip(self.layers, self._blocks if lm is None else lm.transformer.h):
             if ly.attn_adapter is not None:
                 ly.attn_adapter, ly.attn_act, ly.attn_ad_ln = self._pack_adapter(blk.attn)
                 if ly.attn_par is not None:           # scaled_parallel: the scale is a trained parameter too
@@ -712,6 +726,13 @@ class LMEngine:
             for _, cls, kmod, field, _ in self._QUANT_DECODE.values():
                 if getattr(ly, field) is not None:     # the quantised decode operands hold copies of the adapter projections
                     self._quantised_adapters(getattr(ly, field), ly, getattr(ops, cls), kmod)
+
+    def _current_packs(self):
+        """Entry of every pass over the blocks (_blocks_prefill, decode): the adapter operands are those of the weights as they are
+        NOW -- repacked if the weights epoch moved since they were packed (generate() after step() without eval()).  The epoch is
+        process-wide: a write to another model repacks this one's adapters once more, to the values they had."""
+        if self._packs_epoch != adapters._WEIGHTS_EPOCH:
+            self.repack_adapters()
 
     @staticmethod
     def _par_up(up, par):
@@ -994,6 +1015,7 @@ class LMEngine:
         row b by key_scale[b, j] before the causal mask (mg_attn_prefill_scaled_bf16 in place of mg_attn_prefill_bf16)."""
         B, S, d = embeds.shape
         assert d == self.d
+        self._current_packs()
         if key_scale is not None:
             mode = ("a tree forward" if tree is not None else "a chunk that continues a KV cache" if chunk
                     else "the fp8 attention mode" if self.fp8_mode and self.fp8_attn and cache is None else None)
@@ -1611,8 +1633,15 @@ class LMEngine:
     def _ensure_decode_state(self, cache: KVCache):
         """The cache's decode state: scratch buffers, captured graphs and the plan of the token step (st.w8 / st.w4, st.kinds, st.refusal),
         fixed when the state is created -- the eager step and every graph captured on this cache run the same launches, whatever
-        is written to the engine's switches afterwards."""
+        is written to the engine's switches afterwards.  The captured graphs hold the addresses of one set of adapter operands
+        (st.packs_gen): once repack_adapters has replaced them (or the cache has come to another engine) the graphs are dropped
+        here, wherever the cache lives -- pool or caller -- and the next steps capture again on the current operands.  The
+        scratch buffers, the plan and the selection state stay."""
+        self._current_packs()
         st = cache.decode_state
+        if st is not None and st.packs_gen != self._packs_gen:
+            st.graphs.clear()
+            st.packs_gen = self._packs_gen
         if st is None:
             if cache.B <= 16:           # larger batches run the tile GEMM on the prefill operands (no LayerNorm-folded packs)
                 self._ensure_decode_packs()
@@ -1622,6 +1651,7 @@ class LMEngine:
             st = self._alloc_decode_state(cache)
             st.w8, st.w4 = self.decode_w8, self.decode_w4
             st.kinds, st.refusal = self._plan_decode(cache.B)
+            st.packs_gen = self._packs_gen
             cache.decode_state = st
         return st
 

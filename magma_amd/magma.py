@@ -166,6 +166,13 @@ class Magma(nn.Module):
         self.lm.invalidate_packed()
         self.image_prefix.invalidate_packed()
 
+    def resize_token_embeddings(self, *args, **kwargs):
+        """GPTJForCausalLM.resize_token_embeddings, then ``word_embedding`` -- the alias of lm.transformer.wte the reference keeps
+        (magma.py:52), and a state-dict key of its own -- points at the table that replaced the old one."""
+        self.lm.resize_token_embeddings(*args, **kwargs)
+        self.word_embedding = self.lm.transformer.wte
+        return self.word_embedding
+
     def load_state_dict(self, state_dict, strict: bool = True):
         r = super().load_state_dict(state_dict, strict=strict)
         self.invalidate_packed()
@@ -576,8 +583,7 @@ class Magma(nn.Module):
         v_out = fixed["lm.lm_head.weight"].shape[0] if "lm.lm_head.weight" in fixed else None
         cur_in, cur_out = own["lm.transformer.wte.weight"].shape[0], own["lm.lm_head.weight"].shape[0]
         if (v_in is not None and v_in != cur_in) or (v_out is not None and v_out != cur_out):
-            self.lm.resize_token_embeddings(v_in if v_in is not None else cur_in, new_head_rows=v_out if v_out is not None else cur_out)
-            self.word_embedding = self.lm.transformer.wte
+            self.resize_token_embeddings(v_in if v_in is not None else cur_in, new_head_rows=v_out if v_out is not None else cur_out)
             own = self.state_dict()
         missing, unexpected = [], []
         bad = [f"{k}: checkpoint {tuple(v.shape)} vs model {tuple(own[k].shape)}" for k, v in fixed.items()
