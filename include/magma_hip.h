@@ -103,8 +103,10 @@ const char* mg_version(void);
  *  20  explaining answers: added mg_attn_prefill_scaled_bf16 (nothing moved).
  *  21  diverse beam search: added mg_beam_finish_groups (nothing moved).
  *  22  contrastive search: added mg_contrastive_topk_f32, mg_contrastive_sim_bf16, mg_contrastive_finish and
- *      mg_kv_broadcast_bf16 (nothing moved). */
-#define MG_ABI_VERSION 22
+ *      mg_kv_broadcast_bf16 (nothing moved).
+ *  23  losslessly packed decode weights: mg_skinny_desc grew by `pk_lo`, `pk_nib`, `pk_base`, `pk_sign`, `pk_flags` at its end
+ *      (NULL = as before; nothing else moved). */
+#define MG_ABI_VERSION 23
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -281,6 +283,26 @@ typedef struct mg_skinny_desc {
    * as the scale operand (exact: every e2m1 value times such a power of two is a bf16 value), so nothing is applied after the
    * accumulation.  Rows beyond N are zero.  Needs Kp % 512 == 0, a 16-byte aligned w_mx4_scale, and w_scale == NULL.  ABI 11.   */
   const uint8_t* w_mx4_scale;
+  /* Losslessly packed bf16 weights (13.25 bits per weight streamed; every reconstructed bf16 is bit-equal to the one in W, the
+   * MFMA sequence is that of the bf16 launch, so the outputs are bit-identical).  pk_lo == NULL = not packed.  Otherwise W stays
+   * the bf16 MG_W_FRAGTILED operand and the five arrays hold the same weights again.  A bf16 is s | e[7:0] | m[6:0]; per row n and
+   * k-step (32 K-elements: one block) base = min(e>>1), and an element is stored as its low byte (e0<<7 | m), the 4-bit offset
+   * (e>>1) - base and its sign.  With j = the k-step quad (128 K-elements), s = the k-step in it, lane = kq*16 + n, element i =
+   * W[n][128j + 32s + 8kq + i]:
+   *   pk_lo    [ceil(N/16)][Kp/128][2][64 lanes][16 B]  byte 8(s&1) + i of 16-byte group s>>1 = the low byte of element i
+   *   pk_nib   [ceil(N/16)][Kp/128][64 lanes][16 B]     byte 4s + b: low nibble = the offset of element b, high nibble of 4 + b
+   *   pk_base  [ceil(N/16)][Kp/128][16 n] 32-bit words  byte s = base of row n, k-step 4j + s
+   *   pk_sign  [ceil(N/16)][Kp/128][64 lanes] words     bit 8b + 7 - (2s + g) = the sign of element 4g + b of k-step 4j + s
+   *   pk_flags [ceil(ceil(N/16)/4)] 32-bit words        byte t&3 of word t>>2 != 0: row tile t is ESCAPED -- one of its blocks
+   *            spans more than 16 values of e>>1 (an exact zero beside normal values, a ratio above ~2^30): the workgroups of
+   *            such a tile stream W instead (the planes of that tile are not read for values).  Padding bytes are 0.
+   * Needs every array 16-byte aligned, Kp % (128 * waves of the variant) == 0 (every Kp % 1024 == 0 fits the automatic choice),
+   * and w_scale == w_mx4_scale == NULL.  All five are set or none.  ABI 23.                                                     */
+  const uint8_t* pk_lo;
+  const uint8_t* pk_nib;
+  const uint32_t* pk_base;
+  const uint32_t* pk_sign;
+  const uint32_t* pk_flags;
 } mg_skinny_desc;
 
 int mg_gemm_skinny_bf16(const mg_skinny_desc* d, void* stream);

@@ -1201,6 +1201,14 @@ int fill_skinny(const mg_skinny_desc* d, SkinnyParams& sp, const char* who) {
   sp.split_n = d->split_n; sp.ep_b = d->ep_b;
   sp.w_scale = d->w_scale;
   sp.w_mx4 = (const uint32_t*)d->w_mx4_scale;
+  sp.pk_lo = (const u32x4*)d->pk_lo; sp.pk_nib = (const u32x4*)d->pk_nib;
+  sp.pk_base = d->pk_base; sp.pk_sign = d->pk_sign; sp.pk_flags = d->pk_flags;
+  if (d->pk_lo || d->pk_nib || d->pk_base || d->pk_sign || d->pk_flags) {
+    if (!d->pk_lo || !d->pk_nib || !d->pk_base || !d->pk_sign || !d->pk_flags) MG_FAIL(MG_ERR_SHAPE, "%s: packed weights need pk_lo, pk_nib, pk_base, pk_sign and pk_flags together", who);
+    if (d->w_scale || d->w_mx4_scale) MG_FAIL(MG_ERR_UNSUPPORTED, "%s: packed bf16 weights (pk_lo) exclude w_scale / w_mx4_scale", who);
+    if (!MG_ALIGNED16(d->pk_lo) || !MG_ALIGNED16(d->pk_nib) || !MG_ALIGNED16(d->pk_base) || !MG_ALIGNED16(d->pk_sign) || !MG_ALIGNED16(d->pk_flags) || (d->Kp & 511))
+      MG_FAIL(MG_ERR_SHAPE, "%s: packed weights need 16-byte aligned planes and Kp %% 512 == 0", who);
+  }
 #ifdef MG_GEMM_ABLATIONS
   static const int dbg = [] { const char* e = getenv("MAGMA_SKINNY_DBG"); return e ? atoi(e) : 0; }();
   sp.dbg = dbg;
@@ -1247,7 +1255,7 @@ extern "C" int mg_gemm_skinny_bf16(const mg_skinny_desc* d, void* stream) {
   if ((d->nt_hint >> 17) & 1) MG_FAIL(MG_ERR_UNSUPPORTED, "mg_gemm_skinny_bf16: the LDS-DMA GEMV exists only in the ablation library (make ABL=1)");
 #endif
   if (pipe) {
-    if (sp.w_scale || sp.w_mx4 || nt != 1 || sp.ksteps % (waves * kc) != 0) MG_FAIL(MG_ERR_UNSUPPORTED, "mg_gemm_skinny_bf16: pipelined variants are bf16, one n-tile");
+    if (sp.w_scale || sp.w_mx4 || sp.pk_lo || nt != 1 || sp.ksteps % (waves * kc) != 0) MG_FAIL(MG_ERR_UNSUPPORTED, "mg_gemm_skinny_bf16: pipelined variants are bf16, one n-tile");
 #define MG_SKP(W_, K_) if (waves == W_ && kc == K_) return launch_skinny<W_, K_, 1, WT_BF16, true>(sp, s)
     MG_SKP(4, 16); MG_SKP(4, 8); MG_SKP(8, 8); MG_SKP(8, 4); MG_SKP(4, 4);
 #undef MG_SKP
@@ -1286,6 +1294,29 @@ extern "C" int mg_gemm_skinny_bf16(const mg_skinny_desc* d, void* stream) {
   }
   if (waves <= 0 || kc <= 0 || nt <= 0 || sp.ksteps % (waves * kc) != 0)
     MG_FAIL(MG_ERR_SHAPE, "mg_gemm_skinny_bf16: variant (waves=%d,kc=%d,nt=%d) does not divide ksteps=%d", waves, kc, nt, sp.ksteps);
+  if (sp.pk_lo) {
+    // Losslessly packed bf16: the SAME waves as the bf16 launch of this shape (the split of K over the waves and their summation
+    // order decide the bits; burst depth and n-tiles per workgroup do not), each wave in whole k-step quads.
+    const int per_wave = sp.ksteps / waves;
+    if (per_wave % 4 != 0) MG_FAIL(MG_ERR_SHAPE, "mg_gemm_skinny_bf16: packed weights need Kp %% (128 * waves) == 0 (Kp=%d, waves=%d)", d->Kp, waves);
+    // Measured in a captured graph over the 28 layers' operands, M = 8 (tools/decode_pack_bench.py --sweep,
+    // profiles/decode_pack_bench.jsonl), us per launch, bf16 -> packed: [28672 x 4096] 37.8 -> 35.5 at (8 waves, kc 8, nt 1), 35.9 at
+    // (8, 4, 1), 36.4 at (8, 4, 2), 44.3 at (8, 8, 2), 50.4 at (8, 16, 1); [4096 x 16384] 23.6 -> 22.9 at (4, 16, 1), 24.2 at (4, 8, 1),
+    // 28.1 at (4, 4, 1), 29.0 at (4, 32, 1), 35.5 at (4, 16, 2); [1024 x 4096] 6.4 -> 6.7 at (8, 4, 1), 7.1 at (8, 8, 1);
+    // [4096 x 5120] 9.1 -> 9.1 at (8, 4, 1), 10.6 at (8, 20, 1).  So: one n-tile; the deeper burst only where there are
+    // several workgroups per CU.
+    if (d->nt_hint == 0) {
+      nt = 1;
+      kc = waves == 4 && per_wave % 16 == 0 ? 16 : waves == 8 && per_wave % 8 == 0 && sp.ntiles >= 512 ? 8 : 4;
+    } else if (kc % 4 != 0 || per_wave % kc != 0) {
+      MG_FAIL(MG_ERR_SHAPE, "mg_gemm_skinny_bf16: packed variant (waves=%d,kc=%d,nt=%d) needs kc %% 4 == 0 dividing ksteps / waves = %d", waves, kc, nt, per_wave);
+    }
+#define MG_SKPK(W_, K_, N_) if (waves == W_ && kc == K_ && nt == N_) return launch_skinny<W_, K_, N_, WT_PK>(sp, s)
+    MG_SKPK(8, 4, 1); MG_SKPK(8, 4, 2); MG_SKPK(8, 8, 1); MG_SKPK(8, 8, 2); MG_SKPK(8, 16, 1); MG_SKPK(8, 20, 1);
+    MG_SKPK(4, 4, 1); MG_SKPK(4, 8, 1); MG_SKPK(4, 16, 1); MG_SKPK(4, 16, 2); MG_SKPK(4, 32, 1);
+#undef MG_SKPK
+    MG_FAIL(MG_ERR_UNSUPPORTED, "mg_gemm_skinny_bf16: packed variant (waves=%d,kc=%d,nt=%d) not instantiated", waves, kc, nt);
+  }
   if (sp.w_scale) {   // fp8 weights: a 16-byte load covers TWO k-steps, so the bursts are twice as deep as for bf16 to keep
                       // the same bytes in flight (Kp % 1024 == 0 guarantees that every variant below divides)
     if (d->nt_hint != 0) {
@@ -1329,7 +1360,11 @@ extern "C" int mg_gemm_skinny2_bf16(const mg_skinny_desc* a, const mg_skinny_des
     MG_CHECK_LAUNCH();
     return MG_OK;
   }
-  if (pa.w_scale && pa.ksteps % 64 == 0 && pb.ksteps % 64 == 0) {
+  // losslessly packed bf16 (same bits as the bf16 launch below, whose 8 waves it keeps): only where BOTH problems have the planes
+  // and split into whole k-step quads per wave; any other pair streams its bf16 operands
+  if (pa.pk_lo && pb.pk_lo && pa.ksteps % 32 == 0 && pb.ksteps % 32 == 0) {
+    hipLaunchKernelGGL((skinny2_kernel<8, 4, 1, WT_PK>), dim3(grid), dim3(512), 0, s, pa, pb, pa.ntiles);
+  } else if (pa.w_scale && pa.ksteps % 64 == 0 && pb.ksteps % 64 == 0) {
     hipLaunchKernelGGL((skinny2_kernel<8, 8, 1, WT_FP8>), dim3(grid), dim3(512), 0, s, pa, pb, pa.ntiles);
   } else if (pa.w_scale) {
     hipLaunchKernelGGL((skinny2_kernel<8, 4, 1, WT_FP8>), dim3(grid), dim3(512), 0, s, pa, pb, pa.ntiles);
@@ -1369,6 +1404,9 @@ extern "C" int mg_decode_attn_gemv_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_
     else if (sp.ksteps % 32 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<8, WT_MX4>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
     else hipLaunchKernelGGL((decode_attn_gemv_kernel<4, WT_MX4>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
   } else if (sp.w_scale) hipLaunchKernelGGL((decode_attn_gemv_kernel<16, WT_FP8>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
+  // losslessly packed bf16: 4 waves like every bf16 form below (same bits), whole k-step quads per wave
+  else if (sp.pk_lo && sp.ksteps % 64 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<16, WT_PK>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
+  else if (sp.pk_lo && sp.ksteps % 16 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<4, WT_PK>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
   else if (pipe == 16 && sp.ksteps % 64 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<16, WT_BF16, true>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
   else if (pipe == 8 && sp.ksteps % 32 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<8, WT_BF16, true>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
   else if (sp.ksteps % 64 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<16>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);

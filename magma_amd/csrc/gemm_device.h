@@ -602,6 +602,14 @@ struct SkinnyParams {
   // scales as [n-tile][k-step quad j][16 n] words, byte s = the scale of row n's k-step 4j+s -- one MX block IS one row of one
   // MFMA k-step.  The codes are widened to bf16 with the scale applied (exact), nothing happens after the accumulation.
   const uint32_t* w_mx4;
+  // Losslessly packed bf16 weights (13.25 bits per weight streamed, bit-equal reconstruction): W stays the bf16 operand -- the
+  // workgroups of escaped n-tiles stream it -- and the planes hold the same values per k-step quad j (lane = kq*16 + n, s = 0..3):
+  //   pk_lo   [n-tile][j][2][64 lanes][16 B]  the low bytes (e0<<7 | m); bytes 8(s&1)+i of load s>>1 = element i of k-step 4j+s
+  //   pk_nib  [n-tile][j][64 lanes][16 B]     the 4-bit offsets (e>>1) - base; word s, byte b: low nibble = element b, high = 4+b
+  //   pk_base [n-tile][j][16 n] words         byte s = min(e>>1) over row n's 32 elements of k-step 4j+s
+  //   pk_sign [n-tile][j][64 lanes] words     the sign of element 4g+b of k-step 4j+s at bit 8b + 7 - (2s + g)
+  //   pk_flags [ceil(n-tiles / 4)] words      byte t&3 of word t>>2 != 0: n-tile t holds a block whose (e>>1) span exceeds 15
+  const u32x4* pk_lo; const u32x4* pk_nib; const uint32_t* pk_base; const uint32_t* pk_sign; const uint32_t* pk_flags;
 #ifdef MG_GEMM_ABLATIONS
   int dbg;   // ablation library only (`make ABL=1`, MAGMA_SKINNY_DBG): bit 0 = skip the LayerNorm-fold row statistics (WRONG results)
 #endif
@@ -623,7 +631,19 @@ MG_DEV bf16x8 fp8x8_to_bf16(uint32_t w0, uint32_t w1) {
 }
 
 // weight types of the skinny kernels (skinny_body's WT)
-constexpr int WT_BF16 = 0, WT_FP8 = 1, WT_MX4 = 2;
+constexpr int WT_BF16 = 0, WT_FP8 = 1, WT_MX4 = 2, WT_PK = 3;
+
+// one k-step of a lane's losslessly packed weights -> 8 bf16, bit-equal to the stored ones (SkinnyParams::pk_lo ...): l0 / l1 the
+// low bytes of elements 0-3 / 4-7, nib their offset nibbles, basew / sg the quad's base and sign words, s the k-step in the quad.
+// Byte-parallel: base + offset cannot carry (e>>1 <= 127), the sign lands in bit 7, v_perm_b32 interleaves high and low bytes.
+MG_DEV bf16x8 pk8_to_bf16(uint32_t l0, uint32_t l1, uint32_t nib, uint32_t basew, uint32_t sg, int s) {
+  const uint32_t b4 = __builtin_amdgcn_perm(basew, basew, 0x01010101u * (uint32_t)s);      // byte s in every byte
+  const uint32_t h0 = ((nib & 0x0f0f0f0fu) + b4) | ((sg << (2 * s)) & 0x80808080u);
+  const uint32_t h1 = (((nib >> 4) & 0x0f0f0f0fu) + b4) | ((sg << (2 * s + 1)) & 0x80808080u);
+  const u32x4 o = {__builtin_amdgcn_perm(h0, l0, 0x05010400u), __builtin_amdgcn_perm(h0, l0, 0x07030602u),
+                   __builtin_amdgcn_perm(h1, l1, 0x05010400u), __builtin_amdgcn_perm(h1, l1, 0x07030602u)};
+  return __builtin_bit_cast(bf16x8, o);
+}
 
 // 8 e2m1 codes (one 32-bit word, element 2i in the low nibble of byte i) x 2^(e8m0 - 127) -> 8 bf16 (exact for e8m0 in [2, 251]:
 // v_cvt_scalef32_pk_bf16_fp4 widens two codes per instruction, op_sel picks the byte, the block scale is its scale operand)
@@ -650,13 +670,17 @@ struct NoWait { MG_DEV void operator()() const {} };
 // occupancy cannot hide the drain: fc_out (N = 4096 -> 256 workgroups of 4 waves, ONE wave per SIMD, 8 bursts of 16 loads
 // each).  Same MFMA order per accumulator, hence bit-identical results.
 // WT: WT_BF16 | WT_FP8 (e4m3 bytes, two k-steps per 16-byte load) | WT_MX4 (e2m1 codes + E8M0 block scales, four k-steps per load; the
-// burst also loads one word of scales per n-tile and k-step quad, issued with the weights).
+// burst also loads one word of scales per n-tile and k-step quad, issued with the weights) | WT_PK (bf16 losslessly packed to 13.25
+// bits, SkinnyParams::pk_*: five loads per k-step quad instead of four, 53 bytes per lane instead of 64; same MFMA operands in the
+// same order as WT_BF16 with the same WAVES, hence bit-identical results).
 template <int WAVES, int KC, int NT, int WT = WT_BF16, bool COH = false, class Wait = NoWait, bool PIPE = false>
 MG_DEV void skinny_body(const SkinnyParams& p, int block, char* lds, Wait wait = Wait()) {
-  constexpr bool W8 = WT == WT_FP8, W4 = WT == WT_MX4;
+  constexpr bool W8 = WT == WT_FP8, W4 = WT == WT_MX4, WP = WT == WT_PK;
   static_assert(!W8 || KC % 2 == 0, "fp8 weights are stored in k-step pairs");
   static_assert(!W4 || (KC % 4 == 0 && !PIPE && !COH), "MXFP4 weights are stored in k-step quads; burst-and-drain stream only");
   static_assert(!PIPE || (!COH && __is_same(Wait, NoWait)), "the pipelined stream has no dependency wait / coherent loads");
+  static_assert(!WP || (KC % 4 == 0 && 4 % NT == 0 && !PIPE && !COH && __is_same(Wait, NoWait)),
+                "packed weights are stored in k-step quads, a workgroup's n-tiles share one flag word; burst-and-drain stream only");
   float* red = (float*)lds;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -693,7 +717,80 @@ MG_DEV void skinny_body(const SkinnyParams& p, int block, char* lds, Wait wait =
   };
   constexpr bool AHEAD = !__is_same(Wait, NoWait);     // persistent step: first weight burst before the dependency wait
   if constexpr (AHEAD) { load_w(0); wait(); }
-  if constexpr (PIPE) {
+  if constexpr (WP) {
+    // one burst of packed weights in registers: per n-tile and k-step quad two loads of low bytes, one of nibbles, the base word
+    // (row li) and the lane's sign word -- five loads, 53 bytes per lane, where bf16 has four and 64
+    constexpr int WQ = KC / 4;
+    struct PkBurst { u32x4 lo[NT][2 * WQ], nib[NT][WQ]; uint32_t base[NT][WQ], sign[NT][WQ]; };
+    auto load_pk = [&](PkBurst& b, int kc) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const int64_t q0 = (int64_t)min(nt0 + t, p.ntiles - 1) * (p.ksteps >> 2) + ((ks0 + kc) >> 2);
+        const u32x4* lp = p.pk_lo + q0 * 128 + lane;
+        const u32x4* np = p.pk_nib + q0 * 64 + lane;
+        const uint32_t* bp = p.pk_base + q0 * 16 + li;
+        const uint32_t* gp = p.pk_sign + q0 * 64 + lane;
+#pragma unroll
+        for (int i = 0; i < WQ; ++i) {
+          b.lo[t][2 * i] = __builtin_nontemporal_load(lp + i * 128);
+          b.lo[t][2 * i + 1] = __builtin_nontemporal_load(lp + i * 128 + 64);
+          b.nib[t][i] = __builtin_nontemporal_load(np + i * 64);
+        }
+#pragma unroll
+        for (int i = 0; i < WQ; ++i) {
+          b.base[t][i] = __builtin_nontemporal_load(bp + i * 16);
+          b.sign[t][i] = __builtin_nontemporal_load(gp + i * 64);
+        }
+      }
+    };
+    // Workgroup-level escape, outside the K loop: a workgroup with a flagged n-tile runs the bf16 body on W.  The flag word is a
+    // scalar load (the address is uniform).  (The compiler moves the first burst's loads below the flag test, so a workgroup
+    // starts with that round trip; forcing the burst out before the test -- a use of every loaded register ahead of the branch --
+    // took 0.2-0.6 us off the two small launches and cost the large ones 20-35 %: it waits for the whole burst at once.)
+    PkBurst b0;
+    const uint32_t fw = p.pk_flags[nt0 >> 2];
+    load_pk(b0, 0);
+    constexpr uint32_t tmask = NT >= 4 ? 0xffffffffu : (1u << (8 * (NT & 3))) - 1u;
+    if (fw & (tmask << (8 * (nt0 & 3)))) {
+      skinny_body<WAVES, KC, NT, WT_BF16, false, NoWait, false>(p, block, lds);
+      return;
+    }
+    // one burst (its weight loads are out): the x fragments (L2 hits), the row statistics, then unpack and multiply
+    auto burst = [&](const PkBurst& cur, int kc) {
+      bf16x8 xf[KC];
+#pragma unroll
+      for (int i = 0; i < KC; ++i) {
+        u32x4 raw = *(const u32x4*)(xrow + (int64_t)(ks0 + kc + i) * 32);
+        if (!xok) raw = (u32x4){0u, 0u, 0u, 0u};
+        xf[i] = __builtin_bit_cast(bf16x8, raw);
+      }
+      if (p.ln_colsum && !MG_SKINNY_DBG_NOSTATS(p)) {
+#pragma unroll
+        for (int i = 0; i < KC; ++i) {
+          const u32x4 raw = __builtin_bit_cast(u32x4, xf[i]);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float a = bflo(raw[j]), b = bfhi(raw[j]);
+            xs += a + b;
+            xss += a * a + b * b;
+          }
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int i = 0; i < KC; ++i) {
+          const u32x4 lo = cur.lo[t][i >> 1];
+          const bf16x8 w = pk8_to_bf16(lo[(i & 1) * 2], lo[(i & 1) * 2 + 1], cur.nib[t][i >> 2][i & 3], cur.base[t][i >> 2], cur.sign[t][i >> 2], i & 3);
+          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, xf[i], acc[t], 0, 0, 0);
+        }
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    // the first burst is peeled: no run-time branch round a load inside the loop
+    burst(b0, 0);
+    for (int kc = KC; kc < per_wave; kc += KC) { load_pk(b0, kc); burst(b0, kc); }
+  } else if constexpr (PIPE) {
     u32x4 wg[NT][WL];                                    // second register buffer (wf is the first)
     auto load_into = [&](u32x4 (&dst)[NT][WL], int kc) {
 #pragma unroll

@@ -477,6 +477,10 @@ class LMEngine:
         # weight.  Opt-in for the same reason, and exclusive with W8A16 (_quantised_decode: both set is an error).
         self.decode_w4 = os.environ.get("MAGMA_DECODE_W4", "0") == "1"
         self._quantised_decode()
+        # Lossless decode packing: the bf16 token step streams its weights as 13.25-bit twins (ops.DecodePack, built with the decode
+        # operands) that the GEMVs widen back to the SAME bf16 bits in registers -- identical logits, 0.83x the bytes, about 10 GB
+        # more HBM for the benchmark model.  Read when the decode operands are built; the W8A16 / W4A16 steps and B > 16 ignore it.
+        self.decode_pack = os.environ.get("MAGMA_DECODE_PACK", "1") == "1"
         self._dec_in_variant = int(os.environ.get("MAGMA_DEC_IN_VARIANT", "0"))   # tuning knob: nt | waves<<4 | kc<<8
         self._dec_dn_variant = int(os.environ.get("MAGMA_DEC_DN_VARIANT", "0"))   # the same for the adapter-down and the
         self._dec_cat_variant = int(os.environ.get("MAGMA_DEC_CAT_VARIANT", "0"))  # [W_out | W_up] launches of the v1 block
@@ -572,6 +576,48 @@ class LMEngine:
             if self.fold_dn in (1, 2):
                 self._ensure_out_up(ly)          # built HERE, never inside a token step (no allocation under hipGraph capture)
         self.head_dec = self._fold_head(ops.PackedLinear)
+        for ly in self.layers:
+            self._attach_decode_twins(ly)
+        if self.decode_pack:
+            ops.attach_decode_pack(self.head_dec)
+
+    def _attach_decode_twins(self, ly):
+        """decode_pack: the lossless 13.25-bit twins (ops.DecodePack) of the weight-streaming operands of a "fold2" / "grouped" block --
+        the token step then streams 0.83x the bytes and computes the same bits.  An operand that already has its twin keeps it
+        (frozen weights are packed once per model); repack_adapters calls this again for the adapter operands it rebuilt.  Built
+        with the decode operands, never inside a token step."""
+        if not self.decode_pack or self.decode_w8 or self.decode_w4:     # the quantised steps stream their own operands
+            return
+        kind = self._block_kind(ly, False, False, self.fold_dn, self.group_launches)
+        if kind == "fold2":
+            operands = (ly.dec_in, ly.fc_out, ly.mlp_adapter[0], ly.out_up)
+        elif kind == "grouped":
+            operands = (ly.dec_in, ly.fc_out, ly.out) + tuple(ly.mlp_adapter)
+        else:
+            return
+        for p in operands:
+            if p is not None:
+                ops.attach_decode_pack(p)
+
+    def decode_pack_share(self) -> float:
+        """Share of the token step's weight bytes (bf16 count, B <= 16, current switches) that is streamed packed: operands with a
+        twin, less their escaped row tiles."""
+        self._ensure_decode_packs()
+        packed = total = 0
+        kinds = [self._block_kind(ly, False, False, self.fold_dn, self.group_launches) for ly in self.layers]
+        for ly, kind in zip(self.layers, kinds):
+            if kind == "fold2":
+                operands = [ly.dec_in, ly.fc_out, ly.mlp_adapter[0], ly.out_up]
+            elif kind == "fold1":
+                operands = [ly.dec_in, ly.fc_dn, ly.out_up]
+            else:
+                operands = [ly.dec_in, ly.fc_out, ly.out] + [p for pair in (ly.mlp_adapter, ly.attn_adapter) if pair for p in pair]
+            for p in operands + ([self.head_dec] if ly is self.layers[-1] else []):
+                total += p.ft.numel()
+                pk = getattr(p, "pk", None)
+                if pk is not None:
+                    packed += p.ft.numel() * (pk.ntiles - pk.escaped) // pk.ntiles
+        return packed / max(total, 1)
 
     def _block_kind(self, ly, wide=False, w8=False, fold_dn=0, group=True) -> str:
         """Which launch sequence (_block_<kind>) the token step runs for this layer: "wide" | "fold2" | "fold1" | "grouped" | "v2" |
@@ -723,6 +769,8 @@ class LMEngine:
                 self._ensure_out_up(ly)
             if had_up_cat:
                 self._adapter_up_cat(ly)
+            if self.head_dec is not None:
+                self._attach_decode_twins(ly)          # the rebuilt adapter operands get new twins; the frozen ones keep theirs
             for _, cls, kmod, field, _ in self._QUANT_DECODE.values():
                 if getattr(ly, field) is not None:     # the quantised decode operands hold copies of the adapter projections
                     self._quantised_adapters(getattr(ly, field), ly, getattr(ops, cls), kmod)

@@ -19,7 +19,7 @@ MG_A_DENSE, MG_A_CONV3X3 = 0, 1
 MG_AUX_NONE, MG_AUX_RELU_GATE, MG_AUX_GELU_GRAD, MG_AUX_MUL, MG_AUX_QUICK_GELU_GRAD = 0, 1, 2, 3, 4
 
 
-ABI_VERSION = 22     # include/magma_hip.h MG_ABI_VERSION
+ABI_VERSION = 23    # include/magma_hip.h MG_ABI_VERSION
 
 
 class MagmaHipError(RuntimeError):
@@ -83,6 +83,7 @@ class SkinnyDesc(C.Structure):
         ("ep_b", Epilogue),
         ("w_scale", C.c_void_p),
         ("w_mx4_scale", C.c_void_p),
+        ("pk_lo", C.c_void_p), ("pk_nib", C.c_void_p), ("pk_base", C.c_void_p), ("pk_sign", C.c_void_p), ("pk_flags", C.c_void_p),
     ]
 
 

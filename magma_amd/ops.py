@@ -261,6 +261,10 @@ def skinny_desc(x: torch.Tensor, w: PackedLinear, out: Optional[torch.Tensor] = 
         d.w_scale = w.scale.data_ptr()
     elif isinstance(w, PackedLinearW4):
         d.w_mx4_scale = w.scales.data_ptr()
+    elif DECODE_PACK and getattr(w, "pk", None) is not None:
+        pk = w.pk
+        d.pk_lo, d.pk_nib, d.pk_base = pk.lo.data_ptr(), pk.nib.data_ptr(), pk.base.data_ptr()
+        d.pk_sign, d.pk_flags = pk.sign.data_ptr(), pk.flags.data_ptr()
     n_a = w.N if split is None else split[0]
     d.ep = _epilogue(out, n_a, w.bias if use_bias else None, scale, act, residuals, act_after, aux, aux_mode, aux_after, out2)
     if ln_fold is not None:
@@ -376,6 +380,86 @@ class PackedLinearW4:
     def dequant(self) -> torch.Tensor:
         """The exact fp32 values [N, K] the kernel multiplies (every one a bf16 value)."""
         return dequantize_mx_fp4(*untile_mx_fp4(self.ft, self.scales, self.N))
+
+
+DECODE_PACK = True      # skinny_desc hands a PackedLinear's lossless twin (.pk, attach_decode_pack) to the kernel; False: never
+
+
+def pack_bf16_lossless(w: torch.Tensor):
+    """Row-major bf16 [n16, K] (n16 % 16 == 0, K % 128 == 0) -> (lo, nib, base, sign, flags): the same bits in 13.25 per weight, in
+    the lane layouts of the packed weight-streaming GEMV (include/magma_hip.h, mg_skinny_desc.pk_lo).  A bf16 is s | e[7:0] | m[6:0]:
+    the low byte e0<<7 | m goes to ``lo`` verbatim, the high byte is the sign (``sign``) and eh = e>>1, stored as the 4-bit offset
+    eh - base (``nib``) against base = min(eh) over the 32 K-elements of a row that one MFMA k-step consumes (``base``, one byte per
+    block).  A block whose eh span exceeds 15 does not fit: its 16-row tile is flagged in ``flags`` (uint8, padded with zeros to a
+    multiple of 16 entries) and its planes hold clamped offsets nobody reads for values.  Plain torch on the weight's device."""
+    assert w.dtype == BF16 and w.ndim == 2 and w.shape[0] % 16 == 0 and w.shape[1] % 128 == 0
+    n16, K = w.shape
+    nt, kq4 = n16 // 16, K // 128
+    bits = w.contiguous().view(torch.int16)
+    lowb = (bits & 0xff).to(torch.uint8)
+    high = ((bits >> 8) & 0xff).to(torch.uint8)
+    del bits
+    eh = high & 0x7f
+    blk = eh.view(n16, K // 32, 32)
+    base = blk.amin(-1)
+    misfit = (blk.amax(-1) - base) > 15                                  # uint8 arithmetic: amax >= base
+    flags = torch.zeros(ceil_to(nt, 16), dtype=torch.uint8, device=w.device)
+    flags[:nt] = misfit.view(nt, 16, K // 32).any(2).any(1).to(torch.uint8)
+    off = (blk - base[..., None]).clamp_(max=15).view(n16, K)
+    # [n16, K] -> [nt, n(16), pair, step(2), kq(4), 8] -> [nt, pair, kq, n, step, 8]  (PackedLinearW8.ft's lane layout)
+    lo = lowb.view(nt, 16, K // 64, 2, 4, 8).permute(0, 2, 4, 1, 3, 5).contiguous()
+    # element 8kq + 4g + b of k-step 4j + s: [nt, n, j, s, kq, g, b]
+    o7 = off.view(nt, 16, kq4, 4, 4, 2, 4)
+    nib = (o7[..., 0, :] | (o7[..., 1, :] << 4)).permute(0, 2, 4, 1, 3, 5).contiguous()       # [nt, j, kq, n, s, b]
+    base_t = base.view(nt, 16, kq4, 4).permute(0, 2, 1, 3).contiguous().view(torch.int32).squeeze(-1)     # [nt, j, n] words
+    # sign of (s, g, b) at bit 8b + 7 - (2s + g): byte b of the word collects the eight (s, g) of its column
+    sh = (7 - (2 * torch.arange(4, device=w.device)[:, None] + torch.arange(2, device=w.device)[None, :])).to(torch.uint8)
+    s7 = (high >> 7).view(nt, 16, kq4, 4, 4, 2, 4) << sh[:, None, :, None]                       # [.., s, kq, g, b]
+    sign = s7.sum(dim=(3, 5), dtype=torch.uint8).permute(0, 2, 3, 1, 4).contiguous().view(torch.int32).squeeze(-1)   # [nt, j, kq, n]
+    return lo, nib, base_t, sign, flags
+
+
+def unpack_bf16_lossless(lo: torch.Tensor, nib: torch.Tensor, base: torch.Tensor, sign: torch.Tensor) -> torch.Tensor:
+    """Exact inverse of pack_bf16_lossless over the tiles that are not flagged: the row-major bf16 [n16, K] the kernel rebuilds."""
+    nt, kq4 = nib.shape[0], nib.shape[1]
+    n16, K = nt * 16, kq4 * 128
+    lowb = lo.permute(0, 3, 1, 4, 2, 5).reshape(n16, K).to(torch.int32)
+    nb = nib.permute(0, 3, 1, 4, 2, 5)                                                            # [nt, n, j, s, kq, b]
+    off = torch.stack([nb & 15, nb >> 4], dim=5).reshape(n16, K).to(torch.int32)                  # [nt, n, j, s, kq, g, b]
+    bs = base.contiguous().view(nt, kq4, 16, 1).view(torch.uint8).permute(0, 2, 1, 3).reshape(n16, K // 32)   # [nt, n, j, s]
+    sg = sign.contiguous().view(nt, kq4, 4, 16, 1).view(torch.uint8).permute(0, 3, 1, 2, 4)        # [nt, n, j, kq, b]
+    dev = lo.device
+    sh = (7 - (2 * torch.arange(4, device=dev)[:, None] + torch.arange(2, device=dev)[None, :])).to(torch.uint8)   # [s, g]
+    s7 = (sg[:, :, :, None, :, None, :] >> sh[:, None, :, None]) & 1                               # [nt, n, j, s, kq, g, b]
+    high = (s7.reshape(n16, K).to(torch.int32) << 7) | (off + bs.to(torch.int32).repeat_interleave(32, dim=1))
+    return ((high << 8) | lowb).to(torch.int16).view(BF16)
+
+
+class DecodePack:
+    """The lossless 13.25-bit twin of a fragment-tiled bf16 PackedLinear (pack_bf16_lossless): what the decode GEMVs stream instead
+    of ``ft`` -- same bits out, 0.83x the bytes in.  The bf16 operand stays: the workgroups of flagged row tiles read it."""
+
+    def __init__(self, ft: torch.Tensor):
+        self.lo, self.nib, self.base, self.sign, self.flags = pack_bf16_lossless(PackedLinear.untile(ft))
+        self.ntiles = ft.shape[0]
+        self.escaped = int(self.flags.count_nonzero())
+
+    def unpack(self) -> torch.Tensor:
+        return unpack_bf16_lossless(self.lo, self.nib, self.base, self.sign)
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.lo, self.nib, self.base, self.sign, self.flags))
+
+
+def attach_decode_pack(w: PackedLinear) -> Optional[DecodePack]:
+    """Give a bf16 PackedLinear its lossless twin as ``w.pk`` (skinny_desc then fills mg_skinny_desc.pk_*); an operand the packed
+    kernels do not take (Kp not a multiple of 512: four waves in whole k-step quads; not a plain PackedLinear) gets none."""
+    if type(w) is not PackedLinear or w.ft is None or w.Kp % 512:
+        return None
+    if getattr(w, "pk", None) is None:
+        w.pk = DecodePack(w.ft)
+    return w.pk
 
 
 def gemm_skinny(x: torch.Tensor, w: PackedLinear, out: Optional[torch.Tensor] = None, **kw) -> torch.Tensor:
