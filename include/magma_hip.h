@@ -105,8 +105,9 @@ const char* mg_version(void);
  *  22  contrastive search: added mg_contrastive_topk_f32, mg_contrastive_sim_bf16, mg_contrastive_finish and
  *      mg_kv_broadcast_bf16 (nothing moved).
  *  23  losslessly packed decode weights: mg_skinny_desc grew by `pk_lo`, `pk_nib`, `pk_base`, `pk_sign`, `pk_flags` at its end
- *      (NULL = as before; nothing else moved). */
-#define MG_ABI_VERSION 23
+ *      (NULL = as before; nothing else moved).
+ *  24  request streams: added mg_sample_finish_slots and mg_slots_admit_bf16, MG_STOP_LEN and MG_SLOTS_MAX (nothing moved). */
+#define MG_ABI_VERSION 24
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -492,6 +493,39 @@ int mg_sample_finish_rows(int64_t* token, int32_t B, int32_t* state, int32_t* d_
                           int64_t ld_history, int32_t history_cols, int32_t* clear, int32_t n_clear, int32_t clear_stride,
                           int32_t pos_stride, const int32_t* table, int32_t n_eos, int32_t n_seq, int64_t pad, int32_t* finish,
                           void* stream);
+
+/* Request streams (ABI 24; DESIGN.md "Request streams"; host statement: magma_amd/sampling.py, slot_update): the bookkeeping of a
+ * slot session, in which the row of a finished request is handed to the next request while the other rows keep generating.
+ * mg_sample_finish_slots: mg_sample_finish_rows' launch (one workgroup, enqueue-only, graph-capturable, any B; the same table, pad
+ *   and finish record) with
+ *     slot    device int32 [B][2] = {begin, limit}: the history column of the occupant's first token and its max_new_tokens.  The
+ *             occupant's own token count at a step is n = (step % history_cols - begin) mod history_cols + 1.  A stop sequence of
+ *             length l matches only if n >= l: tokens of the previous occupant never take part.  A row that reaches n >= limit
+ *             without an eos or stop match finishes with reason MG_STOP_LEN | 0.
+ *     history a RING: the column of a step is step % history_cols, for the write and for the stop-sequence reads, so a session
+ *             runs for any number of steps.  Required, with 0 < history_cols <= ld_history.
+ *     d_pos   one position per row (pos_stride 1).  Only a row that is still open AFTER this step advances by delta: a finished
+ *             row stays at a written position while it idles.  Its token and history column get `pad`.
+ *   state[1] latches the first step at which no row is open; state[0] advances.
+ * mg_slots_admit_bf16: n <= min(B, MG_SLOTS_MAX) staged requests installed into slots, in one launch outside the captured step.
+ *   kstage / vstage [L, n_stage, H, S_stage, 256] are the staging caches, kcache / vcache [L, B, H, Smax, 256] the live ones.
+ *   src_row, dst_slot, len, limit are HOST arrays of n entries, first_token a DEVICE array of n tokens.  For every j: K and V
+ *   positions [0, len[j]) of every layer and head of staging row src_row[j] are copied to live row dst_slot[j] (16-byte vectors,
+ *   64-bit offsets); d_pos[slot] = len[j]; token[slot] = first_token[j]; slot[slot] = {c, limit[j]} with c = (state[0] - 1) %
+ *   history_cols; history[slot][c] = first_token[j]; the row test runs on the first token (eos, stop sequences of length 1, then
+ *   limit[j] <= 1) and leaves finish[slot] = {state[0] - 1, code} or {-1, 0}.  state[1] = -1.  A session starts with state = {1, -1}.
+ *   Refused: a duplicate dst_slot, a slot or staging row out of range, len outside [1, min(S_stage, Smax)], n > B or > MG_SLOTS_MAX. */
+#define MG_STOP_LEN 0x300
+#define MG_SLOTS_MAX 16
+int mg_sample_finish_slots(int64_t* token, int32_t B, int32_t* state, int32_t* d_pos, int32_t delta, int64_t* history,
+                           int64_t ld_history, int32_t history_cols, int32_t* clear, int32_t n_clear, int32_t clear_stride,
+                           int32_t pos_stride, const int32_t* table, int32_t n_eos, int32_t n_seq, int64_t pad, int32_t* finish,
+                           const int32_t* slot, void* stream);
+int mg_slots_admit_bf16(const mg_bf16* kstage, const mg_bf16* vstage, int32_t n_stage, int32_t S_stage, mg_bf16* kcache,
+                        mg_bf16* vcache, int32_t L, int32_t B, int32_t H, int32_t Smax, int32_t n, const int32_t* src_row,
+                        const int32_t* dst_slot, const int32_t* len, const int64_t* first_token, const int32_t* limit,
+                        int32_t* state, int32_t* d_pos, int64_t* token, int32_t* finish, int32_t* slot, int64_t* history,
+                        int64_t ld_history, int32_t history_cols, const int32_t* table, int32_t n_eos, int32_t n_seq, void* stream);
 
 /* Beam search (transformers' GenerationMixin._beam_search, do_sample=False, one eos id; DESIGN.md "Beam search"): three
  * enqueue-only, graph-capturable launches per token step over R = B * k rows (k = num_beams <= 16, rows sample-major).

@@ -390,6 +390,33 @@ __global__ void sample_finish_kernel(const int64_t* __restrict__ tok, int B, int
   state[0] = step + 1;
 }
 
+// The row test of per-row stopping, shared by sample_finish_rows_kernel, sample_finish_slots_kernel and slots_admit_kernel: the
+// code the row finishes with at token t, or 0.  t is the row's newest token, already written at column `col` of its history h; n is
+// the number of the row's OWN tokens up to and including t, so a sequence longer than n cannot match and no older column is read;
+// a column index below 0 wraps by `cols` (a ring history; the plain history has n <= col + 1 and never wraps).  eos is tested first.
+__device__ __forceinline__ int stop_row_code(int64_t t, const int64_t* __restrict__ h, int col, int n, int cols,
+                                             const int32_t* __restrict__ table, int n_eos, int n_seq, bool seqs) {
+  const int32_t* seq_len = table + MG_STOP_MAX_EOS;
+  const int32_t* seq_tok = seq_len + MG_STOP_MAX_SEQ;
+  int code = 0;
+  for (int e = 0; e < n_eos && !code; ++e)
+    if (t == (int64_t)table[e]) code = MG_STOP_EOS | e;
+  if (!code && seqs) {
+    for (int s = 0; s < n_seq && !code; ++s) {
+      const int L = seq_len[s];
+      if (L < 1 || L > MG_STOP_MAX_LEN || L > n) continue;
+      bool eq = true;
+      for (int j = 0; j < L; ++j) {
+        int c = col - L + 1 + j;
+        if (c < 0) c += cols;
+        eq = eq && h[c] == (int64_t)seq_tok[s * MG_STOP_MAX_LEN + j];
+      }
+      if (eq) code = MG_STOP_SEQ | s;
+    }
+  }
+  return code;
+}
+
 // Per-row stopping (DESIGN.md "Per-row stopping"; host statement: sampling.py stop_update): the bookkeeping above with the rule of
 // transformers' _sample -- a finished row is padded and stays finished, the loop ends when no row is unfinished -- for up to 8 eos
 // ids and 16 stop sequences of up to 16 tokens, read from a device table (its contents may change between graph replays, the
@@ -410,8 +437,6 @@ __global__ void sample_finish_rows_kernel(int64_t* __restrict__ tok, int B, int3
   for (int i = threadIdx.x; i < n_clear; i += blockDim.x) clear[(int64_t)i * clear_stride] = 0;
   if (d_pos)
     for (int b = threadIdx.x; b < n_pos; b += blockDim.x) d_pos[b] += delta;
-  const int32_t* seq_len = table + MG_STOP_MAX_EOS;
-  const int32_t* seq_tok = seq_len + MG_STOP_MAX_SEQ;
   const bool in_hist = history && step >= 0 && step < hist_cols;
   bool open = false;
   for (int b = threadIdx.x; b < B; b += blockDim.x) {
@@ -424,18 +449,7 @@ __global__ void sample_finish_rows_kernel(int64_t* __restrict__ tok, int B, int3
     }
     const int64_t t = tok[b];
     if (in_hist) h[step] = t;
-    int code = 0;
-    for (int e = 0; e < n_eos && !code; ++e)
-      if (t == (int64_t)table[e]) code = MG_STOP_EOS | e;
-    if (!code && in_hist) {
-      for (int s = 0; s < n_seq && !code; ++s) {
-        const int L = seq_len[s];
-        if (L < 1 || L > MG_STOP_MAX_LEN || L > step + 1) continue;
-        bool eq = true;
-        for (int j = 0; j < L; ++j) eq = eq && h[step - L + 1 + j] == (int64_t)seq_tok[s * MG_STOP_MAX_LEN + j];
-        if (eq) code = MG_STOP_SEQ | s;
-      }
-    }
+    const int code = stop_row_code(t, h, step, step + 1, hist_cols, table, n_eos, n_seq, in_hist);
     if (code) { f[0] = step; f[1] = code; }
     else open = true;
   }
@@ -444,6 +458,91 @@ __global__ void sample_finish_rows_kernel(int64_t* __restrict__ tok, int B, int3
   if (threadIdx.x != 0) return;
   if (!s_open && state[1] < 0) state[1] = step;
   state[0] = step + 1;
+}
+
+// Request streams (DESIGN.md "Request streams"; host statement: sampling.py slot_update): the bookkeeping of a slot session.  The
+// launch above with a window per row -- slot[b] = {begin, limit}: the history column of the occupant's first token and its token
+// budget --, a RING history (column step % hist_cols, so a session runs for any number of steps) and frozen finished rows: the
+// position of a row advances only while it stays open after this step, so an idle slot rewrites one written position and never
+// walks past Smax.  The row's own token count is n = (column - begin) mod hist_cols + 1: tokens of the slot's previous occupant
+// never take part in a stop sequence, and a row that reaches n >= limit without a match finishes with MG_STOP_LEN.
+__global__ void sample_finish_slots_kernel(int64_t* __restrict__ tok, int B, int32_t* __restrict__ state, int32_t* __restrict__ d_pos,
+                                           int delta, int64_t* __restrict__ history, int64_t ld_hist, int hist_cols,
+                                           int32_t* __restrict__ clear, int n_clear, int clear_stride,
+                                           const int32_t* __restrict__ table, int n_eos, int n_seq, int64_t pad,
+                                           int32_t* __restrict__ finish, const int32_t* __restrict__ slot) {
+  __shared__ int s_step, s_open;
+  if (threadIdx.x == 0) { s_step = state[0]; s_open = 0; }
+  __syncthreads();
+  const int step = s_step;
+  for (int i = threadIdx.x; i < n_clear; i += blockDim.x) clear[(int64_t)i * clear_stride] = 0;
+  const int col = ((step % hist_cols) + hist_cols) % hist_cols;
+  bool open = false;
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    int64_t* h = history + (int64_t)b * ld_hist;
+    int32_t* f = finish + 2 * (int64_t)b;
+    if (f[0] >= 0) {                      // an idle slot: padded, its position stays where it is
+      tok[b] = pad;
+      h[col] = pad;
+      continue;
+    }
+    const int64_t t = tok[b];
+    h[col] = t;
+    const int begin = slot[2 * (int64_t)b], limit = slot[2 * (int64_t)b + 1];
+    const int n = (((col - begin) % hist_cols) + hist_cols) % hist_cols + 1;
+    int code = stop_row_code(t, h, col, n, hist_cols, table, n_eos, n_seq, true);
+    if (!code && n >= limit) code = MG_STOP_LEN;
+    if (code) { f[0] = step; f[1] = code; }
+    else {
+      open = true;
+      if (d_pos) d_pos[b] += delta;
+    }
+  }
+  if (open) atomicOr(&s_open, 1);
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  if (!s_open && state[1] < 0) state[1] = step;
+  state[0] = step + 1;
+}
+
+// Admission of a slot session: n staged requests installed in one launch.  Block (h, j, l) copies K and V positions [0, len_j) of
+// layer l, head h from staging row src_row[j] to live row dst_slot[j] -- len_j * 512 contiguous bytes each, as 16-byte vectors, all
+// offsets 64-bit --; thread 0 of block (0, j, 0) installs request j's bookkeeping and runs the row test on its first token.
+struct SlotsAdmitArgs {
+  const uint4* kstage; const uint4* vstage; uint4* kcache; uint4* vcache;
+  int n_stage, H, S_stage, B, Smax;
+  int32_t src_row[MG_SLOTS_MAX], dst_slot[MG_SLOTS_MAX], len[MG_SLOTS_MAX], limit[MG_SLOTS_MAX];
+  const int64_t* first_token;
+  int32_t* state; int32_t* d_pos; int64_t* token; int32_t* finish; int32_t* slot;
+  int64_t* history; int64_t ld_hist; int hist_cols;
+  const int32_t* table; int n_eos, n_seq;
+};
+
+__global__ void slots_admit_kernel(SlotsAdmitArgs a) {
+  const int h = blockIdx.x, j = blockIdx.y, l = blockIdx.z;
+  const int64_t n_vec = (int64_t)a.len[j] * 32;                 // 256 bf16 = 32 vectors of 16 bytes per position
+  const int64_t src = (((int64_t)l * a.n_stage + a.src_row[j]) * a.H + h) * a.S_stage * 32;
+  const int64_t dst = (((int64_t)l * a.B + a.dst_slot[j]) * a.H + h) * a.Smax * 32;
+  for (int64_t i = threadIdx.x; i < n_vec; i += blockDim.x) {
+    a.kcache[dst + i] = a.kstage[src + i];
+    a.vcache[dst + i] = a.vstage[src + i];
+  }
+  if (threadIdx.x != 0 || h != 0 || l != 0) return;
+  const int prev = a.state[0] - 1;                              // the step whose column the first token takes
+  const int c = ((prev % a.hist_cols) + a.hist_cols) % a.hist_cols;
+  const int b = a.dst_slot[j];
+  const int64_t t = a.first_token[j];
+  int64_t* hrow = a.history + (int64_t)b * a.ld_hist;
+  a.d_pos[b] = a.len[j];
+  a.token[b] = t;
+  a.slot[2 * b] = c;
+  a.slot[2 * b + 1] = a.limit[j];
+  hrow[c] = t;
+  int code = stop_row_code(t, hrow, c, 1, a.hist_cols, a.table, a.n_eos, a.n_seq, true);
+  if (!code && a.limit[j] <= 1) code = MG_STOP_LEN;
+  a.finish[2 * b] = code ? prev : -1;
+  a.finish[2 * b + 1] = code;
+  if (j == 0) a.state[1] = -1;
 }
 
 }  // namespace
@@ -506,6 +605,63 @@ extern "C" int mg_sample_finish_rows(int64_t* token, int32_t B, int32_t* state, 
   hipLaunchKernelGGL(sample_finish_rows_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, token, B, state, d_pos, delta,
                      pos_stride ? B : 1, history, ld_history, history ? history_cols : 0, clear, clear ? n_clear : 0,
                      clear_stride > 0 ? clear_stride : 1, table, n_eos, n_seq, pad, finish);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_sample_finish_slots(int64_t* token, int32_t B, int32_t* state, int32_t* d_pos, int32_t delta, int64_t* history,
+                                      int64_t ld_history, int32_t history_cols, int32_t* clear, int32_t n_clear, int32_t clear_stride,
+                                      int32_t pos_stride, const int32_t* table, int32_t n_eos, int32_t n_seq, int64_t pad,
+                                      int32_t* finish, const int32_t* slot, void* stream) {
+  const char* who = "mg_sample_finish_slots";
+  if (!token || !state || !table || !finish || !slot || B <= 0) MG_FAIL(MG_ERR_SHAPE, "%s: bad arguments", who);
+  if (d_pos && pos_stride != 1) MG_FAIL(MG_ERR_SHAPE, "%s: a slot session keeps one position per row (pos_stride must be 1)", who);
+  if (!history || history_cols <= 0 || ld_history < history_cols) MG_FAIL(MG_ERR_SHAPE, "%s: needs a ring history with 0 < history_cols <= ld_history", who);
+  if (n_eos < 1 || n_eos > MG_STOP_MAX_EOS || n_seq < 0 || n_seq > MG_STOP_MAX_SEQ)
+    MG_FAIL(MG_ERR_SHAPE, "%s: need 1 <= n_eos <= %d and 0 <= n_seq <= %d, got %d / %d", who, MG_STOP_MAX_EOS, MG_STOP_MAX_SEQ, n_eos, n_seq);
+  hipLaunchKernelGGL(sample_finish_slots_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, token, B, state, d_pos, delta, history,
+                     ld_history, history_cols, clear, clear ? n_clear : 0, clear_stride > 0 ? clear_stride : 1, table, n_eos, n_seq, pad,
+                     finish, slot);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_slots_admit_bf16(const mg_bf16* kstage, const mg_bf16* vstage, int32_t n_stage, int32_t S_stage, mg_bf16* kcache,
+                                   mg_bf16* vcache, int32_t L, int32_t B, int32_t H, int32_t Smax, int32_t n, const int32_t* src_row,
+                                   const int32_t* dst_slot, const int32_t* len, const int64_t* first_token, const int32_t* limit,
+                                   int32_t* state, int32_t* d_pos, int64_t* token, int32_t* finish, int32_t* slot, int64_t* history,
+                                   int64_t ld_history, int32_t history_cols, const int32_t* table, int32_t n_eos, int32_t n_seq,
+                                   void* stream) {
+  const char* who = "mg_slots_admit_bf16";
+  if (!kstage || !vstage || !kcache || !vcache || !src_row || !dst_slot || !len || !first_token || !limit || !state || !d_pos || !token ||
+      !finish || !slot || !history || !table)
+    MG_FAIL(MG_ERR_SHAPE, "%s: null pointer", who);
+  if (L <= 0 || B <= 0 || H <= 0 || Smax <= 0 || n_stage <= 0 || S_stage <= 0) MG_FAIL(MG_ERR_SHAPE, "%s: bad cache geometry", who);
+  if (H > 65535 || L > 65535) MG_FAIL(MG_ERR_SHAPE, "%s: grid too large", who);
+  if (n < 1 || n > B || n > MG_SLOTS_MAX) MG_FAIL(MG_ERR_SHAPE, "%s: need 1 <= n <= min(B, %d), got n = %d at B = %d", who, MG_SLOTS_MAX, n, B);
+  if (history_cols <= 0 || ld_history < history_cols) MG_FAIL(MG_ERR_SHAPE, "%s: bad history geometry", who);
+  if (n_eos < 1 || n_eos > MG_STOP_MAX_EOS || n_seq < 0 || n_seq > MG_STOP_MAX_SEQ)
+    MG_FAIL(MG_ERR_SHAPE, "%s: need 1 <= n_eos <= %d and 0 <= n_seq <= %d, got %d / %d", who, MG_STOP_MAX_EOS, MG_STOP_MAX_SEQ, n_eos, n_seq);
+  if (!MG_ALIGNED16(kstage) || !MG_ALIGNED16(vstage) || !MG_ALIGNED16(kcache) || !MG_ALIGNED16(vcache))
+    MG_FAIL(MG_ERR_ALIGN, "%s: the caches must be 16-byte aligned", who);
+  if (((uintptr_t)state | (uintptr_t)d_pos | (uintptr_t)finish | (uintptr_t)slot | (uintptr_t)table) & 3)
+    MG_FAIL(MG_ERR_ALIGN, "%s: int32 buffers must be 4-byte aligned", who);
+  if (((uintptr_t)token | (uintptr_t)history | (uintptr_t)first_token) & 7) MG_FAIL(MG_ERR_ALIGN, "%s: token buffers must be 8-byte aligned", who);
+  SlotsAdmitArgs a{};
+  const int len_max = S_stage < Smax ? S_stage : Smax;
+  for (int j = 0; j < n; ++j) {
+    if (src_row[j] < 0 || src_row[j] >= n_stage) MG_FAIL(MG_ERR_SHAPE, "%s: src_row[%d] = %d outside [0, %d)", who, j, src_row[j], n_stage);
+    if (dst_slot[j] < 0 || dst_slot[j] >= B) MG_FAIL(MG_ERR_SHAPE, "%s: dst_slot[%d] = %d outside [0, %d)", who, j, dst_slot[j], B);
+    for (int i = 0; i < j; ++i)
+      if (dst_slot[i] == dst_slot[j]) MG_FAIL(MG_ERR_SHAPE, "%s: slot %d is the target of requests %d and %d", who, dst_slot[j], i, j);
+    if (len[j] < 1 || len[j] > len_max) MG_FAIL(MG_ERR_SHAPE, "%s: len[%d] = %d outside [1, %d]", who, j, len[j], len_max);
+    a.src_row[j] = src_row[j]; a.dst_slot[j] = dst_slot[j]; a.len[j] = len[j]; a.limit[j] = limit[j];
+  }
+  a.kstage = (const uint4*)kstage; a.vstage = (const uint4*)vstage; a.kcache = (uint4*)kcache; a.vcache = (uint4*)vcache;
+  a.n_stage = n_stage; a.H = H; a.S_stage = S_stage; a.B = B; a.Smax = Smax;
+  a.first_token = first_token; a.state = state; a.d_pos = d_pos; a.token = token; a.finish = finish; a.slot = slot;
+  a.history = history; a.ld_hist = ld_history; a.hist_cols = history_cols; a.table = table; a.n_eos = n_eos; a.n_seq = n_seq;
+  hipLaunchKernelGGL(slots_admit_kernel, dim3(H, n, L), dim3(256), 0, (hipStream_t)stream, a);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }

@@ -82,6 +82,10 @@ class KVCache:
         # Addresses and the table's capacity are launch arguments of the captured step, the contents are not; trie_held is the
         # ConstraintMode whose table and roots the buffers hold
         self.trie_table = self.trie_roots = self.trie_path = self.trie_held = None
+        # request streams (DESIGN.md "Request streams"): the per-row window int32 [B, 2] = {begin column, token budget} and the RING
+        # token history int64 [B, ring_cols] of a slot session (SlotSession sets ring_cols, SelectionPlan.arm allocates); their
+        # addresses and ring_cols are launch arguments of the captured step
+        self.slot_table, self.ring, self.ring_cols = None, None, 0
 
     def alloc_trie(self, n_ints: int):
         """The constraint's buffers for a table of ``n_ints`` (kept when it fits); steps captured on other buffers are dropped."""
@@ -246,6 +250,7 @@ class StepKey(NamedTuple):
     n_top: Optional[int]        # the log-probability buffers' addresses are launch arguments too (KVCache.alloc_logprobs)
     constrained: bool           # the trie buffers' addresses and capacity are launch arguments (KVCache.alloc_trie)
     guidance: Optional[tuple]   # (scale, cut)
+    slots: bool = False         # the bookkeeping launch is the slot session's (window, ring history, frozen finished rows)
 
     @property
     def beam(self) -> bool:
@@ -269,6 +274,7 @@ class SelectionPlan(NamedTuple):
     vocab: Optional[int] = None             # V the token ids were checked against (None: arm() cannot check them)
     select: bool = True                     # False: a teacher-forced position, only the KV write position advances
     keys: tuple = ()                        # graph_key of feed_back False / True, computed once (keyed)
+    slots: bool = False                     # a slot session's step (SlotSession): per-row stopping with ops.sample_finish_slots
 
     @property
     def is_beam(self) -> bool:
@@ -302,7 +308,7 @@ class SelectionPlan(NamedTuple):
         """The plan with both of its step keys computed: a replayed step looks its graph up without building anything."""
         p, s = self.proc, self.stop
         rest = (self.mode if self.select else "noselect", None if p is None else tuple(p[:3]) + (len(p[3]),),
-                None if s is None else (len(s[0]), len(s[1]), s[0][0]), self.n_top, self.cons is not None, self.guidance)
+                None if s is None else (len(s[0]), len(s[1]), s[0][0]), self.n_top, self.cons is not None, self.guidance, self.slots)
         return self._replace(keys=(StepKey(False, *rest), StepKey(True, *rest)))
 
     def graph_key(self, feed_back: bool) -> StepKey:
@@ -356,6 +362,13 @@ class SelectionPlan(NamedTuple):
                 cache.stop_held = tuple(self.stop)
             if first:       # every row unfinished again
                 cache.finish.copy_(torch.tensor([[-1, 0]] * cache.B, dtype=torch.int32), non_blocking=True)
+        if self.slots:
+            if self.stop is None or not cache.ragged or cache.ring_cols < 1:
+                raise ValueError("a slot step needs per-row stopping and a ragged cache with ring_cols set (SlotSession)")
+            if cache.ring is None or cache.ring.shape[1] != cache.ring_cols:
+                cache.slot_table = torch.zeros(cache.B, 2, dtype=torch.int32, device=dev)
+                cache.ring = torch.zeros(cache.B, cache.ring_cols, dtype=torch.int64, device=dev)
+                cache._drop_graphs(lambda key: key.slots)
         rows = self.rows(cache)
         cons = self.cons
         if cons is not None:
@@ -921,11 +934,15 @@ class LMEngine:
 
     @classmethod
     def selection_plan(cls, plan=None, *, sampling=None, beam=None, processors=None, stop=None, logprobs=None, constraint=None,
-                       guidance=None, vocab: Optional[int] = None, contrast=None) -> SelectionPlan:
+                       guidance=None, vocab: Optional[int] = None, contrast=None, slots: bool = False) -> SelectionPlan:
         """The SelectionPlan of the public selection keywords (forward's), checked: the one place that calls the normalisers
         below and that refuses what beam search and contrastive search (``contrast`` = (top_k, penalty_alpha)) are not combined
         with.  A plan that is already built comes back as it is, so a loop builds one and passes ``plan=`` on every call.
-        ``vocab``: the number of logits V the token ids must lie in."""
+        ``vocab``: the number of logits V the token ids must lie in.  ``slots``: the step of a slot session (SlotSession; DESIGN.md
+        "Request streams"): greedy or sampled selection with per-row stopping, nothing else."""
+        if slots and (stop is None or any(v is not None for v in (beam, processors, logprobs, constraint, guidance, contrast))):
+            raise NotImplementedError("a slot session selects greedily or by sampling under per-row stopping: beam and contrastive search, "
+                                      "the logits processors, log-probabilities, constraints and guidance are not combined with it yet")
         if plan is not None:
             if any(v is not None for v in (sampling, beam, processors, stop, logprobs, constraint, guidance, contrast)):
                 raise ValueError("pass plan= or the selection keywords it was built from, not both")
@@ -948,7 +965,7 @@ class LMEngine:
                 raise ValueError("contrastive search is deterministic: it takes no sampling mode")
             mode = cls.contrast_mode(contrast, vocab)
         return SelectionPlan(mode, cls.proc_mode(processors), cls.stop_mode(stop), cls.logprob_mode(logprobs, vocab),
-                             cls.constraint_mode(constraint), cls.guidance_mode(guidance), vocab).keyed()
+                             cls.constraint_mode(constraint), cls.guidance_mode(guidance), vocab, slots=bool(slots)).keyed()
 
     @staticmethod
     def sample_mode(sampling):
@@ -1527,7 +1544,11 @@ class LMEngine:
         if n_top is not None:
             ops.token_logprobs(logits if raw is None else raw, tok, rows(cache.lp), rows(cache.top_id) if n_top else None,
                                rows(cache.top_lp) if n_top else None, state=cache.sample_state)
-        if stop is not None:
+        if plan.slots:
+            assert guidance is None and n_top is None and proc is None and cons is None
+            ops.sample_finish_slots(tok, cache.sample_state, cache.stop_table, len(stop[0]), len(stop[1]), stop[0][0], cache.finish,
+                                    cache.slot_table, cache.ring, d_pos=cache.d_pos if advance else None)
+        elif stop is not None:
             ops.sample_finish_rows(tok, cache.sample_state, cache.stop_table, len(stop[0]), len(stop[1]), stop[0][0],
                                    rows(cache.finish), d_pos=cache.d_pos if advance else None, history=rows(cache.history),
                                    pos_stride=cache.pos_stride)
@@ -1844,3 +1865,165 @@ class LMEngine:
         top_lp = torch.empty(n, 1, n_top, dtype=torch.float32, device=self.device)
         ops.token_logprobs(logits, kept, lp, top_id if n_top else None, top_lp if n_top else None)
         return lp[:, 0], top_id[:, 0], top_lp[:, 0]
+
+
+class SlotSession:
+    """Generation over a stream of requests (DESIGN.md "Request streams"; sampling.generate_stream): ``slots`` rows generate in
+    one captured token step, and the row of a request that has finished is handed to the next request while the others keep
+    generating.  The session owns a private ragged KVCache (never pooled, never handed out) and a staging cache of
+    ``admit_rows`` rows; it runs rounds of
+      harvest  one host look (one blocking copy) at the finish record and the ring history: every newly finished row gives its
+               tokens;
+      admit    up to as many requests as slots are free are pulled, prefilled in passes of the FIXED shape (admit_rows, S_stage)
+               -- so a request's bits do not depend on what was admitted with it --, their first tokens selected from the staged
+               logits and installed with one ops.slots_admit launch per pass;
+      step     ``every`` replays of the captured token step under ``plan`` (plan.slots).
+    The host mirrors every slot's occupant, begin column and position bound by counting the steps it enqueued: nothing but the
+    harvest reads the device.
+    Sampled selection: a token step draws from the Philox counter (state[0] = 1 + steps enqueued, slot), as every generate() loop
+    does; the first token of a request is drawn at its admission from a counter domain of its own, (admit_counter(pass), staging
+    row) with admit_counter(p) = -1 - p -- as the kernel's unsigned counter word 2^32 - 1 - p, which no token step reaches -- so
+    no two draws of a session share a counter (draw_counters is the host statement of which ones a schedule uses)."""
+
+    @staticmethod
+    def admit_counter(n_pass: int) -> int:
+        """The value of state[0] the first tokens of admission pass ``n_pass`` (0, 1, ...) are drawn under."""
+        return -1 - int(n_pass)
+
+    @staticmethod
+    def draw_counters(schedule):
+        """[(unsigned 32-bit counter word, row)] of every draw of a session, in order: ``schedule`` lists ("admit", staging rows
+        used) and ("step", slots) events as the session enqueues them.  Host statement of the counters, for checking that they
+        are unique."""
+        out, steps, passes = [], 0, 0
+        for kind, rows in schedule:
+            if kind == "admit":
+                out += [(SlotSession.admit_counter(passes) & 0xffffffff, j) for j in range(rows)]
+                passes += 1
+            else:
+                out += [((1 + steps) & 0xffffffff, b) for b in range(rows)]
+                steps += 1
+        return out
+
+    def __init__(self, engine: "LMEngine", plan: SelectionPlan, *, slots: int, max_new: int, max_prompt: int, every: int,
+                 admit_rows: int, seed: Optional[int] = None):
+        if not plan.slots or plan.stop is None:
+            raise ValueError("a slot session runs under a plan built with slots=True and per-row stopping")
+        if not 1 <= slots <= ops.SLOTS_MAX or not 1 <= admit_rows <= slots or max_new < 1 or max_prompt < 1 or every < 1:
+            raise ValueError(f"need 1 <= admit_rows <= slots <= {ops.SLOTS_MAX} and max_new, max_prompt, every >= 1")
+        n_pos = engine.cfg.max_position_embeddings
+        self.S_stage = ops.ceil_to(max_prompt, 64)
+        if max_prompt + max_new > n_pos or self.S_stage > n_pos:
+            raise ValueError(f"max_prompt = {max_prompt} (staged as {self.S_stage} rows) + max_new_tokens = {max_new} exceeds "
+                             f"max_position_embeddings = {n_pos}")
+        dev = engine.device
+        self.engine, self.plan, self.B, self.every, self.n_admit = engine, plan, slots, every, admit_rows
+        self.max_new, self.max_prompt = max_new, max_prompt
+        self.cache = cache = KVCache(engine.L, slots, engine.H, ops.ceil_to(max_prompt + max_new, 64), dev, ragged=True)
+        self.stage = KVCache(engine.L, admit_rows, engine.H, self.S_stage, dev, ragged=True)
+        self.stage_in = torch.zeros(admit_rows, self.S_stage, engine.d, dtype=BF16, device=dev)
+        self.first = torch.zeros(admit_rows, dtype=torch.int64, device=dev)
+        self.admit_state = torch.tensor([-1, -1], dtype=torch.int32, device=dev)      # {admit_counter(pass), unused}: the admissions' draws
+        self.passes = 0                 # admission passes enqueued
+        # the ring holds a finished row's tokens until the next harvest, at most ``every`` steps later: Hc >= max_new + every
+        self.Hc = 1 << (max_new + every - 1).bit_length()
+        assert self.Hc >= max_new + every
+        cache.ring_cols, cache.eos = self.Hc, int(plan.stop[0][0])
+        cache.sample_state.copy_(torch.tensor([1, -1], dtype=torch.int32), non_blocking=True)    # column (state[0] - 1) exists
+        if seed is not None:
+            cache.seed.fill_(int(seed) & 0x7fffffffffffffff)
+        self.st = engine._ensure_decode_state(cache)
+        if self.st.refusal is not None:
+            raise NotImplementedError(self.st.refusal)
+        plan.arm(cache, self.st, first=True)
+        # every slot starts finished and idle at position 0
+        cache.finish.copy_(torch.tensor([[0, ops.STOP_LEN]] * slots, dtype=torch.int32), non_blocking=True)
+        cache.d_pos.zero_()
+        self.steps = 0                  # token steps enqueued: the device's state[0] is 1 + steps
+        self.occ = [None] * slots       # per slot: (request index, begin column, prompt length, limit, steps at admission)
+
+    def _bound(self, o) -> int:
+        """The largest position the occupant's row can be at now."""
+        return o[2] + min(self.steps - o[4], o[3] - 1)
+
+    @torch.no_grad()
+    def _admit(self, batch, slots):
+        """One staging pass: ``batch`` = [(index, (S, d) embeddings, limit)] goes to the free ``slots`` (as many)."""
+        eng, cache, n = self.engine, self.cache, len(batch)
+        self.stage_in.zero_()
+        lens = [1] * self.n_admit       # unused staging rows: one zero row
+        for j, (_, emb, _) in enumerate(batch):
+            lens[j] = emb.shape[0]
+            self.stage_in[j, : lens[j]].copy_(emb)
+        x, _ = eng._blocks_prefill(self.stage_in, self.stage)
+        rows = (torch.arange(self.n_admit, dtype=torch.int64) * self.S_stage + torch.tensor(lens) - 1).to(eng.device, non_blocking=True)
+        logits = eng._head(ops.layernorm(x.index_select(0, rows), eng.lnf_g, eng.lnf_b, eng.eps))
+        mode = self.plan.mode
+        if mode is None:
+            ops.argmax(logits, out=self.first)
+        else:       # a counter domain of its own: the token steps draw under state[0] = 1, 2, ..., never under a negative value
+            self.admit_state[:1].fill_(self.admit_counter(self.passes))
+            if mode[0] == "warp":
+                ops.sample_warp(logits, mode[1], mode[2], mode[3], mode[4], cache.seed, self.admit_state, out=self.first)
+            else:
+                ops.sample(logits, mode[0], mode[1], mode[2], cache.seed, self.admit_state, out=self.first)
+        self.passes += 1
+        stop = self.plan.stop
+        ops.slots_admit(self.stage.k, self.stage.v, cache.k, cache.v, list(range(n)), slots, lens[:n], self.first,
+                        [it[2] for it in batch], cache.sample_state, cache.d_pos, self.st.token, cache.finish, cache.slot_table,
+                        cache.ring, cache.stop_table, len(stop[0]), len(stop[1]))
+        for j, (index, _, limit) in enumerate(batch):
+            self.occ[slots[j]] = (index, self.steps % self.Hc, lens[j], limit, self.steps)
+
+    @torch.no_grad()
+    def _step(self):
+        self.cache.pos = max([self._bound(o) for o in self.occ if o is not None] + [0])
+        self.engine.decode(None, self.cache, plan=self.plan)
+        self.steps += 1
+
+    def _harvest(self):
+        """[(request index, int64 CPU tokens, finish code, slot)] of the rows that have finished since the last look."""
+        if all(o is None for o in self.occ):
+            return []
+        # the one sync of a round: the finish record and the ring in one blocking copy (both are a few KB)
+        both = torch.cat([self.cache.finish.view(-1).to(torch.int64), self.cache.ring.view(-1)]).cpu()
+        fin, ring = both[: 2 * self.B].view(self.B, 2), both[2 * self.B:].view(self.B, self.Hc)
+        done = [b for b, o in enumerate(self.occ) if o is not None and int(fin[b, 0]) >= 0]
+        out = []
+        for b in done:
+            index, begin = self.occ[b][:2]
+            count = (int(fin[b, 0]) % self.Hc - begin) % self.Hc + 1
+            cols = (begin + torch.arange(count)) % self.Hc
+            out.append((index, ring[b, cols].clone(), int(fin[b, 1]), b))
+            self.occ[b] = None
+        return out
+
+    def run(self, requests):
+        """Yield (request index, tokens, finish code, slot) in completion order.  ``requests`` yields (index, (S, d) embeddings on
+        the engine's device, limit), is pulled lazily -- one item when a slot frees.  When it raises, nothing more is pulled, the
+        requests pulled before it are admitted and every row in flight is generated to its end and yielded; then the error is
+        raised: no request in front of the failing one is lost."""
+        it, exhausted, error = iter(requests), False, None
+        while True:
+            yield from self._harvest()
+            free = [b for b in range(self.B) if self.occ[b] is None]
+            while free and not exhausted:
+                batch = []
+                while len(batch) < min(len(free), self.n_admit):
+                    try:
+                        batch.append(next(it))
+                    except StopIteration:
+                        exhausted = True
+                        break
+                    except Exception as e:  # noqa: BLE001  (raised again once the rows in flight are done)
+                        exhausted, error = True, e
+                        break
+                if batch:
+                    self._admit(batch, free[: len(batch)])
+                    free = free[len(batch):]
+            if all(o is None for o in self.occ):
+                if error is not None:
+                    raise error
+                return
+            for _ in range(self.every):
+                self._step()

@@ -336,6 +336,15 @@ class Magma(nn.Module):
                         guidance_min_p=guidance_min_p, num_beam_groups=num_beam_groups, diversity_penalty=diversity_penalty,
                         penalty_alpha=penalty_alpha)
 
+    def generate_stream(self, requests, **kwargs):
+        """Generate over a stream of requests -- an iterable of ``embed`` outputs, or pairs (embeddings, max_new_tokens) --: a
+        generator of ``sampling.StreamResult(index, tokens, text, reason, reason_index, slot)``, one per request in completion
+        order, each what a solo ``generate`` of that request gives.  The HIP engine hands the row of a finished request to the next
+        one while the other rows keep generating (see sampling.generate_stream for the keywords)."""
+        from .sampling import generate_stream
+        torch.cuda.set_device(self.device)
+        return generate_stream(self, requests, **kwargs)
+
     @torch.no_grad()
     def choose(self, embeddings, choices, lengths=None, **generate_kwargs):
         """Which of ``choices`` (a ``sampling.TokenTrie``, a list of token-id sequences or strings, or one of either per row) the

@@ -873,6 +873,64 @@ def sample_finish_rows(token: torch.Tensor, state: torch.Tensor, table: torch.Te
           "mg_sample_finish_rows")
 
 
+STOP_LEN = 0x300                                                        # include/magma_hip.h MG_STOP_LEN: the budget ran out
+SLOTS_MAX = 16                                                          # include/magma_hip.h MG_SLOTS_MAX
+
+
+def sample_finish_slots(token: torch.Tensor, state: torch.Tensor, table: torch.Tensor, n_eos: int, n_seq: int, pad: int,
+                        finish: torch.Tensor, slot: torch.Tensor, history: torch.Tensor, d_pos: Optional[torch.Tensor] = None,
+                        delta: int = 1):
+    """The bookkeeping launch of a slot session (mg_sample_finish_slots; host statement: sampling.slot_update):
+    sample_finish_rows with a per-row window ``slot`` int32 [B, 2] = (begin column, token budget), ``history`` read and written as
+    a ring of ``history.shape[1]`` columns, and positions that advance only for rows still open after this step.  A row whose
+    own tokens reach its budget without a match finishes with ``STOP_LEN``.  Enqueue-only."""
+    _need_gpu(token, state, table, finish, slot, d_pos, history)
+    B = token.numel()
+    assert token.dtype == torch.int64 and token.is_contiguous() and state.dtype == torch.int32 and state.numel() >= 2
+    assert table.dtype == torch.int32 and table.is_contiguous() and table.numel() >= STOP_TABLE_INTS
+    assert finish.dtype == torch.int32 and finish.is_contiguous() and finish.shape == (B, 2)
+    assert slot.dtype == torch.int32 and slot.is_contiguous() and slot.shape == (B, 2)
+    assert history.dtype == torch.int64 and history.ndim == 2 and history.stride(1) == 1 and history.shape[0] == B
+    if d_pos is not None:
+        _pos_stride(d_pos, B, 1)
+    check(L.load().mg_sample_finish_slots(token.data_ptr(), B, state.data_ptr(), _p(d_pos), delta, history.data_ptr(),
+                                          history.stride(0), history.shape[1], None, 0, 1, 1, table.data_ptr(), int(n_eos),
+                                          int(n_seq), int(pad), finish.data_ptr(), slot.data_ptr(), _stream()),
+          "mg_sample_finish_slots")
+
+
+def slots_admit(kstage: torch.Tensor, vstage: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, src_row, dst_slot, lens,
+                first_token: torch.Tensor, limits, state: torch.Tensor, d_pos: torch.Tensor, token: torch.Tensor,
+                finish: torch.Tensor, slot: torch.Tensor, history: torch.Tensor, table: torch.Tensor, n_eos: int, n_seq: int):
+    """Install n staged requests into slots of a slot session in one launch (mg_slots_admit_bf16): K / V positions [0, lens[j])
+    of staging row ``src_row[j]`` ([L, n_stage, H, S_stage, 256]) go to live row ``dst_slot[j]`` ([L, B, H, Smax, 256]); the slot's
+    position, token (``first_token[j]``, on the device), window, history column and finish record are set as the header states.
+    ``src_row``, ``dst_slot``, ``lens`` and ``limits`` are host integers; what they must satisfy is checked by the entry point."""
+    _need_gpu(kstage, vstage, kcache, vcache, first_token, state, d_pos, token, finish, slot, history, table)
+    Lr, n_stage, H, S_stage, hd = kstage.shape
+    _, B, _, Smax, _ = kcache.shape
+    assert hd == 256 and kcache.shape[4] == 256 and (kcache.shape[0], kcache.shape[2]) == (Lr, H)
+    assert vstage.shape == kstage.shape and vcache.shape == kcache.shape
+    assert all(t.dtype == BF16 and t.is_contiguous() for t in (kstage, vstage, kcache, vcache))
+    n = len(src_row)
+    assert len(dst_slot) == len(lens) == len(limits) == n
+    assert first_token.dtype == torch.int64 and first_token.is_contiguous()
+    if first_token.numel() < n:
+        raise ValueError(f"first_token holds {first_token.numel()} tokens for {n} requests")
+    assert state.dtype == torch.int32 and state.numel() >= 2 and token.dtype == torch.int64 and token.is_contiguous()
+    assert d_pos.dtype == torch.int32 and d_pos.is_contiguous() and d_pos.numel() >= B and token.numel() >= B
+    assert finish.dtype == torch.int32 and finish.is_contiguous() and finish.shape == (B, 2)
+    assert slot.dtype == torch.int32 and slot.is_contiguous() and slot.shape == (B, 2)
+    assert history.dtype == torch.int64 and history.ndim == 2 and history.stride(1) == 1 and history.shape[0] == B
+    assert table.dtype == torch.int32 and table.is_contiguous() and table.numel() >= STOP_TABLE_INTS
+    arr = lambda xs: (C.c_int32 * max(n, 1))(*[int(x) for x in xs])  # noqa: E731
+    check(L.load().mg_slots_admit_bf16(kstage.data_ptr(), vstage.data_ptr(), n_stage, S_stage, kcache.data_ptr(), vcache.data_ptr(),
+                                       Lr, B, H, Smax, n, arr(src_row), arr(dst_slot), arr(lens), first_token.data_ptr(),
+                                       arr(limits), state.data_ptr(), d_pos.data_ptr(), token.data_ptr(), finish.data_ptr(),
+                                       slot.data_ptr(), history.data_ptr(), history.stride(0), history.shape[1], table.data_ptr(),
+                                       int(n_eos), int(n_seq), _stream()), "mg_slots_admit_bf16")
+
+
 def advance_pos(d_pos: torch.Tensor, delta: int = 1, *, pos_stride: int = 0):
     """d_pos[0] += delta; with ``pos_stride=1`` every entry of d_pos (one position per row) += delta."""
     ps = _pos_stride(d_pos, d_pos.numel(), pos_stride)

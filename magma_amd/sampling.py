@@ -634,6 +634,8 @@ def guide_logits(cond, uncond, guidance_scale, guidance_min_p=0.0):
 
 MAX_EOS_IDS, MAX_STOP_SEQS, MAX_STOP_LEN = 8, 16, 16
 REASON_NONE, REASON_EOS, REASON_STOP = 0, 1, 2
+REASON_LENGTH = 3       # a slot session's row reached its own max_new_tokens (the device's MG_STOP_LEN >> 8)
+REASON_NAMES = {REASON_NONE: "length", REASON_EOS: "eos", REASON_STOP: "stop", REASON_LENGTH: "length"}
 
 
 class Finish(NamedTuple):
@@ -720,6 +722,46 @@ def stop_update(history, step: int, done, eos_ids, stop_seqs=()):
                 if 1 <= n <= step + 1 and hist[r, step + 1 - n: step + 1].tolist() == [int(x) for x in q]:
                     hit = (REASON_STOP, j)
                     break
+        if hit is not None:
+            done[r] = True
+            reason[r, 0], reason[r, 1] = hit
+    return done, reason
+
+
+def slot_update(ring, step: int, done, begin, limit, eos_ids, stop_seqs=()):
+    """The row test of a slot session, host statement (the device kernel is csrc/sampling.hip, sample_finish_slots_kernel):
+    ``stop_update`` with a window, a budget and a ring.  ``ring`` (R, Hc) int64 is the token history read as a ring: the column of
+    a step is step % Hc, and it already holds this step's tokens.  ``begin`` (R,) is the column of every row's occupant's first
+    token, ``limit`` (R,) its max_new_tokens.  The occupant's own token count is n = (step % Hc - begin) mod Hc + 1.  A row that is
+    not done finishes at this step
+      eos     as in stop_update, tested first;
+      stop    if its last L tokens are one of ``stop_seqs`` AND L <= n: tokens of the slot's previous occupant never take part,
+              while a sequence that straddles the ring's wrap does match;
+      length  if n >= limit without either: reason (REASON_LENGTH, 0).
+    Returns (done, reason) as stop_update does.  With begin = 0 and limit, Hc larger than the run it is stop_update."""
+    hist = torch.as_tensor(ring).to(torch.int64).cpu()
+    done = torch.as_tensor(done).to(torch.bool).cpu().clone()
+    R, Hc = hist.shape
+    col = step % Hc
+    reason = torch.tensor([[REASON_NONE, -1]] * R, dtype=torch.int64).view(R, 2)
+    for r in range(R):
+        if bool(done[r]):
+            continue
+        n = (col - int(begin[r])) % Hc + 1
+        t = int(hist[r, col])
+        hit = None
+        for i, e in enumerate(eos_ids):
+            if t == int(e):
+                hit = (REASON_EOS, i)
+                break
+        if hit is None:
+            for j, q in enumerate(stop_seqs):
+                L = len(q)
+                if 1 <= L <= n and [int(hist[r, (col - L + 1 + k) % Hc]) for k in range(L)] == [int(x) for x in q]:
+                    hit = (REASON_STOP, j)
+                    break
+        if hit is None and n >= int(limit[r]):
+            hit = (REASON_LENGTH, 0)
         if hit is not None:
             done[r] = True
             reason[r, 0], reason[r, 1] = hit
@@ -1558,6 +1600,164 @@ def _host_loop(model, embeddings, lengths, max_steps, eos_token, seed, every, st
     vals = tuple(torch.stack([h[j] for h in host_lp[:n_gen]], 1) for j in range(3)) if n_top is not None and n_gen else None
     keep = stop is not None and (want_finish or (n_top is not None and n_gen))
     return _Generated(out[:, :n], out[:, s:n], past, record if keep else None, vals)
+
+
+class StreamResult(NamedTuple):
+    """One finished request of generate_stream()."""
+    index: int                  # the request's ordinal in ``requests``
+    tokens: torch.Tensor        # int64 CPU: the generated tokens that count, the finishing token included
+    text: Optional[str]         # decoded as generate()'s per-row tail decodes (eos dropped, image tokens removed); None at decode=False
+    reason: str                 # "eos" | "stop" | "length"
+    reason_index: int           # which eos id / which stop sequence (-1 for "length")
+    slot: Optional[int]         # the row of the session the request ran in (None: an LM object without slots)
+
+
+# what generate() takes and a request stream refuses when it differs from generate()'s default
+_STREAM_REFUSED = (
+    ("the logits processors are", ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "suppress_tokens")),
+    ("token log-probabilities (return_logprobs / top_logprobs) are", ("return_logprobs", "top_logprobs")),
+    ("a constraint is", ("constraint",)),
+    ("guidance is", ("guidance_scale", "negative_embeddings", "negative_lengths", "guidance_min_p")),
+    ("beam search is", ("num_beams", "num_beam_groups", "diversity_penalty", "length_penalty", "early_stopping",
+                        "num_return_sequences", "return_scores")),
+    ("contrastive search is", ("penalty_alpha",)),
+    ("a KV cache (past_key_values / return_past_key_values) is", ("past_key_values", "return_past_key_values")),
+)
+
+
+def _max_positions(model):
+    cfg = getattr(getattr(model, "lm", None), "config", None)
+    n = getattr(cfg, "max_position_embeddings", None) or getattr(cfg, "n_positions", None)
+    return int(n) if isinstance(n, int) else None
+
+
+def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 100, max_prompt: int = None, eos_token=None,
+                    stop_sequences=None, temperature: float = 0.0, top_k: int = 0, top_p: float = 0.9,
+                    sampler: str = "reference", min_p: float = 0.0, seed: int = None, every: int = None, admit_rows: int = None,
+                    decode: bool = True, **unsupported):
+    """Generate over a stream of requests (DESIGN.md "Request streams"): yields one ``StreamResult`` per request, in completion
+    order.  Request i's tokens, finish reason and index are those of the solo call
+
+        generate(model, request_i, max_steps=max_new_tokens_i, eos_token=[...], stop_sequences=..., stop_per_row=True,
+                 return_finish=True, temperature=0.0)
+
+    -- that call is the host statement, and for an LM object that is not the HIP engine exactly those calls run one after
+    another.  The HIP engine runs a slot session (engine.SlotSession): ``slots`` rows (1 to 16, the range of the captured GEMV step)
+    generate in one captured token step, and the row of a finished request goes to the next request while the others keep
+    generating; nothing of the token step changes but its bookkeeping launch (ops.sample_finish_slots).
+
+    ``requests``: any iterable of embeddings tensors (1, S, d) / (S, d), as ``embed`` returns them, or pairs (embeddings,
+    max_new_tokens_i) with 1 <= max_new_tokens_i <= ``max_new_tokens`` (the default budget and the session's bound).  It is pulled
+    lazily, one item when a slot frees, so a data loader or preprocess_inputs + embed can run inside it on the same stream.
+    ``max_prompt``: the longest prompt the session takes (default: max_position_embeddings - max_new_tokens rounded down to 64).
+    It sets the cost of the session: EVERY admission prefill runs over (admit_rows, ceil64(max_prompt)) rows whatever the real
+    prompt lengths are, and the session allocates a live cache of ``slots`` x ceil64(max_prompt + max_new_tokens) positions plus a
+    staging cache of admit_rows x ceil64(max_prompt) -- at the default, 28 blocks and 8 slots about 15 GB and prefills of 1920
+    rows per row: pass the longest prompt you expect.  A longer prompt (or any other bad item) raises ValueError naming the
+    request when it is pulled: nothing more is pulled, the requests in front of it are generated to their end and yielded
+    first, then the error is raised -- no earlier request is lost, and the engine stays usable.
+    ``every``: the number of steps between two host looks (default MAGMA_EOS_CHECK_EVERY, as generate).  ``admit_rows`` (1 to
+    ``slots``, default ``slots``): the fixed row count of every admission prefill -- the staging shape (admit_rows,
+    ceil64(max_prompt)) is fixed for the session so that a request's bits do not depend on what was admitted with it.
+    ``eos_token`` (an id or 1 to 8 ids; default the model's) and ``stop_sequences`` are generate()'s per-row stopping arguments.
+    Greedy decoding (``temperature=0``, the default) and both samplers are supported.  A sampled request draws its first token
+    at its admission from the Philox counter (2^32 - 1 - admission pass, staging row) and every later token from (global step
+    of the session, slot) -- two domains that never meet, so no two draws of a session share a counter (engine.SlotSession) --,
+    NOT from the counters of a solo call: only greedy decoding and ``top_k=1`` are reproducible against a solo call.  Not combined yet (NotImplementedError): the logits processors, return_logprobs, constraint,
+    guidance, beam and contrastive search, past_key_values -- their kernels read the token history from column 0.
+    The arguments are checked when the call is made; the work starts with the first ``next``."""
+    import inspect
+    defaults = {k: p.default for k, p in inspect.signature(generate).parameters.items()}
+    known = {k for _, names in _STREAM_REFUSED for k in names}
+    for k in unsupported:
+        if k not in known:
+            raise TypeError(f"generate_stream() got an unexpected keyword argument {k!r}")
+    for what, names in _STREAM_REFUSED:
+        for k in names:
+            if k in unsupported and not (unsupported[k] is defaults[k] or (not torch.is_tensor(unsupported[k]) and unsupported[k] == defaults[k])):
+                raise NotImplementedError(f"{what} not combined with generate_stream yet ({k}=)")
+    on_device = getattr(model.lm, "device_token_selection", False)
+    for name, v, lo, hi in (("slots", slots, 1, 16), ("max_new_tokens", max_new_tokens, 1, None)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < lo or (hi is not None and v > hi):
+            raise ValueError(f"{name} must be an integer in [{lo}, {hi if hi is not None else '...'}], got {v!r}")
+    if admit_rows is None:
+        admit_rows = slots
+    if isinstance(admit_rows, bool) or not isinstance(admit_rows, int) or not 1 <= admit_rows <= slots:
+        raise ValueError(f"admit_rows must be an integer in [1, slots = {slots}], got {admit_rows!r}")
+    if every is None:
+        every = int(os.environ.get("MAGMA_EOS_CHECK_EVERY", "8"))
+    if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+        raise ValueError(f"every must be an integer >= 1, got {every!r}")
+    n_pos = _max_positions(model)
+    if max_prompt is None:
+        if n_pos is None:
+            raise ValueError("max_prompt is needed: this LM object does not say its max_position_embeddings")
+        max_prompt = (n_pos - max_new_tokens) // 64 * 64
+        if max_prompt < 1:
+            raise ValueError(f"max_new_tokens = {max_new_tokens} leaves no room for a prompt within max_position_embeddings = {n_pos}; "
+                             "pass max_prompt")
+    if isinstance(max_prompt, bool) or not isinstance(max_prompt, int) or max_prompt < 1:
+        raise ValueError(f"max_prompt must be an integer >= 1, got {max_prompt!r}")
+    if n_pos is not None and max_prompt + max_new_tokens > n_pos:
+        raise ValueError(f"max_prompt = {max_prompt} + max_new_tokens = {max_new_tokens} exceeds max_position_embeddings = {n_pos}")
+    if eos_token is None or (isinstance(eos_token, int) and not isinstance(eos_token, bool) and not eos_token):
+        eos_token = model.eos_token
+    stop = check_stop_args(eos_token, stop_sequences, True, _logit_count(model),
+                           getattr(getattr(model, "tokenizer", None), "encode", None))
+    warp = check_sampler_args(sampler, min_p, top_p)
+    greedy = temperature == 0.0
+    if min_p > 0 and greedy:
+        raise ValueError("min_p applies to sampled selection: greedy decoding (temperature=0) would drop it")
+    mode = None if greedy else (float(temperature), int(top_k), float(top_p))
+    if warp is not None and not greedy:
+        mode = ("warp",) + mode + (warp["min_p"],)
+    if seed is None and not greedy:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+
+    def pulled():
+        """(index, (S, d) embeddings, limit) of every request, checked as it is pulled."""
+        for index, item in enumerate(requests):
+            emb, limit = item if isinstance(item, (tuple, list)) else (item, max_new_tokens)
+            if not torch.is_tensor(emb) or emb.ndim not in (2, 3) or (emb.ndim == 3 and emb.shape[0] != 1):
+                raise ValueError(f"request {index}: an item is an embeddings tensor (1, S, d) or (S, d), or a pair of one and its "
+                                 "max_new_tokens")
+            emb = emb[0] if emb.ndim == 3 else emb
+            if isinstance(limit, bool) or not isinstance(limit, int) or not 1 <= limit <= max_new_tokens:
+                raise ValueError(f"request {index}: max_new_tokens must be an integer in [1, {max_new_tokens}] (the session's "
+                                 f"max_new_tokens), got {limit!r}")
+            if not 1 <= emb.shape[0] <= max_prompt:
+                raise ValueError(f"request {index}: a prompt of {emb.shape[0]} rows is outside [1, max_prompt = {max_prompt}]")
+            yield index, emb, limit
+
+    def text_of(ids, reason):
+        if not decode:
+            return None
+        ids = ids.tolist()[:-1] if reason == "eos" else ids.tolist()
+        return model.tokenizer.decode([t for t in ids if t != model.image_token])
+
+    def solo_calls():           # the host statement, request after request
+        kw = dict(eos_token=list(stop["eos_ids"]), stop_sequences=[list(q) for q in stop["stop_seqs"]] or None, stop_per_row=True,
+                  return_finish=True, decode=False, temperature=temperature, top_k=top_k, top_p=top_p, sampler=sampler, min_p=min_p,
+                  seed=seed, eos_check_every=every)
+        for index, emb, limit in pulled():
+            out, fin = generate(model, emb[None], max_steps=limit, **kw)
+            ids = out[0, emb.shape[0]: emb.shape[0] + int(fin.kept[0])].to("cpu", torch.int64)
+            yield StreamResult(index, ids, text_of(ids, fin.reason[0]), fin.reason[0], fin.index[0], None)
+
+    def session():
+        from .engine import LMEngine, SlotSession
+        eng = model.lm.engine
+        if getattr(model, "device", None) is not None and torch.device(model.device).type == "cuda":
+            torch.cuda.set_device(model.device)
+        plan = LMEngine.selection_plan(sampling=mode, stop=stop, vocab=eng.V, slots=True)
+        ses = SlotSession(eng, plan, slots=slots, max_new=max_new_tokens, max_prompt=max_prompt, every=every,
+                          admit_rows=admit_rows, seed=seed)
+        dev = eng.device
+        for index, ids, code, slot in ses.run((i, e.to(dev), n) for i, e, n in pulled()):
+            reason = REASON_NAMES[code >> 8]
+            yield StreamResult(index, ids, text_of(ids, reason), reason, -1 if reason == "length" else code & 255, slot)
+
+    return session() if on_device else solo_calls()
 
 
 def choose(model, embeddings, choices, lengths=None, **generate_kwargs):

@@ -1,0 +1,144 @@
+"""Request streams at the bench shape, in ONE process: MAGMA_v1, 28 blocks, 8 slots, 64 requests with a 57-row prompt.
+
+  python tools/stream_bench.py [--layers 28] [--requests 64] [--steps 250] [--reps 5] [--out FILE (default profiles/stream_bench.jsonl)]
+
+(a) Tokens that count per second over the same 64 requests, whose max_new_tokens come from a fixed list spread over 5 to 40 (eos
+    is an id outside the tokenizer's range, so every request runs to its own limit unless the model happens to emit it):
+    ``generate_stream`` with 8 slots; static ``generate(stop_per_row=True)`` batches of 8 in the requests' order, each with its
+    own largest limit as ``max_steps``; the static leg again, to show the spread.  One warm-up pass of every leg first.  The
+    session is given ``max_prompt`` = the prompt length, 57: every admission prefill then runs over (8, 64) rows.
+(b) The captured token step with the slot bookkeeping (mg_sample_finish_slots) against the per-row one (mg_sample_finish_rows),
+    measured as tools/stop_rows_bench.py measures: device events around ``--steps`` replays, windows interleaved, the same
+    context length in every window, ``--reps`` windows each; the per-row step twice, to show the spread."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from magma_amd import Magma  # noqa: E402
+from magma_amd.engine import LMEngine, SlotSession  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--config", default="MAGMA_v1")
+ap.add_argument("--layers", type=int, default=0, help="0 = the config's depth (28)")
+ap.add_argument("--slots", type=int, default=8)
+ap.add_argument("--requests", type=int, default=64)
+ap.add_argument("--every", type=int, default=0, help="0 = MAGMA_EOS_CHECK_EVERY (8)")
+ap.add_argument("--steps", type=int, default=250)
+ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "stream_bench.jsonl"))
+args = ap.parse_args()
+
+if not torch.cuda.is_available():
+    sys.exit("stream_bench: no GPU -- this tool measures, it does not fall back")
+dev = torch.device("cuda:0")
+torch.manual_seed(1234)
+kw = {}
+if args.layers:
+    from magma_amd.language_model import GPTJConfig
+    kw["lm_config"] = GPTJConfig(num_layers=args.layers, vocab_size=50258)
+model = Magma(args.config, device=dev, **kw)
+model.eval()
+eng = model.lm.engine
+B = args.slots
+g = torch.Generator(device=dev).manual_seed(1)
+images = torch.randn(8, 3, 224, 224, device=dev, generator=g).to(torch.bfloat16)
+prompt = torch.randint(0, 50256, (8, 8), device=dev, generator=g)
+LIMITS = [5 + (23 * i) % 36 for i in range(args.requests)]         # 5 .. 40, every residue of 36 in turn
+EOS = 50257
+lines = []
+
+
+def emit(d):
+    lines.append(json.dumps(d))
+    print(lines[-1], flush=True)
+
+
+with torch.no_grad():
+    emb = model.embed([images, prompt])
+    S0 = int(emb.shape[1])
+    requests = [(emb[i % 8], LIMITS[i]) for i in range(args.requests)]
+
+    def leg_stream():
+        n = 0
+        for r in model.generate_stream(requests, slots=B, max_new_tokens=max(LIMITS), max_prompt=S0, eos_token=[EOS], decode=False,
+                                       every=args.every or None):
+            n += int(r.tokens.numel())
+        return n
+
+    def leg_static():
+        n = 0
+        for i in range(0, args.requests, B):
+            group = requests[i:i + B]
+            lim = torch.tensor([x[1] for x in group])
+            out, fin = model.generate(torch.stack([x[0] for x in group]), max_steps=int(lim.max()), temperature=0.0, decode=False,
+                                      eos_token=[EOS], stop_per_row=True, return_finish=True, eos_check_every=args.every or None)
+            n += int(torch.minimum(fin.kept, lim).sum())
+        return n
+
+    # ---- (a) tokens that count per second ----
+    legs = [("generate_stream", leg_stream), ("static", leg_static), ("static_again", leg_static)]
+    for _, leg in legs[:2]:         # one warm-up pass of every distinct leg: code objects, the pool's caches, captured steps
+        leg()
+    for name, leg in legs:
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        n = leg()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t
+        emit({"part": "throughput", "leg": name, "requests": args.requests, "slots": B, "prompt_rows": S0, "tokens_that_count": n,
+              "wall_s": dt, "tokens_per_s": n / dt, "limits_sum": sum(LIMITS)})
+    eng._cache_pool.clear()
+
+    # ---- (b) the captured token step ----
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    stop = dict(eos_ids=(EOS,), stop_seqs=())
+    caches = {}
+    for name in ("rows", "rows_again"):
+        o = model.lm(inputs_embeds=emb[:B] if B <= 8 else emb.repeat(2, 1, 1)[:B], use_cache=True, cache_hint=args.steps + 8,
+                     eos_token=EOS, stop=stop, lengths=[S0] * B)
+        caches[name] = o.past_key_values
+        for _ in range(3):
+            eng.decode(None, caches[name], stop=stop)
+    plan = LMEngine.selection_plan(stop=stop, vocab=eng.V, slots=True)
+    ses = SlotSession(eng, plan, slots=B, max_new=args.steps + 8, max_prompt=S0, every=1, admit_rows=B)
+    ses._admit([(i, emb[i % 8], args.steps + 8) for i in range(B)], list(range(B)))
+    sc = ses.cache
+    keep = [t.clone() for t in (sc.d_pos, sc.finish, sc.slot_table, sc.sample_state, ses.st.token)]
+    occ = list(ses.occ)
+    for _ in range(3):
+        ses._step()
+    ms = {"rows": [], "slots": [], "rows_again": []}
+    for rep in range(args.reps):
+        for name in ms:
+            if name == "slots":
+                for t, k in zip((sc.d_pos, sc.finish, sc.slot_table, sc.sample_state, ses.st.token), keep):
+                    t.copy_(k)
+                ses.steps, ses.occ = 0, list(occ)
+                run = ses._step
+            else:
+                cache = caches[name]
+                cache.pos = S0
+                cache.d_pos.fill_(S0)
+                cache.sample_state.copy_(torch.tensor([0, -1], dtype=torch.int32))
+                cache.finish.copy_(torch.tensor([[-1, 0]] * B, dtype=torch.int32))
+                run = lambda: eng.decode(None, cache, stop=stop)  # noqa: E731
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(args.steps):
+                run()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[name].append(e0.elapsed_time(e1) / args.steps)
+    for name in ms:
+        emit({"part": "step", "variant": name, "step_ms_min": min(ms[name]), "step_ms_median": statistics.median(ms[name]),
+              "step_ms_all": ms[name], "steps_per_window": args.steps,
+              "rows_finished": int(((sc if name == "slots" else caches[name]).finish[:, 0] >= 0).sum())})
+if args.out:
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
