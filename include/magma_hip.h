@@ -106,8 +106,9 @@ const char* mg_version(void);
  *      mg_kv_broadcast_bf16 (nothing moved).
  *  23  losslessly packed decode weights: mg_skinny_desc grew by `pk_lo`, `pk_nib`, `pk_base`, `pk_sign`, `pk_flags` at its end
  *      (NULL = as before; nothing else moved).
- *  24  request streams: added mg_sample_finish_slots and mg_slots_admit_bf16, MG_STOP_LEN and MG_SLOTS_MAX (nothing moved). */
-#define MG_ABI_VERSION 24
+ *  24  request streams: added mg_sample_finish_slots and mg_slots_admit_bf16, MG_STOP_LEN and MG_SLOTS_MAX (nothing moved).
+ *  25  session prefix of a request stream: added mg_slots_admit_at_bf16 (nothing moved). */
+#define MG_ABI_VERSION 25
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -514,7 +515,13 @@ int mg_sample_finish_rows(int64_t* token, int32_t B, int32_t* state, int32_t* d_
  *   64-bit offsets); d_pos[slot] = len[j]; token[slot] = first_token[j]; slot[slot] = {c, limit[j]} with c = (state[0] - 1) %
  *   history_cols; history[slot][c] = first_token[j]; the row test runs on the first token (eos, stop sequences of length 1, then
  *   limit[j] <= 1) and leaves finish[slot] = {state[0] - 1, code} or {-1, 0}.  state[1] = -1.  A session starts with state = {1, -1}.
- *   Refused: a duplicate dst_slot, a slot or staging row out of range, len outside [1, min(S_stage, Smax)], n > B or > MG_SLOTS_MAX. */
+ *   Refused: a duplicate dst_slot, a slot or staging row out of range, len outside [1, min(S_stage, Smax)], n > B or > MG_SLOTS_MAX.
+ * mg_slots_admit_at_bf16 (ABI 25; DESIGN.md "Request streams", session prefix): mg_slots_admit_bf16 behind pos0 cached positions
+ *   that every staging row and every live slot already hold.  For every j, K and V positions [pos0, pos0 + len[j]) of staging row
+ *   src_row[j] go to the SAME positions of live row dst_slot[j], and d_pos[slot] = pos0 + len[j]; positions below pos0 are neither
+ *   read nor written.  Token, window, history column, row test, finish record and state[1] are mg_slots_admit_bf16's; one kernel
+ *   serves both (mg_slots_admit_bf16 is pos0 = 0).  Refused in addition, before anything is launched: pos0 < 0, len[j] < 1,
+ *   pos0 + len[j] > min(S_stage, Smax). */
 #define MG_STOP_LEN 0x300
 #define MG_SLOTS_MAX 16
 int mg_sample_finish_slots(int64_t* token, int32_t B, int32_t* state, int32_t* d_pos, int32_t delta, int64_t* history,
@@ -526,6 +533,12 @@ int mg_slots_admit_bf16(const mg_bf16* kstage, const mg_bf16* vstage, int32_t n_
                         const int32_t* dst_slot, const int32_t* len, const int64_t* first_token, const int32_t* limit,
                         int32_t* state, int32_t* d_pos, int64_t* token, int32_t* finish, int32_t* slot, int64_t* history,
                         int64_t ld_history, int32_t history_cols, const int32_t* table, int32_t n_eos, int32_t n_seq, void* stream);
+int mg_slots_admit_at_bf16(const mg_bf16* kstage, const mg_bf16* vstage, int32_t n_stage, int32_t S_stage, mg_bf16* kcache,
+                           mg_bf16* vcache, int32_t L, int32_t B, int32_t H, int32_t Smax, int32_t n, const int32_t* src_row,
+                           const int32_t* dst_slot, const int32_t* len, const int64_t* first_token, const int32_t* limit,
+                           int32_t* state, int32_t* d_pos, int64_t* token, int32_t* finish, int32_t* slot, int64_t* history,
+                           int64_t ld_history, int32_t history_cols, const int32_t* table, int32_t n_eos, int32_t n_seq,
+                           int32_t pos0, void* stream);
 
 /* Beam search (transformers' GenerationMixin._beam_search, do_sample=False, one eos id; DESIGN.md "Beam search"): three
  * enqueue-only, graph-capturable launches per token step over R = B * k rows (k = num_beams <= 16, rows sample-major).

@@ -505,12 +505,13 @@ __global__ void sample_finish_slots_kernel(int64_t* __restrict__ tok, int B, int
   state[0] = step + 1;
 }
 
-// Admission of a slot session: n staged requests installed in one launch.  Block (h, j, l) copies K and V positions [0, len_j) of
-// layer l, head h from staging row src_row[j] to live row dst_slot[j] -- len_j * 512 contiguous bytes each, as 16-byte vectors, all
-// offsets 64-bit --; thread 0 of block (0, j, 0) installs request j's bookkeeping and runs the row test on its first token.
+// Admission of a slot session: n staged requests installed in one launch.  Block (h, j, l) copies K and V positions
+// [pos0, pos0 + len_j) of layer l, head h from staging row src_row[j] to the same positions of live row dst_slot[j] -- len_j * 512
+// contiguous bytes each, as 16-byte vectors, all offsets 64-bit --; thread 0 of block (0, j, 0) installs request j's bookkeeping
+// and runs the row test on its first token.  pos0 = 0: mg_slots_admit_bf16; pos0 = the session prefix's rows: mg_slots_admit_at_bf16.
 struct SlotsAdmitArgs {
   const uint4* kstage; const uint4* vstage; uint4* kcache; uint4* vcache;
-  int n_stage, H, S_stage, B, Smax;
+  int n_stage, H, S_stage, B, Smax, pos0;
   int32_t src_row[MG_SLOTS_MAX], dst_slot[MG_SLOTS_MAX], len[MG_SLOTS_MAX], limit[MG_SLOTS_MAX];
   const int64_t* first_token;
   int32_t* state; int32_t* d_pos; int64_t* token; int32_t* finish; int32_t* slot;
@@ -521,8 +522,8 @@ struct SlotsAdmitArgs {
 __global__ void slots_admit_kernel(SlotsAdmitArgs a) {
   const int h = blockIdx.x, j = blockIdx.y, l = blockIdx.z;
   const int64_t n_vec = (int64_t)a.len[j] * 32;                 // 256 bf16 = 32 vectors of 16 bytes per position
-  const int64_t src = (((int64_t)l * a.n_stage + a.src_row[j]) * a.H + h) * a.S_stage * 32;
-  const int64_t dst = (((int64_t)l * a.B + a.dst_slot[j]) * a.H + h) * a.Smax * 32;
+  const int64_t src = ((((int64_t)l * a.n_stage + a.src_row[j]) * a.H + h) * a.S_stage + a.pos0) * 32;
+  const int64_t dst = ((((int64_t)l * a.B + a.dst_slot[j]) * a.H + h) * a.Smax + a.pos0) * 32;
   for (int64_t i = threadIdx.x; i < n_vec; i += blockDim.x) {
     a.kcache[dst + i] = a.kstage[src + i];
     a.vcache[dst + i] = a.vstage[src + i];
@@ -533,7 +534,7 @@ __global__ void slots_admit_kernel(SlotsAdmitArgs a) {
   const int b = a.dst_slot[j];
   const int64_t t = a.first_token[j];
   int64_t* hrow = a.history + (int64_t)b * a.ld_hist;
-  a.d_pos[b] = a.len[j];
+  a.d_pos[b] = a.pos0 + a.len[j];
   a.token[b] = t;
   a.slot[2 * b] = c;
   a.slot[2 * b + 1] = a.limit[j];
@@ -626,13 +627,13 @@ extern "C" int mg_sample_finish_slots(int64_t* token, int32_t B, int32_t* state,
   return MG_OK;
 }
 
-extern "C" int mg_slots_admit_bf16(const mg_bf16* kstage, const mg_bf16* vstage, int32_t n_stage, int32_t S_stage, mg_bf16* kcache,
-                                   mg_bf16* vcache, int32_t L, int32_t B, int32_t H, int32_t Smax, int32_t n, const int32_t* src_row,
-                                   const int32_t* dst_slot, const int32_t* len, const int64_t* first_token, const int32_t* limit,
-                                   int32_t* state, int32_t* d_pos, int64_t* token, int32_t* finish, int32_t* slot, int64_t* history,
-                                   int64_t ld_history, int32_t history_cols, const int32_t* table, int32_t n_eos, int32_t n_seq,
-                                   void* stream) {
-  const char* who = "mg_slots_admit_bf16";
+// Both admission entry points: the checks and the one launch.
+static int slots_admit_launch(const char* who, const mg_bf16* kstage, const mg_bf16* vstage, int32_t n_stage, int32_t S_stage,
+                              mg_bf16* kcache, mg_bf16* vcache, int32_t L, int32_t B, int32_t H, int32_t Smax, int32_t n,
+                              const int32_t* src_row, const int32_t* dst_slot, const int32_t* len, const int64_t* first_token,
+                              const int32_t* limit, int32_t* state, int32_t* d_pos, int64_t* token, int32_t* finish, int32_t* slot,
+                              int64_t* history, int64_t ld_history, int32_t history_cols, const int32_t* table, int32_t n_eos,
+                              int32_t n_seq, int32_t pos0, void* stream) {
   if (!kstage || !vstage || !kcache || !vcache || !src_row || !dst_slot || !len || !first_token || !limit || !state || !d_pos || !token ||
       !finish || !slot || !history || !table)
     MG_FAIL(MG_ERR_SHAPE, "%s: null pointer", who);
@@ -648,7 +649,9 @@ extern "C" int mg_slots_admit_bf16(const mg_bf16* kstage, const mg_bf16* vstage,
     MG_FAIL(MG_ERR_ALIGN, "%s: int32 buffers must be 4-byte aligned", who);
   if (((uintptr_t)token | (uintptr_t)history | (uintptr_t)first_token) & 7) MG_FAIL(MG_ERR_ALIGN, "%s: token buffers must be 8-byte aligned", who);
   SlotsAdmitArgs a{};
-  const int len_max = S_stage < Smax ? S_stage : Smax;
+  const int pos_max = S_stage < Smax ? S_stage : Smax;
+  if (pos0 < 0 || pos0 >= pos_max) MG_FAIL(MG_ERR_SHAPE, "%s: pos0 = %d outside [0, %d)", who, pos0, pos_max);
+  const int len_max = pos_max - pos0;
   for (int j = 0; j < n; ++j) {
     if (src_row[j] < 0 || src_row[j] >= n_stage) MG_FAIL(MG_ERR_SHAPE, "%s: src_row[%d] = %d outside [0, %d)", who, j, src_row[j], n_stage);
     if (dst_slot[j] < 0 || dst_slot[j] >= B) MG_FAIL(MG_ERR_SHAPE, "%s: dst_slot[%d] = %d outside [0, %d)", who, j, dst_slot[j], B);
@@ -658,12 +661,34 @@ extern "C" int mg_slots_admit_bf16(const mg_bf16* kstage, const mg_bf16* vstage,
     a.src_row[j] = src_row[j]; a.dst_slot[j] = dst_slot[j]; a.len[j] = len[j]; a.limit[j] = limit[j];
   }
   a.kstage = (const uint4*)kstage; a.vstage = (const uint4*)vstage; a.kcache = (uint4*)kcache; a.vcache = (uint4*)vcache;
-  a.n_stage = n_stage; a.H = H; a.S_stage = S_stage; a.B = B; a.Smax = Smax;
+  a.n_stage = n_stage; a.H = H; a.S_stage = S_stage; a.B = B; a.Smax = Smax; a.pos0 = pos0;
   a.first_token = first_token; a.state = state; a.d_pos = d_pos; a.token = token; a.finish = finish; a.slot = slot;
   a.history = history; a.ld_hist = ld_history; a.hist_cols = history_cols; a.table = table; a.n_eos = n_eos; a.n_seq = n_seq;
   hipLaunchKernelGGL(slots_admit_kernel, dim3(H, n, L), dim3(256), 0, (hipStream_t)stream, a);
   MG_CHECK_LAUNCH();
   return MG_OK;
+}
+
+extern "C" int mg_slots_admit_bf16(const mg_bf16* kstage, const mg_bf16* vstage, int32_t n_stage, int32_t S_stage, mg_bf16* kcache,
+                                   mg_bf16* vcache, int32_t L, int32_t B, int32_t H, int32_t Smax, int32_t n, const int32_t* src_row,
+                                   const int32_t* dst_slot, const int32_t* len, const int64_t* first_token, const int32_t* limit,
+                                   int32_t* state, int32_t* d_pos, int64_t* token, int32_t* finish, int32_t* slot, int64_t* history,
+                                   int64_t ld_history, int32_t history_cols, const int32_t* table, int32_t n_eos, int32_t n_seq,
+                                   void* stream) {
+  return slots_admit_launch("mg_slots_admit_bf16", kstage, vstage, n_stage, S_stage, kcache, vcache, L, B, H, Smax, n, src_row, dst_slot,
+                            len, first_token, limit, state, d_pos, token, finish, slot, history, ld_history, history_cols, table, n_eos,
+                            n_seq, 0, stream);
+}
+
+extern "C" int mg_slots_admit_at_bf16(const mg_bf16* kstage, const mg_bf16* vstage, int32_t n_stage, int32_t S_stage, mg_bf16* kcache,
+                                      mg_bf16* vcache, int32_t L, int32_t B, int32_t H, int32_t Smax, int32_t n, const int32_t* src_row,
+                                      const int32_t* dst_slot, const int32_t* len, const int64_t* first_token, const int32_t* limit,
+                                      int32_t* state, int32_t* d_pos, int64_t* token, int32_t* finish, int32_t* slot, int64_t* history,
+                                      int64_t ld_history, int32_t history_cols, const int32_t* table, int32_t n_eos, int32_t n_seq,
+                                      int32_t pos0, void* stream) {
+  return slots_admit_launch("mg_slots_admit_at_bf16", kstage, vstage, n_stage, S_stage, kcache, vcache, L, B, H, Smax, n, src_row,
+                            dst_slot, len, first_token, limit, state, d_pos, token, finish, slot, history, ld_history, history_cols,
+                            table, n_eos, n_seq, pos0, stream);
 }
 
 // ================================================================================================================================

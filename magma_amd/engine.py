@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import itertools
 import os
+import weakref
 from typing import Any, List, NamedTuple, Optional
 
 import torch
@@ -73,6 +74,7 @@ class KVCache:
         # position _rows_at (None: every row at self.pos), and per row the generated token not yet fed back (-1: none)
         self._rows, self._rows_at = None, 0
         self.pending = None
+        self.owner = None         # weak reference to the LMEngine whose prefill filled the cache (None: not recorded)
         # token log-probabilities (DESIGN.md "Token log-probabilities"), beside the history: fp32 [B, Smax] log-probability of the
         # token selected at step s, and the n_top most probable tokens of that step (int32 / fp32 [B, Smax, n_top]); allocated on
         # first request (SelectionPlan.arm), addresses and n_top are launch arguments of the captured step
@@ -165,7 +167,7 @@ class KVCache:
         out = KVCache(len(self), self.B * n, self.k.shape[2], self.Smax, self.k.device, ragged=True)
         out.k[:, :, :, :used].copy_(self.k[:, :, :, :used].repeat_interleave(n, dim=1))
         out.v[:, :, :, :used].copy_(self.v[:, :, :, :used].repeat_interleave(n, dim=1))
-        out.eos = self.eos
+        out.eos, out.owner = self.eos, self.owner
         out.set_rows(rows.repeat_interleave(n), None if self.pending is None else self.pending.repeat_interleave(n))
         return out
 
@@ -1211,6 +1213,7 @@ class LMEngine:
         # right padding: the prefill is unchanged -- under the causal mask a valid row attends to valid keys only, and the
         # K / V the padded rows leave in slots >= len_b are overwritten by decode steps before any row reads them
         x, hs = self._blocks_prefill(embeds, cache, want_hidden)
+        cache.owner = weakref.ref(self)
         cache.prefill_x = x.view(B, S, self.d) if keep_x else None
         cache._rows, cache.pending = (lens.clone() if ragged else None), None
         if ragged:
@@ -1883,7 +1886,12 @@ class SlotSession:
     Sampled selection: a token step draws from the Philox counter (state[0] = 1 + steps enqueued, slot), as every generate() loop
     does; the first token of a request is drawn at its admission from a counter domain of its own, (admit_counter(pass), staging
     row) with admit_counter(p) = -1 - p -- as the kernel's unsigned counter word 2^32 - 1 - p, which no token step reaches -- so
-    no two draws of a session share a counter (draw_counters is the host statement of which ones a schedule uses)."""
+    no two draws of a session share a counter (draw_counters is the host statement of which ones a schedule uses).
+    Session prefix (``prefix``: (P, d) embeddings or a one-row KVCache that is only read): its K / V positions [0, P) are put into
+    every live slot and every staging row ONCE, at set-up (plain copies, as KVCache.expand); an admission pass then runs the
+    cached-append prefill of LMEngine.extend over the same fixed (admit_rows, S_stage) rows behind them -- every staging row's
+    write position is reset to P on the device first -- and ops.slots_admit(pos0=P) moves positions [P, P + len) only, so a slot
+    keeps its prefix over any number of occupants.  Nothing is ever re-allocated: the captured step stays valid."""
 
     @staticmethod
     def admit_counter(n_pass: int) -> int:
@@ -1906,21 +1914,22 @@ class SlotSession:
         return out
 
     def __init__(self, engine: "LMEngine", plan: SelectionPlan, *, slots: int, max_new: int, max_prompt: int, every: int,
-                 admit_rows: int, seed: Optional[int] = None):
+                 admit_rows: int, seed: Optional[int] = None, prefix=None):
         if not plan.slots or plan.stop is None:
             raise ValueError("a slot session runs under a plan built with slots=True and per-row stopping")
         if not 1 <= slots <= ops.SLOTS_MAX or not 1 <= admit_rows <= slots or max_new < 1 or max_prompt < 1 or every < 1:
             raise ValueError(f"need 1 <= admit_rows <= slots <= {ops.SLOTS_MAX} and max_new, max_prompt, every >= 1")
         n_pos = engine.cfg.max_position_embeddings
         self.S_stage = ops.ceil_to(max_prompt, 64)
-        if max_prompt + max_new > n_pos or self.S_stage > n_pos:
-            raise ValueError(f"max_prompt = {max_prompt} (staged as {self.S_stage} rows) + max_new_tokens = {max_new} exceeds "
-                             f"max_position_embeddings = {n_pos}")
+        self.P = P = self.prefix_rows(engine, prefix)
+        if P + max_prompt + max_new > n_pos or P + self.S_stage > n_pos:
+            raise ValueError((f"a prefix of {P} rows + " if P else "") + f"max_prompt = {max_prompt} (staged as {self.S_stage} rows) + "
+                             f"max_new_tokens = {max_new} exceeds max_position_embeddings = {n_pos}")
         dev = engine.device
         self.engine, self.plan, self.B, self.every, self.n_admit = engine, plan, slots, every, admit_rows
         self.max_new, self.max_prompt = max_new, max_prompt
-        self.cache = cache = KVCache(engine.L, slots, engine.H, ops.ceil_to(max_prompt + max_new, 64), dev, ragged=True)
-        self.stage = KVCache(engine.L, admit_rows, engine.H, self.S_stage, dev, ragged=True)
+        self.cache = cache = KVCache(engine.L, slots, engine.H, ops.ceil_to(P + max_prompt + max_new, 64), dev, ragged=True)
+        self.stage = KVCache(engine.L, admit_rows, engine.H, P + self.S_stage, dev, ragged=True)
         self.stage_in = torch.zeros(admit_rows, self.S_stage, engine.d, dtype=BF16, device=dev)
         self.first = torch.zeros(admit_rows, dtype=torch.int64, device=dev)
         self.admit_state = torch.tensor([-1, -1], dtype=torch.int32, device=dev)      # {admit_counter(pass), unused}: the admissions' draws
@@ -1941,10 +1950,52 @@ class SlotSession:
         cache.d_pos.zero_()
         self.steps = 0                  # token steps enqueued: the device's state[0] is 1 + steps
         self.occ = [None] * slots       # per slot: (request index, begin column, prompt length, limit, steps at admission)
+        if P:
+            self._install_prefix(prefix)
+
+    @staticmethod
+    def prefix_rows(engine: "LMEngine", prefix) -> int:
+        """The number of rows P of a session prefix (0: none), after checking that the session can take it: (P, d) embeddings of
+        the engine's width, or this engine's one-row KVCache with nothing pending that no beam or contrastive search ran on."""
+        if prefix is None:
+            return 0
+        if isinstance(prefix, KVCache):
+            if prefix.B != 1:
+                raise ValueError(f"the prefix cache holds {prefix.B} rows: a session has ONE prefix (cache it alone)")
+            if prefix.pending is not None and bool((prefix.pending >= 0).any()):
+                raise ValueError("the prefix cache holds a token that has not been fed back: a prefix ends at a cached position")
+            if (prefix.beam is not None and prefix.beam.k > 1) or prefix.contrast is not None:
+                raise ValueError("a beam-search or contrastive-search cache cannot be a session prefix")
+            owner = prefix.owner() if prefix.owner is not None else None
+            if (owner is not None and owner is not engine) or (len(prefix), prefix.k.shape[2]) != (engine.L, engine.H) \
+                    or prefix.k.device != engine.wte.device:
+                raise ValueError("the prefix cache belongs to another engine")
+            P = int(prefix.rows_pos()[0])
+        elif torch.is_tensor(prefix):
+            if prefix.ndim != 2 or prefix.shape[1] != engine.d:
+                raise ValueError(f"the prefix must be (P, {engine.d}) embeddings, got {tuple(prefix.shape)}")
+            P = prefix.shape[0]
+        else:
+            raise ValueError(f"the prefix is embeddings or a KVCache, got {type(prefix).__name__}")
+        if P < 1:
+            raise ValueError("the prefix is empty")
+        return P
+
+    @torch.no_grad()
+    def _install_prefix(self, prefix):
+        """Set-up, once: the prefix's K / V positions [0, P) of every layer and head into every live slot and every staging
+        row.  A given cache is only read; embeddings are prefilled once, alone, as Magma.cache_prompt does."""
+        P = self.P
+        if not isinstance(prefix, KVCache):
+            lens = torch.tensor([P], dtype=torch.int64)
+            _, prefix, _ = self.engine.prefill(prefix[None].to(self.engine.device), 0, lengths=lens)
+        for own in (self.cache, self.stage):
+            own.k[:, :, :, :P].copy_(prefix.k[:, :, :, :P])
+            own.v[:, :, :, :P].copy_(prefix.v[:, :, :, :P])
 
     def _bound(self, o) -> int:
         """The largest position the occupant's row can be at now."""
-        return o[2] + min(self.steps - o[4], o[3] - 1)
+        return self.P + o[2] + min(self.steps - o[4], o[3] - 1)
 
     @torch.no_grad()
     def _admit(self, batch, slots):
@@ -1955,7 +2006,11 @@ class SlotSession:
         for j, (_, emb, _) in enumerate(batch):
             lens[j] = emb.shape[0]
             self.stage_in[j, : lens[j]].copy_(emb)
-        x, _ = eng._blocks_prefill(self.stage_in, self.stage)
+        if self.P:      # behind the prefix: LMEngine.extend's cached-append prefill, every staging row's write position back at P
+            self.stage.d_pos.fill_(self.P)
+            x, _ = eng._blocks_prefill(self.stage_in, self.stage, chunk=True)
+        else:
+            x, _ = eng._blocks_prefill(self.stage_in, self.stage)
         rows = (torch.arange(self.n_admit, dtype=torch.int64) * self.S_stage + torch.tensor(lens) - 1).to(eng.device, non_blocking=True)
         logits = eng._head(ops.layernorm(x.index_select(0, rows), eng.lnf_g, eng.lnf_b, eng.eps))
         mode = self.plan.mode
@@ -1971,7 +2026,7 @@ class SlotSession:
         stop = self.plan.stop
         ops.slots_admit(self.stage.k, self.stage.v, cache.k, cache.v, list(range(n)), slots, lens[:n], self.first,
                         [it[2] for it in batch], cache.sample_state, cache.d_pos, self.st.token, cache.finish, cache.slot_table,
-                        cache.ring, cache.stop_table, len(stop[0]), len(stop[1]))
+                        cache.ring, cache.stop_table, len(stop[0]), len(stop[1]), pos0=self.P)
         for j, (index, _, limit) in enumerate(batch):
             self.occ[slots[j]] = (index, self.steps % self.Hc, lens[j], limit, self.steps)
 

@@ -19,7 +19,7 @@ MG_A_DENSE, MG_A_CONV3X3 = 0, 1
 MG_AUX_NONE, MG_AUX_RELU_GATE, MG_AUX_GELU_GRAD, MG_AUX_MUL, MG_AUX_QUICK_GELU_GRAD = 0, 1, 2, 3, 4
 
 
-ABI_VERSION = 24    # include/magma_hip.h MG_ABI_VERSION
+ABI_VERSION = 25    # include/magma_hip.h MG_ABI_VERSION
 
 
 class MagmaHipError(RuntimeError):
@@ -131,6 +131,8 @@ SYMBOLS = {
                                          _vp, _vp]),
     "mg_slots_admit_bf16": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp]),
+    "mg_slots_admit_at_bf16": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp]),
     "mg_beam_topk_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     "mg_beam_topk_scores_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     "mg_token_logprobs_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),

@@ -901,11 +901,14 @@ def sample_finish_slots(token: torch.Tensor, state: torch.Tensor, table: torch.T
 
 def slots_admit(kstage: torch.Tensor, vstage: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, src_row, dst_slot, lens,
                 first_token: torch.Tensor, limits, state: torch.Tensor, d_pos: torch.Tensor, token: torch.Tensor,
-                finish: torch.Tensor, slot: torch.Tensor, history: torch.Tensor, table: torch.Tensor, n_eos: int, n_seq: int):
+                finish: torch.Tensor, slot: torch.Tensor, history: torch.Tensor, table: torch.Tensor, n_eos: int, n_seq: int,
+                pos0: int = 0):
     """Install n staged requests into slots of a slot session in one launch (mg_slots_admit_bf16): K / V positions [0, lens[j])
     of staging row ``src_row[j]`` ([L, n_stage, H, S_stage, 256]) go to live row ``dst_slot[j]`` ([L, B, H, Smax, 256]); the slot's
     position, token (``first_token[j]``, on the device), window, history column and finish record are set as the header states.
-    ``src_row``, ``dst_slot``, ``lens`` and ``limits`` are host integers; what they must satisfy is checked by the entry point."""
+    ``src_row``, ``dst_slot``, ``lens`` and ``limits`` are host integers; what they must satisfy is checked by the entry point.
+    ``pos0`` > 0 (a session prefix; mg_slots_admit_at_bf16): positions [pos0, pos0 + lens[j]) move instead, to the same positions
+    of the slot, whose position becomes pos0 + lens[j]; nothing below pos0 is read or written."""
     _need_gpu(kstage, vstage, kcache, vcache, first_token, state, d_pos, token, finish, slot, history, table)
     Lr, n_stage, H, S_stage, hd = kstage.shape
     _, B, _, Smax, _ = kcache.shape
@@ -924,11 +927,14 @@ def slots_admit(kstage: torch.Tensor, vstage: torch.Tensor, kcache: torch.Tensor
     assert history.dtype == torch.int64 and history.ndim == 2 and history.stride(1) == 1 and history.shape[0] == B
     assert table.dtype == torch.int32 and table.is_contiguous() and table.numel() >= STOP_TABLE_INTS
     arr = lambda xs: (C.c_int32 * max(n, 1))(*[int(x) for x in xs])  # noqa: E731
-    check(L.load().mg_slots_admit_bf16(kstage.data_ptr(), vstage.data_ptr(), n_stage, S_stage, kcache.data_ptr(), vcache.data_ptr(),
-                                       Lr, B, H, Smax, n, arr(src_row), arr(dst_slot), arr(lens), first_token.data_ptr(),
-                                       arr(limits), state.data_ptr(), d_pos.data_ptr(), token.data_ptr(), finish.data_ptr(),
-                                       slot.data_ptr(), history.data_ptr(), history.stride(0), history.shape[1], table.data_ptr(),
-                                       int(n_eos), int(n_seq), _stream()), "mg_slots_admit_bf16")
+    args = (kstage.data_ptr(), vstage.data_ptr(), n_stage, S_stage, kcache.data_ptr(), vcache.data_ptr(), Lr, B, H, Smax, n,
+            arr(src_row), arr(dst_slot), arr(lens), first_token.data_ptr(), arr(limits), state.data_ptr(), d_pos.data_ptr(),
+            token.data_ptr(), finish.data_ptr(), slot.data_ptr(), history.data_ptr(), history.stride(0), history.shape[1],
+            table.data_ptr(), int(n_eos), int(n_seq))
+    if pos0:
+        check(L.load().mg_slots_admit_at_bf16(*args, int(pos0), _stream()), "mg_slots_admit_at_bf16")
+    else:
+        check(L.load().mg_slots_admit_bf16(*args, _stream()), "mg_slots_admit_bf16")
 
 
 def advance_pos(d_pos: torch.Tensor, delta: int = 1, *, pos_stride: int = 0):

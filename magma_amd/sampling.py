@@ -1634,7 +1634,7 @@ def _max_positions(model):
 def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 100, max_prompt: int = None, eos_token=None,
                     stop_sequences=None, temperature: float = 0.0, top_k: int = 0, top_p: float = 0.9,
                     sampler: str = "reference", min_p: float = 0.0, seed: int = None, every: int = None, admit_rows: int = None,
-                    decode: bool = True, **unsupported):
+                    decode: bool = True, prefix=None, **unsupported):
     """Generate over a stream of requests (DESIGN.md "Request streams"): yields one ``StreamResult`` per request, in completion
     order.  Request i's tokens, finish reason and index are those of the solo call
 
@@ -1665,7 +1665,21 @@ def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 10
     of the session, slot) -- two domains that never meet, so no two draws of a session share a counter (engine.SlotSession) --,
     NOT from the counters of a solo call: only greedy decoding and ``top_k=1`` are reproducible against a solo call.  Not combined yet (NotImplementedError): the logits processors, return_logprobs, constraint,
     guidance, beam and contrastive search, past_key_values -- their kernels read the token history from column 0.
-    The arguments are checked when the call is made; the work starts with the first ``next``."""
+    The arguments are checked when the call is made; the work starts with the first ``next``.
+    ``prefix`` (DESIGN.md "Request streams", session prefix): ONE prompt in front of every request -- the few-shot exemplars of an
+    evaluation --, as (P, d) / (1, P, d) embeddings or as a one-row KVCache from ``Magma.cache_prompt`` (HIP engine only; only
+    read: its K / V, positions and pending token are what they were after the session, other calls may keep expanding and
+    continuing it).  Request i's tokens, reason and index are then those of the solo call above on ``request_i`` with
+    ``past_key_values=<a private copy of the prefix cache>``; an LM object that is not the HIP engine runs the solo calls on
+    ``torch.cat([prefix, request_i])``.  The prefix is prefilled ONCE and copied into every slot and every staging row at set-up;
+    an admission prefill still runs over (admit_rows, ceil64(max_prompt)) rows -- the requests' own rows, appended behind the
+    cached prefix --, not over (admit_rows, ceil64(P + max_prompt)).  ``max_prompt`` keeps its meaning, the longest request NOT
+    counting the prefix; its default becomes (max_position_embeddings - P - max_new_tokens) rounded down to 64, and
+    P + max_prompt + max_new_tokens (and the staged P + ceil64(max_prompt)) must fit max_position_embeddings.  Memory: a live
+    cache of ``slots`` x ceil64(P + max_prompt + max_new_tokens) positions plus a staging cache of admit_rows x
+    (P + ceil64(max_prompt)).  Every slot holds its OWN copy of the prefix, so the decode attention of a token step reads P more
+    positions per live row: a prefix saves prefill work, not decode bandwidth.  ValueError at call time: a cache with several
+    rows, with a pending token, of a beam or contrastive search or of another engine, embeddings of the wrong width."""
     import inspect
     defaults = {k: p.default for k, p in inspect.signature(generate).parameters.items()}
     known = {k for _, names in _STREAM_REFUSED for k in names}
@@ -1689,17 +1703,40 @@ def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 10
     if isinstance(every, bool) or not isinstance(every, int) or every < 1:
         raise ValueError(f"every must be an integer >= 1, got {every!r}")
     n_pos = _max_positions(model)
+    P = 0
+    if prefix is not None:
+        if torch.is_tensor(prefix):
+            if prefix.ndim not in (2, 3) or (prefix.ndim == 3 and prefix.shape[0] != 1) or prefix.shape[-2] < 1:
+                raise ValueError(f"prefix must be embeddings (P, d) or (1, P, d) with P >= 1, or a one-row KVCache, got "
+                                 f"{tuple(prefix.shape)}")
+            prefix = prefix[0] if prefix.ndim == 3 else prefix
+            cfg = getattr(model.lm, "config", None)
+            width = getattr(cfg, "hidden_size", None) or getattr(cfg, "n_embd", None)
+            if isinstance(width, int) and prefix.shape[1] != width:
+                raise ValueError(f"prefix must be embeddings of width {width}, got {tuple(prefix.shape)}")
+            P = prefix.shape[0]
+        elif type(prefix).__name__ != "KVCache":
+            raise ValueError(f"prefix must be embeddings (P, d) or (1, P, d), or a one-row KVCache, got {type(prefix).__name__}")
+        elif not on_device:
+            raise ValueError("a KVCache prefix needs the HIP engine's LM: pass the prefix's embeddings")
+        if on_device:           # the session's own checks, now: the cache's rows, pending token, kind and engine, the width
+            from .engine import SlotSession
+            P = SlotSession.prefix_rows(model.lm.engine, prefix)
+    before = f"a prefix of {P} rows + " if P else ""
     if max_prompt is None:
         if n_pos is None:
             raise ValueError("max_prompt is needed: this LM object does not say its max_position_embeddings")
-        max_prompt = (n_pos - max_new_tokens) // 64 * 64
+        max_prompt = (n_pos - P - max_new_tokens) // 64 * 64
         if max_prompt < 1:
-            raise ValueError(f"max_new_tokens = {max_new_tokens} leaves no room for a prompt within max_position_embeddings = {n_pos}; "
-                             "pass max_prompt")
+            raise ValueError(f"{before}max_new_tokens = {max_new_tokens} leaves no room for a prompt within max_position_embeddings = "
+                             f"{n_pos}; pass max_prompt")
     if isinstance(max_prompt, bool) or not isinstance(max_prompt, int) or max_prompt < 1:
         raise ValueError(f"max_prompt must be an integer >= 1, got {max_prompt!r}")
-    if n_pos is not None and max_prompt + max_new_tokens > n_pos:
-        raise ValueError(f"max_prompt = {max_prompt} + max_new_tokens = {max_new_tokens} exceeds max_position_embeddings = {n_pos}")
+    if n_pos is not None and P + max_prompt + max_new_tokens > n_pos:
+        raise ValueError(f"{before}max_prompt = {max_prompt} + max_new_tokens = {max_new_tokens} exceeds max_position_embeddings = {n_pos}")
+    if n_pos is not None and P and on_device and P + (max_prompt + 63) // 64 * 64 > n_pos:
+        raise ValueError(f"{before}max_prompt = {max_prompt}, staged as {(max_prompt + 63) // 64 * 64} rows, exceeds "
+                         f"max_position_embeddings = {n_pos}")
     if eos_token is None or (isinstance(eos_token, int) and not isinstance(eos_token, bool) and not eos_token):
         eos_token = model.eos_token
     stop = check_stop_args(eos_token, stop_sequences, True, _logit_count(model),
@@ -1740,6 +1777,8 @@ def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 10
                   return_finish=True, decode=False, temperature=temperature, top_k=top_k, top_p=top_p, sampler=sampler, min_p=min_p,
                   seed=seed, eos_check_every=every)
         for index, emb, limit in pulled():
+            if P:
+                emb = torch.cat([prefix.to(emb.device, emb.dtype), emb])
             out, fin = generate(model, emb[None], max_steps=limit, **kw)
             ids = out[0, emb.shape[0]: emb.shape[0] + int(fin.kept[0])].to("cpu", torch.int64)
             yield StreamResult(index, ids, text_of(ids, fin.reason[0]), fin.reason[0], fin.index[0], None)
@@ -1751,7 +1790,7 @@ def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 10
             torch.cuda.set_device(model.device)
         plan = LMEngine.selection_plan(sampling=mode, stop=stop, vocab=eng.V, slots=True)
         ses = SlotSession(eng, plan, slots=slots, max_new=max_new_tokens, max_prompt=max_prompt, every=every,
-                          admit_rows=admit_rows, seed=seed)
+                          admit_rows=admit_rows, seed=seed, prefix=prefix)
         dev = eng.device
         for index, ids, code, slot in ses.run((i, e.to(dev), n) for i, e, n in pulled()):
             reason = REASON_NAMES[code >> 8]

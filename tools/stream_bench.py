@@ -9,7 +9,18 @@
     session is given ``max_prompt`` = the prompt length, 57: every admission prefill then runs over (8, 64) rows.
 (b) The captured token step with the slot bookkeeping (mg_sample_finish_slots) against the per-row one (mg_sample_finish_rows),
     measured as tools/stop_rows_bench.py measures: device events around ``--steps`` replays, windows interleaved, the same
-    context length in every window, ``--reps`` windows each; the per-row step twice, to show the spread."""
+    context length in every window, ``--reps`` windows each; the per-row step twice, to show the spread.
+
+  python tools/stream_bench.py --prefix-rows 656 [--request-rows 160] [--out FILE (default profiles/stream_prefix_bench.jsonl)]
+
+The session prefix (DESIGN.md "Request streams", session prefix) instead: 64 requests of ``--request-rows`` rows behind ONE prefix
+of ``--prefix-rows`` rows, max_new_tokens spread over 3 to 12, eos disabled -- few-shot evaluation.
+(a) Tokens that count per second and the rows prefilled in total, legs interleaved after one warm-up pass of each, wall time
+    around each leg ending in a device synchronise: ``generate_stream(prefix=...)``; ``generate_stream`` on the concatenated
+    prompts (``max_prompt`` = prefix + request rows); static ``generate(past_key_values=cache.expand(8), stop_per_row=True)`` in
+    batches of 8 behind one ``cache_prompt``.
+(b) The captured token step of a session with the prefix against the same session without it at equal own-context length: the
+    cost of the P more positions per row the decode attention reads.  Medians over interleaved windows of ``--steps`` replays."""
 import argparse
 import json
 import os
@@ -31,8 +42,13 @@ ap.add_argument("--requests", type=int, default=64)
 ap.add_argument("--every", type=int, default=0, help="0 = MAGMA_EOS_CHECK_EVERY (8)")
 ap.add_argument("--steps", type=int, default=250)
 ap.add_argument("--reps", type=int, default=5)
-ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "stream_bench.jsonl"))
+ap.add_argument("--prefix-rows", type=int, default=0, help="P > 0: measure the session prefix instead (see the module docstring)")
+ap.add_argument("--request-rows", type=int, default=160, help="rows of every request in the --prefix-rows mode")
+ap.add_argument("--out", default=None, help="default: profiles/stream_bench.jsonl, profiles/stream_prefix_bench.jsonl with --prefix-rows")
 args = ap.parse_args()
+if args.out is None:
+    args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                            "stream_prefix_bench.jsonl" if args.prefix_rows else "stream_bench.jsonl")
 
 if not torch.cuda.is_available():
     sys.exit("stream_bench: no GPU -- this tool measures, it does not fall back")
@@ -59,7 +75,109 @@ def emit(d):
     print(lines[-1], flush=True)
 
 
+
+
+def write_out():
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+def prefix_mode():
+    """--prefix-rows P: the three throughput legs and the step with and without the prefix."""
+    P, R = args.prefix_rows, args.request_rows
+    limits = [3 + (7 * i) % 10 for i in range(args.requests)]           # 3 .. 12, every residue of 10 in turn
+    emb = model.embed([images, torch.randint(0, 50256, (8, R - 49), device=dev, generator=g)])       # 49 image rows + text
+    assert emb.shape[1] == R, emb.shape
+    prefix = eng.embed_ids(torch.randint(0, 50256, (1, P), device=dev, generator=g))[0]
+    requests = [(emb[i % 8], limits[i]) for i in range(args.requests)]
+    joined = [(torch.cat([prefix, e]), n) for e, n in requests]
+    admit, passes = SlotSession._admit, []
+
+    def counted(self, batch, slots):
+        passes.append(self.n_admit * self.S_stage)
+        admit(self, batch, slots)
+
+    SlotSession._admit = counted
+    skw = dict(slots=B, max_new_tokens=max(limits), eos_token=[EOS], decode=False, every=args.every or None)
+
+    def leg_prefix():
+        n = sum(int(r.tokens.numel()) for r in model.generate_stream(requests, max_prompt=R, prefix=prefix, **skw))
+        return n, P + sum(passes)
+
+    def leg_joined():
+        n = sum(int(r.tokens.numel()) for r in model.generate_stream(joined, max_prompt=P + R, **skw))
+        return n, sum(passes)
+
+    def leg_static():
+        cache, n, rows = model.cache_prompt(prefix[None]), 0, P
+        for i in range(0, args.requests, B):
+            group = requests[i:i + B]
+            lim = torch.tensor([x[1] for x in group])
+            out, fin = model.generate(torch.stack([x[0] for x in group]), past_key_values=cache.expand(len(group)), max_steps=int(lim.max()),
+                                      temperature=0.0, decode=False, eos_token=[EOS], stop_per_row=True, return_finish=True,
+                                      eos_check_every=args.every or None)
+            n += int(torch.minimum(fin.kept, lim).sum())
+            rows += len(group) * R
+        return n, rows
+
+    legs = [("generate_stream_prefix", leg_prefix), ("generate_stream_concatenated", leg_joined), ("static_expand", leg_static)]
+    for _, leg in legs:             # one warm-up pass of every leg
+        leg()
+    for rep in range(args.reps):
+        for name, leg in legs:
+            passes.clear()
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            n, rows = leg()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t
+            emit({"part": "throughput", "leg": name, "rep": rep, "requests": args.requests, "slots": B, "prefix_rows": P, "request_rows": R,
+                  "tokens_that_count": n, "wall_s": dt, "tokens_per_s": n / dt, "rows_prefilled": rows, "limits_sum": sum(limits)})
+    for name, _ in legs:
+        runs = [json.loads(x) for x in lines]
+        runs = [x for x in runs if x["part"] == "throughput" and x["leg"] == name]
+        emit({"part": "throughput_median", "leg": name, "tokens_per_s_median": statistics.median(x["tokens_per_s"] for x in runs),
+              "wall_s_median": statistics.median(x["wall_s"] for x in runs), "rows_prefilled": runs[0]["rows_prefilled"],
+              "tokens_that_count": runs[0]["tokens_that_count"]})
+    SlotSession._admit = admit
+    eng._cache_pool.clear()
+
+    # ---- the captured token step with and without the prefix, at the same own-context length ----
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    plan = LMEngine.selection_plan(stop=dict(eos_ids=(EOS,), stop_seqs=()), vocab=eng.V, slots=True)
+    held = {}
+    for name, given in (("with_prefix", prefix), ("without_prefix", None), ("without_prefix_again", None)):
+        ses = SlotSession(eng, plan, slots=B, max_new=args.steps + 8, max_prompt=R, every=1, admit_rows=B, prefix=given)
+        ses._admit([(i, emb[i % 8], args.steps + 8) for i in range(B)], list(range(B)))
+        sc = ses.cache
+        tensors = (sc.d_pos, sc.finish, sc.slot_table, sc.sample_state, ses.st.token)
+        held[name] = (ses, tensors, [t.clone() for t in tensors], list(ses.occ))
+        for _ in range(3):
+            ses._step()
+    ms = {name: [] for name in held}
+    for rep in range(args.reps):
+        for name, (ses, tensors, keep, occ) in held.items():
+            for t, k in zip(tensors, keep):
+                t.copy_(k)
+            ses.steps, ses.occ = 0, list(occ)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(args.steps):
+                ses._step()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[name].append(e0.elapsed_time(e1) / args.steps)
+    for name in ms:
+        emit({"part": "step", "variant": name, "prefix_rows": held[name][0].P, "own_rows": R, "step_ms_min": min(ms[name]),
+              "step_ms_median": statistics.median(ms[name]), "step_ms_all": ms[name], "steps_per_window": args.steps})
+    write_out()
+
+
 with torch.no_grad():
+    if args.prefix_rows:
+        prefix_mode()
+        sys.exit(0)
     emb = model.embed([images, prompt])
     S0 = int(emb.shape[1])
     requests = [(emb[i % 8], LIMITS[i]) for i in range(args.requests)]
@@ -139,6 +257,4 @@ with torch.no_grad():
         emit({"part": "step", "variant": name, "step_ms_min": min(ms[name]), "step_ms_median": statistics.median(ms[name]),
               "step_ms_all": ms[name], "steps_per_window": args.steps,
               "rows_finished": int(((sc if name == "slots" else caches[name]).finish[:, 0] >= 0).sum())})
-if args.out:
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+write_out()
