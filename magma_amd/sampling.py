@@ -9,6 +9,7 @@ per-step ``(next_token == eos).all()`` host sync of the reference (:109) became
 a device-side record read every few steps.  ``top_k_filter`` / ``top_p_filter``
 below are the host statements of the same rules (pinned to the reference's own
 functions, tests/test_oracle_pins.py) and serve LM objects other than the engine."""
+import contextlib
 import math
 import os
 from typing import Callable, List, NamedTuple, Optional, Tuple, Union
@@ -1212,6 +1213,64 @@ def _logit_count(model):
     return int(v) if isinstance(v, int) else None
 
 
+@contextlib.contextmanager
+def eval_mode(model):
+    """The model in eval mode for the block; behind it -- after an exception too -- in the mode it was given in."""
+    was_training = model.training
+    model.eval()
+    try:
+        yield
+    finally:
+        model.train(was_training)
+
+
+def poll_every(eos_check_every=None) -> int:
+    """The steps between two host looks at the device's all-eos record: the argument, else MAGMA_EOS_CHECK_EVERY, else 8."""
+    return eos_check_every or int(os.environ.get("MAGMA_EOS_CHECK_EVERY", "8"))
+
+
+def sampling_mode(temperature, top_k, top_p, warp, seed):
+    """(mode, seed): mode None (greedy), (temperature, top_k, top_p), or -- ``warp``: check_sampler_args' dict -- ("warp",
+    temperature, top_k, top_p, min_p); a sampled call without a seed draws one from torch's CPU generator here."""
+    if temperature == 0.0:
+        return None, seed
+    mode = (float(temperature), int(top_k), float(top_p))
+    if warp is not None:
+        mode = ("warp",) + mode + (warp["min_p"],)
+    return mode, int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else seed
+
+
+def layout_ids(tokens, s: int, lengths, image_token: int, eos_token: int, repeat: int = 1):
+    """The ids generate() returns, (rows, s + n) on the device of ``tokens`` (rows, n): per row the image token for the length of
+    its prompt, its tokens, eos up to the width.  ``lengths``: None (every prompt is ``s`` long) or the samples' host int64
+    lengths, each standing for ``repeat`` consecutive rows (the hypotheses beam search returns per sample)."""
+    rows, n = tokens.shape
+    dev = tokens.device
+    out = torch.full((rows, s + n), eos_token, dtype=torch.long, device=dev)
+    if lengths is not None:     # ragged: a row's tokens follow its own prompt, eos after them
+        lens = lengths.to(dev, non_blocking=True)                   # (no host sync: the next call's launches queue behind this one)
+        lens = (lens if repeat == 1 else lens.repeat_interleave(repeat))[:, None]
+        out.masked_fill_(torch.arange(s + n, device=dev)[None, :] < lens, image_token)
+        out.scatter_(1, lens + torch.arange(n, device=dev)[None, :], tokens)
+    else:
+        out[:, :s] = image_token
+        out[:, s:] = tokens
+    return out
+
+
+def decode_ids(model, out, eos_token, s: int = 0, lengths=None, finish=None) -> List[str]:
+    """``decode=True``: every row of ids as text -- by the reference's rule, cut at the first eos, image tokens dropped; with
+    ``finish`` (a per-row call's Finish; ``s`` / ``lengths``: the prompts' width and lengths, as for layout_ids), the row's own
+    kept tokens without the eos that finished it."""
+    if finish is None:
+        return [model.tokenizer.decode(remove_tokens_after_eos(row, eos_token, model.image_token)) for row in out]
+    rows = []
+    for r, at in enumerate(lengths.tolist() if lengths is not None else [s] * len(out)):
+        ids = out[r, at: at + int(finish.kept[r])].tolist()
+        rows.append(model.tokenizer.decode([t for t in (ids[:-1] if finish.reason[r] == "eos" else ids) if t != model.image_token]))
+    return rows
+
+
 @torch.no_grad()
 def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, top_k: int = 0,
              top_p: float = 0.9, eos_token: int = None, decode: bool = True,
@@ -1400,7 +1459,6 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
         return _generate_beam(model, embeddings, max_steps, eos_token, decode, eos_check_every, lengths, num_beams,
                               float(length_penalty), early_stopping, num_return_sequences, return_scores, proc,
                               num_beam_groups, float(diversity_penalty))
-    was_training = model.training
     b, s, _ = embeddings.shape
     if guide is not None:       # the negative prompt as (b, s', d) rows, row counts and hidden size checked
         guide = check_guidance_args(guidance_scale, negative_embeddings, negative_lengths, guidance_min_p, b, embeddings.shape[2])
@@ -1415,42 +1473,26 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     lengths = prompt_batch(embeddings, lengths, per_row=on_device)[1]       # (the batch is normalised: this checks the lengths)
     if guide is not None and guide["lengths"] is not None and not on_device:
         raise ValueError("negative prompts of different lengths need the HIP engine's LM (per-row KV positions)")
-    model.eval()
-    greedy = temperature == 0.0
-    mode = None if greedy else (float(temperature), int(top_k), float(top_p))
-    if warp is not None and not greedy:
-        mode = ("warp",) + mode + (warp["min_p"],)
-    if seed is None and not greedy:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-    every = eos_check_every or int(os.environ.get("MAGMA_EOS_CHECK_EVERY", "8"))
+    mode, seed = sampling_mode(temperature, top_k, top_p, warp, seed)
     modes = dict(mode=mode, proc=proc, stop=stop, n_top=n_top, cons=cons, guide=guide, eos_ids=eos_ids)
     want_finish = stop is not None and (return_finish or continuing or decode)      # the tail reads the per-row finish record
-    run = (_device_loop if on_device else _host_loop)(
-        model, embeddings, lengths, max_steps, eos_token, seed, every, stop_on_eos, modes, want_finish, past_key_values)
-    out, n_gen, past = run.out, run.out.shape[1] - s, run.past
-    record = run.record
-    if record is None and return_finish:                              # the reference's rule: every row ran the whole call
-        record = torch.tensor([[-1, 0]] * b).view(b, 2)
-    finish = None if record is None else finish_from_record(record, n_gen)
-    logprobs = None
-    if n_top is not None:       # what the steps wrote (or the host statement's values), masked past every row's count
-        vals = run.logprobs if n_gen else (torch.zeros(b, 0), torch.zeros(b, 0, n_top, dtype=torch.int64), torch.zeros(b, 0, n_top))
-        logprobs = mask_logprobs(run.tokens, *vals, finish.kept if finish is not None else torch.full((b,), n_gen))
-    if continuing:      # the cache keeps the conversation (a continued one too: it was advanced in place and stays continuable)
-        keep_conversation(past, run.start, n_gen, eos_token, finish if stop is not None else None)
-        model.lm.engine.detach_cache(past)
-    if decode and stop is not None:      # every row up to its own kept count; the eos that finished it is dropped as below
-        first = lengths.tolist() if lengths is not None else [s] * b
-        rows = []
-        for r in range(b):
-            ids = out[r, first[r]: first[r] + int(finish.kept[r])].tolist()
-            if finish.reason[r] == "eos":
-                ids = ids[:-1]
-            rows.append(model.tokenizer.decode([t for t in ids if t != model.image_token]))
-        out = rows
-    elif decode:
-        out = [model.tokenizer.decode(remove_tokens_after_eos(row, eos_token, model.image_token)) for row in out]
-    model.train(was_training)
+    with eval_mode(model):
+        run = (_device_loop if on_device else _host_loop)(
+            model, embeddings, lengths, max_steps, eos_token, seed, poll_every(eos_check_every), stop_on_eos, modes, want_finish,
+            past_key_values)
+        out, n_gen, past, record = run.out, run.out.shape[1] - s, run.past, run.record
+        if record is None and return_finish:                              # the reference's rule: every row ran the whole call
+            record = torch.tensor([[-1, 0]] * b).view(b, 2)
+        finish = None if record is None else finish_from_record(record, n_gen)
+        logprobs = None
+        if n_top is not None:       # what the steps wrote (or the host statement's values), masked past every row's count
+            vals = run.logprobs if n_gen else (torch.zeros(b, 0), torch.zeros(b, 0, n_top, dtype=torch.int64), torch.zeros(b, 0, n_top))
+            logprobs = mask_logprobs(run.tokens, *vals, finish.kept if finish is not None else torch.full((b,), n_gen))
+        if continuing:      # the cache keeps the conversation (a continued one too: it was advanced in place and stays continuable)
+            keep_conversation(past, run.start, n_gen, eos_token, finish if stop is not None else None)
+            model.lm.engine.detach_cache(past)
+        if decode:          # per-row stopping: every row up to its own kept count
+            out = decode_ids(model, out, eos_token, s, lengths, finish if stop is not None else None)
     ret = (out, past) if return_past_key_values else (out,)
     if return_finish:
         ret += (finish,)
@@ -1460,32 +1502,40 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
 
 
 class _Generated(NamedTuple):
-    """What a generate() loop hands to the shared tail: ``out`` (b, s + n) ids laid out for the caller, ``tokens`` (b, n) the
+    """What a generate() loop hands to the shared tail: ``out`` (rows, s + n) ids laid out for the caller, ``tokens`` (rows, n) the
     generated columns, the LM's ``past``, the finish ``record`` (host [b, 2]; None when the tail does not read it), the per-step
-    ``logprobs`` (lp, top ids, top lp; None without a step), ``start`` (engine: the cache position of every row's first new token)."""
+    ``logprobs`` (lp, top ids, top lp; None without a step), ``start`` (engine: the cache position of every row's first new token),
+    ``scores`` (engine, beam search: one per returned hypothesis)."""
     out: torch.Tensor
     tokens: torch.Tensor
     past: object = None
     record: Optional[torch.Tensor] = None
     logprobs: Optional[tuple] = None
     start: Optional[torch.Tensor] = None
+    scores: Optional[torch.Tensor] = None
 
 
 def _device_loop(model, embeddings, lengths, max_steps, eos_token, seed, every, stop_on_eos, modes, want_finish,
-                 past_key_values) -> _Generated:
-    """generate()'s loop on the HIP engine: one prefill (or the new inputs appended to the caller's cache), then steps that feed
-    the selected token back on the device -- nothing crosses the host but the all-eos step, read every ``every`` steps -- under ONE
-    SelectionPlan built here; the output is laid out from the token history the bookkeeping launch kept."""
+                 past_key_values, k: int = 1, first: bool = True, n_ret: int = 0) -> _Generated:
+    """generate()'s loop on the HIP engine, in every selection mode: one prefill (or the new inputs appended to the caller's
+    cache), then steps that feed the selected token back on the device -- nothing crosses the host but the all-eos step, read every
+    ``every`` steps -- under ONE SelectionPlan built here from ``modes`` (generate()'s checked arguments by name; a missing one is
+    None); the output is laid out from the token history the bookkeeping launch kept.  What beam and contrastive search change:
+    ``k`` cache rows per sample (num_beams / top_k); ``first`` False: the prefill selects nothing, max_steps token steps follow
+    it; ``n_ret`` > 0 (beam search): the poll always looks and cuts nothing, the tokens are beam_results(past, n_ret)."""
     from .engine import LMEngine
     b, s, _ = embeddings.shape
     dev = embeddings.device
-    stop, n_top, guide = modes["stop"], modes["n_top"], modes["guide"]
-    plan = LMEngine.selection_plan(sampling=modes["mode"], processors=modes["proc"], stop=stop, logprobs=n_top,
-                                   constraint=modes["cons"], guidance=None if guide is None else (guide["scale"], guide["min_p"]),
-                                   vocab=model.lm.engine.V)
+    stop, n_top, guide = modes.get("stop"), modes.get("n_top"), modes.get("guide")
+    plan = LMEngine.selection_plan(sampling=modes.get("mode"), beam=modes.get("beam"), processors=modes.get("proc"), stop=stop,
+                                   logprobs=n_top, constraint=modes.get("cons"), contrast=modes.get("contrast"),
+                                   guidance=None if guide is None else (guide["scale"], guide["min_p"]), vocab=model.lm.engine.V)
     first_kw = dict(eos_token=eos_token, seed=seed, plan=plan, lengths=lengths)
     own = lengths if lengths is not None else torch.full((b,), s, dtype=torch.int64)     # the positions every row adds
     prompts, start = embeddings, own
+    if k > 1:                   # B prompts -> B * k rows, sample-major
+        prompts = embeddings.repeat_interleave(k, dim=0)
+        first_kw["lengths"] = None if lengths is None else lengths.repeat_interleave(k)
     if guide is not None:       # ONE ragged batch of 2b rows: the prompts, then the negative prompts
         neg = guide["embeddings"].to(device=dev, dtype=embeddings.dtype)
         s_neg = neg.shape[1]
@@ -1497,36 +1547,33 @@ def _device_loop(model, embeddings, lengths, max_steps, eos_token, seed, every, 
         before = past_key_values.rows_pos() + (past_key_values.pending >= 0).to(torch.int64) \
             if past_key_values.pending is not None else past_key_values.rows_pos()
         start, first_kw["lengths"] = before + own, own
-    n_gen, past = 0, None
+
+    def prefill():              # into a pooled cache, or the new rows (``prompts`` are the embeddings) behind the caller's
+        return model.lm(inputs_embeds=prompts, use_cache=True, past_key_values=past_key_values, cache_hint=max_steps,
+                        reuse_cache=past_key_values is None, **first_kw)
+
+    look = bool(n_ret) or (stop_on_eos and eos_token is not None)
+    n_gen, past = 0, None if first else prefill().past_key_values
     for i in range(max_steps):
-        if i > 0:        # the token selected by the previous step is fed back on the device
+        if past is not None:    # the token selected by the previous step (or prefill) is fed back on the device
             outputs = model.lm(input_ids=None, use_cache=True, past_key_values=past, feed_back=True, plan=plan)
-        elif past_key_values is not None:
-            outputs = model.lm(inputs_embeds=embeddings, use_cache=True, past_key_values=past_key_values, cache_hint=max_steps,
-                               **first_kw)
         else:
-            outputs = model.lm(inputs_embeds=prompts, use_cache=True, past_key_values=None, cache_hint=max_steps,
-                               reuse_cache=True, **first_kw)
+            outputs = prefill()
         past = outputs.past_key_values
         n_gen += 1
-        if stop_on_eos and eos_token is not None and ((i + 1) % every == 0 or i + 1 == max_steps):
-            first = int(outputs.eos_state[1])            # one host sync per `every` steps
-            if first >= 0:
-                n_gen = first + 1                        # tokens after the first all-eos step are dropped again
+        if look and ((i + 1) % every == 0 or i + 1 == max_steps):
+            all_eos = int(outputs.eos_state[1])          # one host sync per `every` steps
+            if all_eos >= 0:
+                n_gen = n_gen if n_ret else all_eos + 1  # tokens after the first all-eos step are dropped again
                 break
-    # (``[:b]``: a guided cache holds 2b rows and keeps the per-row records of the b guided ones in its first b rows)
-    tokens = past.history[:b, :n_gen] if past is not None else torch.zeros(b, 0, dtype=torch.long, device=dev)
-    out = torch.full((b, s + n_gen), eos_token, dtype=torch.long, device=dev)
-    if lengths is not None:     # ragged: row b's tokens follow its own prompt, eos after them
-        lens = lengths.to(dev, non_blocking=True)[:, None]          # (no host sync: the next call's launches queue behind this one)
-        out.masked_fill_(torch.arange(s + n_gen, device=dev)[None, :] < lens, model.image_token)
-        out.scatter_(1, lens + torch.arange(n_gen, device=dev)[None, :], tokens)
-    else:                       # one copy of the token history the bookkeeping kernel kept
-        out[:, :s] = model.image_token
-        out[:, s:] = tokens
+    # (``[:b * k:k]``: a sample's k rows hold one history; a guided cache of 2b rows keeps the b guided rows' records first)
+    tokens, scores = past.history[:b * k:k, :n_gen] if past is not None else torch.zeros(b, 0, dtype=torch.long, device=dev), None
+    if n_ret:
+        tokens, scores, _ = model.lm.engine.beam_results(past, n_ret)
+    out = layout_ids(tokens.to(dev), s, lengths, model.image_token, eos_token, n_ret or 1)
     record = past.finish[:b].cpu() if stop is not None and (want_finish or (n_top is not None and n_gen)) else None
     vals = (past.lp[:b, :n_gen], past.top_id[:b, :n_gen], past.top_lp[:b, :n_gen]) if n_top is not None and n_gen else None
-    return _Generated(out, tokens, past, record, vals, start)
+    return _Generated(out, tokens, past, record, vals, start, scores)
 
 
 def _host_loop(model, embeddings, lengths, max_steps, eos_token, seed, every, stop_on_eos, modes, want_finish,
@@ -1699,7 +1746,7 @@ def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 10
     if isinstance(admit_rows, bool) or not isinstance(admit_rows, int) or not 1 <= admit_rows <= slots:
         raise ValueError(f"admit_rows must be an integer in [1, slots = {slots}], got {admit_rows!r}")
     if every is None:
-        every = int(os.environ.get("MAGMA_EOS_CHECK_EVERY", "8"))
+        every = poll_every()
     if isinstance(every, bool) or not isinstance(every, int) or every < 1:
         raise ValueError(f"every must be an integer >= 1, got {every!r}")
     n_pos = _max_positions(model)
@@ -1742,14 +1789,9 @@ def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 10
     stop = check_stop_args(eos_token, stop_sequences, True, _logit_count(model),
                            getattr(getattr(model, "tokenizer", None), "encode", None))
     warp = check_sampler_args(sampler, min_p, top_p)
-    greedy = temperature == 0.0
-    if min_p > 0 and greedy:
+    if min_p > 0 and temperature == 0.0:
         raise ValueError("min_p applies to sampled selection: greedy decoding (temperature=0) would drop it")
-    mode = None if greedy else (float(temperature), int(top_k), float(top_p))
-    if warp is not None and not greedy:
-        mode = ("warp",) + mode + (warp["min_p"],)
-    if seed is None and not greedy:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    mode, seed = sampling_mode(temperature, top_k, top_p, warp, seed)
 
     def pulled():
         """(index, (S, d) embeddings, limit) of every request, checked as it is pulled."""
@@ -2245,120 +2287,75 @@ def keep_conversation(cache, start: torch.Tensor, n_gen: int, eos_token, finish:
 def _generate_beam(model, embeddings, max_steps, eos_token, decode, eos_check_every, lengths, k, length_penalty,
                    early_stopping, n_ret, return_scores, proc=None, groups=1, diversity=0.0):
     """generate()'s beam search over the prompt batch it has normalised: on the HIP engine's device, or beam_search on the host."""
-    was_training = model.training
     on_device = getattr(model.lm, "device_token_selection", False)
     embeddings, lengths = prompt_batch(embeddings, lengths, per_row=on_device)
     b, s, _ = embeddings.shape
     dev = embeddings.device
-    model.eval()
-    emb = embeddings.repeat_interleave(k, dim=0)           # B prompts -> B*k rows, sample-major
-    if on_device:
-        from .engine import LMEngine
-        beam = (k, length_penalty, early_stopping, int(max_steps)) + ((groups, diversity) if groups > 1 else ())
-        plan = LMEngine.selection_plan(beam=beam, processors=proc,
-                                       vocab=model.lm.engine.V)
-        every = eos_check_every or int(os.environ.get("MAGMA_EOS_CHECK_EVERY", "8"))
-        for i in range(max_steps):
-            if i == 0:
-                o = model.lm(inputs_embeds=emb, use_cache=True, past_key_values=None, cache_hint=max_steps, reuse_cache=True,
-                             eos_token=eos_token, plan=plan, lengths=None if lengths is None else lengths.repeat_interleave(k))
-            else:
-                o = model.lm(input_ids=None, use_cache=True, past_key_values=past, feed_back=True, plan=plan)
-            past = o.past_key_values
-            if ((i + 1) % every == 0 or i + 1 == max_steps) and int(o.eos_state[1]) >= 0:     # one host sync per `every` steps
-                break
-        toks, scores, lens = model.lm.engine.beam_results(past, n_ret)
-    else:
-        cache = {}
-
-        def step(rows, tokens):
-            if rows is None:
-                o = model.lm(inputs_embeds=emb, use_cache=True, past_key_values=None)
-            else:
-                o = model.lm(input_ids=tokens[:, None].to(dev), use_cache=True,
-                             past_key_values=reorder_past(cache["past"], rows.to(dev)))
-            cache["past"] = o.past_key_values
-            return o.logits[:, -1, :].float()
-
-        if groups > 1:
-            toks, scores, lens = group_beam_search(step, b, k, groups, diversity, max_steps, eos_token, length_penalty,
-                                                   early_stopping, n_ret, processors=proc)
+    with eval_mode(model):
+        if on_device:
+            beam = (k, length_penalty, early_stopping, int(max_steps)) + ((groups, diversity) if groups > 1 else ())
+            run = _device_loop(model, embeddings, lengths, max_steps, eos_token, seed=None, every=poll_every(eos_check_every),
+                               stop_on_eos=True, modes=dict(beam=beam, proc=proc), want_finish=False, past_key_values=None,
+                               k=k, n_ret=n_ret)
+            out, scores = run.out, run.scores
         else:
-            toks, scores, lens = beam_search(step, b, k, max_steps, eos_token, length_penalty, early_stopping, n_ret,
-                                             processors=proc)
-    toks, lens = toks.to(dev), lens.to(dev)
-    n = toks.shape[1]
-    out = torch.full((b * n_ret, s + n), eos_token, dtype=torch.long, device=dev)
-    if lengths is None:
-        out[:, :s] = model.image_token
-        out[:, s:] = toks
-    else:                                                    # ragged: row j of sample b starts after len_b image tokens
-        lens_r = lengths.to(dev).repeat_interleave(n_ret)[:, None]
-        out.masked_fill_(torch.arange(s + n, device=dev)[None, :] < lens_r, model.image_token)
-        out.scatter_(1, lens_r + torch.arange(n, device=dev)[None, :], toks)
-    if decode:
-        out = [model.tokenizer.decode(remove_tokens_after_eos(row, eos_token, model.image_token)) for row in out]
-    model.train(was_training)
+            emb = embeddings.repeat_interleave(k, dim=0)           # B prompts -> B*k rows, sample-major
+            cache = {}
+
+            def step(rows, tokens):
+                if rows is None:
+                    o = model.lm(inputs_embeds=emb, use_cache=True, past_key_values=None)
+                else:
+                    o = model.lm(input_ids=tokens[:, None].to(dev), use_cache=True,
+                                 past_key_values=reorder_past(cache["past"], rows.to(dev)))
+                cache["past"] = o.past_key_values
+                return o.logits[:, -1, :].float()
+
+            if groups > 1:
+                toks, scores, _ = group_beam_search(step, b, k, groups, diversity, max_steps, eos_token, length_penalty,
+                                                    early_stopping, n_ret, processors=proc)
+            else:
+                toks, scores, _ = beam_search(step, b, k, max_steps, eos_token, length_penalty, early_stopping, n_ret,
+                                              processors=proc)
+            out = layout_ids(toks.to(dev), s, lengths, model.image_token, eos_token, n_ret)
+        if decode:
+            out = decode_ids(model, out, eos_token)
     return (out, scores.float().cpu()) if return_scores else out
 
 
 @torch.no_grad()
 def _generate_contrastive(model, embeddings, max_steps, eos_token, decode, eos_check_every, lengths, k, alpha, stop_on_eos):
-    """generate()'s contrastive search over the prompt batch it has normalised: on the HIP engine's device -- one prefill over
-    B * k rows (every sample k times, sample-major, as beam search lays them out), then one token step per generated token,
-    the first included --, or contrastive_search on the host."""
-    was_training = model.training
+    """generate()'s contrastive search over the prompt batch it has normalised: on the HIP engine's device -- a cache of B * k rows,
+    one token step per generated token behind the prefill, the first included --, or contrastive_search on the host."""
     on_device = getattr(model.lm, "device_token_selection", False)
     embeddings, lengths = prompt_batch(embeddings, lengths, per_row=on_device)
     b, s, _ = embeddings.shape
     dev = embeddings.device
-    model.eval()
-    emb = embeddings.repeat_interleave(k, dim=0)           # B prompts -> B*k rows, sample-major
-    if on_device:
-        from .engine import LMEngine
-        plan = LMEngine.selection_plan(contrast=(k, alpha), vocab=model.lm.engine.V)
-        every = eos_check_every or int(os.environ.get("MAGMA_EOS_CHECK_EVERY", "8"))
-        o = model.lm(inputs_embeds=emb, use_cache=True, past_key_values=None, cache_hint=max_steps, reuse_cache=True,
-                     eos_token=eos_token, plan=plan, lengths=None if lengths is None else lengths.repeat_interleave(k))
-        past, n_gen = o.past_key_values, 0
-        for i in range(max_steps):
-            o = model.lm(input_ids=None, use_cache=True, past_key_values=past, feed_back=True, plan=plan)
-            n_gen += 1
-            if stop_on_eos and eos_token is not None and ((i + 1) % every == 0 or i + 1 == max_steps):
-                first = int(o.eos_state[1])                 # one host sync per `every` steps
-                if first >= 0:
-                    n_gen = first + 1
-                    break
-        toks = past.history[::k, :n_gen]                    # the k rows of a sample hold the same history
-    else:
-        cache = {}
-        ln_f = getattr(getattr(model.lm, "transformer", None), "ln_f", None)
+    with eval_mode(model):
+        if on_device:
+            out = _device_loop(model, embeddings, lengths, max_steps, eos_token, seed=None, every=poll_every(eos_check_every),
+                               stop_on_eos=stop_on_eos, modes=dict(contrast=(k, alpha)), want_finish=False,
+                               past_key_values=None, k=k, first=False).out
+        else:
+            emb = embeddings.repeat_interleave(k, dim=0)           # B prompts -> B*k rows, sample-major
+            cache = {}
+            ln_f = getattr(getattr(model.lm, "transformer", None), "ln_f", None)
 
-        def hidden(o):      # hidden_states[-1] of transformers' GPT-J: the output of ln_f
-            h = o.hidden_states[-1]
-            return ln_f(h) if ln_f is not None else h
+            def hidden(o):      # hidden_states[-1] of transformers' GPT-J: the output of ln_f
+                h = o.hidden_states[-1]
+                return ln_f(h) if ln_f is not None else h
 
-        def step(tokens, parents):
-            past = cache["past"] if parents is None else reorder_past(cache["past"], parents.to(dev))
-            o = model.lm(input_ids=tokens[:, None].to(dev), use_cache=True, past_key_values=past, output_hidden_states=True)
+            def step(tokens, parents):
+                past = cache["past"] if parents is None else reorder_past(cache["past"], parents.to(dev))
+                o = model.lm(input_ids=tokens[:, None].to(dev), use_cache=True, past_key_values=past, output_hidden_states=True)
+                cache["past"] = o.past_key_values
+                return o.logits[:, -1, :].float(), hidden(o)[:, -1, :]
+
+            o = model.lm(inputs_embeds=emb, use_cache=True, past_key_values=None, output_hidden_states=True)
             cache["past"] = o.past_key_values
-            return o.logits[:, -1, :].float(), hidden(o)[:, -1, :]
-
-        o = model.lm(inputs_embeds=emb, use_cache=True, past_key_values=None, output_hidden_states=True)
-        cache["past"] = o.past_key_values
-        toks, _ = contrastive_search(step, hidden(o)[::k], o.logits[::k, -1, :].float(), None, k, alpha, max_steps, eos_token,
-                                     stop_on_eos)
-    toks = toks.to(dev)
-    n = toks.shape[1]
-    out = torch.full((b, s + n), eos_token, dtype=torch.long, device=dev)
-    if lengths is None:
-        out[:, :s] = model.image_token
-        out[:, s:] = toks
-    else:                                                    # ragged: row b's tokens follow its own prompt, eos after them
-        lens = lengths.to(dev)[:, None]
-        out.masked_fill_(torch.arange(s + n, device=dev)[None, :] < lens, model.image_token)
-        out.scatter_(1, lens + torch.arange(n, device=dev)[None, :], toks)
-    if decode:
-        out = [model.tokenizer.decode(remove_tokens_after_eos(row, eos_token, model.image_token)) for row in out]
-    model.train(was_training)
+            toks, _ = contrastive_search(step, hidden(o)[::k], o.logits[::k, -1, :].float(), None, k, alpha, max_steps, eos_token,
+                                         stop_on_eos)
+            out = layout_ids(toks.to(dev), s, lengths, model.image_token, eos_token)
+        if decode:
+            out = decode_ids(model, out, eos_token)
     return out

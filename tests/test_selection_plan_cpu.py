@@ -1,4 +1,4 @@
-"""SelectionPlan (magma_amd/engine.py): the one checked statement of a token step's selection modes.  No engine, no GPU: the
+"""SelectionPlan (magma_amd/selection.py): the one checked statement of a token step's selection modes.  No engine, no GPU: the
 constructor only normalises and refuses, and the key of a captured step is a pure function of the plan.
 
 The key contract: two steps share a captured graph exactly when everything that is a LAUNCH ARGUMENT of the step agrees --
