@@ -107,8 +107,10 @@ const char* mg_version(void);
  *  23  losslessly packed decode weights: mg_skinny_desc grew by `pk_lo`, `pk_nib`, `pk_base`, `pk_sign`, `pk_flags` at its end
  *      (NULL = as before; nothing else moved).
  *  24  request streams: added mg_sample_finish_slots and mg_slots_admit_bf16, MG_STOP_LEN and MG_SLOTS_MAX (nothing moved).
- *  25  session prefix of a request stream: added mg_slots_admit_at_bf16 (nothing moved). */
-#define MG_ABI_VERSION 25
+ *  25  session prefix of a request stream: added mg_slots_admit_at_bf16 (nothing moved).
+ *  26  shared session prefix: added mg_attn_decode_prefix_bf16, mg_attn_decode_fused_shared_bf16, mg_decode_attn_gemv_shared_bf16,
+ *      mg_slots_admit_shared_bf16, MG_PREFIX_CHUNK and MG_PREFIX_PART (nothing moved). */
+#define MG_ABI_VERSION 26
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -322,6 +324,12 @@ int mg_decode_attn_gemv_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_bf16* vcach
                              int32_t B, int32_t H, int32_t Smax, const int32_t* d_pos, int32_t rot_dim,
                              const float* sin_t, const float* cos_t, const mg_skinny_desc* gemv,
                              int32_t pos_stride /* ABI 7: see mg_attn_decode_fused_bf16 */, void* stream);
+/* The same co-launch with the attention workgroups in the shared-prefix mode (ABI 26: mg_attn_decode_fused_shared_bf16 below); the
+ * GEMV runs the variant mg_decode_attn_gemv_bf16 picks for the same operand. */
+int mg_decode_attn_gemv_shared_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_bf16* vcache, mg_bf16* attn_out, int64_t ld_attn_out,
+                                    int32_t B, int32_t H, int32_t Smax, const int32_t* d_pos, int32_t rot_dim, const float* sin_t,
+                                    const float* cos_t, const mg_skinny_desc* gemv, int32_t pos_stride, int32_t n_prefix,
+                                    const float* part, void* stream);
 
 /* K8/K17 + ImagePrefix LN: y = (x-mean)/sqrt(var+eps)*gamma+beta, fp32 stats.  Replaces nn.LayerNorm at reference
  * magma/image_prefix.py:58-60,106-107 and ln_1 / ln_f of the GPT-J blocks built at magma/language_model.py:12-45
@@ -427,6 +435,29 @@ int mg_attn_decode_fused_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_bf16* vcac
                               int32_t H, int32_t Smax, const int32_t* d_pos, int32_t rot_dim,
                               const float* sin_t, const float* cos_t, int32_t pos_stride, void* stream);
 
+/* Decode attention over ONE prefix shared by all rows (ABI 26; DESIGN.md "Shared session prefix").  Every row b <= 16 of the batch has
+ * the same n_prefix cached positions in front of its own: they are stored once, kprefix / vprefix [H, S_prefix, 256] (positions
+ * [0, n_prefix) are read), and the rows' caches [B, H, Smax, 256] hold their OWN positions only -- absolute position p >= n_prefix of a
+ * row at own index p - n_prefix.  d_pos stays absolute (the rotary angle); a d_pos[b] < n_prefix counts as n_prefix.  Two launches:
+ * mg_attn_decode_prefix_bf16: grid H x n_chunk, n_chunk = ceil(n_prefix / MG_PREFIX_CHUNK) -- a function of n_prefix alone.  Workgroup
+ *   (h, c) rotates q of all B rows of the fused qkv [B, 3*H*256] (each at its own position), scores the chunk's keys against all of
+ *   them with one set of K loads (row b = MFMA column b) and writes, per row, the chunk's maximum m, sum l = sum exp(s - m) and
+ *   o = sum exp(s - m) v (fp32, unnormalised): part[((b*H + h)*n_chunk + c)*MG_PREFIX_PART + {0..255: o, 256: m, 257: l}].  Keys >=
+ *   n_prefix of the last chunk are masked.  `part` holds B*H*n_chunk*MG_PREFIX_PART floats.  Nothing of rows >= B is read or written.
+ * mg_attn_decode_fused_shared_bf16: mg_attn_decode_fused_bf16 on the own positions -- k, v appended at own index d_pos[b] - n_prefix,
+ *   attention over own keys [0, d_pos[b] - n_prefix] -- merged with the row's partials in ascending chunk order under one maximum and
+ *   rounded to bf16 once.  A chunk whose weight underflows contributes an exact 0.
+ * Refused before any launch: B > 16, n_prefix outside [1, 4096], S_prefix < n_prefix, Smax outside [1, 4096], pos_stride != 1, null or
+ * misaligned (16-byte) pointers, rot_dim not a multiple of 8 in [0, 256]. */
+#define MG_PREFIX_CHUNK 64
+#define MG_PREFIX_PART 264
+int mg_attn_decode_prefix_bf16(const mg_bf16* qkv, const mg_bf16* kprefix, const mg_bf16* vprefix, float* part, int32_t B, int32_t H,
+                               int32_t n_prefix, int32_t S_prefix, const int32_t* d_pos, int32_t rot_dim, const float* sin_t,
+                               const float* cos_t, int32_t pos_stride, void* stream);
+int mg_attn_decode_fused_shared_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_bf16* vcache, mg_bf16* out, int32_t B, int32_t H,
+                                     int32_t Smax, const int32_t* d_pos, int32_t rot_dim, const float* sin_t, const float* cos_t,
+                                     int32_t pos_stride, int32_t n_prefix, const float* part, void* stream);
+
 /* K24 greedy (reference magma/sampling.py:96-97, temperature == 0.0): token[b] = argmax_v logits[b, v] (first maximum), int64 out;
  * optionally appends to out_tokens[b*out_ld + *d_pos_out] and bumps *d_pos.  */
 int mg_argmax_f32(const float* logits, int64_t ld, int32_t B, int32_t V, int64_t* token,
@@ -521,7 +552,12 @@ int mg_sample_finish_rows(int64_t* token, int32_t B, int32_t* state, int32_t* d_
  *   src_row[j] go to the SAME positions of live row dst_slot[j], and d_pos[slot] = pos0 + len[j]; positions below pos0 are neither
  *   read nor written.  Token, window, history column, row test, finish record and state[1] are mg_slots_admit_bf16's; one kernel
  *   serves both (mg_slots_admit_bf16 is pos0 = 0).  Refused in addition, before anything is launched: pos0 < 0, len[j] < 1,
- *   pos0 + len[j] > min(S_stage, Smax). */
+ *   pos0 + len[j] > min(S_stage, Smax).
+ * mg_slots_admit_shared_bf16 (ABI 26; DESIGN.md "Shared session prefix"): the same launch with a destination offset of its own, for a
+ *   live cache that holds the rows' own positions only.  Staged positions [pos0, pos0 + len[j]) go to live positions
+ *   [dst0, dst0 + len[j]); d_pos[slot] = pos0 + len[j], the absolute position.  Each side is checked against its own extent: refused
+ *   are pos0 outside [0, S_stage), dst0 outside [0, Smax), len[j] < 1, pos0 + len[j] > S_stage, dst0 + len[j] > Smax.  With dst0 = pos0
+ *   it is mg_slots_admit_at_bf16. */
 #define MG_STOP_LEN 0x300
 #define MG_SLOTS_MAX 16
 int mg_sample_finish_slots(int64_t* token, int32_t B, int32_t* state, int32_t* d_pos, int32_t delta, int64_t* history,
@@ -539,6 +575,12 @@ int mg_slots_admit_at_bf16(const mg_bf16* kstage, const mg_bf16* vstage, int32_t
                            int32_t* state, int32_t* d_pos, int64_t* token, int32_t* finish, int32_t* slot, int64_t* history,
                            int64_t ld_history, int32_t history_cols, const int32_t* table, int32_t n_eos, int32_t n_seq,
                            int32_t pos0, void* stream);
+int mg_slots_admit_shared_bf16(const mg_bf16* kstage, const mg_bf16* vstage, int32_t n_stage, int32_t S_stage, mg_bf16* kcache,
+                               mg_bf16* vcache, int32_t L, int32_t B, int32_t H, int32_t Smax, int32_t n, const int32_t* src_row,
+                               const int32_t* dst_slot, const int32_t* len, const int64_t* first_token, const int32_t* limit,
+                               int32_t* state, int32_t* d_pos, int64_t* token, int32_t* finish, int32_t* slot, int64_t* history,
+                               int64_t ld_history, int32_t history_cols, const int32_t* table, int32_t n_eos, int32_t n_seq,
+                               int32_t pos0, int32_t dst0, void* stream);
 
 /* Beam search (transformers' GenerationMixin._beam_search, do_sample=False, one eos id; DESIGN.md "Beam search"): three
  * enqueue-only, graph-capturable launches per token step over R = B * k rows (k = num_beams <= 16, rows sample-major).

@@ -459,6 +459,16 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AttnDecodeParams
   attn_decode_body<FUSED>(P, blockIdx.x, lds);
 }
 
+__global__ __launch_bounds__(256) void attn_decode_shared_kernel(const AttnDecodeParams P, const AttnSharedParams S) {
+  __shared__ __attribute__((aligned(16))) char lds[ATTN_DEC_LDS];
+  attn_decode_body<true, false, true>(P, blockIdx.x, lds, S);
+}
+
+__global__ __launch_bounds__(256) void attn_decode_prefix_kernel(const AttnPrefixParams P) {
+  __shared__ __attribute__((aligned(16))) char lds[ATTN_PREFIX_LDS];
+  attn_prefix_body(P, blockIdx.x, blockIdx.y, lds);
+}
+
 }  // namespace
 
 extern "C" int mg_rotary_split_bf16(const mg_bf16* qkv, int64_t ld_qkv, int32_t B, int32_t S, int32_t H, int32_t rot_dim,
@@ -598,6 +608,45 @@ extern "C" int mg_attn_decode_fused_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg
   if (!MG_ALIGNED16(qkv) || !MG_ALIGNED16(kcache) || !MG_ALIGNED16(vcache) || !MG_ALIGNED16(out)) MG_FAIL(MG_ERR_ALIGN, "mg_attn_decode_fused_bf16: pointers must be 16-byte aligned");
   AttnDecodeParams P{qkv, kcache, vcache, out, H, Smax, d_pos, rot_dim, sin_t, cos_t, 0, pos_stride};
   hipLaunchKernelGGL(attn_decode_kernel<true>, dim3(B * H), dim3(256), 0, (hipStream_t)stream, P);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+// Shared session prefix, kernel 1: the partial attention of all B rows over every chunk of the one prefix (attn_prefix_body).
+extern "C" int mg_attn_decode_prefix_bf16(const mg_bf16* qkv, const mg_bf16* kprefix, const mg_bf16* vprefix, float* part, int32_t B,
+                                          int32_t H, int32_t n_prefix, int32_t S_prefix, const int32_t* d_pos, int32_t rot_dim,
+                                          const float* sin_t, const float* cos_t, int32_t pos_stride, void* stream) {
+  const char* who = "mg_attn_decode_prefix_bf16";
+  if (B <= 0 || H <= 0 || H > 65535) MG_FAIL(MG_ERR_SHAPE, "%s: bad B / H", who);
+  if (B > 16) MG_FAIL(MG_ERR_SHAPE, "%s: a shared prefix serves at most 16 rows, got B = %d", who, B);
+  if (n_prefix < 1 || n_prefix > DEC_MAX_CTX || S_prefix < n_prefix) MG_FAIL(MG_ERR_SHAPE, "%s: need 1 <= n_prefix <= min(S_prefix, %d), got %d of %d", who, DEC_MAX_CTX, n_prefix, S_prefix);
+  if (pos_stride != 1) MG_FAIL(MG_ERR_SHAPE, "%s: the rows of a shared prefix keep one position each (pos_stride must be 1)", who);
+  if (rot_dim < 0 || rot_dim > 256 || (rot_dim & 7)) MG_FAIL(MG_ERR_SHAPE, "%s: rot_dim must be a multiple of 8 in [0,256]", who);
+  if (!qkv || !kprefix || !vprefix || !part || !d_pos || (rot_dim && (!sin_t || !cos_t))) MG_FAIL(MG_ERR_SHAPE, "%s: null pointer", who);
+  if (!MG_ALIGNED16(qkv) || !MG_ALIGNED16(kprefix) || !MG_ALIGNED16(vprefix) || !MG_ALIGNED16(part)) MG_FAIL(MG_ERR_ALIGN, "%s: pointers must be 16-byte aligned", who);
+  const int n_chunk = (n_prefix + PREFIX_CHUNK - 1) / PREFIX_CHUNK;
+  AttnPrefixParams P{qkv, kprefix, vprefix, part, B, H, n_prefix, n_chunk, S_prefix, d_pos, rot_dim, sin_t, cos_t, pos_stride};
+  hipLaunchKernelGGL(attn_decode_prefix_kernel, dim3(H, n_chunk), dim3(256), 0, (hipStream_t)stream, P);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+// Shared session prefix, kernel 2 as a launch of its own: mg_attn_decode_fused_bf16 over the rows' own positions, merged with the
+// partials of mg_attn_decode_prefix_bf16 (attn_decode_body<.., SHARED>).
+extern "C" int mg_attn_decode_fused_shared_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_bf16* vcache, mg_bf16* out, int32_t B, int32_t H,
+                                                int32_t Smax, const int32_t* d_pos, int32_t rot_dim, const float* sin_t,
+                                                const float* cos_t, int32_t pos_stride, int32_t n_prefix, const float* part,
+                                                void* stream) {
+  const char* who = "mg_attn_decode_fused_shared_bf16";
+  constexpr int DH = 256;
+  if (B <= 0 || H <= 0 || Smax <= 0 || Smax > DEC_MAX_CTX) MG_FAIL(MG_ERR_SHAPE, "%s: need 0 < Smax <= %d", who, DEC_MAX_CTX);
+  if (rot_dim < 0 || rot_dim > DH || (rot_dim & 7)) MG_FAIL(MG_ERR_SHAPE, "%s: rot_dim must be a multiple of 8 in [0,256]", who);
+  if (!qkv || !kcache || !vcache || !out || !d_pos || (rot_dim && (!sin_t || !cos_t))) MG_FAIL(MG_ERR_SHAPE, "%s: null pointer", who);
+  if (!MG_ALIGNED16(qkv) || !MG_ALIGNED16(kcache) || !MG_ALIGNED16(vcache) || !MG_ALIGNED16(out)) MG_FAIL(MG_ERR_ALIGN, "%s: pointers must be 16-byte aligned", who);
+  AttnDecodeParams P{qkv, kcache, vcache, out, H, Smax, d_pos, rot_dim, sin_t, cos_t, 0, pos_stride};
+  AttnSharedParams S;
+  if (int rc = attn_shared_check(who, P, S, B, n_prefix, part)) return rc;
+  hipLaunchKernelGGL(attn_decode_shared_kernel, dim3(B * H), dim3(256), 0, (hipStream_t)stream, P, S);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }

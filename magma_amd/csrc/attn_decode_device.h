@@ -28,11 +28,172 @@ struct AttnDecodeParams {
   int pos_stride = 0;      // position of row b = d_pos[b * pos_stride]
 };
 
+// Shared session prefix (attn_decode_body<.., SHARED = true> only; a kernel argument of its own, so that the kernels of the
+// existing entry points keep their argument block): the cache holds the rows' OWN positions, absolute position p >= n_prefix at
+// own index p - n_prefix; `part` holds the prefix partials of attn_prefix_body, n_chunk per (b, h).
+struct AttnSharedParams {
+  int n_prefix = 0, n_chunk = 0;
+  const float* part = nullptr;
+};
+
+// The rotary of 8 dims [d0, d0 + 8) of a q or k row at angle row `pos` (GPT-J: neighbouring pairs), in fp32, rounded to bf16 once.
+// One statement of it for the decode body and the prefix-partials kernel, so that both rotate q to the same bits.
+MG_DEV u32x4 rotary8_at(u32x4 v, const float* __restrict__ sin_t, const float* __restrict__ cos_t, int pos, int rot_dim, int d0) {
+  const int half_rot = rot_dim >> 1;
+  const float* sp = sin_t + (int64_t)pos * half_rot + (d0 >> 1);
+  const float* cp = cos_t + (int64_t)pos * half_rot + (d0 >> 1);
+#pragma unroll
+  for (int pi = 0; pi < 4; ++pi) {
+    const float sn = sp[pi], cs = cp[pi], x0 = bflo(v[pi]), x1 = bfhi(v[pi]);
+    v[pi] = pack2bf(x0 * cs - x1 * sn, x1 * cs + x0 * sn);
+  }
+  return v;
+}
+
+// ---------------------------------------------------------------------------
+// Shared session prefix, kernel 1 (DESIGN.md "Shared session prefix"): the partial attention of ALL B <= 16 batch rows over one
+// chunk of PREFIX_CHUNK keys of the one prefix [H, n_prefix, 256] that every row has in front of its own positions.
+// Workgroup (h, c), 256 threads.  Row b's rotated q is B-operand column b of the score MFMA (columns >= B are zero), so one set
+// of K fragment loads scores the chunk for every row; wave w takes keys [16 w, 16 w + 16) of the chunk.  Per row over the chunk:
+// m = max score, l = sum exp(s - m), o = sum exp(s - m) v in fp32, unnormalised -- PV on the VALU with fp32 weights (lane = 4 dims x
+// 16 rows of accumulators, every V element loaded once), the four waves' sums added in one fixed order.  Keys >= n_prefix of the last
+// chunk are masked (weight 0; their loads are clamped to key n_prefix - 1 and never enter a sum).  Written with plain vector stores:
+// part[((b H + h) n_chunk + c) PREFIX_PART + {0..255: o, 256: m, 257: l}].  The split depends on n_prefix alone.
+// ---------------------------------------------------------------------------
+constexpr int PREFIX_CHUNK = 64;
+constexpr int PREFIX_PART = 264;                 // floats per (b, h, chunk): 256 o, m, l, 6 unused (16-byte rows)
+constexpr int PREFIX_QLD = 256 + 8;              // LDS row stride of q in bf16 (528 B: the 16 rows start in different banks)
+constexpr int ATTN_PREFIX_LDS = 16 * PREFIX_QLD * 2 + PREFIX_CHUNK * 16 * 4 + 2 * 16 * 256 * 4;
+
+struct AttnPrefixParams {
+  const mg_bf16* qkv; const mg_bf16* kpre; const mg_bf16* vpre; float* part;
+  int B, H, n_prefix, n_chunk, Spre; const int* d_pos; int rot_dim; const float* sin_t; const float* cos_t; int pos_stride;
+};
+
+MG_DEV void attn_prefix_body(const AttnPrefixParams& P, int h, int c, char* lds) {
+  constexpr int DH = 256;
+  mg_bf16* qs = (mg_bf16*)lds;                                              // [16][PREFIX_QLD]
+  float* pT = (float*)(lds + 16 * PREFIX_QLD * 2);                          // [PREFIX_CHUNK][16]: score, then weight, of (key, row)
+  float* red = pT + PREFIX_CHUNK * 16;                                      // [2][16 rows][256]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 15, lq = lane >> 4;
+  const int B = P.B, H = P.H, n_prefix = P.n_prefix;
+  const int dmodel = H * DH;
+  // ---- q of every row, rotated at the row's own position, into LDS; rows >= B are zero and nothing of them is read ----
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int b = it * 8 + (tid >> 5), d0 = (tid & 31) * 8;
+    u32x4 v = (u32x4){0u, 0u, 0u, 0u};
+    if (b < B) {
+      v = *(const u32x4*)(P.qkv + (int64_t)b * 3 * dmodel + h * DH + d0);
+      if (d0 < P.rot_dim) v = rotary8_at(v, P.sin_t, P.cos_t, max(P.d_pos[b * P.pos_stride], n_prefix), P.rot_dim, d0);
+    }
+    *(u32x4*)(qs + b * PREFIX_QLD + d0) = v;
+  }
+  __syncthreads();
+  // ---- scores of the wave's 16 keys against the 16 rows: lane (li, lq) ends with row li, keys lq * 4 + r ----
+  const mg_bf16* kb = P.kpre + (int64_t)h * P.Spre * DH;
+  const mg_bf16* vb = P.vpre + (int64_t)h * P.Spre * DH;
+  const int k0 = c * PREFIX_CHUNK + wave * 16;                              // the wave's first key
+  {
+    const mg_bf16* kp = kb + (int64_t)min(k0 + li, n_prefix - 1) * DH + lq * 8;
+    bf16x8 kf[8];
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) kf[ks] = *(const bf16x8*)(kp + ks * 32);
+    f32x4 s = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks)
+      s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[ks], *(const bf16x8*)(qs + li * PREFIX_QLD + ks * 32 + lq * 8), s, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int t = wave * 16 + lq * 4 + r;
+      pT[t * 16 + li] = c * PREFIX_CHUNK + t < n_prefix ? s[r] * 0.0625f : -1e30f;
+    }
+  }
+  __syncthreads();
+  // ---- per row: maximum and weights over the chunk; 16 threads per row, 4 keys each ----
+  {
+    const int b = tid >> 4, j = tid & 15;
+    float sv[4], mx = -1e30f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { sv[r] = pT[(j * 4 + r) * 16 + b]; mx = fmaxf(mx, sv[r]); }
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    float sm = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float e = c * PREFIX_CHUNK + j * 4 + r < n_prefix ? __expf(sv[r] - mx) : 0.f;
+      pT[(j * 4 + r) * 16 + b] = e;
+      sm += e;
+    }
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) sm += __shfl_xor(sm, o);
+    if (j == 0 && b < B) {
+      float* pp = P.part + (((int64_t)b * H + h) * P.n_chunk + c) * PREFIX_PART + DH;
+      pp[0] = mx; pp[1] = sm;
+    }
+  }
+  __syncthreads();
+  // ---- PV: the wave's 16 keys, lane = dims [4 lane, 4 lane + 4) x 16 rows; all 16 V loads in flight at once ----
+  float acc[16][4];
+#pragma unroll
+  for (int b = 0; b < 16; ++b) { acc[b][0] = acc[b][1] = acc[b][2] = acc[b][3] = 0.f; }
+  u32x2 w[16];
+#pragma unroll
+  for (int u = 0; u < 16; ++u) w[u] = *(const u32x2*)(vb + (int64_t)min(k0 + u, n_prefix - 1) * DH + lane * 4);
+#pragma unroll
+  for (int u = 0; u < 16; ++u) {
+    const float v0 = bflo(w[u][0]), v1 = bfhi(w[u][0]), v2 = bflo(w[u][1]), v3 = bfhi(w[u][1]);
+    const float* pr = pT + (wave * 16 + u) * 16;                            // weight 0 for a masked key
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      if (g * 4 < B) {
+        const f32x4 p4 = *(const f32x4*)(pr + g * 4);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          acc[g * 4 + r][0] += p4[r] * v0; acc[g * 4 + r][1] += p4[r] * v1;
+          acc[g * 4 + r][2] += p4[r] * v2; acc[g * 4 + r][3] += p4[r] * v3;
+        }
+      }
+    }
+  }
+  // the four waves' sums, (w0 + w2) + (w1 + w3), through 32 KB of LDS; wave 0 ends with every row's o and stores rows < B
+  auto put = [&](int slot) {
+#pragma unroll
+    for (int b = 0; b < 16; ++b) *(f32x4*)(red + (slot * 16 + b) * DH + lane * 4) = (f32x4){acc[b][0], acc[b][1], acc[b][2], acc[b][3]};
+  };
+  auto add = [&](int slot) {
+#pragma unroll
+    for (int b = 0; b < 16; ++b) {
+      const f32x4 o = *(const f32x4*)(red + (slot * 16 + b) * DH + lane * 4);
+      acc[b][0] += o[0]; acc[b][1] += o[1]; acc[b][2] += o[2]; acc[b][3] += o[3];
+    }
+  };
+  if (wave >= 2) put(wave - 2);
+  __syncthreads();
+  if (wave < 2) add(wave);
+  __syncthreads();
+  if (wave == 1) put(0);
+  __syncthreads();
+  if (wave == 0) {
+    add(0);
+#pragma unroll
+    for (int b = 0; b < 16; ++b)
+      if (b < B)
+        *(f32x4*)(P.part + (((int64_t)b * H + h) * P.n_chunk + c) * PREFIX_PART + lane * 4) = (f32x4){acc[b][0], acc[b][1], acc[b][2], acc[b][3]};
+  }
+}
+
 // Device body: `bh` = (batch, head) index, `lds` = ATTN_DEC_LDS bytes of scratch (16-byte aligned).
 // COH (persistent decode step): the fused qkv row comes from other workgroups of the same launch and the context row
 // goes to others -- both through the coherent accessors of gemm_device.h.
-template <bool FUSED, bool COH = false>
-MG_DEV void attn_decode_body(const AttnDecodeParams& P, int bh, char* lds) {
+// SHARED (FUSED only; shared session prefix, kernel 2; its fields are `S`): the cache holds the row's own positions -- k, v are
+// appended at own index pos - n_prefix (a pos < n_prefix counts as n_prefix), the row attends over its own keys exactly as above,
+// and the unnormalised result (maximum m, sum l, o) is merged with the row's n_chunk prefix partials in ascending chunk order
+// under one maximum M: out = (e^(m - M) o + sum_c e^(m_c - M) o_c) / (e^(m - M) l + sum_c e^(m_c - M) l_c), rounded to bf16 once.
+template <bool FUSED, bool COH = false, bool SHARED = false>
+MG_DEV void attn_decode_body(const AttnDecodeParams& P, int bh, char* lds, const AttnSharedParams& S = AttnSharedParams{}) {
   constexpr int DH = 256;
   const mg_bf16* __restrict__ qin = P.qin;
   mg_bf16* __restrict__ kcache = P.kcache;
@@ -51,8 +212,10 @@ MG_DEV void attn_decode_body(const AttnDecodeParams& P, int bh, char* lds) {
   const int li = lane & 15, lq = lane >> 4;
   const int b = bh / H, h = bh - b * H;
   const int64_t out_off = P.ld_out ? (int64_t)b * P.ld_out + (int64_t)h * DH : (int64_t)bh * DH;
-  const int pos = d_pos[b * P.pos_stride];
-  const int ctx = min(pos + 1, min(Smax, DEC_MAX_CTX));
+  static_assert(!SHARED || (FUSED && !COH), "the shared-prefix mode is the fused, non-coherent body");
+  const int pos = SHARED ? max(d_pos[b * P.pos_stride], S.n_prefix) : d_pos[b * P.pos_stride];    // the rotary angle
+  const int own = SHARED ? min(pos - S.n_prefix, Smax - 1) : pos;                                  // the cache index of the new token
+  const int ctx = min(own + 1, min(Smax, DEC_MAX_CTX));
   mg_bf16* kb = kcache + (int64_t)bh * Smax * DH;
   mg_bf16* vb = vcache + (int64_t)bh * Smax * DH;
   if (FUSED) {
@@ -63,19 +226,10 @@ MG_DEV void attn_decode_body(const AttnDecodeParams& P, int bh, char* lds) {
       u32x4 v;
       if constexpr (COH) v = ld16_coh(qin + (int64_t)b * 3 * dmodel + which * dmodel + h * DH + d0);
       else v = *(const u32x4*)(qin + (int64_t)b * 3 * dmodel + which * dmodel + h * DH + d0);
-      if (which < 2 && d0 < rot_dim) {
-        const int half_rot = rot_dim >> 1;
-        const float* sp = sin_t + (int64_t)pos * half_rot + (d0 >> 1);
-        const float* cp = cos_t + (int64_t)pos * half_rot + (d0 >> 1);
-#pragma unroll
-        for (int pi = 0; pi < 4; ++pi) {
-          const float sn = sp[pi], cs = cp[pi], x0 = bflo(v[pi]), x1 = bfhi(v[pi]);
-          v[pi] = pack2bf(x0 * cs - x1 * sn, x1 * cs + x0 * sn);
-        }
-      }
+      if (which < 2 && d0 < rot_dim) v = rotary8_at(v, sin_t, cos_t, pos, rot_dim, d0);
       if (which == 0) *(u32x4*)(qs + d0) = v;
-      else if (which == 1) *(u32x4*)(kb + (int64_t)pos * DH + d0) = v;
-      else *(u32x4*)(vb + (int64_t)pos * DH + d0) = v;
+      else if (which == 1) *(u32x4*)(kb + (int64_t)own * DH + d0) = v;
+      else *(u32x4*)(vb + (int64_t)own * DH + d0) = v;
     }
     __threadfence_block();
   } else {
@@ -141,6 +295,22 @@ MG_DEV void attn_decode_body(const AttnDecodeParams& P, int bh, char* lds) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) red[wave * DH + lane * 4 + r] = acc[r];
   __syncthreads();
+  if constexpr (SHARED) {
+    // merge with the prefix partials: thread = one dim; m, l of a chunk are the same address for every thread
+    const float* pp = S.part + (int64_t)bh * S.n_chunk * PREFIX_PART;
+    float M = mx;
+    for (int c = 0; c < S.n_chunk; ++c) M = fmaxf(M, pp[c * PREFIX_PART + DH]);
+    const float w_own = __expf(mx - M);
+    float num = w_own * (red[tid] + red[DH + tid] + red[2 * DH + tid] + red[3 * DH + tid]);
+    float den = w_own * (wred[4] + wred[5] + wred[6] + wred[7]);
+    for (int c = 0; c < S.n_chunk; ++c) {
+      const float wc = __expf(pp[c * PREFIX_PART + DH] - M);      // underflows to an exact 0; o_c and l_c are finite
+      num += wc * pp[c * PREFIX_PART + tid];
+      den += wc * pp[c * PREFIX_PART + DH + 1];
+    }
+    out[out_off + tid] = f2bf(num / den);
+    return;
+  }
   const float v = (red[tid] + red[DH + tid] + red[2 * DH + tid] + red[3 * DH + tid]) * inv;
   if constexpr (COH) {      // four dims per lane -> one 8-byte coherent store (lanes 0..63 of wave 0)
     __syncthreads();
@@ -155,3 +325,14 @@ MG_DEV void attn_decode_body(const AttnDecodeParams& P, int bh, char* lds) {
   }
 }
 
+// The refusals the shared-prefix entry points have in common (before any launch); fills `sh`.
+static inline int attn_shared_check(const char* who, const AttnDecodeParams& ap, AttnSharedParams& sh, int32_t B, int32_t n_prefix,
+                                    const float* part) {
+  if (B > 16) MG_FAIL(MG_ERR_SHAPE, "%s: a shared prefix serves at most 16 rows, got B = %d", who, B);
+  if (n_prefix < 1 || n_prefix > DEC_MAX_CTX) MG_FAIL(MG_ERR_SHAPE, "%s: need 1 <= n_prefix <= %d, got %d", who, DEC_MAX_CTX, n_prefix);
+  if (ap.pos_stride != 1) MG_FAIL(MG_ERR_SHAPE, "%s: the rows of a shared prefix keep one position each (pos_stride must be 1)", who);
+  if (!part) MG_FAIL(MG_ERR_SHAPE, "%s: null pointer", who);
+  if (!MG_ALIGNED16(part)) MG_FAIL(MG_ERR_ALIGN, "%s: pointers must be 16-byte aligned", who);
+  sh.n_prefix = n_prefix; sh.n_chunk = (n_prefix + PREFIX_CHUNK - 1) / PREFIX_CHUNK; sh.part = part;
+  return MG_OK;
+}

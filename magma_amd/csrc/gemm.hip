@@ -1235,6 +1235,16 @@ __global__ __launch_bounds__(256) void decode_attn_gemv_kernel(const AttnDecodeP
   else skinny_body<4, KC, 1, WT, false, NoWait, PIPE>(sp, blockIdx.x - n_attn, lds);
 }
 
+// The same co-launch with the attention workgroups in the shared-prefix mode of the body (mg_decode_attn_gemv_shared_bf16).
+template <int KC, int WT = WT_BF16>
+__global__ __launch_bounds__(256) void decode_attn_shared_gemv_kernel(const AttnDecodeParams ap, const AttnSharedParams sh, int n_attn,
+                                                                      const SkinnyParams sp) {
+  constexpr int LDS = ATTN_DEC_LDS > skinny_lds_bytes<4, 1>() ? ATTN_DEC_LDS : skinny_lds_bytes<4, 1>();
+  __shared__ __attribute__((aligned(16))) char lds[LDS];
+  if ((int)blockIdx.x < n_attn) attn_decode_body<true, false, true>(ap, blockIdx.x, lds, sh);
+  else skinny_body<4, KC, 1, WT, false, NoWait, false>(sp, blockIdx.x - n_attn, lds);
+}
+
 constexpr int MG_DECODE_PIPE_DEFAULT = 0;
 }  // namespace
 
@@ -1413,6 +1423,43 @@ extern "C" int mg_decode_attn_gemv_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_
   else if (sp.ksteps % 16 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<4>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
   else if (sp.ksteps % 4 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<1>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
   else MG_FAIL(MG_ERR_UNSUPPORTED, "mg_decode_attn_gemv_bf16: K of the GEMV must be a multiple of 128");
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+// mg_decode_attn_gemv_bf16 with the attention workgroups in the shared-prefix mode (mg_attn_decode_fused_shared_bf16): the same
+// GEMV variants for the same operands, so the GEMV's bits are those of the unshared launch.
+extern "C" int mg_decode_attn_gemv_shared_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_bf16* vcache, mg_bf16* attn_out,
+                                               int64_t ld_attn_out, int32_t B, int32_t H, int32_t Smax, const int32_t* d_pos,
+                                               int32_t rot_dim, const float* sin_t, const float* cos_t, const mg_skinny_desc* gemv,
+                                               int32_t pos_stride, int32_t n_prefix, const float* part, void* stream) {
+  const char* who = "mg_decode_attn_gemv_shared_bf16";
+  if (B <= 0 || H <= 0 || Smax <= 0 || Smax > DEC_MAX_CTX) MG_FAIL(MG_ERR_SHAPE, "%s: need 0 < Smax <= %d", who, DEC_MAX_CTX);
+  if (rot_dim < 0 || rot_dim > 256 || (rot_dim & 7)) MG_FAIL(MG_ERR_SHAPE, "%s: rot_dim must be a multiple of 8 in [0,256]", who);
+  if (!qkv || !kcache || !vcache || !attn_out || !d_pos || !gemv || (rot_dim && (!sin_t || !cos_t))) MG_FAIL(MG_ERR_SHAPE, "%s: null pointer", who);
+  if (!MG_ALIGNED16(qkv) || !MG_ALIGNED16(kcache) || !MG_ALIGNED16(vcache) || !MG_ALIGNED16(attn_out)) MG_FAIL(MG_ERR_ALIGN, "%s: pointers must be 16-byte aligned", who);
+  SkinnyParams sp;
+  if (int rc = fill_skinny(gemv, sp, "mg_decode_attn_gemv_shared_bf16(gemv)")) return rc;
+  if (ld_attn_out != 0 && (ld_attn_out < (int64_t)H * 256 || (ld_attn_out & 7))) MG_FAIL(MG_ERR_SHAPE, "%s: ld_attn_out must be 0 or a multiple of 8 >= H*256", who);
+  AttnDecodeParams ap{qkv, kcache, vcache, attn_out, H, Smax, d_pos, rot_dim, sin_t, cos_t, ld_attn_out, pos_stride};
+  AttnSharedParams sh;
+  if (int rc = attn_shared_check(who, ap, sh, B, n_prefix, part)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int n_attn = B * H, grid = n_attn + sp.ntiles;
+  if (sp.w_scale && sp.ksteps % 64 != 0) MG_FAIL(MG_ERR_UNSUPPORTED, "%s: fp8 weights need K %% 2048 == 0 here", who);
+#define MG_DAS(K_, W_) hipLaunchKernelGGL((decode_attn_shared_gemv_kernel<K_, W_>), dim3(grid), dim3(256), 0, s, ap, sh, n_attn, sp)
+  if (sp.w_mx4) {
+    if (sp.ksteps % 64 == 0) MG_DAS(16, WT_MX4);
+    else if (sp.ksteps % 32 == 0) MG_DAS(8, WT_MX4);
+    else MG_DAS(4, WT_MX4);
+  } else if (sp.w_scale) MG_DAS(16, WT_FP8);
+  else if (sp.pk_lo && sp.ksteps % 64 == 0) MG_DAS(16, WT_PK);
+  else if (sp.pk_lo && sp.ksteps % 16 == 0) MG_DAS(4, WT_PK);
+  else if (sp.ksteps % 64 == 0) MG_DAS(16, WT_BF16);
+  else if (sp.ksteps % 16 == 0) MG_DAS(4, WT_BF16);
+  else if (sp.ksteps % 4 == 0) MG_DAS(1, WT_BF16);
+  else MG_FAIL(MG_ERR_UNSUPPORTED, "%s: K of the GEMV must be a multiple of 128", who);
+#undef MG_DAS
   MG_CHECK_LAUNCH();
   return MG_OK;
 }

@@ -509,9 +509,11 @@ __global__ void sample_finish_slots_kernel(int64_t* __restrict__ tok, int B, int
 // [pos0, pos0 + len_j) of layer l, head h from staging row src_row[j] to the same positions of live row dst_slot[j] -- len_j * 512
 // contiguous bytes each, as 16-byte vectors, all offsets 64-bit --; thread 0 of block (0, j, 0) installs request j's bookkeeping
 // and runs the row test on its first token.  pos0 = 0: mg_slots_admit_bf16; pos0 = the session prefix's rows: mg_slots_admit_at_bf16.
+// dst0: the live position staged position pos0 goes to -- pos0 for those two; mg_slots_admit_shared_bf16 (a live cache that holds the
+// rows' own positions only) passes its own, and d_pos stays the absolute pos0 + len.
 struct SlotsAdmitArgs {
   const uint4* kstage; const uint4* vstage; uint4* kcache; uint4* vcache;
-  int n_stage, H, S_stage, B, Smax, pos0;
+  int n_stage, H, S_stage, B, Smax, pos0, dst0;
   int32_t src_row[MG_SLOTS_MAX], dst_slot[MG_SLOTS_MAX], len[MG_SLOTS_MAX], limit[MG_SLOTS_MAX];
   const int64_t* first_token;
   int32_t* state; int32_t* d_pos; int64_t* token; int32_t* finish; int32_t* slot;
@@ -523,7 +525,7 @@ __global__ void slots_admit_kernel(SlotsAdmitArgs a) {
   const int h = blockIdx.x, j = blockIdx.y, l = blockIdx.z;
   const int64_t n_vec = (int64_t)a.len[j] * 32;                 // 256 bf16 = 32 vectors of 16 bytes per position
   const int64_t src = ((((int64_t)l * a.n_stage + a.src_row[j]) * a.H + h) * a.S_stage + a.pos0) * 32;
-  const int64_t dst = ((((int64_t)l * a.B + a.dst_slot[j]) * a.H + h) * a.Smax + a.pos0) * 32;
+  const int64_t dst = ((((int64_t)l * a.B + a.dst_slot[j]) * a.H + h) * a.Smax + a.dst0) * 32;
   for (int64_t i = threadIdx.x; i < n_vec; i += blockDim.x) {
     a.kcache[dst + i] = a.kstage[src + i];
     a.vcache[dst + i] = a.vstage[src + i];
@@ -627,13 +629,13 @@ extern "C" int mg_sample_finish_slots(int64_t* token, int32_t B, int32_t* state,
   return MG_OK;
 }
 
-// Both admission entry points: the checks and the one launch.
+// The admission entry points: the checks and the one launch.
 static int slots_admit_launch(const char* who, const mg_bf16* kstage, const mg_bf16* vstage, int32_t n_stage, int32_t S_stage,
                               mg_bf16* kcache, mg_bf16* vcache, int32_t L, int32_t B, int32_t H, int32_t Smax, int32_t n,
                               const int32_t* src_row, const int32_t* dst_slot, const int32_t* len, const int64_t* first_token,
                               const int32_t* limit, int32_t* state, int32_t* d_pos, int64_t* token, int32_t* finish, int32_t* slot,
                               int64_t* history, int64_t ld_history, int32_t history_cols, const int32_t* table, int32_t n_eos,
-                              int32_t n_seq, int32_t pos0, void* stream) {
+                              int32_t n_seq, int32_t pos0, int32_t dst0, void* stream) {
   if (!kstage || !vstage || !kcache || !vcache || !src_row || !dst_slot || !len || !first_token || !limit || !state || !d_pos || !token ||
       !finish || !slot || !history || !table)
     MG_FAIL(MG_ERR_SHAPE, "%s: null pointer", who);
@@ -649,9 +651,10 @@ static int slots_admit_launch(const char* who, const mg_bf16* kstage, const mg_b
     MG_FAIL(MG_ERR_ALIGN, "%s: int32 buffers must be 4-byte aligned", who);
   if (((uintptr_t)token | (uintptr_t)history | (uintptr_t)first_token) & 7) MG_FAIL(MG_ERR_ALIGN, "%s: token buffers must be 8-byte aligned", who);
   SlotsAdmitArgs a{};
-  const int pos_max = S_stage < Smax ? S_stage : Smax;
-  if (pos0 < 0 || pos0 >= pos_max) MG_FAIL(MG_ERR_SHAPE, "%s: pos0 = %d outside [0, %d)", who, pos0, pos_max);
-  const int len_max = pos_max - pos0;
+  // each side against its own extent (equal offsets: pos0 inside [0, min(S_stage, Smax)), as ever)
+  if (pos0 < 0 || pos0 >= S_stage) MG_FAIL(MG_ERR_SHAPE, "%s: pos0 = %d outside [0, %d)", who, pos0, S_stage);
+  if (dst0 < 0 || dst0 >= Smax) MG_FAIL(MG_ERR_SHAPE, "%s: %s = %d outside [0, %d)", who, dst0 == pos0 ? "pos0" : "dst0", dst0, Smax);
+  const int len_max = S_stage - pos0 < Smax - dst0 ? S_stage - pos0 : Smax - dst0;
   for (int j = 0; j < n; ++j) {
     if (src_row[j] < 0 || src_row[j] >= n_stage) MG_FAIL(MG_ERR_SHAPE, "%s: src_row[%d] = %d outside [0, %d)", who, j, src_row[j], n_stage);
     if (dst_slot[j] < 0 || dst_slot[j] >= B) MG_FAIL(MG_ERR_SHAPE, "%s: dst_slot[%d] = %d outside [0, %d)", who, j, dst_slot[j], B);
@@ -661,7 +664,7 @@ static int slots_admit_launch(const char* who, const mg_bf16* kstage, const mg_b
     a.src_row[j] = src_row[j]; a.dst_slot[j] = dst_slot[j]; a.len[j] = len[j]; a.limit[j] = limit[j];
   }
   a.kstage = (const uint4*)kstage; a.vstage = (const uint4*)vstage; a.kcache = (uint4*)kcache; a.vcache = (uint4*)vcache;
-  a.n_stage = n_stage; a.H = H; a.S_stage = S_stage; a.B = B; a.Smax = Smax; a.pos0 = pos0;
+  a.n_stage = n_stage; a.H = H; a.S_stage = S_stage; a.B = B; a.Smax = Smax; a.pos0 = pos0; a.dst0 = dst0;
   a.first_token = first_token; a.state = state; a.d_pos = d_pos; a.token = token; a.finish = finish; a.slot = slot;
   a.history = history; a.ld_hist = ld_history; a.hist_cols = history_cols; a.table = table; a.n_eos = n_eos; a.n_seq = n_seq;
   hipLaunchKernelGGL(slots_admit_kernel, dim3(H, n, L), dim3(256), 0, (hipStream_t)stream, a);
@@ -677,7 +680,7 @@ extern "C" int mg_slots_admit_bf16(const mg_bf16* kstage, const mg_bf16* vstage,
                                    void* stream) {
   return slots_admit_launch("mg_slots_admit_bf16", kstage, vstage, n_stage, S_stage, kcache, vcache, L, B, H, Smax, n, src_row, dst_slot,
                             len, first_token, limit, state, d_pos, token, finish, slot, history, ld_history, history_cols, table, n_eos,
-                            n_seq, 0, stream);
+                            n_seq, 0, 0, stream);
 }
 
 extern "C" int mg_slots_admit_at_bf16(const mg_bf16* kstage, const mg_bf16* vstage, int32_t n_stage, int32_t S_stage, mg_bf16* kcache,
@@ -688,7 +691,19 @@ extern "C" int mg_slots_admit_at_bf16(const mg_bf16* kstage, const mg_bf16* vsta
                                       int32_t pos0, void* stream) {
   return slots_admit_launch("mg_slots_admit_at_bf16", kstage, vstage, n_stage, S_stage, kcache, vcache, L, B, H, Smax, n, src_row,
                             dst_slot, len, first_token, limit, state, d_pos, token, finish, slot, history, ld_history, history_cols,
-                            table, n_eos, n_seq, pos0, stream);
+                            table, n_eos, n_seq, pos0, pos0, stream);
+}
+
+extern "C" int mg_slots_admit_shared_bf16(const mg_bf16* kstage, const mg_bf16* vstage, int32_t n_stage, int32_t S_stage, mg_bf16* kcache,
+                                          mg_bf16* vcache, int32_t L, int32_t B, int32_t H, int32_t Smax, int32_t n,
+                                          const int32_t* src_row, const int32_t* dst_slot, const int32_t* len,
+                                          const int64_t* first_token, const int32_t* limit, int32_t* state, int32_t* d_pos,
+                                          int64_t* token, int32_t* finish, int32_t* slot, int64_t* history, int64_t ld_history,
+                                          int32_t history_cols, const int32_t* table, int32_t n_eos, int32_t n_seq, int32_t pos0,
+                                          int32_t dst0, void* stream) {
+  return slots_admit_launch("mg_slots_admit_shared_bf16", kstage, vstage, n_stage, S_stage, kcache, vcache, L, B, H, Smax, n, src_row,
+                            dst_slot, len, first_token, limit, state, d_pos, token, finish, slot, history, ld_history, history_cols,
+                            table, n_eos, n_seq, pos0, dst0, stream);
 }
 
 // ================================================================================================================================

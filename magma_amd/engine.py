@@ -89,6 +89,11 @@ class KVCache:
         # token history int64 [B, ring_cols] of a slot session (SlotSession sets ring_cols, SelectionPlan.arm allocates); their
         # addresses and ring_cols are launch arguments of the captured step
         self.slot_table, self.ring, self.ring_cols = None, None, 0
+        # shared session prefix (DESIGN.md "Shared session prefix"; SlotSession sets it): ONE copy of the K / V of prefix_P positions,
+        # [L, 1, H, prefix_P, 256], in front of every row -- k / v then hold the rows' OWN positions, absolute position p at own index
+        # p - prefix_P, while d_pos and pos stay absolute.  None / 0: every position of a row is its own
+        self.prefix_k = self.prefix_v = None
+        self.prefix_P = 0
 
     def alloc_trie(self, n_ints: int):
         """The constraint's buffers for a table of ``n_ints`` (kept when it fits); steps captured on other buffers are dropped."""
@@ -1051,6 +1056,9 @@ class LMEngine(TokenSelection):
         st.token = torch.zeros(B, dtype=torch.int64, device=dev)
         st.graphs = {}             # StepKey (SelectionPlan.graph_key) -> captured hipGraph
         st.steps = 0
+        # shared session prefix: the partials every block's prefix launch leaves for its attention launch (one buffer: the launches
+        # of a step are ordered), (prefix_P, buffer) as the attention launches take it
+        st.shared = (cache.prefix_P, ops.prefix_part(B, self.H, cache.prefix_P, dev)) if cache.prefix_P else None
         return st
 
     def _decode_step(self, cache: KVCache, st, plan: SelectionPlan, feed_back: bool = False):
@@ -1092,9 +1100,19 @@ class LMEngine(TokenSelection):
         ops.gemm_skinny(x, src.dec_in, out=st.qkv, ln_fold=(src.dec_in.colsum, self.d, self.eps),
                         split=(3 * self.d, st.h, ops.MG_ACT_GELU_NEW, src.dec_in.bias_b), variant=self._dec_in_variant)
 
+    def _attn_prefix(self, cache, st, li):
+        # shared session prefix, kernel 1: every row's partial attention over the one prefix, for the attention launch that follows
+        ops.attn_decode_prefix(st.qkv, cache.prefix_k[li, 0], cache.prefix_v[li, 0], st.shared[1], cache.B, self.H, cache.prefix_P,
+                               cache.d_pos, self.rot, self.sin_t, self.cos_t, pos_stride=cache.pos_stride)
+
     def _attn_gemv(self, cache, st, li, ctx, gemv):
         # attention workgroups + one GEMV's workgroups in one grid (they are independent branches of the parallel block; the
         # latency-bound attention hides under the weight stream)
+        if st.shared is not None:
+            self._attn_prefix(cache, st, li)
+            ops.decode_attn_gemv(st.qkv, cache.k[li], cache.v[li], ctx, cache.B, self.H, cache.d_pos, self.rot, self.sin_t,
+                                 self.cos_t, gemv, pos_stride=cache.pos_stride, shared=st.shared)
+            return
         ops.decode_attn_gemv(st.qkv, cache.k[li], cache.v[li], ctx, cache.B, self.H, cache.d_pos, self.rot, self.sin_t, self.cos_t,
                              gemv, pos_stride=cache.pos_stride)
 
@@ -1143,8 +1161,13 @@ class LMEngine(TokenSelection):
         G = ops.gemm if wide else ops.gemm_skinny
         if not wide:
             self._dec_in(st, src, x)
-        ops.attn_decode_fused(st.qkv, cache.k[li], cache.v[li], st.ctx, cache.B, self.H, cache.d_pos, self.rot,
-                              self.sin_t, self.cos_t, pos_stride=cache.pos_stride)
+        if st.shared is not None:
+            self._attn_prefix(cache, st, li)
+            ops.attn_decode_fused(st.qkv, cache.k[li], cache.v[li], st.ctx, cache.B, self.H, cache.d_pos, self.rot,
+                                  self.sin_t, self.cos_t, pos_stride=cache.pos_stride, shared=st.shared)
+        else:
+            ops.attn_decode_fused(st.qkv, cache.k[li], cache.v[li], st.ctx, cache.B, self.H, cache.d_pos, self.rot,
+                                  self.sin_t, self.cos_t, pos_stride=cache.pos_stride)
         a = G(st.ctx, src.out, out=st.a)
         par = ly.mlp_par is not None or ly.attn_par is not None
         if par and not wide:      # parallel adapters read ln_1(x): the one GEMV-step configuration that needs the LayerNorm as a tensor
@@ -1239,7 +1262,7 @@ class LMEngine(TokenSelection):
         if plan is None:
             plan = self.selection_plan(sampling=sampling, beam=beam, processors=processors, stop=stop, logprobs=logprobs,
                                        constraint=constraint, guidance=guidance, vocab=self.V)
-        if cache.pos >= cache.Smax:
+        if cache.pos - cache.prefix_P >= cache.Smax:
             raise ValueError(f"KV cache full (Smax={cache.Smax}); pass a larger cache_hint / max_steps")
         if cache.B > 16:
             use_graph = False       # the tile-GEMM step of large batches is launched eagerly (split-K scratch is per stream)
@@ -1382,7 +1405,11 @@ class SlotSession:
     every live slot and every staging row ONCE, at set-up (plain copies, as KVCache.expand); an admission pass then runs the
     cached-append prefill of LMEngine.extend over the same fixed (admit_rows, S_stage) rows behind them -- every staging row's
     write position is reset to P on the device first -- and ops.slots_admit(pos0=P) moves positions [P, P + len) only, so a slot
-    keeps its prefix over any number of occupants.  Nothing is ever re-allocated: the captured step stays valid."""
+    keeps its prefix over any number of occupants.  Nothing is ever re-allocated: the captured step stays valid.
+    ``share_prefix`` (DESIGN.md "Shared session prefix"): the live cache holds the rows' OWN positions only, slots x
+    ceil64(max_prompt + max_new) -- it carries ONE copy of the prefix (KVCache.prefix_k / prefix_v) that every block's prefix
+    launch reads for all rows --, ops.slots_admit(pos0=P, dst0=0) moves staged positions [P, P + len) to own indices [0, len), and
+    every d_pos starts at P.  The staging rows keep their own copies: admission is as above."""
 
     @staticmethod
     def admit_counter(n_pass: int) -> int:
@@ -1405,7 +1432,7 @@ class SlotSession:
         return out
 
     def __init__(self, engine: "LMEngine", plan: SelectionPlan, *, slots: int, max_new: int, max_prompt: int, every: int,
-                 admit_rows: int, seed: Optional[int] = None, prefix=None):
+                 admit_rows: int, seed: Optional[int] = None, prefix=None, share_prefix: bool = False):
         if not plan.slots or plan.stop is None:
             raise ValueError("a slot session runs under a plan built with slots=True and per-row stopping")
         if not 1 <= slots <= ops.SLOTS_MAX or not 1 <= admit_rows <= slots or max_new < 1 or max_prompt < 1 or every < 1:
@@ -1413,13 +1440,21 @@ class SlotSession:
         n_pos = engine.cfg.max_position_embeddings
         self.S_stage = ops.ceil_to(max_prompt, 64)
         self.P = P = self.prefix_rows(engine, prefix)
+        if share_prefix and not P:
+            raise ValueError("share_prefix=True needs a prefix: there is nothing to share")
+        self.shared = bool(share_prefix)
         if P + max_prompt + max_new > n_pos or P + self.S_stage > n_pos:
             raise ValueError((f"a prefix of {P} rows + " if P else "") + f"max_prompt = {max_prompt} (staged as {self.S_stage} rows) + "
                              f"max_new_tokens = {max_new} exceeds max_position_embeddings = {n_pos}")
         dev = engine.device
         self.engine, self.plan, self.B, self.every, self.n_admit = engine, plan, slots, every, admit_rows
         self.max_new, self.max_prompt = max_new, max_prompt
-        self.cache = cache = KVCache(engine.L, slots, engine.H, ops.ceil_to(P + max_prompt + max_new, 64), dev, ragged=True)
+        self.cache = cache = KVCache(engine.L, slots, engine.H, ops.ceil_to((0 if self.shared else P) + max_prompt + max_new, 64), dev,
+                                     ragged=True)
+        if self.shared:         # before the decode state: it sizes the partials scratch from the cache
+            cache.prefix_P = P
+            cache.prefix_k = torch.empty(engine.L, 1, engine.H, P, 256, dtype=BF16, device=dev)
+            cache.prefix_v = torch.empty(engine.L, 1, engine.H, P, 256, dtype=BF16, device=dev)
         self.stage = KVCache(engine.L, admit_rows, engine.H, P + self.S_stage, dev, ragged=True)
         self.stage_in = torch.zeros(admit_rows, self.S_stage, engine.d, dtype=BF16, device=dev)
         self.first = torch.zeros(admit_rows, dtype=torch.int64, device=dev)
@@ -1436,9 +1471,9 @@ class SlotSession:
         if self.st.refusal is not None:
             raise NotImplementedError(self.st.refusal)
         plan.arm(cache, self.st, first=True)
-        # every slot starts finished and idle at position 0
+        # every slot starts finished and idle at position 0 (shared prefix: at P, own index 0)
         cache.finish.copy_(torch.tensor([[0, ops.STOP_LEN]] * slots, dtype=torch.int32), non_blocking=True)
-        cache.d_pos.zero_()
+        cache.d_pos.fill_(P if self.shared else 0)
         self.steps = 0                  # token steps enqueued: the device's state[0] is 1 + steps
         self.occ = [None] * slots       # per slot: (request index, begin column, prompt length, limit, steps at admission)
         if P:
@@ -1480,7 +1515,10 @@ class SlotSession:
         if not isinstance(prefix, KVCache):
             lens = torch.tensor([P], dtype=torch.int64)
             _, prefix, _ = self.engine.prefill(prefix[None].to(self.engine.device), 0, lengths=lens)
-        for own in (self.cache, self.stage):
+        if self.shared:         # the live side keeps the one copy
+            self.cache.prefix_k.copy_(prefix.k[:, :, :, :P])
+            self.cache.prefix_v.copy_(prefix.v[:, :, :, :P])
+        for own in (self.stage,) if self.shared else (self.cache, self.stage):
             own.k[:, :, :, :P].copy_(prefix.k[:, :, :, :P])
             own.v[:, :, :, :P].copy_(prefix.v[:, :, :, :P])
 
@@ -1517,7 +1555,7 @@ class SlotSession:
         stop = self.plan.stop
         ops.slots_admit(self.stage.k, self.stage.v, cache.k, cache.v, list(range(n)), slots, lens[:n], self.first,
                         [it[2] for it in batch], cache.sample_state, cache.d_pos, self.st.token, cache.finish, cache.slot_table,
-                        cache.ring, cache.stop_table, len(stop[0]), len(stop[1]), pos0=self.P)
+                        cache.ring, cache.stop_table, len(stop[0]), len(stop[1]), pos0=self.P, dst0=0 if self.shared else None)
         for j, (index, _, limit) in enumerate(batch):
             self.occ[slots[j]] = (index, self.steps % self.Hc, lens[j], limit, self.steps)
 

@@ -19,7 +19,7 @@ MG_A_DENSE, MG_A_CONV3X3 = 0, 1
 MG_AUX_NONE, MG_AUX_RELU_GATE, MG_AUX_GELU_GRAD, MG_AUX_MUL, MG_AUX_QUICK_GELU_GRAD = 0, 1, 2, 3, 4
 
 
-ABI_VERSION = 25    # include/magma_hip.h MG_ABI_VERSION
+ABI_VERSION = 26    # include/magma_hip.h MG_ABI_VERSION
 
 
 class MagmaHipError(RuntimeError):
@@ -99,6 +99,8 @@ SYMBOLS = {
     "mg_gemm_skinny2_bf16": (C.c_int, [C.POINTER(SkinnyDesc), C.POINTER(SkinnyDesc), _vp]),
     "mg_decode_attn_gemv_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _vp,
                                           C.POINTER(SkinnyDesc), _i32, _vp]),
+    "mg_decode_attn_gemv_shared_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _vp,
+                                                 C.POINTER(SkinnyDesc), _i32, _i32, _vp, _vp]),
     "mg_comm_unique_id": (C.c_int, [_vp]),
     "mg_comm_init": (C.c_int, [C.POINTER(C.c_void_p), _vp, _i32, _i32]),
     "mg_comm_allreduce_sum": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
@@ -120,6 +122,8 @@ SYMBOLS = {
     "mg_attn_prefill_tree_bf16": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp]),
     "mg_rotary_split_at_bf16": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "mg_attn_decode_fused_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp]),
+    "mg_attn_decode_prefix_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp]),
+    "mg_attn_decode_fused_shared_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
     "mg_argmax_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp]),
     "mg_advance_pos": (C.c_int, [_vp, _i32, _i32, _i32, _vp]),
     "mg_sample_f32": (C.c_int, [_vp, _i64, _i32, _i32, _f32, _i32, C.c_double, _vp, _vp, _vp, _vp, _i64, _vp]),
@@ -133,6 +137,8 @@ SYMBOLS = {
                                       _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp]),
     "mg_slots_admit_at_bf16": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                          _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "mg_slots_admit_shared_bf16": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                             _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "mg_beam_topk_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     "mg_beam_topk_scores_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     "mg_token_logprobs_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),

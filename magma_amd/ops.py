@@ -490,13 +490,22 @@ def _pos_stride(d_pos: torch.Tensor, B: int, pos_stride: int) -> int:
     return pos_stride
 
 
-def decode_attn_gemv(qkv, kcache, vcache, attn_out, B, H, d_pos, rot_dim, sin_t, cos_t, gemv: tuple, *, pos_stride: int = 0):
+def decode_attn_gemv(qkv, kcache, vcache, attn_out, B, H, d_pos, rot_dim, sin_t, cos_t, gemv: tuple, *, pos_stride: int = 0,
+                     shared=None):
     """Decode attention (rotary + append + attend) co-launched with one independent GEMV
-    gemv = (x, w, out, kwargs).  ``pos_stride=1``: row b writes / attends at its own position d_pos[b]."""
+    gemv = (x, w, out, kwargs).  ``pos_stride=1``: row b writes / attends at its own position d_pos[b].
+    ``shared`` = (n_prefix, part): the attention runs in the shared-prefix mode (attn_decode_fused) -- another entry point."""
     _need_gpu(qkv)
     ps = _pos_stride(d_pos, B, pos_stride)
     d, og = skinny_desc(gemv[0], gemv[1], gemv[2], **gemv[3])
     assert attn_out.ndim == 2 and attn_out.stride(1) == 1 and attn_out.shape[1] == H * 256   # a column range of a wider row is fine
+    if shared is not None:
+        n_prefix, part = _shared_part(shared, B, H)
+        check(L.load().mg_decode_attn_gemv_shared_bf16(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), attn_out.data_ptr(),
+                                                       attn_out.stride(0), B, H, kcache.shape[2], d_pos.data_ptr(), rot_dim,
+                                                       sin_t.data_ptr(), cos_t.data_ptr(), C.byref(d), ps, n_prefix, part.data_ptr(),
+                                                       _stream()), "mg_decode_attn_gemv_shared_bf16")
+        return attn_out, og
     check(L.load().mg_decode_attn_gemv_bf16(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), attn_out.data_ptr(),
                                             attn_out.stride(0), B, H, kcache.shape[2], d_pos.data_ptr(), rot_dim, sin_t.data_ptr(),
                                             cos_t.data_ptr(), C.byref(d), ps, _stream()), "mg_decode_attn_gemv_bf16")
@@ -752,10 +761,55 @@ def attn_decode(q, kcache, vcache, out, B, H, d_pos, *, pos_stride: int = 0):
     return out
 
 
-def attn_decode_fused(qkv, kcache, vcache, out, B, H, d_pos, rot_dim, sin_t, cos_t, *, pos_stride: int = 0):
-    """rotary(q,k) + KV append at pos_b + attention over [0, pos_b], one launch; pos_b = d_pos[b * pos_stride]."""
+PREFIX_CHUNK, PREFIX_PART = 64, 264                                     # include/magma_hip.h MG_PREFIX_CHUNK, MG_PREFIX_PART
+
+
+def prefix_chunks(n_prefix: int) -> int:
+    """Chunks the shared-prefix kernels cut a prefix of ``n_prefix`` positions into: a function of n_prefix alone."""
+    return -(-int(n_prefix) // PREFIX_CHUNK)
+
+
+def prefix_part(B: int, H: int, n_prefix: int, device) -> torch.Tensor:
+    """The partials buffer of attn_decode_prefix for B rows: fp32 [B, H, n_chunk, PREFIX_PART] = (o[256], m, l, unused)."""
+    return torch.zeros(B, H, prefix_chunks(n_prefix), PREFIX_PART, dtype=torch.float32, device=device)
+
+
+def _shared_part(shared, B, H):
+    n_prefix, part = shared
+    assert part.dtype == torch.float32 and part.is_contiguous()
+    if part.numel() < B * H * prefix_chunks(max(int(n_prefix), 1)) * PREFIX_PART:
+        raise ValueError(f"the partials buffer holds {part.numel()} floats, {B} rows x {H} heads behind {n_prefix} positions need more")
+    return int(n_prefix), part
+
+
+def attn_decode_prefix(qkv, kprefix, vprefix, part, B, H, n_prefix, d_pos, rot_dim, sin_t, cos_t, *, pos_stride: int = 1):
+    """Shared session prefix, kernel 1 (mg_attn_decode_prefix_bf16): the partial attention (m, l, o per chunk of PREFIX_CHUNK keys)
+    of all B <= 16 rows of the fused ``qkv`` over positions [0, n_prefix) of the ONE prefix ``kprefix`` / ``vprefix``
+    [H, S_prefix, 256], into ``part`` (prefix_part).  Row b's q is rotated at max(d_pos[b], n_prefix)."""
+    _need_gpu(qkv, kprefix, vprefix, part)
+    ps = _pos_stride(d_pos, B, pos_stride)
+    assert kprefix.dtype == BF16 and kprefix.is_contiguous() and kprefix.ndim == 3 and kprefix.shape[2] == 256
+    assert vprefix.dtype == BF16 and vprefix.is_contiguous() and vprefix.shape == kprefix.shape and kprefix.shape[0] == H
+    n_prefix, part = _shared_part((n_prefix, part), B, H)
+    check(L.load().mg_attn_decode_prefix_bf16(qkv.data_ptr(), kprefix.data_ptr(), vprefix.data_ptr(), part.data_ptr(), B, H, n_prefix,
+                                              kprefix.shape[1], d_pos.data_ptr(), rot_dim, sin_t.data_ptr(), cos_t.data_ptr(), ps,
+                                              _stream()), "mg_attn_decode_prefix_bf16")
+    return part
+
+
+def attn_decode_fused(qkv, kcache, vcache, out, B, H, d_pos, rot_dim, sin_t, cos_t, *, pos_stride: int = 0, shared=None):
+    """rotary(q,k) + KV append at pos_b + attention over [0, pos_b], one launch; pos_b = d_pos[b * pos_stride].
+    ``shared`` = (n_prefix, part) (mg_attn_decode_fused_shared_bf16): the caches hold the rows' OWN positions -- the append goes to own
+    index pos_b - n_prefix, the attention over the own keys is merged with the prefix partials ``part`` of attn_decode_prefix."""
     _need_gpu(qkv)
     ps = _pos_stride(d_pos, B, pos_stride)
+    if shared is not None:
+        n_prefix, part = _shared_part(shared, B, H)
+        check(L.load().mg_attn_decode_fused_shared_bf16(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), B, H,
+                                                        kcache.shape[2], d_pos.data_ptr(), rot_dim, sin_t.data_ptr(),
+                                                        cos_t.data_ptr(), ps, n_prefix, part.data_ptr(), _stream()),
+              "mg_attn_decode_fused_shared_bf16")
+        return out
     check(L.load().mg_attn_decode_fused_bf16(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), B, H,
                                              kcache.shape[2], d_pos.data_ptr(), rot_dim, sin_t.data_ptr(),
                                              cos_t.data_ptr(), ps, _stream()), "mg_attn_decode_fused_bf16")
@@ -902,13 +956,15 @@ def sample_finish_slots(token: torch.Tensor, state: torch.Tensor, table: torch.T
 def slots_admit(kstage: torch.Tensor, vstage: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, src_row, dst_slot, lens,
                 first_token: torch.Tensor, limits, state: torch.Tensor, d_pos: torch.Tensor, token: torch.Tensor,
                 finish: torch.Tensor, slot: torch.Tensor, history: torch.Tensor, table: torch.Tensor, n_eos: int, n_seq: int,
-                pos0: int = 0):
+                pos0: int = 0, dst0: Optional[int] = None):
     """Install n staged requests into slots of a slot session in one launch (mg_slots_admit_bf16): K / V positions [0, lens[j])
     of staging row ``src_row[j]`` ([L, n_stage, H, S_stage, 256]) go to live row ``dst_slot[j]`` ([L, B, H, Smax, 256]); the slot's
     position, token (``first_token[j]``, on the device), window, history column and finish record are set as the header states.
     ``src_row``, ``dst_slot``, ``lens`` and ``limits`` are host integers; what they must satisfy is checked by the entry point.
     ``pos0`` > 0 (a session prefix; mg_slots_admit_at_bf16): positions [pos0, pos0 + lens[j]) move instead, to the same positions
-    of the slot, whose position becomes pos0 + lens[j]; nothing below pos0 is read or written."""
+    of the slot, whose position becomes pos0 + lens[j]; nothing below pos0 is read or written.
+    ``dst0`` (a live cache that holds the rows' own positions only; mg_slots_admit_shared_bf16): staged positions
+    [pos0, pos0 + lens[j]) go to live positions [dst0, dst0 + lens[j]) instead; the slot's position is still pos0 + lens[j]."""
     _need_gpu(kstage, vstage, kcache, vcache, first_token, state, d_pos, token, finish, slot, history, table)
     Lr, n_stage, H, S_stage, hd = kstage.shape
     _, B, _, Smax, _ = kcache.shape
@@ -931,7 +987,9 @@ def slots_admit(kstage: torch.Tensor, vstage: torch.Tensor, kcache: torch.Tensor
             arr(src_row), arr(dst_slot), arr(lens), first_token.data_ptr(), arr(limits), state.data_ptr(), d_pos.data_ptr(),
             token.data_ptr(), finish.data_ptr(), slot.data_ptr(), history.data_ptr(), history.stride(0), history.shape[1],
             table.data_ptr(), int(n_eos), int(n_seq))
-    if pos0:
+    if dst0 is not None:
+        check(L.load().mg_slots_admit_shared_bf16(*args, int(pos0), int(dst0), _stream()), "mg_slots_admit_shared_bf16")
+    elif pos0:
         check(L.load().mg_slots_admit_at_bf16(*args, int(pos0), _stream()), "mg_slots_admit_at_bf16")
     else:
         check(L.load().mg_slots_admit_bf16(*args, _stream()), "mg_slots_admit_bf16")

@@ -1681,7 +1681,7 @@ def _max_positions(model):
 def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 100, max_prompt: int = None, eos_token=None,
                     stop_sequences=None, temperature: float = 0.0, top_k: int = 0, top_p: float = 0.9,
                     sampler: str = "reference", min_p: float = 0.0, seed: int = None, every: int = None, admit_rows: int = None,
-                    decode: bool = True, prefix=None, **unsupported):
+                    decode: bool = True, prefix=None, share_prefix: bool = False, **unsupported):
     """Generate over a stream of requests (DESIGN.md "Request streams"): yields one ``StreamResult`` per request, in completion
     order.  Request i's tokens, finish reason and index are those of the solo call
 
@@ -1726,7 +1726,14 @@ def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 10
     cache of ``slots`` x ceil64(P + max_prompt + max_new_tokens) positions plus a staging cache of admit_rows x
     (P + ceil64(max_prompt)).  Every slot holds its OWN copy of the prefix, so the decode attention of a token step reads P more
     positions per live row: a prefix saves prefill work, not decode bandwidth.  ValueError at call time: a cache with several
-    rows, with a pending token, of a beam or contrastive search or of another engine, embeddings of the wrong width."""
+    rows, with a pending token, of a beam or contrastive search or of another engine, embeddings of the wrong width.
+    ``share_prefix=True`` (DESIGN.md "Shared session prefix"; needs ``prefix``, ValueError at call time without one): the session
+    keeps ONE copy of the prefix's K / V and the live cache holds the rows' own positions only -- ``slots`` x
+    ceil64(max_prompt + max_new_tokens).  The decode attention of a token step then reads the prefix once for all rows (one launch
+    per block computes every row's partial attention over it, cut into chunks that depend on P alone; the attention launch merges
+    them with the row's own keys).  The sums are formed in another order than in the per-slot copies' attention, so tokens agree
+    with the default up to near-ties; a request's tokens do not depend on its slot, on the other requests or on ``every``.  An
+    LM object that is not the HIP engine ignores the flag."""
     import inspect
     defaults = {k: p.default for k, p in inspect.signature(generate).parameters.items()}
     known = {k for _, names in _STREAM_REFUSED for k in names}
@@ -1751,6 +1758,10 @@ def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 10
         raise ValueError(f"every must be an integer >= 1, got {every!r}")
     n_pos = _max_positions(model)
     P = 0
+    if not isinstance(share_prefix, bool):
+        raise ValueError(f"share_prefix must be True or False, got {share_prefix!r}")
+    if share_prefix and prefix is None:
+        raise ValueError("share_prefix=True needs a prefix: there is nothing to share")
     if prefix is not None:
         if torch.is_tensor(prefix):
             if prefix.ndim not in (2, 3) or (prefix.ndim == 3 and prefix.shape[0] != 1) or prefix.shape[-2] < 1:
@@ -1832,7 +1843,7 @@ def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 10
             torch.cuda.set_device(model.device)
         plan = LMEngine.selection_plan(sampling=mode, stop=stop, vocab=eng.V, slots=True)
         ses = SlotSession(eng, plan, slots=slots, max_new=max_new_tokens, max_prompt=max_prompt, every=every,
-                          admit_rows=admit_rows, seed=seed, prefix=prefix)
+                          admit_rows=admit_rows, seed=seed, prefix=prefix, share_prefix=share_prefix)
         dev = eng.device
         for index, ids, code, slot in ses.run((i, e.to(dev), n) for i, e, n in pulled()):
             reason = REASON_NAMES[code >> 8]

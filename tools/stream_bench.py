@@ -20,7 +20,14 @@ of ``--prefix-rows`` rows, max_new_tokens spread over 3 to 12, eos disabled -- f
     prompts (``max_prompt`` = prefix + request rows); static ``generate(past_key_values=cache.expand(8), stop_per_row=True)`` in
     batches of 8 behind one ``cache_prompt``.
 (b) The captured token step of a session with the prefix against the same session without it at equal own-context length: the
-    cost of the P more positions per row the decode attention reads.  Medians over interleaved windows of ``--steps`` replays."""
+    cost of the P more positions per row the decode attention reads.  Medians over interleaved windows of ``--steps`` replays.
+  python tools/stream_bench.py --prefix-rows 656 --share-prefix [--out FILE (default profiles/stream_shared_prefix_bench.jsonl)]
+
+The shared session prefix (DESIGN.md "Shared session prefix") against the per-slot copies, in the same process: the throughput
+legs become ``generate_stream(prefix=..., share_prefix=True)`` and ``generate_stream(prefix=...)``, interleaved; the step part
+gains the variant ``with_shared_prefix`` (every step record carries the live-cache bytes), and one more record times the
+prefix-partials launch alone (one per block, captured, replayed).
+"""
 import argparse
 import json
 import os
@@ -43,12 +50,17 @@ ap.add_argument("--every", type=int, default=0, help="0 = MAGMA_EOS_CHECK_EVERY 
 ap.add_argument("--steps", type=int, default=250)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--prefix-rows", type=int, default=0, help="P > 0: measure the session prefix instead (see the module docstring)")
+ap.add_argument("--share-prefix", action="store_true", help="with --prefix-rows: add the share_prefix=True legs (one copy of the "
+                "prefix, read once per step for all rows), the prefix-partials launch alone and the live-cache bytes")
 ap.add_argument("--request-rows", type=int, default=160, help="rows of every request in the --prefix-rows mode")
 ap.add_argument("--out", default=None, help="default: profiles/stream_bench.jsonl, profiles/stream_prefix_bench.jsonl with --prefix-rows")
 args = ap.parse_args()
 if args.out is None:
     args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                            "stream_shared_prefix_bench.jsonl" if args.prefix_rows and args.share_prefix else
                             "stream_prefix_bench.jsonl" if args.prefix_rows else "stream_bench.jsonl")
+if args.share_prefix and not args.prefix_rows:
+    sys.exit("stream_bench: --share-prefix needs --prefix-rows")
 
 if not torch.cuda.is_available():
     sys.exit("stream_bench: no GPU -- this tool measures, it does not fall back")
@@ -105,6 +117,10 @@ def prefix_mode():
         n = sum(int(r.tokens.numel()) for r in model.generate_stream(requests, max_prompt=R, prefix=prefix, **skw))
         return n, P + sum(passes)
 
+    def leg_shared():
+        n = sum(int(r.tokens.numel()) for r in model.generate_stream(requests, max_prompt=R, prefix=prefix, share_prefix=True, **skw))
+        return n, P + sum(passes)
+
     def leg_joined():
         n = sum(int(r.tokens.numel()) for r in model.generate_stream(joined, max_prompt=P + R, **skw))
         return n, sum(passes)
@@ -122,6 +138,8 @@ def prefix_mode():
         return n, rows
 
     legs = [("generate_stream_prefix", leg_prefix), ("generate_stream_concatenated", leg_joined), ("static_expand", leg_static)]
+    if args.share_prefix:           # interleaved with the unshared leg, which is its yardstick
+        legs = [("generate_stream_shared_prefix", leg_shared), ("generate_stream_prefix", leg_prefix)]
     for _, leg in legs:             # one warm-up pass of every leg
         leg()
     for rep in range(args.reps):
@@ -147,8 +165,11 @@ def prefix_mode():
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     plan = LMEngine.selection_plan(stop=dict(eos_ids=(EOS,), stop_seqs=()), vocab=eng.V, slots=True)
     held = {}
-    for name, given in (("with_prefix", prefix), ("without_prefix", None), ("without_prefix_again", None)):
-        ses = SlotSession(eng, plan, slots=B, max_new=args.steps + 8, max_prompt=R, every=1, admit_rows=B, prefix=given)
+    variants = [("with_prefix", prefix, False), ("without_prefix", None, False), ("without_prefix_again", None, False)]
+    if args.share_prefix:
+        variants.insert(0, ("with_shared_prefix", prefix, True))
+    for name, given, share in variants:
+        ses = SlotSession(eng, plan, slots=B, max_new=args.steps + 8, max_prompt=R, every=1, admit_rows=B, prefix=given, share_prefix=share)
         ses._admit([(i, emb[i % 8], args.steps + 8) for i in range(B)], list(range(B)))
         sc = ses.cache
         tensors = (sc.d_pos, sc.finish, sc.slot_table, sc.sample_state, ses.st.token)
@@ -170,7 +191,29 @@ def prefix_mode():
             ms[name].append(e0.elapsed_time(e1) / args.steps)
     for name in ms:
         emit({"part": "step", "variant": name, "prefix_rows": held[name][0].P, "own_rows": R, "step_ms_min": min(ms[name]),
-              "step_ms_median": statistics.median(ms[name]), "step_ms_all": ms[name], "steps_per_window": args.steps})
+              "step_ms_median": statistics.median(ms[name]), "step_ms_all": ms[name], "steps_per_window": args.steps,
+              "live_cache_bytes": sum(t.numel() * t.element_size() for t in (held[name][0].cache.k, held[name][0].cache.v)),
+              "shared_prefix_bytes": sum(t.numel() * t.element_size() for t in (held[name][0].cache.prefix_k, held[name][0].cache.prefix_v)
+                                         if t is not None)})
+    if args.share_prefix:           # the prefix-partials launch alone: one per block, captured, replayed
+        ses = held["with_shared_prefix"][0]
+        graph = torch.cuda.CUDAGraph()
+        for li in range(eng.L):
+            eng._attn_prefix(ses.cache, ses.st, li)
+        with torch.cuda.graph(graph):
+            for li in range(eng.L):
+                eng._attn_prefix(ses.cache, ses.st, li)
+        us = []
+        for rep in range(args.reps):
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(50):
+                graph.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            us.append(e0.elapsed_time(e1) * 1e3 / 50)
+        emit({"part": "prefix_partials_alone", "prefix_rows": P, "slots": B, "blocks": eng.L, "chunks": ses.st.shared[1].shape[2],
+              "us_per_step_median": statistics.median(us), "us_per_launch_median": statistics.median(us) / eng.L, "us_per_step_all": us})
     write_out()
 
 
