@@ -461,7 +461,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AttnDecodeParams
 
 __global__ __launch_bounds__(256) void attn_decode_shared_kernel(const AttnDecodeParams P, const AttnSharedParams S) {
   __shared__ __attribute__((aligned(16))) char lds[ATTN_DEC_LDS];
-  attn_decode_body<true, false, true>(P, blockIdx.x, lds, S);
+  attn_decode_body<true, true>(P, blockIdx.x, lds, S);
 }
 
 __global__ __launch_bounds__(256) void attn_decode_prefix_kernel(const AttnPrefixParams P) {
@@ -588,11 +588,8 @@ extern "C" int mg_attn_prefill_bf16(const mg_bf16* q, const mg_bf16* kcache, con
 extern "C" int mg_attn_decode_bf16(const mg_bf16* q, const mg_bf16* kcache, const mg_bf16* vcache, mg_bf16* out,
                                    int32_t B, int32_t H, int32_t Smax, const int32_t* d_pos, int32_t pos_stride,
                                    void* stream) {
-  if (B <= 0 || H <= 0 || Smax <= 0 || Smax > DEC_MAX_CTX) MG_FAIL(MG_ERR_SHAPE, "mg_attn_decode_bf16: need 0 < Smax <= %d", DEC_MAX_CTX);
-  if (pos_stride != 0 && pos_stride != 1) MG_FAIL(MG_ERR_SHAPE, "mg_attn_decode_bf16: pos_stride must be 0 or 1");
-  if (!q || !kcache || !vcache || !out || !d_pos) MG_FAIL(MG_ERR_SHAPE, "mg_attn_decode_bf16: null pointer");
-  if (!MG_ALIGNED16(q) || !MG_ALIGNED16(kcache) || !MG_ALIGNED16(vcache) || !MG_ALIGNED16(out)) MG_FAIL(MG_ERR_ALIGN, "mg_attn_decode_bf16: pointers must be 16-byte aligned");
   AttnDecodeParams P{q, (mg_bf16*)kcache, (mg_bf16*)vcache, out, H, Smax, d_pos, 0, nullptr, nullptr, 0, pos_stride};
+  if (int rc = attn_decode_check("mg_attn_decode_bf16", P, B, false)) return rc;
   hipLaunchKernelGGL(attn_decode_kernel<false>, dim3(B * H), dim3(256), 0, (hipStream_t)stream, P);
   MG_CHECK_LAUNCH();
   return MG_OK;
@@ -601,12 +598,8 @@ extern "C" int mg_attn_decode_bf16(const mg_bf16* q, const mg_bf16* kcache, cons
 extern "C" int mg_attn_decode_fused_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_bf16* vcache, mg_bf16* out, int32_t B,
                                          int32_t H, int32_t Smax, const int32_t* d_pos, int32_t rot_dim,
                                          const float* sin_t, const float* cos_t, int32_t pos_stride, void* stream) {
-  if (B <= 0 || H <= 0 || Smax <= 0 || Smax > DEC_MAX_CTX) MG_FAIL(MG_ERR_SHAPE, "mg_attn_decode_fused_bf16: need 0 < Smax <= %d", DEC_MAX_CTX);
-  if (pos_stride != 0 && pos_stride != 1) MG_FAIL(MG_ERR_SHAPE, "mg_attn_decode_fused_bf16: pos_stride must be 0 or 1");
-  if (rot_dim < 0 || rot_dim > DH || (rot_dim & 7)) MG_FAIL(MG_ERR_SHAPE, "mg_attn_decode_fused_bf16: rot_dim must be a multiple of 8 in [0,256]");
-  if (!qkv || !kcache || !vcache || !out || !d_pos || (rot_dim && (!sin_t || !cos_t))) MG_FAIL(MG_ERR_SHAPE, "mg_attn_decode_fused_bf16: null pointer");
-  if (!MG_ALIGNED16(qkv) || !MG_ALIGNED16(kcache) || !MG_ALIGNED16(vcache) || !MG_ALIGNED16(out)) MG_FAIL(MG_ERR_ALIGN, "mg_attn_decode_fused_bf16: pointers must be 16-byte aligned");
   AttnDecodeParams P{qkv, kcache, vcache, out, H, Smax, d_pos, rot_dim, sin_t, cos_t, 0, pos_stride};
+  if (int rc = attn_decode_check("mg_attn_decode_fused_bf16", P, B, false)) return rc;
   hipLaunchKernelGGL(attn_decode_kernel<true>, dim3(B * H), dim3(256), 0, (hipStream_t)stream, P);
   MG_CHECK_LAUNCH();
   return MG_OK;
@@ -638,12 +631,8 @@ extern "C" int mg_attn_decode_fused_shared_bf16(const mg_bf16* qkv, mg_bf16* kca
                                                 const float* cos_t, int32_t pos_stride, int32_t n_prefix, const float* part,
                                                 void* stream) {
   const char* who = "mg_attn_decode_fused_shared_bf16";
-  constexpr int DH = 256;
-  if (B <= 0 || H <= 0 || Smax <= 0 || Smax > DEC_MAX_CTX) MG_FAIL(MG_ERR_SHAPE, "%s: need 0 < Smax <= %d", who, DEC_MAX_CTX);
-  if (rot_dim < 0 || rot_dim > DH || (rot_dim & 7)) MG_FAIL(MG_ERR_SHAPE, "%s: rot_dim must be a multiple of 8 in [0,256]", who);
-  if (!qkv || !kcache || !vcache || !out || !d_pos || (rot_dim && (!sin_t || !cos_t))) MG_FAIL(MG_ERR_SHAPE, "%s: null pointer", who);
-  if (!MG_ALIGNED16(qkv) || !MG_ALIGNED16(kcache) || !MG_ALIGNED16(vcache) || !MG_ALIGNED16(out)) MG_FAIL(MG_ERR_ALIGN, "%s: pointers must be 16-byte aligned", who);
   AttnDecodeParams P{qkv, kcache, vcache, out, H, Smax, d_pos, rot_dim, sin_t, cos_t, 0, pos_stride};
+  if (int rc = attn_decode_check(who, P, B, true)) return rc;
   AttnSharedParams S;
   if (int rc = attn_shared_check(who, P, S, B, n_prefix, part)) return rc;
   hipLaunchKernelGGL(attn_decode_shared_kernel, dim3(B * H), dim3(256), 0, (hipStream_t)stream, P, S);

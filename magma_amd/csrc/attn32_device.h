@@ -51,12 +51,12 @@ MG_DEV void mfma32v0_ba(f32x16& c, const bf16x8 a, const bf16x8 b) {
 // instruction stream.  The builtin (not asm) so that hipcc's scoreboard sees it and drops its own.  gfx9 encoding: vmcnt 63,
 // expcnt 7, lgkmcnt 4.
 #define MG_LGKM4() __builtin_amdgcn_s_waitcnt(0xC47F)
-#define MG_LGKM0() __builtin_amdgcn_s_waitcnt(0xC07F)
 MG_DEV int perm32(int i) { return (i & 19) | ((i & 4) << 1) | ((i & 8) >> 1); }
 
 constexpr int EP_ROW = 528;   // epilogue staging image: 512-B rows padded to 132 dwords (a lane group's 16 rows hit 16 bank quads)
 
-// The same burst addressed as base ^ (ks << 5): chunk ((ks << 1) | hi) ^ sw of row R sits at byte R 512 + (((ks << 1) | hi) ^ sw) 16
+// Fragment bursts of four (chunk (ks << 1) | hi of the swizzled tile row R, ks = g*4 .. g*4+3) addressed as base ^ (ks << 5):
+// chunk ((ks << 1) | hi) ^ sw of row R sits at byte R 512 + (((ks << 1) | hi) ^ sw) 16
 // = (R 512 + (sw ^ hi) 16) ^ (ks << 5), so ONE lane constant (row_base32) + the stage offset + one v_xor per read replace the 16
 // per-lane offsets hipcc otherwise hoists out of the tile loop (16 VGPRs these kernels do not have).  `off` = stage / image
 // offset (a multiple of 512) + row_base32(...).
@@ -64,11 +64,6 @@ MG_DEV uint32_t row_base32(int R, int sw, int hi) { return (uint32_t)(R * 512 + 
 MG_DEV void rd_row4x(bf16x8 (&f)[4], const char* lds, uint32_t off, int g) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) f[i] = *(const bf16x8*)(lds + (off ^ (uint32_t)((g * 4 + i) << 5)));
-}
-// fragment bursts of four: chunk ((ks << 1) | hi) of tile row R (swizzled), ks = g*4 .. g*4+3
-MG_DEV void rd_row4(bf16x8 (&f)[4], const char* row, int g, int hi, int sw) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) f[i] = *(const bf16x8*)(row + (((((g * 4 + i) << 1) | hi) ^ sw) << 4));
 }
 // T image: rows d = db*32 + l31 (64-byte rows), chunk ((ks2 << 1) | hi) ^ tsw; batch g = d-blocks 2g, 2g+1 x both k-steps
 MG_DEV void rd_t4(bf16x8 (&f)[4], const char* tp, int g, int x) {

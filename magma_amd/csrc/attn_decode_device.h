@@ -1,5 +1,5 @@
 // attn_decode_device.h -- body of the single-query decode attention (rotary + KV append + attention),
-// shared by attention.hip (stand-alone launch) and decode_fused.hip (co-launched with a GEMV).
+// shared by attention.hip (stand-alone launch) and gemm.hip (decode_attn_gemv_kernel: co-launched with a GEMV).
 #pragma once
 #include "common.h"
 #include "gemm_device.h"
@@ -186,13 +186,11 @@ MG_DEV void attn_prefix_body(const AttnPrefixParams& P, int h, int c, char* lds)
 }
 
 // Device body: `bh` = (batch, head) index, `lds` = ATTN_DEC_LDS bytes of scratch (16-byte aligned).
-// COH (persistent decode step): the fused qkv row comes from other workgroups of the same launch and the context row
-// goes to others -- both through the coherent accessors of gemm_device.h.
 // SHARED (FUSED only; shared session prefix, kernel 2; its fields are `S`): the cache holds the row's own positions -- k, v are
 // appended at own index pos - n_prefix (a pos < n_prefix counts as n_prefix), the row attends over its own keys exactly as above,
 // and the unnormalised result (maximum m, sum l, o) is merged with the row's n_chunk prefix partials in ascending chunk order
 // under one maximum M: out = (e^(m - M) o + sum_c e^(m_c - M) o_c) / (e^(m - M) l + sum_c e^(m_c - M) l_c), rounded to bf16 once.
-template <bool FUSED, bool COH = false, bool SHARED = false>
+template <bool FUSED, bool SHARED = false>
 MG_DEV void attn_decode_body(const AttnDecodeParams& P, int bh, char* lds, const AttnSharedParams& S = AttnSharedParams{}) {
   constexpr int DH = 256;
   const mg_bf16* __restrict__ qin = P.qin;
@@ -212,7 +210,7 @@ MG_DEV void attn_decode_body(const AttnDecodeParams& P, int bh, char* lds, const
   const int li = lane & 15, lq = lane >> 4;
   const int b = bh / H, h = bh - b * H;
   const int64_t out_off = P.ld_out ? (int64_t)b * P.ld_out + (int64_t)h * DH : (int64_t)bh * DH;
-  static_assert(!SHARED || (FUSED && !COH), "the shared-prefix mode is the fused, non-coherent body");
+  static_assert(!SHARED || FUSED, "the shared-prefix mode is the fused body");
   const int pos = SHARED ? max(d_pos[b * P.pos_stride], S.n_prefix) : d_pos[b * P.pos_stride];    // the rotary angle
   const int own = SHARED ? min(pos - S.n_prefix, Smax - 1) : pos;                                  // the cache index of the new token
   const int ctx = min(own + 1, min(Smax, DEC_MAX_CTX));
@@ -223,9 +221,7 @@ MG_DEV void attn_decode_body(const AttnDecodeParams& P, int bh, char* lds, const
     const int dmodel = H * DH;
     if (tid < 96) {
       const int which = tid >> 5, c = tid & 31, d0 = c * 8;
-      u32x4 v;
-      if constexpr (COH) v = ld16_coh(qin + (int64_t)b * 3 * dmodel + which * dmodel + h * DH + d0);
-      else v = *(const u32x4*)(qin + (int64_t)b * 3 * dmodel + which * dmodel + h * DH + d0);
+      u32x4 v = *(const u32x4*)(qin + (int64_t)b * 3 * dmodel + which * dmodel + h * DH + d0);
       if (which < 2 && d0 < rot_dim) v = rotary8_at(v, sin_t, cos_t, pos, rot_dim, d0);
       if (which == 0) *(u32x4*)(qs + d0) = v;
       else if (which == 1) *(u32x4*)(kb + (int64_t)own * DH + d0) = v;
@@ -312,17 +308,21 @@ MG_DEV void attn_decode_body(const AttnDecodeParams& P, int bh, char* lds, const
     return;
   }
   const float v = (red[tid] + red[DH + tid] + red[2 * DH + tid] + red[3 * DH + tid]) * inv;
-  if constexpr (COH) {      // four dims per lane -> one 8-byte coherent store (lanes 0..63 of wave 0)
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    if (tid < 64) {
-      u32x2 w; w[0] = pack2bf(red[tid * 4], red[tid * 4 + 1]); w[1] = pack2bf(red[tid * 4 + 2], red[tid * 4 + 3]);
-      st8_coh(out + out_off + tid * 4, w);
-    }
-  } else {
-    out[out_off + tid] = f2bf(v);
-  }
+  out[out_off + tid] = f2bf(v);
+}
+
+// The refusals every decode-attention entry point has in common, stand-alone or co-launched (ap.rot_dim = 0 where the entry point
+// has no rotary).  shared: pos_stride is left to attn_shared_check, which answers a wrong one in its own words.  also_null: a
+// further pointer the entry point needs is missing.
+static inline int attn_decode_check(const char* who, const AttnDecodeParams& ap, int32_t B, bool shared, bool also_null = false) {
+  if (B <= 0 || ap.H <= 0 || ap.Smax <= 0 || ap.Smax > DEC_MAX_CTX) MG_FAIL(MG_ERR_SHAPE, "%s: need 0 < Smax <= %d", who, DEC_MAX_CTX);
+  if (!shared && ap.pos_stride != 0 && ap.pos_stride != 1) MG_FAIL(MG_ERR_SHAPE, "%s: pos_stride must be 0 or 1", who);
+  if (ap.rot_dim < 0 || ap.rot_dim > 256 || (ap.rot_dim & 7)) MG_FAIL(MG_ERR_SHAPE, "%s: rot_dim must be a multiple of 8 in [0,256]", who);
+  if (!ap.qin || !ap.kcache || !ap.vcache || !ap.out || !ap.d_pos || also_null || (ap.rot_dim && (!ap.sin_t || !ap.cos_t)))
+    MG_FAIL(MG_ERR_SHAPE, "%s: null pointer", who);
+  if (!MG_ALIGNED16(ap.qin) || !MG_ALIGNED16(ap.kcache) || !MG_ALIGNED16(ap.vcache) || !MG_ALIGNED16(ap.out))
+    MG_FAIL(MG_ERR_ALIGN, "%s: pointers must be 16-byte aligned", who);
+  return MG_OK;
 }
 
 // The refusals the shared-prefix entry points have in common (before any launch); fills `sh`.

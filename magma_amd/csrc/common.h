@@ -96,21 +96,14 @@ MG_DEV void mx_emit8(const u32x4 w, uint8_t* __restrict__ qrow, uint8_t* __restr
 }
 
 // ---- LDS-DMA: global -> LDS without a register round trip -----------------------
-typedef const __attribute__((address_space(1))) void* mg_gptr_t;
 typedef __attribute__((address_space(3))) void* mg_lptr_t;
-MG_DEV void glds16(const void* g, char* lds_wave_base) {
-  // 64 lanes x 16 B -> 1 KiB at lds_wave_base (wave-uniform) + lane*16; any swizzle goes into the SOURCE address
-  __builtin_amdgcn_global_load_lds((mg_gptr_t)g, (mg_lptr_t)lds_wave_base, 16, 0, 0);
-}
-MG_DEV void glds4(const void* g, char* lds_wave_base) {   // 64 lanes x 4 B -> 256 B
-  __builtin_amdgcn_global_load_lds((mg_gptr_t)g, (mg_lptr_t)lds_wave_base, 4, 0, 0);
-}
-// The same two as inline assembly.  hipcc models the builtin as a FLAT access that may touch LDS; while one is in flight
-// (always, in a DMA ring that is only ever waited on with a counted vmcnt) its scoreboard calls both counters out of
-// order and turns EVERY wait for an ordinary ds_read into s_waitcnt lgkmcnt(0) -- a full LDS round trip in front of each
+// 64 lanes x 16 B -> 1 KiB (x 4 B -> 256 B) at lds_wave_base (wave-uniform) + lane*16; any swizzle goes into the SOURCE address.
+// Inline assembly, not __builtin_amdgcn_global_load_lds: hipcc models the builtin as a FLAT access that may touch LDS; while
+// one is in flight (always, in a DMA ring that is only ever waited on with a counted vmcnt) its scoreboard calls both counters
+// out of order and turns EVERY wait for an ordinary ds_read into s_waitcnt lgkmcnt(0) -- a full LDS round trip in front of each
 // MFMA burst that only needed its oldest fragment.  Issued from assembly the DMA is invisible to that pass, the ds_read
-// waits are counted again, and the ring is ordered by hand (MG_WAIT_VMCNT + barrier), as it already was.  A kernel that
-// uses these must not also use the builtin forms (M0 is written behind the compiler's back).
+// waits are counted again, and the ring is ordered by hand (MG_WAIT_VMCNT + barrier).  A kernel that uses these must not also
+// use the builtin (M0 is written behind the compiler's back).
 MG_DEV void glds16a(const void* g, char* lds_wave_base) {
   asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off"
                :: "v"(g), "s"(__builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(mg_lptr_t)lds_wave_base)) : "memory");
@@ -143,10 +136,6 @@ MG_DEV void glds4su(const void* base_uniform, uint32_t byte_off, uint32_t lds_ad
 MG_DEV void glds4au(const void* g, uint32_t lds_addr) {
   asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dword %0, off" :: "v"(g), "s"(lds_addr) : "memory");
 }
-MG_DEV void glds4a(const void* g, char* lds_wave_base) {
-  asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dword %0, off"
-               :: "v"(g), "s"(__builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(mg_lptr_t)lds_wave_base)) : "memory");
-}
 // an ordinary dword load issued from assembly (SGPR base + 32-bit per-lane byte offset): like the DMA forms above it is
 // invisible to hipcc's wait-count pass, so a loop that retires its VMEM traffic with hand-counted vmcnt waits can carry it
 // without the compiler draining the ring in front of the first use.  The CALLER guarantees that one of its own waits
@@ -155,18 +144,9 @@ MG_DEV void gld32s_async(uint32_t& dst, const void* base_uniform, uint32_t byte_
   asm volatile("global_load_dword %0, %1, %2" : "=v"(dst) : "v"(byte_off), "s"(base_uniform) : "memory");
 }
 #define MG_WAIT_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-// vmcnt(0) through the BUILTIN (gfx9 encoding: vmcnt = 0, expcnt / lgkmcnt untouched): unlike the inline-asm
-// form this one updates hipcc's own scoreboard, so it does not re-wait (vmcnt(0), draining the DMA ring)
-// at the first use of an ordinary load's result inside the pipelined loop.  Use it once, before the loop.
-#define MG_WAIT_VMCNT0_TRACKED()            \
-  do {                                     \
-    asm volatile("" ::: "memory");         \
-    __builtin_amdgcn_s_waitcnt(0x0F70);    \
-    asm volatile("" ::: "memory");         \
-  } while (0)
 // "these registers are needed now": hipcc waits (in its own scoreboard) for the ordinary loads that produce them.  Loads
-// through const __restrict__ pointers are invariant loads and float across memory clobbers -- and across the builtin
-// wait above -- so the only way to retire them BEFORE a pipelined loop is to consume their results there.
+// through const __restrict__ pointers are invariant loads and float across memory clobbers -- and across an s_waitcnt
+// builtin -- so the only way to retire them BEFORE a pipelined loop is to consume their results there.
 #define MG_USE8(f) asm volatile("" ::"v"((f)[0]), "v"((f)[1]), "v"((f)[2]), "v"((f)[3]), "v"((f)[4]), "v"((f)[5]), "v"((f)[6]), "v"((f)[7]))
 // workgroup barrier that does NOT drain in-flight LDS-DMA (a __syncthreads() would emit vmcnt(0)):
 // retire this wave's LDS reads, barrier, and keep the compiler from moving LDS accesses across it

@@ -878,7 +878,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
 template <int WAVES, int KC, int NT, int WT = WT_BF16, bool PIPE = false>
 __global__ __launch_bounds__(WAVES * 64) void skinny_kernel(const SkinnyParams p) {
   __shared__ __attribute__((aligned(16))) char lds[skinny_lds_bytes<WAVES, NT>()];
-  skinny_body<WAVES, KC, NT, WT, false, NoWait, PIPE>(p, blockIdx.x, lds);
+  skinny_body<WAVES, KC, NT, WT, PIPE>(p, blockIdx.x, lds);
 }
 
 // two independent GEMVs (same variant) in ONE launch: blocks [0, g0) work on p0, the rest on p1.
@@ -886,8 +886,8 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_kernel(const SkinnyParams p
 template <int WAVES, int KC, int NT, int WT = WT_BF16, bool PIPE = false>
 __global__ __launch_bounds__(WAVES * 64) void skinny2_kernel(const SkinnyParams p0, const SkinnyParams p1, int g0) {
   __shared__ __attribute__((aligned(16))) char lds[skinny_lds_bytes<WAVES, NT>()];
-  if ((int)blockIdx.x < g0) skinny_body<WAVES, KC, NT, WT, false, NoWait, PIPE>(p0, blockIdx.x, lds);
-  else skinny_body<WAVES, KC, NT, WT, false, NoWait, PIPE>(p1, blockIdx.x - g0, lds);
+  if ((int)blockIdx.x < g0) skinny_body<WAVES, KC, NT, WT, PIPE>(p0, blockIdx.x, lds);
+  else skinny_body<WAVES, KC, NT, WT, PIPE>(p1, blockIdx.x - g0, lds);
 }
 
 int check_epilogue(const mg_epilogue& ep, const char* who, bool tile_gemm = false, int N = 0) {
@@ -1232,7 +1232,7 @@ __global__ __launch_bounds__(256) void decode_attn_gemv_kernel(const AttnDecodeP
   constexpr int LDS = ATTN_DEC_LDS > skinny_lds_bytes<4, 1>() ? ATTN_DEC_LDS : skinny_lds_bytes<4, 1>();
   __shared__ __attribute__((aligned(16))) char lds[LDS];
   if ((int)blockIdx.x < n_attn) attn_decode_body<true>(ap, blockIdx.x, lds);
-  else skinny_body<4, KC, 1, WT, false, NoWait, PIPE>(sp, blockIdx.x - n_attn, lds);
+  else skinny_body<4, KC, 1, WT, PIPE>(sp, blockIdx.x - n_attn, lds);
 }
 
 // The same co-launch with the attention workgroups in the shared-prefix mode of the body (mg_decode_attn_gemv_shared_bf16).
@@ -1241,8 +1241,8 @@ __global__ __launch_bounds__(256) void decode_attn_shared_gemv_kernel(const Attn
                                                                       const SkinnyParams sp) {
   constexpr int LDS = ATTN_DEC_LDS > skinny_lds_bytes<4, 1>() ? ATTN_DEC_LDS : skinny_lds_bytes<4, 1>();
   __shared__ __attribute__((aligned(16))) char lds[LDS];
-  if ((int)blockIdx.x < n_attn) attn_decode_body<true, false, true>(ap, blockIdx.x, lds, sh);
-  else skinny_body<4, KC, 1, WT, false, NoWait, false>(sp, blockIdx.x - n_attn, lds);
+  if ((int)blockIdx.x < n_attn) attn_decode_body<true, true>(ap, blockIdx.x, lds, sh);
+  else skinny_body<4, KC, 1, WT, false>(sp, blockIdx.x - n_attn, lds);
 }
 
 constexpr int MG_DECODE_PIPE_DEFAULT = 0;
@@ -1389,77 +1389,69 @@ extern "C" int mg_gemm_skinny2_bf16(const mg_skinny_desc* a, const mg_skinny_des
   return MG_OK;
 }
 
+namespace {
+// The co-launch of both entry points below: the checks, then ONE ladder that picks the GEMV instantiation from the operands --
+// so the shared-prefix launch streams the same GEMV variant as the unshared one for the same operands, and its GEMV has the same
+// bits.  MAGMA_DECODE_PIPE (0 = burst-and-drain, 16 / 8 = double-buffered bursts of that many k-steps, bf16 weights) exists
+// unshared only.
+template <bool SHARED>
+int decode_attn_gemv_launch(const char* who, const char* who_gemv, const AttnDecodeParams& ap, int32_t B, const mg_skinny_desc* gemv,
+                            int32_t n_prefix, const float* part, void* stream) {
+  if (int rc = attn_decode_check(who, ap, B, SHARED, SHARED && !gemv)) return rc;
+  SkinnyParams sp;
+  if (int rc = fill_skinny(gemv, sp, who_gemv)) return rc;
+  if (ap.ld_out != 0 && (ap.ld_out < (int64_t)ap.H * 256 || (ap.ld_out & 7))) MG_FAIL(MG_ERR_SHAPE, "%s: ld_attn_out must be 0 or a multiple of 8 >= H*256", who);
+  [[maybe_unused]] AttnSharedParams sh;
+  if constexpr (SHARED) {
+    if (int rc = attn_shared_check(who, ap, sh, B, n_prefix, part)) return rc;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int n_attn = B * ap.H, grid = n_attn + sp.ntiles;
+  if (sp.w_scale && sp.ksteps % 64 != 0) MG_FAIL(MG_ERR_UNSUPPORTED, "%s: fp8 weights need K %% 2048 == 0 here", who);
+  int pipe = 0;
+  if constexpr (!SHARED) { const char* e = getenv("MAGMA_DECODE_PIPE"); pipe = e ? atoi(e) : MG_DECODE_PIPE_DEFAULT; }   // read per call (graph capture)
+  // (a PIPE row instantiates nothing in the shared launcher, where pipe == 0 never reaches it)
+#define MG_DAG(K_, W_, P_)                                                                                                                \
+  do {                                                                                                                                    \
+    if constexpr (!SHARED) hipLaunchKernelGGL((decode_attn_gemv_kernel<K_, W_, P_>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);         \
+    else if constexpr (!(P_)) hipLaunchKernelGGL((decode_attn_shared_gemv_kernel<K_, W_>), dim3(grid), dim3(256), 0, s, ap, sh, n_attn, sp); \
+  } while (0)
+  if (sp.w_mx4) {   // MXFP4: one n-tile per workgroup (fc_out has 256 tiles: see the measured table in mg_gemm_skinny_bf16)
+    if (sp.ksteps % 64 == 0) MG_DAG(16, WT_MX4, false);
+    else if (sp.ksteps % 32 == 0) MG_DAG(8, WT_MX4, false);
+    else MG_DAG(4, WT_MX4, false);
+  } else if (sp.w_scale) MG_DAG(16, WT_FP8, false);
+  // losslessly packed bf16: 4 waves like every bf16 form below (same bits), whole k-step quads per wave
+  else if (sp.pk_lo && sp.ksteps % 64 == 0) MG_DAG(16, WT_PK, false);
+  else if (sp.pk_lo && sp.ksteps % 16 == 0) MG_DAG(4, WT_PK, false);
+  else if (pipe == 16 && sp.ksteps % 64 == 0) MG_DAG(16, WT_BF16, true);
+  else if (pipe == 8 && sp.ksteps % 32 == 0) MG_DAG(8, WT_BF16, true);
+  else if (sp.ksteps % 64 == 0) MG_DAG(16, WT_BF16, false);
+  else if (sp.ksteps % 16 == 0) MG_DAG(4, WT_BF16, false);
+  else if (sp.ksteps % 4 == 0) MG_DAG(1, WT_BF16, false);
+  else MG_FAIL(MG_ERR_UNSUPPORTED, "%s: K of the GEMV must be a multiple of 128", who);
+#undef MG_DAG
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+}  // namespace
+
 // Decode attention (rotary + KV append + attention, see mg_attn_decode_fused_bf16) co-launched with
 // one weight-streaming GEMV that does not depend on it (fc_out of the parallel GPT-J block).
 extern "C" int mg_decode_attn_gemv_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_bf16* vcache, mg_bf16* attn_out, int64_t ld_attn_out,
                                         int32_t B, int32_t H, int32_t Smax, const int32_t* d_pos, int32_t rot_dim,
                                         const float* sin_t, const float* cos_t, const mg_skinny_desc* gemv,
                                         int32_t pos_stride, void* stream) {
-  if (B <= 0 || H <= 0 || Smax <= 0 || Smax > DEC_MAX_CTX) MG_FAIL(MG_ERR_SHAPE, "mg_decode_attn_gemv_bf16: need 0 < Smax <= %d", DEC_MAX_CTX);
-  if (pos_stride != 0 && pos_stride != 1) MG_FAIL(MG_ERR_SHAPE, "mg_decode_attn_gemv_bf16: pos_stride must be 0 or 1");
-  if (rot_dim < 0 || rot_dim > 256 || (rot_dim & 7)) MG_FAIL(MG_ERR_SHAPE, "mg_decode_attn_gemv_bf16: rot_dim must be a multiple of 8 in [0,256]");
-  if (!qkv || !kcache || !vcache || !attn_out || !d_pos || (rot_dim && (!sin_t || !cos_t))) MG_FAIL(MG_ERR_SHAPE, "mg_decode_attn_gemv_bf16: null pointer");
-  if (!MG_ALIGNED16(qkv) || !MG_ALIGNED16(kcache) || !MG_ALIGNED16(vcache) || !MG_ALIGNED16(attn_out)) MG_FAIL(MG_ERR_ALIGN, "mg_decode_attn_gemv_bf16: pointers must be 16-byte aligned");
-  SkinnyParams sp;
-  if (int rc = fill_skinny(gemv, sp, "mg_decode_attn_gemv_bf16(gemv)")) return rc;
-  if (ld_attn_out != 0 && (ld_attn_out < (int64_t)H * 256 || (ld_attn_out & 7))) MG_FAIL(MG_ERR_SHAPE, "mg_decode_attn_gemv_bf16: ld_attn_out must be 0 or a multiple of 8 >= H*256");
-  AttnDecodeParams ap{qkv, kcache, vcache, attn_out, H, Smax, d_pos, rot_dim, sin_t, cos_t, ld_attn_out, pos_stride};
-  hipStream_t s = (hipStream_t)stream;
-  const int n_attn = B * H, grid = n_attn + sp.ntiles;
-  if (sp.w_scale && sp.ksteps % 64 != 0) MG_FAIL(MG_ERR_UNSUPPORTED, "mg_decode_attn_gemv_bf16: fp8 weights need K %% 2048 == 0 here");
-  // MAGMA_DECODE_PIPE: 0 = burst-and-drain, 16 / 8 = double-buffered bursts of that many k-steps (bf16 weights)
-  const int pipe = [] { const char* e = getenv("MAGMA_DECODE_PIPE"); return e ? atoi(e) : MG_DECODE_PIPE_DEFAULT; }();   // read per call (graph capture)
-  if (sp.w_mx4) {   // MXFP4: one n-tile per workgroup (fc_out has 256 tiles: see the measured table in mg_gemm_skinny_bf16)
-    if (sp.ksteps % 64 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<16, WT_MX4>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
-    else if (sp.ksteps % 32 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<8, WT_MX4>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
-    else hipLaunchKernelGGL((decode_attn_gemv_kernel<4, WT_MX4>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
-  } else if (sp.w_scale) hipLaunchKernelGGL((decode_attn_gemv_kernel<16, WT_FP8>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
-  // losslessly packed bf16: 4 waves like every bf16 form below (same bits), whole k-step quads per wave
-  else if (sp.pk_lo && sp.ksteps % 64 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<16, WT_PK>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
-  else if (sp.pk_lo && sp.ksteps % 16 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<4, WT_PK>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
-  else if (pipe == 16 && sp.ksteps % 64 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<16, WT_BF16, true>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
-  else if (pipe == 8 && sp.ksteps % 32 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<8, WT_BF16, true>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
-  else if (sp.ksteps % 64 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<16>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
-  else if (sp.ksteps % 16 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<4>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
-  else if (sp.ksteps % 4 == 0) hipLaunchKernelGGL((decode_attn_gemv_kernel<1>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);
-  else MG_FAIL(MG_ERR_UNSUPPORTED, "mg_decode_attn_gemv_bf16: K of the GEMV must be a multiple of 128");
-  MG_CHECK_LAUNCH();
-  return MG_OK;
+  const AttnDecodeParams ap{qkv, kcache, vcache, attn_out, H, Smax, d_pos, rot_dim, sin_t, cos_t, ld_attn_out, pos_stride};
+  return decode_attn_gemv_launch<false>("mg_decode_attn_gemv_bf16", "mg_decode_attn_gemv_bf16(gemv)", ap, B, gemv, 0, nullptr, stream);
 }
 
-// mg_decode_attn_gemv_bf16 with the attention workgroups in the shared-prefix mode (mg_attn_decode_fused_shared_bf16): the same
-// GEMV variants for the same operands, so the GEMV's bits are those of the unshared launch.
+// mg_decode_attn_gemv_bf16 with the attention workgroups in the shared-prefix mode (mg_attn_decode_fused_shared_bf16).
 extern "C" int mg_decode_attn_gemv_shared_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_bf16* vcache, mg_bf16* attn_out,
                                                int64_t ld_attn_out, int32_t B, int32_t H, int32_t Smax, const int32_t* d_pos,
                                                int32_t rot_dim, const float* sin_t, const float* cos_t, const mg_skinny_desc* gemv,
                                                int32_t pos_stride, int32_t n_prefix, const float* part, void* stream) {
-  const char* who = "mg_decode_attn_gemv_shared_bf16";
-  if (B <= 0 || H <= 0 || Smax <= 0 || Smax > DEC_MAX_CTX) MG_FAIL(MG_ERR_SHAPE, "%s: need 0 < Smax <= %d", who, DEC_MAX_CTX);
-  if (rot_dim < 0 || rot_dim > 256 || (rot_dim & 7)) MG_FAIL(MG_ERR_SHAPE, "%s: rot_dim must be a multiple of 8 in [0,256]", who);
-  if (!qkv || !kcache || !vcache || !attn_out || !d_pos || !gemv || (rot_dim && (!sin_t || !cos_t))) MG_FAIL(MG_ERR_SHAPE, "%s: null pointer", who);
-  if (!MG_ALIGNED16(qkv) || !MG_ALIGNED16(kcache) || !MG_ALIGNED16(vcache) || !MG_ALIGNED16(attn_out)) MG_FAIL(MG_ERR_ALIGN, "%s: pointers must be 16-byte aligned", who);
-  SkinnyParams sp;
-  if (int rc = fill_skinny(gemv, sp, "mg_decode_attn_gemv_shared_bf16(gemv)")) return rc;
-  if (ld_attn_out != 0 && (ld_attn_out < (int64_t)H * 256 || (ld_attn_out & 7))) MG_FAIL(MG_ERR_SHAPE, "%s: ld_attn_out must be 0 or a multiple of 8 >= H*256", who);
-  AttnDecodeParams ap{qkv, kcache, vcache, attn_out, H, Smax, d_pos, rot_dim, sin_t, cos_t, ld_attn_out, pos_stride};
-  AttnSharedParams sh;
-  if (int rc = attn_shared_check(who, ap, sh, B, n_prefix, part)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const int n_attn = B * H, grid = n_attn + sp.ntiles;
-  if (sp.w_scale && sp.ksteps % 64 != 0) MG_FAIL(MG_ERR_UNSUPPORTED, "%s: fp8 weights need K %% 2048 == 0 here", who);
-#define MG_DAS(K_, W_) hipLaunchKernelGGL((decode_attn_shared_gemv_kernel<K_, W_>), dim3(grid), dim3(256), 0, s, ap, sh, n_attn, sp)
-  if (sp.w_mx4) {
-    if (sp.ksteps % 64 == 0) MG_DAS(16, WT_MX4);
-    else if (sp.ksteps % 32 == 0) MG_DAS(8, WT_MX4);
-    else MG_DAS(4, WT_MX4);
-  } else if (sp.w_scale) MG_DAS(16, WT_FP8);
-  else if (sp.pk_lo && sp.ksteps % 64 == 0) MG_DAS(16, WT_PK);
-  else if (sp.pk_lo && sp.ksteps % 16 == 0) MG_DAS(4, WT_PK);
-  else if (sp.ksteps % 64 == 0) MG_DAS(16, WT_BF16);
-  else if (sp.ksteps % 16 == 0) MG_DAS(4, WT_BF16);
-  else if (sp.ksteps % 4 == 0) MG_DAS(1, WT_BF16);
-  else MG_FAIL(MG_ERR_UNSUPPORTED, "%s: K of the GEMV must be a multiple of 128", who);
-#undef MG_DAS
-  MG_CHECK_LAUNCH();
-  return MG_OK;
+  const AttnDecodeParams ap{qkv, kcache, vcache, attn_out, H, Smax, d_pos, rot_dim, sin_t, cos_t, ld_attn_out, pos_stride};
+  return decode_attn_gemv_launch<true>("mg_decode_attn_gemv_shared_bf16", "mg_decode_attn_gemv_shared_bf16(gemv)", ap, B, gemv, n_prefix,
+                                       part, stream);
 }

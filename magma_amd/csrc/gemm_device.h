@@ -60,53 +60,10 @@ MG_DEV void epilogue_cols(const mg_epilogue& ep, int n, int N, EpiColsW<W>& c) {
   }
 }
 
-// ---- cross-workgroup hand-offs inside ONE launch (persistent decode step, decode_mega_kernel) ----
-// A CU's vector L1 is never refreshed by another CU's stores and the per-XCD L2s are not coherent with each other
-// (MI355X_MICROARCH.md, inter-workgroup visibility).  Data produced and consumed by different workgroups of the same
-// launch therefore moves through 8-byte agent-scope relaxed atomics on BOTH sides (global_load/store_dwordx2 sc1: L1
-// bypassed, written through), ordered by a completion counter: the valid form "{8-B agent atomics both sides}".
-// (hipcc follows every __hip_atomic_load with a full s_waitcnt vmcnt(0), which would serialise the weight stream around each
-// activation fragment, so the loads are written as asm: `sc1` = the agent-scope form, and ONE wait per batch of loads.)
-MG_DEV u32x2 ld8_coh(const void* p) {
-  u32x2 v;
-  asm volatile("global_load_dwordx2 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(v) : "v"(p) : "memory");
-  return v;
-}
-MG_DEV void st8_coh(void* p, u32x2 w) {
-  __hip_atomic_store((unsigned long long*)p, (unsigned long long)w[0] | ((unsigned long long)w[1] << 32), __ATOMIC_RELAXED,
-                     __HIP_MEMORY_SCOPE_AGENT);
-}
-MG_DEV u32x4 ld16_coh(const void* p) {
-  u32x4 v;
-  asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(v) : "v"(p) : "memory");
-  return v;
-}
-// up to three 8-byte rows (the residual operands of an epilogue) with one wait
-MG_DEV void ld8x3_coh(const void* p0, const void* p1, const void* p2, u32x2& a, u32x2& b, u32x2& c) {
-  asm volatile("global_load_dwordx2 %0, %3, off sc1\n\tglobal_load_dwordx2 %1, %4, off sc1\n\t"
-               "global_load_dwordx2 %2, %5, off sc1\n\ts_waitcnt vmcnt(0)"
-               : "=&v"(a), "=&v"(b), "=&v"(c) : "v"(p0), "v"(p1), "v"(p2) : "memory");
-}
-// eight consecutive 64-byte-spaced 16-byte fragments (one chunk of activation k-steps) with one wait; the wait also
-// retires the weight loads issued before it -- the MFMAs that follow need both
-MG_DEV void ld16x8_coh(const void* p, u32x4 (&v)[8]) {
-  asm volatile("global_load_dwordx4 %0, %8, off sc1\n\tglobal_load_dwordx4 %1, %8, off offset:64 sc1\n\t"
-               "global_load_dwordx4 %2, %8, off offset:128 sc1\n\tglobal_load_dwordx4 %3, %8, off offset:192 sc1\n\t"
-               "global_load_dwordx4 %4, %8, off offset:256 sc1\n\tglobal_load_dwordx4 %5, %8, off offset:320 sc1\n\t"
-               "global_load_dwordx4 %6, %8, off offset:384 sc1\n\tglobal_load_dwordx4 %7, %8, off offset:448 sc1\n\t"
-               "s_waitcnt vmcnt(0)"
-               : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7])
-               : "v"(p) : "memory");
-}
-
 // W consecutive bf16 of a row <-> floats (W = 4: one 8-B access, W = 8: one 16-B access; p must be W*2-byte aligned)
-template <int W, bool COH = false>
+template <int W>
 MG_DEV void load_bf16_row(const mg_bf16* p, float* a) {
-  if constexpr (COH) {
-    static_assert(W == 4, "coherent rows are 8-byte accesses");
-    const u32x2 w = ld8_coh(p);
-    a[0] = bflo(w[0]); a[1] = bfhi(w[0]); a[2] = bflo(w[1]); a[3] = bfhi(w[1]);
-  } else if constexpr (W == 8) {
+  if constexpr (W == 8) {
     const u32x4 w = *(const u32x4*)p;
 #pragma unroll
     for (int i = 0; i < 4; ++i) { a[2 * i] = bflo(w[i]); a[2 * i + 1] = bfhi(w[i]); }
@@ -115,13 +72,9 @@ MG_DEV void load_bf16_row(const mg_bf16* p, float* a) {
     a[0] = bflo(w[0]); a[1] = bfhi(w[0]); a[2] = bflo(w[1]); a[3] = bfhi(w[1]);
   }
 }
-template <int W, bool NT, bool COH = false>
+template <int W, bool NT>
 MG_DEV void store_bf16_row(mg_bf16* p, const float* o) {
-  if constexpr (COH) {
-    static_assert(W == 4, "coherent rows are 8-byte accesses");
-    u32x2 w; w[0] = pack2bf(o[0], o[1]); w[1] = pack2bf(o[2], o[3]);
-    st8_coh(p, w);
-  } else if constexpr (W == 8) {
+  if constexpr (W == 8) {
     u32x4 w;
 #pragma unroll
     for (int i = 0; i < 4; ++i) w[i] = pack2bf(o[2 * i], o[2 * i + 1]);
@@ -136,29 +89,18 @@ MG_DEV void store_bf16_row(mg_bf16* p, const float* o) {
 // rows before it stores anything (output and residual pointers may alias as far as the compiler knows, so a load written
 // after a store is never hoisted above it -- one row in flight, 2 TB/s on a three-residual epilogue).
 // (kept as raw bf16 words: W/2 registers per operand and row)
-template <int W> struct EpiPre { uint32_t aux[W / 2]; uint32_t res[3][W / 2]; };
 template <int W>
 MG_DEV void epi_raw_load(const mg_bf16* p, uint32_t (&w)[W / 2]) {
   if constexpr (W == 8) { const u32x4 t = *(const u32x4*)p; w[0] = t[0]; w[1] = t[1]; w[2] = t[2]; w[3] = t[3]; }
   else { const u32x2 t = *(const u32x2*)p; w[0] = t[0]; w[1] = t[1]; }
-}
-template <int W>
-MG_DEV void epilogue_prefetch(const mg_epilogue& ep, int m, int n, EpiPre<W>& p) {
-#pragma unroll
-  for (int r = 0; r < W / 2; ++r) { p.aux[r] = 0u; p.res[0][r] = 0u; p.res[1][r] = 0u; p.res[2][r] = 0u; }
-  if (ep.aux_mode != MG_AUX_NONE) epi_raw_load<W>(ep.aux + (int64_t)m * ep.ldaux + n, p.aux);
-  if (ep.res0) epi_raw_load<W>(ep.res0 + (int64_t)m * ep.ldr + n, p.res[0]);
-  if (ep.res1) epi_raw_load<W>(ep.res1 + (int64_t)m * ep.ldr + n, p.res[1]);
-  if (ep.res2) epi_raw_load<W>(ep.res2 + (int64_t)m * ep.ldr + n, p.res[2]);
 }
 
 // v[W] = accumulators of columns n .. n+W-1 of row m.  NT: non-temporal output stores (large outputs
 // that nobody re-reads soon: keeps the L2 for the operand panels and streams the tile out).
 // FULL: the caller guarantees n + W <= N (interior column tile): the per-element tail paths are not even compiled -- they are
 // most of the instructions of an epilogue, and a tile's epilogue runs once per ~100 us, from a cold instruction cache.
-template <int W, bool NT, bool COH, bool PRE, bool FULL = false>
-MG_DEV void epilogue_apply_impl(const mg_epilogue& ep, const EpiColsW<W>& c, int m, int n, const float* v, int N,
-                                const EpiPre<W>& pre) {
+template <int W, bool NT, bool FULL = false>
+MG_DEV void epilogue_apply(const mg_epilogue& ep, const EpiColsW<W>& c, int m, int n, const float* v, int N) {
   const bool full = FULL || (n + W - 1 < N);
   float o[W];
 #pragma unroll
@@ -179,10 +121,7 @@ MG_DEV void epilogue_apply_impl(const mg_epilogue& ep, const EpiColsW<W>& c, int
     float a[W];
 #pragma unroll
     for (int r = 0; r < W; ++r) a[r] = 0.f;
-    if constexpr (PRE) {
-#pragma unroll
-      for (int r = 0; r < W / 2; ++r) { a[2 * r] = bflo(pre.aux[r]); a[2 * r + 1] = bfhi(pre.aux[r]); }
-    } else if (full) load_bf16_row<W>(ap, a);
+    if (full) load_bf16_row<W>(ap, a);
     else for (int r = 0; r < W; ++r) if (n + r < N) a[r] = bf2f(ap[r]);
 #pragma unroll
     for (int r = 0; r < W; ++r)
@@ -195,28 +134,13 @@ MG_DEV void epilogue_apply_impl(const mg_epilogue& ep, const EpiColsW<W>& c, int
     }
   }
   const mg_bf16* rs[3] = {ep.res0, ep.res1, ep.res2};
-  if constexpr (COH) {       // all residual rows in flight together, one wait (W == 4: 8-byte rows)
-    if (full && (rs[0] || rs[1] || rs[2])) {
-      const mg_bf16* any = rs[0] ? rs[0] : (rs[1] ? rs[1] : rs[2]);
-      u32x2 w[3];
-      ld8x3_coh((rs[0] ? rs[0] : any) + (int64_t)m * ep.ldr + n, (rs[1] ? rs[1] : any) + (int64_t)m * ep.ldr + n,
-                (rs[2] ? rs[2] : any) + (int64_t)m * ep.ldr + n, w[0], w[1], w[2]);
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-        if (rs[t]) { o[0] += bflo(w[t][0]); o[1] += bfhi(w[t][0]); o[2] += bflo(w[t][1]); o[3] += bfhi(w[t][1]); }
-      rs[0] = rs[1] = rs[2] = nullptr;
-    }
-  }
 #pragma unroll
   for (int t = 0; t < 3; ++t) {
     if (rs[t]) {
       const mg_bf16* rp = rs[t] + (int64_t)m * ep.ldr + n;
-      if constexpr (PRE) {
-#pragma unroll
-        for (int r = 0; r < W / 2; ++r) { o[2 * r] += bflo(pre.res[t][r]); o[2 * r + 1] += bfhi(pre.res[t][r]); }
-      } else if (full) {
+      if (full) {
         float a[W];
-        load_bf16_row<W, COH>(rp, a);
+        load_bf16_row<W>(rp, a);
 #pragma unroll
         for (int r = 0; r < W; ++r) o[r] += a[r];
       } else {
@@ -244,70 +168,61 @@ MG_DEV void epilogue_apply_impl(const mg_epilogue& ep, const EpiColsW<W>& c, int
     } else for (int r = 0; r < W; ++r) if (n + r < N) cp[r] = ep.accumulate ? cp[r] + o[r] : o[r];
   } else {
     mg_bf16* cp = (mg_bf16*)ep.C + (int64_t)m * ep.ldc + n;
-    if (full) store_bf16_row<W, NT, COH>(cp, o);
+    if (full) store_bf16_row<W, NT>(cp, o);
     else for (int r = 0; r < W; ++r) if (n + r < N) cp[r] = f2bf(o[r]);
   }
 }
 
-template <int W, bool NT, bool COH = false, bool FULL = false>
-MG_DEV void epilogue_apply(const mg_epilogue& ep, const EpiColsW<W>& c, int m, int n, const float* v, int N) {
-  const EpiPre<W> none{};
-  epilogue_apply_impl<W, NT, COH, false, FULL>(ep, c, m, n, v, N, none);
-}
-
-template <bool COH = false>
 MG_DEV void epilogue_store4(const mg_epilogue& ep, int m, int n, f32x4 v, int N) {
   if (n >= N) return;
-  if constexpr (!COH) {
-    // The common decode / split-K fix-up case -- four columns inside the matrix, no aux operand, no pre-activation copy -- as
-    // one short straight-line block (same arithmetic and order as epilogue_apply_impl).  A weight-streaming GEMV runs its
-    // epilogue ONCE per workgroup, from a cold instruction cache: what counts is how few cache lines the taken path touches.
-    if (n + 3 < N && ep.aux_mode == MG_AUX_NONE && !ep.C2) {
-      f32x4 sc = {1.f, 1.f, 1.f, 1.f}, bi = {0.f, 0.f, 0.f, 0.f};
-      if (ep.scale) sc = *(const f32x4*)(ep.scale + n);
-      if (ep.bias) bi = *(const f32x4*)(ep.bias + n);
-      u32x2 r0 = {0u, 0u}, r1 = {0u, 0u}, r2 = {0u, 0u};
-      if (ep.res0) r0 = *(const u32x2*)(ep.res0 + (int64_t)m * ep.ldr + n);
-      if (ep.res1) r1 = *(const u32x2*)(ep.res1 + (int64_t)m * ep.ldr + n);
-      if (ep.res2) r2 = *(const u32x2*)(ep.res2 + (int64_t)m * ep.ldr + n);
-      float o[4];
+  // The common decode / split-K fix-up case -- four columns inside the matrix, no aux operand, no pre-activation copy -- as
+  // one short straight-line block (same arithmetic and order as epilogue_apply).  A weight-streaming GEMV runs its
+  // epilogue ONCE per workgroup, from a cold instruction cache: what counts is how few cache lines the taken path touches.
+  if (n + 3 < N && ep.aux_mode == MG_AUX_NONE && !ep.C2) {
+    f32x4 sc = {1.f, 1.f, 1.f, 1.f}, bi = {0.f, 0.f, 0.f, 0.f};
+    if (ep.scale) sc = *(const f32x4*)(ep.scale + n);
+    if (ep.bias) bi = *(const f32x4*)(ep.bias + n);
+    u32x2 r0 = {0u, 0u}, r1 = {0u, 0u}, r2 = {0u, 0u};
+    if (ep.res0) r0 = *(const u32x2*)(ep.res0 + (int64_t)m * ep.ldr + n);
+    if (ep.res1) r1 = *(const u32x2*)(ep.res1 + (int64_t)m * ep.ldr + n);
+    if (ep.res2) r2 = *(const u32x2*)(ep.res2 + (int64_t)m * ep.ldr + n);
+    float o[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) o[r] = v[r] * sc[r] + bi[r];
-      if (n >= ep.act_n0 && ep.act != MG_ACT_NONE) {
-        if (ep.act == MG_ACT_RELU) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = o[r] > 0.f ? o[r] : 0.f;
-        } else if (ep.act == MG_ACT_GELU_NEW) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = gelu_new_f(o[r]);
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = apply_act(o[r], ep.act);
-        }
-      }
-      if (ep.res0) { o[0] += bflo(r0[0]); o[1] += bfhi(r0[0]); o[2] += bflo(r0[1]); o[3] += bfhi(r0[1]); }
-      if (ep.res1) { o[0] += bflo(r1[0]); o[1] += bfhi(r1[0]); o[2] += bflo(r1[1]); o[3] += bfhi(r1[1]); }
-      if (ep.res2) { o[0] += bflo(r2[0]); o[1] += bfhi(r2[0]); o[2] += bflo(r2[1]); o[3] += bfhi(r2[1]); }
-      if (ep.act_after == MG_ACT_RELU) {
+    for (int r = 0; r < 4; ++r) o[r] = v[r] * sc[r] + bi[r];
+    if (n >= ep.act_n0 && ep.act != MG_ACT_NONE) {
+      if (ep.act == MG_ACT_RELU) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) o[r] = o[r] > 0.f ? o[r] : 0.f;
-      }
-      if (ep.out_f32) {
-        f32x4* cp = (f32x4*)((float*)ep.C + (int64_t)m * ep.ldc + n);
-        f32x4 w = {o[0], o[1], o[2], o[3]};
-        if (ep.accumulate) w += *cp;
-        *cp = w;
+      } else if (ep.act == MG_ACT_GELU_NEW) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = gelu_new_f(o[r]);
       } else {
-        u32x2 w; w[0] = pack2bf(o[0], o[1]); w[1] = pack2bf(o[2], o[3]);
-        *(u32x2*)((mg_bf16*)ep.C + (int64_t)m * ep.ldc + n) = w;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = apply_act(o[r], ep.act);
       }
-      return;
     }
+    if (ep.res0) { o[0] += bflo(r0[0]); o[1] += bfhi(r0[0]); o[2] += bflo(r0[1]); o[3] += bfhi(r0[1]); }
+    if (ep.res1) { o[0] += bflo(r1[0]); o[1] += bfhi(r1[0]); o[2] += bflo(r1[1]); o[3] += bfhi(r1[1]); }
+    if (ep.res2) { o[0] += bflo(r2[0]); o[1] += bfhi(r2[0]); o[2] += bflo(r2[1]); o[3] += bfhi(r2[1]); }
+    if (ep.act_after == MG_ACT_RELU) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[r] = o[r] > 0.f ? o[r] : 0.f;
+    }
+    if (ep.out_f32) {
+      f32x4* cp = (f32x4*)((float*)ep.C + (int64_t)m * ep.ldc + n);
+      f32x4 w = {o[0], o[1], o[2], o[3]};
+      if (ep.accumulate) w += *cp;
+      *cp = w;
+    } else {
+      u32x2 w; w[0] = pack2bf(o[0], o[1]); w[1] = pack2bf(o[2], o[3]);
+      *(u32x2*)((mg_bf16*)ep.C + (int64_t)m * ep.ldc + n) = w;
+    }
+    return;
   }
   EpiCols c;
   epilogue_cols<4>(ep, n, N, c);
   const float vv[4] = {v[0], v[1], v[2], v[3]};
-  epilogue_apply<4, false, COH>(ep, c, m, n, vv, N);
+  epilogue_apply<4, false>(ep, c, m, n, vv, N);
 }
 
 // 16-byte accesses need every row start 16-byte aligned
@@ -352,7 +267,7 @@ MG_DEV void epilogue_rows_c(const mg_epilogue& ep, const EpiColsW<W>& c, const c
     // epilogue's run-time options are branched on once per iteration -- uniform branches around straight-line code for all
     // two rows -- not once per row and element.  (The per-row form of this loop was ~2 300 instructions of divergent
     // control flow per iteration and took 5 us per 128-row pass of a 256x256 tile; in-kernel stamps, tools/kbench.py stamps.)
-    // Order of the arithmetic as in epilogue_apply_impl: (acc * row_scale) * scale + bias -> [C2] -> act -> aux (before) ->
+    // Order of the arithmetic as in epilogue_apply: (acc * row_scale) * scale + bias -> [C2] -> act -> aux (before) ->
     // residuals 0, 1, 2 -> aux (after) -> trailing ReLU -> store.
     constexpr int R = 2, H = W / 2;      // (four rows: 195 registers in the loop alone -- spills next to the live accumulator half)
     const bool act_on = n >= ep.act_n0;              // act_n0 % 8 == 0: a lane's W columns are on one side
@@ -617,7 +532,7 @@ struct SkinnyParams {
 
 // Device body: `block` is the workgroup's index inside THIS problem's grid, `lds` a caller-provided
 // scratch of skinny_lds_bytes<WAVES,NT>() bytes -- so several problems (and other workgroup kinds,
-// see decode_fused.hip) can share one launch.
+// see decode_attn_gemv_kernel, gemm.hip) can share one launch.
 template <int WAVES, int NT>
 constexpr int skinny_lds_bytes() { return WAVES * NT * 256 * 4 + WAVES * 16 * 2 * 4; }
 
@@ -660,11 +575,6 @@ MG_DEV float e8m0_byte(uint32_t word, int s) { return __builtin_bit_cast(float, 
 // gemv_dma.hip: the same GEMV with an LDS-DMA loader wave and one persistent workgroup per CU (nt_hint bit 17)
 int skinny_dma_launch(const SkinnyParams& sp, int variant, hipStream_t s);
 
-struct NoWait { MG_DEV void operator()() const {} };
-
-// COH: activations in / out go through the coherent 8-byte accessors (persistent decode step); `wait` is called once,
-// AFTER the first chunk's weight loads have been issued and BEFORE the first activation load: inside the persistent
-// launch it blocks on the producer's completion counter while the weights are already streaming in.
 // PIPE: the weight bursts are double-buffered in registers -- burst c+1 is issued BEFORE the MFMAs of burst c, so a wave
 // always has KC..2*KC weight loads in flight instead of draining its queue at every burst boundary.  That matters where
 // occupancy cannot hide the drain: fc_out (N = 4096 -> 256 workgroups of 4 waves, ONE wave per SIMD, 8 bursts of 16 loads
@@ -673,13 +583,12 @@ struct NoWait { MG_DEV void operator()() const {} };
 // burst also loads one word of scales per n-tile and k-step quad, issued with the weights) | WT_PK (bf16 losslessly packed to 13.25
 // bits, SkinnyParams::pk_*: five loads per k-step quad instead of four, 53 bytes per lane instead of 64; same MFMA operands in the
 // same order as WT_BF16 with the same WAVES, hence bit-identical results).
-template <int WAVES, int KC, int NT, int WT = WT_BF16, bool COH = false, class Wait = NoWait, bool PIPE = false>
-MG_DEV void skinny_body(const SkinnyParams& p, int block, char* lds, Wait wait = Wait()) {
+template <int WAVES, int KC, int NT, int WT = WT_BF16, bool PIPE = false>
+MG_DEV void skinny_body(const SkinnyParams& p, int block, char* lds) {
   constexpr bool W8 = WT == WT_FP8, W4 = WT == WT_MX4, WP = WT == WT_PK;
   static_assert(!W8 || KC % 2 == 0, "fp8 weights are stored in k-step pairs");
-  static_assert(!W4 || (KC % 4 == 0 && !PIPE && !COH), "MXFP4 weights are stored in k-step quads; burst-and-drain stream only");
-  static_assert(!PIPE || (!COH && __is_same(Wait, NoWait)), "the pipelined stream has no dependency wait / coherent loads");
-  static_assert(!WP || (KC % 4 == 0 && 4 % NT == 0 && !PIPE && !COH && __is_same(Wait, NoWait)),
+  static_assert(!W4 || (KC % 4 == 0 && !PIPE), "MXFP4 weights are stored in k-step quads; burst-and-drain stream only");
+  static_assert(!WP || (KC % 4 == 0 && 4 % NT == 0 && !PIPE),
                 "packed weights are stored in k-step quads, a workgroup's n-tiles share one flag word; burst-and-drain stream only");
   float* red = (float*)lds;
   const int lane = threadIdx.x & 63;
@@ -715,8 +624,6 @@ MG_DEV void skinny_body(const SkinnyParams& p, int block, char* lds, Wait wait =
       }
     }
   };
-  constexpr bool AHEAD = !__is_same(Wait, NoWait);     // persistent step: first weight burst before the dependency wait
-  if constexpr (AHEAD) { load_w(0); wait(); }
   if constexpr (WP) {
     // one burst of packed weights in registers: per n-tile and k-step quad two loads of low bytes, one of nibbles, the base word
     // (row li) and the lane's sign word -- five loads, 53 bytes per lane, where bf16 has four and 64
@@ -752,7 +659,7 @@ MG_DEV void skinny_body(const SkinnyParams& p, int block, char* lds, Wait wait =
     load_pk(b0, 0);
     constexpr uint32_t tmask = NT >= 4 ? 0xffffffffu : (1u << (8 * (NT & 3))) - 1u;
     if (fw & (tmask << (8 * (nt0 & 3)))) {
-      skinny_body<WAVES, KC, NT, WT_BF16, false, NoWait, false>(p, block, lds);
+      skinny_body<WAVES, KC, NT, WT_BF16, false>(p, block, lds);
       return;
     }
     // one burst (its weight loads are out): the x fragments (L2 hits), the row statistics, then unpack and multiply
@@ -854,21 +761,13 @@ MG_DEV void skinny_body(const SkinnyParams& p, int block, char* lds, Wait wait =
     // Issue the whole chunk's loads before the first MFMA (GEMV recipe: loads
     // straight to VGPRs, deep queue, late wait): weights first (HBM, non-temporal
     // -- each byte is read exactly once per step), then the x fragments (L2 hits).
-    if (!AHEAD || kc > 0) load_w(kc);
+    load_w(kc);
     bf16x8 xf[KC];
-    if constexpr (COH) {
-      static_assert(KC == 8, "the coherent fragment batch is 8 k-steps");
-      u32x4 raw[8];
-      ld16x8_coh(xrow + (int64_t)(ks0 + kc) * 32, raw);
 #pragma unroll
-      for (int i = 0; i < KC; ++i) xf[i] = __builtin_bit_cast(bf16x8, xok ? raw[i] : (u32x4){0u, 0u, 0u, 0u});
-    } else {
-#pragma unroll
-      for (int i = 0; i < KC; ++i) {
-        u32x4 raw = *(const u32x4*)(xrow + (int64_t)(ks0 + kc + i) * 32);
-        if (!xok) raw = (u32x4){0u, 0u, 0u, 0u};
-        xf[i] = __builtin_bit_cast(bf16x8, raw);
-      }
+    for (int i = 0; i < KC; ++i) {
+      u32x4 raw = *(const u32x4*)(xrow + (int64_t)(ks0 + kc + i) * 32);
+      if (!xok) raw = (u32x4){0u, 0u, 0u, 0u};
+      xf[i] = __builtin_bit_cast(bf16x8, raw);
     }
     if (p.ln_colsum && !MG_SKINNY_DBG_NOSTATS(p)) {
 #pragma unroll
@@ -929,8 +828,8 @@ MG_DEV void skinny_body(const SkinnyParams& p, int block, char* lds, Wait wait =
 #pragma unroll
       for (int r = 0; r < 4; ++r) s[r] = rstd * (s[r] - mean * (n + r < p.N ? p.ln_colsum[n + r] : 0.f));
     }
-    if (p.split_n > 0 && n >= p.split_n) epilogue_store4<COH>(p.ep_b, li, n - p.split_n, s, p.N - p.split_n);
-    else epilogue_store4<COH>(p.ep, li, n, s, p.split_n > 0 ? p.split_n : p.N);
+    if (p.split_n > 0 && n >= p.split_n) epilogue_store4(p.ep_b, li, n - p.split_n, s, p.N - p.split_n);
+    else epilogue_store4(p.ep, li, n, s, p.split_n > 0 ? p.split_n : p.N);
   }
 }
 

@@ -182,8 +182,8 @@ __global__ __launch_bounds__(64 * (NL + DMA_NC)) void skinny_dma_kernel(const Sk
 #pragma unroll
       for (int r = 0; r < 4; ++r) sres[r] = rstd * (sres[r] - mean * (n + r < p.N ? p.ln_colsum[n + r] : 0.f));
     }
-    if (p.split_n > 0 && n >= p.split_n) epilogue_store4<false>(p.ep_b, li, n - p.split_n, sres, p.N - p.split_n);
-    else epilogue_store4<false>(p.ep, li, n, sres, p.split_n > 0 ? p.split_n : p.N);
+    if (p.split_n > 0 && n >= p.split_n) epilogue_store4(p.ep_b, li, n - p.split_n, sres, p.N - p.split_n);
+    else epilogue_store4(p.ep, li, n, sres, p.split_n > 0 ? p.split_n : p.N);
   }
 }
 

@@ -109,20 +109,22 @@ def test_chunk_attention_strided_queries_and_wide_output(dev):
 def test_chunk_attention_agrees_with_prefill_and_decode(dev):
     from magma_amd import ops
     B, H, Smax = 2, 2, 256
-    # p = 0: the whole causal prefill of T rows, as attn_fwd_rows computes it
-    T = 77
+    # p = 0: the whole causal prefill of T rows, as attn_fwd_rows computes it -- to the bit: the two kernels are one text, and at
+    # p = 0 they do the same arithmetic in the same order.  T = 128 is a full query block, 130 the first rows of the next one
     kc = rnd(B, H, Smax, 256, dev=dev, seed=7, scale=0.5).to(BF16)
     vc = rnd(B, H, Smax, 256, dev=dev, seed=8).to(BF16)
-    q = rnd(B, H, T, 256, dev=dev, seed=9, scale=0.5).to(BF16)
-    out = torch.empty(B * T, H * 256, dtype=BF16, device=dev)
-    ops.attn_prefill_cached(q, kc, vc, out, B, H, T, torch.zeros(B, dtype=torch.int32, device=dev), pos_stride=1)
-    k, v = kc[:, :, :T].contiguous(), vc[:, :, :T].contiguous()
-    ref = torch.empty_like(out)
-    ops.attn_fwd_rows(ops.AttnRows.of_bhsd(q.contiguous(), k, v), ref)
-    assert rel(out, ref) <= 3e-3
-    kcmp.assert_causal_attention(out, q, k, v, "chunk attention at p = 0")
-    kcmp.assert_causal_attention(ref, q, k, v, "attn_fwd_rows on the same operands")
-    # T = 1: one query per row at its own position, as attn_decode computes it
+    for T in (130, 128, 77):
+        q = rnd(B, H, T, 256, dev=dev, seed=9, scale=0.5).to(BF16)
+        out = torch.empty(B * T, H * 256, dtype=BF16, device=dev)
+        ops.attn_prefill_cached(q, kc, vc, out, B, H, T, torch.zeros(B, dtype=torch.int32, device=dev), pos_stride=1)
+        k, v = kc[:, :, :T].contiguous(), vc[:, :, :T].contiguous()
+        ref = torch.empty_like(out)
+        ops.attn_fwd_rows(ops.AttnRows.of_bhsd(q.contiguous(), k, v), ref)
+        assert rel(out, ref) <= 3e-3, f"T = {T}"
+        assert torch.equal(out, ref), f"T = {T}: {int((out != ref).sum())} elements differ from attn_fwd_rows"
+        kcmp.assert_causal_attention(out, q, k, v, f"chunk attention at p = 0, T = {T}")
+        kcmp.assert_causal_attention(ref, q, k, v, f"attn_fwd_rows on the same operands, T = {T}")
+    # T = 1 (q: the first query of the T = 77 chunk): one query per row at its own position, as attn_decode computes it
     pos = [5, 200]
     d_pos = torch.tensor(pos, dtype=torch.int32, device=dev)
     q1 = q[:, :, :1].contiguous()

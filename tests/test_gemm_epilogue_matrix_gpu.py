@@ -1,6 +1,6 @@
 """One epilogue contract, four hand-written copies: every GEMM path against kernel_compare.epilogue_reference.
 
-mg_epilogue (include/magma_hip.h) is implemented in epilogue_apply_impl, the two-row block of epilogue_rows_c, the fast path of
+mg_epilogue (include/magma_hip.h) is implemented in epilogue_apply, the two-row block of epilogue_rows_c, the fast path of
 epilogue_store4 and its fall-back into epilogue_apply<4> (magma_amd/csrc/gemm_device.h).  Here the named configurations of
 tests/epilogue_cases.py run through every path that reaches one of them, at the smallest shape that reaches the code.  Which
 build a shape selects follows from gemm_dispatch / gemm256_kernel / epilogue_rows (magma_amd/csrc/gemm.hip, gemm_device.h):
