@@ -114,6 +114,64 @@ const char* mg_version(void);
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
+/* ---- Device-resident indices ------------------------------------------------------------------------------------------------------
+ * "Shapes are validated before any launch" covers what the HOST passes.  The token loop never synchronises, so the values that steer
+ * addressing inside it live in device memory -- KV positions (d_pos), the step counter (state[0]), tokens and the token history, beam
+ * parents, contrastive sources, trie nodes, slot windows -- and no entry point can look at them before the launch.  One rule for every
+ * kernel that reads one (DESIGN.md "Device-resident indices" words the same table; tests/test_device_indices_gpu.py holds a case per row):
+ *   - a value outside its range is never turned into an address or a table offset: the compare is unsigned or two-sided and is made
+ *     before anything is formed from the value, and no signed sum can wrap in front of it;
+ *   - SKIP: the row or element the value belongs to is skipped -- nothing of it is written, its output row included, and nothing is
+ *     read through it;
+ *   - CLAMP, where stated: the value counts as the nearest end of its range, and the table says where the access then lands;
+ *   - the other rows of the launch are unaffected, to the bit.
+ * The rotary tables sin_t / cos_t are indexed by a guarded position and no kernel knows their row count: they must hold at least Smax
+ * rows (the three shared-prefix entry points: n_prefix + Smax rows).
+ *
+ *   entry point                              value (range)                              outside the range
+ *   mg_rotary_split_bf16                     d_pos[0] / d_pos[b] + s  ([0, Smax))       SKIP row s (q_out, K, V and the tables untouched)
+ *   mg_rotary_split_at_bf16                  slot d_pos[b] + s, angle row d_pos[b] +    SKIP row s (either one outside)
+ *                                            off[b][s]  (each [0, Smax))
+ *   mg_attn_decode_bf16, _fused_bf16,        d_pos[b * pos_stride]  ([0, Smax))         SKIP row b: no append, no attention, out row untouched
+ *   mg_decode_attn_gemv_bf16                                                            (the co-launched GEMV is unaffected)
+ *   mg_attn_decode_fused_shared_bf16,        d_pos[b]  ([n_prefix, n_prefix + Smax))    below: CLAMP to n_prefix (own index 0, an idle slot);
+ *   mg_decode_attn_gemv_shared_bf16                                                     at or above n_prefix + Smax: SKIP row b
+ *   mg_attn_decode_prefix_bf16               d_pos[b]  (as above)                       below: CLAMP to n_prefix.  Above: NOT guarded -- this launch
+ *                                                                                       is not told Smax; it rotates q at angle row d_pos[b] and
+ *                                                                                       writes partials that the second launch (which skips the
+ *                                                                                       row) never reads.  Only `part` rows of b are written.
+ *   mg_attn_prefill_cached_bf16, _tree_bf16  d_pos[b * pos_stride]  ([0, Smax])         CLAMP into [0, Smax]; key loads land on slots <= Smax - 1
+ *   mg_attn_prefill_tree_bf16                sub[b][j]  ([j + 1, T])                    compared with query indices only, never an index: <= j hides
+ *                                                                                       key j from every query, > T counts as T
+ *   mg_sample_finish, mg_sample_finish_rows  state[0] as history column ([0, cols))     SKIP the history write; step and positions advance
+ *   mg_sample_finish_slots                   state[0], slot[b][0] (any value)           ring: column state[0] mod cols, count in [1, cols]
+ *   mg_slots_admit_bf16, _at_bf16,           state[0] (any value)                       ring column (state[0] - 1) mod cols
+ *   mg_slots_admit_shared_bf16               first_token[j] (any value)                 stored and compared, never an index.  Rows, slots, lengths,
+ *                                                                                       offsets: host arguments, validated before the launch
+ *   mg_logits_process_f32, _constrained_f32  state[0]  ([0, history_cols])              CLAMP: the number of history columns read
+ *                                            history tokens, eos / suppress ids ([0,V)) SKIP that id (no penalty, no ban)
+ *   mg_logits_process_constrained_f32        roots[r], path[r][i], table entries        a node outside [0, n_nodes): the cache entry is not used /
+ *                                                                                       the row is off the trie (eos ids only); edges CLAMP into
+ *                                                                                       [0, n_edges]; a header that does not fit table_ints: no trie
+ *   mg_token_logprobs_f32                    state[0] as column ([0, cols))             SKIP: nothing written
+ *   mg_token_logprobs_f32, _rows_f32         token id ([0, V)), row_of[i] ([0, n_rows)) lp = -inf, nothing read through it
+ *   mg_kv_reorder_bf16                       parent[b]  ([0, R))                        SKIP row b (it is then neither staged nor overwritten)
+ *                                            d_pos  ([0, Smax])                         CLAMP: the number of positions copied
+ *   mg_kv_broadcast_bf16                     src[b]  ([b k, b k + k))                   SKIP the sample
+ *                                            d_pos[r] + pos_delta  ([0, Smax))          SKIP row r
+ *   mg_beam_finish, mg_beam_finish_groups    cand_tok (any value)                       ranked with, stored and compared, never an index; parents are
+ *                                                                                       formed in the launch from list positions, inside the sample
+ *                                            state[0]  ([0, ld))                        below 0: no history column gathered or written; >= ld: ld
+ *                                                                                       columns gathered, none written
+ *   mg_contrastive_sim_bf16                  ctx_len[b]  ([0, Tmax])                    CLAMP: the number of context rows compared
+ *   mg_contrastive_finish                    ctx_len[b]  ([0, Tmax))                    SKIP the append, the length stays
+ *                                            state[0] as history column ([0, cols))     SKIP the history write
+ *   mg_contrastive_topk_f32                  src[b]  ([b k, b k + k))                   CLAMP to row b k
+ *   mg_guidance_follow, mg_advance_pos       token, d_pos                               copied / incremented, never an index
+ *   mg_embedding_bf16                        ids  ([0, vocab))                          CLAMP: row 0 / row vocab - 1
+ *   mg_ce_rows_f32 (mg_ce_reduce_f32,        tgt[r]  ([0, V))                           SKIP: loss 0, gradient 0, not counted, nothing read
+ *   mg_ce_bwd_bf16)                                                                                                                      */
+
 /* Fused epilogue shared by both GEMM kernels:
  *   v = acc * scale[n] + bias[n];  C2[m*ldc2+n] = v (optional, bf16: the
  *   pre-activation a later backward pass needs);  v = act(v);
@@ -348,7 +406,8 @@ int mg_embedding_bf16(const int64_t* ids, int32_t B, int32_t T, const mg_bf16* w
  * rot_dim dims of q,k, scatter K,V into the cache, optional V^T for prefill.
  *   qkv [B*S, 3*H*256];  q_out [B,H,S,256];  kcache/vcache [B,H,Smax,256];
  *   vt (nullable) [B,H,vt_ld/32,256,32] (values transposed in 32-key tiles, vt_ld % 32 == 0);  position of row s = pos0 + s where
- *   pos0 = d_pos ? *d_pos : pos0_host.  sin/cos tables [n_pos, rot_dim/2] f32 */
+ *   pos0 = d_pos ? *d_pos : pos0_host.  sin/cos tables [n_pos, rot_dim/2] f32, n_pos >= Smax.  pos0_host + S > Smax is refused; a
+ *   device position is guarded in the kernel, in both forms: a row s with pos0 + s outside [0, Smax) is skipped ("Device-resident indices") */
 int mg_rotary_split_bf16(const mg_bf16* qkv, int64_t ld_qkv /* row stride in elements, 0 = 3*H*256 */, int32_t B, int32_t S, int32_t H, int32_t rot_dim,
                          const float* sin_t, const float* cos_t, int32_t pos0_host,
                          const int32_t* d_pos, mg_bf16* q_out, mg_bf16* kcache, mg_bf16* vcache,
@@ -430,7 +489,8 @@ int mg_attn_decode_bf16(const mg_bf16* q, const mg_bf16* kcache, const mg_bf16* 
 
 /* K9 epilogue + K10 decode in ONE launch: takes the fused qkv row of the new token
  * [B, 3*H*256], rotates q,k at angle row pos_b, appends k,v at pos_b, attends over [0, pos_b];
- * pos_b = d_pos[b * pos_stride] as in mg_attn_decode_bf16.                                 */
+ * pos_b = d_pos[b * pos_stride] as in mg_attn_decode_bf16.  A pos_b outside [0, Smax) skips the row in all three decode entry
+ * points: nothing is appended, nothing attended over, the output row stays ("Device-resident indices" above).                 */
 int mg_attn_decode_fused_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_bf16* vcache, mg_bf16* out, int32_t B,
                               int32_t H, int32_t Smax, const int32_t* d_pos, int32_t rot_dim,
                               const float* sin_t, const float* cos_t, int32_t pos_stride, void* stream);
@@ -438,7 +498,8 @@ int mg_attn_decode_fused_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_bf16* vcac
 /* Decode attention over ONE prefix shared by all rows (ABI 26; DESIGN.md "Shared session prefix").  Every row b <= 16 of the batch has
  * the same n_prefix cached positions in front of its own: they are stored once, kprefix / vprefix [H, S_prefix, 256] (positions
  * [0, n_prefix) are read), and the rows' caches [B, H, Smax, 256] hold their OWN positions only -- absolute position p >= n_prefix of a
- * row at own index p - n_prefix.  d_pos stays absolute (the rotary angle); a d_pos[b] < n_prefix counts as n_prefix.  Two launches:
+ * row at own index p - n_prefix.  d_pos stays absolute (the rotary angle); a d_pos[b] < n_prefix counts as n_prefix, a d_pos[b] >=
+ * n_prefix + Smax skips the row in the second launch ("Device-resident indices" above; the tables hold n_prefix + Smax rows).  Two launches:
  * mg_attn_decode_prefix_bf16: grid H x n_chunk, n_chunk = ceil(n_prefix / MG_PREFIX_CHUNK) -- a function of n_prefix alone.  Workgroup
  *   (h, c) rotates q of all B rows of the fused qkv [B, 3*H*256] (each at its own position), scores the chunk's keys against all of
  *   them with one set of K loads (row b = MFMA column b) and writes, per row, the chunk's maximum m, sum l = sum exp(s - m) and

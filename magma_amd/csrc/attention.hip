@@ -46,7 +46,10 @@ __global__ __launch_bounds__(256) void rotary_split_kernel(
     const int s = s0 + row;
     const int d0 = c * 8;
     u32x4 vv = (u32x4){0u, 0u, 0u, 0u}, qz = vv, kz = vv;
-    if (s < S && (!PER_ROW || (unsigned)(pos0 + s) < (unsigned)Smax)) {
+    // a position read from device memory (d_pos, either form) is never trusted: a row outside [0, Smax) is skipped -- nothing of
+    // it is read, rotated or written.  s < S <= 2^31 - 1 and the sum is taken unsigned: no signed sum wraps past the compare.  The
+    // host position (d_pos == NULL) was validated by the entry point.
+    if (s < S && (!d_pos || (unsigned)pos0 + (unsigned)s < (unsigned)Smax)) {
       const mg_bf16* base = qkv + (int64_t)(b * S + s) * ld_qkv + h * DH + d0;
       u32x4 qv = *(const u32x4*)base;
       u32x4 kv = *(const u32x4*)(base + dmodel);

@@ -983,7 +983,8 @@ __global__ __launch_bounds__(256) void rotary_split_at_kernel(
     const int s = s0 + row;
     const int d0 = c * 8;
     if (s >= S) continue;
-    const int slot = pos0 + s, pos = pos0 + off[(int64_t)b * S + s];
+    // (both sums unsigned, so that neither can overflow in front of the compare; d_pos and off are device-resident)
+    const int slot = (int)((unsigned)pos0 + (unsigned)s), pos = (int)((unsigned)pos0 + (unsigned)off[(int64_t)b * S + s]);
     if ((unsigned)slot >= (unsigned)Smax || (unsigned)pos >= (unsigned)Smax) continue;
     const mg_bf16* base = qkv + (int64_t)(b * S + s) * ld_qkv + h * DH + d0;
     u32x4 qv = *(const u32x4*)base;

@@ -187,7 +187,8 @@ MG_DEV void attn_prefix_body(const AttnPrefixParams& P, int h, int c, char* lds)
 
 // Device body: `bh` = (batch, head) index, `lds` = ATTN_DEC_LDS bytes of scratch (16-byte aligned).
 // SHARED (FUSED only; shared session prefix, kernel 2; its fields are `S`): the cache holds the row's own positions -- k, v are
-// appended at own index pos - n_prefix (a pos < n_prefix counts as n_prefix), the row attends over its own keys exactly as above,
+// appended at own index pos - n_prefix (a pos < n_prefix counts as n_prefix; a pos >= n_prefix + Smax skips the row like a position
+// outside [0, Smax) in the plain mode: include/magma_hip.h "Device-resident indices"), the row attends over its own keys exactly as above,
 // and the unnormalised result (maximum m, sum l, o) is merged with the row's n_chunk prefix partials in ascending chunk order
 // under one maximum M: out = (e^(m - M) o + sum_c e^(m_c - M) o_c) / (e^(m - M) l + sum_c e^(m_c - M) l_c), rounded to bf16 once.
 template <bool FUSED, bool SHARED = false>
@@ -212,7 +213,11 @@ MG_DEV void attn_decode_body(const AttnDecodeParams& P, int bh, char* lds, const
   const int64_t out_off = P.ld_out ? (int64_t)b * P.ld_out + (int64_t)h * DH : (int64_t)bh * DH;
   static_assert(!SHARED || FUSED, "the shared-prefix mode is the fused body");
   const int pos = SHARED ? max(d_pos[b * P.pos_stride], S.n_prefix) : d_pos[b * P.pos_stride];    // the rotary angle
-  const int own = SHARED ? min(pos - S.n_prefix, Smax - 1) : pos;                                  // the cache index of the new token
+  const int own = SHARED ? pos - S.n_prefix : pos;                                                 // the cache index of the new token
+  // d_pos is device-resident and no entry point can validate it: a row whose index lies outside [0, Smax) appends nothing, attends
+  // over nothing and leaves its output row as it is.  One unsigned compare, uniform over the workgroup (one (b, h) each), in front
+  // of the first barrier and of every address formed from `own` or `pos` (SHARED: pos >= n_prefix >= 1, the difference cannot wrap).
+  if ((unsigned)own >= (unsigned)Smax) return;
   const int ctx = min(own + 1, min(Smax, DEC_MAX_CTX));
   mg_bf16* kb = kcache + (int64_t)bh * Smax * DH;
   mg_bf16* vb = vcache + (int64_t)bh * Smax * DH;

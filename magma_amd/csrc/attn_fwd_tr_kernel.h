@@ -30,7 +30,9 @@ __global__ __launch_bounds__(256) void attn_prefill_tree_tr_kernel(const AttnRow
 
   const int kv_end = min(S, qt0 + 128);
 #else
-  const int p = __builtin_amdgcn_readfirstlane(max(c.d_pos[(int64_t)b * c.pos_stride], 0));
+  // d_pos is device-resident and never trusted: clamped into [0, Smax] before anything is derived from it (below 0 counts as 0,
+  // above Smax as Smax -- a full cache; every key load then clamps to slot Smax - 1 and p + S <= 2 Smax cannot wrap)
+  const int p = __builtin_amdgcn_readfirstlane(min(max(c.d_pos[(int64_t)b * c.pos_stride], 0), c.Smax));
   const int klast = min(p + S, c.Smax) - 1;      // last key row a load may touch
 
   const int kv_end = p + min(S, qt0 + 128);

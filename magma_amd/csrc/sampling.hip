@@ -379,7 +379,7 @@ __global__ void sample_finish_kernel(const int64_t* __restrict__ tok, int B, int
   __syncthreads();
   const int step = s_step;
   for (int i = threadIdx.x; i < n_clear; i += blockDim.x) clear[(int64_t)i * clear_stride] = 0;
-  if (history && step < hist_cols)
+  if (history && step >= 0 && step < hist_cols)        // (the step is device-resident: outside the history nothing is written)
     for (int b = threadIdx.x; b < B; b += blockDim.x) history[(int64_t)b * ld_hist + step] = tok[b];
   if (d_pos)
     for (int b = threadIdx.x; b < n_pos; b += blockDim.x) d_pos[b] += delta;
@@ -531,7 +531,7 @@ __global__ void slots_admit_kernel(SlotsAdmitArgs a) {
     a.vcache[dst + i] = a.vstage[src + i];
   }
   if (threadIdx.x != 0 || h != 0 || l != 0) return;
-  const int prev = a.state[0] - 1;                              // the step whose column the first token takes
+  const int prev = (int)((unsigned)a.state[0] - 1u);            // the step whose column the first token takes (any value: c below lies in the ring)
   const int c = ((prev % a.hist_cols) + a.hist_cols) % a.hist_cols;
   const int b = a.dst_slot[j];
   const int64_t t = a.first_token[j];
@@ -1322,8 +1322,9 @@ __global__ __launch_bounds__(256) void kv_reorder_kernel(uint4* __restrict__ kc,
                                                          int pos_stride, int phase) {
   const int h = blockIdx.x, b = blockIdx.y, l = blockIdx.z;
   auto staged = [&](int row) -> bool {           // row is overwritten and some other row reads it
-    if (parent[row] == row) return false;
-    for (int c = 0; c < R; ++c) if (c != row && parent[c] == row) return true;
+    const int pr = parent[row];
+    if (pr == row || pr < 0 || pr >= R) return false;      // (a row with a parent outside [0, R) is skipped, hence never overwritten:
+    for (int c = 0; c < R; ++c) if (c != row && parent[c] == row) return true;     //  its readers take it from the cache itself)
     return false;
   };
   const int p = parent[b];
@@ -1725,8 +1726,8 @@ __global__ __launch_bounds__(64) void kv_broadcast_kernel(uint4* __restrict__ kc
   const int h = blockIdx.x, r = blockIdx.y, l = blockIdx.z;
   const int b = r / k, s = src[b];
   if (s == r || s < b * k || s >= b * k + k) return;     // written by the bookkeeping launch; never trusted here
-  const int pos = d_pos[r * pos_stride] + pos_delta;
-  if (pos < 0 || pos >= Smax) return;
+  const int pos = (int)((unsigned)d_pos[r * pos_stride] + (unsigned)pos_delta);     // (unsigned: the sum cannot overflow in front of the compare)
+  if ((unsigned)pos >= (unsigned)Smax) return;
   const int64_t per = 32;                                // uint4 per position (256 bf16)
   const int64_t dst = ((((int64_t)l * R + r) * H + h) * Smax + pos) * per;
   const int64_t from = ((((int64_t)l * R + s) * H + h) * Smax + pos) * per;

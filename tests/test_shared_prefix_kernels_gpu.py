@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import kernel_compare as kcmp
+from device_indices import Guarded
 from test_stream_kernels_gpu import EOS_IDS, FILL, HC, SEQS, _session_state
 from test_stream_prefix_kernels_gpu import BOOK, REQS, _caches, admit_at, eq16, first_code
 
@@ -32,29 +33,6 @@ FAMILIES = ("random", "dominant in the prefix", "dominant in the own part", "one
 def rnd(*shape, dev, scale=1.0, seed=0):
     g = torch.Generator(device="cpu").manual_seed(seed)
     return (torch.randn(*shape, generator=g) * scale).to(dev)
-
-
-class Guarded:
-    """A tensor inside a flat buffer with GUARD elements of a NaN pattern in front of and behind it."""
-
-    def __init__(self, shape, dtype, dev):
-        n = 1
-        for s in shape:
-            n *= s
-        self.flat = torch.empty(n + 2 * GUARD, dtype=dtype, device=dev)
-        self.fill_nan(self.flat)
-        self.t = self.flat[GUARD:GUARD + n].view(*shape)
-
-    @staticmethod
-    def fill_nan(t):
-        if t.dtype == BF16:
-            t.view(torch.int16).fill_(NAN16)
-        else:
-            t.fill_(float("nan"))
-
-    def guards_intact(self):
-        g = torch.cat([self.flat[:GUARD], self.flat[-GUARD:]])
-        return bool(g.isnan().all())
 
 
 def tables(rot, n, dev):
