@@ -109,8 +109,10 @@ const char* mg_version(void);
  *  24  request streams: added mg_sample_finish_slots and mg_slots_admit_bf16, MG_STOP_LEN and MG_SLOTS_MAX (nothing moved).
  *  25  session prefix of a request stream: added mg_slots_admit_at_bf16 (nothing moved).
  *  26  shared session prefix: added mg_attn_decode_prefix_bf16, mg_attn_decode_fused_shared_bf16, mg_decode_attn_gemv_shared_bf16,
- *      mg_slots_admit_shared_bf16, MG_PREFIX_CHUNK and MG_PREFIX_PART (nothing moved). */
-#define MG_ABI_VERSION 26
+ *      mg_slots_admit_shared_bf16, MG_PREFIX_CHUNK and MG_PREFIX_PART (nothing moved).
+ *  27  BatchNorm gain gradient from the convolution output instead of the rounded unit output: added mg_scale_rows_acc_bn_grad_f32
+ *      (nothing moved). */
+#define MG_ABI_VERSION 27
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
 
@@ -1029,6 +1031,16 @@ int mg_gelu_erf_bf16(const mg_bf16* x, int64_t ldx, const mg_bf16* g, int64_t ld
                      int32_t cols, void* stream);
 int mg_scale_rows_acc_f32(float* dst, const float* src, int64_t ld_src, const float* row_scale, int32_t rows,
                           int32_t cols, void* stream);
+/* The parameter gradients of a conv + frozen-statistics BatchNorm unit from the UNSCALED fp32 product src = g^T a ([rows = Cout,
+ * cols = Cin k k], row stride ld_src), the bf16 weight w [rows, cols] and gsum[r] = sum_m g[m][r] (ABI 27):
+ *   dst[r][c] += src[r][c] * row_scale[r];   dbeta[r] += gsum[r];
+ *   dgamma[r] += rsqrt(var[r] + eps) * (sum_c src[r][c] * w[r][c] - mean[r] * gsum[r])
+ * sum_c src w = sum_m g z with z = a W^T, the raw convolution output that the forward folds away: dgamma is the layer's own
+ * sum_m g (z - mean) rstd for every gamma, zero included.  mg_bn_param_grad_f32 / mg_transpose_bn_param_grad_bf16 below recover the
+ * normalised activation from the rounded bf16 output instead, (y - sub - beta) / gamma: 2^-9 |y| / |gamma| off per element, and 0 at gamma == 0. */
+int mg_scale_rows_acc_bn_grad_f32(float* dst, const float* src, int64_t ld_src, const mg_bf16* w, const float* row_scale,
+                                  const float* mean, const float* var, float eps, const float* gsum, float* dgamma, float* dbeta,
+                                  int32_t rows, int32_t cols, void* stream);
 int mg_add_gate_bf16(const mg_bf16* a, const mg_bf16* b, const mg_bf16* gate, mg_bf16* out, int64_t n, void* stream);
 int mg_bn_param_grad_f32(const mg_bf16* g, const mg_bf16* y, const mg_bf16* sub, const float* gamma,
                          const float* beta, float* dgamma, float* dbeta, int32_t M, int32_t C, void* stream);

@@ -742,6 +742,41 @@ __global__ __launch_bounds__(256) void scale_rows_acc_kernel(float* __restrict__
   }
 }
 
+// The weight gradient of a conv + frozen-statistics BatchNorm unit and the BatchNorm's own gradients, from the UNSCALED product
+// src = g^T a (fp32, [rows = Cout, cols = Cin k k]); one workgroup per output channel r:
+//   dst[r][c]  += src[r][c] * row_scale[r]                       (as scale_rows_acc_kernel)
+//   dgamma[r]  += rsqrt(var[r] + eps) * (sum_c src[r][c] * w[r][c] - mean[r] * gsum[r])
+//   dbeta[r]   += gsum[r]                                         (gsum = column sums of g)
+// sum_c src[r][c] w[r][c] = sum_m g[m][r] z[m][r] with z = a W^T, the convolution output the forward never stored, so
+// dgamma = sum_m g (z - mean) rstd is the gradient of the layer whatever gamma is (zero included); the output y is not read.
+__global__ __launch_bounds__(256) void scale_rows_acc_bn_grad_kernel(float* __restrict__ dst, const float* __restrict__ src, int64_t lds_,
+                                                                     const mg_bf16* __restrict__ w, const float* __restrict__ row_scale,
+                                                                     const float* __restrict__ mean, const float* __restrict__ var, float eps,
+                                                                     const float* __restrict__ gsum, float* __restrict__ dgamma,
+                                                                     float* __restrict__ dbeta, int cols) {
+  __shared__ float part[4];
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const float s = row_scale[r];
+  const float* sr = src + (int64_t)r * lds_;
+  float* dr = dst + (int64_t)r * cols;
+  const mg_bf16* wr = w + (int64_t)r * cols;
+  float acc = 0.f;
+  for (int c = tid; c < cols; c += 256) {
+    const float v = sr[c];
+    dr[c] += v * s;
+    acc += v * bf2f(wr[c]);
+  }
+  acc = wave_sum(acc);
+  if ((tid & 63) == 0) part[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    const float dot = (part[0] + part[1]) + (part[2] + part[3]);
+    const float gs = gsum[r];
+    dgamma[r] += rsqrtf(var[r] + eps) * (dot - mean[r] * gs);
+    dbeta[r] += gs;
+  }
+}
+
 inline int grid_for(int64_t total) {
   int64_t g = (total + 255) / 256;
   return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
@@ -998,6 +1033,17 @@ extern "C" int mg_scale_rows_acc_f32(float* dst, const float* src, int64_t ld_sr
                                      int32_t cols, void* stream) {
   if (rows <= 0 || cols <= 0 || !dst || !src || ld_src < cols) MG_FAIL(MG_ERR_SHAPE, "mg_scale_rows_acc_f32: bad arguments");
   hipLaunchKernelGGL(scale_rows_acc_kernel, dim3(grid_for((int64_t)rows * cols)), dim3(256), 0, (hipStream_t)stream, dst, src, ld_src, row_scale, rows, cols);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_scale_rows_acc_bn_grad_f32(float* dst, const float* src, int64_t ld_src, const mg_bf16* w, const float* row_scale,
+                                            const float* mean, const float* var, float eps, const float* gsum, float* dgamma,
+                                            float* dbeta, int32_t rows, int32_t cols, void* stream) {
+  if (rows <= 0 || cols <= 0 || ld_src < cols) MG_FAIL(MG_ERR_SHAPE, "mg_scale_rows_acc_bn_grad_f32: rows, cols > 0 and ld_src >= cols required");
+  if (!dst || !src || !w || !row_scale || !mean || !var || !gsum || !dgamma || !dbeta) MG_FAIL(MG_ERR_SHAPE, "mg_scale_rows_acc_bn_grad_f32: null pointer");
+  hipLaunchKernelGGL(scale_rows_acc_bn_grad_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, dst, src, ld_src, w, row_scale, mean, var, eps,
+                     gsum, dgamma, dbeta, cols);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }

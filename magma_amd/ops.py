@@ -1776,6 +1776,22 @@ def scale_rows_acc(dst: torch.Tensor, src: torch.Tensor, row_scale: Optional[tor
           "mg_scale_rows_acc_f32")
 
 
+def scale_rows_acc_bn_grad(dst, src, w, row_scale, mean, var, eps, gsum, dgamma, dbeta):
+    """The parameter gradients of a conv + frozen-statistics BatchNorm unit from the unscaled product src = g^T a (fp32 [Cout, >= K],
+    any row stride), the bf16 weight w [Cout, K] and gsum = the column sums of g:
+    dst[r,c] += src[r,c] * row_scale[r];  dbeta += gsum;  dgamma[r] += rsqrt(var[r] + eps) * (<src[r], w[r]> - mean[r] * gsum[r]).
+    <src[r], w[r]> = sum_m g[m,r] z[m,r] with z the convolution output, which the forward never stores."""
+    _need_gpu(dst, src, w, row_scale, mean, var, gsum, dgamma, dbeta)
+    rows, cols = dst.shape
+    assert dst.dtype == torch.float32 and dst.is_contiguous() and src.dtype == torch.float32 and src.stride(1) == 1
+    assert src.shape[0] == rows and src.shape[1] >= cols and w.dtype == BF16 and w.is_contiguous() and tuple(w.shape) == (rows, cols)
+    for t in (row_scale, mean, var, gsum, dgamma, dbeta):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == rows
+    check(L.load().mg_scale_rows_acc_bn_grad_f32(dst.data_ptr(), src.data_ptr(), src.stride(0), w.data_ptr(), row_scale.data_ptr(),
+                                                 mean.data_ptr(), var.data_ptr(), float(eps), gsum.data_ptr(), dgamma.data_ptr(),
+                                                 dbeta.data_ptr(), rows, cols, _stream()), "mg_scale_rows_acc_bn_grad_f32")
+
+
 def add_gate(a, b=None, gate=None, out=None):
     """out = (a + b) * (gate > 0); b, gate optional; flat bf16 tensors of equal numel (multiple of 8)."""
     _need_gpu(a)

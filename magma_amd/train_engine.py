@@ -124,7 +124,7 @@ class LRScheduler:
 
 _CONV_PLAN = os.environ.get("MAGMA_CONV_PLAN", "1") != "0"               # A/B switch: 0 = one re-layout / BN-fold launch per convolution
 _BOTTOM_PREFIX_ONLY = os.environ.get("MAGMA_BOTTOM_PREFIX_ONLY", "1") != "0"   # A/B switch: 0 = the bottom block's input gradient on all B*S rows
-_BN_GRAD_FUSED = os.environ.get("MAGMA_BN_GRAD_FUSED", "1") != "0"       # A/B switch: 0 = bn_param_grad + transpose as two passes over g
+_BN_GRAD_FUSED = os.environ.get("MAGMA_BN_GRAD_FUSED", "1") != "0"       # A/B switch: 0 = colsum + transpose as two passes over g
 _WGRAD_INPLACE = os.environ.get("MAGMA_WGRAD_INPLACE", "1") != "0"     # A/B switch: 0 = fp32 temporary + scale_rows_acc pass
 
 
@@ -1433,20 +1433,30 @@ class MagmaEngine:
             self.grad_of(bn.weight).add_(dgamma)
             self.grad_of(bn.bias).add_(dbeta)
             g = ops.bn_bwd_dz(g, rec["z"], rec["mean"], rec["rstd"], rec["gamma"], dgamma, dbeta)
-        # the unit's parameter gradients: BatchNorm affine (frozen statistics) + convolution weight
         if rec["batch"]:
             gT = _t(g)
-        elif _BN_GRAD_FUSED and g.is_contiguous() and rec["y"].is_contiguous() and (rec["sub"] is None or rec["sub"].is_contiguous()):
-            # g^T (the weight gradient's operand) and the BatchNorm parameter gradients from ONE pass over g
-            gT = RawWeight(ops.transpose_bn_param_grad(g, rec["y"], rec["sub"], rec["gamma"], rec["beta"], self.grad_of(bn.weight), self.grad_of(bn.bias)))
+            xT = RawWeight(ops.im2col_t(a, Bq, hh, ww, cin)) if rec["kind"] == "3x3" else _t(a)
+            self._acc_wgrad(conv.weight, gT, xT, row_scale=scale)
         else:
-            ops.bn_param_grad(g, rec["y"], rec["sub"], rec["gamma"], rec["beta"], self.grad_of(bn.weight), self.grad_of(bn.bias))
-            gT = _t(g)
-        if rec["kind"] == "3x3":
-            # im2col^T rows come in the weight's own (ci, ky, kx) order -> dW needs no re-layout
-            self._acc_wgrad(conv.weight, gT, RawWeight(ops.im2col_t(a, Bq, hh, ww, cin)), row_scale=scale)
-        else:   # 1x1, or the stem's explicit im2col matrix (columns already in (c, ky, kx) order)
-            self._acc_wgrad(conv.weight, gT, _t(a), row_scale=scale)
+            # frozen statistics: the unit's parameter gradients from the UNSCALED weight gradient g^T a.  dbeta = sum g, and
+            # dgamma = sum g * xhat with xhat = (z - mean) * rstd taken from the convolution output z = a W^T itself, which is
+            # never stored: sum_m g z = <W[co], (g^T a)[co]> (ops.scale_rows_acc_bn_grad).  The stored output
+            # y = bf16([relu](z * scale + shift [+ residual])) is NOT used for xhat: (y - sub - beta) / gamma carries y's rounding
+            # divided by gamma, and at gamma == 0 y holds nothing about z.
+            gsum = torch.zeros(cout, dtype=F32, device=g.device)
+            if _BN_GRAD_FUSED:       # g^T (the weight gradient's operand) and sum g from ONE pass over g
+                gT = RawWeight(ops.transpose_colsum(g, gsum))
+            else:
+                ops.colsum(g, gsum)
+                gT = _t(g)
+            # im2col^T rows come in the weight's own (ci, ky, kx) order; 1x1 and the stem's explicit im2col matrix (columns
+            # already in (c, ky, kx) order) are transposed as they are -> dW needs no re-layout
+            xT = RawWeight(ops.im2col_t(a, Bq, hh, ww, cin)) if rec["kind"] == "3x3" else _t(a)
+            gview = self.grad_of(conv.weight).view(cout, -1)
+            tmp = ops.gemm(gT.rm, xT, out_dtype=F32, layout="rm", use_bias=False)
+            mean, var = self._bn_stats[id(bn)]
+            ops.scale_rows_acc_bn_grad(gview, tmp[:, : gview.shape[1]], w.view(cout, -1), scale, mean, var, bn.eps, gsum,
+                                       self.grad_of(bn.weight), self.grad_of(bn.bias))
         if not need_dgrad:
             return None
         aux_kw = {}

@@ -739,6 +739,61 @@ def test_scale_rows_acc(dev, rows, cols, ld, with_scale):
                             f"scale_rows_acc {rows}x{cols} ld {ld} row_scale={with_scale}")
 
 
+@pytest.mark.parametrize("M,C,K", [(1, 8, 27), (267, 520, 72), (520, 40, 264), (64, 16, 2053)])
+def test_scale_rows_acc_bn_grad(dev, M, C, K):
+    """mg_scale_rows_acc_bn_grad_f32 from src = g^T a (fp32, row stride wider than K), w (bf16 [C, K]) and gsum = sum_m g:
+        dst += src * row_scale[r];  dbeta += gsum;  dgamma[r] += rsqrt(var + eps) * (<src[r], w[r]> - mean[r] gsum[r]),
+    ON TOP of what the three buffers hold.  Checked twice: per element against fp64 on the operands the kernel reads (a row dot of K
+    fp32 products in any order, three more operations, v_rsq_f32), and -- what the entry point is for -- dgamma against the LAYER,
+    sum_m g (z - mean) rstd with z = a W^T in fp64, where the bound also carries the fp32 accumulation of src over M rows.  The
+    gains of this BatchNorm do not enter: the result is the same for gamma = 0 (row_scale = 0 on every fourth row here).
+    Ragged shapes of test_conv_backward_helpers (M 1 / 267 / 520, C 8 / 520 / 40), K = 27 (the stem), below and above one
+    256-thread sweep, and 2053 = 8 sweeps + 5."""
+    from magma_amd import ops
+    eps = 1e-5
+    g, a = rnd(M, C, dev=dev, seed=841).to(BF16), rnd(M, K, dev=dev, seed=842).relu().to(BF16)
+    w = (rnd(C, K, dev=dev, seed=843) * math.sqrt(2.0 / K)).to(BF16)
+    mean, var = rnd(C, dev=dev, seed=844), torch.exp(1.5 * rnd(C, dev=dev, seed=845))
+    rs = rnd(C, dev=dev, seed=846)
+    rs[0::4] = 0.0
+    wide = torch.full((C, K + 5), float("nan"), device=dev)
+    wide[:, :K] = g.float().t() @ a.float()
+    src = wide[:, :K]
+    gsum = g.float().sum(0).contiguous()
+    dst0, dg0, db0 = rnd(C, K, dev=dev, seed=847), rnd(C, dev=dev, seed=848), rnd(C, dev=dev, seed=849)
+    dst, dg, db = dst0.clone(), dg0.clone(), db0.clone()
+    ops.scale_rows_acc_bn_grad(dst, src, w, rs, mean, var, eps, gsum, dg, db)
+    tag = f"scale_rows_acc_bn_grad M={M} C={C} K={K}"
+    f32, s64, w64 = torch.float32, src.double(), w.double()
+    term = s64 * rs.double()[:, None]
+    kcmp.assert_elementwise(dst, dst0.double() + term, kcmp.map_bound(dst0.double() + term, dst0.double().abs() + term.abs(), 2, f32), tag + " dst")
+    kcmp.assert_elementwise(db, db0.double() + gsum.double(), kcmp.map_bound(db0.double() + gsum.double(), db0.double().abs() + gsum.double().abs(), 1, f32),
+                            tag + " dbeta")
+    eps32 = float(torch.tensor(eps, dtype=f32))
+    rstd = (var.double() + eps32).rsqrt()
+    mg = mean.double() * gsum.double()
+
+    def dgamma_bound(dot, dot_mag, dot_err):
+        t = dot - mg
+        e_t = kcmp.gamma(K + 2) * (dot_mag + mg.abs()) + dot_err                 # K products summed in any order, the product, the difference
+        val = rstd * t
+        e_val = rstd * e_t + val.abs() * (kcmp.U_TRANS + 3 * U32)              # var + eps, v_rsq_f32, the product
+        ref = dg0.double() + val
+        return ref, kcmp.rounded(ref, e_val + U32 * (dg0.double().abs() + val.abs()), f32)
+
+    ref, bound = dgamma_bound((s64 * w64).sum(1), (s64 * w64).abs().sum(1), 0.0)
+    kcmp.assert_elementwise(dg, ref, bound, tag + " dgamma (operands)")
+    # the layer: z = a W^T, dgamma = sum_m g (z - mean) rstd; src carries gamma(M) |g|^T |a| of its own
+    g64, a64 = g.double(), a.double()
+    z = a64 @ w64.t()
+    gz_mag = ((g64.abs().t() @ a64.abs()) * w64.abs()).sum(1)
+    operand_err = kcmp.gamma(M) * (gz_mag + mean.double().abs() * g64.abs().sum(0))          # src and gsum: fp32 sums over M rows
+    _, bound_l = dgamma_bound((g64 * z).sum(0), gz_mag, operand_err)
+    ref_l = dg0.double() + (g64 * (z - mean.double()) * rstd).sum(0)
+    kcmp.assert_elementwise(dg, ref_l, bound_l, tag + " dgamma (layer)")
+    assert bool(torch.isnan(wide[:, K:]).all())
+
+
 @pytest.mark.parametrize("n", [4 * 65536, 4 * 1001, 4])
 def test_cast_f32_bf16(dev, n):
     """mg_cast_f32_bf16: round to nearest even, bit for bit what torch's cast gives -- ties to either side and a value just above

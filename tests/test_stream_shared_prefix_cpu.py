@@ -68,4 +68,4 @@ def test_the_chunking_depends_on_the_prefix_alone():
     assert (ops.PREFIX_CHUNK, ops.PREFIX_PART) == (64, 264)
     assert [ops.prefix_chunks(p) for p in (1, 63, 64, 65, 128, 129, 656, 4096)] == [1, 1, 1, 2, 2, 3, 11, 64]
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "magma_hip.h")).read()
-    assert "#define MG_PREFIX_CHUNK 64" in header and "#define MG_PREFIX_PART 264" in header and "#define MG_ABI_VERSION 26" in header
+    assert "#define MG_PREFIX_CHUNK 64" in header and "#define MG_PREFIX_PART 264" in header and "#define MG_ABI_VERSION 27" in header
