@@ -111,7 +111,9 @@ const char* mg_version(void);
  *  26  shared session prefix: added mg_attn_decode_prefix_bf16, mg_attn_decode_fused_shared_bf16, mg_decode_attn_gemv_shared_bf16,
  *      mg_slots_admit_shared_bf16, MG_PREFIX_CHUNK and MG_PREFIX_PART (nothing moved).
  *  27  BatchNorm gain gradient from the convolution output instead of the rounded unit output: added mg_scale_rows_acc_bn_grad_f32
- *      (nothing moved). */
+ *      (nothing moved).  Choosing over a request stream: added mg_logits_process_slots_f32,
+ *      mg_logits_process_constrained_slots_f32 and mg_token_logprobs_slots_f32 (nothing moved, no revision bump: a package that
+ *      binds them names the missing symbol when it meets an older library). */
 #define MG_ABI_VERSION 27
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
@@ -156,6 +158,11 @@ const char* mg_last_error(void);
  *                                                                                       the row is off the trie (eos ids only); edges CLAMP into
  *                                                                                       [0, n_edges]; a header that does not fit table_ints: no trie
  *   mg_token_logprobs_f32                    state[0] as column ([0, cols))             SKIP: nothing written
+ *   mg_logits_process_slots_f32,             finish[r][0] >= 0 (idle), slot[r][0]       SKIP row r: logits / lp untouched, no history, root or path
+ *   _constrained_slots_f32,                  outside [0, history_cols)                  entry of the row read
+ *   mg_token_logprobs_slots_f32              state[0] (any value)                       ring column (state[0] - 1) mod history_cols, count in
+ *                                                                                       [1, history_cols]; the lp column = the count: >= cols SKIP
+ *                                            tokens, ids, roots, path, table entries    as the flat twins above
  *   mg_token_logprobs_f32, _rows_f32         token id ([0, V)), row_of[i] ([0, n_rows)) lp = -inf, nothing read through it
  *   mg_kv_reorder_bf16                       parent[b]  ([0, R))                        SKIP row b (it is then neither staged nor overwritten)
  *                                            d_pos  ([0, Smax])                         CLAMP: the number of positions copied
@@ -750,6 +757,35 @@ int mg_logits_process_constrained_f32(float* logits, int64_t ld, int32_t R, int3
                                       int32_t min_new_tokens, int64_t eos, const int32_t* suppress, int32_t n_suppress,
                                       const int32_t* eos_more, int32_t n_eos_more, const int32_t* table, int64_t table_ints,
                                       const int32_t* roots, int32_t* path, void* stream);
+
+/* The three launches above for the rows of a slot session (DESIGN.md "Choosing over a request stream"; host statement of the
+ * window: magma_amd/sampling.py, slot_tokens): each takes its flat twin's arguments, then slot [R][2] = {begin, limit} and finish
+ * [R][2] = {step or -1, code} -- the tables mg_sample_finish_slots keeps (device int32, read at run time) --, and
+ * mg_token_logprobs_slots_f32 also the ring's column count, which its twin has no argument for.  history is the RING
+ * [R, ld_history >= history_cols] and is never optional.  Per row r, with s = state[0]:
+ *   idle      finish[r][0] >= 0 (finished and not harvested, or never occupied), or begin outside [0, history_cols): the row is
+ *             skipped -- its logits keep their bits, no lp / top column is written, nothing of its history, root or path is read;
+ *   occupied  the occupant has n = (((s - 1) mod history_cols) - begin) mod history_cols + 1 tokens, token i at ring column
+ *             (begin + i) mod history_cols: the twin's row with len = n, step = n (min_new_tokens compares n) over exactly these
+ *             columns -- across the wrap, never a column outside the window --, the same bits as the twin gives on the unrolled
+ *             window with state[0] = n.  The log-probability launch writes column n of row r (column 0 is the admission's);
+ *             n >= cols writes nothing.
+ * path keeps its prove-before-trust rule: what the slot's previous occupant or another table left fails the proof.
+ * Enqueue-only, graph-capturable, one workgroup per row, no allocation, no scratch.                                            */
+int mg_logits_process_slots_f32(float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* state, const int64_t* history,
+                                int64_t ld_history, int32_t history_cols, float repetition_penalty, int32_t no_repeat_ngram,
+                                int32_t min_new_tokens, int64_t eos, const int32_t* suppress, int32_t n_suppress, int32_t normalize,
+                                const int32_t* eos_more, int32_t n_eos_more, const int32_t* slot, const int32_t* finish,
+                                void* stream);
+int mg_logits_process_constrained_slots_f32(float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* state,
+                                            const int64_t* history, int64_t ld_history, int32_t history_cols,
+                                            float repetition_penalty, int32_t no_repeat_ngram, int32_t min_new_tokens, int64_t eos,
+                                            const int32_t* suppress, int32_t n_suppress, const int32_t* eos_more, int32_t n_eos_more,
+                                            const int32_t* table, int64_t table_ints, const int32_t* roots, int32_t* path,
+                                            const int32_t* slot, const int32_t* finish, void* stream);
+int mg_token_logprobs_slots_f32(const float* logits, int64_t ld, int32_t R, int32_t V, const int64_t* token, const int32_t* state,
+                                float* lp, int64_t ld_lp, int32_t cols, int32_t n_top, int32_t* top_id, float* top_lp,
+                                const int32_t* slot, const int32_t* finish, int32_t history_cols, void* stream);
 
 /* Classifier-free guidance (ABI 18; DESIGN.md "Classifier-free guidance"; host statement: magma_amd/sampling.py, guide_logits):
  * the rule of transformers' UnbatchedClassifierFreeGuidanceLogitsProcessor with the plausibility cut of contrastive decoding, in

@@ -853,11 +853,10 @@ __global__ __launch_bounds__(ST) void beam_topk_pre_kernel(const float* __restri
 // log-probability of the row's token and the n_top most probable tokens, from row_topk_body's max / logsumexp -- the arithmetic
 // of the beam step -- ranked by the raw logit.  One workgroup per row; column c = state[0] of the per-step buffers (0 without a
 // state); c outside [0, cols) writes nothing; a token outside [0, V) reads nothing and gives -inf.
-__global__ __launch_bounds__(ST) void token_logprobs_kernel(const float* __restrict__ logits, int64_t ld, int V,
-                                                            const int64_t* __restrict__ token, const int32_t* __restrict__ state,
-                                                            float* __restrict__ lp, int64_t ld_lp, int cols, int n_top,
-                                                            int32_t* __restrict__ top_id, float* __restrict__ top_lp) {
-  const int row = blockIdx.x, c = state ? state[0] : 0;
+MG_DEV void token_logprobs_body(const float* __restrict__ logits, int64_t ld, int V, const int64_t* __restrict__ token, int c,
+                                float* __restrict__ lp, int64_t ld_lp, int cols, int n_top, int32_t* __restrict__ top_id,
+                                float* __restrict__ top_lp) {
+  const int row = blockIdx.x;
   if (c < 0 || c >= cols) return;            // (uniform over the workgroup)
   const float* x = logits + (int64_t)row * ld;
   const int64_t slot = ((int64_t)row * cols + c) * n_top;
@@ -866,6 +865,61 @@ __global__ __launch_bounds__(ST) void token_logprobs_kernel(const float* __restr
     const int64_t t = token[row];
     lp[(int64_t)row * ld_lp + c] = t >= 0 && t < V ? (x[t] - s.mx) - s.lse : -INFINITY;
   }
+}
+
+__global__ __launch_bounds__(ST) void token_logprobs_kernel(const float* __restrict__ logits, int64_t ld, int V,
+                                                            const int64_t* __restrict__ token, const int32_t* __restrict__ state,
+                                                            float* __restrict__ lp, int64_t ld_lp, int cols, int n_top,
+                                                            int32_t* __restrict__ top_id, float* __restrict__ top_lp) {
+  token_logprobs_body(logits, ld, V, token, state ? state[0] : 0, lp, ld_lp, cols, n_top, top_id, top_lp);
+}
+
+// A row's tokens so far, as the logits processors and the trie walk read them (DESIGN.md "Choosing over a request stream"): token
+// i = 0 .. len - 1 at h[(begin + i) % cols].  RING = false is the plain history -- begin = 0, len <= cols, h[i] as it always was --;
+// RING = true is a slot's window of the ring history, walked across the wrap (begin in [0, cols), len in [1, cols]: one
+// conditional subtraction, in unsigned arithmetic, is the modulus).
+template <bool RING>
+struct HistView {
+  const int64_t* h; int begin, len, cols;
+  MG_DEV int64_t operator[](int i) const {
+    if constexpr (!RING) return h[i];
+    else {
+      uint32_t c = (uint32_t)begin + (uint32_t)i;
+      if (c >= (uint32_t)cols) c -= (uint32_t)cols;
+      return h[c];
+    }
+  }
+};
+
+// The window of row b of a slot session before this step's selection, from the tables mg_sample_finish_slots keeps
+// (slot[b] = {begin, limit}, finish[b] = {step or -1, code}) and s = state[0]: the occupant's n = ((s - 1) % cols - begin) mod
+// cols + 1 tokens from column begin on -- the count sample_finish_slots_kernel forms.  n = 0: the row is idle (finished and not
+// harvested yet, or never occupied) or its begin lies outside the ring; such a row is skipped whole.  s is any value: the
+// column is formed as slots_admit_kernel forms it, and n lies in [1, cols] by construction.
+struct SlotWin { int begin, n; };
+MG_DEV SlotWin slot_window(const int32_t* __restrict__ state, const int32_t* __restrict__ slot, const int32_t* __restrict__ finish,
+                           int b, int cols) {
+  if (finish[2 * (int64_t)b] >= 0) return SlotWin{0, 0};
+  const int begin = slot[2 * (int64_t)b];
+  if (begin < 0 || begin >= cols) return SlotWin{0, 0};
+  const int prev = (int)((unsigned)state[0] - 1u);
+  const int col = ((prev % cols) + cols) % cols;
+  int d = col - begin;                      // in (-cols, cols)
+  if (d < 0) d += cols;
+  return SlotWin{begin, d + 1};
+}
+
+// mg_token_logprobs_slots_f32: the body above at column n of an occupied row (column 0 is the admission's); an idle row and a
+// column at or beyond cols write nothing.
+__global__ __launch_bounds__(ST) void token_logprobs_slots_kernel(const float* __restrict__ logits, int64_t ld, int V,
+                                                                  const int64_t* __restrict__ token, const int32_t* __restrict__ state,
+                                                                  float* __restrict__ lp, int64_t ld_lp, int cols, int n_top,
+                                                                  int32_t* __restrict__ top_id, float* __restrict__ top_lp,
+                                                                  const int32_t* __restrict__ slot, const int32_t* __restrict__ finish,
+                                                                  int hist_cols) {
+  const SlotWin w = slot_window(state, slot, finish, blockIdx.x, hist_cols);
+  if (w.n == 0) return;                      // (uniform over the workgroup)
+  token_logprobs_body(logits, ld, V, token, w.n, lp, ld_lp, cols, n_top, top_id, top_lp);
 }
 
 // Classifier-free guidance (DESIGN.md "Classifier-free guidance"; host statement: sampling.py guide_logits): the rule of transformers'
@@ -967,13 +1021,18 @@ struct ProcessParams {
   const int32_t* eos_more; int n_eos_more;   // further eos ids of the min-new-tokens rule (per-row stopping with an eos list)
 };
 
-// the rules of one row; ``seen``: V bits of LDS (only when the penalty applies): token already penalised
-MG_DEV void process_rules(const ProcessParams p, uint32_t* seen, float* shf) {
+// the plain history of the launch's row: tokens [0, min(state[0], hist_cols)) from column 0
+MG_DEV HistView<false> flat_view(const ProcessParams& p) {
+  return HistView<false>{p.history + (int64_t)blockIdx.x * p.ld_hist, 0, max(0, min(p.state[0], p.hist_cols)), p.hist_cols};
+}
+
+// the rules of one row over its tokens h, ``step`` = the count min_new_tokens compares; ``seen``: V bits of LDS (only when the
+// penalty applies): token already penalised
+template <class H>
+MG_DEV void process_rules(const ProcessParams p, const H h, const int step, uint32_t* seen, float* shf) {
   const int tid = threadIdx.x, V = p.V;
   float* x = p.x + (int64_t)blockIdx.x * p.ld;
-  const int step = p.state[0];
-  const int len = max(0, min(step, p.hist_cols));
-  const int64_t* h = p.history + (int64_t)blockIdx.x * p.ld_hist;
+  const int len = h.len;
 
   if (p.normalize) {
     float mx = -INFINITY;
@@ -1004,10 +1063,10 @@ MG_DEV void process_rules(const ProcessParams p, uint32_t* seen, float* shf) {
   // from here on every write is -inf and nothing is read back: no ordering between the three rules is needed
   const int n = p.ngram;
   if (n > 0 && len >= n) {
-    const int64_t* pre = h + (len - n + 1);              // the last n - 1 tokens
+    const int pre = len - n + 1;                         // the last n - 1 tokens
     for (int w = tid; w <= len - n; w += ST) {           // one window per thread
       bool eq = true;
-      for (int j = 0; j < n - 1; ++j) eq = eq && h[w + j] == pre[j];
+      for (int j = 0; j < n - 1; ++j) eq = eq && h[w + j] == h[pre + j];
       const int64_t t = h[w + n - 1];
       if (eq && t >= 0 && t < V) x[t] = -INFINITY;
     }
@@ -1026,7 +1085,18 @@ MG_DEV void process_rules(const ProcessParams p, uint32_t* seen, float* shf) {
 __global__ __launch_bounds__(ST) void logits_process_kernel(const ProcessParams p) {
   extern __shared__ uint32_t seen[];
   __shared__ float shf[ST / 64];
-  process_rules(p, seen, shf);
+  process_rules(p, flat_view(p), p.state[0], seen, shf);
+}
+
+// mg_logits_process_slots_f32: the rules over the occupant's window of the ring; an idle row keeps its bits.
+struct SlotParams { const int32_t* slot; const int32_t* finish; };
+
+__global__ __launch_bounds__(ST) void logits_process_slots_kernel(const ProcessParams p, const SlotParams s) {
+  extern __shared__ uint32_t seen[];
+  __shared__ float shf[ST / 64];
+  const SlotWin w = slot_window(p.state, s.slot, s.finish, blockIdx.x, p.hist_cols);
+  if (w.n == 0) return;                      // (uniform over the workgroup)
+  process_rules(p, HistView<true>{p.history + (int64_t)blockIdx.x * p.ld_hist, w.begin, w.n, p.hist_cols}, w.n, seen, shf);
 }
 
 // Constrained decoding (DESIGN.md "Constrained decoding"; host statement: sampling.py constrain_logits; the table's layout:
@@ -1050,15 +1120,13 @@ struct TrieParams {
   int32_t* path;                            // [R, MG_TRIE_MAX_LEN]
 };
 
-__global__ __launch_bounds__(ST) void logits_process_constrained_kernel(const ProcessParams p, const TrieParams c) {
-  extern __shared__ uint32_t bits[];
-  __shared__ float shf[ST / 64];
+template <class H>
+MG_DEV void constrained_body(const ProcessParams p, const TrieParams c, const H h, const int step, uint32_t* bits, float* shf) {
   __shared__ int s_good, s_child[2];
-  process_rules(p, bits, shf);
+  process_rules(p, h, step, bits, shf);
   const int tid = threadIdx.x, V = p.V, row = blockIdx.x;
   float* x = p.x + (int64_t)row * p.ld;
-  const int len = max(0, min(p.state[0], p.hist_cols));
-  const int64_t* h = p.history + (int64_t)row * p.ld_hist;
+  const int len = h.len;
   const int n = c.table[0], e = c.table[1];
   const bool sane = n >= 1 && e >= 0 && 3 + 4 * (int64_t)n + 2 * (int64_t)e <= c.table_ints;
   const int32_t* first = c.table + 2;
@@ -1115,6 +1183,23 @@ __global__ __launch_bounds__(ST) void logits_process_constrained_kernel(const Pr
   __syncthreads();
   for (int v = tid; v < V; v += ST)
     if (!((bits[v >> 5] >> (v & 31)) & 1u)) x[v] = -INFINITY;
+}
+
+__global__ __launch_bounds__(ST) void logits_process_constrained_kernel(const ProcessParams p, const TrieParams c) {
+  extern __shared__ uint32_t bits[];
+  __shared__ float shf[ST / 64];
+  constrained_body(p, c, flat_view(p), p.state[0], bits, shf);
+}
+
+// mg_logits_process_constrained_slots_f32: rules and trie walk over the occupant's window.  path[row] proves itself against the
+// window's tokens, so what a previous occupant (or another table) left there fails the proof and the walk starts at the root.
+__global__ __launch_bounds__(ST) void logits_process_constrained_slots_kernel(const ProcessParams p, const TrieParams c,
+                                                                              const SlotParams s) {
+  extern __shared__ uint32_t bits[];
+  __shared__ float shf[ST / 64];
+  const SlotWin w = slot_window(p.state, s.slot, s.finish, blockIdx.x, p.hist_cols);
+  if (w.n == 0) return;                      // (uniform over the workgroup)
+  constrained_body(p, c, HistView<true>{p.history + (int64_t)blockIdx.x * p.ld_hist, w.begin, w.n, p.hist_cols}, w.n, bits, shf);
 }
 
 struct BeamArgs {
@@ -1385,6 +1470,24 @@ extern "C" int mg_token_logprobs_f32(const float* logits, int64_t ld, int32_t R,
   return MG_OK;
 }
 
+extern "C" int mg_token_logprobs_slots_f32(const float* logits, int64_t ld, int32_t R, int32_t V, const int64_t* token,
+                                           const int32_t* state, float* lp, int64_t ld_lp, int32_t cols, int32_t n_top,
+                                           int32_t* top_id, float* top_lp, const int32_t* slot, const int32_t* finish,
+                                           int32_t history_cols, void* stream) {
+  const char* who = "mg_token_logprobs_slots_f32";
+  if (!logits || !token || !lp || R <= 0 || V <= 0 || ld < V) MG_FAIL(MG_ERR_SHAPE, "%s: bad logits / token / lp / R / V / ld", who);
+  if (!state || !slot || !finish || history_cols < 1)
+    MG_FAIL(MG_ERR_SHAPE, "%s: needs state, slot [R][2], finish [R][2] and history_cols >= 1 (the ring the windows lie in)", who);
+  if (cols < 1 || ld_lp < cols) MG_FAIL(MG_ERR_SHAPE, "%s: need 1 <= cols <= ld_lp, got %d / %lld", who, cols, (long long)ld_lp);
+  if (n_top < 0 || n_top > MG_LOGPROBS_MAX_TOP || n_top > V)
+    MG_FAIL(MG_ERR_SHAPE, "%s: need 0 <= n_top <= min(%d, V), got %d (V = %d)", who, MG_LOGPROBS_MAX_TOP, n_top, V);
+  if (n_top > 0 && (!top_id || !top_lp)) MG_FAIL(MG_ERR_SHAPE, "%s: n_top > 0 needs top_id and top_lp", who);
+  hipLaunchKernelGGL(token_logprobs_slots_kernel, dim3(R), dim3(ST), 0, (hipStream_t)stream, logits, ld, V, token, state, lp, ld_lp,
+                     cols, n_top, n_top > 0 ? top_id : nullptr, n_top > 0 ? top_lp : nullptr, slot, finish, history_cols);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
 extern "C" int mg_logits_guidance_f32(float* cond, int64_t ld_cond, const float* uncond, int64_t ld_uncond, int32_t R, int32_t V,
                                       float scale, float log_min_p, void* stream) {
   if (!cond || !uncond || R <= 0 || V <= 0 || ld_cond < V || ld_uncond < V)
@@ -1457,6 +1560,48 @@ extern "C" int mg_logits_process_constrained_f32(float* logits, int64_t ld, int3
                   min_new_tokens, eos, suppress, n_suppress, 0, eos_more, eos_more ? n_eos_more : 0};
   TrieParams c{table, table_ints, roots, path};
   hipLaunchKernelGGL(logits_process_constrained_kernel, dim3(R), dim3(ST), (size_t)((V + 31) / 32) * 4, (hipStream_t)stream, p, c);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_logits_process_slots_f32(float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* state,
+                                           const int64_t* history, int64_t ld_history, int32_t history_cols,
+                                           float repetition_penalty, int32_t no_repeat_ngram, int32_t min_new_tokens, int64_t eos,
+                                           const int32_t* suppress, int32_t n_suppress, int32_t normalize, const int32_t* eos_more,
+                                           int32_t n_eos_more, const int32_t* slot, const int32_t* finish, void* stream) {
+  // (the window's length needs the ring's column count whatever the rules are: the history is never optional here)
+  const int rc = process_args_check("mg_logits_process_slots_f32", logits, ld, R, V, state, history, ld_history, history_cols,
+                                    repetition_penalty, no_repeat_ngram, min_new_tokens, suppress, n_suppress, eos_more, n_eos_more,
+                                    true, repetition_penalty != 1.0f);
+  if (rc != MG_OK) return rc;
+  if (!slot || !finish) MG_FAIL(MG_ERR_SHAPE, "mg_logits_process_slots_f32: need slot [R][2] and finish [R][2]");
+  const size_t lds = repetition_penalty != 1.0f ? (size_t)((V + 31) / 32) * 4 : 0;
+  ProcessParams p{logits, ld, V, state, history, ld_history, history_cols, repetition_penalty, no_repeat_ngram,
+                  min_new_tokens, eos, suppress, n_suppress, normalize ? 1 : 0, eos_more, eos_more ? n_eos_more : 0};
+  hipLaunchKernelGGL(logits_process_slots_kernel, dim3(R), dim3(ST), lds, (hipStream_t)stream, p, SlotParams{slot, finish});
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_logits_process_constrained_slots_f32(float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* state,
+                                                       const int64_t* history, int64_t ld_history, int32_t history_cols,
+                                                       float repetition_penalty, int32_t no_repeat_ngram, int32_t min_new_tokens,
+                                                       int64_t eos, const int32_t* suppress, int32_t n_suppress,
+                                                       const int32_t* eos_more, int32_t n_eos_more, const int32_t* table,
+                                                       int64_t table_ints, const int32_t* roots, int32_t* path, const int32_t* slot,
+                                                       const int32_t* finish, void* stream) {
+  const char* who = "mg_logits_process_constrained_slots_f32";
+  const int rc = process_args_check(who, logits, ld, R, V, state, history, ld_history, history_cols, repetition_penalty,
+                                    no_repeat_ngram, min_new_tokens, suppress, n_suppress, eos_more, n_eos_more, true, true);
+  if (rc != MG_OK) return rc;
+  if (!table || table_ints < 2 || !roots || !path)
+    MG_FAIL(MG_ERR_SHAPE, "%s: need a table of at least 2 ints, roots [R] and path [R, %d]", who, MG_TRIE_MAX_LEN);
+  if (!slot || !finish) MG_FAIL(MG_ERR_SHAPE, "%s: need slot [R][2] and finish [R][2]", who);
+  ProcessParams p{logits, ld, V, state, history, ld_history, history_cols, repetition_penalty, no_repeat_ngram,
+                  min_new_tokens, eos, suppress, n_suppress, 0, eos_more, eos_more ? n_eos_more : 0};
+  TrieParams c{table, table_ints, roots, path};
+  hipLaunchKernelGGL(logits_process_constrained_slots_kernel, dim3(R), dim3(ST), (size_t)((V + 31) / 32) * 4, (hipStream_t)stream, p,
+                     c, SlotParams{slot, finish});
   MG_CHECK_LAUNCH();
   return MG_OK;
 }

@@ -79,7 +79,9 @@ class KVCache:
         # token log-probabilities (DESIGN.md "Token log-probabilities"), beside the history: fp32 [B, Smax] log-probability of the
         # token selected at step s, and the n_top most probable tokens of that step (int32 / fp32 [B, Smax, n_top]); allocated on
         # first request (SelectionPlan.arm), addresses and n_top are launch arguments of the captured step
+        # (lp_cols: a slot session keeps one column per token of a request's budget instead -- SlotSession sets it; 0: Smax)
         self.lp = self.top_id = self.top_lp = None
+        self.lp_cols = 0
         # constrained decoding (DESIGN.md "Constrained decoding"): the trie table (int32, grown when a table outgrows it), the
         # per-row roots int32 [B] and the kernel's path cache int32 [B, 64]; allocated on first use (SelectionPlan.arm).
         # Addresses and the table's capacity are launch arguments of the captured step, the contents are not; trie_held is the
@@ -110,12 +112,13 @@ class KVCache:
     def alloc_logprobs(self, n_top: int):
         """The per-step log-probability buffers for ``n_top`` alternatives per token (kept when they already have that shape);
         steps captured on other buffers are dropped."""
-        if self.lp is not None and self.lp.shape[1] == self.Smax and self.top_id.shape[2] == n_top:
+        cols = self.lp_cols or self.Smax
+        if self.lp is not None and self.lp.shape[1] == cols and self.top_id.shape[2] == n_top:
             return
         dev = self.k.device
-        self.lp = torch.zeros(self.B, self.Smax, dtype=torch.float32, device=dev)
-        self.top_id = torch.zeros(self.B, self.Smax, n_top, dtype=torch.int32, device=dev)
-        self.top_lp = torch.zeros(self.B, self.Smax, n_top, dtype=torch.float32, device=dev)
+        self.lp = torch.zeros(self.B, cols, dtype=torch.float32, device=dev)
+        self.top_id = torch.zeros(self.B, cols, n_top, dtype=torch.int32, device=dev)
+        self.top_lp = torch.zeros(self.B, cols, n_top, dtype=torch.float32, device=dev)
         self._drop_graphs(lambda key: key.n_top is not None)
 
     def __len__(self):
@@ -1409,7 +1412,13 @@ class SlotSession:
     ``share_prefix`` (DESIGN.md "Shared session prefix"): the live cache holds the rows' OWN positions only, slots x
     ceil64(max_prompt + max_new) -- it carries ONE copy of the prefix (KVCache.prefix_k / prefix_v) that every block's prefix
     launch reads for all rows --, ops.slots_admit(pos0=P, dst0=0) moves staged positions [P, P + len) to own indices [0, len), and
-    every d_pos starts at P.  The staging rows keep their own copies: admission is as above."""
+    every d_pos starts at P.  The staging rows keep their own copies: admission is as above.
+    Rules, constraint, log-probabilities (DESIGN.md "Choosing over a request stream"; sampling.choose_stream): under a plan built
+    with ``processors`` / ``constraint=True`` / ``logprobs`` the token step's launches are the slot entry points, which read every
+    row's OWN tokens -- its window of the ring -- and skip idle rows.  An item then carries its TokenTrie; the admission selects the
+    first token after the step-0 rules and the root mask (the flat kernels over the staging rows), writes column 0 of the slot's
+    log-probability row from the raw staged logits and installs the slot's root; the device table is the forest of the live slots'
+    tries (_install_tries); the harvest returns a finished row's log-probability columns with its tokens, in the same one copy."""
 
     @staticmethod
     def admit_counter(n_pass: int) -> int:
@@ -1432,7 +1441,8 @@ class SlotSession:
         return out
 
     def __init__(self, engine: "LMEngine", plan: SelectionPlan, *, slots: int, max_new: int, max_prompt: int, every: int,
-                 admit_rows: int, seed: Optional[int] = None, prefix=None, share_prefix: bool = False):
+                 admit_rows: int, seed: Optional[int] = None, prefix=None, share_prefix: bool = False,
+                 trie_capacity: Optional[int] = None):
         if not plan.slots or plan.stop is None:
             raise ValueError("a slot session runs under a plan built with slots=True and per-row stopping")
         if not 1 <= slots <= ops.SLOTS_MAX or not 1 <= admit_rows <= slots or max_new < 1 or max_prompt < 1 or every < 1:
@@ -1470,6 +1480,23 @@ class SlotSession:
         self.st = engine._ensure_decode_state(cache)
         if self.st.refusal is not None:
             raise NotImplementedError(self.st.refusal)
+        # choosing over a stream (DESIGN.md "Choosing over a request stream"): the rules, the constraint and the log-probabilities
+        # of a slot plan.  The admission runs the FLAT kernels over the staging rows at step 0 (zero_state) -- their roots, path and
+        # column-0 buffers are the stage_* ones --; the live side's table is the forest of the live slots' tries (_install_tries)
+        i32 = torch.int32
+        self.zero_state = torch.tensor([0, -1], dtype=i32, device=dev)
+        self.stage_hist = torch.zeros(admit_rows, 1, dtype=torch.int64, device=dev)       # (step 0 reads no column of it)
+        self.slot_trie = [None] * slots         # per slot: its occupant's TokenTrie
+        self.root_of, self.roots_held = {}, None  # id(trie) -> its root in the device table; the roots the device holds
+        if plan.cons is not None:
+            cache.alloc_trie((int(trie_capacity) + 1) // 2 if trie_capacity else 1)      # (alloc_trie doubles what it is asked for)
+            self.stage_roots = torch.zeros(admit_rows, dtype=i32, device=dev)
+            self.stage_path = ops.trie_path(admit_rows, dev)
+        if plan.n_top is not None:
+            cache.lp_cols = max_new
+            self.stage_lp = torch.zeros(admit_rows, 1, dtype=torch.float32, device=dev)
+            self.stage_top_id = torch.zeros(admit_rows, 1, plan.n_top, dtype=i32, device=dev)
+            self.stage_top_lp = torch.zeros(admit_rows, 1, plan.n_top, dtype=torch.float32, device=dev)
         plan.arm(cache, self.st, first=True)
         # every slot starts finished and idle at position 0 (shared prefix: at P, own index 0)
         cache.finish.copy_(torch.tensor([[0, ops.STOP_LEN]] * slots, dtype=torch.int32), non_blocking=True)
@@ -1527,12 +1554,72 @@ class SlotSession:
         return self.P + o[2] + min(self.steps - o[4], o[3] - 1)
 
     @torch.no_grad()
+    def _install_tries(self, batch, slots):
+        """The tries of an admission pass: the device table is the forest of the live slots' tries (sampling.trie_forest: one
+        entry per OBJECT), rebuilt and copied only when the pass brings a trie the table does not hold; a table that outgrows the
+        buffer re-allocates it, which drops the captured constrained steps (KVCache.alloc_trie).  A rebuild renumbers the nodes:
+        every live slot's root is rewritten, and what its path cache holds fails its proof and is walked again.  The roots are
+        copied only when they differ from what the device holds.  Returns the staging rows' roots.  Enqueue-only."""
+        from .sampling import trie_forest
+        cache = self.cache
+        for it, b in zip(batch, slots):
+            self.slot_trie[b] = it[3]
+        if any(id(it[3]) not in self.root_of for it in batch):
+            live = [t for t in self.slot_trie if t is not None]
+            table, roots = trie_forest(live)
+            cache.alloc_trie(table.numel())
+            cache.trie_table[: table.numel()].copy_(table, non_blocking=True)
+            self.root_of = {id(t): int(r) for t, r in zip(live, roots.tolist())}
+            self.tries_held = live              # (the objects stay alive: their ids key root_of)
+        roots = [0 if t is None else self.root_of[id(t)] for t in self.slot_trie]
+        if roots != self.roots_held:
+            cache.trie_roots.copy_(torch.tensor(roots, dtype=torch.int32), non_blocking=True)
+            self.roots_held = roots
+        return [self.root_of[id(it[3])] for it in batch] + [0] * (self.n_admit - len(batch))
+
+    def _select_first(self, logits, batch, slots):
+        """The first tokens of an admission pass into self.first, from the staged logits (n_admit, V): the plan's rules at step 0
+        and the root mask of every staging row's own trie, by the flat kernels on a copy; then -- from the RAW logits -- column 0
+        of the slots' log-probability rows.  Enqueue-only."""
+        plan, cache, n = self.plan, self.cache, len(batch)
+        mode, proc, stop, n_top, cons = plan[:5]
+        raw = logits
+        if plan.rewrites_logits:
+            logits = logits.clone() if n_top is not None else logits
+            more = {} if len(stop[0]) < 2 else dict(eos_more=cache.stop_table[1:ops.STOP_MAX_EOS], n_eos_more=len(stop[0]) - 1)
+            rules = proc if proc is not None else (1.0, 0, 0, ())
+            kw = dict(repetition_penalty=rules[0], no_repeat_ngram_size=rules[1], min_new_tokens=rules[2], eos=cache.eos,
+                      suppress=cache.suppress, n_suppress=len(rules[3]), **more)
+            if cons is not None:
+                self.stage_roots.copy_(torch.tensor(self._install_tries(batch, slots), dtype=torch.int32), non_blocking=True)
+                ops.logits_process_constrained(logits, self.zero_state, self.stage_hist, cache.trie_table, self.stage_roots,
+                                               self.stage_path, **kw)
+            else:
+                ops.logits_process(logits, self.zero_state, self.stage_hist, **kw)
+        if mode is None:
+            ops.argmax(logits, out=self.first)
+        else:       # a counter domain of its own: the token steps draw under state[0] = 1, 2, ..., never under a negative value
+            self.admit_state[:1].fill_(self.admit_counter(self.passes))
+            if mode[0] == "warp":
+                ops.sample_warp(logits, mode[1], mode[2], mode[3], mode[4], cache.seed, self.admit_state, out=self.first)
+            else:
+                ops.sample(logits, mode[0], mode[1], mode[2], cache.seed, self.admit_state, out=self.first)
+        if n_top is not None:
+            ops.token_logprobs(raw, self.first, self.stage_lp, self.stage_top_id if n_top else None,
+                               self.stage_top_lp if n_top else None)
+            at = torch.tensor(slots, dtype=torch.int64).to(raw.device, non_blocking=True)
+            cache.lp[:, 0].index_copy_(0, at, self.stage_lp[:n, 0])
+            if n_top:
+                cache.top_id[:, 0].index_copy_(0, at, self.stage_top_id[:n, 0])
+                cache.top_lp[:, 0].index_copy_(0, at, self.stage_top_lp[:n, 0])
+
+    @torch.no_grad()
     def _admit(self, batch, slots):
-        """One staging pass: ``batch`` = [(index, (S, d) embeddings, limit)] goes to the free ``slots`` (as many)."""
+        """One staging pass: ``batch`` = [(index, (S, d) embeddings, limit[, TokenTrie])] goes to the free ``slots`` (as many)."""
         eng, cache, n = self.engine, self.cache, len(batch)
         self.stage_in.zero_()
         lens = [1] * self.n_admit       # unused staging rows: one zero row
-        for j, (_, emb, _) in enumerate(batch):
+        for j, (_, emb, *_) in enumerate(batch):
             lens[j] = emb.shape[0]
             self.stage_in[j, : lens[j]].copy_(emb)
         if self.P:      # behind the prefix: LMEngine.extend's cached-append prefill, every staging row's write position back at P
@@ -1542,21 +1629,13 @@ class SlotSession:
             x, _ = eng._blocks_prefill(self.stage_in, self.stage)
         rows = (torch.arange(self.n_admit, dtype=torch.int64) * self.S_stage + torch.tensor(lens) - 1).to(eng.device, non_blocking=True)
         logits = eng._head(ops.layernorm(x.index_select(0, rows), eng.lnf_g, eng.lnf_b, eng.eps))
-        mode = self.plan.mode
-        if mode is None:
-            ops.argmax(logits, out=self.first)
-        else:       # a counter domain of its own: the token steps draw under state[0] = 1, 2, ..., never under a negative value
-            self.admit_state[:1].fill_(self.admit_counter(self.passes))
-            if mode[0] == "warp":
-                ops.sample_warp(logits, mode[1], mode[2], mode[3], mode[4], cache.seed, self.admit_state, out=self.first)
-            else:
-                ops.sample(logits, mode[0], mode[1], mode[2], cache.seed, self.admit_state, out=self.first)
+        self._select_first(logits, batch, slots)
         self.passes += 1
         stop = self.plan.stop
         ops.slots_admit(self.stage.k, self.stage.v, cache.k, cache.v, list(range(n)), slots, lens[:n], self.first,
                         [it[2] for it in batch], cache.sample_state, cache.d_pos, self.st.token, cache.finish, cache.slot_table,
                         cache.ring, cache.stop_table, len(stop[0]), len(stop[1]), pos0=self.P, dst0=0 if self.shared else None)
-        for j, (index, _, limit) in enumerate(batch):
+        for j, (index, _, limit, *_) in enumerate(batch):
             self.occ[slots[j]] = (index, self.steps % self.Hc, lens[j], limit, self.steps)
 
     @torch.no_grad()
@@ -1566,25 +1645,38 @@ class SlotSession:
         self.steps += 1
 
     def _harvest(self):
-        """[(request index, int64 CPU tokens, finish code, slot)] of the rows that have finished since the last look."""
+        """[(request index, int64 CPU tokens, finish code, slot)] of the rows that have finished since the last look -- under a plan
+        with log-probabilities, followed by (lp [count], top ids [count, n_top], top lp [count, n_top]) of the row's columns."""
         if all(o is None for o in self.occ):
             return []
-        # the one sync of a round: the finish record and the ring in one blocking copy (both are a few KB)
-        both = torch.cat([self.cache.finish.view(-1).to(torch.int64), self.cache.ring.view(-1)]).cpu()
-        fin, ring = both[: 2 * self.B].view(self.B, 2), both[2 * self.B:].view(self.B, self.Hc)
+        # the one sync of a round: the finish record, the ring and -- as their bits -- the log-probability rows in one blocking copy
+        cache, n_top = self.cache, self.plan.n_top
+        parts = [cache.finish.view(-1).to(torch.int64), cache.ring.view(-1)]
+        if n_top is not None:
+            parts += [t.view(torch.int32).view(-1).to(torch.int64) for t in (cache.lp, cache.top_id, cache.top_lp)]
+        both = torch.cat(parts).cpu()
+        fin, ring = both[: 2 * self.B].view(self.B, 2), both[2 * self.B: 2 * self.B + self.B * self.Hc].view(self.B, self.Hc)
+        if n_top is not None:
+            rest, n = both[2 * self.B + self.B * self.Hc:].to(torch.int32), self.B * self.max_new
+            lp = rest[:n].view(torch.float32).view(self.B, self.max_new)
+            top_id = rest[n: n + n * n_top].view(self.B, self.max_new, n_top)
+            top_lp = rest[n + n * n_top:].view(torch.float32).view(self.B, self.max_new, n_top)
         done = [b for b, o in enumerate(self.occ) if o is not None and int(fin[b, 0]) >= 0]
         out = []
         for b in done:
             index, begin = self.occ[b][:2]
             count = (int(fin[b, 0]) % self.Hc - begin) % self.Hc + 1
             cols = (begin + torch.arange(count)) % self.Hc
-            out.append((index, ring[b, cols].clone(), int(fin[b, 1]), b))
-            self.occ[b] = None
+            item = (index, ring[b, cols].clone(), int(fin[b, 1]), b)
+            if n_top is not None:
+                item += ((lp[b, :count].clone(), top_id[b, :count].to(torch.int64), top_lp[b, :count].clone()),)
+            out.append(item)
+            self.occ[b], self.slot_trie[b] = None, None
         return out
 
     def run(self, requests):
-        """Yield (request index, tokens, finish code, slot) in completion order.  ``requests`` yields (index, (S, d) embeddings on
-        the engine's device, limit), is pulled lazily -- one item when a slot frees.  When it raises, nothing more is pulled, the
+        """Yield (request index, tokens, finish code, slot[, log-probabilities: _harvest]) in completion order.  ``requests`` yields
+        (index, (S, d) embeddings on the engine's device, limit[, TokenTrie: under a constrained plan]), is pulled lazily -- one item when a slot frees.  When it raises, nothing more is pulled, the
         requests pulled before it are admitted and every row in flight is generated to its end and yielded; then the error is
         raised: no request in front of the failing one is lost."""
         it, exhausted, error = iter(requests), False, None

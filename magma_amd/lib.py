@@ -147,6 +147,12 @@ SYMBOLS = {
                                         _vp]),
     "mg_logits_process_constrained_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _f32, _i32, _i32, _i64, _vp, _i32, _vp,
                                                     _i32, _vp, _i64, _vp, _vp, _vp]),
+    # choosing over a request stream (added under ABI 27 without a bump: load() names a symbol an older library lacks)
+    "mg_logits_process_slots_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _f32, _i32, _i32, _i64, _vp, _i32, _i32, _vp,
+                                              _i32, _vp, _vp, _vp]),
+    "mg_logits_process_constrained_slots_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _f32, _i32, _i32, _i64, _vp, _i32,
+                                                          _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "mg_token_logprobs_slots_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "mg_logits_guidance_f32": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _f32, _f32, _vp]),
     "mg_guidance_follow": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "mg_beam_finish": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, C.c_double, _i32, _i32, _vp, _vp, _i32, C.POINTER(BeamState), _vp]),
@@ -249,7 +255,11 @@ def load() -> C.CDLL:
         raise MagmaHipError(f"{path} speaks C-ABI revision {abi}, this package binds revision {ABI_VERSION} "
                             "(include/magma_hip.h MG_ABI_VERSION): rebuild with `make -C magma_amd/csrc`")
     for name, (res, args) in SYMBOLS.items():
-        fn = getattr(lib, name)  # AttributeError if the symbol is missing
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise MagmaHipError(f"{path} has no symbol {name}: the library is older than this package (entry points are added "
+                                f"within a C-ABI revision): rebuild with `make -C magma_amd/csrc`") from None
         fn.restype = res
         fn.argtypes = args
     _lib = lib

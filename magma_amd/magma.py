@@ -356,6 +356,15 @@ class Magma(nn.Module):
         torch.cuda.set_device(self.device)
         return choose(self, embeddings, choices, lengths=lengths, **generate_kwargs)
 
+    def choose_stream(self, requests, **kwargs):
+        """``choose`` over a stream of requests -- an iterable of pairs (``embed`` output, that request's choices) --: a generator
+        of ``sampling.StreamChoice(index, choice, tokens, logprobs, top_ids, top_logprobs, reason, slot)``, one per request in
+        completion order, each what a solo ``choose`` of that request gives.  The HIP engine runs them through the slots of a
+        request stream: a short answer frees its row for the next request (see sampling.choose_stream for the keywords)."""
+        from .sampling import choose_stream
+        torch.cuda.set_device(self.device)
+        return choose_stream(self, requests, **kwargs)
+
     @torch.no_grad()
     def rank(self, embeddings, choices, lengths=None, *, eos: bool = True, length_penalty: float = 0.0, max_nodes: int = None,
              return_terms: bool = False):

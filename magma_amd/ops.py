@@ -1077,6 +1077,71 @@ def logits_process_constrained(logits: torch.Tensor, state: torch.Tensor, histor
     return logits
 
 
+def _slot_operands(R: int, state: torch.Tensor, history: torch.Tensor, slot: torch.Tensor, finish: torch.Tensor):
+    """The checks the three slot launches share: the state, the ring history and the tables sample_finish_slots keeps."""
+    assert state is not None and state.dtype == torch.int32 and state.numel() >= 1
+    assert history.dtype == torch.int64 and history.ndim == 2 and history.stride(1) == 1 and history.shape[0] == R
+    assert slot.dtype == torch.int32 and slot.is_contiguous() and slot.shape == (R, 2)
+    assert finish.dtype == torch.int32 and finish.is_contiguous() and finish.shape == (R, 2)
+
+
+def _counted(t: Optional[torch.Tensor], n: Optional[int]) -> int:
+    """How many leading entries of the device int32 array ``t`` count (default: all)."""
+    if t is not None:
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    n = (0 if t is None else t.numel()) if n is None else int(n)
+    assert n == 0 or (t is not None and n <= t.numel())
+    return n
+
+
+def logits_process_slots(logits: torch.Tensor, state: torch.Tensor, history: torch.Tensor, slot: torch.Tensor, finish: torch.Tensor, *,
+                         repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, eos: int = -1,
+                         suppress: Optional[torch.Tensor] = None, n_suppress: Optional[int] = None, normalize: bool = False,
+                         eos_more: Optional[torch.Tensor] = None, n_eos_more: Optional[int] = None):
+    """logits_process for the rows of a slot session (mg_logits_process_slots_f32; host statement of the window:
+    sampling.slot_tokens): ``history`` is the ring, ``slot`` int32 [R, 2] = (begin column, budget) and ``finish`` int32 [R, 2] the
+    tables sample_finish_slots keeps.  An occupied row gets the rules over its occupant's n tokens in ring order, with n as the
+    step; an idle row (finish[r, 0] >= 0) keeps its bits.  Enqueue-only."""
+    _need_gpu(logits, state, history, suppress, eos_more, slot, finish)
+    assert logits.dtype == torch.float32 and logits.ndim == 2 and logits.stride(1) == 1
+    R, V = logits.shape
+    _slot_operands(R, state, history, slot, finish)
+    ns, nm = _counted(suppress, n_suppress), _counted(eos_more, n_eos_more)
+    check(L.load().mg_logits_process_slots_f32(logits.data_ptr(), logits.stride(0), R, V, state.data_ptr(), history.data_ptr(),
+                                               history.stride(0), history.shape[1], float(repetition_penalty),
+                                               int(no_repeat_ngram_size), int(min_new_tokens), int(eos), _p(suppress), ns,
+                                               1 if normalize else 0, _p(eos_more) if nm else None, nm, slot.data_ptr(),
+                                               finish.data_ptr(), _stream()),
+          "mg_logits_process_slots_f32")
+    return logits
+
+
+def logits_process_constrained_slots(logits: torch.Tensor, state: torch.Tensor, history: torch.Tensor, table: torch.Tensor,
+                                     roots: torch.Tensor, path: torch.Tensor, slot: torch.Tensor, finish: torch.Tensor, *,
+                                     repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
+                                     eos: int = -1, suppress: Optional[torch.Tensor] = None, n_suppress: Optional[int] = None,
+                                     eos_more: Optional[torch.Tensor] = None, n_eos_more: Optional[int] = None):
+    """logits_process_constrained for the rows of a slot session (mg_logits_process_constrained_slots_f32): the rules and the trie
+    walk run over the occupant's window of the ring ``history`` (logits_process_slots); ``path`` rows of an earlier occupant fail
+    their proof and are re-walked from ``roots[r]``.  An idle row keeps its bits.  Enqueue-only."""
+    _need_gpu(logits, state, history, suppress, eos_more, table, roots, path, slot, finish)
+    assert logits.dtype == torch.float32 and logits.ndim == 2 and logits.stride(1) == 1
+    R, V = logits.shape
+    _slot_operands(R, state, history, slot, finish)
+    assert table.dtype == torch.int32 and table.is_contiguous() and table.ndim == 1 and table.numel() >= 2
+    assert roots.dtype == torch.int32 and roots.is_contiguous() and roots.numel() >= R
+    assert path.dtype == torch.int32 and path.is_contiguous() and path.ndim == 2 and path.shape[0] >= R and path.shape[1] == TRIE_MAX_LEN
+    ns, nm = _counted(suppress, n_suppress), _counted(eos_more, n_eos_more)
+    check(L.load().mg_logits_process_constrained_slots_f32(logits.data_ptr(), logits.stride(0), R, V, state.data_ptr(),
+                                                           history.data_ptr(), history.stride(0), history.shape[1],
+                                                           float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens),
+                                                           int(eos), _p(suppress), ns, _p(eos_more) if nm else None, nm,
+                                                           table.data_ptr(), table.numel(), roots.data_ptr(), path.data_ptr(),
+                                                           slot.data_ptr(), finish.data_ptr(), _stream()),
+          "mg_logits_process_constrained_slots_f32")
+    return logits
+
+
 def logits_guidance(cond: torch.Tensor, uncond: torch.Tensor, scale: float, min_p: float = 0.0):
     """Classifier-free guidance in place on the fp32 rows ``cond`` (R, V) against ``uncond`` (R, V), one launch of one workgroup
     per pair (mg_logits_guidance_f32; host statement: sampling.guide_logits): with c / u the log_softmax of the two rows,
@@ -1150,6 +1215,37 @@ def token_logprobs(logits: torch.Tensor, token: torch.Tensor, lp: torch.Tensor, 
                                          lp.stride(0) if R > 1 else max(lp.stride(0), cols), cols, n_top,
                                          _p(top_id) if n_top else None, _p(top_lp) if n_top else None, _stream()),
           "mg_token_logprobs_f32")
+    return lp
+
+
+def token_logprobs_slots(logits: torch.Tensor, token: torch.Tensor, lp: torch.Tensor, top_id: Optional[torch.Tensor],
+                         top_lp: Optional[torch.Tensor], state: torch.Tensor, slot: torch.Tensor, finish: torch.Tensor,
+                         ring_cols: int):
+    """token_logprobs for the rows of a slot session (mg_token_logprobs_slots_f32): an occupied row writes column n of ``lp`` /
+    ``top_id`` / ``top_lp`` -- n = the tokens its occupant has generated before this step, from ``state[0]``, ``slot`` and
+    ``finish`` (sample_finish_slots' tables) over a ring of ``ring_cols`` columns; column 0 belongs to the admission --, an idle
+    row and a column >= lp.shape[1] write nothing.  Enqueue-only."""
+    _need_gpu(logits, token, lp, top_id, top_lp, state, slot, finish)
+    assert logits.dtype == torch.float32 and logits.ndim == 2 and logits.stride(1) == 1
+    R, V = logits.shape
+    assert token.dtype == torch.int64 and token.is_contiguous() and token.numel() == R
+    assert lp.dtype == torch.float32 and lp.ndim == 2 and lp.shape[0] == R and lp.shape[1] >= 1
+    assert lp.stride(1) == 1 and (R == 1 or lp.stride(0) >= lp.shape[1])
+    cols = lp.shape[1]
+    assert (top_id is None) == (top_lp is None), "top_id and top_lp come together"
+    n_top = 0
+    if top_id is not None:
+        assert top_id.dtype == torch.int32 and top_lp.dtype == torch.float32 and top_id.is_contiguous() and top_lp.is_contiguous()
+        assert top_id.ndim == 3 and top_id.shape[:2] == (R, cols) and top_lp.shape == top_id.shape
+        n_top = top_id.shape[2]
+    assert state is not None and state.dtype == torch.int32 and state.numel() >= 1
+    assert slot.dtype == torch.int32 and slot.is_contiguous() and slot.shape == (R, 2)
+    assert finish.dtype == torch.int32 and finish.is_contiguous() and finish.shape == (R, 2)
+    check(L.load().mg_token_logprobs_slots_f32(logits.data_ptr(), logits.stride(0), R, V, token.data_ptr(), state.data_ptr(),
+                                               lp.data_ptr(), lp.stride(0) if R > 1 else max(lp.stride(0), cols), cols, n_top,
+                                               _p(top_id) if n_top else None, _p(top_lp) if n_top else None, slot.data_ptr(),
+                                               finish.data_ptr(), int(ring_cols), _stream()),
+          "mg_token_logprobs_slots_f32")
     return lp
 
 

@@ -769,6 +769,21 @@ def slot_update(ring, step: int, done, begin, limit, eos_ids, stop_seqs=()):
     return done, reason
 
 
+def slot_tokens(ring_row, begin: int, step: int, cols: int):
+    """The tokens a slot's occupant has generated BEFORE step ``step`` (the device's state[0]) selects, in order, host statement
+    of the window the slot kernels read (csrc/sampling.hip, slot_window / HistView): ``ring_row`` is the row of the ring history of
+    ``cols`` columns, ``begin`` the column of the occupant's first token (slot_update's).  The newest token stands at column
+    (step - 1) % cols, so there are n = ((step - 1) % cols - begin) % cols + 1 of them -- the count slot_update forms at the step
+    before --, token i at column (begin + i) % cols: a window that reaches the last column goes on at column 0.  n lies in
+    [1, cols]; no column outside the window is read."""
+    row = torch.as_tensor(ring_row).to(torch.int64).cpu().view(-1)
+    begin, step, cols = int(begin), int(step), int(cols)
+    if cols < 1 or row.numel() < cols or not 0 <= begin < cols:
+        raise ValueError(f"need a ring row of at least cols = {cols} >= 1 columns and 0 <= begin < cols, got begin = {begin}")
+    n = ((step - 1) % cols - begin) % cols + 1
+    return row[(begin + torch.arange(n)) % cols].clone()
+
+
 def finish_from_record(record, n_gen: int) -> Finish:
     """``record`` (B, 2) integers = (step at which the row finished or -1, reason * 256 + index) -- the device's finish record,
     or the host loop's in the same form -- of a call that kept n_gen steps."""
@@ -1678,74 +1693,12 @@ def _max_positions(model):
     return int(n) if isinstance(n, int) else None
 
 
-def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 100, max_prompt: int = None, eos_token=None,
-                    stop_sequences=None, temperature: float = 0.0, top_k: int = 0, top_p: float = 0.9,
-                    sampler: str = "reference", min_p: float = 0.0, seed: int = None, every: int = None, admit_rows: int = None,
-                    decode: bool = True, prefix=None, share_prefix: bool = False, **unsupported):
-    """Generate over a stream of requests (DESIGN.md "Request streams"): yields one ``StreamResult`` per request, in completion
-    order.  Request i's tokens, finish reason and index are those of the solo call
-
-        generate(model, request_i, max_steps=max_new_tokens_i, eos_token=[...], stop_sequences=..., stop_per_row=True,
-                 return_finish=True, temperature=0.0)
-
-    -- that call is the host statement, and for an LM object that is not the HIP engine exactly those calls run one after
-    another.  The HIP engine runs a slot session (engine.SlotSession): ``slots`` rows (1 to 16, the range of the captured GEMV step)
-    generate in one captured token step, and the row of a finished request goes to the next request while the others keep
-    generating; nothing of the token step changes but its bookkeeping launch (ops.sample_finish_slots).
-
-    ``requests``: any iterable of embeddings tensors (1, S, d) / (S, d), as ``embed`` returns them, or pairs (embeddings,
-    max_new_tokens_i) with 1 <= max_new_tokens_i <= ``max_new_tokens`` (the default budget and the session's bound).  It is pulled
-    lazily, one item when a slot frees, so a data loader or preprocess_inputs + embed can run inside it on the same stream.
-    ``max_prompt``: the longest prompt the session takes (default: max_position_embeddings - max_new_tokens rounded down to 64).
-    It sets the cost of the session: EVERY admission prefill runs over (admit_rows, ceil64(max_prompt)) rows whatever the real
-    prompt lengths are, and the session allocates a live cache of ``slots`` x ceil64(max_prompt + max_new_tokens) positions plus a
-    staging cache of admit_rows x ceil64(max_prompt) -- at the default, 28 blocks and 8 slots about 15 GB and prefills of 1920
-    rows per row: pass the longest prompt you expect.  A longer prompt (or any other bad item) raises ValueError naming the
-    request when it is pulled: nothing more is pulled, the requests in front of it are generated to their end and yielded
-    first, then the error is raised -- no earlier request is lost, and the engine stays usable.
-    ``every``: the number of steps between two host looks (default MAGMA_EOS_CHECK_EVERY, as generate).  ``admit_rows`` (1 to
-    ``slots``, default ``slots``): the fixed row count of every admission prefill -- the staging shape (admit_rows,
-    ceil64(max_prompt)) is fixed for the session so that a request's bits do not depend on what was admitted with it.
-    ``eos_token`` (an id or 1 to 8 ids; default the model's) and ``stop_sequences`` are generate()'s per-row stopping arguments.
-    Greedy decoding (``temperature=0``, the default) and both samplers are supported.  A sampled request draws its first token
-    at its admission from the Philox counter (2^32 - 1 - admission pass, staging row) and every later token from (global step
-    of the session, slot) -- two domains that never meet, so no two draws of a session share a counter (engine.SlotSession) --,
-    NOT from the counters of a solo call: only greedy decoding and ``top_k=1`` are reproducible against a solo call.  Not combined yet (NotImplementedError): the logits processors, return_logprobs, constraint,
-    guidance, beam and contrastive search, past_key_values -- their kernels read the token history from column 0.
-    The arguments are checked when the call is made; the work starts with the first ``next``.
-    ``prefix`` (DESIGN.md "Request streams", session prefix): ONE prompt in front of every request -- the few-shot exemplars of an
-    evaluation --, as (P, d) / (1, P, d) embeddings or as a one-row KVCache from ``Magma.cache_prompt`` (HIP engine only; only
-    read: its K / V, positions and pending token are what they were after the session, other calls may keep expanding and
-    continuing it).  Request i's tokens, reason and index are then those of the solo call above on ``request_i`` with
-    ``past_key_values=<a private copy of the prefix cache>``; an LM object that is not the HIP engine runs the solo calls on
-    ``torch.cat([prefix, request_i])``.  The prefix is prefilled ONCE and copied into every slot and every staging row at set-up;
-    an admission prefill still runs over (admit_rows, ceil64(max_prompt)) rows -- the requests' own rows, appended behind the
-    cached prefix --, not over (admit_rows, ceil64(P + max_prompt)).  ``max_prompt`` keeps its meaning, the longest request NOT
-    counting the prefix; its default becomes (max_position_embeddings - P - max_new_tokens) rounded down to 64, and
-    P + max_prompt + max_new_tokens (and the staged P + ceil64(max_prompt)) must fit max_position_embeddings.  Memory: a live
-    cache of ``slots`` x ceil64(P + max_prompt + max_new_tokens) positions plus a staging cache of admit_rows x
-    (P + ceil64(max_prompt)).  Every slot holds its OWN copy of the prefix, so the decode attention of a token step reads P more
-    positions per live row: a prefix saves prefill work, not decode bandwidth.  ValueError at call time: a cache with several
-    rows, with a pending token, of a beam or contrastive search or of another engine, embeddings of the wrong width.
-    ``share_prefix=True`` (DESIGN.md "Shared session prefix"; needs ``prefix``, ValueError at call time without one): the session
-    keeps ONE copy of the prefix's K / V and the live cache holds the rows' own positions only -- ``slots`` x
-    ceil64(max_prompt + max_new_tokens).  The decode attention of a token step then reads the prefix once for all rows (one launch
-    per block computes every row's partial attention over it, cut into chunks that depend on P alone; the attention launch merges
-    them with the row's own keys).  The sums are formed in another order than in the per-slot copies' attention, so tokens agree
-    with the default up to near-ties; a request's tokens do not depend on its slot, on the other requests or on ``every``.  An
-    LM object that is not the HIP engine ignores the flag."""
-    import inspect
-    defaults = {k: p.default for k, p in inspect.signature(generate).parameters.items()}
-    known = {k for _, names in _STREAM_REFUSED for k in names}
-    for k in unsupported:
-        if k not in known:
-            raise TypeError(f"generate_stream() got an unexpected keyword argument {k!r}")
-    for what, names in _STREAM_REFUSED:
-        for k in names:
-            if k in unsupported and not (unsupported[k] is defaults[k] or (not torch.is_tensor(unsupported[k]) and unsupported[k] == defaults[k])):
-                raise NotImplementedError(f"{what} not combined with generate_stream yet ({k}=)")
+def _stream_args(model, slots, max_new_tokens, max_prompt, every, admit_rows, prefix, share_prefix, budget="max_new_tokens"):
+    """The session arguments generate_stream and choose_stream share, checked when the call is made: returns (on_device,
+    admit_rows, every, prefix as (P, d) embeddings or a KVCache or None, P, max_prompt).  ``budget``: what the caller names
+    ``max_new_tokens`` in its messages."""
     on_device = getattr(model.lm, "device_token_selection", False)
-    for name, v, lo, hi in (("slots", slots, 1, 16), ("max_new_tokens", max_new_tokens, 1, None)):
+    for name, v, lo, hi in (("slots", slots, 1, 16), (budget, max_new_tokens, 1, None)):
         if isinstance(v, bool) or not isinstance(v, int) or v < lo or (hi is not None and v > hi):
             raise ValueError(f"{name} must be an integer in [{lo}, {hi if hi is not None else '...'}], got {v!r}")
     if admit_rows is None:
@@ -1786,15 +1739,87 @@ def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 10
             raise ValueError("max_prompt is needed: this LM object does not say its max_position_embeddings")
         max_prompt = (n_pos - P - max_new_tokens) // 64 * 64
         if max_prompt < 1:
-            raise ValueError(f"{before}max_new_tokens = {max_new_tokens} leaves no room for a prompt within max_position_embeddings = "
+            raise ValueError(f"{before}{budget} = {max_new_tokens} leaves no room for a prompt within max_position_embeddings = "
                              f"{n_pos}; pass max_prompt")
     if isinstance(max_prompt, bool) or not isinstance(max_prompt, int) or max_prompt < 1:
         raise ValueError(f"max_prompt must be an integer >= 1, got {max_prompt!r}")
     if n_pos is not None and P + max_prompt + max_new_tokens > n_pos:
-        raise ValueError(f"{before}max_prompt = {max_prompt} + max_new_tokens = {max_new_tokens} exceeds max_position_embeddings = {n_pos}")
+        raise ValueError(f"{before}max_prompt = {max_prompt} + {budget} = {max_new_tokens} exceeds max_position_embeddings = {n_pos}")
     if n_pos is not None and P and on_device and P + (max_prompt + 63) // 64 * 64 > n_pos:
         raise ValueError(f"{before}max_prompt = {max_prompt}, staged as {(max_prompt + 63) // 64 * 64} rows, exceeds "
                          f"max_position_embeddings = {n_pos}")
+    return on_device, admit_rows, every, prefix, P, max_prompt
+
+
+def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 100, max_prompt: int = None, eos_token=None,
+                    stop_sequences=None, temperature: float = 0.0, top_k: int = 0, top_p: float = 0.9,
+                    sampler: str = "reference", min_p: float = 0.0, seed: int = None, every: int = None, admit_rows: int = None,
+                    decode: bool = True, prefix=None, share_prefix: bool = False, **unsupported):
+    """Generate over a stream of requests (DESIGN.md "Request streams"): yields one ``StreamResult`` per request, in completion
+    order.  Request i's tokens, finish reason and index are those of the solo call
+
+        generate(model, request_i, max_steps=max_new_tokens_i, eos_token=[...], stop_sequences=..., stop_per_row=True,
+                 return_finish=True, temperature=0.0)
+
+    -- that call is the host statement, and for an LM object that is not the HIP engine exactly those calls run one after
+    another.  The HIP engine runs a slot session (engine.SlotSession): ``slots`` rows (1 to 16, the range of the captured GEMV step)
+    generate in one captured token step, and the row of a finished request goes to the next request while the others keep
+    generating; nothing of the token step changes but its bookkeeping launch (ops.sample_finish_slots).
+
+    ``requests``: any iterable of embeddings tensors (1, S, d) / (S, d), as ``embed`` returns them, or pairs (embeddings,
+    max_new_tokens_i) with 1 <= max_new_tokens_i <= ``max_new_tokens`` (the default budget and the session's bound).  It is pulled
+    lazily, one item when a slot frees, so a data loader or preprocess_inputs + embed can run inside it on the same stream.
+    ``max_prompt``: the longest prompt the session takes (default: max_position_embeddings - max_new_tokens rounded down to 64).
+    It sets the cost of the session: EVERY admission prefill runs over (admit_rows, ceil64(max_prompt)) rows whatever the real
+    prompt lengths are, and the session allocates a live cache of ``slots`` x ceil64(max_prompt + max_new_tokens) positions plus a
+    staging cache of admit_rows x ceil64(max_prompt) -- at the default, 28 blocks and 8 slots about 15 GB and prefills of 1920
+    rows per row: pass the longest prompt you expect.  A longer prompt (or any other bad item) raises ValueError naming the
+    request when it is pulled: nothing more is pulled, the requests in front of it are generated to their end and yielded
+    first, then the error is raised -- no earlier request is lost, and the engine stays usable.
+    ``every``: the number of steps between two host looks (default MAGMA_EOS_CHECK_EVERY, as generate).  ``admit_rows`` (1 to
+    ``slots``, default ``slots``): the fixed row count of every admission prefill -- the staging shape (admit_rows,
+    ceil64(max_prompt)) is fixed for the session so that a request's bits do not depend on what was admitted with it.
+    ``eos_token`` (an id or 1 to 8 ids; default the model's) and ``stop_sequences`` are generate()'s per-row stopping arguments.
+    Greedy decoding (``temperature=0``, the default) and both samplers are supported.  A sampled request draws its first token
+    at its admission from the Philox counter (2^32 - 1 - admission pass, staging row) and every later token from (global step
+    of the session, slot) -- two domains that never meet, so no two draws of a session share a counter (engine.SlotSession) --,
+    NOT from the counters of a solo call: only greedy decoding and ``top_k=1`` are reproducible against a solo call.  Not combined (NotImplementedError): the logits processors, return_logprobs, constraint,
+    guidance, beam and contrastive search, past_key_values.  (A closed answer set per request with its log-probabilities and the
+    rules is ``choose_stream``, whose session runs the constraint, rule and log-probability kernels over the ring.)
+    The arguments are checked when the call is made; the work starts with the first ``next``.
+    ``prefix`` (DESIGN.md "Request streams", session prefix): ONE prompt in front of every request -- the few-shot exemplars of an
+    evaluation --, as (P, d) / (1, P, d) embeddings or as a one-row KVCache from ``Magma.cache_prompt`` (HIP engine only; only
+    read: its K / V, positions and pending token are what they were after the session, other calls may keep expanding and
+    continuing it).  Request i's tokens, reason and index are then those of the solo call above on ``request_i`` with
+    ``past_key_values=<a private copy of the prefix cache>``; an LM object that is not the HIP engine runs the solo calls on
+    ``torch.cat([prefix, request_i])``.  The prefix is prefilled ONCE and copied into every slot and every staging row at set-up;
+    an admission prefill still runs over (admit_rows, ceil64(max_prompt)) rows -- the requests' own rows, appended behind the
+    cached prefix --, not over (admit_rows, ceil64(P + max_prompt)).  ``max_prompt`` keeps its meaning, the longest request NOT
+    counting the prefix; its default becomes (max_position_embeddings - P - max_new_tokens) rounded down to 64, and
+    P + max_prompt + max_new_tokens (and the staged P + ceil64(max_prompt)) must fit max_position_embeddings.  Memory: a live
+    cache of ``slots`` x ceil64(P + max_prompt + max_new_tokens) positions plus a staging cache of admit_rows x
+    (P + ceil64(max_prompt)).  Every slot holds its OWN copy of the prefix, so the decode attention of a token step reads P more
+    positions per live row: a prefix saves prefill work, not decode bandwidth.  ValueError at call time: a cache with several
+    rows, with a pending token, of a beam or contrastive search or of another engine, embeddings of the wrong width.
+    ``share_prefix=True`` (DESIGN.md "Shared session prefix"; needs ``prefix``, ValueError at call time without one): the session
+    keeps ONE copy of the prefix's K / V and the live cache holds the rows' own positions only -- ``slots`` x
+    ceil64(max_prompt + max_new_tokens).  The decode attention of a token step then reads the prefix once for all rows (one launch
+    per block computes every row's partial attention over it, cut into chunks that depend on P alone; the attention launch merges
+    them with the row's own keys).  The sums are formed in another order than in the per-slot copies' attention, so tokens agree
+    with the default up to near-ties; a request's tokens do not depend on its slot, on the other requests or on ``every``.  An
+    LM object that is not the HIP engine ignores the flag."""
+    import inspect
+    defaults = {k: p.default for k, p in inspect.signature(generate).parameters.items()}
+    known = {k for _, names in _STREAM_REFUSED for k in names}
+    for k in unsupported:
+        if k not in known:
+            raise TypeError(f"generate_stream() got an unexpected keyword argument {k!r}")
+    for what, names in _STREAM_REFUSED:
+        for k in names:
+            if k in unsupported and not (unsupported[k] is defaults[k] or (not torch.is_tensor(unsupported[k]) and unsupported[k] == defaults[k])):
+                raise NotImplementedError(f"{what} not combined with generate_stream yet ({k}=)")
+    on_device, admit_rows, every, prefix, P, max_prompt = _stream_args(model, slots, max_new_tokens, max_prompt, every, admit_rows,
+                                                                       prefix, share_prefix)
     if eos_token is None or (isinstance(eos_token, int) and not isinstance(eos_token, bool) and not eos_token):
         eos_token = model.eos_token
     stop = check_stop_args(eos_token, stop_sequences, True, _logit_count(model),
@@ -1883,6 +1908,120 @@ def choose(model, embeddings, choices, lengths=None, **generate_kwargs):
             ids.pop()
         index[r] = tries[r].index(ids)
     return index, lp
+
+
+class StreamChoice(NamedTuple):
+    """One finished request of choose_stream(): CPU tensors over the answer's ``count`` tokens."""
+    index: int                  # the request's ordinal in ``requests``
+    choice: int                 # the position of the answer in the request's list of choices
+    tokens: torch.Tensor        # int64 [count]: the answer's tokens and the eos that ended it
+    logprobs: torch.Tensor      # fp32 [count]: log p(tokens[i]) under the raw model distribution of that step
+    top_ids: torch.Tensor       # int64 [count, top_logprobs]
+    top_logprobs: torch.Tensor  # fp32 [count, top_logprobs]
+    reason: str                 # "eos" (a walk through a trie always ends there within its budget) | "length"
+    slot: Optional[int]         # the row of the session the request ran in (None: an LM object without slots)
+
+
+def choose_stream(model, requests, *, slots: int = 8, max_choice_tokens: int = 16, max_prompt: int = None, eos_token=None,
+                  top_logprobs: int = 0, every: int = None, admit_rows: int = None, prefix=None, share_prefix: bool = False,
+                  trie_capacity: int = None, repetition_penalty: float = 1.0, min_new_tokens: int = 0, suppress_tokens=None):
+    """``choose`` over a stream of requests (DESIGN.md "Choosing over a request stream"): every request brings its own closed set
+    of answers, and one ``StreamChoice`` per request is yielded in completion order.  Request i's choice, tokens and
+    log-probabilities are those of the solo call
+
+        choose(model, request_i, choices_i, eos_token=..., top_logprobs=..., [past_key_values=<a private copy of the prefix cache>],
+               repetition_penalty=..., min_new_tokens=..., suppress_tokens=...)
+
+    -- that call is the definition, and for an LM object that is not the HIP engine exactly those calls run one after another (on
+    ``torch.cat([prefix, request_i])`` with a prefix).  The HIP engine runs generate_stream's slot session under a plan with the
+    constraint, the rules and the log-probabilities: a short answer frees its row for the next request while longer ones go on.
+
+    ``requests``: any iterable of pairs (embeddings (1, S, d) / (S, d), choices); ``choices`` is what ``choose`` takes for ONE row:
+    a ``TokenTrie``, or a list of id sequences or strings.  Requests that pass the same TokenTrie OBJECT share its entry in the
+    device table; a list is built into a trie of its own when the request is pulled.  The request's budget is its longest choice
+    + 1 (the eos); ``max_choice_tokens`` (1 to 64) bounds every choice of the session.  A request is checked when it is pulled,
+    under generate_stream's rule: bad choices, or a choice longer than ``max_choice_tokens``, raise ValueError naming the request
+    after the requests in front of it were finished and yielded.  Selection is greedy, as in ``choose``.
+    ``slots``, ``max_prompt``, ``every``, ``admit_rows``, ``prefix``, ``share_prefix``, ``eos_token`` (an id or 1 to 8 ids): as in
+    generate_stream, with max_choice_tokens + 1 as the session's token budget.  ``top_logprobs``: the alternatives per token.
+    ``trie_capacity``: int32 entries the device table is allocated for (3 + 4 nodes + 2 edges, summed over the tries that are live
+    at once; default 4096) -- a table that outgrows it is re-allocated mid-session, and the captured step with it.
+    ``repetition_penalty`` / ``min_new_tokens`` / ``suppress_tokens``: generate()'s rules, checked against every request's choices
+    as generate(constraint=...) checks them."""
+    for name, v, lo, hi in (("max_choice_tokens", max_choice_tokens, 1, MAX_TRIE_LEN), ("trie_capacity", trie_capacity, 1, None)):
+        if (name != "trie_capacity" or v is not None) and (isinstance(v, bool) or not isinstance(v, int) or v < lo or
+                                                          (hi is not None and v > hi)):
+            raise ValueError(f"{name} must be an integer in [{lo}, {hi if hi is not None else '...'}], got {v!r}")
+    budget = max_choice_tokens + 1
+    on_device, admit_rows, every, prefix, P, max_prompt = _stream_args(model, slots, budget, max_prompt, every, admit_rows, prefix,
+                                                                       share_prefix, budget="max_choice_tokens + 1")
+    V = _logit_count(model)
+    encode = getattr(getattr(model, "tokenizer", None), "encode", None)
+    if eos_token is None or (isinstance(eos_token, int) and not isinstance(eos_token, bool) and not eos_token):
+        eos_token = model.eos_token
+    stop = check_stop_args(eos_token, None, True, V, encode)
+    eos_ids = [int(t) for t in stop["eos_ids"]]
+    n_top = check_logprob_args(True, top_logprobs, V)
+    rules = dict(repetition_penalty=repetition_penalty, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens)
+    proc = check_processor_args(vocab=V, **rules)
+
+    def pulled():
+        """(index, (S, d) embeddings, TokenTrie) of every request, checked as it is pulled."""
+        for index, item in enumerate(requests):
+            if not isinstance(item, (tuple, list)) or len(item) != 2:
+                raise ValueError(f"request {index}: an item is a pair (embeddings, choices)")
+            emb, choices = item
+            if not torch.is_tensor(emb) or emb.ndim not in (2, 3) or (emb.ndim == 3 and emb.shape[0] != 1):
+                raise ValueError(f"request {index}: the embeddings are a tensor (1, S, d) or (S, d)")
+            emb = emb[0] if emb.ndim == 3 else emb
+            if not 1 <= emb.shape[0] <= max_prompt:
+                raise ValueError(f"request {index}: a prompt of {emb.shape[0]} rows is outside [1, max_prompt = {max_prompt}]")
+            try:
+                trie = (check_constraint_args(choices, 1, encode, V, eos_ids, proc) or [None])[0]
+            except ValueError as e:
+                raise ValueError(f"request {index}: {e}") from None
+            if trie is None:
+                raise ValueError(f"request {index}: choose_stream needs choices")
+            if trie.max_len() > max_choice_tokens:
+                raise ValueError(f"request {index}: a choice of {trie.max_len()} tokens exceeds max_choice_tokens = {max_choice_tokens}")
+            yield index, emb, trie
+
+    def result(index, trie, ids, lp, top_ids, top_lp, slot):
+        ids = ids.to("cpu", torch.int64)
+        answer = ids.tolist()
+        reason = "eos" if answer and answer[-1] in eos_ids else "length"
+        while answer and answer[-1] in eos_ids:
+            answer.pop()
+        return StreamChoice(index, trie.index(answer), ids, lp, top_ids, top_lp, reason, slot)
+
+    def solo_calls():           # the definition, request after request
+        for index, emb, trie in pulled():
+            if P:
+                emb = torch.cat([prefix.to(emb.device, emb.dtype), emb])
+            _, lp = choose(model, emb[None], trie, eos_token=list(eos_ids), top_logprobs=n_top, eos_check_every=every, **rules)
+            n = int(lp.count[0])
+            yield result(index, trie, lp.tokens[0, :n], lp.logprobs[0, :n], lp.top_ids[0, :n], lp.top_logprobs[0, :n], None)
+
+    def session():
+        from .engine import LMEngine, SlotSession
+        eng = model.lm.engine
+        if getattr(model, "device", None) is not None and torch.device(model.device).type == "cuda":
+            torch.cuda.set_device(model.device)
+        plan = LMEngine.selection_plan(stop=stop, processors=None if proc is None else rules, logprobs=n_top, constraint=True,
+                                       vocab=eng.V, slots=True)
+        ses = SlotSession(eng, plan, slots=slots, max_new=budget, max_prompt=max_prompt, every=every, admit_rows=admit_rows,
+                          prefix=prefix, share_prefix=share_prefix, trie_capacity=trie_capacity)
+        dev, tries = eng.device, {}
+
+        def items():
+            for index, emb, trie in pulled():
+                tries[index] = trie
+                yield index, emb.to(dev), trie.max_len() + 1, trie
+
+        for index, ids, _, slot, (lp, top_ids, top_lp) in ses.run(items()):
+            yield result(index, tries.pop(index), ids, lp, top_ids, top_lp, slot)
+
+    return session() if on_device else solo_calls()
 
 
 class Ranking(NamedTuple):

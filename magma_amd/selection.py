@@ -79,6 +79,13 @@ class ConstraintMode:
         self.max_token = max(max(t.tokens()) for t in {id(t): t for t in tries}.values())
 
 
+class SlotConstraint:
+    """The constraint of a slot plan (DESIGN.md "Choosing over a request stream"): every row walks a trie of its own, and the
+    SESSION keeps the device table and the roots (engine.SlotSession: the forest of the live slots' tries, rebuilt when an
+    admission changes the set) -- the plan only says that the step's launch is the constrained one."""
+    table = roots = None
+
+
 class StepKey(NamedTuple):
     """What the launches of a token step depend on (SelectionPlan.graph_key): two steps share a captured graph exactly when their
     keys are equal.  Launch arguments are in it; the contents of the device tables, rewritten between replays, are not."""
@@ -210,7 +217,10 @@ class SelectionPlan(NamedTuple):
                 cache._drop_graphs(lambda key: key.slots)
         rows = self.rows(cache)
         cons = self.cons
-        if cons is not None:
+        if isinstance(cons, SlotConstraint):
+            if not self.slots or cache.trie_table is None:
+                raise ValueError("a slot plan's constraint needs the session's trie buffers (SlotSession allocates them)")
+        elif cons is not None:
             if cons.max_token >= V:
                 raise ValueError(f"the constraint holds token ids outside [0, {V})")
             if cons.roots.numel() != rows:
@@ -222,7 +232,7 @@ class SelectionPlan(NamedTuple):
                 cache.trie_roots[:rows].copy_(cons.roots, non_blocking=True)
                 cache.trie_held = cons
         if self.n_top is not None:
-            cache.alloc_logprobs(self.n_top)
+            cache.alloc_logprobs(self.n_top)        # (a slot session's: [slots, max_new] -- it has set cache.lp_cols)
             if self.rewrites_logits and st.logits_proc is None:
                 st.logits_proc = torch.empty_like(st.logits)
 
@@ -239,10 +249,15 @@ class TokenSelection:
         below and that refuses what beam search and contrastive search (``contrast`` = (top_k, penalty_alpha)) are not combined
         with.  A plan that is already built comes back as it is, so a loop builds one and passes ``plan=`` on every call.
         ``vocab``: the number of logits V the token ids must lie in.  ``slots``: the step of a slot session (SlotSession; DESIGN.md
-        "Request streams"): greedy or sampled selection with per-row stopping, nothing else."""
-        if slots and (stop is None or any(v is not None for v in (beam, processors, logprobs, constraint, guidance, contrast))):
-            raise NotImplementedError("a slot session selects greedily or by sampling under per-row stopping: beam and contrastive search, "
-                                      "the logits processors, log-probabilities, constraints and guidance are not combined with it yet")
+        "Request streams"): greedy or sampled selection with per-row stopping, and -- "Choosing over a request stream" -- the logits
+        processors, log-probabilities and ``constraint=True``: the rows' own tries, whose table the session keeps (SlotConstraint)."""
+        if slots and (stop is None or any(v is not None for v in (beam, guidance, contrast))):
+            raise NotImplementedError("a slot session selects greedily or by sampling under per-row stopping: beam and contrastive search "
+                                      "and guidance are not combined with it yet")
+        if slots and constraint is not None and constraint is not True:
+            raise ValueError("a slot plan takes constraint=True: the session keeps the tries of its rows")
+        if constraint is True and not slots:
+            raise ValueError("constraint=True is a slot plan's: pass one TokenTrie per row")
         if plan is not None:
             if any(v is not None for v in (sampling, beam, processors, stop, logprobs, constraint, guidance, contrast)):
                 raise ValueError("pass plan= or the selection keywords it was built from, not both")
@@ -301,7 +316,9 @@ class TokenSelection:
 
     @staticmethod
     def constraint_mode(constraint):
-        """None (today's launches) or a ConstraintMode, from one sampling.TokenTrie per row."""
+        """None (today's launches), a ConstraintMode from one sampling.TokenTrie per row, or -- True -- a slot plan's SlotConstraint."""
+        if constraint is True:
+            return SlotConstraint()
         return None if constraint is None else ConstraintMode(list(constraint))
 
     @staticmethod
@@ -492,12 +509,18 @@ class TokenSelection:
             half, logits, raw, out = out, logits[:R], None if raw is None else raw[:R], out[:R]
         rows = (lambda t: t) if guidance is None else (lambda t: None if t is None else t[:R])   # the per-row buffers' share
         more = {} if stop is None or len(stop[0]) < 2 else dict(eos_more=cache.stop_table[1:ops.STOP_MAX_EOS], n_eos_more=len(stop[0]) - 1)
+        # a slot step (plan.slots): the same launches through the slot entry points -- the rows' tokens are windows of the ring
+        window = (cache.slot_table, cache.finish) if plan.slots else ()
         if cons is not None:
             rules = proc if proc is not None else (1.0, 0, 0, ())
-            ops.logits_process_constrained(logits, cache.sample_state, rows(cache.history), cache.trie_table, cache.trie_roots,
-                                           cache.trie_path, repetition_penalty=rules[0], no_repeat_ngram_size=rules[1],
-                                           min_new_tokens=rules[2], eos=cache.eos, suppress=cache.suppress,
-                                           n_suppress=len(rules[3]), **more)
+            launch = ops.logits_process_constrained_slots if plan.slots else ops.logits_process_constrained
+            launch(logits, cache.sample_state, cache.ring if plan.slots else rows(cache.history), cache.trie_table, cache.trie_roots,
+                   cache.trie_path, *window, repetition_penalty=rules[0], no_repeat_ngram_size=rules[1],
+                   min_new_tokens=rules[2], eos=cache.eos, suppress=cache.suppress, n_suppress=len(rules[3]), **more)
+        elif proc is not None and plan.slots:
+            ops.logits_process_slots(logits, cache.sample_state, cache.ring, *window, repetition_penalty=proc[0],
+                                     no_repeat_ngram_size=proc[1], min_new_tokens=proc[2], eos=cache.eos, suppress=cache.suppress,
+                                     n_suppress=len(proc[3]), **more)
         elif proc is not None:
             ops.logits_process(logits, cache.sample_state, rows(cache.history), repetition_penalty=proc[0], no_repeat_ngram_size=proc[1],
                                min_new_tokens=proc[2], eos=cache.eos, suppress=cache.suppress, n_suppress=len(proc[3]),
@@ -510,11 +533,14 @@ class TokenSelection:
             tok = ops.sample_warp(logits, mode[1], mode[2], mode[3], mode[4], cache.seed, cache.sample_state, out=out)
         else:
             tok = ops.sample(logits, mode[0], mode[1], mode[2], cache.seed, cache.sample_state, out=out)
-        if n_top is not None:
+        if n_top is not None and plan.slots:
+            ops.token_logprobs_slots(logits if raw is None else raw, tok, cache.lp, cache.top_id if n_top else None,
+                                     cache.top_lp if n_top else None, cache.sample_state, *window, cache.ring_cols)
+        elif n_top is not None:
             ops.token_logprobs(logits if raw is None else raw, tok, rows(cache.lp), rows(cache.top_id) if n_top else None,
                                rows(cache.top_lp) if n_top else None, state=cache.sample_state)
         if plan.slots:
-            assert guidance is None and n_top is None and proc is None and cons is None
+            assert guidance is None
             ops.sample_finish_slots(tok, cache.sample_state, cache.stop_table, len(stop[0]), len(stop[1]), stop[0][0], cache.finish,
                                     cache.slot_table, cache.ring, d_pos=cache.d_pos if advance else None)
         elif stop is not None:

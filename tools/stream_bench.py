@@ -21,6 +21,18 @@ of ``--prefix-rows`` rows, max_new_tokens spread over 3 to 12, eos disabled -- f
     batches of 8 behind one ``cache_prompt``.
 (b) The captured token step of a session with the prefix against the same session without it at equal own-context length: the
     cost of the P more positions per row the decode attention reads.  Medians over interleaved windows of ``--steps`` replays.
+  python tools/stream_bench.py --choices [--prefix-rows 656] [--request-rows 160] [--out FILE (default profiles/choose_stream_bench.jsonl)]
+
+Choosing over a request stream (DESIGN.md "Choosing over a request stream"): 64 requests of ``--request-rows`` rows behind ONE prefix
+(default 656 rows), every request with an answer set of its own -- four choices whose lengths are spread over 1 to 12 tokens --.
+(a) Answers per second, legs interleaved after one warm-up pass of each: ``choose_stream(prefix=...)``; the same with
+    ``share_prefix=True``; static ``choose(past_key_values=cache.expand(8))`` in batches of 8 behind one ``cache_prompt``.
+(b) The captured slot step with the constraint and log-probability launches against the slot step without them and against
+    generate()'s per-row step with them: device events around windows of min(``--steps``, 48) replays, interleaved, medians of
+    ``--reps``.  Every row walks a trie of ONE 64-token sequence, so no row finishes inside a window (a finished slot stops
+    advancing and would make its step cheaper): every record carries ``rows_finished``, which must be 0, and every window of every
+    variant starts from the same positions.
+
   python tools/stream_bench.py --prefix-rows 656 --share-prefix [--out FILE (default profiles/stream_shared_prefix_bench.jsonl)]
 
 The shared session prefix (DESIGN.md "Shared session prefix") against the per-slot copies, in the same process: the throughput
@@ -52,13 +64,17 @@ ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--prefix-rows", type=int, default=0, help="P > 0: measure the session prefix instead (see the module docstring)")
 ap.add_argument("--share-prefix", action="store_true", help="with --prefix-rows: add the share_prefix=True legs (one copy of the "
                 "prefix, read once per step for all rows), the prefix-partials launch alone and the live-cache bytes")
+ap.add_argument("--choices", action="store_true", help="measure choose_stream instead (see the module docstring)")
 ap.add_argument("--request-rows", type=int, default=160, help="rows of every request in the --prefix-rows mode")
 ap.add_argument("--out", default=None, help="default: profiles/stream_bench.jsonl, profiles/stream_prefix_bench.jsonl with --prefix-rows")
 args = ap.parse_args()
 if args.out is None:
     args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                            "choose_stream_bench.jsonl" if args.choices else
                             "stream_shared_prefix_bench.jsonl" if args.prefix_rows and args.share_prefix else
                             "stream_prefix_bench.jsonl" if args.prefix_rows else "stream_bench.jsonl")
+if args.choices and not args.prefix_rows:
+    args.prefix_rows = 656
 if args.share_prefix and not args.prefix_rows:
     sys.exit("stream_bench: --share-prefix needs --prefix-rows")
 
@@ -93,6 +109,110 @@ def write_out():
     if args.out:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")
+
+
+def choices_mode():
+    """--choices: answers per second of choose_stream against static choose batches, and the slot step with the constraint and
+    log-probability launches against the step without them and against generate()'s per-row step with them."""
+    from magma_amd.sampling import TokenTrie
+    P, R, n_top = args.prefix_rows, args.request_rows, 3
+    emb = model.embed([images, torch.randint(0, 50256, (8, R - 49), device=dev, generator=g)])
+    assert emb.shape[1] == R, emb.shape
+    prefix = eng.embed_ids(torch.randint(0, 50256, (1, P), device=dev, generator=g))[0]
+    host = torch.Generator().manual_seed(7)
+
+    def answer_set(i):             # four choices, lengths spread over 1 .. 12: the longest of request i is 1 + (5 i) % 12
+        top = 1 + (5 * i) % 12
+        lens = sorted({top, max(1, top // 2), max(1, top // 3), 1})
+        return [torch.randint(0, 50256, (n,), generator=host).tolist() for n in lens]
+
+    sets = [answer_set(i) for i in range(args.requests)]
+    tries = [TokenTrie(c) for c in sets]
+    requests = [(emb[i % 8], tries[i]) for i in range(args.requests)]
+    longest = max(t.max_len() for t in tries)
+    skw = dict(slots=B, max_choice_tokens=longest, max_prompt=R, eos_token=[EOS], top_logprobs=n_top, every=args.every or None)
+
+    def leg_stream(share=False):
+        return sum(int(r.tokens.numel()) for r in model.choose_stream(requests, prefix=prefix, share_prefix=share, **skw))
+
+    def leg_static():
+        cache, n = model.cache_prompt(prefix[None]), 0
+        for i in range(0, args.requests, B):
+            group = requests[i:i + B]
+            _, lp = model.choose(torch.stack([x[0] for x in group]), [x[1] for x in group], past_key_values=cache.expand(len(group)),
+                                 eos_token=[EOS], top_logprobs=n_top, eos_check_every=args.every or None)
+            n += int(lp.count.sum())
+        return n
+
+    legs = [("choose_stream_prefix", leg_stream), ("choose_stream_shared_prefix", lambda: leg_stream(True)), ("static_choose_expand", leg_static)]
+    for _, leg in legs:
+        leg()
+    for rep in range(args.reps):
+        for name, leg in legs:
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            n = leg()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t
+            emit({"part": "throughput", "leg": name, "rep": rep, "requests": args.requests, "slots": B, "prefix_rows": P, "request_rows": R,
+                  "answer_tokens": n, "wall_s": dt, "answers_per_s": args.requests / dt, "longest_choice": longest})
+    for name, _ in legs:
+        runs = [x for x in map(json.loads, lines) if x["part"] == "throughput" and x["leg"] == name]
+        emit({"part": "throughput_median", "leg": name, "answers_per_s_median": statistics.median(x["answers_per_s"] for x in runs),
+              "wall_s_median": statistics.median(x["wall_s"] for x in runs), "answer_tokens": runs[0]["answer_tokens"]})
+    eng._cache_pool.clear()
+
+    # ---- the captured step: slots with the modes, slots without, generate()'s per-row step with the modes ----
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    stop = dict(eos_ids=(EOS,), stop_seqs=())
+    steps = min(args.steps, 48)
+    n_new = steps + 8
+    walks = [TokenTrie([torch.randint(0, 50256, (64,), generator=host).tolist()]) for _ in range(B)]      # one path: nobody finishes
+    plans = {"slots_constraint_logprobs": LMEngine.selection_plan(stop=stop, vocab=eng.V, slots=True, constraint=True, logprobs=n_top),
+             "slots_plain": LMEngine.selection_plan(stop=stop, vocab=eng.V, slots=True)}
+    held = {}
+    for name, plan in plans.items():
+        ses = SlotSession(eng, plan, slots=B, max_new=n_new, max_prompt=R, every=1, admit_rows=B)
+        ses._admit([(i, emb[i % 8], n_new) + ((walks[i],) if plan.cons is not None else ()) for i in range(B)], list(range(B)))
+        sc = ses.cache
+        tensors = (sc.d_pos, sc.finish, sc.slot_table, sc.sample_state, ses.st.token)
+        held[name] = (ses, tensors, [t.clone() for t in tensors], list(ses.occ))
+        for _ in range(3):
+            ses._step()
+    rows_kw = dict(plan=LMEngine.selection_plan(stop=stop, constraint=walks, logprobs=n_top, vocab=eng.V))      # built once
+    o = model.lm(inputs_embeds=emb[:B] if B <= 8 else emb.repeat(2, 1, 1)[:B], use_cache=True, cache_hint=n_new, eos_token=EOS,
+                 lengths=[R] * B, **rows_kw)
+    rows_cache = o.past_key_values
+    for _ in range(3):
+        eng.decode(None, rows_cache, **rows_kw)
+    ms = {"slots_constraint_logprobs": [], "slots_plain": [], "rows_constraint_logprobs": []}
+    finished = dict.fromkeys(ms, 0)
+    for rep in range(args.reps):
+        for name in ms:
+            if name in held:
+                ses, tensors, keep, occ = held[name]
+                for t, k in zip(tensors, keep):
+                    t.copy_(k)
+                ses.steps, ses.occ = 0, list(occ)
+                run, fin = ses._step, ses.cache.finish
+            else:               # step 0 again: the walk starts at the root, the step writes its own history
+                rows_cache.pos = R
+                rows_cache.d_pos.fill_(R)
+                rows_cache.sample_state.copy_(torch.tensor([0, -1], dtype=torch.int32))
+                rows_cache.finish.copy_(torch.tensor([[-1, 0]] * B, dtype=torch.int32))
+                run, fin = (lambda: eng.decode(None, rows_cache, **rows_kw)), rows_cache.finish  # noqa: E731
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(steps):
+                run()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[name].append(e0.elapsed_time(e1) / steps)
+            finished[name] = max(finished[name], int((fin[:, 0] >= 0).sum()))
+    for name in ms:
+        emit({"part": "step", "variant": name, "own_rows": R, "step_ms_min": min(ms[name]), "step_ms_median": statistics.median(ms[name]),
+              "step_ms_all": ms[name], "steps_per_window": steps, "rows_finished": finished[name]})
+    write_out()
 
 
 def prefix_mode():
@@ -219,7 +339,7 @@ def prefix_mode():
 
 with torch.no_grad():
     if args.prefix_rows:
-        prefix_mode()
+        choices_mode() if args.choices else prefix_mode()
         sys.exit(0)
     emb = model.embed([images, prompt])
     S0 = int(emb.shape[1])
