@@ -113,7 +113,8 @@ const char* mg_version(void);
  *  27  BatchNorm gain gradient from the convolution output instead of the rounded unit output: added mg_scale_rows_acc_bn_grad_f32
  *      (nothing moved).  Choosing over a request stream: added mg_logits_process_slots_f32,
  *      mg_logits_process_constrained_slots_f32 and mg_token_logprobs_slots_f32 (nothing moved, no revision bump: a package that
- *      binds them names the missing symbol when it meets an older library). */
+ *      binds them names the missing symbol when it meets an older library).  Per-request sampling: added mg_sample_rows_f32 and
+ *      MG_SAMPLE_ROW_BYTES, in the same way. */
 #define MG_ABI_VERSION 27
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
@@ -163,6 +164,10 @@ const char* mg_last_error(void);
  *   mg_token_logprobs_slots_f32              state[0] (any value)                       ring column (state[0] - 1) mod history_cols, count in
  *                                                                                       [1, history_cols]; the lp column = the count: >= cols SKIP
  *                                            tokens, ids, roots, path, table entries    as the flat twins above
+ *   mg_sample_rows_f32                       finish[r][0], slot[r][0], state[0]         as the slot twins above: SKIP an idle row (token, filtered
+ *                                                                                       untouched, no logit read); the counter is any value
+ *                                            record r of params (any bits)              never an index: temperature not finite > 0 = greedy,
+ *                                                                                       top_k < 0 = off, top_p / log_min_p NaN or out of range = off
  *   mg_token_logprobs_f32, _rows_f32         token id ([0, V)), row_of[i] ([0, n_rows)) lp = -inf, nothing read through it
  *   mg_kv_reorder_bf16                       parent[b]  ([0, R))                        SKIP row b (it is then neither staged nor overwritten)
  *                                            d_pos  ([0, Smax])                         CLAMP: the number of positions copied
@@ -567,6 +572,38 @@ int mg_sample_f32(const float* logits, int64_t ld, int32_t B, int32_t V, float t
 int mg_sample_warp_f32(const float* logits, int64_t ld, int32_t B, int32_t V, float temperature, int32_t top_k, double top_p,
                        double min_p, const uint64_t* seed, const int32_t* state, int64_t* token, float* filtered,
                        int64_t ld_filtered, void* stream);
+/* Per-request sampling (DESIGN.md "Per-request sampling"): the launch of mg_sample_f32 (warp = 0) or mg_sample_warp_f32 (warp = 1)
+ * -- one workgroup per row, enqueue-only, graph-capturable, no allocation, no scratch, nothing shared between workgroups -- in
+ * which every row has its own temperature, top_k, top_p, min_p and seed, read at run time from a device table: another request's
+ * settings replay the same captured graph.  It is the same kernel body compiled with another source for its scalars, so for
+ * equal logits bits row r's token and filtered row are those of the flat call on that row ALONE (B = 1) with the row's scalars
+ * and seed at state[0] = j -- whichever row, and whatever the other rows hold.
+ *   params  device table of R records of MG_SAMPLE_ROW_BYTES = 32 bytes, 16-byte aligned:
+ *             offset  0  double   top_p        as mg_sample_f32 / mg_sample_warp_f32 take it
+ *             offset  8  double   log_min_p    log(min_p) in double as mg_sample_warp_f32 forms it on the host (the C library's
+ *                                              log), -inf = off.  The LOGARITHM is stored so that the row's bound max + T log(min_p)
+ *                                              has the flat call's bits; read only with warp = 1.
+ *             offset 16  uint64   seed         the Philox4x32-10 key of the row
+ *             offset 24  float    temperature  0 = the row is greedy: the first maximum, as mg_argmax_f32; it reads no seed
+ *             offset 28  int32    top_k        0 or >= V: off
+ *   counter the draw of row r uses counter {j, 0, 0, 0}, j = the row's own token index.  slot == NULL (a static call: all rows
+ *           start together): j = state[0].  Otherwise (a slot session; slot, finish, history_cols as in
+ *           mg_token_logprobs_slots_f32): j = the occupant's token count before this step, (state[0] - 1) mod history_cols - begin
+ *           mod history_cols + 1 -- the n - 1 of mg_sample_finish_slots, which runs behind this launch --, and a row whose finish
+ *           record says finished / idle, or whose begin lies outside the ring, is SKIPPED: none of its logits is read (they may be
+ *           NaN), its token and filtered row are left alone.
+ *   token   [R] int64 (NULL: filter only); filtered optional [R, V] (row stride ld_filtered): -inf where a rule dropped the token;
+ *           a greedy row keeps its first maximum alone.
+ * The table's values cannot be validated here: a temperature that is NaN, negative, zero or infinite selects greedily, a negative
+ * top_k is off, a top_p outside (0, 1) or NaN is off, a NaN log_min_p is off; no value of a record forms an address.
+ * Refused before anything is launched: R <= 0, V <= 0, ld < V, ld_filtered < V, warp outside {0, 1}, a null logits / params / state,
+ * token and filtered both null, finish without slot or slot without finish, slot with history_cols <= 0, params not 16-byte
+ * aligned, an fp32 / int32 pointer not 4-byte or token not 8-byte aligned.  (Added without a revision bump, as the slot entry
+ * points of 27 were: a package that binds it names the missing symbol when it meets an older library.) */
+#define MG_SAMPLE_ROW_BYTES 32
+int mg_sample_rows_f32(const float* logits, int64_t ld, int32_t R, int32_t V, int32_t warp, const void* params,
+                       const int32_t* state, const int32_t* slot, const int32_t* finish, int32_t history_cols, int64_t* token,
+                       float* filtered, int64_t ld_filtered, void* stream);
 int mg_sample_finish(const int64_t* token, int32_t B, int64_t eos, int32_t* state, int32_t* d_pos, int32_t delta,
                      int64_t* history, int64_t ld_history, int32_t history_cols, int32_t* clear, int32_t n_clear,
                      int32_t clear_stride, int32_t pos_stride, void* stream);

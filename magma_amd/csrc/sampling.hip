@@ -38,6 +38,10 @@
 //                by index stay.  The level-0 bins span [max(min, max - 32 T), max].
 //   min-p        a token stays iff x >= max + T log(min_p): one more comparison in `kept`, no sweep.
 // The instance with WARP = false is the kernel as it was.
+//
+// Per-request sampling (mg_sample_rows_f32; DESIGN.md "Per-request sampling"): both instances once more with S = TableRows -- the
+// same body, every workgroup taking its scalars and seed from its row's record of a device table and drawing at the counter
+// (the row's own token index, 0), which is what row 0 of a one-row flat call draws at.  S = FlatRows is the kernel as it was.
 #include "common.h"
 #include <type_traits>
 
@@ -110,9 +114,74 @@ struct WarpParams : SampleParams {
 
 constexpr double FIX = 1099511627776.0;   // 2^40
 
-template <class P>
-__global__ __launch_bounds__(ST) void sample_kernel(const P p) {
+// The window of row b of a slot session before this step's selection, from the tables mg_sample_finish_slots keeps
+// (slot[b] = {begin, limit}, finish[b] = {step or -1, code}) and s = state[0]: the occupant's n = ((s - 1) % cols - begin) mod
+// cols + 1 tokens from column begin on -- the count sample_finish_slots_kernel forms.  n = 0: the row is idle (finished and not
+// harvested yet, or never occupied) or its begin lies outside the ring; such a row is skipped whole.  s is any value: the
+// column is formed as slots_admit_kernel forms it, and n lies in [1, cols] by construction.
+struct SlotWin { int begin, n; };
+MG_DEV SlotWin slot_window(const int32_t* __restrict__ state, const int32_t* __restrict__ slot, const int32_t* __restrict__ finish,
+                           int b, int cols) {
+  if (finish[2 * (int64_t)b] >= 0) return SlotWin{0, 0};
+  const int begin = slot[2 * (int64_t)b];
+  if (begin < 0 || begin >= cols) return SlotWin{0, 0};
+  const int prev = (int)((unsigned)state[0] - 1u);
+  const int col = ((prev % cols) + cols) % cols;
+  int d = col - begin;                      // in (-cols, cols)
+  if (d < 0) d += cols;
+  return SlotWin{begin, d + 1};
+}
+
+// Where a workgroup takes its scalars from (DESIGN.md "Per-request sampling").  FlatRows: the launch arguments, one set for all
+// rows, the draw at counter (state[0], row) under *seed -- mg_sample_f32 / mg_sample_warp_f32 as they were.  TableRows
+// (mg_sample_rows_f32): row r's record of a device table, read at run time, and the draw at counter (j, 0) under the record's seed,
+// with j the row's own token index -- state[0] of a static call, or the occupant's token count so far from the slot session's
+// tables (slot_window's n: sample_finish_slots_kernel's n - 1 for the token this step selects).  Those are the key and the counter
+// of row 0 of a one-row flat call at step j.
+struct FlatRows {};
+struct SampleRow {            // MG_SAMPLE_ROW_BYTES = 32, 16-byte aligned
+  double top_p;
+  double log_min_p;           // log(min_p) as mg_sample_warp_f32 forms it on the host, -inf: off (read by the WARP instance only)
+  uint64_t seed;
+  float temperature;          // 0 (or anything that is not a finite value > 0): the row is greedy
+  int32_t top_k;              // <= 0 or >= V: off
+};
+static_assert(sizeof(SampleRow) == MG_SAMPLE_ROW_BYTES, "the record of mg_sample_rows_f32");
+struct TableRows { const SampleRow* rows; const int32_t* slot; const int32_t* finish; int hist_cols; };
+
+struct RowScalars { float temperature; int top_k; double top_p, log_min_p; };
+
+template <class P, class S = FlatRows>
+__global__ __launch_bounds__(ST) void sample_kernel(const P p0, const S src) {
   constexpr bool WARP = std::is_same<P, WarpParams>::value;
+  constexpr bool ROWS = std::is_same<S, TableRows>::value;
+  // `p`: the row's scalars under the names the body reads -- the launch arguments, or the row's record
+  RowScalars p{p0.temperature, p0.top_k, p0.top_p, -(double)INFINITY};
+  if constexpr (WARP) p.log_min_p = p0.log_min_p;
+  uint32_t ctr0 = 0u, ctr1 = blockIdx.x;
+  unsigned long long seed = 0ull;
+  bool greedy = false;
+  if constexpr (ROWS) {
+    if (src.slot) {             // a slot session: idle rows are skipped whole (uniform over the workgroup)
+      const SlotWin w = slot_window(p0.state, src.slot, src.finish, blockIdx.x, src.hist_cols);
+      if (w.n == 0) return;
+      ctr0 = (uint32_t)w.n;
+    } else {
+      ctr0 = (uint32_t)p0.state[0];
+    }
+    ctr1 = 0u;
+    const SampleRow r = src.rows[blockIdx.x];
+    // the table is device memory no entry point can look at: a temperature that is not a finite value > 0 selects greedily, a
+    // negative top_k is off (nothing below forms an address from a record's value)
+    greedy = !(r.temperature > 0.f) || r.temperature == INFINITY;
+    p.temperature = greedy ? 1.0f : r.temperature;
+    p.top_k = greedy || r.top_k < 0 ? 0 : r.top_k;
+    p.top_p = greedy ? 0.0 : r.top_p;
+    p.log_min_p = greedy || !WARP ? -(double)INFINITY : r.log_min_p;
+    seed = r.seed;
+  } else {
+    if (p0.out) { ctr0 = (uint32_t)p0.state[0]; seed = p0.seed ? *p0.seed : 0ull; }
+  }
   __shared__ unsigned long long hist64[256];
   __shared__ uint32_t hist32[256];
   __shared__ float shf[ST / 64];
@@ -120,8 +189,8 @@ __global__ __launch_bounds__(ST) void sample_kernel(const P p) {
   __shared__ unsigned long long shu[ST / 64 + 1];
   __shared__ uint32_t bc[4];
   __shared__ unsigned long long bc64[2];
-  const int tid = threadIdx.x, V = p.V;
-  const float* x = p.logits + (int64_t)blockIdx.x * p.ld;
+  const int tid = threadIdx.x, V = p0.V;
+  const float* x = p0.logits + (int64_t)blockIdx.x * p0.ld;
 
   // One wave scans the 256 buckets of a top-p level (it used to be one thread walking them: ~8 us per level): the lowest
   // non-empty bucket whose strictly-larger mass -- `start` plus the buckets above it -- is below `limit`.  That mass only grows
@@ -199,6 +268,16 @@ __global__ __launch_bounds__(ST) void sample_kernel(const P p) {
   int imax = 0x7fffffff;
   for (int i = tid; i < V; i += ST) if (x[i] == mx) { imax = min(imax, i); }
   imax = blk_min_i(imax, shi);
+  if constexpr (ROWS) {
+    if (greedy) {             // a temperature-0 row of the table: the first maximum, as mg_argmax_f32 (uniform over the workgroup)
+      if (p0.filtered) {
+        float* f = p0.filtered + (int64_t)blockIdx.x * p0.ldf;
+        for (int i = tid; i < V; i += ST) f[i] = i == imax ? x[i] : -INFINITY;
+      }
+      if (p0.out && tid == 0) p0.out[blockIdx.x] = imax == 0x7fffffff ? 0 : imax;
+      return;
+    }
+  }
 
   // ---------------- the reference's top-p rule ----------------
   uint32_t tstar = WARP ? 0u : 0xffffffffu;    // dropped(i) = alive && i != imax && (key > tstar || (key == tstar && i < tie_cut))
@@ -303,11 +382,11 @@ __global__ __launch_bounds__(ST) void sample_kernel(const P p) {
     else return !(k > tstar || (k == tstar && i < tie_cut));
   };
 
-  if (p.filtered) {
-    float* f = p.filtered + (int64_t)blockIdx.x * p.ldf;
+  if (p0.filtered) {
+    float* f = p0.filtered + (int64_t)blockIdx.x * p0.ldf;
     for (int i = tid; i < V; i += ST) { const float v = x[i]; f[i] = kept(i, v) ? v : -INFINITY; }
   }
-  if (!p.out) return;
+  if (!p0.out) return;
 
   // ---------------- multinomial draw: inverse CDF over fixed-point weights, index order ----------------
   // Wave w owns the contiguous index range [w * RW * 64, (w + 1) * RW * 64) as RW rows of 64: lane l reads index
@@ -337,8 +416,7 @@ __global__ __launch_bounds__(ST) void sample_kernel(const P p) {
   }
   __syncthreads();
   const unsigned long long excl = shu[wave], total = shu[ST / 64];
-  uint32_t c[4] = {(uint32_t)p.state[0], blockIdx.x, 0u, 0u};
-  const unsigned long long seed = p.seed ? *p.seed : 0ull;
+  uint32_t c[4] = {ctr0, ctr1, 0u, 0u};
   philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
   const unsigned long long r = ((unsigned long long)c[0] << 32) | c[1];
   const unsigned long long target = __umul64hi(r, total);           // uniform in [0, total)
@@ -355,13 +433,13 @@ __global__ __launch_bounds__(ST) void sample_kernel(const P p) {
       const unsigned long long row_total = __shfl(incl, 63, 64);
       if (run + row_total > target) {                               // the token is in this row
         const unsigned long long hit = __ballot(run + incl > target);
-        if (lane == 0) p.out[blockIdx.x] = seg0 + j * 64 + (int)__builtin_ctzll(hit);     // first index whose inclusive CDF exceeds the target
+        if (lane == 0) p0.out[blockIdx.x] = seg0 + j * 64 + (int)__builtin_ctzll(hit);     // first index whose inclusive CDF exceeds the target
         break;
       }
       run += row_total;
     }
   }
-  if (total == 0 && tid == 0) p.out[blockIdx.x] = imax == 0x7fffffff ? 0 : imax;   // nothing representable: the maximum
+  if (total == 0 && tid == 0) p0.out[blockIdx.x] = imax == 0x7fffffff ? 0 : imax;   // nothing representable: the maximum
 }
 
 // Loop bookkeeping of one token step in ONE small launch: (next_token == eos).all() of reference sampling.py:109 recorded as
@@ -559,7 +637,7 @@ extern "C" int mg_sample_f32(const float* logits, int64_t ld, int32_t B, int32_t
   if (top_k < 0 || top_p < 0.0 || top_p > 1.0) MG_FAIL(MG_ERR_SHAPE, "mg_sample_f32: need top_k >= 0 and 0 <= top_p <= 1");
   if (filtered && ld_filtered < V) MG_FAIL(MG_ERR_SHAPE, "mg_sample_f32: ld_filtered < V");
   SampleParams p{logits, ld, V, temperature, top_k, top_p, seed, state, token, filtered, ld_filtered};
-  hipLaunchKernelGGL(sample_kernel<SampleParams>, dim3(B), dim3(ST), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL((sample_kernel<SampleParams, FlatRows>), dim3(B), dim3(ST), 0, (hipStream_t)stream, p, FlatRows{});
   MG_CHECK_LAUNCH();
   return MG_OK;
 }
@@ -576,7 +654,37 @@ extern "C" int mg_sample_warp_f32(const float* logits, int64_t ld, int32_t B, in
   if (filtered && ld_filtered < V) MG_FAIL(MG_ERR_SHAPE, "mg_sample_warp_f32: ld_filtered < V");
   WarpParams p{{logits, ld, V, temperature, top_k, top_p, seed, state, token, filtered, ld_filtered},
                min_p > 0.0 ? log(min_p) : -(double)INFINITY};
-  hipLaunchKernelGGL(sample_kernel<WarpParams>, dim3(B), dim3(ST), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL((sample_kernel<WarpParams, FlatRows>), dim3(B), dim3(ST), 0, (hipStream_t)stream, p, FlatRows{});
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+// Per-request sampling (DESIGN.md "Per-request sampling"): sample_kernel's two instances once more, with TableRows as the source of
+// a row's scalars.  The checks cover what the host passes; the table's values are the kernel's to guard (SampleRow above).
+extern "C" int mg_sample_rows_f32(const float* logits, int64_t ld, int32_t R, int32_t V, int32_t warp, const void* params,
+                                  const int32_t* state, const int32_t* slot, const int32_t* finish, int32_t history_cols,
+                                  int64_t* token, float* filtered, int64_t ld_filtered, void* stream) {
+  const char* who = "mg_sample_rows_f32";
+  if (R <= 0 || V <= 0 || !logits || ld < V) MG_FAIL(MG_ERR_SHAPE, "%s: bad logits / R / V / ld", who);
+  if (warp != 0 && warp != 1) MG_FAIL(MG_ERR_SHAPE, "%s: warp must be 0 (the reference's filters) or 1 (transformers' sampler)", who);
+  if (!params || !state) MG_FAIL(MG_ERR_SHAPE, "%s: needs the parameter table and a state buffer", who);
+  if (!token && !filtered) MG_FAIL(MG_ERR_SHAPE, "%s: nothing to produce (token and filtered are both null)", who);
+  if (finish && !slot) MG_FAIL(MG_ERR_SHAPE, "%s: a finish record without the slot table (the static call skips no row)", who);
+  if (slot && !finish) MG_FAIL(MG_ERR_SHAPE, "%s: the slot table without the finish record", who);
+  if (slot && history_cols <= 0) MG_FAIL(MG_ERR_SHAPE, "%s: a slot session's ring has history_cols > 0", who);
+  if (filtered && ld_filtered < V) MG_FAIL(MG_ERR_SHAPE, "%s: ld_filtered < V", who);
+  if (!MG_ALIGNED16(params)) MG_FAIL(MG_ERR_ALIGN, "%s: the parameter table must be 16-byte aligned", who);
+  if (((uintptr_t)logits | (uintptr_t)state | (uintptr_t)slot | (uintptr_t)finish | (uintptr_t)filtered) & 3)
+    MG_FAIL(MG_ERR_ALIGN, "%s: fp32 / int32 buffers must be 4-byte aligned", who);
+  if ((uintptr_t)token & 7) MG_FAIL(MG_ERR_ALIGN, "%s: the token buffer must be 8-byte aligned", who);
+  const TableRows src{(const SampleRow*)params, slot, finish, history_cols};
+  const SampleParams p{logits, ld, V, 1.0f, 0, 0.0, nullptr, state, token, filtered, ld_filtered};
+  if (warp) {
+    const WarpParams w{p, -(double)INFINITY};
+    hipLaunchKernelGGL((sample_kernel<WarpParams, TableRows>), dim3(R), dim3(ST), 0, (hipStream_t)stream, w, src);
+  } else {
+    hipLaunchKernelGGL((sample_kernel<SampleParams, TableRows>), dim3(R), dim3(ST), 0, (hipStream_t)stream, p, src);
+  }
   MG_CHECK_LAUNCH();
   return MG_OK;
 }
@@ -890,24 +998,6 @@ struct HistView {
     }
   }
 };
-
-// The window of row b of a slot session before this step's selection, from the tables mg_sample_finish_slots keeps
-// (slot[b] = {begin, limit}, finish[b] = {step or -1, code}) and s = state[0]: the occupant's n = ((s - 1) % cols - begin) mod
-// cols + 1 tokens from column begin on -- the count sample_finish_slots_kernel forms.  n = 0: the row is idle (finished and not
-// harvested yet, or never occupied) or its begin lies outside the ring; such a row is skipped whole.  s is any value: the
-// column is formed as slots_admit_kernel forms it, and n lies in [1, cols] by construction.
-struct SlotWin { int begin, n; };
-MG_DEV SlotWin slot_window(const int32_t* __restrict__ state, const int32_t* __restrict__ slot, const int32_t* __restrict__ finish,
-                           int b, int cols) {
-  if (finish[2 * (int64_t)b] >= 0) return SlotWin{0, 0};
-  const int begin = slot[2 * (int64_t)b];
-  if (begin < 0 || begin >= cols) return SlotWin{0, 0};
-  const int prev = (int)((unsigned)state[0] - 1u);
-  const int col = ((prev % cols) + cols) % cols;
-  int d = col - begin;                      // in (-cols, cols)
-  if (d < 0) d += cols;
-  return SlotWin{begin, d + 1};
-}
 
 // mg_token_logprobs_slots_f32: the body above at column n of an occupied row (column 0 is the admission's); an idle row and a
 // column at or beyond cols write nothing.

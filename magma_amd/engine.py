@@ -57,6 +57,9 @@ class KVCache:
         # the seed of the sampling stream, the eos id the bookkeeping launch compares against
         self.sample_state = torch.tensor([0, -1], dtype=torch.int32, device=device)
         self.seed = torch.zeros(1, dtype=torch.int64, device=device)
+        # per-request sampling (DESIGN.md "Per-request sampling"): one record of settings and seed per row (uint8 [B,
+        # ops.SAMPLE_ROW_BYTES]; allocated by SelectionPlan.arm under a ("rows", warp) mode, written outside the captured step)
+        self.sample_rows = None
         self.eos = -1
         self.history = torch.zeros(B, Smax, dtype=torch.int64, device=device)   # token selected at step s of the current loop
         self.B, self.Smax = B, Smax
@@ -1404,6 +1407,12 @@ class SlotSession:
     does; the first token of a request is drawn at its admission from a counter domain of its own, (admit_counter(pass), staging
     row) with admit_counter(p) = -1 - p -- as the kernel's unsigned counter word 2^32 - 1 - p, which no token step reaches -- so
     no two draws of a session share a counter (draw_counters is the host statement of which ones a schedule uses).
+    Per-request sampling (plan.is_rows; DESIGN.md "Per-request sampling"): an item carries its own record (temperature, top_k, top_p,
+    min_p, seed) as its fourth entry.  The admission draws the first tokens with ops.sample_rows over the staging rows at counter 0
+    under a staging table (unused staging rows are greedy) and copies every admitted request's record into its slot's row of the
+    live table -- outside the captured step, before the next replay --; a token step draws row b at its occupant's own token index
+    under that record.  A request's draws then depend on its seed and its logits alone: admit_counter and draw_counters describe
+    the session-wide mode only.
     Session prefix (``prefix``: (P, d) embeddings or a one-row KVCache that is only read): its K / V positions [0, P) are put into
     every live slot and every staging row ONCE, at set-up (plain copies, as KVCache.expand); an admission pass then runs the
     cached-append prefill of LMEngine.extend over the same fixed (admit_rows, S_stage) rows behind them -- every staging row's
@@ -1475,8 +1484,12 @@ class SlotSession:
         assert self.Hc >= max_new + every
         cache.ring_cols, cache.eos = self.Hc, int(plan.stop[0][0])
         cache.sample_state.copy_(torch.tensor([1, -1], dtype=torch.int32), non_blocking=True)    # column (state[0] - 1) exists
-        if seed is not None:
+        if seed is not None and not plan.is_rows:
             cache.seed.fill_(int(seed) & 0x7fffffffffffffff)
+        if plan.is_rows:
+            if plan.cons is not None:
+                raise NotImplementedError("per-request sampler settings are not combined with a constrained slot plan")
+            self.stage_rows = torch.zeros(admit_rows, ops.SAMPLE_ROW_BYTES, dtype=torch.uint8, device=dev)
         self.st = engine._ensure_decode_state(cache)
         if self.st.refusal is not None:
             raise NotImplementedError(self.st.refusal)
@@ -1598,6 +1611,12 @@ class SlotSession:
                 ops.logits_process(logits, self.zero_state, self.stage_hist, **kw)
         if mode is None:
             ops.argmax(logits, out=self.first)
+        elif plan.is_rows:      # every request under its own record at counter 0 -- its solo call's first draw; then the records go live
+            recs = [it[3] for it in batch] + [(0.0, 0, 0.0, 0.0, 0)] * (self.n_admit - n)
+            self.stage_rows.copy_(ops.sample_rows_table(*zip(*recs)), non_blocking=True)
+            ops.sample_rows(logits, self.stage_rows, self.zero_state, mode[1], out=self.first)
+            at = torch.tensor(slots, dtype=torch.int64).to(logits.device, non_blocking=True)
+            cache.sample_rows.index_copy_(0, at, self.stage_rows[:n])
         else:       # a counter domain of its own: the token steps draw under state[0] = 1, 2, ..., never under a negative value
             self.admit_state[:1].fill_(self.admit_counter(self.passes))
             if mode[0] == "warp":
@@ -1676,7 +1695,8 @@ class SlotSession:
 
     def run(self, requests):
         """Yield (request index, tokens, finish code, slot[, log-probabilities: _harvest]) in completion order.  ``requests`` yields
-        (index, (S, d) embeddings on the engine's device, limit[, TokenTrie: under a constrained plan]), is pulled lazily -- one item when a slot frees.  When it raises, nothing more is pulled, the
+        (index, (S, d) embeddings on the engine's device, limit[, TokenTrie: under a constrained plan; or the request's sampler record
+        (temperature, top_k, top_p, min_p, seed): under a per-row plan]), is pulled lazily -- one item when a slot frees.  When it raises, nothing more is pulled, the
         requests pulled before it are admitted and every row in flight is generated to its end and yielded; then the error is
         raised: no request in front of the failing one is lost."""
         it, exhausted, error = iter(requests), False, None

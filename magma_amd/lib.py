@@ -128,6 +128,7 @@ SYMBOLS = {
     "mg_advance_pos": (C.c_int, [_vp, _i32, _i32, _i32, _vp]),
     "mg_sample_f32": (C.c_int, [_vp, _i64, _i32, _i32, _f32, _i32, C.c_double, _vp, _vp, _vp, _vp, _i64, _vp]),
     "mg_sample_warp_f32": (C.c_int, [_vp, _i64, _i32, _i32, _f32, _i32, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "mg_sample_rows_f32": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _vp]),
     "mg_sample_finish": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp]),
     "mg_sample_finish_rows": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i64, _vp,
                                         _vp]),

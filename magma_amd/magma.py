@@ -321,7 +321,9 @@ class Magma(nn.Module):
         that are penalised for selecting the tokens earlier groups selected at the same step, and ``num_return_sequences`` takes
         the groups' hypotheses round-robin: several different captions of one image (see sampling.generate).
         ``penalty_alpha`` in (0, 1] with ``top_k`` in [1, 16]: contrastive search -- among the ``top_k`` most probable tokens the one
-        whose hidden state is least similar to the context's, deterministic (see sampling.generate)."""
+        whose hidden state is least similar to the context's, deterministic (see sampling.generate).
+        ``seed`` / ``temperature`` / ``top_k`` / ``top_p`` / ``min_p`` may each be a sequence of B values: every row then samples
+        under its own settings and seed and equals its one-row call (see sampling.generate, per-row sampling)."""
         torch.cuda.set_device(self.device)
         return generate(self, embeddings=embeddings, max_steps=max_steps, temperature=temperature, top_k=top_k,
                         top_p=top_p, decode=decode, stop_on_eos=stop_on_eos, seed=seed, eos_check_every=eos_check_every,
@@ -340,7 +342,8 @@ class Magma(nn.Module):
         """Generate over a stream of requests -- an iterable of ``embed`` outputs, or pairs (embeddings, max_new_tokens) --: a
         generator of ``sampling.StreamResult(index, tokens, text, reason, reason_index, slot)``, one per request in completion
         order, each what a solo ``generate`` of that request gives.  The HIP engine hands the row of a finished request to the next
-        one while the other rows keep generating (see sampling.generate_stream for the keywords)."""
+        one while the other rows keep generating (see sampling.generate_stream for the keywords).  ``per_request=True``: an item may
+        be a ``sampling.StreamRequest`` with sampler settings and a seed of its own, reproducible against its solo call."""
         from .sampling import generate_stream
         torch.cuda.set_device(self.device)
         return generate_stream(self, requests, **kwargs)

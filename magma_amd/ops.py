@@ -864,6 +864,49 @@ def sample_warp(logits: torch.Tensor, temperature: float, top_k: int, top_p: flo
     return out
 
 
+SAMPLE_ROW_BYTES = 32                                                   # include/magma_hip.h MG_SAMPLE_ROW_BYTES
+
+
+def sample_rows_table(temperature, top_k, top_p, min_p, seed) -> torch.Tensor:
+    """The host image of mg_sample_rows_f32's table, uint8 [R, SAMPLE_ROW_BYTES], from five sequences of R values: per row
+    {double top_p, double log(min_p) (-inf: off), uint64 seed, float temperature, int32 top_k}.  The logarithm is math.log -- the C
+    library's, which mg_sample_warp_f32 calls on its ``min_p`` -- so a row's min-p bound has the flat call's bits."""
+    import math
+    import struct
+    rows = list(zip(temperature, top_k, top_p, min_p, seed))
+    raw = b"".join(struct.pack("<ddQfi", float(p), math.log(float(m)) if float(m) > 0.0 else -math.inf,
+                               int(s) & 0xffffffffffffffff, float(t), int(k)) for t, k, p, m, s in rows)
+    assert len(raw) == SAMPLE_ROW_BYTES * len(rows)
+    return torch.frombuffer(bytearray(raw), dtype=torch.uint8).view(len(rows), SAMPLE_ROW_BYTES)
+
+
+def sample_rows(logits: torch.Tensor, params: torch.Tensor, state: torch.Tensor, warp: bool = False,
+                out: Optional[torch.Tensor] = None, filtered: Optional[torch.Tensor] = None, want_token: bool = True,
+                slot: Optional[torch.Tensor] = None, finish: Optional[torch.Tensor] = None, history_cols: int = 0):
+    """``sample`` (``warp``: ``sample_warp``) with every row's temperature, top_k, top_p, min_p and seed read from the device
+    table ``params`` (sample_rows_table; mg_sample_rows_f32; DESIGN.md "Per-request sampling"): row r draws at the Philox counter
+    (j, 0) under its own seed -- j = ``state[0]``, or with ``slot`` / ``finish`` (a slot session's tables, ``history_cols`` its
+    ring) the occupant's own token index, idle rows skipped --, so it selects what the flat call on that row alone selects at
+    step j.  A row with temperature 0 takes its first maximum.  Enqueue-only."""
+    _need_gpu(logits, params, state, out, filtered, slot, finish)
+    assert logits.dtype == torch.float32 and logits.ndim == 2 and logits.stride(1) == 1
+    R, V = logits.shape
+    assert params.dtype == torch.uint8 and params.is_contiguous() and params.shape == (R, SAMPLE_ROW_BYTES)
+    assert state.dtype == torch.int32 and state.numel() >= 1
+    if want_token and out is None:
+        out = torch.empty(R, dtype=torch.int64, device=logits.device)
+    if want_token:
+        assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() == R
+    if filtered is not None:
+        assert filtered.dtype == torch.float32 and filtered.shape == logits.shape and filtered.stride(1) == 1
+    for t in (slot, finish):
+        assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.shape == (R, 2))
+    check(L.load().mg_sample_rows_f32(logits.data_ptr(), logits.stride(0), R, V, int(bool(warp)), params.data_ptr(), _p(state),
+                                      _p(slot), _p(finish), int(history_cols), _p(out) if want_token else None, _p(filtered),
+                                      0 if filtered is None else filtered.stride(0), _stream()), "mg_sample_rows_f32")
+    return out
+
+
 def sample_finish(token: torch.Tensor, eos: int, state: torch.Tensor, d_pos: Optional[torch.Tensor] = None, delta: int = 1,
                   history: Optional[torch.Tensor] = None, clear: Optional[torch.Tensor] = None, clear_stride: int = 1, *,
                   pos_stride: int = 0):

@@ -1255,6 +1255,59 @@ def sampling_mode(temperature, top_k, top_p, warp, seed):
     return mode, int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else seed
 
 
+ROW_SAMPLER_ARGS = ("temperature", "top_k", "top_p", "min_p", "seed")
+
+
+def per_row_given(**args) -> tuple:
+    """The names among generate()'s ``temperature, top_k, top_p, min_p, seed`` that are given per row: a list, a tuple or a
+    tensor / array of one dimension.  Empty: the call is the scalar one."""
+    def is_seq(v):
+        return isinstance(v, (list, tuple)) or (hasattr(v, "ndim") and hasattr(v, "tolist") and getattr(v, "ndim", 0) >= 1)
+    return tuple(k for k in ROW_SAMPLER_ARGS if is_seq(args.get(k)))
+
+
+def check_row_sampler_args(batch: int, sampler="reference", temperature=0.7, top_k=0, top_p=0.9, min_p=0.0, seed=None) -> list:
+    """Per-row sampler settings (DESIGN.md "Per-request sampling"): each of the five may be a sequence or a one-dimensional tensor of
+    ``batch`` values, a scalar stands for every row.  Returns one record (temperature, top_k, top_p, min_p, seed) per row, every
+    row checked as the scalar call checks its arguments (check_sampler_args; min_p on a greedy row), with the bounds the flat
+    kernels refuse; a sampled row without a seed draws one from torch's CPU generator, where the scalar call draws its own, and a
+    greedy row's seed is 0 (it reads none).  A tensor's values are taken as they are: a float32 0.9 is not the double 0.9 the scalar
+    call passes down, so pass float64 tensors (or lists) where a row must equal its scalar call."""
+    cols = {}
+    for name, v in zip(ROW_SAMPLER_ARGS, (temperature, top_k, top_p, min_p, seed)):
+        if per_row_given(**{name: v}):
+            v = v.tolist() if hasattr(v, "tolist") else list(v)
+            if len(v) != batch:
+                raise ValueError(f"{name} has {len(v)} entries, the batch {batch} rows: pass one value per row or a scalar")
+        else:
+            v = [v] * batch
+        cols[name] = v
+    rows = []
+    for r in range(batch):
+        t, k, p, m, sd = (cols[name][r] for name in ROW_SAMPLER_ARGS)
+        where = f"row {r}: "
+        if isinstance(t, bool) or not isinstance(t, (int, float)) or not 0.0 <= t < float("inf"):
+            raise ValueError(f"{where}temperature must be a finite number >= 0 (0: greedy), got {t!r}")
+        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < 2 ** 31:
+            raise ValueError(f"{where}top_k must be an integer >= 0 (0: off), got {k!r}")
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0:
+            raise ValueError(f"{where}top_p must be a number in [0, 1], got {p!r}")
+        try:
+            check_sampler_args(sampler, m, p)
+        except ValueError as e:
+            raise ValueError(where + str(e)) from None
+        if m > 0 and t == 0.0:
+            raise ValueError(f"{where}min_p applies to sampled selection: greedy decoding (temperature=0) would drop it")
+        if sd is not None and (isinstance(sd, bool) or not isinstance(sd, int)):
+            raise ValueError(f"{where}seed must be an integer or None, got {sd!r}")
+        if t == 0.0:
+            sd = 0
+        elif sd is None:
+            sd = int(torch.randint(0, 2 ** 62, (1,)).item())
+        rows.append((float(t), int(k), float(p), float(m), int(sd) & 0x7fffffffffffffff))
+    return rows
+
+
 def layout_ids(tokens, s: int, lengths, image_token: int, eos_token: int, repeat: int = 1):
     """The ids generate() returns, (rows, s + n) on the device of ``tokens`` (rows, n): per row the image token for the length of
     its prompt, its tokens, eos up to the width.  ``lengths``: None (every prompt is ``s`` long) or the samples' host int64
@@ -1417,9 +1470,35 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     object runs the host statement on ``output_hidden_states``.  Not yet combined (NotImplementedError) with beam search /
     ``return_scores``, the logits processors, per-row stopping / several eos ids / ``return_finish``, ``return_logprobs``,
     ``constraint``, guidance, ``past_key_values`` / ``return_past_key_values``.  ``penalty_alpha=0.0`` (the default) is the call as
-    it was, bit for bit, with the same launches and nothing allocated."""
+    it was, bit for bit, with the same launches and nothing allocated.
+
+    Per-row sampling (DESIGN.md "Per-request sampling"; HIP engine only): ``seed``, ``temperature``, ``top_k``, ``top_p`` and
+    ``min_p`` may each be a list, tuple or one-dimensional tensor of B values (a scalar stands for every row); any of them given so
+    switches the call to the per-row mode.  Row b's j-th token (j = 0: the one selected from the prompt's logits) is then drawn
+    from the Philox stream keyed by ITS seed at counter j, over ITS logits filtered by ITS settings -- the key and counter of the
+    one-row call --, so for equal logits bits row b is the solo call ``generate(request_b, seed=seed_b, temperature=...,
+    sampler=...)`` whatever its row and its neighbours are: n samples of one cached prompt (``cache_prompt`` +
+    ``KVCache.expand(n)`` with n seeds) can each be regenerated alone, and greedy rows (temperature 0: the first maximum, no
+    seed) sit beside sampled ones.  ``sampler`` stays one per call.  Every row is checked as the scalar call checks its arguments
+    (ValueError names the row: a wrong length, ``min_p`` with the reference's sampler or on a greedy row, a value out of bounds);
+    a sampled row without a seed draws one from torch's CPU generator.  Combines with ragged prompts, per-row stopping, the
+    logits processors, log-probabilities, constraints, a continued cache and the quantised decode weights; not (NotImplementedError)
+    with beam search, contrastive search or guidance.  The selection is the same single launch of the captured step, reading a
+    device table (ops.sample_rows).  With scalars only, the call is what it was, bit for bit and launch for launch."""
     if eos_token is None or (isinstance(eos_token, int) and not eos_token):
         eos_token = model.eos_token
+    per_row = per_row_given(temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, seed=seed)
+    if per_row:
+        for what, given in (("beam search (num_beams > 1 / return_scores=True)", num_beams > 1 or return_scores),
+                            ("contrastive search (penalty_alpha > 0)", penalty_alpha != 0.0),
+                            ("guidance (guidance_scale / negative_embeddings)", guidance_scale != 1.0 or negative_embeddings is not None)):
+            if given:
+                raise NotImplementedError(f"per-row sampler settings ({', '.join(per_row)} given per row) are not combined with {what}")
+        # the scalar checks below see stand-ins for what is given per row; check_row_sampler_args checks every row once the
+        # batch is known
+        row_args = dict(temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, seed=seed)
+        stand_in = dict(temperature=1.0, top_k=0, top_p=0.9, min_p=0.0, seed=None)
+        temperature, top_k, top_p, min_p, seed = (stand_in[k] if k in per_row else row_args[k] for k in ROW_SAMPLER_ARGS)
     early_stopping = check_beam_args(num_beams, num_return_sequences, early_stopping, num_beam_groups, diversity_penalty,
                                      _logit_count(model))
     proc = check_processor_args(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, _logit_count(model))
@@ -1475,6 +1554,10 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
                               float(length_penalty), early_stopping, num_return_sequences, return_scores, proc,
                               num_beam_groups, float(diversity_penalty))
     b, s, _ = embeddings.shape
+    if per_row:
+        row_records = check_row_sampler_args(b, sampler, **row_args)
+        if not on_device:
+            raise ValueError("per-row sampler settings need the HIP engine's LM (one selection launch reads every row's record)")
     if guide is not None:       # the negative prompt as (b, s', d) rows, row counts and hidden size checked
         guide = check_guidance_args(guidance_scale, negative_embeddings, negative_lengths, guidance_min_p, b, embeddings.shape[2])
     cons = check_constraint_args(constraint, b, getattr(getattr(model, "tokenizer", None), "encode", None), _logit_count(model),
@@ -1489,6 +1572,8 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     if guide is not None and guide["lengths"] is not None and not on_device:
         raise ValueError("negative prompts of different lengths need the HIP engine's LM (per-row KV positions)")
     mode, seed = sampling_mode(temperature, top_k, top_p, warp, seed)
+    if per_row:                 # ("rows", warp): the values travel in the cache's table, ``seed`` carries the rows' records to it
+        mode, seed = ("rows", warp is not None), row_records
     modes = dict(mode=mode, proc=proc, stop=stop, n_top=n_top, cons=cons, guide=guide, eos_ids=eos_ids)
     want_finish = stop is not None and (return_finish or continuing or decode)      # the tail reads the per-row finish record
     with eval_mode(model):
@@ -1545,6 +1630,9 @@ def _device_loop(model, embeddings, lengths, max_steps, eos_token, seed, every, 
     plan = LMEngine.selection_plan(sampling=modes.get("mode"), beam=modes.get("beam"), processors=modes.get("proc"), stop=stop,
                                    logprobs=n_top, constraint=modes.get("cons"), contrast=modes.get("contrast"),
                                    guidance=None if guide is None else (guide["scale"], guide["min_p"]), vocab=model.lm.engine.V)
+    if plan.is_rows:            # the rows' records as the host image of the device table (SelectionPlan._arm_first_token copies it)
+        from . import ops
+        seed = ops.sample_rows_table(*zip(*seed))
     first_kw = dict(eos_token=eos_token, seed=seed, plan=plan, lengths=lengths)
     own = lengths if lengths is not None else torch.full((b,), s, dtype=torch.int64)     # the positions every row adds
     prompts, start = embeddings, own
@@ -1674,6 +1762,23 @@ class StreamResult(NamedTuple):
     slot: Optional[int]         # the row of the session the request ran in (None: an LM object without slots)
 
 
+class StreamRequest:
+    """One request of ``generate_stream(..., per_request=True)`` with sampler settings and a seed of its own (DESIGN.md "Per-request
+    sampling"): ``embeddings`` (1, S, d) / (S, d); a field left at None takes the session's keyword -- ``max_new_tokens``,
+    ``temperature``, ``top_k``, ``top_p``, ``min_p``, and ``seed`` (the session's ``seed`` is the default seed of a request that gives
+    none)."""
+    __slots__ = ("embeddings", "max_new_tokens", "temperature", "top_k", "top_p", "min_p", "seed")
+
+    def __init__(self, embeddings, max_new_tokens=None, temperature=None, top_k=None, top_p=None, min_p=None, seed=None):
+        self.embeddings, self.max_new_tokens = embeddings, max_new_tokens
+        self.temperature, self.top_k, self.top_p, self.min_p, self.seed = temperature, top_k, top_p, min_p, seed
+
+    def __repr__(self):
+        shape = tuple(self.embeddings.shape) if torch.is_tensor(self.embeddings) else type(self.embeddings).__name__
+        return "StreamRequest(" + ", ".join([f"embeddings={shape}"] + [f"{k}={getattr(self, k)!r}" for k in self.__slots__[1:]
+                                                                        if getattr(self, k) is not None]) + ")"
+
+
 # what generate() takes and a request stream refuses when it differs from generate()'s default
 _STREAM_REFUSED = (
     ("the logits processors are", ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "suppress_tokens")),
@@ -1754,7 +1859,7 @@ def _stream_args(model, slots, max_new_tokens, max_prompt, every, admit_rows, pr
 def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 100, max_prompt: int = None, eos_token=None,
                     stop_sequences=None, temperature: float = 0.0, top_k: int = 0, top_p: float = 0.9,
                     sampler: str = "reference", min_p: float = 0.0, seed: int = None, every: int = None, admit_rows: int = None,
-                    decode: bool = True, prefix=None, share_prefix: bool = False, **unsupported):
+                    decode: bool = True, prefix=None, share_prefix: bool = False, per_request: bool = False, **unsupported):
     """Generate over a stream of requests (DESIGN.md "Request streams"): yields one ``StreamResult`` per request, in completion
     order.  Request i's tokens, finish reason and index are those of the solo call
 
@@ -1783,7 +1888,21 @@ def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 10
     Greedy decoding (``temperature=0``, the default) and both samplers are supported.  A sampled request draws its first token
     at its admission from the Philox counter (2^32 - 1 - admission pass, staging row) and every later token from (global step
     of the session, slot) -- two domains that never meet, so no two draws of a session share a counter (engine.SlotSession) --,
-    NOT from the counters of a solo call: only greedy decoding and ``top_k=1`` are reproducible against a solo call.  Not combined (NotImplementedError): the logits processors, return_logprobs, constraint,
+    NOT from the counters of a solo call: in this session-wide mode only greedy decoding and ``top_k=1`` are reproducible against a
+    solo call.
+    ``per_request=True`` (DESIGN.md "Per-request sampling"): every request has sampler settings and a seed of its own, and a sampled
+    request IS reproducible against its solo call.  An item may then also be a ``StreamRequest(embeddings, max_new_tokens=None,
+    temperature=None, top_k=None, top_p=None, min_p=None, seed=None)``; a field left at None -- and every field of a plain tensor or
+    pair item -- takes the session's keyword, the session's ``seed`` being the default seed of a request that gives none (a sampled
+    request without either draws one from torch's CPU generator when it is pulled).  Request i's tokens, reason and index are
+    those of the solo call above with ``temperature=, top_k=, top_p=, min_p=, seed=`` of request i and the session's ``sampler``
+    (the rule set stays one per session): its j-th token is drawn from the Philox stream keyed by ITS seed at counter j over ITS
+    logits filtered by ITS settings, the first at its admission, so its tokens do not depend on its slot, on the requests beside
+    it, on ``every``, on ``admit_rows`` or on the admission pass, and greedy and sampled requests share a session.  The HIP engine
+    reads the settings from a device table inside the same selection launch of the same captured step (ops.sample_rows); an LM
+    object that is not the HIP engine runs the solo calls one after another with each request's own settings.  A
+    ``StreamRequest`` without ``per_request=True`` raises ValueError when it is pulled.  With ``per_request=False`` (the default)
+    everything is what it was.  Not combined (NotImplementedError): the logits processors, return_logprobs, constraint,
     guidance, beam and contrastive search, past_key_values.  (A closed answer set per request with its log-probabilities and the
     rules is ``choose_stream``, whose session runs the constraint, rule and log-probability kernels over the ring.)
     The arguments are checked when the call is made; the work starts with the first ``next``.
@@ -1825,14 +1944,36 @@ def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 10
     stop = check_stop_args(eos_token, stop_sequences, True, _logit_count(model),
                            getattr(getattr(model, "tokenizer", None), "encode", None))
     warp = check_sampler_args(sampler, min_p, top_p)
-    if min_p > 0 and temperature == 0.0:
+    if not isinstance(per_request, bool):
+        raise ValueError(f"per_request must be True or False, got {per_request!r}")
+    if min_p > 0 and temperature == 0.0 and not per_request:
         raise ValueError("min_p applies to sampled selection: greedy decoding (temperature=0) would drop it")
-    mode, seed = sampling_mode(temperature, top_k, top_p, warp, seed)
+    if per_request:             # the values travel with the requests; the session's are the defaults of their None fields
+        if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int)):
+            raise ValueError(f"seed must be an integer or None, got {seed!r}")
+        mode = ("rows", warp is not None)
+        session_values = dict(temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, seed=seed)
+    else:
+        mode, seed = sampling_mode(temperature, top_k, top_p, warp, seed)
+
+    def record_of(index, item):
+        """Request ``index``'s (temperature, top_k, top_p, min_p, seed), checked as generate() checks a row's."""
+        given = {k: getattr(item, k, None) for k in ROW_SAMPLER_ARGS}
+        try:
+            return check_row_sampler_args(1, sampler, **{k: session_values[k] if v is None else v for k, v in given.items()})[0]
+        except ValueError as e:
+            raise ValueError(f"request {index}: {str(e).replace('row 0: ', '', 1)}") from None
 
     def pulled():
-        """(index, (S, d) embeddings, limit) of every request, checked as it is pulled."""
+        """(index, (S, d) embeddings, limit) of every request, checked as it is pulled -- with ``per_request``, followed by the
+        request's record (temperature, top_k, top_p, min_p, seed)."""
         for index, item in enumerate(requests):
-            emb, limit = item if isinstance(item, (tuple, list)) else (item, max_new_tokens)
+            if isinstance(item, StreamRequest):
+                if not per_request:
+                    raise ValueError(f"request {index}: a StreamRequest needs generate_stream(..., per_request=True)")
+                emb, limit = item.embeddings, max_new_tokens if item.max_new_tokens is None else item.max_new_tokens
+            else:
+                emb, limit = item if isinstance(item, (tuple, list)) else (item, max_new_tokens)
             if not torch.is_tensor(emb) or emb.ndim not in (2, 3) or (emb.ndim == 3 and emb.shape[0] != 1):
                 raise ValueError(f"request {index}: an item is an embeddings tensor (1, S, d) or (S, d), or a pair of one and its "
                                  "max_new_tokens")
@@ -1842,7 +1983,10 @@ def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 10
                                  f"max_new_tokens), got {limit!r}")
             if not 1 <= emb.shape[0] <= max_prompt:
                 raise ValueError(f"request {index}: a prompt of {emb.shape[0]} rows is outside [1, max_prompt = {max_prompt}]")
-            yield index, emb, limit
+            if per_request:
+                yield index, emb, limit, record_of(index, item)
+            else:
+                yield index, emb, limit
 
     def text_of(ids, reason):
         if not decode:
@@ -1854,9 +1998,11 @@ def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 10
         kw = dict(eos_token=list(stop["eos_ids"]), stop_sequences=[list(q) for q in stop["stop_seqs"]] or None, stop_per_row=True,
                   return_finish=True, decode=False, temperature=temperature, top_k=top_k, top_p=top_p, sampler=sampler, min_p=min_p,
                   seed=seed, eos_check_every=every)
-        for index, emb, limit in pulled():
+        for index, emb, limit, *record in pulled():
             if P:
                 emb = torch.cat([prefix.to(emb.device, emb.dtype), emb])
+            if record:          # per_request: the request's own settings and seed reach its solo call
+                kw.update(zip(ROW_SAMPLER_ARGS, record[0]))
             out, fin = generate(model, emb[None], max_steps=limit, **kw)
             ids = out[0, emb.shape[0]: emb.shape[0] + int(fin.kept[0])].to("cpu", torch.int64)
             yield StreamResult(index, ids, text_of(ids, fin.reason[0]), fin.reason[0], fin.index[0], None)
@@ -1868,9 +2014,9 @@ def generate_stream(model, requests, *, slots: int = 8, max_new_tokens: int = 10
             torch.cuda.set_device(model.device)
         plan = LMEngine.selection_plan(sampling=mode, stop=stop, vocab=eng.V, slots=True)
         ses = SlotSession(eng, plan, slots=slots, max_new=max_new_tokens, max_prompt=max_prompt, every=every,
-                          admit_rows=admit_rows, seed=seed, prefix=prefix, share_prefix=share_prefix)
+                          admit_rows=admit_rows, seed=None if per_request else seed, prefix=prefix, share_prefix=share_prefix)
         dev = eng.device
-        for index, ids, code, slot in ses.run((i, e.to(dev), n) for i, e, n in pulled()):
+        for index, ids, code, slot in ses.run((i, e.to(dev), n, *rest) for i, e, n, *rest in pulled()):
             reason = REASON_NAMES[code >> 8]
             yield StreamResult(index, ids, text_of(ids, reason), reason, -1 if reason == "length" else code & 255, slot)
 

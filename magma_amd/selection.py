@@ -131,6 +131,12 @@ class SelectionPlan(NamedTuple):
         return isinstance(self.mode, tuple) and self.mode[:1] == ("contrast",)
 
     @property
+    def is_rows(self) -> bool:
+        """Per-request sampling (DESIGN.md "Per-request sampling"): mode ("rows", warp) -- every row's settings and seed come from
+        the cache's table (``cache.sample_rows``), not from the mode."""
+        return isinstance(self.mode, tuple) and self.mode[:1] == ("rows",)
+
+    @property
     def beam_groups(self) -> tuple:
         """(num_beam_groups, diversity_penalty) of a beam mode: (1, 0.0) for the five-entry tuple of plain beam search."""
         return tuple(self.mode[5:7]) if len(self.mode) > 5 else (1, 0.0)
@@ -208,6 +214,11 @@ class SelectionPlan(NamedTuple):
                 cache.stop_held = tuple(self.stop)
             if first:       # every row unfinished again
                 cache.finish.copy_(torch.tensor([[-1, 0]] * cache.B, dtype=torch.int32), non_blocking=True)
+        if self.is_rows and (cache.sample_rows is None or cache.sample_rows.shape[0] != cache.B):
+            # one record per row (ops.sample_rows_table), greedy until a call or an admission writes the row's own; the table's
+            # address is a launch argument of the captured step, its contents are not
+            cache.sample_rows = torch.zeros(cache.B, ops.SAMPLE_ROW_BYTES, dtype=torch.uint8, device=dev)
+            cache._drop_graphs(lambda key: isinstance(key.mode, tuple) and key.mode[:1] == ("rows",))
         if self.slots:
             if self.stop is None or not cache.ragged or cache.ring_cols < 1:
                 raise ValueError("a slot step needs per-row stopping and a ragged cache with ring_cols set (SlotSession)")
@@ -273,6 +284,8 @@ class TokenSelection:
             if contrast is not None and given is not None:
                 raise NotImplementedError(f"{what} not combined with contrastive search")
         mode = cls.sample_mode(sampling)
+        if isinstance(mode, tuple) and mode[:1] == ("rows",) and any(v is not None for v in (beam, guidance, contrast)):
+            raise NotImplementedError("per-row sampler settings are not combined with beam search, contrastive search or guidance")
         if beam is not None:
             mode = cls.beam_mode(beam)
         if contrast is not None:
@@ -286,9 +299,14 @@ class TokenSelection:
     def sample_mode(sampling):
         """None (greedy), (temperature, top_k, top_p) -- the reference's filters, ops.sample -- or ("warp", temperature, top_k,
         top_p, min_p) -- transformers' sampler, ops.sample_warp (DESIGN.md "transformers' sampler"): the selection mode, with its
-        values normalised so that it can key a captured step."""
+        values normalised so that it can key a captured step.  ("rows", warp) -- ops.sample_rows (DESIGN.md "Per-request
+        sampling") -- carries no values: every row's are in the cache's table, so one captured step serves any of them."""
         if sampling is None:
             return None
+        if sampling[0] == "rows":
+            if len(sampling) != 2:
+                raise ValueError(f'the per-row selection mode is ("rows", warp), got {sampling!r}')
+            return ("rows", bool(sampling[1]))
         if sampling[0] == "warp":
             if len(sampling) != 5:
                 raise ValueError(f'the warp selection mode is ("warp", temperature, top_k, top_p, min_p), got {sampling!r}')
@@ -352,12 +370,14 @@ class TokenSelection:
         return n
 
     def _arm_first_token(self, out: LMOutput, logits, cache: KVCache, eos_token, seed, plan: SelectionPlan):
-        """generate(): the first token of the loop selected from the prefill / extend logits, device-side bookkeeping armed."""
+        """generate(): the first token of the loop selected from the prefill / extend logits, device-side bookkeeping armed.
+        Under a per-row plan (plan.is_rows) ``seed`` is the rows' host table (ops.sample_rows_table): it goes into
+        cache.sample_rows, and token 0 is selected by the step's own launch at counter 0."""
         if cache.eos != int(eos_token):        # the eos id is a launch argument of the captured bookkeeping kernel
             cache.eos = int(eos_token)
             cache._drop_graphs()
         cache.sample_state.copy_(torch.tensor([0, -1], dtype=torch.int32), non_blocking=True)
-        if seed is not None:
+        if seed is not None and not plan.is_rows:
             cache.seed.fill_(int(seed) & 0x7fffffffffffffff)
         st = self._ensure_decode_state(cache)      # the first token lands where the decode steps read it back
         if plan.is_beam:
@@ -371,6 +391,11 @@ class TokenSelection:
         if plan.stop is not None and int(eos_token) != plan.stop[0][0]:
             raise ValueError(f"per-row stopping pads with the first eos id: eos_token must be {plan.stop[0][0]}, got {eos_token}")
         plan.arm(cache, st, first=True)
+        if plan.is_rows:
+            if not torch.is_tensor(seed) or tuple(seed.shape) != tuple(cache.sample_rows.shape) or seed.dtype != torch.uint8:
+                raise ValueError(f"a per-row plan takes the rows' table as seed=: uint8 {tuple(cache.sample_rows.shape)} "
+                                 "(ops.sample_rows_table)")
+            cache.sample_rows.copy_(seed, non_blocking=True)
         if plan.is_contrast:
             # no token yet: selecting one needs its candidates' hidden states, so the prefill's logits give the first candidate set
             self._arm_contrast(cache, st, plan, logits)
@@ -529,6 +554,9 @@ class TokenSelection:
             return self._select_beam(logits, cache, plan, advance)
         if mode is None:
             tok = ops.argmax(logits, out=out)
+        elif mode[0] == "rows":     # every row under its own record; a slot step: at the occupant's own token index, idle rows skipped
+            tok = ops.sample_rows(logits, cache.sample_rows, cache.sample_state, mode[1], out=out,
+                                  **(dict(slot=cache.slot_table, finish=cache.finish, history_cols=cache.ring_cols) if plan.slots else {}))
         elif mode[0] == "warp":
             tok = ops.sample_warp(logits, mode[1], mode[2], mode[3], mode[4], cache.seed, cache.sample_state, out=out)
         else:

@@ -39,6 +39,14 @@ The shared session prefix (DESIGN.md "Shared session prefix") against the per-sl
 legs become ``generate_stream(prefix=..., share_prefix=True)`` and ``generate_stream(prefix=...)``, interleaved; the step part
 gains the variant ``with_shared_prefix`` (every step record carries the live-cache bytes), and one more record times the
 prefix-partials launch alone (one per block, captured, replayed).
+
+  python tools/stream_bench.py --per-request [--out FILE (default profiles/stream_per_request_bench.jsonl)]
+
+Per-request sampling (DESIGN.md "Per-request sampling"): the captured step of an 8-slot session sampled at temperature 0.7, top_k 40,
+once under the session-wide sampler (mg_sample_f32: one set of launch arguments, one seed) and once under the per-row launch
+(mg_sample_rows_f32: the same settings in every row's record of the device table, eight seeds).  Device events around ``--steps``
+replays, windows interleaved, every window from the same positions, medians of ``--reps``; the session-wide step runs twice
+(``session_wide``, ``session_wide_again``): the difference of the two is the spread the per-row step is read against.
 """
 import argparse
 import json
@@ -65,11 +73,14 @@ ap.add_argument("--prefix-rows", type=int, default=0, help="P > 0: measure the s
 ap.add_argument("--share-prefix", action="store_true", help="with --prefix-rows: add the share_prefix=True legs (one copy of the "
                 "prefix, read once per step for all rows), the prefix-partials launch alone and the live-cache bytes")
 ap.add_argument("--choices", action="store_true", help="measure choose_stream instead (see the module docstring)")
+ap.add_argument("--per-request", action="store_true", help="measure the per-row sampling launch against the session-wide one "
+                "(see the module docstring)")
 ap.add_argument("--request-rows", type=int, default=160, help="rows of every request in the --prefix-rows mode")
 ap.add_argument("--out", default=None, help="default: profiles/stream_bench.jsonl, profiles/stream_prefix_bench.jsonl with --prefix-rows")
 args = ap.parse_args()
 if args.out is None:
     args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                            "stream_per_request_bench.jsonl" if args.per_request else
                             "choose_stream_bench.jsonl" if args.choices else
                             "stream_shared_prefix_bench.jsonl" if args.prefix_rows and args.share_prefix else
                             "stream_prefix_bench.jsonl" if args.prefix_rows else "stream_bench.jsonl")
@@ -337,7 +348,53 @@ def prefix_mode():
     write_out()
 
 
+def per_request_mode():
+    """--per-request: the captured sampled slot step, session-wide sampler against the per-row launch."""
+    emb = model.embed([images, prompt])
+    S0, n_new = int(emb.shape[1]), args.steps + 8
+    stop = dict(eos_ids=(EOS,), stop_seqs=())
+    T, K, TOP_P = 0.7, 40, 0.9
+    plans = {"session_wide": LMEngine.selection_plan(sampling=(T, K, TOP_P), stop=stop, vocab=eng.V, slots=True),
+             "per_row": LMEngine.selection_plan(sampling=("rows", False), stop=stop, vocab=eng.V, slots=True)}
+    plans["session_wide_again"] = plans["session_wide"]
+    held = {}
+    for name, plan in plans.items():
+        ses = SlotSession(eng, plan, slots=B, max_new=n_new, max_prompt=S0, every=1, admit_rows=B, seed=5)
+        ses._admit([(i, emb[i % 8], n_new) + (((T, K, TOP_P, 0.0, 100 + i),) if plan.is_rows else ()) for i in range(B)], list(range(B)))
+        sc = ses.cache
+        tensors = (sc.d_pos, sc.finish, sc.slot_table, sc.sample_state, ses.st.token)
+        held[name] = (ses, tensors, [t.clone() for t in tensors], list(ses.occ))
+        for _ in range(3):
+            ses._step()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ms, finished = {name: [] for name in held}, dict.fromkeys(held, 0)
+    for rep in range(args.reps):
+        for name, (ses, tensors, keep, occ) in held.items():
+            for t, k in zip(tensors, keep):
+                t.copy_(k)
+            ses.steps, ses.occ = 0, list(occ)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(args.steps):
+                ses._step()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[name].append(e0.elapsed_time(e1) / args.steps)
+            finished[name] = max(finished[name], int((ses.cache.finish[:, 0] >= 0).sum()))
+    for name in ms:
+        emit({"part": "step", "variant": name, "slots": B, "blocks": eng.L, "prompt_rows": S0, "temperature": T, "top_k": K, "top_p": TOP_P,
+              "step_ms_min": min(ms[name]), "step_ms_median": statistics.median(ms[name]), "step_ms_all": ms[name],
+              "steps_per_window": args.steps, "rows_finished": finished[name]})
+    med = {name: statistics.median(v) for name, v in ms.items()}
+    emit({"part": "step_summary", "session_wide_ms": med["session_wide"], "per_row_ms": med["per_row"],
+          "spread_ms": abs(med["session_wide_again"] - med["session_wide"]), "per_row_minus_session_wide_ms": med["per_row"] - med["session_wide"]})
+    write_out()
+
+
 with torch.no_grad():
+    if args.per_request:
+        per_request_mode()
+        sys.exit(0)
     if args.prefix_rows:
         choices_mode() if args.choices else prefix_mode()
         sys.exit(0)
