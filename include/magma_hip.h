@@ -114,7 +114,8 @@ const char* mg_version(void);
  *      (nothing moved).  Choosing over a request stream: added mg_logits_process_slots_f32,
  *      mg_logits_process_constrained_slots_f32 and mg_token_logprobs_slots_f32 (nothing moved, no revision bump: a package that
  *      binds them names the missing symbol when it meets an older library).  Per-request sampling: added mg_sample_rows_f32 and
- *      MG_SAMPLE_ROW_BYTES, in the same way. */
+ *      MG_SAMPLE_ROW_BYTES, in the same way.  Speculative decoding: added mg_attn_decode_chunk_bf16,
+ *      mg_decode_attn_gemv_chunk_bf16 and mg_spec_finish, in the same way. */
 #define MG_ABI_VERSION 27
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
@@ -139,6 +140,8 @@ const char* mg_last_error(void);
  *                                            off[b][s]  (each [0, Smax))
  *   mg_attn_decode_bf16, _fused_bf16,        d_pos[b * pos_stride]  ([0, Smax))         SKIP row b: no append, no attention, out row untouched
  *   mg_decode_attn_gemv_bf16                                                            (the co-launched GEMV is unaffected)
+ *   mg_attn_decode_chunk_bf16,               d_pos[b * pos_stride] + t  ([0, Smax))     per row t < T of the chunk, the sum formed unsigned: SKIP row
+ *   mg_decode_attn_gemv_chunk_bf16                                                      b * T + t alone (no append, no attention, out row untouched)
  *   mg_attn_decode_fused_shared_bf16,        d_pos[b]  ([n_prefix, n_prefix + Smax))    below: CLAMP to n_prefix (own index 0, an idle slot);
  *   mg_decode_attn_gemv_shared_bf16                                                     at or above n_prefix + Smax: SKIP row b
  *   mg_attn_decode_prefix_bf16               d_pos[b]  (as above)                       below: CLAMP to n_prefix.  Above: NOT guarded -- this launch
@@ -153,6 +156,10 @@ const char* mg_last_error(void);
  *   mg_slots_admit_bf16, _at_bf16,           state[0] (any value)                       ring column (state[0] - 1) mod cols
  *   mg_slots_admit_shared_bf16               first_token[j] (any value)                 stored and compared, never an index.  Rows, slots, lengths,
  *                                                                                       offsets: host arguments, validated before the launch
+ *   mg_spec_finish                           count[b]  ([0, history_cols])              SKIP row b whole: nothing of it is written, it holds no loop open
+ *                                            n_draft[b]  ([0, min(T, token_stride) - 1])  CLAMP; lookup_len[b] CLAMP into [0, lookup_cols]
+ *                                            ids, tokens, lookup entries (any value)     compared and stored, never an index; a draft id outside
+ *                                                                                       [0, vocab) ends the draft in front of it
  *   mg_logits_process_f32, _constrained_f32  state[0]  ([0, history_cols])              CLAMP: the number of history columns read
  *                                            history tokens, eos / suppress ids ([0,V)) SKIP that id (no penalty, no ban)
  *   mg_logits_process_constrained_f32        roots[r], path[r][i], table entries        a node outside [0, n_nodes): the cache entry is not used /
@@ -509,6 +516,31 @@ int mg_attn_decode_fused_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_bf16* vcac
                               int32_t H, int32_t Smax, const int32_t* d_pos, int32_t rot_dim,
                               const float* sin_t, const float* cos_t, int32_t pos_stride, void* stream);
 
+/* Chunk decode attention (DESIGN.md "Speculative decoding"): mg_attn_decode_fused_bf16 for T consecutive positions of every
+ * sequence, 2 <= T <= 8, in one launch that reads the sequence's K/V once.  qkv is [B*T, 3*H*256], sequence-major: row b*T + t is the
+ * t-th new token of sequence b and sits at position p = pos_b + t, pos_b = d_pos[b * pos_stride]; the caches are [B, H, Smax, 256];
+ * out is [B*T, >= H*256] at row stride ld_out (0 = H*256).  Row t is live iff (unsigned)p < Smax; a dead row appends nothing, attends
+ * over nothing and leaves its out row as it is.  All live rows' q and k are rotated at their own angle rows, k and v appended at
+ * [pos_b, pos_b + T), then query t attends over keys [0, pos_b + t].  Grid B*H workgroups of 256 threads; query t is column t of the
+ * score MFMA's B operand, softmax and PV are formed per query in the single-query kernel's order, so out and both caches have the
+ * BITS of T successive mg_attn_decode_fused_bf16 launches over the same sequences with row t fed at position pos_b + t (finite K/V).
+ * The score area lives in dynamic LDS, T * (Smax * 4 + 4656) bytes: T = 8 at Smax = 2048 takes 100 KB of the 160 KB of a workgroup.
+ * Refused before any launch: what mg_attn_decode_fused_bf16 refuses, T outside [2, 8], B*T > 16, an ld_out that is neither 0 nor a
+ * multiple of 8 >= H*256, a T and Smax whose LDS does not fit (MG_ERR_SHAPE).  (Added without a revision bump, as mg_sample_rows_f32
+ * was: a package that binds it names the missing symbol when it meets an older library.)
+ * mg_decode_attn_gemv_chunk_bf16: mg_decode_attn_gemv_bf16 for such a chunk, ONE launch -- B*H attention workgroups that run the chunk
+ * body above, and the workgroups of one independent GEMV over an M = B*T operand in the instantiation mg_decode_attn_gemv_bf16 picks
+ * for the same descriptor, so the GEMV has that launch's bits.  The grid's LDS block is dynamic, max(the chunk body's, the GEMV's), and
+ * every workgroup gets it; the GEMV workgroups also carry the chunk bodies' register count (DESIGN.md "Speculative decoding" has what
+ * that does to their occupancy).  Every refusal of either part -- mg_attn_decode_chunk_bf16's, the descriptor's, a K of the GEMV that
+ * is no multiple of 128 -- comes before the launch. */
+int mg_attn_decode_chunk_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_bf16* vcache, mg_bf16* out, int64_t ld_out, int32_t B, int32_t T,
+                              int32_t H, int32_t Smax, const int32_t* d_pos, int32_t rot_dim, const float* sin_t, const float* cos_t,
+                              int32_t pos_stride, void* stream);
+int mg_decode_attn_gemv_chunk_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_bf16* vcache, mg_bf16* attn_out, int64_t ld_attn_out, int32_t B,
+                                   int32_t T, int32_t H, int32_t Smax, const int32_t* d_pos, int32_t rot_dim, const float* sin_t,
+                                   const float* cos_t, const mg_skinny_desc* gemv, int32_t pos_stride, void* stream);
+
 /* Decode attention over ONE prefix shared by all rows (ABI 26; DESIGN.md "Shared session prefix").  Every row b <= 16 of the batch has
  * the same n_prefix cached positions in front of its own: they are stored once, kprefix / vprefix [H, S_prefix, 256] (positions
  * [0, n_prefix) are read), and the rows' caches [B, H, Smax, 256] hold their OWN positions only -- absolute position p >= n_prefix of a
@@ -632,6 +664,31 @@ int mg_sample_finish_rows(int64_t* token, int32_t B, int32_t* state, int32_t* d_
                           int64_t ld_history, int32_t history_cols, int32_t* clear, int32_t n_clear, int32_t clear_stride,
                           int32_t pos_stride, const int32_t* table, int32_t n_eos, int32_t n_seq, int64_t pad, int32_t* finish,
                           void* stream);
+
+/* Speculative greedy decoding (DESIGN.md "Speculative decoding"; host statement: magma_amd/sampling.py, speculate_update): the
+ * bookkeeping of a step that fed T tokens per sequence, in ONE enqueue-only, graph-capturable launch of one workgroup, B*T <= 16.
+ *   ids        int64 [B][T]: the tokens the step fed -- ids[b][0] the last emitted token, ids[b][1 .. n_draft[b]] the drafts; rewritten
+ *              for the next step (unused entries repeat ids[b][0]; a finished row holds the pad id table[0])
+ *   token      int64: token[b * token_stride + t] = the argmax of fed row t (token_stride = T), or the prefill's selected token with
+ *              token_stride = 1 and n_draft = 0: the arming call, which records token 0 and makes the first drafts
+ *   history    int64 [B][ld_history], count int32 [B]: the row's emitted tokens and their number
+ *   finish     int32 [B][2] = {count at which the row finished or -1, reason}; table: the stop table (eos ids 0 .. n_eos - 1)
+ *   lookup     int32 [B][ld_lookup], lookup_len int32 [B]: ids searched in front of the history (lookup_cols may be 0)
+ *   stats      int32 [B][3] = {launches in which the row was open, drafts fed, drafts accepted}
+ * Per unfinished row: a = the leading j in [1, n_draft] with ids[b][j] == token[b][j - 1]; the tokens token[b][0 .. a] are emitted, cut
+ * behind the first eos id among them (MG_STOP_EOS | i) and at limit - count (MG_STOP_LEN; history_cols bounds limit); the m emitted
+ * tokens go to history[b][count ..], count += m, d_pos[b] += m (d_pos may be NULL: the arming call feeds nothing).  A row that stays
+ * open gets drafts by transformers' prompt-lookup rule over lookup[b][:lookup_len[b]] ++ history[b][:count]: for n from
+ * min(max_ngram, L - 1) down to 1, the first window from the left that equals the last n tokens and has a continuation inside the
+ * sequence gives at most num_tokens drafts, cut in front of the first eos id (or id outside [0, vocab)); the first n with a match
+ * decides.  A finished row is frozen: n_draft = 0, ids = pad, nothing recorded, its position stays.  state[1] latches the step
+ * (state[0]) at which no row is open; state[0] += 1.  Refused: null or misaligned pointers, T outside [2, 8], B*T > 16, token_stride
+ * other than 1 or T, num_tokens outside [1, T - 1], max_ngram outside [1, 16], n_eos outside [1, 8], bad history / lookup geometry. */
+int mg_spec_finish(int64_t* ids, int32_t B, int32_t T, int32_t* n_draft, const int64_t* token, int32_t token_stride, int64_t* history,
+                   int64_t ld_history, int32_t history_cols, int32_t* count, int32_t* finish, const int32_t* table, int32_t n_eos,
+                   int32_t limit, int32_t* d_pos, const int32_t* lookup, int64_t ld_lookup, int32_t lookup_cols,
+                   const int32_t* lookup_len, int32_t* stats, int32_t* state, int32_t num_tokens, int32_t max_ngram, int32_t vocab,
+                   void* stream);
 
 /* Request streams (ABI 24; DESIGN.md "Request streams"; host statement: magma_amd/sampling.py, slot_update): the bookkeeping of a
  * slot session, in which the row of a finished request is handed to the next request while the other rows keep generating.

@@ -467,6 +467,13 @@ __global__ __launch_bounds__(256) void attn_decode_shared_kernel(const AttnDecod
   attn_decode_body<true, true>(P, blockIdx.x, lds, S);
 }
 
+// NQ consecutive positions of one sequence per workgroup (attn_decode_chunk_body); the LDS is dynamic, sized by the launch's Smax.
+template <int NQ>
+__global__ __launch_bounds__(256) void attn_decode_chunk_kernel(const AttnDecodeParams P) {
+  extern __shared__ __attribute__((aligned(16))) char chunk_lds[];
+  attn_decode_chunk_body<NQ>(P, blockIdx.x, chunk_lds);
+}
+
 __global__ __launch_bounds__(256) void attn_decode_prefix_kernel(const AttnPrefixParams P) {
   __shared__ __attribute__((aligned(16))) char lds[ATTN_PREFIX_LDS];
   attn_prefix_body(P, blockIdx.x, blockIdx.y, lds);
@@ -606,6 +613,30 @@ extern "C" int mg_attn_decode_fused_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg
   hipLaunchKernelGGL(attn_decode_kernel<true>, dim3(B * H), dim3(256), 0, (hipStream_t)stream, P);
   MG_CHECK_LAUNCH();
   return MG_OK;
+}
+
+static int attn_decode_chunk_launch(const char* who, const AttnDecodeParams& P, int32_t B, int32_t T, void* stream) {
+  const int lds = (int)attn_chunk_lds_bytes(T, P.Smax);
+#define MG_CHUNK(T_)                                                                                                        \
+  case T_:                                                                                                                  \
+    if (int rc = mg_allow_dynamic_lds((const void*)attn_decode_chunk_kernel<T_>, DEC_CHUNK_MAX_LDS, who)) return rc;        \
+    hipLaunchKernelGGL(attn_decode_chunk_kernel<T_>, dim3(B * P.H), dim3(256), lds, (hipStream_t)stream, P);                \
+    break;
+  switch (T) { MG_CHUNK(2) MG_CHUNK(3) MG_CHUNK(4) MG_CHUNK(5) MG_CHUNK(6) MG_CHUNK(7) MG_CHUNK(8) }
+#undef MG_CHUNK
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+// mg_attn_decode_fused_bf16 for T consecutive positions of every sequence in one launch (attn_decode_chunk_body): qkv [B*T, 3*H*256]
+// sequence-major, caches [B, H, Smax, 256], out [B*T, ld_out].  Same bits as T successive single-query launches.
+extern "C" int mg_attn_decode_chunk_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_bf16* vcache, mg_bf16* out, int64_t ld_out, int32_t B,
+                                         int32_t T, int32_t H, int32_t Smax, const int32_t* d_pos, int32_t rot_dim, const float* sin_t,
+                                         const float* cos_t, int32_t pos_stride, void* stream) {
+  const char* who = "mg_attn_decode_chunk_bf16";
+  AttnDecodeParams P{qkv, kcache, vcache, out, H, Smax, d_pos, rot_dim, sin_t, cos_t, ld_out, pos_stride};
+  if (int rc = attn_chunk_check(who, P, B, T)) return rc;
+  return attn_decode_chunk_launch(who, P, B, T, stream);
 }
 
 // Shared session prefix, kernel 1: the partial attention of all B rows over every chunk of the one prefix (attn_prefix_body).

@@ -316,6 +316,158 @@ MG_DEV void attn_decode_body(const AttnDecodeParams& P, int bh, char* lds, const
   out[out_off + tid] = f2bf(v);
 }
 
+// ---------------------------------------------------------------------------
+// Chunk decode attention (DESIGN.md "Speculative decoding"): the fused body for NQ consecutive positions of one sequence, the NQ
+// rows b * NQ + t of the fused qkv [B * NQ, 3*H*256].  Row t sits at position p = pos_b + t and is live iff (unsigned)p < Smax (the
+// guard of the single-query body, per row: a dead row appends nothing, attends over nothing and leaves its out row as it is).
+// All live rows' q and k are rotated at their own angle rows and k, v appended at their positions; after the barrier query t attends
+// over keys [0, pos_b + t].  Query t is B-operand column t of the score MFMA, so one set of K fragment loads per 16 keys scores
+// every query (lanes li < NQ keep their column); softmax and PV are the single-query body's, per query and in its order, every V
+// load shared by the NQ queries -- a key beyond a query's own context enters its sum with weight exactly 0.f.  An element of the
+// MFMA result depends on its own A row and B column alone, the statistics are reduced per query as there, and acc + 0.f * v = acc
+// for a finite v: out and both caches have the bits of NQ successive single-query launches with row t fed at position pos_b + t.
+// LDS (dynamic, sized by the launch's Smax): q [NQ][DEC_CHUNK_QLD] bf16, statistics [NQ][8], scores [NQ][Smax rounded up to 4]
+// fp32, the four waves' PV sums [4][NQ][256] fp32 (last, so that the PV loop's look-ahead past a score row stays inside the block).
+// ---------------------------------------------------------------------------
+constexpr int DEC_CHUNK_MAX_Q = 8;
+constexpr int DEC_CHUNK_QLD = 256 + 8;           // LDS row stride of q in bf16 (528 B: the rows start in different banks)
+constexpr int DEC_CHUNK_MAX_LDS = 160 * 1024;    // LDS of one workgroup on gfx950
+
+static inline int64_t attn_chunk_lds_bytes(int nq, int Smax) {
+  return (int64_t)nq * (DEC_CHUNK_QLD * 2 + 8 * 4 + (int64_t)((Smax + 3) & ~3) * 4 + 4 * 256 * 4);
+}
+
+template <int NQ>
+MG_DEV void attn_decode_chunk_body(const AttnDecodeParams& P, int bh, char* lds) {
+  constexpr int DH = 256;
+  static_assert(NQ >= 2 && NQ <= DEC_CHUNK_MAX_Q, "2 to 8 queries per sequence");
+  const mg_bf16* __restrict__ qin = P.qin;
+  mg_bf16* __restrict__ out = P.out;
+  const int H = P.H, Smax = P.Smax, rot_dim = P.rot_dim;
+  const int scld = (Smax + 3) & ~3;
+  mg_bf16* qs = (mg_bf16*)lds;                                   // [NQ][DEC_CHUNK_QLD] (first: 16-byte aligned)
+  float* wred = (float*)(lds + NQ * DEC_CHUNK_QLD * 2);          // [NQ][8]
+  float* sc = wred + NQ * 8;                                     // [NQ][scld]
+  float* red = sc + NQ * scld;                                   // [4][NQ][DH]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 15, lq = lane >> 4;
+  const int b = bh / H, h = bh - b * H;
+  const int64_t ld_out = P.ld_out ? P.ld_out : (int64_t)H * DH;
+  const unsigned upos = (unsigned)P.d_pos[b * P.pos_stride];
+  // The per-row guard: the sum is unsigned (no signed wrap in front of the compare), and nothing is formed from a position that
+  // fails it.  ctx_of(t) = the keys query t attends over, 0 for a dead row; a live row's position is upos + t < Smax.
+  auto ctx_of = [&](int t) -> int { const unsigned p = upos + (unsigned)t; return p < (unsigned)Smax ? (int)p + 1 : 0; };
+  int ctx_max = 0;
+#pragma unroll
+  for (int t = 0; t < NQ; ++t) ctx_max = max(ctx_max, ctx_of(t));
+  if (ctx_max == 0) return;                                      // uniform over the workgroup, in front of the first barrier
+  mg_bf16* kb = P.kcache + (int64_t)bh * Smax * DH;
+  mg_bf16* vb = P.vcache + (int64_t)bh * Smax * DH;
+  {
+    // item = (row t, which of q / k / v, 8 dims): 96 per row as in the single-query body
+    const int dmodel = H * DH;
+    for (int i = tid; i < NQ * 96; i += 256) {
+      const int t = i / 96, r = i - t * 96, which = r >> 5, d0 = (r & 31) * 8;
+      const int ctx = ctx_of(t);
+      if (ctx == 0) {                                            // a dead row: its MFMA column is zero and nothing of it is read
+        if (which == 0) *(u32x4*)(qs + t * DEC_CHUNK_QLD + d0) = (u32x4){0u, 0u, 0u, 0u};
+        continue;
+      }
+      const int p = ctx - 1;
+      u32x4 v = *(const u32x4*)(qin + (int64_t)(b * NQ + t) * 3 * dmodel + which * dmodel + h * DH + d0);
+      if (which < 2 && d0 < rot_dim) v = rotary8_at(v, P.sin_t, P.cos_t, p, rot_dim, d0);
+      if (which == 0) *(u32x4*)(qs + t * DEC_CHUNK_QLD + d0) = v;
+      else if (which == 1) *(u32x4*)(kb + (int64_t)p * DH + d0) = v;
+      else *(u32x4*)(vb + (int64_t)p * DH + d0) = v;
+    }
+    __threadfence_block();
+  }
+  __syncthreads();
+  // ---- phase 1: scores on the MFMA, 16 keys per wave step; column li = query li ----
+  const int my_ctx = li < NQ ? ctx_of(li) : 0;
+  bf16x8 qf[8];
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks) qf[ks] = *(const bf16x8*)(qs + min(li, NQ - 1) * DEC_CHUNK_QLD + ks * 32 + lq * 8);
+  for (int t0 = wave * 16; t0 < ctx_max; t0 += 64) {
+    const int key = min(t0 + li, ctx_max - 1);
+    const mg_bf16* kp = kb + (int64_t)key * DH + lq * 8;
+    bf16x8 kf[8];
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) kf[ks] = *(const bf16x8*)(kp + ks * 32);
+    f32x4 s = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[ks], qf[ks], s, 0, 0, 0);
+    if (li < NQ) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int t = t0 + lq * 4 + r;
+        if (t < my_ctx) sc[li * scld + t] = s[r] * 0.0625f;
+      }
+    }
+  }
+  __syncthreads();
+  // ---- phase 2: softmax statistics, per query ----
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int ctx = ctx_of(q);
+    float mx = -1e30f;
+    for (int t = tid; t < ctx; t += 256) mx = fmaxf(mx, sc[q * scld + t]);
+    mx = wave_max(mx);
+    if (lane == 0) wred[q * 8 + wave] = mx;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int ctx = ctx_of(q);
+    const float mx = fmaxf(fmaxf(wred[q * 8 + 0], wred[q * 8 + 1]), fmaxf(wred[q * 8 + 2], wred[q * 8 + 3]));
+    float sm = 0.f;
+    for (int t = tid; t < ctx; t += 256) {
+      const float e = __expf(sc[q * scld + t] - mx);
+      sc[q * scld + t] = e;
+      sm += e;
+    }
+    sm = wave_sum(sm);
+    if (lane == 0) wred[q * 8 + 4 + wave] = sm;
+  }
+  __syncthreads();
+  // ---- phase 3: o_q = sum_t p_q[t] V[t]; wave w takes keys == w mod 4, 8 keys in flight, every V load used by all NQ queries ----
+  float acc[NQ][4];
+  int ctxs[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) { acc[q][0] = acc[q][1] = acc[q][2] = acc[q][3] = 0.f; ctxs[q] = ctx_of(q); }
+  for (int t0 = wave; t0 < ctx_max; t0 += 32) {
+    u32x2 w[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int t = min(t0 + u * 4, ctx_max - 1);
+      w[u] = *(const u32x2*)(vb + (int64_t)t * DH + lane * 4);
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int t = t0 + u * 4;
+      const float v0 = bflo(w[u][0]), v1 = bfhi(w[u][0]), v2 = bflo(w[u][1]), v3 = bfhi(w[u][1]);
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const float pt = t < ctxs[q] ? sc[q * scld + t] : 0.f;
+        acc[q][0] += pt * v0; acc[q][1] += pt * v1;
+        acc[q][2] += pt * v2; acc[q][3] += pt * v3;
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < NQ; ++q)
+    *(f32x4*)(red + (wave * NQ + q) * DH + lane * 4) = (f32x4){acc[q][0], acc[q][1], acc[q][2], acc[q][3]};
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    if (ctxs[q] == 0) continue;                                  // a dead row's out row stays as it is
+    const float inv = 1.0f / (wred[q * 8 + 4] + wred[q * 8 + 5] + wred[q * 8 + 6] + wred[q * 8 + 7]);
+    const float v = (red[q * DH + tid] + red[(NQ + q) * DH + tid] + red[(2 * NQ + q) * DH + tid] + red[(3 * NQ + q) * DH + tid]) * inv;
+    out[(int64_t)(b * NQ + q) * ld_out + (int64_t)h * DH + tid] = f2bf(v);
+  }
+}
+
 // The refusals every decode-attention entry point has in common, stand-alone or co-launched (ap.rot_dim = 0 where the entry point
 // has no rotary).  shared: pos_stride is left to attn_shared_check, which answers a wrong one in its own words.  also_null: a
 // further pointer the entry point needs is missing.
@@ -327,6 +479,18 @@ static inline int attn_decode_check(const char* who, const AttnDecodeParams& ap,
     MG_FAIL(MG_ERR_SHAPE, "%s: null pointer", who);
   if (!MG_ALIGNED16(ap.qin) || !MG_ALIGNED16(ap.kcache) || !MG_ALIGNED16(ap.vcache) || !MG_ALIGNED16(ap.out))
     MG_FAIL(MG_ERR_ALIGN, "%s: pointers must be 16-byte aligned", who);
+  return MG_OK;
+}
+
+// The refusals of the chunk entry points, before any launch: attn_decode_check's in its words, then the chunk's own.
+static inline int attn_chunk_check(const char* who, const AttnDecodeParams& ap, int32_t B, int32_t T) {
+  if (int rc = attn_decode_check(who, ap, B, false)) return rc;
+  if (T < 2 || T > DEC_CHUNK_MAX_Q) MG_FAIL(MG_ERR_SHAPE, "%s: need 2 <= T <= %d queries per sequence, got %d", who, DEC_CHUNK_MAX_Q, T);
+  if ((int64_t)B * T > 16) MG_FAIL(MG_ERR_SHAPE, "%s: a chunk step serves at most 16 rows, got B * T = %d * %d", who, B, T);
+  if (ap.ld_out != 0 && (ap.ld_out < (int64_t)ap.H * 256 || (ap.ld_out & 7))) MG_FAIL(MG_ERR_SHAPE, "%s: ld_out must be 0 or a multiple of 8 >= H*256", who);
+  if (attn_chunk_lds_bytes(T, ap.Smax) > DEC_CHUNK_MAX_LDS)
+    MG_FAIL(MG_ERR_SHAPE, "%s: T = %d queries over Smax = %d need %lld bytes of LDS, a workgroup has %d", who, T, ap.Smax,
+            (long long)attn_chunk_lds_bytes(T, ap.Smax), DEC_CHUNK_MAX_LDS);
   return MG_OK;
 }
 

@@ -1245,6 +1245,26 @@ __global__ __launch_bounds__(256) void decode_attn_shared_gemv_kernel(const Attn
   else skinny_body<4, KC, 1, WT, false>(sp, blockIdx.x - n_attn, lds);
 }
 
+// The same co-launch with the attention workgroups running the chunk body (mg_decode_attn_gemv_chunk_bf16): nq consecutive
+// positions per sequence.  The LDS block is dynamic -- the chunk body's score area is sized by the launch's Smax -- and every
+// workgroup of the grid gets it, the GEMV workgroups too, which also carry the chunk body's register count: both cost the GEMV
+// part occupancy (DESIGN.md "Speculative decoding").  The GEMV body and its instantiation are the plain co-launch's.
+template <int KC, int WT = WT_BF16, bool PIPE = false>
+__global__ __launch_bounds__(256) void decode_attn_chunk_gemv_kernel(const AttnDecodeParams ap, int nq, int n_attn, const SkinnyParams sp) {
+  extern __shared__ __attribute__((aligned(16))) char dlds[];
+  if ((int)blockIdx.x < n_attn) {
+    switch (nq) {
+      case 2: attn_decode_chunk_body<2>(ap, blockIdx.x, dlds); break;
+      case 3: attn_decode_chunk_body<3>(ap, blockIdx.x, dlds); break;
+      case 4: attn_decode_chunk_body<4>(ap, blockIdx.x, dlds); break;
+      case 5: attn_decode_chunk_body<5>(ap, blockIdx.x, dlds); break;
+      case 6: attn_decode_chunk_body<6>(ap, blockIdx.x, dlds); break;
+      case 7: attn_decode_chunk_body<7>(ap, blockIdx.x, dlds); break;
+      case 8: attn_decode_chunk_body<8>(ap, blockIdx.x, dlds); break;
+    }
+  } else skinny_body<4, KC, 1, WT, PIPE>(sp, blockIdx.x - n_attn, dlds);
+}
+
 constexpr int MG_DECODE_PIPE_DEFAULT = 0;
 }  // namespace
 
@@ -1394,10 +1414,15 @@ namespace {
 // so the shared-prefix launch streams the same GEMV variant as the unshared one for the same operands, and its GEMV has the same
 // bits.  MAGMA_DECODE_PIPE (0 = burst-and-drain, 16 / 8 = double-buffered bursts of that many k-steps, bf16 weights) exists
 // unshared only.
-template <bool SHARED>
+// MODE: DAG_PLAIN, DAG_SHARED (the shared-prefix body) or DAG_CHUNK (``chunk`` = T consecutive positions per sequence, the chunk
+// body, dynamic LDS).  Every refusal, the ladder's last one included, comes before the one launch.
+enum { DAG_PLAIN = 0, DAG_SHARED = 1, DAG_CHUNK = 2 };
+template <int MODE>
 int decode_attn_gemv_launch(const char* who, const char* who_gemv, const AttnDecodeParams& ap, int32_t B, const mg_skinny_desc* gemv,
-                            int32_t n_prefix, const float* part, void* stream) {
-  if (int rc = attn_decode_check(who, ap, B, SHARED, SHARED && !gemv)) return rc;
+                            int32_t n_prefix, const float* part, void* stream, int32_t chunk = 0) {
+  constexpr bool SHARED = MODE == DAG_SHARED;
+  if constexpr (MODE == DAG_CHUNK) { if (int rc = attn_chunk_check(who, ap, B, chunk)) return rc; }
+  else if (int rc = attn_decode_check(who, ap, B, SHARED, SHARED && !gemv)) return rc;
   SkinnyParams sp;
   if (int rc = fill_skinny(gemv, sp, who_gemv)) return rc;
   if (ap.ld_out != 0 && (ap.ld_out < (int64_t)ap.H * 256 || (ap.ld_out & 7))) MG_FAIL(MG_ERR_SHAPE, "%s: ld_attn_out must be 0 or a multiple of 8 >= H*256", who);
@@ -1410,10 +1435,14 @@ int decode_attn_gemv_launch(const char* who, const char* who_gemv, const AttnDec
   if (sp.w_scale && sp.ksteps % 64 != 0) MG_FAIL(MG_ERR_UNSUPPORTED, "%s: fp8 weights need K %% 2048 == 0 here", who);
   int pipe = 0;
   if constexpr (!SHARED) { const char* e = getenv("MAGMA_DECODE_PIPE"); pipe = e ? atoi(e) : MG_DECODE_PIPE_DEFAULT; }   // read per call (graph capture)
+  [[maybe_unused]] const int chunk_lds = MODE == DAG_CHUNK ? max((int)attn_chunk_lds_bytes(chunk, ap.Smax), skinny_lds_bytes<4, 1>()) : 0;
   // (a PIPE row instantiates nothing in the shared launcher, where pipe == 0 never reaches it)
 #define MG_DAG(K_, W_, P_)                                                                                                                \
   do {                                                                                                                                    \
-    if constexpr (!SHARED) hipLaunchKernelGGL((decode_attn_gemv_kernel<K_, W_, P_>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp);         \
+    if constexpr (MODE == DAG_CHUNK) {                                                                                                    \
+      if (int rc = mg_allow_dynamic_lds((const void*)decode_attn_chunk_gemv_kernel<K_, W_, P_>, DEC_CHUNK_MAX_LDS, who)) return rc;       \
+      hipLaunchKernelGGL((decode_attn_chunk_gemv_kernel<K_, W_, P_>), dim3(grid), dim3(256), chunk_lds, s, ap, chunk, n_attn, sp);        \
+    } else if constexpr (!SHARED) hipLaunchKernelGGL((decode_attn_gemv_kernel<K_, W_, P_>), dim3(grid), dim3(256), 0, s, ap, n_attn, sp); \
     else if constexpr (!(P_)) hipLaunchKernelGGL((decode_attn_shared_gemv_kernel<K_, W_>), dim3(grid), dim3(256), 0, s, ap, sh, n_attn, sp); \
   } while (0)
   if (sp.w_mx4) {   // MXFP4: one n-tile per workgroup (fc_out has 256 tiles: see the measured table in mg_gemm_skinny_bf16)
@@ -1443,7 +1472,18 @@ extern "C" int mg_decode_attn_gemv_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_
                                         const float* sin_t, const float* cos_t, const mg_skinny_desc* gemv,
                                         int32_t pos_stride, void* stream) {
   const AttnDecodeParams ap{qkv, kcache, vcache, attn_out, H, Smax, d_pos, rot_dim, sin_t, cos_t, ld_attn_out, pos_stride};
-  return decode_attn_gemv_launch<false>("mg_decode_attn_gemv_bf16", "mg_decode_attn_gemv_bf16(gemv)", ap, B, gemv, 0, nullptr, stream);
+  return decode_attn_gemv_launch<DAG_PLAIN>("mg_decode_attn_gemv_bf16", "mg_decode_attn_gemv_bf16(gemv)", ap, B, gemv, 0, nullptr, stream);
+}
+
+// mg_decode_attn_gemv_bf16 for T consecutive positions per sequence (mg_attn_decode_chunk_bf16): qkv [B*T, 3*H*256], the attention
+// workgroups run the chunk body, the GEMV over an M = B*T operand is the instantiation the plain co-launch picks for it.
+extern "C" int mg_decode_attn_gemv_chunk_bf16(const mg_bf16* qkv, mg_bf16* kcache, mg_bf16* vcache, mg_bf16* attn_out, int64_t ld_attn_out,
+                                              int32_t B, int32_t T, int32_t H, int32_t Smax, const int32_t* d_pos, int32_t rot_dim,
+                                              const float* sin_t, const float* cos_t, const mg_skinny_desc* gemv, int32_t pos_stride,
+                                              void* stream) {
+  const AttnDecodeParams ap{qkv, kcache, vcache, attn_out, H, Smax, d_pos, rot_dim, sin_t, cos_t, ld_attn_out, pos_stride};
+  return decode_attn_gemv_launch<DAG_CHUNK>("mg_decode_attn_gemv_chunk_bf16", "mg_decode_attn_gemv_chunk_bf16(gemv)", ap, B, gemv, 0, nullptr,
+                                            stream, T);
 }
 
 // mg_decode_attn_gemv_bf16 with the attention workgroups in the shared-prefix mode (mg_attn_decode_fused_shared_bf16).
@@ -1452,6 +1492,6 @@ extern "C" int mg_decode_attn_gemv_shared_bf16(const mg_bf16* qkv, mg_bf16* kcac
                                                int32_t rot_dim, const float* sin_t, const float* cos_t, const mg_skinny_desc* gemv,
                                                int32_t pos_stride, int32_t n_prefix, const float* part, void* stream) {
   const AttnDecodeParams ap{qkv, kcache, vcache, attn_out, H, Smax, d_pos, rot_dim, sin_t, cos_t, ld_attn_out, pos_stride};
-  return decode_attn_gemv_launch<true>("mg_decode_attn_gemv_shared_bf16", "mg_decode_attn_gemv_shared_bf16(gemv)", ap, B, gemv, n_prefix,
+  return decode_attn_gemv_launch<DAG_SHARED>("mg_decode_attn_gemv_shared_bf16", "mg_decode_attn_gemv_shared_bf16(gemv)", ap, B, gemv, n_prefix,
                                        part, stream);
 }

@@ -583,6 +583,124 @@ __global__ void sample_finish_slots_kernel(int64_t* __restrict__ tok, int B, int
   state[0] = step + 1;
 }
 
+// Speculative greedy decoding (DESIGN.md "Speculative decoding"; host statement: sampling.py speculate_update): the bookkeeping of
+// a step that fed T tokens per sequence -- ids[b][0], the last emitted token, and n_draft[b] <= T - 1 guessed continuations -- and
+// holds the argmax of every fed row in token[b * token_stride + t].  One workgroup, three phases with a barrier between them:
+//   A  thread b, row b: accept the longest prefix of drafts the model agrees with, record the emitted tokens, test them;
+//   B  all threads: prompt lookup over the two-segment sequence lookup[b][:len] ++ history[b][:count] of every open row.  For the
+//      position c behind a window, m(c) = how many tokens in front of c equal the sequence's last tokens (at most max_ngram, c and
+//      L - 1); a window of n tokens in front of c matches iff m(c) >= n, so ONE pass leaves best[b][n] = the first c with m(c) >= n;
+//   C  thread b: the largest n with a match gives the drafts; ids and n_draft for the next step; thread 0 latches and counts.
+// Device-resident values never form an address unchecked: n_draft counts as clamped into [0, min(T, token_stride) - 1], lookup_len
+// into [0, lookup_cols]; a row whose count lies outside [0, history_cols] is skipped whole (nothing of it written, it does not hold
+// the loop open); a draft id outside [0, vocab) ends the draft in front of it.
+struct SpecArgs {
+  int64_t* ids; int B, T; int32_t* n_draft; const int64_t* token; int token_stride;
+  int64_t* history; int64_t ld_hist; int hist_cols; int32_t* count; int32_t* finish;
+  const int32_t* table; int n_eos, limit; int32_t* d_pos;
+  const int32_t* lookup; int64_t ld_lookup; int lookup_cols; const int32_t* lookup_len;
+  int32_t* stats; int32_t* state; int num_tokens, max_ngram, vocab;
+};
+constexpr int SPEC_MAX_ROWS = 16, SPEC_MAX_NGRAM = 16;
+
+__global__ __launch_bounds__(256) void spec_finish_kernel(const SpecArgs a) {
+  __shared__ int s_step, s_open;
+  __shared__ int s_cnt[SPEC_MAX_ROWS], s_llen[SPEC_MAX_ROWS];                 // an open row's count after this step (-1: no search)
+  __shared__ int s_best[SPEC_MAX_ROWS][SPEC_MAX_NGRAM + 1];
+  const int tid = threadIdx.x, T = a.T;
+  if (tid == 0) { s_step = a.state[0]; s_open = 0; }                         // read once, before thread 0 bumps it
+  for (int i = tid; i < SPEC_MAX_ROWS * (SPEC_MAX_NGRAM + 1); i += 256) (&s_best[0][0])[i] = 0x7fffffff;
+  if (tid < SPEC_MAX_ROWS) { s_cnt[tid] = -1; s_llen[tid] = 0; }
+  __syncthreads();
+  const int64_t pad = (int64_t)a.table[0];
+  // ---- A: accept, record, test ----
+  if (tid < a.B) {
+    const int b = tid;
+    int64_t* idr = a.ids + (int64_t)b * T;
+    int32_t* f = a.finish + 2 * (int64_t)b;
+    const int c = a.count[b];
+    if (f[0] >= 0) {                                                          // frozen: padded, its position stays
+      a.n_draft[b] = 0;
+      for (int t = 0; t < T; ++t) idr[t] = pad;
+    } else if (c >= 0 && c <= a.hist_cols) {
+      int64_t* h = a.history + (int64_t)b * a.ld_hist;
+      const int64_t* tk = a.token + (int64_t)b * a.token_stride;
+      const int nd = max(0, min(a.n_draft[b], min(T, a.token_stride) - 1));
+      int acc = 0;
+      while (acc < nd && idr[acc + 1] == tk[acc]) ++acc;
+      const int lim = min(a.limit, a.hist_cols);
+      int m = 0, code = 0;
+      for (int j = 0; j <= acc && c + j < lim && !code; ++j) {
+        const int64_t t = tk[j];
+        h[c + j] = t;
+        m = j + 1;
+        for (int e = 0; e < a.n_eos && !code; ++e)
+          if (t == (int64_t)a.table[e]) code = MG_STOP_EOS | e;
+      }
+      if (!code && c + m >= lim) code = MG_STOP_LEN;
+      a.count[b] = c + m;
+      if (a.d_pos) a.d_pos[b] += m;
+      int32_t* st = a.stats + 3 * (int64_t)b;
+      st[0] += 1; st[1] += nd; st[2] += acc;
+      if (code) {
+        f[0] = c + m; f[1] = code;
+        a.n_draft[b] = 0;
+        for (int t = 0; t < T; ++t) idr[t] = pad;
+      } else {
+        s_cnt[b] = c + m;
+        s_llen[b] = max(0, min(a.lookup_len[b], a.lookup_cols));
+      }
+    }
+  }
+  __syncthreads();
+  // ---- B: first match of every n-gram size, all open rows ----
+  for (int b = 0; b < a.B; ++b) {
+    const int cnt = s_cnt[b];
+    if (cnt < 0) continue;
+    const int llen = s_llen[b], L = llen + cnt, nmax = min(a.max_ngram, L - 1);
+    const int32_t* lk = a.lookup + (int64_t)b * a.ld_lookup;
+    const int64_t* h = a.history + (int64_t)b * a.ld_hist;
+    auto seq = [&](int i) -> int64_t { return i < llen ? (int64_t)lk[i] : h[i - llen]; };
+    for (int c = 1 + tid; c < L; c += 256) {
+      int m = 0;
+      while (m < nmax && m < c && seq(c - 1 - m) == seq(L - 1 - m)) ++m;
+      for (int n = 1; n <= m; ++n) atomicMin(&s_best[b][n], c);
+    }
+  }
+  __syncthreads();
+  // ---- C: the drafts of the next step ----
+  if (tid < a.B && s_cnt[tid] >= 0) {
+    const int b = tid, cnt = s_cnt[b], llen = s_llen[b], L = llen + cnt;
+    int64_t* idr = a.ids + (int64_t)b * T;
+    const int32_t* lk = a.lookup + (int64_t)b * a.ld_lookup;
+    const int64_t* h = a.history + (int64_t)b * a.ld_hist;
+    auto seq = [&](int i) -> int64_t { return i < llen ? (int64_t)lk[i] : h[i - llen]; };
+    const int64_t last = h[cnt - 1];                                           // cnt >= 1: an open row has just emitted a token
+    idr[0] = last;
+    int nd = 0;
+    for (int n = min(a.max_ngram, L - 1); n >= 1; --n) {
+      const int c = s_best[b][n];
+      if (c == 0x7fffffff) continue;
+      const int want = min(min(a.num_tokens, T - 1), L - c);
+      for (; nd < want; ++nd) {
+        const int64_t t = seq(c + nd);
+        bool stop = t < 0 || t >= (int64_t)a.vocab;
+        for (int e = 0; e < a.n_eos; ++e) stop = stop || t == (int64_t)a.table[e];
+        if (stop) break;
+        idr[1 + nd] = t;
+      }
+      break;                                                                  // the first size with a match decides, as the host rule has it
+    }
+    for (int t = 1 + nd; t < T; ++t) idr[t] = last;
+    a.n_draft[b] = nd;
+    atomicOr(&s_open, 1);
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  if (!s_open && a.state[1] < 0) a.state[1] = s_step;
+  a.state[0] = s_step + 1;
+}
+
 // Admission of a slot session: n staged requests installed in one launch.  Block (h, j, l) copies K and V positions
 // [pos0, pos0 + len_j) of layer l, head h from staging row src_row[j] to the same positions of live row dst_slot[j] -- len_j * 512
 // contiguous bytes each, as 16-byte vectors, all offsets 64-bit --; thread 0 of block (0, j, 0) installs request j's bookkeeping
@@ -733,6 +851,34 @@ extern "C" int mg_sample_finish_slots(int64_t* token, int32_t B, int32_t* state,
   hipLaunchKernelGGL(sample_finish_slots_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, token, B, state, d_pos, delta, history,
                      ld_history, history_cols, clear, clear ? n_clear : 0, clear_stride > 0 ? clear_stride : 1, table, n_eos, n_seq, pad,
                      finish, slot);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_spec_finish(int64_t* ids, int32_t B, int32_t T, int32_t* n_draft, const int64_t* token, int32_t token_stride,
+                              int64_t* history, int64_t ld_history, int32_t history_cols, int32_t* count, int32_t* finish,
+                              const int32_t* table, int32_t n_eos, int32_t limit, int32_t* d_pos, const int32_t* lookup,
+                              int64_t ld_lookup, int32_t lookup_cols, const int32_t* lookup_len, int32_t* stats, int32_t* state,
+                              int32_t num_tokens, int32_t max_ngram, int32_t vocab, void* stream) {
+  const char* who = "mg_spec_finish";
+  if (!ids || !n_draft || !token || !history || !count || !finish || !table || !lookup_len || !stats || !state || (lookup_cols > 0 && !lookup))
+    MG_FAIL(MG_ERR_SHAPE, "%s: null pointer", who);
+  if (B < 1 || B > SPEC_MAX_ROWS || T < 2 || T > 8 || B * T > 16) MG_FAIL(MG_ERR_SHAPE, "%s: need 2 <= T <= 8 and B * T <= 16, got B = %d, T = %d", who, B, T);
+  if (token_stride != 1 && token_stride != T) MG_FAIL(MG_ERR_SHAPE, "%s: token_stride is T (a step's rows) or 1 (the arming call), got %d", who, token_stride);
+  if (history_cols <= 0 || ld_history < history_cols) MG_FAIL(MG_ERR_SHAPE, "%s: bad history geometry", who);
+  if (lookup_cols < 0 || ld_lookup < lookup_cols) MG_FAIL(MG_ERR_SHAPE, "%s: bad lookup geometry", who);
+  if ((int64_t)lookup_cols + history_cols > 0x7fffff00) MG_FAIL(MG_ERR_SHAPE, "%s: lookup_cols + history_cols must stay below 2^31", who);
+  if (n_eos < 1 || n_eos > MG_STOP_MAX_EOS) MG_FAIL(MG_ERR_SHAPE, "%s: need 1 <= n_eos <= %d, got %d", who, MG_STOP_MAX_EOS, n_eos);
+  if (num_tokens < 1 || num_tokens > T - 1 || max_ngram < 1 || max_ngram > SPEC_MAX_NGRAM)
+    MG_FAIL(MG_ERR_SHAPE, "%s: need 1 <= num_tokens <= T - 1 and 1 <= max_ngram <= %d, got %d / %d", who, SPEC_MAX_NGRAM, num_tokens, max_ngram);
+  if (limit < 0 || vocab < 1) MG_FAIL(MG_ERR_SHAPE, "%s: need limit >= 0 and vocab >= 1", who);
+  if (((uintptr_t)n_draft | (uintptr_t)count | (uintptr_t)finish | (uintptr_t)table | (uintptr_t)d_pos | (uintptr_t)lookup |
+       (uintptr_t)lookup_len | (uintptr_t)stats | (uintptr_t)state) & 3)
+    MG_FAIL(MG_ERR_ALIGN, "%s: int32 buffers must be 4-byte aligned", who);
+  if (((uintptr_t)ids | (uintptr_t)token | (uintptr_t)history) & 7) MG_FAIL(MG_ERR_ALIGN, "%s: token buffers must be 8-byte aligned", who);
+  const SpecArgs a{ids, B, T, n_draft, token, token_stride, history, ld_history, history_cols, count, finish, table, n_eos, limit, d_pos,
+                   lookup, ld_lookup, lookup_cols, lookup_len, stats, state, num_tokens, max_ngram, vocab};
+  hipLaunchKernelGGL(spec_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }

@@ -99,6 +99,10 @@ class KVCache:
         # p - prefix_P, while d_pos and pos stay absolute.  None / 0: every position of a row is its own
         self.prefix_k = self.prefix_v = None
         self.prefix_P = 0
+        # speculative decoding (DESIGN.md "Speculative decoding"): T -> the decode state of the step that runs T rows per sequence
+        # (scratch for B * T rows, its own captured graphs, the loop's bookkeeping buffers), apart from decode_state: a plain call
+        # on this cache replays its own graphs untouched
+        self.spec = {}
 
     def alloc_trie(self, n_ints: int):
         """The constraint's buffers for a table of ``n_ints`` (kept when it fits); steps captured on other buffers are dropped."""
@@ -138,6 +142,9 @@ class KVCache:
         graphs = self.decode_state.graphs if self.decode_state is not None else {}
         for key in [k for k in graphs if which(k)]:
             del graphs[key]
+        for st in self.spec.values():         # (a speculative step's key: its StepKey, the token limit, the lookup width)
+            for key in [k for k in st.graphs if which(k[0])]:
+                del st.graphs[key]
 
     def set_rows(self, pos, pending=None):
         """Row b's next write position becomes pos[b] (host ints; the cache turns ragged), its not-yet-fed token pending[b] (-1 none)."""
@@ -165,6 +172,7 @@ class KVCache:
         self.history = torch.zeros(self.B, Smax, dtype=torch.int64, device=self.k.device)
         self.Smax = Smax
         self.beam = self.contrast = None
+        self.spec = {}
         self._drop_graphs()
         if self.lp is not None:           # one column per history column
             self.alloc_logprobs(self.top_id.shape[2])
@@ -1041,8 +1049,9 @@ class LMEngine(TokenSelection):
         return out[:, : self.V]
 
     # --------------------------------------------------------------- decode
-    def _alloc_decode_state(self, cache: KVCache):
-        B, d, dev = cache.B, self.d, self.device
+    def _alloc_decode_state(self, cache: KVCache, rows: Optional[int] = None):
+        """``rows``: the rows of the step when they are not the cache's (a speculative step: B * T)."""
+        B, d, dev = rows or cache.B, self.d, self.device
         ff = self.layers[0].fc_in.N
         st = _Layer()
         e = lambda *s, dt=BF16: torch.empty(*s, dtype=dt, device=dev)  # noqa: E731
@@ -1062,6 +1071,8 @@ class LMEngine(TokenSelection):
         st.token = torch.zeros(B, dtype=torch.int64, device=dev)
         st.graphs = {}             # StepKey (SelectionPlan.graph_key) -> captured hipGraph
         st.steps = 0
+        st.colaunch = True
+        st.rows, st.T = B, 1       # T > 1: the rows are T consecutive positions of each of the cache's sequences (_ensure_spec_state)
         # shared session prefix: the partials every block's prefix launch leaves for its attention launch (one buffer: the launches
         # of a step are ordered), (prefix_P, buffer) as the attention launches take it
         st.shared = (cache.prefix_P, ops.prefix_part(B, self.H, cache.prefix_P, dev)) if cache.prefix_P else None
@@ -1073,18 +1084,7 @@ class LMEngine(TokenSelection):
         kind planned for it (st.kinds, _ensure_decode_state), the head, token selection under ``plan``.
         ``feed_back``: the input ids are the tokens the previous step selected (st.token, still on the device) -- the
         reference's loop feeds exactly those back (sampling.py:88-90) -- instead of ids copied in from the caller."""
-        B = cache.B
-        ops.embedding(st.token.view(B, 1) if feed_back else st.ids, self.wte, st.xa.view(B, 1, self.d))
-        x, xn = st.xa, st.xb
-        for li, (ly, kind) in enumerate(zip(self.layers, st.kinds)):
-            getattr(self, "_block_" + kind)(cache, st, li, ly, ly.w8 if st.w8 else ly.w4 if st.w4 else ly, x, xn)
-            x, xn = xn, x
-        if B > 16:
-            ops.layernorm(x, self.lnf_g, self.lnf_b, self.eps, out=st.lnf)
-            ops.gemm(st.lnf, self.head, out=st.logits)
-        else:
-            head = self.head_w8 if st.w8 else self.head_w4 if st.w4 else self.head_dec
-            ops.gemm_skinny(x, head, out=st.logits, ln_fold=(head.colsum, self.d, self.eps))
+        x = self._step_logits(cache, st, st.token.view(cache.B, 1) if feed_back else st.ids)
         if plan.is_contrast and plan.select:
             self._select_contrast(x, cache, st, plan)
         elif not plan.select:
@@ -1097,6 +1097,34 @@ class LMEngine(TokenSelection):
         else:
             self.select_token(st.logits[:, : self.V], cache, plan, out=st.token, advance=True)
 
+
+    def _step_logits(self, cache: KVCache, st, ids):
+        """The step up to its logits (st.logits) for the st.rows rows whose token ids are ``ids`` (rows, 1): embedding, the blocks,
+        the head.  Returns the last block's output."""
+        B = st.rows
+        ops.embedding(ids, self.wte, st.xa.view(B, 1, self.d))
+        x, xn = st.xa, st.xb
+        for li, (ly, kind) in enumerate(zip(self.layers, st.kinds)):
+            getattr(self, "_block_" + kind)(cache, st, li, ly, ly.w8 if st.w8 else ly.w4 if st.w4 else ly, x, xn)
+            x, xn = xn, x
+        if B > 16:
+            ops.layernorm(x, self.lnf_g, self.lnf_b, self.eps, out=st.lnf)
+            ops.gemm(st.lnf, self.head, out=st.logits)
+        else:
+            head = self.head_w8 if st.w8 else self.head_w4 if st.w4 else self.head_dec
+            ops.gemm_skinny(x, head, out=st.logits, ln_fold=(head.colsum, self.d, self.eps))
+        return x
+
+    def _spec_step(self, cache: KVCache, st, plan: SelectionPlan):
+        """Enqueue one speculative step (graph-capturable): the B * T rows st.ids -- per sequence its last emitted token and its
+        drafts -- through the blocks against the cache of B rows (chunk attention: row t of a sequence attends up to its own
+        position), the argmax of every row, and the bookkeeping launch that accepts, records, advances and drafts again."""
+        B, T = cache.B, st.T
+        self._step_logits(cache, st, st.ids)
+        ops.argmax(st.logits[:, : self.V], out=st.token)
+        ops.spec_finish(st.ids.view(B, T), st.n_draft, st.token, cache.history, st.count, cache.finish, cache.stop_table,
+                        len(plan.stop[0]), st.limit, st.lookup, st.lookup_len, st.stats, cache.sample_state, T - 1, plan.mode[2],
+                        self.V, cache.d_pos)
 
     # One method per block kind (_block_kind): x -> xn for layer li.  ``src`` holds the block's weight-streaming operands: the
     # layer itself, or its e4m3 / MXFP4 copies (ly.w8 / ly.w4) under W8A16 / W4A16 -- the same launches.  On a ragged cache (pos_stride 1) every
@@ -1118,6 +1146,15 @@ class LMEngine(TokenSelection):
             self._attn_prefix(cache, st, li)
             ops.decode_attn_gemv(st.qkv, cache.k[li], cache.v[li], ctx, cache.B, self.H, cache.d_pos, self.rot, self.sin_t,
                                  self.cos_t, gemv, pos_stride=cache.pos_stride, shared=st.shared)
+            return
+        if st.T > 1 and not st.colaunch:      # MAGMA_SPEC_COLAUNCH=0: the chunk attention alone, then the GEMV alone (two launches)
+            ops.attn_decode_chunk(st.qkv, cache.k[li], cache.v[li], ctx, cache.B, st.T, self.H, cache.d_pos, self.rot, self.sin_t,
+                                  self.cos_t, pos_stride=cache.pos_stride)
+            ops.gemm_skinny(gemv[0], gemv[1], out=gemv[2], **gemv[3])
+            return
+        if st.T > 1:      # a speculative step: T consecutive positions per sequence, the GEMV over all B * T rows
+            ops.decode_attn_gemv(st.qkv, cache.k[li], cache.v[li], ctx, cache.B, self.H, cache.d_pos, self.rot, self.sin_t,
+                                 self.cos_t, gemv, pos_stride=cache.pos_stride, chunk=st.T)
             return
         ops.decode_attn_gemv(st.qkv, cache.k[li], cache.v[li], ctx, cache.B, self.H, cache.d_pos, self.rot, self.sin_t, self.cos_t,
                              gemv, pos_stride=cache.pos_stride)
@@ -1171,6 +1208,9 @@ class LMEngine(TokenSelection):
             self._attn_prefix(cache, st, li)
             ops.attn_decode_fused(st.qkv, cache.k[li], cache.v[li], st.ctx, cache.B, self.H, cache.d_pos, self.rot,
                                   self.sin_t, self.cos_t, pos_stride=cache.pos_stride, shared=st.shared)
+        elif st.T > 1:
+            ops.attn_decode_chunk(st.qkv, cache.k[li], cache.v[li], st.ctx, cache.B, st.T, self.H, cache.d_pos, self.rot,
+                                  self.sin_t, self.cos_t, pos_stride=cache.pos_stride)
         else:
             ops.attn_decode_fused(st.qkv, cache.k[li], cache.v[li], st.ctx, cache.B, self.H, cache.d_pos, self.rot,
                                   self.sin_t, self.cos_t, pos_stride=cache.pos_stride)
@@ -1247,6 +1287,94 @@ class LMEngine(TokenSelection):
             cache.decode_state = st
         return st
 
+    def _ensure_spec_state(self, cache: KVCache, T: int):
+        """The cache's state of the speculative step with T rows per sequence (cache.spec[T]): _ensure_decode_state's scratch and
+        plan for B * T rows -- every GEMV of the step sees an ordinary M = B * T operand, the quantised and packed steps
+        included --, graphs of its own, and the loop's bookkeeping buffers (ids, draft counts, token counts, statistics, lookup ids)."""
+        self._current_packs()
+        st = cache.spec.get(T)
+        if st is not None and st.packs_gen != self._packs_gen:
+            st.graphs.clear()
+            st.packs_gen = self._packs_gen
+        if st is None:
+            B, R, dev = cache.B, cache.B * T, self.device
+            if not 2 <= T <= 8 or R > 16:
+                raise ValueError(f"a speculative step runs B * T rows through the weight-streaming GEMVs, which take at most 16: got "
+                                 f"B * T = {B} * {T} = {R}")
+            if cache.prefix_P:
+                raise NotImplementedError("speculative decoding is not combined with a shared session prefix")
+            self._ensure_decode_packs()
+            mode = self._quantised_decode()
+            if mode is not None:
+                self._ensure_decode_packs_q(mode)
+            st = self._alloc_decode_state(cache, rows=R)
+            st.T = T
+            # MAGMA_SPEC_COLAUNCH (default 1; read when the state is created, like the step's other switches): 0 runs the chunk
+            # attention and the co-launched GEMV as two launches -- the GEMV workgroups then keep their own LDS block and registers,
+            # the attention no longer hides under the weight stream (tools/speculative_bench.py times both)
+            st.colaunch = os.environ.get("MAGMA_SPEC_COLAUNCH", "1") != "0"
+            st.w8, st.w4 = self.decode_w8, self.decode_w4
+            st.kinds, st.refusal = self._plan_decode(R)
+            st.packs_gen = self._packs_gen
+            z = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)  # noqa: E731
+            st.n_draft, st.count, st.lookup_len, st.stats, st.lookup = z(B), z(B), z(B), z(B, 3), z(B, 0)
+            st.limit, st.armed = 0, False
+            cache.spec[T] = st
+        return st
+
+    def decode_chunk(self, input_ids: torch.Tensor, cache: KVCache) -> torch.Tensor:
+        """``input_ids`` (B, T), 2 <= T <= 8, B * T <= 16, as T consecutive positions of every sequence in ONE step against the cache
+        (chunk attention): fp32 logits (B * T, V), row b * T + t those of position pos_b + t -- what T single-token steps give.
+        Eager, teacher-forced: K / V are appended at [pos_b, pos_b + T), the positions do not advance, nothing is selected.  The
+        speculative step (_spec_step) runs the same launches."""
+        B, T = input_ids.shape
+        if B != cache.B:
+            raise ValueError(f"the cache holds {cache.B} rows, input_ids {B}")
+        if int(cache.rows_pos().max()) - cache.prefix_P + T > cache.Smax:
+            raise ValueError(f"KV cache full (Smax={cache.Smax}); pass a larger cache_hint / max_steps")
+        st = self._ensure_spec_state(cache, T)
+        if st.refusal is not None:
+            raise NotImplementedError(st.refusal)
+        st.ids.copy_(input_ids.reshape(B * T, 1))
+        self._step_logits(cache, st, st.ids)
+        return st.logits[:, : self.V]
+
+    def _decode_speculate(self, cache: KVCache, plan: SelectionPlan, use_graph: bool = True):
+        """One speculative step of a loop armed by _arm_speculate; the captured graphs live in cache.spec[T]."""
+        T = plan.mode[1]
+        st = cache.spec.get(T)
+        if st is None or not st.armed or cache.finish is None or not cache.ragged:
+            raise ValueError("speculative decoding needs a cache armed for this T (prefill with eos_token= and a speculative plan)")
+        self._current_packs()
+        if st.packs_gen != self._packs_gen:
+            st.graphs.clear()
+            st.packs_gen = self._packs_gen
+        key = (plan.graph_key(True), st.limit, st.lookup.shape[1])
+        if not use_graph:
+            self._spec_step(cache, st, plan)
+        elif key in st.graphs:
+            st.graphs[key].replay()
+        elif st.steps == 0:
+            self._spec_step(cache, st, plan)              # first step eager (loads code objects)
+        else:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._spec_step(cache, st, plan)
+            st.graphs[key] = g
+            g.replay()
+        st.steps += 1
+        cache.pos += T          # an upper bound: the rows' own positions are on the device until speculate_results reads them
+        return st.logits[:, : self.V], st.token
+
+    def speculate_results(self, cache: KVCache, T: int):
+        """After a speculative loop: (count int64 [B] of every row's emitted tokens, stats int64 [B, 3] = steps, drafted, accepted),
+        on the host; the one read-back of the loop, which also makes the host mirror of the positions exact again."""
+        st = cache.spec[T]
+        pos, count, stats = cache.d_pos.cpu(), st.count.cpu(), st.stats.cpu()
+        cache.set_rows(pos.to(torch.int64))
+        st.armed = False
+        return count.to(torch.int64), stats.to(torch.int64)
+
     def decode(self, input_ids: Optional[torch.Tensor], cache: KVCache, use_graph: bool = True, sampling=None, select: bool = True,
                beam=None, processors=None, stop=None, logprobs=None, constraint=None, guidance=None, plan=None):
         """One cached step.  Returns (fp32 logits (B,V) view, selected token (B,) view: greedy, or sampled when
@@ -1268,6 +1396,10 @@ class LMEngine(TokenSelection):
         if plan is None:
             plan = self.selection_plan(sampling=sampling, beam=beam, processors=processors, stop=stop, logprobs=logprobs,
                                        constraint=constraint, guidance=guidance, vocab=self.V)
+        if plan.is_speculate:
+            if input_ids is not None or not select:
+                raise ValueError("a speculative step feeds its own ids back: decode(None, cache, plan=plan)")
+            return self._decode_speculate(cache, plan, use_graph)
         if cache.pos - cache.prefix_P >= cache.Smax:
             raise ValueError(f"KV cache full (Smax={cache.Smax}); pass a larger cache_hint / max_steps")
         if cache.B > 16:

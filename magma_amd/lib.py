@@ -101,6 +101,8 @@ SYMBOLS = {
                                           C.POINTER(SkinnyDesc), _i32, _vp]),
     "mg_decode_attn_gemv_shared_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _vp,
                                                  C.POINTER(SkinnyDesc), _i32, _i32, _vp, _vp]),
+    "mg_decode_attn_gemv_chunk_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp,
+                                                C.POINTER(SkinnyDesc), _i32, _vp]),
     "mg_comm_unique_id": (C.c_int, [_vp]),
     "mg_comm_init": (C.c_int, [C.POINTER(C.c_void_p), _vp, _i32, _i32]),
     "mg_comm_allreduce_sum": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
@@ -122,6 +124,7 @@ SYMBOLS = {
     "mg_attn_prefill_tree_bf16": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp]),
     "mg_rotary_split_at_bf16": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "mg_attn_decode_fused_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp]),
+    "mg_attn_decode_chunk_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp]),
     "mg_attn_decode_prefix_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp]),
     "mg_attn_decode_fused_shared_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
     "mg_argmax_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp]),
@@ -132,6 +135,8 @@ SYMBOLS = {
     "mg_sample_finish": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp]),
     "mg_sample_finish_rows": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i64, _vp,
                                         _vp]),
+    "mg_spec_finish": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _i32, _vp,
+                                 _vp, _vp, _i32, _i32, _i32, _vp]),
     "mg_sample_finish_slots": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i64, _vp,
                                          _vp, _vp]),
     "mg_slots_admit_bf16": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,

@@ -296,7 +296,8 @@ class Magma(nn.Module):
                  return_finish: bool = False, sampler: str = "reference", min_p: float = 0.0, return_logprobs: bool = False,
                  top_logprobs: int = 0, constraint=None, guidance_scale: float = 1.0, negative_embeddings=None,
                  negative_lengths=None, guidance_min_p: float = 0.0, num_beam_groups: int = 1, diversity_penalty: float = 0.0,
-                 penalty_alpha: float = 0.0):
+                 penalty_alpha: float = 0.0, prompt_lookup_num_tokens: int = 0, max_matching_ngram_size: int = 2, lookup_ids=None,
+                 return_speculation: bool = False):
         """reference magma.py:214-236 (+ stop_on_eos / seed / eos_check_every / lengths, see sampling.generate).
         ``lengths``: prompts of different lengths, right-padded (embed_batch); ``embeddings`` may also be a list of
         per-sample (1, s_i, d) tensors.  ``num_beams`` > 1: beam search (length_penalty, early_stopping,
@@ -323,7 +324,10 @@ class Magma(nn.Module):
         ``penalty_alpha`` in (0, 1] with ``top_k`` in [1, 16]: contrastive search -- among the ``top_k`` most probable tokens the one
         whose hidden state is least similar to the context's, deterministic (see sampling.generate).
         ``seed`` / ``temperature`` / ``top_k`` / ``top_p`` / ``min_p`` may each be a sequence of B values: every row then samples
-        under its own settings and seed and equals its one-row call (see sampling.generate, per-row sampling)."""
+        under its own settings and seed and equals its one-row call (see sampling.generate, per-row sampling).
+        ``prompt_lookup_num_tokens`` = k in [1, 7] / ``max_matching_ngram_size`` / ``lookup_ids`` / ``return_speculation``:
+        speculative greedy decoding -- every step verifies k prompt-lookup drafts per row beside its newest token and keeps what the
+        model agrees with; the output is the per-row greedy call's, token for token (see sampling.generate)."""
         torch.cuda.set_device(self.device)
         return generate(self, embeddings=embeddings, max_steps=max_steps, temperature=temperature, top_k=top_k,
                         top_p=top_p, decode=decode, stop_on_eos=stop_on_eos, seed=seed, eos_check_every=eos_check_every,
@@ -336,7 +340,9 @@ class Magma(nn.Module):
                         min_p=min_p, return_logprobs=return_logprobs, top_logprobs=top_logprobs, constraint=constraint,
                         guidance_scale=guidance_scale, negative_embeddings=negative_embeddings, negative_lengths=negative_lengths,
                         guidance_min_p=guidance_min_p, num_beam_groups=num_beam_groups, diversity_penalty=diversity_penalty,
-                        penalty_alpha=penalty_alpha)
+                        penalty_alpha=penalty_alpha, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
+                        max_matching_ngram_size=max_matching_ngram_size, lookup_ids=lookup_ids,
+                        return_speculation=return_speculation)
 
     def generate_stream(self, requests, **kwargs):
         """Generate over a stream of requests -- an iterable of ``embed`` outputs, or pairs (embeddings, max_new_tokens) --: a

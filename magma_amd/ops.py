@@ -491,14 +491,24 @@ def _pos_stride(d_pos: torch.Tensor, B: int, pos_stride: int) -> int:
 
 
 def decode_attn_gemv(qkv, kcache, vcache, attn_out, B, H, d_pos, rot_dim, sin_t, cos_t, gemv: tuple, *, pos_stride: int = 0,
-                     shared=None):
+                     shared=None, chunk: int = 0):
     """Decode attention (rotary + append + attend) co-launched with one independent GEMV
     gemv = (x, w, out, kwargs).  ``pos_stride=1``: row b writes / attends at its own position d_pos[b].
-    ``shared`` = (n_prefix, part): the attention runs in the shared-prefix mode (attn_decode_fused) -- another entry point."""
+    ``shared`` = (n_prefix, part): the attention runs in the shared-prefix mode (attn_decode_fused) -- another entry point.
+    ``chunk`` = T >= 2 (mg_decode_attn_gemv_chunk_bf16, one launch as well): ``qkv`` / ``attn_out`` hold B * T rows, T consecutive
+    positions of each of the B sequences -- the attention workgroups run attn_decode_chunk's body --, the GEMV runs over its
+    M = B * T operand with the bits of the plain co-launch's."""
     _need_gpu(qkv)
     ps = _pos_stride(d_pos, B, pos_stride)
     d, og = skinny_desc(gemv[0], gemv[1], gemv[2], **gemv[3])
     assert attn_out.ndim == 2 and attn_out.stride(1) == 1 and attn_out.shape[1] == H * 256   # a column range of a wider row is fine
+    if chunk:
+        assert shared is None
+        check(L.load().mg_decode_attn_gemv_chunk_bf16(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), attn_out.data_ptr(),
+                                                      attn_out.stride(0), B, int(chunk), H, kcache.shape[2], d_pos.data_ptr(), rot_dim,
+                                                      _p(sin_t), _p(cos_t), C.byref(d), ps, _stream()),
+              "mg_decode_attn_gemv_chunk_bf16")
+        return attn_out, og
     if shared is not None:
         n_prefix, part = _shared_part(shared, B, H)
         check(L.load().mg_decode_attn_gemv_shared_bf16(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), attn_out.data_ptr(),
@@ -816,6 +826,21 @@ def attn_decode_fused(qkv, kcache, vcache, out, B, H, d_pos, rot_dim, sin_t, cos
     return out
 
 
+def attn_decode_chunk(qkv, kcache, vcache, out, B, T, H, d_pos, rot_dim, sin_t, cos_t, *, pos_stride: int = 0):
+    """attn_decode_fused for T consecutive positions of every sequence in one launch (mg_attn_decode_chunk_bf16): ``qkv``
+    (B * T, 3 * H * 256) sequence-major, row b * T + t at position pos_b + t; k, v appended at [pos_b, pos_b + T), query t attends
+    over [0, pos_b + t].  ``out`` (B * T, H * 256) may be a column range of wider rows.  Same bits as T successive attn_decode_fused
+    launches for finite K / V (a later row's v enters an earlier query's sum as 0.f * v, so an Inf or NaN there would reach it);
+    a row whose position lies outside [0, Smax) is skipped alone."""
+    _need_gpu(qkv)
+    ps = _pos_stride(d_pos, B, pos_stride)
+    assert out.ndim == 2 and out.stride(1) == 1 and out.shape[1] == H * 256
+    check(L.load().mg_attn_decode_chunk_bf16(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), out.stride(0), B, T,
+                                             H, kcache.shape[2], d_pos.data_ptr(), rot_dim, _p(sin_t), _p(cos_t), ps, _stream()),
+          "mg_attn_decode_chunk_bf16")
+    return out
+
+
 def argmax(logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _need_gpu(logits)
     assert logits.dtype == torch.float32 and logits.ndim == 2 and logits.stride(1) == 1
@@ -968,6 +993,35 @@ def sample_finish_rows(token: torch.Tensor, state: torch.Tensor, table: torch.Te
                                          _p(clear), 0 if clear is None else clear.numel() // clear_stride, clear_stride, ps,
                                          table.data_ptr(), int(n_eos), int(n_seq), int(pad), finish.data_ptr(), _stream()),
           "mg_sample_finish_rows")
+
+
+def spec_finish(ids: torch.Tensor, n_draft: torch.Tensor, token: torch.Tensor, history: torch.Tensor, count: torch.Tensor,
+                finish: torch.Tensor, table: torch.Tensor, n_eos: int, limit: int, lookup: torch.Tensor, lookup_len: torch.Tensor,
+                stats: torch.Tensor, state: torch.Tensor, num_tokens: int, max_ngram: int, vocab: int,
+                d_pos: Optional[torch.Tensor] = None, *, arm: bool = False):
+    """The bookkeeping launch of a speculative step (mg_spec_finish; host statement: sampling.speculate_update): accepts the
+    longest prefix of the drafts ``ids[b, 1:1 + n_draft[b]]`` that the step's argmaxes ``token`` (B * T) agree with, records the
+    emitted tokens in ``history`` / ``count`` / ``finish`` / ``stats``, advances ``d_pos`` by their number and writes the next
+    step's ``ids`` and ``n_draft`` by the prompt-lookup rule over ``lookup[b, :lookup_len[b]] ++ history[b, :count[b]]``.
+    ``arm=True``: ``token`` holds the prefill's B selected tokens, nothing was fed (``d_pos`` is left alone).  Enqueue-only."""
+    _need_gpu(ids, n_draft, token, history, count, finish, table, lookup, lookup_len, stats, state, d_pos)
+    B, T = ids.shape
+    assert ids.dtype == torch.int64 and ids.is_contiguous() and token.dtype == torch.int64 and token.is_contiguous()
+    assert token.numel() >= (B if arm else B * T)
+    assert history.dtype == torch.int64 and history.ndim == 2 and history.stride(1) == 1 and history.shape[0] == B
+    assert lookup.dtype == torch.int32 and lookup.ndim == 2 and lookup.shape[0] == B and (lookup.shape[1] == 0 or lookup.stride(1) == 1)
+    for t, n in ((n_draft, B), (count, B), (lookup_len, B), (finish, 2 * B), (stats, 3 * B)):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n
+    assert state.dtype == torch.int32 and state.numel() >= 2
+    assert table.dtype == torch.int32 and table.is_contiguous() and table.numel() >= STOP_TABLE_INTS
+    if d_pos is not None:
+        _pos_stride(d_pos, B, 1)
+    check(L.load().mg_spec_finish(ids.data_ptr(), B, T, n_draft.data_ptr(), token.data_ptr(), 1 if arm else T, history.data_ptr(),
+                                  history.stride(0), history.shape[1], count.data_ptr(), finish.data_ptr(), table.data_ptr(),
+                                  int(n_eos), int(limit), None if arm else _p(d_pos), lookup.data_ptr() if lookup.shape[1] else None,
+                                  lookup.stride(0) if lookup.shape[1] else 0, lookup.shape[1], lookup_len.data_ptr(),
+                                  stats.data_ptr(), state.data_ptr(), int(num_tokens), int(max_ngram), int(vocab), _stream()),
+          "mg_spec_finish")
 
 
 STOP_LEN = 0x300                                                        # include/magma_hip.h MG_STOP_LEN: the budget ran out

@@ -795,6 +795,156 @@ def finish_from_record(record, n_gen: int) -> Finish:
     return Finish(kept, reason, index)
 
 
+# ------------------------------------------------------------------------------------------------- speculative greedy decoding
+MAX_SPEC_TOKENS, MAX_SPEC_NGRAM, MAX_SPEC_ROWS = 7, 16, 16
+
+
+class Speculation(NamedTuple):
+    """What speculation did for every row of a generate() call (``return_speculation=True``): CPU int64 [B] each."""
+    steps: torch.Tensor         # model calls in which the row was open, the prefill included
+    drafted: torch.Tensor       # draft tokens fed
+    accepted: torch.Tensor      # draft tokens the model agreed with
+
+
+def prompt_lookup(ids, num_tokens: int, max_ngram: int, eos_ids=(), vocab: int = None) -> List[int]:
+    """The draft of prompt-lookup decoding, the rule of transformers' ``PromptLookupCandidateGenerator.get_candidates``
+    (``prompt_lookup_num_tokens`` / ``max_matching_ngram_size``): for n from min(max_ngram, len - 1) down to 1, the first window
+    from the left that equals the last n tokens of ``ids`` and has a non-empty continuation inside ``ids`` decides: its
+    continuation, at most ``num_tokens`` long, cut in front of the first eos id (``vocab``: or id outside [0, vocab)), is the
+    draft -- possibly empty, no further window is tried then.  No window: no draft."""
+    ids = [int(t) for t in (ids.tolist() if hasattr(ids, "tolist") else ids)]
+    L, eos = len(ids), {int(e) for e in eos_ids}
+    for n in range(min(int(max_ngram), L - 1), 0, -1):
+        tail = ids[L - n:]
+        for i in range(L - n):                      # i + n < L: the continuation is not empty
+            if ids[i:i + n] == tail:
+                draft = []
+                for t in ids[i + n:min(i + n + int(num_tokens), L)]:
+                    if t in eos or (vocab is not None and not 0 <= t < vocab):
+                        break
+                    draft.append(t)
+                return draft
+    return []
+
+
+def speculate_update(ids, n_draft, token, history, count, finish, pos, stats, lookup, lookup_len, state, *, num_tokens: int,
+                     max_ngram: int, eos_ids, limit: int, arm: bool = False, vocab: int = None):
+    """The bookkeeping of a speculative step, host statement (the device kernel is csrc/sampling.hip, spec_finish_kernel), IN
+    PLACE on CPU tensors.  The step fed ``ids`` (B, T) int64 -- ids[b, 0] the row's last emitted token, ids[b, 1:1 + n_draft[b]]
+    its drafts -- and ``token`` (B * T,) int64 holds the argmax of every fed row (``arm``: (B,), the prefill's selected tokens;
+    nothing was fed, ``n_draft`` counts as 0 and ``pos`` stays).  Per row b with finish[b, 0] < 0:
+      accept  a = the leading j in [1, n_draft[b]] with ids[b, j] == token[b * T + j - 1]; token[b * T + 0 .. a] are emitted, cut
+              behind the first of ``eos_ids`` among them (finish[b] = (count, STOP_EOS | i)) and at min(limit, history columns) -
+              count[b] (finish[b] = (count, STOP_LEN));
+      record  the m emitted tokens go to history[b, count[b]:], count[b] += m, pos[b] += m, stats[b] += (1, n_draft, a);
+      draft   a row still open: ids[b, 0] = its last emitted token, ids[b, 1:] = prompt_lookup(lookup[b, :lookup_len[b]] ++
+              history[b, :count[b]], num_tokens, max_ngram, eos_ids), n_draft[b] their number, unused entries repeat ids[b, 0].
+    A finished row (now or earlier) is frozen: n_draft[b] = 0, ids[b] = eos_ids[0], nothing else of it moves.  state[1] latches
+    state[0] when no row is open; state[0] += 1.  Degenerate values: n_draft counts as clamped into [0, T - 1] (0 when arming),
+    lookup_len into [0, lookup columns]; a row whose count lies outside [0, history columns] is skipped whole."""
+    from .ops import STOP_EOS, STOP_LEN
+    B, T = ids.shape
+    cols, lcols, ts = history.shape[1], lookup.shape[1], 1 if arm else T
+    eos_ids = [int(e) for e in eos_ids]
+    any_open = False
+    for b in range(B):
+        c = int(count[b])
+        if int(finish[b, 0]) >= 0:
+            n_draft[b], ids[b] = 0, eos_ids[0]
+            continue
+        if not 0 <= c <= cols:
+            continue
+        nd = max(0, min(int(n_draft[b]), min(T, ts) - 1))
+        tk = [int(t) for t in token[b * ts:b * ts + nd + 1]]
+        a = 0
+        while a < nd and int(ids[b, a + 1]) == tk[a]:
+            a += 1
+        lim, m, code = min(int(limit), cols), 0, 0
+        for j in range(a + 1):
+            if c + j >= lim or code:
+                break
+            history[b, c + j], m = tk[j], j + 1
+            if tk[j] in eos_ids:
+                code = STOP_EOS | eos_ids.index(tk[j])
+        if not code and c + m >= lim:
+            code = STOP_LEN
+        count[b] = c + m
+        if pos is not None and not arm:
+            pos[b] += m
+        stats[b, 0] += 1
+        stats[b, 1] += nd
+        stats[b, 2] += a
+        if code:
+            finish[b, 0], finish[b, 1], n_draft[b], ids[b] = c + m, code, 0, eos_ids[0]
+            continue
+        any_open = True
+        llen = max(0, min(int(lookup_len[b]), lcols))
+        draft = prompt_lookup(lookup[b, :llen].tolist() + history[b, :c + m].tolist(), min(num_tokens, T - 1), max_ngram, eos_ids,
+                              vocab)
+        last = int(history[b, c + m - 1])
+        ids[b] = last
+        ids[b, 1:1 + len(draft)] = torch.tensor(draft, dtype=ids.dtype)
+        n_draft[b] = len(draft)
+    if not any_open and int(state[1]) < 0:
+        state[1] = int(state[0])
+    state[0] += 1
+
+
+def crop_past(past, length: int):
+    """A KV cache cut back to its first ``length`` positions (the rejected drafts of a speculative step leave it): transformers
+    Cache objects (crop), or nested lists / tuples of (batch, heads, positions, dim) tensors."""
+    if hasattr(past, "crop"):
+        past.crop(length)
+        return past
+    if isinstance(past, (list, tuple)):
+        return type(past)(crop_past(p, length) for p in past)
+    if torch.is_tensor(past):
+        return past[..., :length, :]
+    raise TypeError(f"cannot crop a cache of type {type(past).__name__} for speculative decoding")
+
+
+def check_speculation_args(prompt_lookup_num_tokens=0, max_matching_ngram_size=2, lookup_ids=None, return_speculation=False,
+                           batch: int = None, vocab: int = None, encode: Callable = None):
+    """ValueError for speculation arguments generate() does not take (NotImplementedError: more than 16 rows per step).  Returns
+    None when the call does not speculate
+    (``prompt_lookup_num_tokens`` = 0), else dict(T = drafts + 1 rows per sequence, max_ngram, lookup = None or ``batch`` lists of
+    token ids).  ``prompt_lookup_num_tokens`` in [0, 7], ``max_matching_ngram_size`` in [1, 16]; ``lookup_ids``: one list of ids,
+    tensor or string (``encode`` turns it into ids) per row, every id in [0, vocab); B * T may not exceed 16."""
+    k, n = prompt_lookup_num_tokens, max_matching_ngram_size
+    if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= MAX_SPEC_TOKENS:
+        raise ValueError(f"prompt_lookup_num_tokens must be an integer in [0, {MAX_SPEC_TOKENS}] (0: off), got {k!r}")
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= MAX_SPEC_NGRAM:
+        raise ValueError(f"max_matching_ngram_size must be an integer in [1, {MAX_SPEC_NGRAM}], got {n!r}")
+    if k == 0:
+        if lookup_ids is not None or return_speculation:
+            raise ValueError("lookup_ids / return_speculation belong to speculative decoding: set prompt_lookup_num_tokens >= 1")
+        return None
+    if batch is not None and batch * (k + 1) > MAX_SPEC_ROWS:
+        raise NotImplementedError(f"a speculative step runs B * (prompt_lookup_num_tokens + 1) rows and takes at most {MAX_SPEC_ROWS}: "
+                         f"got {batch} * {k + 1} = {batch * (k + 1)}")
+    rows = None
+    if lookup_ids is not None:
+        if isinstance(lookup_ids, str) or not isinstance(lookup_ids, (list, tuple)):
+            raise ValueError("lookup_ids must be a list with one entry (token ids or a string) per row")
+        if batch is not None and len(lookup_ids) != batch:
+            raise ValueError(f"lookup_ids has {len(lookup_ids)} entries, the batch {batch} rows")
+        rows = []
+        for r, q in enumerate(lookup_ids):
+            if isinstance(q, str):
+                if encode is None:
+                    raise ValueError(f"lookup_ids[{r}] is text and this model has no tokenizer to encode it")
+                q = encode(q)
+            if torch.is_tensor(q):
+                q = q.flatten().tolist()
+            if not isinstance(q, (list, tuple)):
+                raise ValueError(f"lookup_ids[{r}] must be a list of token ids, a tensor or a string, got {q!r}")
+            for t in q:
+                if isinstance(t, bool) or not isinstance(t, int) or t < 0 or (vocab is not None and t >= vocab):
+                    raise ValueError(f"lookup_ids[{r}] must hold token ids in [0, {'V' if vocab is None else vocab}), got {t!r}")
+            rows.append([int(t) for t in q])
+    return dict(T=k + 1, max_ngram=n, lookup=rows)
+
+
 MAX_TOP_LOGPROBS = 20
 
 
@@ -1350,7 +1500,9 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
              return_finish: bool = False, sampler: str = "reference", min_p: float = 0.0, return_logprobs: bool = False,
              top_logprobs: int = 0, constraint=None, guidance_scale: float = 1.0, negative_embeddings=None,
              negative_lengths=None, guidance_min_p: float = 0.0, num_beam_groups: int = 1,
-             diversity_penalty: float = 0.0, penalty_alpha: float = 0.0) -> Union[List[str], torch.Tensor]:
+             diversity_penalty: float = 0.0, penalty_alpha: float = 0.0, prompt_lookup_num_tokens: int = 0,
+             max_matching_ngram_size: int = 2, lookup_ids=None,
+             return_speculation: bool = False) -> Union[List[str], torch.Tensor]:
     """reference sampling.py:43-121.  Token selection (argmax, or top-k / the reference's top-p rule / softmax /
     multinomial) and the ``(next_token == eos).all()`` test run on the device inside the captured token step; the host
     reads the recorded "first all-eos step" every ``eos_check_every`` steps (default 8, MAGMA_EOS_CHECK_EVERY) instead of
@@ -1484,9 +1636,33 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     a sampled row without a seed draws one from torch's CPU generator.  Combines with ragged prompts, per-row stopping, the
     logits processors, log-probabilities, constraints, a continued cache and the quantised decode weights; not (NotImplementedError)
     with beam search, contrastive search or guidance.  The selection is the same single launch of the captured step, reading a
-    device table (ops.sample_rows).  With scalars only, the call is what it was, bit for bit and launch for launch."""
+    device table (ops.sample_rows).  With scalars only, the call is what it was, bit for bit and launch for launch.
+
+    Speculative greedy decoding (DESIGN.md "Speculative decoding"; ``temperature=0.0``): ``prompt_lookup_num_tokens`` = k in
+    [1, 7] makes every token step verify k guessed continuations per row beside the row's newest token -- k + 1 rows per
+    sequence ride one weight stream -- and keep the longest prefix the model agrees with, plus the model's own next token: 1 to
+    k + 1 tokens per step and row instead of one, token for token the output of ``generate(..., temperature=0.0,
+    stop_per_row=True)``.  The guesses are transformers' prompt lookup (``prompt_lookup_num_tokens`` /
+    ``max_matching_ngram_size`` there; ``prompt_lookup`` above): the continuation of the earliest earlier occurrence of the row's
+    last ``max_matching_ngram_size`` (1 to 16; then fewer) tokens.  The prompt is embeddings, so its text is searched only when
+    ``lookup_ids`` gives it: a list of B id lists, tensors or strings (``model.tokenizer.encode``), searched in front of the tokens
+    this call generates; None searches those alone.  It pays where the answer repeats text that is there: few-shot answer formats,
+    lists, OCR-like questions.  Speculation implies per-row stopping (``stop_per_row=None`` means True, False raises; ``eos_token``
+    takes 1 to 8 ids; layout, padding and ``return_finish`` as there).  ``return_speculation=True`` appends a ``Speculation`` --
+    per row the model calls it was open in, the drafts fed and the drafts accepted.  The HIP engine runs the whole step on the
+    device (chunk attention, one bookkeeping launch that accepts, records and drafts again); any other LM object runs the host
+    statement row by row.  B * (k + 1) may not exceed 16.  Not yet combined (NotImplementedError) with sampled selection, beam and
+    contrastive search, guidance, the logits processors, ``return_logprobs``, a constraint, stop sequences, ``past_key_values`` /
+    ``return_past_key_values``, ``generate_stream`` / ``choose_stream``.  At ``prompt_lookup_num_tokens=0`` (the default) the call
+    is launch for launch what it was."""
     if eos_token is None or (isinstance(eos_token, int) and not eos_token):
         eos_token = model.eos_token
+    spec = check_speculation_args(prompt_lookup_num_tokens, max_matching_ngram_size, lookup_ids, return_speculation,
+                                  vocab=_logit_count(model), encode=getattr(getattr(model, "tokenizer", None), "encode", None))
+    if spec is not None:
+        if stop_per_row is False:
+            raise ValueError("speculative decoding (prompt_lookup_num_tokens > 0) stops per row: stop_per_row=False does not apply")
+        stop_per_row = True
     per_row = per_row_given(temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, seed=seed)
     if per_row:
         for what, given in (("beam search (num_beams > 1 / return_scores=True)", num_beams > 1 or return_scores),
@@ -1528,6 +1704,18 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
                                   "return_past_key_values): a guided cache holds two conversations per row")
     continuing = past_key_values is not None or return_past_key_values
     contrast = check_contrastive_args(penalty_alpha, top_k, _logit_count(model))
+    if spec is not None:
+        for what, given in (("sampled selection (temperature != 0, per-row sampler settings) is", bool(per_row) or temperature != 0.0),
+                            ("beam search (num_beams > 1 / return_scores=True) is", num_beams > 1 or return_scores),
+                            ("contrastive search (penalty_alpha > 0) is", contrast is not None),
+                            ("guidance is", guide is not None), ("the logits processors are", proc is not None),
+                            ("token log-probabilities (return_logprobs / top_logprobs) are", n_top is not None),
+                            ("a constraint is", constraint is not None), ("stop sequences are", bool(stop["stop_seqs"])),
+                            ("a KV cache (past_key_values / return_past_key_values) is", continuing)):
+            if given:
+                raise NotImplementedError(f"{what} not combined with speculative decoding (prompt_lookup_num_tokens > 0) yet")
+        return _generate_speculative(model, embeddings, lengths, max_steps, eos_ids, decode, eos_check_every, stop_on_eos, spec,
+                                     lookup_ids, return_finish, return_speculation)
     if contrast is not None:
         for what, given in (("beam search (num_beams > 1 / return_scores=True) is", num_beams > 1 or return_scores),
                             ("the logits processors are", proc is not None),
@@ -1752,6 +1940,123 @@ def _host_loop(model, embeddings, lengths, max_steps, eos_token, seed, every, st
     return _Generated(out[:, :n], out[:, s:n], past, record if keep else None, vals)
 
 
+def _generate_speculative(model, embeddings, lengths, max_steps, eos_ids, decode, eos_check_every, stop_on_eos, spec, lookup_ids,
+                          return_finish, return_speculation):
+    """generate() with prompt_lookup_num_tokens > 0: the checks that need the batch, the device or the host loop, and the
+    per-row tail -- every row's tokens up to its own count, the pad id behind them."""
+    embeddings, lengths = prompt_batch(embeddings, lengths, check=False)
+    b, s, _ = embeddings.shape
+    on_device = getattr(model.lm, "device_token_selection", False)
+    spec = check_speculation_args(spec["T"] - 1, spec["max_ngram"], lookup_ids, return_speculation, batch=b, vocab=_logit_count(model),
+                                  encode=getattr(getattr(model, "tokenizer", None), "encode", None))
+    if lengths is not None:
+        from .engine import LMEngine
+        lengths = LMEngine.check_lengths(lengths, b, s)
+    pad = eos_ids[0]
+    with eval_mode(model):
+        loop = _speculate_device_loop if on_device else _speculate_host_loop
+        history, count, record, stats = loop(model, embeddings, lengths, max_steps, eos_ids, poll_every(eos_check_every), spec)
+        n, n_gen = history.shape[1], int(count.max()) if stop_on_eos else max_steps
+        tokens = torch.full((b, n_gen), pad, dtype=torch.int64)
+        tokens[:, :n] = torch.where(torch.arange(n)[None, :] < count[:, None], history.cpu(), tokens[:, :n])
+        out = layout_ids(tokens.to(embeddings.device), s, lengths, model.image_token, pad)
+        finish = finish_from_record(record, n_gen)
+        if decode:
+            out = decode_ids(model, out, pad, s, lengths, finish)
+    ret = (out,)
+    if return_finish:
+        ret += (finish,)
+    if return_speculation:
+        ret += (Speculation(stats[:, 0].clone(), stats[:, 1].clone(), stats[:, 2].clone()),)
+    return ret if len(ret) > 1 else ret[0]
+
+
+def _spec_record(finish) -> torch.Tensor:
+    """The loop's finish record (count at which the row finished or -1, code) as finish_from_record reads one: a row that finished
+    on an eos id at count c did so at step c - 1; a row that ran out of its budget, or never finished, ran to the end of the call."""
+    from .ops import STOP_EOS
+    rec = torch.as_tensor(finish).to(torch.int64).cpu().clone()
+    eos = (rec[:, 0] >= 0) & ((rec[:, 1] & ~0xFF) == STOP_EOS)
+    rec[:, 0] = torch.where(eos, rec[:, 0] - 1, torch.full_like(rec[:, 0], -1))
+    rec[:, 1] = torch.where(eos, rec[:, 1], torch.zeros_like(rec[:, 1]))
+    return rec
+
+
+def _speculate_device_loop(model, embeddings, lengths, max_steps, eos_ids, every, spec):
+    """The speculative loop on the HIP engine: one ragged prefill (every row keeps its own position: they advance by different
+    amounts) armed with a speculative plan, then steps that feed their own ids back on the device; the host reads the
+    all-finished latch every ``every`` steps, and once at the end the token history, the counts, the finish record and the
+    statistics.  At most max_steps steps: every step emits at least one token per open row."""
+    from .engine import LMEngine
+    b, s, _ = embeddings.shape
+    T = spec["T"]
+    engine = model.lm.engine
+    plan = LMEngine.selection_plan(stop=dict(eos_ids=eos_ids, stop_seqs=()), speculate=(T, spec["max_ngram"]), vocab=engine.V)
+    lens = lengths if lengths is not None else torch.full((b,), s, dtype=torch.int64)
+    if max_steps < 1:
+        return (torch.zeros(b, 0, dtype=torch.int64), torch.zeros(b, dtype=torch.int64), torch.tensor([[-1, 0]] * b).view(b, 2),
+                torch.zeros(b, 3, dtype=torch.int64))
+    outputs = model.lm(inputs_embeds=embeddings, use_cache=True, past_key_values=None, cache_hint=max_steps + T, reuse_cache=True,
+                       eos_token=eos_ids[0], seed=dict(limit=max_steps, lookup=spec["lookup"]), plan=plan, lengths=lens)
+    past = outputs.past_key_values
+    for i in range(max_steps - 1):
+        outputs = model.lm(input_ids=None, use_cache=True, past_key_values=past, feed_back=True, plan=plan)
+        if ((i + 1) % every == 0 or i + 2 == max_steps) and int(outputs.eos_state[1]) >= 0:     # one host sync per `every` steps
+            break
+    count, stats = engine.speculate_results(past, T)
+    n = int(count.max())
+    return past.history[:b, :n].cpu(), count, _spec_record(past.finish[:b]), stats
+
+
+def _speculate_host_loop(model, embeddings, lengths, max_steps, eos_ids, every, spec):
+    """The speculative loop over any other LM object, the statement the device loop is compared with: row by row -- a row's
+    prompt alone, then its last token and its drafts as ONE (1, 1 + drafts) chunk against its cache --, the greedy token of every
+    fed position, speculate_update, and the cache cropped to the accepted length (crop_past)."""
+    b, s, _ = embeddings.shape
+    T, cols = spec["T"], max(max_steps, 1)
+    rows = spec["lookup"] or [[] for _ in range(b)]
+    width = max(len(q) for q in rows)
+    st = dict(ids=torch.zeros(b, T, dtype=torch.int64), n_draft=torch.zeros(b, dtype=torch.int32),
+              history=torch.zeros(b, cols, dtype=torch.int64), count=torch.zeros(b, dtype=torch.int32),
+              finish=torch.tensor([[-1, 0]] * b, dtype=torch.int32).view(b, 2), pos=torch.zeros(b, dtype=torch.int32),
+              stats=torch.zeros(b, 3, dtype=torch.int32), lookup=torch.zeros(b, width, dtype=torch.int32),
+              lookup_len=torch.tensor([len(q) for q in rows], dtype=torch.int32), state=torch.tensor([0, -1], dtype=torch.int32))
+    for r, q in enumerate(rows):
+        st["lookup"][r, :len(q)] = torch.tensor(q, dtype=torch.int32)
+    kw = dict(num_tokens=T - 1, max_ngram=spec["max_ngram"], eos_ids=eos_ids, limit=max_steps, vocab=_logit_count(model))
+
+    def update(token, arm):
+        speculate_update(st["ids"], st["n_draft"], token, st["history"], st["count"], st["finish"], st["pos"], st["stats"],
+                         st["lookup"], st["lookup_len"], st["state"], arm=arm, **kw)
+
+    if max_steps < 1:
+        return st["history"][:, :0], st["count"].to(torch.int64), _spec_record(st["finish"]), st["stats"].to(torch.int64)
+    pasts, token = [], torch.zeros(b, dtype=torch.int64)
+    for r in range(b):
+        n = s if lengths is None else int(lengths[r])
+        out = model.lm(inputs_embeds=embeddings[r:r + 1, :n], use_cache=True, past_key_values=None, cache_hint=max_steps + T,
+                       reuse_cache=False)
+        pasts.append(out.past_key_values)
+        token[r] = int(torch.argmax(out.logits[0, -1, :].float()))
+        st["pos"][r] = n
+    update(token, True)
+    while int(st["state"][1]) < 0:
+        token = torch.zeros(b * T, dtype=torch.int64)
+        for r in range(b):
+            if int(st["finish"][r, 0]) >= 0:
+                continue
+            fed = 1 + int(st["n_draft"][r])
+            out = model.lm(input_ids=st["ids"][r:r + 1, :fed].to(embeddings.device), use_cache=True, past_key_values=pasts[r])
+            pasts[r] = out.past_key_values
+            token[r * T:r * T + fed] = torch.argmax(out.logits[0, -fed:, :].float(), dim=-1).cpu()
+        update(token, False)
+        for r in range(b):              # the rejected drafts leave the cache (a finished row's cache is not read again)
+            if int(st["finish"][r, 0]) < 0:
+                pasts[r] = crop_past(pasts[r], int(st["pos"][r]))
+    n = int(st["count"].max())
+    return st["history"][:, :n], st["count"].to(torch.int64), _spec_record(st["finish"]), st["stats"].to(torch.int64)
+
+
 class StreamResult(NamedTuple):
     """One finished request of generate_stream()."""
     index: int                  # the request's ordinal in ``requests``
@@ -1789,6 +2094,7 @@ _STREAM_REFUSED = (
                         "num_return_sequences", "return_scores")),
     ("contrastive search is", ("penalty_alpha",)),
     ("a KV cache (past_key_values / return_past_key_values) is", ("past_key_values", "return_past_key_values")),
+    ("speculative decoding is", ("prompt_lookup_num_tokens", "max_matching_ngram_size", "lookup_ids", "return_speculation")),
 )
 
 
@@ -2070,7 +2376,8 @@ class StreamChoice(NamedTuple):
 
 def choose_stream(model, requests, *, slots: int = 8, max_choice_tokens: int = 16, max_prompt: int = None, eos_token=None,
                   top_logprobs: int = 0, every: int = None, admit_rows: int = None, prefix=None, share_prefix: bool = False,
-                  trie_capacity: int = None, repetition_penalty: float = 1.0, min_new_tokens: int = 0, suppress_tokens=None):
+                  trie_capacity: int = None, repetition_penalty: float = 1.0, min_new_tokens: int = 0, suppress_tokens=None,
+                  **unsupported):
     """``choose`` over a stream of requests (DESIGN.md "Choosing over a request stream"): every request brings its own closed set
     of answers, and one ``StreamChoice`` per request is yielded in completion order.  Request i's choice, tokens and
     log-probabilities are those of the solo call
@@ -2093,7 +2400,16 @@ def choose_stream(model, requests, *, slots: int = 8, max_choice_tokens: int = 1
     ``trie_capacity``: int32 entries the device table is allocated for (3 + 4 nodes + 2 edges, summed over the tries that are live
     at once; default 4096) -- a table that outgrows it is re-allocated mid-session, and the captured step with it.
     ``repetition_penalty`` / ``min_new_tokens`` / ``suppress_tokens``: generate()'s rules, checked against every request's choices
-    as generate(constraint=...) checks them."""
+    as generate(constraint=...) checks them.  generate()'s speculation keywords are refused (NotImplementedError) when they differ
+    from their defaults, as generate_stream refuses them."""
+    import inspect
+    defaults = {k: p.default for k, p in inspect.signature(generate).parameters.items()}
+    spec_names = _STREAM_REFUSED[-1][1]
+    for k, v in unsupported.items():
+        if k not in spec_names:
+            raise TypeError(f"choose_stream() got an unexpected keyword argument {k!r}")
+        if not (v is defaults[k] or (not torch.is_tensor(v) and v == defaults[k])):
+            raise NotImplementedError(f"speculative decoding is not combined with choose_stream yet ({k}=)")
     for name, v, lo, hi in (("max_choice_tokens", max_choice_tokens, 1, MAX_TRIE_LEN), ("trie_capacity", trie_capacity, 1, None)):
         if (name != "trie_capacity" or v is not None) and (isinstance(v, bool) or not isinstance(v, int) or v < lo or
                                                           (hi is not None and v > hi)):

@@ -137,6 +137,12 @@ class SelectionPlan(NamedTuple):
         return isinstance(self.mode, tuple) and self.mode[:1] == ("rows",)
 
     @property
+    def is_speculate(self) -> bool:
+        """Speculative greedy decoding (DESIGN.md "Speculative decoding"): mode ("speculate", T, max_ngram) -- every step runs T rows
+        per sequence, the last emitted token and up to T - 1 prompt-lookup drafts, and keeps the prefix the model agrees with."""
+        return isinstance(self.mode, tuple) and self.mode[:1] == ("speculate",)
+
+    @property
     def beam_groups(self) -> tuple:
         """(num_beam_groups, diversity_penalty) of a beam mode: (1, 0.0) for the five-entry tuple of plain beam search."""
         return tuple(self.mode[5:7]) if len(self.mode) > 5 else (1, 0.0)
@@ -255,7 +261,8 @@ class TokenSelection:
 
     @classmethod
     def selection_plan(cls, plan=None, *, sampling=None, beam=None, processors=None, stop=None, logprobs=None, constraint=None,
-                       guidance=None, vocab: Optional[int] = None, contrast=None, slots: bool = False) -> SelectionPlan:
+                       guidance=None, vocab: Optional[int] = None, contrast=None, slots: bool = False,
+                       speculate=None) -> SelectionPlan:
         """The SelectionPlan of the public selection keywords (forward's), checked: the one place that calls the normalisers
         below and that refuses what beam search and contrastive search (``contrast`` = (top_k, penalty_alpha)) are not combined
         with.  A plan that is already built comes back as it is, so a loop builds one and passes ``plan=`` on every call.
@@ -283,6 +290,17 @@ class TokenSelection:
                             ("token log-probabilities are", logprobs), ("a constraint is", constraint), ("guidance is", guidance)):
             if contrast is not None and given is not None:
                 raise NotImplementedError(f"{what} not combined with contrastive search")
+        # ``speculate`` = (T, max_ngram): speculative greedy decoding (DESIGN.md "Speculative decoding") -- greedy selection under
+        # per-row stopping by eos ids; everything else would have to be applied per fed row, and is a follow-up
+        if speculate is not None:
+            for what, given in (("sampled selection is", sampling), ("beam search is", beam), ("logits processors are", processors),
+                                ("token log-probabilities are", logprobs), ("a constraint is", constraint), ("guidance is", guidance),
+                                ("contrastive search is", contrast), ("a slot session is", True if slots else None)):
+                if given is not None:
+                    raise NotImplementedError(f"{what} not combined with speculative decoding yet")
+            if stop is None or tuple(stop.get("stop_seqs", ())):
+                raise NotImplementedError("speculative decoding stops per row on eos ids: it needs stop= and takes no stop sequences yet")
+            return SelectionPlan(cls.speculate_mode(speculate), stop=cls.stop_mode(stop), vocab=vocab).keyed()
         mode = cls.sample_mode(sampling)
         if isinstance(mode, tuple) and mode[:1] == ("rows",) and any(v is not None for v in (beam, guidance, contrast)):
             raise NotImplementedError("per-row sampler settings are not combined with beam search, contrastive search or guidance")
@@ -312,6 +330,16 @@ class TokenSelection:
                 raise ValueError(f'the warp selection mode is ("warp", temperature, top_k, top_p, min_p), got {sampling!r}')
             return ("warp", float(sampling[1]), int(sampling[2]), float(sampling[3]), float(sampling[4]))
         return (float(sampling[0]), int(sampling[1]), float(sampling[2]))
+
+    @staticmethod
+    def speculate_mode(speculate):
+        """("speculate", T, max_ngram): the token-selection mode (and graph key: both are launch arguments) of speculative greedy
+        decoding, from (T, max_ngram) -- T rows per sequence and step, 2 to 8; n-grams of at most max_ngram tokens, 1 to 16."""
+        T, n = speculate
+        for v, lo, hi, what in ((T, 2, 8, "T (rows per sequence and step)"), (n, 1, 16, "max_ngram")):
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+                raise ValueError(f"speculative decoding takes {what} in [{lo}, {hi}], got {v!r}")
+        return ("speculate", T, n)
 
     @staticmethod
     def contrast_mode(contrast, vocab: Optional[int] = None):
@@ -377,8 +405,10 @@ class TokenSelection:
             cache.eos = int(eos_token)
             cache._drop_graphs()
         cache.sample_state.copy_(torch.tensor([0, -1], dtype=torch.int32), non_blocking=True)
-        if seed is not None and not plan.is_rows:
+        if seed is not None and not plan.is_rows and not plan.is_speculate:
             cache.seed.fill_(int(seed) & 0x7fffffffffffffff)
+        if plan.is_speculate:                      # its own decode state (B * T rows), kept apart from the plain step's
+            return self._arm_speculate(out, logits, cache, eos_token, seed, plan)
         st = self._ensure_decode_state(cache)      # the first token lands where the decode steps read it back
         if plan.is_beam:
             self._arm_beam(cache, st, plan.mode)
@@ -404,6 +434,50 @@ class TokenSelection:
         # step 0 of the rules runs on a copy: the caller's .logits stay raw
         out["next_token"] = self.select_token(logits.clone() if plan.rewrites_logits else logits, cache, plan, out=st.token, raw=logits)
         out["eos_state"] = cache.sample_state
+
+    def _arm_speculate(self, out: LMOutput, logits, cache: KVCache, eos_token, spec, plan: SelectionPlan):
+        """generate(), speculative: token 0 selected from the prefill logits and the first drafts made by the arming call of the
+        bookkeeping launch (ops.spec_finish, arm=True).  ``spec`` (in place of a seed, which greedy selection has none of): dict(limit
+        = max_steps, lookup = None or B lists of token ids).  The cache turns ragged -- the rows advance by different amounts --,
+        the state of the T-row step lives in cache.spec[T] (_ensure_spec_state)."""
+        T, n = plan.mode[1:3]
+        if not isinstance(spec, dict) or "limit" not in spec:
+            raise ValueError("a speculative plan takes dict(limit=max_steps, lookup=None or one id list per row) as seed=")
+        if plan.stop is None or int(eos_token) != plan.stop[0][0]:
+            raise ValueError("speculative decoding pads with the first eos id: eos_token must be the plan's first eos id")
+        if not cache.ragged:
+            cache.set_rows(cache.rows_pos())
+        st = self._ensure_spec_state(cache, T)
+        if st.refusal is not None:
+            raise NotImplementedError(st.refusal)
+        limit, B, dev = int(spec["limit"]), cache.B, cache.k.device
+        # rows never pass their prompt + limit, and a step writes T positions from there: inside the cache, or refused here (the
+        # host mirror cache.pos only bounds the positions from above until the loop ends)
+        if limit < 0 or int(cache.rows_pos().max()) + limit + T > cache.Smax:
+            raise ValueError(f"KV cache too small (Smax={cache.Smax}) for {limit} tokens of T = {T} rows: pass cache_hint = max_steps + T")
+        rows = spec.get("lookup") or [[] for _ in range(B)]
+        if len(rows) != B:
+            raise ValueError(f"lookup has {len(rows)} rows, the cache {B}")
+        if any(not 0 <= int(t) < self.V for q in rows for t in q):
+            raise ValueError(f"lookup ids must be token ids in [0, {self.V})")
+        longest = max(len(q) for q in rows)
+        if longest > st.lookup.shape[1]:             # grown, never shrunk: its address and width are launch arguments
+            st.lookup = torch.zeros(B, ops.ceil_to(longest, 256), dtype=torch.int32, device=dev)
+            st.graphs.clear()
+        if longest:
+            host = torch.zeros(B, longest, dtype=torch.int32)
+            for b, q in enumerate(rows):
+                host[b, :len(q)] = torch.tensor([int(t) for t in q], dtype=torch.int32)
+            st.lookup[:, :longest].copy_(host, non_blocking=True)
+        st.lookup_len.copy_(torch.tensor([len(q) for q in rows], dtype=torch.int32), non_blocking=True)
+        for t in (st.n_draft, st.count, st.stats):
+            t.zero_()
+        st.limit, st.armed = limit, True
+        plan.arm(cache, st, first=True)
+        ops.argmax(logits, out=st.token[:B])
+        ops.spec_finish(st.ids.view(B, T), st.n_draft, st.token, cache.history, st.count, cache.finish, cache.stop_table,
+                        len(plan.stop[0]), limit, st.lookup, st.lookup_len, st.stats, cache.sample_state, T - 1, n, self.V, arm=True)
+        out["next_token"], out["eos_state"] = st.token[:B], cache.sample_state
 
     @staticmethod
     def beam_mode(beam):
