@@ -115,7 +115,8 @@ const char* mg_version(void);
  *      mg_logits_process_constrained_slots_f32 and mg_token_logprobs_slots_f32 (nothing moved, no revision bump: a package that
  *      binds them names the missing symbol when it meets an older library).  Per-request sampling: added mg_sample_rows_f32 and
  *      MG_SAMPLE_ROW_BYTES, in the same way.  Speculative decoding: added mg_attn_decode_chunk_bf16,
- *      mg_decode_attn_gemv_chunk_bf16 and mg_spec_finish, in the same way. */
+ *      mg_decode_attn_gemv_chunk_bf16 and mg_spec_finish, in the same way.  Speculative decoding for sampled rows and stop
+ *      sequences: added mg_sample_chunk_f32 and mg_spec_finish_seq, in the same way. */
 #define MG_ABI_VERSION 27
 int32_t mg_abi_version(void);
 const char* mg_last_error(void);
@@ -156,7 +157,7 @@ const char* mg_last_error(void);
  *   mg_slots_admit_bf16, _at_bf16,           state[0] (any value)                       ring column (state[0] - 1) mod cols
  *   mg_slots_admit_shared_bf16               first_token[j] (any value)                 stored and compared, never an index.  Rows, slots, lengths,
  *                                                                                       offsets: host arguments, validated before the launch
- *   mg_spec_finish                           count[b]  ([0, history_cols])              SKIP row b whole: nothing of it is written, it holds no loop open
+ *   mg_spec_finish, mg_spec_finish_seq       count[b]  ([0, history_cols])              SKIP row b whole: nothing of it is written, it holds no loop open
  *                                            n_draft[b]  ([0, min(T, token_stride) - 1])  CLAMP; lookup_len[b] CLAMP into [0, lookup_cols]
  *                                            ids, tokens, lookup entries (any value)     compared and stored, never an index; a draft id outside
  *                                                                                       [0, vocab) ends the draft in front of it
@@ -175,6 +176,10 @@ const char* mg_last_error(void);
  *                                                                                       untouched, no logit read); the counter is any value
  *                                            record r of params (any bits)              never an index: temperature not finite > 0 = greedy,
  *                                                                                       top_k < 0 = off, top_p / log_min_p NaN or out of range = off
+ *   mg_sample_chunk_f32                      finish[b][0] >= 0, count[b]                SKIP the T rows of sequence b (token, filtered untouched, no
+ *                                            ([0, history_cols])                        logit read); the counter count[b] + t is any value
+ *                                            n_draft[b]  ([0, T - 1])                   CLAMP; rows t above it are SKIPPED
+ *                                            record b of params (any bits)              as mg_sample_rows_f32
  *   mg_token_logprobs_f32, _rows_f32         token id ([0, V)), row_of[i] ([0, n_rows)) lp = -inf, nothing read through it
  *   mg_kv_reorder_bf16                       parent[b]  ([0, R))                        SKIP row b (it is then neither staged nor overwritten)
  *                                            d_pos  ([0, Smax])                         CLAMP: the number of positions copied
@@ -636,6 +641,25 @@ int mg_sample_warp_f32(const float* logits, int64_t ld, int32_t B, int32_t V, fl
 int mg_sample_rows_f32(const float* logits, int64_t ld, int32_t R, int32_t V, int32_t warp, const void* params,
                        const int32_t* state, const int32_t* slot, const int32_t* finish, int32_t history_cols, int64_t* token,
                        float* filtered, int64_t ld_filtered, void* stream);
+
+/* The selection launch of a speculative step (DESIGN.md "Speculative decoding"): a third source for the same kernel body, both
+ * warp values -- one workgroup per fed row r = b * T + t of logits [B * T, V], enqueue-only, graph-capturable, no allocation, no
+ * scratch.
+ *   params  the table of mg_sample_rows_f32, ONE record per sequence: fed row r reads record b = r / T
+ *   count   int32 [B]: mg_spec_finish's count, read before that launch updates it.  The draw of row r uses counter
+ *           {count[b] + t, 0, 0, 0} under the record's seed: the index token[r] has in sequence b's own stream when the drafts in
+ *           front of it were right, which is the only case mg_spec_finish keeps it in.  T = 1 with count[b] = 0 is the arming
+ *           call's selection from the prefill logits.
+ *   n_draft int32 [B] or NULL (= 0); finish int32 [B][2] and history_cols as mg_spec_finish takes them
+ * Row r is SKIPPED whole -- none of its logits read (they may be NaN), token[r] and filtered row r left alone -- if finish[b][0] >= 0,
+ * count[b] lies outside [0, history_cols], or t > clamp(n_draft[b], 0, T - 1): the rows mg_spec_finish never reads.  For equal
+ * logits bits a live row's token and filtered row are those of mg_sample_rows_f32 on that one row with params[b] and state[0] =
+ * count[b] + t; a greedy record takes the first maximum.  No value of a record, of count or of n_draft forms an address unclamped.
+ * Refused before anything is launched: as mg_sample_rows_f32 (B for R), and T outside [1, 8], B * T > 16, a null count or finish,
+ * history_cols < 0.  (Added without a revision bump, as mg_sample_rows_f32 was.) */
+int mg_sample_chunk_f32(const float* logits, int64_t ld, int32_t B, int32_t T, int32_t V, int32_t warp, const void* params,
+                        const int32_t* count, const int32_t* n_draft, const int32_t* finish, int32_t history_cols, int64_t* token,
+                        float* filtered, int64_t ld_filtered, void* stream);
 int mg_sample_finish(const int64_t* token, int32_t B, int64_t eos, int32_t* state, int32_t* d_pos, int32_t delta,
                      int64_t* history, int64_t ld_history, int32_t history_cols, int32_t* clear, int32_t n_clear,
                      int32_t clear_stride, int32_t pos_stride, void* stream);
@@ -689,6 +713,17 @@ int mg_spec_finish(int64_t* ids, int32_t B, int32_t T, int32_t* n_draft, const i
                    int32_t limit, int32_t* d_pos, const int32_t* lookup, int64_t ld_lookup, int32_t lookup_cols,
                    const int32_t* lookup_len, int32_t* stats, int32_t* state, int32_t num_tokens, int32_t max_ngram, int32_t vocab,
                    void* stream);
+/* mg_spec_finish with stop sequences: the same kernel (mg_spec_finish is it at n_seq = 0).  table is the full MG_STOP_TABLE_INTS
+ * table of mg_sample_finish_rows, n_seq in [0, 16] of its sequences live.  Every emitted token j is recorded at
+ * history[b][count + j], then tested: eos ids first, then every sequence against the tail of history[b][:count + j + 1] -- only this
+ * call's tokens, a sequence longer than that never matches -- the lowest matching index winning with MG_STOP_SEQ | i.  The finishing
+ * token is kept and emission is cut behind it: stop_update's rule token by token.  Drafts are still cut only in front of eos ids; a
+ * draft that completes a sequence is accepted and the row finishes.  (Added without a revision bump.) */
+int mg_spec_finish_seq(int64_t* ids, int32_t B, int32_t T, int32_t* n_draft, const int64_t* token, int32_t token_stride,
+                       int64_t* history, int64_t ld_history, int32_t history_cols, int32_t* count, int32_t* finish,
+                       const int32_t* table, int32_t n_eos, int32_t n_seq, int32_t limit, int32_t* d_pos, const int32_t* lookup,
+                       int64_t ld_lookup, int32_t lookup_cols, const int32_t* lookup_len, int32_t* stats, int32_t* state,
+                       int32_t num_tokens, int32_t max_ngram, int32_t vocab, void* stream);
 
 /* Request streams (ABI 24; DESIGN.md "Request streams"; host statement: magma_amd/sampling.py, slot_update): the bookkeeping of a
  * slot session, in which the row of a finished request is handed to the next request while the other rows keep generating.

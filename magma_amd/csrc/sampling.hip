@@ -42,6 +42,11 @@
 // Per-request sampling (mg_sample_rows_f32; DESIGN.md "Per-request sampling"): both instances once more with S = TableRows -- the
 // same body, every workgroup taking its scalars and seed from its row's record of a device table and drawing at the counter
 // (the row's own token index, 0), which is what row 0 of a one-row flat call draws at.  S = FlatRows is the kernel as it was.
+//
+// Speculative decoding for sampled rows (mg_sample_chunk_f32; DESIGN.md "Speculative decoding"): both instances a third time with
+// S = ChunkRows -- one workgroup per fed row b * T + t of a speculative step, the record of SEQUENCE b, the draw at the counter
+// (count[b] + t, 0): the index the row's token has in b's own stream when the drafts in front of it were right, which is the only
+// case spec_finish_kernel keeps it in.  The rows that kernel never reads are skipped whole.
 #include "common.h"
 #include <type_traits>
 
@@ -148,13 +153,19 @@ struct SampleRow {            // MG_SAMPLE_ROW_BYTES = 32, 16-byte aligned
 };
 static_assert(sizeof(SampleRow) == MG_SAMPLE_ROW_BYTES, "the record of mg_sample_rows_f32");
 struct TableRows { const SampleRow* rows; const int32_t* slot; const int32_t* finish; int hist_cols; };
+// ChunkRows (mg_sample_chunk_f32; DESIGN.md "Speculative decoding"): the selection of a speculative step that fed T rows per
+// sequence.  Workgroup r = b * T + t takes the record of SEQUENCE b and draws at counter (count[b] + t, 0) -- the index the token
+// would have in b's own stream if every draft in front of it was right, which is the only case spec_finish_kernel keeps it in.
+// count is that kernel's count, read before it moves.  The rows it never reads are skipped whole.
+struct ChunkRows { const SampleRow* rows; const int32_t* count; const int32_t* n_draft; const int32_t* finish; int hist_cols, T; };
 
 struct RowScalars { float temperature; int top_k; double top_p, log_min_p; };
 
 template <class P, class S = FlatRows>
 __global__ __launch_bounds__(ST) void sample_kernel(const P p0, const S src) {
   constexpr bool WARP = std::is_same<P, WarpParams>::value;
-  constexpr bool ROWS = std::is_same<S, TableRows>::value;
+  constexpr bool CHUNK = std::is_same<S, ChunkRows>::value;
+  constexpr bool ROWS = std::is_same<S, TableRows>::value || CHUNK;
   // `p`: the row's scalars under the names the body reads -- the launch arguments, or the row's record
   RowScalars p{p0.temperature, p0.top_k, p0.top_p, -(double)INFINITY};
   if constexpr (WARP) p.log_min_p = p0.log_min_p;
@@ -162,7 +173,16 @@ __global__ __launch_bounds__(ST) void sample_kernel(const P p0, const S src) {
   unsigned long long seed = 0ull;
   bool greedy = false;
   if constexpr (ROWS) {
-    if (src.slot) {             // a slot session: idle rows are skipped whole (uniform over the workgroup)
+    int rec = blockIdx.x;
+    if constexpr (CHUNK) {      // a speculative step: the rows spec_finish_kernel never reads are skipped whole (uniform)
+      const int b = blockIdx.x / src.T, t = blockIdx.x % src.T;
+      const int c = src.count[b];
+      if (src.finish[2 * (int64_t)b] >= 0 || c < 0 || c > src.hist_cols) return;
+      const int nd = src.n_draft ? max(0, min(src.n_draft[b], src.T - 1)) : 0;
+      if (t > nd) return;
+      ctr0 = (uint32_t)(c + t);
+      rec = b;
+    } else if (src.slot) {      // a slot session: idle rows are skipped whole (uniform over the workgroup)
       const SlotWin w = slot_window(p0.state, src.slot, src.finish, blockIdx.x, src.hist_cols);
       if (w.n == 0) return;
       ctr0 = (uint32_t)w.n;
@@ -170,7 +190,7 @@ __global__ __launch_bounds__(ST) void sample_kernel(const P p0, const S src) {
       ctr0 = (uint32_t)p0.state[0];
     }
     ctr1 = 0u;
-    const SampleRow r = src.rows[blockIdx.x];
+    const SampleRow r = src.rows[rec];
     // the table is device memory no entry point can look at: a temperature that is not a finite value > 0 selects greedily, a
     // negative top_k is off (nothing below forms an address from a record's value)
     greedy = !(r.temperature > 0.f) || r.temperature == INFINITY;
@@ -594,10 +614,13 @@ __global__ void sample_finish_slots_kernel(int64_t* __restrict__ tok, int B, int
 // Device-resident values never form an address unchecked: n_draft counts as clamped into [0, min(T, token_stride) - 1], lookup_len
 // into [0, lookup_cols]; a row whose count lies outside [0, history_cols] is skipped whole (nothing of it written, it does not hold
 // the loop open); a draft id outside [0, vocab) ends the draft in front of it.
+// Stop sequences (mg_spec_finish_seq; n_seq > 0): every emitted token is tested as sample_finish_rows_kernel tests a step's one
+// token, so a draft that completes a sequence is accepted, the finishing token is kept and emission is cut behind it.  Drafts are
+// still cut only in front of eos ids.  n_seq = 0 is mg_spec_finish.
 struct SpecArgs {
   int64_t* ids; int B, T; int32_t* n_draft; const int64_t* token; int token_stride;
   int64_t* history; int64_t ld_hist; int hist_cols; int32_t* count; int32_t* finish;
-  const int32_t* table; int n_eos, limit; int32_t* d_pos;
+  const int32_t* table; int n_eos, n_seq, limit; int32_t* d_pos;
   const int32_t* lookup; int64_t ld_lookup; int lookup_cols; const int32_t* lookup_len;
   int32_t* stats; int32_t* state; int num_tokens, max_ngram, vocab;
 };
@@ -634,8 +657,8 @@ __global__ __launch_bounds__(256) void spec_finish_kernel(const SpecArgs a) {
         const int64_t t = tk[j];
         h[c + j] = t;
         m = j + 1;
-        for (int e = 0; e < a.n_eos && !code; ++e)
-          if (t == (int64_t)a.table[e]) code = MG_STOP_EOS | e;
+        // stop_update's rule token by token: eos first, then the stop sequences against the tail of this call's c + j + 1 tokens
+        code = stop_row_code(t, h, c + j, c + j + 1, a.hist_cols, a.table, a.n_eos, a.n_seq, a.n_seq > 0);
       }
       if (!code && c + m >= lim) code = MG_STOP_LEN;
       a.count[b] = c + m;
@@ -807,6 +830,36 @@ extern "C" int mg_sample_rows_f32(const float* logits, int64_t ld, int32_t R, in
   return MG_OK;
 }
 
+// The selection launch of a speculative step (DESIGN.md "Speculative decoding"): sample_kernel's two instances a third time, with
+// ChunkRows as the source -- one workgroup per fed row b * T + t, sequence b's record, the draw at counter count[b] + t.  The checks
+// are mg_sample_rows_f32's; the records, count and n_draft are device values the kernel clamps or skips on.
+extern "C" int mg_sample_chunk_f32(const float* logits, int64_t ld, int32_t B, int32_t T, int32_t V, int32_t warp, const void* params,
+                                   const int32_t* count, const int32_t* n_draft, const int32_t* finish, int32_t history_cols,
+                                   int64_t* token, float* filtered, int64_t ld_filtered, void* stream) {
+  const char* who = "mg_sample_chunk_f32";
+  if (B <= 0 || V <= 0 || !logits || ld < V) MG_FAIL(MG_ERR_SHAPE, "%s: bad logits / B / V / ld", who);
+  if (T < 1 || T > 8 || (int64_t)B * T > 16) MG_FAIL(MG_ERR_SHAPE, "%s: need 1 <= T <= 8 and B * T <= 16, got B = %d, T = %d", who, B, T);
+  if (warp != 0 && warp != 1) MG_FAIL(MG_ERR_SHAPE, "%s: warp must be 0 (the reference's filters) or 1 (transformers' sampler)", who);
+  if (!params || !count || !finish) MG_FAIL(MG_ERR_SHAPE, "%s: needs the parameter table, count and the finish record", who);
+  if (!token && !filtered) MG_FAIL(MG_ERR_SHAPE, "%s: nothing to produce (token and filtered are both null)", who);
+  if (history_cols < 0) MG_FAIL(MG_ERR_SHAPE, "%s: history_cols < 0", who);
+  if (filtered && ld_filtered < V) MG_FAIL(MG_ERR_SHAPE, "%s: ld_filtered < V", who);
+  if (!MG_ALIGNED16(params)) MG_FAIL(MG_ERR_ALIGN, "%s: the parameter table must be 16-byte aligned", who);
+  if (((uintptr_t)logits | (uintptr_t)count | (uintptr_t)n_draft | (uintptr_t)finish | (uintptr_t)filtered) & 3)
+    MG_FAIL(MG_ERR_ALIGN, "%s: fp32 / int32 buffers must be 4-byte aligned", who);
+  if ((uintptr_t)token & 7) MG_FAIL(MG_ERR_ALIGN, "%s: the token buffer must be 8-byte aligned", who);
+  const ChunkRows src{(const SampleRow*)params, count, n_draft, finish, history_cols, T};
+  const SampleParams p{logits, ld, V, 1.0f, 0, 0.0, nullptr, nullptr, token, filtered, ld_filtered};
+  if (warp) {
+    const WarpParams w{p, -(double)INFINITY};
+    hipLaunchKernelGGL((sample_kernel<WarpParams, ChunkRows>), dim3(B * T), dim3(ST), 0, (hipStream_t)stream, w, src);
+  } else {
+    hipLaunchKernelGGL((sample_kernel<SampleParams, ChunkRows>), dim3(B * T), dim3(ST), 0, (hipStream_t)stream, p, src);
+  }
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
 extern "C" int mg_sample_finish(const int64_t* token, int32_t B, int64_t eos, int32_t* state, int32_t* d_pos, int32_t delta,
                                 int64_t* history, int64_t ld_history, int32_t history_cols, int32_t* clear, int32_t n_clear,
                                 int32_t clear_stride, int32_t pos_stride, void* stream) {
@@ -855,12 +908,11 @@ extern "C" int mg_sample_finish_slots(int64_t* token, int32_t B, int32_t* state,
   return MG_OK;
 }
 
-extern "C" int mg_spec_finish(int64_t* ids, int32_t B, int32_t T, int32_t* n_draft, const int64_t* token, int32_t token_stride,
-                              int64_t* history, int64_t ld_history, int32_t history_cols, int32_t* count, int32_t* finish,
-                              const int32_t* table, int32_t n_eos, int32_t limit, int32_t* d_pos, const int32_t* lookup,
-                              int64_t ld_lookup, int32_t lookup_cols, const int32_t* lookup_len, int32_t* stats, int32_t* state,
-                              int32_t num_tokens, int32_t max_ngram, int32_t vocab, void* stream) {
-  const char* who = "mg_spec_finish";
+static int spec_finish_launch(const char* who, int64_t* ids, int32_t B, int32_t T, int32_t* n_draft, const int64_t* token,
+                              int32_t token_stride, int64_t* history, int64_t ld_history, int32_t history_cols, int32_t* count,
+                              int32_t* finish, const int32_t* table, int32_t n_eos, int32_t n_seq, int32_t limit, int32_t* d_pos,
+                              const int32_t* lookup, int64_t ld_lookup, int32_t lookup_cols, const int32_t* lookup_len,
+                              int32_t* stats, int32_t* state, int32_t num_tokens, int32_t max_ngram, int32_t vocab, void* stream) {
   if (!ids || !n_draft || !token || !history || !count || !finish || !table || !lookup_len || !stats || !state || (lookup_cols > 0 && !lookup))
     MG_FAIL(MG_ERR_SHAPE, "%s: null pointer", who);
   if (B < 1 || B > SPEC_MAX_ROWS || T < 2 || T > 8 || B * T > 16) MG_FAIL(MG_ERR_SHAPE, "%s: need 2 <= T <= 8 and B * T <= 16, got B = %d, T = %d", who, B, T);
@@ -869,6 +921,7 @@ extern "C" int mg_spec_finish(int64_t* ids, int32_t B, int32_t T, int32_t* n_dra
   if (lookup_cols < 0 || ld_lookup < lookup_cols) MG_FAIL(MG_ERR_SHAPE, "%s: bad lookup geometry", who);
   if ((int64_t)lookup_cols + history_cols > 0x7fffff00) MG_FAIL(MG_ERR_SHAPE, "%s: lookup_cols + history_cols must stay below 2^31", who);
   if (n_eos < 1 || n_eos > MG_STOP_MAX_EOS) MG_FAIL(MG_ERR_SHAPE, "%s: need 1 <= n_eos <= %d, got %d", who, MG_STOP_MAX_EOS, n_eos);
+  if (n_seq < 0 || n_seq > MG_STOP_MAX_SEQ) MG_FAIL(MG_ERR_SHAPE, "%s: need 0 <= n_seq <= %d, got %d", who, MG_STOP_MAX_SEQ, n_seq);
   if (num_tokens < 1 || num_tokens > T - 1 || max_ngram < 1 || max_ngram > SPEC_MAX_NGRAM)
     MG_FAIL(MG_ERR_SHAPE, "%s: need 1 <= num_tokens <= T - 1 and 1 <= max_ngram <= %d, got %d / %d", who, SPEC_MAX_NGRAM, num_tokens, max_ngram);
   if (limit < 0 || vocab < 1) MG_FAIL(MG_ERR_SHAPE, "%s: need limit >= 0 and vocab >= 1", who);
@@ -876,11 +929,32 @@ extern "C" int mg_spec_finish(int64_t* ids, int32_t B, int32_t T, int32_t* n_dra
        (uintptr_t)lookup_len | (uintptr_t)stats | (uintptr_t)state) & 3)
     MG_FAIL(MG_ERR_ALIGN, "%s: int32 buffers must be 4-byte aligned", who);
   if (((uintptr_t)ids | (uintptr_t)token | (uintptr_t)history) & 7) MG_FAIL(MG_ERR_ALIGN, "%s: token buffers must be 8-byte aligned", who);
-  const SpecArgs a{ids, B, T, n_draft, token, token_stride, history, ld_history, history_cols, count, finish, table, n_eos, limit, d_pos,
-                   lookup, ld_lookup, lookup_cols, lookup_len, stats, state, num_tokens, max_ngram, vocab};
+  const SpecArgs a{ids, B, T, n_draft, token, token_stride, history, ld_history, history_cols, count, finish, table, n_eos, n_seq, limit,
+                   d_pos, lookup, ld_lookup, lookup_cols, lookup_len, stats, state, num_tokens, max_ngram, vocab};
   hipLaunchKernelGGL(spec_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
   MG_CHECK_LAUNCH();
   return MG_OK;
+}
+
+extern "C" int mg_spec_finish(int64_t* ids, int32_t B, int32_t T, int32_t* n_draft, const int64_t* token, int32_t token_stride,
+                              int64_t* history, int64_t ld_history, int32_t history_cols, int32_t* count, int32_t* finish,
+                              const int32_t* table, int32_t n_eos, int32_t limit, int32_t* d_pos, const int32_t* lookup,
+                              int64_t ld_lookup, int32_t lookup_cols, const int32_t* lookup_len, int32_t* stats, int32_t* state,
+                              int32_t num_tokens, int32_t max_ngram, int32_t vocab, void* stream) {
+  return spec_finish_launch("mg_spec_finish", ids, B, T, n_draft, token, token_stride, history, ld_history, history_cols, count, finish,
+                            table, n_eos, 0, limit, d_pos, lookup, ld_lookup, lookup_cols, lookup_len, stats, state, num_tokens,
+                            max_ngram, vocab, stream);
+}
+
+// mg_spec_finish with stop sequences: `table` is the full MG_STOP_TABLE_INTS table of mg_sample_finish_rows, n_seq of its sequences live.
+extern "C" int mg_spec_finish_seq(int64_t* ids, int32_t B, int32_t T, int32_t* n_draft, const int64_t* token, int32_t token_stride,
+                                  int64_t* history, int64_t ld_history, int32_t history_cols, int32_t* count, int32_t* finish,
+                                  const int32_t* table, int32_t n_eos, int32_t n_seq, int32_t limit, int32_t* d_pos,
+                                  const int32_t* lookup, int64_t ld_lookup, int32_t lookup_cols, const int32_t* lookup_len,
+                                  int32_t* stats, int32_t* state, int32_t num_tokens, int32_t max_ngram, int32_t vocab, void* stream) {
+  return spec_finish_launch("mg_spec_finish_seq", ids, B, T, n_draft, token, token_stride, history, ld_history, history_cols, count,
+                            finish, table, n_eos, n_seq, limit, d_pos, lookup, ld_lookup, lookup_cols, lookup_len, stats, state,
+                            num_tokens, max_ngram, vocab, stream);
 }
 
 // The admission entry points: the checks and the one launch.

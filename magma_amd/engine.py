@@ -1118,13 +1118,19 @@ class LMEngine(TokenSelection):
     def _spec_step(self, cache: KVCache, st, plan: SelectionPlan):
         """Enqueue one speculative step (graph-capturable): the B * T rows st.ids -- per sequence its last emitted token and its
         drafts -- through the blocks against the cache of B rows (chunk attention: row t of a sequence attends up to its own
-        position), the argmax of every row, and the bookkeeping launch that accepts, records, advances and drafts again."""
+        position), the selection of every row -- its argmax, or under a sampled plan (plan.spec_rows) the chunk selection: fed row
+        b * T + t under sequence b's record at the counter count[b] + t, the rows the bookkeeping never reads skipped --, and the
+        bookkeeping launch that accepts, records, advances and drafts again (with stop sequences: mg_spec_finish_seq)."""
         B, T = cache.B, st.T
         self._step_logits(cache, st, st.ids)
-        ops.argmax(st.logits[:, : self.V], out=st.token)
+        if plan.spec_rows is None:
+            ops.argmax(st.logits[:, : self.V], out=st.token)
+        else:
+            ops.sample_chunk(st.logits[:, : self.V], T, st.sample_rows, st.count, cache.finish, n_draft=st.n_draft,
+                             history_cols=cache.history.shape[1], warp=plan.spec_rows, out=st.token)
         ops.spec_finish(st.ids.view(B, T), st.n_draft, st.token, cache.history, st.count, cache.finish, cache.stop_table,
                         len(plan.stop[0]), st.limit, st.lookup, st.lookup_len, st.stats, cache.sample_state, T - 1, plan.mode[2],
-                        self.V, cache.d_pos)
+                        self.V, cache.d_pos, **(dict(n_seq=len(plan.stop[1])) if plan.stop[1] else {}))
 
     # One method per block kind (_block_kind): x -> xn for layer li.  ``src`` holds the block's weight-streaming operands: the
     # layer itself, or its e4m3 / MXFP4 copies (ly.w8 / ly.w4) under W8A16 / W4A16 -- the same launches.  On a ragged cache (pos_stride 1) every
@@ -1318,6 +1324,9 @@ class LMEngine(TokenSelection):
             st.packs_gen = self._packs_gen
             z = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)  # noqa: E731
             st.n_draft, st.count, st.lookup_len, st.stats, st.lookup = z(B), z(B), z(B), z(B, 3), z(B, 0)
+            # the sequences' sampler records of a sampled speculative call (ops.sample_rows_table; greedy until a call writes its
+            # own): the table's address is a launch argument of the captured step, its contents are not
+            st.sample_rows = torch.zeros(B, ops.SAMPLE_ROW_BYTES, dtype=torch.uint8, device=dev)
             st.limit, st.armed = 0, False
             cache.spec[T] = st
         return st

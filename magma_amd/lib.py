@@ -139,6 +139,10 @@ SYMBOLS = {
                                  _vp, _vp, _i32, _i32, _i32, _vp]),
     "mg_sample_finish_slots": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i64, _vp,
                                          _vp, _vp]),
+    # speculative decoding for sampled rows and stop sequences (added under ABI 27 without a bump, as the entries above)
+    "mg_sample_chunk_f32": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _vp]),
+    "mg_spec_finish_seq": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i64,
+                                     _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "mg_slots_admit_bf16": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp]),
     "mg_slots_admit_at_bf16": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,

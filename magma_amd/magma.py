@@ -326,8 +326,10 @@ class Magma(nn.Module):
         ``seed`` / ``temperature`` / ``top_k`` / ``top_p`` / ``min_p`` may each be a sequence of B values: every row then samples
         under its own settings and seed and equals its one-row call (see sampling.generate, per-row sampling).
         ``prompt_lookup_num_tokens`` = k in [1, 7] / ``max_matching_ngram_size`` / ``lookup_ids`` / ``return_speculation``:
-        speculative greedy decoding -- every step verifies k prompt-lookup drafts per row beside its newest token and keeps what the
-        model agrees with; the output is the per-row greedy call's, token for token (see sampling.generate)."""
+        speculative decoding -- every step verifies k prompt-lookup drafts per row beside its newest token and keeps what the
+        model agrees with; the output is the per-row greedy call's, token for token.  With ``temperature != 0`` (scalars stand for
+        every row) or per-row settings it is seed-exact: row b equals ``generate(row_b, ..., seed=s_b)`` alone; ``stop_sequences``
+        apply as in the plain call (see sampling.generate)."""
         torch.cuda.set_device(self.device)
         return generate(self, embeddings=embeddings, max_steps=max_steps, temperature=temperature, top_k=top_k,
                         top_p=top_p, decode=decode, stop_on_eos=stop_on_eos, seed=seed, eos_check_every=eos_check_every,

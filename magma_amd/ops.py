@@ -932,6 +932,36 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, state: torch.Tensor,
     return out
 
 
+def sample_chunk(logits: torch.Tensor, T: int, params: torch.Tensor, count: torch.Tensor, finish: torch.Tensor,
+                 n_draft: Optional[torch.Tensor] = None, history_cols: int = 0, warp: bool = False,
+                 out: Optional[torch.Tensor] = None, filtered: Optional[torch.Tensor] = None, want_token: bool = True):
+    """The selection launch of a speculative step (mg_sample_chunk_f32; DESIGN.md "Speculative decoding"): ``logits`` [B * T, V]
+    holds T fed rows per sequence, ``params`` (sample_rows_table) ONE record per sequence.  Fed row b * T + t is selected under
+    record b at the Philox counter (``count[b]`` + t, 0) -- what ``sample_rows`` selects on that row alone at ``state[0] =
+    count[b] + t``.  Rows of a finished sequence (``finish[b, 0] >= 0``), of a sequence whose count lies outside
+    ``[0, history_cols]`` and rows t > ``n_draft[b]`` (None: 0) are skipped whole: no logit read, ``out`` and ``filtered`` left
+    alone.  ``T=1`` with a zero count is the arming call's selection.  Enqueue-only."""
+    _need_gpu(logits, params, count, finish, n_draft, out, filtered)
+    assert logits.dtype == torch.float32 and logits.ndim == 2 and logits.stride(1) == 1
+    R, V = logits.shape
+    T = int(T)
+    assert T >= 1 and R % T == 0
+    B = R // T
+    assert params.dtype == torch.uint8 and params.is_contiguous() and params.shape == (B, SAMPLE_ROW_BYTES)
+    for t, n in ((count, B), (finish, 2 * B), (n_draft, B)):
+        assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n)
+    if want_token and out is None:
+        out = torch.empty(R, dtype=torch.int64, device=logits.device)
+    if want_token:
+        assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() >= R
+    if filtered is not None:
+        assert filtered.dtype == torch.float32 and filtered.shape == logits.shape and filtered.stride(1) == 1
+    check(L.load().mg_sample_chunk_f32(logits.data_ptr(), logits.stride(0), B, T, V, int(bool(warp)), params.data_ptr(), _p(count),
+                                       _p(n_draft), _p(finish), int(history_cols), _p(out) if want_token else None, _p(filtered),
+                                       0 if filtered is None else filtered.stride(0), _stream()), "mg_sample_chunk_f32")
+    return out
+
+
 def sample_finish(token: torch.Tensor, eos: int, state: torch.Tensor, d_pos: Optional[torch.Tensor] = None, delta: int = 1,
                   history: Optional[torch.Tensor] = None, clear: Optional[torch.Tensor] = None, clear_stride: int = 1, *,
                   pos_stride: int = 0):
@@ -998,12 +1028,14 @@ def sample_finish_rows(token: torch.Tensor, state: torch.Tensor, table: torch.Te
 def spec_finish(ids: torch.Tensor, n_draft: torch.Tensor, token: torch.Tensor, history: torch.Tensor, count: torch.Tensor,
                 finish: torch.Tensor, table: torch.Tensor, n_eos: int, limit: int, lookup: torch.Tensor, lookup_len: torch.Tensor,
                 stats: torch.Tensor, state: torch.Tensor, num_tokens: int, max_ngram: int, vocab: int,
-                d_pos: Optional[torch.Tensor] = None, *, arm: bool = False):
+                d_pos: Optional[torch.Tensor] = None, *, arm: bool = False, n_seq: Optional[int] = None):
     """The bookkeeping launch of a speculative step (mg_spec_finish; host statement: sampling.speculate_update): accepts the
     longest prefix of the drafts ``ids[b, 1:1 + n_draft[b]]`` that the step's argmaxes ``token`` (B * T) agree with, records the
     emitted tokens in ``history`` / ``count`` / ``finish`` / ``stats``, advances ``d_pos`` by their number and writes the next
     step's ``ids`` and ``n_draft`` by the prompt-lookup rule over ``lookup[b, :lookup_len[b]] ++ history[b, :count[b]]``.
-    ``arm=True``: ``token`` holds the prefill's B selected tokens, nothing was fed (``d_pos`` is left alone).  Enqueue-only."""
+    ``arm=True``: ``token`` holds the prefill's B selected tokens, nothing was fed (``d_pos`` is left alone).  ``n_seq`` (not
+    None: mg_spec_finish_seq): every emitted token is also tested against the first ``n_seq`` stop sequences of ``table``, as
+    sample_finish_rows tests a step's token.  Enqueue-only."""
     _need_gpu(ids, n_draft, token, history, count, finish, table, lookup, lookup_len, stats, state, d_pos)
     B, T = ids.shape
     assert ids.dtype == torch.int64 and ids.is_contiguous() and token.dtype == torch.int64 and token.is_contiguous()
@@ -1016,12 +1048,15 @@ def spec_finish(ids: torch.Tensor, n_draft: torch.Tensor, token: torch.Tensor, h
     assert table.dtype == torch.int32 and table.is_contiguous() and table.numel() >= STOP_TABLE_INTS
     if d_pos is not None:
         _pos_stride(d_pos, B, 1)
-    check(L.load().mg_spec_finish(ids.data_ptr(), B, T, n_draft.data_ptr(), token.data_ptr(), 1 if arm else T, history.data_ptr(),
-                                  history.stride(0), history.shape[1], count.data_ptr(), finish.data_ptr(), table.data_ptr(),
-                                  int(n_eos), int(limit), None if arm else _p(d_pos), lookup.data_ptr() if lookup.shape[1] else None,
-                                  lookup.stride(0) if lookup.shape[1] else 0, lookup.shape[1], lookup_len.data_ptr(),
-                                  stats.data_ptr(), state.data_ptr(), int(num_tokens), int(max_ngram), int(vocab), _stream()),
-          "mg_spec_finish")
+    head = (ids.data_ptr(), B, T, n_draft.data_ptr(), token.data_ptr(), 1 if arm else T, history.data_ptr(), history.stride(0),
+            history.shape[1], count.data_ptr(), finish.data_ptr(), table.data_ptr(), int(n_eos))
+    tail = (int(limit), None if arm else _p(d_pos), lookup.data_ptr() if lookup.shape[1] else None,
+            lookup.stride(0) if lookup.shape[1] else 0, lookup.shape[1], lookup_len.data_ptr(), stats.data_ptr(), state.data_ptr(),
+            int(num_tokens), int(max_ngram), int(vocab), _stream())
+    if n_seq is None:
+        check(L.load().mg_spec_finish(*head, *tail), "mg_spec_finish")
+    else:
+        check(L.load().mg_spec_finish_seq(*head, int(n_seq), *tail), "mg_spec_finish_seq")
 
 
 STOP_LEN = 0x300                                                        # include/magma_hip.h MG_STOP_LEN: the budget ran out

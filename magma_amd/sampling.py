@@ -799,6 +799,11 @@ def finish_from_record(record, n_gen: int) -> Finish:
 MAX_SPEC_TOKENS, MAX_SPEC_NGRAM, MAX_SPEC_ROWS = 7, 16, 16
 
 
+class EngineOnlySpeculation(NotImplementedError, ValueError):
+    """Speculation asked of an LM object without the HIP engine for something only the engine's launches do (sampled rows, stop
+    sequences): not implemented for that LM, and a value the call cannot take -- callers that catch either class see it."""
+
+
 class Speculation(NamedTuple):
     """What speculation did for every row of a generate() call (``return_speculation=True``): CPU int64 [B] each."""
     steps: torch.Tensor         # model calls in which the row was open, the prefill included
@@ -828,24 +833,28 @@ def prompt_lookup(ids, num_tokens: int, max_ngram: int, eos_ids=(), vocab: int =
 
 
 def speculate_update(ids, n_draft, token, history, count, finish, pos, stats, lookup, lookup_len, state, *, num_tokens: int,
-                     max_ngram: int, eos_ids, limit: int, arm: bool = False, vocab: int = None):
+                     max_ngram: int, eos_ids, limit: int, arm: bool = False, vocab: int = None, stop_seqs=()):
     """The bookkeeping of a speculative step, host statement (the device kernel is csrc/sampling.hip, spec_finish_kernel), IN
     PLACE on CPU tensors.  The step fed ``ids`` (B, T) int64 -- ids[b, 0] the row's last emitted token, ids[b, 1:1 + n_draft[b]]
     its drafts -- and ``token`` (B * T,) int64 holds the argmax of every fed row (``arm``: (B,), the prefill's selected tokens;
     nothing was fed, ``n_draft`` counts as 0 and ``pos`` stays).  Per row b with finish[b, 0] < 0:
       accept  a = the leading j in [1, n_draft[b]] with ids[b, j] == token[b * T + j - 1]; token[b * T + 0 .. a] are emitted, cut
               behind the first of ``eos_ids`` among them (finish[b] = (count, STOP_EOS | i)) and at min(limit, history columns) -
-              count[b] (finish[b] = (count, STOP_LEN));
+              count[b] (finish[b] = (count, STOP_LEN)).  ``stop_seqs``: stop_update's rule token by token -- emitted token j is
+              recorded, tested against the eos ids first, then history[b, :count[b] + j + 1] against every sequence (one longer
+              than that cannot match; the lowest matching index i wins: STOP_SEQ | i); the finishing token is kept, emission is
+              cut behind it.  A draft that completes a sequence is accepted like any other: drafts are cut in front of eos ids only;
       record  the m emitted tokens go to history[b, count[b]:], count[b] += m, pos[b] += m, stats[b] += (1, n_draft, a);
       draft   a row still open: ids[b, 0] = its last emitted token, ids[b, 1:] = prompt_lookup(lookup[b, :lookup_len[b]] ++
               history[b, :count[b]], num_tokens, max_ngram, eos_ids), n_draft[b] their number, unused entries repeat ids[b, 0].
     A finished row (now or earlier) is frozen: n_draft[b] = 0, ids[b] = eos_ids[0], nothing else of it moves.  state[1] latches
     state[0] when no row is open; state[0] += 1.  Degenerate values: n_draft counts as clamped into [0, T - 1] (0 when arming),
     lookup_len into [0, lookup columns]; a row whose count lies outside [0, history columns] is skipped whole."""
-    from .ops import STOP_EOS, STOP_LEN
+    from .ops import STOP_EOS, STOP_LEN, STOP_SEQ
     B, T = ids.shape
     cols, lcols, ts = history.shape[1], lookup.shape[1], 1 if arm else T
     eos_ids = [int(e) for e in eos_ids]
+    stop_seqs = [[int(t) for t in q] for q in stop_seqs]
     any_open = False
     for b in range(B):
         c = int(count[b])
@@ -866,6 +875,12 @@ def speculate_update(ids, n_draft, token, history, count, finish, pos, stats, lo
             history[b, c + j], m = tk[j], j + 1
             if tk[j] in eos_ids:
                 code = STOP_EOS | eos_ids.index(tk[j])
+                continue
+            n = c + j + 1
+            for i, q in enumerate(stop_seqs):
+                if 1 <= len(q) <= n and [int(t) for t in history[b, n - len(q):n]] == q:
+                    code = STOP_SEQ | i
+                    break
         if not code and c + m >= lim:
             code = STOP_LEN
         count[b] = c + m
@@ -1638,7 +1653,7 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     with beam search, contrastive search or guidance.  The selection is the same single launch of the captured step, reading a
     device table (ops.sample_rows).  With scalars only, the call is what it was, bit for bit and launch for launch.
 
-    Speculative greedy decoding (DESIGN.md "Speculative decoding"; ``temperature=0.0``): ``prompt_lookup_num_tokens`` = k in
+    Speculative decoding (DESIGN.md "Speculative decoding"; greedy at ``temperature=0.0``): ``prompt_lookup_num_tokens`` = k in
     [1, 7] makes every token step verify k guessed continuations per row beside the row's newest token -- k + 1 rows per
     sequence ride one weight stream -- and keep the longest prefix the model agrees with, plus the model's own next token: 1 to
     k + 1 tokens per step and row instead of one, token for token the output of ``generate(..., temperature=0.0,
@@ -1651,10 +1666,19 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     takes 1 to 8 ids; layout, padding and ``return_finish`` as there).  ``return_speculation=True`` appends a ``Speculation`` --
     per row the model calls it was open in, the drafts fed and the drafts accepted.  The HIP engine runs the whole step on the
     device (chunk attention, one bookkeeping launch that accepts, records and drafts again); any other LM object runs the host
-    statement row by row.  B * (k + 1) may not exceed 16.  Not yet combined (NotImplementedError) with sampled selection, beam and
-    contrastive search, guidance, the logits processors, ``return_logprobs``, a constraint, stop sequences, ``past_key_values`` /
-    ``return_past_key_values``, ``generate_stream`` / ``choose_stream``.  At ``prompt_lookup_num_tokens=0`` (the default) the call
-    is launch for launch what it was."""
+    statement row by row.  B * (k + 1) may not exceed 16.  ``stop_sequences`` (HIP engine only) apply as in the plain call: every
+    emitted token is tested, a draft that completes a sequence is accepted and the row finishes (``return_finish``: "stop" and
+    the index).
+    Sampled rows (HIP engine only; seed-exact, no rejection sampling): with ``temperature != 0`` or any of ``temperature``,
+    ``top_k``, ``top_p``, ``min_p``, ``seed`` given per row, under either ``sampler``, the call ALWAYS selects by the per-row rule
+    above -- scalars stand for every row, so ``seed=s`` means ``seed=[s] * B`` and ``None`` draws one seed per sampled row -- and
+    fed position t of row b is drawn at the row's own counter (tokens emitted so far + t) under the row's own record: row b is,
+    token for token, ``generate(row_b, ..., seed=s_b)`` alone, and the whole call is the plain per-row sampled call with
+    ``stop_per_row=True``.  Greedy rows (temperature 0) may sit beside sampled ones.  An LM object without the engine is refused
+    (``EngineOnlySpeculation``: a NotImplementedError and a ValueError), ``min_p`` on a greedy row too (ValueError).  Not yet combined (NotImplementedError) with beam and contrastive search,
+    guidance, the logits processors, ``return_logprobs``, a constraint, ``past_key_values`` / ``return_past_key_values``,
+    ``generate_stream`` / ``choose_stream``.  At ``prompt_lookup_num_tokens=0`` (the default) the call is launch for launch what
+    it was."""
     if eos_token is None or (isinstance(eos_token, int) and not eos_token):
         eos_token = model.eos_token
     spec = check_speculation_args(prompt_lookup_num_tokens, max_matching_ngram_size, lookup_ids, return_speculation,
@@ -1705,17 +1729,23 @@ def generate(model, embeddings, max_steps: int = 100, temperature: float = 0.7, 
     continuing = past_key_values is not None or return_past_key_values
     contrast = check_contrastive_args(penalty_alpha, top_k, _logit_count(model))
     if spec is not None:
-        for what, given in (("sampled selection (temperature != 0, per-row sampler settings) is", bool(per_row) or temperature != 0.0),
-                            ("beam search (num_beams > 1 / return_scores=True) is", num_beams > 1 or return_scores),
+        for what, given in (("beam search (num_beams > 1 / return_scores=True) is", num_beams > 1 or return_scores),
                             ("contrastive search (penalty_alpha > 0) is", contrast is not None),
                             ("guidance is", guide is not None), ("the logits processors are", proc is not None),
                             ("token log-probabilities (return_logprobs / top_logprobs) are", n_top is not None),
-                            ("a constraint is", constraint is not None), ("stop sequences are", bool(stop["stop_seqs"])),
+                            ("a constraint is", constraint is not None),
                             ("a KV cache (past_key_values / return_past_key_values) is", continuing)):
             if given:
                 raise NotImplementedError(f"{what} not combined with speculative decoding (prompt_lookup_num_tokens > 0) yet")
+        # a sampled speculative call always selects by the per-row rule: scalars stand for every row (check_row_sampler_args, once
+        # the batch is known).  temperature=0.0 as a scalar stays the greedy call, launch for launch.
+        # A greedy call with stop sequences runs under the same rule with greedy records (the first maximum, mg_argmax_f32's token).
+        sampled = None
+        if per_row or temperature != 0.0 or stop["stop_seqs"]:
+            sampled = dict(row_args if per_row else dict(temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, seed=seed),
+                           sampler=sampler)
         return _generate_speculative(model, embeddings, lengths, max_steps, eos_ids, decode, eos_check_every, stop_on_eos, spec,
-                                     lookup_ids, return_finish, return_speculation)
+                                     lookup_ids, return_finish, return_speculation, stop["stop_seqs"], sampled)
     if contrast is not None:
         for what, given in (("beam search (num_beams > 1 / return_scores=True) is", num_beams > 1 or return_scores),
                             ("the logits processors are", proc is not None),
@@ -1941,9 +1971,10 @@ def _host_loop(model, embeddings, lengths, max_steps, eos_token, seed, every, st
 
 
 def _generate_speculative(model, embeddings, lengths, max_steps, eos_ids, decode, eos_check_every, stop_on_eos, spec, lookup_ids,
-                          return_finish, return_speculation):
+                          return_finish, return_speculation, stop_seqs=(), sampled=None):
     """generate() with prompt_lookup_num_tokens > 0: the checks that need the batch, the device or the host loop, and the
-    per-row tail -- every row's tokens up to its own count, the pad id behind them."""
+    per-row tail -- every row's tokens up to its own count, the pad id behind them.  ``sampled``: None (greedy), or
+    check_row_sampler_args' keywords -- the rows' records then select on the HIP engine (("rows", warp))."""
     embeddings, lengths = prompt_batch(embeddings, lengths, check=False)
     b, s, _ = embeddings.shape
     on_device = getattr(model.lm, "device_token_selection", False)
@@ -1953,9 +1984,23 @@ def _generate_speculative(model, embeddings, lengths, max_steps, eos_ids, decode
         from .engine import LMEngine
         lengths = LMEngine.check_lengths(lengths, b, s)
     pad = eos_ids[0]
+    if sampled is not None:
+        try:
+            rows = check_row_sampler_args(b, **sampled)
+        except ValueError as e:
+            if "min_p applies" in str(e):       # a greedy row of the HIP engine's chunk selection takes its first maximum
+                raise ValueError(f"{e} (the HIP engine's selection launch takes a greedy row's first maximum)") from None
+            raise
+        if not on_device:
+            raise EngineOnlySpeculation(
+                "speculative decoding (prompt_lookup_num_tokens > 0) of sampled rows (temperature != 0 or per-row sampler settings) "
+                "and with stop sequences needs the HIP engine's LM: its selection launch draws every fed row at the sequence's own "
+                "counter, its bookkeeping launch tests every emitted token; not combined with this LM object yet")
+        spec = dict(spec, rows=rows, warp=sampled["sampler"] == "transformers")
     with eval_mode(model):
         loop = _speculate_device_loop if on_device else _speculate_host_loop
-        history, count, record, stats = loop(model, embeddings, lengths, max_steps, eos_ids, poll_every(eos_check_every), spec)
+        history, count, record, stats = loop(model, embeddings, lengths, max_steps, eos_ids, poll_every(eos_check_every), spec,
+                                             stop_seqs)
         n, n_gen = history.shape[1], int(count.max()) if stop_on_eos else max_steps
         tokens = torch.full((b, n_gen), pad, dtype=torch.int64)
         tokens[:, :n] = torch.where(torch.arange(n)[None, :] < count[:, None], history.cpu(), tokens[:, :n])
@@ -1973,16 +2018,17 @@ def _generate_speculative(model, embeddings, lengths, max_steps, eos_ids, decode
 
 def _spec_record(finish) -> torch.Tensor:
     """The loop's finish record (count at which the row finished or -1, code) as finish_from_record reads one: a row that finished
-    on an eos id at count c did so at step c - 1; a row that ran out of its budget, or never finished, ran to the end of the call."""
-    from .ops import STOP_EOS
+    on an eos id or a stop sequence at count c did so at step c - 1; a row that ran out of its budget, or never finished, ran to the
+    end of the call."""
+    from .ops import STOP_EOS, STOP_SEQ
     rec = torch.as_tensor(finish).to(torch.int64).cpu().clone()
-    eos = (rec[:, 0] >= 0) & ((rec[:, 1] & ~0xFF) == STOP_EOS)
+    eos = (rec[:, 0] >= 0) & (((rec[:, 1] & ~0xFF) == STOP_EOS) | ((rec[:, 1] & ~0xFF) == STOP_SEQ))
     rec[:, 0] = torch.where(eos, rec[:, 0] - 1, torch.full_like(rec[:, 0], -1))
     rec[:, 1] = torch.where(eos, rec[:, 1], torch.zeros_like(rec[:, 1]))
     return rec
 
 
-def _speculate_device_loop(model, embeddings, lengths, max_steps, eos_ids, every, spec):
+def _speculate_device_loop(model, embeddings, lengths, max_steps, eos_ids, every, spec, stop_seqs=()):
     """The speculative loop on the HIP engine: one ragged prefill (every row keeps its own position: they advance by different
     amounts) armed with a speculative plan, then steps that feed their own ids back on the device; the host reads the
     all-finished latch every ``every`` steps, and once at the end the token history, the counts, the finish record and the
@@ -1991,13 +2037,19 @@ def _speculate_device_loop(model, embeddings, lengths, max_steps, eos_ids, every
     b, s, _ = embeddings.shape
     T = spec["T"]
     engine = model.lm.engine
-    plan = LMEngine.selection_plan(stop=dict(eos_ids=eos_ids, stop_seqs=()), speculate=(T, spec["max_ngram"]), vocab=engine.V)
+    rows = spec.get("rows")
+    plan = LMEngine.selection_plan(stop=dict(eos_ids=eos_ids, stop_seqs=stop_seqs), speculate=(T, spec["max_ngram"]), vocab=engine.V,
+                                   sampling=None if rows is None else ("rows", spec["warp"]))
+    arm = dict(limit=max_steps, lookup=spec["lookup"])
+    if rows is not None:        # the sequences' records as the host image of the device table (_arm_speculate copies it)
+        from . import ops
+        arm["rows"] = ops.sample_rows_table(*zip(*rows))
     lens = lengths if lengths is not None else torch.full((b,), s, dtype=torch.int64)
     if max_steps < 1:
         return (torch.zeros(b, 0, dtype=torch.int64), torch.zeros(b, dtype=torch.int64), torch.tensor([[-1, 0]] * b).view(b, 2),
                 torch.zeros(b, 3, dtype=torch.int64))
     outputs = model.lm(inputs_embeds=embeddings, use_cache=True, past_key_values=None, cache_hint=max_steps + T, reuse_cache=True,
-                       eos_token=eos_ids[0], seed=dict(limit=max_steps, lookup=spec["lookup"]), plan=plan, lengths=lens)
+                       eos_token=eos_ids[0], seed=arm, plan=plan, lengths=lens)
     past = outputs.past_key_values
     for i in range(max_steps - 1):
         outputs = model.lm(input_ids=None, use_cache=True, past_key_values=past, feed_back=True, plan=plan)
@@ -2008,7 +2060,7 @@ def _speculate_device_loop(model, embeddings, lengths, max_steps, eos_ids, every
     return past.history[:b, :n].cpu(), count, _spec_record(past.finish[:b]), stats
 
 
-def _speculate_host_loop(model, embeddings, lengths, max_steps, eos_ids, every, spec):
+def _speculate_host_loop(model, embeddings, lengths, max_steps, eos_ids, every, spec, stop_seqs=()):
     """The speculative loop over any other LM object, the statement the device loop is compared with: row by row -- a row's
     prompt alone, then its last token and its drafts as ONE (1, 1 + drafts) chunk against its cache --, the greedy token of every
     fed position, speculate_update, and the cache cropped to the accepted length (crop_past)."""
@@ -2023,7 +2075,8 @@ def _speculate_host_loop(model, embeddings, lengths, max_steps, eos_ids, every, 
               lookup_len=torch.tensor([len(q) for q in rows], dtype=torch.int32), state=torch.tensor([0, -1], dtype=torch.int32))
     for r, q in enumerate(rows):
         st["lookup"][r, :len(q)] = torch.tensor(q, dtype=torch.int32)
-    kw = dict(num_tokens=T - 1, max_ngram=spec["max_ngram"], eos_ids=eos_ids, limit=max_steps, vocab=_logit_count(model))
+    kw = dict(num_tokens=T - 1, max_ngram=spec["max_ngram"], eos_ids=eos_ids, limit=max_steps, vocab=_logit_count(model),
+              stop_seqs=stop_seqs)
 
     def update(token, arm):
         speculate_update(st["ids"], st["n_draft"], token, st["history"], st["count"], st["finish"], st["pos"], st["stats"],

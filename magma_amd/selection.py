@@ -138,9 +138,23 @@ class SelectionPlan(NamedTuple):
 
     @property
     def is_speculate(self) -> bool:
-        """Speculative greedy decoding (DESIGN.md "Speculative decoding"): mode ("speculate", T, max_ngram) -- every step runs T rows
-        per sequence, the last emitted token and up to T - 1 prompt-lookup drafts, and keeps the prefix the model agrees with."""
+        """Speculative decoding (DESIGN.md "Speculative decoding"): mode ("speculate", T, max_ngram) -- every step runs T rows
+        per sequence, the last emitted token and up to T - 1 prompt-lookup drafts, and keeps the prefix the model agrees with.
+        Sampled rows: ("speculate", T, max_ngram, ("rows", warp)) -- the selection is the chunk launch over the sequences' records."""
         return isinstance(self.mode, tuple) and self.mode[:1] == ("speculate",)
+
+    @property
+    def spec_rows(self) -> Optional[bool]:
+        """A speculative plan's selection: None (the argmax of every fed row) or ``warp`` of its ("rows", warp) -- every fed row
+        under its SEQUENCE's record (cache.spec[T].sample_rows) at the counter count + t (ops.sample_chunk)."""
+        return self.mode[3][1] if self.is_speculate and len(self.mode) > 3 else None
+
+    @property
+    def spec_launches(self) -> tuple:
+        """The two entry points a speculative step enqueues behind the head: the selection and the bookkeeping."""
+        assert self.is_speculate
+        return ("mg_argmax_f32" if self.spec_rows is None else "mg_sample_chunk_f32",
+                "mg_spec_finish_seq" if self.stop[1] else "mg_spec_finish")     # (stop sequences: under ("rows", warp) only)
 
     @property
     def beam_groups(self) -> tuple:
@@ -290,17 +304,26 @@ class TokenSelection:
                             ("token log-probabilities are", logprobs), ("a constraint is", constraint), ("guidance is", guidance)):
             if contrast is not None and given is not None:
                 raise NotImplementedError(f"{what} not combined with contrastive search")
-        # ``speculate`` = (T, max_ngram): speculative greedy decoding (DESIGN.md "Speculative decoding") -- greedy selection under
-        # per-row stopping by eos ids; everything else would have to be applied per fed row, and is a follow-up
+        # ``speculate`` = (T, max_ngram): speculative decoding (DESIGN.md "Speculative decoding") -- greedy selection, or
+        # ``sampling`` = ("rows", warp): every sequence under its own record, seed-exact -- under per-row stopping by eos ids and stop
+        # sequences; everything else would have to be applied per fed row, and is a follow-up
         if speculate is not None:
-            for what, given in (("sampled selection is", sampling), ("beam search is", beam), ("logits processors are", processors),
+            rows = sampling is not None and tuple(sampling[:1]) == ("rows",)
+            for what, given in (("session-wide sampled selection (pass (\"rows\", warp): the seed-exact rule) is", None if rows else sampling),
+                                ("beam search is", beam), ("logits processors are", processors),
                                 ("token log-probabilities are", logprobs), ("a constraint is", constraint), ("guidance is", guidance),
                                 ("contrastive search is", contrast), ("a slot session is", True if slots else None)):
                 if given is not None:
                     raise NotImplementedError(f"{what} not combined with speculative decoding yet")
-            if stop is None or tuple(stop.get("stop_seqs", ())):
-                raise NotImplementedError("speculative decoding stops per row on eos ids: it needs stop= and takes no stop sequences yet")
-            return SelectionPlan(cls.speculate_mode(speculate), stop=cls.stop_mode(stop), vocab=vocab).keyed()
+            if stop is None:
+                raise NotImplementedError("speculative decoding stops per row: it needs stop=")
+            if tuple(stop.get("stop_seqs", ())) and not rows:
+                # the argmax plan keeps the launches it had (mg_argmax_f32, mg_spec_finish); a greedy call with stop sequences runs
+                # under ("rows", warp) with greedy records -- the first maximum, as mg_argmax_f32 takes it -- and mg_spec_finish_seq
+                raise NotImplementedError('speculative decoding takes stop sequences under the per-row selection mode: pass '
+                                          'sampling=("rows", warp); a record with temperature 0 selects greedily')
+            mode = cls.speculate_mode(speculate) + ((cls.sample_mode(sampling),) if rows else ())
+            return SelectionPlan(mode, stop=cls.stop_mode(stop), vocab=vocab).keyed()
         mode = cls.sample_mode(sampling)
         if isinstance(mode, tuple) and mode[:1] == ("rows",) and any(v is not None for v in (beam, guidance, contrast)):
             raise NotImplementedError("per-row sampler settings are not combined with beam search, contrastive search or guidance")
@@ -437,10 +460,11 @@ class TokenSelection:
 
     def _arm_speculate(self, out: LMOutput, logits, cache: KVCache, eos_token, spec, plan: SelectionPlan):
         """generate(), speculative: token 0 selected from the prefill logits and the first drafts made by the arming call of the
-        bookkeeping launch (ops.spec_finish, arm=True).  ``spec`` (in place of a seed, which greedy selection has none of): dict(limit
-        = max_steps, lookup = None or B lists of token ids).  The cache turns ragged -- the rows advance by different amounts --,
+        bookkeeping launch (ops.spec_finish, arm=True).  ``spec`` (in place of a seed): dict(limit = max_steps, lookup = None or B
+        lists of token ids, rows = a sampled plan's table of the B sequences' records, ops.sample_rows_table).  The cache turns ragged -- the rows advance by different amounts --,
         the state of the T-row step lives in cache.spec[T] (_ensure_spec_state)."""
         T, n = plan.mode[1:3]
+        warp, n_seq = plan.spec_rows, len(plan.stop[1]) if plan.stop is not None and plan.stop[1] else None
         if not isinstance(spec, dict) or "limit" not in spec:
             raise ValueError("a speculative plan takes dict(limit=max_steps, lookup=None or one id list per row) as seed=")
         if plan.stop is None or int(eos_token) != plan.stop[0][0]:
@@ -472,11 +496,22 @@ class TokenSelection:
         st.lookup_len.copy_(torch.tensor([len(q) for q in rows], dtype=torch.int32), non_blocking=True)
         for t in (st.n_draft, st.count, st.stats):
             t.zero_()
+        if warp is not None:                         # the sequences' records, written once per call: the captured step reads the table
+            table = spec.get("rows")
+            if not torch.is_tensor(table) or tuple(table.shape) != tuple(st.sample_rows.shape) or table.dtype != torch.uint8:
+                raise ValueError(f"a sampled speculative plan takes the sequences' table as rows=: uint8 {tuple(st.sample_rows.shape)} "
+                                 "(ops.sample_rows_table)")
+            st.sample_rows.copy_(table, non_blocking=True)
         st.limit, st.armed = limit, True
         plan.arm(cache, st, first=True)
-        ops.argmax(logits, out=st.token[:B])
+        if warp is None:
+            ops.argmax(logits, out=st.token[:B])
+        else:       # the chunk selection at T = 1 over the zeroed counts: token 0 of every sequence, drawn at counter 0
+            ops.sample_chunk(logits, 1, st.sample_rows, st.count, cache.finish, history_cols=cache.history.shape[1], warp=warp,
+                             out=st.token[:B])
         ops.spec_finish(st.ids.view(B, T), st.n_draft, st.token, cache.history, st.count, cache.finish, cache.stop_table,
-                        len(plan.stop[0]), limit, st.lookup, st.lookup_len, st.stats, cache.sample_state, T - 1, n, self.V, arm=True)
+                        len(plan.stop[0]), limit, st.lookup, st.lookup_len, st.stats, cache.sample_state, T - 1, n, self.V, arm=True,
+                        **({} if n_seq is None else dict(n_seq=n_seq)))
         out["next_token"], out["eos_state"] = st.token[:B], cache.sample_state
 
     @staticmethod

@@ -19,6 +19,13 @@ End to end: tokens per second of a 64-token generate() at B = 1 and 2 -- the pla
 times after a warm-up call each, with the acceptance counts of ``Speculation``.  The weights are synthetic: acceptance on real
 prompts is NOT what the no-lookup number shows.
 
+Sampled rows (case "step_sampled"): per (B, T), in the same way, the plain per-row greedy step over B * T rows (b), the plain
+per-row SAMPLED step over B * T rows (e: mg_sample_rows_f32 where mg_argmax_f32 stood), the greedy speculative step (c) and the
+sampled speculative step (f: mg_sample_chunk_f32 where mg_argmax_f32 stood), every record temperature 0.7, top_p 0.9.  The
+expectation to check: f - c exceeds e - b by no more than the larger leg's own window spread.  Case "e2e_sampled": the 64-token call
+with those settings and one seed per row -- the plain per-row sampled call, the speculative call with ``lookup_ids`` = that
+call's own output (the mode is seed-exact, so this is a true ceiling) and with none.
+
 One JSON line per case is printed and appended to --out.  No GPU: the tool fails, it does not fall back."""
 import argparse
 import json
@@ -41,7 +48,7 @@ def main():
     ap.add_argument("--attn-launches", type=int, default=64)
     ap.add_argument("--attn-replays", type=int, default=20)
     ap.add_argument("--tokens", type=int, default=64)
-    ap.add_argument("--skip", default="", help="comma list of parts to leave out: step, attn, e2e")
+    ap.add_argument("--skip", default="", help="comma list of parts to leave out: step, attn, e2e, step_sampled, e2e_sampled")
     ap.add_argument("--out", default=os.path.join("profiles", "speculative_bench.jsonl"))
     args = ap.parse_args()
     skip = set(filter(None, args.skip.split(",")))
@@ -128,6 +135,56 @@ def main():
             os.environ.pop("MAGMA_SPEC_COLAUNCH", None)
             torch.cuda.empty_cache()
 
+        # ---- the sampled step: (b) plain greedy and (e) plain per-row sampled over B * T rows, (c) greedy and (f) sampled speculative
+        for case in ([] if "step_sampled" in skip else args.cases.split(",")):
+            B, T = (int(v) for v in case.split("x"))
+            table = lambda n: ops.sample_rows_table([0.7] * n, [0] * n, [0.9] * n, [0.0] * n, list(range(11, 11 + n)))  # noqa: E731
+            plans = {"b_plain_BT": LMEngine.selection_plan(stop=stop, vocab=eng.V),
+                     "e_plain_rows_BT": LMEngine.selection_plan(stop=stop, sampling=("rows", False), vocab=eng.V),
+                     "c_speculative": LMEngine.selection_plan(stop=stop, speculate=(T, 2), vocab=eng.V),
+                     "f_speculative_rows": LMEngine.selection_plan(stop=stop, speculate=(T, 2), sampling=("rows", False), vocab=eng.V)}
+            seeds = {"b_plain_BT": {}, "e_plain_rows_BT": dict(seed=table(B * T)), "c_speculative": dict(seed=dict(limit=args.steps, lookup=None)),
+                     "f_speculative_rows": dict(seed=dict(limit=args.steps, lookup=None, rows=table(B)))}
+            legs = {}
+            for name, plan in plans.items():
+                rows = B if plan.is_speculate else B * T
+                o = model.lm(inputs_embeds=prompts(B).repeat_interleave(rows // B, 0), use_cache=True, cache_hint=args.steps + T + 8,
+                             eos_token=eos, plan=plan, lengths=torch.full((rows,), S0, dtype=torch.int64), **seeds[name])
+                legs[name] = (o.past_key_values, plan)
+                for _ in range(3):        # eager, capture, replay
+                    eng.decode(None, o.past_key_values, plan=plan)
+            assert len({id(c) for c, _ in legs.values()}) == 4
+
+            def reset_rows(cache, plan):
+                cache.pos = S0
+                cache.d_pos.fill_(S0)
+                cache.sample_state.copy_(torch.tensor([0, -1], dtype=torch.int32))
+                cache.finish.copy_(torch.tensor([[-1, 0]] * cache.B, dtype=torch.int32))
+                if plan.is_speculate:
+                    st = cache.spec[T]
+                    for t in (st.n_draft, st.count, st.stats, st.ids):
+                        t.zero_()
+            ms = {name: [] for name in legs}
+            for _ in range(args.reps):
+                for name, (cache, plan) in legs.items():
+                    reset_rows(cache, plan)
+                    torch.cuda.synchronize()
+                    e0.record()
+                    for _ in range(args.steps):
+                        eng.decode(None, cache, plan=plan)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    ms[name].append(round(e0.elapsed_time(e1) / args.steps, 4))
+            m = {name: med(v) for name, v in ms.items()}
+            spread = {name: round(max(v) - min(v), 4) for name, v in ms.items()}
+            emit({"case": "step_sampled", "config": args.config, "layers": eng.L, "prompt_rows": S0, "B": B, "T": T, "rows": B * T,
+                  "steps_per_window": args.steps, "windows": args.reps, "ms_per_step_all": ms, "ms_per_step_median": m,
+                  "spread_ms": spread, "e_minus_b_ms": round(m["e_plain_rows_BT"] - m["b_plain_BT"], 4),
+                  "f_minus_c_ms": round(m["f_speculative_rows"] - m["c_speculative"], 4),
+                  "last_window_stats_steps_drafted_accepted": legs["f_speculative_rows"][0].spec[T].stats.cpu().tolist()})
+            legs.clear()
+            torch.cuda.empty_cache()
+
         # ---- the chunk launch alone against T single-query launches
         if "attn" not in skip:
             B, T, H, Smax = 2, 8, eng.H, 2112
@@ -200,6 +257,35 @@ def main():
             for T in (4, 8):
                 for name, lookup in (("lookup_answer", answer), ("lookup_none", None)):
                     ts, (got, sp) = timed(prompt_lookup_num_tokens=T - 1, lookup_ids=lookup, return_speculation=True)
+                    line[f"T{T}_{name}"] = {"tokens_per_s": round(B * n / statistics.median(ts), 1), "s_all": [round(t, 5) for t in ts],
+                                            "equals_plain": bool(torch.equal(got, ref)), "steps": sp.steps.tolist(),
+                                            "drafted": sp.drafted.tolist(), "accepted": sp.accepted.tolist()}
+            emit(line)
+
+        # ---- end to end, sampled rows: the plain per-row sampled call, then its own output as the lookup text (seed-exact: the ceiling)
+        for B in ([] if "e2e_sampled" in skip else (1, 2)):
+            emb, n = prompts(B), args.tokens
+            kw = dict(max_steps=n, temperature=[0.7] * B, top_p=[0.9] * B, seed=list(range(11, 11 + B)), decode=False, eos_token=[eos],
+                      stop_per_row=True, stop_on_eos=False)
+            ref = generate(model, emb, **kw)
+            answer = [ref[b, S0:].tolist() for b in range(B)]
+
+            def timed_rows(**more):
+                generate(model, emb, **kw, **more)                      # warm-up: allocation, capture
+                ts, last = [], None
+                for _ in range(args.reps):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    last = generate(model, emb, **kw, **more)
+                    torch.cuda.synchronize()
+                    ts.append(time.perf_counter() - t0)
+                return ts, last
+            t_plain, _ = timed_rows()
+            line = {"case": "e2e_sampled", "B": B, "new_tokens": n, "prompt_rows": S0, "layers": eng.L, "temperature": 0.7, "top_p": 0.9,
+                    "plain_tokens_per_s": round(B * n / statistics.median(t_plain), 1), "plain_s_all": [round(t, 5) for t in t_plain]}
+            for T in (4, 8):
+                for name, lookup in (("lookup_answer", answer), ("lookup_none", None)):
+                    ts, (got, sp) = timed_rows(prompt_lookup_num_tokens=T - 1, lookup_ids=lookup, return_speculation=True)
                     line[f"T{T}_{name}"] = {"tokens_per_s": round(B * n / statistics.median(ts), 1), "s_all": [round(t, 5) for t in ts],
                                             "equals_plain": bool(torch.equal(got, ref)), "steps": sp.steps.tolist(),
                                             "drafted": sp.drafted.tolist(), "accepted": sp.accepted.tolist()}
